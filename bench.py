@@ -8,7 +8,12 @@ into HBM.  (The work plan -- gap / centromere segments, runs, the longest-first 
 first call and stays resident; the timed passes, which repeat its arguments, only enqueue the two kernels.)
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|ns|c3w100|small] [--mode lod|wlod|tgls]
-                    [--also auto|none|leg,leg..] [--no-cpu]
+                    [--dump-outputs DIR] [--full [--also auto|none|leg,leg..] [--no-cpu]]
+
+A plain run sets up (panel, score buffer), warms up, times the K steps, writes the scores of the last step if
+--dump-outputs is given, and prints the line.  Everything else it measures or checks -- the CPU baseline and bit
+check, one plain hipMalloc buffer beside the placement candidates, the `also` legs, and at N > 1 rank 0's solo run
+and every rank's bit check -- runs only with --full.
 
 N = 1 (default): the workload BASELINE.json's metric is quoted on, configs[1] (C2: 1M SNPs x 1000
 individuals, --winsize 100, unweighted).  N > 1 is launched by the driver through torch.distributed.run, one
@@ -18,7 +23,7 @@ owns all SNPs of its individuals (weak scaling); there is no collective on the d
 barrier, and with --mode wlod one integer all-reduce of the LD pair counts before the timed region.
 
 Rank 0 prints ONE JSON line.  `roofline` prices the dominant kernel against its bound with the kernel's
-HIP-event time measured live on the stream it runs on; `cpu_baseline` times the reference's own calcLOD
+HIP-event time measured live on the stream it runs on; with --full, `cpu_baseline` times the reference's own calcLOD
 (oracle/_ref, built from the reference sources in the build container) or, if that library is absent, the C
 port in oracle/, on a bounded sample of the same panel on the host cores -- and the GPU scores of those
 individuals are compared with it bit for bit.  At N = 1 the line also carries, under `also`, the other
@@ -530,6 +535,41 @@ def leg_end_to_end(ctx, dev):
             "feed_only": {"call_s": t_feed, "value": win / W / t_feed, "unit": "LOD-windows/s", "feed_values": int(feed.shape[0])}}
 
 
+DUMP_ROWS, DUMP_ROW_SNPS, DUMP_SAMPLE = 3, 1 << 20, 2_000_000     # 24 + 16 + 16 MB of float64 per run at most
+
+
+def dump_outputs(dirname, out, base, pitch, spec, nind, rank, world):
+    """The scores the last timed step left in `out` -- [individual][SNP] rows per chromosome, `pitch` apart from
+    `base` on (what the timed path hands its caller) -- as float64 .npy files in `dirname`.  A whole matrix is GBs, so
+    a fixed sample that depends on the shape alone: scores_rows = DUMP_ROWS individuals spread over the panel, their
+    first DUMP_ROW_SNPS SNPs (across chromosome ends); scores_sample = DUMP_SAMPLE (individual, SNP) cells drawn with a
+    fixed seed, ascending in individual * nloci + SNP, which scores_sample_index holds.  At N > 1 every rank writes
+    its own shard (file names end in _rank<r>) and the sizes shrink by N."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    nloci = spec.nloci
+    snp = np.arange(nloci, dtype=np.int64)
+    chrom = np.searchsorted(spec.chr_off, snp, side="right") - 1
+    snp_base = base[chrom] + snp - spec.chr_off[chrom]           # offset of individual 0's score at each SNP
+
+    def gather(flat):                                            # flat = individual * nloci + SNP
+        ind, s = np.divmod(flat, nloci)
+        off = snp_base[s] + ind * pitch[chrom[s]]
+        assert off.min() >= 0 and off.max() < out.numel(), "dump index outside the score buffer"
+        return out.index_select(0, torch.from_numpy(off).to(out.device)).cpu().numpy().astype(np.float64)
+
+    suffix = "" if world == 1 else "_rank%d" % rank
+    rows = np.unique(np.linspace(0, nind - 1, max(1, DUMP_ROWS // world)).astype(np.int64))
+    ncol = min(nloci, DUMP_ROW_SNPS)
+    flat = (rows[:, None] * nloci + np.arange(ncol, dtype=np.int64)[None, :]).ravel()
+    np.save(os.path.join(dirname, "scores_rows%s.npy" % suffix), gather(flat).reshape(len(rows), ncol))
+    n = nloci * nind
+    draw = np.random.default_rng(20260101).integers(0, n, size=min(n, DUMP_SAMPLE // world), dtype=np.int64)
+    flat = np.unique(draw)
+    np.save(os.path.join(dirname, "scores_sample%s.npy" % suffix), gather(flat))
+    np.save(os.path.join(dirname, "scores_sample_index%s.npy" % suffix), flat.astype(np.float64))
+
+
 def self_launch(n):
     """python bench.py --gpus N without torch.distributed.run: the same command under the launcher, as a child"""
     import socket
@@ -557,9 +597,14 @@ def main():
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--out-candidates", type=int, default=8,
                     help="score buffers to try for the timed passes (placement in VRAM changes the kernel time)")
-    ap.add_argument("--also", default="auto", help="auto | none | comma list of c3,ns,e2e (N = 1 only)")
+    ap.add_argument("--also", default="auto", help="auto | none | comma list of c3,ns,e2e (N = 1 and --full only)")
     ap.add_argument("--also-budget-s", type=float, default=330.0,
                     help="no further `also` leg is started once the run has taken this long")
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline does not need: CPU baseline and bit check, one plain hipMalloc buffer, "
+                         "the `also` legs, rank 0's solo run at N > 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a fixed sample of the scores of the last timed step to DIR/*.npy (float64)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -603,7 +648,7 @@ def main():
     # CPU baseline: N = 1: the bounded sample of SURVEY 8(d) on rank 0.  N > 1: EVERY rank keeps a few of its own
     # individuals on the host and checks their scores bit for bit against the CPU path after the timed region (a
     # few seconds: the others wait for nobody longer than that); rank 0's timing of it is the line's cpu_baseline
-    if args.no_cpu or args.mode != "lod":
+    if not args.full or args.no_cpu or args.mode != "lod":
         n_cpu = 0
     elif world > 1:
         n_cpu = min(args.cpu_inds_multi, nind)
@@ -618,7 +663,7 @@ def main():
     # buffers it is asked for: garlic_panel_alloc_scores allocates a few candidates, times the real kernel into each
     # and keeps the fastest (its own host-output scratch is chosen the same way), which is what this bench -- like any
     # caller that follows INTEGRATION.md -- uses.  Every candidate's time is reported, with the fractions of the
-    # median and the worst candidate and of one plain hipMalloc buffer beside the headline.
+    # median and the worst candidate (and, with --full, of one plain hipMalloc buffer) beside the headline.
     placement = None
     n_cand = 1 if (args.out_candidates <= 1 or total * 8 * args.out_candidates > (96 << 30) or args.mode != "lod") else args.out_candidates
 
@@ -631,25 +676,28 @@ def main():
         return float(np.mean(ctx.recent_kernel_ms(3)))
 
     if n_cand > 1:
-        # (one plain hipMalloc buffer first, for comparison; nothing is allocated or released between the library's choice
-        # and the timed region)
-        plain = torch.empty(total, dtype=torch.float64, device=dev)
-        torch.cuda.synchronize()
-        plain_ms = three_passes(plain.data_ptr())
-        del plain
-        torch.cuda.empty_cache()
+        # (--full: one plain hipMalloc buffer first, for comparison; nothing is allocated or released between the library's
+        # choice and the timed region)
+        plain_ms = None
+        if args.full:
+            plain = torch.empty(total, dtype=torch.float64, device=dev)
+            torch.cuda.synchronize()
+            plain_ms = three_passes(plain.data_ptr())
+            del plain
+            torch.cuda.empty_cache()
         ctx.set_async(False)
         out_buf, times = panel.alloc_scores(W, ERROR, MAX_GAP, pitch_align=PITCH_ALIGN, nind_out=nind, candidates=n_cand)
         ctx.set_async(True)
         out = out_buf.tensor()
         placement = {"candidates_kernel_ms": times, "kept_ms": float(min(times)),
                      "median_ms": float(np.median(times)), "worst_ms": float(max(times)),
-                     "one_plain_hipmalloc_buffer_ms": plain_ms,
                      "drawn": panel.alloc_scores_info(),
                      "note": "garlic_panel_alloc_scores: candidates from the library's pooled allocator side by side, the real "
                              "kernel timed into each (passes enqueued back to back, the last three of five), fastest kept -- the buffer the "
                              "timed region writes; rounds of candidates are drawn until one takes its bytes at 0.74 of the HBM peak or three "
                              "rounds / 2 s are spent (`drawn`; candidates_kernel_ms: the round the kept buffer came from)"}
+        if plain_ms is not None:
+            placement["one_plain_hipmalloc_buffer_ms"] = plain_ms
     else:
         out_buf = ctx.alloc_scores(total)
         out = out_buf.tensor()
@@ -704,7 +752,7 @@ def main():
         step()
     torch.cuda.synchronize()
     solo_elapsed = None
-    if world > 1:
+    if world > 1 and args.full:
         # rank 0 alone first, the other GPUs idle: the same K steps of the same shard, so that the joint line can be
         # read against a one-GPU point of the SAME workload (no collective on the data path: expect joint = solo;
         # what is missing is host, power or PCIe, not the kernels)
@@ -740,6 +788,8 @@ def main():
     if os.environ.get("GARLIC_BENCH_DEBUG"):
         print("debug: kernel ms of the timed steps:", [round(x, 3) for x in kernel_ms], file=sys.stderr)
     st = panel.stats()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, base, pitch, spec, nind, rank, world)
     # the bit check: this rank's first n_cpu individuals against the CPU path (reference build if present, else the port)
     cpu = None
     if n_cpu:
@@ -755,7 +805,7 @@ def main():
         cpu = cpu_baseline(spec, geno_sample, W, rows, seconds_budget=25.0 if world == 1 else 4.0, all_cores=(world == 1))
         del host, rows
     mism_by_rank = None
-    if world > 1:
+    if world > 1 and args.full:
         m = torch.tensor([cpu["gpu_bit_mismatches_on_sample"] if cpu else -1, cpu["values_compared"] if cpu else 0],
                          dtype=torch.int64, device="cpu" if rehearse else dev)
         g = [torch.zeros_like(m) for _ in range(world)]
@@ -798,6 +848,7 @@ def main():
         }
         if per_rank is not None:
             res["ms_per_step_by_rank"] = per_rank
+        if solo_elapsed is not None:
             solo_value = nloci * nind / W * args.steps / solo_elapsed
             res["per_gpu_value"] = res["value"] / world
             res["solo_value_rank0"] = solo_value
@@ -816,7 +867,8 @@ def main():
                 alg = BYTES_LOD * win_rank
                 for key, name in (("median_ms", "frac_median"), ("worst_ms", "frac_worst"),
                                   ("one_plain_hipmalloc_buffer_ms", "frac_one_plain_hipmalloc_buffer")):
-                    res["roofline"][name] = alg / (placement[key] * 1e-3) / 1e9 / res["roofline"]["peak"]
+                    if key in placement:
+                        res["roofline"][name] = alg / (placement[key] * 1e-3) / 1e9 / res["roofline"]["peak"]
                 res["roofline"]["placement_note"] = ("frac: the buffer garlic_panel_alloc_scores kept (what a caller of the library "
                                                      "gets); frac_median / frac_worst: the median / worst of its candidates")
         res["cpu_baseline"] = cpu
@@ -829,7 +881,7 @@ def main():
     torch.cuda.empty_cache()
     ctx.trim()
 
-    if rank == 0 and world == 1 and args.also != "none":
+    if args.full and rank == 0 and world == 1 and args.also != "none":
         want = ["e2e", "ns", "c3"] if args.also == "auto" else [x for x in args.also.split(",") if x]
         also = {}
         ctx.set_async(True)

@@ -6,7 +6,7 @@ O=gpurun_out/r4; mkdir -p $O
 N=${N:-8}
 : > $O/placement_runs.jsonl
 for i in $(seq 1 $N); do
-  timeout -k 10 200 python bench.py --steps 20 --warmup 5 --no-cpu --also none 2>> $O/placement_runs.err >> $O/placement_runs.jsonl || break
+  timeout -k 10 200 python bench.py --steps 20 --warmup 5 --full --no-cpu --also none 2>> $O/placement_runs.err >> $O/placement_runs.jsonl || break
 done
 python - <<'PY'
 import json
@@ -14,7 +14,7 @@ rows = [json.loads(l) for l in open("gpurun_out/r4/placement_runs.jsonl") if l.s
 out = open("gpurun_out/r4/placement_hit_rate.txt", "w")
 def p(*a):
     s = " ".join(str(x) for x in a); print(s); out.write(s + "\n")
-p("# tools/exp/r4_placement_hit_rate.sh: %d fresh processes of `python bench.py --steps 20 --warmup 5 --no-cpu --also none` on one MI355X" % len(rows))
+p("# tools/exp/r4_placement_hit_rate.sh: %d fresh processes of `python bench.py --steps 20 --warmup 5 --full --no-cpu --also none` on one MI355X" % len(rows))
 p("# (C2: 1M SNPs x 1000 individuals, W = 100, 8.25 GB per pass).  ms = HIP-event time of lod_chain_kernel; frac = of 8 TB/s.")
 p("# kept: the buffer garlic_panel_alloc_scores kept (what the timed region writes); median / worst: over the candidates of the kept")
 p("# buffer's round; plain: one hipMalloc buffer; drawn / rounds: candidates timed until one reached 0.74 of the HBM peak (1.394 ms) or")

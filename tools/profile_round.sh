@@ -8,7 +8,7 @@ TAG=${1:-r02}
 export TMPDIR=/tmp
 OUT=$PWD/gpurun_out
 mkdir -p $OUT
-python3 bench.py --steps 20 --warmup 5 > $OUT/${TAG}_bench_plain.json 2> $OUT/${TAG}_bench_plain.err
+python3 bench.py --steps 20 --warmup 5 --full > $OUT/${TAG}_bench_plain.json 2> $OUT/${TAG}_bench_plain.err
 echo "plain bench done"
 ARGS="bench.py --steps 20 --warmup 5 --no-cpu --also none"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_trace -- python3 $ARGS > $OUT/${TAG}_trace_bench.json 2> $OUT/${TAG}_trace.err
