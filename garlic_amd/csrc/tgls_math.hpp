@@ -43,9 +43,10 @@ GARLIC_HD uint64_t f64_bits(double d)
     return u;
 }
 
-// x86's default NaN (what 0/0, inf-inf, (x-x)/(x-x) produce there): sign bit set.  gfx950 produces
-// +NaN for the same operations, so invalid operations are canonicalised to this wherever the
-// reference's arithmetic would have produced the x86 one.
+// x86's default NaN (what 0/0, inf-inf, (x-x)/(x-x) produce there): sign bit set.  gfx950 can
+// produce +NaN for these operations, so invalid operations are canonicalised to this wherever the
+// reference's arithmetic would have produced the x86 one.  (The inf-inf of the chains' rolling sums,
+// v_add_f64, gives this NaN as it is: tests/test_gpu_window_regimes.py, --error 0.)
 constexpr uint64_t X86_DEFAULT_NAN = 0xFFF8000000000000ull;
 
 // __log_fma for finite positive normal x in [0.5, 2) -- all log10 passes it.  tab: 128 x {invc, logc}.
