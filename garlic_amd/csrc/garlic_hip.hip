@@ -28,6 +28,7 @@
 #include <cstring>
 #include <string>
 #include <thread>
+#include <tuple>
 #include <unordered_map>
 #include <vector>
 
@@ -59,9 +60,17 @@ int fail(int code, const char *fmt, ...)
 
 int score_pool_trim();    // idle score buffers (garlic_device_free keeps them mapped) give their memory back
 
-template <class T> struct DevBuf {
+struct NoCopy {
+    NoCopy() = default;
+    NoCopy(const NoCopy &) = delete;
+    NoCopy &operator=(const NoCopy &) = delete;
+};
+
+// owns its memory: released when it leaves scope (a scope with work in flight that reads it synchronises first)
+template <class T> struct DevBuf : NoCopy {
     T *p = nullptr;
     size_t cap = 0;
+    ~DevBuf() { release(); }
     int reserve(size_t n)
     {
         if (n <= cap) return GARLIC_OK;
@@ -78,6 +87,13 @@ template <class T> struct DevBuf {
         }
         HIP_TRY(hipMalloc(reinterpret_cast<void **>(&p), n * sizeof(T)));
         cap = n;
+        return GARLIC_OK;
+    }
+    int put(const std::vector<T> &h, hipStream_t s)      // room for a host list and the list on its way there (an empty one: nothing)
+    {
+        int rc = h.empty() ? GARLIC_OK : reserve(h.size());
+        if (rc || h.empty()) return rc;
+        HIP_TRY(hipMemcpyAsync(p, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice, s));
         return GARLIC_OK;
     }
     void release()
@@ -150,9 +166,10 @@ static int score_alloc(garlic_ctx *ctx, size_t bytes, void **out);   // pooled s
 static int score_free(garlic_ctx *ctx, void *ptr);
 
 // per-call scratch from the score pool (freed buffers stay mapped there: the next call's request costs no hipMalloc)
-template <class T> struct PoolBuf {
+template <class T> struct PoolBuf : NoCopy {
     T *p = nullptr;
     garlic_ctx *ctx = nullptr;
+    ~PoolBuf() { release(); }
     int reserve(garlic_ctx *c, size_t n)
     {
         release();
@@ -318,16 +335,19 @@ struct garlic_panel {
     Placement placement;                           // the last garlic_panel_alloc_scores on this panel
     // work list of the last call, still on the device: repeated calls with the same arguments
     // (bench steps, window-size sweeps coming back to a size) skip planning and uploads
-    struct {
-        bool valid = false;
+    struct PlanKey {              // what a plan depends on: compared and stored whole
         int mode = -1;
-        int32_t W = 0, max_gap = 0, ind_begin = 0, ind_count = 0, pitch_align = 0;
-        size_t n_items = 0, n_fill = 0;
-        bool wlod_fast = false, wlod_strip = false, feed_kernel = false;
-        int32_t thin_step = 0;
-        size_t n_feed_items = 0;
-        int feed_per_cu = 1;      // persistent workgroups per CU the feed kernel of this plan is launched with (feed_grid)
+        int32_t W = 0, max_gap = 0, ind_begin = 0, ind_count = 0, pitch_align = 0, thin_step = 0;
         uint64_t blocks_hash = 0;                  // 0: every 64-individual block; else a hash of the block subset
+        bool wlod_tuned = false, wlod_strip = false, feed_kernel = false;
+        auto tie() const { return std::tie(mode, W, max_gap, ind_begin, ind_count, pitch_align, thin_step, blocks_hash, wlod_tuned, wlod_strip, feed_kernel); }
+        bool operator==(const PlanKey &o) const { return tie() == o.tie(); }
+    };
+    struct Plan {
+        bool valid = false;
+        PlanKey key;
+        size_t n_items = 0, n_fill = 0, n_feed_items = 0;
+        int feed_per_cu = 1;      // persistent workgroups per CU the feed kernel of this plan is launched with (feed_grid)
         int32_t n_tiles = 0, n_segs = 0, n_strips = 0;
         int64_t n_runs = 0, n_valid = 0;
     } plan;
@@ -562,10 +582,7 @@ int ensure_term_table(garlic_panel *p, double error)
             t[l * 4 + 3] = host_lod(-9, freq[l], error);
         }
     });
-    int rc;
-    if ((rc = p->d_tab.reserve((size_t)rows * 4))) return rc;
-    HIP_TRY(hipMemcpyAsync(p->d_tab.p, tab.data(), sizeof(double) * rows * 4, hipMemcpyHostToDevice,
-                           p->ctx->stream));
+    if (int rc = p->d_tab.put(tab, p->ctx->stream)) return rc;
     HIP_TRY(hipStreamSynchronize(p->ctx->stream));
     p->tab_valid = true;
     p->tab_error = error;
@@ -610,6 +627,15 @@ Layout make_layout(const garlic_panel *p, int32_t pitch_align, int32_t nind_out,
 struct Run {
     int32_t chr, a, b;
 };
+
+// run indices, longest run first (LPT); a stable sort: ties keep chromosome and position order, and the order reaches the device
+std::vector<int> longest_first(const std::vector<Run> &runs)
+{
+    std::vector<int> order(runs.size());
+    for (size_t i = 0; i < runs.size(); i++) order[i] = (int)i;
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return (runs[x].b - runs[x].a) > (runs[y].b - runs[y].a); });
+    return order;
+}
 
 // segments -> maximal runs of valid windows for one window size, and the MISSING stretches
 void plan_runs(const garlic_panel *p, int32_t W, std::vector<Run> &runs, std::vector<FillItem> &fill,
@@ -773,10 +799,7 @@ int ensure_gl_table(garlic_panel *p)
                 e[3] = host_lod(-9, freq[l], val[c]);
             }
     });
-    int rc;
-    if ((rc = p->d_tabgl.reserve(tab.size()))) return rc;
-    HIP_TRY(hipMemcpyAsync(p->d_tabgl.p, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice,
-                           p->ctx->stream));
+    if (int rc = p->d_tabgl.put(tab, p->ctx->stream)) return rc;
     HIP_TRY(hipStreamSynchronize(p->ctx->stream));
     p->tabgl_valid = true;
     p->tabgl_ncodes = ncodes;
@@ -821,8 +844,7 @@ int ensure_log10(garlic_ctx *ctx)
     }
     const int64_t n = (int64_t)in.size();
     DevBuf<double> d_in, d_out;
-    auto done = [&](int code) { d_in.release(); d_out.release(); return code; };
-    if ((rc = d_in.reserve((size_t)n)) || (rc = d_out.reserve((size_t)n))) return done(rc);
+    if ((rc = d_in.reserve((size_t)n)) || (rc = d_out.reserve((size_t)n))) return rc;
     std::vector<double> out((size_t)n);
     hipError_t e = hipMemcpyAsync(d_in.p, in.data(), sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) {
@@ -831,7 +853,7 @@ int ensure_log10(garlic_ctx *ctx)
     }
     if (e == hipSuccess) e = hipMemcpyAsync(out.data(), d_out.p, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return done(fail(GARLIC_ERR_HIP, "log10 probe: %s", hipGetErrorString(e)));
+    if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "log10 probe: %s", hipGetErrorString(e));
     int64_t bad = 0;
     for (int64_t i = 0; i < n; i++) {
         const double want = log10(in[(size_t)i]);
@@ -842,7 +864,7 @@ int ensure_log10(garlic_ctx *ctx)
         fprintf(stderr, "libgarlic_hip: the host's log10 is not the glibc 2.35 FMA variant the device restates "
                         "(%lld of %lld probes differ); continuous TGLS terms will be computed on the host\n",
                 (long long)bad, (long long)n);
-    return done(GARLIC_OK);
+    return GARLIC_OK;
 }
 
 // allele frequencies on the device, in padded row order (pad rows 0 -> term +0.0)
@@ -852,9 +874,7 @@ int ensure_dfreq(garlic_panel *p)
     const int64_t rows = GOFF + p->nloci + GPAD_BACK;
     std::vector<double> f((size_t)rows, 0.0);
     memcpy(f.data() + GOFF, p->freq.data(), sizeof(double) * (size_t)p->nloci);
-    int rc;
-    if ((rc = p->d_freq.reserve((size_t)rows))) return rc;
-    HIP_TRY(hipMemcpyAsync(p->d_freq.p, f.data(), sizeof(double) * rows, hipMemcpyHostToDevice, p->ctx->stream));
+    if (int rc = p->d_freq.put(f, p->ctx->stream)) return rc;
     HIP_TRY(hipStreamSynchronize(p->ctx->stream));
     p->dfreq_valid = true;
     return GARLIC_OK;
@@ -885,7 +905,6 @@ int switch_to_continuous(garlic_panel *p)
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipStreamSynchronize(s);
-        d_dict.release();
         if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "set_gl: %s", hipGetErrorString(e));
     } else {
         HIP_TRY(hipMemsetAsync(p->d_glval.p, 0, sizeof(double) * n, s));
@@ -1050,7 +1069,6 @@ int ensure_gl_terms(garlic_panel *p, bool scaled = false, int32_t M = 0, double 
             hipLaunchKernelGGL(min_finite_kernel, dim3(NB), dim3(256), 0, s, p->d_glterms.p, (int64_t)n, d_part.p);
             hipError_t e = hipMemcpyAsync(part, d_part.p, sizeof part, hipMemcpyDeviceToHost, s);
             if (e == hipSuccess) e = hipStreamSynchronize(s);
-            d_part.release();
             if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "term minimum: %s", hipGetErrorString(e));
             p->glterms_min = min_finite(part, NB);
         }
@@ -1131,10 +1149,7 @@ int ensure_decay_table(garlic_panel *p, int32_t M, double mu)
             dec[(GOFF + l) * 2 + 0] = exp(-2.0 * Md * mu * dP);
             dec[(GOFF + l) * 2 + 1] = exp(-2.0 * Md * 1 * dG);
         }
-    int rc;
-    if ((rc = p->d_decay.reserve(dec.size()))) return rc;
-    HIP_TRY(hipMemcpyAsync(p->d_decay.p, dec.data(), sizeof(double) * dec.size(), hipMemcpyHostToDevice,
-                           p->ctx->stream));
+    if (int rc = p->d_decay.put(dec, p->ctx->stream)) return rc;
     HIP_TRY(hipStreamSynchronize(p->ctx->stream));
     p->decay_valid = true;
     p->decay_M = M;
@@ -1160,493 +1175,555 @@ int ensure_score_rows(garlic_panel *p, double error, int32_t M, double mu, int32
         for (int64_t G = lo; G < hi; G++)
             for (int g = 0; g < 4; g++) wp[G * 4 + g] = (t[G * 4 + g] * d[2 * G]) * d[2 * G + 1];
     });
-    int rc;
-    if ((rc = p->d_wtab.reserve(w.size()))) return rc;
-    HIP_TRY(hipMemcpyAsync(p->d_wtab.p, w.data(), sizeof(double) * w.size(), hipMemcpyHostToDevice,
-                           p->ctx->stream));
+    if (int rc = p->d_wtab.put(w, p->ctx->stream)) return rc;
     HIP_TRY(hipStreamSynchronize(p->ctx->stream));
     p->wtab_valid = true;
     p->wtab_error = error; p->wtab_M = M; p->wtab_mu = mu; p->wtab_rows = rows;
     return GARLIC_OK;
 }
 
-// thin_step > 0 (unweighted scores, device output, pitch_align 32 only): `out` is the thinned matrix
-// of make_layout(p, 32, ind_count, thin_step) -- the chain kernel stores only the windows at loci
-// 0, thin_step, 2 * thin_step, .. of each chromosome, everything else of that matrix is MISSING.
-int launch_lod(garlic_panel *p, Mode mode, int32_t W, double error, int32_t max_gap, int32_t M, double mu,
-               int32_t ind_begin, int32_t ind_count, int32_t pitch_align, double *out, int32_t where,
-               int32_t thin_step = 0, const std::vector<uint8_t> *blocks = nullptr)
-{   // blocks (chain kernels only): per 64-individual block of the call, 1 = score it; rows of the other
-    // blocks are left unwritten (the subset feed never reads them)
-    garlic_ctx *ctx = p->ctx;
-    int rc;
-    if ((rc = set_device(ctx))) return rc;
-    if (W <= 1) return fail(GARLIC_ERR_INVALID, "SNP window size must be > 1 (got %d)", W);
+// ---- A score call, step by step: arguments (LodCall) -> kernel form (LodForm) -> work lists (LodWork, counted in the
+// panel's plan) -> score buffer -> launches (enqueue_lod) -> by-value -9999 rescan -> copy out -> statistics.
+struct LodCall {
+    Mode mode;
+    int32_t W, max_gap, M, ind_begin, ind_count, pitch_align, thin_step, where, host_pitch_align;     // pitch_align: of the device layout
+    double error, mu, *out;
+    const std::vector<uint8_t> *blocks;
+};
+
+// Which kernel takes the call and what that needs: filled once by decide_form, then by finish_form with what depends on the
+// score buffer.  Everything after reads it: no later code looks at W, the mode or the environment to pick a kernel.
+enum class Family { chain, feed, exact, tgls_ring, tgls_terms, tgls_lookup, wlod_tile, wlod_tile2, wlod_tile_gl, wlod_glring,
+                    wlod_small_tiles, wlod_stream, wlod_strip, wlod_generic };
+
+struct LodForm {
+    Family family = Family::chain;
+    bool use_gl = false;
+    bool exact_possible = false;   // a window can sum to exactly -9999.0: rescan, and Family::exact if one did
+    bool cov_bits = false;         // coverage bits instead of scores (garlic_panel::cov_pending); `out` is no score buffer then
+    bool writes_bits = false;      // ... and this family can write them
+    bool wlod_tuned = false;       // a tuned wLOD kernel: reads the plan's valid mask, tiles, segments; writes MISSING itself
+    bool wlod_gl = false;          // ... with its scores from the scaled term matrix
+    int strip_waves = 0;           // wlod_strip: compute waves per workgroup
+    bool use_patch = false, no_prefetch = false, feed_asm = true, strip_force_rerun = false;
+    size_t tile_lds = 0;           // dynamic LDS of the tile kernels
+    bool aligned16 = false;        // finish_form: every score row 16-byte aligned
+    bool strip_three = false;      // finish_form: the 80-VGPR strip kernel, three workgroups per CU
+};
+
+int check_lod_args(const garlic_panel *p, const LodCall &c)
+{
+    if (c.W <= 1) return fail(GARLIC_ERR_INVALID, "SNP window size must be > 1 (got %d)", c.W);
     if (!p->have_map || !p->have_freq || !p->have_geno)
         return fail(GARLIC_ERR_STATE, "panel needs map, freq and genotypes before computing LOD");
-    if (ind_begin < 0 || ind_count < 1 || (int64_t)ind_begin + ind_count > p->nind)
-        return fail(GARLIC_ERR_INVALID, "individual range [%d,+%d) outside panel of %d", ind_begin,
-                    ind_count, p->nind);
-    if (!out) return fail(GARLIC_ERR_INVALID, "out is NULL");
-    if (pitch_align < 1) return fail(GARLIC_ERR_INVALID, "pitch_align must be >= 1");
-    const bool use_gl = (mode == MODE_LOD_GL) || (mode == MODE_WLOD && p->wlod_use_gl);
-    if (thin_step > 0 && (mode != MODE_LOD || where != GARLIC_DEVICE || pitch_align != 32))
+    if (c.ind_begin < 0 || c.ind_count < 1 || (int64_t)c.ind_begin + c.ind_count > p->nind)
+        return fail(GARLIC_ERR_INVALID, "individual range [%d,+%d) outside panel of %d", c.ind_begin,
+                    c.ind_count, p->nind);
+    if (!c.out) return fail(GARLIC_ERR_INVALID, "out is NULL");
+    if (c.host_pitch_align < 1) return fail(GARLIC_ERR_INVALID, "pitch_align must be >= 1");
+    if (c.thin_step > 0 && (c.mode != MODE_LOD || c.where != GARLIC_DEVICE || c.host_pitch_align != 32))
         return fail(GARLIC_ERR_INVALID, "internal: thinned output is for unweighted device scores");
+    return GARLIC_OK;
+}
 
-    if ((rc = ensure_segments(p, max_gap))) return rc;
-    if (use_gl) {
+// Shape from the arguments and the switches -> the ensure_* that shape asks for -> the form from what the panel now holds.
+int decide_form(garlic_panel *p, const LodCall &c, LodForm &f)
+{
+    const Mode mode = c.mode;
+    const int32_t W = c.W;
+    int rc;
+    f.use_gl = (mode == MODE_LOD_GL) || (mode == MODE_WLOD && p->wlod_use_gl);
+    if ((rc = ensure_segments(p, c.max_gap))) return rc;
+    if (f.use_gl) {
         if (!p->have_gl) return fail(GARLIC_ERR_STATE, "use_gl set but no genotype likelihoods were given");
         if (!p->gl_cont && (rc = ensure_gl_table(p))) return rc;
         if (mode == MODE_LOD_GL && (rc = ensure_gl_terms(p))) return rc;
-    } else if ((rc = ensure_term_table(p, error))) return rc;
+    } else if ((rc = ensure_term_table(p, c.error))) return rc;
     if (mode == MODE_WLOD) {
         if (!p->have_ld || p->ld_winsize != W)
             return fail(GARLIC_ERR_STATE, "wLOD needs LD weights for winsize %d (garlic_panel_set_ld)", W);
-        if ((rc = ensure_decay_table(p, M, mu))) return rc;
+        if ((rc = ensure_decay_table(p, c.M, c.mu))) return rc;
     }
-    // tuned wLOD kernels: 16 window accumulators per lane; scores from one LDS row per SNP (plain
-    // --error) or from the TGLS score matrix (use_gl); very narrow / very wide windows keep the
-    // generic kernel
     // A window sum of exactly -9999.0 is possible (lod_exact_needed): the tuned chain runs first, its scored windows
     // are scanned for that value, and only if one is there the chain that follows the reference to the letter
     // (11-17 x slower) runs instead.  GARLIC_EXACT_CHAIN_ONLY: that chain straight away.
-    const bool exact_possible = mode != MODE_WLOD && lod_exact_needed(p, mode, W);
-    bool exact = exact_possible && getenv("GARLIC_EXACT_CHAIN_ONLY") != nullptr;
-    if (exact_possible && thin_step > 0) return fail(GARLIC_ERR_INVALID, "internal: thinned output with the exact chain");
+    f.exact_possible = mode != MODE_WLOD && lod_exact_needed(p, mode, W);
+    if (f.exact_possible && c.thin_step > 0) return fail(GARLIC_ERR_INVALID, "internal: thinned output with the exact chain");
     // coverage bits instead of scores (garlic_roh_coverage_fused): only the kernels that know how; nothing else may touch
     // `out` (it is not a score buffer then)
-    const bool cov_bits = p->cov_pending.bits != nullptr;
-    if (cov_bits && mode == MODE_LOD)
+    f.cov_bits = p->cov_pending.bits != nullptr;
+    if (f.cov_bits && mode == MODE_LOD)
         return fail(GARLIC_ERR_STATE, "internal: coverage bits of the unweighted --error scores come from lod_bits_kernel");
-    if (cov_bits && mode == MODE_LOD_GL &&
-        (exact_possible || where != GARLIC_DEVICE || (ind_begin & (WAVE - 1)) != 0 || getenv("GARLIC_TGLS_NO_RING")))
+    const bool tgls_ring_shape = (c.ind_begin & (WAVE - 1)) == 0 && !getenv("GARLIC_TGLS_NO_RING");
+    if (f.cov_bits && mode == MODE_LOD_GL && (f.exact_possible || c.where != GARLIC_DEVICE || !tgls_ring_shape))
         return GARLIC_INTERNAL_NO_BITS;      // the TGLS ring chain / the tuned wLOD kernels do not take this shape
-    const bool wlod_shape_ok = mode == MODE_WLOD && W + 64 <= GPAD_BACK && !getenv("GARLIC_WLOD_GENERIC") &&
+    if (mode != MODE_WLOD) {
+        f.feed_asm = !getenv("GARLIC_FEED_NO_ASM");
+        if (mode == MODE_LOD) f.family = c.thin_step > 0 ? Family::feed : Family::chain;   // thinned output: every wave a chain of its own (feed_kernel.hpp)
+        else if (!p->glterms_valid || p->glterms_scaled) f.family = Family::tgls_lookup;
+        else f.family = tgls_ring_shape ? Family::tgls_ring : Family::tgls_terms;
+        f.writes_bits = f.family == Family::tgls_ring;
+        if (f.exact_possible && getenv("GARLIC_EXACT_CHAIN_ONLY")) f.family = Family::exact;
+        return GARLIC_OK;
+    }
+    // wLOD.  Tuned kernels: 16 window accumulators per lane; scores from one LDS row per SNP (plain --error) or from the TGLS
+    // score matrix (use_gl); very narrow / very wide windows keep the generic kernel.
+    const bool use_gl = f.use_gl;
+    const bool wlod_shape_ok = W + 64 <= GPAD_BACK && !getenv("GARLIC_WLOD_GENERIC") &&
                                (W >= WLOD_R || !getenv("GARLIC_WLOD_SMALL_GENERIC"));
     const bool wlod_small = W < WLOD_R;      // narrower than a window group: wlod_group_small (compiler-scheduled)
-    if (wlod_shape_ok && use_gl && (rc = ensure_gl_terms(p, true, M, mu))) return rc;
-    const bool wlod_gl = wlod_shape_ok && use_gl && p->glterms_valid && p->glterms_scaled;   // scores from the term matrix
-    bool wlod_fast = (wlod_shape_ok && !use_gl) || wlod_gl;                 // tile kernel, either variant
-    if (wlod_fast && !wlod_gl && sizeof(double) * (size_t)(W + TILE) * 4 + 16 > 150 * 1024) wlod_fast = false;
-    if (wlod_fast && !wlod_gl && (rc = ensure_score_rows(p, error, M, mu, W))) return rc;
-    if (mode == MODE_WLOD && !wlod_fast && (rc = ensure_rld(p))) return rc;
+    if (wlod_shape_ok && use_gl && (rc = ensure_gl_terms(p, true, c.M, c.mu))) return rc;
+    f.wlod_gl = wlod_shape_ok && use_gl && p->glterms_valid && p->glterms_scaled;   // (the term matrix may have been declined)
+    f.wlod_tuned = (wlod_shape_ok && !use_gl) || f.wlod_gl;
+    if (f.wlod_tuned && !f.wlod_gl && sizeof(double) * (size_t)(W + TILE) * 4 + 16 > 150 * 1024) f.wlod_tuned = false;
+    if (f.wlod_tuned && !f.wlod_gl && (rc = ensure_score_rows(p, c.error, c.M, c.mu, W))) return rc;
+    if (!f.wlod_tuned && (rc = ensure_rld(p))) return rc;
     // narrow windows, plain scores: the streaming kernel (wlod_small_kernel.hpp) reads the plain reciprocals, a window's
     // W weights contiguous
-    const bool wlod_stream = wlod_fast && wlod_small && !p->cov_pending.bits && !getenv("GARLIC_WLOD_SMALL_TILES");
-    if (p->cov_pending.bits && mode == MODE_WLOD && !wlod_fast) return GARLIC_INTERNAL_NO_BITS;
+    const bool wlod_stream = f.wlod_tuned && wlod_small && !f.cov_bits && !getenv("GARLIC_WLOD_SMALL_TILES");
+    if (f.cov_bits && !f.wlod_tuned) return GARLIC_INTERNAL_NO_BITS;
     if (wlod_stream && (rc = ensure_rld(p))) return rc;
     // continuous likelihoods have no code table: the generic kernel takes its terms from the raw matrix
-    if (mode == MODE_WLOD && use_gl && p->gl_cont && !wlod_fast && (rc = ensure_gl_terms(p))) return rc;
+    if (use_gl && p->gl_cont && !f.wlod_tuned && (rc = ensure_gl_terms(p))) return rc;
+    if (!f.wlod_tuned) {
+        f.family = Family::wlod_generic;
+        return GARLIC_OK;
+    }
+    f.writes_bits = true;
+    f.no_prefetch = getenv("GARLIC_WLOD_NO_PF") != nullptr;
     // transposed write-out patch only while rows + patch keep 8 workgroups (32 waves) on a CU
-    const size_t wlod_rows = wlod_gl ? 0 : sizeof(double) * (size_t)(W + TILE) * 4;
+    const size_t wlod_rows = f.wlod_gl ? 0 : sizeof(double) * (size_t)(W + TILE) * 4;
     const size_t wlod_patch = sizeof(double) * (size_t)WAVE * WT_PITCH;
     const bool wlod_use_patch = wlod_rows + 16 + wlod_patch <= 160 * 1024 / 8 && !getenv("GARLIC_WLOD_NO_PATCH");
     // term-matrix variant: the hand-scheduled loop stages the block's term rows through one LDS ring
     // per wave; it needs a block-aligned shard (a wave's 64 lanes = one block of the matrix)
-    const bool wlod_gl_ring = wlod_gl && !wlod_small && (ind_begin & (WAVE - 1)) == 0 && !getenv("GARLIC_WLOD_GL_NO_RING");
+    const bool wlod_gl_ring = f.wlod_gl && !wlod_small && (c.ind_begin & (WAVE - 1)) == 0 && !getenv("GARLIC_WLOD_GL_NO_RING");
     const bool ring_patch = !getenv("GARLIC_WLOD_GL_NO_PATCH");
     // ... and with windows narrow enough for WS_WAVES (W <= 113) or WS_WAVES_WIDE (W <= 241) compute waves per workgroup the strip form: the
     // blocks' term rows enter a CU once per strip (wlod_strip_kernel.hpp)
     const int strip_waves = (W + 15 - 16 * WS_WAVES <= 16 || getenv("GARLIC_WLOD_STRIP_NARROW_ONLY")) ? WS_WAVES : WS_WAVES_WIDE;
     const bool wlod_gl_strip = wlod_gl_ring && W + 15 - 16 * strip_waves <= 16 && !getenv("GARLIC_WLOD_GL_NO_STRIP");
-    const bool strip_now = wlod_gl_strip;
-    const size_t wlod_lds = wlod_gl_ring ? WLOD_GL_RING_OFF + (size_t)WLOD_WAVES * GARLIC_WLOD_GL_RING_ROWS * WAVE * 8
-                                   : wlod_rows + 16 + (wlod_use_patch ? wlod_patch : 0);   // 16: the patch lock
+    f.strip_waves = strip_waves;
+    f.use_patch = wlod_gl_ring ? ring_patch : wlod_use_patch;
+    f.tile_lds = wlod_gl_ring ? WLOD_GL_RING_OFF + (size_t)WLOD_WAVES * GARLIC_WLOD_GL_RING_ROWS * WAVE * 8
+                              : wlod_rows + 16 + (wlod_use_patch ? wlod_patch : 0);   // 16: the patch lock
+    f.strip_force_rerun = wlod_gl_strip && getenv("GARLIC_WLOD_STRIP_FORCE_RERUN") != nullptr;
+    // plain --error scores: two blocks per wave (every scalar-loaded weight used twice); the per-genotype
+    // variants keep one block per wave (their term rows, not the weights, set their pace)
+    f.family = wlod_stream                            ? Family::wlod_stream      // (finish_form: 16-byte aligned rows only)
+               : wlod_small                           ? Family::wlod_small_tiles
+               : wlod_gl_strip                        ? Family::wlod_strip
+               : wlod_gl_ring                         ? Family::wlod_glring
+               : f.wlod_gl                            ? Family::wlod_tile_gl
+               : !getenv("GARLIC_WLOD_ONE_BLOCK")     ? Family::wlod_tile2
+                                                      : Family::wlod_tile;
+    return GARLIC_OK;
+}
 
-    // Host output: the device always computes into the padded layout the tuned kernels need; the
-    // rows are copied out into the caller's (possibly dense) layout by strided D2H copies.
-    const Layout Lhost = make_layout(p, pitch_align, ind_count);
-    const int32_t pitch_align_host = pitch_align;
-    if (where == GARLIC_HOST) pitch_align = std::max(pitch_align, 32);
-    Layout L = make_layout(p, pitch_align, ind_count, thin_step);
-    for (int c = 0; c < p->nchr; c++)
-        if (3 * L.pitch[c] * 8 + 512 >= (int64_t)1 << 32)
-            return fail(GARLIC_ERR_INVALID, "chromosome %d too long for 32-bit row offsets", c);
+// ... and what is known only once the score buffer is: the rows' alignment, and with it the last two choices
+void finish_form(const garlic_panel *p, const LodCall &c, const Layout &L, const double *d_out, LodForm &f)
+{
+    f.aligned16 = (c.pitch_align % 2 == 0) && ((reinterpret_cast<uintptr_t>(d_out) & 15) == 0);
+    if (f.family == Family::wlod_stream && !f.aligned16) f.family = Family::wlod_small_tiles;
+    // scores into 16-B aligned rows at W <= 113: the 80-VGPR form, three workgroups per CU (wlod_strip_kernel.hpp)
+    f.strip_three = f.family == Family::wlod_strip && f.strip_waves != WS_WAVES_WIDE && f.aligned16 && !f.cov_bits &&
+                    !getenv("GARLIC_WLOD_STRIP_TWO_PER_CU");
+    for (int k = 0; f.strip_three && k < p->nchr; k++) f.strip_three = L.pitch[k] * 8 < ((int64_t)1 << 32);
+}
 
-    // Thinned output: every wave a chain of its own (feed_kernel.hpp)
-    const bool feed_kernel = thin_step > 0;
-    uint64_t blocks_hash = 0;
-    if (blocks) {
-        blocks_hash = 0xCBF29CE484222325ull;
-        for (uint8_t b : *blocks) blocks_hash = (blocks_hash ^ (b ? 1u : 2u)) * 0x100000001B3ull;
-        blocks_hash |= 1;
-    }
-    const bool reuse = p->plan.valid && p->plan.blocks_hash == blocks_hash && p->plan.mode == (int)mode && p->plan.W == W &&
-                       p->plan.max_gap == max_gap && p->plan.ind_begin == ind_begin &&
-                       p->plan.ind_count == ind_count && p->plan.pitch_align == pitch_align &&
-                       p->plan.wlod_fast == wlod_fast && p->plan.thin_step == thin_step && p->plan.wlod_strip == wlod_gl_strip &&
-                       p->plan.feed_kernel == feed_kernel;
-    const int nblk = (ind_count + WAVE - 1) / WAVE;
+using Plan = garlic_panel::Plan;
+
+// host side of a new plan, uploaded by enqueue_lod (a reused plan is on the device already)
+struct LodWork {
     std::vector<Run> runs;
     std::vector<FillItem> fill;
     std::vector<ChainItem> items;
     std::vector<FeedItem> feed_items;
     std::vector<ChrDev> chrs;
-    int64_t n_valid = p->plan.n_valid;
-    size_t n_items = p->plan.n_items, n_fill = p->plan.n_fill, n_feed_items = p->plan.n_feed_items;
-    int64_t n_runs = p->plan.n_runs;
-    if (!reuse) {
-        plan_runs(p, W, runs, fill, n_valid);
-        // Work list: (run, 64-individual block) items, longest runs first (LPT); the persistent
-        // workgroups of lod_chain_kernel pull them from a device counter.
-        std::vector<int> order(runs.size());
-        for (size_t i = 0; i < runs.size(); i++) order[i] = (int)i;
-        std::stable_sort(order.begin(), order.end(), [&](int x, int y) {
-            return (runs[x].b - runs[x].a) > (runs[y].b - runs[y].a);
-        });
-        items.reserve(runs.size() * nblk);
-        for (size_t i = 0; i < order.size(); i++) {
-            const Run &r = runs[order[i]];
-            for (int k = 0; k < nblk; k++)
-                if (!blocks || (*blocks)[(size_t)k]) items.push_back(ChainItem{r.chr, r.a, r.b, k * WAVE});
-        }
-        if (feed_kernel) {
-            // the thinned score matrix: row = individual, column = locus / step
-            std::vector<int32_t> col0(runs.size());
-            for (size_t i = 0; i < runs.size(); i++) {
-                const int32_t s = (runs[i].a + thin_step - 1) / thin_step;
-                col0[i] = (int64_t)s * thin_step <= runs[i].b ? s : -1;
-            }
-            build_feed_items(runs, order, blocks, nblk, col0, feed_items);
-            n_feed_items = feed_items.size();
-            if ((rc = p->d_feed_items.reserve(std::max<size_t>(n_feed_items, 1)))) return rc;
-        }
-        chrs.resize(p->nchr);
-        for (int c = 0; c < p->nchr; c++)
-            chrs[c] = ChrDev{p->chr_off[c], L.base[c], L.pitch[c], p->chr_nloci[c],
-                             (pitch_align >= 2 && 64 * L.pitch[c] * 8 + 512 < ((int64_t)1 << 32)) ? 1 : 0};
-        n_items = items.size();
-        n_fill = fill.size();
-        n_runs = (int64_t)runs.size();
-        if ((rc = p->d_chrs.reserve(chrs.size()))) return rc;
-        if ((rc = p->d_items.reserve(std::max<size_t>(n_items, 1)))) return rc;
-        if ((rc = p->d_fill.reserve(std::max<size_t>(n_fill, 1)))) return rc;
-        // [0], [1]: the chain kernel's queue; [2]: sentinel_scan_kernel's flag; [3]: the strip kernel's stall flag;
-        // [4]: strip launches repaired by the tile form since the panel was made (garlic_call_stats::n_stall_reruns)
-        if (!p->d_counter.p) {
-            if ((rc = p->d_counter.reserve(8))) return rc;
-            HIP_TRY(hipMemsetAsync(p->d_counter.p, 0, 8 * sizeof(int32_t), ctx->stream));
-        }
-        p->plan.valid = false;
-    }
-    std::vector<uint8_t> valid;
+    std::vector<uint8_t> valid;                    // tuned wLOD kernels: window mask, tiles, segments, strips
     std::vector<int2> tiles, segs;
-    if (wlod_fast && !reuse) {
-        valid.assign((size_t)p->nloci, 0);
-        for (const Run &r : runs)
-            memset(valid.data() + p->chr_off[r.chr] + r.a, 1, (size_t)(r.b - r.a + 1));
-        for (int c = 0; c < p->nchr; c++)
-            for (int s0 = 0; s0 < p->chr_nloci[c]; s0 += TILE) tiles.push_back(make_int2(c, s0));
-        p->plan.n_tiles = (int32_t)tiles.size();
-        for (int c = 0; c < p->nchr; c++)
-            for (int s0 = 0; s0 < p->chr_nloci[c]; s0 += WSM_T) segs.push_back(make_int2(c, s0));
-        p->plan.n_segs = (int32_t)segs.size();
-        if ((rc = p->d_valid.reserve(valid.size()))) return rc;
-        if ((rc = p->d_tiles.reserve(tiles.size())) || (rc = p->d_segs.reserve(segs.size()))) return rc;
-    }
     std::vector<WlodStrip> strips;
-    if (wlod_gl_strip && !reuse) {
+};
+
+// Runs, chain / feed items, the wLOD kernels' tiles, segments and strips, the ChrDev table; room for them on the device.
+int plan_lod(garlic_panel *p, const LodCall &c, const LodForm &form, const Layout &L, const garlic_panel::PlanKey &key, LodWork &w, Plan &plan)
+{
+    plan = Plan{false, key};
+    const int nblk = (c.ind_count + WAVE - 1) / WAVE;
+    int rc;
+    p->plan.valid = false;
+    plan_runs(p, c.W, w.runs, w.fill, plan.n_valid);
+    // Work list: (run, 64-individual block) items, longest runs first (LPT); the persistent
+    // workgroups of lod_chain_kernel pull them from a device counter.
+    const std::vector<int> order = longest_first(w.runs);
+    w.items.reserve(w.runs.size() * nblk);
+    for (size_t i = 0; i < order.size(); i++) {
+        const Run &r = w.runs[order[i]];
+        for (int k = 0; k < nblk; k++)
+            if (!c.blocks || (*c.blocks)[(size_t)k]) w.items.push_back(ChainItem{r.chr, r.a, r.b, k * WAVE});
+    }
+    if (form.family == Family::feed) {
+        // the thinned score matrix: row = individual, column = locus / step
+        std::vector<int32_t> col0(w.runs.size());
+        for (size_t i = 0; i < w.runs.size(); i++) {
+            const int32_t s = (w.runs[i].a + c.thin_step - 1) / c.thin_step;
+            col0[i] = (int64_t)s * c.thin_step <= w.runs[i].b ? s : -1;
+        }
+        build_feed_items(w.runs, order, c.blocks, nblk, col0, w.feed_items);
+        plan.n_feed_items = w.feed_items.size();
+    }
+    w.chrs.resize(p->nchr);
+    for (int k = 0; k < p->nchr; k++)
+        w.chrs[k] = ChrDev{p->chr_off[k], L.base[k], L.pitch[k], p->chr_nloci[k],
+                           (c.pitch_align >= 2 && 64 * L.pitch[k] * 8 + 512 < ((int64_t)1 << 32)) ? 1 : 0};
+    plan.n_items = w.items.size();
+    plan.n_fill = w.fill.size();
+    plan.n_runs = (int64_t)w.runs.size();
+    // [0], [1]: the chain kernel's queue; [2]: sentinel_scan_kernel's flag; [3]: the strip kernel's stall flag;
+    // [4]: strip launches repaired by the tile form since the panel was made (garlic_call_stats::n_stall_reruns)
+    if (!p->d_counter.p) {
+        if ((rc = p->d_counter.reserve(8))) return rc;
+        HIP_TRY(hipMemsetAsync(p->d_counter.p, 0, 8 * sizeof(int32_t), p->ctx->stream));
+    }
+    if (form.wlod_tuned) {
+        w.valid.assign((size_t)p->nloci, 0);
+        for (const Run &r : w.runs)
+            memset(w.valid.data() + p->chr_off[r.chr] + r.a, 1, (size_t)(r.b - r.a + 1));
+        for (int k = 0; k < p->nchr; k++)
+            for (int s0 = 0; s0 < p->chr_nloci[k]; s0 += TILE) w.tiles.push_back(make_int2(k, s0));
+        plan.n_tiles = (int32_t)w.tiles.size();
+        for (int k = 0; k < p->nchr; k++)
+            for (int s0 = 0; s0 < p->chr_nloci[k]; s0 += WSM_T) w.segs.push_back(make_int2(k, s0));
+        plan.n_segs = (int32_t)w.segs.size();
+    }
+    if (form.family == Family::wlod_strip) {
         // strips of 16-window groups: long enough that filling and draining the workgroup's pipeline (~ 8 groups)
         // stays a few percent, short enough for a few thousand work items
         int64_t total_groups = 0;
-        for (int c = 0; c < p->nchr; c++) total_groups += (p->chr_nloci[c] + WLOD_R - 1) / WLOD_R;
+        for (int k = 0; k < p->nchr; k++) total_groups += (p->chr_nloci[k] + WLOD_R - 1) / WLOD_R;
         const int64_t pairs = (nblk + 1) / 2;
         int64_t per = total_groups * pairs / 8192;
         per = std::min<int64_t>(256, std::max<int64_t>(64, per)) & ~(int64_t)1;
         if (const char *e = getenv("GARLIC_WLOD_STRIP_GROUPS")) per = std::max<int64_t>(1, atol(e));   // tests: many short strips
-        for (int c = 0; c < p->nchr; c++) {
-            const int ng = (p->chr_nloci[c] + WLOD_R - 1) / WLOD_R;
+        for (int k = 0; k < p->nchr; k++) {
+            const int ng = (p->chr_nloci[k] + WLOD_R - 1) / WLOD_R;
             for (int g0 = 0; g0 < ng; g0 += (int)per)
-                strips.push_back(WlodStrip{c, g0 * WLOD_R, std::min<int>((int)per, ng - g0), 0});
+                w.strips.push_back(WlodStrip{k, g0 * WLOD_R, std::min<int>((int)per, ng - g0), 0});
         }
-        p->plan.n_strips = (int32_t)strips.size();
-        if ((rc = p->d_strips.reserve(strips.size()))) return rc;
+        plan.n_strips = (int32_t)w.strips.size();
     }
+    return GARLIC_OK;
+}
+
+// Where the kernels write: the caller's device buffer, or the panel's scratch (host output).  A big unweighted scratch is placed first:
+// candidates, the real kernel timed into each, the fastest kept (1.36 or 1.62 ms at 1M x 1000 by where the scores sit: DESIGN.md section 4).
+int score_buffer(garlic_panel *p, const LodCall &c, const Layout &L, double **d_out)
+{
+    *d_out = c.out;
+    if (c.where != GARLIC_HOST) return GARLIC_OK;
+    int rc;
+    if (p->d_out.cap < (size_t)L.total && c.mode == MODE_LOD && c.thin_step == 0 && !p->placing &&
+        (size_t)L.total * sizeof(double) >= ((size_t)1 << 30) && !getenv("GARLIC_NO_PLACEMENT")) {
+        p->placing = true;
+        void *best = nullptr;
+        rc = garlic_panel_alloc_scores(p, c.pitch_align, c.ind_count, c.W, c.error, c.max_gap, 0, &best, nullptr);
+        p->placing = false;
+        if (rc) return rc;
+        p->d_out.adopt(p->ctx, best, (size_t)L.total);
+    }
+    if ((rc = p->d_out.reserve(p->ctx, (size_t)L.total))) return rc;
+    *d_out = p->d_out.p;
+    return GARLIC_OK;
+}
+
+// GARLIC_TRACE=<file>, a debugging aid: the per-item time stamps (cols each) a persistent kernel leaves are written there
+struct ItemTrace {
+    DevBuf<int64_t> d;
+    const char *path = nullptr;
+    const char *eol = "\n";
+    size_t cols = 0, n = 0;
+    int64_t *begin(size_t cols_, size_t n_, const char *eol_, hipStream_t s)     // NULL: no trace
+    {
+        path = getenv("GARLIC_TRACE");
+        if (!path || d.reserve(cols_ * n_) != GARLIC_OK) return nullptr;
+        cols = cols_;
+        n = n_;
+        eol = eol_;
+        (void)hipMemsetAsync(d.p, 0, sizeof(int64_t) * cols * n, s);
+        return d.p;
+    }
+    void write(hipStream_t s)      // after the launch
+    {
+        if (!n) return;
+        std::vector<int64_t> tr(cols * n);
+        (void)hipMemcpyAsync(tr.data(), d.p, sizeof(int64_t) * tr.size(), hipMemcpyDeviceToHost, s);
+        (void)hipStreamSynchronize(s);
+        if (FILE *fo = fopen(path, "w")) {
+            for (size_t i = 0; i < n; i++) {
+                fprintf(fo, "%zu", i);
+                for (size_t q = 0; q < cols; q++) fprintf(fo, " %lld", (long long)tr[cols * i + q]);
+                fputs(eol, fo);
+            }
+            fclose(fo);
+        }
+        d.release();
+    }
+};
+
+// the context's event pair around a call's dominant kernels (garlic_recent_kernel_ms): its first event, or its second and on to the next pair
+hipError_t hist_mark(garlic_ctx *ctx, bool end)
+{
+    const int slot = (int)(ctx->n_calls % garlic_ctx::HIST);
+    if (end) ctx->n_calls++;
+    return hipEventRecord(end ? ctx->hist1[slot] : ctx->hist0[slot], ctx->stream);
+}
+
+VariantArgs variant_args(const garlic_panel *p, const LodCall &c, const LodForm &form, double *d_out)
+{
+    return VariantArgs{p->d_packed.p, p->d_tab.p,  p->d_tabgl.p, p->d_codes.p, p->d_decay.p, p->d_rld.p,
+                       p->d_items.p,  p->d_chrs.p, d_out,        p->nind_pad,  p->nwordrows, c.ind_begin,  c.ind_count,
+                       c.W,           (int32_t)p->gl_values.size(), form.use_gl ? 1 : 0,
+                       (form.use_gl && p->gl_cont) ? p->d_glterms.p : nullptr, (int64_t)(GOFF + p->nloci + GPAD_BACK)};
+}
+
+// the tile kernel of a family (the strip form's is the one that repairs it)
+const void *wlod_tile_fn(Family family, bool gl, bool aligned16)
+{
+#define WLOD_FN(kernel) (aligned16 ? (const void *)kernel<WLOD_R, true> : (const void *)kernel<WLOD_R, false>)
+    switch (family) {
+    case Family::wlod_tile2: return WLOD_FN(wlod_tile2_kernel);
+    case Family::wlod_tile_gl: return WLOD_FN(wlod_tile_gl_kernel);
+    case Family::wlod_glring:
+    case Family::wlod_strip: return WLOD_FN(wlod_tile_glring_kernel);
+    case Family::wlod_small_tiles: return gl ? WLOD_FN(wlod_tile_small_gl_kernel) : WLOD_FN(wlod_tile_small_kernel);
+    default: return WLOD_FN(wlod_tile_kernel);
+    }
+#undef WLOD_FN
+}
+
+int launch_wlod(garlic_panel *p, const LodCall &c, const LodForm &form, const Plan &plan, double *d_out)
+{
+    hipStream_t s = p->ctx->stream;
+    const int nblk = (c.ind_count + WAVE - 1) / WAVE;
+    const int per_wg = form.family == Family::wlod_tile2 ? WLOD2_BLOCKS : WLOD_WAVES;
+    const int nquad = (nblk + per_wg - 1) / per_wg;
+    const bool gl_ring = form.family == Family::wlod_glring || form.family == Family::wlod_strip;
+    const int64_t score_rows = GOFF + p->nloci + GPAD_BACK;
+    WlodArgs a{p->d_valid.p, p->d_chrs.p, p->d_tiles.p, p->nwordrows, p->nchr, c.ind_begin, c.ind_count, c.W, nquad,
+               (uint32_t)((int64_t)plan.n_tiles * nquad), (form.use_patch ? 1 : 0) | (form.no_prefetch ? 2 : 0),
+               score_rows, gl_ring ? 1 : 0, p->cov_pending, nullptr, nullptr};
+    const uint32_t *a_packed = p->d_packed.p;
+    const double *a_wtab = form.wlod_gl ? p->d_glterms.p : p->d_wtab.p, *a_skew = p->d_skew.p + SKEW_FRONT;
+    const dim3 wl_block(WLOD_WAVES * WAVE);
+    if (form.family == Family::wlod_stream) {
+        // segments of WSM_T windows x eight blocks per workgroup, everything the window loop reads staged in LDS
+        a.tiles = p->d_segs.p;
+        a.nquad = (nblk + WLOD2_BLOCKS - 1) / WLOD2_BLOCKS;
+        a.n_work = (uint32_t)((int64_t)plan.n_segs * a.nquad);
+        a.use_patch = 1;
+        const void *fn = form.wlod_gl ? wlod_stream_small_gl_fn(c.W) : wlod_stream_small_fn(c.W);
+        const size_t lds = wlod_small_lds_bytes(c.W);
+        if (lds > 48 * 1024) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        const double *a_rld = p->d_rld.p;
+        void *kargs[] = {(void *)&a_packed, (void *)&a_wtab, (void *)&a_rld, (void *)&d_out, (void *)&a};
+        HIP_TRY(hipLaunchKernel(fn, dim3((a.n_work + 7u) / 8u * 8u), wl_block, kargs, lds, s));
+        return GARLIC_OK;
+    }
+    if (form.family == Family::wlod_strip) {
+        const int n_pairs = (nblk + 1) / 2;
+        WlodStripArgs sa{p->d_valid.p, p->d_chrs.p, p->d_strips.p, p->d_glterms.p, a_skew, d_out,
+                         score_rows, c.ind_begin, c.ind_count, c.W, form.strip_waves, n_pairs,
+                         form.use_patch ? 1 : 0, (uint32_t)((int64_t)plan.n_strips * n_pairs), p->d_counter.p + 3, p->cov_pending};
+        HIP_TRY(hipMemsetAsync(p->d_counter.p + 3, 0, sizeof(int32_t), s));
+        const void *fn = form.strip_three ? (const void *)wlod_strip_gl3_kernel
+                         : form.strip_waves == WS_WAVES_WIDE ? (form.aligned16 ? (const void *)wlod_strip_gl_kernel<true, WS_WAVES_WIDE>
+                                                  : (const void *)wlod_strip_gl_kernel<false, WS_WAVES_WIDE>)
+                                : (form.aligned16 ? (const void *)wlod_strip_gl_kernel<true, WS_WAVES>
+                                                  : (const void *)wlod_strip_gl_kernel<false, WS_WAVES>);
+        const uint32_t strip_lds = form.strip_three ? WF_LDS_BYTES : WS_LDS_BYTES;
+        HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)strip_lds));
+        void *kargs[] = {(void *)&sa};
+        HIP_TRY(hipLaunchKernel(fn, dim3((sa.n_work + 7u) / 8u * 8u), dim3((form.strip_waves + 1) * WAVE), kargs, strip_lds, s));
+        // A wave of the strip kernel that ran out of its poll budget flags the launch (its scores are wrong).  The tile
+        // form, which computes the same values without waits between waves, is enqueued behind it (below) and runs only if
+        // the flag is set -- on the device: no copy back, no synchronisation, the call stays asynchronous -- and
+        // counts itself (garlic_call_stats::n_stall_reruns: expected 0; a liveness bug shows there, not as a slow call)
+        if (form.strip_force_rerun) HIP_TRY(hipMemsetAsync(p->d_counter.p + 3, 1, sizeof(int32_t), s));
+        a.run_if = p->d_counter.p + 3;
+        a.rerun_count = p->d_counter.p + 4;
+    }
+    const void *fn = wlod_tile_fn(form.family, form.wlod_gl, form.aligned16);
+    if (form.tile_lds > 48 * 1024) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)form.tile_lds));
+    void *kargs[] = {(void *)&a_packed, (void *)&a_wtab, (void *)&a_skew, (void *)&d_out, (void *)&a};
+    HIP_TRY(hipLaunchKernel(fn, dim3((a.n_work + 7u) / 8u * 8u), wl_block, kargs, form.tile_lds, s));
+    return GARLIC_OK;
+}
+
+// unweighted --error scores: the persistent chain kernel, or for thinned output the feed kernel (its grid is chosen from a fresh plan)
+int launch_chain(garlic_panel *p, const LodCall &c, const LodForm &form, Plan &plan, const LodWork *fresh, int workers, double *d_out)
+{
+    garlic_ctx *ctx = p->ctx;
+    ItemTrace trace;
+    if (form.family == Family::feed && plan.n_feed_items) {
+        FeedArgs f{p->d_packed.p, p->d_tab.p, p->d_feed_items.p, p->d_chrs.p, d_out, nullptr, p->nwordrows, c.ind_begin, c.ind_count, c.W,
+                   (int32_t)plan.n_feed_items, c.thin_step, form.feed_asm ? 1 : 0, p->d_counter.p, nullptr};
+        f.trace = trace.begin(8, plan.n_feed_items, "\n", ctx->stream);
+        int grid = (int)std::min<size_t>(plan.n_feed_items, (size_t)ctx->n_cu * std::max(1, plan.feed_per_cu)), rc;
+        if (fresh && (rc = feed_grid(ctx, fresh->feed_items, &grid, &plan.feed_per_cu))) return rc;
+        void *kargs[] = {(void *)&f};
+        HIP_TRY(hipLaunchKernel((const void *)lod_feed_kernel, dim3((unsigned)grid), dim3(FEED_G * WAVE), kargs, 0, ctx->stream));
+    } else {
+        ChainArgs a{p->d_packed.p, p->d_tab.p, p->d_items.p,     p->d_chrs.p,          d_out, p->nind_pad, p->nwordrows,
+                    c.ind_begin,   c.ind_count, c.W,             (int32_t)plan.n_items, p->d_counter.p, nullptr};
+        a.trace = trace.begin(4, plan.n_items, " 0\n", ctx->stream);      // (a fifth column of zeros: the readers of the chain trace expect it)
+        if (form.aligned16)
+            hipLaunchKernelGGL((lod_chain_kernel<true>), dim3((unsigned)workers), dim3(CHAIN_THREADS), 0, ctx->stream, a);
+        else
+            hipLaunchKernelGGL((lod_chain_kernel<false>), dim3((unsigned)workers), dim3(CHAIN_THREADS), 0, ctx->stream, a);
+    }
+    trace.write(ctx->stream);
+    return GARLIC_OK;
+}
+
+int launch_tgls(garlic_panel *p, const LodCall &c, const LodForm &form, const Plan &plan, int workers, double *d_out)
+{
+    hipStream_t s = p->ctx->stream;
+    const int64_t rows = GOFF + p->nloci + GPAD_BACK;
+    if (form.cov_bits && !form.writes_bits) return GARLIC_INTERNAL_NO_BITS;      // only the ring chain takes this shape
+    if (form.family == Family::tgls_ring) {
+        // persistent workgroups, every term row through an LDS ring once (tgls_ring_kernel.hpp)
+        TglsArgs t{p->d_glterms.p, rows, p->d_items.p, p->d_chrs.p, d_out,
+                   c.ind_begin, c.ind_count, c.W, (int32_t)plan.n_items, p->d_counter.p, p->cov_pending};
+        if (form.cov_bits) p->cov_written = true;
+        hipLaunchKernelGGL(lod_chain_ring_kernel, dim3((unsigned)workers), dim3(TG_THREADS), 0, s, t);
+        return GARLIC_OK;
+    }
+    const VariantArgs a = variant_args(p, c, form, d_out);
+    if (form.family == Family::tgls_terms)
+        hipLaunchKernelGGL(lod_chain_terms_kernel, dim3((unsigned)plan.n_items), dim3(2 * WAVE), 0, s, a, (int)plan.n_items, rows, p->d_glterms.p);
+    else
+        hipLaunchKernelGGL(lod_chain_gl_kernel, dim3((unsigned)((plan.n_items + GL_WAVES - 1) / GL_WAVES)), dim3(GL_WAVES * WAVE), 0, s, a,
+                           (int)plan.n_items);
+    return GARLIC_OK;
+}
+
+int launch_generic_wlod(garlic_panel *p, const LodCall &c, const LodForm &form, const Plan &plan, double *d_out)
+{
+    const int ring = c.W + TILE;
+    const size_t lds = sizeof(double) * ((size_t)ring * WAVE + ((c.W + 1) & ~1) + (size_t)WAVE * TPITCH);
+    if (lds > 160 * 1024)
+        return fail(GARLIC_ERR_INVALID, "wLOD with winsize %d: this build supports 2..240 and 16..4096", c.W);
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(wlod_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(wlod_kernel, dim3((unsigned)plan.n_items), dim3(WAVE), lds, p->ctx->stream, variant_args(p, c, form, d_out), ring);
+    return GARLIC_OK;
+}
+
+// Everything a call puts on the stream (a second time, as Family::exact, when the rescan found a -9999.0).  (Replaying a repeated
+// asynchronous pass as one HIP graph -- counter reset, MISSING fill, chain kernel, events -- was measured: no difference, the
+// 1.6 ms kernel hides the launch gaps of the small operations once passes are enqueued back to back.)
+int enqueue_lod(garlic_panel *p, const LodCall &c, const LodForm &form, const Layout &L, Plan &plan, const LodWork *fresh,
+                double *d_out, Family family)
+{
+    garlic_ctx *ctx = p->ctx;
+    hipStream_t s = ctx->stream;
+    int rc = GARLIC_OK;
+    HIP_TRY(hipEventRecord(ctx->ev_begin, s));
+    if (fresh && ((rc = p->d_chrs.put(fresh->chrs, s)) || (rc = p->d_items.put(fresh->items, s)) || (rc = p->d_fill.put(fresh->fill, s)) ||
+                  (rc = p->d_feed_items.put(fresh->feed_items, s)) || (rc = p->d_valid.put(fresh->valid, s)) ||
+                  (rc = p->d_tiles.put(fresh->tiles, s)) || (rc = p->d_segs.put(fresh->segs, s)) || (rc = p->d_strips.put(fresh->strips, s))))
+        return rc;
+    if (family == Family::feed) {          // small matrix: MISSING everywhere, the chain kernel overwrites the scored samples
+        hipLaunchKernelGGL(fill_value_kernel, dim3(1024), dim3(256), 0, s, d_out, L.total, MISSING_D);
+    } else if (plan.n_fill && !form.wlod_tuned && !form.cov_bits) {   // the tuned wLOD kernel writes MISSING itself
+        dim3 grid((unsigned)plan.n_fill, (unsigned)((c.ind_count + FILL_ROWS - 1) / FILL_ROWS));
+        hipLaunchKernelGGL(fill_missing_kernel, grid, dim3(256), 0, s, p->d_fill.p, p->d_chrs.p, c.ind_count, d_out);
+    }
+    // queue head and exit count of the persistent chain kernel: its last workgroup leaves both at
+    // zero, so only a new plan (or a first call) clears them
+    if (plan.n_items && (fresh || c.mode != MODE_LOD)) HIP_TRY(hipMemsetAsync(p->d_counter.p, 0, 2 * sizeof(int32_t), s));
+    p->stats_slot = (int)(ctx->n_calls % garlic_ctx::HIST);
+    HIP_TRY(hist_mark(ctx, false));
     // Persistent workgroups (4 waves each: CHAIN, POST, PRE, COMB), one per CU; items are pulled longest
     // first, so the short runs pack behind the long ones instead of competing with them for HBM
     // bandwidth.
     int workers = ctx->n_cu;
     if (const char *e = getenv("GARLIC_WORKERS")) workers = std::max(1, atoi(e));
-    workers = std::min<int>(workers, (int)n_items);
-
-    double *d_out = out;
-    if (where == GARLIC_HOST) {
-        // big unweighted score scratch: several candidates, the real kernel timed into each, the fastest kept
-        // (the same kernel runs 1.36 or 1.62 ms at 1M x 1000 depending on where its scores sit: DESIGN.md section 4)
-        if (p->d_out.cap < (size_t)L.total && mode == MODE_LOD && thin_step == 0 && !p->placing &&
-            (size_t)L.total * sizeof(double) >= ((size_t)1 << 30) && !getenv("GARLIC_NO_PLACEMENT")) {
-            p->placing = true;
-            void *best = nullptr;
-            rc = garlic_panel_alloc_scores(p, pitch_align, ind_count, W, error, max_gap, 0, &best, nullptr);
-            p->placing = false;
-            if (rc) return rc;
-            p->d_out.adopt(ctx, best, (size_t)L.total);
-            return launch_lod(p, mode, W, error, max_gap, M, mu, ind_begin, ind_count, pitch_align_host, out, where, thin_step, blocks);
+    workers = std::min<int>(workers, (int)plan.n_items);
+    if (form.wlod_tuned || plan.n_items)
+        switch (family) {
+        case Family::chain:
+        case Family::feed: rc = launch_chain(p, c, form, plan, fresh, workers, d_out); break;
+        case Family::exact:
+            hipLaunchKernelGGL(lod_chain_exact_kernel, dim3((unsigned)plan.n_items), dim3(WAVE), 0, s, variant_args(p, c, form, d_out),
+                               (int)plan.n_items);
+            break;
+        case Family::tgls_ring:
+        case Family::tgls_terms:
+        case Family::tgls_lookup: rc = launch_tgls(p, c, form, plan, workers, d_out); break;
+        case Family::wlod_generic: rc = launch_generic_wlod(p, c, form, plan, d_out); break;
+        default: rc = launch_wlod(p, c, form, plan, d_out);
         }
-        if ((rc = p->d_out.reserve(ctx, (size_t)L.total))) return rc;
-        d_out = p->d_out.p;
-    }
-    const bool aligned16 = (pitch_align % 2 == 0) && ((reinterpret_cast<uintptr_t>(d_out) & 15) == 0);
-
-    // Everything this call puts on the stream.  (Replaying a repeated asynchronous pass as one HIP
-    // graph -- counter reset, MISSING fill, chain kernel, events -- was measured: no difference, the
-    // 1.6 ms kernel hides the launch gaps of the small operations once passes are enqueued back to back.)
-    auto enqueue = [&]() -> int {
-    HIP_TRY(hipEventRecord(ctx->ev_begin, ctx->stream));
-    if (!reuse) {
-        HIP_TRY(hipMemcpyAsync(p->d_chrs.p, chrs.data(), sizeof(ChrDev) * chrs.size(),
-                               hipMemcpyHostToDevice, ctx->stream));
-        if (n_items)
-            HIP_TRY(hipMemcpyAsync(p->d_items.p, items.data(), sizeof(ChainItem) * n_items,
-                                   hipMemcpyHostToDevice, ctx->stream));
-        if (feed_kernel && n_feed_items)
-            HIP_TRY(hipMemcpyAsync(p->d_feed_items.p, feed_items.data(), sizeof(FeedItem) * n_feed_items,
-                                   hipMemcpyHostToDevice, ctx->stream));
-        if (n_fill)
-            HIP_TRY(hipMemcpyAsync(p->d_fill.p, fill.data(), sizeof(FillItem) * n_fill,
-                                   hipMemcpyHostToDevice, ctx->stream));
-        if (wlod_fast) {
-            HIP_TRY(hipMemcpyAsync(p->d_valid.p, valid.data(), valid.size(), hipMemcpyHostToDevice,
-                                   ctx->stream));
-            HIP_TRY(hipMemcpyAsync(p->d_tiles.p, tiles.data(), sizeof(int2) * tiles.size(),
-                                   hipMemcpyHostToDevice, ctx->stream));
-            HIP_TRY(hipMemcpyAsync(p->d_segs.p, segs.data(), sizeof(int2) * segs.size(),
-                                   hipMemcpyHostToDevice, ctx->stream));
-            if (!strips.empty())
-                HIP_TRY(hipMemcpyAsync(p->d_strips.p, strips.data(), sizeof(WlodStrip) * strips.size(),
-                                       hipMemcpyHostToDevice, ctx->stream));
-        }
-    }
-    if (thin_step > 0) {          // small matrix: MISSING everywhere, the chain kernel overwrites the scored samples
-        hipLaunchKernelGGL(fill_value_kernel, dim3(1024), dim3(256), 0, ctx->stream, d_out, L.total, MISSING_D);
-    } else if (n_fill && !wlod_fast && !cov_bits) {   // the tuned wLOD kernel writes MISSING itself
-        dim3 grid((unsigned)n_fill, (unsigned)((ind_count + FILL_ROWS - 1) / FILL_ROWS));
-        hipLaunchKernelGGL(fill_missing_kernel, grid, dim3(256), 0, ctx->stream, p->d_fill.p,
-                           p->d_chrs.p, ind_count, d_out);
-    }
-    // queue head and exit count of the persistent chain kernel: its last workgroup leaves both at
-    // zero, so only a new plan (or a first call) clears them
-    if (n_items && (!reuse || mode != MODE_LOD)) HIP_TRY(hipMemsetAsync(p->d_counter.p, 0, 2 * sizeof(int32_t), ctx->stream));
-    p->stats_slot = (int)(ctx->n_calls % garlic_ctx::HIST);
-    HIP_TRY(hipEventRecord(ctx->hist0[p->stats_slot], ctx->stream));
-    if (wlod_fast) {
-        // plain --error scores: two blocks per wave (every scalar-loaded weight used twice); the per-genotype
-        // variants keep one block per wave (their term rows, not the weights, set their pace)
-        const bool two_blocks = !wlod_gl && !wlod_small && !getenv("GARLIC_WLOD_ONE_BLOCK");
-        const int per_wg = two_blocks ? WLOD2_BLOCKS : WLOD_WAVES;
-        const int nquad = (nblk + per_wg - 1) / per_wg;
-        WlodArgs a{p->d_valid.p, p->d_chrs.p, p->d_tiles.p, p->nwordrows, p->nchr, ind_begin, ind_count, W, nquad,
-                   (uint32_t)((int64_t)p->plan.n_tiles * nquad), ((wlod_gl_ring ? ring_patch : wlod_use_patch) ? 1 : 0) | (getenv("GARLIC_WLOD_NO_PF") ? 2 : 0),
-                   (int64_t)(GOFF + p->nloci + GPAD_BACK), wlod_gl_ring ? 1 : 0, p->cov_pending, nullptr, nullptr};
-        const uint32_t *a_packed = p->d_packed.p;
-        const double *a_wtab = wlod_gl ? p->d_glterms.p : p->d_wtab.p, *a_skew = p->d_skew.p + SKEW_FRONT;
-        const unsigned wl_grid = (a.n_work + 7u) / 8u * 8u;
-        const dim3 wl_block(WLOD_WAVES * WAVE);
-        if (wlod_lds > 48 * 1024 && two_blocks) {
-            const void *fn = aligned16 ? (const void *)wlod_tile2_kernel<WLOD_R, true> : (const void *)wlod_tile2_kernel<WLOD_R, false>;
-            HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wlod_lds));
-        } else if (wlod_lds > 48 * 1024) {
-            const void *fn = wlod_gl ? (aligned16 ? (const void *)wlod_tile_gl_kernel<WLOD_R, true>
-                                                  : (const void *)wlod_tile_gl_kernel<WLOD_R, false>)
-                                     : (aligned16 ? (const void *)wlod_tile_kernel<WLOD_R, true>
-                                                  : (const void *)wlod_tile_kernel<WLOD_R, false>);
-            HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wlod_lds));
-        }
-        if (wlod_stream && aligned16) {
-            // segments of WSM_T windows x eight blocks per workgroup, everything the window loop reads staged in LDS
-            const int nquad8 = (nblk + WLOD2_BLOCKS - 1) / WLOD2_BLOCKS;
-            WlodArgs as = a;
-            as.tiles = p->d_segs.p;
-            as.nquad = nquad8;
-            as.n_work = (uint32_t)((int64_t)p->plan.n_segs * nquad8);
-            as.use_patch = 1;
-            const void *fn = wlod_gl ? wlod_stream_small_gl_fn(W) : wlod_stream_small_fn(W);
-            const size_t lds = wlod_small_lds_bytes(W);
-            if (lds > 48 * 1024) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            const double *a_rld = p->d_rld.p;
-            void *kargs[] = {(void *)&a_packed, (void *)&a_wtab, (void *)&a_rld, (void *)&d_out, (void *)&as};
-            HIP_TRY(hipLaunchKernel(fn, dim3((as.n_work + 7u) / 8u * 8u), wl_block, kargs, lds, ctx->stream));
-        } else if (wlod_small) {
-            const void *fn = wlod_gl ? (aligned16 ? (const void *)wlod_tile_small_gl_kernel<WLOD_R, true>
-                                                  : (const void *)wlod_tile_small_gl_kernel<WLOD_R, false>)
-                                     : (aligned16 ? (const void *)wlod_tile_small_kernel<WLOD_R, true>
-                                                  : (const void *)wlod_tile_small_kernel<WLOD_R, false>);
-            void *kargs[] = {(void *)&a_packed, (void *)&a_wtab, (void *)&a_skew, (void *)&d_out, (void *)&a};
-            HIP_TRY(hipLaunchKernel(fn, dim3(wl_grid), wl_block, kargs, wlod_lds, ctx->stream));
-        } else if (strip_now) {
-            const int n_pairs = (nblk + 1) / 2;
-            WlodStripArgs sa{p->d_valid.p, p->d_chrs.p, p->d_strips.p, p->d_glterms.p, a_skew, d_out,
-                             (int64_t)(GOFF + p->nloci + GPAD_BACK), ind_begin, ind_count, W, strip_waves, n_pairs,
-                             ring_patch ? 1 : 0, (uint32_t)((int64_t)p->plan.n_strips * n_pairs), p->d_counter.p + 3, p->cov_pending};
-            HIP_TRY(hipMemsetAsync(p->d_counter.p + 3, 0, sizeof(int32_t), ctx->stream));
-            const unsigned grid = (sa.n_work + 7u) / 8u * 8u;
-            const bool wide = strip_waves == WS_WAVES_WIDE;
-            // scores into 16-B aligned rows at W <= 113: the 80-VGPR form, three workgroups per CU (wlod_strip_kernel.hpp)
-            bool three = !wide && aligned16 && !sa.cov.bits && !getenv("GARLIC_WLOD_STRIP_TWO_PER_CU");
-            for (int k = 0; three && k < p->nchr; k++) three = L.pitch[k] * 8 < ((int64_t)1 << 32);
-            const void *fn = three ? (const void *)wlod_strip_gl3_kernel
-                             : wide ? (aligned16 ? (const void *)wlod_strip_gl_kernel<true, WS_WAVES_WIDE>
-                                                 : (const void *)wlod_strip_gl_kernel<false, WS_WAVES_WIDE>)
-                                    : (aligned16 ? (const void *)wlod_strip_gl_kernel<true, WS_WAVES>
-                                                 : (const void *)wlod_strip_gl_kernel<false, WS_WAVES>);
-            const uint32_t strip_lds = three ? WF_LDS_BYTES : WS_LDS_BYTES;
-            HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)strip_lds));
-            void *kargs[] = {(void *)&sa};
-            HIP_TRY(hipLaunchKernel(fn, dim3(grid), dim3((strip_waves + 1) * WAVE), kargs, strip_lds, ctx->stream));
-            // A wave of the strip kernel that ran out of its poll budget flags the launch (its scores are wrong).  The tile
-            // form, which computes the same values without waits between waves, is enqueued behind it and runs only if
-            // the flag is set -- on the device: no copy back, no synchronisation, the call stays asynchronous -- and
-            // counts itself (garlic_call_stats::n_stall_reruns: expected 0; a liveness bug shows there, not as a slow call)
-            if (getenv("GARLIC_WLOD_STRIP_FORCE_RERUN")) HIP_TRY(hipMemsetAsync(p->d_counter.p + 3, 1, sizeof(int32_t), ctx->stream));
-            WlodArgs ar = a;
-            ar.run_if = p->d_counter.p + 3;
-            ar.rerun_count = p->d_counter.p + 4;
-            if (aligned16)
-                hipLaunchKernelGGL((wlod_tile_glring_kernel<WLOD_R, true>), dim3(wl_grid), wl_block, wlod_lds, ctx->stream,
-                                   a_packed, a_wtab, a_skew, d_out, ar);
-            else
-                hipLaunchKernelGGL((wlod_tile_glring_kernel<WLOD_R, false>), dim3(wl_grid), wl_block, wlod_lds, ctx->stream,
-                                   a_packed, a_wtab, a_skew, d_out, ar);
-        } else if (wlod_gl_ring && aligned16)
-            hipLaunchKernelGGL((wlod_tile_glring_kernel<WLOD_R, true>), dim3(wl_grid), wl_block, wlod_lds, ctx->stream,
-                               a_packed, a_wtab, a_skew, d_out, a);
-        else if (wlod_gl_ring)
-            hipLaunchKernelGGL((wlod_tile_glring_kernel<WLOD_R, false>), dim3(wl_grid), wl_block, wlod_lds, ctx->stream,
-                               a_packed, a_wtab, a_skew, d_out, a);
-        else if (wlod_gl && aligned16)
-            hipLaunchKernelGGL((wlod_tile_gl_kernel<WLOD_R, true>), dim3(wl_grid), wl_block, wlod_lds, ctx->stream,
-                               a_packed, a_wtab, a_skew, d_out, a);
-        else if (wlod_gl)
-            hipLaunchKernelGGL((wlod_tile_gl_kernel<WLOD_R, false>), dim3(wl_grid), wl_block, wlod_lds, ctx->stream,
-                               a_packed, a_wtab, a_skew, d_out, a);
-        else if (two_blocks && aligned16)
-            hipLaunchKernelGGL((wlod_tile2_kernel<WLOD_R, true>), dim3(wl_grid), wl_block, wlod_lds, ctx->stream,
-                               a_packed, a_wtab, a_skew, d_out, a);
-        else if (two_blocks)
-            hipLaunchKernelGGL((wlod_tile2_kernel<WLOD_R, false>), dim3(wl_grid), wl_block, wlod_lds, ctx->stream,
-                               a_packed, a_wtab, a_skew, d_out, a);
-        else if (aligned16)
-            hipLaunchKernelGGL((wlod_tile_kernel<WLOD_R, true>), dim3(wl_grid), wl_block, wlod_lds, ctx->stream,
-                               a_packed, a_wtab, a_skew, d_out, a);
-        else
-            hipLaunchKernelGGL((wlod_tile_kernel<WLOD_R, false>), dim3(wl_grid), wl_block, wlod_lds, ctx->stream,
-                               a_packed, a_wtab, a_skew, d_out, a);
-    } else if (n_items && exact) {
-        VariantArgs a{p->d_packed.p, p->d_tab.p,  p->d_tabgl.p, p->d_codes.p, p->d_decay.p, p->d_rld.p,
-                      p->d_items.p,  p->d_chrs.p, d_out,        p->nind_pad,  p->nwordrows, ind_begin,    ind_count,
-                      W,             (int32_t)p->gl_values.size(), use_gl ? 1 : 0,
-                      (use_gl && p->gl_cont) ? p->d_glterms.p : nullptr, (int64_t)(GOFF + p->nloci + GPAD_BACK)};
-        hipLaunchKernelGGL(lod_chain_exact_kernel, dim3((unsigned)n_items), dim3(WAVE), 0, ctx->stream, a, (int)n_items);
-    } else if (n_items && mode == MODE_LOD) {
-        ChainArgs a{p->d_packed.p, p->d_tab.p, p->d_items.p,     p->d_chrs.p,     d_out, p->nind_pad, p->nwordrows,
-                    ind_begin,     ind_count,  W,               (int32_t)n_items, p->d_counter.p, nullptr};
-        DevBuf<int64_t> d_trace;   // debugging aid: GARLIC_TRACE=<file> dumps per-item timestamps
-        const char *trace_path = getenv("GARLIC_TRACE");
-        if (trace_path && !(feed_kernel && n_feed_items) && d_trace.reserve(4 * n_items) == GARLIC_OK) {
-            (void)hipMemsetAsync(d_trace.p, 0, sizeof(int64_t) * 4 * n_items, ctx->stream);
-            a.trace = d_trace.p;
-        }
-        if (feed_kernel && n_feed_items) {
-            FeedArgs f{p->d_packed.p, p->d_tab.p, p->d_feed_items.p, p->d_chrs.p, d_out, nullptr, p->nwordrows, ind_begin, ind_count, W,
-                       (int32_t)n_feed_items, thin_step, getenv("GARLIC_FEED_NO_ASM") ? 0 : 1, p->d_counter.p, nullptr};
-            DevBuf<int64_t> d_ftrace;   // debugging aid: GARLIC_TRACE=<file> dumps per-item time stamps
-            const char *ftrace_path = getenv("GARLIC_TRACE");
-            if (ftrace_path && d_ftrace.reserve(8 * n_feed_items) == GARLIC_OK) {
-                (void)hipMemsetAsync(d_ftrace.p, 0, sizeof(int64_t) * 8 * n_feed_items, ctx->stream);
-                f.trace = d_ftrace.p;
-            }
-            const void *fn = (const void *)lod_feed_kernel;
-            int grid = (int)std::min<size_t>(n_feed_items, (size_t)ctx->n_cu * std::max(1, p->plan.feed_per_cu));
-            if (!reuse && (rc = feed_grid(ctx, feed_items, &grid, &p->plan.feed_per_cu))) return rc;
-            void *kargs[] = {(void *)&f};
-            HIP_TRY(hipLaunchKernel(fn, dim3((unsigned)grid), dim3(FEED_G * WAVE), kargs, 0, ctx->stream));
-            if (f.trace) {
-                std::vector<int64_t> tr(8 * n_feed_items);
-                (void)hipMemcpyAsync(tr.data(), d_ftrace.p, sizeof(int64_t) * tr.size(), hipMemcpyDeviceToHost, ctx->stream);
-                (void)hipStreamSynchronize(ctx->stream);
-                if (FILE *fo = fopen(ftrace_path, "w")) {
-                    for (size_t i = 0; i < n_feed_items; i++) {
-                        fprintf(fo, "%zu", i);
-                        for (int q = 0; q < 8; q++) fprintf(fo, " %lld", (long long)tr[8 * i + q]);
-                        fprintf(fo, "\n");
-                    }
-                    fclose(fo);
-                }
-                d_ftrace.release();
-            }
-        } else if (aligned16)
-            hipLaunchKernelGGL((lod_chain_kernel<true>), dim3((unsigned)workers), dim3(CHAIN_THREADS), 0,
-                               ctx->stream, a);
-        else
-            hipLaunchKernelGGL((lod_chain_kernel<false>), dim3((unsigned)workers), dim3(CHAIN_THREADS), 0,
-                               ctx->stream, a);
-        if (a.trace) {
-            std::vector<int64_t> tr(4 * n_items);
-            (void)hipMemcpyAsync(tr.data(), d_trace.p, sizeof(int64_t) * tr.size(), hipMemcpyDeviceToHost, ctx->stream);
-            (void)hipStreamSynchronize(ctx->stream);
-            if (FILE *f = fopen(trace_path, "w")) {
-                for (size_t i = 0; i < n_items; i++)
-                    fprintf(f, "%zu %lld %lld %lld %lld %d\n", i, (long long)tr[4 * i], (long long)tr[4 * i + 1],
-                            (long long)tr[4 * i + 2], (long long)tr[4 * i + 3], 0);
-                fclose(f);
-            }
-            d_trace.release();
-        }
-    } else if (n_items) {
-        VariantArgs a{p->d_packed.p, p->d_tab.p,  p->d_tabgl.p, p->d_codes.p, p->d_decay.p, p->d_rld.p,
-                      p->d_items.p,  p->d_chrs.p, d_out,        p->nind_pad,  p->nwordrows, ind_begin,    ind_count,
-                      W,             (int32_t)p->gl_values.size(), use_gl ? 1 : 0,
-                      (use_gl && p->gl_cont) ? p->d_glterms.p : nullptr, (int64_t)(GOFF + p->nloci + GPAD_BACK)};
-        if (mode == MODE_LOD_GL && p->glterms_valid && !p->glterms_scaled && (ind_begin & (WAVE - 1)) == 0 &&
-            !getenv("GARLIC_TGLS_NO_RING")) {
-            // persistent workgroups, every term row through an LDS ring once (tgls_ring_kernel.hpp)
-            TglsArgs t{p->d_glterms.p, (int64_t)(GOFF + p->nloci + GPAD_BACK), p->d_items.p, p->d_chrs.p, d_out,
-                       ind_begin, ind_count, W, (int32_t)n_items, p->d_counter.p, p->cov_pending};
-            if (p->cov_pending.bits) p->cov_written = true;
-            hipLaunchKernelGGL(lod_chain_ring_kernel, dim3((unsigned)workers), dim3(TG_THREADS), 0, ctx->stream, t);
-        } else if (cov_bits) {
-            return GARLIC_INTERNAL_NO_BITS;      // the TGLS ring chain / the tuned wLOD kernels do not take this shape
-        } else if (mode == MODE_LOD_GL && p->glterms_valid && !p->glterms_scaled) {
-            hipLaunchKernelGGL(lod_chain_terms_kernel, dim3((unsigned)n_items), dim3(2 * WAVE), 0, ctx->stream, a,
-                               (int)n_items, (int64_t)(GOFF + p->nloci + GPAD_BACK), p->d_glterms.p);
-        } else if (mode == MODE_LOD_GL) {
-            hipLaunchKernelGGL(lod_chain_gl_kernel, dim3((unsigned)((n_items + GL_WAVES - 1) / GL_WAVES)),
-                               dim3(GL_WAVES * WAVE), 0, ctx->stream, a, (int)n_items);
-        } else {
-            const int ring = W + TILE;
-            const size_t lds = sizeof(double) * ((size_t)ring * WAVE + ((W + 1) & ~1) + (size_t)WAVE * TPITCH);
-            if (lds > 160 * 1024)
-                return fail(GARLIC_ERR_INVALID, "wLOD with winsize %d: this build supports 2..240 and 16..4096", W);
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(wlod_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(wlod_kernel, dim3((unsigned)n_items), dim3(WAVE), lds, ctx->stream, a,
-                               ring);
-        }
-    }
-    HIP_TRY(hipEventRecord(ctx->hist1[ctx->n_calls % garlic_ctx::HIST], ctx->stream));
-    ctx->n_calls++;
+    if (rc) return rc;
+    HIP_TRY(hist_mark(ctx, true));
     HIP_TRY(hipGetLastError());
     return GARLIC_OK;
-    };   // enqueue
-    if ((rc = enqueue())) return rc;
-    p->last_chain_kind = exact ? 2 : 0;
-    if (exact_possible && !exact && n_items) {
+}
+
+// thin_step > 0 (unweighted scores, device output, pitch_align 32 only): `out` is the thinned matrix
+// of make_layout(p, 32, ind_count, thin_step) -- the chain kernel stores only the windows at loci
+// 0, thin_step, 2 * thin_step, .. of each chromosome, everything else of that matrix is MISSING.
+// blocks (chain kernels only): per 64-individual block of the call, 1 = score it; rows of the other
+// blocks are left unwritten (the subset feed never reads them)
+int launch_lod(garlic_panel *p, Mode mode, int32_t W, double error, int32_t max_gap, int32_t M, double mu,
+               int32_t ind_begin, int32_t ind_count, int32_t pitch_align, double *out, int32_t where,
+               int32_t thin_step = 0, const std::vector<uint8_t> *blocks = nullptr)
+{
+    garlic_ctx *ctx = p->ctx;
+    int rc;
+    if ((rc = set_device(ctx))) return rc;
+    // Host output: the device always computes into the padded layout the tuned kernels need; the
+    // rows are copied out into the caller's (possibly dense) layout by strided D2H copies.
+    const LodCall c{mode, W, max_gap, M, ind_begin, ind_count, where == GARLIC_HOST ? std::max(pitch_align, 32) : pitch_align,
+                    thin_step, where, pitch_align, error, mu, out, blocks};
+    LodForm form;
+    if ((rc = check_lod_args(p, c)) || (rc = decide_form(p, c, form))) return rc;
+    const Layout Lhost = make_layout(p, pitch_align, ind_count), L = make_layout(p, c.pitch_align, ind_count, thin_step);
+    for (int k = 0; k < p->nchr; k++)
+        if (3 * L.pitch[k] * 8 + 512 >= (int64_t)1 << 32)
+            return fail(GARLIC_ERR_INVALID, "chromosome %d too long for 32-bit row offsets", k);
+    double *d_out = nullptr;
+    if ((rc = score_buffer(p, c, L, &d_out))) return rc;
+    finish_form(p, c, L, d_out, form);
+
+    garlic_panel::PlanKey key{(int)mode, W, max_gap, ind_begin, ind_count, c.pitch_align, thin_step, 0, form.wlod_tuned,
+                form.family == Family::wlod_strip, thin_step > 0};
+    if (blocks) {
+        key.blocks_hash = 0xCBF29CE484222325ull;
+        for (uint8_t b : *blocks) key.blocks_hash = (key.blocks_hash ^ (b ? 1u : 2u)) * 0x100000001B3ull;
+        key.blocks_hash |= 1;
+    }
+    const bool reuse = p->plan.valid && p->plan.key == key;
+    Plan plan = p->plan;
+    LodWork work;
+    if (!reuse && (rc = plan_lod(p, c, form, L, key, work, plan))) return rc;
+
+    if ((rc = enqueue_lod(p, c, form, L, plan, reuse ? nullptr : &work, d_out, form.family))) return rc;
+    p->last_chain_kind = form.family == Family::exact ? 2 : 0;
+    if (form.exact_possible && form.family != Family::exact && plan.n_items) {
+        // the reference tests "no score" by value: did a scored window of the tuned chain come out as exactly -9999.0?
         int32_t found = 0;
         HIP_TRY(hipMemsetAsync(p->d_counter.p + 2, 0, sizeof(int32_t), ctx->stream));
-        hipLaunchKernelGGL(sentinel_scan_kernel, dim3((unsigned)n_items), dim3(256), 0, ctx->stream, p->d_items.p, p->d_chrs.p,
+        hipLaunchKernelGGL(sentinel_scan_kernel, dim3((unsigned)plan.n_items), dim3(256), 0, ctx->stream, p->d_items.p, p->d_chrs.p,
                            d_out, ind_count, p->d_counter.p + 2);
         HIP_TRY(hipMemcpyAsync(&found, p->d_counter.p + 2, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         p->last_chain_kind = found ? 2 : 1;
-        if (found) {
-            exact = true;
-            if ((rc = enqueue())) return rc;
-        }
+        if (found && (rc = enqueue_lod(p, c, form, L, plan, reuse ? nullptr : &work, d_out, Family::exact))) return rc;
     }
     if (where == GARLIC_HOST)
-        for (int c = 0; c < p->nchr; c++)
-            HIP_TRY(hipMemcpy2DAsync(out + Lhost.base[c], sizeof(double) * Lhost.pitch[c], d_out + L.base[c],
-                                     sizeof(double) * L.pitch[c], sizeof(double) * p->chr_nloci[c],
+        for (int k = 0; k < p->nchr; k++)
+            HIP_TRY(hipMemcpy2DAsync(out + Lhost.base[k], sizeof(double) * Lhost.pitch[k], d_out + L.base[k],
+                                     sizeof(double) * L.pitch[k], sizeof(double) * p->chr_nloci[k],
                                      (size_t)ind_count, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipEventRecord(ctx->ev_end, ctx->stream));
     // The work list lives in host vectors and per-panel device scratch: finish before returning --
@@ -1655,19 +1732,15 @@ int launch_lod(garlic_panel *p, Mode mode, int32_t W, double error, int32_t max_
     const bool enqueue_only = ctx->async_device && where == GARLIC_DEVICE && reuse;
     if (!enqueue_only) HIP_TRY(hipStreamSynchronize(ctx->stream));
     p->stats_pending = true;
+    plan.valid = true;
+    p->plan = plan;
 
     garlic_call_stats &st = p->stats;
     st.n_segments = (int64_t)p->boundaries.size();
-    st.n_runs = n_runs;
-    st.n_chain_items = (int64_t)n_items;
-    p->plan.valid = true;
-    p->plan.mode = (int)mode; p->plan.W = W; p->plan.max_gap = max_gap; p->plan.ind_begin = ind_begin;
-    p->plan.ind_count = ind_count; p->plan.pitch_align = pitch_align;
-    p->plan.wlod_fast = wlod_fast; p->plan.wlod_strip = wlod_gl_strip; p->plan.thin_step = thin_step; p->plan.blocks_hash = blocks_hash;
-    p->plan.feed_kernel = feed_kernel; p->plan.n_feed_items = n_feed_items;
-    p->plan.n_items = n_items; p->plan.n_fill = n_fill; p->plan.n_runs = n_runs; p->plan.n_valid = n_valid;
-    st.n_valid_windows = n_valid;
-    st.n_missing = p->nloci - n_valid;
+    st.n_runs = plan.n_runs;
+    st.n_chain_items = (int64_t)plan.n_items;
+    st.n_valid_windows = plan.n_valid;
+    st.n_missing = p->nloci - plan.n_valid;
     return GARLIC_OK;
 }
 
@@ -1815,7 +1888,6 @@ static void release_feed_slots(garlic_panel *p)
         if (sl->stream) { (void)hipStreamSynchronize(sl->stream); (void)hipStreamDestroy(sl->stream); }
         if (sl->ev0) (void)hipEventDestroy(sl->ev0);
         if (sl->ev1) (void)hipEventDestroy(sl->ev1);
-        sl->items.release(); sl->chrs.release(); sl->counter.release(); sl->row_counts.release(); sl->out.release(); sl->feed.release();
         delete sl;
     }
     p->feed_slots.clear();
@@ -1826,15 +1898,9 @@ int garlic_panel_destroy(garlic_panel *p)
     if (!p) return GARLIC_OK;
     (void)hipSetDevice(p->ctx->device);
     (void)hipStreamSynchronize(p->ctx->stream);
-    p->d_packed.release(); p->d_pos.release(); p->d_cs.release(); p->d_ce.release();
-    p->d_chr_off.release(); p->d_tab.release(); p->d_blk_counts.release();
-    p->d_blk_offsets.release(); p->d_total.release(); p->d_boundaries.release();
-    p->d_items.release(); p->d_fill.release(); p->d_counter.release(); p->d_chrs.release(); p->d_stage16.release(); p->d_row_counts.release(); p->d_codes.release(); p->d_tabgl.release();
-    p->d_rld.release(); p->d_decay.release(); p->d_stage64.release(); p->d_phase.release(); p->lds.release();
-    p->d_glterms.release(); p->d_glval.release(); p->d_freq.release(); p->d_skew.release(); p->d_wtab.release(); p->d_valid.release(); p->d_tiles.release(); p->d_segs.release(); p->d_strips.release();
-    p->d_out.release(); p->d_feed.release(); p->d_feed_items.release();
+    p->d_out.release();
     release_feed_slots(p);
-    delete p;
+    delete p;      // (its DevBuf members free themselves: the device is set and the stream idle)
     return GARLIC_OK;
 }
 
@@ -1996,10 +2062,9 @@ int garlic_panel_set_gl(garlic_panel *p, const double *gl, int64_t ld, int64_t l
     DevBuf<uint64_t> d_bits, d_unk;
     DevBuf<uint8_t> d_dcode;
     DevBuf<int32_t> d_nunk;
-    auto done = [&](int code) { stage.release(); d_bits.release(); d_unk.release(); d_dcode.release(); d_nunk.release(); return code; };
     if ((rc = d_bits.reserve(GL_DICT_MAX)) || (rc = d_dcode.reserve(GL_DICT_MAX)) || (rc = d_unk.reserve(UNK_CAP)) ||
         (rc = d_nunk.reserve(1)))
-        return done(rc);
+        return rc;
     const int64_t slab_rows = (where == GARLIC_HOST) ? std::max<int64_t>(16, ((int64_t)256 << 20) / (8 * ld)) : locus_count;
     std::vector<uint64_t> unk(UNK_CAP);
     for (int64_t at = 0; at < locus_count; at += slab_rows) {
@@ -2007,7 +2072,7 @@ int garlic_panel_set_gl(garlic_panel *p, const double *gl, int64_t ld, int64_t l
         const double *src = gl + at * ld;
         hipError_t e = hipSuccess;
         if (where == GARLIC_HOST) {
-            if ((rc = stage.reserve((size_t)(nrows * ld)))) return done(rc);
+            if ((rc = stage.reserve((size_t)(nrows * ld)))) return rc;
             e = hipMemcpyAsync(stage.p, src, sizeof(double) * nrows * ld, hipMemcpyHostToDevice, s);
             src = stage.p;
         }
@@ -2040,7 +2105,7 @@ int garlic_panel_set_gl(garlic_panel *p, const double *gl, int64_t ld, int64_t l
                 if (p->gl_code.count(unk[k])) continue;
                 const int code = (int)p->gl_values.size();
                 if (code >= GL_DICT_MAX) {       // continuous inputs: keep values, not codes
-                    if ((rc = switch_to_continuous(p))) return done(rc);
+                    if ((rc = switch_to_continuous(p))) return rc;
                     break;
                 }
                 double v;
@@ -2056,13 +2121,13 @@ int garlic_panel_set_gl(garlic_panel *p, const double *gl, int64_t ld, int64_t l
             e = hipGetLastError();
             if (e == hipSuccess) e = hipStreamSynchronize(s);          // the staging slab is free again
         }
-        if (e != hipSuccess) return done(fail(GARLIC_ERR_HIP, "set_gl: %s", hipGetErrorString(e)));
+        if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "set_gl: %s", hipGetErrorString(e));
     }
     if (p->gl_cont && !p->gl_cover.empty())
         memset(p->gl_cover.data() + locus_begin, 1, (size_t)locus_count);
     p->have_gl = true;
     p->glterms_valid = false;
-    return done(GARLIC_OK);
+    return GARLIC_OK;
 }
 
 int garlic_panel_set_gl_codes(garlic_panel *p, const uint8_t *codes, int64_t ld, int64_t locus_begin,
@@ -2109,15 +2174,14 @@ int garlic_panel_set_gl_codes(garlic_panel *p, const uint8_t *codes, int64_t ld,
     }
     DevBuf<uint8_t> stage, d_remap;
     DevBuf<double> d_dict;
-    auto done = [&](int code) { stage.release(); d_remap.release(); d_dict.release(); return code; };
     hipError_t e = hipSuccess;
     if (p->gl_cont) {
         std::vector<double> dict(GL_DICT_MAX, 0.0);
         std::copy(values, values + nvalues, dict.begin());
-        if ((rc = d_dict.reserve(GL_DICT_MAX))) return done(rc);
+        if ((rc = d_dict.reserve(GL_DICT_MAX))) return rc;
         e = hipMemcpy(d_dict.p, dict.data(), sizeof(double) * GL_DICT_MAX, hipMemcpyHostToDevice);
     } else {
-        if ((rc = d_remap.reserve(256))) return done(rc);
+        if ((rc = d_remap.reserve(256))) return rc;
         e = hipMemcpy(d_remap.p, remap, 256, hipMemcpyHostToDevice);
     }
     const int64_t slab_rows = (where == GARLIC_HOST) ? std::max<int64_t>(16, ((int64_t)256 << 20) / ld) : locus_count;
@@ -2125,7 +2189,7 @@ int garlic_panel_set_gl_codes(garlic_panel *p, const uint8_t *codes, int64_t ld,
         const int64_t nrows = std::min(slab_rows, locus_count - at);
         const uint8_t *src = codes + at * ld;
         if (where == GARLIC_HOST) {
-            if ((rc = stage.reserve((size_t)(nrows * ld)))) return done(rc);
+            if ((rc = stage.reserve((size_t)(nrows * ld)))) return rc;
             e = hipMemcpyAsync(stage.p, src, (size_t)(nrows * ld), hipMemcpyHostToDevice, s);
             src = stage.p;
         }
@@ -2139,12 +2203,12 @@ int garlic_panel_set_gl_codes(garlic_panel *p, const uint8_t *codes, int64_t ld,
         e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(s);                      // staging slab free again
     }
-    if (e != hipSuccess) return done(fail(GARLIC_ERR_HIP, "set_gl_codes: %s", hipGetErrorString(e)));
+    if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "set_gl_codes: %s", hipGetErrorString(e));
     if (p->gl_cont && !p->gl_cover.empty())
         memset(p->gl_cover.data() + locus_begin, 1, (size_t)locus_count);
     p->have_gl = true;
     p->glterms_valid = false;
-    return done(GARLIC_OK);
+    return GARLIC_OK;
 }
 
 int garlic_panel_set_phase(garlic_panel *p, const uint8_t *first_copy, int64_t ld, int64_t locus_begin,
@@ -2323,13 +2387,12 @@ int garlic_ld_counts(garlic_panel *p, int32_t winsize, int32_t phased, const int
     }
     DevBuf<uint64_t> &d_sub = p->lds.sub, &d_m = p->lds.m, &d_h = p->lds.h, &d_o = p->lds.o;
     DevBuf<int32_t> &d_loc = p->lds.loc, &d_pair = p->lds.pair;
-    auto done = [&](int code) { return code; };   // the scratch stays with the panel
     const size_t npl = (size_t)nblk * p->nloci, npair = (size_t)p->nloci * winsize * 2;
-    if ((rc = d_sub.reserve(nblk)) || (rc = d_m.reserve(npl)) || (rc = d_h.reserve(npl))) return done(rc);
-    if (phased && (rc = d_o.reserve(npl))) return done(rc);
+    if ((rc = d_sub.reserve(nblk)) || (rc = d_m.reserve(npl)) || (rc = d_h.reserve(npl))) return rc;
+    if (phased && (rc = d_o.reserve(npl))) return rc;
     int32_t *loc = locus_counts, *pair = pair_counts;
     if (where == GARLIC_HOST) {
-        if ((rc = d_loc.reserve((size_t)p->nloci * 2)) || (rc = d_pair.reserve(npair))) return done(rc);
+        if ((rc = d_loc.reserve((size_t)p->nloci * 2)) || (rc = d_pair.reserve(npair))) return rc;
         loc = d_loc.p; pair = d_pair.p;
     }
     // pair counts: LDS-tiled (thread = distance, W - 1 <= 256; writes every entry of the table) or streamed from L2
@@ -2355,13 +2418,13 @@ int garlic_ld_counts(garlic_panel *p, int32_t winsize, int32_t phased, const int
     const bool pair_tiled = !pair_mfma && !pair_flat && !pair_lane && winsize - 1 <= 256 && !getenv("GARLIC_LD_PAIR_L2");
     hipError_t e = hipMemcpyAsync(d_sub.p, sub.data(), sizeof(uint64_t) * nblk, hipMemcpyHostToDevice, s);
     if (e == hipSuccess && !pair_tiled && !pair_flat && !pair_lane && !pair_mfma) e = hipMemsetAsync(pair, 0, sizeof(int32_t) * npair, s);
-    if (e != hipSuccess) return done(fail(GARLIC_ERR_HIP, "LD counts: %s", hipGetErrorString(e)));
+    if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "LD counts: %s", hipGetErrorString(e));
     uint64_t planes_key = 0xCBF29CE484222325ull;
     for (uint64_t w : sub) planes_key = (planes_key ^ w) * 0x100000001B3ull;
     planes_key = (planes_key ^ (uint64_t)(phased ? 2 : 1)) * 0x100000001B3ull;
     planes_key = (planes_key ^ p->geno_epoch) * 0x100000001B3ull;
     planes_key = (planes_key ^ (uint64_t)nblk) * 0x100000001B3ull;
-    if ((rc = p->lds.loc_planes.reserve((size_t)p->nloci * 2))) return done(rc);
+    if ((rc = p->lds.loc_planes.reserve((size_t)p->nloci * 2))) return rc;
     if (!(p->lds.planes_valid && p->lds.planes_key == planes_key) || getenv("GARLIC_LD_NO_PLANE_CACHE")) {
         p->lds.planes_valid = false;
         if (phased)
@@ -2371,18 +2434,18 @@ int garlic_ld_counts(garlic_panel *p, int32_t winsize, int32_t phased, const int
             hipLaunchKernelGGL(ld_planes_kernel<false>, dim3((unsigned)p->nwordrows), dim3(256), 0, s, p->d_packed.p,
                                p->nwordrows, nblk, d_sub.p, p->nloci, d_m.p, d_h.p, (uint64_t *)nullptr, p->lds.loc_planes.p);
         e = hipGetLastError();
-        if (e != hipSuccess) return done(fail(GARLIC_ERR_HIP, "LD planes: %s", hipGetErrorString(e)));
+        if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "LD planes: %s", hipGetErrorString(e));
         p->lds.planes_key = planes_key;
         p->lds.planes_valid = true;
     }
     e = hipMemcpyAsync(loc, p->lds.loc_planes.p, sizeof(int32_t) * p->nloci * 2, hipMemcpyDeviceToDevice, s);
-    if (e != hipSuccess) return done(fail(GARLIC_ERR_HIP, "LD counts: %s", hipGetErrorString(e)));
+    if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "LD counts: %s", hipGetErrorString(e));
     const int pair_threads = (winsize - 1 + WAVE - 1) / WAVE * WAVE;
     const size_t pair_lds = sizeof(uint64_t) * (phased ? 4 : 2) * LD_PAIR_BLK * (LD_PAIR_T + winsize - 1);
     if (pair_tiled && pair_lds > 48 * 1024) {
         const void *fn = phased ? (const void *)ld_pair_tiled_kernel<true> : (const void *)ld_pair_tiled_kernel<false>;
         hipError_t ae = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pair_lds);
-        if (ae != hipSuccess) return done(fail(GARLIC_ERR_HIP, "LD counts: %s", hipGetErrorString(ae)));
+        if (ae != hipSuccess) return fail(GARLIC_ERR_HIP, "LD counts: %s", hipGetErrorString(ae));
     }
     if (pair_tiled) {   // all chromosomes in one grid
         std::vector<LdPairChr> pc;
@@ -2392,9 +2455,9 @@ int garlic_ld_counts(garlic_panel *p, int32_t winsize, int32_t phased, const int
             blocks += (p->chr_nloci[c] + LD_PAIR_T - 1) / LD_PAIR_T;
         }
         DevBuf<LdPairChr> &d_pc = p->lds.pair_chrs;
-        if ((rc = d_pc.reserve(pc.size()))) return done(rc);
+        if ((rc = d_pc.reserve(pc.size()))) return rc;
         e = hipMemcpyAsync(d_pc.p, pc.data(), sizeof(LdPairChr) * pc.size(), hipMemcpyHostToDevice, s);
-        if (e != hipSuccess) return done(fail(GARLIC_ERR_HIP, "LD counts: %s", hipGetErrorString(e)));
+        if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "LD counts: %s", hipGetErrorString(e));
         if (phased)
             hipLaunchKernelGGL(ld_pair_tiled_kernel<true>, dim3((unsigned)blocks), dim3(pair_threads), pair_lds, s, d_m.p,
                                d_h.p, d_o.p, p->d_phase.p, nblk, p->nloci, d_pc.p, p->nchr, winsize, pair);
@@ -2404,7 +2467,7 @@ int garlic_ld_counts(garlic_panel *p, int32_t winsize, int32_t phased, const int
                                p->nchr, winsize, pair);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(s);   // pc (host) is read by the copy above
-        if (e != hipSuccess) return done(fail(GARLIC_ERR_HIP, "LD counts: %s", hipGetErrorString(e)));
+        if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "LD counts: %s", hipGetErrorString(e));
     }
     if (pair_mfma) {   // all chromosomes in one grid, 256 SNPs i per workgroup
         std::vector<LdPairChr> pc;
@@ -2414,7 +2477,7 @@ int garlic_ld_counts(garlic_panel *p, int32_t winsize, int32_t phased, const int
             blocks += (p->chr_nloci[c] + LDM_TI - 1) / LDM_TI;
         }
         DevBuf<LdPairChr> &d_pc = p->lds.pair_chrs;
-        if ((rc = d_pc.reserve(pc.size()))) return done(rc);
+        if ((rc = d_pc.reserve(pc.size()))) return rc;
         e = hipMemcpyAsync(d_pc.p, pc.data(), sizeof(LdPairChr) * pc.size(), hipMemcpyHostToDevice, s);
         const void *fn = fuse_hr2 ? (mfma_nj <= 2 ? (const void *)ld_pair_mfma_kernel<2, true> : mfma_nj == 3 ? (const void *)ld_pair_mfma_kernel<3, true>
                                      : mfma_nj == 4 ? (const void *)ld_pair_mfma_kernel<4, true> : (const void *)ld_pair_mfma_kernel<5, true>)
@@ -2426,14 +2489,14 @@ int garlic_ld_counts(garlic_panel *p, int32_t winsize, int32_t phased, const int
         double *a_c = nullptr;
         if (fuse_hr2) {      // homFreq from the locus counts, room for the combined table (+ 1 KB: ld_sum_col_kernel's last request)
             const size_t n = (size_t)p->nloci * winsize;
-            if ((rc = p->lds.hf.reserve(p->nloci)) || (rc = p->lds.fwd.reserve(2 * n + 256))) return done(rc);
+            if ((rc = p->lds.hf.reserve(p->nloci)) || (rc = p->lds.fwd.reserve(2 * n + 256))) return rc;
             hipLaunchKernelGGL(ld_homfreq_kernel, dim3((unsigned)((p->nloci + 255) / 256)), dim3(256), 0, s, p->lds.loc_planes.p, p->nloci,
                                p->lds.hf.p);
             a_hf = p->lds.hf.p;
             a_c = p->lds.fwd.p;
         }
         if (e == hipSuccess && lds > 48 * 1024) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return done(fail(GARLIC_ERR_HIP, "LD counts: %s", hipGetErrorString(e)));
+        if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "LD counts: %s", hipGetErrorString(e));
         const uint64_t *a_m = d_m.p, *a_h = d_h.p;
         const LdPairChr *a_pc = d_pc.p;
         int a_nblk = nblk, a_nchr = p->nchr, a_w = winsize;
@@ -2442,7 +2505,7 @@ int garlic_ld_counts(garlic_panel *p, int32_t winsize, int32_t phased, const int
                          (void *)&a_hf, (void *)&a_c};
         e = hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(256), kargs, lds, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);   // pc (host) is read by the copy above
-        if (e != hipSuccess) return done(fail(GARLIC_ERR_HIP, "LD counts: %s", hipGetErrorString(e)));
+        if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "LD counts: %s", hipGetErrorString(e));
         p->lds.fused_done = fuse_hr2;
     }
     if (pair_lane) {   // all chromosomes in one grid, tiles of 256 SNPs
@@ -2453,12 +2516,12 @@ int garlic_ld_counts(garlic_panel *p, int32_t winsize, int32_t phased, const int
             blocks += (p->chr_nloci[c] + LD_LANE_T - 1) / LD_LANE_T;
         }
         DevBuf<LdPairChr> &d_pc = p->lds.pair_chrs;
-        if ((rc = d_pc.reserve(pc.size()))) return done(rc);
+        if ((rc = d_pc.reserve(pc.size()))) return rc;
         e = hipMemcpyAsync(d_pc.p, pc.data(), sizeof(LdPairChr) * pc.size(), hipMemcpyHostToDevice, s);
         const void *fn = lane_dc == 16 ? (phased ? (const void *)ld_pair_lane_kernel<true, 16> : (const void *)ld_pair_lane_kernel<false, 16>)
                                        : (phased ? (const void *)ld_pair_lane_kernel<true, 32> : (const void *)ld_pair_lane_kernel<false, 32>);
         if (e == hipSuccess && lane_lds > 48 * 1024) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lane_lds);
-        if (e != hipSuccess) return done(fail(GARLIC_ERR_HIP, "LD counts: %s", hipGetErrorString(e)));
+        if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "LD counts: %s", hipGetErrorString(e));
         const uint64_t *a_m = d_m.p, *a_h = d_h.p, *a_o = phased ? d_o.p : nullptr, *a_f = phased ? p->d_phase.p : nullptr;
         const LdPairChr *a_pc = d_pc.p;
         int a_nblk = nblk, a_nchr = p->nchr, a_w = winsize, a_stage = lane_stage;
@@ -2467,7 +2530,7 @@ int garlic_ld_counts(garlic_panel *p, int32_t winsize, int32_t phased, const int
                          (void *)&a_nchr, (void *)&a_w, (void *)&a_stage, (void *)&pair};
         e = hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(LD_LANE_T), kargs, lane_lds, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);   // pc (host) is read by the copy above
-        if (e != hipSuccess) return done(fail(GARLIC_ERR_HIP, "LD counts: %s", hipGetErrorString(e)));
+        if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "LD counts: %s", hipGetErrorString(e));
     }
     if (pair_flat) {
         const unsigned grid = (unsigned)(((int64_t)p->nloci * winsize + 255) / 256);
@@ -2494,8 +2557,8 @@ int garlic_ld_counts(garlic_panel *p, int32_t winsize, int32_t phased, const int
             e = hipMemcpyAsync(pair_counts, pair, sizeof(int32_t) * npair, hipMemcpyDeviceToHost, s);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return done(fail(GARLIC_ERR_HIP, "LD counts: %s", hipGetErrorString(e)));
-    return done(GARLIC_OK);
+    if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "LD counts: %s", hipGetErrorString(e));
+    return GARLIC_OK;
 }
 
 int garlic_ld_finish(garlic_panel *p, int32_t winsize, int32_t phased, const int32_t *locus_counts,
@@ -2509,11 +2572,10 @@ int garlic_ld_finish(garlic_panel *p, int32_t winsize, int32_t phased, const int
     DevBuf<int32_t> &d_loc = p->lds.loc, &d_pair = p->lds.pair;
     DevBuf<double> &d_hf = p->lds.hf, &d_fwd = p->lds.fwd, &d_bwd = p->lds.bwd, &d_ld = p->lds.ld;
     DevBuf<LdSumChr> &d_sum_chrs = p->lds.sum_chrs;
-    auto done = [&](int code) { return code; };   // the scratch stays with the panel
     const int32_t *loc = locus_counts, *pair = pair_counts;
     hipError_t e = hipSuccess;
     if (where == GARLIC_HOST) {
-        if ((rc = d_loc.reserve((size_t)p->nloci * 2)) || (rc = d_pair.reserve(n * 2))) return done(rc);
+        if ((rc = d_loc.reserve((size_t)p->nloci * 2)) || (rc = d_pair.reserve(n * 2))) return rc;
         e = hipMemcpyAsync(d_loc.p, locus_counts, sizeof(int32_t) * p->nloci * 2, hipMemcpyHostToDevice, s);
         if (e == hipSuccess)
             e = hipMemcpyAsync(d_pair.p, pair_counts, sizeof(int32_t) * n * 2, hipMemcpyHostToDevice, s);
@@ -2521,15 +2583,15 @@ int garlic_ld_finish(garlic_panel *p, int32_t winsize, int32_t phased, const int
     }
     // narrow windows (GARLIC's default --winsize is 10): hr2 evaluated in place, one thread per (window start, column)
     if (winsize <= LD_SMALL_MAX_W && !getenv("GARLIC_LD_NO_FLAT")) {
-        if ((rc = d_hf.reserve(p->nloci))) return done(rc);
+        if ((rc = d_hf.reserve(p->nloci))) return rc;
         double *ld = ld_out;
         if (where == GARLIC_HOST || !ld_out) {
-            if ((rc = d_ld.reserve(n))) return done(rc);
+            if ((rc = d_ld.reserve(n))) return rc;
             ld = d_ld.p;
         }
         if (e == hipSuccess) e = hipMemsetAsync(ld, 0, sizeof(double) * n, s);      // initLDData zero-fills
         if (e == hipSuccess && phased) e = hipMemcpyAsync(d_hf.p, p->freq.data(), sizeof(double) * p->nloci, hipMemcpyHostToDevice, s);
-        if (e != hipSuccess) return done(fail(GARLIC_ERR_HIP, "LD finish: %s", hipGetErrorString(e)));
+        if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "LD finish: %s", hipGetErrorString(e));
         if (!phased)
             hipLaunchKernelGGL(ld_homfreq_kernel, dim3((unsigned)((p->nloci + 255) / 256)), dim3(256), 0, s, loc, p->nloci, d_hf.p);
         garlic_ctx *ctx = p->ctx;
@@ -2540,14 +2602,14 @@ int garlic_ld_finish(garlic_panel *p, int32_t winsize, int32_t phased, const int
         (void)hipEventRecord(ctx->hist1[slot], s);
         ctx->n_calls++;
         e = hipGetLastError();
-        if (e != hipSuccess) return done(fail(GARLIC_ERR_HIP, "LD finish: %s", hipGetErrorString(e)));
-        if ((rc = install_ld(p, winsize, ld, false))) return done(rc);
+        if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "LD finish: %s", hipGetErrorString(e));
+        if ((rc = install_ld(p, winsize, ld, false))) return rc;
         if (where == GARLIC_HOST && ld_out) {
             e = hipMemcpyAsync(ld_out, ld, sizeof(double) * n, hipMemcpyDeviceToHost, s);
             if (e == hipSuccess) e = hipStreamSynchronize(s);
-            if (e != hipSuccess) return done(fail(GARLIC_ERR_HIP, "LD finish: %s", hipGetErrorString(e)));
+            if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "LD finish: %s", hipGetErrorString(e));
         }
-        return done(GARLIC_OK);
+        return GARLIC_OK;
     }
     // ordered sums: LDS-tiled kernel (one thread per column of the LD row) unless the window is too wide
     // ... thread = SNP of the window, accumulators = window starts (ld_sum_col_kernel: 32 < W <= 512) unless switched off
@@ -2560,12 +2622,12 @@ int garlic_ld_finish(garlic_panel *p, int32_t winsize, int32_t phased, const int
     // (the SNP-per-thread kernel reads one combined row of 2W doubles per SNP, in d_fwd; + 1 KB the last row's
     // last request may run over)
     if ((rc = d_hf.reserve(p->nloci)) || (rc = d_fwd.reserve(by_snp ? 2 * n + 256 : n)) || (!by_snp && (rc = d_bwd.reserve(n))))
-        return done(rc);
+        return rc;
     double *ld = ld_out;
     // nobody asked for the LD matrix itself and the sum kernel writes the wLOD weights directly: it is not made at all
     const bool weights_only = by_snp && !ld_out;
     if (!weights_only && (where == GARLIC_HOST || !ld_out)) {
-        if ((rc = d_ld.reserve(n))) return done(rc);
+        if ((rc = d_ld.reserve(n))) return rc;
         ld = d_ld.p;
     }
     // initLDData zero-fills; ld_sum_col_kernel writes every entry of the window starts that have a full window, which
@@ -2579,10 +2641,10 @@ int garlic_ld_finish(garlic_panel *p, int32_t winsize, int32_t phased, const int
     } else {
         e = hipMemsetAsync(ld, 0, sizeof(double) * n, s);
     }
-    if (e != hipSuccess) return done(fail(GARLIC_ERR_HIP, "LD finish: %s", hipGetErrorString(e)));
+    if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "LD finish: %s", hipGetErrorString(e));
     if (phased) {       // r2 takes FreqData::freq where hr2 takes homFreq (garlic-data.cpp:587-588)
         e = hipMemcpyAsync(d_hf.p, p->freq.data(), sizeof(double) * p->nloci, hipMemcpyHostToDevice, s);
-        if (e != hipSuccess) return done(fail(GARLIC_ERR_HIP, "LD finish: %s", hipGetErrorString(e)));
+        if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "LD finish: %s", hipGetErrorString(e));
     } else {
         hipLaunchKernelGGL(ld_homfreq_kernel, dim3((unsigned)((p->nloci + 255) / 256)), dim3(256), 0, s, loc,
                            p->nloci, d_hf.p);
@@ -2595,8 +2657,8 @@ int garlic_ld_finish(garlic_panel *p, int32_t winsize, int32_t phased, const int
         sum_chrs.push_back(LdSumChr{p->chr_off[c], nstarts, sum_blocks});
         sum_blocks += (nstarts + sum_b - 1) / sum_b;
     }
-    if (tiled && (rc = d_sum_chrs.reserve(std::max<size_t>(sum_chrs.size(), 1)))) return done(rc);
-    if (by_snp && (rc = reserve_skew(p, winsize, false))) return done(rc);      // the sum kernel writes the wLOD weights as well
+    if (tiled && (rc = d_sum_chrs.reserve(std::max<size_t>(sum_chrs.size(), 1)))) return rc;
+    if (by_snp && (rc = reserve_skew(p, winsize, false))) return rc;      // the sum kernel writes the wLOD weights as well
     for (int c = 0; c < p->nchr; c++) {
         const int64_t lo = p->chr_off[c], hi = p->chr_off[c + 1];
         const size_t hr2_lds = sizeof(double) * (LD_HR2_T + winsize + (size_t)LD_HR2_T * (winsize + 1));
@@ -2617,7 +2679,7 @@ int garlic_ld_finish(garlic_panel *p, int32_t winsize, int32_t phased, const int
     }
     if (tiled && !sum_chrs.empty()) {   // all chromosomes in one grid, after every hr2 value exists
         e = hipMemcpyAsync(d_sum_chrs.p, sum_chrs.data(), sizeof(LdSumChr) * sum_chrs.size(), hipMemcpyHostToDevice, s);
-        if (e != hipSuccess) return done(fail(GARLIC_ERR_HIP, "LD finish: %s", hipGetErrorString(e)));
+        if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "LD finish: %s", hipGetErrorString(e));
         const int threads = by_snp ? col_threads : (winsize + WAVE - 1) / WAVE * WAVE;
         const int col_pieces = (threads * 8 + 1023) / 1024;
         const size_t lds = by_snp ? sizeof(double) * std::max<size_t>((size_t)LD_COL_BATCH * LD_COL_NBATCH * col_pieces * 128 + 130, (size_t)threads * 17)
@@ -2633,7 +2695,7 @@ int garlic_ld_finish(garlic_panel *p, int32_t winsize, int32_t phased, const int
                                                                                                     : (const void *)ld_sum_col_kernel<5>;
             if (lds > 48 * 1024) {
                 e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                if (e != hipSuccess) return done(fail(GARLIC_ERR_HIP, "LD finish: %s", hipGetErrorString(e)));
+                if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "LD finish: %s", hipGetErrorString(e));
             }
             const double *a_c = d_fwd.p;
             const LdSumChr *a_chrs = d_sum_chrs.p;
@@ -2642,7 +2704,7 @@ int garlic_ld_finish(garlic_panel *p, int32_t winsize, int32_t phased, const int
             unsigned a_nwork = (unsigned)sum_blocks;
             void *kargs[] = {(void *)&a_c, (void *)&a_chrs, (void *)&a_nchr, (void *)&a_w, (void *)&a_b, (void *)&a_ld, (void *)&a_d, (void *)&a_nwork};
             e = hipLaunchKernel(fn, dim3((a_nwork + 7u) / 8u * 8u), dim3(threads), kargs, lds, s);
-            if (e != hipSuccess) return done(fail(GARLIC_ERR_HIP, "LD finish: %s", hipGetErrorString(e)));
+            if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "LD finish: %s", hipGetErrorString(e));
         }
         else
             hipLaunchKernelGGL(ld_sum_tiled_kernel, dim3((unsigned)sum_blocks), dim3(threads), lds, s, d_fwd.p, d_bwd.p,
@@ -2651,14 +2713,14 @@ int garlic_ld_finish(garlic_panel *p, int32_t winsize, int32_t phased, const int
         ctx->n_calls++;
     }
     e = hipGetLastError();
-    if (e != hipSuccess) return done(fail(GARLIC_ERR_HIP, "LD finish: %s", hipGetErrorString(e)));
-    if ((rc = install_ld(p, winsize, ld, by_snp))) return done(rc);
+    if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "LD finish: %s", hipGetErrorString(e));
+    if ((rc = install_ld(p, winsize, ld, by_snp))) return rc;
     if (where == GARLIC_HOST && ld_out) {
         e = hipMemcpyAsync(ld_out, ld, sizeof(double) * n, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return done(fail(GARLIC_ERR_HIP, "LD finish: %s", hipGetErrorString(e)));
+        if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "LD finish: %s", hipGetErrorString(e));
     }
-    return done(GARLIC_OK);
+    return GARLIC_OK;
 }
 
 int garlic_panel_compute_ld(garlic_panel *p, int32_t winsize, int32_t phased, const int32_t *sub_idx,
@@ -2827,7 +2889,6 @@ static int feed_single(garlic_panel *p, int32_t winsize, double error, int32_t m
     const int nblk = (p->nind + WAVE - 1) / WAVE;
     std::vector<uint8_t> blocks;
     DevBuf<int32_t> d_list;
-    auto done = [&](int code) { d_list.release(); return code; };
     if (ind_idx) {
         blocks.assign((size_t)nblk, 0);
         std::vector<uint8_t> seen((size_t)p->nind, 0);
@@ -2838,9 +2899,9 @@ static int feed_single(garlic_panel *p, int32_t winsize, double error, int32_t m
             seen[(size_t)i] = 1;
             blocks[(size_t)(i >> 6)] = 1;
         }
-        if ((rc = d_list.reserve((size_t)n_idx))) return done(rc);
+        if ((rc = d_list.reserve((size_t)n_idx))) return rc;
         hipError_t e = hipMemcpy(d_list.p, ind_idx, sizeof(int32_t) * (size_t)n_idx, hipMemcpyHostToDevice);
-        if (e != hipSuccess) return done(fail(GARLIC_ERR_HIP, "feed: %s", hipGetErrorString(e)));
+        if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "feed: %s", hipGetErrorString(e));
     }
     const int32_t n_rows = ind_idx ? n_idx : p->nind;
     // Unweighted --error scores with a real thinning step: the chain kernel stores only the sampled
@@ -2849,30 +2910,30 @@ static int feed_single(garlic_panel *p, int32_t winsize, double error, int32_t m
     // of 8 GB per call would cost more than the kernels) and are sampled from there.
     int32_t thinned = (!weighted && !use_gl && step >= 4) ? step : 0;
     if (thinned) {   // the exact chain (lod_exact_needed) writes full scores only
-        if (!p->have_freq) return done(fail(GARLIC_ERR_STATE, "panel needs map, freq and genotypes before computing LOD"));
-        if ((rc = ensure_term_table(p, error))) return done(rc);
+        if (!p->have_freq) return fail(GARLIC_ERR_STATE, "panel needs map, freq and genotypes before computing LOD");
+        if ((rc = ensure_term_table(p, error))) return rc;
         if (lod_exact_needed(p, MODE_LOD, winsize)) thinned = 0;
     }
     const Layout L = make_layout(p, 32, p->nind, thinned);
     garlic_panel::ScoreBuf &scores = p->d_out;
     DevBuf<double> &d_feed = p->d_feed;            // kept with the panel: window-size sweeps call this repeatedly
-    if ((rc = scores.reserve(p->ctx, (size_t)L.total))) return done(rc);
+    if ((rc = scores.reserve(p->ctx, (size_t)L.total))) return rc;
     if (weighted) p->wlod_use_gl = use_gl != 0;
     rc = launch_lod(p, weighted ? MODE_WLOD : (use_gl ? MODE_LOD_GL : MODE_LOD), winsize, error, max_gap, M, mu, 0,
                     p->nind, 32, scores.p, GARLIC_DEVICE, thinned, ind_idx ? &blocks : nullptr);
-    if (rc) return done(rc);
+    if (rc) return rc;
     // at most ceil(nloci_c / step) values per (chromosome, individual)
     int64_t cap = 0;
     for (int c = 0; c < p->nchr; c++) cap += ((int64_t)p->chr_nloci[c] + step - 1) / step * n_rows;
-    if ((rc = d_feed.reserve((size_t)std::max<int64_t>(cap, 1)))) return done(rc);
+    if ((rc = d_feed.reserve((size_t)std::max<int64_t>(cap, 1)))) return rc;
     if ((rc = flatten_impl(p, scores.p, 32, p->nind, step, d_feed.p, cap, count, chr_counts, thinned,
                            ind_idx ? d_list.p : nullptr, n_idx)))
-        return done(rc);
-    if (*count > feed_capacity || *count == 0) return done(GARLIC_OK);
-    if (!feed) return done(fail(GARLIC_ERR_INVALID, "feed is NULL"));
+        return rc;
+    if (*count > feed_capacity || *count == 0) return GARLIC_OK;
+    if (!feed) return fail(GARLIC_ERR_INVALID, "feed is NULL");
     hipError_t e = hipMemcpy(feed, d_feed.p, sizeof(double) * (size_t)*count, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return done(fail(GARLIC_ERR_HIP, "feed copy-out: %s", hipGetErrorString(e)));
-    return done(GARLIC_OK);
+    if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "feed copy-out: %s", hipGetErrorString(e));
+    return GARLIC_OK;
 }
 
 int garlic_lod_feed_subset(garlic_panel *p, int32_t winsize, double error, int32_t max_gap, int32_t use_gl,
@@ -3007,11 +3068,8 @@ int garlic_lod_feed_multi(garlic_panel *p, const int32_t *winsizes, const int32_
             col0[r] = (int32_t)nkeep[(size_t)runs[r].chr];
             nkeep[(size_t)runs[r].chr] += (runs[r].b - s) / step + 1;
         }
-        std::vector<int> order(runs.size());
-        for (size_t k = 0; k < runs.size(); k++) order[k] = (int)k;
-        std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return (runs[x].b - runs[x].a) > (runs[y].b - runs[y].a); });
         std::vector<FeedItem> items;
-        build_feed_items(runs, order, ind_idx ? &blocks : nullptr, nblk, col0, items);
+        build_feed_items(runs, longest_first(runs), ind_idx ? &blocks : nullptr, nblk, col0, items);
         std::vector<ChrDev> chrs((size_t)p->nchr);
         int64_t off = 0;
         for (int c = 0; c < p->nchr; c++) {
@@ -3074,23 +3132,43 @@ int garlic_lod_feed_multi(garlic_panel *p, const int32_t *winsizes, const int32_
 // (coverage_kernel.hpp).  Where that kernel does not apply -- a cutoff at or below MISSING, terms that are not all
 // finite, a window sum that can be -9999.0, W > COVF_MAX_W -- the scores are computed into the panel's scratch and
 // counted by garlic_roh_coverage.
-static int coverage_bits_layout(garlic_panel *p, std::vector<ChrDev> &bchrs, std::vector<int32_t> &word_base, int64_t &total)
-{
-    bchrs.assign((size_t)p->nchr, ChrDev{});
-    word_base.assign((size_t)p->nchr + 1, 0);
-    total = 0;
-    for (int c = 0; c < p->nchr; c++) {
-        const int64_t words = (p->chr_nloci[c] + 31) / 32;
-        bchrs[(size_t)c] = ChrDev{p->chr_off[c], total, words, p->chr_nloci[c], 0};
-        total += words * p->nind;
-        word_base[(size_t)c + 1] = word_base[(size_t)c] + (int32_t)words;
-        if (words * 4 * (int64_t)p->nind >= (int64_t)1 << 32) return fail(GARLIC_ERR_INVALID, "chromosome %d: bit rows beyond 32-bit offsets", c);
-    }
-    return GARLIC_OK;
-}
 
-// What becomes of the window bits: the sliding counts (garlic_roh_coverage_fused) or the ROH segments (garlic_roh_segments)
+// The window bits, one per window and individual: [chromosome][individual][word] on the device, with the two tables the
+// kernels that write and read them take (bchrs: out_base / out_pitch in dwords; word_base: words before each chromosome).
+struct BitMatrix {
+    std::vector<ChrDev> bchrs;
+    std::vector<int32_t> word_base;
+    int64_t total = 0;             // dwords
+    PoolBuf<uint32_t> d_bits;
+    DevBuf<ChrDev> d_bchrs;
+    DevBuf<int32_t> d_wbase;
+    // row_align: rows padded to a multiple of that many dwords (8 for lod_bits_kernel, which stores eight tiles' dwords as
+    // one aligned 32-byte piece; 1 for everything else).  Then room for the bits and the tables on their way.
+    int make(garlic_panel *p, int row_align)
+    {
+        bchrs.assign((size_t)p->nchr, ChrDev{});
+        word_base.assign((size_t)p->nchr + 1, 0);
+        for (int c = 0; c < p->nchr; c++) {
+            const int64_t words = (p->chr_nloci[c] + 31) / 32;
+            const int64_t row_words = (words + row_align - 1) / row_align * row_align;
+            bchrs[(size_t)c] = ChrDev{p->chr_off[c], total, row_words, p->chr_nloci[c], 0};
+            total += row_words * p->nind;
+            word_base[(size_t)c + 1] = word_base[(size_t)c] + (int32_t)words;
+            if (row_words * 4 * (int64_t)p->nind >= (int64_t)1 << 32) return fail(GARLIC_ERR_INVALID, "chromosome %d: bit rows beyond 32-bit offsets", c);
+        }
+        int rc;
+        if ((rc = d_bits.reserve(p->ctx, zeroed_words())) || (rc = d_bchrs.put(bchrs, p->ctx->stream))) return rc;
+        return d_wbase.put(word_base, p->ctx->stream);
+    }
+    // (never fewer than four dwords.  Zeroing is for kernels that set bits: one that writes every word needs none, a memset is traffic.)
+    size_t zeroed_words() const { return (size_t)std::max<int64_t>(total, 4); }
+    hipError_t zero(hipStream_t s) { return hipMemsetAsync(d_bits.p, 0, sizeof(uint32_t) * zeroed_words(), s); }
+};
+
+// The arguments of garlic_roh_coverage_fused / garlic_roh_segments: what becomes of the window bits, counts or segments
 struct CovSink {
+    int32_t W, max_gap, use_gl, weighted, M;
+    double error, mu, cutoff;
     int16_t *inwin = nullptr;            // counts
     int32_t inwin_pitch_align = 8, where = GARLIC_DEVICE;
     bool segments = false;               // segments
@@ -3099,11 +3177,62 @@ struct CovSink {
     int64_t cap = 0, *n_out = nullptr;
 };
 
-// ROH segments from the window bits (roh_segments_kernel.hpp): r bits, break bits, the list; sorted on the host into
-// the reference's order.  The bit matrix is [chromosome][individual][word], bchrs / word_base as coverage_bits_layout.
-static int segments_from_bits(garlic_panel *p, const uint32_t *d_bits, const ChrDev *d_bchrs, const std::vector<ChrDev> &bchrs,
-                              const std::vector<int32_t> &word_base, int32_t W, const CovSink &sink)
+// a layout as the kernels take it
+static std::vector<ChrDev> chr_table(const garlic_panel *p, const Layout &L)
 {
+    std::vector<ChrDev> chrs((size_t)p->nchr);
+    for (int c = 0; c < p->nchr; c++) chrs[(size_t)c] = ChrDev{p->chr_off[c], L.base[c], L.pitch[c], p->chr_nloci[c], 0};
+    return chrs;
+}
+
+// eight counts per store: every row of the count matrix 16-B aligned
+static bool cov_vec_ok(const garlic_panel *p, const Layout &Lo, const int16_t *dst)
+{
+    bool vec_ok = (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
+    for (int c = 0; c < p->nchr; c++) vec_ok = vec_ok && Lo.base[c] % 8 == 0 && Lo.pitch[c] % 8 == 0;
+    return vec_ok;
+}
+
+// where the counts are written: the caller's device matrix, or scratch that finish_counts copies to the caller's host matrix
+static int counts_target(int16_t *inwin, int32_t where, const Layout &Lo, DevBuf<int16_t> &d_cov, int16_t **dst)
+{
+    *dst = inwin;
+    if (where != GARLIC_HOST) return GARLIC_OK;
+    const int rc = d_cov.reserve((size_t)Lo.total);
+    *dst = d_cov.p;
+    return rc;
+}
+
+// the sliding counts from the window bits (d_ochrs: the count matrix's table on the device)
+static void launch_counts_from_bits(garlic_panel *p, const BitMatrix &bm, const CovSink &c, const Layout &Lo, const ChrDev *d_ochrs, int16_t *dst)
+{
+    hipLaunchKernelGGL(cov_counts_from_bits_kernel, dim3((unsigned)((bm.word_base[(size_t)p->nchr] + 255) / 256),
+                                                         (unsigned)((p->nind + COV_ITEM_ROWS - 1) / COV_ITEM_ROWS)),
+                       dim3(256), 0, p->ctx->stream, bm.d_bits.p, bm.d_bchrs.p, d_ochrs, bm.d_wbase.p, p->nchr, c.W, p->nind,
+                       cov_vec_ok(p, Lo, dst) ? 1 : 0, dst);
+}
+
+// the counts to the caller and the end of the call (d_timed_out: the flag of count items that rode in the chain kernel's queue)
+static int finish_counts(garlic_panel *p, int16_t *inwin, int32_t where, const Layout &Lo, const int16_t *dst, const int32_t *d_timed_out)
+{
+    hipStream_t s = p->ctx->stream;
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess && where == GARLIC_HOST)
+        e = hipMemcpyAsync(inwin, dst, sizeof(int16_t) * (size_t)Lo.total, hipMemcpyDeviceToHost, s);
+    int32_t timed_out = 0;
+    if (e == hipSuccess && d_timed_out) e = hipMemcpyAsync(&timed_out, d_timed_out, sizeof(int32_t), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "coverage: %s", hipGetErrorString(e));
+    if (!timed_out) return GARLIC_OK;
+    p->n_count_timeouts++;
+    return fail(GARLIC_ERR_HIP, "coverage: a count item gave up waiting for its chromosome's chains");
+}
+
+// ROH segments from the window bits (roh_segments_kernel.hpp): r bits, break bits, the list; sorted on the host into
+// the reference's order.
+static int segments_from_bits(garlic_panel *p, const BitMatrix &bm, const CovSink &sink)
+{
+    const int32_t W = sink.W;
     garlic_ctx *ctx = p->ctx;
     hipStream_t s = ctx->stream;
     double T = sink.overlap_frac * W;              // src/garlic-roh.cpp:421-423
@@ -3111,337 +3240,226 @@ static int segments_from_bits(garlic_panel *p, const uint32_t *d_bits, const Chr
     T = (T <= W) ? T : W;
     const int thr = (int)std::ceil(T);             // counts are integers: cnt >= T  <=>  cnt >= ceil(T)
     const size_t nchr = (size_t)p->nchr;
-    const int64_t total_words = word_base[nchr];
+    const int64_t total_words = bm.word_base[nchr];
     int64_t bit_words = 0;
-    for (size_t c = 0; c < nchr; c++) bit_words = std::max<int64_t>(bit_words, bchrs[c].out_base + bchrs[c].out_pitch * p->nind);
+    for (size_t c = 0; c < nchr; c++) bit_words = std::max<int64_t>(bit_words, bm.bchrs[c].out_base + bm.bchrs[c].out_pitch * p->nind);
     PoolBuf<uint32_t> d_mask;
     PoolBuf<garlic_roh_segment> d_segs;
     DevBuf<uint32_t> d_brk;
-    DevBuf<int32_t> d_wbase;
     DevBuf<unsigned long long> d_count;
     DevBuf<int32_t> d_w0, d_wedge_chr;             // chromosomes whose first SNP is at position 0 (roh_segments_kernel.hpp)
     std::vector<int32_t> wedge_chr;
     for (int c = 0; c < p->nchr; c++)
         if (p->chr_nloci[c] > 0 && p->pos[(size_t)p->chr_off[c]] == 0) wedge_chr.push_back(c);
-    auto done = [&](int code) { d_mask.release(); d_brk.release(); d_wbase.release(); d_segs.release(); d_count.release();
-                                d_w0.release(); d_wedge_chr.release(); return code; };
     int rc;
     const int64_t cap = std::max<int64_t>(sink.cap, 0);
     if ((rc = d_mask.reserve(ctx, (size_t)std::max<int64_t>(bit_words, 1))) || (rc = d_brk.reserve((size_t)std::max<int64_t>(total_words, 1))) ||
-        (rc = d_wbase.reserve(word_base.size())) || (rc = d_segs.reserve(ctx, (size_t)std::max<int64_t>(cap, 1))) || (rc = d_count.reserve(1)))
-        return done(rc);
-    hipError_t e = hipMemcpyAsync(d_wbase.p, word_base.data(), sizeof(int32_t) * word_base.size(), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemsetAsync(d_brk.p, 0, sizeof(uint32_t) * (size_t)std::max<int64_t>(total_words, 1), s);
+        (rc = d_segs.reserve(ctx, (size_t)std::max<int64_t>(cap, 1))) || (rc = d_count.reserve(1)))
+        return rc;
+    hipError_t e = hipMemsetAsync(d_brk.p, 0, sizeof(uint32_t) * (size_t)std::max<int64_t>(total_words, 1), s);
     if (e == hipSuccess) e = hipMemsetAsync(d_count.p, 0, sizeof(unsigned long long), s);
-    if (e != hipSuccess) return done(fail(GARLIC_ERR_HIP, "roh segments: %s", hipGetErrorString(e)));
+    if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "roh segments: %s", hipGetErrorString(e));
     unsigned long long found = 0;
     if (total_words > 0) {
         const int nb = (int)p->boundaries.size();
         if (nb > 0)
             hipLaunchKernelGGL(roh_break_bits_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s, p->d_boundaries.p, nb,
-                               p->d_chr_off.p, d_wbase.p, p->nchr, d_brk.p);
+                               p->d_chr_off.p, bm.d_wbase.p, p->nchr, d_brk.p);
         const dim3 grid((unsigned)((total_words + 255) / 256), (unsigned)((p->nind + ROH_ROWS - 1) / ROH_ROWS));
-        hipLaunchKernelGGL(roh_mask_from_bits_kernel, grid, dim3(256), 0, s, d_bits, d_bchrs, d_wbase.p, p->nchr, p->nind, W, thr, d_mask.p);
+        hipLaunchKernelGGL(roh_mask_from_bits_kernel, grid, dim3(256), 0, s, bm.d_bits.p, bm.d_bchrs.p, bm.d_wbase.p, p->nchr, p->nind, W, thr, d_mask.p);
         const int32_t *a_w0 = nullptr;
         if (!wedge_chr.empty()) {
             const size_t n_w0 = nchr * (size_t)p->nind;
-            if ((rc = d_w0.reserve(n_w0)) || (rc = d_wedge_chr.reserve(wedge_chr.size()))) return done(rc);
+            if ((rc = d_w0.reserve(n_w0)) || (rc = d_wedge_chr.reserve(wedge_chr.size()))) return rc;
             e = hipMemsetAsync(d_w0.p, 0xff, sizeof(int32_t) * n_w0, s);            // -1: an ordinary row
             if (e == hipSuccess)
                 e = hipMemcpyAsync(d_wedge_chr.p, wedge_chr.data(), sizeof(int32_t) * wedge_chr.size(), hipMemcpyHostToDevice, s);
-            if (e != hipSuccess) return done(fail(GARLIC_ERR_HIP, "roh segments: %s", hipGetErrorString(e)));
+            if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "roh segments: %s", hipGetErrorString(e));
             const int n_threads = (int)wedge_chr.size() * p->nind;
-            hipLaunchKernelGGL(roh_wedge_kernel, dim3((unsigned)((n_threads + 63) / 64)), dim3(64), 0, s, d_mask.p, d_bchrs, d_brk.p, d_wbase.p,
+            hipLaunchKernelGGL(roh_wedge_kernel, dim3((unsigned)((n_threads + 63) / 64)), dim3(64), 0, s, d_mask.p, bm.d_bchrs.p, d_brk.p, bm.d_wbase.p,
                                d_wedge_chr.p, (int)wedge_chr.size(), p->nind, T, d_w0.p, d_segs.p, (long long)cap, d_count.p);
             a_w0 = d_w0.p;
         }
-        hipLaunchKernelGGL(roh_segments_from_mask_kernel, grid, dim3(256), 0, s, d_mask.p, d_bchrs, d_brk.p, d_wbase.p, p->nchr, p->nind, T,
+        hipLaunchKernelGGL(roh_segments_from_mask_kernel, grid, dim3(256), 0, s, d_mask.p, bm.d_bchrs.p, d_brk.p, bm.d_wbase.p, p->nchr, p->nind, T,
                            d_segs.p, (long long)cap, d_count.p, a_w0);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(&found, d_count.p, sizeof found, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return done(fail(GARLIC_ERR_HIP, "roh segments: %s", hipGetErrorString(e)));
+        if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "roh segments: %s", hipGetErrorString(e));
     }
     if (sink.n_out) *sink.n_out = (int64_t)found;
     if ((int64_t)found <= cap && found > 0) {
         e = hipMemcpyAsync(sink.segs, d_segs.p, sizeof(garlic_roh_segment) * found, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return done(fail(GARLIC_ERR_HIP, "roh segments: %s", hipGetErrorString(e)));
+        if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "roh segments: %s", hipGetErrorString(e));
         std::sort(sink.segs, sink.segs + found, [](const garlic_roh_segment &x, const garlic_roh_segment &y) {
             return x.ind != y.ind ? x.ind < y.ind : x.chr != y.chr ? x.chr < y.chr : x.start < y.start;
         });
     }
-    return done(GARLIC_OK);
+    return GARLIC_OK;
 }
 
-static int coverage_impl(garlic_panel *p, int32_t winsize, double error, int32_t max_gap, int32_t use_gl,
-                         int32_t weighted, int32_t M, double mu, double cutoff, const CovSink &sink)
+// scores into the panel's scratch, then garlic_roh_coverage; for segments the scores' bits, then as from the chains' bits
+static int coverage_unfused(garlic_panel *p, const CovSink &c)
 {
-    int16_t *const inwin = sink.inwin;
-    const int32_t inwin_pitch_align = sink.inwin_pitch_align, where = sink.where;
-    garlic_ctx *ctx = p->ctx;
+    hipStream_t s = p->ctx->stream;
+    const Layout L = make_layout(p, 32, p->nind);
     int rc;
-    if ((rc = set_device(ctx))) return rc;
-    if (!p->have_map || !p->have_freq || !p->have_geno)
-        return fail(GARLIC_ERR_STATE, "panel needs map, freq and genotypes before computing LOD");
-    if ((rc = ensure_segments(p, max_gap))) return rc;
-    if ((rc = ensure_term_table(p, error))) return rc;
-    const int32_t W = winsize;
-    auto unfused = [&]() -> int {      // scores into the panel's scratch, then garlic_roh_coverage
-        const Layout L = make_layout(p, 32, p->nind);
-        int rc2;
-        if ((rc2 = p->d_out.reserve(ctx, (size_t)L.total))) return rc2;
-        if (weighted) rc2 = garlic_wlod_windows(p, W, error, max_gap, use_gl, M, mu, 0, p->nind, 32, p->d_out.p, GARLIC_DEVICE);
-        else rc2 = garlic_lod_windows(p, W, error, max_gap, use_gl, 0, p->nind, 32, p->d_out.p, GARLIC_DEVICE);
-        if (rc2) return rc2;
-        if (!sink.segments) return garlic_roh_coverage(p, p->d_out.p, 32, p->nind, W, cutoff, inwin, inwin_pitch_align, where);
-        // segments: the scores' bits (score >= cutoff, MISSING compared like any score), then as from the chains' bits
-        std::vector<ChrDev> bchrs, schrs((size_t)p->nchr);
-        std::vector<int32_t> word_base;
-        int64_t boff = 0;
-        if ((rc2 = coverage_bits_layout(p, bchrs, word_base, boff))) return rc2;
-        for (int c = 0; c < p->nchr; c++) schrs[(size_t)c] = ChrDev{p->chr_off[c], L.base[c], L.pitch[c], p->chr_nloci[c], 0};
-        PoolBuf<uint32_t> d_bits;
-        DevBuf<ChrDev> d_bchrs, d_schrs;
-        DevBuf<int32_t> d_wbase;
-        auto done = [&](int code) { d_bits.release(); d_bchrs.release(); d_schrs.release(); d_wbase.release(); return code; };
-        if ((rc2 = d_bits.reserve(ctx, (size_t)std::max<int64_t>(boff, 1))) || (rc2 = d_bchrs.reserve(bchrs.size())) ||
-            (rc2 = d_schrs.reserve(schrs.size())) || (rc2 = d_wbase.reserve(word_base.size())))
-            return done(rc2);
-        hipStream_t s2 = ctx->stream;
-        hipError_t e2 = hipMemcpyAsync(d_bchrs.p, bchrs.data(), sizeof(ChrDev) * bchrs.size(), hipMemcpyHostToDevice, s2);
-        if (e2 == hipSuccess) e2 = hipMemcpyAsync(d_schrs.p, schrs.data(), sizeof(ChrDev) * schrs.size(), hipMemcpyHostToDevice, s2);
-        if (e2 == hipSuccess) e2 = hipMemcpyAsync(d_wbase.p, word_base.data(), sizeof(int32_t) * word_base.size(), hipMemcpyHostToDevice, s2);
-        if (e2 != hipSuccess) return done(fail(GARLIC_ERR_HIP, "roh segments: %s", hipGetErrorString(e2)));
-        if (word_base[(size_t)p->nchr] > 0)
-            hipLaunchKernelGGL(roh_bits_from_scores_kernel, dim3((unsigned)((word_base[(size_t)p->nchr] + 255) / 256), (unsigned)p->nind),
-                               dim3(256), 0, s2, p->d_out.p, d_schrs.p, d_bchrs.p, d_wbase.p, p->nchr, W, cutoff, d_bits.p);
-        e2 = hipStreamSynchronize(s2);      // (the host vectors above)
-        if (e2 != hipSuccess) return done(fail(GARLIC_ERR_HIP, "roh segments: %s", hipGetErrorString(e2)));
-        return done(segments_from_bits(p, d_bits.p, d_bchrs.p, bchrs, word_base, W, sink));
-    };
+    if ((rc = p->d_out.reserve(p->ctx, (size_t)L.total))) return rc;
+    if (c.weighted) rc = garlic_wlod_windows(p, c.W, c.error, c.max_gap, c.use_gl, c.M, c.mu, 0, p->nind, 32, p->d_out.p, GARLIC_DEVICE);
+    else rc = garlic_lod_windows(p, c.W, c.error, c.max_gap, c.use_gl, 0, p->nind, 32, p->d_out.p, GARLIC_DEVICE);
+    if (rc) return rc;
+    if (!c.segments) return garlic_roh_coverage(p, p->d_out.p, 32, p->nind, c.W, c.cutoff, c.inwin, c.inwin_pitch_align, c.where);
+    // (score >= cutoff, MISSING compared like any score; the kernel writes every word of the matrix)
+    const std::vector<ChrDev> schrs = chr_table(p, L);
+    BitMatrix bm;
+    DevBuf<ChrDev> d_schrs;
+    if ((rc = bm.make(p, 1)) || (rc = d_schrs.put(schrs, s))) return rc;
+    if (bm.word_base[(size_t)p->nchr] > 0)
+        hipLaunchKernelGGL(roh_bits_from_scores_kernel, dim3((unsigned)((bm.word_base[(size_t)p->nchr] + 255) / 256), (unsigned)p->nind),
+                           dim3(256), 0, s, p->d_out.p, d_schrs.p, bm.d_bchrs.p, bm.d_wbase.p, p->nchr, c.W, c.cutoff, bm.d_bits.p);
+    const hipError_t e = hipStreamSynchronize(s);      // (the host vectors above)
+    if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "roh segments: %s", hipGetErrorString(e));
+    return segments_from_bits(p, bm, c);
+}
+
+// --weighted (with or without likelihoods), or unweighted scores with likelihoods: the tuned wLOD kernels leave 16 bits per
+// individual and group instead of 16 scores (wlod_write_group), the TGLS ring chain a dword of bits per lane and tile; the
+// counts come from the bits as for the unweighted scores
+static int coverage_from_score_kernels(garlic_panel *p, const CovSink &c)
+{
+    hipStream_t s = p->ctx->stream;
+    const Layout Lo = make_layout(p, c.inwin_pitch_align, p->nind);
+    const std::vector<ChrDev> ochrs = chr_table(p, Lo);
+    BitMatrix bm;
+    DevBuf<ChrDev> d_ochrs;
+    DevBuf<int16_t> d_cov;
+    int16_t *dst;
+    int rc;
+    if ((rc = bm.make(p, 1)) || (rc = d_ochrs.put(ochrs, s)) || (rc = counts_target(c.inwin, c.where, Lo, d_cov, &dst))) return rc;
+    hipError_t e = bm.zero(s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);      // (the host vectors above)
+    if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "coverage: %s", hipGetErrorString(e));
+    p->cov_pending = CovBits{bm.d_bits.p, bm.d_bchrs.p, c.cutoff};
+    p->cov_written = false;
+    double *bits_as_out = reinterpret_cast<double *>(bm.d_bits.p);
+    if (c.weighted) rc = garlic_wlod_windows(p, c.W, c.error, c.max_gap, c.use_gl, c.M, c.mu, 0, p->nind, 32, bits_as_out, GARLIC_DEVICE);
+    else rc = garlic_lod_windows(p, c.W, c.error, c.max_gap, 1, 0, p->nind, 32, bits_as_out, GARLIC_DEVICE);
+    const bool written = c.weighted || p->cov_written;
+    p->cov_pending = CovBits{nullptr, nullptr, 0.0};
+    if (rc == GARLIC_INTERNAL_NO_BITS) return coverage_unfused(p, c);
+    if (rc) return rc;
+    if (!written) return coverage_unfused(p, c);       // (no scored window at all: nothing was launched)
+    if (c.segments) return segments_from_bits(p, bm, c);
+    launch_counts_from_bits(p, bm, c, Lo, d_ochrs.p, dst);
+    return finish_counts(p, c.inwin, c.where, Lo, dst, nullptr);
+}
+
+// unweighted --error scores.  Two kernels: one bit per window and individual from the hand-scheduled chain
+// (lod_bits_kernel), then the sliding counts from the bits (cov_counts_from_bits_kernel): a 64th of the score bytes in between
+static int coverage_lod_bits(garlic_panel *p, const CovSink &c)
+{
+    garlic_ctx *ctx = p->ctx;
     hipStream_t s = ctx->stream;
-    if ((weighted || use_gl) && cutoff > MISSING_D && !getenv("GARLIC_COVERAGE_UNFUSED")) {
-        // --weighted (with or without likelihoods): the tuned wLOD kernels leave 16 bits per individual and group instead
-        // of 16 scores (wlod_write_group), the counts come from the bits as for the unweighted scores
-        std::vector<ChrDev> bchrs;
-        std::vector<int32_t> word_base;
-        int64_t boff = 0;
-        if ((rc = coverage_bits_layout(p, bchrs, word_base, boff))) return rc;
-        const Layout Lo = make_layout(p, inwin_pitch_align, p->nind);
-        std::vector<ChrDev> ochrs((size_t)p->nchr);
-        for (int c = 0; c < p->nchr; c++) ochrs[(size_t)c] = ChrDev{p->chr_off[c], Lo.base[c], Lo.pitch[c], p->chr_nloci[c], 0};
-        PoolBuf<uint32_t> d_bits;
-        DevBuf<ChrDev> d_bchrs, d_ochrs;
-        DevBuf<int32_t> d_wbase;
-        DevBuf<int16_t> d_cov;
-        auto done = [&](int code) { d_bits.release(); d_bchrs.release(); d_ochrs.release(); d_wbase.release(); d_cov.release(); return code; };
-        if ((rc = d_bits.reserve(ctx, (size_t)std::max<int64_t>(boff, 4))) || (rc = d_bchrs.reserve(bchrs.size())) ||
-            (rc = d_ochrs.reserve(ochrs.size())) || (rc = d_wbase.reserve(word_base.size())))
-            return done(rc);
-        int16_t *dst = inwin;
-        if (where == GARLIC_HOST) {
-            if ((rc = d_cov.reserve((size_t)Lo.total))) return done(rc);
-            dst = d_cov.p;
-        }
-        hipError_t e = hipMemcpyAsync(d_bchrs.p, bchrs.data(), sizeof(ChrDev) * bchrs.size(), hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_ochrs.p, ochrs.data(), sizeof(ChrDev) * ochrs.size(), hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_wbase.p, word_base.data(), sizeof(int32_t) * word_base.size(), hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemsetAsync(d_bits.p, 0, sizeof(uint32_t) * (size_t)std::max<int64_t>(boff, 4), s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);      // (the host vectors above)
-        if (e != hipSuccess) return done(fail(GARLIC_ERR_HIP, "coverage: %s", hipGetErrorString(e)));
-        p->cov_pending = CovBits{d_bits.p, d_bchrs.p, cutoff};
-        p->cov_written = false;
-        if (weighted)
-            rc = garlic_wlod_windows(p, W, error, max_gap, use_gl, M, mu, 0, p->nind, 32, reinterpret_cast<double *>(d_bits.p), GARLIC_DEVICE);
-        else      // unweighted scores with likelihoods: the TGLS ring chain leaves a dword of bits per lane and tile
-            rc = garlic_lod_windows(p, W, error, max_gap, 1, 0, p->nind, 32, reinterpret_cast<double *>(d_bits.p), GARLIC_DEVICE);
-        const bool written = weighted || p->cov_written;
-        p->cov_pending = CovBits{nullptr, nullptr, 0.0};
-        if (rc == GARLIC_INTERNAL_NO_BITS) return done(unfused());
-        if (rc) return done(rc);
-        if (!written) return done(unfused());       // (no scored window at all: nothing was launched)
-        if (sink.segments) return done(segments_from_bits(p, d_bits.p, d_bchrs.p, bchrs, word_base, W, sink));
-        bool vec_ok = (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
-        for (int c = 0; c < p->nchr; c++) vec_ok = vec_ok && Lo.base[c] % 8 == 0 && Lo.pitch[c] % 8 == 0;
-        hipLaunchKernelGGL(cov_counts_from_bits_kernel, dim3((unsigned)((word_base[(size_t)p->nchr] + 255) / 256),
-                                                             (unsigned)((p->nind + COV_ITEM_ROWS - 1) / COV_ITEM_ROWS)),
-                           dim3(256), 0, s, d_bits.p, d_bchrs.p, d_ochrs.p, d_wbase.p, p->nchr, W, p->nind, vec_ok ? 1 : 0, dst);
-        e = hipGetLastError();
-        if (e == hipSuccess && where == GARLIC_HOST)
-            e = hipMemcpyAsync(inwin, dst, sizeof(int16_t) * (size_t)Lo.total, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return done(fail(GARLIC_ERR_HIP, "coverage: %s", hipGetErrorString(e)));
-        return done(GARLIC_OK);
-    }
-    const bool fused = !weighted && !use_gl && W <= COVF_MAX_W && cutoff > MISSING_D && p->tab_all_finite &&
-                       !lod_exact_needed(p, MODE_LOD, W) && !getenv("GARLIC_COVERAGE_UNFUSED");
-    if (!fused) return unfused();
-    const int nblk = (p->nind + WAVE - 1) / WAVE;
+    const int32_t W = c.W;
+    const size_t nchr = (size_t)p->nchr;
     std::vector<Run> runs;
     std::vector<FillItem> fill;
     int64_t n_valid = 0;
     plan_runs(p, W, runs, fill, n_valid);              // in chromosome and position order
-    std::vector<int> order(runs.size());
-    for (size_t k = 0; k < runs.size(); k++) order[k] = (int)k;
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return (runs[x].b - runs[x].a) > (runs[y].b - runs[y].a); });
     std::vector<int32_t> col0(runs.size(), 0);
     std::vector<FeedItem> items;
-    build_feed_items(runs, order, nullptr, nblk, col0, items);
-    const Layout Lo = make_layout(p, inwin_pitch_align, p->nind);
-    std::vector<ChrDev> chrs((size_t)p->nchr);
-    for (int c = 0; c < p->nchr; c++) chrs[(size_t)c] = ChrDev{p->chr_off[c], Lo.base[c], Lo.pitch[c], p->chr_nloci[c], 0};
+    build_feed_items(runs, longest_first(runs), nullptr, (p->nind + WAVE - 1) / WAVE, col0, items);
+    const Layout Lo = make_layout(p, c.inwin_pitch_align, p->nind);
+    const std::vector<ChrDev> chrs = chr_table(p, Lo);
+    BitMatrix bm;
     DevBuf<FeedItem> d_items;
     DevBuf<ChrDev> d_chrs;
-    DevBuf<int32_t> d_counter;
+    DevBuf<int32_t> d_counter, d_cnt;      // d_cnt: chr_done[nchr] | timeout | chr_need[nchr] | cnt_order[nchr] | cnt_base[nchr + 1]
     DevBuf<int16_t> d_cov;
-    auto done = [&](int code) { d_items.release(); d_chrs.release(); d_counter.release(); d_cov.release(); return code; };
-    if ((rc = d_items.reserve(std::max<size_t>(items.size(), 1))) || (rc = d_chrs.reserve(chrs.size())) ||
-        (rc = d_counter.reserve(4)))
-        return done(rc);
-    int16_t *dst = inwin;
-    if (where == GARLIC_HOST) {
-        if ((rc = d_cov.reserve((size_t)Lo.total))) return done(rc);
-        dst = d_cov.p;
-    }
-    hipError_t e = hipMemcpyAsync(d_chrs.p, chrs.data(), sizeof(ChrDev) * chrs.size(), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && !items.empty())
-        e = hipMemcpyAsync(d_items.p, items.data(), sizeof(FeedItem) * items.size(), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemsetAsync(d_counter.p, 0, 4 * sizeof(int32_t), s);
-    if (e != hipSuccess) return done(fail(GARLIC_ERR_HIP, "coverage: %s", hipGetErrorString(e)));
-    bool vec_ok = (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
-    for (int c = 0; c < p->nchr; c++) vec_ok = vec_ok && Lo.base[c] % 8 == 0 && Lo.pitch[c] % 8 == 0;
-    const int slot = (int)(ctx->n_calls % garlic_ctx::HIST);
-    {
-        // two kernels: one bit per window and individual from the hand-scheduled chain (lod_bits_kernel), then the
-        // sliding counts from the bits (cov_counts_from_bits_kernel): a 64th of the score bytes in between
-        std::vector<ChrDev> bchrs((size_t)p->nchr);
-        std::vector<int32_t> word_base((size_t)p->nchr + 1, 0);
-        int64_t boff = 0;
-        for (int c = 0; c < p->nchr; c++) {
-            const int64_t words = (p->chr_nloci[c] + 31) / 32;
-            // rows a multiple of eight dwords long: the chain kernel stores eight tiles' dwords as one aligned 32-byte piece
-            const int64_t row_words = (words + 7) / 8 * 8;
-            bchrs[(size_t)c] = ChrDev{p->chr_off[c], boff, row_words, p->chr_nloci[c], 0};
-            boff += row_words * p->nind;
-            word_base[(size_t)c + 1] = word_base[(size_t)c] + (int32_t)words;
-            if (row_words * 4 * (int64_t)p->nind >= (int64_t)1 << 32)
-                return done(fail(GARLIC_ERR_INVALID, "chromosome %d: bit rows beyond 32-bit offsets", c));
+    int16_t *dst;
+    int rc;
+    if ((rc = d_items.put(items, s)) || (rc = d_chrs.put(chrs, s)) || (rc = d_counter.reserve(4)) || (rc = counts_target(c.inwin, c.where, Lo, d_cov, &dst)))
+        return rc;
+    hipError_t e = hipMemsetAsync(d_counter.p, 0, 4 * sizeof(int32_t), s);
+    if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "coverage: %s", hipGetErrorString(e));
+    const bool vec_ok = cov_vec_ok(p, Lo, dst);
+    if ((rc = bm.make(p, 8))) return rc;
+    (void)hist_mark(ctx, false);
+    if ((e = bm.zero(s)) != hipSuccess) return fail(GARLIC_ERR_HIP, "coverage: %s", hipGetErrorString(e));
+    // GARLIC_COVERAGE_OVERLAP=1: the counts ride in the chain kernel's queue (FeedArgs::cnt_order) instead of a launch of
+    // their own behind it -- the longest runs' chains are that kernel's critical path and leave most of the chip idle,
+    // the counts of every finished chromosome could fill it.  Built and measured ("Coverage
+    // counts without the scores"): the chains are latency-bound and the counts' traffic slows the longest one from
+    // 22.8 to 36.5 ns per window, 19.5 ms against 17.6 ms for the two launches at 10M x 1250.  Off by default.
+    const bool overlap = !items.empty() && !c.segments && getenv("GARLIC_COVERAGE_OVERLAP");
+    int64_t n_cnt_items = 0;
+    if (overlap) {
+        std::vector<int32_t> h(4 * nchr + 2, 0);
+        int32_t *need = h.data() + nchr + 1, *corder = need + nchr, *cbase = corder + nchr;
+        std::vector<int32_t> longest(nchr, 0);
+        for (const FeedItem &it : items) need[it.chr]++;
+        for (const Run &r : runs) longest[(size_t)r.chr] = std::max(longest[(size_t)r.chr], r.b - r.a + 1);
+        for (size_t k = 0; k < nchr; k++) corder[k] = (int32_t)k;
+        std::stable_sort(corder, corder + nchr, [&](int32_t x, int32_t y) { return longest[(size_t)x] < longest[(size_t)y]; });
+        const int64_t nrg = (p->nind + COV_ITEM_ROWS - 1) / COV_ITEM_ROWS;
+        for (size_t k = 0; k < nchr; k++) {
+            cbase[k] = (int32_t)n_cnt_items;
+            const int64_t words = (p->chr_nloci[corder[k]] + 31) / 32;
+            n_cnt_items += (words + COV_ITEM_WORDS - 1) / COV_ITEM_WORDS * nrg;
         }
-        PoolBuf<uint32_t> d_bits;
-        DevBuf<ChrDev> d_bchrs;
-        DevBuf<int32_t> d_wbase;
-        auto done2 = [&](int code) { d_bits.release(); d_bchrs.release(); d_wbase.release(); return done(code); };
-        if ((rc = d_bits.reserve(ctx, (size_t)std::max<int64_t>(boff, 1))) || (rc = d_bchrs.reserve(bchrs.size())) ||
-            (rc = d_wbase.reserve(word_base.size())))
-            return done2(rc);
-        e = hipMemcpyAsync(d_bchrs.p, bchrs.data(), sizeof(ChrDev) * bchrs.size(), hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_wbase.p, word_base.data(), sizeof(int32_t) * word_base.size(), hipMemcpyHostToDevice, s);
-        (void)hipEventRecord(ctx->hist0[slot], s);
-        if (e == hipSuccess) e = hipMemsetAsync(d_bits.p, 0, sizeof(uint32_t) * (size_t)boff, s);
-        if (e != hipSuccess) return done2(fail(GARLIC_ERR_HIP, "coverage: %s", hipGetErrorString(e)));
-        // GARLIC_COVERAGE_OVERLAP=1: the counts ride in the chain kernel's queue (FeedArgs::cnt_order) instead of a launch of
-        // their own behind it -- the longest runs' chains are that kernel's critical path and leave most of the chip idle,
-        // the counts of every finished chromosome could fill it.  Built and measured ("Coverage
-        // counts without the scores"): the chains are latency-bound and the counts' traffic slows the longest one from
-        // 22.8 to 36.5 ns per window, 19.5 ms against 17.6 ms for the two launches at 10M x 1250.  Off by default.
-        const bool overlap = !items.empty() && !sink.segments && getenv("GARLIC_COVERAGE_OVERLAP");
-        DevBuf<int32_t> d_cnt;      // chr_done[nchr] | timeout | chr_need[nchr] | cnt_order[nchr] | cnt_base[nchr + 1]
-        auto done3 = [&](int code) { d_cnt.release(); return done2(code); };
-        const size_t nchr = (size_t)p->nchr;
-        int64_t n_cnt_items = 0;
+        cbase[nchr] = (int32_t)n_cnt_items;
+        if (n_cnt_items + (int64_t)items.size() >= ((int64_t)1 << 31)) return fail(GARLIC_ERR_INVALID, "coverage: more than 2^31 work items");
+        if ((rc = d_cnt.put(h, s))) return rc;
+        if ((e = hipStreamSynchronize(s)) != hipSuccess) return fail(GARLIC_ERR_HIP, "coverage: %s", hipGetErrorString(e));      // (h leaves scope)
+    }
+    if (!items.empty()) {
+        FeedArgs f{p->d_packed.p, p->d_tab.p, d_items.p, bm.d_bchrs.p, reinterpret_cast<double *>(bm.d_bits.p), nullptr, p->nwordrows, 0,
+                   p->nind, W, (int32_t)items.size(), 1, getenv("GARLIC_FEED_NO_ASM") ? 0 : 1, d_counter.p, nullptr, c.cutoff};
         if (overlap) {
-            std::vector<int32_t> h(4 * nchr + 2, 0);
-            int32_t *need = h.data() + nchr + 1, *corder = need + nchr, *cbase = corder + nchr;
-            std::vector<int32_t> longest(nchr, 0);
-            for (const FeedItem &it : items) need[it.chr]++;
-            for (const Run &r : runs) longest[(size_t)r.chr] = std::max(longest[(size_t)r.chr], r.b - r.a + 1);
-            for (size_t c = 0; c < nchr; c++) corder[c] = (int32_t)c;
-            std::stable_sort(corder, corder + nchr, [&](int32_t x, int32_t y) { return longest[(size_t)x] < longest[(size_t)y]; });
-            const int64_t nrg = (p->nind + COV_ITEM_ROWS - 1) / COV_ITEM_ROWS;
-            for (size_t k = 0; k < nchr; k++) {
-                cbase[k] = (int32_t)n_cnt_items;
-                const int64_t words = (p->chr_nloci[corder[k]] + 31) / 32;
-                n_cnt_items += (words + COV_ITEM_WORDS - 1) / COV_ITEM_WORDS * nrg;
-            }
-            cbase[nchr] = (int32_t)n_cnt_items;
-            if (n_cnt_items + (int64_t)items.size() >= ((int64_t)1 << 31))
-                return done3(fail(GARLIC_ERR_INVALID, "coverage: more than 2^31 work items"));
-            if ((rc = d_cnt.reserve(h.size()))) return done3(rc);
-            e = hipMemcpyAsync(d_cnt.p, h.data(), sizeof(int32_t) * h.size(), hipMemcpyHostToDevice, s);
-            if (e == hipSuccess) e = hipStreamSynchronize(s);      // (h leaves scope)
-            if (e != hipSuccess) return done3(fail(GARLIC_ERR_HIP, "coverage: %s", hipGetErrorString(e)));
+            f.chr_done = d_cnt.p;
+            f.cnt_timeout = d_cnt.p + nchr;
+            f.chr_need = d_cnt.p + nchr + 1;
+            f.cnt_order = d_cnt.p + 2 * nchr + 1;
+            f.cnt_base = d_cnt.p + 3 * nchr + 1;
+            f.cnt_chrs = d_chrs.p;
+            f.cnt_out = dst;
+            f.n_cnt_items = (int32_t)n_cnt_items;
+            f.n_cnt_chr = p->nchr;
+            f.cnt_vec_ok = vec_ok ? 1 : 0;
         }
-        if (!items.empty()) {
-            FeedArgs f{p->d_packed.p, p->d_tab.p, d_items.p, d_bchrs.p, reinterpret_cast<double *>(d_bits.p), nullptr, p->nwordrows, 0,
-                       p->nind, W, (int32_t)items.size(), 1, getenv("GARLIC_FEED_NO_ASM") ? 0 : 1, d_counter.p, nullptr, cutoff};
-            if (overlap) {
-                f.chr_done = d_cnt.p;
-                f.cnt_timeout = d_cnt.p + nchr;
-                f.chr_need = d_cnt.p + nchr + 1;
-                f.cnt_order = d_cnt.p + 2 * nchr + 1;
-                f.cnt_base = d_cnt.p + 3 * nchr + 1;
-                f.cnt_chrs = d_chrs.p;
-                f.cnt_out = dst;
-                f.n_cnt_items = (int32_t)n_cnt_items;
-                f.n_cnt_chr = p->nchr;
-                f.cnt_vec_ok = vec_ok ? 1 : 0;
-            }
-            DevBuf<int64_t> d_ftrace;   // debugging aid: GARLIC_TRACE=<file> dumps the chain items' time stamps
-            const char *ftrace_path = getenv("GARLIC_TRACE");
-            if (ftrace_path && d_ftrace.reserve(8 * items.size()) == GARLIC_OK) {
-                (void)hipMemsetAsync(d_ftrace.p, 0, sizeof(int64_t) * 8 * items.size(), s);
-                f.trace = d_ftrace.p;
-            }
-            // workgroups per CU as the chains want them (feed_grid: the same chains, the same paces); the count items behind
-            // them in the queue are short and fill whatever is idle.  (Persistent workgroups, all resident: a count item
-            // that waits must not keep a chain item from starting.)
-            int per_cu = 1, chain_grid = 1;
-            if ((rc = feed_grid(ctx, items, &chain_grid, &per_cu))) return done3(rc);
-            const int grid = (int)std::min<size_t>(items.size() + (size_t)n_cnt_items, (size_t)ctx->n_cu * per_cu);
-            void *kargs[] = {(void *)&f};
-            e = hipLaunchKernel((const void *)lod_bits_kernel, dim3((unsigned)grid), dim3(FEED_G * WAVE), kargs, 0, s);
-            if (e != hipSuccess) return done3(fail(GARLIC_ERR_HIP, "coverage: %s", hipGetErrorString(e)));
-            if (f.trace) {
-                std::vector<int64_t> tr(8 * items.size());
-                (void)hipMemcpyAsync(tr.data(), d_ftrace.p, sizeof(int64_t) * tr.size(), hipMemcpyDeviceToHost, s);
-                (void)hipStreamSynchronize(s);
-                if (FILE *fo = fopen(ftrace_path, "w")) {
-                    for (size_t i = 0; i < items.size(); i++) {
-                        fprintf(fo, "%zu", i);
-                        for (int q = 0; q < 8; q++) fprintf(fo, " %lld", (long long)tr[8 * i + q]);
-                        fprintf(fo, "\n");
-                    }
-                    fclose(fo);
-                }
-                d_ftrace.release();
-            }
-        }
-        if (sink.segments) {
-            (void)hipEventRecord(ctx->hist1[slot], s);
-            ctx->n_calls++;
-            return done3(segments_from_bits(p, d_bits.p, d_bchrs.p, bchrs, word_base, W, sink));
-        }
-        if (!overlap)
-            hipLaunchKernelGGL(cov_counts_from_bits_kernel, dim3((unsigned)((word_base[(size_t)p->nchr] + 255) / 256),
-                                                                 (unsigned)((p->nind + COV_ITEM_ROWS - 1) / COV_ITEM_ROWS)),
-                               dim3(256), 0, s, d_bits.p, d_bchrs.p, d_chrs.p, d_wbase.p, p->nchr, W, p->nind, vec_ok ? 1 : 0, dst);
-        (void)hipEventRecord(ctx->hist1[slot], s);
-        ctx->n_calls++;
-        e = hipGetLastError();
-        if (e == hipSuccess && where == GARLIC_HOST)
-            e = hipMemcpyAsync(inwin, dst, sizeof(int16_t) * (size_t)Lo.total, hipMemcpyDeviceToHost, s);
-        int32_t timed_out = 0;
-        if (e == hipSuccess && overlap)
-            e = hipMemcpyAsync(&timed_out, d_cnt.p + nchr, sizeof(int32_t), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return done3(fail(GARLIC_ERR_HIP, "coverage: %s", hipGetErrorString(e)));
-        if (timed_out) {
-            p->n_count_timeouts++;
-            return done3(fail(GARLIC_ERR_HIP, "coverage: a count item gave up waiting for its chromosome's chains"));
-        }
-        return done3(GARLIC_OK);
+        ItemTrace trace;
+        f.trace = trace.begin(8, items.size(), "\n", s);
+        // workgroups per CU as the chains want them (feed_grid: the same chains, the same paces); the count items behind
+        // them in the queue are short and fill whatever is idle.  (Persistent workgroups, all resident: a count item
+        // that waits must not keep a chain item from starting.)
+        int per_cu = 1, chain_grid = 1;
+        if ((rc = feed_grid(ctx, items, &chain_grid, &per_cu))) return rc;
+        const int grid = (int)std::min<size_t>(items.size() + (size_t)n_cnt_items, (size_t)ctx->n_cu * per_cu);
+        void *kargs[] = {(void *)&f};
+        e = hipLaunchKernel((const void *)lod_bits_kernel, dim3((unsigned)grid), dim3(FEED_G * WAVE), kargs, 0, s);
+        if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "coverage: %s", hipGetErrorString(e));
+        trace.write(s);
     }
+    if (!c.segments && !overlap) launch_counts_from_bits(p, bm, c, Lo, d_chrs.p, dst);
+    (void)hist_mark(ctx, true);
+    if (c.segments) return segments_from_bits(p, bm, c);
+    return finish_counts(p, c.inwin, c.where, Lo, dst, overlap ? d_cnt.p + nchr : nullptr);
+}
+
+static int coverage_impl(garlic_panel *p, const CovSink &c)
+{
+    const int32_t W = c.W, weighted = c.weighted, use_gl = c.use_gl;
+    int rc;
+    if ((rc = set_device(p->ctx))) return rc;
+    if (!p->have_map || !p->have_freq || !p->have_geno)
+        return fail(GARLIC_ERR_STATE, "panel needs map, freq and genotypes before computing LOD");
+    if ((rc = ensure_segments(p, c.max_gap))) return rc;
+    if ((rc = ensure_term_table(p, c.error))) return rc;
+    if ((weighted || use_gl) && c.cutoff > MISSING_D && !getenv("GARLIC_COVERAGE_UNFUSED")) return coverage_from_score_kernels(p, c);
+    const bool fused = !weighted && !use_gl && W <= COVF_MAX_W && c.cutoff > MISSING_D && p->tab_all_finite &&
+                       !lod_exact_needed(p, MODE_LOD, W) && !getenv("GARLIC_COVERAGE_UNFUSED");
+    return fused ? coverage_lod_bits(p, c) : coverage_unfused(p, c);
 }
 
 int garlic_roh_coverage_fused(garlic_panel *p, int32_t winsize, double error, int32_t max_gap, int32_t use_gl,
@@ -3452,11 +3470,8 @@ int garlic_roh_coverage_fused(garlic_panel *p, int32_t winsize, double error, in
     if (winsize <= 1 || inwin_pitch_align < 1) return fail(GARLIC_ERR_INVALID, "winsize must be > 1, inwin_pitch_align >= 1");
     if (winsize > 32767) return fail(GARLIC_ERR_INVALID, "coverage counts are 16-bit: winsize <= 32767");
     if (p->nind > 65535) return fail(GARLIC_ERR_INVALID, "coverage: at most 65535 individuals per call");
-    CovSink sink;
-    sink.inwin = inwin;
-    sink.inwin_pitch_align = inwin_pitch_align;
-    sink.where = where;
-    return coverage_impl(p, winsize, error, max_gap, use_gl, weighted, M, mu, cutoff, sink);
+    const CovSink sink{winsize, max_gap, use_gl, weighted, M, error, mu, cutoff, inwin, inwin_pitch_align, where};
+    return coverage_impl(p, sink);
 }
 
 int garlic_roh_segments(garlic_panel *p, int32_t winsize, double error, int32_t max_gap, int32_t use_gl, int32_t weighted,
@@ -3477,13 +3492,13 @@ int garlic_roh_segments(garlic_panel *p, int32_t winsize, double error, int32_t 
             if (p->chr_nloci[c] > 0 && p->pos[(size_t)p->chr_off[c]] < 0)
                 return fail(GARLIC_ERR_INVALID, "chromosome %d starts at position %d: ROH segments need positions >= 0", c,
                             (int)p->pos[(size_t)p->chr_off[c]]);
-    CovSink sink;
+    CovSink sink{winsize, max_gap, use_gl, weighted, M, error, mu, cutoff};
     sink.segments = true;
     sink.overlap_frac = overlap_frac;
     sink.segs = segments;
     sink.cap = capacity;
     sink.n_out = n_segments;
-    return coverage_impl(p, winsize, error, max_gap, use_gl, weighted, M, mu, cutoff, sink);
+    return coverage_impl(p, sink);
 }
 
 int garlic_panel_tgls_mode(garlic_panel *p, int32_t *mode, int32_t *terms_by)
@@ -3507,42 +3522,24 @@ int garlic_roh_coverage(garlic_panel *p, const double *scores, int32_t pitch_ali
     if ((rc = set_device(p->ctx))) return rc;
     hipStream_t s = p->ctx->stream;
     const Layout L = make_layout(p, pitch_align, nind_out), Lo = make_layout(p, inwin_pitch_align, nind_out);
-    std::vector<ChrDev> chrs(2 * (size_t)p->nchr);
+    std::vector<ChrDev> chrs = chr_table(p, L);
+    const std::vector<ChrDev> ochrs = chr_table(p, Lo);
+    chrs.insert(chrs.end(), ochrs.begin(), ochrs.end());
     std::vector<int32_t> seg_base(p->nchr + 1, 0);
-    for (int c = 0; c < p->nchr; c++) {
-        chrs[c] = ChrDev{p->chr_off[c], L.base[c], L.pitch[c], p->chr_nloci[c], 0};
-        chrs[p->nchr + c] = ChrDev{p->chr_off[c], Lo.base[c], Lo.pitch[c], p->chr_nloci[c], 0};
-        seg_base[c + 1] = seg_base[c] + (p->chr_nloci[c] + COV_SEG - 1) / COV_SEG;
-    }
+    for (int c = 0; c < p->nchr; c++) seg_base[c + 1] = seg_base[c] + (p->chr_nloci[c] + COV_SEG - 1) / COV_SEG;
     DevBuf<ChrDev> d_chrs;
     DevBuf<int32_t> d_seg;
     DevBuf<int16_t> d_cov;
-    auto done = [&](int code) { d_chrs.release(); d_seg.release(); d_cov.release(); return code; };
-    if ((rc = d_chrs.reserve(chrs.size())) || (rc = d_seg.reserve(seg_base.size()))) return done(rc);
-    int16_t *dst = inwin;
-    if (where == GARLIC_HOST) {
-        if ((rc = d_cov.reserve((size_t)Lo.total))) return done(rc);
-        dst = d_cov.p;
-    }
-    hipError_t e = hipMemcpyAsync(d_chrs.p, chrs.data(), sizeof(ChrDev) * chrs.size(), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(d_seg.p, seg_base.data(), sizeof(int32_t) * seg_base.size(), hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) return done(fail(GARLIC_ERR_HIP, "coverage: %s", hipGetErrorString(e)));
+    int16_t *dst;
+    if ((rc = d_chrs.put(chrs, s)) || (rc = d_seg.put(seg_base, s)) || (rc = counts_target(inwin, where, Lo, d_cov, &dst))) return rc;
     const size_t lds = sizeof(uint16_t) * ((size_t)winsize + COV_SEG + 2);      // (counts <= COV_SEG + W - 1: 16 bits, W < 57000)
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(roh_coverage_kernel),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(roh_coverage_kernel),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return done(fail(GARLIC_ERR_HIP, "coverage: %s", hipGetErrorString(e)));
-    bool vec_ok = (reinterpret_cast<uintptr_t>(dst) & 15) == 0;        // eight counts per store: every row 16-B aligned
-    for (int c = 0; c < p->nchr && vec_ok; c++) vec_ok = Lo.base[c] % 8 == 0 && Lo.pitch[c] % 8 == 0;
+    if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "coverage: %s", hipGetErrorString(e));
     hipLaunchKernelGGL(roh_coverage_kernel, dim3((unsigned)seg_base[p->nchr], (unsigned)nind_out),
                        dim3(COV_THREADS), lds, s, scores, d_chrs.p, d_chrs.p + p->nchr, d_seg.p, p->nchr, nind_out,
-                       winsize, cutoff, dst, vec_ok ? 1 : 0);
-    e = hipGetLastError();
-    if (e == hipSuccess && where == GARLIC_HOST)
-        e = hipMemcpyAsync(inwin, dst, sizeof(int16_t) * (size_t)Lo.total, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return done(fail(GARLIC_ERR_HIP, "coverage: %s", hipGetErrorString(e)));
-    return done(GARLIC_OK);
+                       winsize, cutoff, dst, cov_vec_ok(p, Lo, dst) ? 1 : 0);
+    return finish_counts(p, inwin, where, Lo, dst, nullptr);
 }
 
 int garlic_last_call_stats(garlic_panel *p, garlic_call_stats *stats)
