@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libgarlic_hip.so")
 
 OK, ERR_INVALID, ERR_HIP, ERR_STATE, ERR_NOMEM = 0, 1, 2, 3, 4
 HOST, DEVICE = 0, 1
+FEED_FROM_SCORES, FEED_CHAIN, FEED_SAMPLED_WLOD = 0, 1, 2   # garlic_lod_feed_info
 MISSING = -9999.0
 
 # every symbol include/garlic_hip.h declares (tests check the library exports them all)
@@ -31,7 +32,7 @@ SYMBOLS = [
     "garlic_recent_kernel_ms", "garlic_panel_tgls_mode", "garlic_lod_feed_subset", "garlic_lod_feed_multi",
     "garlic_device_alloc", "garlic_device_free", "garlic_panel_chain_kind", "garlic_device_alloc_stats",
     "garlic_panel_alloc_scores", "garlic_device_trim", "garlic_roh_coverage_fused", "garlic_roh_segments",
-    "garlic_panel_alloc_scores_info",
+    "garlic_panel_alloc_scores_info", "garlic_lod_feed_info",
 ]
 
 
@@ -119,6 +120,7 @@ def lib():
                                         C.POINTER(C.c_void_p), _i64p, _i64p, _i64p]
     L.garlic_panel_tgls_mode.argtypes = [_vp, _i32p, _i32p]
     L.garlic_panel_chain_kind.argtypes = [_vp, _i32p]
+    L.garlic_lod_feed_info.argtypes = [_vp, _i32p, _i64p]
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int and name not in ("garlic_hip_abi_version",):
@@ -507,6 +509,13 @@ class Panel:
                                                    C.byref(worst), C.byref(target), C.byref(reached)))
         return {"candidates_drawn": drawn.value, "rounds": rounds.value, "best_ms": best.value, "median_ms": med.value,
                 "worst_ms": worst.value, "target_ms_at_0.74_of_hbm": target.value, "reached_target": bool(reached.value)}
+
+    def feed_info(self):
+        """(form, score_doubles) of the last lod_feed / lod_feed_multi call: FEED_FROM_SCORES, FEED_CHAIN or
+        FEED_SAMPLED_WLOD, and the doubles of score scratch it needed (garlic_hip.h)"""
+        form, n = C.c_int32(), C.c_int64()
+        check(lib().garlic_lod_feed_info(self.handle, C.byref(form), C.byref(n)))
+        return form.value, n.value
 
     def chain_kind(self):
         """0 tuned chain, 1 tuned chain + scan for the value -9999.0 (none found), 2 by-value chain (garlic_hip.h)"""

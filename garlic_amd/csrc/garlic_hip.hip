@@ -15,6 +15,7 @@
 #include "coverage_kernel.hpp"
 #include "roh_segments_kernel.hpp"
 #include "feed_kernel.hpp"
+#include "wlod_feed_kernel.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -250,6 +251,8 @@ struct garlic_panel {
     // wLOD
     bool have_ld = false, wlod_use_gl = false, rld_valid = false;
     int32_t last_chain_kind = 0;                   // garlic_panel_chain_kind
+    int32_t last_feed_form = GARLIC_FEED_FROM_SCORES;   // garlic_lod_feed_info
+    int64_t last_feed_doubles = 0;
     int32_t ld_winsize = 0;
     DevBuf<double> d_rld, d_decay, d_stage64;
     DevBuf<uint64_t> d_phase;                      // HapData::firstCopy as bit planes [blk][nloci] (--phased LD)
@@ -283,6 +286,7 @@ struct garlic_panel {
     DevBuf<uint8_t> d_valid;
     DevBuf<int2> d_tiles, d_segs;        // wLOD work lists: 32-window tiles; WSM_T-window segments (narrow windows)
     DevBuf<WlodStrip> d_strips;
+    DevBuf<int32_t> d_feed_blocks;       // wlod_feed_kernel: the 64-individual blocks in play
     std::vector<double> h_tab, h_decay;            // host copies the score rows are built from
     bool wtab_valid = false;
     double wtab_error = 0.0, wtab_mu = 0.0;
@@ -348,7 +352,7 @@ struct garlic_panel {
         PlanKey key;
         size_t n_items = 0, n_fill = 0, n_feed_items = 0;
         int feed_per_cu = 1;      // persistent workgroups per CU the feed kernel of this plan is launched with (feed_grid)
-        int32_t n_tiles = 0, n_segs = 0, n_strips = 0;
+        int32_t n_tiles = 0, n_segs = 0, n_strips = 0, n_feed_blocks = 0;
         int64_t n_runs = 0, n_valid = 0;
     } plan;
 };
@@ -672,6 +676,7 @@ enum Mode { MODE_LOD, MODE_LOD_GL, MODE_WLOD };
 // internal (never returned through the ABI): launch_lod was asked for coverage bits (garlic_panel::cov_pending) by a shape
 // only the score kernels take; garlic_roh_coverage_fused then computes the scores and counts from them
 constexpr int GARLIC_INTERNAL_NO_BITS = -1001;
+constexpr int GARLIC_INTERNAL_NO_SAMPLED = -1002;   // launch_lod: the sampled-window wLOD kernel does not take this call (feed_single: full scores)
 
 // Work list of lod_feed_kernel: (run, FEED_G blocks) items, longest runs first (`order`); the runs within reach of
 // the longest one run at raised issue priority: their length x one wave's pace is the kernel's critical path.
@@ -1194,7 +1199,7 @@ struct LodCall {
 // Which kernel takes the call and what that needs: filled once by decide_form, then by finish_form with what depends on the
 // score buffer.  Everything after reads it: no later code looks at W, the mode or the environment to pick a kernel.
 enum class Family { chain, feed, exact, tgls_ring, tgls_terms, tgls_lookup, wlod_tile, wlod_tile2, wlod_tile_gl, wlod_glring,
-                    wlod_small_tiles, wlod_stream, wlod_strip, wlod_generic };
+                    wlod_small_tiles, wlod_stream, wlod_strip, wlod_generic, wlod_feed };
 
 struct LodForm {
     Family family = Family::chain;
@@ -1221,8 +1226,8 @@ int check_lod_args(const garlic_panel *p, const LodCall &c)
                     c.ind_count, p->nind);
     if (!c.out) return fail(GARLIC_ERR_INVALID, "out is NULL");
     if (c.host_pitch_align < 1) return fail(GARLIC_ERR_INVALID, "pitch_align must be >= 1");
-    if (c.thin_step > 0 && (c.mode != MODE_LOD || c.where != GARLIC_DEVICE || c.host_pitch_align != 32))
-        return fail(GARLIC_ERR_INVALID, "internal: thinned output is for unweighted device scores");
+    if (c.thin_step > 0 && (c.mode == MODE_LOD_GL || c.where != GARLIC_DEVICE || c.host_pitch_align != 32 || c.ind_begin != 0))
+        return fail(GARLIC_ERR_INVALID, "internal: thinned output is for unweighted --error or weighted device scores");
     return GARLIC_OK;
 }
 
@@ -1264,6 +1269,18 @@ int decide_form(garlic_panel *p, const LodCall &c, LodForm &f)
         else f.family = tgls_ring_shape ? Family::tgls_ring : Family::tgls_terms;
         f.writes_bits = f.family == Family::tgls_ring;
         if (f.exact_possible && getenv("GARLIC_EXACT_CHAIN_ONLY")) f.family = Family::exact;
+        return GARLIC_OK;
+    }
+    // wLOD, thinned output: only the sampled windows (wlod_feed_kernel.hpp), from the score rows or the scaled term matrix
+    if (c.thin_step > 0) {
+        if (f.cov_bits) return fail(GARLIC_ERR_STATE, "internal: coverage bits with thinned output");
+        if (W + 64 > GPAD_BACK) return GARLIC_INTERNAL_NO_SAMPLED;
+        if (f.use_gl) {
+            if ((rc = ensure_gl_terms(p, true, c.M, c.mu))) return rc;
+            if (!(p->glterms_valid && p->glterms_scaled)) return GARLIC_INTERNAL_NO_SAMPLED;   // (the term matrix was declined)
+        } else if ((rc = ensure_score_rows(p, c.error, c.M, c.mu, W))) return rc;
+        f.wlod_gl = f.use_gl;
+        f.family = Family::wlod_feed;
         return GARLIC_OK;
     }
     // wLOD.  Tuned kernels: 16 window accumulators per lane; scores from one LDS row per SNP (plain --error) or from the TGLS
@@ -1343,6 +1360,7 @@ struct LodWork {
     std::vector<uint8_t> valid;                    // tuned wLOD kernels: window mask, tiles, segments, strips
     std::vector<int2> tiles, segs;
     std::vector<WlodStrip> strips;
+    std::vector<int32_t> feed_blocks;              // wlod_feed_kernel: the blocks in play (its column groups: tiles)
 };
 
 // Runs, chain / feed items, the wLOD kernels' tiles, segments and strips, the ChrDev table; room for them on the device.
@@ -1385,10 +1403,23 @@ int plan_lod(garlic_panel *p, const LodCall &c, const LodForm &form, const Layou
         if ((rc = p->d_counter.reserve(8))) return rc;
         HIP_TRY(hipMemsetAsync(p->d_counter.p, 0, 8 * sizeof(int32_t), p->ctx->stream));
     }
-    if (form.wlod_tuned) {
+    if (form.wlod_tuned || form.family == Family::wlod_feed) {
         w.valid.assign((size_t)p->nloci, 0);
         for (const Run &r : w.runs)
             memset(w.valid.data() + p->chr_off[r.chr] + r.a, 1, (size_t)(r.b - r.a + 1));
+    }
+    if (form.family == Family::wlod_feed) {
+        // WFD_COLS columns of the thinned matrix x the blocks in play
+        for (int k = 0; k < p->nchr; k++) {
+            const int32_t cols = (int32_t)(((int64_t)p->chr_nloci[k] + c.thin_step - 1) / c.thin_step);
+            for (int32_t c0 = 0; c0 < cols; c0 += WFD_COLS) w.tiles.push_back(make_int2(k, c0));
+        }
+        plan.n_tiles = (int32_t)w.tiles.size();
+        for (int k = 0; k < nblk; k++)
+            if (!c.blocks || (*c.blocks)[(size_t)k]) w.feed_blocks.push_back(k);
+        plan.n_feed_blocks = (int32_t)w.feed_blocks.size();
+    }
+    if (form.wlod_tuned) {
         for (int k = 0; k < p->nchr; k++)
             for (int s0 = 0; s0 < p->chr_nloci[k]; s0 += TILE) w.tiles.push_back(make_int2(k, s0));
         plan.n_tiles = (int32_t)w.tiles.size();
@@ -1618,6 +1649,19 @@ int launch_generic_wlod(garlic_panel *p, const LodCall &c, const LodForm &form, 
     return GARLIC_OK;
 }
 
+// weighted scores, thinned output: the sampled windows only (wlod_feed_kernel.hpp)
+int launch_wlod_feed(garlic_panel *p, const LodCall &c, const LodForm &form, const Plan &plan, double *d_out)
+{
+    const int nquad = (plan.n_feed_blocks + WFD_WAVES - 1) / WFD_WAVES;
+    WlodFeedArgs a{p->d_packed.p, form.wlod_gl ? p->d_glterms.p : p->d_wtab.p, p->d_skew.p + SKEW_FRONT, p->d_valid.p, p->d_chrs.p,
+                   p->d_tiles.p, p->d_feed_blocks.p, d_out, p->nwordrows, GOFF + p->nloci + GPAD_BACK, c.ind_count, c.W, c.thin_step,
+                   plan.n_feed_blocks, nquad, (uint32_t)((int64_t)plan.n_tiles * nquad)};
+    if (!a.n_work) return GARLIC_OK;
+    if (form.wlod_gl) hipLaunchKernelGGL(wlod_feed_kernel<true>, dim3(a.n_work), dim3(WFD_WAVES * WAVE), 0, p->ctx->stream, a);
+    else hipLaunchKernelGGL(wlod_feed_kernel<false>, dim3(a.n_work), dim3(WFD_WAVES * WAVE), 0, p->ctx->stream, a);
+    return GARLIC_OK;
+}
+
 // Everything a call puts on the stream (a second time, as Family::exact, when the rescan found a -9999.0).  (Replaying a repeated
 // asynchronous pass as one HIP graph -- counter reset, MISSING fill, chain kernel, events -- was measured: no difference, the
 // 1.6 ms kernel hides the launch gaps of the small operations once passes are enqueued back to back.)
@@ -1630,11 +1674,12 @@ int enqueue_lod(garlic_panel *p, const LodCall &c, const LodForm &form, const La
     HIP_TRY(hipEventRecord(ctx->ev_begin, s));
     if (fresh && ((rc = p->d_chrs.put(fresh->chrs, s)) || (rc = p->d_items.put(fresh->items, s)) || (rc = p->d_fill.put(fresh->fill, s)) ||
                   (rc = p->d_feed_items.put(fresh->feed_items, s)) || (rc = p->d_valid.put(fresh->valid, s)) ||
-                  (rc = p->d_tiles.put(fresh->tiles, s)) || (rc = p->d_segs.put(fresh->segs, s)) || (rc = p->d_strips.put(fresh->strips, s))))
+                  (rc = p->d_tiles.put(fresh->tiles, s)) || (rc = p->d_segs.put(fresh->segs, s)) || (rc = p->d_strips.put(fresh->strips, s)) ||
+                  (rc = p->d_feed_blocks.put(fresh->feed_blocks, s))))
         return rc;
     if (family == Family::feed) {          // small matrix: MISSING everywhere, the chain kernel overwrites the scored samples
         hipLaunchKernelGGL(fill_value_kernel, dim3(1024), dim3(256), 0, s, d_out, L.total, MISSING_D);
-    } else if (plan.n_fill && !form.wlod_tuned && !form.cov_bits) {   // the tuned wLOD kernel writes MISSING itself
+    } else if (plan.n_fill && !form.wlod_tuned && family != Family::wlod_feed && !form.cov_bits) {   // the tuned and the sampled wLOD kernels write MISSING themselves
         dim3 grid((unsigned)plan.n_fill, (unsigned)((c.ind_count + FILL_ROWS - 1) / FILL_ROWS));
         hipLaunchKernelGGL(fill_missing_kernel, grid, dim3(256), 0, s, p->d_fill.p, p->d_chrs.p, c.ind_count, d_out);
     }
@@ -1649,7 +1694,7 @@ int enqueue_lod(garlic_panel *p, const LodCall &c, const LodForm &form, const La
     int workers = ctx->n_cu;
     if (const char *e = getenv("GARLIC_WORKERS")) workers = std::max(1, atoi(e));
     workers = std::min<int>(workers, (int)plan.n_items);
-    if (form.wlod_tuned || plan.n_items)
+    if (form.wlod_tuned || plan.n_items || family == Family::wlod_feed)
         switch (family) {
         case Family::chain:
         case Family::feed: rc = launch_chain(p, c, form, plan, fresh, workers, d_out); break;
@@ -1661,6 +1706,7 @@ int enqueue_lod(garlic_panel *p, const LodCall &c, const LodForm &form, const La
         case Family::tgls_terms:
         case Family::tgls_lookup: rc = launch_tgls(p, c, form, plan, workers, d_out); break;
         case Family::wlod_generic: rc = launch_generic_wlod(p, c, form, plan, d_out); break;
+        case Family::wlod_feed: rc = launch_wlod_feed(p, c, form, plan, d_out); break;
         default: rc = launch_wlod(p, c, form, plan, d_out);
         }
     if (rc) return rc;
@@ -1669,10 +1715,11 @@ int enqueue_lod(garlic_panel *p, const LodCall &c, const LodForm &form, const La
     return GARLIC_OK;
 }
 
-// thin_step > 0 (unweighted scores, device output, pitch_align 32 only): `out` is the thinned matrix
-// of make_layout(p, 32, ind_count, thin_step) -- the chain kernel stores only the windows at loci
-// 0, thin_step, 2 * thin_step, .. of each chromosome, everything else of that matrix is MISSING.
-// blocks (chain kernels only): per 64-individual block of the call, 1 = score it; rows of the other
+// thin_step > 0 (unweighted --error or weighted scores, device output, pitch_align 32 only): `out` is the thinned matrix
+// of make_layout(p, 32, ind_count, thin_step) -- the feed kernels store only the windows at loci
+// 0, thin_step, 2 * thin_step, .. of each chromosome, everything else of that matrix is MISSING.  A weighted call the
+// sampled-window kernel does not take returns GARLIC_INTERNAL_NO_SAMPLED with nothing written.
+// blocks (chain and feed kernels only): per 64-individual block of the call, 1 = score it; rows of the other
 // blocks are left unwritten (the subset feed never reads them)
 int launch_lod(garlic_panel *p, Mode mode, int32_t W, double error, int32_t max_gap, int32_t M, double mu,
                int32_t ind_begin, int32_t ind_count, int32_t pitch_align, double *out, int32_t where,
@@ -2908,19 +2955,32 @@ static int feed_single(garlic_panel *p, int32_t winsize, double error, int32_t m
     // windows (8/step B per window instead of 8 B, no full-size scratch).  Otherwise the full scores
     // go to the panel's device scratch (the one host-output calls use; it stays allocated, hipMalloc
     // of 8 GB per call would cost more than the kernels) and are sampled from there.
+    // Weighted scores sampled at most once per window length (the reference thins with step = winsize): every
+    // window is a sum of its own, so wlod_feed_kernel computes the sampled ones only, into the same thinned matrix.
+    // (step < winsize: the sampled windows overlap and that kernel would do winsize / step times the per-SNP work;
+    // not measured against the tuned kernels, so such steps keep the full scores.)  GARLIC_WLOD_FEED_FULL: never.
     int32_t thinned = (!weighted && !use_gl && step >= 4) ? step : 0;
-    if (thinned) {   // the exact chain (lod_exact_needed) writes full scores only
+    if (weighted && step >= winsize && !getenv("GARLIC_WLOD_FEED_FULL")) thinned = step;
+    if (thinned && !weighted) {   // the exact chain (lod_exact_needed) writes full scores only
         if (!p->have_freq) return fail(GARLIC_ERR_STATE, "panel needs map, freq and genotypes before computing LOD");
         if ((rc = ensure_term_table(p, error))) return rc;
         if (lod_exact_needed(p, MODE_LOD, winsize)) thinned = 0;
     }
-    const Layout L = make_layout(p, 32, p->nind, thinned);
     garlic_panel::ScoreBuf &scores = p->d_out;
     DevBuf<double> &d_feed = p->d_feed;            // kept with the panel: window-size sweeps call this repeatedly
-    if ((rc = scores.reserve(p->ctx, (size_t)L.total))) return rc;
     if (weighted) p->wlod_use_gl = use_gl != 0;
-    rc = launch_lod(p, weighted ? MODE_WLOD : (use_gl ? MODE_LOD_GL : MODE_LOD), winsize, error, max_gap, M, mu, 0,
-                    p->nind, 32, scores.p, GARLIC_DEVICE, thinned, ind_idx ? &blocks : nullptr);
+    for (;;) {
+        const Layout L = make_layout(p, 32, p->nind, thinned);
+        if ((rc = scores.reserve(p->ctx, (size_t)L.total))) return rc;
+        rc = launch_lod(p, weighted ? MODE_WLOD : (use_gl ? MODE_LOD_GL : MODE_LOD), winsize, error, max_gap, M, mu, 0,
+                        p->nind, 32, scores.p, GARLIC_DEVICE, thinned, ind_idx ? &blocks : nullptr);
+        if (rc != GARLIC_INTERNAL_NO_SAMPLED) {
+            p->last_feed_form = !thinned ? GARLIC_FEED_FROM_SCORES : weighted ? GARLIC_FEED_SAMPLED_WLOD : GARLIC_FEED_CHAIN;
+            p->last_feed_doubles = L.total;
+            break;
+        }
+        thinned = 0;      // the sampled-window kernel does not take this call: full scores
+    }
     if (rc) return rc;
     // at most ceil(nloci_c / step) values per (chromosome, individual)
     int64_t cap = 0;
@@ -3000,6 +3060,8 @@ int garlic_lod_feed_multi(garlic_panel *p, const int32_t *winsizes, const int32_
                 return rc;
         return GARLIC_OK;
     }
+    p->last_feed_form = GARLIC_FEED_CHAIN;      // the samples go straight into the feeds: no score matrix of any kind
+    p->last_feed_doubles = 0;
     // rows of the feed: the listed individuals in list order, or everyone
     const int nblk = (p->nind + WAVE - 1) / WAVE;
     const int nrows = ind_idx ? n_idx : p->nind;
@@ -3728,6 +3790,14 @@ int garlic_panel_alloc_scores_info(garlic_panel *p, int32_t *drawn, int32_t *rou
     if (worst_ms) *worst_ms = p->placement.worst_ms;
     if (target_ms) *target_ms = p->placement.target_ms;
     if (reached_target) *reached_target = p->placement.reached;
+    return GARLIC_OK;
+}
+
+int garlic_lod_feed_info(garlic_panel *p, int32_t *form, int64_t *score_doubles)
+{
+    if (!p || !form) return fail(GARLIC_ERR_INVALID, "panel and form are required");
+    *form = p->last_feed_form;
+    if (score_doubles) *score_doubles = p->last_feed_doubles;
     return GARLIC_OK;
 }
 

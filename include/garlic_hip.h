@@ -44,7 +44,9 @@ extern "C" {
  * 5: garlic_lod_feed_multi (the feeds of several window sizes in one call); garlic_panel_alloc_scores,
  *    garlic_device_alloc_stats, garlic_device_trim
  * 6: garlic_roh_coverage_fused (coverage counts without the score matrix)
- * 7: garlic_roh_segments (the ROH segments of assembleROHWindows without scores or counts) */
+ * 7: garlic_roh_segments (the ROH segments of assembleROHWindows without scores or counts)
+ * 8: garlic_call_stats::n_stall_reruns / n_count_timeouts, garlic_panel_alloc_scores_info; garlic_lod_feed_info (added
+ *    under the same number: nothing that existed changed) */
 #define GARLIC_HIP_ABI_VERSION 8
 
 #define GARLIC_OK 0
@@ -250,8 +252,13 @@ int garlic_lod_flatten(garlic_panel *panel, const double *scores, int32_t pitch_
  * feeds of individual shards can be merged in the reference's chromosome -> individual order.
  * 8 / step bytes per window cross PCIe instead of 8.  Unweighted --error scores with step >= 4 are
  * thinned by the LOD kernel itself (only the sampled windows are ever stored: 8 / step bytes per
- * window of HBM writes, no full-size scratch); the other variants compute the full scores into
- * device scratch and sample them there.  Same values either way. */
+ * window of HBM writes, no full-size scratch).  Weighted scores (with or without per-genotype
+ * likelihoods) with step >= winsize, the reference's thinning: every wLOD window is a sum of its
+ * own, so only the sampled windows are computed at all, into the same thinned matrix (winsize
+ * times less arithmetic, no full-size scratch; GARLIC_WLOD_FEED_FULL=1 in the environment keeps the
+ * full scores).  The other variants (unweighted per-genotype likelihoods, steps below 4, weighted
+ * with step < winsize) compute the full scores into device scratch and sample them there.  Same
+ * values either way; garlic_lod_feed_info tells which it was. */
 int garlic_lod_feed(garlic_panel *panel, int32_t winsize, double error, int32_t max_gap, int32_t use_gl,
                     int32_t weighted, int32_t M, double mu, int32_t step, double *feed,
                     int64_t feed_capacity, int64_t *count, int64_t *chr_counts);
@@ -265,6 +272,17 @@ int garlic_lod_feed(garlic_panel *panel, int32_t winsize, double error, int32_t 
 int garlic_lod_feed_subset(garlic_panel *panel, int32_t winsize, double error, int32_t max_gap, int32_t use_gl,
                            int32_t weighted, int32_t M, double mu, int32_t step, const int32_t *ind_idx,
                            int32_t n_idx, double *feed, int64_t feed_capacity, int64_t *count, int64_t *chr_counts);
+
+/* How the last garlic_lod_feed / _subset / _multi call on this panel produced its feed:
+ * GARLIC_FEED_FROM_SCORES (full scores in device scratch, then garlic_lod_flatten),
+ * GARLIC_FEED_CHAIN (unweighted: the chain stores only the samples),
+ * GARLIC_FEED_SAMPLED_WLOD (weighted: only the sampled windows are computed).
+ * *score_doubles (may be NULL): doubles of score scratch that call needed (a _multi call whose chains write
+ * straight into the feeds: 0). */
+#define GARLIC_FEED_FROM_SCORES 0
+#define GARLIC_FEED_CHAIN 1
+#define GARLIC_FEED_SAMPLED_WLOD 2
+int garlic_lod_feed_info(garlic_panel *panel, int32_t *form, int64_t *score_doubles);
 
 /* The callers that sweep window sizes -- exploreWinsizes (src/garlic-roh.cpp:726-751), selectWinsize (:798-837),
  * selectWinsizeFromList (:881-920: --winsize-multi with --auto-winsize) -- run calcLODWindows + the KDE thinning once

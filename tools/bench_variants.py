@@ -3,6 +3,10 @@
 (--weighted) variants of the path on a synthetic panel, one JSON line each.
 
     python tools/bench_variants.py [--snps 200000] [--inds 1000] [--winsize 100] [--steps 5]
+
+--modes wlod_feed is a leg of its own: the weighted KDE feed (garlic_lod_feed, weighted, step = winsize) without and
+with dictionary likelihoods, for every size of --winsizes on one resident panel; --tree DIR takes garlic_amd from another
+checkout (the A/B against the parent commit: profiles/wlod_feed_ab.txt).
 """
 import argparse
 import json
@@ -15,6 +19,70 @@ ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
 
 
+def wlod_feed_leg(args):
+    """The whole garlic_lod_feed call (host clock around the synchronous call: scores, the two flatten passes, the feed's
+    copy to the host buffer the call defines) and its score part / dominant kernel (the library's HIP events), repeated
+    args.steps times after two warm-up calls; the score memory the call holds (garlic_device_alloc_stats, live + pooled)
+    and the device memory in use after it."""
+    import time
+    import torch
+    from garlic_amd import abi, synth
+
+    torch.cuda.set_device(0)
+    dev = torch.device("cuda", 0)
+    nloci, nind = args.snps, args.inds
+    error, max_gap = 0.001, 200000
+    spec = synth.PanelSpec(nloci, seed=20260105, max_gap=max_gap)
+    ctx = abi.Context(0)
+    panel = abi.Panel(ctx, spec.chr_nloci, nind)
+    panel.set_map(spec.pos, spec.centro_start, spec.centro_end, gpos=spec.gpos)
+    panel.set_freq(spec.freq)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(7)
+    for l0, g in synth.genotype_chunks(spec, nind, dev):
+        gq = torch.randint(3, 61, g.shape, generator=gen, device=dev).to(torch.float64)
+        gl = torch.pow(torch.tensor(10.0, dtype=torch.float64, device=dev), -gq / 10.0)
+        torch.cuda.synchronize()
+        panel.set_genotypes_device(g.data_ptr(), g.shape[1], l0, g.shape[0])
+        panel.set_gl_device(gl.data_ptr(), gl.shape[1], l0, gl.shape[0])
+        del gq, gl
+    del g
+    full_bytes = int(panel.out_layout(32, nind)[2]) * 8
+    for W in [int(w) for w in args.winsizes.split(",")]:
+        ld = 1.0 + (max(2.0, W / 4.0) - 1.0) * torch.rand((nloci, W), generator=gen, device=dev, dtype=torch.float64)
+        torch.cuda.synchronize()
+        panel.set_ld_device(W, ld.data_ptr())
+        del ld
+        for step in [int(x) for x in args.feed_steps.split(",")] if args.feed_steps else [W]:
+            for use_gl in (False, True):
+                panel.release_scratch()
+                ctx.trim()
+                torch.cuda.empty_cache()
+                wall, score, kern = [], [], []
+                for k in range(2 + args.steps):
+                    t0 = time.perf_counter()
+                    feed, _ = panel.lod_feed(W, error, max_gap, step, use_gl=use_gl, weighted=True, copy=False)
+                    dt = time.perf_counter() - t0
+                    st = panel.stats()
+                    if k >= 2:
+                        wall.append(dt * 1e3)
+                        score.append(st["total_ms"])
+                        kern.append(st["chain_kernel_ms"])
+                live, pooled, _ = ctx.alloc_stats()
+                free_b, total_b = torch.cuda.mem_get_info()
+                line = {"mode": "wlod_feed", "snps": nloci, "inds": nind, "winsize": W, "step": step, "use_gl": use_gl,
+                        "repeats": args.steps, "feed_values": int(feed.shape[0]),
+                        "call_ms_median": float(np.median(wall)), "call_ms_min": min(wall), "call_ms_max": max(wall),
+                        "score_part_ms_median": float(np.median(score)),
+                        "kernel_ms_median": float(np.median(kern)), "kernel_ms_min": min(kern), "kernel_ms_max": max(kern),
+                        "score_memory_bytes": live + pooled, "full_score_matrix_bytes": full_bytes,
+                        "device_memory_in_use_bytes": int(total_b - free_b),
+                        "feed_checksum": float(np.sum(feed[np.isfinite(feed)]))}
+                if hasattr(panel, "feed_info"):
+                    line["feed_form"], line["score_doubles"] = panel.feed_info()
+                print(json.dumps(line), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--snps", type=int, default=200000)
@@ -22,7 +90,14 @@ def main():
     ap.add_argument("--winsize", type=int, default=100)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--modes", default="lod,tgls,wlod")
+    ap.add_argument("--winsizes", default="100,10", help="wlod_feed: window sizes, one resident panel")
+    ap.add_argument("--feed-steps", default="", help="wlod_feed: thinning steps (default: the window size)")
+    ap.add_argument("--tree", default="", help="take garlic_amd from this checkout instead of the one the tool is in")
     args = ap.parse_args()
+    if args.tree:
+        sys.path.insert(0, os.path.abspath(args.tree))
+    if args.modes == "wlod_feed":
+        return wlod_feed_leg(args)
 
     import torch
     from garlic_amd import abi, synth
