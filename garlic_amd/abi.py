@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libgarlic_hip.so")
 
 OK, ERR_INVALID, ERR_HIP, ERR_STATE, ERR_NOMEM = 0, 1, 2, 3, 4
 HOST, DEVICE = 0, 1
-FEED_FROM_SCORES, FEED_CHAIN, FEED_SAMPLED_WLOD = 0, 1, 2   # garlic_lod_feed_info
+FEED_FROM_SCORES, FEED_CHAIN, FEED_SAMPLED_WLOD, FEED_TGLS_CHAIN = 0, 1, 2, 3   # garlic_lod_feed_info
 MISSING = -9999.0
 
 # every symbol include/garlic_hip.h declares (tests check the library exports them all)
@@ -511,8 +511,8 @@ class Panel:
                 "worst_ms": worst.value, "target_ms_at_0.74_of_hbm": target.value, "reached_target": bool(reached.value)}
 
     def feed_info(self):
-        """(form, score_doubles) of the last lod_feed / lod_feed_multi call: FEED_FROM_SCORES, FEED_CHAIN or
-        FEED_SAMPLED_WLOD, and the doubles of score scratch it needed (garlic_hip.h)"""
+        """(form, score_doubles) of the last lod_feed / lod_feed_multi call: FEED_FROM_SCORES, FEED_CHAIN,
+        FEED_SAMPLED_WLOD or FEED_TGLS_CHAIN, and the doubles of score scratch it needed (garlic_hip.h)"""
         form, n = C.c_int32(), C.c_int64()
         check(lib().garlic_lod_feed_info(self.handle, C.byref(form), C.byref(n)))
         return form.value, n.value

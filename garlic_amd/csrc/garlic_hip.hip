@@ -10,6 +10,7 @@
 #include "variant_kernels.hpp"
 #include "ld_kernels.hpp"
 #include "tgls_ring_kernel.hpp"
+#include "tgls_feed_kernel.hpp"
 #include "wlod_strip_kernel.hpp"
 #include "wlod_small_kernel.hpp"
 #include "coverage_kernel.hpp"
@@ -676,7 +677,7 @@ enum Mode { MODE_LOD, MODE_LOD_GL, MODE_WLOD };
 // internal (never returned through the ABI): launch_lod was asked for coverage bits (garlic_panel::cov_pending) by a shape
 // only the score kernels take; garlic_roh_coverage_fused then computes the scores and counts from them
 constexpr int GARLIC_INTERNAL_NO_BITS = -1001;
-constexpr int GARLIC_INTERNAL_NO_SAMPLED = -1002;   // launch_lod: the sampled-window wLOD kernel does not take this call (feed_single: full scores)
+constexpr int GARLIC_INTERNAL_NO_SAMPLED = -1002;   // launch_lod: no kernel with thinned output (wlod_feed_kernel, tgls_feed_kernel) takes this call (feed_single: full scores)
 
 // Work list of lod_feed_kernel: (run, FEED_G blocks) items, longest runs first (`order`); the runs within reach of
 // the longest one run at raised issue priority: their length x one wave's pace is the kernel's critical path.
@@ -1198,7 +1199,7 @@ struct LodCall {
 
 // Which kernel takes the call and what that needs: filled once by decide_form, then by finish_form with what depends on the
 // score buffer.  Everything after reads it: no later code looks at W, the mode or the environment to pick a kernel.
-enum class Family { chain, feed, exact, tgls_ring, tgls_terms, tgls_lookup, wlod_tile, wlod_tile2, wlod_tile_gl, wlod_glring,
+enum class Family { chain, feed, exact, tgls_ring, tgls_feed, tgls_terms, tgls_lookup, wlod_tile, wlod_tile2, wlod_tile_gl, wlod_glring,
                     wlod_small_tiles, wlod_stream, wlod_strip, wlod_generic, wlod_feed };
 
 struct LodForm {
@@ -1226,8 +1227,8 @@ int check_lod_args(const garlic_panel *p, const LodCall &c)
                     c.ind_count, p->nind);
     if (!c.out) return fail(GARLIC_ERR_INVALID, "out is NULL");
     if (c.host_pitch_align < 1) return fail(GARLIC_ERR_INVALID, "pitch_align must be >= 1");
-    if (c.thin_step > 0 && (c.mode == MODE_LOD_GL || c.where != GARLIC_DEVICE || c.host_pitch_align != 32 || c.ind_begin != 0))
-        return fail(GARLIC_ERR_INVALID, "internal: thinned output is for unweighted --error or weighted device scores");
+    if (c.thin_step > 0 && (c.where != GARLIC_DEVICE || c.host_pitch_align != 32 || c.ind_begin != 0))
+        return fail(GARLIC_ERR_INVALID, "internal: thinned output is for device scores of the whole panel, pitch_align 32");
     return GARLIC_OK;
 }
 
@@ -1253,7 +1254,10 @@ int decide_form(garlic_panel *p, const LodCall &c, LodForm &f)
     // are scanned for that value, and only if one is there the chain that follows the reference to the letter
     // (11-17 x slower) runs instead.  GARLIC_EXACT_CHAIN_ONLY: that chain straight away.
     f.exact_possible = mode != MODE_WLOD && lod_exact_needed(p, mode, W);
-    if (f.exact_possible && c.thin_step > 0) return fail(GARLIC_ERR_INVALID, "internal: thinned output with the exact chain");
+    if (f.exact_possible && c.thin_step > 0) {      // the rescan and the exact chain need the full matrix
+        if (mode == MODE_LOD_GL) return GARLIC_INTERNAL_NO_SAMPLED;
+        return fail(GARLIC_ERR_INVALID, "internal: thinned output with the exact chain");
+    }
     // coverage bits instead of scores (garlic_roh_coverage_fused): only the kernels that know how; nothing else may touch
     // `out` (it is not a score buffer then)
     f.cov_bits = p->cov_pending.bits != nullptr;
@@ -1269,6 +1273,14 @@ int decide_form(garlic_panel *p, const LodCall &c, LodForm &f)
         else f.family = tgls_ring_shape ? Family::tgls_ring : Family::tgls_terms;
         f.writes_bits = f.family == Family::tgls_ring;
         if (f.exact_possible && getenv("GARLIC_EXACT_CHAIN_ONLY")) f.family = Family::exact;
+        // TGLS, thinned output: the ring chain that stores the sampled windows only (tgls_feed_kernel.hpp); the other TGLS
+        // chains write full scores.  GARLIC_TGLS_FEED_FULL: never.
+        if (mode == MODE_LOD_GL && c.thin_step > 0) {
+            if (f.cov_bits) return fail(GARLIC_ERR_STATE, "internal: coverage bits with thinned output");
+            if (f.family != Family::tgls_ring || getenv("GARLIC_TGLS_FEED_FULL")) return GARLIC_INTERNAL_NO_SAMPLED;
+            f.family = Family::tgls_feed;
+            f.writes_bits = false;
+        }
         return GARLIC_OK;
     }
     // wLOD, thinned output: only the sampled windows (wlod_feed_kernel.hpp), from the score rows or the scaled term matrix
@@ -1621,6 +1633,13 @@ int launch_tgls(garlic_panel *p, const LodCall &c, const LodForm &form, const Pl
     hipStream_t s = p->ctx->stream;
     const int64_t rows = GOFF + p->nloci + GPAD_BACK;
     if (form.cov_bits && !form.writes_bits) return GARLIC_INTERNAL_NO_BITS;      // only the ring chain takes this shape
+    if (form.family == Family::tgls_feed) {
+        // the same ring chain storing the sampled windows only, into the thinned matrix (tgls_feed_kernel.hpp)
+        TglsFeedArgs t{p->d_glterms.p, rows, p->d_items.p, p->d_chrs.p, d_out,
+                       c.ind_begin, c.ind_count, c.W, (int32_t)plan.n_items, c.thin_step, p->d_counter.p};
+        hipLaunchKernelGGL(tgls_feed_kernel, dim3((unsigned)workers), dim3(TGF_THREADS), 0, s, t);
+        return GARLIC_OK;
+    }
     if (form.family == Family::tgls_ring) {
         // persistent workgroups, every term row through an LDS ring once (tgls_ring_kernel.hpp)
         TglsArgs t{p->d_glterms.p, rows, p->d_items.p, p->d_chrs.p, d_out,
@@ -1677,7 +1696,7 @@ int enqueue_lod(garlic_panel *p, const LodCall &c, const LodForm &form, const La
                   (rc = p->d_tiles.put(fresh->tiles, s)) || (rc = p->d_segs.put(fresh->segs, s)) || (rc = p->d_strips.put(fresh->strips, s)) ||
                   (rc = p->d_feed_blocks.put(fresh->feed_blocks, s))))
         return rc;
-    if (family == Family::feed) {          // small matrix: MISSING everywhere, the chain kernel overwrites the scored samples
+    if (family == Family::feed || family == Family::tgls_feed) {          // small matrix: MISSING everywhere, the chain kernel overwrites the scored samples
         hipLaunchKernelGGL(fill_value_kernel, dim3(1024), dim3(256), 0, s, d_out, L.total, MISSING_D);
     } else if (plan.n_fill && !form.wlod_tuned && family != Family::wlod_feed && !form.cov_bits) {   // the tuned and the sampled wLOD kernels write MISSING themselves
         dim3 grid((unsigned)plan.n_fill, (unsigned)((c.ind_count + FILL_ROWS - 1) / FILL_ROWS));
@@ -1703,6 +1722,7 @@ int enqueue_lod(garlic_panel *p, const LodCall &c, const LodForm &form, const La
                                (int)plan.n_items);
             break;
         case Family::tgls_ring:
+        case Family::tgls_feed:
         case Family::tgls_terms:
         case Family::tgls_lookup: rc = launch_tgls(p, c, form, plan, workers, d_out); break;
         case Family::wlod_generic: rc = launch_generic_wlod(p, c, form, plan, d_out); break;
@@ -1715,10 +1735,10 @@ int enqueue_lod(garlic_panel *p, const LodCall &c, const LodForm &form, const La
     return GARLIC_OK;
 }
 
-// thin_step > 0 (unweighted --error or weighted scores, device output, pitch_align 32 only): `out` is the thinned matrix
+// thin_step > 0 (device output of the whole panel, pitch_align 32 only): `out` is the thinned matrix
 // of make_layout(p, 32, ind_count, thin_step) -- the feed kernels store only the windows at loci
-// 0, thin_step, 2 * thin_step, .. of each chromosome, everything else of that matrix is MISSING.  A weighted call the
-// sampled-window kernel does not take returns GARLIC_INTERNAL_NO_SAMPLED with nothing written.
+// 0, thin_step, 2 * thin_step, .. of each chromosome, everything else of that matrix is MISSING.  A weighted or TGLS call
+// that no kernel with thinned output takes returns GARLIC_INTERNAL_NO_SAMPLED with nothing written.
 // blocks (chain and feed kernels only): per 64-individual block of the call, 1 = score it; rows of the other
 // blocks are left unwritten (the subset feed never reads them)
 int launch_lod(garlic_panel *p, Mode mode, int32_t W, double error, int32_t max_gap, int32_t M, double mu,
@@ -2959,9 +2979,12 @@ static int feed_single(garlic_panel *p, int32_t winsize, double error, int32_t m
     // window is a sum of its own, so wlod_feed_kernel computes the sampled ones only, into the same thinned matrix.
     // (step < winsize: the sampled windows overlap and that kernel would do winsize / step times the per-SNP work;
     // not measured against the tuned kernels, so such steps keep the full scores.)  GARLIC_WLOD_FEED_FULL: never.
-    int32_t thinned = (!weighted && !use_gl && step >= 4) ? step : 0;
+    // Unweighted scores from per-genotype likelihoods, step >= 4 as for --error: the ring chain stores the sampled windows
+    // only (tgls_feed_kernel.hpp) unless decide_form says the call is not the ring chain's (exact chain possible, term
+    // matrix declined or looked up, GARLIC_TGLS_NO_RING, GARLIC_TGLS_FEED_FULL): full scores then.
+    int32_t thinned = (!weighted && step >= 4) ? step : 0;
     if (weighted && step >= winsize && !getenv("GARLIC_WLOD_FEED_FULL")) thinned = step;
-    if (thinned && !weighted) {   // the exact chain (lod_exact_needed) writes full scores only
+    if (thinned && !weighted && !use_gl) {   // the exact chain (lod_exact_needed) writes full scores only
         if (!p->have_freq) return fail(GARLIC_ERR_STATE, "panel needs map, freq and genotypes before computing LOD");
         if ((rc = ensure_term_table(p, error))) return rc;
         if (lod_exact_needed(p, MODE_LOD, winsize)) thinned = 0;
@@ -2975,7 +2998,7 @@ static int feed_single(garlic_panel *p, int32_t winsize, double error, int32_t m
         rc = launch_lod(p, weighted ? MODE_WLOD : (use_gl ? MODE_LOD_GL : MODE_LOD), winsize, error, max_gap, M, mu, 0,
                         p->nind, 32, scores.p, GARLIC_DEVICE, thinned, ind_idx ? &blocks : nullptr);
         if (rc != GARLIC_INTERNAL_NO_SAMPLED) {
-            p->last_feed_form = !thinned ? GARLIC_FEED_FROM_SCORES : weighted ? GARLIC_FEED_SAMPLED_WLOD : GARLIC_FEED_CHAIN;
+            p->last_feed_form = !thinned ? GARLIC_FEED_FROM_SCORES : weighted ? GARLIC_FEED_SAMPLED_WLOD : use_gl ? GARLIC_FEED_TGLS_CHAIN : GARLIC_FEED_CHAIN;
             p->last_feed_doubles = L.total;
             break;
         }

@@ -46,7 +46,7 @@ extern "C" {
  * 6: garlic_roh_coverage_fused (coverage counts without the score matrix)
  * 7: garlic_roh_segments (the ROH segments of assembleROHWindows without scores or counts)
  * 8: garlic_call_stats::n_stall_reruns / n_count_timeouts, garlic_panel_alloc_scores_info; garlic_lod_feed_info (added
- *    under the same number: nothing that existed changed) */
+ *    under the same number: nothing that existed changed); GARLIC_FEED_TGLS_CHAIN (a fourth value of its form, likewise) */
 #define GARLIC_HIP_ABI_VERSION 8
 
 #define GARLIC_OK 0
@@ -256,9 +256,14 @@ int garlic_lod_flatten(garlic_panel *panel, const double *scores, int32_t pitch_
  * likelihoods) with step >= winsize, the reference's thinning: every wLOD window is a sum of its
  * own, so only the sampled windows are computed at all, into the same thinned matrix (winsize
  * times less arithmetic, no full-size scratch; GARLIC_WLOD_FEED_FULL=1 in the environment keeps the
- * full scores).  The other variants (unweighted per-genotype likelihoods, steps below 4, weighted
- * with step < winsize) compute the full scores into device scratch and sample them there.  Same
- * values either way; garlic_lod_feed_info tells which it was. */
+ * full scores).  Unweighted scores from per-genotype likelihoods with step >= 4: the ring chain still
+ * computes every window (a rolling sum) but stores only the sampled ones (algorithmically 8 + 8 / step
+ * bytes per window against 16.25; the samples leave as 8-byte words, one per row, and the thinned
+ * matrix is filled with -9999.0 first, so the bytes really written are more) and no full-size scratch; it keeps the full scores when a window could sum to
+ * exactly -9999.0 (garlic_panel_chain_kind 1 or 2), when the term matrix was declined or
+ * GARLIC_TGLS_NO_RING=1 is set, and under GARLIC_TGLS_FEED_FULL=1.  The other variants (steps below 4,
+ * weighted with step < winsize) compute the full scores into device scratch and sample them there.
+ * Same values either way; garlic_lod_feed_info tells which it was. */
 int garlic_lod_feed(garlic_panel *panel, int32_t winsize, double error, int32_t max_gap, int32_t use_gl,
                     int32_t weighted, int32_t M, double mu, int32_t step, double *feed,
                     int64_t feed_capacity, int64_t *count, int64_t *chr_counts);
@@ -276,12 +281,14 @@ int garlic_lod_feed_subset(garlic_panel *panel, int32_t winsize, double error, i
 /* How the last garlic_lod_feed / _subset / _multi call on this panel produced its feed:
  * GARLIC_FEED_FROM_SCORES (full scores in device scratch, then garlic_lod_flatten),
  * GARLIC_FEED_CHAIN (unweighted: the chain stores only the samples),
- * GARLIC_FEED_SAMPLED_WLOD (weighted: only the sampled windows are computed).
+ * GARLIC_FEED_SAMPLED_WLOD (weighted: only the sampled windows are computed),
+ * GARLIC_FEED_TGLS_CHAIN (unweighted per-genotype likelihoods: the ring chain stores only the samples).
  * *score_doubles (may be NULL): doubles of score scratch that call needed (a _multi call whose chains write
  * straight into the feeds: 0). */
 #define GARLIC_FEED_FROM_SCORES 0
 #define GARLIC_FEED_CHAIN 1
 #define GARLIC_FEED_SAMPLED_WLOD 2
+#define GARLIC_FEED_TGLS_CHAIN 3
 int garlic_lod_feed_info(garlic_panel *panel, int32_t *form, int64_t *score_doubles);
 
 /* The callers that sweep window sizes -- exploreWinsizes (src/garlic-roh.cpp:726-751), selectWinsize (:798-837),

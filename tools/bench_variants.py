@@ -6,7 +6,9 @@
 
 --modes wlod_feed is a leg of its own: the weighted KDE feed (garlic_lod_feed, weighted, step = winsize) without and
 with dictionary likelihoods, for every size of --winsizes on one resident panel; --tree DIR takes garlic_amd from another
-checkout (the A/B against the parent commit: profiles/wlod_feed_ab.txt).
+checkout (the A/B against the parent commit: profiles/wlod_feed_ab.txt).  --modes tgls_feed: the same leg for the
+unweighted feed with per-genotype likelihoods (use_gl, not weighted; --gl-kind codes or continuous; no LD weights), with the
+kernel's fraction of the HBM roofline at the bytes per window of the form the call took (profiles/tgls_feed_ab.txt).
 """
 import argparse
 import json
@@ -19,11 +21,13 @@ ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
 
 
-def wlod_feed_leg(args):
+def wlod_feed_leg(args, tgls=False):
     """The whole garlic_lod_feed call (host clock around the synchronous call: scores, the two flatten passes, the feed's
     copy to the host buffer the call defines) and its score part / dominant kernel (the library's HIP events), repeated
     args.steps times after two warm-up calls; the score memory the call holds (garlic_device_alloc_stats, live + pooled)
-    and the device memory in use after it."""
+    and the device memory in use after it.  score_part_ms is the library's total_ms: the MISSING fill and the score kernel;
+    the flatten passes are part of call_ms only.  tgls: the unweighted feed with likelihoods instead of the weighted one
+    (same panel, same fields, plus the score part's min / max and the kernel's roofline fraction)."""
     import time
     import torch
     from garlic_amd import abi, synth
@@ -40,7 +44,10 @@ def wlod_feed_leg(args):
     gen = torch.Generator(device=dev)
     gen.manual_seed(7)
     for l0, g in synth.genotype_chunks(spec, nind, dev):
-        gq = torch.randint(3, 61, g.shape, generator=gen, device=dev).to(torch.float64)
+        if tgls and args.gl_kind == "continuous":      # real-valued GQ in [3, 60): more values than the dictionary holds
+            gq = 3.0 + 57.0 * torch.rand(g.shape, generator=gen, device=dev, dtype=torch.float64)
+        else:
+            gq = torch.randint(3, 61, g.shape, generator=gen, device=dev).to(torch.float64)
         gl = torch.pow(torch.tensor(10.0, dtype=torch.float64, device=dev), -gq / 10.0)
         torch.cuda.synchronize()
         panel.set_genotypes_device(g.data_ptr(), g.shape[1], l0, g.shape[0])
@@ -49,19 +56,20 @@ def wlod_feed_leg(args):
     del g
     full_bytes = int(panel.out_layout(32, nind)[2]) * 8
     for W in [int(w) for w in args.winsizes.split(",")]:
-        ld = 1.0 + (max(2.0, W / 4.0) - 1.0) * torch.rand((nloci, W), generator=gen, device=dev, dtype=torch.float64)
-        torch.cuda.synchronize()
-        panel.set_ld_device(W, ld.data_ptr())
-        del ld
+        if not tgls:
+            ld = 1.0 + (max(2.0, W / 4.0) - 1.0) * torch.rand((nloci, W), generator=gen, device=dev, dtype=torch.float64)
+            torch.cuda.synchronize()
+            panel.set_ld_device(W, ld.data_ptr())
+            del ld
         for step in [int(x) for x in args.feed_steps.split(",")] if args.feed_steps else [W]:
-            for use_gl in (False, True):
+            for use_gl in ((True,) if tgls else (False, True)):
                 panel.release_scratch()
                 ctx.trim()
                 torch.cuda.empty_cache()
                 wall, score, kern = [], [], []
                 for k in range(2 + args.steps):
                     t0 = time.perf_counter()
-                    feed, _ = panel.lod_feed(W, error, max_gap, step, use_gl=use_gl, weighted=True, copy=False)
+                    feed, _ = panel.lod_feed(W, error, max_gap, step, use_gl=use_gl, weighted=not tgls, copy=False)
                     dt = time.perf_counter() - t0
                     st = panel.stats()
                     if k >= 2:
@@ -70,7 +78,7 @@ def wlod_feed_leg(args):
                         kern.append(st["chain_kernel_ms"])
                 live, pooled, _ = ctx.alloc_stats()
                 free_b, total_b = torch.cuda.mem_get_info()
-                line = {"mode": "wlod_feed", "snps": nloci, "inds": nind, "winsize": W, "step": step, "use_gl": use_gl,
+                line = {"mode": "tgls_feed" if tgls else "wlod_feed", "snps": nloci, "inds": nind, "winsize": W, "step": step, "use_gl": use_gl,
                         "repeats": args.steps, "feed_values": int(feed.shape[0]),
                         "call_ms_median": float(np.median(wall)), "call_ms_min": min(wall), "call_ms_max": max(wall),
                         "score_part_ms_median": float(np.median(score)),
@@ -80,6 +88,15 @@ def wlod_feed_leg(args):
                         "feed_checksum": float(np.sum(feed[np.isfinite(feed)]))}
                 if hasattr(panel, "feed_info"):
                     line["feed_form"], line["score_doubles"] = panel.feed_info()
+                if tgls:
+                    # the ring chain's HBM bytes per window: terms in + the samples out (form 3; a library without
+                    # garlic_lod_feed_info or with another form wrote full scores: 16.25 B)
+                    line["gl_kind"] = args.gl_kind
+                    line["score_part_ms_min"], line["score_part_ms_max"] = min(score), max(score)
+                    per_win = 8.0 + 8.0 / step if line.get("feed_form") == 3 else 16.25
+                    a = nloci * nind * per_win / (line["kernel_ms_median"] * 1e-3) / 1e9
+                    line["roofline"] = {"bound": "hbm", "achieved": a, "peak": 8000.0, "unit": "GB/s", "frac": a / 8000.0,
+                                        "algorithmic_bytes_per_window": per_win}
                 print(json.dumps(line), flush=True)
 
 
@@ -90,14 +107,15 @@ def main():
     ap.add_argument("--winsize", type=int, default=100)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--modes", default="lod,tgls,wlod")
-    ap.add_argument("--winsizes", default="100,10", help="wlod_feed: window sizes, one resident panel")
-    ap.add_argument("--feed-steps", default="", help="wlod_feed: thinning steps (default: the window size)")
+    ap.add_argument("--winsizes", default="100,10", help="wlod_feed / tgls_feed: window sizes, one resident panel")
+    ap.add_argument("--feed-steps", default="", help="wlod_feed / tgls_feed: thinning steps (default: the window size)")
+    ap.add_argument("--gl-kind", default="codes", choices=["codes", "continuous"], help="tgls_feed: the likelihoods' form")
     ap.add_argument("--tree", default="", help="take garlic_amd from this checkout instead of the one the tool is in")
     args = ap.parse_args()
     if args.tree:
         sys.path.insert(0, os.path.abspath(args.tree))
-    if args.modes == "wlod_feed":
-        return wlod_feed_leg(args)
+    if args.modes in ("wlod_feed", "tgls_feed"):
+        return wlod_feed_leg(args, tgls=args.modes == "tgls_feed")
 
     import torch
     from garlic_amd import abi, synth
