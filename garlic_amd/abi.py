@@ -33,6 +33,7 @@ SYMBOLS = [
     "garlic_device_alloc", "garlic_device_free", "garlic_panel_chain_kind", "garlic_device_alloc_stats",
     "garlic_panel_alloc_scores", "garlic_device_trim", "garlic_roh_coverage_fused", "garlic_roh_segments",
     "garlic_panel_alloc_scores_info", "garlic_lod_feed_info",
+    "garlic_panel_set_tgls_term_budget", "garlic_panel_tgls_terms_info",
 ]
 
 
@@ -121,6 +122,8 @@ def lib():
     L.garlic_panel_tgls_mode.argtypes = [_vp, _i32p, _i32p]
     L.garlic_panel_chain_kind.argtypes = [_vp, _i32p]
     L.garlic_lod_feed_info.argtypes = [_vp, _i32p, _i64p]
+    L.garlic_panel_set_tgls_term_budget.argtypes = [_vp, C.c_int64]
+    L.garlic_panel_tgls_terms_info.argtypes = [_vp, _i64p, _i64p, _i32p, _i32p]
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int and name not in ("garlic_hip_abi_version",):
@@ -529,6 +532,19 @@ class Panel:
         mode, by = C.c_int32(), C.c_int32()
         check(lib().garlic_panel_tgls_mode(self.handle, C.byref(mode), C.byref(by)))
         return mode.value, by.value
+
+    def set_tgls_term_budget(self, nbytes):
+        """garlic_panel_set_tgls_term_budget: 0 the whole term matrix or none (the default), > 0 an upper bound in bytes for the
+        term buffers (a larger matrix is built and read slab by slab), -1 whole if it fits, else slabs from the free memory"""
+        check(lib().garlic_panel_set_tgls_term_budget(self.handle, int(nbytes)))
+
+    def tgls_terms_info(self):
+        """{whole_bytes, resident_bytes, slab_blocks, n_slabs}: what the full term matrix needs, what the panel holds now, and
+        the slabs of the last unweighted use_gl call (n_slabs 0: it read a whole matrix or looked its terms up)"""
+        whole, res = C.c_int64(), C.c_int64()
+        sb, ns = C.c_int32(), C.c_int32()
+        check(lib().garlic_panel_tgls_terms_info(self.handle, C.byref(whole), C.byref(res), C.byref(sb), C.byref(ns)))
+        return {"whole_bytes": whole.value, "resident_bytes": res.value, "slab_blocks": sb.value, "n_slabs": ns.value}
 
     def roh_coverage(self, scores_ptr, winsize, cutoff, pitch_align=32, nind_out=None, inwin_pitch_align=1):
         """assembleROHWindows' coverage counts of device-resident scores: list of per-chromosome int16

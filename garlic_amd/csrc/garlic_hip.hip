@@ -237,6 +237,15 @@ struct garlic_panel {
     bool glterms_valid = false, glterms_scaled = false;   // scaled: holds (term * nomut) * norec of (glterms_M, glterms_mu)
     int32_t glterms_M = 0;
     double glterms_mu = 0.0;
+    // ... or, under garlic_panel_set_tgls_term_budget, two slab buffers [blk - b0][GOFF+nloci+pad][64] that every unweighted
+    // use_gl call fills and reads slab by slab (launch_tgls_slabs): slab k + 1 is built on slab_stream while the chain of
+    // slab k runs on the context's stream, ordered by the events alone
+    int64_t terms_budget = 0;                      // 0: whole matrix or none; > 0: bytes; -1: from the free memory
+    DevBuf<double> d_slab[2];
+    hipStream_t slab_stream = nullptr;
+    hipEvent_t ev_slab_begin = nullptr, ev_slab_built[2] = {}, ev_slab_read[2] = {};
+    DevBuf<int32_t> d_slab_queues;                 // one queue-head pair per slab
+    int32_t last_slab_blocks = 0, last_n_slabs = 0;   // garlic_panel_tgls_terms_info
 
     int tabgl_ncodes = 0;
     // TGLS, continuous likelihoods (more distinct values than the dictionary holds): the error
@@ -345,7 +354,8 @@ struct garlic_panel {
         int32_t W = 0, max_gap = 0, ind_begin = 0, ind_count = 0, pitch_align = 0, thin_step = 0;
         uint64_t blocks_hash = 0;                  // 0: every 64-individual block; else a hash of the block subset
         bool wlod_tuned = false, wlod_strip = false, feed_kernel = false;
-        auto tie() const { return std::tie(mode, W, max_gap, ind_begin, ind_count, pitch_align, thin_step, blocks_hash, wlod_tuned, wlod_strip, feed_kernel); }
+        int32_t slab_blocks = 0;                   // TGLS term slabs: the item list is one list per slab
+        auto tie() const { return std::tie(mode, W, max_gap, ind_begin, ind_count, pitch_align, thin_step, blocks_hash, wlod_tuned, wlod_strip, feed_kernel, slab_blocks); }
         bool operator==(const PlanKey &o) const { return tie() == o.tie(); }
     };
     struct Plan {
@@ -355,6 +365,8 @@ struct garlic_panel {
         int feed_per_cu = 1;      // persistent workgroups per CU the feed kernel of this plan is launched with (feed_grid)
         int32_t n_tiles = 0, n_segs = 0, n_strips = 0, n_feed_blocks = 0;
         int64_t n_runs = 0, n_valid = 0;
+        struct Slab { int32_t b0, b1; size_t item0, n_items; };   // panel blocks [b0, b1); its items: [item0, item0 + n_items)
+        std::vector<Slab> slabs;
     } plan;
 };
 
@@ -897,6 +909,8 @@ int switch_to_continuous(garlic_panel *p)
     int rc;
     HIP_TRY(hipStreamSynchronize(s));
     p->d_glterms.release();          // terms of the dictionary the panel leaves behind
+    p->d_slab[0].release();          // ... and its term slabs (continuous likelihoods have no budget)
+    p->d_slab[1].release();
     p->glterms_valid = false;
     if ((rc = p->d_glval.reserve(n))) return rc;
     if (p->d_codes.p && !p->gl_values.empty()) {
@@ -1139,6 +1153,60 @@ int ensure_gl_terms(garlic_panel *p, bool scaled = false, int32_t M = 0, double 
     return GARLIC_OK;
 }
 
+// ---- TGLS term slabs (garlic_panel_set_tgls_term_budget).  A 64-individual block of the matrix and what the panel holds of it:
+size_t tgls_block_bytes(const garlic_panel *p) { return sizeof(double) * (size_t)(GOFF + p->nloci + GPAD_BACK) * WAVE; }
+
+// Slab size under a bound of `bytes`: the largest number of blocks s whose buffers fit -- the slabs of a call alternate between
+// two buffers, so the first needs s blocks and the second what the second slab holds, min(s, nblk - s), of the nblk blocks that
+// hold individuals (the whole matrix has nind_pad / 64 of them, a pad block more when nind leaves less than one free).  0: none fits.
+int32_t tgls_slab_blocks_for(const garlic_panel *p, size_t bytes)
+{
+    const int64_t nblk = (p->nind + WAVE - 1) / WAVE;
+    int32_t best = 0;
+    for (int64_t s = 1; s <= nblk; s++)
+        if ((size_t)(s + std::min(s, nblk - s)) * tgls_block_bytes(p) <= bytes) best = (int32_t)s;
+    return best;
+}
+
+void release_tgls_slabs(garlic_panel *p)
+{
+    p->d_slab[0].release();
+    p->d_slab[1].release();
+}
+
+// The unweighted use_gl call at hand: *slab_blocks > 0 when its terms are to come slab by slab, 0 when the whole matrix (or,
+// declined, the look-up chain) serves it as before.  Dictionary-coded panels only; GARLIC_GL_NO_TERMS keeps its meaning.
+int tgls_terms_or_slabs(garlic_panel *p, int32_t *slab_blocks)
+{
+    *slab_blocks = 0;
+    const size_t block = tgls_block_bytes(p), whole = block * (size_t)(p->nind_pad / WAVE);
+    int rc;
+    if (p->gl_cont || p->terms_budget == 0 || getenv("GARLIC_GL_NO_TERMS") || (p->terms_budget > 0 && whole <= (size_t)p->terms_budget)) {
+        if (!p->gl_cont && p->d_slab[0].p) {       // (a budget that now admits the whole matrix: not both)
+            HIP_TRY(hipStreamSynchronize(p->ctx->stream));
+            release_tgls_slabs(p);
+        }
+        return ensure_gl_terms(p);
+    }
+    size_t bytes = (size_t)p->terms_budget;
+    if (p->terms_budget < 0) {
+        // the whole matrix when today's test lets it in; otherwise two slab buffers in half of what is free now
+        if ((rc = ensure_gl_terms(p))) return rc;
+        if (p->glterms_valid && !p->glterms_scaled) return GARLIC_OK;
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return GARLIC_OK;
+        bytes = (free_b + (p->d_slab[0].cap + p->d_slab[1].cap) * sizeof(double)) / 2;
+        if (!tgls_slab_blocks_for(p, bytes)) return GARLIC_OK;     // not even one-block slabs: the look-up chain
+    } else if (p->d_glterms.cap) {
+        // a whole matrix from before the budget (or the scaled one of a weighted call, which the budget does not bind)
+        HIP_TRY(hipStreamSynchronize(p->ctx->stream));
+        p->d_glterms.release();
+        p->glterms_valid = false;
+    }
+    *slab_blocks = tgls_slab_blocks_for(p, bytes);
+    return GARLIC_OK;
+}
+
 // ---- wLOD: per-SNP {nomut, norec} (garlic-roh.cpp:134-140, 246-249), host libm exp
 int ensure_decay_table(garlic_panel *p, int32_t M, double mu)
 {
@@ -1215,6 +1283,7 @@ struct LodForm {
     size_t tile_lds = 0;           // dynamic LDS of the tile kernels
     bool aligned16 = false;        // finish_form: every score row 16-byte aligned
     bool strip_three = false;      // finish_form: the 80-VGPR strip kernel, three workgroups per CU
+    int32_t slab_blocks = 0;       // tgls_ring / tgls_feed: the term matrix comes slab by slab, this many blocks each
 };
 
 int check_lod_args(const garlic_panel *p, const LodCall &c)
@@ -1243,7 +1312,7 @@ int decide_form(garlic_panel *p, const LodCall &c, LodForm &f)
     if (f.use_gl) {
         if (!p->have_gl) return fail(GARLIC_ERR_STATE, "use_gl set but no genotype likelihoods were given");
         if (!p->gl_cont && (rc = ensure_gl_table(p))) return rc;
-        if (mode == MODE_LOD_GL && (rc = ensure_gl_terms(p))) return rc;
+        if (mode == MODE_LOD_GL && (rc = tgls_terms_or_slabs(p, &f.slab_blocks))) return rc;
     } else if ((rc = ensure_term_table(p, c.error))) return rc;
     if (mode == MODE_WLOD) {
         if (!p->have_ld || p->ld_winsize != W)
@@ -1269,10 +1338,12 @@ int decide_form(garlic_panel *p, const LodCall &c, LodForm &f)
     if (mode != MODE_WLOD) {
         f.feed_asm = !getenv("GARLIC_FEED_NO_ASM");
         if (mode == MODE_LOD) f.family = c.thin_step > 0 ? Family::feed : Family::chain;   // thinned output: every wave a chain of its own (feed_kernel.hpp)
+        else if (f.slab_blocks && tgls_ring_shape) f.family = Family::tgls_ring;      // (launch_tgls_slabs; only the ring chains read slabs)
         else if (!p->glterms_valid || p->glterms_scaled) f.family = Family::tgls_lookup;
         else f.family = tgls_ring_shape ? Family::tgls_ring : Family::tgls_terms;
         f.writes_bits = f.family == Family::tgls_ring;
         if (f.exact_possible && getenv("GARLIC_EXACT_CHAIN_ONLY")) f.family = Family::exact;
+        if (f.family != Family::tgls_ring) f.slab_blocks = 0;
         // TGLS, thinned output: the ring chain that stores the sampled windows only (tgls_feed_kernel.hpp); the other TGLS
         // chains write full scores.  GARLIC_TGLS_FEED_FULL: never.
         if (mode == MODE_LOD_GL && c.thin_step > 0) {
@@ -1387,10 +1458,21 @@ int plan_lod(garlic_panel *p, const LodCall &c, const LodForm &form, const Layou
     // workgroups of lod_chain_kernel pull them from a device counter.
     const std::vector<int> order = longest_first(w.runs);
     w.items.reserve(w.runs.size() * nblk);
-    for (size_t i = 0; i < order.size(); i++) {
-        const Run &r = w.runs[order[i]];
-        for (int k = 0; k < nblk; k++)
-            if (!c.blocks || (*c.blocks)[(size_t)k]) w.items.push_back(ChainItem{r.chr, r.a, r.b, k * WAVE});
+    // TGLS term slabs: one list per slab, the lists one behind the other -- a slab begins at the next block in play and
+    // spans slab_blocks consecutive blocks (the subset feed's skipped blocks get no items, a slab of nothing else no launch);
+    // a chain launch sees its own slab's list and queue only, longest runs first inside it.  Otherwise one list over all blocks.
+    const int per_list = form.slab_blocks ? form.slab_blocks : std::max(nblk, 1);
+    for (int k0 = 0; k0 < nblk && !w.runs.empty(); ) {
+        if (c.blocks && !(*c.blocks)[(size_t)k0]) { k0++; continue; }
+        const int k1 = std::min(nblk, k0 + per_list);
+        const size_t item0 = w.items.size();
+        for (size_t i = 0; i < order.size(); i++) {
+            const Run &r = w.runs[order[i]];
+            for (int k = k0; k < k1; k++)
+                if (!c.blocks || (*c.blocks)[(size_t)k]) w.items.push_back(ChainItem{r.chr, r.a, r.b, k * WAVE});
+        }
+        if (form.slab_blocks) plan.slabs.push_back(Plan::Slab{c.ind_begin / WAVE + k0, c.ind_begin / WAVE + k1, item0, w.items.size() - item0});
+        k0 = k1;
     }
     if (form.family == Family::feed) {
         // the thinned score matrix: row = individual, column = locus / step
@@ -1628,22 +1710,95 @@ int launch_chain(garlic_panel *p, const LodCall &c, const LodForm &form, Plan &p
     return GARLIC_OK;
 }
 
+// The ring chains over a term matrix that is never whole (garlic_panel_set_tgls_term_budget): per slab of the plan
+// gl_terms_slab_kernel into one of two buffers on the panel's second stream, then the chain of that slab's items on the
+// context's stream.  Events alone order them -- a chain waits for its slab's terms, a buffer is rebuilt once the chain
+// that read it (two slabs back) has finished -- so the terms of slab k + 1 are built while the chain of slab k runs and
+// every kernel can finish on its own.  Same kernels, same doubles as over the whole matrix.
+int launch_tgls_slabs(garlic_panel *p, const LodCall &c, const LodForm &form, const Plan &plan, double *d_out)
+{
+    garlic_ctx *ctx = p->ctx;
+    hipStream_t s = ctx->stream;
+    const int64_t rows = GOFF + p->nloci + GPAD_BACK;
+    const size_t n_slabs = plan.slabs.size();
+    int rc;
+    p->last_slab_blocks = form.slab_blocks;
+    p->last_n_slabs = (int32_t)n_slabs;
+    if (!n_slabs) return GARLIC_OK;
+    if (!p->slab_stream) {
+        HIP_TRY(hipStreamCreateWithFlags(&p->slab_stream, hipStreamNonBlocking));
+        for (hipEvent_t *ev : {&p->ev_slab_begin, &p->ev_slab_built[0], &p->ev_slab_built[1], &p->ev_slab_read[0], &p->ev_slab_read[1]})
+            HIP_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+    }
+    // buffer q serves the slabs q, q + 2, ..: room for the largest of them (a change of plan that needs more waits for the stream first)
+    for (int q = 0; q < 2; q++) {
+        size_t blocks = 0;
+        for (size_t k = (size_t)q; k < n_slabs; k += 2) blocks = std::max(blocks, (size_t)(plan.slabs[k].b1 - plan.slabs[k].b0));
+        const size_t need = blocks * (size_t)rows * WAVE;
+        if (need > p->d_slab[q].cap || (!need && p->d_slab[q].cap)) {
+            HIP_TRY(hipStreamSynchronize(s));
+            p->d_slab[q].release();
+            if (need && (rc = p->d_slab[q].reserve(need))) return rc;
+        }
+    }
+    if ((rc = p->d_slab_queues.reserve(2 * n_slabs))) return rc;
+    HIP_TRY(hipMemsetAsync(p->d_slab_queues.p, 0, 2 * n_slabs * sizeof(int32_t), s));
+    // what the term pass reads (tables, codes, genotypes) was put on the context's stream
+    HIP_TRY(hipEventRecord(p->ev_slab_begin, s));
+    HIP_TRY(hipStreamWaitEvent(p->slab_stream, p->ev_slab_begin, 0));
+    VariantArgs a{p->d_packed.p, nullptr, p->d_tabgl.p, p->d_codes.p, nullptr, nullptr, nullptr, nullptr, nullptr,
+                  p->nind_pad, p->nwordrows, 0, 0, 0, (int32_t)p->gl_values.size(), 1, nullptr, 0};
+    const size_t terms_lds = sizeof(double) * GL_TERMS_S * 4 * (size_t)a.ncodes;      // <= 64 KB (256 codes)
+    if (terms_lds > 48 * 1024)
+        HIP_TRY(hipFuncSetAttribute((const void *)gl_terms_slab_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)terms_lds));
+    const unsigned terms_grid = (unsigned)((p->nloci + GL_TERMS_S - 1) / GL_TERMS_S + (GL_PAD_ROWS + GL_TERMS_S - 1) / GL_TERMS_S);
+    if (form.cov_bits) p->cov_written = true;
+    for (size_t k = 0; k < n_slabs; k++) {
+        const Plan::Slab &sl = plan.slabs[k];
+        const int q = (int)(k & 1);
+        if (k >= 2) HIP_TRY(hipStreamWaitEvent(p->slab_stream, p->ev_slab_read[q], 0));
+        hipLaunchKernelGGL(gl_terms_slab_kernel, dim3(terms_grid), dim3(256), terms_lds, p->slab_stream, a, p->nloci, rows, sl.b0, sl.b1,
+                           p->d_slab[q].p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(p->ev_slab_built[q], p->slab_stream));
+        HIP_TRY(hipStreamWaitEvent(s, p->ev_slab_built[q], 0));
+        int workers = ctx->n_cu;
+        if (const char *e = getenv("GARLIC_WORKERS")) workers = std::max(1, atoi(e));
+        workers = std::min<int>(workers, (int)sl.n_items);
+        if (form.family == Family::tgls_feed) {
+            TglsFeedArgs t{p->d_slab[q].p, rows, p->d_items.p + sl.item0, p->d_chrs.p, d_out,
+                           c.ind_begin, c.ind_count, c.W, (int32_t)sl.n_items, c.thin_step, sl.b0, p->d_slab_queues.p + 2 * k};
+            hipLaunchKernelGGL(tgls_feed_kernel, dim3((unsigned)workers), dim3(TGF_THREADS), 0, s, t);
+        } else {
+            TglsArgs t{p->d_slab[q].p, rows, p->d_items.p + sl.item0, p->d_chrs.p, d_out,
+                       c.ind_begin, c.ind_count, c.W, (int32_t)sl.n_items, sl.b0, p->d_slab_queues.p + 2 * k, p->cov_pending};
+            hipLaunchKernelGGL(lod_chain_ring_kernel, dim3((unsigned)workers), dim3(TG_THREADS), 0, s, t);
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(p->ev_slab_read[q], s));
+    }
+    return GARLIC_OK;
+}
+
 int launch_tgls(garlic_panel *p, const LodCall &c, const LodForm &form, const Plan &plan, int workers, double *d_out)
 {
     hipStream_t s = p->ctx->stream;
     const int64_t rows = GOFF + p->nloci + GPAD_BACK;
     if (form.cov_bits && !form.writes_bits) return GARLIC_INTERNAL_NO_BITS;      // only the ring chain takes this shape
+    p->last_slab_blocks = p->last_n_slabs = 0;
+    if (form.slab_blocks && (form.family == Family::tgls_feed || form.family == Family::tgls_ring))
+        return launch_tgls_slabs(p, c, form, plan, d_out);
     if (form.family == Family::tgls_feed) {
         // the same ring chain storing the sampled windows only, into the thinned matrix (tgls_feed_kernel.hpp)
         TglsFeedArgs t{p->d_glterms.p, rows, p->d_items.p, p->d_chrs.p, d_out,
-                       c.ind_begin, c.ind_count, c.W, (int32_t)plan.n_items, c.thin_step, p->d_counter.p};
+                       c.ind_begin, c.ind_count, c.W, (int32_t)plan.n_items, c.thin_step, 0, p->d_counter.p};
         hipLaunchKernelGGL(tgls_feed_kernel, dim3((unsigned)workers), dim3(TGF_THREADS), 0, s, t);
         return GARLIC_OK;
     }
     if (form.family == Family::tgls_ring) {
         // persistent workgroups, every term row through an LDS ring once (tgls_ring_kernel.hpp)
         TglsArgs t{p->d_glterms.p, rows, p->d_items.p, p->d_chrs.p, d_out,
-                   c.ind_begin, c.ind_count, c.W, (int32_t)plan.n_items, p->d_counter.p, p->cov_pending};
+                   c.ind_begin, c.ind_count, c.W, (int32_t)plan.n_items, 0, p->d_counter.p, p->cov_pending};
         if (form.cov_bits) p->cov_written = true;
         hipLaunchKernelGGL(lod_chain_ring_kernel, dim3((unsigned)workers), dim3(TG_THREADS), 0, s, t);
         return GARLIC_OK;
@@ -1754,6 +1909,7 @@ int launch_lod(garlic_panel *p, Mode mode, int32_t W, double error, int32_t max_
                     thin_step, where, pitch_align, error, mu, out, blocks};
     LodForm form;
     if ((rc = check_lod_args(p, c)) || (rc = decide_form(p, c, form))) return rc;
+    if (mode == MODE_LOD_GL) p->last_slab_blocks = p->last_n_slabs = 0;      // (launch_tgls_slabs sets them)
     const Layout Lhost = make_layout(p, pitch_align, ind_count), L = make_layout(p, c.pitch_align, ind_count, thin_step);
     for (int k = 0; k < p->nchr; k++)
         if (3 * L.pitch[k] * 8 + 512 >= (int64_t)1 << 32)
@@ -1763,7 +1919,7 @@ int launch_lod(garlic_panel *p, Mode mode, int32_t W, double error, int32_t max_
     finish_form(p, c, L, d_out, form);
 
     garlic_panel::PlanKey key{(int)mode, W, max_gap, ind_begin, ind_count, c.pitch_align, thin_step, 0, form.wlod_tuned,
-                form.family == Family::wlod_strip, thin_step > 0};
+                form.family == Family::wlod_strip, thin_step > 0, form.slab_blocks};
     if (blocks) {
         key.blocks_hash = 0xCBF29CE484222325ull;
         for (uint8_t b : *blocks) key.blocks_hash = (key.blocks_hash ^ (b ? 1u : 2u)) * 0x100000001B3ull;
@@ -1967,6 +2123,12 @@ int garlic_panel_destroy(garlic_panel *p)
     (void)hipStreamSynchronize(p->ctx->stream);
     p->d_out.release();
     release_feed_slots(p);
+    if (p->slab_stream) {
+        (void)hipStreamSynchronize(p->slab_stream);
+        for (hipEvent_t ev : {p->ev_slab_begin, p->ev_slab_built[0], p->ev_slab_built[1], p->ev_slab_read[0], p->ev_slab_read[1]})
+            if (ev) (void)hipEventDestroy(ev);
+        (void)hipStreamDestroy(p->slab_stream);
+    }
     delete p;      // (its DevBuf members free themselves: the device is set and the stream idle)
     return GARLIC_OK;
 }
@@ -3591,6 +3753,37 @@ int garlic_panel_tgls_mode(garlic_panel *p, int32_t *mode, int32_t *terms_by)
     if (!p || !mode) return fail(GARLIC_ERR_INVALID, "panel and mode are required");
     *mode = !p->have_gl ? 0 : (p->gl_cont ? GARLIC_TGLS_CONTINUOUS : GARLIC_TGLS_DICTIONARY);
     if (terms_by) *terms_by = p->glterms_valid ? p->gl_terms_by : 0;
+    return GARLIC_OK;
+}
+
+int garlic_panel_set_tgls_term_budget(garlic_panel *p, int64_t bytes)
+{
+    if (!p) return fail(GARLIC_ERR_INVALID, "panel is NULL");
+    if (bytes < -1) return fail(GARLIC_ERR_INVALID, "term budget %lld: 0, -1 or a number of bytes", (long long)bytes);
+    if (bytes > 0 && !tgls_slab_blocks_for(p, (size_t)bytes))
+        return fail(GARLIC_ERR_INVALID, "term budget of %lld bytes: the buffers of one-block slabs of this panel need %lld",
+                    (long long)bytes, (long long)(tgls_block_bytes(p) * (p->nind > WAVE ? 2 : 1)));
+    int rc;
+    if ((rc = set_device(p->ctx))) return rc;
+    HIP_TRY(hipStreamSynchronize(p->ctx->stream));
+    p->terms_budget = bytes;
+    if (p->gl_cont) return GARLIC_OK;            // (8 bytes per genotype are the panel's data there: no budget)
+    // what the new bound does not allow goes now; the next call builds what it needs
+    if (bytes == 0 || (bytes > 0 && (p->d_slab[0].cap + p->d_slab[1].cap) * sizeof(double) > (size_t)bytes)) release_tgls_slabs(p);
+    if (bytes > 0 && p->d_glterms.cap * sizeof(double) > (size_t)bytes) {
+        p->d_glterms.release();
+        p->glterms_valid = false;
+    }
+    return GARLIC_OK;
+}
+
+int garlic_panel_tgls_terms_info(garlic_panel *p, int64_t *whole_bytes, int64_t *resident_bytes, int32_t *slab_blocks, int32_t *n_slabs)
+{
+    if (!p) return fail(GARLIC_ERR_INVALID, "panel is NULL");
+    if (whole_bytes) *whole_bytes = (int64_t)(tgls_block_bytes(p) * (size_t)(p->nind_pad / WAVE));
+    if (resident_bytes) *resident_bytes = (int64_t)((p->d_glterms.cap + p->d_slab[0].cap + p->d_slab[1].cap) * sizeof(double));
+    if (slab_blocks) *slab_blocks = p->last_slab_blocks;
+    if (n_slabs) *n_slabs = p->last_n_slabs;
     return GARLIC_OK;
 }
 

@@ -34,12 +34,13 @@ namespace garlic {
 constexpr int TGF_THREADS = 3 * WAVE;    // LOAD0, LOAD1, CHAIN
 
 struct TglsFeedArgs {
-    const double *terms;      // [blk][term_rows][64]
+    const double *terms;      // [blk - blk0][term_rows][64]
     int64_t term_rows;
     const ChainItem *items;
     const ChrDev *chrs;       // out_base / out_pitch: the thinned matrix
     double *out;
     int32_t ind_begin, ind_count, winsize, n_items, thin_step;
+    int32_t blk0;             // first block `terms` holds (TglsArgs::blk0)
     int32_t *next_item;       // [0] queue head, [1] workgroups that have left (both zero at launch; reset by the last one)
 };
 
@@ -78,7 +79,7 @@ tgls_feed_kernel(TglsFeedArgs p)
         const int ring_rows = single ? TG_RING : TG_RING / 2;
         const int64_t col0 = (int64_t)p.ind_begin + it.ind0;            // block-aligned (host-checked)
         const int64_t Gbase = c.loc_base + GOFF;
-        const double *blk = p.terms + ((col0 >> 6) * p.term_rows) * WAVE;   // the block's rows, 64 doubles each
+        const double *blk = p.terms + (((col0 >> 6) - p.blk0) * p.term_rows) * WAVE;   // the block's rows, 64 doubles each
         // row streams: leaving rows start at local locus first - 1, entering rows at first + W - 1
         const double *trail = blk + (Gbase + first - 1) * WAVE;
         const double *lead = blk + (Gbase + first + W - 1) * WAVE;

@@ -44,12 +44,14 @@ constexpr int TG_THREADS = 4 * WAVE;    // LOAD0, LOAD1, CHAIN, POST
 constexpr int TG_SINGLE_MAX_W = TG_RING - 32 - 4 * TG_GROUP * 2;   // one stream: W + the tile + a few rounds must fit
 
 struct TglsArgs {
-    const double *terms;      // [blk][term_rows][64]
+    const double *terms;      // [blk - blk0][term_rows][64]
     int64_t term_rows;
     const ChainItem *items;
     const ChrDev *chrs;
     double *out;
     int32_t ind_begin, ind_count, winsize, n_items;
+    int32_t blk0;             // first 64-individual block `terms` holds: 0 for the whole matrix, a slab's first block otherwise
+                              // (every item of the launch lies in the slab: the host builds one item list per slab)
     int32_t *next_item;       // [0] queue head, [1] workgroups that have left (both zero at launch; reset by the last one)
     CovBits cov;              // coverage bits instead of scores (variant_kernels.hpp): one dword per lane and tile; NULL: scores
 };
@@ -160,7 +162,7 @@ lod_chain_ring_kernel(TglsArgs p)
         const int ring_rows = single ? TG_RING : TG_RING / 2;
         const int64_t col0 = (int64_t)p.ind_begin + it.ind0;            // block-aligned (host-checked)
         const int64_t Gbase = c.loc_base + GOFF;
-        const double *blk = p.terms + ((col0 >> 6) * p.term_rows) * WAVE;   // the block's rows, 64 doubles each
+        const double *blk = p.terms + (((col0 >> 6) - p.blk0) * p.term_rows) * WAVE;   // the block's rows, 64 doubles each
         // row streams: leaving rows start at local locus first - 1, entering rows at first + W - 1
         const double *trail = blk + (Gbase + first - 1) * WAVE;
         const double *lead = blk + (Gbase + first + W - 1) * WAVE;

@@ -263,6 +263,52 @@ gl_terms_lds_kernel(VariantArgs p, int64_t nloci, int64_t rows, int nblk, const 
     }
 }
 
+// The slab form: the terms of the blocks [b0, b1) only, into a slab-local matrix terms[blk - b0][rows][64] that the
+// ring chains then read with TglsArgs::blk0 = b0 (garlic_panel_set_tgls_term_budget: the whole matrix is never resident).
+// Same staging -- a workgroup's table rows come in once for all blocks of the slab -- and the same look-ups, so the
+// same doubles.  The pad rows in front of and behind each block's SNPs (+0.0, the term of a missing genotype) are
+// written here too, by the workgroups behind the SNP chunks, GL_TERMS_S pad rows each: a slab buffer is rebuilt for
+// every slab of every call, and two memsets per block and slab would be hundreds of tiny operations on the stream.
+// A block's rows start at a multiple of 512 B (one row) from the buffer's base, as in the whole matrix; the ring
+// loaders ask for no more of their source (their 1-KB pieces are aligned in LDS, not in memory).
+constexpr int GL_PAD_ROWS = GOFF + GPAD_BACK;
+__global__ void __launch_bounds__(256)
+gl_terms_slab_kernel(VariantArgs p, int64_t nloci, int64_t rows, int b0, int b1, double *__restrict__ terms)
+{
+    extern __shared__ double gl_rows[];                      // [GL_TERMS_S][ncodes][4]
+    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x >> 6;
+    const int64_t n_chunks = (nloci + GL_TERMS_S - 1) / GL_TERMS_S;
+    if ((int64_t)blockIdx.x >= n_chunks) {                   // pad rows: pr < GOFF in front, the others behind the SNPs
+        const int pr0 = (int)((int64_t)blockIdx.x - n_chunks) * GL_TERMS_S;
+        for (int blk = b0 + wave; blk < b1; blk += 4)
+#pragma unroll
+            for (int u = 0; u < GL_TERMS_S; u++) {
+                const int pr = pr0 + u;
+                if (pr < GL_PAD_ROWS) terms[((int64_t)(blk - b0) * rows + (pr < GOFF ? pr : nloci + pr)) * WAVE + lane] = 0.0;
+            }
+        return;
+    }
+    const int64_t l0 = (int64_t)blockIdx.x * GL_TERMS_S;
+    const int ns = (int)min<int64_t>(GL_TERMS_S, nloci - l0);
+    const int64_t G0 = GOFF + l0;
+    const int row_doubles = p.ncodes * 4;
+    for (int e = threadIdx.x; e < ns * row_doubles; e += blockDim.x) gl_rows[e] = p.tabgl[G0 * row_doubles + e];
+    __syncthreads();
+    const int shift0 = 2 * (int)(G0 & 15);                   // 0 or 16: the chunk is one half of a genotype word
+    for (int blk = b0 + wave; blk < b1; blk += 4) {
+        const int64_t col = (int64_t)blk * WAVE + lane;
+        const uint32_t word = p.packed[packed_index(G0 >> 4, col, p.nwordrows)] >> shift0;
+        uint32_t code[GL_TERMS_S];
+#pragma unroll
+        for (int u = 0; u < GL_TERMS_S; u++) code[u] = u < ns ? p.codes[(G0 + u) * p.nind_pad + col] : 0u;
+#pragma unroll
+        for (int u = 0; u < GL_TERMS_S; u++)
+            if (u < ns)
+                terms[((int64_t)(blk - b0) * rows + G0 + u) * WAVE + lane] =
+                    gl_rows[(u * p.ncodes + (int)code[u]) * 4 + (int)((word >> (2 * u)) & 3u)];
+    }
+}
+
 // ---- Continuous likelihoods (--gl-type GL / PL: more distinct values than a dictionary holds).
 // The error probabilities live in the term matrix's layout, vals[blk][rows][64]; the terms come from
 // lod() evaluated on the device with glibc's log10 restated (tgls_math.hpp).

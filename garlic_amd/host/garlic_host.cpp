@@ -1009,6 +1009,8 @@ void LodEngine::upload(std::vector<HapData *> *haps, std::vector<FreqData *> *fr
         check(garlic_panel_create(s.ctx, nchr, impl->chr_nloci.data(), s.nind, &s.panel), "garlic_panel_create");
         check(garlic_panel_set_map(s.panel, pos.data(), gpos.data(), cs.data(), ce.data()), "garlic_panel_set_map");
         check(garlic_panel_set_freq(s.panel, freq.data()), "garlic_panel_set_freq");
+        if (USE_GL && g_options.tgls_term_bytes != 0)      // --tgls-term-gb: the term matrix of each shard in slabs
+            check(garlic_panel_set_tgls_term_budget(s.panel, g_options.tgls_term_bytes), "garlic_panel_set_tgls_term_budget");
     }
     // genotype rows are separate allocations in HapData: stage a slab of SNP rows at a time
     const int64_t slab = std::max<int64_t>(1, ((int64_t)64 << 20) / (2 * (int64_t)impl->nind));
@@ -1070,6 +1072,15 @@ void LodEngine::upload(std::vector<HapData *> *haps, std::vector<FreqData *> *fr
 }
 
 LodEngine::~LodEngine() { release(); }
+
+void LodEngine::tglsTermSlabs(int *slab_blocks, int *n_slabs)
+{
+    int32_t sb = 0, ns = 0;
+    if (!impl->shards.empty())
+        check(garlic_panel_tgls_terms_info(impl->shards[0].panel, nullptr, nullptr, &sb, &ns), "garlic_panel_tgls_terms_info");
+    if (slab_blocks) *slab_blocks = sb;
+    if (n_slabs) *n_slabs = ns;
+}
 
 std::vector<WinData *> *LodEngine::lodWindows(int winsize, double error, int MAX_GAP)
 {

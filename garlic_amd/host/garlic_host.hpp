@@ -204,6 +204,9 @@ struct LodOptions {
     // --ld-subsample draw: the reference seeds its generator with time(NULL)
     // (garlic-data.cpp:346); 0 does the same here, any other value makes the draw repeatable.
     unsigned long long ld_seed = 0;
+    // garlic_panel_set_tgls_term_budget for every shard's panel (dictionary-coded likelihoods): 0 the whole term matrix or
+    // none, > 0 bytes (the matrix in slabs when it is larger), -1 whole if it fits, else slabs from the free memory
+    long long tgls_term_bytes = 0;
 };
 void setLodOptions(const LodOptions &o);
 
@@ -274,6 +277,8 @@ public:
     std::vector<ROHData *> *assembleROHWindows(IndData *indData, double lodScoreCutoff, ROHLength **rohLength, int winSize,
                                                double error, int MAX_GAP, double OVERLAP_FRAC, bool CM, bool weighted = false,
                                                int M = 0, double mu = 0.0);
+    // garlic_panel_tgls_terms_info of the first shard: the slabs of its last unweighted call with likelihoods (n_slabs 0: none)
+    void tglsTermSlabs(int *slab_blocks, int *n_slabs);
     LodEngine(const LodEngine &) = delete;
     LodEngine &operator=(const LodEngine &) = delete;
 

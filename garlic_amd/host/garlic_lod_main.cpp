@@ -34,6 +34,7 @@ struct Args {
     int resample = 0;              // src/garlic-cli.cpp:62-64: resamples for the allele frequencies
     unsigned long long resample_seed = 0;   // extension: 0 = time-seeded like the reference
     unsigned long long ld_seed = 0; // extension: 0 = time-seeded like the reference
+    double tgls_term_gb = 0;       // extension: garlic_panel_set_tgls_term_budget in GB (0 whole matrix or none, -1 automatic)
     unsigned long long kde_seed = 0; // extension: the --kde-subsample draw, 0 = time-seeded like the reference
     double mu = 1e-9, overlap_frac = 0.25;
     bool have_cutoff = false, cm = false;   // --lod-cutoff (src/garlic-cli.cpp:101), --cm (:167)
@@ -49,7 +50,7 @@ struct Args {
                  "         [--auto-winsize] [--auto-winsize-step N] [--winsize-stream] [--max-gap N] [--overlap-frac X]\n"
                  "         [--freq-file F] [--tped-missing C] [--raw-lod] [--kde-subsample N] [--kde-seed S] [--no-kde-thinning]\n"
                  "         [--weighted --map F --M N --mu X --ld-subsample N --ld-seed S --threads N]\n"
-                 "         [--resample N --resample-seed S] [--gpus N | --devices 0,1,...] [--genotype-cache F]\n"
+                 "         [--resample N --resample-seed S] [--gpus N | --devices 0,1,...] [--genotype-cache F] [--tgls-term-gb X]\n"
                  "         [--lod-cutoff X --size-bounds B1 B2 ... [--cm]]   (ROH calls: <out>.roh.bed)\n";
     exit(1);
 }
@@ -100,6 +101,7 @@ Args parse(int argc, char **argv)
         else if (f == "--resample-seed") a.resample_seed = strtoull(val().c_str(), nullptr, 10);
         else if (f == "--no-kde-thinning") a.kde_thinning = !a.kde_thinning;
         else if (f == "--gpus") a.gpus = atoi(val().c_str());
+        else if (f == "--tgls-term-gb") a.tgls_term_gb = atof(val().c_str());
         else if (f == "--devices") {   // explicit HIP ordinals, e.g. 0,1,2,3 (an ordinal may repeat: shards share that GPU)
             std::stringstream ss(val());
             std::string tok;
@@ -210,6 +212,12 @@ int main(int argc, char **argv)
             for (int d = 0; d < a.gpus; d++) devices.push_back(d);
 
         std::vector<int> sizes = a.winsize_multi.empty() ? std::vector<int>{a.winsize} : a.winsize_multi;
+        if (a.tgls_term_gb != 0) {   // per device: the TGLS term matrix in slabs when it is larger than this
+            LodOptions lo;
+            lo.devices = devices;
+            lo.tgls_term_bytes = a.tgls_term_gb < 0 ? -1 : (long long)(a.tgls_term_gb * 1e9);
+            setLodOptions(lo);
+        }
         LodEngine engine(haps, freqs, maps, gls, &centro, USE_GL, devices); // one upload, many window sizes
         const std::vector<int> ldsub = a.weighted ? drawLdSubsample(numInd, a.ld_subsample, a.ld_seed) : std::vector<int>();
         // selectLODCutoff (garlic-roh.cpp:674-675): the KDE sees --kde-subsample individuals (default 20,
@@ -291,6 +299,12 @@ int main(int argc, char **argv)
         } else if (a.auto_winsize)
             std::cerr << "NOTE: --auto-winsize picks among the feeds above in GARLIC's KDE stage (Phase II, not part of this tool); "
                          "--winsize-stream lets that stage ask for further window sizes on the resident panel\n";
+        if (USE_GL && a.tgls_term_gb != 0) {
+            int slab_blocks = 0, n_slabs = 0;
+            engine.tglsTermSlabs(&slab_blocks, &n_slabs);
+            std::cerr << "TGLS terms (--tgls-term-gb " << a.tgls_term_gb << "): last call in " << n_slabs << " slabs of " << slab_blocks
+                      << " blocks on the first device (0: the whole matrix, or terms looked up)\n";
+        }
     } catch (...) {
         return 1;
     }

@@ -46,7 +46,8 @@ extern "C" {
  * 6: garlic_roh_coverage_fused (coverage counts without the score matrix)
  * 7: garlic_roh_segments (the ROH segments of assembleROHWindows without scores or counts)
  * 8: garlic_call_stats::n_stall_reruns / n_count_timeouts, garlic_panel_alloc_scores_info; garlic_lod_feed_info (added
- *    under the same number: nothing that existed changed); GARLIC_FEED_TGLS_CHAIN (a fourth value of its form, likewise) */
+ *    under the same number: nothing that existed changed); GARLIC_FEED_TGLS_CHAIN (a fourth value of its form, likewise);
+ *    garlic_panel_set_tgls_term_budget, garlic_panel_tgls_terms_info (likewise) */
 #define GARLIC_HIP_ABI_VERSION 8
 
 #define GARLIC_OK 0
@@ -133,6 +134,8 @@ int garlic_panel_set_genotypes_2bit(garlic_panel *panel, const uint8_t *rows, in
  * lod() (src/garlic-roh.cpp:355-386) runs on the device with glibc's log10 restated operation by
  * operation -- checked against the host's log10 when first needed; should they ever differ, the terms
  * are computed on the host instead.  Same scores either way: those of the reference on this host.
+ * (Dictionary codes: the terms are expanded into a matrix of 8 bytes per genotype when the device has room for it, whole
+ * or -- garlic_panel_set_tgls_term_budget -- slab by slab; with neither the chain looks them up.)
  * When the device cannot hold values and terms side by side the values are converted in place at the
  * first computation; changing genotypes, frequencies, the map or the weighting parameters (M, mu)
  * afterwards then needs the likelihoods uploaded again, over all loci (GARLIC_ERR_STATE says so). */
@@ -153,6 +156,36 @@ int garlic_panel_set_gl_codes(garlic_panel *panel, const uint8_t *codes, int64_t
 #define GARLIC_TGLS_DICTIONARY 1
 #define GARLIC_TGLS_CONTINUOUS 2
 int garlic_panel_tgls_mode(garlic_panel *panel, int32_t *mode, int32_t *terms_by);
+
+/* Unweighted scores from dictionary-coded likelihoods run in two passes: the codes are expanded once into the TGLS term
+ * matrix (8 bytes per genotype, 64-individual blocks of rows x 64 doubles, rows = 32 + nloci + 4160), which the chain then
+ * streams.  By default the panel keeps the whole matrix, and when the device cannot hold it the chain looks every term up
+ * itself (several times slower; feed, coverage and segment calls then also lose their fused forms and need a full-size
+ * score scratch).  This sets an upper bound in bytes for the term buffers instead:
+ *   0 (default): the whole matrix, or none and the look-up chain.
+ *   > 0: the term buffers of this panel never hold more than `bytes`; when the whole matrix is larger, every unweighted
+ *        use_gl call (garlic_lod_windows / _multi, garlic_lod_feed / _subset, garlic_roh_coverage_fused, garlic_roh_segments)
+ *        builds and consumes it slab by slab (a slab = consecutive 64-individual blocks; the terms of one slab are built
+ *        while the chain reads the other, so two buffers: slab_blocks is the largest s for which s + min(s, nblk - s)
+ *        blocks fit in `bytes`, nblk = ceil(nind / 64) -- the first buffer holds a full slab, the second what the
+ *        second slab holds).  Same kernels and forms, same doubles.  A slab begins at the next block the call scores,
+ *        so n_slabs = ceil(blocks / slab_blocks) for a range of individuals; a subset feed's skipped blocks are not
+ *        scored, a slab of nothing else is not built.
+ *  -1: the whole matrix when the default's test lets it in, otherwise slabs in half of the memory free at the call.
+ * GARLIC_ERR_INVALID when `bytes` > 0 cannot hold the buffers of one-block slabs (2 x rows x 512 bytes; a panel of at
+ * most 64 individuals has one slab and one buffer).
+ * Slabs are rebuilt by every call, so a sweep over several window sizes pays the term pass per size where the whole matrix
+ * is built once and reused: a caller with room for it keeps budget 0.  May be changed between calls in both directions;
+ * what the new bound does not allow is freed at once.  Panels that hold continuous likelihoods keep 8 bytes per genotype
+ * as their data and ignore the budget.  Weighted scores with likelihoods (garlic_wlod_windows and the weighted feed /
+ * coverage / segment calls) are not covered: their kernels pair blocks over a scaled matrix of their own, built whole as
+ * before and outside this bound (the next unweighted call under a budget it exceeds frees it). */
+int garlic_panel_set_tgls_term_budget(garlic_panel *panel, int64_t bytes);
+/* whole_bytes: what the full matrix needs (rows x 8 x the panel's padded individual count, (nind + 126) / 64 * 64); resident_bytes: term buffers held now;
+ * slab_blocks / n_slabs: of the last unweighted use_gl call (n_slabs 0: it read a whole matrix or looked terms up).
+ * Any pointer may be NULL. */
+int garlic_panel_tgls_terms_info(garlic_panel *panel, int64_t *whole_bytes, int64_t *resident_bytes,
+                                 int32_t *slab_blocks, int32_t *n_slabs);
 
 /* HapData::firstCopy (src/garlic-data.h:36; filled by readTPED under --phased,
  * src/garlic-data.cpp:106,129: "the first allele of the pair is the counted allele"), one byte per

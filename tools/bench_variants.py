@@ -9,6 +9,10 @@ with dictionary likelihoods, for every size of --winsizes on one resident panel;
 checkout (the A/B against the parent commit: profiles/wlod_feed_ab.txt).  --modes tgls_feed: the same leg for the
 unweighted feed with per-genotype likelihoods (use_gl, not weighted; --gl-kind codes or continuous; no LD weights), with the
 kernel's fraction of the HBM roofline at the bytes per window of the form the call took (profiles/tgls_feed_ab.txt).
+--modes tgls_slabs: garlic_lod_windows (device output) and garlic_roh_segments with dictionary likelihoods under
+GARLIC_GL_NO_TERMS=1 (the look-up chain), over the whole term matrix (first call and warm calls), and -- a library that has
+garlic_panel_set_tgls_term_budget -- under every budget of --term-budgets-gb, with the device memory in use around the
+calls (profiles/tgls_slabs_ab.txt; --tree for the parent commit).
 """
 import argparse
 import json
@@ -100,6 +104,78 @@ def wlod_feed_leg(args, tgls=False):
                 print(json.dumps(line), flush=True)
 
 
+def tgls_slabs_leg(args):
+    """Host clock around the synchronous calls (the term pass, where there is one, is part of the call).  One panel; legs in
+    this order so that the code table (host work of the first use_gl call) is built before anything is timed as a first
+    call: look-up chain, whole matrix, then the budgets."""
+    import time
+    import torch
+    from garlic_amd import abi, synth
+
+    torch.cuda.set_device(0)
+    dev = torch.device("cuda", 0)
+    nloci, nind, W = args.snps, args.inds, args.winsize
+    error, max_gap = 0.001, 200000
+    spec = synth.PanelSpec(nloci, seed=20260105, max_gap=max_gap)
+    ctx = abi.Context(0)
+    panel = abi.Panel(ctx, spec.chr_nloci, nind)
+    panel.set_map(spec.pos, spec.centro_start, spec.centro_end, gpos=spec.gpos)
+    panel.set_freq(spec.freq)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(7)
+    for l0, g in synth.genotype_chunks(spec, nind, dev):
+        gq = torch.randint(3, 61, g.shape, generator=gen, device=dev).to(torch.float64)
+        gl = torch.pow(torch.tensor(10.0, dtype=torch.float64, device=dev), -gq / 10.0)
+        torch.cuda.synchronize()
+        panel.set_genotypes_device(g.data_ptr(), g.shape[1], l0, g.shape[0])
+        panel.set_gl_device(gl.data_ptr(), gl.shape[1], l0, gl.shape[0])
+        del gq, gl
+    del g
+    total = panel.out_layout(32, nind)[2]
+    out = torch.empty(total, dtype=torch.float64, device=dev)
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+
+    def used():
+        free_b, total_b = torch.cuda.mem_get_info()
+        return int(total_b - free_b)
+
+    def leg(name, budget_gb=None):
+        line = {"mode": "tgls_slabs", "leg": name, "snps": nloci, "inds": nind, "winsize": W, "repeats": args.steps,
+                "device_memory_before_bytes": used()}
+        for what, call in (("windows", lambda: panel.lod_windows_device(out.data_ptr(), W, error, max_gap, use_gl=True)),
+                           ("segments", lambda: panel.roh_segments(W, error, max_gap, args.cutoff, 0.25, use_gl=True))):
+            ms = []
+            for k in range(1 + args.steps):
+                t0 = time.perf_counter()
+                r = call()
+                ms.append((time.perf_counter() - t0) * 1e3)
+            line[what] = {"first_call_ms": ms[0], "warm_ms_median": float(np.median(ms[1:])), "warm_ms_min": min(ms[1:]),
+                          "warm_ms_max": max(ms[1:])}
+            if what == "segments":
+                line[what]["n_segments"] = len(r)
+            if hasattr(panel, "tgls_terms_info"):
+                line[what].update(panel.tgls_terms_info())
+            line[what]["device_memory_after_bytes"] = used()
+        line["scores_checksum"] = float(out[: min(total, 1 << 24)].nan_to_num(0.0, 0.0, 0.0).sum().item())
+        if budget_gb is not None:
+            line["term_budget_gb"] = budget_gb
+        print(json.dumps(line), flush=True)
+
+    os.environ["GARLIC_GL_NO_TERMS"] = "1"
+    leg("lookup chain (GARLIC_GL_NO_TERMS=1)")
+    del os.environ["GARLIC_GL_NO_TERMS"]
+    leg("whole matrix")
+    if hasattr(panel, "set_tgls_term_budget"):
+        for gb in [float(x) for x in args.term_budgets_gb.split(",") if x]:
+            try:
+                panel.set_tgls_term_budget(int(gb * 1e9))
+            except abi.GarlicError as e:
+                print(json.dumps({"mode": "tgls_slabs", "leg": "budget", "term_budget_gb": gb, "refused": str(e)}), flush=True)
+                continue
+            leg("budget", gb)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--snps", type=int, default=200000)
@@ -110,10 +186,14 @@ def main():
     ap.add_argument("--winsizes", default="100,10", help="wlod_feed / tgls_feed: window sizes, one resident panel")
     ap.add_argument("--feed-steps", default="", help="wlod_feed / tgls_feed: thinning steps (default: the window size)")
     ap.add_argument("--gl-kind", default="codes", choices=["codes", "continuous"], help="tgls_feed: the likelihoods' form")
+    ap.add_argument("--term-budgets-gb", default="8,12,32", help="tgls_slabs: garlic_panel_set_tgls_term_budget values to time")
+    ap.add_argument("--cutoff", type=float, default=2.5, help="tgls_slabs: the LOD cutoff of the segments call")
     ap.add_argument("--tree", default="", help="take garlic_amd from this checkout instead of the one the tool is in")
     args = ap.parse_args()
     if args.tree:
         sys.path.insert(0, os.path.abspath(args.tree))
+    if args.modes == "tgls_slabs":
+        return tgls_slabs_leg(args)
     if args.modes in ("wlod_feed", "tgls_feed"):
         return wlod_feed_leg(args, tgls=args.modes == "tgls_feed")
 
