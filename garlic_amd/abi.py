@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libgarlic_hip.so")
 OK, ERR_INVALID, ERR_HIP, ERR_STATE, ERR_NOMEM = 0, 1, 2, 3, 4
 HOST, DEVICE = 0, 1
 FEED_FROM_SCORES, FEED_CHAIN, FEED_SAMPLED_WLOD, FEED_TGLS_CHAIN = 0, 1, 2, 3   # garlic_lod_feed_info
+FEED_TGLS_CHAIN_SHARED = 4   # garlic_lod_feed_multi_info: the size shared its chain launch with another size
 MISSING = -9999.0
 
 # every symbol include/garlic_hip.h declares (tests check the library exports them all)
@@ -34,6 +35,7 @@ SYMBOLS = [
     "garlic_panel_alloc_scores", "garlic_device_trim", "garlic_roh_coverage_fused", "garlic_roh_segments",
     "garlic_panel_alloc_scores_info", "garlic_lod_feed_info",
     "garlic_panel_set_tgls_term_budget", "garlic_panel_tgls_terms_info",
+    "garlic_lod_feed_multi_tgls", "garlic_lod_feed_multi_info",
 ]
 
 
@@ -119,6 +121,9 @@ def lib():
                                          C.c_double, C.c_int32, _i32p, C.c_int32, _vp, C.c_int64, _i64p, _i64p]
     L.garlic_lod_feed_multi.argtypes = [_vp, _i32p, _i32p, C.c_int32, C.c_double, C.c_int32, _i32p, C.c_int32,
                                         C.POINTER(C.c_void_p), _i64p, _i64p, _i64p]
+    L.garlic_lod_feed_multi_tgls.argtypes = [_vp, _i32p, _i32p, C.c_int32, C.c_int32, _i32p, C.c_int32,
+                                             C.POINTER(C.c_void_p), _i64p, _i64p, _i64p]
+    L.garlic_lod_feed_multi_info.argtypes = [_vp, C.c_int32, _i32p, _i32p, _i32p, _i32p]
     L.garlic_panel_tgls_mode.argtypes = [_vp, _i32p, _i32p]
     L.garlic_panel_chain_kind.argtypes = [_vp, _i32p]
     L.garlic_lod_feed_info.argtypes = [_vp, _i32p, _i64p]
@@ -491,6 +496,40 @@ class Panel:
                                           _ptr(idx, _i32p), 0 if idx is None else n_rows, ptrs, _ptr(caps, _i64p),
                                           _ptr(counts, _i64p), _ptr(per_chr, _i64p)))
         return [b[: int(n)] for b, n in zip(bufs, counts)], per_chr
+
+    def lod_feed_multi_tgls(self, winsizes, max_gap, steps=None, ind_idx=None, copy=True):
+        """garlic_lod_feed_multi_tgls: lod_feed_multi for per-genotype likelihoods (use_gl, unweighted); the sizes that
+        take the thinned ring chain share one pass over the term matrix in groups (garlic_hip.h).  Returns and copy as there."""
+        sizes = np.ascontiguousarray(winsizes, dtype=np.int32)
+        st = sizes.copy() if steps is None else np.ascontiguousarray(steps, dtype=np.int32)
+        idx = None if ind_idx is None else np.ascontiguousarray(ind_idx, dtype=np.int32)
+        n_rows = self.nind if idx is None else int(idx.shape[0])
+        caps = np.array([max(1, int(sum((int(n) + int(s) - 1) // int(s) for n in self.chr_nloci)) * n_rows) for s in st],
+                        dtype=np.int64)
+        if copy:
+            bufs = [np.empty(int(c), dtype=np.float64) for c in caps]
+        else:
+            old = getattr(self, "_feed_multi", [])
+            bufs = [old[i] if i < len(old) and old[i].shape[0] >= int(c) else np.empty(int(c), dtype=np.float64)
+                    for i, c in enumerate(caps)]
+            self._feed_multi = bufs
+        ptrs = (C.c_void_p * len(bufs))(*[b.ctypes.data for b in bufs])
+        counts = np.zeros(len(bufs), dtype=np.int64)
+        per_chr = np.zeros((len(bufs), self.nchr), dtype=np.int64)
+        check(lib().garlic_lod_feed_multi_tgls(self.handle, _ptr(sizes, _i32p), _ptr(st, _i32p), len(bufs), max_gap,
+                                               _ptr(idx, _i32p), 0 if idx is None else n_rows, ptrs, _ptr(caps, _i64p),
+                                               _ptr(counts, _i64p), _ptr(per_chr, _i64p)))
+        return [b[: int(n)] for b, n in zip(bufs, counts)], per_chr
+
+    def feed_multi_info(self, n):
+        """garlic_lod_feed_multi_info for the first n sizes of the last lod_feed_multi_tgls call: {"forms": [..], "groups": [..],
+        "n_chain_launches": int, "n_term_builds": int}"""
+        forms, groups = np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1), dtype=np.int32)
+        launches, builds = C.c_int32(), C.c_int32()
+        check(lib().garlic_lod_feed_multi_info(self.handle, n, _ptr(forms, _i32p), _ptr(groups, _i32p), C.byref(launches),
+                                               C.byref(builds)))
+        return {"forms": [int(x) for x in forms[:n]], "groups": [int(x) for x in groups[:n]],
+                "n_chain_launches": launches.value, "n_term_builds": builds.value}
 
     def alloc_scores(self, winsize, error, max_gap, pitch_align=32, nind_out=None, candidates=0):
         """garlic_panel_alloc_scores: score memory in the chain kernel's fast placement (the real kernel timed into

@@ -11,6 +11,7 @@
 #include "ld_kernels.hpp"
 #include "tgls_ring_kernel.hpp"
 #include "tgls_feed_kernel.hpp"
+#include "tgls_feed_multi_kernel.hpp"
 #include "wlod_strip_kernel.hpp"
 #include "wlod_small_kernel.hpp"
 #include "coverage_kernel.hpp"
@@ -341,6 +342,13 @@ struct garlic_panel {
         DevBuf<double> out, feed;
     };
     std::vector<FeedSlot *> feed_slots;
+    // garlic_lod_feed_multi_tgls: work lists of all groups, the sizes' ChrDev tables (by size; by group and place in it), one
+    // queue-head pair per chain launch; what garlic_lod_feed_multi_info reports
+    DevBuf<ChainItem> d_multi_items;
+    DevBuf<ChrDev> d_multi_chrs, d_multi_gchrs;
+    DevBuf<int32_t> d_multi_queues;
+    std::vector<int32_t> multi_forms, multi_groups;
+    int32_t multi_chain_launches = 0, multi_term_builds = 0;
     garlic_call_stats stats{};
     bool stats_pending = false;                    // event times of the last call not read yet
     int stats_slot = 0;                            // the context's event pair that brackets its dominant kernel
@@ -1715,14 +1723,19 @@ int launch_chain(garlic_panel *p, const LodCall &c, const LodForm &form, Plan &p
 // context's stream.  Events alone order them -- a chain waits for its slab's terms, a buffer is rebuilt once the chain
 // that read it (two slabs back) has finished -- so the terms of slab k + 1 are built while the chain of slab k runs and
 // every kernel can finish on its own.  Same kernels, same doubles as over the whole matrix.
-int launch_tgls_slabs(garlic_panel *p, const LodCall &c, const LodForm &form, const Plan &plan, double *d_out)
+//
+// `chains(k, terms)` enqueues on the context's stream every chain that reads slab k (one per call of the single-size paths; one
+// per group of window sizes for garlic_lod_feed_multi_tgls: a slab is built once and every group runs over it before its
+// buffer is reused).
+template <class Chains>
+int for_each_tgls_slab(garlic_panel *p, const std::vector<Plan::Slab> &slabs, int32_t slab_blocks, Chains chains)
 {
     garlic_ctx *ctx = p->ctx;
     hipStream_t s = ctx->stream;
     const int64_t rows = GOFF + p->nloci + GPAD_BACK;
-    const size_t n_slabs = plan.slabs.size();
+    const size_t n_slabs = slabs.size();
     int rc;
-    p->last_slab_blocks = form.slab_blocks;
+    p->last_slab_blocks = slab_blocks;
     p->last_n_slabs = (int32_t)n_slabs;
     if (!n_slabs) return GARLIC_OK;
     if (!p->slab_stream) {
@@ -1733,7 +1746,7 @@ int launch_tgls_slabs(garlic_panel *p, const LodCall &c, const LodForm &form, co
     // buffer q serves the slabs q, q + 2, ..: room for the largest of them (a change of plan that needs more waits for the stream first)
     for (int q = 0; q < 2; q++) {
         size_t blocks = 0;
-        for (size_t k = (size_t)q; k < n_slabs; k += 2) blocks = std::max(blocks, (size_t)(plan.slabs[k].b1 - plan.slabs[k].b0));
+        for (size_t k = (size_t)q; k < n_slabs; k += 2) blocks = std::max(blocks, (size_t)(slabs[k].b1 - slabs[k].b0));
         const size_t need = blocks * (size_t)rows * WAVE;
         if (need > p->d_slab[q].cap || (!need && p->d_slab[q].cap)) {
             HIP_TRY(hipStreamSynchronize(s));
@@ -1741,8 +1754,6 @@ int launch_tgls_slabs(garlic_panel *p, const LodCall &c, const LodForm &form, co
             if (need && (rc = p->d_slab[q].reserve(need))) return rc;
         }
     }
-    if ((rc = p->d_slab_queues.reserve(2 * n_slabs))) return rc;
-    HIP_TRY(hipMemsetAsync(p->d_slab_queues.p, 0, 2 * n_slabs * sizeof(int32_t), s));
     // what the term pass reads (tables, codes, genotypes) was put on the context's stream
     HIP_TRY(hipEventRecord(p->ev_slab_begin, s));
     HIP_TRY(hipStreamWaitEvent(p->slab_stream, p->ev_slab_begin, 0));
@@ -1752,9 +1763,8 @@ int launch_tgls_slabs(garlic_panel *p, const LodCall &c, const LodForm &form, co
     if (terms_lds > 48 * 1024)
         HIP_TRY(hipFuncSetAttribute((const void *)gl_terms_slab_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)terms_lds));
     const unsigned terms_grid = (unsigned)((p->nloci + GL_TERMS_S - 1) / GL_TERMS_S + (GL_PAD_ROWS + GL_TERMS_S - 1) / GL_TERMS_S);
-    if (form.cov_bits) p->cov_written = true;
     for (size_t k = 0; k < n_slabs; k++) {
-        const Plan::Slab &sl = plan.slabs[k];
+        const Plan::Slab &sl = slabs[k];
         const int q = (int)(k & 1);
         if (k >= 2) HIP_TRY(hipStreamWaitEvent(p->slab_stream, p->ev_slab_read[q], 0));
         hipLaunchKernelGGL(gl_terms_slab_kernel, dim3(terms_grid), dim3(256), terms_lds, p->slab_stream, a, p->nloci, rows, sl.b0, sl.b1,
@@ -1762,22 +1772,46 @@ int launch_tgls_slabs(garlic_panel *p, const LodCall &c, const LodForm &form, co
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(p->ev_slab_built[q], p->slab_stream));
         HIP_TRY(hipStreamWaitEvent(s, p->ev_slab_built[q], 0));
-        int workers = ctx->n_cu;
-        if (const char *e = getenv("GARLIC_WORKERS")) workers = std::max(1, atoi(e));
-        workers = std::min<int>(workers, (int)sl.n_items);
-        if (form.family == Family::tgls_feed) {
-            TglsFeedArgs t{p->d_slab[q].p, rows, p->d_items.p + sl.item0, p->d_chrs.p, d_out,
-                           c.ind_begin, c.ind_count, c.W, (int32_t)sl.n_items, c.thin_step, sl.b0, p->d_slab_queues.p + 2 * k};
-            hipLaunchKernelGGL(tgls_feed_kernel, dim3((unsigned)workers), dim3(TGF_THREADS), 0, s, t);
-        } else {
-            TglsArgs t{p->d_slab[q].p, rows, p->d_items.p + sl.item0, p->d_chrs.p, d_out,
-                       c.ind_begin, c.ind_count, c.W, (int32_t)sl.n_items, sl.b0, p->d_slab_queues.p + 2 * k, p->cov_pending};
-            hipLaunchKernelGGL(lod_chain_ring_kernel, dim3((unsigned)workers), dim3(TG_THREADS), 0, s, t);
-        }
+        if ((rc = chains(k, (const double *)p->d_slab[q].p))) return rc;
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(p->ev_slab_read[q], s));
     }
     return GARLIC_OK;
+}
+
+// persistent workgroups of a ring chain: one per CU (GARLIC_WORKERS: another count), no more than there are items
+int tgls_workers(const garlic_ctx *ctx, size_t n_items)
+{
+    int workers = ctx->n_cu;
+    if (const char *e = getenv("GARLIC_WORKERS")) workers = std::max(1, atoi(e));
+    return std::min<int>(workers, (int)n_items);
+}
+
+int launch_tgls_slabs(garlic_panel *p, const LodCall &c, const LodForm &form, const Plan &plan, double *d_out)
+{
+    hipStream_t s = p->ctx->stream;
+    const int64_t rows = GOFF + p->nloci + GPAD_BACK;
+    const size_t n_slabs = plan.slabs.size();
+    int rc;
+    if (n_slabs) {
+        if ((rc = p->d_slab_queues.reserve(2 * n_slabs))) return rc;
+        HIP_TRY(hipMemsetAsync(p->d_slab_queues.p, 0, 2 * n_slabs * sizeof(int32_t), s));
+        if (form.cov_bits) p->cov_written = true;
+    }
+    return for_each_tgls_slab(p, plan.slabs, form.slab_blocks, [&](size_t k, const double *terms) {
+        const Plan::Slab &sl = plan.slabs[k];
+        const int workers = tgls_workers(p->ctx, sl.n_items);
+        if (form.family == Family::tgls_feed) {
+            TglsFeedArgs t{terms, rows, p->d_items.p + sl.item0, p->d_chrs.p, d_out,
+                           c.ind_begin, c.ind_count, c.W, (int32_t)sl.n_items, c.thin_step, sl.b0, p->d_slab_queues.p + 2 * k};
+            hipLaunchKernelGGL(tgls_feed_kernel, dim3((unsigned)workers), dim3(TGF_THREADS), 0, s, t);
+        } else {
+            TglsArgs t{terms, rows, p->d_items.p + sl.item0, p->d_chrs.p, d_out,
+                       c.ind_begin, c.ind_count, c.W, (int32_t)sl.n_items, sl.b0, p->d_slab_queues.p + 2 * k, p->cov_pending};
+            hipLaunchKernelGGL(lod_chain_ring_kernel, dim3((unsigned)workers), dim3(TG_THREADS), 0, s, t);
+        }
+        return (int)GARLIC_OK;
+    });
 }
 
 int launch_tgls(garlic_panel *p, const LodCall &c, const LodForm &form, const Plan &plan, int workers, double *d_out)
@@ -3201,6 +3235,25 @@ int garlic_lod_feed(garlic_panel *p, int32_t winsize, double error, int32_t max_
                                   feed_capacity, count, chr_counts);
 }
 
+// one FeedSlot (stream, events, scratch) per window size of a multi-size feed call, kept with the panel
+static int ensure_feed_slots(garlic_panel *p, int32_t n_sizes)
+{
+    while ((int)p->feed_slots.size() < n_sizes) {
+        auto *sl = new garlic_panel::FeedSlot;            // (joins the panel's slots only once it is complete)
+        bool ok = hipStreamCreateWithFlags(&sl->stream, hipStreamNonBlocking) == hipSuccess;
+        const bool ok0 = ok && hipEventCreate(&sl->ev0) == hipSuccess;
+        const bool ok1 = ok0 && hipEventCreate(&sl->ev1) == hipSuccess;
+        if (!ok1) {
+            if (ok0) (void)hipEventDestroy(sl->ev0);
+            if (ok) (void)hipStreamDestroy(sl->stream);
+            delete sl;
+            return fail(GARLIC_ERR_HIP, "feed: stream / event creation failed");
+        }
+        p->feed_slots.push_back(sl);
+    }
+    return GARLIC_OK;
+}
+
 // The KDE feeds of several window sizes in one call (exploreWinsizes / selectWinsizeFromList run the same panel
 // through every size of --winsize-multi, src/garlic-roh.cpp:726-751, 881-920).
 //
@@ -3280,19 +3333,7 @@ int garlic_lod_feed_multi(garlic_panel *p, const int32_t *winsizes, const int32_
         hipError_t e = hipMemcpy(d_rowmap.p, row_map.data(), sizeof(int32_t) * (size_t)p->nind, hipMemcpyHostToDevice);
         if (e != hipSuccess) return done(fail(GARLIC_ERR_HIP, "feed: %s", hipGetErrorString(e)));
     }
-    while ((int)p->feed_slots.size() < n_sizes) {
-        auto *sl = new garlic_panel::FeedSlot;            // (joins the panel's slots only once it is complete)
-        bool ok = hipStreamCreateWithFlags(&sl->stream, hipStreamNonBlocking) == hipSuccess;
-        const bool ok0 = ok && hipEventCreate(&sl->ev0) == hipSuccess;
-        const bool ok1 = ok0 && hipEventCreate(&sl->ev1) == hipSuccess;
-        if (!ok1) {
-            if (ok0) (void)hipEventDestroy(sl->ev0);
-            if (ok) (void)hipStreamDestroy(sl->stream);
-            delete sl;
-            return done(fail(GARLIC_ERR_HIP, "feed: stream / event creation failed"));
-        }
-        p->feed_slots.push_back(sl);
-    }
+    if ((rc = ensure_feed_slots(p, n_sizes))) return done(rc);
     FEED_TRY(hipStreamSynchronize(ctx->stream));          // uploads and earlier calls on the context's stream
     // ---- plans and their uploads, all sizes, before any kernel is enqueued (an upload from pageable memory waits
     //      for the device to take it: behind a running chain kernel it would hold back the sizes that follow)
@@ -3373,6 +3414,320 @@ int garlic_lod_feed_multi(garlic_panel *p, const int32_t *winsizes, const int32_
     p->stats_pending = false;
     return done(GARLIC_OK);
 #undef FEED_TRY
+}
+
+// Which sizes of a garlic_lod_feed_multi_tgls call share a chain launch (include/garlic_hip.h states the rule): `shared[i]`
+// says whether size i can take the thinned ring form at all.  Returns the number of groups.
+static int32_t tgls_multi_groups(const int32_t *winsizes, int32_t n, const std::vector<uint8_t> &ring_ok, bool solo,
+                                 std::vector<int32_t> &group)
+{
+    std::vector<int32_t> order((size_t)n);
+    for (int i = 0; i < n; i++) order[(size_t)i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return winsizes[x] < winsizes[y]; });
+    group.assign((size_t)n, -1);
+    int32_t n_groups = 0, in_group = 0;
+    for (int i : order)       // ascending: the sizes one ring serves, cut every TGM_MAX_SIZES
+        if (ring_ok[(size_t)i] && winsizes[i] <= TG_SINGLE_MAX_W) {
+            if (in_group == 0 || in_group == TGM_MAX_SIZES || solo) { n_groups++; in_group = 0; }
+            group[(size_t)i] = n_groups - 1;
+            in_group++;
+        }
+    for (int i : order)       // then, ascending again, every other size on its own
+        if (group[(size_t)i] < 0) group[(size_t)i] = n_groups++;
+    return n_groups;
+}
+
+// The TGLS KDE feeds of several window sizes in one call: garlic_lod_feed_multi's counterpart for per-genotype likelihoods
+// (the reference's sweeps run with USE_GL as they do with --error).  The sizes that take the thinned ring form are chained
+// group by group over one pass of the term matrix (tgls_feed_multi_kernel.hpp; a group of one: tgls_feed_kernel) -- under
+// a term budget every slab is built once for the whole call -- each size into a thinned matrix of its own, which is then
+// flattened per size on the size's own stream.  Every other size goes through feed_single, after the groups.
+int garlic_lod_feed_multi_tgls(garlic_panel *p, const int32_t *winsizes, const int32_t *steps, int32_t n_sizes, int32_t max_gap,
+                               const int32_t *ind_idx, int32_t n_idx, double *const *feeds, const int64_t *feed_capacity,
+                               int64_t *counts, int64_t *chr_counts)
+{
+    if (!p || !winsizes || !steps || !feeds || !feed_capacity || !counts)
+        return fail(GARLIC_ERR_INVALID, "panel, winsizes, steps, feeds, feed_capacity and counts are required");
+    if (n_sizes < 1) return fail(GARLIC_ERR_INVALID, "n_sizes must be >= 1");
+    if (ind_idx && n_idx < 1) return fail(GARLIC_ERR_INVALID, "an individual list needs at least one entry");
+    for (int i = 0; i < n_sizes; i++) {
+        if (winsizes[i] <= 1) return fail(GARLIC_ERR_INVALID, "SNP window size must be > 1 (got %d)", winsizes[i]);
+        if (steps[i] < 1) return fail(GARLIC_ERR_INVALID, "step must be >= 1");
+    }
+    garlic_ctx *ctx = p->ctx;
+    hipStream_t s = ctx->stream;
+    int rc;
+    if ((rc = set_device(ctx))) return rc;
+    const int nblk = (p->nind + WAVE - 1) / WAVE;
+    const int nrows = ind_idx ? n_idx : p->nind;
+    std::vector<uint8_t> blocks;
+    DevBuf<int32_t> d_list;
+    if (ind_idx) {
+        blocks.assign((size_t)nblk, 0);
+        std::vector<uint8_t> seen((size_t)p->nind, 0);
+        for (int k = 0; k < n_idx; k++) {
+            const int i = ind_idx[k];
+            if (i < 0 || i >= p->nind) return fail(GARLIC_ERR_INVALID, "feed individual %d outside panel of %d", i, p->nind);
+            if (seen[(size_t)i]) return fail(GARLIC_ERR_INVALID, "feed individual %d listed twice", i);
+            seen[(size_t)i] = 1;
+            blocks[(size_t)(i >> 6)] = 1;
+        }
+    }
+    // ---- which sizes the thinned ring chain takes (decide_form, as for a single call), and with what term matrix
+    double dummy = 0.0;
+    std::vector<uint8_t> ring_ok((size_t)n_sizes, 0);
+    int32_t slab_blocks = 0;
+    bool have_form = false;
+    for (int i = 0; i < n_sizes; i++) {
+        if (steps[i] < 4) continue;
+        const LodCall c{MODE_LOD_GL, winsizes[i], max_gap, 0, 0, p->nind, 32, steps[i], GARLIC_DEVICE, 32, 0.0, 0.0, &dummy,
+                        ind_idx ? &blocks : nullptr};
+        LodForm form;
+        if ((rc = check_lod_args(p, c))) return rc;
+        rc = decide_form(p, c, form);
+        if (rc == GARLIC_INTERNAL_NO_SAMPLED) continue;
+        if (rc) return rc;
+        if (form.family != Family::tgls_feed) continue;
+        if (!have_form) slab_blocks = form.slab_blocks;
+        have_form = true;
+        ring_ok[(size_t)i] = 1;
+    }
+    std::vector<int32_t> group;
+    const int32_t n_groups = tgls_multi_groups(winsizes, n_sizes, ring_ok, getenv("GARLIC_TGLS_FEED_MULTI_SOLO") != nullptr, group);
+    p->multi_forms.assign((size_t)n_sizes, GARLIC_FEED_FROM_SCORES);
+    p->multi_groups = group;
+    p->multi_chain_launches = p->multi_term_builds = 0;
+    // the ring groups: their sizes in ascending order
+    struct Group { std::vector<int> sizes; std::vector<size_t> item0, n_items; };     // item ranges per slab (one range: whole matrix)
+    std::vector<Group> G;
+    {
+        std::vector<int32_t> order((size_t)n_sizes);
+        for (int i = 0; i < n_sizes; i++) order[(size_t)i] = i;
+        std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return winsizes[x] < winsizes[y]; });
+        std::vector<int> slot((size_t)n_groups, -1);
+        for (int i : order) {
+            if (!ring_ok[(size_t)i]) continue;
+            int &g = slot[(size_t)group[(size_t)i]];
+            if (g < 0) { g = (int)G.size(); G.emplace_back(); }
+            G[(size_t)g].sizes.push_back(i);
+        }
+    }
+    for (const Group &g : G)
+        for (int i : g.sizes) p->multi_forms[(size_t)i] = g.sizes.size() >= 2 ? GARLIC_FEED_TGLS_CHAIN_SHARED : GARLIC_FEED_TGLS_CHAIN;
+
+    // one way out of the part that enqueues: every stream used has finished (the next call reuses the scratch)
+    auto done = [&](int code) {
+        if (code != GARLIC_OK) {
+            (void)hipStreamSynchronize(s);
+            if (p->slab_stream) (void)hipStreamSynchronize(p->slab_stream);
+            for (auto *sl : p->feed_slots) (void)hipStreamSynchronize(sl->stream);
+        }
+        d_list.release();
+        return code;
+    };
+#define FEED_TRY(expr)                                                                              \
+    do {                                                                                            \
+        hipError_t e_ = (expr);                                                                     \
+        if (e_ != hipSuccess) return done(fail(GARLIC_ERR_HIP, "feed: %s: %s", #expr, hipGetErrorString(e_))); \
+    } while (0)
+    if (!G.empty()) {
+        if ((rc = ensure_feed_slots(p, n_sizes))) return rc;
+        FEED_TRY(hipStreamSynchronize(s));          // uploads and earlier calls on the context's stream
+        if (ind_idx) {
+            if ((rc = d_list.reserve((size_t)n_idx))) return done(rc);
+            FEED_TRY(hipMemcpy(d_list.p, ind_idx, sizeof(int32_t) * (size_t)n_idx, hipMemcpyHostToDevice));
+        }
+        // ---- slabs of the call (as plan_lod cuts them: a slab begins at the next block in play), or one range of all blocks
+        std::vector<Plan::Slab> slabs;
+        const int per_list = slab_blocks ? slab_blocks : std::max(nblk, 1);
+        for (int k0 = 0; k0 < nblk;) {
+            if (ind_idx && !blocks[(size_t)k0]) { k0++; continue; }
+            const int k1 = std::min(nblk, k0 + per_list);
+            slabs.push_back(Plan::Slab{k0, k1, 0, 0});
+            k0 = k1;
+        }
+        // ---- work lists: per group the stretches that hold its smallest size, longest first, x the blocks in play of each slab
+        std::vector<ChainItem> items;
+        bool any_items = false;
+        for (Group &g : G) {
+            const int32_t Wmin = winsizes[g.sizes[0]];
+            std::vector<Run> runs;
+            std::vector<FillItem> fill;
+            int64_t n_valid = 0;
+            plan_runs(p, Wmin, runs, fill, n_valid);
+            const std::vector<int> order = longest_first(runs);
+            // (tgls_feed_kernel: b is the run's last window; tgls_feed_multi_kernel: the stretch's last SNP)
+            const int32_t b_add = g.sizes.size() >= 2 ? Wmin - 1 : 0;
+            for (const Plan::Slab &sl : slabs) {
+                g.item0.push_back(items.size());
+                for (size_t r = 0; r < order.size(); r++) {
+                    const Run &run = runs[(size_t)order[r]];
+                    for (int k = sl.b0; k < sl.b1; k++)
+                        if (!ind_idx || blocks[(size_t)k]) items.push_back(ChainItem{run.chr, run.a, run.b + b_add, k * WAVE});
+                }
+                g.n_items.push_back(items.size() - g.item0.back());
+                any_items = any_items || g.n_items.back();
+            }
+        }
+        if (!any_items) slabs.clear();      // (no stretch holds a window of any size: nothing to build or chain)
+        // ---- per size: the thinned matrix, its table, MISSING everywhere
+        std::vector<ChrDev> chrs((size_t)n_sizes * p->nchr);
+        std::vector<Layout> layouts((size_t)n_sizes);
+        for (const Group &g : G)
+            for (int i : g.sizes) {
+                Layout &L = layouts[(size_t)i] = make_layout(p, 32, p->nind, steps[i]);
+                for (int c = 0; c < p->nchr; c++) {
+                    if (3 * L.pitch[c] * 8 + 512 >= (int64_t)1 << 32)
+                        return done(fail(GARLIC_ERR_INVALID, "chromosome %d too long for 32-bit row offsets", c));
+                    const int32_t cols = (int32_t)(((int64_t)p->chr_nloci[c] + steps[i] - 1) / steps[i]);
+                    chrs[(size_t)i * p->nchr + c] = ChrDev{p->chr_off[c], L.base[c], L.pitch[c], cols, 0};
+                }
+                garlic_panel::FeedSlot &sl = *p->feed_slots[(size_t)i];
+                if ((rc = sl.out.reserve((size_t)std::max<int64_t>(L.total, 1)))) return done(rc);
+                if ((rc = sl.row_counts.reserve((size_t)p->nchr * nrows))) return done(rc);
+            }
+        const size_t n_launch = G.size() * std::max<size_t>(slabs.size(), 1);
+        if ((rc = p->d_multi_items.put(items, s)) || (rc = p->d_multi_chrs.put(chrs, s)) || (rc = p->d_multi_queues.reserve(2 * n_launch)))
+            return done(rc);
+        FEED_TRY(hipMemsetAsync(p->d_multi_queues.p, 0, 2 * n_launch * sizeof(int32_t), s));
+        for (const Group &g : G)
+            for (int i : g.sizes)
+                hipLaunchKernelGGL(fill_value_kernel, dim3(1024), dim3(256), 0, s, p->feed_slots[(size_t)i]->out.p, layouts[(size_t)i].total,
+                                   MISSING_D);
+        FEED_TRY(hipGetLastError());
+        // ---- the chains: every group over the whole matrix, or over every slab before that slab's buffer is rebuilt
+        const int64_t rows = GOFF + p->nloci + GPAD_BACK;
+        FEED_TRY(hipEventRecord(p->feed_slots[0]->ev0, s));
+        auto chains = [&](size_t k, const double *terms) -> int {
+            for (size_t gi = 0; gi < G.size(); gi++) {
+                const Group &g = G[gi];
+                const size_t n = g.n_items[k];
+                if (!n) continue;
+                const int32_t blk0 = slab_blocks ? slabs[k].b0 : 0;
+                int32_t *queue = p->d_multi_queues.p + 2 * (k * G.size() + gi);
+                const int workers = tgls_workers(ctx, n);
+                if (g.sizes.size() == 1) {
+                    const int i = g.sizes[0];
+                    TglsFeedArgs t{terms, rows, p->d_multi_items.p + g.item0[k], p->d_multi_chrs.p + (size_t)i * p->nchr,
+                                   p->feed_slots[(size_t)i]->out.p, 0, p->nind, winsizes[i], (int32_t)n, steps[i], blk0, queue};
+                    hipLaunchKernelGGL(tgls_feed_kernel, dim3((unsigned)workers), dim3(TGF_THREADS), 0, s, t);
+                } else {
+                    // (the group's tables are consecutive only when its sizes are: a table of its own, in the group's order)
+                    TglsFeedMultiArgs t{};
+                    t.terms = terms; t.term_rows = rows; t.items = p->d_multi_items.p + g.item0[k];
+                    t.chrs = p->d_multi_gchrs.p + gi * (size_t)TGM_MAX_SIZES * p->nchr;
+                    for (size_t j = 0; j < g.sizes.size(); j++) {
+                        const int i = g.sizes[j];
+                        t.out[j] = p->feed_slots[(size_t)i]->out.p;
+                        t.winsize[j] = winsizes[i];
+                        t.thin_step[j] = steps[i];
+                    }
+                    t.n_sizes = (int32_t)g.sizes.size(); t.nchr = p->nchr; t.ind_begin = 0; t.ind_count = p->nind;
+                    t.n_items = (int32_t)n; t.blk0 = blk0; t.next_item = queue;
+                    hipLaunchKernelGGL(tgls_feed_multi_kernel, dim3((unsigned)workers), dim3(TGF_THREADS), 0, s, t);
+                }
+                p->multi_chain_launches++;
+            }
+            return GARLIC_OK;
+        };
+        // the shared groups' tables, in group order
+        {
+            std::vector<ChrDev> gchrs(G.size() * (size_t)TGM_MAX_SIZES * p->nchr);
+            for (size_t gi = 0; gi < G.size(); gi++)
+                for (size_t j = 0; j < G[gi].sizes.size(); j++)
+                    for (int c = 0; c < p->nchr; c++)
+                        gchrs[(gi * TGM_MAX_SIZES + j) * p->nchr + c] = chrs[(size_t)G[gi].sizes[j] * p->nchr + c];
+            if ((rc = p->d_multi_gchrs.put(gchrs, s))) return done(rc);
+            FEED_TRY(hipStreamSynchronize(s));      // (the host lists go out of use here)
+        }
+        if (slab_blocks) {
+            if ((rc = for_each_tgls_slab(p, slabs, slab_blocks, chains))) return done(rc);
+            p->multi_term_builds = (int32_t)slabs.size();
+        } else {
+            p->last_slab_blocks = p->last_n_slabs = 0;
+            if (!slabs.empty() && (rc = chains(0, p->d_glterms.p))) return done(rc);
+        }
+        FEED_TRY(hipGetLastError());
+        FEED_TRY(hipEventRecord(p->feed_slots[0]->ev1, s));
+        // ---- per size, on its own stream: the samples of every (chromosome, listed individual) counted
+        std::vector<std::vector<int64_t>> row_counts((size_t)n_sizes);
+        const int n_flat = p->nchr * nrows;
+        for (const Group &g : G)
+            for (int i : g.sizes) {
+                garlic_panel::FeedSlot &sl = *p->feed_slots[(size_t)i];
+                FEED_TRY(hipStreamWaitEvent(sl.stream, p->feed_slots[0]->ev1, 0));
+                hipLaunchKernelGGL(feed_count_kernel, dim3((unsigned)n_flat), dim3(WAVE), 0, sl.stream, sl.out.p,
+                                   p->d_multi_chrs.p + (size_t)i * p->nchr, p->nchr, nrows, ind_idx ? d_list.p : nullptr, 1, sl.row_counts.p);
+                row_counts[(size_t)i].resize((size_t)n_flat);
+                FEED_TRY(hipMemcpyAsync(row_counts[(size_t)i].data(), sl.row_counts.p, sizeof(int64_t) * n_flat, hipMemcpyDeviceToHost, sl.stream));
+            }
+        // ---- the feeds, in order: offsets (a tiny scan on the host), the compaction, the copy out -- every size's
+        //      chain and count kernels were enqueued above, before the first feed is fetched
+        for (const Group &g : G)
+            for (int i : g.sizes) {
+                garlic_panel::FeedSlot &sl = *p->feed_slots[(size_t)i];
+                std::vector<int64_t> &rcnt = row_counts[(size_t)i];
+                FEED_TRY(hipStreamSynchronize(sl.stream));
+                int64_t total = 0;
+                if (chr_counts)
+                    for (int c = 0; c < p->nchr; c++) {
+                        int64_t &cc = chr_counts[(size_t)i * p->nchr + c] = 0;
+                        for (int r = 0; r < nrows; r++) cc += rcnt[(size_t)c * nrows + r];
+                    }
+                for (auto &c : rcnt) { const int64_t n = c; c = total; total += n; }
+                counts[i] = total;
+                if (total > feed_capacity[i] || total == 0) continue;
+                if (!feeds[i]) return done(fail(GARLIC_ERR_INVALID, "feed %d is NULL", i));
+                if ((rc = sl.feed.reserve((size_t)total))) return done(rc);
+                FEED_TRY(hipMemcpyAsync(sl.row_counts.p, rcnt.data(), sizeof(int64_t) * n_flat, hipMemcpyHostToDevice, sl.stream));
+                hipLaunchKernelGGL(feed_write_kernel, dim3((unsigned)n_flat), dim3(WAVE), 0, sl.stream, sl.out.p,
+                                   p->d_multi_chrs.p + (size_t)i * p->nchr, p->nchr, nrows, ind_idx ? d_list.p : nullptr, 1, sl.row_counts.p,
+                                   sl.feed.p);
+                FEED_TRY(hipMemcpyAsync(feeds[i], sl.feed.p, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, sl.stream));
+            }
+        for (const Group &g : G)
+            for (int i : g.sizes) FEED_TRY(hipStreamSynchronize(p->feed_slots[(size_t)i]->stream));
+        FEED_TRY(hipGetLastError());
+        float ms = 0.f;
+        p->stats = garlic_call_stats{};
+        if (hipEventElapsedTime(&ms, p->feed_slots[0]->ev0, p->feed_slots[0]->ev1) == hipSuccess) p->stats.chain_kernel_ms = ms;
+        p->stats_pending = false;
+        p->last_feed_form = p->multi_forms[(size_t)G.back().sizes.back()];      // garlic_lod_feed_info: the last size processed
+        p->last_feed_doubles = layouts[(size_t)G.back().sizes.back()].total;
+    }
+#undef FEED_TRY
+    d_list.release();
+    // ---- every other size on its own: full scores (or whatever form feed_single finds), after the groups
+    {
+        std::vector<int32_t> order((size_t)n_sizes);
+        for (int i = 0; i < n_sizes; i++) order[(size_t)i] = i;
+        std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return group[(size_t)x] < group[(size_t)y]; });
+        for (int i : order) {
+            if (ring_ok[(size_t)i]) continue;
+            if ((rc = feed_single(p, winsizes[i], 0.0, max_gap, 1, 0, 0, 0.0, steps[i], ind_idx, n_idx, feeds[i], feed_capacity[i],
+                                  &counts[i], chr_counts ? chr_counts + (size_t)i * p->nchr : nullptr)))
+                return rc;
+            p->multi_forms[(size_t)i] = p->last_feed_form;
+            p->multi_chain_launches++;
+            p->multi_term_builds += p->last_n_slabs;
+        }
+    }
+    return GARLIC_OK;
+}
+
+int garlic_lod_feed_multi_info(garlic_panel *p, int32_t n, int32_t *forms, int32_t *groups, int32_t *n_chain_launches,
+                               int32_t *n_term_builds)
+{
+    if (!p) return fail(GARLIC_ERR_INVALID, "panel is required");
+    if (n < 0 || (size_t)n > p->multi_forms.size())
+        return fail(GARLIC_ERR_INVALID, "the last garlic_lod_feed_multi_tgls call had %d sizes (asked for %d)", (int)p->multi_forms.size(), n);
+    for (int i = 0; i < n; i++) {
+        if (forms) forms[i] = p->multi_forms[(size_t)i];
+        if (groups) groups[i] = p->multi_groups[(size_t)i];
+    }
+    if (n_chain_launches) *n_chain_launches = p->multi_chain_launches;
+    if (n_term_builds) *n_term_builds = p->multi_term_builds;
+    return GARLIC_OK;
 }
 
 // Coverage counts of the unweighted --error scores without the scores: chain + compare + sliding count in one kernel

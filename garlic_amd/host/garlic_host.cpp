@@ -1286,8 +1286,9 @@ std::vector<ROHData *> *LodEngine::assembleROHWindows(IndData *indData, double l
 }
 
 // The callers that sweep window sizes on one data set -- exploreWinsizes (garlic-roh.cpp:726-751), selectWinsize
-// (:798-837), selectWinsizeFromList (:881-920) -- through garlic_lod_feed_multi: unweighted --error scores, the thinning
-// step of a size is the size itself (convertWinData2DoubleData(.., winsize), :735,743,817,900) unless `steps` says otherwise.
+// (:798-837), selectWinsizeFromList (:881-920) -- through garlic_lod_feed_multi (unweighted --error scores) or, when the
+// engine holds per-genotype likelihoods (USE_GL; the sweeps run with --tgls as with --error), garlic_lod_feed_multi_tgls.  The
+// thinning step of a size is the size itself (convertWinData2DoubleData(.., winsize), :735,743,817,900) unless `steps` says otherwise.
 std::vector<DoubleData *> LodEngine::lodFeedMulti(const std::vector<int> &winsizes, double error, int MAX_GAP,
                                                   const std::vector<int> *steps, const std::vector<int> *kdeSubsample)
 {
@@ -1326,15 +1327,19 @@ std::vector<DoubleData *> LodEngine::lodFeedMulti(const std::vector<int> &winsiz
                 feeds[k][i].resize((size_t)std::max<int64_t>(cap[i], 1));
                 ptrs[i] = feeds[k][i].data();
             }
-            if (garlic_lod_feed_multi(s.panel, W32.data(), S32.data(), (int32_t)nw, error, MAX_GAP, subset ? mine.data() : nullptr,
-                                      (int32_t)mine.size(), ptrs.data(), cap.data(), n.data(), per_chr[k].data()) != GARLIC_OK)
+            const int rc = impl->use_gl
+                               ? garlic_lod_feed_multi_tgls(s.panel, W32.data(), S32.data(), (int32_t)nw, MAX_GAP, subset ? mine.data() : nullptr,
+                                                            (int32_t)mine.size(), ptrs.data(), cap.data(), n.data(), per_chr[k].data())
+                               : garlic_lod_feed_multi(s.panel, W32.data(), S32.data(), (int32_t)nw, error, MAX_GAP, subset ? mine.data() : nullptr,
+                                                       (int32_t)mine.size(), ptrs.data(), cap.data(), n.data(), per_chr[k].data());
+            if (rc != GARLIC_OK)
                 errors[k] = garlic_hip_last_error();
             else
                 for (size_t i = 0; i < nw; i++) feeds[k][i].resize((size_t)n[i]);
         });
     for (auto &t : th) t.join();
     for (auto &e : errors)
-        if (!e.empty()) fail("garlic_lod_feed_multi: " + e);
+        if (!e.empty()) fail(std::string(impl->use_gl ? "garlic_lod_feed_multi_tgls: " : "garlic_lod_feed_multi: ") + e);
     // merge per size in the reference's order: chromosome -> individual (= shard order) -> locus
     std::vector<DoubleData *> out(nw, nullptr);
     for (size_t i = 0; i < nw; i++) {

@@ -228,8 +228,9 @@ int main(int argc, char **argv)
             for (int i : kdesub) std::cerr << " " << ind->indID[i];
             std::cerr << "\n";
         }
-        if (!a.raw_lod && !a.weighted && !USE_GL && sizes.size() > 1) {
-            // --winsize-multi, feeds only, unweighted: all sizes in one call (their kernels and downloads overlap)
+        if (!a.raw_lod && !a.weighted && sizes.size() > 1) {
+            // --winsize-multi, feeds only, unweighted: all sizes in one call (their kernels and downloads overlap; with --tgls
+            // the sizes share passes over the term matrix: garlic_lod_feed_multi_tgls)
             std::vector<int> steps;
             for (int W : sizes) steps.push_back(a.kde_thinning ? W : 1);
             std::vector<DoubleData *> feeds = engine.lodFeedMulti(sizes, a.error, a.max_gap, &steps, &kdesub);

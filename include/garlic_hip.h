@@ -47,7 +47,8 @@ extern "C" {
  * 7: garlic_roh_segments (the ROH segments of assembleROHWindows without scores or counts)
  * 8: garlic_call_stats::n_stall_reruns / n_count_timeouts, garlic_panel_alloc_scores_info; garlic_lod_feed_info (added
  *    under the same number: nothing that existed changed); GARLIC_FEED_TGLS_CHAIN (a fourth value of its form, likewise);
- *    garlic_panel_set_tgls_term_budget, garlic_panel_tgls_terms_info (likewise) */
+ *    garlic_panel_set_tgls_term_budget, garlic_panel_tgls_terms_info (likewise); garlic_lod_feed_multi_tgls,
+ *    garlic_lod_feed_multi_info, GARLIC_FEED_TGLS_CHAIN_SHARED (likewise) */
 #define GARLIC_HIP_ABI_VERSION 8
 
 #define GARLIC_OK 0
@@ -336,6 +337,41 @@ int garlic_lod_feed_info(garlic_panel *panel, int32_t *form, int64_t *score_doub
 int garlic_lod_feed_multi(garlic_panel *panel, const int32_t *winsizes, const int32_t *steps, int32_t n_sizes, double error,
                           int32_t max_gap, const int32_t *ind_idx, int32_t n_idx, double *const *feeds,
                           const int64_t *feed_capacity, int64_t *counts, int64_t *chr_counts);
+
+/* garlic_lod_feed_multi for per-genotype likelihoods: the sweeps above run with USE_GL (--tgls) exactly as with --error.
+ * The results are those of n_sizes garlic_lod_feed_subset(use_gl = 1, weighted = 0) calls -- values, counts,
+ * per-chromosome counts and order (chromosome -> ind_idx order -> locus) identical; duplicate sizes with different
+ * steps are allowed.  One pass over the term matrix serves several sizes (csrc/tgls_feed_multi_kernel.hpp):
+ *
+ * Grouping rule.  A size "takes the ring" when a single call would answer GARLIC_FEED_TGLS_CHAIN for it: step >= 4, no
+ * window sum of exactly -9999.0 possible, a term matrix (whole, or slabs under garlic_panel_set_tgls_term_budget) that
+ * was neither declined nor looked up, neither GARLIC_TGLS_NO_RING nor GARLIC_TGLS_FEED_FULL set.  The sizes that take
+ * the ring and are <= 144 (the one-stream ring's widest window) are sorted ascending (ties: call order) and cut greedily
+ * into groups of at most 4 (TGM_MAX_SIZES): group 0 holds the 4 smallest, group 1 the next 4, ..  Every other size is a
+ * group of one, numbered after those in ascending order again: a size above 144 that takes the ring runs through the
+ * single-size ring chain in the same call (and over the same slabs), a size that does not take the ring goes through
+ * the single-size path (full scores, then garlic_lod_flatten's passes) after the groups.  GARLIC_TGLS_FEED_MULTI_SOLO=1:
+ * groups of one throughout.
+ *
+ * Whole term matrix: one chain launch per group.  Under a term budget every slab is built ONCE per call and every group
+ * chains over it before its buffer is rebuilt (a single call per size builds every slab per size);
+ * garlic_panel_tgls_terms_info reports the call's slab_blocks and n_slabs as for a single call.  Each size has a thinned
+ * matrix, a stream and a feed buffer of its own; every size's kernels are enqueued before the first feed is fetched.
+ * Arguments as in garlic_lod_feed_multi. */
+int garlic_lod_feed_multi_tgls(garlic_panel *panel, const int32_t *winsizes, const int32_t *steps, int32_t n_sizes,
+                               int32_t max_gap, const int32_t *ind_idx, int32_t n_idx, double *const *feeds,
+                               const int64_t *feed_capacity, int64_t *counts, int64_t *chr_counts);
+
+/* What the last garlic_lod_feed_multi_tgls call on this panel did, for its first n sizes (n <= that call's n_sizes;
+ * every pointer may be NULL).  forms[i]: GARLIC_FEED_TGLS_CHAIN_SHARED when size i's group held at least two sizes,
+ * GARLIC_FEED_TGLS_CHAIN for a ring chain of its own, else what the single-size path reported (GARLIC_FEED_FROM_SCORES).
+ * groups[i]: size i's group index under the rule above.  *n_chain_launches: chain kernels enqueued (groups x slabs; a
+ * size on the single-size path counts one).  *n_term_builds: term slabs built (0 with the whole matrix) -- the slabs of
+ * the call, not slabs x sizes; a size on the single-size path adds its own.  garlic_lod_feed_info keeps reporting the
+ * last size processed. */
+#define GARLIC_FEED_TGLS_CHAIN_SHARED 4
+int garlic_lod_feed_multi_info(garlic_panel *panel, int32_t n, int32_t *forms, int32_t *groups, int32_t *n_chain_launches,
+                               int32_t *n_term_builds);
 
 /* First half of assembleROHWindows (src/garlic-roh.cpp:446-454) on the device: for every individual
  * and SNP the number of windows with score >= cutoff that cover the SNP,

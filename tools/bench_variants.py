@@ -13,6 +13,11 @@ kernel's fraction of the HBM roofline at the bytes per window of the form the ca
 GARLIC_GL_NO_TERMS=1 (the look-up chain), over the whole term matrix (first call and warm calls), and -- a library that has
 garlic_panel_set_tgls_term_budget -- under every budget of --term-budgets-gb, with the device memory in use around the
 calls (profiles/tgls_slabs_ab.txt; --tree for the parent commit).
+--modes tgls_feed_multi: the TGLS KDE feeds of every size of --winsizes (step = size) on one resident panel with dictionary
+likelihoods, as one garlic_lod_feed(use_gl) call per size and -- a library that has it -- as one garlic_lod_feed_multi_tgls
+call, over the whole term matrix and under every budget of --term-budgets-gb: chain kernels, the whole call, chain launches,
+term slabs built, device memory around the calls (--tree for the parent commit, which times the single calls only; set
+GARLIC_TGLS_FEED_MULTI_SOLO=1 for the groups-of-one leg).
 """
 import argparse
 import json
@@ -176,6 +181,83 @@ def tgls_slabs_leg(args):
             leg("budget", gb)
 
 
+def tgls_feed_multi_leg(args):
+    """Host clock around the synchronous calls; kernels: the library's events around the chain launches (a loop of single calls:
+    the sum over its calls; under a budget the term passes run beside the chains and are inside neither kernel figure)."""
+    import time
+    import torch
+    from garlic_amd import abi, synth
+
+    torch.cuda.set_device(0)
+    dev = torch.device("cuda", 0)
+    nloci, nind = args.snps, args.inds
+    error, max_gap = 0.001, 200000
+    sizes = [int(w) for w in args.winsizes.split(",")]
+    spec = synth.PanelSpec(nloci, seed=20260105, max_gap=max_gap)
+    ctx = abi.Context(0)
+    panel = abi.Panel(ctx, spec.chr_nloci, nind)
+    panel.set_map(spec.pos, spec.centro_start, spec.centro_end, gpos=spec.gpos)
+    panel.set_freq(spec.freq)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(7)
+    for l0, g in synth.genotype_chunks(spec, nind, dev):
+        gq = torch.randint(3, 61, g.shape, generator=gen, device=dev).to(torch.float64)
+        gl = torch.pow(torch.tensor(10.0, dtype=torch.float64, device=dev), -gq / 10.0)
+        torch.cuda.synchronize()
+        panel.set_genotypes_device(g.data_ptr(), g.shape[1], l0, g.shape[0])
+        panel.set_gl_device(gl.data_ptr(), gl.shape[1], l0, gl.shape[0])
+        del gq, gl
+    del g
+    torch.cuda.empty_cache()
+
+    def used():
+        free_b, total_b = torch.cuda.mem_get_info()
+        return int(total_b - free_b)
+
+    def singles():
+        kern, total, n_slabs = 0.0, 0.0, 0
+        for W in sizes:
+            feed, _ = panel.lod_feed(W, error, max_gap, W, use_gl=True, copy=False)
+            st = panel.stats()
+            kern, total = kern + st["chain_kernel_ms"], total + float(np.sum(feed[np.isfinite(feed)]))
+            if hasattr(panel, "tgls_terms_info"):
+                n_slabs += panel.tgls_terms_info()["n_slabs"]
+        return kern, total, {"n_chain_launches": max(n_slabs, len(sizes)), "n_term_builds": n_slabs}
+
+    def multi():
+        feeds, _ = panel.lod_feed_multi_tgls(sizes, max_gap, copy=False)
+        info = panel.feed_multi_info(len(sizes))
+        return panel.stats()["chain_kernel_ms"], float(sum(np.sum(f[np.isfinite(f)]) for f in feeds)), info
+
+    def leg(name, call, budget_gb):
+        line = {"mode": "tgls_feed_multi", "leg": name, "snps": nloci, "inds": nind, "winsizes": sizes, "repeats": args.steps,
+                "solo_switch": bool(os.environ.get("GARLIC_TGLS_FEED_MULTI_SOLO")), "term_budget_gb": budget_gb,
+                "device_memory_before_bytes": used()}
+        wall, kern = [], []
+        for k in range(2 + args.steps):
+            t0 = time.perf_counter()
+            k_ms, checksum, info = call()
+            dt = (time.perf_counter() - t0) * 1e3
+            if k >= 2:
+                wall.append(dt)
+                kern.append(k_ms)
+        line.update({"call_ms_median": float(np.median(wall)), "call_ms_min": min(wall), "call_ms_max": max(wall),
+                     "kernels_ms_median": float(np.median(kern)), "kernels_ms_min": min(kern), "kernels_ms_max": max(kern),
+                     "feeds_checksum": checksum, "device_memory_after_bytes": used()})
+        line.update(info)
+        if hasattr(panel, "tgls_terms_info"):
+            line.update(panel.tgls_terms_info())
+        print(json.dumps(line), flush=True)
+
+    budgets = [0.0] + ([float(x) for x in args.term_budgets_gb.split(",") if x] if hasattr(panel, "set_tgls_term_budget") else [])
+    for gb in budgets:
+        if gb:
+            panel.set_tgls_term_budget(int(gb * 1e9))
+        leg("single calls", singles, gb)
+        if hasattr(panel, "lod_feed_multi_tgls"):
+            leg("one multi call", multi, gb)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--snps", type=int, default=200000)
@@ -194,6 +276,8 @@ def main():
         sys.path.insert(0, os.path.abspath(args.tree))
     if args.modes == "tgls_slabs":
         return tgls_slabs_leg(args)
+    if args.modes == "tgls_feed_multi":
+        return tgls_feed_multi_leg(args)
     if args.modes in ("wlod_feed", "tgls_feed"):
         return wlod_feed_leg(args, tgls=args.modes == "tgls_feed")
 
