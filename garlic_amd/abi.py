@@ -36,6 +36,7 @@ SYMBOLS = [
     "garlic_panel_alloc_scores_info", "garlic_lod_feed_info",
     "garlic_panel_set_tgls_term_budget", "garlic_panel_tgls_terms_info",
     "garlic_lod_feed_multi_tgls", "garlic_lod_feed_multi_info",
+    "garlic_panel_compute_ld_multi", "garlic_ld_finish_multi", "garlic_panel_ld_info",
 ]
 
 
@@ -129,6 +130,9 @@ def lib():
     L.garlic_lod_feed_info.argtypes = [_vp, _i32p, _i64p]
     L.garlic_panel_set_tgls_term_budget.argtypes = [_vp, C.c_int64]
     L.garlic_panel_tgls_terms_info.argtypes = [_vp, _i64p, _i64p, _i32p, _i32p]
+    L.garlic_panel_compute_ld_multi.argtypes = [_vp, _i32p, C.c_int32, C.c_int32, _i32p, C.c_int32, C.POINTER(_vp), C.c_int32]
+    L.garlic_ld_finish_multi.argtypes = [_vp, _i32p, C.c_int32, C.c_int32, _vp, _vp, C.POINTER(_vp), C.c_int32]
+    L.garlic_panel_ld_info.argtypes = [_vp, C.c_int32, _i32p, _i32p, _i32p, _i64p, _i32p, _i32p]
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int and name not in ("garlic_hip_abi_version",):
@@ -376,6 +380,45 @@ class Panel:
         check(lib().garlic_ld_finish(self.handle, winsize, int(phased), _vp(loc.ctypes.data), _vp(pair.ctypes.data),
                                      _vp(out.ctypes.data) if want_output else None, HOST))
         return out
+
+    def _ld_multi_outs(self, winsizes, want_output):
+        """want_output: True / False for every size, or one flag per listed size"""
+        sizes = np.ascontiguousarray(winsizes, dtype=np.int32)
+        want = [bool(want_output)] * len(sizes) if isinstance(want_output, (bool, np.bool_)) else [bool(w) for w in want_output]
+        assert len(want) == len(sizes)
+        outs = [np.empty((self.nloci, int(w)), dtype=np.float64) if k else None for w, k in zip(sizes, want)]
+        ptrs = (_vp * len(sizes))(*[o.ctypes.data if o is not None else None for o in outs])
+        return sizes, outs, (ptrs if any(want) else None)
+
+    def compute_ld_multi(self, winsizes, sub_idx=None, want_output=True, phased=False):
+        """The LD weights of every listed window size from shared passes; installs them all.  Returns one float64
+        [nloci][winsize] per listed size (None where no output was wanted)."""
+        sub, n = self._sub(sub_idx)
+        sizes, outs, ptrs = self._ld_multi_outs(winsizes, want_output)
+        check(lib().garlic_panel_compute_ld_multi(self.handle, _ptr(sizes, _i32p), len(sizes), int(phased), _ptr(sub, _i32p), n,
+                                                  ptrs, HOST))
+        return outs
+
+    def ld_finish_multi(self, winsizes, locus_counts, pair_counts, want_output=True, phased=False):
+        """pair_counts: those of ld_counts(max(winsizes)), summed over the shards"""
+        sizes, outs, ptrs = self._ld_multi_outs(winsizes, want_output)
+        loc = np.ascontiguousarray(locus_counts, dtype=np.int32)
+        pair = np.ascontiguousarray(pair_counts, dtype=np.int32)
+        assert loc.shape == (self.nloci, 2) and pair.shape == (self.nloci, int(sizes.max()), 2)
+        check(lib().garlic_ld_finish_multi(self.handle, _ptr(sizes, _i32p), len(sizes), int(phased), _vp(loc.ctypes.data),
+                                           _vp(pair.ctypes.data), ptrs, HOST))
+        return outs
+
+    def ld_info(self, cap=64):
+        """(installed winsizes ascending, their group of the last multi call, bytes held by the sets, pair stages, sum passes)"""
+        w = np.zeros(cap, dtype=np.int32)
+        g = np.zeros(cap, dtype=np.int32)
+        n, npair, nsum = C.c_int32(), C.c_int32(), C.c_int32()
+        nbytes = C.c_int64()
+        check(lib().garlic_panel_ld_info(self.handle, cap, _ptr(w, _i32p), _ptr(g, _i32p), C.byref(n), C.byref(nbytes),
+                                         C.byref(npair), C.byref(nsum)))
+        k = min(n.value, cap)
+        return [int(x) for x in w[:k]], [int(x) for x in g[:k]], nbytes.value, npair.value, nsum.value
 
     def ld_counts_device(self, winsize, locus_ptr, pair_ptr, sub_idx=None, phased=False):
         sub, n = self._sub(sub_idx)

@@ -9,6 +9,7 @@
 #include "lod_kernels.hpp"
 #include "variant_kernels.hpp"
 #include "ld_kernels.hpp"
+#include "ld_multi_kernel.hpp"
 #include "tgls_ring_kernel.hpp"
 #include "tgls_feed_kernel.hpp"
 #include "tgls_feed_multi_kernel.hpp"
@@ -22,6 +23,7 @@
 #include <algorithm>
 #include <chrono>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <queue>
 #include <cmath>
@@ -265,6 +267,16 @@ struct garlic_panel {
     int32_t last_feed_form = GARLIC_FEED_FROM_SCORES;   // garlic_lod_feed_info
     int64_t last_feed_doubles = 0;
     int32_t ld_winsize = 0;
+    // garlic_panel_compute_ld_multi / garlic_ld_finish_multi: the weights of the other installed sizes (d_skew holds those
+    // of ld_winsize, the size in use; select_ld swaps).  group: the pass of the multi call that made the set, -1: none
+    struct LdSet {
+        int32_t W = 0, group = -1;
+        DevBuf<double> skew;
+    };
+    std::vector<std::unique_ptr<LdSet>> ld_sets;
+    int32_t ld_group = -1;
+    bool ld_multi_active = false;                  // inside a multi call: install_ld keeps the other sets
+    int32_t ld_pair_passes = 0, ld_sum_passes = 0; // of the last multi call (garlic_panel_ld_info)
     DevBuf<double> d_rld, d_decay, d_stage64;
     DevBuf<uint64_t> d_phase;                      // HapData::firstCopy as bit planes [blk][nloci] (--phased LD)
     uint64_t geno_epoch = 0;                       // bumped by every genotype upload (LD plane cache)
@@ -279,6 +291,7 @@ struct garlic_panel {
         DevBuf<double> hf, fwd, bwd, ld;
         DevBuf<LdSumChr> sum_chrs;
         DevBuf<LdPairChr> pair_chrs;
+        DevBuf<LdMultiChr> multi_chrs;
         // the bit planes (and the per-SNP counts made with them) depend on the genotypes and the LD subsample only, not
         // on the window size: kept across calls (--winsize-multi with --weighted: 3.5 of a call's 32 ms at 10M x 1250)
         uint64_t planes_key = 0;
@@ -289,6 +302,7 @@ struct garlic_panel {
         {
             sub.release(); m.release(); h.release(); o.release(); loc.release(); pair.release(); loc_planes.release();
             hf.release(); fwd.release(); bwd.release(); ld.release(); sum_chrs.release(); pair_chrs.release();
+            multi_chrs.release();
             planes_valid = false;
         }
     } lds;
@@ -378,6 +392,7 @@ struct garlic_panel {
     } plan;
 };
 
+static bool select_ld(garlic_panel *p, int32_t winsize);   // makes the installed LD weights of winsize the ones in use
 static int ensure_rld(garlic_panel *p);   // plain reciprocals of the LD weights, made when the generic wLOD kernel needs them
 
 // ---- Score buffers.  Where 8 GB of scores sit in VRAM decides between two speeds of lod_chain_kernel at 1M SNPs x
@@ -1323,7 +1338,7 @@ int decide_form(garlic_panel *p, const LodCall &c, LodForm &f)
         if (mode == MODE_LOD_GL && (rc = tgls_terms_or_slabs(p, &f.slab_blocks))) return rc;
     } else if ((rc = ensure_term_table(p, c.error))) return rc;
     if (mode == MODE_WLOD) {
-        if (!p->have_ld || p->ld_winsize != W)
+        if (!select_ld(p, W))
             return fail(GARLIC_ERR_STATE, "wLOD needs LD weights for winsize %d (garlic_panel_set_ld)", W);
         if ((rc = ensure_decay_table(p, c.M, c.mu))) return rc;
     }
@@ -2523,19 +2538,68 @@ int garlic_panel_set_phase(garlic_panel *p, const uint8_t *first_copy, int64_t l
 // zero: clear it (skew_reciprocal_kernel's caller).  ld_sum_col_kernel writes every weight a scored window reads; what it
 // leaves alone only ever reaches windows that have no score (they are computed along and written as MISSING), so its
 // caller clears just the padding behind the panel, which the last windows' loads run into.
-static int reserve_skew(garlic_panel *p, int32_t winsize, bool zero = true)
+static int reserve_skew_buf(garlic_panel *p, DevBuf<double> &buf, int32_t winsize, bool zero)
 {
     int rc;
     const size_t nskew = SKEW_FRONT + ((size_t)p->nloci + winsize + 64) * winsize;
-    if ((rc = p->d_skew.reserve(nskew))) return rc;
+    if ((rc = buf.reserve(nskew))) return rc;
     if (zero) {
-        HIP_TRY(hipMemsetAsync(p->d_skew.p, 0, sizeof(double) * nskew, p->ctx->stream));
+        HIP_TRY(hipMemsetAsync(buf.p, 0, sizeof(double) * nskew, p->ctx->stream));
     } else {
-        HIP_TRY(hipMemsetAsync(p->d_skew.p, 0, sizeof(double) * SKEW_FRONT, p->ctx->stream));
+        HIP_TRY(hipMemsetAsync(buf.p, 0, sizeof(double) * SKEW_FRONT, p->ctx->stream));
         const size_t body = SKEW_FRONT + (size_t)p->nloci * winsize;
-        HIP_TRY(hipMemsetAsync(p->d_skew.p + body, 0, sizeof(double) * (nskew - body), p->ctx->stream));
+        HIP_TRY(hipMemsetAsync(buf.p + body, 0, sizeof(double) * (nskew - body), p->ctx->stream));
     }
     return GARLIC_OK;
+}
+static int reserve_skew(garlic_panel *p, int32_t winsize, bool zero = true)
+{
+    return reserve_skew_buf(p, p->d_skew, winsize, zero);
+}
+
+// The panel's sets of LD weights: the one in use (d_skew, ld_winsize) and, after a multi call, the others.
+static void drop_ld_sets(garlic_panel *p) { p->ld_sets.clear(); }
+static bool select_ld(garlic_panel *p, int32_t winsize)
+{
+    if (p->have_ld && p->ld_winsize == winsize) return true;
+    for (size_t i = 0; i < p->ld_sets.size(); i++) {
+        garlic_panel::LdSet &set = *p->ld_sets[i];
+        if (set.W != winsize) continue;
+        std::swap(set.skew.p, p->d_skew.p);
+        std::swap(set.skew.cap, p->d_skew.cap);
+        std::swap(set.group, p->ld_group);
+        if (p->have_ld) set.W = p->ld_winsize;
+        else p->ld_sets.erase(p->ld_sets.begin() + (ptrdiff_t)i);
+        p->ld_winsize = winsize;
+        p->have_ld = true;
+        p->rld_valid = false;          // the plain reciprocals follow the size in use (ensure_rld)
+        return true;
+    }
+    return false;
+}
+// the set in use joins the others (a multi call goes on to the next size)
+static void stash_ld(garlic_panel *p, int32_t group)
+{
+    if (!p->have_ld) return;
+    std::unique_ptr<garlic_panel::LdSet> set(new garlic_panel::LdSet);
+    set->W = p->ld_winsize;
+    set->group = group;
+    std::swap(set->skew.p, p->d_skew.p);
+    std::swap(set->skew.cap, p->d_skew.cap);
+    p->ld_sets.push_back(std::move(set));
+    p->have_ld = false;
+    p->rld_valid = false;
+    p->ld_winsize = 0;
+    p->ld_group = -1;
+}
+static void drop_all_ld(garlic_panel *p)
+{
+    drop_ld_sets(p);
+    p->d_skew.release();
+    p->d_rld.release();
+    p->have_ld = p->rld_valid = false;
+    p->ld_winsize = 0;
+    p->ld_group = -1;
 }
 
 // skew_done: the LD kernels have written D themselves (ld_sum_col_kernel)
@@ -2555,6 +2619,11 @@ static int install_ld(garlic_panel *p, int32_t winsize, const double *src, bool 
     p->rld_valid = false;
     p->have_ld = true;
     p->ld_winsize = winsize;
+    p->ld_group = -1;
+    if (!p->ld_multi_active) {   // a single-size call leaves exactly the one set it installs
+        drop_ld_sets(p);
+        p->ld_pair_passes = p->ld_sum_passes = 0;
+    }
     return GARLIC_OK;
 }
 
@@ -3013,6 +3082,306 @@ int garlic_panel_compute_ld(garlic_panel *p, int32_t winsize, int32_t phased, co
         if (e != hipSuccess) rc = fail(GARLIC_ERR_HIP, "LD copy-out: %s", hipGetErrorString(e));
     }
     return rc;
+}
+
+// ---- LD weights of several window sizes from shared passes (ld_multi_kernel.hpp; the rule is stated in garlic_hip.h)
+static int ld_col_threads(int32_t winsize) { return (winsize + 16 + WAVE - 1) / WAVE * WAVE; }
+
+struct LdMultiPlan {
+    std::vector<int32_t> uniq;                     // the distinct sizes, ascending
+    std::vector<std::vector<int32_t>> groups;      // the shared passes (ascending), then the sizes on their own (ascending)
+    size_t n_shared = 0;                           // groups [0, n_shared) go through ld_sum_multi_kernel
+    int32_t wtab = 0;                              // the widest shared size: the pitch of their one pair table
+};
+static LdMultiPlan ld_multi_plan(const int32_t *winsizes, int32_t n_sizes)
+{
+    LdMultiPlan plan;
+    plan.uniq.assign(winsizes, winsizes + n_sizes);
+    std::sort(plan.uniq.begin(), plan.uniq.end());
+    plan.uniq.erase(std::unique(plan.uniq.begin(), plan.uniq.end()), plan.uniq.end());
+    const char *solo_env = getenv("GARLIC_LD_MULTI_SOLO");
+    const bool solo = solo_env && atoi(solo_env) != 0;
+    std::vector<int32_t> sharing, alone;
+    for (int32_t w : plan.uniq) (!solo && ld_sums_by_snp(w) ? sharing : alone).push_back(w);
+    if (sharing.size() < 2) {                      // nothing to share a pass with
+        alone = plan.uniq;
+        sharing.clear();
+    }
+    for (int32_t w : sharing) {
+        const bool fits = !plan.groups.empty() && plan.groups.back().size() < (size_t)LDM_MAX_SIZES &&
+                          ldms_lds_bytes(ld_col_threads(w), (int)plan.groups.back().size()) <= LDMS_LDS_MAX;
+        if (!fits) plan.groups.emplace_back();
+        plan.groups.back().push_back(w);
+    }
+    plan.n_shared = plan.groups.size();
+    plan.wtab = sharing.empty() ? 0 : sharing.back();
+    for (int32_t w : alone) plan.groups.push_back(std::vector<int32_t>{w});
+    return plan;
+}
+
+typedef std::vector<std::unique_ptr<garlic_panel::LdSet>> LdSetPool;
+// a weight buffer for winsize: the one the panel held for that size before the call, or a new one
+static std::unique_ptr<garlic_panel::LdSet> ld_pool_take(LdSetPool &pool, int32_t winsize)
+{
+    for (size_t i = 0; i < pool.size(); i++)
+        if (pool[i]->W == winsize) {
+            std::unique_ptr<garlic_panel::LdSet> set = std::move(pool[i]);
+            pool.erase(pool.begin() + (ptrdiff_t)i);
+            return set;
+        }
+    std::unique_ptr<garlic_panel::LdSet> set(new garlic_panel::LdSet);
+    set->W = winsize;
+    return set;
+}
+
+// the combined table C at pitch 2 W from pair counts at pitch W (garlic_ld_finish's hr2 stage for ld_sum_col_kernel)
+static int ld_build_table(garlic_panel *p, int32_t W, int32_t phased, const int32_t *loc, const int32_t *pair)
+{
+    int rc;
+    hipStream_t s = p->ctx->stream;
+    const size_t n = (size_t)p->nloci * W;
+    if ((rc = p->lds.hf.reserve(p->nloci)) || (rc = p->lds.fwd.reserve(2 * n + 256))) return rc;
+    if (phased)
+        HIP_TRY(hipMemcpyAsync(p->lds.hf.p, p->freq.data(), sizeof(double) * p->nloci, hipMemcpyHostToDevice, s));
+    else
+        hipLaunchKernelGGL(ld_homfreq_kernel, dim3((unsigned)((p->nloci + 255) / 256)), dim3(256), 0, s, loc, p->nloci, p->lds.hf.p);
+    const size_t hr2_lds = sizeof(double) * (LD_HR2_T + W + (size_t)LD_HR2_T * (W + 1));
+    for (int c = 0; c < p->nchr; c++) {
+        const int64_t lo = p->chr_off[c], hi = p->chr_off[c + 1];
+        if (hr2_lds <= 64 * 1024 && !getenv("GARLIC_LD_HR2_PLAIN"))
+            hipLaunchKernelGGL(ld_hr2_tile_kernel, dim3((unsigned)((hi - lo + LD_HR2_T - 1) / LD_HR2_T)), dim3(256), hr2_lds, s, pair,
+                               p->lds.hf.p, lo, hi, W, p->lds.fwd.p);
+        else
+            hipLaunchKernelGGL(ld_hr2_kernel<true>, dim3((unsigned)(hi - lo)), dim3(128), 0, s, pair, p->lds.hf.p, lo, hi, W,
+                               p->lds.fwd.p, (double *)nullptr);
+    }
+    HIP_TRY(hipGetLastError());
+    return GARLIC_OK;
+}
+
+// one shared pass: the sizes g (ascending, distinct) from the table of pitch 2 wtab in lds.fwd; dev_ld[i]: LD matrix of g[i] or NULL
+static int ld_multi_group(garlic_panel *p, const std::vector<int32_t> &g, int32_t gid, int32_t wtab, double *const *dev_ld,
+                          LdSetPool &pool)
+{
+    int rc;
+    hipStream_t s = p->ctx->stream;
+    const int32_t W = g.back(), wmin = g.front();
+    const int threads = ld_col_threads(W), B = std::min(LD_COL_B, threads - W), pieces = (threads * 8 + 1023) / 1024;
+    const size_t lds = ldms_lds_bytes(threads, (int)g.size() - 1);
+    std::vector<LdMultiChr> chrs;
+    int64_t blocks = 0;
+    for (int c = 0; c < p->nchr; c++) {
+        const int64_t lo = p->chr_off[c], hi = p->chr_off[c + 1], nstarts = hi - lo - wmin + 1;
+        if (nstarts < 1) continue;
+        chrs.push_back(LdMultiChr{lo, hi, nstarts, blocks});
+        blocks += (nstarts + B - 1) / B;
+    }
+    std::vector<std::unique_ptr<garlic_panel::LdSet>> sets;
+    LdMultiSmall small{};
+    small.n = (int32_t)g.size() - 1;
+    for (size_t i = 0; i < g.size(); i++) {
+        sets.push_back(ld_pool_take(pool, g[i]));
+        sets.back()->group = gid;
+        if ((rc = reserve_skew_buf(p, sets.back()->skew, g[i], false))) return rc;
+        // initLDData zero-fills: the rows without a full window of the size (the kernel writes every other entry)
+        for (int c = 0; dev_ld[i] && c < p->nchr; c++) {
+            const int64_t lo = p->chr_off[c], hi = p->chr_off[c + 1], from = std::max<int64_t>(lo, hi - g[i] + 1);
+            if (hi > from) HIP_TRY(hipMemsetAsync(dev_ld[i] + from * g[i], 0, sizeof(double) * (size_t)(hi - from) * g[i], s));
+        }
+        if (i + 1 < g.size()) {
+            small.w[i] = g[i];
+            small.ld[i] = dev_ld[i];
+            small.d[i] = sets.back()->skew.p + SKEW_FRONT;
+        }
+    }
+    if (!chrs.empty()) {
+        if ((rc = p->lds.multi_chrs.reserve(chrs.size()))) return rc;
+        HIP_TRY(hipMemcpyAsync(p->lds.multi_chrs.p, chrs.data(), sizeof(LdMultiChr) * chrs.size(), hipMemcpyHostToDevice, s));
+        static_assert(LD_COL_MAX_THREADS <= 128 * LD_COL_MAX_PIECES, "one instantiation per request count");
+        const void *fn = pieces == 1 ? (const void *)ld_sum_multi_kernel<1> : pieces == 2 ? (const void *)ld_sum_multi_kernel<2>
+                       : pieces == 3 ? (const void *)ld_sum_multi_kernel<3> : pieces == 4 ? (const void *)ld_sum_multi_kernel<4>
+                                                                                         : (const void *)ld_sum_multi_kernel<5>;
+        if (lds > 48 * 1024) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        const double *a_c = p->lds.fwd.p;
+        const LdMultiChr *a_chrs = p->lds.multi_chrs.p;
+        int a_nchr = (int)chrs.size(), a_wtab = wtab, a_w = W, a_b = B;
+        double *a_ld = dev_ld[g.size() - 1], *a_d = sets.back()->skew.p + SKEW_FRONT;
+        unsigned a_nwork = (unsigned)blocks;
+        void *kargs[] = {(void *)&a_c, (void *)&a_chrs, (void *)&a_nchr, (void *)&a_wtab, (void *)&a_w, (void *)&a_b, (void *)&small,
+                         (void *)&a_ld, (void *)&a_d, (void *)&a_nwork};
+        garlic_ctx *ctx = p->ctx;
+        const int slot = (int)(ctx->n_calls % garlic_ctx::HIST);
+        (void)hipEventRecord(ctx->hist0[slot], s);
+        HIP_TRY(hipLaunchKernel(fn, dim3((a_nwork + 7u) / 8u * 8u), dim3(threads), kargs, lds, s));
+        (void)hipEventRecord(ctx->hist1[slot], s);
+        ctx->n_calls++;
+        HIP_TRY(hipStreamSynchronize(s));          // chrs (host) is read by the copy above
+    }
+    p->ld_sum_passes++;
+    for (auto &set : sets) p->ld_sets.push_back(std::move(set));
+    return GARLIC_OK;
+}
+
+// counts == false: garlic_panel_compute_ld_multi (sub_idx, n_sub); counts == true: garlic_ld_finish_multi (loc, pair_all: device
+// pointers, the pair counts at pitch wall)
+static int ld_multi_run(garlic_panel *p, const LdMultiPlan &plan, int32_t phased, bool counts, const int32_t *sub_idx, int32_t n_sub,
+                        const int32_t *loc, const int32_t *pair_all, int32_t wall, double *const *dev_ld /* per plan.uniq */)
+{
+    int rc;
+    hipStream_t s = p->ctx->stream;
+    auto out_of = [&](int32_t w) { return dev_ld[std::lower_bound(plan.uniq.begin(), plan.uniq.end(), w) - plan.uniq.begin()]; };
+    // what the panel held becomes the pool the new sets take their buffers from (a sweep repeats its sizes)
+    LdSetPool pool;
+    stash_ld(p, -1);
+    pool.swap(p->ld_sets);
+    p->ld_pair_passes = p->ld_sum_passes = 0;
+    DevBuf<int32_t> &d_loc = p->lds.loc, &d_pair = p->lds.pair;
+    // the pair counts at the pitch of w (finish): the caller's table or its first w columns
+    auto pair_at = [&](int32_t w, const int32_t **out) -> int {
+        if (w == wall) { *out = pair_all; return GARLIC_OK; }
+        int r = d_pair.reserve((size_t)p->nloci * w * 2);
+        if (r) return r;
+        hipLaunchKernelGGL(ld_pair_repitch_kernel, dim3((unsigned)(((int64_t)p->nloci * w + 255) / 256)), dim3(256), 0, s, pair_all, wall,
+                           p->nloci, w, d_pair.p);
+        HIP_TRY(hipGetLastError());
+        *out = d_pair.p;
+        return GARLIC_OK;
+    };
+    if (plan.n_shared > 0) {
+        const int32_t wtab = plan.wtab;
+        bool have_table = false;
+        const int32_t *pair = nullptr;
+        if (!counts) {
+            const bool fuse = ld_pairs_on_mfma(wtab, phased) && ld_sums_by_snp(wtab) && !getenv("GARLIC_LD_UNFUSED");
+            if ((rc = d_loc.reserve((size_t)p->nloci * 2)) || (rc = d_pair.reserve(fuse ? 2 : (size_t)p->nloci * wtab * 2))) return rc;
+            p->lds.fuse_request = fuse;
+            if ((rc = garlic_ld_counts(p, wtab, phased, sub_idx, n_sub, d_loc.p, d_pair.p, GARLIC_DEVICE))) {
+                p->lds.fuse_request = false;
+                return rc;
+            }
+            have_table = p->lds.fused_done;
+            p->lds.fused_done = false;
+            loc = d_loc.p;
+            pair = d_pair.p;
+        } else if ((rc = pair_at(wtab, &pair))) {
+            return rc;
+        }
+        p->ld_pair_passes++;
+        if (!have_table && (rc = ld_build_table(p, wtab, phased, loc, pair))) return rc;
+        for (size_t g = 0; g < plan.n_shared; g++) {
+            std::vector<double *> outs;
+            for (int32_t w : plan.groups[g]) outs.push_back(out_of(w));
+            if ((rc = ld_multi_group(p, plan.groups[g], (int32_t)g, wtab, outs.data(), pool))) return rc;
+        }
+    }
+    for (size_t g = plan.n_shared; g < plan.groups.size(); g++) {       // today's single-size path, then the set joins the others
+        const int32_t w = plan.groups[g][0];
+        std::unique_ptr<garlic_panel::LdSet> set = ld_pool_take(pool, w);
+        std::swap(set->skew.p, p->d_skew.p);
+        std::swap(set->skew.cap, p->d_skew.cap);
+        set.reset();
+        if (!counts) {
+            rc = garlic_panel_compute_ld(p, w, phased, sub_idx, n_sub, out_of(w), GARLIC_DEVICE);
+        } else {
+            const int32_t *pair = nullptr;
+            if ((rc = pair_at(w, &pair))) return rc;
+            rc = garlic_ld_finish(p, w, phased, loc, pair, out_of(w), GARLIC_DEVICE);
+        }
+        if (rc) return rc;
+        p->ld_pair_passes++;
+        p->ld_sum_passes++;
+        stash_ld(p, (int32_t)g);
+    }
+    HIP_TRY(hipStreamSynchronize(s));               // the pool's leftovers are freed on return
+    return GARLIC_OK;
+}
+
+static int ld_multi_call(garlic_panel *p, const int32_t *winsizes, int32_t n_sizes, int32_t phased, bool counts, const int32_t *sub_idx,
+                         int32_t n_sub, const int32_t *locus_counts, const int32_t *pair_counts, double *const *ld_out, int32_t where)
+{
+    int rc;
+    if (!p) return fail(GARLIC_ERR_INVALID, "panel is NULL");
+    if (!winsizes || n_sizes < 1) return fail(GARLIC_ERR_INVALID, "at least one window size is required");
+    for (int i = 0; i < n_sizes; i++)
+        if ((rc = ld_check(p, winsizes[i], phased))) return rc;
+    if (counts && (!locus_counts || !pair_counts)) return fail(GARLIC_ERR_INVALID, "count buffers are required");
+    if (!counts && (n_sub < 0 || (n_sub > 0 && !sub_idx))) return fail(GARLIC_ERR_INVALID, "bad LD subsample");
+    hipStream_t s = p->ctx->stream;
+    const LdMultiPlan plan = ld_multi_plan(winsizes, n_sizes);
+    const int32_t wall = plan.uniq.back();
+    // one device LD matrix per distinct size somebody wants: the caller's (device) or a temporary (host)
+    std::vector<std::unique_ptr<DevBuf<double>>> tmp;
+    std::vector<double *> dev_ld(plan.uniq.size(), nullptr);
+    for (int i = 0; ld_out && i < n_sizes; i++) {
+        if (!ld_out[i]) continue;
+        const size_t u = std::lower_bound(plan.uniq.begin(), plan.uniq.end(), winsizes[i]) - plan.uniq.begin();
+        if (dev_ld[u]) continue;
+        if (where == GARLIC_DEVICE) { dev_ld[u] = ld_out[i]; continue; }
+        tmp.emplace_back(new DevBuf<double>);
+        if ((rc = tmp.back()->reserve((size_t)p->nloci * winsizes[i]))) { drop_all_ld(p); return rc; }
+        dev_ld[u] = tmp.back()->p;
+    }
+    DevBuf<int32_t> in_loc, in_pair;                // the caller's host counts on the device (the panel's scratch is in use)
+    if (counts && where == GARLIC_HOST) {
+        const size_t npair = (size_t)p->nloci * wall * 2;
+        if ((rc = in_loc.reserve((size_t)p->nloci * 2)) || (rc = in_pair.reserve(npair))) { drop_all_ld(p); return rc; }
+        hipError_t e = hipMemcpyAsync(in_loc.p, locus_counts, sizeof(int32_t) * p->nloci * 2, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(in_pair.p, pair_counts, sizeof(int32_t) * npair, hipMemcpyHostToDevice, s);
+        if (e != hipSuccess) { drop_all_ld(p); return fail(GARLIC_ERR_HIP, "LD finish: %s", hipGetErrorString(e)); }
+        locus_counts = in_loc.p;
+        pair_counts = in_pair.p;
+    }
+    p->ld_multi_active = true;
+    rc = ld_multi_run(p, plan, phased, counts, sub_idx, n_sub, locus_counts, pair_counts, wall, dev_ld.data());
+    p->ld_multi_active = false;
+    (void)hipStreamSynchronize(s);
+    if (rc) {                                       // no LD weights stay installed
+        drop_all_ld(p);
+        return rc;
+    }
+    for (int i = 0; ld_out && i < n_sizes; i++) {
+        if (!ld_out[i]) continue;
+        const size_t u = std::lower_bound(plan.uniq.begin(), plan.uniq.end(), winsizes[i]) - plan.uniq.begin();
+        if (ld_out[i] == dev_ld[u]) continue;
+        hipError_t e = hipMemcpy(ld_out[i], dev_ld[u], sizeof(double) * p->nloci * winsizes[i],
+                                 where == GARLIC_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice);
+        if (e != hipSuccess) { drop_all_ld(p); return fail(GARLIC_ERR_HIP, "LD copy-out: %s", hipGetErrorString(e)); }
+    }
+    select_ld(p, winsizes[0]);
+    return GARLIC_OK;
+}
+
+int garlic_panel_compute_ld_multi(garlic_panel *p, const int32_t *winsizes, int32_t n_sizes, int32_t phased, const int32_t *sub_idx,
+                                  int32_t n_sub, double *const *ld_out, int32_t where)
+{
+    return ld_multi_call(p, winsizes, n_sizes, phased, false, sub_idx, n_sub, nullptr, nullptr, ld_out, where);
+}
+
+int garlic_ld_finish_multi(garlic_panel *p, const int32_t *winsizes, int32_t n_sizes, int32_t phased, const int32_t *locus_counts,
+                           const int32_t *pair_counts, double *const *ld_out, int32_t where)
+{
+    return ld_multi_call(p, winsizes, n_sizes, phased, true, nullptr, 0, locus_counts, pair_counts, ld_out, where);
+}
+
+int garlic_panel_ld_info(garlic_panel *p, int32_t cap, int32_t *winsizes, int32_t *groups, int32_t *n_installed, int64_t *weight_bytes,
+                         int32_t *n_pair_passes, int32_t *n_sum_passes)
+{
+    if (!p) return fail(GARLIC_ERR_INVALID, "panel is NULL");
+    std::vector<std::pair<int32_t, int32_t>> sets;
+    if (p->have_ld) sets.emplace_back(p->ld_winsize, p->ld_group);
+    for (const auto &set : p->ld_sets) sets.emplace_back(set->W, set->group);
+    std::sort(sets.begin(), sets.end());
+    int64_t bytes = 0;
+    for (size_t i = 0; i < sets.size(); i++) {
+        bytes += (int64_t)sizeof(double) * (SKEW_FRONT + ((int64_t)p->nloci + sets[i].first + 64) * sets[i].first);
+        if ((int32_t)i < cap && winsizes) winsizes[i] = sets[i].first;
+        if ((int32_t)i < cap && groups) groups[i] = sets[i].second;
+    }
+    if (n_installed) *n_installed = (int32_t)sets.size();
+    if (weight_bytes) *weight_bytes = bytes;
+    if (n_pair_passes) *n_pair_passes = p->ld_pair_passes;
+    if (n_sum_passes) *n_sum_passes = p->ld_sum_passes;
+    return GARLIC_OK;
 }
 
 // Drops everything the panel keeps only to make the next call cheaper: LD scratch, the score and

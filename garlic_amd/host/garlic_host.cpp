@@ -1431,6 +1431,77 @@ std::vector<LDData *> *LodEngine::ldWeights(int winsize, const std::vector<int> 
     return out;
 }
 
+bool LodEngine::ldWeightsMulti(const std::vector<int> &sizes, const std::vector<int> &subsample, bool phased)
+{
+    if (sizes.empty()) return true;
+    if (phased && !impl->have_phase) fail("--phased: the genotypes were loaded without phase (HapData::firstCopy)");
+    const int32_t ph = phased ? 1 : 0;
+    std::cerr << "Calculating LD weights with winsizes";
+    for (int W : sizes) std::cerr << " " << W;
+    std::cerr << " (one LD computation for " << sizes.size() << " window sizes).\n";
+    const std::vector<int32_t> ws(sizes.begin(), sizes.end());
+    const int32_t wmax = *std::max_element(ws.begin(), ws.end());
+    int64_t nloci = 0;
+    for (int n : impl->chr_nloci) nloci += n;
+    const size_t ns = impl->shards.size();
+    std::vector<std::string> errors(ns);
+    std::vector<int> codes(ns, GARLIC_OK);
+    auto shard_sub = [&](size_t k, std::vector<int32_t> &sub) -> const int32_t * {
+        auto &s = impl->shards[k];
+        for (int g : subsample)
+            if (g >= s.ind_begin && g < s.ind_begin + s.nind) sub.push_back(g - s.ind_begin);
+        static const int32_t no_index = 0;
+        return subsample.empty() ? nullptr : (sub.empty() ? &no_index : sub.data());
+    };
+    if (ns == 1) {      // every individual's counts are on the one device: pair stage and shared sums in one call
+        std::vector<int32_t> sub;
+        const int32_t *sub_ptr = shard_sub(0, sub);
+        const int rc = garlic_panel_compute_ld_multi(impl->shards[0].panel, ws.data(), (int32_t)ws.size(), ph, sub_ptr, (int32_t)sub.size(),
+                                                     nullptr, GARLIC_HOST);
+        if (rc == GARLIC_ERR_NOMEM) return false;
+        if (rc != GARLIC_OK) fail(std::string("garlic_panel_compute_ld_multi: ") + garlic_hip_last_error());
+        return true;
+    }
+    // the integer counts at the largest size, summed over the shards, serve every size
+    std::vector<int32_t> loc((size_t)nloci * 2, 0), pair((size_t)nloci * wmax * 2, 0);
+    std::mutex sum_lock;
+    {
+        std::vector<std::thread> th;
+        for (size_t k = 0; k < ns; k++)
+            th.emplace_back([&, k] {
+                std::vector<int32_t> sub, lo(loc.size()), pa(pair.size());
+                const int32_t *sub_ptr = shard_sub(k, sub);
+                if (garlic_ld_counts(impl->shards[k].panel, wmax, ph, sub_ptr, (int32_t)sub.size(), lo.data(), pa.data(), GARLIC_HOST) !=
+                    GARLIC_OK) {
+                    errors[k] = garlic_hip_last_error();
+                    return;
+                }
+                std::lock_guard<std::mutex> hold(sum_lock);
+                for (size_t i = 0; i < loc.size(); i++) loc[i] += lo[i];
+                for (size_t i = 0; i < pair.size(); i++) pair[i] += pa[i];
+            });
+        for (auto &t : th) t.join();
+    }
+    for (auto &e : errors)
+        if (!e.empty()) fail("garlic_ld_counts: " + e);
+    {
+        std::vector<std::thread> th;
+        for (size_t k = 0; k < ns; k++)
+            th.emplace_back([&, k] {
+                codes[k] = garlic_ld_finish_multi(impl->shards[k].panel, ws.data(), (int32_t)ws.size(), ph, loc.data(), pair.data(), nullptr,
+                                                  GARLIC_HOST);
+                if (codes[k] != GARLIC_OK) errors[k] = garlic_hip_last_error();
+            });
+        for (auto &t : th) t.join();
+    }
+    bool nomem = false;
+    for (size_t k = 0; k < ns; k++) {
+        if (codes[k] == GARLIC_ERR_NOMEM) nomem = true;
+        else if (codes[k] != GARLIC_OK) fail("garlic_ld_finish_multi: " + errors[k]);
+    }
+    return !nomem;
+}
+
 std::vector<WinData *> *LodEngine::run(bool weighted, int winsize, double error, int MAX_GAP, int M, double mu)
 {
     std::cerr << "Calculating LOD scores with winsize " << winsize << ".\n";

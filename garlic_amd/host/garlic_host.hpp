@@ -256,6 +256,11 @@ public:
     // phased: calcR2LD (r2 from HapData::firstCopy and FreqData::freq) instead of calcHR2LD.
     std::vector<LDData *> *ldWeights(int winsize, const std::vector<int> &subsample, bool want_host = true,
                                      bool phased = false);
+    // The LD weights of every listed window size from shared passes (garlic_panel_compute_ld_multi; several shards:
+    // garlic_ld_counts at the largest size, the host sum, garlic_ld_finish_multi on every shard); all of them stay
+    // installed for wlodWindowsResident / lodFeed / assembleROHWindows.  false: the sets do not fit the device memory
+    // (nothing is installed: go on with ldWeights per size).
+    bool ldWeightsMulti(const std::vector<int> &sizes, const std::vector<int> &subsample, bool phased = false);
     std::vector<WinData *> *wlodWindowsResident(int winsize, double error, int MAX_GAP, int M, double mu);
     // What exploreWinsizes / selectWinsize keep of a window size (garlic-roh.cpp:741-745, 816-823):
     // convertWinData2DoubleData(calcLODWindows(...), step), with the scores thinned on the device(s)

@@ -256,8 +256,13 @@ int main(int argc, char **argv)
         const bool single_size = a.winsize_multi.empty();
         if (a.have_cutoff && !a.weighted)
             for (int W : a.winsize_multi.empty() ? std::vector<int>{a.winsize} : a.winsize_multi) roh_calls(W, single_size);
+        // --weighted --winsize-multi: the LD weights of all sizes from shared passes, once; where the sets do not fit the
+        // device, per size as before
+        const bool ld_shared = a.weighted && sizes.size() > 1 && engine.ldWeightsMulti(sizes, ldsub, a.phased);
+        if (a.weighted && sizes.size() > 1 && !ld_shared)
+            std::cerr << "NOTE: the LD weights of all window sizes do not fit the device memory; computing them per size\n";
         for (int W : sizes) {
-            if (a.weighted) engine.ldWeights(W, ldsub, false, a.phased);   // garlic-main.cpp:346-357: LD weights per window size
+            if (a.weighted && !ld_shared) engine.ldWeights(W, ldsub, false, a.phased);   // garlic-main.cpp:346-357: LD weights per window size
             if (a.weighted) roh_calls(W, single_size);
             const std::string feed_path = a.out + "." + std::to_string(W) + "SNPs.lod.f64";
             if (!a.raw_lod) {   // only the KDE feed is wanted: thin on the device, no full-score download

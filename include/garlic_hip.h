@@ -48,7 +48,8 @@ extern "C" {
  * 8: garlic_call_stats::n_stall_reruns / n_count_timeouts, garlic_panel_alloc_scores_info; garlic_lod_feed_info (added
  *    under the same number: nothing that existed changed); GARLIC_FEED_TGLS_CHAIN (a fourth value of its form, likewise);
  *    garlic_panel_set_tgls_term_budget, garlic_panel_tgls_terms_info (likewise); garlic_lod_feed_multi_tgls,
- *    garlic_lod_feed_multi_info, GARLIC_FEED_TGLS_CHAIN_SHARED (likewise) */
+ *    garlic_lod_feed_multi_info, GARLIC_FEED_TGLS_CHAIN_SHARED (likewise); garlic_panel_compute_ld_multi,
+ *    garlic_ld_finish_multi, garlic_panel_ld_info (likewise) */
 #define GARLIC_HIP_ABI_VERSION 8
 
 #define GARLIC_OK 0
@@ -227,6 +228,42 @@ int garlic_ld_counts(garlic_panel *panel, int32_t winsize, int32_t phased, const
                      int32_t n_sub, int32_t *locus_counts, int32_t *pair_counts, int32_t where);
 int garlic_ld_finish(garlic_panel *panel, int32_t winsize, int32_t phased, const int32_t *locus_counts,
                      const int32_t *pair_counts, double *ld_out, int32_t where);
+
+/* The LD weights of SEVERAL window sizes (a --weighted sweep over window sizes).  ld_out may be NULL and so may any of
+ * its entries; ld_out[i] receives nloci * winsizes[i] doubles, exactly what garlic_panel_compute_ld(winsizes[i]) writes.
+ * The call installs the weights of EVERY listed size: the panel keeps a set of weights per window size, and
+ * garlic_wlod_windows, the weighted garlic_lod_feed / _subset, garlic_roh_coverage_fused and garlic_roh_segments use the
+ * set of their winsize (GARLIC_ERR_STATE when it is not installed).  Sizes may come in any order and may repeat; a
+ * repeated size has one set.  garlic_panel_set_ld, garlic_panel_compute_ld and garlic_ld_finish still leave the panel
+ * with exactly the one set they install; garlic_panel_release_scratch keeps every installed set.  Per size a set is
+ * (16 + (nloci + W + 64) * W) * 8 bytes; when the sets do not fit the call returns GARLIC_ERR_NOMEM and no LD weights
+ * stay installed.
+ *
+ * The pair value c(i, j) does not depend on the window size, so LD_W'[s][k] is LD_W[s][k]'s accumulator after its first
+ * W' terms (W' < W, k < W'): one ordered-sum pass at the largest size of a group yields every size of the group as
+ * snapshots of the running sums -- same operands, same order, same roundings.  Grouping rule, on the distinct sizes:
+ *   - a size SHARES when it takes the SNP-per-thread sum kernel (32 < W <= 512, no sum-form switch set) and
+ *     GARLIC_LD_MULTI_SOLO is not set to a non-zero value; if fewer than two sizes share, none does
+ *   - the sharing sizes, ascending, are cut greedily into groups: a size joins the current group unless the group has
+ *     4 sizes already or 8 * max(R + (n - 1) * 9 * T, 17 * T) > 131072, where n is the group's size count with it,
+ *     T = W + 16 rounded up to a multiple of 64 and R = 2048 * ceil(T / 128) + 130 (the launch's LDS in bytes)
+ *   - the sharing sizes cost ONE pair stage, at the largest of them (its table serves every group; the stage is the one
+ *     garlic_panel_compute_ld / garlic_ld_counts + garlic_ld_finish would pick for that width, hr2 or r2), and one sum
+ *     pass per group
+ *   - every other size goes through the single-size path unchanged: one pair stage and one sum pass each
+ * garlic_ld_finish_multi is the sharded form: pair_counts are those of garlic_ld_counts at max(winsizes), summed over
+ * the shards ([nloci][max(winsizes)][2]); the counts of narrower sizes are its first columns.
+ * garlic_panel_ld_info lists the installed sizes ascending (up to cap of them; n_installed counts all), for each the
+ * index of its group in the last multi call -- the shared groups in ascending order first, then the sizes on their own,
+ * ascending; -1: not installed by a multi call -- the bytes the sets hold, and the pair stages and sum passes the last
+ * multi call ran (0 after a single-size call).  Any output may be NULL. */
+int garlic_panel_compute_ld_multi(garlic_panel *panel, const int32_t *winsizes, int32_t n_sizes, int32_t phased,
+                                  const int32_t *sub_idx, int32_t n_sub, double *const *ld_out, int32_t where);
+int garlic_ld_finish_multi(garlic_panel *panel, const int32_t *winsizes, int32_t n_sizes, int32_t phased,
+                           const int32_t *locus_counts, const int32_t *pair_counts /* of garlic_ld_counts at max(winsizes) */,
+                           double *const *ld_out, int32_t where);
+int garlic_panel_ld_info(garlic_panel *panel, int32_t cap, int32_t *winsizes, int32_t *groups, int32_t *n_installed,
+                         int64_t *weight_bytes, int32_t *n_pair_passes, int32_t *n_sum_passes);
 
 /* A panel keeps its device scratch between calls (LD counting and summing buffers: about
  * 5 x nloci x winsize x 8 bytes; the score scratch of host-output and feed calls), because at scale

@@ -18,6 +18,9 @@ likelihoods, as one garlic_lod_feed(use_gl) call per size and -- a library that 
 call, over the whole term matrix and under every budget of --term-budgets-gb: chain kernels, the whole call, chain launches,
 term slabs built, device memory around the calls (--tree for the parent commit, which times the single calls only; set
 GARLIC_TGLS_FEED_MULTI_SOLO=1 for the groups-of-one leg).
+--modes ld_multi: the LD weights (no matrix output) of every size of --winsizes on one resident panel: a loop of single
+garlic_panel_compute_ld calls and, where the library has it, one garlic_panel_compute_ld_multi call (--tree for the parent
+commit, which times the loop only; several lists separated by ";" share one panel; profiles/ld_multi_ab.txt).
 """
 import argparse
 import json
@@ -258,6 +261,68 @@ def tgls_feed_multi_leg(args):
             leg("one multi call", multi, gb)
 
 
+def ld_multi_leg(args):
+    """Host clock around the synchronous calls, weights only (no LD matrix leaves the device); the device memory in use after
+    each leg and, for the multi call, the bytes the installed sets hold and the passes it ran."""
+    import time
+    import torch
+    from garlic_amd import abi, synth
+
+    torch.cuda.set_device(0)
+    dev = torch.device("cuda", 0)
+    nloci, nind = args.snps, args.inds
+    size_lists = [[int(w) for w in part.split(",")] for part in args.winsizes.split(";")]      # several lists: one panel for all
+    spec = synth.PanelSpec(nloci, seed=20260105, max_gap=200000)
+    ctx = abi.Context(0)
+    panel = abi.Panel(ctx, spec.chr_nloci, nind)
+    panel.set_map(spec.pos, spec.centro_start, spec.centro_end, gpos=spec.gpos)
+    panel.set_freq(spec.freq)
+    for l0, g in synth.genotype_chunks(spec, nind, dev):
+        torch.cuda.synchronize()
+        panel.set_genotypes_device(g.data_ptr(), g.shape[1], l0, g.shape[0])
+    del g
+    torch.cuda.empty_cache()
+
+    def used():
+        free_b, total_b = torch.cuda.mem_get_info()
+        return int(total_b - free_b)
+
+    sizes = size_lists[0]
+
+    def singles():
+        for W in sizes:
+            panel.compute_ld(W, want_output=False)
+        return {}
+
+    def multi():
+        panel.compute_ld_multi(sizes, want_output=False)
+        installed, groups, nbytes, n_pair, n_sum = panel.ld_info()
+        return {"installed": installed, "groups": groups, "weight_bytes": nbytes, "n_pair_passes": n_pair, "n_sum_passes": n_sum}
+
+    def leg(name, call):
+        nonlocal sizes
+        line = {"mode": "ld_multi", "leg": name, "snps": nloci, "inds": nind, "winsizes": sizes, "repeats": args.steps,
+                "solo_switch": bool(os.environ.get("GARLIC_LD_MULTI_SOLO"))}
+        wall = []
+        for k in range(2 + args.steps):
+            t0 = time.perf_counter()
+            info = call()
+            dt = (time.perf_counter() - t0) * 1e3
+            if k >= 2:
+                wall.append(dt)
+        line.update({"call_ms_median": float(np.median(wall)), "call_ms_min": min(wall), "call_ms_max": max(wall),
+                     "device_memory_after_bytes": used()})
+        line.update(info)
+        print(json.dumps(line), flush=True)
+
+    for sizes_k in size_lists:
+        sizes = sizes_k
+        panel.release_scratch()
+        leg("loop of single calls", singles)
+        if hasattr(panel, "compute_ld_multi"):
+            leg("one multi call", multi)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--snps", type=int, default=200000)
@@ -278,6 +343,8 @@ def main():
         return tgls_slabs_leg(args)
     if args.modes == "tgls_feed_multi":
         return tgls_feed_multi_leg(args)
+    if args.modes == "ld_multi":
+        return ld_multi_leg(args)
     if args.modes in ("wlod_feed", "tgls_feed"):
         return wlod_feed_leg(args, tgls=args.modes == "tgls_feed")
 
