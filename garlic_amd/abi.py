@@ -16,6 +16,7 @@ OK, ERR_INVALID, ERR_HIP, ERR_STATE, ERR_NOMEM = 0, 1, 2, 3, 4
 HOST, DEVICE = 0, 1
 FEED_FROM_SCORES, FEED_CHAIN, FEED_SAMPLED_WLOD, FEED_TGLS_CHAIN = 0, 1, 2, 3   # garlic_lod_feed_info
 FEED_TGLS_CHAIN_SHARED = 4   # garlic_lod_feed_multi_info: the size shared its chain launch with another size
+FEED_ORDER_REFERENCE, FEED_ORDER_SORTED = 0, 1   # garlic_panel_set_feed_order
 MISSING = -9999.0
 
 # every symbol include/garlic_hip.h declares (tests check the library exports them all)
@@ -37,6 +38,7 @@ SYMBOLS = [
     "garlic_panel_set_tgls_term_budget", "garlic_panel_tgls_terms_info",
     "garlic_lod_feed_multi_tgls", "garlic_lod_feed_multi_info",
     "garlic_panel_compute_ld_multi", "garlic_ld_finish_multi", "garlic_panel_ld_info",
+    "garlic_panel_set_feed_order", "garlic_feed_sort", "garlic_feed_sort_info",
 ]
 
 
@@ -133,6 +135,9 @@ def lib():
     L.garlic_panel_compute_ld_multi.argtypes = [_vp, _i32p, C.c_int32, C.c_int32, _i32p, C.c_int32, C.POINTER(_vp), C.c_int32]
     L.garlic_ld_finish_multi.argtypes = [_vp, _i32p, C.c_int32, C.c_int32, _vp, _vp, C.POINTER(_vp), C.c_int32]
     L.garlic_panel_ld_info.argtypes = [_vp, C.c_int32, _i32p, _i32p, _i32p, _i64p, _i32p, _i32p]
+    L.garlic_panel_set_feed_order.argtypes = [_vp, C.c_int32]
+    L.garlic_feed_sort.argtypes = [_vp, _vp, C.c_int64, C.c_int32]
+    L.garlic_feed_sort_info.argtypes = [_vp, _i32p, _i32p, _i64p]
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int and name not in ("garlic_hip_abi_version",):
@@ -185,6 +190,24 @@ class Context:
         a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
         check(lib().garlic_device_alloc_stats(self.handle, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
+
+    def feed_sort(self, values, n=None):
+        """garlic_feed_sort: ascending order in place (the array nrd0's gsl_sort leaves; key order in garlic_hip.h).
+        values: a contiguous float64 numpy array (host; n defaults to its length) or a device address (int) of n doubles."""
+        if isinstance(values, np.ndarray):
+            assert values.dtype == np.float64 and values.flags["C_CONTIGUOUS"] and values.ndim == 1
+            n = values.shape[0] if n is None else int(n)
+            assert n <= values.shape[0]
+            check(lib().garlic_feed_sort(self.handle, _vp(values.ctypes.data), n, HOST))
+        else:
+            check(lib().garlic_feed_sort(self.handle, _vp(values) if values else None, int(n), DEVICE))
+        return values
+
+    def feed_sort_info(self):
+        """garlic_feed_sort_info: {passes_run, passes_skipped, scratch_bytes} of the last sort on this context"""
+        run, skipped, nbytes = C.c_int32(), C.c_int32(), C.c_int64()
+        check(lib().garlic_feed_sort_info(self.handle, C.byref(run), C.byref(skipped), C.byref(nbytes)))
+        return {"passes_run": run.value, "passes_skipped": skipped.value, "scratch_bytes": nbytes.value}
 
     def close(self):
         if self.handle:
@@ -307,6 +330,11 @@ class Panel:
         values = np.ascontiguousarray(values, dtype=np.float64)
         check(lib().garlic_panel_set_gl_codes(self.handle, _vp(codes.ctypes.data), codes.shape[1], locus_begin,
                                               codes.shape[0], _vp(values.ctypes.data), values.shape[0], HOST))
+
+    def set_feed_order(self, order):
+        """garlic_panel_set_feed_order: FEED_ORDER_REFERENCE (chromosome -> individual -> locus, the default) or
+        FEED_ORDER_SORTED (every feed call returns its values ascending, sorted on the device)"""
+        check(lib().garlic_panel_set_feed_order(self.handle, int(order)))
 
     def release_scratch(self):
         """free the device scratch the panel keeps between calls (LD buffers, score / feed scratch)"""

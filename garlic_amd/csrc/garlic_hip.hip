@@ -19,6 +19,7 @@
 #include "roh_segments_kernel.hpp"
 #include "feed_kernel.hpp"
 #include "wlod_feed_kernel.hpp"
+#include "feed_sort_kernel.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -109,6 +110,15 @@ template <class T> struct DevBuf : NoCopy {
     }
 };
 
+// what one feed sorter keeps between calls (feed_sort_kernel.hpp): the second key buffer, the tile counts, the digit table
+struct FeedSortScratch {
+    DevBuf<double> keys, stage;                    // stage: the keys of a host-buffer garlic_feed_sort
+    DevBuf<unsigned long long> tiles;
+    DevBuf<FsTable> table;
+    size_t bytes() const { return keys.cap * sizeof(double) + tiles.cap * sizeof(unsigned long long) + table.cap * sizeof(FsTable); }
+    void release() { keys.release(); stage.release(); tiles.release(); table.release(); }
+};
+
 // lod(), src/garlic-roh.cpp:355-386.  Host arithmetic, host libm: identical to the reference.
 double host_lod(int genotype, double freq, double error)
 {
@@ -165,6 +175,10 @@ struct garlic_ctx {
     // the device's log10 with the host's: 0 not run yet, 1 identical on every probe, -1 differs
     DevBuf<double> d_logtab;
     int log10_state = 0;
+    // garlic_feed_sort: its scratch, and what garlic_feed_sort_info reports (the last sort, a feed call's included)
+    FeedSortScratch fs;
+    int32_t fs_run = 0, fs_skipped = 0;
+    int64_t fs_scratch_bytes = 0;
 };
 
 static int score_alloc(garlic_ctx *ctx, size_t bytes, void **out);   // pooled score memory (below)
@@ -345,6 +359,8 @@ struct garlic_panel {
     } d_out;
     bool placing = false;                          // inside the placement probe of d_out
     DevBuf<double> d_feed;
+    int32_t feed_order = GARLIC_FEED_ORDER_REFERENCE;   // garlic_panel_set_feed_order
+    FeedSortScratch fs;                            // ... SORTED: the sorter's scratch of the single-size feed calls
     // garlic_lod_feed_multi: one set of scratch and one stream per window size of the call, kept for the next call
     struct FeedSlot {
         hipStream_t stream = nullptr;
@@ -354,6 +370,7 @@ struct garlic_panel {
         DevBuf<int32_t> counter;
         DevBuf<int64_t> row_counts;
         DevBuf<double> out, feed;
+        FeedSortScratch fs;
     };
     std::vector<FeedSlot *> feed_slots;
     // garlic_lod_feed_multi_tgls: work lists of all groups, the sizes' ChrDev tables (by size; by group and place in it), one
@@ -3396,6 +3413,11 @@ int garlic_panel_release_scratch(garlic_panel *p)
     p->lds.release();
     p->d_out.release(); p->d_feed.release();
     p->d_stage16.release(); p->d_stage64.release();
+    p->fs.release(); p->ctx->fs.release();
+    for (auto *sl : p->feed_slots) {
+        HIP_TRY(hipStreamSynchronize(sl->stream));
+        sl->fs.release();
+    }
     return GARLIC_OK;
 }
 
@@ -3450,6 +3472,56 @@ int garlic_wlod_windows(garlic_panel *p, int32_t winsize, double error, int32_t 
     p->wlod_use_gl = use_gl != 0;
     return launch_lod(p, MODE_WLOD, winsize, error, max_gap, M, mu, ind_begin, ind_count, pitch_align,
                       out, where);
+}
+
+// ---- The feed in ascending order (feed_sort_kernel.hpp): nrd0's gsl_sort, src/garlic-kde.cpp:132.
+// sort_reserve: everything the sort of n keys needs, before anything is enqueued (out of memory: nothing was touched).
+static int sort_reserve(FeedSortScratch &fs, int64_t n)
+{
+    const int64_t n_tiles = (n + FS_TILE - 1) / FS_TILE;
+    if (n_tiles > 0x7fffffff) return fail(GARLIC_ERR_INVALID, "feed sort: %lld keys are more tiles than one launch holds", (long long)n);
+    int rc;
+    if ((rc = fs.keys.reserve((size_t)n)) || (rc = fs.tiles.reserve((size_t)n_tiles * 256)) || (rc = fs.table.reserve(1))) return rc;
+    return GARLIC_OK;
+}
+
+// The one sort step: `buf` (device, n > 1 doubles) sorted on stream s, every kernel enqueued at once -- the passes decide on
+// the device which of them run.  copy_back: the result always ends in buf (a device copy when an odd number of passes
+// ran); else it ends where sort_result says.
+static int sort_feed(garlic_ctx *ctx, hipStream_t s, double *buf, int64_t n, FeedSortScratch &fs, bool copy_back)
+{
+    int rc;
+    if ((rc = sort_reserve(fs, n))) return rc;
+    const int64_t n_tiles = (n + FS_TILE - 1) / FS_TILE;
+    FsTable *tab = fs.table.p;
+    HIP_TRY(hipMemsetAsync(tab, 0, sizeof(FsTable), s));
+    const int64_t rounds = (n + FS_HIST_KEYS - 1) / FS_HIST_KEYS;
+    hipLaunchKernelGGL(fs_hist_kernel, dim3((unsigned)std::min<int64_t>(rounds, 8 * (int64_t)ctx->n_cu)), dim3(FS_THREADS), 0, s, buf, n, tab);
+    hipLaunchKernelGGL(fs_plan_kernel, dim3(1), dim3(256), 0, s, tab, n);
+    for (int pass = 0; pass < 8; pass++) {
+        hipLaunchKernelGGL(fs_count_kernel, dim3((unsigned)n_tiles), dim3(FS_THREADS), 0, s, buf, fs.keys.p, n, n_tiles, pass, tab, fs.tiles.p);
+        hipLaunchKernelGGL(fs_scan_kernel, dim3(256), dim3(FS_SCAN_THREADS), 0, s, n_tiles, pass, tab, fs.tiles.p);
+        hipLaunchKernelGGL(fs_scatter_kernel, dim3((unsigned)n_tiles), dim3(FS_THREADS), 0, s, buf, fs.keys.p, n, n_tiles, pass, tab, fs.tiles.p);
+    }
+    if (copy_back)
+        hipLaunchKernelGGL(fs_copy_back_kernel, dim3((unsigned)std::min<int64_t>((n + FS_THREADS - 1) / FS_THREADS, 16 * (int64_t)ctx->n_cu)),
+                           dim3(FS_THREADS), 0, s, buf, fs.keys.p, n, tab);
+    HIP_TRY(hipGetLastError());
+    ctx->fs_scratch_bytes = (int64_t)fs.bytes();
+    return GARLIC_OK;
+}
+
+// Waits for the sort on stream s; *from: the buffer that holds the sorted keys (buf or the scratch).  Notes the pass
+// counts for garlic_feed_sort_info.
+static int sort_result(garlic_ctx *ctx, hipStream_t s, double *buf, FeedSortScratch &fs, const double **from)
+{
+    int32_t tail[2] = {0, 0};       // FsTable::n_run, in_scratch
+    HIP_TRY(hipMemcpyAsync(tail, &fs.table.p->n_run, sizeof tail, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    ctx->fs_run = tail[0];
+    ctx->fs_skipped = 8 - tail[0];
+    if (from) *from = tail[1] ? fs.keys.p : buf;
+    return GARLIC_OK;
 }
 
 // thinned > 0: `scores` is already the thinned matrix of make_layout(.., thinned) (every column is a
@@ -3579,7 +3651,12 @@ static int feed_single(garlic_panel *p, int32_t winsize, double error, int32_t m
         return rc;
     if (*count > feed_capacity || *count == 0) return GARLIC_OK;
     if (!feed) return fail(GARLIC_ERR_INVALID, "feed is NULL");
-    hipError_t e = hipMemcpy(feed, d_feed.p, sizeof(double) * (size_t)*count, hipMemcpyDeviceToHost);
+    const double *from = d_feed.p;
+    if (p->feed_order == GARLIC_FEED_ORDER_SORTED && *count > 1) {
+        if ((rc = sort_feed(p->ctx, p->ctx->stream, d_feed.p, *count, p->fs, false))) return rc;
+        if ((rc = sort_result(p->ctx, p->ctx->stream, d_feed.p, p->fs, &from))) return rc;
+    }
+    hipError_t e = hipMemcpy(feed, from, sizeof(double) * (size_t)*count, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "feed copy-out: %s", hipGetErrorString(e));
     return GARLIC_OK;
 }
@@ -3688,6 +3765,7 @@ int garlic_lod_feed_multi(garlic_panel *p, const int32_t *winsizes, const int32_
         hipError_t e_ = (expr);                                                                     \
         if (e_ != hipSuccess) return done(fail(GARLIC_ERR_HIP, "feed: %s: %s", #expr, hipGetErrorString(e_))); \
     } while (0)
+    const bool sorted = p->feed_order == GARLIC_FEED_ORDER_SORTED;
     if (ind_idx) {
         blocks.assign((size_t)nblk, 0);
         row_map.assign((size_t)p->nind, -1);
@@ -3746,6 +3824,7 @@ int garlic_lod_feed_multi(garlic_panel *p, const int32_t *winsizes, const int32_
         if ((rc = sl.chrs.reserve((size_t)p->nchr))) return done(rc);
         if ((rc = sl.counter.reserve(4))) return done(rc);
         if ((rc = sl.feed.reserve((size_t)off))) return done(rc);
+        if (sorted && off > 1 && (rc = sort_reserve(sl.fs, off))) return done(rc);
         FEED_TRY(hipMemcpy(sl.chrs.p, chrs.data(), sizeof(ChrDev) * (size_t)p->nchr, hipMemcpyHostToDevice));
         if (!items.empty()) FEED_TRY(hipMemcpy(sl.items.p, items.data(), sizeof(FeedItem) * items.size(), hipMemcpyHostToDevice));
         FEED_TRY(hipMemset(sl.counter.p, 0, 2 * sizeof(int32_t)));
@@ -3764,12 +3843,17 @@ int garlic_lod_feed_multi(garlic_panel *p, const int32_t *winsizes, const int32_
         }
         FEED_TRY(hipEventRecord(sl.ev1, sl.stream));
         FEED_TRY(hipGetLastError());
+        // ascending order: the sort follows the chain on the size's own stream, nothing is waited for here
+        if (sorted && n_items[(size_t)i] && total[(size_t)i] > 1 && (rc = sort_feed(ctx, sl.stream, sl.feed.p, total[(size_t)i], sl.fs, false)))
+            return done(rc);
     }
     // ---- the feeds, in order
     for (int i = 0; i < n_sizes; i++) {
         garlic_panel::FeedSlot &sl = *p->feed_slots[(size_t)i];
-        if (n_items[(size_t)i])
-            FEED_TRY(hipMemcpyAsync(feeds[i], sl.feed.p, sizeof(double) * (size_t)total[(size_t)i], hipMemcpyDeviceToHost, sl.stream));
+        if (!n_items[(size_t)i]) continue;
+        const double *from = sl.feed.p;
+        if (sorted && total[(size_t)i] > 1 && (rc = sort_result(ctx, sl.stream, sl.feed.p, sl.fs, &from))) return done(rc);
+        FEED_TRY(hipMemcpyAsync(feeds[i], from, sizeof(double) * (size_t)total[(size_t)i], hipMemcpyDeviceToHost, sl.stream));
     }
     float ms_sum = 0.f;
     for (int i = 0; i < n_sizes; i++) {
@@ -4020,6 +4104,7 @@ int garlic_lod_feed_multi_tgls(garlic_panel *p, const int32_t *winsizes, const i
         FEED_TRY(hipEventRecord(p->feed_slots[0]->ev1, s));
         // ---- per size, on its own stream: the samples of every (chromosome, listed individual) counted
         std::vector<std::vector<int64_t>> row_counts((size_t)n_sizes);
+        std::vector<int64_t> sort_n((size_t)n_sizes, 0);     // sizes whose feed is being sorted: its length
         const int n_flat = p->nchr * nrows;
         for (const Group &g : G)
             for (int i : g.sizes) {
@@ -4052,7 +4137,20 @@ int garlic_lod_feed_multi_tgls(garlic_panel *p, const int32_t *winsizes, const i
                 hipLaunchKernelGGL(feed_write_kernel, dim3((unsigned)n_flat), dim3(WAVE), 0, sl.stream, sl.out.p,
                                    p->d_multi_chrs.p + (size_t)i * p->nchr, p->nchr, nrows, ind_idx ? d_list.p : nullptr, 1, sl.row_counts.p,
                                    sl.feed.p);
+                if (p->feed_order == GARLIC_FEED_ORDER_SORTED && total > 1) {      // fetched below, once every size's sort is enqueued
+                    if ((rc = sort_feed(ctx, sl.stream, sl.feed.p, total, sl.fs, false))) return done(rc);
+                    sort_n[(size_t)i] = total;
+                    continue;
+                }
                 FEED_TRY(hipMemcpyAsync(feeds[i], sl.feed.p, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, sl.stream));
+            }
+        for (const Group &g : G)
+            for (int i : g.sizes) {
+                if (!sort_n[(size_t)i]) continue;
+                garlic_panel::FeedSlot &sl = *p->feed_slots[(size_t)i];
+                const double *from = sl.feed.p;
+                if ((rc = sort_result(ctx, sl.stream, sl.feed.p, sl.fs, &from))) return done(rc);
+                FEED_TRY(hipMemcpyAsync(feeds[i], from, sizeof(double) * (size_t)sort_n[(size_t)i], hipMemcpyDeviceToHost, sl.stream));
             }
         for (const Group &g : G)
             for (int i : g.sizes) FEED_TRY(hipStreamSynchronize(p->feed_slots[(size_t)i]->stream));
@@ -4730,6 +4828,53 @@ int garlic_panel_alloc_scores_info(garlic_panel *p, int32_t *drawn, int32_t *rou
     if (worst_ms) *worst_ms = p->placement.worst_ms;
     if (target_ms) *target_ms = p->placement.target_ms;
     if (reached_target) *reached_target = p->placement.reached;
+    return GARLIC_OK;
+}
+
+int garlic_panel_set_feed_order(garlic_panel *p, int32_t order)
+{
+    if (!p) return fail(GARLIC_ERR_INVALID, "panel is NULL");
+    if (order != GARLIC_FEED_ORDER_REFERENCE && order != GARLIC_FEED_ORDER_SORTED)
+        return fail(GARLIC_ERR_INVALID, "feed order must be GARLIC_FEED_ORDER_REFERENCE or GARLIC_FEED_ORDER_SORTED (got %d)", order);
+    p->feed_order = order;
+    return GARLIC_OK;
+}
+
+int garlic_feed_sort(garlic_ctx *ctx, double *values, int64_t n, int32_t where)
+{
+    if (!ctx) return fail(GARLIC_ERR_INVALID, "context is NULL");
+    if (n < 0) return fail(GARLIC_ERR_INVALID, "feed sort: n must be >= 0 (got %lld)", (long long)n);
+    if (n > 0 && !values) return fail(GARLIC_ERR_INVALID, "feed sort: values is NULL");
+    if (where != GARLIC_HOST && where != GARLIC_DEVICE) return fail(GARLIC_ERR_INVALID, "feed sort: where must be GARLIC_HOST or GARLIC_DEVICE");
+    int rc;
+    if ((rc = set_device(ctx))) return rc;
+    if (n <= 1) {                                    // nothing to order
+        ctx->fs_run = 0;
+        ctx->fs_skipped = 8;
+        ctx->fs_scratch_bytes = (int64_t)ctx->fs.bytes();
+        return GARLIC_OK;
+    }
+    hipStream_t s = ctx->stream;
+    if ((rc = sort_reserve(ctx->fs, n))) return rc;   // before the caller's data is touched
+    if (where == GARLIC_DEVICE) {
+        if ((rc = sort_feed(ctx, s, values, n, ctx->fs, true))) return rc;
+        return sort_result(ctx, s, values, ctx->fs, nullptr);
+    }
+    if ((rc = ctx->fs.stage.reserve((size_t)n))) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->fs.stage.p, values, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
+    if ((rc = sort_feed(ctx, s, ctx->fs.stage.p, n, ctx->fs, false))) return rc;
+    const double *from = nullptr;
+    if ((rc = sort_result(ctx, s, ctx->fs.stage.p, ctx->fs, &from))) return rc;
+    HIP_TRY(hipMemcpy(values, from, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+    return GARLIC_OK;
+}
+
+int garlic_feed_sort_info(garlic_ctx *ctx, int32_t *passes_run, int32_t *passes_skipped, int64_t *scratch_bytes)
+{
+    if (!ctx) return fail(GARLIC_ERR_INVALID, "context is NULL");
+    if (passes_run) *passes_run = ctx->fs_run;
+    if (passes_skipped) *passes_skipped = ctx->fs_skipped;
+    if (scratch_bytes) *scratch_bytes = ctx->fs_scratch_bytes;
     return GARLIC_OK;
 }
 

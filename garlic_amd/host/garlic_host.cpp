@@ -1107,6 +1107,18 @@ std::vector<WinData *> *LodEngine::wlodWindowsResident(int winsize, double error
     return run(true, winsize, error, MAX_GAP, M, mu);
 }
 
+// LodOptions::feed_sorted: the shards' ascending feeds into `out` (feed_merge.hpp)
+static void mergeShardFeeds(const std::vector<std::vector<double>> &feeds, double *out)
+{
+    std::vector<const double *> parts;
+    std::vector<int64_t> sizes;
+    for (const auto &f : feeds) {
+        parts.push_back(f.data());
+        sizes.push_back((int64_t)f.size());
+    }
+    mergeSortedFeeds(parts, sizes, out);
+}
+
 DoubleData *LodEngine::lodFeed(int winsize, double error, int MAX_GAP, int step, bool weighted, int M, double mu,
                                const std::vector<int> *kdeSubsample)
 {
@@ -1120,6 +1132,7 @@ DoubleData *LodEngine::lodFeed(int winsize, double error, int MAX_GAP, int step,
     if (subset)
         for (size_t i = 1; i < kdeSubsample->size(); i++)
             if ((*kdeSubsample)[i] <= (*kdeSubsample)[i - 1]) fail("KDE subsample must be in increasing order");
+    const bool sorted = g_options.feed_sorted;
     std::vector<std::vector<double>> feeds(ns);
     std::vector<std::vector<int64_t>> per_chr(ns, std::vector<int64_t>(nchr, 0));
     std::vector<std::string> errors(ns);
@@ -1137,7 +1150,8 @@ DoubleData *LodEngine::lodFeed(int winsize, double error, int MAX_GAP, int step,
             int64_t cap = 0, n = 0;
             for (int c = 0; c < nchr; c++) cap += ((int64_t)impl->chr_nloci[c] + step - 1) / step * rows;
             feeds[k].resize((size_t)std::max<int64_t>(cap, 1));
-            if (garlic_lod_feed_subset(s.panel, winsize, error, MAX_GAP, impl->use_gl, weighted, M, mu, step,
+            if (garlic_panel_set_feed_order(s.panel, sorted ? GARLIC_FEED_ORDER_SORTED : GARLIC_FEED_ORDER_REFERENCE) != GARLIC_OK ||
+                garlic_lod_feed_subset(s.panel, winsize, error, MAX_GAP, impl->use_gl, weighted, M, mu, step,
                                        subset ? mine.data() : nullptr, (int32_t)mine.size(), feeds[k].data(), cap, &n,
                                        per_chr[k].data()) != GARLIC_OK)
                 errors[k] = garlic_hip_last_error();
@@ -1154,6 +1168,10 @@ DoubleData *LodEngine::lodFeed(int winsize, double error, int MAX_GAP, int step,
     DoubleData *d = new DoubleData;
     d->size = (int)total;
     d->data = new double[total > 0 ? total : 1];
+    if (sorted) {       // every shard's feed is ascending: their merge is the ascending feed of the whole panel
+        mergeShardFeeds(feeds, d->data);
+        return d;
+    }
     std::vector<int64_t> off(ns, 0);
     int64_t o = 0;
     for (int c = 0; c < nchr; c++)
@@ -1303,6 +1321,7 @@ std::vector<DoubleData *> LodEngine::lodFeedMulti(const std::vector<int> &winsiz
     if (subset)
         for (size_t i = 1; i < kdeSubsample->size(); i++)
             if ((*kdeSubsample)[i] <= (*kdeSubsample)[i - 1]) fail("KDE subsample must be in increasing order");
+    const bool sorted = g_options.feed_sorted;
     std::vector<int32_t> W32(winsizes.begin(), winsizes.end()), S32(nw);
     for (size_t i = 0; i < nw; i++) S32[i] = steps ? (*steps)[i] : winsizes[i];
     // feeds[shard][size], per_chr[shard][size * nchr + c]
@@ -1327,7 +1346,9 @@ std::vector<DoubleData *> LodEngine::lodFeedMulti(const std::vector<int> &winsiz
                 feeds[k][i].resize((size_t)std::max<int64_t>(cap[i], 1));
                 ptrs[i] = feeds[k][i].data();
             }
-            const int rc = impl->use_gl
+            int rc = garlic_panel_set_feed_order(s.panel, sorted ? GARLIC_FEED_ORDER_SORTED : GARLIC_FEED_ORDER_REFERENCE);
+            if (rc == GARLIC_OK)
+                rc = impl->use_gl
                                ? garlic_lod_feed_multi_tgls(s.panel, W32.data(), S32.data(), (int32_t)nw, MAX_GAP, subset ? mine.data() : nullptr,
                                                             (int32_t)mine.size(), ptrs.data(), cap.data(), n.data(), per_chr[k].data())
                                : garlic_lod_feed_multi(s.panel, W32.data(), S32.data(), (int32_t)nw, error, MAX_GAP, subset ? mine.data() : nullptr,
@@ -1349,6 +1370,13 @@ std::vector<DoubleData *> LodEngine::lodFeedMulti(const std::vector<int> &winsiz
         DoubleData *d = new DoubleData;
         d->size = (int)total;
         d->data = new double[total > 0 ? total : 1];
+        out[i] = d;
+        if (sorted) {
+            std::vector<std::vector<double>> of_size(ns);
+            for (size_t k = 0; k < ns; k++) of_size[k].swap(feeds[k][i]);
+            mergeShardFeeds(of_size, d->data);
+            continue;
+        }
         std::vector<int64_t> off(ns, 0);
         int64_t o = 0;
         for (int c = 0; c < nchr; c++)
@@ -1358,7 +1386,6 @@ std::vector<DoubleData *> LodEngine::lodFeedMulti(const std::vector<int> &winsiz
                 o += m;
                 off[k] += m;
             }
-        out[i] = d;
     }
     return out;
 }

@@ -14,6 +14,8 @@
 #include <string>
 #include <vector>
 
+#include "feed_merge.hpp"
+
 namespace garlic_host {
 
 const int MISSING = -9999; // src/garlic-data.h:24
@@ -207,6 +209,10 @@ struct LodOptions {
     // garlic_panel_set_tgls_term_budget for every shard's panel (dictionary-coded likelihoods): 0 the whole term matrix or
     // none, > 0 bytes (the matrix in slabs when it is larger), -1 whole if it fits, else slabs from the free memory
     long long tgls_term_bytes = 0;
+    // LodEngine::lodFeed / lodFeedMulti return every feed ascending instead of in the reference's chromosome -> individual
+    // -> locus order: the array nrd0's gsl_sort (garlic-kde.cpp:132) would make of it.  Sorted on the devices
+    // (garlic_panel_set_feed_order on every shard's panel), the shards' arrays merged on the host (feed_merge.hpp).
+    bool feed_sorted = false;
 };
 void setLodOptions(const LodOptions &o);
 

@@ -5,9 +5,13 @@
 //   <out>.<W>SNPs.lod.f64                  the KDE feed: convertWinData2DoubleData's doubles
 //                                          (src/garlic-data.cpp:2026), thinned to every W-th window
 //                                          unless --no-kde-thinning
+//   <out>.<W>SNPs.lod.sorted.f64           instead, with --sorted-feed: the same doubles ascending -- the array
+//                                          computeKDE's nrd0 makes of the feed first (gsl_sort, src/garlic-kde.cpp:132),
+//                                          sorted on the device
 // KDE / ROH assembly / GMM themselves stay in GARLIC (out of scope here).
 #include "garlic_host.hpp"
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -27,6 +31,7 @@ struct Args {
     int winsize = 0;               // :38
     std::vector<int> winsize_multi;
     bool auto_winsize = false, weighted = false, raw_lod = false, kde_thinning = true, phased = false;
+    bool sorted_feed = false;      // extension: the feeds ascending, <out>.<W>SNPs.lod.sorted.f64 (the device sorts them)
     bool winsize_stream = false;   // extension: further window sizes from stdin (the loop of selectWinsize, driven by the KDE's owner)
     int auto_winsize_step = 10, max_gap = 200000, M = 7, threads = 1, kde_subsample = 20, gpus = 1;
     std::vector<int> devices;      // --devices; empty = 0 .. gpus-1
@@ -51,6 +56,7 @@ struct Args {
                  "         [--freq-file F] [--tped-missing C] [--raw-lod] [--kde-subsample N] [--kde-seed S] [--no-kde-thinning]\n"
                  "         [--weighted --map F --M N --mu X --ld-subsample N --ld-seed S --threads N]\n"
                  "         [--resample N --resample-seed S] [--gpus N | --devices 0,1,...] [--genotype-cache F] [--tgls-term-gb X]\n"
+                 "         [--sorted-feed]   (the KDE feeds ascending, as nrd0's gsl_sort leaves them: <out>.<W>SNPs.lod.sorted.f64)\n"
                  "         [--lod-cutoff X --size-bounds B1 B2 ... [--cm]]   (ROH calls: <out>.roh.bed)\n";
     exit(1);
 }
@@ -80,6 +86,7 @@ Args parse(int argc, char **argv)
         else if (f == "--auto-winsize") a.auto_winsize = !a.auto_winsize; // bool flags toggle (param_t.cpp:278)
         else if (f == "--auto-winsize-step") a.auto_winsize_step = atoi(val().c_str());
         else if (f == "--winsize-stream") a.winsize_stream = !a.winsize_stream;
+        else if (f == "--sorted-feed") a.sorted_feed = !a.sorted_feed;
         else if (f == "--max-gap") a.max_gap = atoi(val().c_str());
         else if (f == "--overlap-frac") a.overlap_frac = atof(val().c_str());
         else if (f == "--weighted") a.weighted = !a.weighted;
@@ -212,12 +219,15 @@ int main(int argc, char **argv)
             for (int d = 0; d < a.gpus; d++) devices.push_back(d);
 
         std::vector<int> sizes = a.winsize_multi.empty() ? std::vector<int>{a.winsize} : a.winsize_multi;
-        if (a.tgls_term_gb != 0) {   // per device: the TGLS term matrix in slabs when it is larger than this
+        if (a.tgls_term_gb != 0 || a.sorted_feed) {
             LodOptions lo;
             lo.devices = devices;
-            lo.tgls_term_bytes = a.tgls_term_gb < 0 ? -1 : (long long)(a.tgls_term_gb * 1e9);
+            // per device: the TGLS term matrix in slabs when it is larger than this
+            if (a.tgls_term_gb != 0) lo.tgls_term_bytes = a.tgls_term_gb < 0 ? -1 : (long long)(a.tgls_term_gb * 1e9);
+            lo.feed_sorted = a.sorted_feed;      // every feed of the engine arrives ascending
             setLodOptions(lo);
         }
+        auto feed_file = [&](int W) { return a.out + "." + std::to_string(W) + (a.sorted_feed ? "SNPs.lod.sorted.f64" : "SNPs.lod.f64"); };
         LodEngine engine(haps, freqs, maps, gls, &centro, USE_GL, devices); // one upload, many window sizes
         const std::vector<int> ldsub = a.weighted ? drawLdSubsample(numInd, a.ld_subsample, a.ld_seed) : std::vector<int>();
         // selectLODCutoff (garlic-roh.cpp:674-675): the KDE sees --kde-subsample individuals (default 20,
@@ -235,7 +245,7 @@ int main(int argc, char **argv)
             for (int W : sizes) steps.push_back(a.kde_thinning ? W : 1);
             std::vector<DoubleData *> feeds = engine.lodFeedMulti(sizes, a.error, a.max_gap, &steps, &kdesub);
             for (size_t i = 0; i < sizes.size(); i++) {
-                writeFeed(a.out + "." + std::to_string(sizes[i]) + "SNPs.lod.f64", feeds[i]);
+                writeFeed(feed_file(sizes[i]), feeds[i]);
                 releaseDoubleData(feeds[i]);
             }
             sizes.clear();
@@ -264,7 +274,7 @@ int main(int argc, char **argv)
         for (int W : sizes) {
             if (a.weighted && !ld_shared) engine.ldWeights(W, ldsub, false, a.phased);   // garlic-main.cpp:346-357: LD weights per window size
             if (a.weighted) roh_calls(W, single_size);
-            const std::string feed_path = a.out + "." + std::to_string(W) + "SNPs.lod.f64";
+            const std::string feed_path = feed_file(W);
             if (!a.raw_lod) {   // only the KDE feed is wanted: thin on the device, no full-score download
                 DoubleData *feed = engine.lodFeed(W, a.error, a.max_gap, a.kde_thinning ? W : 1, a.weighted, a.M, a.mu, &kdesub);
                 writeFeed(feed_path, feed);
@@ -276,6 +286,7 @@ int main(int argc, char **argv)
             writeWinData(win, ind, maps, sizes.size() == 1 ? a.out : a.out + "." + std::to_string(W) + "SNPs");
             DoubleData *feed = kdesub.empty() ? convertWinData2DoubleData(win, a.kde_thinning ? W : 1)
                                               : convertSubsetWinData2DoubleData(win, kdesub, a.kde_thinning ? W : 1);
+            if (a.sorted_feed) std::sort(feed->data, feed->data + feed->size);   // host scores: the same file as the device's sort
             writeFeed(feed_path, feed);
             releaseDoubleData(feed);
             releaseWinData(win);
@@ -296,7 +307,7 @@ int main(int argc, char **argv)
                 if (W <= 1) { std::cerr << "ERROR: SNP window size must be > 1.\n"; return 1; }
                 if (a.weighted) engine.ldWeights(W, ldsub, false, a.phased);
                 DoubleData *feed = engine.lodFeed(W, a.error, a.max_gap, a.kde_thinning ? W : 1, a.weighted, a.M, a.mu, &kdesub);
-                const std::string path = a.out + "." + std::to_string(W) + "SNPs.lod.f64";
+                const std::string path = feed_file(W);
                 writeFeed(path, feed);
                 std::cout << "FEED " << W << " " << path << " " << feed->size << std::endl;
                 releaseDoubleData(feed);

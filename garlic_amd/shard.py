@@ -99,3 +99,33 @@ def allreduce_ld_counts(locus_counts, pair_counts, group=None):
         dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
         outs.append(t if isinstance(a, torch.Tensor) else t.numpy())
     return outs[0], outs[1]
+
+
+def feed_sort_key(values):
+    """The sorted feed's key (include/garlic_hip.h): uint64 whose unsigned order is the numeric order of the doubles, -0.0
+    in front of +0.0."""
+    b = np.ascontiguousarray(values, dtype=np.float64).view(np.uint64)
+    return b ^ np.where(b >> np.uint64(63) != 0, np.uint64(0xFFFFFFFFFFFFFFFF), np.uint64(0x8000000000000000))
+
+
+def merge_sorted_feeds(feeds):
+    """feeds: the ascending KDE feeds of the shards (Panel.set_feed_order(FEED_ORDER_SORTED)), any of them possibly empty.
+    Returns one ascending float64 array: the sorted feed of the whole panel, what nrd0's gsl_sort (src/garlic-kde.cpp:132)
+    leaves of it.  Merges, never sorts: every part is placed by its rank among the values merged so far (ties: the
+    earlier shard first)."""
+    out = np.empty(0, dtype=np.float64)
+    for f in feeds:
+        f = np.ascontiguousarray(f, dtype=np.float64)
+        if f.shape[0] == 0:
+            continue
+        if out.shape[0] == 0:
+            out = f.copy()
+            continue
+        at = np.searchsorted(feed_sort_key(out), feed_sort_key(f), side="right") + np.arange(f.shape[0])
+        merged = np.empty(out.shape[0] + f.shape[0], dtype=np.float64)
+        mask = np.ones(merged.shape[0], dtype=bool)
+        mask[at] = False
+        merged[at] = f
+        merged[mask] = out
+        out = merged
+    return out

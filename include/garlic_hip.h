@@ -49,7 +49,8 @@ extern "C" {
  *    under the same number: nothing that existed changed); GARLIC_FEED_TGLS_CHAIN (a fourth value of its form, likewise);
  *    garlic_panel_set_tgls_term_budget, garlic_panel_tgls_terms_info (likewise); garlic_lod_feed_multi_tgls,
  *    garlic_lod_feed_multi_info, GARLIC_FEED_TGLS_CHAIN_SHARED (likewise); garlic_panel_compute_ld_multi,
- *    garlic_ld_finish_multi, garlic_panel_ld_info (likewise) */
+ *    garlic_ld_finish_multi, garlic_panel_ld_info (likewise); garlic_panel_set_feed_order, garlic_feed_sort,
+ *    garlic_feed_sort_info, GARLIC_FEED_ORDER_* (likewise) */
 #define GARLIC_HIP_ABI_VERSION 8
 
 #define GARLIC_OK 0
@@ -409,6 +410,39 @@ int garlic_lod_feed_multi_tgls(garlic_panel *panel, const int32_t *winsizes, con
 #define GARLIC_FEED_TGLS_CHAIN_SHARED 4
 int garlic_lod_feed_multi_info(garlic_panel *panel, int32_t n, int32_t *forms, int32_t *groups, int32_t *n_chain_launches,
                                int32_t *n_term_builds);
+
+/* The feed in ascending order.  The consumer of every feed above is computeKDE (src/garlic-kde.cpp:14), and its first
+ * step is nrd0 (:43, :130-139), whose first statement is gsl_sort(x, 1, N) (:132) -- in place, on the feed: gsl_stats_sd,
+ * the two gsl_stats_quantile_from_sorted_data calls, gsl_stats_minmax and figtree (:81) all read the sorted array.  A
+ * single-threaded heapsort on the host, once per window size of every sweep; here an FP64 radix sort on the device
+ * between the flatten and the copy-out (csrc/feed_sort_kernel.hpp).
+ *
+ * Key order: k(x) = bits(x) ^ (bits(x) >> 63 ? 0xFFFFFFFFFFFFFFFF : 0x8000000000000000), compared as unsigned.  That is
+ * numeric ascending order for everything that is not NaN; -0.0 sorts in front of +0.0, NaNs with the sign bit set sort
+ * first and the other NaNs last, so the order is total.
+ * Why the result is the one gsl_sort leaves: a feed holds no NaN (the flatten drops them) and no -0.0 (every window sum
+ * starts from 0.0 + ..., and under round-to-nearest a + b or a - b is -0.0 only when both operands already carry that
+ * sign), so equal values are equal bit patterns and the ascending arrangement of the values is unique -- what any correct
+ * comparison sort leaves in the array, bit for bit.
+ *
+ * garlic_panel_set_feed_order: GARLIC_FEED_ORDER_SORTED makes garlic_lod_feed, _subset, _multi and _multi_tgls sort the
+ * values on the device after the flatten's write pass and before the copy to the host (the multi calls: on the size's own
+ * stream; which passes run is decided on the device, so nothing is waited for per pass).  *count, chr_counts, the
+ * behaviour when the capacity is exceeded (nothing written), garlic_lod_feed_info, garlic_lod_feed_multi_info and the
+ * kernel forms chosen are those of the reference order.  Any other value: GARLIC_ERR_INVALID.  garlic_lod_flatten (a
+ * device feed buffer of the caller's) stays in reference order; its caller uses garlic_feed_sort.
+ * garlic_feed_sort: n doubles sorted in place under the key order above; `where` GARLIC_DEVICE or GARLIC_HOST (upload,
+ * sort, download).  n = 0: nothing happens; n < 0, or a NULL pointer with n > 0: GARLIC_ERR_INVALID.  Scratch: n doubles
+ * (a host buffer: 2 n) plus 2 KB per FS_TILE keys, kept with the context -- with the panel or the size's slot for feed
+ * calls -- until garlic_panel_release_scratch; when it does not fit, GARLIC_ERR_NOMEM and the caller's data untouched.
+ * garlic_feed_sort_info: the last sort on the context, the one inside a feed call included (a multi call: the size
+ * fetched last).  A pass whose digit is the same in every key moves nothing and is skipped: passes_run + passes_skipped
+ * == 8 after any sort of n > 1 keys.  scratch_bytes: what that sorter holds.  Any pointer may be NULL. */
+#define GARLIC_FEED_ORDER_REFERENCE 0   /* chromosome -> individual -> locus (default) */
+#define GARLIC_FEED_ORDER_SORTED    1   /* ascending: the array nrd0's gsl_sort leaves (garlic-kde.cpp:132) */
+int garlic_panel_set_feed_order(garlic_panel *panel, int32_t order);
+int garlic_feed_sort(garlic_ctx *ctx, double *values, int64_t n, int32_t where);
+int garlic_feed_sort_info(garlic_ctx *ctx, int32_t *passes_run, int32_t *passes_skipped, int64_t *scratch_bytes);
 
 /* First half of assembleROHWindows (src/garlic-roh.cpp:446-454) on the device: for every individual
  * and SNP the number of windows with score >= cutoff that cover the SNP,

@@ -21,6 +21,11 @@ GARLIC_TGLS_FEED_MULTI_SOLO=1 for the groups-of-one leg).
 --modes ld_multi: the LD weights (no matrix output) of every size of --winsizes on one resident panel: a loop of single
 garlic_panel_compute_ld calls and, where the library has it, one garlic_panel_compute_ld_multi call (--tree for the parent
 commit, which times the loop only; several lists separated by ";" share one panel; profiles/ld_multi_ab.txt).
+--modes feed_sort: the sorted KDE feed (garlic_panel_set_feed_order / garlic_feed_sort) on real thinned feeds of one
+resident panel: the unweighted feed (step = winsize) of --kde-inds individuals (the --kde-subsample scale) and of
+everyone -- the device sort alone by HIP events, its bytes per second at 24 B x keys x passes run, the whole feed call in
+both orders, and on the same data one thread of std::sort and numpy's sort on the host, as stand-ins for gsl_sort
+(profiles/feed_sort_ab.txt).
 """
 import argparse
 import json
@@ -110,6 +115,90 @@ def wlod_feed_leg(args, tgls=False):
                     line["roofline"] = {"bound": "hbm", "achieved": a, "peak": 8000.0, "unit": "GB/s", "frac": a / 8000.0,
                                         "algorithmic_bytes_per_window": per_win}
                 print(json.dumps(line), flush=True)
+
+
+def feed_sort_leg(args):
+    """The context runs on a torch stream, so torch's events (HIP events) bracket exactly the sort's kernels: the
+    histogram, the plan and the passes that run (plus the 8-byte read-back of the pass count).  The feeds are the library's
+    own: their top bytes repeat, so which passes drop out is the data's doing."""
+    import ctypes
+    import subprocess
+    import tempfile
+    import time
+    import torch
+    from garlic_amd import abi, synth
+
+    torch.cuda.set_device(0)
+    dev = torch.device("cuda", 0)
+    nloci, nind, W = args.snps, args.inds, args.winsize
+    error, max_gap = 0.001, 200000
+    spec = synth.PanelSpec(nloci, seed=20260105, max_gap=max_gap)
+    stream = torch.cuda.Stream()          # (not the null stream: the context would take a NULL handle for "create one")
+    ctx = abi.Context(0, stream=stream.cuda_stream)
+    panel = abi.Panel(ctx, spec.chr_nloci, nind)
+    panel.set_map(spec.pos, spec.centro_start, spec.centro_end)
+    panel.set_freq(spec.freq)
+    for l0, g in synth.genotype_chunks(spec, nind, dev):
+        torch.cuda.synchronize()
+        panel.set_genotypes_device(g.data_ptr(), g.shape[1], l0, g.shape[0])
+    del g
+    tmp = tempfile.mkdtemp()
+    so = os.path.join(tmp, "libhost_sort.so")
+    subprocess.check_call(["g++", "-O2", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tools", "ubench", "host_sort.cpp")])
+    host = ctypes.CDLL(so)
+    host.host_std_sort_seconds.restype = ctypes.c_double
+    host.host_std_sort_seconds.argtypes = [ctypes.c_void_p, ctypes.c_int64]
+    rng = np.random.default_rng(11)
+    subsets = [np.sort(rng.choice(nind, size=min(args.kde_inds, nind), replace=False)).astype(np.int32), None]
+    for idx in subsets:
+        call = {}
+        for order, name in ((abi.FEED_ORDER_REFERENCE, "reference"), (abi.FEED_ORDER_SORTED, "sorted")):
+            panel.set_feed_order(order)
+            wall = []
+            for k in range(1 + args.steps):
+                t0 = time.perf_counter()
+                feed, _ = panel.lod_feed(W, error, max_gap, W, copy=False, ind_idx=idx)
+                if k:
+                    wall.append((time.perf_counter() - t0) * 1e3)
+            call[name] = float(np.median(wall))
+            if name == "reference":
+                ref = feed.copy()
+        n = int(ref.shape[0])
+        assert np.array_equal(feed.view(np.uint64), np.sort(ref).view(np.uint64)), "sorted feed differs from numpy's sort"
+        panel.set_feed_order(abi.FEED_ORDER_REFERENCE)
+        d_ref = torch.from_numpy(ref).to(dev)
+        ms = []
+        for k in range(1 + args.steps):
+            d = d_ref.clone()
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            ctx.feed_sort(d.data_ptr(), n=n)
+            e1.record(stream)
+            torch.cuda.synchronize()
+            if k:
+                ms.append(e0.elapsed_time(e1))
+        info = ctx.feed_sort_info()
+        assert np.array_equal(d.cpu().numpy().view(np.uint64), feed.view(np.uint64))
+        del d, d_ref
+        x = ref.copy()
+        std_s = host.host_std_sort_seconds(x.ctypes.data, n)
+        x = ref.copy()
+        t0 = time.perf_counter()
+        x.sort()
+        np_s = time.perf_counter() - t0
+        sort_ms = float(np.median(ms))
+        print(json.dumps({"mode": "feed_sort", "snps": nloci, "inds": nind, "winsize": W, "step": W,
+                          "feed_individuals": nind if idx is None else int(idx.shape[0]), "keys": n, "repeats": args.steps,
+                          "device_sort_ms_median": sort_ms, "device_sort_ms_min": min(ms), "device_sort_ms_max": max(ms),
+                          "passes_run": info["passes_run"], "passes_skipped": info["passes_skipped"],
+                          "sort_scratch_bytes": info["scratch_bytes"],
+                          "traffic_GBps_at_24B_per_key_and_pass_run": 24.0 * n * info["passes_run"] / (sort_ms * 1e-3) / 1e9,
+                          "feed_call_ms_reference_order": call["reference"], "feed_call_ms_sorted": call["sorted"],
+                          "host_std_sort_1_thread_ms": std_s * 1e3, "host_numpy_sort_ms": np_s * 1e3,
+                          "host_sorts_are": "stand-ins for gsl_sort (GSL is not available here); same data, this machine's host"}),
+              flush=True)
+        panel.release_scratch()
 
 
 def tgls_slabs_leg(args):
@@ -335,6 +424,7 @@ def main():
     ap.add_argument("--gl-kind", default="codes", choices=["codes", "continuous"], help="tgls_feed: the likelihoods' form")
     ap.add_argument("--term-budgets-gb", default="8,12,32", help="tgls_slabs: garlic_panel_set_tgls_term_budget values to time")
     ap.add_argument("--cutoff", type=float, default=2.5, help="tgls_slabs: the LOD cutoff of the segments call")
+    ap.add_argument("--kde-inds", type=int, default=20, help="feed_sort: individuals of the subsampled feed (--kde-subsample)")
     ap.add_argument("--tree", default="", help="take garlic_amd from this checkout instead of the one the tool is in")
     args = ap.parse_args()
     if args.tree:
@@ -345,6 +435,8 @@ def main():
         return tgls_feed_multi_leg(args)
     if args.modes == "ld_multi":
         return ld_multi_leg(args)
+    if args.modes == "feed_sort":
+        return feed_sort_leg(args)
     if args.modes in ("wlod_feed", "tgls_feed"):
         return wlod_feed_leg(args, tgls=args.modes == "tgls_feed")
 
