@@ -64,6 +64,10 @@ int fail(int code, const char *fmt, ...)
                         __LINE__);                                                          \
     } while (0)
 
+// dynamic LDS a launch may ask for until hipFuncAttributeMaxDynamicSharedMemorySize has raised the kernel's limit
+constexpr size_t LDS_DEFAULT_MAX = 48 * 1024;
+constexpr size_t LDS_STAGING_MAX = 150 * 1024;      // what a kernel that stages whole tiles may take of the CU's 160 KB
+
 int score_pool_trim();    // idle score buffers (garlic_device_free keeps them mapped) give their memory back
 
 struct NoCopy {
@@ -289,7 +293,6 @@ struct garlic_panel {
     };
     std::vector<std::unique_ptr<LdSet>> ld_sets;
     int32_t ld_group = -1;
-    bool ld_multi_active = false;                  // inside a multi call: install_ld keeps the other sets
     int32_t ld_pair_passes = 0, ld_sum_passes = 0; // of the last multi call (garlic_panel_ld_info)
     DevBuf<double> d_rld, d_decay, d_stage64;
     DevBuf<uint64_t> d_phase;                      // HapData::firstCopy as bit planes [blk][nloci] (--phased LD)
@@ -310,8 +313,6 @@ struct garlic_panel {
         // on the window size: kept across calls (--winsize-multi with --weighted: 3.5 of a call's 32 ms at 10M x 1250)
         uint64_t planes_key = 0;
         bool planes_valid = false;
-        // garlic_panel_compute_ld -> garlic_ld_counts: go on to the hr2 table in the pair kernel; -> garlic_ld_finish: it is there
-        bool fuse_request = false, fused_done = false;
         void release()
         {
             sub.release(); m.release(); h.release(); o.release(); loc.release(); pair.release(); loc_planes.release();
@@ -1163,7 +1164,7 @@ int ensure_gl_terms(garlic_panel *p, bool scaled = false, int32_t M = 0, double 
                       p->nind_pad, p->nwordrows, 0, 0, 0, (int32_t)p->gl_values.size(), 1, nullptr, 0};
         const size_t terms_lds = sizeof(double) * GL_TERMS_S * 4 * (size_t)a.ncodes;      // <= 64 KB (256 codes)
         if (!getenv("GARLIC_GL_TERMS_GATHER")) {
-            if (terms_lds > 48 * 1024)
+            if (terms_lds > LDS_DEFAULT_MAX)
                 HIP_TRY(hipFuncSetAttribute((const void *)gl_terms_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)terms_lds));
             // (the weighted kernel's scores in the same pass when that is what is asked for)
             hipLaunchKernelGGL(gl_terms_lds_kernel, dim3((unsigned)((p->nloci + GL_TERMS_S - 1) / GL_TERMS_S)), dim3(256), terms_lds, s,
@@ -1415,7 +1416,7 @@ int decide_form(garlic_panel *p, const LodCall &c, LodForm &f)
     if (wlod_shape_ok && use_gl && (rc = ensure_gl_terms(p, true, c.M, c.mu))) return rc;
     f.wlod_gl = wlod_shape_ok && use_gl && p->glterms_valid && p->glterms_scaled;   // (the term matrix may have been declined)
     f.wlod_tuned = (wlod_shape_ok && !use_gl) || f.wlod_gl;
-    if (f.wlod_tuned && !f.wlod_gl && sizeof(double) * (size_t)(W + TILE) * 4 + 16 > 150 * 1024) f.wlod_tuned = false;
+    if (f.wlod_tuned && !f.wlod_gl && sizeof(double) * (size_t)(W + TILE) * 4 + 16 > LDS_STAGING_MAX) f.wlod_tuned = false;
     if (f.wlod_tuned && !f.wlod_gl && (rc = ensure_score_rows(p, c.error, c.M, c.mu, W))) return rc;
     if (!f.wlod_tuned && (rc = ensure_rld(p))) return rc;
     // narrow windows, plain scores: the streaming kernel (wlod_small_kernel.hpp) reads the plain reciprocals, a window's
@@ -1688,7 +1689,7 @@ int launch_wlod(garlic_panel *p, const LodCall &c, const LodForm &form, const Pl
         a.use_patch = 1;
         const void *fn = form.wlod_gl ? wlod_stream_small_gl_fn(c.W) : wlod_stream_small_fn(c.W);
         const size_t lds = wlod_small_lds_bytes(c.W);
-        if (lds > 48 * 1024) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        if (lds > LDS_DEFAULT_MAX) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         const double *a_rld = p->d_rld.p;
         void *kargs[] = {(void *)&a_packed, (void *)&a_wtab, (void *)&a_rld, (void *)&d_out, (void *)&a};
         HIP_TRY(hipLaunchKernel(fn, dim3((a.n_work + 7u) / 8u * 8u), wl_block, kargs, lds, s));
@@ -1718,7 +1719,7 @@ int launch_wlod(garlic_panel *p, const LodCall &c, const LodForm &form, const Pl
         a.rerun_count = p->d_counter.p + 4;
     }
     const void *fn = wlod_tile_fn(form.family, form.wlod_gl, form.aligned16);
-    if (form.tile_lds > 48 * 1024) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)form.tile_lds));
+    if (form.tile_lds > LDS_DEFAULT_MAX) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)form.tile_lds));
     void *kargs[] = {(void *)&a_packed, (void *)&a_wtab, (void *)&a_skew, (void *)&d_out, (void *)&a};
     HIP_TRY(hipLaunchKernel(fn, dim3((a.n_work + 7u) / 8u * 8u), wl_block, kargs, form.tile_lds, s));
     return GARLIC_OK;
@@ -1792,7 +1793,7 @@ int for_each_tgls_slab(garlic_panel *p, const std::vector<Plan::Slab> &slabs, in
     VariantArgs a{p->d_packed.p, nullptr, p->d_tabgl.p, p->d_codes.p, nullptr, nullptr, nullptr, nullptr, nullptr,
                   p->nind_pad, p->nwordrows, 0, 0, 0, (int32_t)p->gl_values.size(), 1, nullptr, 0};
     const size_t terms_lds = sizeof(double) * GL_TERMS_S * 4 * (size_t)a.ncodes;      // <= 64 KB (256 codes)
-    if (terms_lds > 48 * 1024)
+    if (terms_lds > LDS_DEFAULT_MAX)
         HIP_TRY(hipFuncSetAttribute((const void *)gl_terms_slab_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)terms_lds));
     const unsigned terms_grid = (unsigned)((p->nloci + GL_TERMS_S - 1) / GL_TERMS_S + (GL_PAD_ROWS + GL_TERMS_S - 1) / GL_TERMS_S);
     for (size_t k = 0; k < n_slabs; k++) {
@@ -2619,8 +2620,8 @@ static void drop_all_ld(garlic_panel *p)
     p->ld_group = -1;
 }
 
-// skew_done: the LD kernels have written D themselves (ld_sum_col_kernel)
-static int install_ld(garlic_panel *p, int32_t winsize, const double *src, bool skew_done = false)
+// skew_done: the LD kernels have written D themselves (ld_sum_col_kernel); keep_sets: inside a multi call, the other sets stay
+static int install_ld(garlic_panel *p, int32_t winsize, const double *src, bool skew_done = false, bool keep_sets = false)
 {
     int rc;
     hipStream_t s = p->ctx->stream;
@@ -2637,7 +2638,7 @@ static int install_ld(garlic_panel *p, int32_t winsize, const double *src, bool 
     p->have_ld = true;
     p->ld_winsize = winsize;
     p->ld_group = -1;
-    if (!p->ld_multi_active) {   // a single-size call leaves exactly the one set it installs
+    if (!keep_sets) {   // a single-size call leaves exactly the one set it installs
         drop_ld_sets(p);
         p->ld_pair_passes = p->ld_sum_passes = 0;
     }
@@ -2677,35 +2678,268 @@ int garlic_panel_set_ld(garlic_panel *p, int32_t winsize, const double *ld, int3
     return rc;
 }
 
-// ---- LD weights on the device (ld_kernels.hpp)
-// unphased, 16 < W <= 129: the pair counts as banded Gram matrices on the matrix cores (ld_pair_mfma_kernel)
-static bool ld_pairs_on_mfma(int32_t winsize, int32_t phased)
+// ---- LD weights on the device (ld_kernels.hpp, ld_multi_kernel.hpp).  An LD call, step by step: arguments (ld_check) -> kernel
+// form (LdForm) -> the subsample as a bitmap -> counts (ld_counts_run: bit planes and per-SNP counts, kept per subsample -> grid
+// table -> one pair kernel) -> weights (ld_finish_run: zero fill -> hf -> hr2 table -> ordered sums -> install_ld) -> copy out.
+// garlic_ld_counts and garlic_ld_finish are the two halves with the integer counts in between (a sharded panel adds them up over
+// its shards); garlic_panel_compute_ld runs both on the panel's scratch and, where the form allows it, fused: the pair kernel goes
+// on to the hr2 table and no pair table is made.  The multi-size calls run the same steps at the widest shared size, then one sum
+// pass per group of sizes.
+enum class LdPair { mfma, lane, tiled, flat, plain };
+enum class LdSum { flat, col, tiled, plain };
+
+// Which kernels take a call of (panel, W, phased) under the switches of the moment, and what they need.  ld_form fills it, once
+// per call; everything after reads it: no later code looks at W, the phasing or the environment to pick a kernel.
+struct LdForm {
+    int32_t W = 0, nblk = 0;       // nblk: 64-individual blocks of the panel
+    bool phased = false;
+    // pair counts.  mfma: banded Gram matrices on the matrix cores (unphased, 16 < W <= 129); lane: a lane per SNP while the
+    // tile's plane words fit LDS; tiled: a thread per distance (W - 1 <= 256); flat: a thread per pair (a switch); plain: a
+    // workgroup per SNP, streamed from L2 -- the only one that adds into a zeroed table instead of writing every entry
+    LdPair pair = LdPair::plain;
+    int pair_tile = 0;             // mfma, lane, tiled: SNPs per workgroup, all chromosomes in one grid (LdPairChr)
+    int mfma_nj = 0;               // mfma: 32-SNP tiles per row of the band
+    int lane_stage = 0, lane_dc = 0;   // lane: blocks staged at a time, distances per pass
+    size_t pair_lds = 0;           // dynamic LDS of the pair kernel (mfma: without the fused form's transposition tiles)
+    bool plane_cache = true;       // the bit planes of an unchanged (genotypes, subsample) are not made again
+    // ordered sums.  flat: hr2 evaluated in place, a thread per (window start, column) (W <= 16: GARLIC's default --winsize is
+    // 10); col: a thread per SNP of the window over the combined hr2 table, writes the wLOD weights too (32 < W <= 512); tiled: a
+    // thread per column of the LD row over two hr2 tables (W <= 256); plain: that streamed from L2, chromosome by chromosome
+    LdSum sum = LdSum::plain;
+    int col_threads = 0;           // col, and ld_sum_multi_kernel at this W: W + 16 SNPs in whole waves
+    int sum_threads = 0;           // tiled: a thread per column, in whole waves
+    int sum_b = 0;                 // col, tiled: window starts per workgroup (col: thread W + B - 1 reads one element further on odd steps)
+    int pieces = 0;                // col: 1-KB requests per row of the table
+    bool hr2_tile = false;         // col: the table from LDS tiles of the pair counts (ld_hr2_tile_kernel), hr2_lds bytes each
+    size_t hr2_lds = 0;
+    // every individual's counts in one place: the pair kernel can write the hr2 table itself (GARLIC_LD_UNFUSED: the two steps of
+    // garlic_ld_counts / garlic_ld_finish, which a sharded panel needs)
+    bool fusable = false;
+};
+
+constexpr size_t LD_HR2_TILE_LDS_MAX = 64 * 1024;       // ld_hr2_tile_kernel's tile
+
+static LdForm ld_form(const garlic_panel *p, int32_t W, int32_t phased)
 {
-    const int mfma_nj = 1 + (30 + winsize) / 32;
-    const bool pair_flat = getenv("GARLIC_LD_PAIR_FLAT") && winsize <= 32;
-    return !phased && !pair_flat && winsize > LD_SMALL_MAX_W && mfma_nj <= 5 && !getenv("GARLIC_LD_PAIR_NO_MFMA") &&
-           !getenv("GARLIC_LD_PAIR_TILED") && !getenv("GARLIC_LD_PAIR_L2");
-}
-// 32 < W <= 512: the ordered sums with a thread per SNP of the window (ld_sum_col_kernel), from the combined hr2 table
-static bool ld_sums_by_snp(int32_t winsize)
-{
-    const int col_threads = (winsize + 16 + WAVE - 1) / WAVE * WAVE;
-    return winsize > LD_COL_B && winsize <= 512 && col_threads <= LD_COL_MAX_THREADS && !getenv("GARLIC_LD_SUM_BY_COLUMN") &&
-           !getenv("GARLIC_LD_SUM_L2");
+    LdForm f;
+    f.W = W;
+    f.nblk = (int)(p->nind_pad / WAVE);
+    f.phased = phased != 0;
+    const size_t planes = phased ? 4 : 2;      // plane words per (SNP, block) that a pair kernel stages
+    const bool no_stage = getenv("GARLIC_LD_PAIR_L2"), no_lane = getenv("GARLIC_LD_PAIR_TILED") || no_stage;
+    const bool flat = getenv("GARLIC_LD_PAIR_FLAT") && W <= 32;
+    f.mfma_nj = 1 + (30 + W) / 32;
+    f.lane_stage = std::min(f.nblk, getenv("GARLIC_LD_LANE_STAGE") ? atoi(getenv("GARLIC_LD_LANE_STAGE")) : 4);
+    f.lane_dc = W - 1 <= 16 ? 16 : 32;
+    const size_t lane_lds = sizeof(uint64_t) * planes * (size_t)f.lane_stage * (LD_LANE_T + W - 1);
+    if (!phased && !flat && W > LD_SMALL_MAX_W && f.mfma_nj <= 5 && !getenv("GARLIC_LD_PAIR_NO_MFMA") && !no_lane) {
+        f.pair = LdPair::mfma;
+        f.pair_tile = LDM_TI;
+        f.pair_lds = (size_t)2 * 2 * (4 + f.mfma_nj - 1) * WAVE * 16;
+    } else if (flat) {
+        f.pair = LdPair::flat;
+    } else if (W - 1 <= 256 && lane_lds <= LDS_STAGING_MAX && !no_lane) {
+        f.pair = LdPair::lane;
+        f.pair_tile = LD_LANE_T;
+        f.pair_lds = lane_lds;
+    } else if (W - 1 <= 256 && !no_stage) {
+        f.pair = LdPair::tiled;
+        f.pair_tile = LD_PAIR_T;
+        f.pair_lds = sizeof(uint64_t) * planes * LD_PAIR_BLK * (LD_PAIR_T + W - 1);
+    }
+    f.plane_cache = !getenv("GARLIC_LD_NO_PLANE_CACHE");
+    f.col_threads = (W + 16 + WAVE - 1) / WAVE * WAVE;
+    if (W <= LD_SMALL_MAX_W && !getenv("GARLIC_LD_NO_FLAT")) {
+        f.sum = LdSum::flat;
+    } else if (W > LD_COL_B && W <= 512 && f.col_threads <= LD_COL_MAX_THREADS && !getenv("GARLIC_LD_SUM_BY_COLUMN") &&
+               !getenv("GARLIC_LD_SUM_L2")) {
+        f.sum = LdSum::col;
+        f.sum_b = std::min(LD_COL_B, f.col_threads - W);
+        f.pieces = (f.col_threads * 8 + 1023) / 1024;
+        f.hr2_lds = sizeof(double) * (LD_HR2_T + W + (size_t)LD_HR2_T * (W + 1));
+        f.hr2_tile = f.hr2_lds <= LD_HR2_TILE_LDS_MAX && !getenv("GARLIC_LD_HR2_PLAIN");
+    } else if (W <= LD_SUM_MAX_W && !getenv("GARLIC_LD_SUM_L2")) {
+        f.sum = LdSum::tiled;
+        f.sum_threads = (W + WAVE - 1) / WAVE * WAVE;
+        f.sum_b = LD_SUM_B;
+    }
+    f.fusable = f.pair == LdPair::mfma && f.sum == LdSum::col && !getenv("GARLIC_LD_UNFUSED");
+    return f;
 }
 
 static int ld_check(garlic_panel *p, int32_t winsize, int32_t phased)
 {
     if (!p) return fail(GARLIC_ERR_INVALID, "panel is NULL");
     if (!p->have_geno) return fail(GARLIC_ERR_STATE, "panel needs genotypes before LD weights");
-    if (phased && !p->have_phase)
-        return fail(GARLIC_ERR_STATE, "phased LD weights need garlic_panel_set_phase first");
-    if (phased && !p->have_freq)
-        return fail(GARLIC_ERR_STATE, "phased LD weights need the allele frequencies (garlic_panel_set_freq)");
+    if (phased && !p->have_phase) return fail(GARLIC_ERR_STATE, "phased LD weights need garlic_panel_set_phase first");
+    if (phased && !p->have_freq) return fail(GARLIC_ERR_STATE, "phased LD weights need the allele frequencies (garlic_panel_set_freq)");
     if (winsize <= 1) return fail(GARLIC_ERR_INVALID, "winsize must be > 1");
     if ((int64_t)p->nloci * winsize * 2 >= ((int64_t)1 << 40))
         return fail(GARLIC_ERR_INVALID, "LD table of %lld x %d too large", (long long)p->nloci, winsize);
     return set_device(p->ctx);
+}
+
+// The LD subsample as one bit per individual (order and repeats do not matter for counts of a set; the reference draws distinct
+// indices, garlic-data.cpp:361-362).  sub_idx == NULL: every individual; otherwise exactly the n_sub listed ones -- none when
+// n_sub is 0 (a shard that holds no member of a panel-wide subsample)
+static int ld_sub_bitmap(const garlic_panel *p, const int32_t *sub_idx, int32_t n_sub, std::vector<uint64_t> &sub)
+{
+    if (n_sub < 0 || (n_sub > 0 && !sub_idx)) return fail(GARLIC_ERR_INVALID, "bad LD subsample");
+    sub.assign((size_t)(p->nind_pad / WAVE), 0);
+    for (int i = 0; !sub_idx && i < p->nind; i++) sub[i >> 6] |= (uint64_t)1 << (i & 63);
+    for (int k = 0; sub_idx && k < n_sub; k++) {
+        const int i = sub_idx[k];
+        if (i < 0 || i >= p->nind) return fail(GARLIC_ERR_INVALID, "LD subsample index %d outside panel of %d", i, p->nind);
+        if (sub[i >> 6] & ((uint64_t)1 << (i & 63))) return fail(GARLIC_ERR_INVALID, "LD subsample index %d given twice", i);
+        sub[i >> 6] |= (uint64_t)1 << (i & 63);
+    }
+    return GARLIC_OK;
+}
+
+// The subsample's bit planes (lds.m, h, o) and the per-SNP counts made with them (lds.loc_planes).  They depend on the genotypes
+// and the subsample only, not on the window size: kept across calls, under a key of both.
+static int ld_planes(garlic_panel *p, const LdForm &f, const std::vector<uint64_t> &sub)
+{
+    int rc;
+    hipStream_t s = p->ctx->stream;
+    auto &L = p->lds;
+    const size_t npl = (size_t)f.nblk * p->nloci;
+    if ((rc = L.sub.put(sub, s)) || (rc = L.m.reserve(npl)) || (rc = L.h.reserve(npl)) || (f.phased && (rc = L.o.reserve(npl))) ||
+        (rc = L.loc_planes.reserve((size_t)p->nloci * 2)))
+        return rc;
+    uint64_t key = 0xCBF29CE484222325ull;
+    for (uint64_t w : sub) key = (key ^ w) * 0x100000001B3ull;
+    key = (key ^ (uint64_t)(f.phased ? 2 : 1)) * 0x100000001B3ull;
+    key = (key ^ p->geno_epoch) * 0x100000001B3ull;
+    key = (key ^ (uint64_t)f.nblk) * 0x100000001B3ull;
+    if (L.planes_valid && L.planes_key == key && f.plane_cache) return GARLIC_OK;
+    L.planes_valid = false;
+    hipLaunchKernelGGL(f.phased ? ld_planes_kernel<true> : ld_planes_kernel<false>, dim3((unsigned)p->nwordrows), dim3(256), 0, s,
+                       p->d_packed.p, p->nwordrows, f.nblk, L.sub.p, p->nloci, L.m.p, L.h.p, f.phased ? L.o.p : nullptr, L.loc_planes.p);
+    HIP_TRY(hipGetLastError());
+    L.planes_key = key;
+    L.planes_valid = true;
+    return GARLIC_OK;
+}
+
+// All chromosomes in one grid, `tile` SNPs per workgroup: the table on its way to lds.pair_chrs, the workgroups in *blocks.  pc
+// is the host copy that the upload reads: the caller keeps it until it has synchronised.
+static int ld_pair_table(garlic_panel *p, int tile, std::vector<LdPairChr> &pc, unsigned *blocks)
+{
+    int64_t n = 0;
+    for (int c = 0; c < p->nchr; c++) {
+        pc.push_back(LdPairChr{p->chr_off[c], p->chr_off[c + 1], n});
+        n += (p->chr_nloci[c] + tile - 1) / tile;
+    }
+    *blocks = (unsigned)n;
+    return p->lds.pair_chrs.put(pc, p->ctx->stream);
+}
+
+// The per-SNP frequency of the hr2 / r2 formula in lds.hf: homFreq from the per-SNP counts; phased: r2 takes FreqData::freq
+// where hr2 takes homFreq (garlic-data.cpp:587-588)
+static int ld_hf(garlic_panel *p, const LdForm &f, const int32_t *loc)
+{
+    hipStream_t s = p->ctx->stream;
+    if (int rc = p->lds.hf.reserve(p->nloci)) return rc;
+    if (f.phased)
+        HIP_TRY(hipMemcpyAsync(p->lds.hf.p, p->freq.data(), sizeof(double) * p->nloci, hipMemcpyHostToDevice, s));
+    else
+        hipLaunchKernelGGL(ld_homfreq_kernel, dim3((unsigned)((p->nloci + 255) / 256)), dim3(256), 0, s, loc, p->nloci, p->lds.hf.p);
+    return GARLIC_OK;
+}
+
+// room for the combined hr2 table C of ld_sum_col_kernel, 2 W doubles per SNP (+ 1 KB: the last row's last request may run over)
+static int ld_reserve_table(garlic_panel *p, int32_t W) { return p->lds.fwd.reserve(2 * (size_t)p->nloci * W + 256); }
+// the phased kernels' two further planes (heterozygous-or-missing, firstCopy); NULL for the unphased ones
+static const uint64_t *ld_plane_o(const garlic_panel *p, const LdForm &f) { return f.phased ? p->lds.o.p : nullptr; }
+static const uint64_t *ld_plane_fc(const garlic_panel *p, const LdForm &f) { return f.phased ? p->d_phase.p : nullptr; }
+
+// fuse: the kernel goes on from the counts to the hr2 values and writes the table C (lds.fwd); pair is a token then
+static int ld_pair_mfma(garlic_panel *p, const LdForm &f, unsigned blocks, int32_t *pair, bool fuse)
+{
+    int rc;
+    decltype(&ld_pair_mfma_kernel<2, false>) const fns[2][4] = {
+        {ld_pair_mfma_kernel<2, false>, ld_pair_mfma_kernel<3, false>, ld_pair_mfma_kernel<4, false>, ld_pair_mfma_kernel<5, false>},
+        {ld_pair_mfma_kernel<2, true>, ld_pair_mfma_kernel<3, true>, ld_pair_mfma_kernel<4, true>, ld_pair_mfma_kernel<5, true>}};
+    const auto fn = fns[fuse][f.mfma_nj - 2];          // (16 < W: two tiles at least)
+    const size_t lds = std::max(f.pair_lds, fuse ? LDM_XT_BYTES : (size_t)0);
+    if (fuse && ((rc = ld_hf(p, f, p->lds.loc_planes.p)) || (rc = ld_reserve_table(p, f.W)))) return rc;
+    if (lds > LDS_DEFAULT_MAX) HIP_TRY(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(fn, dim3(blocks), dim3(256), lds, p->ctx->stream, p->lds.m.p, p->lds.h.p, f.nblk, p->nloci, p->lds.pair_chrs.p,
+                       p->nchr, f.W, pair, fuse ? p->lds.hf.p : nullptr, fuse ? p->lds.fwd.p : nullptr);
+    return GARLIC_OK;
+}
+
+static int ld_pair_lane(garlic_panel *p, const LdForm &f, unsigned blocks, int32_t *pair)
+{
+    const auto fn = f.lane_dc == 16 ? (f.phased ? ld_pair_lane_kernel<true, 16> : ld_pair_lane_kernel<false, 16>)
+                                    : (f.phased ? ld_pair_lane_kernel<true, 32> : ld_pair_lane_kernel<false, 32>);
+    if (f.pair_lds > LDS_DEFAULT_MAX) HIP_TRY(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.pair_lds));
+    hipLaunchKernelGGL(fn, dim3(blocks), dim3(LD_LANE_T), f.pair_lds, p->ctx->stream, p->lds.m.p, p->lds.h.p, ld_plane_o(p, f),
+                       ld_plane_fc(p, f), f.nblk, p->nloci, p->lds.pair_chrs.p, p->nchr, f.W, f.lane_stage, pair);
+    return GARLIC_OK;
+}
+
+static int ld_pair_tiled(garlic_panel *p, const LdForm &f, unsigned blocks, int32_t *pair)
+{
+    const int threads = (f.W - 1 + WAVE - 1) / WAVE * WAVE;
+    const auto fn = f.phased ? ld_pair_tiled_kernel<true> : ld_pair_tiled_kernel<false>;
+    if (f.pair_lds > LDS_DEFAULT_MAX) HIP_TRY(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.pair_lds));
+    hipLaunchKernelGGL(fn, dim3(blocks), dim3(threads), f.pair_lds, p->ctx->stream, p->lds.m.p, p->lds.h.p, ld_plane_o(p, f),
+                       ld_plane_fc(p, f), f.nblk, p->nloci, p->lds.pair_chrs.p, p->nchr, f.W, pair);
+    return GARLIC_OK;
+}
+
+static int ld_pair_flat(garlic_panel *p, const LdForm &f, int32_t *pair)
+{
+    hipLaunchKernelGGL(f.phased ? ld_pair_flat_kernel<true> : ld_pair_flat_kernel<false>, dim3((unsigned)(((int64_t)p->nloci * f.W + 255) / 256)),
+                       dim3(256), 0, p->ctx->stream, p->lds.m.p, p->lds.h.p, ld_plane_o(p, f), ld_plane_fc(p, f), f.nblk, p->nloci,
+                       p->d_chr_off.p, p->nchr, f.W, pair);
+    return GARLIC_OK;
+}
+
+// a workgroup per SNP, chromosome by chromosome; adds into a zeroed table
+static int ld_pair_plain(garlic_panel *p, const LdForm &f, int32_t *pair)
+{
+    hipStream_t s = p->ctx->stream;
+    HIP_TRY(hipMemsetAsync(pair, 0, sizeof(int32_t) * (size_t)p->nloci * f.W * 2, s));
+    for (int c = 0; c < p->nchr; c++) {
+        if (f.phased)
+            hipLaunchKernelGGL(ld_pair_phased_kernel, dim3((unsigned)p->chr_nloci[c]), dim3(256), 0, s, p->lds.m.p, p->lds.h.p, p->lds.o.p,
+                               p->d_phase.p, f.nblk, p->nloci, p->chr_off[c], p->chr_off[c + 1], f.W, pair);
+        else
+            hipLaunchKernelGGL(ld_pair_kernel, dim3((unsigned)p->chr_nloci[c]), dim3(256), 0, s, p->lds.m.p, p->lds.h.p, f.nblk, p->nloci,
+                               p->chr_off[c], p->chr_off[c + 1], f.W, pair);
+    }
+    return GARLIC_OK;
+}
+
+// The integer counts of the subsample `sub` into the device tables loc [nloci][2] and pair [nloci][W][2], and from there into
+// host_loc / host_pair where given.  fuse (only where f.fusable): the hr2 table of ld_finish_run is made instead, in lds.fwd, and
+// pair needs no more than a token allocation.
+static int ld_counts_run(garlic_panel *p, const LdForm &f, const std::vector<uint64_t> &sub, int32_t *loc, int32_t *pair, bool fuse,
+                         int32_t *host_loc = nullptr, int32_t *host_pair = nullptr)
+{
+    int rc;
+    hipStream_t s = p->ctx->stream;
+    if ((rc = ld_planes(p, f, sub))) return rc;
+    HIP_TRY(hipMemcpyAsync(loc, p->lds.loc_planes.p, sizeof(int32_t) * p->nloci * 2, hipMemcpyDeviceToDevice, s));
+    std::vector<LdPairChr> pc;          // read by its upload; a call that succeeds has synchronised before it goes
+    unsigned blocks = 0;
+    if (f.pair_tile && (rc = ld_pair_table(p, f.pair_tile, pc, &blocks))) return rc;
+    switch (f.pair) {
+    case LdPair::mfma: rc = ld_pair_mfma(p, f, blocks, pair, fuse); break;
+    case LdPair::lane: rc = ld_pair_lane(p, f, blocks, pair); break;
+    case LdPair::tiled: rc = ld_pair_tiled(p, f, blocks, pair); break;
+    case LdPair::flat: rc = ld_pair_flat(p, f, pair); break;
+    case LdPair::plain: rc = ld_pair_plain(p, f, pair); break;
+    }
+    if (rc) return rc;
+    HIP_TRY(hipGetLastError());
+    if (host_loc) HIP_TRY(hipMemcpyAsync(host_loc, loc, sizeof(int32_t) * p->nloci * 2, hipMemcpyDeviceToHost, s));
+    if (host_pair) HIP_TRY(hipMemcpyAsync(host_pair, pair, sizeof(int32_t) * (size_t)p->nloci * f.W * 2, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return GARLIC_OK;
 }
 
 int garlic_ld_counts(garlic_panel *p, int32_t winsize, int32_t phased, const int32_t *sub_idx, int32_t n_sub,
@@ -2714,200 +2948,167 @@ int garlic_ld_counts(garlic_panel *p, int32_t winsize, int32_t phased, const int
     int rc;
     if ((rc = ld_check(p, winsize, phased))) return rc;
     if (!locus_counts || !pair_counts) return fail(GARLIC_ERR_INVALID, "count buffers are required");
-    if (n_sub < 0 || (n_sub > 0 && !sub_idx)) return fail(GARLIC_ERR_INVALID, "bad LD subsample");
-    // sub_idx == NULL: every individual; otherwise exactly the n_sub listed ones -- none when n_sub is 0
-    // (a shard that holds no member of a panel-wide subsample)
-    hipStream_t s = p->ctx->stream;
-    const int nblk = (int)(p->nind_pad / WAVE);
-    // LD subsample as one bit per individual (order and repeats do not matter for counts of a set;
-    // the reference draws distinct indices, garlic-data.cpp:361-362)
-    std::vector<uint64_t> sub((size_t)nblk, 0);
-    if (!sub_idx) {
-        for (int i = 0; i < p->nind; i++) sub[i >> 6] |= (uint64_t)1 << (i & 63);
-    } else {
-        for (int k = 0; k < n_sub; k++) {
-            const int i = sub_idx[k];
-            if (i < 0 || i >= p->nind)
-                return fail(GARLIC_ERR_INVALID, "LD subsample index %d outside panel of %d", i, p->nind);
-            if (sub[i >> 6] & ((uint64_t)1 << (i & 63)))
-                return fail(GARLIC_ERR_INVALID, "LD subsample index %d given twice", i);
-            sub[i >> 6] |= (uint64_t)1 << (i & 63);
-        }
-    }
-    DevBuf<uint64_t> &d_sub = p->lds.sub, &d_m = p->lds.m, &d_h = p->lds.h, &d_o = p->lds.o;
+    std::vector<uint64_t> sub;
+    if ((rc = ld_sub_bitmap(p, sub_idx, n_sub, sub))) return rc;
+    const LdForm f = ld_form(p, winsize, phased);
+    if (where != GARLIC_HOST) return ld_counts_run(p, f, sub, locus_counts, pair_counts, false);
     DevBuf<int32_t> &d_loc = p->lds.loc, &d_pair = p->lds.pair;
-    const size_t npl = (size_t)nblk * p->nloci, npair = (size_t)p->nloci * winsize * 2;
-    if ((rc = d_sub.reserve(nblk)) || (rc = d_m.reserve(npl)) || (rc = d_h.reserve(npl))) return rc;
-    if (phased && (rc = d_o.reserve(npl))) return rc;
-    int32_t *loc = locus_counts, *pair = pair_counts;
-    if (where == GARLIC_HOST) {
-        if ((rc = d_loc.reserve((size_t)p->nloci * 2)) || (rc = d_pair.reserve(npair))) return rc;
-        loc = d_loc.p; pair = d_pair.p;
-    }
-    // pair counts: LDS-tiled (thread = distance, W - 1 <= 256; writes every entry of the table) or streamed from L2
-    // pair counts: a lane per SNP while the tile's plane words fit LDS (ld_pair_lane_kernel); else a thread per distance
-    // (ld_pair_tiled_kernel, W - 1 <= 256; writes every entry of the table too) or streamed from L2
-    const bool pair_flat = getenv("GARLIC_LD_PAIR_FLAT") && winsize <= 32;
-    const int lane_stage = std::min(nblk, getenv("GARLIC_LD_LANE_STAGE") ? atoi(getenv("GARLIC_LD_LANE_STAGE")) : 4);
-    const int lane_dc = winsize - 1 <= 16 ? 16 : 32;
-    const size_t lane_lds = sizeof(uint64_t) * (phased ? 4 : 2) * (size_t)lane_stage * (LD_LANE_T + winsize - 1);
-    // unphased, 16 < W <= 129: the counts as banded Gram matrices on the matrix cores (ld_pair_mfma_kernel)
-    const int mfma_nj = 1 + (30 + winsize) / 32;
-    const bool pair_mfma = ld_pairs_on_mfma(winsize, phased);
-    // garlic_panel_compute_ld (every individual's counts are local): the pair kernel writes the hr2 table itself
-    const bool fuse_hr2 = p->lds.fuse_request && pair_mfma && ld_sums_by_snp(winsize);
-    if (p->lds.fuse_request && !fuse_hr2) {      // (the caller has sized the pair table for the fused form)
-        p->lds.fuse_request = false;
-        return fail(GARLIC_ERR_STATE, "internal: LD fusion requested for a shape the pair kernel does not take");
-    }
-    p->lds.fuse_request = false;
-    p->lds.fused_done = false;
-    const bool pair_lane = !pair_mfma && !pair_flat && winsize - 1 <= 256 && lane_lds <= 150 * 1024 && !getenv("GARLIC_LD_PAIR_TILED") &&
-                           !getenv("GARLIC_LD_PAIR_L2");
-    const bool pair_tiled = !pair_mfma && !pair_flat && !pair_lane && winsize - 1 <= 256 && !getenv("GARLIC_LD_PAIR_L2");
-    hipError_t e = hipMemcpyAsync(d_sub.p, sub.data(), sizeof(uint64_t) * nblk, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && !pair_tiled && !pair_flat && !pair_lane && !pair_mfma) e = hipMemsetAsync(pair, 0, sizeof(int32_t) * npair, s);
-    if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "LD counts: %s", hipGetErrorString(e));
-    uint64_t planes_key = 0xCBF29CE484222325ull;
-    for (uint64_t w : sub) planes_key = (planes_key ^ w) * 0x100000001B3ull;
-    planes_key = (planes_key ^ (uint64_t)(phased ? 2 : 1)) * 0x100000001B3ull;
-    planes_key = (planes_key ^ p->geno_epoch) * 0x100000001B3ull;
-    planes_key = (planes_key ^ (uint64_t)nblk) * 0x100000001B3ull;
-    if ((rc = p->lds.loc_planes.reserve((size_t)p->nloci * 2))) return rc;
-    if (!(p->lds.planes_valid && p->lds.planes_key == planes_key) || getenv("GARLIC_LD_NO_PLANE_CACHE")) {
-        p->lds.planes_valid = false;
-        if (phased)
-            hipLaunchKernelGGL(ld_planes_kernel<true>, dim3((unsigned)p->nwordrows), dim3(256), 0, s, p->d_packed.p,
-                               p->nwordrows, nblk, d_sub.p, p->nloci, d_m.p, d_h.p, d_o.p, p->lds.loc_planes.p);
+    if ((rc = d_loc.reserve((size_t)p->nloci * 2)) || (rc = d_pair.reserve((size_t)p->nloci * winsize * 2))) return rc;
+    return ld_counts_run(p, f, sub, d_loc.p, d_pair.p, false, locus_counts, pair_counts);
+}
+
+// The combined table C at pitch 2 W in lds.fwd, from pair counts at pitch W and lds.hf: what ld_sum_col_kernel and
+// ld_sum_multi_kernel read (and the fused pair kernel writes itself)
+static int ld_build_table(garlic_panel *p, const LdForm &f, const int32_t *pair)
+{
+    hipStream_t s = p->ctx->stream;
+    if (int rc = ld_reserve_table(p, f.W)) return rc;
+    for (int c = 0; c < p->nchr; c++) {
+        const int64_t lo = p->chr_off[c], hi = p->chr_off[c + 1];
+        if (f.hr2_tile)
+            hipLaunchKernelGGL(ld_hr2_tile_kernel, dim3((unsigned)((hi - lo + LD_HR2_T - 1) / LD_HR2_T)), dim3(256), f.hr2_lds, s, pair,
+                               p->lds.hf.p, lo, hi, f.W, p->lds.fwd.p);
         else
-            hipLaunchKernelGGL(ld_planes_kernel<false>, dim3((unsigned)p->nwordrows), dim3(256), 0, s, p->d_packed.p,
-                               p->nwordrows, nblk, d_sub.p, p->nloci, d_m.p, d_h.p, (uint64_t *)nullptr, p->lds.loc_planes.p);
-        e = hipGetLastError();
-        if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "LD planes: %s", hipGetErrorString(e));
-        p->lds.planes_key = planes_key;
-        p->lds.planes_valid = true;
+            hipLaunchKernelGGL(ld_hr2_kernel<true>, dim3((unsigned)(hi - lo)), dim3(128), 0, s, pair, p->lds.hf.p, lo, hi, f.W,
+                               p->lds.fwd.p, (double *)nullptr);
     }
-    e = hipMemcpyAsync(loc, p->lds.loc_planes.p, sizeof(int32_t) * p->nloci * 2, hipMemcpyDeviceToDevice, s);
-    if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "LD counts: %s", hipGetErrorString(e));
-    const int pair_threads = (winsize - 1 + WAVE - 1) / WAVE * WAVE;
-    const size_t pair_lds = sizeof(uint64_t) * (phased ? 4 : 2) * LD_PAIR_BLK * (LD_PAIR_T + winsize - 1);
-    if (pair_tiled && pair_lds > 48 * 1024) {
-        const void *fn = phased ? (const void *)ld_pair_tiled_kernel<true> : (const void *)ld_pair_tiled_kernel<false>;
-        hipError_t ae = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pair_lds);
-        if (ae != hipSuccess) return fail(GARLIC_ERR_HIP, "LD counts: %s", hipGetErrorString(ae));
-    }
-    if (pair_tiled) {   // all chromosomes in one grid
-        std::vector<LdPairChr> pc;
-        int64_t blocks = 0;
-        for (int c = 0; c < p->nchr; c++) {
-            pc.push_back(LdPairChr{p->chr_off[c], p->chr_off[c + 1], blocks});
-            blocks += (p->chr_nloci[c] + LD_PAIR_T - 1) / LD_PAIR_T;
-        }
-        DevBuf<LdPairChr> &d_pc = p->lds.pair_chrs;
-        if ((rc = d_pc.reserve(pc.size()))) return rc;
-        e = hipMemcpyAsync(d_pc.p, pc.data(), sizeof(LdPairChr) * pc.size(), hipMemcpyHostToDevice, s);
-        if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "LD counts: %s", hipGetErrorString(e));
-        if (phased)
-            hipLaunchKernelGGL(ld_pair_tiled_kernel<true>, dim3((unsigned)blocks), dim3(pair_threads), pair_lds, s, d_m.p,
-                               d_h.p, d_o.p, p->d_phase.p, nblk, p->nloci, d_pc.p, p->nchr, winsize, pair);
-        else
-            hipLaunchKernelGGL(ld_pair_tiled_kernel<false>, dim3((unsigned)blocks), dim3(pair_threads), pair_lds, s, d_m.p,
-                               d_h.p, (const uint64_t *)nullptr, (const uint64_t *)nullptr, nblk, p->nloci, d_pc.p,
-                               p->nchr, winsize, pair);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(s);   // pc (host) is read by the copy above
-        if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "LD counts: %s", hipGetErrorString(e));
-    }
-    if (pair_mfma) {   // all chromosomes in one grid, 256 SNPs i per workgroup
-        std::vector<LdPairChr> pc;
-        int64_t blocks = 0;
-        for (int c = 0; c < p->nchr; c++) {
-            pc.push_back(LdPairChr{p->chr_off[c], p->chr_off[c + 1], blocks});
-            blocks += (p->chr_nloci[c] + LDM_TI - 1) / LDM_TI;
-        }
-        DevBuf<LdPairChr> &d_pc = p->lds.pair_chrs;
-        if ((rc = d_pc.reserve(pc.size()))) return rc;
-        e = hipMemcpyAsync(d_pc.p, pc.data(), sizeof(LdPairChr) * pc.size(), hipMemcpyHostToDevice, s);
-        const void *fn = fuse_hr2 ? (mfma_nj <= 2 ? (const void *)ld_pair_mfma_kernel<2, true> : mfma_nj == 3 ? (const void *)ld_pair_mfma_kernel<3, true>
-                                     : mfma_nj == 4 ? (const void *)ld_pair_mfma_kernel<4, true> : (const void *)ld_pair_mfma_kernel<5, true>)
-                                  : (mfma_nj <= 2 ? (const void *)ld_pair_mfma_kernel<2, false> : mfma_nj == 3 ? (const void *)ld_pair_mfma_kernel<3, false>
-                                     : mfma_nj == 4 ? (const void *)ld_pair_mfma_kernel<4, false> : (const void *)ld_pair_mfma_kernel<5, false>);
-        const int nj = std::max(2, mfma_nj);
-        const size_t lds = std::max((size_t)2 * 2 * (4 + nj - 1) * WAVE * 16, fuse_hr2 ? LDM_XT_BYTES : (size_t)0);
-        const double *a_hf = nullptr;
-        double *a_c = nullptr;
-        if (fuse_hr2) {      // homFreq from the locus counts, room for the combined table (+ 1 KB: ld_sum_col_kernel's last request)
-            const size_t n = (size_t)p->nloci * winsize;
-            if ((rc = p->lds.hf.reserve(p->nloci)) || (rc = p->lds.fwd.reserve(2 * n + 256))) return rc;
-            hipLaunchKernelGGL(ld_homfreq_kernel, dim3((unsigned)((p->nloci + 255) / 256)), dim3(256), 0, s, p->lds.loc_planes.p, p->nloci,
-                               p->lds.hf.p);
-            a_hf = p->lds.hf.p;
-            a_c = p->lds.fwd.p;
-        }
-        if (e == hipSuccess && lds > 48 * 1024) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "LD counts: %s", hipGetErrorString(e));
-        const uint64_t *a_m = d_m.p, *a_h = d_h.p;
-        const LdPairChr *a_pc = d_pc.p;
-        int a_nblk = nblk, a_nchr = p->nchr, a_w = winsize;
-        int64_t a_nloci = p->nloci;
-        void *kargs[] = {(void *)&a_m, (void *)&a_h, (void *)&a_nblk, (void *)&a_nloci, (void *)&a_pc, (void *)&a_nchr, (void *)&a_w, (void *)&pair,
-                         (void *)&a_hf, (void *)&a_c};
-        e = hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(256), kargs, lds, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);   // pc (host) is read by the copy above
-        if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "LD counts: %s", hipGetErrorString(e));
-        p->lds.fused_done = fuse_hr2;
-    }
-    if (pair_lane) {   // all chromosomes in one grid, tiles of 256 SNPs
-        std::vector<LdPairChr> pc;
-        int64_t blocks = 0;
-        for (int c = 0; c < p->nchr; c++) {
-            pc.push_back(LdPairChr{p->chr_off[c], p->chr_off[c + 1], blocks});
-            blocks += (p->chr_nloci[c] + LD_LANE_T - 1) / LD_LANE_T;
-        }
-        DevBuf<LdPairChr> &d_pc = p->lds.pair_chrs;
-        if ((rc = d_pc.reserve(pc.size()))) return rc;
-        e = hipMemcpyAsync(d_pc.p, pc.data(), sizeof(LdPairChr) * pc.size(), hipMemcpyHostToDevice, s);
-        const void *fn = lane_dc == 16 ? (phased ? (const void *)ld_pair_lane_kernel<true, 16> : (const void *)ld_pair_lane_kernel<false, 16>)
-                                       : (phased ? (const void *)ld_pair_lane_kernel<true, 32> : (const void *)ld_pair_lane_kernel<false, 32>);
-        if (e == hipSuccess && lane_lds > 48 * 1024) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lane_lds);
-        if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "LD counts: %s", hipGetErrorString(e));
-        const uint64_t *a_m = d_m.p, *a_h = d_h.p, *a_o = phased ? d_o.p : nullptr, *a_f = phased ? p->d_phase.p : nullptr;
-        const LdPairChr *a_pc = d_pc.p;
-        int a_nblk = nblk, a_nchr = p->nchr, a_w = winsize, a_stage = lane_stage;
-        int64_t a_nloci = p->nloci;
-        void *kargs[] = {(void *)&a_m, (void *)&a_h, (void *)&a_o, (void *)&a_f, (void *)&a_nblk, (void *)&a_nloci, (void *)&a_pc,
-                         (void *)&a_nchr, (void *)&a_w, (void *)&a_stage, (void *)&pair};
-        e = hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(LD_LANE_T), kargs, lane_lds, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);   // pc (host) is read by the copy above
-        if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "LD counts: %s", hipGetErrorString(e));
-    }
-    if (pair_flat) {
-        const unsigned grid = (unsigned)(((int64_t)p->nloci * winsize + 255) / 256);
-        if (phased)
-            hipLaunchKernelGGL(ld_pair_flat_kernel<true>, dim3(grid), dim3(256), 0, s, d_m.p, d_h.p, d_o.p, p->d_phase.p, nblk,
-                               p->nloci, p->d_chr_off.p, p->nchr, winsize, pair);
-        else
-            hipLaunchKernelGGL(ld_pair_flat_kernel<false>, dim3(grid), dim3(256), 0, s, d_m.p, d_h.p, (const uint64_t *)nullptr,
-                               (const uint64_t *)nullptr, nblk, p->nloci, p->d_chr_off.p, p->nchr, winsize, pair);
-    }
-    for (int c = 0; !pair_tiled && !pair_flat && !pair_lane && !pair_mfma && c < p->nchr; c++) {
-        if (phased)
-            hipLaunchKernelGGL(ld_pair_phased_kernel, dim3((unsigned)p->chr_nloci[c]), dim3(256), 0, s, d_m.p,
-                               d_h.p, d_o.p, p->d_phase.p, nblk, p->nloci, p->chr_off[c], p->chr_off[c + 1],
-                               winsize, pair);
-        else
-            hipLaunchKernelGGL(ld_pair_kernel, dim3((unsigned)p->chr_nloci[c]), dim3(256), 0, s, d_m.p, d_h.p,
-                               nblk, p->nloci, p->chr_off[c], p->chr_off[c + 1], winsize, pair);
-    }
-    e = hipGetLastError();
-    if (e == hipSuccess && where == GARLIC_HOST) {
-        e = hipMemcpyAsync(locus_counts, loc, sizeof(int32_t) * p->nloci * 2, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(pair_counts, pair, sizeof(int32_t) * npair, hipMemcpyDeviceToHost, s);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "LD counts: %s", hipGetErrorString(e));
+    HIP_TRY(hipGetLastError());
     return GARLIC_OK;
+}
+
+// initLDData zero-fills, and the kernels with a thread per SNP of the window write every entry of the window starts that have a
+// full window: that leaves the last W - 1 rows of each chromosome
+static int ld_zero_short_rows(garlic_panel *p, int32_t W, double *ld)
+{
+    for (int c = 0; c < p->nchr; c++) {
+        const int64_t lo = p->chr_off[c], hi = p->chr_off[c + 1], from = std::max<int64_t>(lo, hi - W + 1);
+        if (hi > from) HIP_TRY(hipMemsetAsync(ld + from * W, 0, sizeof(double) * (size_t)(hi - from) * W, p->ctx->stream));
+    }
+    return GARLIC_OK;
+}
+
+// The launch of ld_sum_col_kernel (n_small == 0) or ld_sum_multi_kernel at f.W: the instantiation for the row's 1-KB requests,
+// its LDS, the grid in eights (the kernels deal their workgroups over the 8 XCDs).  The call's dominant kernel: its HIP-event
+// time is what garlic_recent_kernel_ms reports for an LD call.
+extern "C++" template <class K, class... A>
+int ld_launch_col(garlic_panel *p, const LdForm &f, K *const (&fns)[LD_COL_MAX_PIECES], int n_small, unsigned nwork, A... args)
+{
+    static_assert(LD_COL_MAX_THREADS <= 128 * LD_COL_MAX_PIECES, "one instantiation per request count");
+    K *const fn = fns[f.pieces - 1];
+    const size_t lds = ldms_lds_bytes(f.col_threads, n_small);
+    if (lds > LDS_DEFAULT_MAX) HIP_TRY(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    (void)hist_mark(p->ctx, false);
+    hipLaunchKernelGGL(fn, dim3((nwork + 7u) / 8u * 8u), dim3(f.col_threads), lds, p->ctx->stream, args..., nwork);
+    (void)hist_mark(p->ctx, true);
+    HIP_TRY(hipGetLastError());
+    return GARLIC_OK;
+}
+#define LD_COL_FNS(kernel) {kernel<1>, kernel<2>, kernel<3>, kernel<4>, kernel<5>}
+
+// the window starts of a sum kernel's grid, b per workgroup, over all chromosomes that have one; chrs is the host copy that the
+// upload to lds.sum_chrs reads
+static int ld_sum_table(garlic_panel *p, const LdForm &f, std::vector<LdSumChr> &chrs, unsigned *blocks)
+{
+    int64_t n = 0;
+    for (int c = 0; c < p->nchr; c++) {
+        const int64_t nstarts = p->chr_off[c + 1] - p->chr_off[c] - f.W + 1;
+        if (nstarts < 1) continue;
+        chrs.push_back(LdSumChr{p->chr_off[c], nstarts, n});
+        n += (nstarts + f.sum_b - 1) / f.sum_b;
+    }
+    *blocks = (unsigned)n;
+    return p->lds.sum_chrs.put(chrs, p->ctx->stream);
+}
+
+// LdSum::col, from the table in lds.fwd: the LD matrix (ld may be NULL) and the wLOD weights, which this kernel writes as well
+static int ld_sum_col(garlic_panel *p, const LdForm &f, double *ld, std::vector<LdSumChr> &chrs)
+{
+    int rc;
+    unsigned nwork = 0;
+    if ((rc = ld_sum_table(p, f, chrs, &nwork)) || (rc = reserve_skew(p, f.W, false))) return rc;
+    if (chrs.empty()) return GARLIC_OK;
+    decltype(&ld_sum_col_kernel<1>) const fns[] = LD_COL_FNS(ld_sum_col_kernel);
+    return ld_launch_col(p, f, fns, 0, nwork, p->lds.fwd.p, p->lds.sum_chrs.p, (int)chrs.size(), f.W, f.sum_b, ld, p->d_skew.p + SKEW_FRONT);
+}
+
+// LdSum::tiled and LdSum::plain: hr2 forwards and backwards in two tables (lds.fwd, lds.bwd), then the sums -- tiled: all
+// chromosomes in one grid, after every hr2 value exists; plain: chromosome by chromosome
+static int ld_sum_two_tables(garlic_panel *p, const LdForm &f, const int32_t *pair, double *ld, std::vector<LdSumChr> &chrs)
+{
+    int rc;
+    hipStream_t s = p->ctx->stream;
+    const int32_t W = f.W;
+    const size_t n = (size_t)p->nloci * W;
+    if ((rc = p->lds.fwd.reserve(n)) || (rc = p->lds.bwd.reserve(n))) return rc;
+    for (int c = 0; c < p->nchr; c++) {
+        const int64_t lo = p->chr_off[c], hi = p->chr_off[c + 1];
+        hipLaunchKernelGGL(ld_hr2_kernel<false>, dim3((unsigned)(hi - lo)), dim3(256), 0, s, pair, p->lds.hf.p, lo, hi, W, p->lds.fwd.p,
+                           p->lds.bwd.p);
+        if (f.sum == LdSum::plain && hi - lo >= W)
+            hipLaunchKernelGGL(ld_sum_kernel, dim3((unsigned)(hi - lo - W + 1)), dim3(256), 0, s, p->lds.fwd.p, p->lds.bwd.p, lo, W, ld);
+    }
+    if (f.sum == LdSum::plain) return GARLIC_OK;
+    unsigned blocks = 0;
+    if ((rc = ld_sum_table(p, f, chrs, &blocks))) return rc;
+    if (chrs.empty()) return GARLIC_OK;
+    const size_t lds = sizeof(double) * 2 * (2 * (size_t)W - 1 + 128 + f.sum_threads);
+    (void)hist_mark(p->ctx, false);
+    hipLaunchKernelGGL(ld_sum_tiled_kernel, dim3(blocks), dim3(f.sum_threads), lds, s, p->lds.fwd.p, p->lds.bwd.p, p->lds.sum_chrs.p,
+                       (int)chrs.size(), W, ld);
+    (void)hist_mark(p->ctx, true);
+    return GARLIC_OK;
+}
+
+// From the counts (device tables) to the installed wLOD weights and, in ld (device, [nloci][W]), the LD matrix.  ld may be
+// NULL only where the sum kernel writes the weights itself (LdSum::col): the matrix is not made at all then.  have_table: the
+// pair kernel has left the hr2 table in lds.fwd (ld_counts_run with fuse) and pair is not read.
+static int ld_finish_run(garlic_panel *p, const LdForm &f, const int32_t *loc, const int32_t *pair, double *ld, bool have_table,
+                         bool keep_sets)
+{
+    int rc;
+    const bool col = f.sum == LdSum::col;
+    if (ld && !col) HIP_TRY(hipMemsetAsync(ld, 0, sizeof(double) * (size_t)p->nloci * f.W, p->ctx->stream));      // initLDData zero-fills
+    if ((ld && col && (rc = ld_zero_short_rows(p, f.W, ld))) || (rc = ld_hf(p, f, loc))) return rc;
+    std::vector<LdSumChr> chrs;         // read by its upload; a call that succeeds has synchronised (install_ld) before it goes
+    switch (f.sum) {
+    case LdSum::flat:
+        (void)hist_mark(p->ctx, false);
+        hipLaunchKernelGGL(ld_sum_flat_kernel, dim3((unsigned)(((size_t)p->nloci * f.W + 255) / 256)), dim3(256), 0, p->ctx->stream, pair,
+                           p->lds.hf.p, p->d_chr_off.p, p->nchr, p->nloci, f.W, ld);
+        (void)hist_mark(p->ctx, true);
+        break;
+    case LdSum::col:
+        if (!have_table) rc = ld_build_table(p, f, pair);
+        if (!rc) rc = ld_sum_col(p, f, ld, chrs);
+        break;
+    case LdSum::tiled:
+    case LdSum::plain: rc = ld_sum_two_tables(p, f, pair, ld, chrs); break;
+    }
+    if (rc) return rc;
+    HIP_TRY(hipGetLastError());
+    return install_ld(p, f.W, ld, col, keep_sets);
+}
+
+static int ld_copy_out(double *dst, const double *src, size_t n, int32_t where)
+{
+    HIP_TRY(hipMemcpy(dst, src, sizeof(double) * n, where == GARLIC_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));
+    return GARLIC_OK;
+}
+
+// ld_finish_run into the device matrix the call needs (the caller's; scratch when it wants a host copy or the weights are made
+// from the matrix; none when nobody asked for it and the sum kernel writes the weights itself), then the copy out
+static int ld_finish_to(garlic_panel *p, const LdForm &f, const int32_t *loc, const int32_t *pair, bool have_table, double *ld_out,
+                        bool host_out, bool keep_sets)
+{
+    int rc;
+    const size_t n = (size_t)p->nloci * f.W;
+    double *ld = host_out ? nullptr : ld_out;
+    if (!ld && (ld_out || f.sum != LdSum::col)) {
+        if ((rc = p->lds.ld.reserve(n))) return rc;
+        ld = p->lds.ld.p;
+    }
+    if ((rc = ld_finish_run(p, f, loc, pair, ld, have_table, keep_sets))) return rc;
+    return ld_out && ld != ld_out ? ld_copy_out(ld_out, ld, n, GARLIC_HOST) : GARLIC_OK;
 }
 
 int garlic_ld_finish(garlic_panel *p, int32_t winsize, int32_t phased, const int32_t *locus_counts,
@@ -2917,159 +3118,25 @@ int garlic_ld_finish(garlic_panel *p, int32_t winsize, int32_t phased, const int
     if ((rc = ld_check(p, winsize, phased))) return rc;
     if (!locus_counts || !pair_counts) return fail(GARLIC_ERR_INVALID, "count buffers are required");
     hipStream_t s = p->ctx->stream;
-    const size_t n = (size_t)p->nloci * winsize;
-    DevBuf<int32_t> &d_loc = p->lds.loc, &d_pair = p->lds.pair;
-    DevBuf<double> &d_hf = p->lds.hf, &d_fwd = p->lds.fwd, &d_bwd = p->lds.bwd, &d_ld = p->lds.ld;
-    DevBuf<LdSumChr> &d_sum_chrs = p->lds.sum_chrs;
-    const int32_t *loc = locus_counts, *pair = pair_counts;
-    hipError_t e = hipSuccess;
     if (where == GARLIC_HOST) {
-        if ((rc = d_loc.reserve((size_t)p->nloci * 2)) || (rc = d_pair.reserve(n * 2))) return rc;
-        e = hipMemcpyAsync(d_loc.p, locus_counts, sizeof(int32_t) * p->nloci * 2, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(d_pair.p, pair_counts, sizeof(int32_t) * n * 2, hipMemcpyHostToDevice, s);
-        loc = d_loc.p; pair = d_pair.p;
+        DevBuf<int32_t> &d_loc = p->lds.loc, &d_pair = p->lds.pair;
+        const size_t npair = (size_t)p->nloci * winsize * 2;
+        if ((rc = d_loc.reserve((size_t)p->nloci * 2)) || (rc = d_pair.reserve(npair))) return rc;
+        HIP_TRY(hipMemcpyAsync(d_loc.p, locus_counts, sizeof(int32_t) * p->nloci * 2, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d_pair.p, pair_counts, sizeof(int32_t) * npair, hipMemcpyHostToDevice, s));
+        locus_counts = d_loc.p; pair_counts = d_pair.p;
     }
-    // narrow windows (GARLIC's default --winsize is 10): hr2 evaluated in place, one thread per (window start, column)
-    if (winsize <= LD_SMALL_MAX_W && !getenv("GARLIC_LD_NO_FLAT")) {
-        if ((rc = d_hf.reserve(p->nloci))) return rc;
-        double *ld = ld_out;
-        if (where == GARLIC_HOST || !ld_out) {
-            if ((rc = d_ld.reserve(n))) return rc;
-            ld = d_ld.p;
-        }
-        if (e == hipSuccess) e = hipMemsetAsync(ld, 0, sizeof(double) * n, s);      // initLDData zero-fills
-        if (e == hipSuccess && phased) e = hipMemcpyAsync(d_hf.p, p->freq.data(), sizeof(double) * p->nloci, hipMemcpyHostToDevice, s);
-        if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "LD finish: %s", hipGetErrorString(e));
-        if (!phased)
-            hipLaunchKernelGGL(ld_homfreq_kernel, dim3((unsigned)((p->nloci + 255) / 256)), dim3(256), 0, s, loc, p->nloci, d_hf.p);
-        garlic_ctx *ctx = p->ctx;
-        const int slot = (int)(ctx->n_calls % garlic_ctx::HIST);
-        (void)hipEventRecord(ctx->hist0[slot], s);
-        hipLaunchKernelGGL(ld_sum_flat_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, pair, d_hf.p, p->d_chr_off.p,
-                           p->nchr, p->nloci, winsize, ld);
-        (void)hipEventRecord(ctx->hist1[slot], s);
-        ctx->n_calls++;
-        e = hipGetLastError();
-        if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "LD finish: %s", hipGetErrorString(e));
-        if ((rc = install_ld(p, winsize, ld, false))) return rc;
-        if (where == GARLIC_HOST && ld_out) {
-            e = hipMemcpyAsync(ld_out, ld, sizeof(double) * n, hipMemcpyDeviceToHost, s);
-            if (e == hipSuccess) e = hipStreamSynchronize(s);
-            if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "LD finish: %s", hipGetErrorString(e));
-        }
-        return GARLIC_OK;
-    }
-    // ordered sums: LDS-tiled kernel (one thread per column of the LD row) unless the window is too wide
-    // ... thread = SNP of the window, accumulators = window starts (ld_sum_col_kernel: 32 < W <= 512) unless switched off
-    const int col_threads = (winsize + 16 + WAVE - 1) / WAVE * WAVE;
-    const bool by_snp = ld_sums_by_snp(winsize);
-    const bool have_table = p->lds.fused_done && by_snp;      // the pair kernel has written the hr2 table (garlic_panel_compute_ld)
-    p->lds.fused_done = false;
-    const bool tiled = by_snp || (winsize <= LD_SUM_MAX_W && !getenv("GARLIC_LD_SUM_L2"));
-    const int sum_b = by_snp ? std::min(LD_COL_B, col_threads - winsize) : LD_SUM_B;      // (thread W + B - 1 reads one element further on odd steps)
-    // (the SNP-per-thread kernel reads one combined row of 2W doubles per SNP, in d_fwd; + 1 KB the last row's
-    // last request may run over)
-    if ((rc = d_hf.reserve(p->nloci)) || (rc = d_fwd.reserve(by_snp ? 2 * n + 256 : n)) || (!by_snp && (rc = d_bwd.reserve(n))))
-        return rc;
-    double *ld = ld_out;
-    // nobody asked for the LD matrix itself and the sum kernel writes the wLOD weights directly: it is not made at all
-    const bool weights_only = by_snp && !ld_out;
-    if (!weights_only && (where == GARLIC_HOST || !ld_out)) {
-        if ((rc = d_ld.reserve(n))) return rc;
-        ld = d_ld.p;
-    }
-    // initLDData zero-fills; ld_sum_col_kernel writes every entry of the window starts that have a full window, which
-    // leaves the last W - 1 rows of each chromosome
-    if (weights_only) {
-    } else if (by_snp) {
-        for (int c = 0; c < p->nchr && e == hipSuccess; c++) {
-            const int64_t lo = p->chr_off[c], hi = p->chr_off[c + 1], from = std::max(lo, hi - winsize + 1);
-            if (hi > from) e = hipMemsetAsync(ld + from * winsize, 0, sizeof(double) * (size_t)(hi - from) * winsize, s);
-        }
-    } else {
-        e = hipMemsetAsync(ld, 0, sizeof(double) * n, s);
-    }
-    if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "LD finish: %s", hipGetErrorString(e));
-    if (phased) {       // r2 takes FreqData::freq where hr2 takes homFreq (garlic-data.cpp:587-588)
-        e = hipMemcpyAsync(d_hf.p, p->freq.data(), sizeof(double) * p->nloci, hipMemcpyHostToDevice, s);
-        if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "LD finish: %s", hipGetErrorString(e));
-    } else {
-        hipLaunchKernelGGL(ld_homfreq_kernel, dim3((unsigned)((p->nloci + 255) / 256)), dim3(256), 0, s, loc,
-                           p->nloci, d_hf.p);
-    }
-    std::vector<LdSumChr> sum_chrs;
-    int64_t sum_blocks = 0;
-    for (int c = 0; tiled && c < p->nchr; c++) {
-        const int64_t nstarts = p->chr_off[c + 1] - p->chr_off[c] - winsize + 1;
-        if (nstarts < 1) continue;
-        sum_chrs.push_back(LdSumChr{p->chr_off[c], nstarts, sum_blocks});
-        sum_blocks += (nstarts + sum_b - 1) / sum_b;
-    }
-    if (tiled && (rc = d_sum_chrs.reserve(std::max<size_t>(sum_chrs.size(), 1)))) return rc;
-    if (by_snp && (rc = reserve_skew(p, winsize, false))) return rc;      // the sum kernel writes the wLOD weights as well
-    for (int c = 0; c < p->nchr; c++) {
-        const int64_t lo = p->chr_off[c], hi = p->chr_off[c + 1];
-        const size_t hr2_lds = sizeof(double) * (LD_HR2_T + winsize + (size_t)LD_HR2_T * (winsize + 1));
-        if (have_table)
-            ;
-        else if (by_snp && hr2_lds <= 64 * 1024 && !getenv("GARLIC_LD_HR2_PLAIN"))
-            hipLaunchKernelGGL(ld_hr2_tile_kernel, dim3((unsigned)((hi - lo + LD_HR2_T - 1) / LD_HR2_T)), dim3(256),
-                               hr2_lds, s, pair, d_hf.p, lo, hi, winsize, d_fwd.p);
-        else if (by_snp)
-            hipLaunchKernelGGL(ld_hr2_kernel<true>, dim3((unsigned)(hi - lo)), dim3(128), 0, s, pair, d_hf.p, lo, hi,
-                               winsize, d_fwd.p, (double *)nullptr);
-        else
-            hipLaunchKernelGGL(ld_hr2_kernel<false>, dim3((unsigned)(hi - lo)), dim3(256), 0, s, pair, d_hf.p, lo, hi,
-                               winsize, d_fwd.p, d_bwd.p);
-        if (hi - lo >= winsize && !tiled)
-            hipLaunchKernelGGL(ld_sum_kernel, dim3((unsigned)(hi - lo - winsize + 1)), dim3(256), 0, s, d_fwd.p, d_bwd.p,
-                               lo, winsize, ld);
-    }
-    if (tiled && !sum_chrs.empty()) {   // all chromosomes in one grid, after every hr2 value exists
-        e = hipMemcpyAsync(d_sum_chrs.p, sum_chrs.data(), sizeof(LdSumChr) * sum_chrs.size(), hipMemcpyHostToDevice, s);
-        if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "LD finish: %s", hipGetErrorString(e));
-        const int threads = by_snp ? col_threads : (winsize + WAVE - 1) / WAVE * WAVE;
-        const int col_pieces = (threads * 8 + 1023) / 1024;
-        const size_t lds = by_snp ? sizeof(double) * std::max<size_t>((size_t)LD_COL_BATCH * LD_COL_NBATCH * col_pieces * 128 + 130, (size_t)threads * 17)
-                                  : sizeof(double) * 2 * (2 * (size_t)winsize - 1 + 128 + threads);
-        // (the call's dominant kernel: its HIP-event time is what garlic_recent_kernel_ms reports for an LD call)
-        garlic_ctx *ctx = p->ctx;
-        const int slot = (int)(ctx->n_calls % garlic_ctx::HIST);
-        (void)hipEventRecord(ctx->hist0[slot], s);
-        if (by_snp) {
-            static_assert(LD_COL_MAX_THREADS <= 128 * LD_COL_MAX_PIECES, "one instantiation per request count");
-            const void *fn = col_pieces == 1 ? (const void *)ld_sum_col_kernel<1> : col_pieces == 2 ? (const void *)ld_sum_col_kernel<2>
-                           : col_pieces == 3 ? (const void *)ld_sum_col_kernel<3> : col_pieces == 4 ? (const void *)ld_sum_col_kernel<4>
-                                                                                                    : (const void *)ld_sum_col_kernel<5>;
-            if (lds > 48 * 1024) {
-                e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "LD finish: %s", hipGetErrorString(e));
-            }
-            const double *a_c = d_fwd.p;
-            const LdSumChr *a_chrs = d_sum_chrs.p;
-            int a_nchr = (int)sum_chrs.size(), a_w = winsize, a_b = sum_b;
-            double *a_ld = ld, *a_d = p->d_skew.p + SKEW_FRONT;
-            unsigned a_nwork = (unsigned)sum_blocks;
-            void *kargs[] = {(void *)&a_c, (void *)&a_chrs, (void *)&a_nchr, (void *)&a_w, (void *)&a_b, (void *)&a_ld, (void *)&a_d, (void *)&a_nwork};
-            e = hipLaunchKernel(fn, dim3((a_nwork + 7u) / 8u * 8u), dim3(threads), kargs, lds, s);
-            if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "LD finish: %s", hipGetErrorString(e));
-        }
-        else
-            hipLaunchKernelGGL(ld_sum_tiled_kernel, dim3((unsigned)sum_blocks), dim3(threads), lds, s, d_fwd.p, d_bwd.p,
-                               d_sum_chrs.p, (int)sum_chrs.size(), winsize, ld);
-        (void)hipEventRecord(ctx->hist1[slot], s);
-        ctx->n_calls++;
-    }
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "LD finish: %s", hipGetErrorString(e));
-    if ((rc = install_ld(p, winsize, ld, by_snp))) return rc;
-    if (where == GARLIC_HOST && ld_out) {
-        e = hipMemcpyAsync(ld_out, ld, sizeof(double) * n, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "LD finish: %s", hipGetErrorString(e));
-    }
-    return GARLIC_OK;
+    return ld_finish_to(p, ld_form(p, winsize, phased), locus_counts, pair_counts, false, ld_out, where == GARLIC_HOST, false);
+}
+
+// counts and finish on the panel's scratch (kept with the panel, as all LD scratch), fused where the form allows
+static int ld_compute(garlic_panel *p, const LdForm &f, const std::vector<uint64_t> &sub, double *ld_out, bool host_out, bool keep_sets)
+{
+    int rc;
+    DevBuf<int32_t> &d_loc = p->lds.loc, &d_pair = p->lds.pair;
+    if ((rc = d_loc.reserve((size_t)p->nloci * 2)) || (rc = d_pair.reserve(f.fusable ? 2 : (size_t)p->nloci * f.W * 2))) return rc;
+    if ((rc = ld_counts_run(p, f, sub, d_loc.p, d_pair.p, f.fusable))) return rc;
+    return ld_finish_to(p, f, d_loc.p, d_pair.p, f.fusable, ld_out, host_out, keep_sets);
 }
 
 int garlic_panel_compute_ld(garlic_panel *p, int32_t winsize, int32_t phased, const int32_t *sub_idx,
@@ -3077,40 +3144,19 @@ int garlic_panel_compute_ld(garlic_panel *p, int32_t winsize, int32_t phased, co
 {
     int rc;
     if ((rc = ld_check(p, winsize, phased))) return rc;
-    DevBuf<int32_t> &d_loc = p->lds.loc, &d_pair = p->lds.pair;   // kept with the panel, as all LD scratch
-    // every individual's counts are here: the pair kernel can go on to the hr2 values, no pair table (GARLIC_LD_UNFUSED:
-    // the two steps of garlic_ld_counts / garlic_ld_finish, which a sharded panel needs)
-    const bool fuse = ld_pairs_on_mfma(winsize, phased) && ld_sums_by_snp(winsize) && !getenv("GARLIC_LD_UNFUSED");
-    if ((rc = d_loc.reserve((size_t)p->nloci * 2)) || (rc = d_pair.reserve(fuse ? 2 : (size_t)p->nloci * winsize * 2)))
-        return rc;
-    p->lds.fuse_request = fuse;
-    if ((rc = garlic_ld_counts(p, winsize, phased, sub_idx, n_sub, d_loc.p, d_pair.p, GARLIC_DEVICE))) {
-        p->lds.fuse_request = false;
-        return rc;
-    }
-    if (where == GARLIC_DEVICE || !ld_out)
-        return garlic_ld_finish(p, winsize, phased, d_loc.p, d_pair.p, ld_out, GARLIC_DEVICE);
-    // host output: finish on the device, then copy out
-    DevBuf<double> &d_ld = p->lds.ld;
-    if ((rc = d_ld.reserve((size_t)p->nloci * winsize))) return rc;
-    rc = garlic_ld_finish(p, winsize, phased, d_loc.p, d_pair.p, d_ld.p, GARLIC_DEVICE);
-    if (rc == GARLIC_OK) {
-        hipError_t e = hipMemcpy(ld_out, d_ld.p, sizeof(double) * p->nloci * winsize, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = fail(GARLIC_ERR_HIP, "LD copy-out: %s", hipGetErrorString(e));
-    }
-    return rc;
+    std::vector<uint64_t> sub;
+    if ((rc = ld_sub_bitmap(p, sub_idx, n_sub, sub))) return rc;
+    return ld_compute(p, ld_form(p, winsize, phased), sub, ld_out, where != GARLIC_DEVICE, false);
 }
 
 // ---- LD weights of several window sizes from shared passes (ld_multi_kernel.hpp; the rule is stated in garlic_hip.h)
-static int ld_col_threads(int32_t winsize) { return (winsize + 16 + WAVE - 1) / WAVE * WAVE; }
-
 struct LdMultiPlan {
     std::vector<int32_t> uniq;                     // the distinct sizes, ascending
     std::vector<std::vector<int32_t>> groups;      // the shared passes (ascending), then the sizes on their own (ascending)
     size_t n_shared = 0;                           // groups [0, n_shared) go through ld_sum_multi_kernel
     int32_t wtab = 0;                              // the widest shared size: the pitch of their one pair table
 };
-static LdMultiPlan ld_multi_plan(const int32_t *winsizes, int32_t n_sizes)
+static LdMultiPlan ld_multi_plan(const garlic_panel *p, const int32_t *winsizes, int32_t n_sizes, int32_t phased)
 {
     LdMultiPlan plan;
     plan.uniq.assign(winsizes, winsizes + n_sizes);
@@ -3118,20 +3164,22 @@ static LdMultiPlan ld_multi_plan(const int32_t *winsizes, int32_t n_sizes)
     plan.uniq.erase(std::unique(plan.uniq.begin(), plan.uniq.end()), plan.uniq.end());
     const char *solo_env = getenv("GARLIC_LD_MULTI_SOLO");
     const bool solo = solo_env && atoi(solo_env) != 0;
-    std::vector<int32_t> sharing, alone;
-    for (int32_t w : plan.uniq) (!solo && ld_sums_by_snp(w) ? sharing : alone).push_back(w);
-    if (sharing.size() < 2) {                      // nothing to share a pass with
-        alone = plan.uniq;
-        sharing.clear();
+    std::vector<LdForm> sharing;                   // the sizes whose sums go by SNP, with their forms
+    std::vector<int32_t> alone;
+    for (int32_t w : plan.uniq) {
+        const LdForm f = ld_form(p, w, phased);
+        if (!solo && f.sum == LdSum::col) sharing.push_back(f);
+        else alone.push_back(w);
     }
-    for (int32_t w : sharing) {
+    if (sharing.size() < 2) { alone = plan.uniq; sharing.clear(); }      // nothing to share a pass with
+    for (const LdForm &f : sharing) {
         const bool fits = !plan.groups.empty() && plan.groups.back().size() < (size_t)LDM_MAX_SIZES &&
-                          ldms_lds_bytes(ld_col_threads(w), (int)plan.groups.back().size()) <= LDMS_LDS_MAX;
+                          ldms_lds_bytes(f.col_threads, (int)plan.groups.back().size()) <= LDMS_LDS_MAX;
         if (!fits) plan.groups.emplace_back();
-        plan.groups.back().push_back(w);
+        plan.groups.back().push_back(f.W);
     }
     plan.n_shared = plan.groups.size();
-    plan.wtab = sharing.empty() ? 0 : sharing.back();
+    plan.wtab = sharing.empty() ? 0 : sharing.back().W;
     for (int32_t w : alone) plan.groups.push_back(std::vector<int32_t>{w});
     return plan;
 }
@@ -3151,47 +3199,21 @@ static std::unique_ptr<garlic_panel::LdSet> ld_pool_take(LdSetPool &pool, int32_
     return set;
 }
 
-// the combined table C at pitch 2 W from pair counts at pitch W (garlic_ld_finish's hr2 stage for ld_sum_col_kernel)
-static int ld_build_table(garlic_panel *p, int32_t W, int32_t phased, const int32_t *loc, const int32_t *pair)
-{
-    int rc;
-    hipStream_t s = p->ctx->stream;
-    const size_t n = (size_t)p->nloci * W;
-    if ((rc = p->lds.hf.reserve(p->nloci)) || (rc = p->lds.fwd.reserve(2 * n + 256))) return rc;
-    if (phased)
-        HIP_TRY(hipMemcpyAsync(p->lds.hf.p, p->freq.data(), sizeof(double) * p->nloci, hipMemcpyHostToDevice, s));
-    else
-        hipLaunchKernelGGL(ld_homfreq_kernel, dim3((unsigned)((p->nloci + 255) / 256)), dim3(256), 0, s, loc, p->nloci, p->lds.hf.p);
-    const size_t hr2_lds = sizeof(double) * (LD_HR2_T + W + (size_t)LD_HR2_T * (W + 1));
-    for (int c = 0; c < p->nchr; c++) {
-        const int64_t lo = p->chr_off[c], hi = p->chr_off[c + 1];
-        if (hr2_lds <= 64 * 1024 && !getenv("GARLIC_LD_HR2_PLAIN"))
-            hipLaunchKernelGGL(ld_hr2_tile_kernel, dim3((unsigned)((hi - lo + LD_HR2_T - 1) / LD_HR2_T)), dim3(256), hr2_lds, s, pair,
-                               p->lds.hf.p, lo, hi, W, p->lds.fwd.p);
-        else
-            hipLaunchKernelGGL(ld_hr2_kernel<true>, dim3((unsigned)(hi - lo)), dim3(128), 0, s, pair, p->lds.hf.p, lo, hi, W,
-                               p->lds.fwd.p, (double *)nullptr);
-    }
-    HIP_TRY(hipGetLastError());
-    return GARLIC_OK;
-}
-
-// one shared pass: the sizes g (ascending, distinct) from the table of pitch 2 wtab in lds.fwd; dev_ld[i]: LD matrix of g[i] or NULL
-static int ld_multi_group(garlic_panel *p, const std::vector<int32_t> &g, int32_t gid, int32_t wtab, double *const *dev_ld,
+// one shared pass: the sizes g (ascending, distinct; f: the form of the widest) from the table of pitch 2 wtab in lds.fwd;
+// dev_ld[i]: LD matrix of g[i] or NULL
+static int ld_multi_group(garlic_panel *p, const LdForm &f, const std::vector<int32_t> &g, int32_t gid, int32_t wtab, double *const *dev_ld,
                           LdSetPool &pool)
 {
     int rc;
     hipStream_t s = p->ctx->stream;
     const int32_t W = g.back(), wmin = g.front();
-    const int threads = ld_col_threads(W), B = std::min(LD_COL_B, threads - W), pieces = (threads * 8 + 1023) / 1024;
-    const size_t lds = ldms_lds_bytes(threads, (int)g.size() - 1);
     std::vector<LdMultiChr> chrs;
     int64_t blocks = 0;
     for (int c = 0; c < p->nchr; c++) {
         const int64_t lo = p->chr_off[c], hi = p->chr_off[c + 1], nstarts = hi - lo - wmin + 1;
         if (nstarts < 1) continue;
         chrs.push_back(LdMultiChr{lo, hi, nstarts, blocks});
-        blocks += (nstarts + B - 1) / B;
+        blocks += (nstarts + f.sum_b - 1) / f.sum_b;
     }
     std::vector<std::unique_ptr<garlic_panel::LdSet>> sets;
     LdMultiSmall small{};
@@ -3200,11 +3222,7 @@ static int ld_multi_group(garlic_panel *p, const std::vector<int32_t> &g, int32_
         sets.push_back(ld_pool_take(pool, g[i]));
         sets.back()->group = gid;
         if ((rc = reserve_skew_buf(p, sets.back()->skew, g[i], false))) return rc;
-        // initLDData zero-fills: the rows without a full window of the size (the kernel writes every other entry)
-        for (int c = 0; dev_ld[i] && c < p->nchr; c++) {
-            const int64_t lo = p->chr_off[c], hi = p->chr_off[c + 1], from = std::max<int64_t>(lo, hi - g[i] + 1);
-            if (hi > from) HIP_TRY(hipMemsetAsync(dev_ld[i] + from * g[i], 0, sizeof(double) * (size_t)(hi - from) * g[i], s));
-        }
+        if (dev_ld[i] && (rc = ld_zero_short_rows(p, g[i], dev_ld[i]))) return rc;
         if (i + 1 < g.size()) {
             small.w[i] = g[i];
             small.ld[i] = dev_ld[i];
@@ -3212,26 +3230,11 @@ static int ld_multi_group(garlic_panel *p, const std::vector<int32_t> &g, int32_
         }
     }
     if (!chrs.empty()) {
-        if ((rc = p->lds.multi_chrs.reserve(chrs.size()))) return rc;
-        HIP_TRY(hipMemcpyAsync(p->lds.multi_chrs.p, chrs.data(), sizeof(LdMultiChr) * chrs.size(), hipMemcpyHostToDevice, s));
-        static_assert(LD_COL_MAX_THREADS <= 128 * LD_COL_MAX_PIECES, "one instantiation per request count");
-        const void *fn = pieces == 1 ? (const void *)ld_sum_multi_kernel<1> : pieces == 2 ? (const void *)ld_sum_multi_kernel<2>
-                       : pieces == 3 ? (const void *)ld_sum_multi_kernel<3> : pieces == 4 ? (const void *)ld_sum_multi_kernel<4>
-                                                                                         : (const void *)ld_sum_multi_kernel<5>;
-        if (lds > 48 * 1024) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        const double *a_c = p->lds.fwd.p;
-        const LdMultiChr *a_chrs = p->lds.multi_chrs.p;
-        int a_nchr = (int)chrs.size(), a_wtab = wtab, a_w = W, a_b = B;
-        double *a_ld = dev_ld[g.size() - 1], *a_d = sets.back()->skew.p + SKEW_FRONT;
-        unsigned a_nwork = (unsigned)blocks;
-        void *kargs[] = {(void *)&a_c, (void *)&a_chrs, (void *)&a_nchr, (void *)&a_wtab, (void *)&a_w, (void *)&a_b, (void *)&small,
-                         (void *)&a_ld, (void *)&a_d, (void *)&a_nwork};
-        garlic_ctx *ctx = p->ctx;
-        const int slot = (int)(ctx->n_calls % garlic_ctx::HIST);
-        (void)hipEventRecord(ctx->hist0[slot], s);
-        HIP_TRY(hipLaunchKernel(fn, dim3((a_nwork + 7u) / 8u * 8u), dim3(threads), kargs, lds, s));
-        (void)hipEventRecord(ctx->hist1[slot], s);
-        ctx->n_calls++;
+        if ((rc = p->lds.multi_chrs.put(chrs, s))) return rc;
+        decltype(&ld_sum_multi_kernel<1>) const fns[] = LD_COL_FNS(ld_sum_multi_kernel);
+        if ((rc = ld_launch_col(p, f, fns, small.n, (unsigned)blocks, p->lds.fwd.p, p->lds.multi_chrs.p, (int)chrs.size(), wtab, W, f.sum_b, small,
+                                dev_ld[g.size() - 1], sets.back()->skew.p + SKEW_FRONT)))
+            return rc;
         HIP_TRY(hipStreamSynchronize(s));          // chrs (host) is read by the copy above
     }
     p->ld_sum_passes++;
@@ -3239,9 +3242,9 @@ static int ld_multi_group(garlic_panel *p, const std::vector<int32_t> &g, int32_
     return GARLIC_OK;
 }
 
-// counts == false: garlic_panel_compute_ld_multi (sub_idx, n_sub); counts == true: garlic_ld_finish_multi (loc, pair_all: device
-// pointers, the pair counts at pitch wall)
-static int ld_multi_run(garlic_panel *p, const LdMultiPlan &plan, int32_t phased, bool counts, const int32_t *sub_idx, int32_t n_sub,
+// counts == false: garlic_panel_compute_ld_multi (sub: the subsample's bitmap); counts == true: garlic_ld_finish_multi (loc, pair_all:
+// device pointers, the pair counts at pitch wall)
+static int ld_multi_run(garlic_panel *p, const LdMultiPlan &plan, int32_t phased, bool counts, const std::vector<uint64_t> &sub,
                         const int32_t *loc, const int32_t *pair_all, int32_t wall, double *const *dev_ld /* per plan.uniq */)
 {
     int rc;
@@ -3264,45 +3267,42 @@ static int ld_multi_run(garlic_panel *p, const LdMultiPlan &plan, int32_t phased
         *out = d_pair.p;
         return GARLIC_OK;
     };
-    if (plan.n_shared > 0) {
-        const int32_t wtab = plan.wtab;
-        bool have_table = false;
+    if (plan.n_shared > 0) {             // one table at the widest shared size, in lds.fwd across all the shared groups
+        const LdForm ftab = ld_form(p, plan.wtab, phased);
+        const bool fuse = !counts && ftab.fusable;
         const int32_t *pair = nullptr;
         if (!counts) {
-            const bool fuse = ld_pairs_on_mfma(wtab, phased) && ld_sums_by_snp(wtab) && !getenv("GARLIC_LD_UNFUSED");
-            if ((rc = d_loc.reserve((size_t)p->nloci * 2)) || (rc = d_pair.reserve(fuse ? 2 : (size_t)p->nloci * wtab * 2))) return rc;
-            p->lds.fuse_request = fuse;
-            if ((rc = garlic_ld_counts(p, wtab, phased, sub_idx, n_sub, d_loc.p, d_pair.p, GARLIC_DEVICE))) {
-                p->lds.fuse_request = false;
-                return rc;
-            }
-            have_table = p->lds.fused_done;
-            p->lds.fused_done = false;
+            if ((rc = d_loc.reserve((size_t)p->nloci * 2)) || (rc = d_pair.reserve(fuse ? 2 : (size_t)p->nloci * plan.wtab * 2))) return rc;
+            if ((rc = ld_counts_run(p, ftab, sub, d_loc.p, d_pair.p, fuse))) return rc;
             loc = d_loc.p;
             pair = d_pair.p;
-        } else if ((rc = pair_at(wtab, &pair))) {
+        } else if ((rc = pair_at(plan.wtab, &pair))) {
             return rc;
         }
         p->ld_pair_passes++;
-        if (!have_table && (rc = ld_build_table(p, wtab, phased, loc, pair))) return rc;
+        if (!fuse && ((rc = ld_hf(p, ftab, loc)) || (rc = ld_build_table(p, ftab, pair)))) return rc;
         for (size_t g = 0; g < plan.n_shared; g++) {
             std::vector<double *> outs;
             for (int32_t w : plan.groups[g]) outs.push_back(out_of(w));
-            if ((rc = ld_multi_group(p, plan.groups[g], (int32_t)g, wtab, outs.data(), pool))) return rc;
+            if ((rc = ld_multi_group(p, ld_form(p, plan.groups[g].back(), phased), plan.groups[g], (int32_t)g, plan.wtab, outs.data(), pool)))
+                return rc;
         }
     }
-    for (size_t g = plan.n_shared; g < plan.groups.size(); g++) {       // today's single-size path, then the set joins the others
+    // the sizes on their own, as single-size calls; after the shared groups, whose table and counts they overwrite.  Each set
+    // then joins the others
+    for (size_t g = plan.n_shared; g < plan.groups.size(); g++) {
         const int32_t w = plan.groups[g][0];
+        const LdForm f = ld_form(p, w, phased);
         std::unique_ptr<garlic_panel::LdSet> set = ld_pool_take(pool, w);
         std::swap(set->skew.p, p->d_skew.p);
         std::swap(set->skew.cap, p->d_skew.cap);
         set.reset();
         if (!counts) {
-            rc = garlic_panel_compute_ld(p, w, phased, sub_idx, n_sub, out_of(w), GARLIC_DEVICE);
+            rc = ld_compute(p, f, sub, out_of(w), false, true);
         } else {
             const int32_t *pair = nullptr;
             if ((rc = pair_at(w, &pair))) return rc;
-            rc = garlic_ld_finish(p, w, phased, loc, pair, out_of(w), GARLIC_DEVICE);
+            rc = ld_finish_to(p, f, loc, pair, false, out_of(w), false, true);
         }
         if (rc) return rc;
         p->ld_pair_passes++;
@@ -3324,7 +3324,7 @@ static int ld_multi_call(garlic_panel *p, const int32_t *winsizes, int32_t n_siz
     if (counts && (!locus_counts || !pair_counts)) return fail(GARLIC_ERR_INVALID, "count buffers are required");
     if (!counts && (n_sub < 0 || (n_sub > 0 && !sub_idx))) return fail(GARLIC_ERR_INVALID, "bad LD subsample");
     hipStream_t s = p->ctx->stream;
-    const LdMultiPlan plan = ld_multi_plan(winsizes, n_sizes);
+    const LdMultiPlan plan = ld_multi_plan(p, winsizes, n_sizes, phased);
     const int32_t wall = plan.uniq.back();
     // one device LD matrix per distinct size somebody wants: the caller's (device) or a temporary (host)
     std::vector<std::unique_ptr<DevBuf<double>>> tmp;
@@ -3348,9 +3348,9 @@ static int ld_multi_call(garlic_panel *p, const int32_t *winsizes, int32_t n_siz
         locus_counts = in_loc.p;
         pair_counts = in_pair.p;
     }
-    p->ld_multi_active = true;
-    rc = ld_multi_run(p, plan, phased, counts, sub_idx, n_sub, locus_counts, pair_counts, wall, dev_ld.data());
-    p->ld_multi_active = false;
+    std::vector<uint64_t> sub;
+    rc = counts ? GARLIC_OK : ld_sub_bitmap(p, sub_idx, n_sub, sub);
+    if (!rc) rc = ld_multi_run(p, plan, phased, counts, sub, locus_counts, pair_counts, wall, dev_ld.data());
     (void)hipStreamSynchronize(s);
     if (rc) {                                       // no LD weights stay installed
         drop_all_ld(p);
@@ -3360,9 +3360,7 @@ static int ld_multi_call(garlic_panel *p, const int32_t *winsizes, int32_t n_siz
         if (!ld_out[i]) continue;
         const size_t u = std::lower_bound(plan.uniq.begin(), plan.uniq.end(), winsizes[i]) - plan.uniq.begin();
         if (ld_out[i] == dev_ld[u]) continue;
-        hipError_t e = hipMemcpy(ld_out[i], dev_ld[u], sizeof(double) * p->nloci * winsizes[i],
-                                 where == GARLIC_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice);
-        if (e != hipSuccess) { drop_all_ld(p); return fail(GARLIC_ERR_HIP, "LD copy-out: %s", hipGetErrorString(e)); }
+        if ((rc = ld_copy_out(ld_out[i], dev_ld[u], (size_t)p->nloci * winsizes[i], where))) { drop_all_ld(p); return rc; }
     }
     select_ld(p, winsizes[0]);
     return GARLIC_OK;

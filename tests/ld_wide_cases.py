@@ -2,9 +2,9 @@
 without a GPU.
 
   nblk_of        the block count garlic_panel_create gives a panel (nind_pad / 64), restated
-  pair_kernel    which pair kernel garlic_ld_counts picks -- a RESTATEMENT of the rule in garlic_ld_counts and
-                 ld_pairs_on_mfma (garlic_amd/csrc/garlic_hip.hip), kept here so that the case table can be checked without a
-                 GPU; when the rule there changes, this one follows it
+  pair_kernel    which pair kernel an LD call picks -- a RESTATEMENT of the rule in ld_form (LdForm::pair,
+                 garlic_amd/csrc/garlic_hip.hip), kept here so that the case table can be checked without a GPU; when the rule
+                 there changes, this one follows it
   staging        the block-staging paths of ld_kernels.hpp / ld_pair_mfma_kernel a (kernel, nblk) reaches, restated likewise
   wide_chroms    panels whose 64-individual blocks differ from one another, so that a block swapped, skipped or repeated
                  changes the integer counts
@@ -23,7 +23,7 @@ WAVE = 64
 LD_SMALL_MAX_W = 16        # ld_kernels.hpp
 LD_LANE_T = 256
 LD_PAIR_BLK = 8
-LD_LANE_STAGE = 4          # garlic_ld_counts' default of GARLIC_LD_LANE_STAGE
+LD_LANE_STAGE = 4          # ld_form's default of GARLIC_LD_LANE_STAGE
 PLANES_TRIP = 32           # ld_planes_kernel: 4 waves x 8 blocks per outer trip
 
 PAIR_SWITCHES = ["GARLIC_LD_PAIR_TILED", "GARLIC_LD_PAIR_L2", "GARLIC_LD_PAIR_NO_MFMA", "GARLIC_LD_PAIR_FLAT",
@@ -47,7 +47,7 @@ def lane_stage_of(nblk, switches=None):
 
 
 def pair_kernel(winsize, phased, nblk, switches=None):
-    """'mfma' | 'lane' | 'tiled' | 'flat' | 'plain' | 'plain_phased': the pair kernel of garlic_ld_counts.  switches: {name:
+    """'mfma' | 'lane' | 'tiled' | 'flat' | 'plain' | 'plain_phased': the pair kernel ld_form picks (LdPair).  switches: {name:
     value} of the GARLIC_LD_* variables that are set (a set variable counts whatever its value, as getenv() != NULL does)"""
     sw = switches or {}
     w = int(winsize)

@@ -293,3 +293,22 @@ def test_ld_plane_cache_follows_genotypes_and_subsample(gpu_ctx):
         panel.set_genotypes(np.concatenate([c[0] for c in chroms2], axis=0))
         assert same(panel.compute_ld(40, sub_idx=sub), oracle_ld(chroms2, 40, sub))
         assert same(panel.compute_ld(40), oracle_ld(chroms2, 40))
+
+
+@pytest.mark.parametrize("unfused", [False, True])
+def test_ld_finish_after_a_fused_compute_builds_its_own_table(gpu_ctx, monkeypatch, unfused):
+    """W = 40 unphased is the matrix-core pair kernel with the sums by SNP: compute_ld fuses, and the hr2 table it leaves in
+    the panel's scratch is subsample B's.  A stand-alone ld_finish with subsample A's counts must build A's table, not sum the
+    one that is there; the same sequence under GARLIC_LD_UNFUSED"""
+    if unfused:
+        monkeypatch.setenv("GARLIC_LD_UNFUSED", "1")
+    rng = np.random.default_rng(4040)
+    W, nind = 40, 70
+    chroms = [ol.random_panel(rng, 300, nind, max_gap=10 ** 9, gaps=0, miss=0.05)]
+    sub_a = np.sort(rng.choice(nind, size=30, replace=False)).astype(np.int32)
+    sub_b = np.sort(rng.choice(nind, size=45, replace=False)).astype(np.int32)
+    assert not np.array_equal(sub_a, sub_b)
+    with make_panel(gpu_ctx, chroms, nind) as panel:
+        loc, pair = panel.ld_counts(W, sub_idx=sub_a)
+        assert same(panel.compute_ld(W, sub_idx=sub_b), oracle_ld(chroms, W, sub_b))
+        assert same(panel.ld_finish(W, loc, pair), oracle_ld(chroms, W, sub_a))
