@@ -258,9 +258,10 @@ struct garlic_panel {
     bool glterms_valid = false, glterms_scaled = false;   // scaled: holds (term * nomut) * norec of (glterms_M, glterms_mu)
     int32_t glterms_M = 0;
     double glterms_mu = 0.0;
-    // ... or, under garlic_panel_set_tgls_term_budget, two slab buffers [blk - b0][GOFF+nloci+pad][64] that every unweighted
-    // use_gl call fills and reads slab by slab (launch_tgls_slabs): slab k + 1 is built on slab_stream while the chain of
-    // slab k runs on the context's stream, ordered by the events alone
+    // ... or, under garlic_panel_set_tgls_term_budget, two slab buffers [blk - b0][GOFF+nloci+pad][64] that every use_gl call
+    // fills and reads slab by slab (for_each_tgls_slab) -- raw terms for the unweighted chains, scaled ones for the weighted
+    // kernels, in the same two buffers: slab k + 1 is built on slab_stream while the kernels of slab k run on the context's
+    // stream, ordered by the events alone
     int64_t terms_budget = 0;                      // 0: whole matrix or none; > 0: bytes; -1: from the free memory
     DevBuf<double> d_slab[2];
     hipStream_t slab_stream = nullptr;
@@ -405,7 +406,8 @@ struct garlic_panel {
         int feed_per_cu = 1;      // persistent workgroups per CU the feed kernel of this plan is launched with (feed_grid)
         int32_t n_tiles = 0, n_segs = 0, n_strips = 0, n_feed_blocks = 0;
         int64_t n_runs = 0, n_valid = 0;
-        struct Slab { int32_t b0, b1; size_t item0, n_items; };   // panel blocks [b0, b1); its items: [item0, item0 + n_items)
+        // panel blocks [b0, b1); its items: [item0, item0 + n_items); wlod_feed: its blocks in play, [fb0, fb0 + n_fb) of d_feed_blocks
+        struct Slab { int32_t b0, b1; size_t item0, n_items; int32_t fb0 = 0, n_fb = 0; };
         std::vector<Slab> slabs;
     } plan;
 };
@@ -1215,9 +1217,11 @@ void release_tgls_slabs(garlic_panel *p)
     p->d_slab[1].release();
 }
 
-// The unweighted use_gl call at hand: *slab_blocks > 0 when its terms are to come slab by slab, 0 when the whole matrix (or,
-// declined, the look-up chain) serves it as before.  Dictionary-coded panels only; GARLIC_GL_NO_TERMS keeps its meaning.
-int tgls_terms_or_slabs(garlic_panel *p, int32_t *slab_blocks)
+// What holds the terms of the use_gl call at hand -- raw ones for the unweighted chains, scaled by the decay factors of (M, mu)
+// for the weighted kernels (ensure_decay_table first): *slab_blocks > 0 when they are to come slab by slab; 0 when the whole
+// matrix serves it as before or, declined, nothing does (glterms_valid / glterms_scaled tell: the caller then looks its terms
+// up).  Dictionary-coded panels only; GARLIC_GL_NO_TERMS keeps its meaning.
+int tgls_terms_or_slabs(garlic_panel *p, int32_t *slab_blocks, bool scaled = false, int32_t M = 0, double mu = 0.0)
 {
     *slab_blocks = 0;
     const size_t block = tgls_block_bytes(p), whole = block * (size_t)(p->nind_pad / WAVE);
@@ -1227,19 +1231,19 @@ int tgls_terms_or_slabs(garlic_panel *p, int32_t *slab_blocks)
             HIP_TRY(hipStreamSynchronize(p->ctx->stream));
             release_tgls_slabs(p);
         }
-        return ensure_gl_terms(p);
+        return ensure_gl_terms(p, scaled, M, mu);
     }
     size_t bytes = (size_t)p->terms_budget;
     if (p->terms_budget < 0) {
         // the whole matrix when today's test lets it in; otherwise two slab buffers in half of what is free now
-        if ((rc = ensure_gl_terms(p))) return rc;
-        if (p->glterms_valid && !p->glterms_scaled) return GARLIC_OK;
+        if ((rc = ensure_gl_terms(p, scaled, M, mu))) return rc;
+        if (p->glterms_valid && p->glterms_scaled == scaled) return GARLIC_OK;
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return GARLIC_OK;
         bytes = (free_b + (p->d_slab[0].cap + p->d_slab[1].cap) * sizeof(double)) / 2;
         if (!tgls_slab_blocks_for(p, bytes)) return GARLIC_OK;     // not even one-block slabs: the look-up chain
     } else if (p->d_glterms.cap) {
-        // a whole matrix from before the budget (or the scaled one of a weighted call, which the budget does not bind)
+        // a whole matrix, raw or scaled, from before the budget
         HIP_TRY(hipStreamSynchronize(p->ctx->stream));
         p->d_glterms.release();
         p->glterms_valid = false;
@@ -1324,7 +1328,8 @@ struct LodForm {
     size_t tile_lds = 0;           // dynamic LDS of the tile kernels
     bool aligned16 = false;        // finish_form: every score row 16-byte aligned
     bool strip_three = false;      // finish_form: the 80-VGPR strip kernel, three workgroups per CU
-    int32_t slab_blocks = 0;       // tgls_ring / tgls_feed: the term matrix comes slab by slab, this many blocks each
+    int32_t slab_blocks = 0;       // tgls_ring / tgls_feed, and with wlod_gl the tuned wLOD kernels and wlod_feed: the term matrix
+                                   // comes slab by slab, this many blocks each
 };
 
 int check_lod_args(const garlic_panel *p, const LodCall &c)
@@ -1400,8 +1405,8 @@ int decide_form(garlic_panel *p, const LodCall &c, LodForm &f)
         if (f.cov_bits) return fail(GARLIC_ERR_STATE, "internal: coverage bits with thinned output");
         if (W + 64 > GPAD_BACK) return GARLIC_INTERNAL_NO_SAMPLED;
         if (f.use_gl) {
-            if ((rc = ensure_gl_terms(p, true, c.M, c.mu))) return rc;
-            if (!(p->glterms_valid && p->glterms_scaled)) return GARLIC_INTERNAL_NO_SAMPLED;   // (the term matrix was declined)
+            if ((rc = tgls_terms_or_slabs(p, &f.slab_blocks, true, c.M, c.mu))) return rc;
+            if (!f.slab_blocks && !(p->glterms_valid && p->glterms_scaled)) return GARLIC_INTERNAL_NO_SAMPLED;   // (the term matrix was declined)
         } else if ((rc = ensure_score_rows(p, c.error, c.M, c.mu, W))) return rc;
         f.wlod_gl = f.use_gl;
         f.family = Family::wlod_feed;
@@ -1413,8 +1418,11 @@ int decide_form(garlic_panel *p, const LodCall &c, LodForm &f)
     const bool wlod_shape_ok = W + 64 <= GPAD_BACK && !getenv("GARLIC_WLOD_GENERIC") &&
                                (W >= WLOD_R || !getenv("GARLIC_WLOD_SMALL_GENERIC"));
     const bool wlod_small = W < WLOD_R;      // narrower than a window group: wlod_group_small (compiler-scheduled)
-    if (wlod_shape_ok && use_gl && (rc = ensure_gl_terms(p, true, c.M, c.mu))) return rc;
-    f.wlod_gl = wlod_shape_ok && use_gl && p->glterms_valid && p->glterms_scaled;   // (the term matrix may have been declined)
+    if (wlod_shape_ok && use_gl && (rc = tgls_terms_or_slabs(p, &f.slab_blocks, true, c.M, c.mu))) return rc;
+    // a slab launch starts at a block of the matrix: a sub-range that does not, and every shape that keeps the generic
+    // kernel, looks its terms up in the code table under a budget (nothing is built past the bound)
+    if ((c.ind_begin & (WAVE - 1)) != 0) f.slab_blocks = 0;
+    f.wlod_gl = wlod_shape_ok && use_gl && (f.slab_blocks || (p->glterms_valid && p->glterms_scaled));   // (the term matrix may have been declined)
     f.wlod_tuned = (wlod_shape_ok && !use_gl) || f.wlod_gl;
     if (f.wlod_tuned && !f.wlod_gl && sizeof(double) * (size_t)(W + TILE) * 4 + 16 > LDS_STAGING_MAX) f.wlod_tuned = false;
     if (f.wlod_tuned && !f.wlod_gl && (rc = ensure_score_rows(p, c.error, c.M, c.mu, W))) return rc;
@@ -1428,6 +1436,7 @@ int decide_form(garlic_panel *p, const LodCall &c, LodForm &f)
     if (use_gl && p->gl_cont && !f.wlod_tuned && (rc = ensure_gl_terms(p))) return rc;
     if (!f.wlod_tuned) {
         f.family = Family::wlod_generic;
+        f.slab_blocks = 0;
         return GARLIC_OK;
     }
     f.writes_bits = true;
@@ -1502,8 +1511,10 @@ int plan_lod(garlic_panel *p, const LodCall &c, const LodForm &form, const Layou
     // TGLS term slabs: one list per slab, the lists one behind the other -- a slab begins at the next block in play and
     // spans slab_blocks consecutive blocks (the subset feed's skipped blocks get no items, a slab of nothing else no launch);
     // a chain launch sees its own slab's list and queue only, longest runs first inside it.  Otherwise one list over all blocks.
+    // (The weighted kernels write MISSING themselves: their slabs are cut with no run to score too.)
+    const bool wlod_slabs = form.slab_blocks && (form.wlod_tuned || form.family == Family::wlod_feed);
     const int per_list = form.slab_blocks ? form.slab_blocks : std::max(nblk, 1);
-    for (int k0 = 0; k0 < nblk && !w.runs.empty(); ) {
+    for (int k0 = 0; k0 < nblk && (!w.runs.empty() || wlod_slabs); ) {
         if (c.blocks && !(*c.blocks)[(size_t)k0]) { k0++; continue; }
         const int k1 = std::min(nblk, k0 + per_list);
         const size_t item0 = w.items.size();
@@ -1553,6 +1564,13 @@ int plan_lod(garlic_panel *p, const LodCall &c, const LodForm &form, const Layou
         for (int k = 0; k < nblk; k++)
             if (!c.blocks || (*c.blocks)[(size_t)k]) w.feed_blocks.push_back(k);
         plan.n_feed_blocks = (int32_t)w.feed_blocks.size();
+        // term slabs: the list is ascending, so a slab's blocks in play are one stretch of it (ind_begin is 0 here)
+        size_t at = 0;
+        for (Plan::Slab &sl : plan.slabs) {
+            sl.fb0 = (int32_t)at;
+            while (at < w.feed_blocks.size() && w.feed_blocks[at] < sl.b1) at++;
+            sl.n_fb = (int32_t)at - sl.fb0;
+        }
     }
     if (form.wlod_tuned) {
         for (int k = 0; k < p->nchr; k++)
@@ -1667,19 +1685,36 @@ const void *wlod_tile_fn(Family family, bool gl, bool aligned16)
 #undef WLOD_FN
 }
 
-int launch_wlod(garlic_panel *p, const LodCall &c, const LodForm &form, const Plan &plan, double *d_out)
+// What a weighted launch reads its per-genotype scores from, and the individuals it covers: the whole scaled matrix and the
+// whole call, or one slab [b0, b1) of it (blk0 = b0: the kernels count blocks from there, variant_kernels.hpp wlod_slab_first_block)
+struct WlodTerms {
+    const double *terms;
+    int32_t blk0, ind_end, nblk;       // ind_end: one past the launch's last individual, counted from the call's ind_begin
+};
+
+WlodTerms wlod_terms_whole(const garlic_panel *p, const LodCall &c)
+{
+    return WlodTerms{p->d_glterms.p, 0, c.ind_count, (c.ind_count + WAVE - 1) / WAVE};
+}
+
+WlodTerms wlod_terms_slab(const LodCall &c, const Plan::Slab &sl, const double *terms)
+{
+    return WlodTerms{terms, sl.b0, std::min<int32_t>(c.ind_count, sl.b1 * WAVE - c.ind_begin), sl.b1 - sl.b0};
+}
+
+int launch_wlod(garlic_panel *p, const LodCall &c, const LodForm &form, const Plan &plan, double *d_out, const WlodTerms &t)
 {
     hipStream_t s = p->ctx->stream;
-    const int nblk = (c.ind_count + WAVE - 1) / WAVE;
+    const int nblk = t.nblk;
     const int per_wg = form.family == Family::wlod_tile2 ? WLOD2_BLOCKS : WLOD_WAVES;
     const int nquad = (nblk + per_wg - 1) / per_wg;
     const bool gl_ring = form.family == Family::wlod_glring || form.family == Family::wlod_strip;
     const int64_t score_rows = GOFF + p->nloci + GPAD_BACK;
-    WlodArgs a{p->d_valid.p, p->d_chrs.p, p->d_tiles.p, p->nwordrows, p->nchr, c.ind_begin, c.ind_count, c.W, nquad,
+    WlodArgs a{p->d_valid.p, p->d_chrs.p, p->d_tiles.p, p->nwordrows, p->nchr, c.ind_begin, t.ind_end, c.W, nquad,
                (uint32_t)((int64_t)plan.n_tiles * nquad), (form.use_patch ? 1 : 0) | (form.no_prefetch ? 2 : 0),
-               score_rows, gl_ring ? 1 : 0, p->cov_pending, nullptr, nullptr};
+               score_rows, gl_ring ? 1 : 0, p->cov_pending, nullptr, nullptr, t.blk0};
     const uint32_t *a_packed = p->d_packed.p;
-    const double *a_wtab = form.wlod_gl ? p->d_glterms.p : p->d_wtab.p, *a_skew = p->d_skew.p + SKEW_FRONT;
+    const double *a_wtab = form.wlod_gl ? t.terms : p->d_wtab.p, *a_skew = p->d_skew.p + SKEW_FRONT;
     const dim3 wl_block(WLOD_WAVES * WAVE);
     if (form.family == Family::wlod_stream) {
         // segments of WSM_T windows x eight blocks per workgroup, everything the window loop reads staged in LDS
@@ -1697,9 +1732,9 @@ int launch_wlod(garlic_panel *p, const LodCall &c, const LodForm &form, const Pl
     }
     if (form.family == Family::wlod_strip) {
         const int n_pairs = (nblk + 1) / 2;
-        WlodStripArgs sa{p->d_valid.p, p->d_chrs.p, p->d_strips.p, p->d_glterms.p, a_skew, d_out,
-                         score_rows, c.ind_begin, c.ind_count, c.W, form.strip_waves, n_pairs,
-                         form.use_patch ? 1 : 0, (uint32_t)((int64_t)plan.n_strips * n_pairs), p->d_counter.p + 3, p->cov_pending};
+        WlodStripArgs sa{p->d_valid.p, p->d_chrs.p, p->d_strips.p, t.terms, a_skew, d_out,
+                         score_rows, c.ind_begin, t.ind_end, c.W, form.strip_waves, n_pairs,
+                         form.use_patch ? 1 : 0, (uint32_t)((int64_t)plan.n_strips * n_pairs), p->d_counter.p + 3, p->cov_pending, t.blk0};
         HIP_TRY(hipMemsetAsync(p->d_counter.p + 3, 0, sizeof(int32_t), s));
         const void *fn = form.strip_three ? (const void *)wlod_strip_gl3_kernel
                          : form.strip_waves == WS_WAVES_WIDE ? (form.aligned16 ? (const void *)wlod_strip_gl_kernel<true, WS_WAVES_WIDE>
@@ -1713,7 +1748,9 @@ int launch_wlod(garlic_panel *p, const LodCall &c, const LodForm &form, const Pl
         // A wave of the strip kernel that ran out of its poll budget flags the launch (its scores are wrong).  The tile
         // form, which computes the same values without waits between waves, is enqueued behind it (below) and runs only if
         // the flag is set -- on the device: no copy back, no synchronisation, the call stays asynchronous -- and
-        // counts itself (garlic_call_stats::n_stall_reruns: expected 0; a liveness bug shows there, not as a slow call)
+        // counts itself (garlic_call_stats::n_stall_reruns: expected 0; a liveness bug shows there, not as a slow call).
+        // Over term slabs every slab's strip launch has its own reset of the flag and its own repair behind it, reading the
+        // same slab: the buffer is released (for_each_tgls_slab) only behind both.
         if (form.strip_force_rerun) HIP_TRY(hipMemsetAsync(p->d_counter.p + 3, 1, sizeof(int32_t), s));
         a.run_if = p->d_counter.p + 3;
         a.rerun_count = p->d_counter.p + 4;
@@ -1760,8 +1797,10 @@ int launch_chain(garlic_panel *p, const LodCall &c, const LodForm &form, Plan &p
 // `chains(k, terms)` enqueues on the context's stream every chain that reads slab k (one per call of the single-size paths; one
 // per group of window sizes for garlic_lod_feed_multi_tgls: a slab is built once and every group runs over it before its
 // buffer is reused).
+// scaled: the slabs hold (term * nomut) * norec of the panel's decay table (ensure_decay_table uploads it on the context's
+// stream and waits; the term pass reads it on the second stream behind ev_slab_begin).
 template <class Chains>
-int for_each_tgls_slab(garlic_panel *p, const std::vector<Plan::Slab> &slabs, int32_t slab_blocks, Chains chains)
+int for_each_tgls_slab(garlic_panel *p, const std::vector<Plan::Slab> &slabs, int32_t slab_blocks, Chains chains, bool scaled = false)
 {
     garlic_ctx *ctx = p->ctx;
     hipStream_t s = ctx->stream;
@@ -1801,7 +1840,7 @@ int for_each_tgls_slab(garlic_panel *p, const std::vector<Plan::Slab> &slabs, in
         const int q = (int)(k & 1);
         if (k >= 2) HIP_TRY(hipStreamWaitEvent(p->slab_stream, p->ev_slab_read[q], 0));
         hipLaunchKernelGGL(gl_terms_slab_kernel, dim3(terms_grid), dim3(256), terms_lds, p->slab_stream, a, p->nloci, rows, sl.b0, sl.b1,
-                           p->d_slab[q].p);
+                           scaled ? p->d_decay.p : (const double *)nullptr, p->d_slab[q].p);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(p->ev_slab_built[q], p->slab_stream));
         HIP_TRY(hipStreamWaitEvent(s, p->ev_slab_built[q], 0));
@@ -1891,16 +1930,30 @@ int launch_generic_wlod(garlic_panel *p, const LodCall &c, const LodForm &form, 
 }
 
 // weighted scores, thinned output: the sampled windows only (wlod_feed_kernel.hpp)
-int launch_wlod_feed(garlic_panel *p, const LodCall &c, const LodForm &form, const Plan &plan, double *d_out)
+// fb0, n_fb: the launch's stretch of the plan's blocks in play (all of them, or those of the slab t)
+int launch_wlod_feed(garlic_panel *p, const LodCall &c, const LodForm &form, const Plan &plan, double *d_out, const WlodTerms &t,
+                     int32_t fb0, int32_t n_fb)
 {
-    const int nquad = (plan.n_feed_blocks + WFD_WAVES - 1) / WFD_WAVES;
-    WlodFeedArgs a{p->d_packed.p, form.wlod_gl ? p->d_glterms.p : p->d_wtab.p, p->d_skew.p + SKEW_FRONT, p->d_valid.p, p->d_chrs.p,
-                   p->d_tiles.p, p->d_feed_blocks.p, d_out, p->nwordrows, GOFF + p->nloci + GPAD_BACK, c.ind_count, c.W, c.thin_step,
-                   plan.n_feed_blocks, nquad, (uint32_t)((int64_t)plan.n_tiles * nquad)};
+    const int nquad = (n_fb + WFD_WAVES - 1) / WFD_WAVES;
+    WlodFeedArgs a{p->d_packed.p, form.wlod_gl ? t.terms : p->d_wtab.p, p->d_skew.p + SKEW_FRONT, p->d_valid.p, p->d_chrs.p,
+                   p->d_tiles.p, p->d_feed_blocks.p + fb0, d_out, p->nwordrows, GOFF + p->nloci + GPAD_BACK, c.ind_count, c.W, c.thin_step,
+                   n_fb, nquad, (uint32_t)((int64_t)plan.n_tiles * nquad), t.blk0};
     if (!a.n_work) return GARLIC_OK;
     if (form.wlod_gl) hipLaunchKernelGGL(wlod_feed_kernel<true>, dim3(a.n_work), dim3(WFD_WAVES * WAVE), 0, p->ctx->stream, a);
     else hipLaunchKernelGGL(wlod_feed_kernel<false>, dim3(a.n_work), dim3(WFD_WAVES * WAVE), 0, p->ctx->stream, a);
     return GARLIC_OK;
+}
+
+// The weighted kernels over a term matrix that is never whole: per slab of the plan a scaled slab (for_each_tgls_slab), then the
+// call's kernel over that slab's individuals -- for the strip form with the tile form that repairs it behind it
+int launch_wlod_slabs(garlic_panel *p, const LodCall &c, const LodForm &form, const Plan &plan, double *d_out)
+{
+    return for_each_tgls_slab(p, plan.slabs, form.slab_blocks, [&](size_t k, const double *terms) {
+        const Plan::Slab &sl = plan.slabs[k];
+        const WlodTerms t = wlod_terms_slab(c, sl, terms);
+        if (form.family == Family::wlod_feed) return launch_wlod_feed(p, c, form, plan, d_out, t, sl.fb0, sl.n_fb);
+        return launch_wlod(p, c, form, plan, d_out, t);
+    }, /*scaled=*/true);
 }
 
 // Everything a call puts on the stream (a second time, as Family::exact, when the rescan found a -9999.0).  (Replaying a repeated
@@ -1948,8 +2001,12 @@ int enqueue_lod(garlic_panel *p, const LodCall &c, const LodForm &form, const La
         case Family::tgls_terms:
         case Family::tgls_lookup: rc = launch_tgls(p, c, form, plan, workers, d_out); break;
         case Family::wlod_generic: rc = launch_generic_wlod(p, c, form, plan, d_out); break;
-        case Family::wlod_feed: rc = launch_wlod_feed(p, c, form, plan, d_out); break;
-        default: rc = launch_wlod(p, c, form, plan, d_out);
+        case Family::wlod_feed:
+            rc = form.slab_blocks ? launch_wlod_slabs(p, c, form, plan, d_out)
+                                  : launch_wlod_feed(p, c, form, plan, d_out, wlod_terms_whole(p, c), 0, plan.n_feed_blocks);
+            break;
+        default:
+            rc = form.slab_blocks ? launch_wlod_slabs(p, c, form, plan, d_out) : launch_wlod(p, c, form, plan, d_out, wlod_terms_whole(p, c));
         }
     if (rc) return rc;
     HIP_TRY(hist_mark(ctx, true));
@@ -1976,7 +2033,7 @@ int launch_lod(garlic_panel *p, Mode mode, int32_t W, double error, int32_t max_
                     thin_step, where, pitch_align, error, mu, out, blocks};
     LodForm form;
     if ((rc = check_lod_args(p, c)) || (rc = decide_form(p, c, form))) return rc;
-    if (mode == MODE_LOD_GL) p->last_slab_blocks = p->last_n_slabs = 0;      // (launch_tgls_slabs sets them)
+    if (form.use_gl) p->last_slab_blocks = p->last_n_slabs = 0;      // (for_each_tgls_slab sets them)
     const Layout Lhost = make_layout(p, pitch_align, ind_count), L = make_layout(p, c.pitch_align, ind_count, thin_step);
     for (int k = 0; k < p->nchr; k++)
         if (3 * L.pitch[k] * 8 + 512 >= (int64_t)1 << 32)

@@ -271,9 +271,12 @@ gl_terms_lds_kernel(VariantArgs p, int64_t nloci, int64_t rows, int nblk, const 
 // every slab of every call, and two memsets per block and slab would be hundreds of tiny operations on the stream.
 // A block's rows start at a multiple of 512 B (one row) from the buffer's base, as in the whole matrix; the ring
 // loaders ask for no more of their source (their 1-KB pieces are aligned in LDS, not in memory).
+// decay != NULL: the slab of the weighted kernels, (term * nomut) * norec as gl_scale_kernel makes them -- the same two
+// multiplications, separately rounded, on the staged table rows as in gl_terms_lds_kernel; the pad rows stay +0.0.
 constexpr int GL_PAD_ROWS = GOFF + GPAD_BACK;
 __global__ void __launch_bounds__(256)
-gl_terms_slab_kernel(VariantArgs p, int64_t nloci, int64_t rows, int b0, int b1, double *__restrict__ terms)
+gl_terms_slab_kernel(VariantArgs p, int64_t nloci, int64_t rows, int b0, int b1, const double *__restrict__ decay,
+                     double *__restrict__ terms)
 {
     extern __shared__ double gl_rows[];                      // [GL_TERMS_S][ncodes][4]
     const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x >> 6;
@@ -292,7 +295,11 @@ gl_terms_slab_kernel(VariantArgs p, int64_t nloci, int64_t rows, int b0, int b1,
     const int ns = (int)min<int64_t>(GL_TERMS_S, nloci - l0);
     const int64_t G0 = GOFF + l0;
     const int row_doubles = p.ncodes * 4;
-    for (int e = threadIdx.x; e < ns * row_doubles; e += blockDim.x) gl_rows[e] = p.tabgl[G0 * row_doubles + e];
+    for (int e = threadIdx.x; e < ns * row_doubles; e += blockDim.x) {
+        const double t = p.tabgl[G0 * row_doubles + e];
+        const int64_t G = G0 + e / row_doubles;
+        gl_rows[e] = decay ? (t * decay[2 * G]) * decay[2 * G + 1] : t;
+    }
     __syncthreads();
     const int shift0 = 2 * (int)(G0 & 15);                   // 0 or 16: the chunk is one half of a genotype word
     for (int blk = b0 + wave; blk < b1; blk += 4) {
@@ -685,7 +692,15 @@ struct WlodArgs {
     // no call has to come back to the host to look at the flag; NULL: an ordinary launch
     const int32_t *run_if;
     int32_t *rerun_count;
+    // FROM_SCORES over a slab of the term matrix (garlic_panel_set_tgls_term_budget): wtab is the slab-local matrix
+    // [blk - blk0][score_rows][64] and the launch covers the slab's individuals, block wlod_slab_first_block() .. ind_count - 1 of the
+    // call (ind_count: the slab's end); 0: the whole matrix, the whole call
+    int32_t blk0;
 };
+// A launch over the slab that begins at panel block blk0 starts at that block, counted in blocks from the call's ind_begin (a
+// multiple of 64 under slabs, host-checked) -- the workgroups' grouping of blocks restarts there; output rows and coverage
+// bits stay addressed by the call's own ind_begin.  blk0 = 0 (the whole matrix): 0.
+__device__ __forceinline__ int wlod_slab_first_block(int ind_begin, int blk0) { return max(blk0 - (ind_begin >> 6), 0); }
 // dynamic LDS of the term-matrix variant: patch lock (16 B) + patch [64][WT_PITCH] doubles, then, 1-KB
 // aligned, one ring of GARLIC_WLOD_GL_RING_ROWS x 512 B per wave
 constexpr uint32_t WLOD_GL_RING_OFF = (16u + 64u * 18u * 8u + 1023u) & ~1023u;
@@ -971,7 +986,7 @@ wlod_tile_body(const uint32_t *__restrict__ packed,
     const unsigned v = (blockIdx.x & 7u) * per_xcd + (blockIdx.x >> 3);
     if (v >= p.n_work) return;
     const int tile_idx = (int)(v / (unsigned)p.nquad);
-    const int ind0 = ((int)(v % (unsigned)p.nquad) * WLOD_WAVES + wave) * WAVE;
+    const int ind0 = (wlod_slab_first_block(p.ind_begin, p.blk0) + (int)(v % (unsigned)p.nquad) * WLOD_WAVES + wave) * WAVE;
     const bool active = ind0 < p.ind_count;      // the last workgroup of a tile may have idle waves
     const int2 td = p.tiles[tile_idx];
     const ChrDev c = p.chrs[td.x];
@@ -997,7 +1012,7 @@ wlod_tile_body(const uint32_t *__restrict__ packed,
                 const double *Dp = D + (c.loc_base + s0 + grp * R) * (int64_t)W;
                 const int64_t G = G0 + grp * R;
                 if (FROM_SCORES) {
-                    const double *tp = wtab + ((col >> 6) * p.score_rows + G) * WAVE + (col & 63);
+                    const double *tp = wtab + (((col >> 6) - p.blk0) * p.score_rows + G) * WAVE + (col & 63);
                     wlod_group_small<R>([&](int i) -> double { return tp[i * WAVE]; }, Dp, W, acc);
                 } else {
                     const double *rw = rows + grp * R * 4;
@@ -1008,13 +1023,13 @@ wlod_tile_body(const uint32_t *__restrict__ packed,
                 }
             } else if (GL_RING) {
                 // block-aligned shard (host-checked): the wave's 64 lanes are one block of the matrix
-                const int64_t blk = ((int64_t)p.ind_begin + ind0) >> 6;
+                const int64_t blk = (((int64_t)p.ind_begin + ind0) >> 6) - p.blk0;
                 const uint32_t ring = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) double *)dyn +
                                       WLOD_GL_RING_OFF + (uint32_t)wave * (GARLIC_WLOD_GL_RING_ROWS * WAVE * 8u);
                 wlod_group_gl<R>(ring, wtab + (blk * p.score_rows + (G0 + grp * R)) * WAVE, lane,
                                  D + (c.loc_base + s0 + grp * R) * (int64_t)W, W, acc);
             } else if (FROM_SCORES)
-                wlod_group_scores<R>(wtab + ((col >> 6) * p.score_rows) * WAVE + (col & 63), G0 + grp * R,
+                wlod_group_scores<R>(wtab + (((col >> 6) - p.blk0) * p.score_rows) * WAVE + (col & 63), G0 + grp * R,
                                      D + (c.loc_base + s0 + grp * R) * (int64_t)W, W, acc);
             else
                 wlod_group<R>(rows + grp * R * 4, gcol, G0 + grp * R,

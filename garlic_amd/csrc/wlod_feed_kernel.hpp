@@ -41,6 +41,7 @@ struct WlodFeedArgs {
     int64_t nwordrows, score_rows;
     int32_t ind_count, winsize, step, nblocks, nquad;      // nquad = workgroups per column group
     uint32_t n_work;           // column groups x nquad
+    int32_t blk0;              // GL: sc is the slab [block - blk0][score_rows][64] and `blocks` lists that slab's blocks; 0: the whole matrix
 };
 
 template <bool GL>
@@ -82,7 +83,7 @@ wlod_feed_kernel(WlodFeedArgs p)
                 __syncthreads();
                 if (!active) continue;
                 if (GL) {
-                    const double *t = p.sc + (((int64_t)(ind0 >> 6) * p.score_rows + G) << 6) + lane;
+                    const double *t = p.sc + (((int64_t)((ind0 >> 6) - p.blk0) * p.score_rows + G) << 6) + lane;
 #pragma unroll 8
                     for (int k = 0; k < n; k++) {
                         const double pr = __builtin_nontemporal_load(t + (int64_t)k * WAVE) * wts[k];

@@ -110,7 +110,8 @@ wlod_small_body(const uint32_t *__restrict__ packed, const double *__restrict__ 
     const unsigned v = (blockIdx.x & 7u) * per_xcd + (blockIdx.x >> 3);
     if (v >= p.n_work) return;
     const int seg = (int)(v / (unsigned)p.nquad);
-    const int ind0A = ((int)(v % (unsigned)p.nquad) * WLOD2_BLOCKS + 2 * wave) * WAVE, ind0B = ind0A + WAVE;
+    const int ind0A = (wlod_slab_first_block(p.ind_begin, p.blk0) + (int)(v % (unsigned)p.nquad) * WLOD2_BLOCKS + 2 * wave) * WAVE;
+    const int ind0B = ind0A + WAVE;
     const bool activeA = ind0A < p.ind_count, activeB = ind0B < p.ind_count;
     const int2 td = p.tiles[seg];
     const ChrDev c = p.chrs[td.x];
@@ -149,9 +150,11 @@ wlod_small_body(const uint32_t *__restrict__ packed, const double *__restrict__ 
         b0 = gB[0]; b1 = gB[WAVE]; b2 = gB[2 * WAVE];
     }
     // GL: the lanes' own rows of the term matrix, row i of the segment at tA[i * 64] (rows past a chromosome's end exist:
-    // GPAD_BACK; what they hold only reaches windows without a score)
-    const double *tA = wtab + ((colA >> 6) * p.score_rows + G0) * WAVE + (colA & 63);
-    const double *tB = wtab + ((colB >> 6) * p.score_rows + G0) * WAVE + (colB & 63);
+    // GPAD_BACK; what they hold only reaches windows without a score); over a slab the blocks count from its first --
+    // row (blk - blk0) * score_rows + G0 of the slab, blk0's share taken off on the scalar side
+    const int64_t G0s = G0 - (int64_t)p.blk0 * p.score_rows;
+    const double *tA = wtab + ((colA >> 6) * p.score_rows + G0s) * WAVE + (colA & 63);
+    const double *tB = wtab + ((colB >> 6) * p.score_rows + G0s) * WAVE + (colB & 63);
     double sa[WC + 15], sb[WC + 15];    // the lanes' scores of a group's 16 + WC - 1 SNPs
     bool carried = false;               // GL: sa / sb [16 ..] are the next group's first WC - 1
     const int ngroups = (nwin + 15) >> 4;

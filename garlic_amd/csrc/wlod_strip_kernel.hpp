@@ -81,6 +81,8 @@ struct WlodStripArgs {
                                // call with the tile form.  A poll budget measures time, not progress -- under a
                                // counter-serialising profiler a correct run may exhaust it -- so nothing traps.
     CovBits cov;               // coverage bits instead of scores (variant_kernels.hpp); bits == NULL: scores
+    int32_t blk0;              // terms is the slab [blk - blk0][term_rows][64] and the launch covers its individuals, from
+                               // block wlod_slab_first_block() up to ind_count (WlodArgs::blk0); 0: the whole matrix, the whole call
 };
 
 // flag rows: lane i's copy at row + 8 i
@@ -282,10 +284,10 @@ wlod_strip_gl_kernel(WlodStripArgs p)
     if (wave == 0) landed[2 * lane] = 0;
     for (int r = wave; r < WS_NEED_ROWS; r += N + 1) need[(r * WAVE + lane) * 2] = (r < N && r < st.n_groups) ? 16 * r : WS_NEVER;
     __syncthreads();
-    const int ind0A = pair * 2 * WAVE, ind0B = ind0A + WAVE;
+    const int ind0A = (wlod_slab_first_block(p.ind_begin, p.blk0) + pair * 2) * WAVE, ind0B = ind0A + WAVE;
     const bool activeB = ind0B < p.ind_count;
     const uint32_t ring_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char *)ws_lds;
-    const int64_t blkA = ((int64_t)p.ind_begin + ind0A) >> 6;          // block-aligned shard (host-checked)
+    const int64_t blkA = (((int64_t)p.ind_begin + ind0A) >> 6) - p.blk0;   // block-aligned shard (host-checked)
     const int64_t G0 = c.loc_base + GOFF + st.s_begin;                  // padded row of the strip's row 0
     if (wave == N) {
         const double *srcA = p.terms + (blkA * p.term_rows + G0) * WAVE;
@@ -373,10 +375,10 @@ wlod_strip_gl3_kernel(WlodStripArgs p)
     if (wave == 0) landed[2 * lane] = 0;
     need[(wave * WAVE + lane) * 2] = (wave < N && wave < st.n_groups) ? 16 * wave : WS_NEVER;
     __syncthreads();
-    const int ind0A = pair * 2 * WAVE, ind0B = ind0A + WAVE;
+    const int ind0A = (wlod_slab_first_block(p.ind_begin, p.blk0) + pair * 2) * WAVE, ind0B = ind0A + WAVE;
     const bool activeB = ind0B < p.ind_count;
     const uint32_t ring_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char *)ws_lds;
-    const int64_t blkA = ((int64_t)p.ind_begin + ind0A) >> 6;
+    const int64_t blkA = (((int64_t)p.ind_begin + ind0A) >> 6) - p.blk0;
     const int64_t G0 = c.loc_base + GOFF + st.s_begin;
     if (wave == N) {
         const double *srcA = p.terms + (blkA * p.term_rows + G0) * WAVE;

@@ -1009,7 +1009,7 @@ void LodEngine::upload(std::vector<HapData *> *haps, std::vector<FreqData *> *fr
         check(garlic_panel_create(s.ctx, nchr, impl->chr_nloci.data(), s.nind, &s.panel), "garlic_panel_create");
         check(garlic_panel_set_map(s.panel, pos.data(), gpos.data(), cs.data(), ce.data()), "garlic_panel_set_map");
         check(garlic_panel_set_freq(s.panel, freq.data()), "garlic_panel_set_freq");
-        if (USE_GL && g_options.tgls_term_bytes != 0)      // --tgls-term-gb: the term matrix of each shard in slabs
+        if (USE_GL && g_options.tgls_term_bytes != 0)      // --tgls-term-gb: the term matrix of each shard in slabs (weighted calls too)
             check(garlic_panel_set_tgls_term_budget(s.panel, g_options.tgls_term_bytes), "garlic_panel_set_tgls_term_budget");
     }
     // genotype rows are separate allocations in HapData: stage a slab of SNP rows at a time

@@ -288,7 +288,7 @@ public:
     std::vector<ROHData *> *assembleROHWindows(IndData *indData, double lodScoreCutoff, ROHLength **rohLength, int winSize,
                                                double error, int MAX_GAP, double OVERLAP_FRAC, bool CM, bool weighted = false,
                                                int M = 0, double mu = 0.0);
-    // garlic_panel_tgls_terms_info of the first shard: the slabs of its last unweighted call with likelihoods (n_slabs 0: none)
+    // garlic_panel_tgls_terms_info of the first shard: the slabs of its last call with likelihoods, weighted or not (n_slabs 0: none)
     void tglsTermSlabs(int *slab_blocks, int *n_slabs);
     LodEngine(const LodEngine &) = delete;
     LodEngine &operator=(const LodEngine &) = delete;

@@ -56,6 +56,7 @@ struct Args {
                  "         [--freq-file F] [--tped-missing C] [--raw-lod] [--kde-subsample N] [--kde-seed S] [--no-kde-thinning]\n"
                  "         [--weighted --map F --M N --mu X --ld-subsample N --ld-seed S --threads N]\n"
                  "         [--resample N --resample-seed S] [--gpus N | --devices 0,1,...] [--genotype-cache F] [--tgls-term-gb X]\n"
+                 "         (--tgls-term-gb X: at most X GB of TGLS terms per device, built and read in slabs; binds --weighted --tgls too)\n"
                  "         [--sorted-feed]   (the KDE feeds ascending, as nrd0's gsl_sort leaves them: <out>.<W>SNPs.lod.sorted.f64)\n"
                  "         [--lod-cutoff X --size-bounds B1 B2 ... [--cm]]   (ROH calls: <out>.roh.bed)\n";
     exit(1);

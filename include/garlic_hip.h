@@ -162,30 +162,39 @@ int garlic_panel_tgls_mode(garlic_panel *panel, int32_t *mode, int32_t *terms_by
 
 /* Unweighted scores from dictionary-coded likelihoods run in two passes: the codes are expanded once into the TGLS term
  * matrix (8 bytes per genotype, 64-individual blocks of rows x 64 doubles, rows = 32 + nloci + 4160), which the chain then
- * streams.  By default the panel keeps the whole matrix, and when the device cannot hold it the chain looks every term up
- * itself (several times slower; feed, coverage and segment calls then also lose their fused forms and need a full-size
- * score scratch).  This sets an upper bound in bytes for the term buffers instead:
- *   0 (default): the whole matrix, or none and the look-up chain.
- *   > 0: the term buffers of this panel never hold more than `bytes`; when the whole matrix is larger, every unweighted
- *        use_gl call (garlic_lod_windows / _multi, garlic_lod_feed / _subset, garlic_roh_coverage_fused, garlic_roh_segments)
- *        builds and consumes it slab by slab (a slab = consecutive 64-individual blocks; the terms of one slab are built
- *        while the chain reads the other, so two buffers: slab_blocks is the largest s for which s + min(s, nblk - s)
- *        blocks fit in `bytes`, nblk = ceil(nind / 64) -- the first buffer holds a full slab, the second what the
- *        second slab holds).  Same kernels and forms, same doubles.  A slab begins at the next block the call scores,
- *        so n_slabs = ceil(blocks / slab_blocks) for a range of individuals; a subset feed's skipped blocks are not
- *        scored, a slab of nothing else is not built.
+ * streams; the weighted kernels read the same matrix scaled by the decay factors of (M, mu).  By default the panel keeps the
+ * whole matrix, and when the device cannot hold it the kernels look every term up themselves (several times slower; feed,
+ * coverage and segment calls then also lose their fused forms and need a full-size score scratch).  This sets an upper
+ * bound in bytes for the term buffers instead:
+ *   0 (default): the whole matrix, or none and the look-up kernels.
+ *   > 0: the term buffers of this panel never hold more than `bytes`; when the whole matrix is larger, every use_gl call
+ *        -- unweighted: garlic_lod_windows / _multi, garlic_lod_feed / _subset, garlic_roh_coverage_fused,
+ *        garlic_roh_segments; weighted: garlic_wlod_windows (to host and device, the whole panel or a range of individuals),
+ *        garlic_lod_feed / _subset (GARLIC_FEED_SAMPLED_WLOD at step >= winsize, from full scores below),
+ *        garlic_roh_coverage_fused, garlic_roh_segments -- builds and consumes it slab by slab (a slab = consecutive
+ *        64-individual blocks; the terms of one slab are built while the kernels read the other, so two buffers, shared by
+ *        raw and scaled slabs: slab_blocks is the largest s for which s + min(s, nblk - s) blocks fit in `bytes`,
+ *        nblk = ceil(nind / 64) -- the first buffer holds a full slab, the second what the second slab holds).  Same
+ *        kernels and forms as budget 0 picks, same doubles, bits and segments; garlic_lod_feed_info answers the same.  A
+ *        slab begins at the next block the call scores, so n_slabs = ceil(blocks / slab_blocks) for a range of
+ *        individuals; a subset feed's skipped blocks are not scored, a slab of nothing else is not built.  The weighted
+ *        kernels group blocks per workgroup (two, four or eight): the grouping restarts at every slab's first block.
  *  -1: the whole matrix when the default's test lets it in, otherwise slabs in half of the memory free at the call.
  * GARLIC_ERR_INVALID when `bytes` > 0 cannot hold the buffers of one-block slabs (2 x rows x 512 bytes; a panel of at
  * most 64 individuals has one slab and one buffer).
  * Slabs are rebuilt by every call, so a sweep over several window sizes pays the term pass per size where the whole matrix
  * is built once and reused: a caller with room for it keeps budget 0.  May be changed between calls in both directions;
- * what the new bound does not allow is freed at once.  Panels that hold continuous likelihoods keep 8 bytes per genotype
- * as their data and ignore the budget.  Weighted scores with likelihoods (garlic_wlod_windows and the weighted feed /
- * coverage / segment calls) are not covered: their kernels pair blocks over a scaled matrix of their own, built whole as
- * before and outside this bound (the next unweighted call under a budget it exceeds frees it). */
+ * what the new bound does not allow -- a whole matrix, raw or scaled, from before -- is freed at once or by the next
+ * use_gl call.  Panels that hold continuous likelihoods keep 8 bytes per genotype as their data and ignore the budget.
+ * Weighted shapes that are not covered by slabs: a slab launch starts at a block of the matrix, so a weighted call whose
+ * ind_begin is not a multiple of 64 (the ring, strip, stream and tile forms alike), and every weighted call that keeps
+ * the generic kernel (GARLIC_WLOD_GENERIC, GARLIC_WLOD_SMALL_GENERIC below 16, winsize + 64 > 4160) looks its terms up
+ * in the code table under a budget (n_slabs 0); nothing is built past the bound.  The generic kernel takes windows up to
+ * 250 SNPs: a wider weighted call of such a shape is refused (GARLIC_ERR_INVALID) where budget 0 would have read the
+ * whole scaled matrix.  garlic_lod_feed_multi_tgls is unweighted. */
 int garlic_panel_set_tgls_term_budget(garlic_panel *panel, int64_t bytes);
 /* whole_bytes: what the full matrix needs (rows x 8 x the panel's padded individual count, (nind + 126) / 64 * 64); resident_bytes: term buffers held now;
- * slab_blocks / n_slabs: of the last unweighted use_gl call (n_slabs 0: it read a whole matrix or looked terms up).
+ * slab_blocks / n_slabs: of the last use_gl call, weighted or not (n_slabs 0: it read a whole matrix or looked terms up).
  * Any pointer may be NULL. */
 int garlic_panel_tgls_terms_info(garlic_panel *panel, int64_t *whole_bytes, int64_t *resident_bytes,
                                  int32_t *slab_blocks, int32_t *n_slabs);

@@ -9,7 +9,8 @@ with dictionary likelihoods, for every size of --winsizes on one resident panel;
 checkout (the A/B against the parent commit: profiles/wlod_feed_ab.txt).  --modes tgls_feed: the same leg for the
 unweighted feed with per-genotype likelihoods (use_gl, not weighted; --gl-kind codes or continuous; no LD weights), with the
 kernel's fraction of the HBM roofline at the bytes per window of the form the call took (profiles/tgls_feed_ab.txt).
---modes tgls_slabs: garlic_lod_windows (device output) and garlic_roh_segments with dictionary likelihoods under
+--modes tgls_slabs: garlic_lod_windows (device output) and garlic_roh_segments, and the weighted garlic_wlod_windows, sampled
+feed (step = winsize) and garlic_roh_segments (weights: synthetic), with dictionary likelihoods under
 GARLIC_GL_NO_TERMS=1 (the look-up chain), over the whole term matrix (first call and warm calls), and -- a library that has
 garlic_panel_set_tgls_term_budget -- under every budget of --term-budgets-gb, with the device memory in use around the
 calls (profiles/tgls_slabs_ab.txt; --tree for the parent commit).
@@ -230,27 +231,43 @@ def tgls_slabs_leg(args):
     del g
     total = panel.out_layout(32, nind)[2]
     out = torch.empty(total, dtype=torch.float64, device=dev)
+    # the weighted legs: synthetic LD weights U(1, max(2, W/4)), an input of the calls timed here
+    ld = 1.0 + (max(2.0, W / 4.0) - 1.0) * torch.rand((nloci, W), generator=gen, device=dev, dtype=torch.float64)
+    torch.cuda.synchronize()
+    panel.set_ld_device(W, ld.data_ptr())
+    del ld
     torch.cuda.synchronize()
     torch.cuda.empty_cache()
+    wargs = dict(use_gl=True, weighted=True, M=7, mu=1e-9)
 
     def used():
         free_b, total_b = torch.cuda.mem_get_info()
         return int(total_b - free_b)
 
-    def leg(name, budget_gb=None):
+    def leg(name, budget_gb=None, weighted=True):
         line = {"mode": "tgls_slabs", "leg": name, "snps": nloci, "inds": nind, "winsize": W, "repeats": args.steps,
                 "device_memory_before_bytes": used()}
         for what, call in (("windows", lambda: panel.lod_windows_device(out.data_ptr(), W, error, max_gap, use_gl=True)),
-                           ("segments", lambda: panel.roh_segments(W, error, max_gap, args.cutoff, 0.25, use_gl=True))):
+                           ("segments", lambda: panel.roh_segments(W, error, max_gap, args.cutoff, 0.25, use_gl=True)),
+                           ("weighted_windows", lambda: panel.wlod_windows_device(out.data_ptr(), W, error, max_gap, 7, 1e-9, use_gl=True)),
+                           ("weighted_feed", lambda: panel.lod_feed(W, error, max_gap, W, copy=False, **wargs)),
+                           ("weighted_segments", lambda: panel.roh_segments(W, error, max_gap, args.cutoff, 0.25, **wargs))):
+            if what.startswith("weighted") and not weighted:
+                continue
             ms = []
+            peak = used()
             for k in range(1 + args.steps):
                 t0 = time.perf_counter()
                 r = call()
                 ms.append((time.perf_counter() - t0) * 1e3)
+                peak = max(peak, used())
             line[what] = {"first_call_ms": ms[0], "warm_ms_median": float(np.median(ms[1:])), "warm_ms_min": min(ms[1:]),
-                          "warm_ms_max": max(ms[1:])}
-            if what == "segments":
+                          "warm_ms_max": max(ms[1:]), "device_memory_peak_after_calls_bytes": peak}
+            if what.endswith("segments"):
                 line[what]["n_segments"] = len(r)
+            if what == "weighted_feed":
+                line[what]["feed_values"] = int(len(r[0]))
+                line[what]["feed_form"] = panel.feed_info()[0]
             if hasattr(panel, "tgls_terms_info"):
                 line[what].update(panel.tgls_terms_info())
             line[what]["device_memory_after_bytes"] = used()
@@ -260,7 +277,7 @@ def tgls_slabs_leg(args):
         print(json.dumps(line), flush=True)
 
     os.environ["GARLIC_GL_NO_TERMS"] = "1"
-    leg("lookup chain (GARLIC_GL_NO_TERMS=1)")
+    leg("lookup chain (GARLIC_GL_NO_TERMS=1)", weighted=False)      # (the generic weighted kernel takes seconds per call)
     del os.environ["GARLIC_GL_NO_TERMS"]
     leg("whole matrix")
     if hasattr(panel, "set_tgls_term_budget"):
