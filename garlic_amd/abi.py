@@ -17,6 +17,8 @@ HOST, DEVICE = 0, 1
 FEED_FROM_SCORES, FEED_CHAIN, FEED_SAMPLED_WLOD, FEED_TGLS_CHAIN = 0, 1, 2, 3   # garlic_lod_feed_info
 FEED_TGLS_CHAIN_SHARED = 4   # garlic_lod_feed_multi_info: the size shared its chain launch with another size
 FEED_ORDER_REFERENCE, FEED_ORDER_SORTED = 0, 1   # garlic_panel_set_feed_order
+LD_PAIR_PLAIN, LD_PAIR_MFMA, LD_PAIR_LANE, LD_PAIR_TILED, LD_PAIR_FLAT = 0, 1, 2, 3, 4   # garlic_panel_ld_form_info
+LD_SUM_PLAIN, LD_SUM_FLAT, LD_SUM_COL, LD_SUM_TILED = 0, 1, 2, 3
 MISSING = -9999.0
 
 # every symbol include/garlic_hip.h declares (tests check the library exports them all)
@@ -39,6 +41,7 @@ SYMBOLS = [
     "garlic_lod_feed_multi_tgls", "garlic_lod_feed_multi_info",
     "garlic_panel_compute_ld_multi", "garlic_ld_finish_multi", "garlic_panel_ld_info",
     "garlic_panel_set_feed_order", "garlic_feed_sort", "garlic_feed_sort_info",
+    "garlic_panel_set_phase_bits", "garlic_panel_ld_form_info",
 ]
 
 
@@ -136,6 +139,8 @@ def lib():
     L.garlic_ld_finish_multi.argtypes = [_vp, _i32p, C.c_int32, C.c_int32, _vp, _vp, C.POINTER(_vp), C.c_int32]
     L.garlic_panel_ld_info.argtypes = [_vp, C.c_int32, _i32p, _i32p, _i32p, _i64p, _i32p, _i32p]
     L.garlic_panel_set_feed_order.argtypes = [_vp, C.c_int32]
+    L.garlic_panel_set_phase_bits.argtypes = [_vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32]
+    L.garlic_panel_ld_form_info.argtypes = [_vp, _i32p, _i32p, _i32p, _i32p]
     L.garlic_feed_sort.argtypes = [_vp, _vp, C.c_int64, C.c_int32]
     L.garlic_feed_sort_info.argtypes = [_vp, _i32p, _i32p, _i64p]
     for name in SYMBOLS:
@@ -347,6 +352,23 @@ class Panel:
         assert fc.ndim == 2 and fc.shape[1] >= self.nind
         check(lib().garlic_panel_set_phase(self.handle, _vp(fc.ctypes.data), fc.shape[1], locus_begin,
                                            fc.shape[0], HOST))
+
+    def set_phase_bits(self, rows, locus_begin=0):
+        """rows: uint8 [nloci_chunk][row_bytes], HapData::firstCopy at one bit per genotype -- bit i & 7 of byte i >> 3 of a
+        row is individual i (np.packbits(first_copy, axis=1, bitorder="little")); row_bytes >= (nind + 7) / 8."""
+        rows = np.ascontiguousarray(rows, dtype=np.uint8)
+        assert rows.ndim == 2
+        check(lib().garlic_panel_set_phase_bits(self.handle, _vp(rows.ctypes.data), rows.shape[1], locus_begin, rows.shape[0], HOST))
+
+    def set_phase_bits_device(self, ptr, row_bytes, locus_begin, locus_count):
+        """ptr: device address of such rows"""
+        check(lib().garlic_panel_set_phase_bits(self.handle, _vp(ptr), row_bytes, locus_begin, locus_count, DEVICE))
+
+    def ld_form_info(self):
+        """(pair kernel LD_PAIR_*, sum kernel LD_SUM_*, fused, phased) of the panel's last LD call"""
+        v = [C.c_int32() for _ in range(4)]
+        check(lib().garlic_panel_ld_form_info(self.handle, *[C.byref(x) for x in v]))
+        return v[0].value, v[1].value, bool(v[2].value), bool(v[3].value)
 
     def set_gl_device(self, ptr, ld, locus_begin, locus_count):
         """ptr: device address of float64 [locus_count][ld] per-genotype error probabilities."""

@@ -295,6 +295,8 @@ struct garlic_panel {
     std::vector<std::unique_ptr<LdSet>> ld_sets;
     int32_t ld_group = -1;
     int32_t ld_pair_passes = 0, ld_sum_passes = 0; // of the last multi call (garlic_panel_ld_info)
+    // the form of the last LD call (garlic_panel_ld_form_info); pair < 0: no LD call yet
+    struct { int32_t pair = -1, sum = 0, fused = 0, phased = 0; } ld_last;
     DevBuf<double> d_rld, d_decay, d_stage64;
     DevBuf<uint64_t> d_phase;                      // HapData::firstCopy as bit planes [blk][nloci] (--phased LD)
     uint64_t geno_epoch = 0;                       // bumped by every genotype upload (LD plane cache)
@@ -2606,6 +2608,46 @@ int garlic_panel_set_phase(garlic_panel *p, const uint8_t *first_copy, int64_t l
     return GARLIC_OK;
 }
 
+int garlic_panel_set_phase_bits(garlic_panel *p, const uint8_t *rows, int64_t row_bytes, int64_t locus_begin, int64_t locus_count,
+                                int32_t where)
+{
+    if (!p || !rows) return fail(GARLIC_ERR_INVALID, "panel and rows are required");
+    if (row_bytes < ((int64_t)p->nind + 7) / 8) return fail(GARLIC_ERR_INVALID, "row_bytes %lld < %d bits", (long long)row_bytes, p->nind);
+    if (locus_begin < 0 || locus_count < 1 || locus_begin + locus_count > p->nloci)
+        return fail(GARLIC_ERR_INVALID, "locus range [%lld,+%lld) outside panel of %lld loci",
+                    (long long)locus_begin, (long long)locus_count, (long long)p->nloci);
+    int rc;
+    if ((rc = set_device(p->ctx))) return rc;
+    hipStream_t s = p->ctx->stream;
+    const int nblk = (int)(p->nind_pad / WAVE);
+    if (!p->d_phase.p) {
+        if ((rc = p->d_phase.reserve((size_t)nblk * p->nloci))) return rc;
+        HIP_TRY(hipMemsetAsync(p->d_phase.p, 0, sizeof(uint64_t) * nblk * p->nloci, s));
+    }
+    DevBuf<uint8_t> stage;
+    const int64_t slab_rows = (where == GARLIC_HOST) ? std::max<int64_t>(16, ((int64_t)256 << 20) / row_bytes) : locus_count;
+    for (int64_t done = 0; done < locus_count; done += slab_rows) {
+        const int64_t n = std::min(slab_rows, locus_count - done);
+        const uint8_t *src = rows + done * row_bytes;
+        hipError_t e = hipSuccess;
+        if (where == GARLIC_HOST) {
+            if ((rc = stage.reserve((size_t)(n * row_bytes)))) { stage.release(); return rc; }
+            e = hipMemcpyAsync(stage.p, src, (size_t)(n * row_bytes), hipMemcpyHostToDevice, s);
+            src = stage.p;
+        }
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(phase_bits_planes_kernel, dim3((unsigned)((n + WAVE - 1) / WAVE)), dim3(256), 0, s, src, row_bytes,
+                               locus_begin + done, n, p->nind, nblk, p->nloci, p->d_phase.p);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(s);                      // staging buffer is reused
+        if (e != hipSuccess) { stage.release(); return fail(GARLIC_ERR_HIP, "set_phase_bits: %s", hipGetErrorString(e)); }
+    }
+    stage.release();
+    p->have_phase = true;
+    return GARLIC_OK;
+}
+
 // reciprocals of device-resident LD weights, plain and skewed (what the wLOD kernels read)
 // the skewed reciprocals D[l][j] = 1 / LD[l - j][j]: the weights SNP l has in the windows that contain it as one
 // contiguous row (tuned wLOD kernels); rows past the panel stay 0 (SKEW_FRONT doubles of zero padding in front:
@@ -2750,7 +2792,8 @@ enum class LdSum { flat, col, tiled, plain };
 struct LdForm {
     int32_t W = 0, nblk = 0;       // nblk: 64-individual blocks of the panel
     bool phased = false;
-    // pair counts.  mfma: banded Gram matrices on the matrix cores (unphased, 16 < W <= 129); lane: a lane per SNP while the
+    // pair counts.  mfma: banded Gram matrices on the matrix cores (16 < W <= 129; phased: three products per block, while the
+    // haplotype counts, up to 2 * nind_pad, stay below 2^22 and exact in the f32 accumulators); lane: a lane per SNP while the
     // tile's plane words fit LDS; tiled: a thread per distance (W - 1 <= 256); flat: a thread per pair (a switch); plain: a
     // workgroup per SNP, streamed from L2 -- the only one that adds into a zeroed table instead of writing every entry
     LdPair pair = LdPair::plain;
@@ -2789,10 +2832,11 @@ static LdForm ld_form(const garlic_panel *p, int32_t W, int32_t phased)
     f.lane_stage = std::min(f.nblk, getenv("GARLIC_LD_LANE_STAGE") ? atoi(getenv("GARLIC_LD_LANE_STAGE")) : 4);
     f.lane_dc = W - 1 <= 16 ? 16 : 32;
     const size_t lane_lds = sizeof(uint64_t) * planes * (size_t)f.lane_stage * (LD_LANE_T + W - 1);
-    if (!phased && !flat && W > LD_SMALL_MAX_W && f.mfma_nj <= 5 && !getenv("GARLIC_LD_PAIR_NO_MFMA") && !no_lane) {
+    const bool counts_fit = !phased || 2 * (int64_t)p->nind_pad < LDM_COUNT_MAX;      // (wider panels keep the lane kernel)
+    if (counts_fit && !flat && W > LD_SMALL_MAX_W && f.mfma_nj <= 5 && !getenv("GARLIC_LD_PAIR_NO_MFMA") && !no_lane) {
         f.pair = LdPair::mfma;
         f.pair_tile = LDM_TI;
-        f.pair_lds = (size_t)2 * 2 * (4 + f.mfma_nj - 1) * WAVE * 16;
+        f.pair_lds = (size_t)2 * (phased ? 3 : 2) * (4 + f.mfma_nj - 1) * WAVE * 16;      // two buffers of {M, H} or {M, A, B}
     } else if (flat) {
         f.pair = LdPair::flat;
     } else if (W - 1 <= 256 && lane_lds <= LDS_STAGING_MAX && !no_lane) {
@@ -2822,6 +2866,29 @@ static LdForm ld_form(const garlic_panel *p, int32_t W, int32_t phased)
     }
     f.fusable = f.pair == LdPair::mfma && f.sum == LdSum::col && !getenv("GARLIC_LD_UNFUSED");
     return f;
+}
+
+// what garlic_panel_ld_form_info reports: the form an LD call ran (fused: its pair kernel wrote the hr2 table itself)
+static void ld_note_form(garlic_panel *p, const LdForm &f, bool fused)
+{
+    static_assert((int)LdPair::mfma == 0 && (int)LdPair::plain == 4 && (int)LdSum::flat == 0 && (int)LdSum::plain == 3, "the maps below");
+    const int32_t pair_code[] = {GARLIC_LD_PAIR_MFMA, GARLIC_LD_PAIR_LANE, GARLIC_LD_PAIR_TILED, GARLIC_LD_PAIR_FLAT, GARLIC_LD_PAIR_PLAIN};
+    const int32_t sum_code[] = {GARLIC_LD_SUM_FLAT, GARLIC_LD_SUM_COL, GARLIC_LD_SUM_TILED, GARLIC_LD_SUM_PLAIN};
+    p->ld_last.pair = pair_code[(int)f.pair];
+    p->ld_last.sum = sum_code[(int)f.sum];
+    p->ld_last.fused = fused;
+    p->ld_last.phased = f.phased;
+}
+
+int garlic_panel_ld_form_info(garlic_panel *p, int32_t *pair_kernel, int32_t *sum_kernel, int32_t *fused, int32_t *phased)
+{
+    if (!p) return fail(GARLIC_ERR_INVALID, "panel is NULL");
+    if (p->ld_last.pair < 0) return fail(GARLIC_ERR_STATE, "no LD call on this panel yet");
+    if (pair_kernel) *pair_kernel = p->ld_last.pair;
+    if (sum_kernel) *sum_kernel = p->ld_last.sum;
+    if (fused) *fused = p->ld_last.fused;
+    if (phased) *phased = p->ld_last.phased;
+    return GARLIC_OK;
 }
 
 static int ld_check(garlic_panel *p, int32_t winsize, int32_t phased)
@@ -2915,15 +2982,19 @@ static const uint64_t *ld_plane_fc(const garlic_panel *p, const LdForm &f) { ret
 static int ld_pair_mfma(garlic_panel *p, const LdForm &f, unsigned blocks, int32_t *pair, bool fuse)
 {
     int rc;
-    decltype(&ld_pair_mfma_kernel<2, false>) const fns[2][4] = {
-        {ld_pair_mfma_kernel<2, false>, ld_pair_mfma_kernel<3, false>, ld_pair_mfma_kernel<4, false>, ld_pair_mfma_kernel<5, false>},
-        {ld_pair_mfma_kernel<2, true>, ld_pair_mfma_kernel<3, true>, ld_pair_mfma_kernel<4, true>, ld_pair_mfma_kernel<5, true>}};
-    const auto fn = fns[fuse][f.mfma_nj - 2];          // (16 < W: two tiles at least)
+    decltype(&ld_pair_mfma_kernel<2, false>) const fns[2][2][4] = {
+        {{ld_pair_mfma_kernel<2, false>, ld_pair_mfma_kernel<3, false>, ld_pair_mfma_kernel<4, false>, ld_pair_mfma_kernel<5, false>},
+         {ld_pair_mfma_kernel<2, true>, ld_pair_mfma_kernel<3, true>, ld_pair_mfma_kernel<4, true>, ld_pair_mfma_kernel<5, true>}},
+        {{ld_pair_mfma_kernel<2, false, true>, ld_pair_mfma_kernel<3, false, true>, ld_pair_mfma_kernel<4, false, true>,
+          ld_pair_mfma_kernel<5, false, true>},
+         {ld_pair_mfma_kernel<2, true, true>, ld_pair_mfma_kernel<3, true, true>, ld_pair_mfma_kernel<4, true, true>,
+          ld_pair_mfma_kernel<5, true, true>}}};
+    const auto fn = fns[f.phased][fuse][f.mfma_nj - 2];          // (16 < W: two tiles at least)
     const size_t lds = std::max(f.pair_lds, fuse ? LDM_XT_BYTES : (size_t)0);
     if (fuse && ((rc = ld_hf(p, f, p->lds.loc_planes.p)) || (rc = ld_reserve_table(p, f.W)))) return rc;
     if (lds > LDS_DEFAULT_MAX) HIP_TRY(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(fn, dim3(blocks), dim3(256), lds, p->ctx->stream, p->lds.m.p, p->lds.h.p, f.nblk, p->nloci, p->lds.pair_chrs.p,
-                       p->nchr, f.W, pair, fuse ? p->lds.hf.p : nullptr, fuse ? p->lds.fwd.p : nullptr);
+                       p->nchr, f.W, pair, fuse ? p->lds.hf.p : nullptr, fuse ? p->lds.fwd.p : nullptr, ld_plane_o(p, f), ld_plane_fc(p, f));
     return GARLIC_OK;
 }
 
@@ -3008,6 +3079,7 @@ int garlic_ld_counts(garlic_panel *p, int32_t winsize, int32_t phased, const int
     std::vector<uint64_t> sub;
     if ((rc = ld_sub_bitmap(p, sub_idx, n_sub, sub))) return rc;
     const LdForm f = ld_form(p, winsize, phased);
+    ld_note_form(p, f, false);
     if (where != GARLIC_HOST) return ld_counts_run(p, f, sub, locus_counts, pair_counts, false);
     DevBuf<int32_t> &d_loc = p->lds.loc, &d_pair = p->lds.pair;
     if ((rc = d_loc.reserve((size_t)p->nloci * 2)) || (rc = d_pair.reserve((size_t)p->nloci * winsize * 2))) return rc;
@@ -3183,7 +3255,9 @@ int garlic_ld_finish(garlic_panel *p, int32_t winsize, int32_t phased, const int
         HIP_TRY(hipMemcpyAsync(d_pair.p, pair_counts, sizeof(int32_t) * npair, hipMemcpyHostToDevice, s));
         locus_counts = d_loc.p; pair_counts = d_pair.p;
     }
-    return ld_finish_to(p, ld_form(p, winsize, phased), locus_counts, pair_counts, false, ld_out, where == GARLIC_HOST, false);
+    const LdForm f = ld_form(p, winsize, phased);
+    ld_note_form(p, f, false);
+    return ld_finish_to(p, f, locus_counts, pair_counts, false, ld_out, where == GARLIC_HOST, false);
 }
 
 // counts and finish on the panel's scratch (kept with the panel, as all LD scratch), fused where the form allows
@@ -3191,6 +3265,7 @@ static int ld_compute(garlic_panel *p, const LdForm &f, const std::vector<uint64
 {
     int rc;
     DevBuf<int32_t> &d_loc = p->lds.loc, &d_pair = p->lds.pair;
+    ld_note_form(p, f, f.fusable);
     if ((rc = d_loc.reserve((size_t)p->nloci * 2)) || (rc = d_pair.reserve(f.fusable ? 2 : (size_t)p->nloci * f.W * 2))) return rc;
     if ((rc = ld_counts_run(p, f, sub, d_loc.p, d_pair.p, f.fusable))) return rc;
     return ld_finish_to(p, f, d_loc.p, d_pair.p, f.fusable, ld_out, host_out, keep_sets);
@@ -3365,6 +3440,12 @@ static int ld_multi_run(garlic_panel *p, const LdMultiPlan &plan, int32_t phased
         p->ld_pair_passes++;
         p->ld_sum_passes++;
         stash_ld(p, (int32_t)g);
+    }
+    if (plan.n_shared > 0) {                        // the call's form: the widest sharing size's pair stage
+        const LdForm ftab = ld_form(p, plan.wtab, phased);
+        ld_note_form(p, ftab, !counts && ftab.fusable);
+    } else if (counts) {
+        ld_note_form(p, ld_form(p, plan.groups.back()[0], phased), false);
     }
     HIP_TRY(hipStreamSynchronize(s));               // the pool's leftovers are freed on return
     return GARLIC_OK;

@@ -278,6 +278,31 @@ phase_planes_kernel(const uint8_t *__restrict__ fc, int64_t ld, int64_t l0, int6
     if (lane == 0) planeF[(int64_t)blk * nloci + l0 + r] = bits;
 }
 
+// The same planes from HapData::firstCopy at one bit per genotype (the genotype cache's rows: SNP-major, bit i & 7 of byte
+// i >> 3 is individual i): a plane word is 8 consecutive bytes of a row, so this is a strided copy with the bits past the
+// last individual cleared.  Lanes along the rows (one 512-B store per wave and block), the four waves on neighbouring
+// blocks of the same rows.  Rows need no alignment: read byte by byte, never past (nind + 7) / 8 bytes of a row.
+__global__ void __launch_bounds__(256)
+phase_bits_planes_kernel(const uint8_t *__restrict__ rows, int64_t row_bytes, int64_t l0, int64_t count, int nind, int nblk,
+                         int64_t nloci, uint64_t *__restrict__ planeF)
+{
+    const int64_t r = (int64_t)blockIdx.x * WAVE + (threadIdx.x & 63);
+    if (r >= count) return;
+    const int nbytes = (nind + 7) >> 3;
+    const uint8_t *row = rows + r * row_bytes;
+    for (int blk = threadIdx.x >> 6; blk < nblk; blk += 4) {
+        uint64_t w = 0;
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const int b = blk * 8 + k;
+            if (b < nbytes) w |= (uint64_t)row[b] << (8 * k);
+        }
+        const int left = nind - blk * WAVE;                      // individuals of this block
+        if (left < WAVE) w &= left > 0 ? (((uint64_t)1 << left) - 1) : 0;
+        planeF[(int64_t)blk * nloci + l0 + r] = w;
+    }
+}
+
 __global__ void ld_homfreq_kernel(const int32_t *__restrict__ counts, int64_t nloci, double *__restrict__ hf)
 {
     const int64_t l = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -922,6 +947,7 @@ typedef int ldm_i32x4 __attribute__((ext_vector_type(4)));
 // instruction in the cycles the i8 form needs for 32 individuals.  A set bit becomes the nibble 0001 = 0.5, the block
 // scales are 2^0, the products 0.25 and the f32 sums exact (counts below 2^22): count = 4 * sum.  Half the MFMAs,
 // half the LDS bytes, 7 instead of 10 vector instructions per 8 individuals for the expansion.
+constexpr int64_t LDM_COUNT_MAX = (int64_t)1 << 22;      // the largest count a tile may reach (phased: 2 per individual)
 typedef int ldm_i32x8 __attribute__((ext_vector_type(8)));
 typedef float ldm_f32x16 __attribute__((ext_vector_type(16)));
 
@@ -944,15 +970,28 @@ __device__ __forceinline__ uint32_t ldm_spread8(uint32_t x)
 constexpr int LDM_XT = 33;                         // doubles per row of a wave's transposition tile (conflict-free)
 constexpr size_t LDM_XT_BYTES = ((size_t)4 * 32 * LDM_XT + 256) * 8;      // + homFreq of the workgroup's (up to) 256 staged SNPs
 
-template <int NJ, bool HR2>
+//
+// PHASED (r2, garlic-data.cpp:585-617): planeH holds T ("genotype 2"), planeO "genotype 1" (ld_planes_kernel<true>), planeF
+// firstCopy.  Per individual the two haplotypes that carry the counted allele are
+//     A = T | (O & F)      B = T | (O & ~F)
+// and x11(i, j) = |A_i & A_j| + |B_i & B_j|: (2, 2) counts in both products, (1, 2) and (2, 1) in the one product of the
+// heterozygote's carrying haplotype, (1, 1) in one product exactly when the two firstCopy bits agree (:598-604).  A set bit
+// of A or B is a non-missing genotype, so "both non-missing" needs no mask; total = 2 |M_i & M_j|.  Three Gram products per
+// block, {M, A, B}; A and B add into the same accumulator tile, so the register budget stays 2 NJ tiles and the LDS per
+// buffer grows by half (48 KB for both at NJ = 5).  The haplotype tile reaches 2 n_sub: the host takes this form while
+// 2 * nind_pad stays below 2^22 (ld_form).  The counts leave as {2 tot, x11} (what ld_pair_lane_kernel<true> writes); the
+// HR2 epilogue divides x11 by 2 tot and is otherwise the same, hf being FreqData::freq.
+template <int NJ, bool HR2, bool PHASED = false>
 __global__ void __launch_bounds__(256, 2)
 ld_pair_mfma_kernel(const uint64_t *__restrict__ planeM, const uint64_t *__restrict__ planeH, int nblk, int64_t nloci,
                     const LdPairChr *__restrict__ chrs, int nchr, int W, int32_t *__restrict__ pair,
-                    const double *__restrict__ hf, double *__restrict__ C)
+                    const double *__restrict__ hf, double *__restrict__ C, const uint64_t *__restrict__ planeO = nullptr,
+                    const uint64_t *__restrict__ planeF = nullptr)
 {
     constexpr int NT = 4 + NJ - 1;                 // staged tiles of 32 SNPs (<= 8: one SNP per thread)
     static_assert(NT * 32 <= 256, "one staged SNP per thread");
-    constexpr int BUF = 2 * NT * WAVE * 16;        // bytes per buffer: [plane][tile][lane][16]: 32 individuals per lane
+    constexpr int NP = PHASED ? 3 : 2;             // staged planes: {M, H} or {M, A, B}
+    constexpr int BUF = NP * NT * WAVE * 16;       // bytes per buffer: [plane][tile][lane][16]: 32 individuals per lane
     extern __shared__ __attribute__((aligned(16))) unsigned char ldm_lds[];      // two buffers
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -962,18 +1001,22 @@ ld_pair_mfma_kernel(const uint64_t *__restrict__ planeM, const uint64_t *__restr
     const int64_t i0 = chrs[c].lo + ((int64_t)blockIdx.x - chrs[c].block0) * LDM_TI;
     const bool mine = tid < NT * 32;                            // this thread stages SNP i0 + tid
     const bool in = mine && i0 + tid < hi;
-    uint64_t wm = 0, wh = 0;
+    uint64_t wm = 0, wh = 0, wo = 0, wf = 0;
     auto fetch = [&](int b) {
         const int64_t g = (int64_t)b * nloci + i0 + (in ? tid : 0);
         wm = in ? planeM[g] : 0;
         wh = in ? planeH[g] : 0;
+        if (PHASED) {
+            wo = in ? planeO[g] : 0;
+            wf = in ? planeF[g] : 0;
+        }
     };
     auto stage = [&](int buf) {
         if (!mine) return;
         const int tile = tid >> 5, r = tid & 31;
 #pragma unroll
-        for (int pl = 0; pl < 2; pl++) {
-            const uint64_t w = pl ? wh : wm;
+        for (int pl = 0; pl < NP; pl++) {
+            const uint64_t w = !PHASED ? (pl ? wh : wm) : (pl == 0 ? wm : (pl == 1 ? wh | (wo & wf) : wh | (wo & ~wf)));
 #pragma unroll
             for (int h = 0; h < 2; h++) {                      // lane half = individuals 32 h .. 32 h + 31
                 const uint32_t x = (uint32_t)(w >> (32 * h));
@@ -1002,7 +1045,8 @@ ld_pair_mfma_kernel(const uint64_t *__restrict__ planeM, const uint64_t *__restr
 #endif
         if (b + 2 < nblk) fetch(b + 2);
 #pragma unroll
-        for (int pl = 0; pl < 2; pl++) {
+        for (int pl = 0; pl < NP; pl++) {
+            const int a = pl ? 1 : 0;                           // accumulator tile: M; H, or A and B together
             ldm_i32x8 fb[NJ];
 #pragma unroll
             for (int q = 0; q < NJ; q++) {
@@ -1011,7 +1055,7 @@ ld_pair_mfma_kernel(const uint64_t *__restrict__ planeM, const uint64_t *__restr
             }
 #pragma unroll
             for (int q = 0; q < NJ; q++)
-                acc[q][pl] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(fb[0], fb[q], acc[q][pl], 4, 4, 0, one, 0, one);
+                acc[q][a] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(fb[0], fb[q], acc[q][a], 4, 4, 0, one, 0, one);
         }
         __syncthreads();
     }
@@ -1043,7 +1087,7 @@ ld_pair_mfma_kernel(const uint64_t *__restrict__ planeM, const uint64_t *__restr
                 double f = 0.0, b = 0.0;
                 if (HA > 0 && HA < 1 && okB) {                     // hr2_from_counts(HA, HB, ..) and (HB, HA, ..)
                     double HAB = (double)(int)(acc[q][1][k] * 4.0f);
-                    HAB /= (double)(int)(acc[q][0][k] * 4.0f);
+                    HAB /= (double)((PHASED ? 2 : 1) * (int)(acc[q][0][k] * 4.0f));
                     const double H = HAB - HA * HB, HH = H * H;
                     const double vf = HH / (HA * (1 - HA) * HB * (1 - HB));
                     const double vb = HH / (pB * HA * (1 - HA));
@@ -1075,7 +1119,7 @@ ld_pair_mfma_kernel(const uint64_t *__restrict__ planeM, const uint64_t *__restr
             const int64_t i = it + (k & 3) + 8 * (k >> 2) + rh;
             const int64_t d = j - i;
             if (i < hi && d >= 0 && d < W) {
-                int2 v = make_int2((int)(acc[q][0][k] * 4.0f), (int)(acc[q][1][k] * 4.0f));
+                int2 v = make_int2((PHASED ? 2 : 1) * (int)(acc[q][0][k] * 4.0f), (int)(acc[q][1][k] * 4.0f));
                 if (d == 0) v = make_int2(0, 0);
 #ifdef GARLIC_LDM_ABL_NO_STORE      // timing experiment (results wrong)
                 if (v.x != 0x7FFFFFF1) continue;

@@ -155,6 +155,7 @@ HapData *initHapData(unsigned int nind, unsigned int nloci, bool PHASED)
     d->data = new short *[nloci];
     d->firstCopy = PHASED ? new bool *[nloci] : nullptr;
     d->packed = nullptr;
+    d->phaseBits = nullptr;
     for (unsigned l = 0; l < nloci; l++) {
         d->data[l] = new short[nind];
         std::fill(d->data[l], d->data[l] + nind, (short)MISSING);
@@ -172,10 +173,12 @@ void releaseHapData(HapData *d)
         if (d->data) delete[] d->data[l];
         if (d->firstCopy) delete[] d->firstCopy[l];
         if (d->packed) delete[] d->packed[l];
+        if (d->phaseBits) delete[] d->phaseBits[l];
     }
     delete[] d->data;
     delete[] d->firstCopy;
     delete[] d->packed;
+    delete[] d->phaseBits;
     delete d;
 }
 void releaseHapData(std::vector<HapData *> *v) { for (auto d : *v) releaseHapData(d); delete v; }
@@ -347,6 +350,7 @@ void flushChromosome(const std::string &chr, std::vector<short *> &hap, std::vec
     h->data = new short *[n];
     h->firstCopy = fc.empty() ? nullptr : new bool *[n];
     h->packed = nullptr;
+    h->phaseBits = nullptr;
     FreqData *f = initFreqData(n);
     for (int l = 0; l < n; l++) {
         if (h->firstCopy) h->firstCopy[l] = fc[l];
@@ -659,7 +663,7 @@ void filterSites(size_t c, const std::vector<char> &keep, std::vector<MapData *>
     MapData *m2 = initMapData(n);
     m2->chr = m->chr;
     HapData *h2 = new HapData{h->data ? new short *[n] : nullptr, h->nind, n, h->firstCopy ? new bool *[n] : nullptr,
-                              h->packed ? new unsigned char *[n] : nullptr};
+                              h->packed ? new unsigned char *[n] : nullptr, h->phaseBits ? new unsigned char *[n] : nullptr};
     FreqData *f2 = initFreqData(n);
     GenoLikeData *g2 = nullptr;
     if (g) {
@@ -673,6 +677,7 @@ void filterSites(size_t c, const std::vector<char> &keep, std::vector<MapData *>
             if (h->data) delete[] h->data[l];
             if (h->packed) delete[] h->packed[l];
             if (h->firstCopy) delete[] h->firstCopy[l];
+            if (h->phaseBits) delete[] h->phaseBits[l];
             if (g && g->data) delete[] g->data[l];
             if (g && g->codes) delete[] g->codes[l];
             continue;
@@ -682,12 +687,13 @@ void filterSites(size_t c, const std::vector<char> &keep, std::vector<MapData *>
         if (h->data) h2->data[j] = h->data[l];
         if (h->packed) h2->packed[j] = h->packed[l];
         if (h->firstCopy) h2->firstCopy[j] = h->firstCopy[l];
+        if (h->phaseBits) h2->phaseBits[j] = h->phaseBits[l];
         f2->freq[j] = f->freq[l];
         if (g && g->data) g2->data[j] = g->data[l];
         if (g && g->codes) g2->codes[j] = g->codes[l];
         j++;
     }
-    delete[] h->data; delete[] h->firstCopy; delete[] h->packed; delete h;
+    delete[] h->data; delete[] h->firstCopy; delete[] h->packed; delete[] h->phaseBits; delete h;
     if (g) { delete[] g->data; delete[] g->codes; delete g; (*gls)[c] = g2; }
     releaseMapData(m); releaseFreqData(f);
     (*maps)[c] = m2; (*haps)[c] = h2; (*freqs)[c] = f2;
@@ -832,7 +838,7 @@ void writeGenotypeCache(const std::string &path, std::vector<HapData *> *haps, s
     o.val<uint32_t>((uint32_t)nind);
     o.val<uint32_t>((uint32_t)maps->size());
     bool phased = true;
-    for (auto h : *haps) phased = phased && h->firstCopy;
+    for (auto h : *haps) phased = phased && hasPhase(h);
     o.val<uint32_t>(phased ? CACHE_FLAG_PHASE : 0u);
     const size_t row = ((size_t)nind + 3) / 4, prow = ((size_t)nind + 7) / 8;
     std::vector<uint8_t> bits(row), pbits(prow);
@@ -857,7 +863,8 @@ void writeGenotypeCache(const std::string &path, std::vector<HapData *> *haps, s
             o.put(bits.data(), row);
         }
         if (phased)
-            for (int l = 0; l < m->nloci; l++) {   // HapData::firstCopy, one bit per individual
+            for (int l = 0; l < m->nloci; l++) {   // HapData::firstCopy, one bit per individual: bit i & 7 of byte i >> 3
+                if (h->phaseBits) { o.put(h->phaseBits[l], prow); continue; }
                 std::fill(pbits.begin(), pbits.end(), 0);
                 for (int i = 0; i < nind; i++)
                     if (h->firstCopy[l][i]) pbits[i >> 3] |= (uint8_t)(1u << (i & 7));
@@ -905,7 +912,8 @@ void loadGenotypeCache(const std::string &path, int &numLoci, int &numInd, std::
             in.get(f->freq, sizeof(double) * n);
             for (int l = 0; l < n; l++) m->locusName[l] = in.str();
             HapData *h = new HapData{keepPacked ? nullptr : new short *[n](), nind, n, phased ? new bool *[n]() : nullptr,
-                                     keepPacked ? new unsigned char *[n]() : nullptr};
+                                     keepPacked ? new unsigned char *[n]() : nullptr,
+                                     phased && keepPacked ? new unsigned char *[n]() : nullptr};
             (*haps)->push_back(h);
             for (int l = 0; l < n; l++) {
                 if (keepPacked) {   // the rows as stored: the engine uploads them 2-bit
@@ -919,6 +927,11 @@ void loadGenotypeCache(const std::string &path, int &numLoci, int &numInd, std::
             }
             for (int l = 0; phased && l < n; l++) {
                 in.get(pbits.data(), prow);
+                if (keepPacked) {   // the phase rows as stored, next to firstCopy (which the host's readers use): the engine uploads them 1-bit
+                    if (nind & 7) pbits[prow - 1] &= (uint8_t)((1u << (nind & 7)) - 1);
+                    h->phaseBits[l] = new unsigned char[prow];
+                    memcpy(h->phaseBits[l], pbits.data(), prow);
+                }
                 bool *d = h->firstCopy[l] = new bool[nind];
                 for (int i = 0; i < nind; i++) d[i] = (pbits[i >> 3] >> (i & 7)) & 1;
             }
@@ -1017,9 +1030,9 @@ void LodEngine::upload(std::vector<HapData *> *haps, std::vector<FreqData *> *fr
     std::vector<int16_t> stage;
     std::vector<uint8_t> stage2, stage_glc;
     std::vector<double> stage_gl;
-    std::vector<uint8_t> stage_fc;
+    std::vector<uint8_t> stage_fc, stage_fcbits;
     impl->have_phase = true;
-    for (auto h : *haps) impl->have_phase = impl->have_phase && h->firstCopy;
+    for (auto h : *haps) impl->have_phase = impl->have_phase && hasPhase(h);
     o = 0;
     for (int c = 0; c < nchr; c++) {
         const HapData *h = haps->at(c);
@@ -1043,7 +1056,11 @@ void LodEngine::upload(std::vector<HapData *> *haps, std::vector<FreqData *> *fr
                 for (int r = 0; r < rows; r++)
                     memcpy(&stage_gl[(size_t)r * impl->nind], gld->data[l0 + r], sizeof(double) * impl->nind);
             }
-            if (impl->have_phase) {
+            const size_t prow_bytes = ((size_t)impl->nind + 7) / 8;
+            if (impl->have_phase && h->phaseBits) {   // one bit per genotype, as the cache holds them
+                stage_fc.resize((size_t)rows * prow_bytes);
+                for (int r = 0; r < rows; r++) memcpy(&stage_fc[(size_t)r * prow_bytes], h->phaseBits[l0 + r], prow_bytes);
+            } else if (impl->have_phase) {
                 stage_fc.resize((size_t)rows * impl->nind);
                 for (int r = 0; r < rows; r++)
                     for (int i = 0; i < impl->nind; i++)
@@ -1056,9 +1073,24 @@ void LodEngine::upload(std::vector<HapData *> *haps, std::vector<FreqData *> *fr
                 else
                     check(garlic_panel_set_genotypes(s.panel, stage.data() + s.ind_begin, impl->nind, o + l0, rows,
                                                      GARLIC_HOST), "garlic_panel_set_genotypes");
-                if (impl->have_phase)
+                if (impl->have_phase && h->phaseBits && (s.ind_begin & 7) == 0) {
+                    check(garlic_panel_set_phase_bits(s.panel, stage_fc.data() + s.ind_begin / 8, (int64_t)prow_bytes, o + l0, rows,
+                                                      GARLIC_HOST), "garlic_panel_set_phase_bits");
+                } else if (impl->have_phase && h->phaseBits) {   // a shard that begins inside a byte: its bits moved down
+                    const size_t sb = ((size_t)s.nind + 7) / 8;
+                    stage_fcbits.assign((size_t)rows * sb, 0);
+                    for (int r = 0; r < rows; r++)
+                        for (int i = 0; i < s.nind; i++) {
+                            const int g = s.ind_begin + i;
+                            if ((stage_fc[(size_t)r * prow_bytes + (g >> 3)] >> (g & 7)) & 1)
+                                stage_fcbits[(size_t)r * sb + (i >> 3)] |= (uint8_t)(1u << (i & 7));
+                        }
+                    check(garlic_panel_set_phase_bits(s.panel, stage_fcbits.data(), (int64_t)sb, o + l0, rows, GARLIC_HOST),
+                          "garlic_panel_set_phase_bits");
+                } else if (impl->have_phase) {
                     check(garlic_panel_set_phase(s.panel, stage_fc.data() + s.ind_begin, impl->nind, o + l0, rows,
                                                  GARLIC_HOST), "garlic_panel_set_phase");
+                }
                 if (gld && gld->codes)
                     check(garlic_panel_set_gl_codes(s.panel, stage_glc.data() + s.ind_begin, impl->nind, o + l0, rows,
                                                     gld->values, gld->nvalues, GARLIC_HOST), "garlic_panel_set_gl_codes");

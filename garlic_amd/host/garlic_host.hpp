@@ -29,7 +29,13 @@ struct HapData {           // src/garlic-data.h:32-38
     // (nind + 3) / 4 bytes each; then `data` is NULL.  Everything in this adapter takes either form
     // (genotypeAt reads one value); the engine uploads the packed rows as they are.
     unsigned char **packed;
+    // Extension: the firstCopy rows as the genotype cache stores them, 1 bit per genotype (bit i & 7 of byte i >> 3 is
+    // individual i, the bits past the last individual 0), (nind + 7) / 8 bytes each; NULL unless the cache was loaded with
+    // keepPacked.  `firstCopy` stays filled next to them for the host's readers; the engine uploads these rows as they are
+    // (garlic_panel_set_phase_bits: an eighth of the bytes, no staging expansion).
+    unsigned char **phaseBits;
 };
+inline bool hasPhase(const HapData *h) { return h->firstCopy || h->phaseBits; }
 inline short genotypeAt(const HapData *h, int locus, int ind)
 {
     if (h->data) return h->data[locus][ind];

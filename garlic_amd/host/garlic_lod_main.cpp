@@ -174,7 +174,7 @@ int main(int argc, char **argv)
             fclose(probe);
             loadGenotypeCache(a.cache, numLoci, numInd, &haps, &maps, &freqs, /*keepPacked=*/true);
             std::cerr << "Loaded genotype cache " << a.cache << "\n";
-            if (a.phased && !haps->at(0)->firstCopy) {
+            if (a.phased && !hasPhase(haps->at(0))) {
                 std::cerr << "ERROR: --phased, but " << a.cache << " was written without phase; delete it to re-read the tped\n";
                 return 1;
             }

@@ -50,7 +50,8 @@ extern "C" {
  *    garlic_panel_set_tgls_term_budget, garlic_panel_tgls_terms_info (likewise); garlic_lod_feed_multi_tgls,
  *    garlic_lod_feed_multi_info, GARLIC_FEED_TGLS_CHAIN_SHARED (likewise); garlic_panel_compute_ld_multi,
  *    garlic_ld_finish_multi, garlic_panel_ld_info (likewise); garlic_panel_set_feed_order, garlic_feed_sort,
- *    garlic_feed_sort_info, GARLIC_FEED_ORDER_* (likewise) */
+ *    garlic_feed_sort_info, GARLIC_FEED_ORDER_* (likewise); garlic_panel_set_phase_bits, garlic_panel_ld_form_info,
+ *    GARLIC_LD_PAIR_* / GARLIC_LD_SUM_* (likewise) */
 #define GARLIC_HIP_ABI_VERSION 8
 
 #define GARLIC_OK 0
@@ -205,6 +206,13 @@ int garlic_panel_tgls_terms_info(garlic_panel *panel, int64_t *whole_bytes, int6
 int garlic_panel_set_phase(garlic_panel *panel, const uint8_t *first_copy, int64_t ld,
                            int64_t locus_begin, int64_t locus_count, int32_t where);
 
+/* The same phase at one bit per genotype, as the genotype cache stores HapData::firstCopy: rows are SNP-major, row r
+ * (locus locus_begin + r) starts at rows + r * row_bytes, and bit (i & 7) of its byte (i >> 3) is individual i of the
+ * panel; row_bytes >= (nind + 7) / 8, bits past the last individual are ignored.  Rows need no alignment.  Same effect on
+ * the panel as garlic_panel_set_phase over the same loci, at an eighth of the bytes. */
+int garlic_panel_set_phase_bits(garlic_panel *panel, const uint8_t *rows, int64_t row_bytes, int64_t locus_begin,
+                                int64_t locus_count, int32_t where);
+
 /* LDData::LD (src/garlic-data.h:105) for winsize: ld[l * winsize + k], l global locus. */
 int garlic_panel_set_ld(garlic_panel *panel, int32_t winsize, const double *ld, int32_t where);
 
@@ -274,6 +282,23 @@ int garlic_ld_finish_multi(garlic_panel *panel, const int32_t *winsizes, int32_t
                            double *const *ld_out, int32_t where);
 int garlic_panel_ld_info(garlic_panel *panel, int32_t cap, int32_t *winsizes, int32_t *groups, int32_t *n_installed,
                          int64_t *weight_bytes, int32_t *n_pair_passes, int32_t *n_sum_passes);
+
+/* Which kernels the last LD call on the panel took (garlic_panel_compute_ld, garlic_ld_counts, garlic_ld_finish and the
+ * multi-size calls; for a multi call with sizes that share passes: the pair stage at the widest sharing size).  fused: the
+ * pair kernel wrote the hr2 / r2 table itself and no pair-count table was made (garlic_panel_compute_ld{,_multi} only;
+ * never under GARLIC_LD_UNFUSED, never for garlic_ld_counts / garlic_ld_finish).  Pair kernels: _MFMA, banded Gram matrices
+ * on the matrix cores (16 < winsize <= 129; phased as well as unphased); _LANE / _TILED / _FLAT / _PLAIN: AND + popcount
+ * forms.  Any pointer may be NULL; GARLIC_ERR_STATE before the panel's first LD call. */
+#define GARLIC_LD_PAIR_PLAIN 0
+#define GARLIC_LD_PAIR_MFMA 1
+#define GARLIC_LD_PAIR_LANE 2
+#define GARLIC_LD_PAIR_TILED 3
+#define GARLIC_LD_PAIR_FLAT 4
+#define GARLIC_LD_SUM_PLAIN 0
+#define GARLIC_LD_SUM_FLAT 1
+#define GARLIC_LD_SUM_COL 2
+#define GARLIC_LD_SUM_TILED 3
+int garlic_panel_ld_form_info(garlic_panel *panel, int32_t *pair_kernel, int32_t *sum_kernel, int32_t *fused, int32_t *phased);
 
 /* A panel keeps its device scratch between calls (LD counting and summing buffers: about
  * 5 x nloci x winsize x 8 bytes; the score scratch of host-output and feed calls), because at scale

@@ -27,6 +27,11 @@ resident panel: the unweighted feed (step = winsize) of --kde-inds individuals (
 everyone -- the device sort alone by HIP events, its bytes per second at 24 B x keys x passes run, the whole feed call in
 both orders, and on the same data one thread of std::sort and numpy's sort on the host, as stand-ins for gsl_sort
 (profiles/feed_sort_ab.txt).
+--modes ld_phased: the warm garlic_panel_compute_ld(phased = 1) call (weights only) for every size of --winsizes on one resident
+panel -- host clock around the synchronous call and the ordered-sum kernel by the library's HIP events, median and spread
+of --steps calls -- with the form the call took where the library reports it; and the phase upload from host memory both
+ways, bytes and milliseconds: one byte per genotype (garlic_panel_set_phase) and bit rows (garlic_panel_set_phase_bits).
+--tree for the parent commit; GARLIC_LD_PAIR_NO_MFMA=1 for this tree's AND + popcount form (profiles/ld_phased_mfma_ab.txt).
 """
 import argparse
 import json
@@ -429,6 +434,66 @@ def ld_multi_leg(args):
             leg("one multi call", multi)
 
 
+def ld_phased_leg(args):
+    import time
+    import torch
+    from garlic_amd import abi, synth
+
+    torch.cuda.set_device(0)
+    dev = torch.device("cuda", 0)
+    nloci, nind = args.snps, args.inds
+    sizes = [int(w) for w in args.winsizes.split(",")]
+    spec = synth.PanelSpec(nloci, seed=20260105, max_gap=200000)
+    ctx = abi.Context(0)
+    panel = abi.Panel(ctx, spec.chr_nloci, nind)
+    panel.set_map(spec.pos, spec.centro_start, spec.centro_end, gpos=spec.gpos)
+    panel.set_freq(spec.freq)
+    for l0, g in synth.genotype_chunks(spec, nind, dev):
+        torch.cuda.synchronize()
+        panel.set_genotypes_device(g.data_ptr(), g.shape[1], l0, g.shape[0])
+    del g
+    torch.cuda.empty_cache()
+    # the phase, slab by slab from host memory: bytes first, then (where the library has the call) the same values as bit rows,
+    # which leaves the same planes
+    rng = np.random.default_rng(11)
+    slab = max(1, min(nloci, (1 << 30) // nind))
+    up = {"bytes": [0, 0.0], "bits": [0, 0.0]}
+    for l0 in range(0, nloci, slab):
+        n = min(slab, nloci - l0)
+        fc = rng.integers(0, 2, size=(n, nind), dtype=np.uint8)
+        t0 = time.perf_counter()
+        panel.set_phase(fc, locus_begin=l0)
+        up["bytes"][1] += (time.perf_counter() - t0) * 1e3
+        up["bytes"][0] += fc.nbytes
+        if hasattr(panel, "set_phase_bits"):
+            rows = np.packbits(fc, axis=1, bitorder="little")
+            t0 = time.perf_counter()
+            panel.set_phase_bits(rows, locus_begin=l0)
+            up["bits"][1] += (time.perf_counter() - t0) * 1e3
+            up["bits"][0] += rows.nbytes
+    print(json.dumps({"mode": "ld_phased", "leg": "phase upload", "snps": nloci, "inds": nind,
+                      "byte_upload_bytes": up["bytes"][0], "byte_upload_ms": up["bytes"][1],
+                      "bit_upload_bytes": up["bits"][0], "bit_upload_ms": up["bits"][1]}), flush=True)
+    for W in sizes:
+        wall, kern = [], []
+        for k in range(2 + args.steps):
+            t0 = time.perf_counter()
+            panel.compute_ld(W, want_output=False, phased=True)
+            dt = (time.perf_counter() - t0) * 1e3
+            if k >= 2:
+                wall.append(dt)
+                kern.append(ctx.recent_kernel_ms(1)[-1])
+        line = {"mode": "ld_phased", "leg": "compute_ld", "snps": nloci, "inds": nind, "winsize": W, "repeats": args.steps,
+                "no_mfma_switch": bool(os.environ.get("GARLIC_LD_PAIR_NO_MFMA")),
+                "call_ms_median": float(np.median(wall)), "call_ms_min": min(wall), "call_ms_max": max(wall),
+                "sum_kernel_ms_median": float(np.median(kern)), "sum_kernel_ms_min": min(kern), "sum_kernel_ms_max": max(kern)}
+        if hasattr(panel, "ld_form_info"):
+            pair, sumk, fused, phased = panel.ld_form_info()
+            line.update({"pair_kernel": pair, "sum_kernel": sumk, "fused": fused})
+        print(json.dumps(line), flush=True)
+        panel.release_scratch()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--snps", type=int, default=200000)
@@ -454,6 +519,8 @@ def main():
         return ld_multi_leg(args)
     if args.modes == "feed_sort":
         return feed_sort_leg(args)
+    if args.modes == "ld_phased":
+        return ld_phased_leg(args)
     if args.modes in ("wlod_feed", "tgls_feed"):
         return wlod_feed_leg(args, tgls=args.modes == "tgls_feed")
 
