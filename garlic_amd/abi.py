@@ -19,6 +19,7 @@ FEED_TGLS_CHAIN_SHARED = 4   # garlic_lod_feed_multi_info: the size shared its c
 FEED_ORDER_REFERENCE, FEED_ORDER_SORTED = 0, 1   # garlic_panel_set_feed_order
 LD_PAIR_PLAIN, LD_PAIR_MFMA, LD_PAIR_LANE, LD_PAIR_TILED, LD_PAIR_FLAT = 0, 1, 2, 3, 4   # garlic_panel_ld_form_info
 LD_SUM_PLAIN, LD_SUM_FLAT, LD_SUM_COL, LD_SUM_TILED = 0, 1, 2, 3
+TGLS_DICTIONARY, TGLS_CONTINUOUS, TGLS_DICTIONARY16 = 1, 2, 3   # garlic_panel_tgls_mode
 MISSING = -9999.0
 
 # every symbol include/garlic_hip.h declares (tests check the library exports them all)
@@ -42,6 +43,7 @@ SYMBOLS = [
     "garlic_panel_compute_ld_multi", "garlic_ld_finish_multi", "garlic_panel_ld_info",
     "garlic_panel_set_feed_order", "garlic_feed_sort", "garlic_feed_sort_info",
     "garlic_panel_set_phase_bits", "garlic_panel_ld_form_info",
+    "garlic_panel_set_gl_codes16",
 ]
 
 
@@ -102,6 +104,7 @@ def lib():
     L.garlic_lod_windows_multi.argtypes = [_vp, _i32p, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                            C.c_int32, _vp, C.c_int64, C.c_int32]
     L.garlic_panel_set_gl_codes.argtypes = [_vp, _vp, C.c_int64, C.c_int64, C.c_int64, _vp, C.c_int32, C.c_int32]
+    L.garlic_panel_set_gl_codes16.argtypes = [_vp, _vp, C.c_int64, C.c_int64, C.c_int64, _vp, C.c_int32, C.c_int32]
     L.garlic_panel_set_genotypes_2bit.argtypes = [_vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32]
     L.garlic_panel_set_phase.argtypes = [_vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32]
     L.garlic_panel_set_ld.argtypes = [_vp, C.c_int32, _vp, C.c_int32]
@@ -335,6 +338,15 @@ class Panel:
         values = np.ascontiguousarray(values, dtype=np.float64)
         check(lib().garlic_panel_set_gl_codes(self.handle, _vp(codes.ctypes.data), codes.shape[1], locus_begin,
                                               codes.shape[0], _vp(values.ctypes.data), values.shape[0], HOST))
+
+    def set_gl_codes16(self, codes, values, locus_begin=0):
+        """codes: uint16 [nloci_chunk][nind] indexing values (float64, <= 65536 error probabilities); the panel keeps
+        2 bytes per genotype (TGLS_DICTIONARY16)"""
+        codes = np.ascontiguousarray(codes, dtype=np.uint16)
+        values = np.ascontiguousarray(values, dtype=np.float64)
+        assert codes.ndim == 2 and values.ndim == 1
+        check(lib().garlic_panel_set_gl_codes16(self.handle, _vp(codes.ctypes.data), codes.shape[1], locus_begin,
+                                                codes.shape[0], _vp(values.ctypes.data), values.shape[0], HOST))
 
     def set_feed_order(self, order):
         """garlic_panel_set_feed_order: FEED_ORDER_REFERENCE (chromosome -> individual -> locus, the default) or

@@ -11,6 +11,7 @@
 #include "ld_kernels.hpp"
 #include "ld_multi_kernel.hpp"
 #include "tgls_ring_kernel.hpp"
+#include "tgls_wide_kernel.hpp"
 #include "tgls_feed_kernel.hpp"
 #include "tgls_feed_multi_kernel.hpp"
 #include "wlod_strip_kernel.hpp"
@@ -280,6 +281,16 @@ struct garlic_panel {
     DevBuf<double> d_freq;                         // [GOFF+nloci+pad], pad rows 0
     bool dfreq_valid = false;
     int gl_terms_by = 0;                           // who built the current terms: 1 device log10, 2 host libm
+    int slab_terms_by = 0;                         // 16-bit codes: who built the term slabs of the last call
+    // wide_term_bound's part that needs the whole table and every frequency: recomputed after either changed
+    mutable bool wide_bound_known = false;
+    mutable double wide_bound_cached = 0;
+    // TGLS, 16-bit dictionary (GARLIC_TGLS_DICTIONARY16; tgls_wide_kernel.hpp): gl_values / gl_code hold up to 65,536 values,
+    // the codes sit in the term matrix's layout and are never overwritten; d_codes / d_tabgl are empty
+    bool gl_wide = false;
+    DevBuf<uint16_t> d_codes16;                    // [blk][GOFF+nloci+pad][64]
+    DevBuf<double> d_values16;                     // the value table, GL_WIDE_MAX doubles
+    bool values16_valid = false;
     // wLOD
     bool have_ld = false, wlod_use_gl = false, rld_valid = false;
     int32_t last_chain_kind = 0;                   // garlic_panel_chain_kind
@@ -834,10 +845,38 @@ int feed_grid(garlic_ctx *ctx, const std::vector<FeedItem> &items, int *grid, in
 // position.  They agree unless a scored window sums to exactly -9999.0, which needs W terms that can add
 // up to it: impossible while W * (most negative term) stays above -9999 (a margin covers the rounding of
 // the sums).  Otherwise the exact kernel runs (lod_chain_exact_kernel).  Tables / terms must be current.
+// 16-bit dictionary: a lower bound of every finite term that is known BEFORE any term is built -- under term slabs the chain
+// kind is decided before the first slab exists.  With every table value e in (0, 1] and every frequency f in [0, 1]
+// (f = 0, 1: term +0.0) the homozygous quotients are (1 - e) / (1 - f) + e >= 1 and (1 - e) / f + e >= 1 up to a few roundings
+// (terms >= about -1e-15), and the heterozygous quotient is (e * non) / non = e up to one rounding: term = log10(e) within
+// an ulp or two.  So: the host's log10 of the smallest table value, minus 1e-6 (a million times the rounding at stake, and
+// at most 0.004 over the widest window).  Any value outside (0, 1], any frequency outside {0} and [1e-150, 1] (reachable through
+// --freq-file; below 1e-150 the genotype probabilities f * f and 2 f (1 - f) can be subnormal, where e * non rounds in units of
+// 2^-1074 and the quotient is no longer e), a NaN among either: no bound -- the scan always runs.  It errs towards kind 1 only.  Where a whole raw matrix
+// has been built its measured minimum is taken in as well (it can only lower the bound).
+double wide_term_bound(const garlic_panel *p)
+{
+    if (!p->wide_bound_known) {      // set_freq and every change of the value table clear the flag
+        double vmin = 1.0;
+        bool bounded = true;
+        for (double v : p->gl_values) {
+            if (!(v > 0.0 && v <= 1.0)) bounded = false;
+            vmin = std::min(vmin, v);
+        }
+        for (double f : p->freq)
+            if (!(f == 0.0 || (f >= 1e-150 && f <= 1.0))) bounded = false;
+        p->wide_bound_cached = bounded ? log10(vmin) - 1e-6 : -HUGE_VAL;
+        p->wide_bound_known = true;
+    }
+    double bound = p->wide_bound_cached;
+    if (p->glterms_valid && p->d_glterms.p && p->gl_terms_by) bound = std::min(bound, p->glterms_min);
+    return bound;
+}
+
 bool lod_exact_needed(const garlic_panel *p, Mode mode, int32_t W)
 {
     if (getenv("GARLIC_EXACT_CHAIN") || getenv("GARLIC_EXACT_CHAIN_ONLY")) return true;
-    const double tmin = mode == MODE_LOD ? p->tab_min : (p->gl_cont ? p->glterms_min : p->tabgl_min);
+    const double tmin = mode == MODE_LOD ? p->tab_min : p->gl_wide ? wide_term_bound(p) : (p->gl_cont ? p->glterms_min : p->tabgl_min);
     return (double)W * tmin <= -9990.0;
 }
 
@@ -943,6 +982,50 @@ int ensure_dfreq(garlic_panel *p)
     return GARLIC_OK;
 }
 
+void release_tgls_slabs(garlic_panel *p);
+
+// ---- 16-bit dictionary.  The value table on the device (its unused tail 0.0)
+int ensure_values16(garlic_panel *p)
+{
+    if (p->values16_valid) return GARLIC_OK;
+    int rc;
+    if ((rc = p->d_values16.reserve(GL_WIDE_MAX))) return rc;
+    std::vector<double> v(GL_WIDE_MAX, 0.0);
+    std::copy(p->gl_values.begin(), p->gl_values.end(), v.begin());
+    HIP_TRY(hipMemcpyAsync(p->d_values16.p, v.data(), sizeof(double) * GL_WIDE_MAX, hipMemcpyHostToDevice, p->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(p->ctx->stream));
+    p->values16_valid = true;
+    return GARLIC_OK;
+}
+
+// A panel without likelihoods, or one with one-byte codes, takes 16-bit codes from here on: what has been coded is widened
+// (the code numbers stay), the per-SNP term table and the terms made from it go.
+int switch_to_wide(garlic_panel *p)
+{
+    if (p->gl_wide || p->gl_cont) return GARLIC_OK;
+    const int64_t rows = GOFF + p->nloci + GPAD_BACK;
+    const size_t n = (size_t)rows * p->nind_pad;
+    hipStream_t s = p->ctx->stream;
+    int rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    if ((rc = p->d_codes16.reserve(n))) return rc;
+    if (p->d_codes.p) {
+        hipLaunchKernelGGL(gl_widen_kernel, dim3(4096), dim3(256), 0, s, p->d_codes.p, p->nind_pad, rows, p->d_codes16.p);
+        HIP_TRY(hipGetLastError());
+    } else
+        HIP_TRY(hipMemsetAsync(p->d_codes16.p, 0, sizeof(uint16_t) * n, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    p->d_codes.release();
+    p->d_tabgl.release();
+    p->tabgl_valid = false;
+    p->d_glterms.release();
+    release_tgls_slabs(p);
+    p->glterms_valid = false;
+    p->values16_valid = false;
+    p->gl_wide = true;
+    return GARLIC_OK;
+}
+
 // The dictionary is full (or the caller's values are continuous from the start): from here on the
 // panel keeps the error probabilities themselves.  What has been coded so far is decoded.
 int switch_to_continuous(garlic_panel *p)
@@ -958,7 +1041,14 @@ int switch_to_continuous(garlic_panel *p)
     p->d_slab[1].release();
     p->glterms_valid = false;
     if ((rc = p->d_glval.reserve(n))) return rc;
-    if (p->d_codes.p && !p->gl_values.empty()) {
+    if (p->gl_wide) {      // 16-bit codes and values share the layout: decoded element for element
+        if ((rc = ensure_values16(p))) return rc;
+        hipLaunchKernelGGL(gl_decode16_kernel, dim3(4096), dim3(256), 0, s, p->d_codes16.p, p->d_values16.p,
+                           (int32_t)p->gl_values.size(), (int64_t)n, p->d_glval.p);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "set_gl: %s", hipGetErrorString(e));
+    } else if (p->d_codes.p && !p->gl_values.empty()) {
         std::vector<double> dict(GL_DICT_MAX, 0.0);
         std::copy(p->gl_values.begin(), p->gl_values.end(), dict.begin());
         DevBuf<double> d_dict;
@@ -976,9 +1066,13 @@ int switch_to_continuous(garlic_panel *p)
         HIP_TRY(hipStreamSynchronize(s));
     }
     p->d_codes.release();
+    p->d_codes16.release();
+    p->d_values16.release();
+    p->gl_wide = p->values16_valid = false;
     p->d_tabgl.release();
     p->gl_code.clear();
     p->gl_values.clear();
+    p->wide_bound_known = false;
     p->tabgl_valid = false;
     p->gl_cont = true;
     p->gl_vals_dropped = false;
@@ -1046,6 +1140,81 @@ int build_terms_on_host(garlic_panel *p, const double *vals, double *terms)
         HIP_TRY(hipStreamSynchronize(s));
     }
     return GARLIC_OK;
+}
+
+// The same for a panel of 16-bit codes: the terms of the blocks [b0, b1) into the slab-local matrix dst[blk - b0][rows][64]
+// (the whole matrix: b0 = 0), on stream s.  The codes are downloaded chunk by chunk (no host copy is kept: the fall-back is
+// rare, a second copy of 2 B per genotype on the host is not).  decay: NULL, or the host's {nomut, norec} rows for the
+// scaled slab, (term * nomut) * norec.  *tmin: the most negative finite raw term met, 0.0 when none is negative.
+int build_wide_terms_on_host(garlic_panel *p, int b0, int b1, const double *decay, double *dst, hipStream_t s, double *tmin)
+{
+    const int64_t rows = GOFF + p->nloci + GPAD_BACK;
+    const int nb = b1 - b0;
+    const int64_t chunk = std::max<int64_t>(16, (((int64_t)128 << 20) / (8 * WAVE * nb)) & ~(int64_t)15);
+    std::vector<double> hv((size_t)chunk * WAVE * nb);
+    std::vector<uint16_t> hc((size_t)chunk * WAVE * nb);
+    std::vector<uint32_t> hw((size_t)(chunk / 16 + 2) * WAVE * nb);
+    const double *freq = p->freq.data(), *val = p->gl_values.data();
+    const int nval = (int)p->gl_values.size();
+    std::mutex mu;
+    double best = 0.0;
+    HIP_TRY(hipMemsetAsync(dst, 0, sizeof(double) * (size_t)nb * rows * WAVE, s));      // pad rows: +0.0
+    for (int64_t G0 = GOFF; G0 < GOFF + p->nloci; G0 += chunk) {
+        const int64_t G1 = std::min<int64_t>(GOFF + p->nloci, G0 + chunk), nr = G1 - G0;
+        const int64_t w0 = G0 >> 4, nw = ((G1 - 1) >> 4) - w0 + 1;
+        for (int b = 0; b < nb; b++) {
+            HIP_TRY(hipMemcpyAsync(hc.data() + (size_t)b * chunk * WAVE, p->d_codes16.p + ((int64_t)(b0 + b) * rows + G0) * WAVE,
+                                   sizeof(uint16_t) * nr * WAVE, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(hw.data() + (size_t)b * (chunk / 16 + 2) * WAVE,
+                                   p->d_packed.p + ((int64_t)(b0 + b) * p->nwordrows + w0) * WAVE, sizeof(uint32_t) * nw * WAVE,
+                                   hipMemcpyDeviceToHost, s));
+        }
+        HIP_TRY(hipStreamSynchronize(s));
+        double *hvp = hv.data();
+        const uint16_t *hcp = hc.data();
+        const uint32_t *hwp = hw.data();
+        double *bestp = &best;
+        std::mutex *mup = &mu;
+        parallel_for(nr * nb, 256, [=](int64_t lo, int64_t hi) {
+            double m = 0.0;
+            for (int64_t k = lo; k < hi; k++) {
+                const int64_t b = k / nr, r = k % nr, G = G0 + r;
+                double *v = hvp + ((size_t)b * chunk + r) * WAVE;
+                const uint16_t *c = hcp + ((size_t)b * chunk + r) * WAVE;
+                const uint32_t *w = hwp + ((size_t)b * (chunk / 16 + 2) + ((G >> 4) - w0)) * WAVE;
+                const double f = freq[G - GOFF];
+                for (int lane = 0; lane < WAVE; lane++) {
+                    const uint32_t code = (w[lane] >> (2 * (int)(G & 15))) & 3u;
+                    double t = host_lod(code == 3u ? -9 : (int)code, f, val[c[lane] < nval ? c[lane] : 0]);
+                    if (t < m && t > -1.7976931348623157e308) m = t;
+                    if (decay) t = (t * decay[2 * G]) * decay[2 * G + 1];
+                    v[lane] = t;
+                }
+            }
+            if (m < 0.0) {
+                std::lock_guard<std::mutex> lock(*mup);
+                if (m < *bestp) *bestp = m;
+            }
+        });
+        for (int b = 0; b < nb; b++)
+            HIP_TRY(hipMemcpyAsync(dst + ((int64_t)b * rows + G0) * WAVE, hv.data() + (size_t)b * chunk * WAVE,
+                                   sizeof(double) * nr * WAVE, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    if (tmin) *tmin = best;
+    return GARLIC_OK;
+}
+
+// who builds the terms of lod() on values: the device once its log10 has reproduced the host's, else the host
+bool tgls_terms_on_host(const garlic_panel *p) { return p->ctx->log10_state < 0 || getenv("GARLIC_TGLS_HOST_TERMS"); }
+
+// gl_terms_wide_kernel for the blocks [b0, b1) into the slab-local dst, on stream s (values, frequencies and log table are in place)
+void launch_wide_terms(garlic_panel *p, int b0, int b1, const double *d_decay, double *dst, unsigned long long *d_minbits, hipStream_t s)
+{
+    const int64_t rows = GOFF + p->nloci + GPAD_BACK;
+    hipLaunchKernelGGL(gl_terms_wide_kernel, dim3((unsigned)((rows + 63) / 64), (unsigned)std::min(b1 - b0, 65535)), dim3(256), 0, s,
+                       p->d_packed.p, p->nwordrows, p->d_freq.p, p->ctx->d_logtab.p, p->d_codes16.p, p->d_values16.p,
+                       (int32_t)p->gl_values.size(), d_decay, rows, b0, b1, dst, d_minbits);
 }
 
 // ---- TGLS pass 1: every (SNP, individual) term, once per panel (window-size independent).
@@ -1137,6 +1306,41 @@ int ensure_gl_terms(garlic_panel *p, bool scaled = false, int32_t M = 0, double 
             if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "term minimum: %s", hipGetErrorString(e));
             p->glterms_min = min_finite(part, NB);
         }
+    } else if (rebuild && p->gl_wide) {
+        // 16-bit codes: lod() on the device as for continuous values (or on the host), the weighted kernels' scaling in the same
+        // pass.  Room is judged as for a one-byte panel; declined (glterms_valid unset) the caller goes on to slabs.
+        if ((rc = ensure_log10(p->ctx)) || (rc = ensure_dfreq(p)) || (rc = ensure_values16(p))) return rc;
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return GARLIC_OK;
+        if (p->d_glterms.cap < n && n * sizeof(double) + ((size_t)8 << 30) > free_b) {
+            HIP_TRY(hipStreamSynchronize(s));
+            (void)score_pool_trim();
+            p->lds.release();
+            if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return GARLIC_OK;
+            if (n * sizeof(double) + ((size_t)8 << 30) > free_b) return GARLIC_OK;
+        }
+        if ((rc = p->d_glterms.reserve(n))) return rc;
+        p->glterms_valid = false;
+        const int nblk = (int)(p->nind_pad / WAVE);
+        if (tgls_terms_on_host(p)) {
+            if ((rc = build_wide_terms_on_host(p, 0, nblk, scaled ? p->h_decay.data() : nullptr, p->d_glterms.p, s, &p->glterms_min))) return rc;
+            p->gl_terms_by = 2;
+        } else {
+            DevBuf<unsigned long long> d_minbits;
+            if ((rc = d_minbits.reserve(GL_MIN_SLOTS))) return rc;
+            HIP_TRY(hipMemsetAsync(d_minbits.p, 0, sizeof(unsigned long long) * GL_MIN_SLOTS, s));
+            launch_wide_terms(p, 0, nblk, scaled ? p->d_decay.p : nullptr, p->d_glterms.p, d_minbits.p, s);
+            HIP_TRY(hipGetLastError());
+            unsigned long long bits[GL_MIN_SLOTS], best = 0;
+            hipError_t e = hipMemcpyAsync(bits, d_minbits.p, sizeof bits, hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess) e = hipStreamSynchronize(s);
+            if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "term minimum: %s", hipGetErrorString(e));
+            for (unsigned long long b : bits) best = std::max(best, b);
+            p->glterms_min = best ? f64_from_bits(best) : 0.0;
+            p->gl_terms_by = 1;
+        }
+        p->glterms_scaled = false;
+        fused_scale = scaled;
     } else if (rebuild) {
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return GARLIC_OK;
@@ -1228,7 +1432,9 @@ int tgls_terms_or_slabs(garlic_panel *p, int32_t *slab_blocks, bool scaled = fal
     *slab_blocks = 0;
     const size_t block = tgls_block_bytes(p), whole = block * (size_t)(p->nind_pad / WAVE);
     int rc;
-    if (p->gl_cont || p->terms_budget == 0 || getenv("GARLIC_GL_NO_TERMS") || (p->terms_budget > 0 && whole <= (size_t)p->terms_budget)) {
+    // (16-bit codes have no look-up chain to fall back to: where budget 0 finds no room for the whole matrix they go on as under -1)
+    const bool wide_auto = p->gl_wide && (p->terms_budget == 0 || getenv("GARLIC_GL_NO_TERMS"));
+    if (!wide_auto && (p->gl_cont || p->terms_budget == 0 || getenv("GARLIC_GL_NO_TERMS") || (p->terms_budget > 0 && whole <= (size_t)p->terms_budget))) {
         if (!p->gl_cont && p->d_slab[0].p) {       // (a budget that now admits the whole matrix: not both)
             HIP_TRY(hipStreamSynchronize(p->ctx->stream));
             release_tgls_slabs(p);
@@ -1236,10 +1442,16 @@ int tgls_terms_or_slabs(garlic_panel *p, int32_t *slab_blocks, bool scaled = fal
         return ensure_gl_terms(p, scaled, M, mu);
     }
     size_t bytes = (size_t)p->terms_budget;
-    if (p->terms_budget < 0) {
+    if (p->terms_budget < 0 || wide_auto) {
         // the whole matrix when today's test lets it in; otherwise two slab buffers in half of what is free now
         if ((rc = ensure_gl_terms(p, scaled, M, mu))) return rc;
-        if (p->glterms_valid && p->glterms_scaled == scaled) return GARLIC_OK;
+        if (p->glterms_valid && p->glterms_scaled == scaled) {
+            if (wide_auto && p->d_slab[0].p) {
+                HIP_TRY(hipStreamSynchronize(p->ctx->stream));
+                release_tgls_slabs(p);
+            }
+            return GARLIC_OK;
+        }
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return GARLIC_OK;
         bytes = (free_b + (p->d_slab[0].cap + p->d_slab[1].cap) * sizeof(double)) / 2;
@@ -1359,8 +1571,10 @@ int decide_form(garlic_panel *p, const LodCall &c, LodForm &f)
     if ((rc = ensure_segments(p, c.max_gap))) return rc;
     if (f.use_gl) {
         if (!p->have_gl) return fail(GARLIC_ERR_STATE, "use_gl set but no genotype likelihoods were given");
-        if (!p->gl_cont && (rc = ensure_gl_table(p))) return rc;
+        if (!p->gl_cont && !p->gl_wide && (rc = ensure_gl_table(p))) return rc;
         if (mode == MODE_LOD_GL && (rc = tgls_terms_or_slabs(p, &f.slab_blocks))) return rc;
+        if (mode == MODE_LOD_GL && p->gl_wide && !f.slab_blocks && !(p->glterms_valid && !p->glterms_scaled))
+            return fail(GARLIC_ERR_NOMEM, "16-bit likelihood codes: no room for the term matrix, nor for one-block term slabs");
     } else if ((rc = ensure_term_table(p, c.error))) return rc;
     if (mode == MODE_WLOD) {
         if (!select_ld(p, W))
@@ -1391,6 +1605,10 @@ int decide_form(garlic_panel *p, const LodCall &c, LodForm &f)
         else f.family = tgls_ring_shape ? Family::tgls_ring : Family::tgls_terms;
         f.writes_bits = f.family == Family::tgls_ring;
         if (f.exact_possible && getenv("GARLIC_EXACT_CHAIN_ONLY")) f.family = Family::exact;
+        // 16-bit codes have no look-up chain: what only that chain covers under slabs is refused
+        if (mode == MODE_LOD_GL && p->gl_wide && f.slab_blocks && f.family != Family::tgls_ring)
+            return fail(GARLIC_ERR_NOMEM, "16-bit likelihood codes: this call is not covered by term slabs (an ind_begin that is no "
+                                          "multiple of 64, GARLIC_TGLS_NO_RING or the by-value chain) and the whole term matrix has no room");
         if (f.family != Family::tgls_ring) f.slab_blocks = 0;
         // TGLS, thinned output: the ring chain that stores the sampled windows only (tgls_feed_kernel.hpp); the other TGLS
         // chains write full scores.  GARLIC_TGLS_FEED_FULL: never.
@@ -1423,6 +1641,9 @@ int decide_form(garlic_panel *p, const LodCall &c, LodForm &f)
     if (wlod_shape_ok && use_gl && (rc = tgls_terms_or_slabs(p, &f.slab_blocks, true, c.M, c.mu))) return rc;
     // a slab launch starts at a block of the matrix: a sub-range that does not, and every shape that keeps the generic
     // kernel, looks its terms up in the code table under a budget (nothing is built past the bound)
+    if (p->gl_wide && use_gl && f.slab_blocks && (c.ind_begin & (WAVE - 1)) != 0)
+        return fail(GARLIC_ERR_NOMEM, "16-bit likelihood codes: a weighted call whose ind_begin is no multiple of 64 is not covered by "
+                                      "term slabs and the whole term matrix has no room");
     if ((c.ind_begin & (WAVE - 1)) != 0) f.slab_blocks = 0;
     f.wlod_gl = wlod_shape_ok && use_gl && (f.slab_blocks || (p->glterms_valid && p->glterms_scaled));   // (the term matrix may have been declined)
     f.wlod_tuned = (wlod_shape_ok && !use_gl) || f.wlod_gl;
@@ -1436,6 +1657,20 @@ int decide_form(garlic_panel *p, const LodCall &c, LodForm &f)
     if (wlod_stream && (rc = ensure_rld(p))) return rc;
     // continuous likelihoods have no code table: the generic kernel takes its terms from the raw matrix
     if (use_gl && p->gl_cont && !f.wlod_tuned && (rc = ensure_gl_terms(p))) return rc;
+    // ... nor have 16-bit codes: the same, where the whole raw matrix may be held
+    if (use_gl && p->gl_wide && !f.wlod_tuned) {
+        const size_t whole = tgls_block_bytes(p) * (size_t)(p->nind_pad / WAVE);
+        if (p->terms_budget > 0 && whole > (size_t)p->terms_budget)
+            return fail(GARLIC_ERR_NOMEM, "16-bit likelihood codes: the generic weighted kernel is not covered by term slabs and the "
+                                          "term budget does not admit the whole matrix");
+        if (p->d_slab[0].p || p->d_slab[1].p) {
+            HIP_TRY(hipStreamSynchronize(p->ctx->stream));
+            release_tgls_slabs(p);
+        }
+        if ((rc = ensure_gl_terms(p))) return rc;
+        if (!(p->glterms_valid && !p->glterms_scaled))
+            return fail(GARLIC_ERR_NOMEM, "16-bit likelihood codes: the generic weighted kernel needs the whole term matrix, which has no room");
+    }
     if (!f.wlod_tuned) {
         f.family = Family::wlod_generic;
         f.slab_blocks = 0;
@@ -1669,7 +1904,7 @@ VariantArgs variant_args(const garlic_panel *p, const LodCall &c, const LodForm 
     return VariantArgs{p->d_packed.p, p->d_tab.p,  p->d_tabgl.p, p->d_codes.p, p->d_decay.p, p->d_rld.p,
                        p->d_items.p,  p->d_chrs.p, d_out,        p->nind_pad,  p->nwordrows, c.ind_begin,  c.ind_count,
                        c.W,           (int32_t)p->gl_values.size(), form.use_gl ? 1 : 0,
-                       (form.use_gl && p->gl_cont) ? p->d_glterms.p : nullptr, (int64_t)(GOFF + p->nloci + GPAD_BACK)};
+                       (form.use_gl && (p->gl_cont || p->gl_wide)) ? p->d_glterms.p : nullptr, (int64_t)(GOFF + p->nloci + GPAD_BACK)};
 }
 
 // the tile kernel of a family (the strip form's is the one that repairs it)
@@ -1828,19 +2063,32 @@ int for_each_tgls_slab(garlic_panel *p, const std::vector<Plan::Slab> &slabs, in
             if (need && (rc = p->d_slab[q].reserve(need))) return rc;
         }
     }
+    // 16-bit codes: the slab's terms come from lod() on the table values (gl_terms_wide_kernel; the host where the device's
+    // log10 is not the host's)
+    const bool wide = p->gl_wide, wide_host = wide && tgls_terms_on_host(p);
+    if (wide) {
+        if ((rc = ensure_log10(p->ctx)) || (rc = ensure_dfreq(p)) || (rc = ensure_values16(p))) return rc;
+        p->gl_terms_by = p->slab_terms_by = tgls_terms_on_host(p) ? 2 : 1;
+    }
     // what the term pass reads (tables, codes, genotypes) was put on the context's stream
     HIP_TRY(hipEventRecord(p->ev_slab_begin, s));
     HIP_TRY(hipStreamWaitEvent(p->slab_stream, p->ev_slab_begin, 0));
     VariantArgs a{p->d_packed.p, nullptr, p->d_tabgl.p, p->d_codes.p, nullptr, nullptr, nullptr, nullptr, nullptr,
                   p->nind_pad, p->nwordrows, 0, 0, 0, (int32_t)p->gl_values.size(), 1, nullptr, 0};
     const size_t terms_lds = sizeof(double) * GL_TERMS_S * 4 * (size_t)a.ncodes;      // <= 64 KB (256 codes)
-    if (terms_lds > LDS_DEFAULT_MAX)
+    if (!wide && terms_lds > LDS_DEFAULT_MAX)
         HIP_TRY(hipFuncSetAttribute((const void *)gl_terms_slab_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)terms_lds));
     const unsigned terms_grid = (unsigned)((p->nloci + GL_TERMS_S - 1) / GL_TERMS_S + (GL_PAD_ROWS + GL_TERMS_S - 1) / GL_TERMS_S);
     for (size_t k = 0; k < n_slabs; k++) {
         const Plan::Slab &sl = slabs[k];
         const int q = (int)(k & 1);
         if (k >= 2) HIP_TRY(hipStreamWaitEvent(p->slab_stream, p->ev_slab_read[q], 0));
+        if (wide_host) {
+            if ((rc = build_wide_terms_on_host(p, sl.b0, sl.b1, scaled ? p->h_decay.data() : nullptr, p->d_slab[q].p, p->slab_stream, nullptr)))
+                return rc;
+        } else if (wide)
+            launch_wide_terms(p, sl.b0, sl.b1, scaled ? p->d_decay.p : nullptr, p->d_slab[q].p, nullptr, p->slab_stream);
+        else
         hipLaunchKernelGGL(gl_terms_slab_kernel, dim3(terms_grid), dim3(256), terms_lds, p->slab_stream, a, p->nloci, rows, sl.b0, sl.b1,
                            scaled ? p->d_decay.p : (const double *)nullptr, p->d_slab[q].p);
         HIP_TRY(hipGetLastError());
@@ -2067,6 +2315,9 @@ int launch_lod(garlic_panel *p, Mode mode, int32_t W, double error, int32_t max_
         HIP_TRY(hipMemcpyAsync(&found, p->d_counter.p + 2, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         p->last_chain_kind = found ? 2 : 1;
+        if (found && form.use_gl && p->gl_wide && !(p->glterms_valid && !p->glterms_scaled && p->d_glterms.p))
+            return fail(GARLIC_ERR_NOMEM, "16-bit likelihood codes: a window sums to exactly -9999.0 and the by-value chain needs the "
+                                          "whole term matrix, which the term budget does not admit");
         if (found && (rc = enqueue_lod(p, c, form, L, plan, reuse ? nullptr : &work, d_out, Family::exact))) return rc;
     }
     if (where == GARLIC_HOST)
@@ -2291,6 +2542,7 @@ int garlic_panel_set_freq(garlic_panel *p, const double *freq)
 {
     if (!p || !freq) return fail(GARLIC_ERR_INVALID, "panel and freq are required");
     p->freq.assign(freq, freq + p->nloci);
+    p->wide_bound_known = false;
     p->have_freq = true;
     p->tab_valid = false;
     p->tabgl_valid = false;
@@ -2388,6 +2640,150 @@ int garlic_panel_set_genotypes_2bit(garlic_panel *p, const uint8_t *rows, int64_
     return GARLIC_OK;
 }
 
+// ---- uploads into a panel of 16-bit codes.
+// The caller's table joins the panel's (by bit pattern, first seen first): remap[caller code] = panel code.  When the merged
+// table would pass 65,536 values the panel goes on with the values themselves (gl_wide unset on return; remap is void then).
+static int merge_wide_table(garlic_panel *p, const double *values, int32_t nvalues, std::vector<uint16_t> &remap)
+{
+    remap.assign((size_t)nvalues, 0);
+    size_t fresh = 0;
+    for (int k = 0; k < nvalues; k++) {
+        uint64_t bits;
+        memcpy(&bits, &values[k], sizeof bits);
+        fresh += p->gl_code.count(bits) == 0;      // (a value twice in the caller's table counts twice: an upper bound is enough)
+    }
+    if (p->gl_values.size() + fresh > (size_t)GL_WIDE_MAX) {
+        std::unordered_map<uint64_t, int> probe = p->gl_code;      // exact count before giving the codes up
+        for (int k = 0; k < nvalues; k++) {
+            uint64_t bits;
+            memcpy(&bits, &values[k], sizeof bits);
+            probe.emplace(bits, 0);
+        }
+        if (probe.size() > (size_t)GL_WIDE_MAX) return switch_to_continuous(p);
+    }
+    for (int k = 0; k < nvalues; k++) {
+        uint64_t bits;
+        memcpy(&bits, &values[k], sizeof bits);
+        auto it = p->gl_code.find(bits);
+        if (it == p->gl_code.end()) {
+            it = p->gl_code.emplace(bits, (int)p->gl_values.size()).first;
+            p->gl_values.push_back(values[k]);
+            p->wide_bound_known = false;
+            p->values16_valid = false;
+        }
+        remap[(size_t)k] = (uint16_t)it->second;
+    }
+    return GARLIC_OK;
+}
+
+// caller rows of one-byte (codes8) or 16-bit (codes16) codes, translated by remap into the panel's codes
+static int upload_wide_codes(garlic_panel *p, const uint8_t *codes8, const uint16_t *codes16, int64_t ld, int64_t locus_begin,
+                             int64_t locus_count, const std::vector<uint16_t> &remap, int32_t where)
+{
+    hipStream_t s = p->ctx->stream;
+    const int64_t rows_total = GOFF + p->nloci + GPAD_BACK;
+    const size_t esz = codes8 ? 1 : 2;
+    const uint8_t *base = codes8 ? codes8 : (const uint8_t *)codes16;
+    DevBuf<uint8_t> stage;
+    DevBuf<uint16_t> d_remap;
+    int rc;
+    if ((rc = d_remap.reserve(remap.size()))) return rc;
+    hipError_t e = hipMemcpy(d_remap.p, remap.data(), sizeof(uint16_t) * remap.size(), hipMemcpyHostToDevice);
+    const int64_t slab_rows = (where == GARLIC_HOST) ? std::max<int64_t>(16, ((int64_t)256 << 20) / (int64_t)(esz * ld)) : locus_count;
+    for (int64_t at = 0; e == hipSuccess && at < locus_count; at += slab_rows) {
+        const int64_t nrows = std::min(slab_rows, locus_count - at);
+        const uint8_t *src = base + (size_t)(at * ld) * esz;
+        if (where == GARLIC_HOST) {
+            if ((rc = stage.reserve((size_t)(nrows * ld) * esz))) return rc;
+            e = hipMemcpyAsync(stage.p, src, (size_t)(nrows * ld) * esz, hipMemcpyHostToDevice, s);
+            src = stage.p;
+        }
+        if (e != hipSuccess) break;
+        if (codes8)
+            hipLaunchKernelGGL(gl_recode8to16_kernel, dim3(2048), dim3(256), 0, s, src, ld, locus_begin + at, nrows, p->nind, d_remap.p,
+                               rows_total, p->d_codes16.p);
+        else
+            hipLaunchKernelGGL(gl_recode16_kernel, dim3(2048), dim3(256), 0, s, (const uint16_t *)src, ld, locus_begin + at, nrows, p->nind,
+                               d_remap.p, (int32_t)remap.size(), rows_total, p->d_codes16.p);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(s);                      // staging slab free again
+    }
+    if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "set_gl_codes16: %s", hipGetErrorString(e));
+    p->have_gl = true;
+    p->glterms_valid = false;
+    return GARLIC_OK;
+}
+
+// garlic_panel_set_gl on a panel of 16-bit codes: coded on the device against the table so far, unknown values come back and
+// join it (the loop of the one-byte path with a table in global memory); past 65,536 values the panel turns continuous and the
+// call starts over on that path.
+static int set_gl_wide(garlic_panel *p, const double *gl, int64_t ld, int64_t locus_begin, int64_t locus_count, int32_t where)
+{
+    hipStream_t s = p->ctx->stream;
+    const int64_t rows_total = GOFF + p->nloci + GPAD_BACK;
+    constexpr int UNK_CAP = 8192;
+    DevBuf<double> stage;
+    DevBuf<uint64_t> d_bits, d_unk;
+    DevBuf<uint16_t> d_dcode;
+    DevBuf<int32_t> d_nunk;
+    int rc;
+    if ((rc = d_bits.reserve(GL_WIDE_MAX)) || (rc = d_dcode.reserve(GL_WIDE_MAX)) || (rc = d_unk.reserve(UNK_CAP)) || (rc = d_nunk.reserve(1)))
+        return rc;
+    const int64_t slab_rows = (where == GARLIC_HOST) ? std::max<int64_t>(16, ((int64_t)256 << 20) / (8 * ld)) : locus_count;
+    std::vector<uint64_t> unk(UNK_CAP);
+    for (int64_t at = 0; at < locus_count; at += slab_rows) {
+        const int64_t nrows = std::min(slab_rows, locus_count - at);
+        const double *src = gl + at * ld;
+        hipError_t e = hipSuccess;
+        if (where == GARLIC_HOST) {
+            if ((rc = stage.reserve((size_t)(nrows * ld)))) return rc;
+            e = hipMemcpyAsync(stage.p, src, sizeof(double) * nrows * ld, hipMemcpyHostToDevice, s);
+            src = stage.p;
+        }
+        while (e == hipSuccess) {   // until the slab holds no value outside the dictionary
+            std::vector<std::pair<uint64_t, uint16_t>> dict;
+            for (auto &kv : p->gl_code) dict.emplace_back(kv.first, (uint16_t)kv.second);
+            std::sort(dict.begin(), dict.end());
+            std::vector<uint64_t> hb(dict.size());
+            std::vector<uint16_t> hc(dict.size());
+            for (size_t k = 0; k < dict.size(); k++) { hb[k] = dict[k].first; hc[k] = dict[k].second; }
+            if (!dict.empty()) {
+                e = hipMemcpyAsync(d_bits.p, hb.data(), sizeof(uint64_t) * hb.size(), hipMemcpyHostToDevice, s);
+                if (e == hipSuccess) e = hipMemcpyAsync(d_dcode.p, hc.data(), sizeof(uint16_t) * hc.size(), hipMemcpyHostToDevice, s);
+            }
+            if (e == hipSuccess) e = hipMemsetAsync(d_nunk.p, 0, sizeof(int32_t), s);
+            if (e != hipSuccess) break;
+            hipLaunchKernelGGL(gl_encode16_kernel, dim3(2048), dim3(256), 0, s, src, ld, locus_begin + at, nrows, p->nind, d_bits.p, d_dcode.p,
+                               (int)dict.size(), rows_total, p->d_codes16.p, d_unk.p, d_nunk.p, UNK_CAP);
+            int32_t nunk = 0;
+            e = hipGetLastError();
+            if (e == hipSuccess) e = hipMemcpyAsync(&nunk, d_nunk.p, sizeof nunk, hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess) e = hipStreamSynchronize(s);
+            if (e != hipSuccess || nunk == 0) break;
+            const int got = std::min<int32_t>(nunk, UNK_CAP);
+            e = hipMemcpy(unk.data(), d_unk.p, sizeof(uint64_t) * got, hipMemcpyDeviceToHost);
+            if (e != hipSuccess) break;
+            for (int k = 0; k < got; k++) {
+                if (p->gl_code.count(unk[k])) continue;
+                if (p->gl_values.size() >= (size_t)GL_WIDE_MAX) {      // continuous after all: decode, and the rest of the call as values
+                    if ((rc = switch_to_continuous(p))) return rc;
+                    return garlic_panel_set_gl(p, gl + at * ld, ld, locus_begin + at, locus_count - at, where);
+                }
+                double v;
+                memcpy(&v, &unk[k], sizeof v);
+                p->gl_code.emplace(unk[k], (int)p->gl_values.size());
+                p->gl_values.push_back(v);
+                p->wide_bound_known = false;
+                p->values16_valid = false;
+            }
+        }
+        if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "set_gl: %s", hipGetErrorString(e));
+    }
+    p->have_gl = true;
+    p->glterms_valid = false;
+    return GARLIC_OK;
+}
+
 int garlic_panel_set_gl(garlic_panel *p, const double *gl, int64_t ld, int64_t locus_begin,
                         int64_t locus_count, int32_t where)
 {
@@ -2402,6 +2798,7 @@ int garlic_panel_set_gl(garlic_panel *p, const double *gl, int64_t ld, int64_t l
     const int64_t rows_total = GOFF + p->nloci + GPAD_BACK;
     if ((rc = restart_continuous_upload(p))) return rc;
     if (!p->gl_cont && getenv("GARLIC_TGLS_CONTINUOUS") && (rc = switch_to_continuous(p))) return rc;
+    if (p->gl_wide) return set_gl_wide(p, gl, ld, locus_begin, locus_count, where);
     if (!p->gl_cont && !p->d_codes.p) {
         if ((rc = p->d_codes.reserve((size_t)(rows_total * p->nind_pad)))) return rc;
         HIP_TRY(hipMemsetAsync(p->d_codes.p, 0, (size_t)(rows_total * p->nind_pad), s));
@@ -2467,6 +2864,7 @@ int garlic_panel_set_gl(garlic_panel *p, const double *gl, int64_t ld, int64_t l
                 memcpy(&v, &unk[k], sizeof v);
                 p->gl_code.emplace(unk[k], code);
                 p->gl_values.push_back(v);
+                p->wide_bound_known = false;
                 p->tabgl_valid = false;
             }
         }
@@ -2502,6 +2900,14 @@ int garlic_panel_set_gl_codes(garlic_panel *p, const uint8_t *codes, int64_t ld,
     if (!p->gl_cont && getenv("GARLIC_TGLS_CONTINUOUS") && (rc = switch_to_continuous(p))) return rc;
     // the caller's table joins the panel's dictionary; its codes are translated on the device.  A
     // panel whose tables add up to more than 256 values keeps the values themselves from then on.
+    if (p->gl_wide) {
+        std::vector<uint16_t> remap16;
+        if ((rc = merge_wide_table(p, values, nvalues, remap16))) return rc;
+        if (p->gl_wide) {
+            remap16.resize(256, 0);
+            return upload_wide_codes(p, codes, nullptr, ld, locus_begin, locus_count, remap16, where);
+        }
+    }
     uint8_t remap[256] = {0};
     for (int k = 0; k < nvalues && !p->gl_cont; k++) {
         uint64_t bits;
@@ -2513,12 +2919,14 @@ int garlic_panel_set_gl_codes(garlic_panel *p, const uint8_t *codes, int64_t ld,
                 if (!p->d_codes.p) {   // nothing coded yet: start from an empty value matrix
                     p->gl_code.clear();
                     p->gl_values.clear();
+                    p->wide_bound_known = false;
                 }
                 if ((rc = switch_to_continuous(p))) return rc;
                 break;
             }
             it = p->gl_code.emplace(bits, code).first;
             p->gl_values.push_back(values[k]);
+            p->wide_bound_known = false;
             p->tabgl_valid = false;
         }
         remap[k] = (uint8_t)it->second;
@@ -2561,6 +2969,53 @@ int garlic_panel_set_gl_codes(garlic_panel *p, const uint8_t *codes, int64_t ld,
     if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "set_gl_codes: %s", hipGetErrorString(e));
     if (p->gl_cont && !p->gl_cover.empty())
         memset(p->gl_cover.data() + locus_begin, 1, (size_t)locus_count);
+    p->have_gl = true;
+    p->glterms_valid = false;
+    return GARLIC_OK;
+}
+
+int garlic_panel_set_gl_codes16(garlic_panel *p, const uint16_t *codes, int64_t ld, int64_t locus_begin,
+                                int64_t locus_count, const double *values, int32_t nvalues, int32_t where)
+{
+    if (!p || !codes || !values) return fail(GARLIC_ERR_INVALID, "panel, codes and values are required");
+    if (nvalues < 1 || nvalues > GL_WIDE_MAX) return fail(GARLIC_ERR_INVALID, "nvalues must be 1..65536 (got %d)", nvalues);
+    if (ld < p->nind) return fail(GARLIC_ERR_INVALID, "ld %lld < nind %d", (long long)ld, p->nind);
+    if (locus_begin < 0 || locus_count < 1 || locus_begin + locus_count > p->nloci)
+        return fail(GARLIC_ERR_INVALID, "locus range [%lld,+%lld) outside panel of %lld loci",
+                    (long long)locus_begin, (long long)locus_count, (long long)p->nloci);
+    int rc;
+    if ((rc = set_device(p->ctx))) return rc;
+    hipStream_t s = p->ctx->stream;
+    const int64_t rows_total = GOFF + p->nloci + GPAD_BACK;
+    if ((rc = restart_continuous_upload(p))) return rc;
+    if (!p->gl_cont && getenv("GARLIC_TGLS_CONTINUOUS") && (rc = switch_to_continuous(p))) return rc;
+    if (!p->gl_cont) {
+        std::vector<uint16_t> remap;
+        if ((rc = switch_to_wide(p)) || (rc = merge_wide_table(p, values, nvalues, remap))) return rc;
+        if (p->gl_wide) return upload_wide_codes(p, nullptr, codes, ld, locus_begin, locus_count, remap, where);
+    }
+    // a continuous panel: the caller's codes become values straight away
+    DevBuf<uint16_t> stage;
+    DevBuf<double> d_dict;
+    if ((rc = d_dict.reserve((size_t)nvalues))) return rc;
+    hipError_t e = hipMemcpy(d_dict.p, values, sizeof(double) * (size_t)nvalues, hipMemcpyHostToDevice);
+    const int64_t slab_rows = (where == GARLIC_HOST) ? std::max<int64_t>(16, ((int64_t)256 << 20) / (2 * ld)) : locus_count;
+    for (int64_t at = 0; e == hipSuccess && at < locus_count; at += slab_rows) {
+        const int64_t nrows = std::min(slab_rows, locus_count - at);
+        const uint16_t *src = codes + at * ld;
+        if (where == GARLIC_HOST) {
+            if ((rc = stage.reserve((size_t)(nrows * ld)))) return rc;
+            e = hipMemcpyAsync(stage.p, src, sizeof(uint16_t) * (size_t)(nrows * ld), hipMemcpyHostToDevice, s);
+            src = stage.p;
+        }
+        if (e != hipSuccess) break;
+        hipLaunchKernelGGL(gl_store_codes16_kernel, dim3(2048), dim3(256), 0, s, src, ld, locus_begin + at, nrows, p->nind, d_dict.p,
+                           nvalues, rows_total, p->d_glval.p);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(s);                      // staging slab free again
+    }
+    if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "set_gl_codes16: %s", hipGetErrorString(e));
+    if (!p->gl_cover.empty()) memset(p->gl_cover.data() + locus_begin, 1, (size_t)locus_count);
     p->have_gl = true;
     p->glterms_valid = false;
     return GARLIC_OK;
@@ -4709,8 +5164,9 @@ int garlic_roh_segments(garlic_panel *p, int32_t winsize, double error, int32_t 
 int garlic_panel_tgls_mode(garlic_panel *p, int32_t *mode, int32_t *terms_by)
 {
     if (!p || !mode) return fail(GARLIC_ERR_INVALID, "panel and mode are required");
-    *mode = !p->have_gl ? 0 : (p->gl_cont ? GARLIC_TGLS_CONTINUOUS : GARLIC_TGLS_DICTIONARY);
-    if (terms_by) *terms_by = p->glterms_valid ? p->gl_terms_by : 0;
+    *mode = !p->have_gl ? 0 : p->gl_cont ? GARLIC_TGLS_CONTINUOUS : p->gl_wide ? GARLIC_TGLS_DICTIONARY16 : GARLIC_TGLS_DICTIONARY;
+    // 16-bit codes under term slabs: there is no resident matrix, the answer is who built the slabs of the last call
+    if (terms_by) *terms_by = p->glterms_valid ? p->gl_terms_by : (p->gl_wide && p->last_n_slabs > 0) ? p->slab_terms_by : 0;
     return GARLIC_OK;
 }
 

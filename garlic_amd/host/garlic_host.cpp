@@ -16,6 +16,7 @@
 #include <random>
 #include <mutex>
 #include <thread>
+#include <unordered_map>
 #include <ctime>
 
 namespace garlic_host {
@@ -226,6 +227,7 @@ GenoLikeData *initGLData(unsigned int nind, unsigned int nloci)
     d->codes = nullptr;
     d->values = nullptr;
     d->nvalues = 0;
+    d->codes16 = nullptr;
     for (unsigned l = 0; l < nloci; l++) {
         d->data[l] = new double[nind];
         std::fill(d->data[l], d->data[l] + nind, (double)MISSING);
@@ -238,9 +240,11 @@ void releaseGLData(GenoLikeData *d)
     for (int l = 0; l < d->nloci; l++) {
         if (d->data) delete[] d->data[l];
         if (d->codes) delete[] d->codes[l];
+        if (d->codes16) delete[] d->codes16[l];
     }
     delete[] d->data;
     delete[] d->codes;
+    delete[] d->codes16;
     delete[] d->values;
     delete d;
 }
@@ -539,8 +543,13 @@ std::vector<GenoLikeData *> *readTGLSData(const std::string &filename, int /*exp
     std::string line, junk;
     for (auto m : *maps) {
         GenoLikeData *d;
-        if (compact) {   // one byte per genotype and a table of the distinct converted values
-            d = new GenoLikeData{nullptr, expectedInd, m->nloci, new unsigned char *[m->nloci](), new double[256], 0};
+        // compact: one byte per genotype and a table of the distinct converted values, in the order they are first seen;
+        // at the 257th value the rows read so far widen to two bytes, at the 65,537th to the doubles themselves
+        int width = compact ? 1 : 8;
+        std::unordered_map<uint64_t, int> code_of;   // bit pattern of a value -> its code
+        if (compact) {
+            d = new GenoLikeData{nullptr, expectedInd, m->nloci, new unsigned char *[m->nloci](), new double[256], 0, nullptr};
+            code_of.reserve(512);
         } else {
             d = initGLData(expectedInd, m->nloci);
         }
@@ -551,6 +560,11 @@ std::vector<GenoLikeData *> *readTGLSData(const std::string &filename, int /*exp
             if (num != expectedInd + 4) fail("Incorrect number of columns in tgls file: " + std::to_string(num));
             std::stringstream ss(line);
             ss >> junk >> junk >> junk >> junk;
+            if (compact && width == 1) d->codes[l] = new unsigned char[expectedInd];
+            else if (compact && width == 2) d->codes16[l] = new unsigned short[expectedInd];
+            else if (compact) d->data[l] = new double[expectedInd];
+            uint64_t last_bits = 0;
+            int last_code = -1;
             for (int i = 0; i < expectedInd; i++) {
                 double gl;
                 ss >> gl;
@@ -560,15 +574,60 @@ std::vector<GenoLikeData *> *readTGLSData(const std::string &filename, int /*exp
                 else { gl /= (-10.0); gl = (gl > -10) ? gl : -10; gl = 1 - pow(10, gl); }
                 if (gl <= 0) gl = 0.0000000000000001;
                 if (gl > 1) gl = 1;
-                if (!compact) { d->data[l][i] = gl; continue; }
-                if (i == 0) d->codes[l] = new unsigned char[expectedInd];
-                int code = 0;
-                while (code < d->nvalues && memcmp(&d->values[code], &gl, sizeof gl) != 0) code++;
-                if (code == d->nvalues) {
-                    if (code == 256) fail("more than 256 distinct genotype likelihood values on " + m->chr + " in " + filename);
+                if (width == 8) { d->data[l][i] = gl; continue; }
+                uint64_t bits;
+                memcpy(&bits, &gl, sizeof bits);
+                int code;
+                if (last_code >= 0 && bits == last_bits) {
+                    code = last_code;
+                } else {
+                    auto hit = code_of.find(bits);
+                    code = hit == code_of.end() ? -1 : hit->second;
+                }
+                if (code < 0 && d->nvalues == 256 && width == 1) {          // rows 0 .. l (this one up to i) widen to 16 bits
+                    d->codes16 = new unsigned short *[m->nloci]();
+                    for (int r = 0; r <= l; r++) {
+                        d->codes16[r] = new unsigned short[expectedInd];
+                        const int n = r < l ? expectedInd : i;
+                        for (int k = 0; k < n; k++) d->codes16[r][k] = d->codes[r][k];
+                        delete[] d->codes[r];
+                    }
+                    delete[] d->codes;
+                    d->codes = nullptr;
+                    double *wider = new double[65536];
+                    memcpy(wider, d->values, 256 * sizeof(double));
+                    delete[] d->values;
+                    d->values = wider;
+                    code_of.reserve(1 << 17);
+                    width = 2;
+                }
+                if (code < 0 && d->nvalues == 65536) {                      // ... and past 65,536 values to the doubles
+                    d->data = new double *[m->nloci]();
+                    for (int r = 0; r <= l; r++) {
+                        d->data[r] = new double[expectedInd];
+                        const int n = r < l ? expectedInd : i;
+                        for (int k = 0; k < n; k++) d->data[r][k] = d->values[d->codes16[r][k]];
+                        delete[] d->codes16[r];
+                    }
+                    delete[] d->codes16;
+                    d->codes16 = nullptr;
+                    delete[] d->values;
+                    d->values = nullptr;
+                    d->nvalues = 0;
+                    code_of.clear();
+                    width = 8;
+                    d->data[l][i] = gl;
+                    continue;
+                }
+                if (code < 0) {
+                    code = d->nvalues;
+                    code_of.emplace(bits, code);
                     d->values[d->nvalues++] = gl;
                 }
-                d->codes[l][i] = (unsigned char)code;
+                last_bits = bits;
+                last_code = code;
+                if (width == 1) d->codes[l][i] = (unsigned char)code;
+                else d->codes16[l][i] = (unsigned short)code;
             }
         }
     }
@@ -668,7 +727,7 @@ void filterSites(size_t c, const std::vector<char> &keep, std::vector<MapData *>
     GenoLikeData *g2 = nullptr;
     if (g) {
         g2 = new GenoLikeData{g->data ? new double *[n] : nullptr, g->nind, n, g->codes ? new unsigned char *[n] : nullptr,
-                              g->values, g->nvalues};
+                              g->values, g->nvalues, g->codes16 ? new unsigned short *[n] : nullptr};
         if (g->values) g->values = nullptr;   // the table moves on with the kept rows
     }
     int j = 0;
@@ -680,6 +739,7 @@ void filterSites(size_t c, const std::vector<char> &keep, std::vector<MapData *>
             if (h->phaseBits) delete[] h->phaseBits[l];
             if (g && g->data) delete[] g->data[l];
             if (g && g->codes) delete[] g->codes[l];
+            if (g && g->codes16) delete[] g->codes16[l];
             continue;
         }
         m2->physicalPos[j] = m->physicalPos[l]; m2->geneticPos[j] = m->geneticPos[l];
@@ -691,10 +751,11 @@ void filterSites(size_t c, const std::vector<char> &keep, std::vector<MapData *>
         f2->freq[j] = f->freq[l];
         if (g && g->data) g2->data[j] = g->data[l];
         if (g && g->codes) g2->codes[j] = g->codes[l];
+        if (g && g->codes16) g2->codes16[j] = g->codes16[l];
         j++;
     }
     delete[] h->data; delete[] h->firstCopy; delete[] h->packed; delete[] h->phaseBits; delete h;
-    if (g) { delete[] g->data; delete[] g->codes; delete g; (*gls)[c] = g2; }
+    if (g) { delete[] g->data; delete[] g->codes; delete[] g->codes16; delete g; (*gls)[c] = g2; }
     releaseMapData(m); releaseFreqData(f);
     (*maps)[c] = m2; (*haps)[c] = h2; (*freqs)[c] = f2;
 }
@@ -1029,7 +1090,12 @@ void LodEngine::upload(std::vector<HapData *> *haps, std::vector<FreqData *> *fr
     const int64_t slab = std::max<int64_t>(1, ((int64_t)64 << 20) / (2 * (int64_t)impl->nind));
     std::vector<int16_t> stage;
     std::vector<uint8_t> stage2, stage_glc;
+    std::vector<uint16_t> stage_glc16;
     std::vector<double> stage_gl;
+    // one chromosome with 16-bit codes: the one-byte chromosomes go up widened too, so the panel's table merges them all
+    // (one-byte uploads alone that pass 256 values between them would turn the panel continuous)
+    bool wide_codes = false;
+    if (USE_GL) for (auto g : *gls) wide_codes = wide_codes || g->codes16;
     std::vector<uint8_t> stage_fc, stage_fcbits;
     impl->have_phase = true;
     for (auto h : *haps) impl->have_phase = impl->have_phase && hasPhase(h);
@@ -1048,7 +1114,13 @@ void LodEngine::upload(std::vector<HapData *> *haps, std::vector<FreqData *> *fr
                     memcpy(&stage[(size_t)r * impl->nind], h->data[l0 + r], sizeof(short) * impl->nind);
             }
             const GenoLikeData *gld = USE_GL ? gls->at(c) : nullptr;
-            if (gld && gld->codes) {
+            const bool gl16 = gld && (gld->codes16 || (gld->codes && wide_codes));
+            if (gl16) {
+                stage_glc16.resize((size_t)rows * impl->nind);
+                for (int r = 0; r < rows; r++)
+                    for (int i = 0; i < impl->nind; i++)
+                        stage_glc16[(size_t)r * impl->nind + i] = gld->codes16 ? gld->codes16[l0 + r][i] : gld->codes[l0 + r][i];
+            } else if (gld && gld->codes) {
                 stage_glc.resize((size_t)rows * impl->nind);
                 for (int r = 0; r < rows; r++) memcpy(&stage_glc[(size_t)r * impl->nind], gld->codes[l0 + r], impl->nind);
             } else if (gld) {
@@ -1091,7 +1163,10 @@ void LodEngine::upload(std::vector<HapData *> *haps, std::vector<FreqData *> *fr
                     check(garlic_panel_set_phase(s.panel, stage_fc.data() + s.ind_begin, impl->nind, o + l0, rows,
                                                  GARLIC_HOST), "garlic_panel_set_phase");
                 }
-                if (gld && gld->codes)
+                if (gl16)
+                    check(garlic_panel_set_gl_codes16(s.panel, stage_glc16.data() + s.ind_begin, impl->nind, o + l0, rows,
+                                                      gld->values, gld->nvalues, GARLIC_HOST), "garlic_panel_set_gl_codes16");
+                else if (gld && gld->codes)
                     check(garlic_panel_set_gl_codes(s.panel, stage_glc.data() + s.ind_begin, impl->nind, o + l0, rows,
                                                     gld->values, gld->nvalues, GARLIC_HOST), "garlic_panel_set_gl_codes");
                 else if (gld)

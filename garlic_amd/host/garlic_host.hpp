@@ -66,14 +66,21 @@ struct GenoLikeData {      // src/garlic-data.h:89-95
     // Extension (readTGLSData with compact = true): the same values dictionary-coded, one byte per
     // genotype -- codes[locus][ind] indexes values[0 .. nvalues) -- and `data` NULL.  GQ / PL / GL
     // files hold a few dozen distinct values; the engine uploads the codes as they are.
+    // A chromosome with more than 256 distinct values (GL / PL columns of printed numbers) has codes16
+    // instead, two bytes per genotype and up to 65,536 values; one with more than that has `data` and
+    // no table.  Exactly one of data / codes / codes16 is set.
     unsigned char **codes;
     double *values;
     int nvalues;
+    unsigned short **codes16;
 };
 inline double likelihoodAt(const GenoLikeData *g, int locus, int ind)
 {
-    return g->data ? g->data[locus][ind] : g->values[g->codes[locus][ind]];
+    if (g->data) return g->data[locus][ind];
+    return g->values[g->codes16 ? g->codes16[locus][ind] : g->codes[locus][ind]];
 }
+// "one-byte codes", "16-bit codes" or "doubles": how a chromosome's likelihoods are held
+inline const char *likelihoodForm(const GenoLikeData *g) { return g->data ? "doubles" : g->codes16 ? "16-bit codes" : "one-byte codes"; }
 struct LDData {            // src/garlic-data.h:103-108
     double **LD;           // [locus][winsize]
     int nloci;
@@ -149,7 +156,7 @@ IndData *readIndData3(const std::string &filename, int numInd);                 
 std::vector<GenoLikeData *> *readTGLSData(const std::string &filename, int expectedLoci, int expectedInd,
                                           std::vector<MapData *> *mapDataByChr,
                                           const std::string &GL_TYPE,
-                                          bool compact = false);   // compact: ::codes instead of ::data             // :1516
+                                          bool compact = false);   // compact: ::codes / ::codes16 where the values allow, else ::data   // :1516
 std::vector<FreqData *> *readFreqData(const std::string &freqfile,
                                       std::vector<MapData *> *mapDataByChr);        // :1345
 void writeFreqData(const std::string &freqOutfile, std::vector<FreqData *> *freqDataByChr,

@@ -195,7 +195,16 @@ int main(int argc, char **argv)
         std::cerr << "Loaded " << numLoci << " loci x " << numInd << " individuals (" << maps->size() << " chromosomes)\n";
 
         const bool USE_GL = a.tgls != "none";
-        if (USE_GL) gls = readTGLSData(a.tgls, numLoci, numInd, maps, a.gl_type, /*compact=*/true); // rows in pre-filter TPED order
+        if (USE_GL) {
+            gls = readTGLSData(a.tgls, numLoci, numInd, maps, a.gl_type, /*compact=*/true); // rows in pre-filter TPED order
+            // the form each chromosome took: one byte per genotype up to 256 distinct values, two up to 65,536, else doubles
+            std::cerr << "Genotype likelihoods (" << a.gl_type << "):";
+            for (size_t c = 0; c < gls->size(); c++) {
+                std::cerr << (c ? ", " : " ") << maps->at(c)->chr << " as " << likelihoodForm(gls->at(c));
+                if (!gls->at(c)->data) std::cerr << " (" << gls->at(c)->nvalues << " values)";
+            }
+            std::cerr << "\n";
+        }
         if (a.freq_file != "none") { releaseFreqData(freqs); freqs = nullptr; freqs = readFreqData(a.freq_file, maps); }
         else writeFreqData(a.out + ".freq", freqs, maps);                        // garlic-main.cpp:245-253
         int kept;

@@ -51,7 +51,7 @@ extern "C" {
  *    garlic_lod_feed_multi_info, GARLIC_FEED_TGLS_CHAIN_SHARED (likewise); garlic_panel_compute_ld_multi,
  *    garlic_ld_finish_multi, garlic_panel_ld_info (likewise); garlic_panel_set_feed_order, garlic_feed_sort,
  *    garlic_feed_sort_info, GARLIC_FEED_ORDER_* (likewise); garlic_panel_set_phase_bits, garlic_panel_ld_form_info,
- *    GARLIC_LD_PAIR_* / GARLIC_LD_SUM_* (likewise) */
+ *    GARLIC_LD_PAIR_* / GARLIC_LD_SUM_* (likewise); garlic_panel_set_gl_codes16, GARLIC_TGLS_DICTIONARY16 (likewise) */
 #define GARLIC_HIP_ABI_VERSION 8
 
 #define GARLIC_OK 0
@@ -131,13 +131,22 @@ int garlic_panel_set_genotypes_2bit(garlic_panel *panel, const uint8_t *rows, in
                                     int32_t where);
 
 /* GenoLikeData::data (src/garlic-data.h:91): per-genotype error probabilities, already converted
- * as readTGLSData does (src/garlic-data.cpp:1557-1576); same addressing as genotypes.  Any doubles:
- * while a panel has seen at most 256 distinct values (--gl-type GQ, PL integers) it keeps one-byte
- * dictionary codes and the host tabulates lod() per (SNP, value, genotype) with the host libm; beyond
- * that (--gl-type GL, continuous values) it keeps the values themselves (8 bytes per genotype) and
- * lod() (src/garlic-roh.cpp:355-386) runs on the device with glibc's log10 restated operation by
+ * as readTGLSData does (src/garlic-data.cpp:1557-1576); same addressing as genotypes.  Any doubles.
+ * A panel holds its likelihoods in one of three forms (garlic_panel_tgls_mode):
+ *   GARLIC_TGLS_DICTIONARY    one-byte codes, at most 256 distinct values (--gl-type GQ, PL integers): the host tabulates
+ *                             lod() per (SNP, value, genotype) with the host libm.
+ *   GARLIC_TGLS_DICTIONARY16  16-bit codes (2 bytes per genotype) and one panel-wide table of at most 65,536 values
+ *                             (--gl-type GL / PL as printed numbers: a column of three decimals holds about 10,000).
+ *   GARLIC_TGLS_CONTINUOUS    the values themselves, 8 bytes per genotype.
+ * In the last two forms lod() (src/garlic-roh.cpp:355-386) runs on the device with glibc's log10 restated operation by
  * operation -- checked against the host's log10 when first needed; should they ever differ, the terms
- * are computed on the host instead.  Same scores either way: those of the reference on this host.
+ * are computed on the host instead.  Same scores in every form: those of the reference on this host.
+ * Transitions.  A panel enters DICTIONARY16 through garlic_panel_set_gl_codes16 only: from no likelihoods, or from
+ * one-byte codes, which a kernel widens (the code numbers stay).  Once there, garlic_panel_set_gl and
+ * garlic_panel_set_gl_codes uploads are coded into the 16-bit table as well, and the panel turns CONTINUOUS (its codes
+ * expanded on the device) when the merged table would pass 65,536 values.  A panel that has never seen
+ * garlic_panel_set_gl_codes16 behaves as it always has: a garlic_panel_set_gl / garlic_panel_set_gl_codes upload that
+ * takes the table past 256 values turns it CONTINUOUS directly.  A continuous panel stays continuous.
  * (Dictionary codes: the terms are expanded into a matrix of 8 bytes per genotype when the device has room for it, whole
  * or -- garlic_panel_set_tgls_term_budget -- slab by slab; with neither the chain looks them up.)
  * When the device cannot hold values and terms side by side the values are converted in place at the
@@ -149,16 +158,28 @@ int garlic_panel_set_gl(garlic_panel *panel, const double *gl, int64_t ld, int64
 /* The same likelihoods already dictionary-coded, as a reader that converts GQ / PL integers produces
  * them anyway: codes[(l - locus_begin) * ld + i] indexes values[0 .. nvalues), nvalues <= 256, the
  * error probabilities as readTGLSData converts them.  One byte per genotype on the host and over
- * PCIe instead of eight.  Every call may bring its own table; a panel whose tables add up to more than
- * 256 distinct values keeps the values themselves from then on (see garlic_panel_set_gl). */
+ * PCIe instead of eight.  Every call may bring its own table; a one-byte panel whose tables add up to more than
+ * 256 distinct values keeps the values themselves from then on, a panel of 16-bit codes merges them into its table
+ * (see garlic_panel_set_gl). */
 int garlic_panel_set_gl_codes(garlic_panel *panel, const uint8_t *codes, int64_t ld, int64_t locus_begin,
                               int64_t locus_count, const double *values, int32_t nvalues, int32_t where);
 
-/* How the panel holds its likelihoods: 0 none yet, GARLIC_TGLS_DICTIONARY, GARLIC_TGLS_CONTINUOUS.
- * *terms_by (may be NULL): who computed the current TGLS term matrix -- 0 nothing computed yet or
- * tabulated from the dictionary, 1 the device (log10 verified against the host), 2 the host. */
+/* The same with 16-bit codes: codes[(l - locus_begin) * ld + i] indexes values[0 .. nvalues), nvalues <= 65536 (a code
+ * past the table counts as code 0).  Addressing and chunking as garlic_panel_set_gl_codes; every call may bring its own
+ * table, the tables are merged by bit pattern in first-seen order.  The panel becomes (or stays) GARLIC_TGLS_DICTIONARY16:
+ * 2 bytes per genotype on the host, over PCIe and on the device.  The codes are never overwritten -- terms, raw or scaled
+ * by (M, mu), are rebuilt from them, so no change of genotypes, frequencies, map or weighting ever asks for the
+ * likelihoods again -- and the panel honours garlic_panel_set_tgls_term_budget (below).  When the merged table would pass
+ * 65,536 values the panel turns GARLIC_TGLS_CONTINUOUS.  On a continuous panel the call stores the values. */
+int garlic_panel_set_gl_codes16(garlic_panel *panel, const uint16_t *codes, int64_t ld, int64_t locus_begin,
+                                int64_t locus_count, const double *values, int32_t nvalues, int32_t where);
+
+/* How the panel holds its likelihoods: 0 none yet, GARLIC_TGLS_DICTIONARY, GARLIC_TGLS_CONTINUOUS, GARLIC_TGLS_DICTIONARY16.
+ * *terms_by (may be NULL): who computed the current TGLS term matrix -- 0 nothing computed yet (or the terms come slab
+ * by slab) or tabulated from the one-byte dictionary, 1 the device (log10 verified against the host), 2 the host. */
 #define GARLIC_TGLS_DICTIONARY 1
 #define GARLIC_TGLS_CONTINUOUS 2
+#define GARLIC_TGLS_DICTIONARY16 3
 int garlic_panel_tgls_mode(garlic_panel *panel, int32_t *mode, int32_t *terms_by);
 
 /* Unweighted scores from dictionary-coded likelihoods run in two passes: the codes are expanded once into the TGLS term
@@ -187,6 +208,14 @@ int garlic_panel_tgls_mode(garlic_panel *panel, int32_t *mode, int32_t *terms_by
  * is built once and reused: a caller with room for it keeps budget 0.  May be changed between calls in both directions;
  * what the new bound does not allow -- a whole matrix, raw or scaled, from before -- is freed at once or by the next
  * use_gl call.  Panels that hold continuous likelihoods keep 8 bytes per genotype as their data and ignore the budget.
+ * Panels of 16-bit codes (GARLIC_TGLS_DICTIONARY16) honour it as one-byte panels do -- whole matrix, slabs or -1, the same
+ * calls slab by slab with the same doubles, bits and segments -- with one difference: they have no look-up kernels (a per-SNP
+ * table of 65,536 x 4 terms is out of the question).  Where a one-byte panel would look its terms up they instead: under
+ * budget 0 without room for the whole matrix, go on as under -1; for the shapes listed next as not covered by slabs (and the
+ * unweighted counterparts: an ind_begin that is no multiple of 64, GARLIC_TGLS_NO_RING, a window that sums to exactly
+ * -9999.0), use the whole matrix where the budget admits it and otherwise return GARLIC_ERR_NOMEM with a message that says so.
+ * Their chain kind (garlic_panel_chain_kind) is decided before any term exists, from log10 of the smallest table value
+ * minus 1e-6 as the most negative term: 0 only when W times that bound stays above -9990.
  * Weighted shapes that are not covered by slabs: a slab launch starts at a block of the matrix, so a weighted call whose
  * ind_begin is not a multiple of 64 (the ring, strip, stream and tile forms alike), and every weighted call that keeps
  * the generic kernel (GARLIC_WLOD_GENERIC, GARLIC_WLOD_SMALL_GENERIC below 16, winsize + 64 > 4160) looks its terms up

@@ -31,6 +31,11 @@ both orders, and on the same data one thread of std::sort and numpy's sort on th
 panel -- host clock around the synchronous call and the ordered-sum kernel by the library's HIP events, median and spread
 of --steps calls -- with the form the call took where the library reports it; and the phase upload from host memory both
 ways, bytes and milliseconds: one byte per genotype (garlic_panel_set_phase) and bit rows (garlic_panel_set_phase_bits).
+--modes tgls_dict16: GL-typed likelihoods with about 10,000 distinct values (three printed decimals after the clamp) on one
+resident panel: through garlic_panel_set_gl_codes16 where the library has it (2 B per genotype), else through garlic_panel_set_gl
+(continuous, 8 B per genotype: --tree for the parent commit).  The first TGLS score call (term pass + chain), warm calls (chain
+alone), their difference as the term pass, the same after a change of frequencies (no re-upload with codes), and the device
+memory in use (profiles/tgls_dict16_ab.txt).
 --tree for the parent commit; GARLIC_LD_PAIR_NO_MFMA=1 for this tree's AND + popcount form (profiles/ld_phased_mfma_ab.txt).
 """
 import argparse
@@ -121,6 +126,83 @@ def wlod_feed_leg(args, tgls=False):
                     line["roofline"] = {"bound": "hbm", "achieved": a, "peak": 8000.0, "unit": "GB/s", "frac": a / 8000.0,
                                         "algorithmic_bytes_per_window": per_win}
                 print(json.dumps(line), flush=True)
+
+
+def tgls_dict16_leg(args):
+    """Wall clock around the synchronous garlic_lod_windows(use_gl, device output) call: the first call after an upload or a
+    change of frequencies builds the terms and runs the chain, the following ones run the chain on resident terms (whole
+    matrix) or build slabs again (--term-budget-gb); term_pass_ms is the median of the calls after a change of frequencies
+    minus the median of the warm calls (under a budget every call builds its slabs, so it is near 0 there)."""
+    import time
+    import torch
+    from garlic_amd import abi, synth
+
+    torch.cuda.set_device(0)
+    dev = torch.device("cuda", 0)
+    nloci, nind, W = args.snps, args.inds, args.winsize
+    error, max_gap = 0.001, 200000
+    spec = synth.PanelSpec(nloci, seed=20260105, max_gap=max_gap)
+    ctx = abi.Context(0)
+    panel = abi.Panel(ctx, spec.chr_nloci, nind)
+    panel.set_map(spec.pos, spec.centro_start, spec.centro_end, gpos=spec.gpos)
+    panel.set_freq(spec.freq)
+    # GL column x = -k / 1000, k in [0, 10000): value 1 - 10^x, 0 -> 1e-16 (garlic-data.cpp:1557-1576)
+    table = 1.0 - np.power(10.0, -np.arange(10000) / 1000.0)
+    table[table <= 0] = 1e-16
+    d_table = torch.from_numpy(table).to(dev)
+    codes16 = hasattr(panel, "set_gl_codes16")
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(7)
+    t0 = time.perf_counter()
+    for l0, g in synth.genotype_chunks(spec, nind, dev):
+        k = torch.randint(0, 10000, g.shape, generator=gen, device=dev)
+        torch.cuda.synchronize()
+        panel.set_genotypes_device(g.data_ptr(), g.shape[1], l0, g.shape[0])
+        if codes16:
+            panel.set_gl_codes16(k.to(torch.int32).cpu().numpy().astype(np.uint16), table, locus_begin=l0)
+        else:
+            gl = d_table[k]
+            torch.cuda.synchronize()
+            panel.set_gl_device(gl.data_ptr(), gl.shape[1], l0, gl.shape[0])
+            del gl
+        del k
+    del g
+    upload_s = time.perf_counter() - t0
+    base, pitch, total = panel.out_layout(32, nind)
+    out = torch.empty(total, dtype=torch.float64, device=dev)
+
+    def call():
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        panel.lod_windows_device(out.data_ptr(), W, error, max_gap, use_gl=True)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t) * 1e3
+
+    if args.term_budget_gb:
+        panel.set_tgls_term_budget(-1 if args.term_budget_gb < 0 else int(args.term_budget_gb * 1e9))
+    # the very first call also carries the log10 probe, the table upload and the allocations: reported on its own
+    first, warm, rebuild, reupload = call(), [], [], False
+    for _ in range(args.steps):
+        warm.append(call())
+    try:
+        for k in range(args.steps):          # new frequencies: the terms are built again
+            panel.set_freq(np.clip(spec.freq * (1.0 + 1e-3 * (k + 1)), 0.0, 1.0))
+            rebuild.append(call())
+    except abi.GarlicError as e:
+        reupload = str(e)
+    free_b, total_b = torch.cuda.mem_get_info()
+    line = {"mode": "tgls_dict16", "snps": nloci, "inds": nind, "winsize": W, "door": "set_gl_codes16" if codes16 else "set_gl",
+            "tgls_mode": panel.tgls_mode()[0], "terms_by": panel.tgls_mode()[1], "upload_s": upload_s,
+            "term_budget_gb": args.term_budget_gb,
+            "first_call_ms": first, "rebuild_call_ms_median": float(np.median(rebuild)) if rebuild else None,
+            "warm_call_ms_median": float(np.median(warm)), "warm_call_ms_min": min(warm), "warm_call_ms_max": max(warm),
+            "term_pass_ms": float(np.median(rebuild)) - float(np.median(warm)) if rebuild else None, "chain_kernel_ms": panel.stats()["chain_kernel_ms"],
+            "needs_reupload_after_set_freq": reupload, "device_memory_in_use_bytes": int(total_b - free_b),
+            "likelihood_bytes": nloci * nind * (2 if codes16 else 8), "terms": nloci * nind,
+            "checksum": float(out[base[0]: base[0] + nloci].nan_to_num(0.0, 0.0, 0.0).sum().item())}
+    if hasattr(panel, "tgls_terms_info"):
+        line["terms_info"] = panel.tgls_terms_info()
+    print(json.dumps(line), flush=True)
 
 
 def feed_sort_leg(args):
@@ -505,6 +587,7 @@ def main():
     ap.add_argument("--feed-steps", default="", help="wlod_feed / tgls_feed: thinning steps (default: the window size)")
     ap.add_argument("--gl-kind", default="codes", choices=["codes", "continuous"], help="tgls_feed: the likelihoods' form")
     ap.add_argument("--term-budgets-gb", default="8,12,32", help="tgls_slabs: garlic_panel_set_tgls_term_budget values to time")
+    ap.add_argument("--term-budget-gb", type=float, default=0.0, help="tgls_dict16: garlic_panel_set_tgls_term_budget (GB; < 0: -1)")
     ap.add_argument("--cutoff", type=float, default=2.5, help="tgls_slabs: the LOD cutoff of the segments call")
     ap.add_argument("--kde-inds", type=int, default=20, help="feed_sort: individuals of the subsampled feed (--kde-subsample)")
     ap.add_argument("--tree", default="", help="take garlic_amd from this checkout instead of the one the tool is in")
@@ -521,6 +604,8 @@ def main():
         return feed_sort_leg(args)
     if args.modes == "ld_phased":
         return ld_phased_leg(args)
+    if args.modes == "tgls_dict16":
+        return tgls_dict16_leg(args)
     if args.modes in ("wlod_feed", "tgls_feed"):
         return wlod_feed_leg(args, tgls=args.modes == "tgls_feed")
 
