@@ -983,6 +983,7 @@ int ensure_dfreq(garlic_panel *p)
 }
 
 void release_tgls_slabs(garlic_panel *p);
+void dict_clear(garlic_panel *p);     // the likelihood dictionary, emptied (with the other uploads' shared steps, below)
 
 // ---- 16-bit dictionary.  The value table on the device (its unused tail 0.0)
 int ensure_values16(garlic_panel *p)
@@ -1068,12 +1069,9 @@ int switch_to_continuous(garlic_panel *p)
     p->d_codes.release();
     p->d_codes16.release();
     p->d_values16.release();
-    p->gl_wide = p->values16_valid = false;
+    p->gl_wide = false;
     p->d_tabgl.release();
-    p->gl_code.clear();
-    p->gl_values.clear();
-    p->wide_bound_known = false;
-    p->tabgl_valid = false;
+    dict_clear(p);
     p->gl_cont = true;
     p->gl_vals_dropped = false;
     p->glterms_valid = false;
@@ -1095,6 +1093,174 @@ int restart_continuous_upload(garlic_panel *p)
     p->glterms_valid = false;
     p->gl_cover_required = true;
     p->gl_cover.assign((size_t)p->nloci, 0);
+    return GARLIC_OK;
+}
+
+// ---- uploads (the garlic_panel_set_* doors): what they share
+int check_loci(const garlic_panel *p, int64_t locus_begin, int64_t locus_count)
+{
+    if (locus_begin < 0 || locus_count < 1 || locus_begin + locus_count > p->nloci)
+        return fail(GARLIC_ERR_INVALID, "locus range [%lld,+%lld) outside panel of %lld loci",
+                    (long long)locus_begin, (long long)locus_count, (long long)p->nloci);
+    return GARLIC_OK;
+}
+
+// rows of one element per individual
+int check_rows(const garlic_panel *p, int64_t ld, int64_t locus_begin, int64_t locus_count)
+{
+    if (ld < p->nind) return fail(GARLIC_ERR_INVALID, "ld %lld < nind %d", (long long)ld, p->nind);
+    return check_loci(p, locus_begin, locus_count);
+}
+
+int upload_fail(const char *door, hipError_t e) { return fail(GARLIC_ERR_HIP, "%s: %s", door, hipGetErrorString(e)); }
+
+// what the body of a slab (and encode_until_known) may answer besides GARLIC_OK and an error code
+constexpr int SLAB_DRAINED = -1;      // done, and the stream is idle: the body synchronised after its last look at the rows
+constexpr int DICT_FULL = -2;         // a value of the slab found no room in the dictionary: the slab's codes are void
+
+// The caller's rows, `pitch` bytes each, a slab at a time.  Host rows travel through `stage`, at most 256 MB and at least 16 rows
+// of them; device rows are one slab, read where they are.  body(device rows, first row, number of rows) enqueues the slab's
+// work; the stream is synchronised once behind every slab, because the staging buffer is used again (and the caller's rows are
+// free when the call returns).  A HIP failure is reported under the door's name.
+template <class T, class Body>
+int for_each_upload_slab(hipStream_t s, const char *door, const void *rows, int64_t pitch, int64_t locus_count, int32_t where,
+                         DevBuf<T> &stage, Body body)
+{
+    const bool host = where == GARLIC_HOST;
+    const int64_t slab_rows = host ? std::max<int64_t>(16, ((int64_t)256 << 20) / pitch) : locus_count;
+    for (int64_t at = 0; at < locus_count; at += slab_rows) {
+        const int64_t n = std::min(slab_rows, locus_count - at);
+        const void *src = (const uint8_t *)rows + at * pitch;
+        if (host) {
+            if (int rc = stage.reserve((size_t)(n * pitch) / sizeof(T))) return rc;
+            hipError_t e = hipMemcpyAsync(stage.p, src, (size_t)(n * pitch), hipMemcpyHostToDevice, s);
+            if (e != hipSuccess) return upload_fail(door, e);
+            src = stage.p;
+        }
+        const int rc = body(src, at, n);
+        if (rc == SLAB_DRAINED) continue;
+        if (rc) return rc;
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) return upload_fail(door, e);
+    }
+    return GARLIC_OK;
+}
+
+// ---- the likelihood dictionary (gl_values / gl_code): written here and nowhere else
+uint64_t value_bits(double v)
+{
+    uint64_t bits;
+    memcpy(&bits, &v, sizeof bits);
+    return bits;
+}
+
+// The code of a value, a new one if it has none: DICT_FULL when that would be value number cap + 1.  Neither form of the panel
+// reads the other's table flag (ensure_gl_table runs on one-byte panels only, ensure_values16 on 16-bit ones only, and
+// switch_to_wide clears both), so both go.
+int dict_add(garlic_panel *p, uint64_t bits, int cap)
+{
+    auto it = p->gl_code.find(bits);
+    if (it != p->gl_code.end()) return it->second;
+    const int code = (int)p->gl_values.size();
+    if (code >= cap) return DICT_FULL;
+    double v;
+    memcpy(&v, &bits, sizeof v);
+    p->gl_code.emplace(bits, code);
+    p->gl_values.push_back(v);
+    p->wide_bound_known = false;
+    p->tabgl_valid = p->values16_valid = false;
+    return code;
+}
+
+void dict_clear(garlic_panel *p)
+{
+    p->gl_code.clear();
+    p->gl_values.clear();
+    p->wide_bound_known = false;
+    p->tabgl_valid = p->values16_valid = false;
+}
+
+// device room for a dictionary of cap values, sorted by bit pattern, and for the values that come back unknown
+constexpr int UNK_CAP = 8192;
+struct EncodeScratch {
+    DevBuf<uint64_t> bits, unk;
+    DevBuf<uint8_t> codes;               // cap codes of one or two bytes
+    DevBuf<int32_t> nunk;
+    std::vector<uint64_t> host_unk;
+    int reserve(int cap, size_t code_bytes)
+    {
+        int rc;
+        if ((rc = bits.reserve((size_t)cap)) || (rc = codes.reserve((size_t)cap * code_bytes)) || (rc = unk.reserve(UNK_CAP)) ||
+            (rc = nunk.reserve(1)))
+            return rc;
+        host_unk.resize(UNK_CAP);
+        return GARLIC_OK;
+    }
+};
+
+// A slab of values is coded on the device against the dictionary so far; the values it does not know come back (up to UNK_CAP a
+// round), join the dictionary, and the slab is coded again, until none is left: SLAB_DRAINED (every round ends synchronised:
+// the counter is read).  launch(codes by sorted position, number of values) starts the door's encode kernel on sc.bits / sc.unk /
+// sc.nunk.  (A hash look-up per genotype on the host took minutes at 1e10 genotypes.)
+template <class Code, class Launch>
+int encode_until_known(garlic_panel *p, const char *door, int cap, EncodeScratch &sc, Launch launch)
+{
+    hipStream_t s = p->ctx->stream;
+    for (;;) {
+        std::vector<std::pair<uint64_t, Code>> dict;
+        for (auto &kv : p->gl_code) dict.emplace_back(kv.first, (Code)kv.second);
+        std::sort(dict.begin(), dict.end());
+        std::vector<uint64_t> hb(dict.size());
+        std::vector<Code> hc(dict.size());
+        for (size_t k = 0; k < dict.size(); k++) { hb[k] = dict[k].first; hc[k] = dict[k].second; }
+        hipError_t e = hipSuccess;
+        if (!dict.empty()) {
+            e = hipMemcpyAsync(sc.bits.p, hb.data(), sizeof(uint64_t) * hb.size(), hipMemcpyHostToDevice, s);
+            if (e == hipSuccess) e = hipMemcpyAsync(sc.codes.p, hc.data(), sizeof(Code) * hc.size(), hipMemcpyHostToDevice, s);
+        }
+        if (e == hipSuccess) e = hipMemsetAsync(sc.nunk.p, 0, sizeof(int32_t), s);
+        if (e != hipSuccess) return upload_fail(door, e);
+        launch((const Code *)sc.codes.p, (int)dict.size());
+        int32_t nunk = 0;
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(&nunk, sc.nunk.p, sizeof nunk, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);          // also: hb / hc are free again
+        if (e != hipSuccess) return upload_fail(door, e);
+        if (nunk == 0) return SLAB_DRAINED;
+        const int got = std::min<int32_t>(nunk, UNK_CAP);
+        e = hipMemcpy(sc.host_unk.data(), sc.unk.p, sizeof(uint64_t) * got, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return upload_fail(door, e);
+        for (int k = 0; k < got; k++)
+            if (dict_add(p, sc.host_unk[k], cap) == DICT_FULL) return DICT_FULL;
+    }
+}
+
+// what every likelihood door does first ...
+int begin_gl_upload(garlic_panel *p)
+{
+    int rc;
+    if ((rc = set_device(p->ctx)) || (rc = restart_continuous_upload(p))) return rc;
+    if (!p->gl_cont && getenv("GARLIC_TGLS_CONTINUOUS") && (rc = switch_to_continuous(p))) return rc;
+    return GARLIC_OK;
+}
+
+// ... and last
+int end_gl_upload(garlic_panel *p, int64_t locus_begin, int64_t locus_count)
+{
+    if (p->gl_cont && !p->gl_cover.empty()) memset(p->gl_cover.data() + locus_begin, 1, (size_t)locus_count);
+    p->have_gl = true;
+    p->glterms_valid = false;
+    return GARLIC_OK;
+}
+
+// the one-byte code matrix of a panel that keeps such codes, all zero when it is new
+int ensure_byte_codes(garlic_panel *p)
+{
+    if (p->gl_cont || p->gl_wide || p->d_codes.p) return GARLIC_OK;
+    const size_t n = (size_t)((GOFF + p->nloci + GPAD_BACK) * p->nind_pad);
+    if (int rc = p->d_codes.reserve(n)) return rc;
+    HIP_TRY(hipMemsetAsync(p->d_codes.p, 0, n, p->ctx->stream));
     return GARLIC_OK;
 }
 
@@ -2555,40 +2721,23 @@ int garlic_panel_set_genotypes(garlic_panel *p, const int16_t *geno, int64_t ld,
                                int64_t locus_count, int32_t where)
 {
     if (!p || !geno) return fail(GARLIC_ERR_INVALID, "panel and geno are required");
-    if (ld < p->nind) return fail(GARLIC_ERR_INVALID, "ld %lld < nind %d", (long long)ld, p->nind);
-    if (locus_begin < 0 || locus_count < 1 || locus_begin + locus_count > p->nloci)
-        return fail(GARLIC_ERR_INVALID, "locus range [%lld,+%lld) outside panel of %lld loci",
-                    (long long)locus_begin, (long long)locus_count, (long long)p->nloci);
     int rc;
-    if ((rc = set_device(p->ctx))) return rc;
+    if ((rc = check_rows(p, ld, locus_begin, locus_count)) || (rc = set_device(p->ctx))) return rc;
     hipStream_t s = p->ctx->stream;
-    // host data goes through a bounded staging buffer, a slab of SNP rows at a time
-    const int64_t slab_rows = (where == GARLIC_HOST)
-                                  ? std::max<int64_t>(16, ((int64_t)256 << 20) / (2 * ld))
-                                  : locus_count;
-    for (int64_t done = 0; done < locus_count; done += slab_rows) {
-        const int64_t rows = std::min(slab_rows, locus_count - done);
-        const int64_t l0 = locus_begin + done;
-        const int16_t *src = geno + done * ld;
-        if (where == GARLIC_HOST) {
-            if ((rc = p->d_stage16.reserve((size_t)(rows * ld)))) return rc;
-            HIP_TRY(hipMemcpyAsync(p->d_stage16.p, src, sizeof(int16_t) * rows * ld,
-                                   hipMemcpyHostToDevice, s));
-            src = p->d_stage16.p;
-        }
+    // (the staging buffer stays with the panel until garlic_panel_release_scratch)
+    rc = for_each_upload_slab(s, "set_genotypes", geno, 2 * ld, locus_count, where, p->d_stage16, [&](const void *rows, int64_t at, int64_t n) {
+        const int64_t l0 = locus_begin + at;
         const int64_t w_lo = (GOFF + l0) >> 4;
-        const int64_t w_hi = ((GOFF + l0 + rows - 1) >> 4) + 1;
-        dim3 block(256);
+        const int64_t w_hi = ((GOFF + l0 + n - 1) >> 4) + 1;
         for (int64_t w = w_lo; w < w_hi; w += 65535) {
             const int64_t wn = std::min<int64_t>(65535, w_hi - w);
             dim3 grid((unsigned)((p->nind_pad + 255) / 256), (unsigned)wn);
-            hipLaunchKernelGGL(pack_genotypes_kernel, grid, block, 0, s, src, ld, l0, rows, p->nind,
+            hipLaunchKernelGGL(pack_genotypes_kernel, grid, dim3(256), 0, s, (const int16_t *)rows, ld, l0, n, p->nind,
                                p->nind_pad, p->nwordrows, p->d_packed.p, w, w + wn);
         }
-        if (where == GARLIC_HOST) HIP_TRY(hipStreamSynchronize(s)); // staging buffer is reused
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(s));
+        return GARLIC_OK;
+    });
+    if (rc) return rc;
     p->have_geno = true;
     p->geno_epoch++;
     p->glterms_valid = false;
@@ -2602,38 +2751,23 @@ int garlic_panel_set_genotypes_2bit(garlic_panel *p, const uint8_t *rows, int64_
     if (ind_offset < 0 || row_bytes < (ind_offset + p->nind + 3) / 4)
         return fail(GARLIC_ERR_INVALID, "row_bytes %lld too small for individuals [%lld,+%d)", (long long)row_bytes,
                     (long long)ind_offset, p->nind);
-    if (locus_begin < 0 || locus_count < 1 || locus_begin + locus_count > p->nloci)
-        return fail(GARLIC_ERR_INVALID, "locus range [%lld,+%lld) outside panel of %lld loci",
-                    (long long)locus_begin, (long long)locus_count, (long long)p->nloci);
     int rc;
-    if ((rc = set_device(p->ctx))) return rc;
+    if ((rc = check_loci(p, locus_begin, locus_count)) || (rc = set_device(p->ctx))) return rc;
     hipStream_t s = p->ctx->stream;
     DevBuf<uint8_t> stage;
-    const int64_t slab_rows = (where == GARLIC_HOST) ? std::max<int64_t>(16, ((int64_t)256 << 20) / row_bytes)
-                                                     : locus_count;
-    for (int64_t done = 0; done < locus_count; done += slab_rows) {
-        const int64_t nrows = std::min(slab_rows, locus_count - done);
-        const int64_t l0 = locus_begin + done;
-        const uint8_t *src = rows + done * row_bytes;
-        hipError_t e = hipSuccess;
-        if (where == GARLIC_HOST) {
-            if ((rc = stage.reserve((size_t)(nrows * row_bytes)))) { stage.release(); return rc; }
-            e = hipMemcpyAsync(stage.p, src, (size_t)(nrows * row_bytes), hipMemcpyHostToDevice, s);
-            src = stage.p;
-        }
+    rc = for_each_upload_slab(s, "set_genotypes_2bit", rows, row_bytes, locus_count, where, stage, [&](const void *src, int64_t at, int64_t n) {
+        const int64_t l0 = locus_begin + at;
         const int64_t w_lo = (GOFF + l0) >> 4;
-        const int64_t w_hi = ((GOFF + l0 + nrows - 1) >> 4) + 1;
-        for (int64_t w = w_lo; e == hipSuccess && w < w_hi; w += 65535) {
+        const int64_t w_hi = ((GOFF + l0 + n - 1) >> 4) + 1;
+        for (int64_t w = w_lo; w < w_hi; w += 65535) {
             const int64_t wn = std::min<int64_t>(65535, w_hi - w);
             dim3 grid((unsigned)((p->nind_pad + 255) / 256), (unsigned)wn);
-            hipLaunchKernelGGL(pack_genotypes_2bit_kernel, grid, dim3(256), 0, s, src, row_bytes, ind_offset, l0, nrows,
+            hipLaunchKernelGGL(pack_genotypes_2bit_kernel, grid, dim3(256), 0, s, (const uint8_t *)src, row_bytes, ind_offset, l0, n,
                                p->nind, p->nind_pad, p->nwordrows, p->d_packed.p, w, w + wn);
-            e = hipGetLastError();
         }
-        if (e == hipSuccess) e = hipStreamSynchronize(s);                      // staging buffer is reused
-        if (e != hipSuccess) { stage.release(); return fail(GARLIC_ERR_HIP, "set_genotypes_2bit: %s", hipGetErrorString(e)); }
-    }
-    stage.release();
+        return GARLIC_OK;
+    });
+    if (rc) return rc;
     p->have_geno = true;
     p->geno_epoch++;
     p->glterms_valid = false;
@@ -2647,240 +2781,78 @@ static int merge_wide_table(garlic_panel *p, const double *values, int32_t nvalu
 {
     remap.assign((size_t)nvalues, 0);
     size_t fresh = 0;
-    for (int k = 0; k < nvalues; k++) {
-        uint64_t bits;
-        memcpy(&bits, &values[k], sizeof bits);
-        fresh += p->gl_code.count(bits) == 0;      // (a value twice in the caller's table counts twice: an upper bound is enough)
-    }
+    for (int k = 0; k < nvalues; k++)
+        fresh += p->gl_code.count(value_bits(values[k])) == 0;      // (a value twice in the caller's table counts twice: an upper bound is enough)
     if (p->gl_values.size() + fresh > (size_t)GL_WIDE_MAX) {
         std::unordered_map<uint64_t, int> probe = p->gl_code;      // exact count before giving the codes up
-        for (int k = 0; k < nvalues; k++) {
-            uint64_t bits;
-            memcpy(&bits, &values[k], sizeof bits);
-            probe.emplace(bits, 0);
-        }
+        for (int k = 0; k < nvalues; k++) probe.emplace(value_bits(values[k]), 0);
         if (probe.size() > (size_t)GL_WIDE_MAX) return switch_to_continuous(p);
     }
-    for (int k = 0; k < nvalues; k++) {
-        uint64_t bits;
-        memcpy(&bits, &values[k], sizeof bits);
-        auto it = p->gl_code.find(bits);
-        if (it == p->gl_code.end()) {
-            it = p->gl_code.emplace(bits, (int)p->gl_values.size()).first;
-            p->gl_values.push_back(values[k]);
-            p->wide_bound_known = false;
-            p->values16_valid = false;
-        }
-        remap[(size_t)k] = (uint16_t)it->second;
-    }
+    for (int k = 0; k < nvalues; k++) remap[(size_t)k] = (uint16_t)dict_add(p, value_bits(values[k]), GL_WIDE_MAX);      // (there is room: counted)
     return GARLIC_OK;
 }
 
-// caller rows of one-byte (codes8) or 16-bit (codes16) codes, translated by remap into the panel's codes
-static int upload_wide_codes(garlic_panel *p, const uint8_t *codes8, const uint16_t *codes16, int64_t ld, int64_t locus_begin,
+// caller rows of codes of code_bytes (1 or 2) each, translated by remap into the panel's codes
+static int upload_wide_codes(garlic_panel *p, const void *codes, size_t code_bytes, int64_t ld, int64_t locus_begin,
                              int64_t locus_count, const std::vector<uint16_t> &remap, int32_t where)
 {
     hipStream_t s = p->ctx->stream;
     const int64_t rows_total = GOFF + p->nloci + GPAD_BACK;
-    const size_t esz = codes8 ? 1 : 2;
-    const uint8_t *base = codes8 ? codes8 : (const uint8_t *)codes16;
     DevBuf<uint8_t> stage;
     DevBuf<uint16_t> d_remap;
     int rc;
     if ((rc = d_remap.reserve(remap.size()))) return rc;
     hipError_t e = hipMemcpy(d_remap.p, remap.data(), sizeof(uint16_t) * remap.size(), hipMemcpyHostToDevice);
-    const int64_t slab_rows = (where == GARLIC_HOST) ? std::max<int64_t>(16, ((int64_t)256 << 20) / (int64_t)(esz * ld)) : locus_count;
-    for (int64_t at = 0; e == hipSuccess && at < locus_count; at += slab_rows) {
-        const int64_t nrows = std::min(slab_rows, locus_count - at);
-        const uint8_t *src = base + (size_t)(at * ld) * esz;
-        if (where == GARLIC_HOST) {
-            if ((rc = stage.reserve((size_t)(nrows * ld) * esz))) return rc;
-            e = hipMemcpyAsync(stage.p, src, (size_t)(nrows * ld) * esz, hipMemcpyHostToDevice, s);
-            src = stage.p;
-        }
-        if (e != hipSuccess) break;
-        if (codes8)
-            hipLaunchKernelGGL(gl_recode8to16_kernel, dim3(2048), dim3(256), 0, s, src, ld, locus_begin + at, nrows, p->nind, d_remap.p,
-                               rows_total, p->d_codes16.p);
+    if (e != hipSuccess) return upload_fail("set_gl_codes16", e);
+    rc = for_each_upload_slab(s, "set_gl_codes16", codes, (int64_t)code_bytes * ld, locus_count, where, stage, [&](const void *rows, int64_t at, int64_t n) {
+        if (code_bytes == 1)
+            hipLaunchKernelGGL(gl_recode8to16_kernel, dim3(2048), dim3(256), 0, s, (const uint8_t *)rows, ld, locus_begin + at, n, p->nind,
+                               d_remap.p, rows_total, p->d_codes16.p);
         else
-            hipLaunchKernelGGL(gl_recode16_kernel, dim3(2048), dim3(256), 0, s, (const uint16_t *)src, ld, locus_begin + at, nrows, p->nind,
+            hipLaunchKernelGGL(gl_recode16_kernel, dim3(2048), dim3(256), 0, s, (const uint16_t *)rows, ld, locus_begin + at, n, p->nind,
                                d_remap.p, (int32_t)remap.size(), rows_total, p->d_codes16.p);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(s);                      // staging slab free again
-    }
-    if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "set_gl_codes16: %s", hipGetErrorString(e));
-    p->have_gl = true;
-    p->glterms_valid = false;
-    return GARLIC_OK;
-}
-
-// garlic_panel_set_gl on a panel of 16-bit codes: coded on the device against the table so far, unknown values come back and
-// join it (the loop of the one-byte path with a table in global memory); past 65,536 values the panel turns continuous and the
-// call starts over on that path.
-static int set_gl_wide(garlic_panel *p, const double *gl, int64_t ld, int64_t locus_begin, int64_t locus_count, int32_t where)
-{
-    hipStream_t s = p->ctx->stream;
-    const int64_t rows_total = GOFF + p->nloci + GPAD_BACK;
-    constexpr int UNK_CAP = 8192;
-    DevBuf<double> stage;
-    DevBuf<uint64_t> d_bits, d_unk;
-    DevBuf<uint16_t> d_dcode;
-    DevBuf<int32_t> d_nunk;
-    int rc;
-    if ((rc = d_bits.reserve(GL_WIDE_MAX)) || (rc = d_dcode.reserve(GL_WIDE_MAX)) || (rc = d_unk.reserve(UNK_CAP)) || (rc = d_nunk.reserve(1)))
-        return rc;
-    const int64_t slab_rows = (where == GARLIC_HOST) ? std::max<int64_t>(16, ((int64_t)256 << 20) / (8 * ld)) : locus_count;
-    std::vector<uint64_t> unk(UNK_CAP);
-    for (int64_t at = 0; at < locus_count; at += slab_rows) {
-        const int64_t nrows = std::min(slab_rows, locus_count - at);
-        const double *src = gl + at * ld;
-        hipError_t e = hipSuccess;
-        if (where == GARLIC_HOST) {
-            if ((rc = stage.reserve((size_t)(nrows * ld)))) return rc;
-            e = hipMemcpyAsync(stage.p, src, sizeof(double) * nrows * ld, hipMemcpyHostToDevice, s);
-            src = stage.p;
-        }
-        while (e == hipSuccess) {   // until the slab holds no value outside the dictionary
-            std::vector<std::pair<uint64_t, uint16_t>> dict;
-            for (auto &kv : p->gl_code) dict.emplace_back(kv.first, (uint16_t)kv.second);
-            std::sort(dict.begin(), dict.end());
-            std::vector<uint64_t> hb(dict.size());
-            std::vector<uint16_t> hc(dict.size());
-            for (size_t k = 0; k < dict.size(); k++) { hb[k] = dict[k].first; hc[k] = dict[k].second; }
-            if (!dict.empty()) {
-                e = hipMemcpyAsync(d_bits.p, hb.data(), sizeof(uint64_t) * hb.size(), hipMemcpyHostToDevice, s);
-                if (e == hipSuccess) e = hipMemcpyAsync(d_dcode.p, hc.data(), sizeof(uint16_t) * hc.size(), hipMemcpyHostToDevice, s);
-            }
-            if (e == hipSuccess) e = hipMemsetAsync(d_nunk.p, 0, sizeof(int32_t), s);
-            if (e != hipSuccess) break;
-            hipLaunchKernelGGL(gl_encode16_kernel, dim3(2048), dim3(256), 0, s, src, ld, locus_begin + at, nrows, p->nind, d_bits.p, d_dcode.p,
-                               (int)dict.size(), rows_total, p->d_codes16.p, d_unk.p, d_nunk.p, UNK_CAP);
-            int32_t nunk = 0;
-            e = hipGetLastError();
-            if (e == hipSuccess) e = hipMemcpyAsync(&nunk, d_nunk.p, sizeof nunk, hipMemcpyDeviceToHost, s);
-            if (e == hipSuccess) e = hipStreamSynchronize(s);
-            if (e != hipSuccess || nunk == 0) break;
-            const int got = std::min<int32_t>(nunk, UNK_CAP);
-            e = hipMemcpy(unk.data(), d_unk.p, sizeof(uint64_t) * got, hipMemcpyDeviceToHost);
-            if (e != hipSuccess) break;
-            for (int k = 0; k < got; k++) {
-                if (p->gl_code.count(unk[k])) continue;
-                if (p->gl_values.size() >= (size_t)GL_WIDE_MAX) {      // continuous after all: decode, and the rest of the call as values
-                    if ((rc = switch_to_continuous(p))) return rc;
-                    return garlic_panel_set_gl(p, gl + at * ld, ld, locus_begin + at, locus_count - at, where);
-                }
-                double v;
-                memcpy(&v, &unk[k], sizeof v);
-                p->gl_code.emplace(unk[k], (int)p->gl_values.size());
-                p->gl_values.push_back(v);
-                p->wide_bound_known = false;
-                p->values16_valid = false;
-            }
-        }
-        if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "set_gl: %s", hipGetErrorString(e));
-    }
-    p->have_gl = true;
-    p->glterms_valid = false;
-    return GARLIC_OK;
+        return GARLIC_OK;
+    });
+    return rc ? rc : end_gl_upload(p, locus_begin, locus_count);
 }
 
 int garlic_panel_set_gl(garlic_panel *p, const double *gl, int64_t ld, int64_t locus_begin,
                         int64_t locus_count, int32_t where)
 {
     if (!p || !gl) return fail(GARLIC_ERR_INVALID, "panel and gl are required");
-    if (ld < p->nind) return fail(GARLIC_ERR_INVALID, "ld %lld < nind %d", (long long)ld, p->nind);
-    if (locus_begin < 0 || locus_count < 1 || locus_begin + locus_count > p->nloci)
-        return fail(GARLIC_ERR_INVALID, "locus range [%lld,+%lld) outside panel of %lld loci",
-                    (long long)locus_begin, (long long)locus_count, (long long)p->nloci);
     int rc;
-    if ((rc = set_device(p->ctx))) return rc;
+    if ((rc = check_rows(p, ld, locus_begin, locus_count)) || (rc = begin_gl_upload(p)) || (rc = ensure_byte_codes(p))) return rc;
     hipStream_t s = p->ctx->stream;
     const int64_t rows_total = GOFF + p->nloci + GPAD_BACK;
-    if ((rc = restart_continuous_upload(p))) return rc;
-    if (!p->gl_cont && getenv("GARLIC_TGLS_CONTINUOUS") && (rc = switch_to_continuous(p))) return rc;
-    if (p->gl_wide) return set_gl_wide(p, gl, ld, locus_begin, locus_count, where);
-    if (!p->gl_cont && !p->d_codes.p) {
-        if ((rc = p->d_codes.reserve((size_t)(rows_total * p->nind_pad)))) return rc;
-        HIP_TRY(hipMemsetAsync(p->d_codes.p, 0, (size_t)(rows_total * p->nind_pad), s));
-    }
     // Few distinct error probabilities (GQ / PL integers) -> one-byte codes: the term table per (SNP,
-    // code, genotype) comes from the host libm and the panel keeps 1 B instead of 8 B per genotype.
-    // Coded on the device against the dictionary so far; values it does not know come back, join the
-    // dictionary and the slab is coded again (a hash look-up per genotype on the host took minutes at
-    // 1e10 genotypes).  When the dictionary is full (256 values: --gl-type GL, continuous inputs) the
-    // panel switches to keeping the values themselves and evaluates lod() on the device.
-    constexpr int UNK_CAP = 8192;
+    // code, genotype) comes from the host libm and the panel keeps 1 B instead of 8 B per genotype.  A
+    // panel of 16-bit codes (garlic_panel_set_gl_codes16) codes the values against its table of up to
+    // 65,536.  Either way a slab is coded on the device (encode_until_known); when the dictionary is full
+    // (--gl-type GL, continuous inputs) the panel switches to keeping the values themselves and evaluates
+    // lod() on the device: what was coded is decoded, this slab and every later one is stored as it is.
+    EncodeScratch sc;
+    if (!p->gl_cont && (rc = sc.reserve(p->gl_wide ? GL_WIDE_MAX : GL_DICT_MAX, p->gl_wide ? 2 : 1))) return rc;
     DevBuf<double> stage;
-    DevBuf<uint64_t> d_bits, d_unk;
-    DevBuf<uint8_t> d_dcode;
-    DevBuf<int32_t> d_nunk;
-    if ((rc = d_bits.reserve(GL_DICT_MAX)) || (rc = d_dcode.reserve(GL_DICT_MAX)) || (rc = d_unk.reserve(UNK_CAP)) ||
-        (rc = d_nunk.reserve(1)))
-        return rc;
-    const int64_t slab_rows = (where == GARLIC_HOST) ? std::max<int64_t>(16, ((int64_t)256 << 20) / (8 * ld)) : locus_count;
-    std::vector<uint64_t> unk(UNK_CAP);
-    for (int64_t at = 0; at < locus_count; at += slab_rows) {
-        const int64_t nrows = std::min(slab_rows, locus_count - at);
-        const double *src = gl + at * ld;
-        hipError_t e = hipSuccess;
-        if (where == GARLIC_HOST) {
-            if ((rc = stage.reserve((size_t)(nrows * ld)))) return rc;
-            e = hipMemcpyAsync(stage.p, src, sizeof(double) * nrows * ld, hipMemcpyHostToDevice, s);
-            src = stage.p;
+    rc = for_each_upload_slab(s, "set_gl", gl, 8 * ld, locus_count, where, stage, [&](const void *rows, int64_t at, int64_t n) {
+        const double *src = (const double *)rows;
+        const int64_t l0 = locus_begin + at;
+        if (!p->gl_cont) {
+            const int coded =
+                p->gl_wide ? encode_until_known<uint16_t>(p, "set_gl", GL_WIDE_MAX, sc, [&](const uint16_t *dcode, int ndict) {
+                    hipLaunchKernelGGL(gl_encode16_kernel, dim3(2048), dim3(256), 0, s, src, ld, l0, n, p->nind, sc.bits.p, dcode, ndict,
+                                       rows_total, p->d_codes16.p, sc.unk.p, sc.nunk.p, UNK_CAP);
+                })
+                           : encode_until_known<uint8_t>(p, "set_gl", GL_DICT_MAX, sc, [&](const uint8_t *dcode, int ndict) {
+                                 hipLaunchKernelGGL(gl_encode_kernel, dim3(2048), dim3(256), 0, s, src, ld, n, p->nind, p->nind_pad, sc.bits.p,
+                                                    dcode, ndict, p->d_codes.p + (GOFF + l0) * p->nind_pad, sc.unk.p, sc.nunk.p, UNK_CAP);
+                             });
+            if (coded != DICT_FULL) return coded;
+            if (int full_rc = switch_to_continuous(p)) return full_rc;
         }
-        while (e == hipSuccess && !p->gl_cont) {   // until the slab holds no value outside the dictionary
-            // dictionary, sorted by bit pattern
-            std::vector<std::pair<uint64_t, uint8_t>> dict;
-            for (auto &kv : p->gl_code) dict.emplace_back(kv.first, (uint8_t)kv.second);
-            std::sort(dict.begin(), dict.end());
-            std::vector<uint64_t> hb(dict.size());
-            std::vector<uint8_t> hc(dict.size());
-            for (size_t k = 0; k < dict.size(); k++) { hb[k] = dict[k].first; hc[k] = dict[k].second; }
-            if (!dict.empty()) {
-                e = hipMemcpyAsync(d_bits.p, hb.data(), sizeof(uint64_t) * hb.size(), hipMemcpyHostToDevice, s);
-                if (e == hipSuccess) e = hipMemcpyAsync(d_dcode.p, hc.data(), hc.size(), hipMemcpyHostToDevice, s);
-            }
-            if (e == hipSuccess) e = hipMemsetAsync(d_nunk.p, 0, sizeof(int32_t), s);
-            if (e != hipSuccess) break;
-            hipLaunchKernelGGL(gl_encode_kernel, dim3(2048), dim3(256), 0, s, src, ld, nrows, p->nind, p->nind_pad, d_bits.p,
-                               d_dcode.p, (int)dict.size(), p->d_codes.p + (GOFF + locus_begin + at) * p->nind_pad,
-                               d_unk.p, d_nunk.p, UNK_CAP);
-            int32_t nunk = 0;
-            e = hipGetLastError();
-            if (e == hipSuccess) e = hipMemcpyAsync(&nunk, d_nunk.p, sizeof nunk, hipMemcpyDeviceToHost, s);
-            if (e == hipSuccess) e = hipStreamSynchronize(s);          // also: hb / hc / the staging slab are free again
-            if (e != hipSuccess || nunk == 0) break;
-            const int got = std::min<int32_t>(nunk, UNK_CAP);
-            e = hipMemcpy(unk.data(), d_unk.p, sizeof(uint64_t) * got, hipMemcpyDeviceToHost);
-            if (e != hipSuccess) break;
-            for (int k = 0; k < got; k++) {
-                if (p->gl_code.count(unk[k])) continue;
-                const int code = (int)p->gl_values.size();
-                if (code >= GL_DICT_MAX) {       // continuous inputs: keep values, not codes
-                    if ((rc = switch_to_continuous(p))) return rc;
-                    break;
-                }
-                double v;
-                memcpy(&v, &unk[k], sizeof v);
-                p->gl_code.emplace(unk[k], code);
-                p->gl_values.push_back(v);
-                p->wide_bound_known = false;
-                p->tabgl_valid = false;
-            }
-        }
-        if (e == hipSuccess && p->gl_cont) {
-            hipLaunchKernelGGL(gl_store_kernel, dim3(2048), dim3(256), 0, s, src, ld, locus_begin + at, nrows, p->nind,
-                               rows_total, p->d_glval.p);
-            e = hipGetLastError();
-            if (e == hipSuccess) e = hipStreamSynchronize(s);          // the staging slab is free again
-        }
-        if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "set_gl: %s", hipGetErrorString(e));
-    }
-    if (p->gl_cont && !p->gl_cover.empty())
-        memset(p->gl_cover.data() + locus_begin, 1, (size_t)locus_count);
-    p->have_gl = true;
-    p->glterms_valid = false;
-    return GARLIC_OK;
+        hipLaunchKernelGGL(gl_store_kernel, dim3(2048), dim3(256), 0, s, src, ld, l0, n, p->nind, rows_total, p->d_glval.p);
+        return GARLIC_OK;
+    });
+    return rc ? rc : end_gl_upload(p, locus_begin, locus_count);
 }
 
 int garlic_panel_set_gl_codes(garlic_panel *p, const uint8_t *codes, int64_t ld, int64_t locus_begin,
@@ -2888,16 +2860,10 @@ int garlic_panel_set_gl_codes(garlic_panel *p, const uint8_t *codes, int64_t ld,
 {
     if (!p || !codes || !values) return fail(GARLIC_ERR_INVALID, "panel, codes and values are required");
     if (nvalues < 1 || nvalues > GL_DICT_MAX) return fail(GARLIC_ERR_INVALID, "nvalues must be 1..256 (got %d)", nvalues);
-    if (ld < p->nind) return fail(GARLIC_ERR_INVALID, "ld %lld < nind %d", (long long)ld, p->nind);
-    if (locus_begin < 0 || locus_count < 1 || locus_begin + locus_count > p->nloci)
-        return fail(GARLIC_ERR_INVALID, "locus range [%lld,+%lld) outside panel of %lld loci",
-                    (long long)locus_begin, (long long)locus_count, (long long)p->nloci);
     int rc;
-    if ((rc = set_device(p->ctx))) return rc;
+    if ((rc = check_rows(p, ld, locus_begin, locus_count)) || (rc = begin_gl_upload(p))) return rc;
     hipStream_t s = p->ctx->stream;
     const int64_t rows_total = GOFF + p->nloci + GPAD_BACK;
-    if ((rc = restart_continuous_upload(p))) return rc;
-    if (!p->gl_cont && getenv("GARLIC_TGLS_CONTINUOUS") && (rc = switch_to_continuous(p))) return rc;
     // the caller's table joins the panel's dictionary; its codes are translated on the device.  A
     // panel whose tables add up to more than 256 values keeps the values themselves from then on.
     if (p->gl_wide) {
@@ -2905,39 +2871,23 @@ int garlic_panel_set_gl_codes(garlic_panel *p, const uint8_t *codes, int64_t ld,
         if ((rc = merge_wide_table(p, values, nvalues, remap16))) return rc;
         if (p->gl_wide) {
             remap16.resize(256, 0);
-            return upload_wide_codes(p, codes, nullptr, ld, locus_begin, locus_count, remap16, where);
+            return upload_wide_codes(p, codes, 1, ld, locus_begin, locus_count, remap16, where);
         }
     }
     uint8_t remap[256] = {0};
     for (int k = 0; k < nvalues && !p->gl_cont; k++) {
-        uint64_t bits;
-        memcpy(&bits, &values[k], sizeof bits);
-        auto it = p->gl_code.find(bits);
-        if (it == p->gl_code.end()) {
-            const int code = (int)p->gl_values.size();
-            if (code >= GL_DICT_MAX) {
-                if (!p->d_codes.p) {   // nothing coded yet: start from an empty value matrix
-                    p->gl_code.clear();
-                    p->gl_values.clear();
-                    p->wide_bound_known = false;
-                }
-                if ((rc = switch_to_continuous(p))) return rc;
-                break;
-            }
-            it = p->gl_code.emplace(bits, code).first;
-            p->gl_values.push_back(values[k]);
-            p->wide_bound_known = false;
-            p->tabgl_valid = false;
+        const int code = dict_add(p, value_bits(values[k]), GL_DICT_MAX);
+        if (code == DICT_FULL) {
+            if (!p->d_codes.p) dict_clear(p);      // nothing coded yet: start from an empty value matrix
+            if ((rc = switch_to_continuous(p))) return rc;
+            break;
         }
-        remap[k] = (uint8_t)it->second;
+        remap[k] = (uint8_t)code;
     }
-    if (!p->gl_cont && !p->d_codes.p) {
-        if ((rc = p->d_codes.reserve((size_t)(rows_total * p->nind_pad)))) return rc;
-        HIP_TRY(hipMemsetAsync(p->d_codes.p, 0, (size_t)(rows_total * p->nind_pad), s));
-    }
+    if ((rc = ensure_byte_codes(p))) return rc;
     DevBuf<uint8_t> stage, d_remap;
     DevBuf<double> d_dict;
-    hipError_t e = hipSuccess;
+    hipError_t e;
     if (p->gl_cont) {
         std::vector<double> dict(GL_DICT_MAX, 0.0);
         std::copy(values, values + nvalues, dict.begin());
@@ -2947,31 +2897,17 @@ int garlic_panel_set_gl_codes(garlic_panel *p, const uint8_t *codes, int64_t ld,
         if ((rc = d_remap.reserve(256))) return rc;
         e = hipMemcpy(d_remap.p, remap, 256, hipMemcpyHostToDevice);
     }
-    const int64_t slab_rows = (where == GARLIC_HOST) ? std::max<int64_t>(16, ((int64_t)256 << 20) / ld) : locus_count;
-    for (int64_t at = 0; e == hipSuccess && at < locus_count; at += slab_rows) {
-        const int64_t nrows = std::min(slab_rows, locus_count - at);
-        const uint8_t *src = codes + at * ld;
-        if (where == GARLIC_HOST) {
-            if ((rc = stage.reserve((size_t)(nrows * ld)))) return rc;
-            e = hipMemcpyAsync(stage.p, src, (size_t)(nrows * ld), hipMemcpyHostToDevice, s);
-            src = stage.p;
-        }
-        if (e != hipSuccess) break;
+    if (e != hipSuccess) return upload_fail("set_gl_codes", e);
+    rc = for_each_upload_slab(s, "set_gl_codes", codes, ld, locus_count, where, stage, [&](const void *rows, int64_t at, int64_t n) {
         if (p->gl_cont)
-            hipLaunchKernelGGL(gl_store_codes_kernel, dim3(2048), dim3(256), 0, s, src, ld, locus_begin + at, nrows, p->nind,
+            hipLaunchKernelGGL(gl_store_codes_kernel, dim3(2048), dim3(256), 0, s, (const uint8_t *)rows, ld, locus_begin + at, n, p->nind,
                                d_dict.p, rows_total, p->d_glval.p);
         else
-            hipLaunchKernelGGL(gl_recode_kernel, dim3(2048), dim3(256), 0, s, src, ld, nrows, p->nind, p->nind_pad, d_remap.p,
+            hipLaunchKernelGGL(gl_recode_kernel, dim3(2048), dim3(256), 0, s, (const uint8_t *)rows, ld, n, p->nind, p->nind_pad, d_remap.p,
                                p->d_codes.p + (GOFF + locus_begin + at) * p->nind_pad);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(s);                      // staging slab free again
-    }
-    if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "set_gl_codes: %s", hipGetErrorString(e));
-    if (p->gl_cont && !p->gl_cover.empty())
-        memset(p->gl_cover.data() + locus_begin, 1, (size_t)locus_count);
-    p->have_gl = true;
-    p->glterms_valid = false;
-    return GARLIC_OK;
+        return GARLIC_OK;
+    });
+    return rc ? rc : end_gl_upload(p, locus_begin, locus_count);
 }
 
 int garlic_panel_set_gl_codes16(garlic_panel *p, const uint16_t *codes, int64_t ld, int64_t locus_begin,
@@ -2979,45 +2915,35 @@ int garlic_panel_set_gl_codes16(garlic_panel *p, const uint16_t *codes, int64_t 
 {
     if (!p || !codes || !values) return fail(GARLIC_ERR_INVALID, "panel, codes and values are required");
     if (nvalues < 1 || nvalues > GL_WIDE_MAX) return fail(GARLIC_ERR_INVALID, "nvalues must be 1..65536 (got %d)", nvalues);
-    if (ld < p->nind) return fail(GARLIC_ERR_INVALID, "ld %lld < nind %d", (long long)ld, p->nind);
-    if (locus_begin < 0 || locus_count < 1 || locus_begin + locus_count > p->nloci)
-        return fail(GARLIC_ERR_INVALID, "locus range [%lld,+%lld) outside panel of %lld loci",
-                    (long long)locus_begin, (long long)locus_count, (long long)p->nloci);
     int rc;
-    if ((rc = set_device(p->ctx))) return rc;
+    if ((rc = check_rows(p, ld, locus_begin, locus_count)) || (rc = begin_gl_upload(p))) return rc;
     hipStream_t s = p->ctx->stream;
     const int64_t rows_total = GOFF + p->nloci + GPAD_BACK;
-    if ((rc = restart_continuous_upload(p))) return rc;
-    if (!p->gl_cont && getenv("GARLIC_TGLS_CONTINUOUS") && (rc = switch_to_continuous(p))) return rc;
     if (!p->gl_cont) {
         std::vector<uint16_t> remap;
         if ((rc = switch_to_wide(p)) || (rc = merge_wide_table(p, values, nvalues, remap))) return rc;
-        if (p->gl_wide) return upload_wide_codes(p, nullptr, codes, ld, locus_begin, locus_count, remap, where);
+        if (p->gl_wide) return upload_wide_codes(p, codes, 2, ld, locus_begin, locus_count, remap, where);
     }
     // a continuous panel: the caller's codes become values straight away
     DevBuf<uint16_t> stage;
     DevBuf<double> d_dict;
     if ((rc = d_dict.reserve((size_t)nvalues))) return rc;
     hipError_t e = hipMemcpy(d_dict.p, values, sizeof(double) * (size_t)nvalues, hipMemcpyHostToDevice);
-    const int64_t slab_rows = (where == GARLIC_HOST) ? std::max<int64_t>(16, ((int64_t)256 << 20) / (2 * ld)) : locus_count;
-    for (int64_t at = 0; e == hipSuccess && at < locus_count; at += slab_rows) {
-        const int64_t nrows = std::min(slab_rows, locus_count - at);
-        const uint16_t *src = codes + at * ld;
-        if (where == GARLIC_HOST) {
-            if ((rc = stage.reserve((size_t)(nrows * ld)))) return rc;
-            e = hipMemcpyAsync(stage.p, src, sizeof(uint16_t) * (size_t)(nrows * ld), hipMemcpyHostToDevice, s);
-            src = stage.p;
-        }
-        if (e != hipSuccess) break;
-        hipLaunchKernelGGL(gl_store_codes16_kernel, dim3(2048), dim3(256), 0, s, src, ld, locus_begin + at, nrows, p->nind, d_dict.p,
-                           nvalues, rows_total, p->d_glval.p);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(s);                      // staging slab free again
-    }
-    if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "set_gl_codes16: %s", hipGetErrorString(e));
-    if (!p->gl_cover.empty()) memset(p->gl_cover.data() + locus_begin, 1, (size_t)locus_count);
-    p->have_gl = true;
-    p->glterms_valid = false;
+    if (e != hipSuccess) return upload_fail("set_gl_codes16", e);
+    rc = for_each_upload_slab(s, "set_gl_codes16", codes, 2 * ld, locus_count, where, stage, [&](const void *rows, int64_t at, int64_t n) {
+        hipLaunchKernelGGL(gl_store_codes16_kernel, dim3(2048), dim3(256), 0, s, (const uint16_t *)rows, ld, locus_begin + at, n, p->nind,
+                           d_dict.p, nvalues, rows_total, p->d_glval.p);
+        return GARLIC_OK;
+    });
+    return rc ? rc : end_gl_upload(p, locus_begin, locus_count);
+}
+
+// the phase planes of a panel that gets its first phase, all zero
+static int ensure_phase_planes(garlic_panel *p, int nblk)
+{
+    if (p->d_phase.p) return GARLIC_OK;
+    if (int rc = p->d_phase.reserve((size_t)nblk * p->nloci)) return rc;
+    HIP_TRY(hipMemsetAsync(p->d_phase.p, 0, sizeof(uint64_t) * nblk * p->nloci, p->ctx->stream));
     return GARLIC_OK;
 }
 
@@ -3025,40 +2951,18 @@ int garlic_panel_set_phase(garlic_panel *p, const uint8_t *first_copy, int64_t l
                            int64_t locus_count, int32_t where)
 {
     if (!p || !first_copy) return fail(GARLIC_ERR_INVALID, "panel and first_copy are required");
-    if (ld < p->nind) return fail(GARLIC_ERR_INVALID, "ld %lld < nind %d", (long long)ld, p->nind);
-    if (locus_begin < 0 || locus_count < 1 || locus_begin + locus_count > p->nloci)
-        return fail(GARLIC_ERR_INVALID, "locus range [%lld,+%lld) outside panel of %lld loci",
-                    (long long)locus_begin, (long long)locus_count, (long long)p->nloci);
-    int rc;
-    if ((rc = set_device(p->ctx))) return rc;
-    hipStream_t s = p->ctx->stream;
     const int nblk = (int)(p->nind_pad / WAVE);
-    if (!p->d_phase.p) {
-        if ((rc = p->d_phase.reserve((size_t)nblk * p->nloci))) return rc;
-        HIP_TRY(hipMemsetAsync(p->d_phase.p, 0, sizeof(uint64_t) * nblk * p->nloci, s));
-    }
+    int rc;
+    if ((rc = check_rows(p, ld, locus_begin, locus_count)) || (rc = set_device(p->ctx)) || (rc = ensure_phase_planes(p, nblk))) return rc;
+    hipStream_t s = p->ctx->stream;
     DevBuf<uint8_t> stage;
-    const int64_t slab_rows = (where == GARLIC_HOST) ? std::max<int64_t>(16, ((int64_t)256 << 20) / ld)
-                                                     : locus_count;
-    for (int64_t done = 0; done < locus_count; done += slab_rows) {
-        const int64_t rows = std::min(slab_rows, locus_count - done);
-        const uint8_t *src = first_copy + done * ld;
-        hipError_t e = hipSuccess;
-        if (where == GARLIC_HOST) {
-            if ((rc = stage.reserve((size_t)(rows * ld)))) { stage.release(); return rc; }
-            e = hipMemcpyAsync(stage.p, src, (size_t)(rows * ld), hipMemcpyHostToDevice, s);
-            src = stage.p;
-        }
-        if (e == hipSuccess) {
-            const int64_t waves = rows * nblk;
-            hipLaunchKernelGGL(phase_planes_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, src,
-                               ld, locus_begin + done, rows, p->nind, nblk, p->nloci, p->d_phase.p);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(s);                      // staging buffer is reused
-        if (e != hipSuccess) { stage.release(); return fail(GARLIC_ERR_HIP, "set_phase: %s", hipGetErrorString(e)); }
-    }
-    stage.release();
+    rc = for_each_upload_slab(s, "set_phase", first_copy, ld, locus_count, where, stage, [&](const void *rows, int64_t at, int64_t n) {
+        const int64_t waves = n * nblk;
+        hipLaunchKernelGGL(phase_planes_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, (const uint8_t *)rows,
+                           ld, locus_begin + at, n, p->nind, nblk, p->nloci, p->d_phase.p);
+        return GARLIC_OK;
+    });
+    if (rc) return rc;
     p->have_phase = true;
     return GARLIC_OK;
 }
@@ -3068,37 +2972,17 @@ int garlic_panel_set_phase_bits(garlic_panel *p, const uint8_t *rows, int64_t ro
 {
     if (!p || !rows) return fail(GARLIC_ERR_INVALID, "panel and rows are required");
     if (row_bytes < ((int64_t)p->nind + 7) / 8) return fail(GARLIC_ERR_INVALID, "row_bytes %lld < %d bits", (long long)row_bytes, p->nind);
-    if (locus_begin < 0 || locus_count < 1 || locus_begin + locus_count > p->nloci)
-        return fail(GARLIC_ERR_INVALID, "locus range [%lld,+%lld) outside panel of %lld loci",
-                    (long long)locus_begin, (long long)locus_count, (long long)p->nloci);
-    int rc;
-    if ((rc = set_device(p->ctx))) return rc;
-    hipStream_t s = p->ctx->stream;
     const int nblk = (int)(p->nind_pad / WAVE);
-    if (!p->d_phase.p) {
-        if ((rc = p->d_phase.reserve((size_t)nblk * p->nloci))) return rc;
-        HIP_TRY(hipMemsetAsync(p->d_phase.p, 0, sizeof(uint64_t) * nblk * p->nloci, s));
-    }
+    int rc;
+    if ((rc = check_loci(p, locus_begin, locus_count)) || (rc = set_device(p->ctx)) || (rc = ensure_phase_planes(p, nblk))) return rc;
+    hipStream_t s = p->ctx->stream;
     DevBuf<uint8_t> stage;
-    const int64_t slab_rows = (where == GARLIC_HOST) ? std::max<int64_t>(16, ((int64_t)256 << 20) / row_bytes) : locus_count;
-    for (int64_t done = 0; done < locus_count; done += slab_rows) {
-        const int64_t n = std::min(slab_rows, locus_count - done);
-        const uint8_t *src = rows + done * row_bytes;
-        hipError_t e = hipSuccess;
-        if (where == GARLIC_HOST) {
-            if ((rc = stage.reserve((size_t)(n * row_bytes)))) { stage.release(); return rc; }
-            e = hipMemcpyAsync(stage.p, src, (size_t)(n * row_bytes), hipMemcpyHostToDevice, s);
-            src = stage.p;
-        }
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(phase_bits_planes_kernel, dim3((unsigned)((n + WAVE - 1) / WAVE)), dim3(256), 0, s, src, row_bytes,
-                               locus_begin + done, n, p->nind, nblk, p->nloci, p->d_phase.p);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(s);                      // staging buffer is reused
-        if (e != hipSuccess) { stage.release(); return fail(GARLIC_ERR_HIP, "set_phase_bits: %s", hipGetErrorString(e)); }
-    }
-    stage.release();
+    rc = for_each_upload_slab(s, "set_phase_bits", rows, row_bytes, locus_count, where, stage, [&](const void *src, int64_t at, int64_t n) {
+        hipLaunchKernelGGL(phase_bits_planes_kernel, dim3((unsigned)((n + WAVE - 1) / WAVE)), dim3(256), 0, s, (const uint8_t *)src,
+                           row_bytes, locus_begin + at, n, p->nind, nblk, p->nloci, p->d_phase.p);
+        return GARLIC_OK;
+    });
+    if (rc) return rc;
     p->have_phase = true;
     return GARLIC_OK;
 }
