@@ -44,6 +44,7 @@ SYMBOLS = [
     "garlic_panel_set_feed_order", "garlic_feed_sort", "garlic_feed_sort_info",
     "garlic_panel_set_phase_bits", "garlic_panel_ld_form_info",
     "garlic_panel_set_gl_codes16",
+    "garlic_bed_create", "garlic_bed_set_rows", "garlic_bed_census", "garlic_bed_destroy", "garlic_panel_set_genotypes_bed",
 ]
 
 
@@ -146,6 +147,11 @@ def lib():
     L.garlic_panel_ld_form_info.argtypes = [_vp, _i32p, _i32p, _i32p, _i32p]
     L.garlic_feed_sort.argtypes = [_vp, _vp, C.c_int64, C.c_int32]
     L.garlic_feed_sort_info.argtypes = [_vp, _i32p, _i32p, _i64p]
+    L.garlic_bed_create.argtypes = [_vp, C.c_int64, C.c_int32, C.POINTER(_vp)]
+    L.garlic_bed_set_rows.argtypes = [_vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32]
+    L.garlic_bed_census.argtypes = [_vp, _vp, _vp, C.c_int32]
+    L.garlic_bed_destroy.argtypes = [_vp]
+    L.garlic_panel_set_genotypes_bed.argtypes = [_vp, _vp, C.c_int64, _i64p]
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int and name not in ("garlic_hip_abi_version",):
@@ -264,6 +270,56 @@ class DeviceBuffer:
             pass
 
 
+class Bed:
+    """The SNP-major image of a PLINK .bed file on a context's device (garlic_bed): nrows rows of (nind_total + 3) // 4
+    bytes in PLINK's 2-bit codes."""
+
+    def __init__(self, ctx, nrows, nind_total):
+        self.ctx = ctx
+        self.nrows = int(nrows)
+        self.nind_total = int(nind_total)
+        self.row_bytes = (self.nind_total + 3) // 4
+        self.handle = _vp()
+        check(lib().garlic_bed_create(ctx.handle, self.nrows, self.nind_total, C.byref(self.handle)))
+
+    @classmethod
+    def create(cls, ctx, nrows, nind_total):
+        return cls(ctx, nrows, nind_total)
+
+    def set_rows(self, rows, row_begin=0):
+        """rows: uint8 [row_count][row_bytes >= (nind_total + 3) // 4] (host)."""
+        rows = np.asarray(rows)
+        assert rows.dtype == np.uint8 and rows.ndim == 2 and (rows.shape[1] == 1 or rows.strides[1] == 1)
+        check(lib().garlic_bed_set_rows(self.handle, _vp(rows.ctypes.data), rows.strides[0], row_begin, rows.shape[0], HOST))
+
+    def set_rows_device(self, ptr, row_bytes, row_begin, row_count):
+        """ptr: device address of row_count rows, row_bytes apart."""
+        check(lib().garlic_bed_set_rows(self.handle, _vp(ptr), row_bytes, row_begin, row_count, DEVICE))
+
+    def census(self):
+        """(counts int32 [nrows][2] = nalleles, total; counted uint8 [nrows] = 0 A1, 1 A2, 2 none)."""
+        counts = np.empty((self.nrows, 2), dtype=np.int32)
+        counted = np.empty(self.nrows, dtype=np.uint8)
+        check(lib().garlic_bed_census(self.handle, _vp(counts.ctypes.data), _vp(counted.ctypes.data), HOST))
+        return counts, counted
+
+    def census_device(self, counts_ptr, counted_ptr):
+        check(lib().garlic_bed_census(self.handle, _vp(counts_ptr), _vp(counted_ptr), DEVICE))
+
+    def destroy(self):
+        if self.handle:
+            lib().garlic_bed_destroy(self.handle)
+            self.handle = _vp()
+
+    close = destroy
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.destroy()
+
+
 class Panel:
     """Device-resident genotype panel (garlic_panel) for the individuals one context owns."""
 
@@ -331,6 +387,13 @@ class Panel:
         assert rows.ndim == 2
         check(lib().garlic_panel_set_genotypes_2bit(self.handle, _vp(rows.ctypes.data), rows.shape[1], ind_offset,
                                                     locus_begin, rows.shape[0], HOST))
+
+    def set_genotypes_bed(self, bed, dest_locus, ind_offset=0):
+        """The rows of a Bed image recoded into the panel: dest_locus[r] = global locus of file row r, -1 = dropped; this
+        panel's individuals start at ind_offset of the row."""
+        dest = np.ascontiguousarray(dest_locus, dtype=np.int64)
+        assert dest.shape == (bed.nrows,)
+        check(lib().garlic_panel_set_genotypes_bed(self.handle, bed.handle, ind_offset, _ptr(dest, _i64p)))
 
     def set_gl_codes(self, codes, values, locus_begin=0):
         """codes: uint8 [nloci_chunk][nind] indexing values (float64, <= 256 error probabilities)"""

@@ -1,0 +1,183 @@
+// PLINK .bed rows on the device (gfx950, wave64): the allele census and the recode into the packed panel.
+//
+// A .bed row holds the N individuals of one SNP at 2 bits each, 4 per byte, individual j at bits 2 * (j % 4) of byte j / 4:
+// 00 hom A1, 01 missing, 10 het, 11 hom A2.  GARLIC counts "the first non-missing allele on the line"
+// (src/garlic-data.cpp:107-113); on the TPED line the row stands for a hom A1 genotype reads "A1 A1", a het "A1 A2", a hom A2
+// "A2 A2", so the counted allele is A2 when the first non-missing genotype is hom A2 and A1 otherwise.  Both kernels are
+// integer work and exact.
+//
+// The image keeps the rows back to back, (N + 3) / 4 bytes each: a row starts at any byte.  Both kernels therefore read the
+// image in ALIGNED 16-byte pieces (the buffer is 256-byte aligned and padded past its last row) and mask what a piece holds
+// of the neighbouring rows.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "lod_kernels.hpp"
+
+namespace garlic {
+
+constexpr uint64_t BED_LO = 0x5555555555555555ull;
+constexpr int BED_IMAGE_PAD = 32;      // bytes past the last row that an aligned 16-byte read may touch
+
+// the fields [a, b) of a 64-bit word of 32 two-bit fields, as a mask on the low bit of each field (0 <= a, b <= 32)
+__device__ __forceinline__ uint64_t bed_field_mask(int a, int b)
+{
+    if (b <= a) return 0;
+    const uint64_t upto_b = b >= 32 ? ~0ull : ((1ull << (2 * b)) - 1);
+    const uint64_t upto_a = (1ull << (2 * a)) - 1;     // a < b <= 32: a <= 31
+    return (upto_b & ~upto_a) & BED_LO;
+}
+
+// One row per group of `group` lanes (a power of two, 1 .. 64; 64 / group rows share a wave, so the 12-byte rows of a
+// 45-individual panel go 32 to a wave); a group walks its row in 16-byte pieces, `group` of them a trip.  Per lane: the
+// class counts of its pieces by popcount and the first non-missing genotype as the key  2 * individual + (hom A2);  per
+// group: sums and the minimum key over the lanes by cross-lane exchange -- no atomics, nothing depends on arrival order.
+// counts[r] = {nalleles, total}, counted[r] = 0 (A1), 1 (A2), 2 (none: every genotype missing).
+__global__ void __launch_bounds__(256)
+bed_census_kernel(const uint8_t *__restrict__ image, int64_t nrows, int32_t nind, int64_t row_bytes, int32_t group,
+                  int32_t *__restrict__ counts, uint8_t *__restrict__ counted)
+{
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int sub = lane & (group - 1);
+    const int64_t rows_per_wave = WAVE / group;
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    const int64_t nsteps = (nrows + rows_per_wave - 1) / rows_per_wave;
+    for (int64_t step = wave; step < nsteps; step += nwaves) {
+        const int64_t r = step * rows_per_wave + lane / group;
+        const bool live = r < nrows;
+        const int64_t begin = live ? r * row_bytes : 0;              // first byte of the row
+        const int64_t a0 = begin & ~(int64_t)15;
+        const int64_t npieces = live ? ((begin + row_bytes - a0 + 15) >> 4) : 0;
+        uint32_t n_a1 = 0, n_het = 0, n_a2 = 0, first = 0xFFFFFFFFu;
+        for (int64_t pc = sub; pc < npieces; pc += group) {
+            const int64_t at = a0 + 16 * pc;
+            const uint4 v = *reinterpret_cast<const uint4 *>(image + at);
+            const uint64_t w2[2] = {(uint64_t)v.x | ((uint64_t)v.y << 32), (uint64_t)v.z | ((uint64_t)v.w << 32)};
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                // field t of this word is individual j0 + t
+                const int64_t j0 = 4 * (at + 8 * h - begin);
+                const int lo_t = j0 < 0 ? (int)(-j0 < 32 ? -j0 : 32) : 0;
+                const int64_t left = (int64_t)nind - j0;
+                const int hi_t = left < 0 ? 0 : (left < 32 ? (int)left : 32);
+                const uint64_t valid = bed_field_mask(lo_t, hi_t);
+                const uint64_t lo = w2[h] & BED_LO, hi = (w2[h] >> 1) & BED_LO;
+                const uint64_t a1 = ~lo & ~hi & valid, het = ~lo & hi & valid, a2 = lo & hi & valid;
+                n_a1 += __popcll(a1);
+                n_het += __popcll(het);
+                n_a2 += __popcll(a2);
+                const uint64_t nm = a1 | het | a2;
+                if (nm) {
+                    const int t = (__ffsll((unsigned long long)nm) - 1) >> 1;
+                    const uint32_t key = (uint32_t)(2 * (j0 + t)) + (uint32_t)((a2 >> (2 * t)) & 1);
+                    first = key < first ? key : first;
+                }
+            }
+        }
+        for (int d = group >> 1; d > 0; d >>= 1) {
+            n_a1 += __shfl_xor(n_a1, d, WAVE);
+            n_het += __shfl_xor(n_het, d, WAVE);
+            n_a2 += __shfl_xor(n_a2, d, WAVE);
+            const uint32_t o = __shfl_xor(first, d, WAVE);
+            first = o < first ? o : first;
+        }
+        if (live && sub == 0) {
+            const bool none = first == 0xFFFFFFFFu;
+            const uint32_t c = none ? 2u : (first & 1u);
+            counts[2 * r] = none ? 0 : (int32_t)(2 * (c ? n_a2 : n_a1) + n_het);
+            counts[2 * r + 1] = none ? 0 : (int32_t)(2 * (n_a1 + n_het + n_a2));
+            counted[r] = (uint8_t)c;
+        }
+    }
+}
+
+// PLINK codes -> the panel's (copies of the counted allele; 3 = missing), 32 fields at once.  By field value v = 2 hi + lo:
+// counted A1: 0 -> 2, 1 -> 3, 2 -> 1, 3 -> 0;  counted A2: 0 -> 0, 1 -> 3, 2 -> 1, 3 -> 2;  none: all 3.  In both the new
+// low bit is lo ^ hi; the new high bit is ~hi (A1) or lo (A2).
+__device__ __forceinline__ uint64_t bed_recode64(uint64_t w, uint32_t c)
+{
+    const uint64_t lo = w & BED_LO, hi = (w >> 1) & BED_LO;
+    const uint64_t nh = c == 0 ? (~hi & BED_LO) : lo;
+    return c >= 2 ? ~0ull : ((lo ^ hi) | (nh << 1));
+}
+
+// The transpose of pack_genotypes_2bit_kernel into the same [64-individual block][word row][64 individuals] layout, with the
+// code map chosen per file row and the rows of a 16-locus word gathered through word_rows (built by the host from dest_locus):
+// word_rows[(w - word_lo) * 16 + q] = file row whose genotypes go to bit position q of word row w, -1 = none (that position
+// keeps its bits).  A workgroup takes one word row and a span of 64 blocks (4096 individuals): each of its 4 waves reads the
+// pieces of 4 of the 16 file rows ONCE, 16 bytes per lane, 1 KB per wave instruction, recodes them and leaves them in LDS;
+// then lane = individual, wave = block, and every lane picks its 16 codes from LDS (4 lanes share a byte: a broadcast) and
+// writes one word -- 256 contiguous bytes per wave store.  (The one-byte-per-lane-and-locus reads of pack_genotypes_2bit_kernel
+// fetch every row piece once per individual block and word.)
+constexpr int BED_SPAN_BLOCKS = 64;
+constexpr int BED_ROW_PIECES = BED_SPAN_BLOCKS + 2;    // 1 KB of a row + its misalignment (15 B) + the shift inside a byte
+constexpr int BED_ROW_LDS = BED_ROW_PIECES * 16;
+
+__global__ void __launch_bounds__(256)
+bed_pack_kernel(const uint8_t *__restrict__ image, int64_t image_bytes /* padded: every aligned piece below it may be read */,
+                int64_t row_bytes, const uint8_t *__restrict__ counted, const int32_t *__restrict__ word_rows,
+                int64_t ind_offset, int32_t nind, int64_t nind_pad, int64_t nwordrows, uint32_t *__restrict__ packed,
+                int64_t word_lo)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t tile[16][BED_ROW_LDS];
+    __shared__ int64_t row_a0[16];       // image offset of tile[q][0]; -1: no row at this position
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & (WAVE - 1);
+    const int64_t w = word_lo + blockIdx.x;
+    const int64_t blk0 = (int64_t)blockIdx.y * BED_SPAN_BLOCKS;
+    const int32_t *rows = word_rows + (int64_t)blockIdx.x * 16;
+    // the span's individuals of the whole data set: [j_lo, j_hi]
+    const int64_t j_lo = ind_offset + blk0 * 64;
+    const int64_t last = (blk0 + BED_SPAN_BLOCKS) * 64 < nind ? (blk0 + BED_SPAN_BLOCKS) * 64 : nind;
+    const int64_t j_hi = ind_offset + last - 1;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int q = wv + 4 * k;
+        const int32_t r = rows[q];
+        if (r < 0 || j_hi < j_lo) {
+            if (lane == 0) row_a0[q] = -1;
+            continue;
+        }
+        const int64_t begin = (int64_t)r * row_bytes;
+        const int64_t a0 = (begin + (j_lo >> 2)) & ~(int64_t)15;
+        const int64_t end = begin + (j_hi >> 2);                 // last byte the span needs of this row
+        const uint32_t c = counted[r];
+        if (lane == 0) row_a0[q] = a0;
+        for (int pc = lane; pc < BED_ROW_PIECES; pc += WAVE) {
+            const int64_t at = a0 + 16 * (int64_t)pc;
+            if (at > end || at + 16 > image_bytes) continue;
+            const uint4 v = *reinterpret_cast<const uint4 *>(image + at);
+            const uint64_t x = bed_recode64((uint64_t)v.x | ((uint64_t)v.y << 32), c);
+            const uint64_t y = bed_recode64((uint64_t)v.z | ((uint64_t)v.w << 32), c);
+            *reinterpret_cast<uint4 *>(&tile[q][16 * pc]) = make_uint4((uint32_t)x, (uint32_t)(x >> 32), (uint32_t)y, (uint32_t)(y >> 32));
+        }
+    }
+    __syncthreads();
+    // (rows[] is the same for the whole workgroup: a word without rows is left alone, pad individuals included -- they are
+    // 0xFFFFFFFF since the panel was created)
+    bool word_any = false;
+#pragma unroll
+    for (int q = 0; q < 16; q++) word_any = word_any || rows[q] >= 0;
+    if (!word_any) return;
+    for (int b = wv; b < BED_SPAN_BLOCKS; b += 4) {
+        const int64_t ind = (blk0 + b) * 64 + lane;
+        if (ind >= nind_pad) break;
+        uint32_t *dst = packed + packed_index(w, ind, nwordrows);
+        if (ind >= nind) { *dst = 0xFFFFFFFFu; continue; }
+        const int64_t j = ind_offset + ind;
+        const int sh = 2 * (int)(j & 3);
+        uint32_t word = *dst;             // positions no row maps to keep their previous bits
+#pragma unroll
+        for (int q = 0; q < 16; q++) {
+            const int64_t a0 = row_a0[q];
+            if (a0 < 0) continue;
+            const int64_t off = (int64_t)rows[q] * row_bytes + (j >> 2) - a0;
+            const uint32_t code = ((uint32_t)tile[q][off] >> sh) & 3u;
+            word = (word & ~(3u << (2 * q))) | (code << (2 * q));
+        }
+        *dst = word;
+    }
+}
+
+} // namespace garlic

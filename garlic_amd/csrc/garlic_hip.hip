@@ -21,6 +21,7 @@
 #include "feed_kernel.hpp"
 #include "wlod_feed_kernel.hpp"
 #include "feed_sort_kernel.hpp"
+#include "bed_kernels.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -247,6 +248,7 @@ struct garlic_panel {
     DevBuf<int32_t> d_counter;
     DevBuf<ChrDev> d_chrs;
     DevBuf<int16_t> d_stage16;
+    DevBuf<int32_t> d_bed_word_rows;               // garlic_panel_set_genotypes_bed: the file rows of every 16-locus word of the call
     DevBuf<int64_t> d_row_counts;
     // TGLS: dictionary-coded per-genotype error probabilities
     bool have_gl = false;
@@ -2774,6 +2776,171 @@ int garlic_panel_set_genotypes_2bit(garlic_panel *p, const uint8_t *rows, int64_
     return GARLIC_OK;
 }
 
+// ---- PLINK .bed rows (bed_kernels.hpp): the image, its census, and the door into a panel
+struct garlic_bed {
+    garlic_ctx *ctx = nullptr;
+    int64_t nrows = 0, row_bytes = 0, image_bytes = 0;      // image_bytes: rows + pad, a multiple of 16
+    int32_t nind = 0;
+    DevBuf<uint8_t> d_image, d_counted, stage;
+    DevBuf<int32_t> d_counts;
+    std::vector<uint64_t> row_set;                          // one bit per row that has been set
+    int64_t n_set = 0;
+    bool census_valid = false;
+    std::vector<int32_t> counts;                            // the census, cached with the image
+    std::vector<uint8_t> counted;
+};
+
+int garlic_bed_create(garlic_ctx *ctx, int64_t nrows, int32_t nind_total, garlic_bed **out)
+{
+    if (!out) return fail(GARLIC_ERR_INVALID, "bed out pointer is NULL");
+    *out = nullptr;
+    if (!ctx) return fail(GARLIC_ERR_INVALID, "ctx is NULL");
+    if (nrows < 1 || nrows > 0x7FFFFFFF || nind_total < 1 || nind_total >= (1 << 30))
+        return fail(GARLIC_ERR_INVALID, "need 1 <= nrows < 2^31 and 1 <= nind_total < 2^30");    // total = 2 * #non-missing is an int32
+    int rc;
+    if ((rc = set_device(ctx))) return rc;
+    std::unique_ptr<garlic_bed> b(new garlic_bed);
+    b->ctx = ctx;
+    b->nrows = nrows;
+    b->nind = nind_total;
+    b->row_bytes = ((int64_t)nind_total + 3) / 4;
+    b->image_bytes = ((nrows * b->row_bytes + 15) & ~(int64_t)15) + BED_IMAGE_PAD;
+    if ((rc = b->d_image.reserve((size_t)b->image_bytes)) || (rc = b->d_counts.reserve((size_t)(2 * nrows))) ||
+        (rc = b->d_counted.reserve((size_t)nrows)))
+        return rc;
+    HIP_TRY(hipMemsetAsync(b->d_image.p + b->image_bytes - BED_IMAGE_PAD, 0, BED_IMAGE_PAD, ctx->stream));   // (masked anyway)
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    b->row_set.assign((size_t)((nrows + 63) / 64), 0);
+    *out = b.release();
+    return GARLIC_OK;
+}
+
+int garlic_bed_destroy(garlic_bed *b)
+{
+    if (!b) return GARLIC_OK;
+    (void)hipSetDevice(b->ctx->device);
+    (void)hipStreamSynchronize(b->ctx->stream);
+    delete b;
+    return GARLIC_OK;
+}
+
+int garlic_bed_set_rows(garlic_bed *b, const uint8_t *rows, int64_t row_bytes, int64_t row_begin, int64_t row_count, int32_t where)
+{
+    if (!b || !rows) return fail(GARLIC_ERR_INVALID, "bed and rows are required");
+    if (where != GARLIC_HOST && where != GARLIC_DEVICE) return fail(GARLIC_ERR_INVALID, "where must be GARLIC_HOST or GARLIC_DEVICE");
+    if (row_bytes < b->row_bytes)
+        return fail(GARLIC_ERR_INVALID, "row_bytes %lld too small for %d individuals (%lld)", (long long)row_bytes, b->nind,
+                    (long long)b->row_bytes);
+    if (row_begin < 0 || row_count < 1 || row_begin + row_count > b->nrows)
+        return fail(GARLIC_ERR_INVALID, "row range [%lld,+%lld) outside image of %lld rows", (long long)row_begin,
+                    (long long)row_count, (long long)b->nrows);
+    int rc;
+    if ((rc = set_device(b->ctx))) return rc;
+    hipStream_t s = b->ctx->stream;
+    b->census_valid = false;
+    rc = for_each_upload_slab(s, "bed_set_rows", rows, row_bytes, row_count, where, b->stage, [&](const void *src, int64_t at, int64_t n) {
+        uint8_t *dst = b->d_image.p + (row_begin + at) * b->row_bytes;
+        const hipError_t e = row_bytes == b->row_bytes
+            ? hipMemcpyAsync(dst, src, (size_t)(n * row_bytes), hipMemcpyDeviceToDevice, s)
+            : hipMemcpy2DAsync(dst, (size_t)b->row_bytes, src, (size_t)row_bytes, (size_t)b->row_bytes, (size_t)n, hipMemcpyDeviceToDevice, s);
+        return e == hipSuccess ? GARLIC_OK : upload_fail("bed_set_rows", e);
+    });
+    if (rc) return rc;
+    for (int64_t r = row_begin; r < row_begin + row_count; r++) {
+        uint64_t &word = b->row_set[(size_t)(r >> 6)];
+        const uint64_t bit = 1ull << (r & 63);
+        if (!(word & bit)) { word |= bit; b->n_set++; }
+    }
+    return GARLIC_OK;
+}
+
+// the census of the image as it stands, on the device and in the host cache
+static int bed_ensure_census(garlic_bed *b)
+{
+    if (b->n_set != b->nrows)
+        return fail(GARLIC_ERR_STATE, "bed census needs every row: %lld of %lld set", (long long)b->n_set, (long long)b->nrows);
+    if (b->census_valid) return GARLIC_OK;
+    int rc;
+    if ((rc = set_device(b->ctx))) return rc;
+    hipStream_t s = b->ctx->stream;
+    // lanes per row: the pieces a row can touch (it starts at any byte), as a power of two; narrower rows share a wave
+    const int64_t pieces = (b->row_bytes + 30) >> 4;
+    int group = 1;
+    while (group < 64 && group < pieces) group <<= 1;
+    const int64_t rows_per_block = 4 * (64 / group);
+    const unsigned grid = (unsigned)std::min<int64_t>((b->nrows + rows_per_block - 1) / rows_per_block, 8 * (int64_t)b->ctx->n_cu);
+    hipLaunchKernelGGL(bed_census_kernel, dim3(grid), dim3(256), 0, s, b->d_image.p, b->nrows, b->nind, b->row_bytes, group,
+                       b->d_counts.p, b->d_counted.p);
+    HIP_TRY(hipGetLastError());
+    b->counts.resize((size_t)(2 * b->nrows));
+    b->counted.resize((size_t)b->nrows);
+    HIP_TRY(hipMemcpyAsync(b->counts.data(), b->d_counts.p, sizeof(int32_t) * 2 * b->nrows, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(b->counted.data(), b->d_counted.p, (size_t)b->nrows, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    b->census_valid = true;
+    return GARLIC_OK;
+}
+
+int garlic_bed_census(garlic_bed *b, int32_t *counts, uint8_t *counted, int32_t where)
+{
+    if (!b) return fail(GARLIC_ERR_INVALID, "bed is NULL");
+    if (where != GARLIC_HOST && where != GARLIC_DEVICE) return fail(GARLIC_ERR_INVALID, "where must be GARLIC_HOST or GARLIC_DEVICE");
+    int rc;
+    if ((rc = bed_ensure_census(b))) return rc;
+    if (where == GARLIC_HOST) {
+        if (counts) memcpy(counts, b->counts.data(), sizeof(int32_t) * b->counts.size());
+        if (counted) memcpy(counted, b->counted.data(), b->counted.size());
+        return GARLIC_OK;
+    }
+    hipStream_t s = b->ctx->stream;
+    if (counts) HIP_TRY(hipMemcpyAsync(counts, b->d_counts.p, sizeof(int32_t) * 2 * b->nrows, hipMemcpyDeviceToDevice, s));
+    if (counted) HIP_TRY(hipMemcpyAsync(counted, b->d_counted.p, (size_t)b->nrows, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return GARLIC_OK;
+}
+
+int garlic_panel_set_genotypes_bed(garlic_panel *p, garlic_bed *b, int64_t ind_offset, const int64_t *dest_locus)
+{
+    if (!p || !b || !dest_locus) return fail(GARLIC_ERR_INVALID, "panel, bed and dest_locus are required");
+    if (b->ctx->device != p->ctx->device)
+        return fail(GARLIC_ERR_INVALID, "the bed image is on device %d, the panel on device %d", b->ctx->device, p->ctx->device);
+    if (ind_offset < 0 || ind_offset + p->nind > b->nind)
+        return fail(GARLIC_ERR_INVALID, "individuals [%lld,+%d) outside the image's %d", (long long)ind_offset, p->nind, b->nind);
+    int64_t prev = -1, first = -1;
+    for (int64_t r = 0; r < b->nrows; r++) {
+        const int64_t l = dest_locus[r];
+        if (l == -1) continue;
+        if (l < 0 || l >= p->nloci)
+            return fail(GARLIC_ERR_INVALID, "dest_locus[%lld] = %lld outside panel of %lld loci", (long long)r, (long long)l, (long long)p->nloci);
+        if (l <= prev)
+            return fail(GARLIC_ERR_INVALID, "dest_locus must ascend over the kept rows: row %lld maps to %lld after %lld", (long long)r,
+                        (long long)l, (long long)prev);
+        if (first < 0) first = l;
+        prev = l;
+    }
+    if (first < 0) return fail(GARLIC_ERR_INVALID, "dest_locus keeps no row");
+    int rc;
+    if ((rc = bed_ensure_census(b)) || (rc = set_device(p->ctx))) return rc;
+    // the rows of every 16-locus word the call touches
+    const int64_t w_lo = (GOFF + first) >> 4, w_hi = ((GOFF + prev) >> 4) + 1;
+    std::vector<int32_t> word_rows((size_t)((w_hi - w_lo) * 16), -1);
+    for (int64_t r = 0; r < b->nrows; r++)
+        if (dest_locus[r] >= 0) word_rows[(size_t)(GOFF + dest_locus[r] - 16 * w_lo)] = (int32_t)r;
+    hipStream_t s = p->ctx->stream;
+    if ((rc = p->d_bed_word_rows.put(word_rows, s))) return rc;
+    const int64_t nblk = p->nind_pad / 64;
+    const dim3 grid((unsigned)(w_hi - w_lo), (unsigned)((nblk + BED_SPAN_BLOCKS - 1) / BED_SPAN_BLOCKS));
+    hipLaunchKernelGGL(bed_pack_kernel, grid, dim3(256), 0, s, b->d_image.p, b->image_bytes, b->row_bytes, b->d_counted.p,
+                       p->d_bed_word_rows.p, ind_offset, p->nind, p->nind_pad, p->nwordrows, p->d_packed.p, w_lo);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(s);       // also: word_rows is free again
+    if (e != hipSuccess) return upload_fail("set_genotypes_bed", e);
+    p->have_geno = true;
+    p->geno_epoch++;
+    p->glterms_valid = false;
+    return GARLIC_OK;
+}
+
 // ---- uploads into a panel of 16-bit codes.
 // The caller's table joins the panel's (by bit pattern, first seen first): remap[caller code] = panel code.  When the merged
 // table would pass 65,536 values the panel goes on with the values themselves (gl_wide unset on return; remap is void then).
@@ -3887,7 +4054,7 @@ int garlic_panel_release_scratch(garlic_panel *p)
     HIP_TRY(hipStreamSynchronize(p->ctx->stream));
     p->lds.release();
     p->d_out.release(); p->d_feed.release();
-    p->d_stage16.release(); p->d_stage64.release();
+    p->d_stage16.release(); p->d_stage64.release(); p->d_bed_word_rows.release();
     p->fs.release(); p->ctx->fs.release();
     for (auto *sl : p->feed_slots) {
         HIP_TRY(hipStreamSynchronize(sl->stream));

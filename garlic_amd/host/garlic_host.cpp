@@ -4,6 +4,10 @@
 #include "../../include/garlic_hip.h"
 
 #include <zlib.h>
+#include <fcntl.h>
+#include <sys/mman.h>
+#include <sys/stat.h>
+#include <unistd.h>
 
 #include <algorithm>
 #include <atomic>
@@ -14,6 +18,7 @@
 #include <iostream>
 #include <sstream>
 #include <random>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <unordered_map>
@@ -157,6 +162,8 @@ HapData *initHapData(unsigned int nind, unsigned int nloci, bool PHASED)
     d->firstCopy = PHASED ? new bool *[nloci] : nullptr;
     d->packed = nullptr;
     d->phaseBits = nullptr;
+    d->bed = nullptr;
+    d->bedRow = nullptr;
     for (unsigned l = 0; l < nloci; l++) {
         d->data[l] = new short[nind];
         std::fill(d->data[l], d->data[l] + nind, (short)MISSING);
@@ -180,6 +187,8 @@ void releaseHapData(HapData *d)
     delete[] d->firstCopy;
     delete[] d->packed;
     delete[] d->phaseBits;
+    delete[] d->bedRow;
+    if (d->bed && --d->bed->refs == 0) closeBedFile(d->bed);
     delete d;
 }
 void releaseHapData(std::vector<HapData *> *v) { for (auto d : *v) releaseHapData(d); delete v; }
@@ -355,6 +364,8 @@ void flushChromosome(const std::string &chr, std::vector<short *> &hap, std::vec
     h->firstCopy = fc.empty() ? nullptr : new bool *[n];
     h->packed = nullptr;
     h->phaseBits = nullptr;
+    h->bed = nullptr;
+    h->bedRow = nullptr;
     FreqData *f = initFreqData(n);
     for (int l = 0; l < n; l++) {
         if (h->firstCopy) h->firstCopy[l] = fc[l];
@@ -496,6 +507,160 @@ void loadTPEDData(const std::string &tpedfile, int &numLoci, int &numInd, std::v
     if (numLoci == 0) fail("no loci in " + tpedfile);
     flushChromosome(chr, hap, fc, gpos, ppos, names, allele, freq, numInd, *hapDataByChr, *mapDataByChr,
                     *freqDataByChr);
+}
+
+// ------------------------------------------------------------------------- PLINK .bed/.bim/.fam
+void closeBedFile(BedFile *b)
+{
+    if (!b) return;
+    for (auto &im : b->images) {
+        if (im.bed) garlic_bed_destroy((garlic_bed *)im.bed);
+        if (im.ctx) garlic_ctx_destroy((garlic_ctx *)im.ctx);
+    }
+    if (b->map) munmap(b->map, b->map_bytes);
+    delete b;
+}
+
+BedFile *openBedFile(const std::string &bedfile, const std::string &bimfile, const std::string &famfile)
+{
+    std::unique_ptr<BedFile, void (*)(BedFile *)> b(new BedFile, closeBedFile);
+    b->path = bedfile;
+    std::string pop;
+    scanIndData3(famfile, b->nind, pop);
+    if (b->nind < 1) fail("no individuals in " + famfile);
+    b->row_bytes = ((size_t)b->nind + 3) / 4;
+    {
+        LineReader in(bimfile);
+        std::string line;
+        int n = 0;
+        while (in.next(line)) {
+            n++;
+            if (line.empty()) continue;
+            if (countFields(line) != 6)
+                fail("line " + std::to_string(n) + " of " + bimfile + " does not have the 6 columns chr snpid gpos ppos a1 a2");
+            std::stringstream ss(line);
+            std::string chr, name, a1, a2;
+            double g = 0, p = 0;       // ppos as a double, stored as an int later: "1e6" is 1000000 as on the TPED path
+            ss >> chr >> name >> g >> p >> a1 >> a2;
+            if (ss.fail()) fail("line " + std::to_string(n) + " of " + bimfile + ": cannot read gpos / ppos");
+            if (a1.size() != 1 || a2.size() != 1)
+                fail("line " + std::to_string(n) + " of " + bimfile + ": allele \"" + (a1.size() != 1 ? a1 : a2) +
+                     "\" is not a single character (GARLIC's alleles are single characters)");
+            b->chr.push_back(chr); b->name.push_back(name); b->gpos.push_back(g); b->ppos.push_back(p);
+            b->a1.push_back(a1[0]); b->a2.push_back(a2[0]);
+        }
+    }
+    b->nrows = (long long)b->chr.size();
+    if (b->nrows < 1) fail("no loci in " + bimfile);
+    const int fd = open(bedfile.c_str(), O_RDONLY);
+    if (fd < 0) fail("Failed to open " + bedfile);
+    struct stat st;
+    if (fstat(fd, &st) != 0) { close(fd); fail("Failed to stat " + bedfile); }
+    unsigned char magic[3] = {0, 0, 0};
+    const ssize_t got = pread(fd, magic, 3, 0);
+    if (got != 3 || magic[0] != 0x6c || magic[1] != 0x1b) { close(fd); fail(bedfile + " is not a PLINK .bed file (magic bytes 6c 1b 01 expected)"); }
+    if (magic[2] == 0x00) { close(fd); fail(bedfile + " is an individual-major .bed (6c 1b 00); only SNP-major files (6c 1b 01) are read"); }
+    if (magic[2] != 0x01) { close(fd); fail(bedfile + " is not a PLINK .bed file (magic bytes 6c 1b 01 expected)"); }
+    const unsigned long long want = 3ull + (unsigned long long)b->nrows * b->row_bytes;
+    if ((unsigned long long)st.st_size != want) {
+        close(fd);
+        fail(bedfile + ((unsigned long long)st.st_size < want ? " is truncated: " : " is too long: ") + std::to_string((long long)st.st_size) + " bytes, " +
+             std::to_string(b->nrows) + " loci x " + std::to_string(b->nind) + " individuals need " + std::to_string(want));
+    }
+    void *m = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+    close(fd);
+    if (m == MAP_FAILED) fail("Failed to map " + bedfile);
+    b->map = m;
+    b->map_bytes = (size_t)st.st_size;
+    b->rows = (const unsigned char *)m + 3;
+    return b.release();
+}
+
+namespace {
+// the image of the file on `device` (made, filled chunk by chunk and censused at the first request)
+garlic_bed *bedImageOn(BedFile *b, int device)
+{
+    for (auto &im : b->images)
+        if (im.device == device) return (garlic_bed *)im.bed;
+    b->images.push_back({device, nullptr, nullptr});
+    garlic_ctx *ctx = nullptr;
+    check(garlic_ctx_create(device, nullptr, &ctx), "garlic_ctx_create");
+    b->images.back().ctx = ctx;
+    garlic_bed *bed = nullptr;
+    check(garlic_bed_create(ctx, b->nrows, b->nind, &bed), "garlic_bed_create");
+    b->images.back().bed = bed;
+    // chunks of 64 MB through an ordinary buffer (not the read-only file mapping itself: what the runtime does to pin or stage
+    // the source of a large copy is then no concern of the mapping)
+    const long long chunk = std::max<long long>(1, ((long long)64 << 20) / (long long)b->row_bytes);
+    std::vector<unsigned char> buf((size_t)std::min(chunk, b->nrows) * b->row_bytes);
+    for (long long r = 0; r < b->nrows; r += chunk) {
+        const long long n = std::min(chunk, b->nrows - r);
+        memcpy(buf.data(), b->rows + (size_t)r * b->row_bytes, (size_t)n * b->row_bytes);
+        check(garlic_bed_set_rows(bed, buf.data(), (int64_t)b->row_bytes, r, n, GARLIC_HOST), "garlic_bed_set_rows");
+    }
+    if (b->counted.empty()) {
+        b->counts.resize(2 * (size_t)b->nrows);
+        b->counted.resize((size_t)b->nrows);
+        check(garlic_bed_census(bed, b->counts.data(), b->counted.data(), GARLIC_HOST), "garlic_bed_census");
+    }
+    return bed;
+}
+} // namespace
+
+void loadBedData(const std::string &bedfile, const std::string &bimfile, const std::string &famfile, int &numLoci, int &numInd,
+                 std::vector<HapData *> **hapDataByChr, std::vector<MapData *> **mapDataByChr,
+                 std::vector<FreqData *> **freqDataByChr, int nresample, unsigned long long resampleSeed, int device)
+{
+    BedFile *b = openBedFile(bedfile, bimfile, famfile);
+    b->refs = 1;                 // this function's, until the HapData hold theirs
+    *hapDataByChr = new std::vector<HapData *>;
+    *mapDataByChr = new std::vector<MapData *>;
+    *freqDataByChr = new std::vector<FreqData *>;
+    try {
+        bedImageOn(b, device);   // the census
+        const unsigned long long seed0 = resampleSeed ? resampleSeed : (unsigned long long)time(nullptr);   // as loadTPEDData
+        std::mt19937 resampler((uint32_t)(seed0 & 0xffffffffull) ? (uint32_t)(seed0 & 0xffffffffull) : 4357u);
+        for (long long r0 = 0; r0 < b->nrows;) {
+            long long r1 = r0;
+            while (r1 < b->nrows && b->chr[(size_t)r1] == b->chr[(size_t)r0]) r1++;   // a new chromosome where the chr string changes
+            const int n = (int)(r1 - r0);
+            MapData *m = initMapData(n);
+            (*mapDataByChr)->push_back(m);
+            m->chr = checkChrName(b->chr[(size_t)r0]);
+            FreqData *f = initFreqData(n);
+            (*freqDataByChr)->push_back(f);
+            HapData *h = new HapData{nullptr, b->nind, n, nullptr, nullptr, nullptr, b, new long long[n]};
+            b->refs++;
+            (*hapDataByChr)->push_back(h);
+            for (int l = 0; l < n; l++) {
+                const size_t r = (size_t)(r0 + l);
+                h->bedRow[l] = (long long)r;
+                m->physicalPos[l] = (int)b->ppos[r];
+                m->geneticPos[l] = b->gpos[r];
+                m->locusName[l] = b->name[r];
+                // what loadTPEDData stores as oneAllele: the counted allele's character, the missing character '0' for none
+                m->allele[l] = b->counted[r] == 0 ? b->a1[r] : b->counted[r] == 1 ? b->a2[r] : '0';
+                const int nalleles = b->counts[2 * r], total = b->counts[2 * r + 1];
+                double freq = total == 0 ? 0.0 : double(nalleles) / double(total);   // garlic-data.cpp:141
+                if (nresample > 0 && total != 0) {
+                    int count = 0;
+                    for (int i = 0; i < nresample; i++)
+                        if ((double)resampler() / 4294967296.0 <= freq) count++;
+                    freq = double(count) / double(nresample);
+                }
+                f->freq[l] = freq;
+            }
+            r0 = r1;
+        }
+    } catch (...) {
+        releaseHapData(*hapDataByChr); releaseMapData(*mapDataByChr); releaseFreqData(*freqDataByChr);
+        *hapDataByChr = nullptr; *mapDataByChr = nullptr; *freqDataByChr = nullptr;
+        if (--b->refs == 0) closeBedFile(b);
+        throw;
+    }
+    numLoci = (int)b->nrows;
+    numInd = b->nind;
+    b->refs--;                   // at least one HapData holds the file now
 }
 
 void scanIndData3(const std::string &filename, int &numInd, std::string &popName)
@@ -722,7 +887,8 @@ void filterSites(size_t c, const std::vector<char> &keep, std::vector<MapData *>
     MapData *m2 = initMapData(n);
     m2->chr = m->chr;
     HapData *h2 = new HapData{h->data ? new short *[n] : nullptr, h->nind, n, h->firstCopy ? new bool *[n] : nullptr,
-                              h->packed ? new unsigned char *[n] : nullptr, h->phaseBits ? new unsigned char *[n] : nullptr};
+                              h->packed ? new unsigned char *[n] : nullptr, h->phaseBits ? new unsigned char *[n] : nullptr,
+                              h->bed, h->bed ? new long long[n] : nullptr};      // (a bed panel: only the row map is edited)
     FreqData *f2 = initFreqData(n);
     GenoLikeData *g2 = nullptr;
     if (g) {
@@ -748,13 +914,14 @@ void filterSites(size_t c, const std::vector<char> &keep, std::vector<MapData *>
         if (h->packed) h2->packed[j] = h->packed[l];
         if (h->firstCopy) h2->firstCopy[j] = h->firstCopy[l];
         if (h->phaseBits) h2->phaseBits[j] = h->phaseBits[l];
+        if (h->bed) h2->bedRow[j] = h->bedRow[l];
         f2->freq[j] = f->freq[l];
         if (g && g->data) g2->data[j] = g->data[l];
         if (g && g->codes) g2->codes[j] = g->codes[l];
         if (g && g->codes16) g2->codes16[j] = g->codes16[l];
         j++;
     }
-    delete[] h->data; delete[] h->firstCopy; delete[] h->packed; delete[] h->phaseBits; delete h;
+    delete[] h->data; delete[] h->firstCopy; delete[] h->packed; delete[] h->phaseBits; delete[] h->bedRow; delete h;
     if (g) { delete[] g->data; delete[] g->codes; delete[] g->codes16; delete g; (*gls)[c] = g2; }
     releaseMapData(m); releaseFreqData(f);
     (*maps)[c] = m2; (*haps)[c] = h2; (*freqs)[c] = f2;
@@ -889,6 +1056,25 @@ struct CacheIn {
 };
 } // namespace
 
+// four PLINK codes -> four cache codes (0/1/2 copies of the counted allele, 3 = missing), per counted[row]
+static const uint8_t *bedByteTable(unsigned counted)
+{
+    static uint8_t table[3][256];
+    static std::once_flag once;
+    std::call_once(once, [] {
+        for (unsigned c = 0; c < 3; c++)
+            for (unsigned b = 0; b < 256; b++) {
+                unsigned out = 0;
+                for (int k = 0; k < 4; k++) {
+                    const short g = bedGenotype(c, (b >> (2 * k)) & 3u);
+                    out |= (g < 0 ? 3u : (unsigned)g) << (2 * k);
+                }
+                table[c][b] = (uint8_t)out;
+            }
+    });
+    return table[counted];
+}
+
 void writeGenotypeCache(const std::string &path, std::vector<HapData *> *haps, std::vector<MapData *> *maps,
                         std::vector<FreqData *> *freqs)
 {
@@ -915,6 +1101,15 @@ void writeGenotypeCache(const std::string &path, std::vector<HapData *> *haps, s
         for (int l = 0; l < m->nloci; l++) o.str(m->locusName[l]);
         for (int l = 0; l < m->nloci; l++) {
             if (h->packed) { o.put(h->packed[l], row); continue; }
+            if (h->bed) {   // the row in the cache's codes: a 256-entry byte table per counted allele
+                const size_t r = (size_t)h->bedRow[l];
+                const uint8_t *t = bedByteTable(h->bed->counted[r]);
+                const unsigned char *src = h->bed->rows + r * row;
+                for (size_t k = 0; k < row; k++) bits[k] = t[src[k]];
+                if (nind & 3) bits[row - 1] &= (uint8_t)((1u << (2 * (nind & 3))) - 1);   // the unused bits 0, as below
+                o.put(bits.data(), row);
+                continue;
+            }
             std::fill(bits.begin(), bits.end(), 0);
             for (int i = 0; i < nind; i++) {
                 const short g = h->data[l][i];
@@ -1086,6 +1281,21 @@ void LodEngine::upload(std::vector<HapData *> *haps, std::vector<FreqData *> *fr
         if (USE_GL && g_options.tgls_term_bytes != 0)      // --tgls-term-gb: the term matrix of each shard in slabs (weighted calls too)
             check(garlic_panel_set_tgls_term_budget(s.panel, g_options.tgls_term_bytes), "garlic_panel_set_tgls_term_budget");
     }
+    // a .bed panel: every shard's context fills its column block from the image on its device, through the row map the
+    // site filters left
+    if (haps->at(0)->bed) {
+        BedFile *b = haps->at(0)->bed;
+        std::vector<int64_t> dest((size_t)b->nrows, -1);
+        int64_t at = 0;
+        for (int c = 0; c < nchr; c++) {
+            const HapData *h = haps->at(c);
+            if (h->bed != b) fail("the chromosomes come from different .bed files");
+            for (int l = 0; l < h->nloci; l++) dest[(size_t)h->bedRow[l]] = at++;
+        }
+        for (auto &s : impl->shards)
+            check(garlic_panel_set_genotypes_bed(s.panel, bedImageOn(b, s.device), s.ind_begin, dest.data()),
+                  "garlic_panel_set_genotypes_bed");
+    }
     // genotype rows are separate allocations in HapData: stage a slab of SNP rows at a time
     const int64_t slab = std::max<int64_t>(1, ((int64_t)64 << 20) / (2 * (int64_t)impl->nind));
     std::vector<int16_t> stage;
@@ -1105,7 +1315,8 @@ void LodEngine::upload(std::vector<HapData *> *haps, std::vector<FreqData *> *fr
         for (int l0 = 0; l0 < h->nloci; l0 += (int)slab) {
             const int rows = (int)std::min<int64_t>(slab, h->nloci - l0);
             const size_t row_bytes = ((size_t)impl->nind + 3) / 4;
-            if (h->packed) {
+            if (h->bed) {   // (uploaded above)
+            } else if (h->packed) {
                 stage2.resize((size_t)rows * row_bytes);
                 for (int r = 0; r < rows; r++) memcpy(&stage2[(size_t)r * row_bytes], h->packed[l0 + r], row_bytes);
             } else {
@@ -1139,7 +1350,8 @@ void LodEngine::upload(std::vector<HapData *> *haps, std::vector<FreqData *> *fr
                         stage_fc[(size_t)r * impl->nind + i] = h->firstCopy[l0 + r][i];
             }
             for (auto &s : impl->shards) {
-                if (h->packed)
+                if (h->bed) {
+                } else if (h->packed)
                     check(garlic_panel_set_genotypes_2bit(s.panel, stage2.data(), (int64_t)row_bytes, s.ind_begin, o + l0,
                                                           rows, GARLIC_HOST), "garlic_panel_set_genotypes_2bit");
                 else

@@ -20,6 +20,34 @@ namespace garlic_host {
 
 const int MISSING = -9999; // src/garlic-data.h:24
 
+// A PLINK .bed/.bim/.fam triple (openBedFile): the .bed mapped read-only, the .bim columns per file row, and -- once
+// loadBedData has run the census on a device -- every row's counted allele and the two integers of its frequency.  The
+// genotypes stay in the file's codes (00 hom A1, 01 missing, 10 het, 11 hom A2; 4 per byte): the devices hold the image
+// (garlic_bed), the host reads single values through genotypeAt when a consumer needs them.
+struct BedFile {
+    std::string path;
+    int nind = 0;
+    long long nrows = 0;
+    size_t row_bytes = 0;                 // (nind + 3) / 4
+    const unsigned char *rows = nullptr;  // row r at rows + r * row_bytes (behind the three magic bytes)
+    void *map = nullptr;
+    size_t map_bytes = 0;
+    std::vector<std::string> chr, name;
+    std::vector<double> gpos, ppos;
+    std::vector<char> a1, a2;
+    std::vector<unsigned char> counted;   // per row: 0 = A1, 1 = A2, 2 = none (every genotype missing)
+    std::vector<int> counts;              // per row: nalleles, total
+    struct Image { int device; void *ctx; void *bed; };
+    std::vector<Image> images;            // the image on each device that has asked for it (bedImageOn)
+    int refs = 0;                         // HapData that point here; the last one released closes the file
+};
+// copies of the counted allele by counted[row] and PLINK code; -9 = missing
+inline short bedGenotype(unsigned counted, unsigned code)
+{
+    static const short T[3][4] = {{2, -9, 1, 0}, {0, -9, 1, 2}, {-9, -9, -9, -9}};
+    return T[counted][code];
+}
+
 struct HapData {           // src/garlic-data.h:32-38
     short **data;          // [locus][ind]: copies of the counted allele, -9 = missing
     int nind;
@@ -34,11 +62,20 @@ struct HapData {           // src/garlic-data.h:32-38
     // keepPacked.  `firstCopy` stays filled next to them for the host's readers; the engine uploads these rows as they are
     // (garlic_panel_set_phase_bits: an eighth of the bytes, no staging expansion).
     unsigned char **phaseBits;
+    // Extension: the genotypes are rows of a .bed file (loadBedData): `data` and `packed` are NULL, locus l is file row
+    // bedRow[l] of `bed`.  The site filters only edit bedRow; the engine fills its panels from the image on the device
+    // (garlic_panel_set_genotypes_bed).
+    BedFile *bed;
+    long long *bedRow;
 };
 inline bool hasPhase(const HapData *h) { return h->firstCopy || h->phaseBits; }
 inline short genotypeAt(const HapData *h, int locus, int ind)
 {
     if (h->data) return h->data[locus][ind];
+    if (h->bed) {
+        const long long r = h->bedRow[locus];
+        return bedGenotype(h->bed->counted[(size_t)r], (h->bed->rows[(size_t)r * h->bed->row_bytes + (ind >> 2)] >> (2 * (ind & 3))) & 3u);
+    }
     const unsigned code = (h->packed[locus][ind >> 2] >> (2 * (ind & 3))) & 3u;
     return code == 3u ? (short)-9 : (short)code;
 }
@@ -151,6 +188,20 @@ void loadTPEDData(const std::string &tpedfile, int &numLoci, int &numInd,
                   unsigned long long resampleSeed = 0);                          // garlic-data.cpp:10
 // nresample > 0 (--resample, garlic-data.cpp:142-148): binomial resampling of every frequency, one mt19937
 // stream in file order; resampleSeed 0 = time(NULL) as in the reference, else the stream GSL gives that seed
+// PLINK input.  openBedFile reads the .fam (already the TFAM format) for the individual count and the .bim
+// (chr snpid gpos ppos a1 a2; ppos is read as a double like the TPED's), maps the .bed and checks it: the magic bytes
+// 6c 1b 01 (anything else, the individual-major 6c 1b 00 included, is refused), its size against rows x individuals, alleles
+// of one character (GARLIC's alleles are single characters: a longer one is an error that names the line).  No GPU needed.
+BedFile *openBedFile(const std::string &bedfile, const std::string &bimfile, const std::string &famfile);
+void closeBedFile(BedFile *b);
+// The same (hap, map, freq) triple as loadTPEDData from a .bed/.bim/.fam: the rows go to `device` in chunks, the census there
+// (garlic_bed_census) finds every row's counted allele -- the first non-missing allele of the TPED line the row stands for,
+// on which a het reads "A1 A2" -- and the two integers of its frequency; the division is the host's, :141.  HapData::bed /
+// ::bedRow instead of ::data.  A .bed carries no phase.
+void loadBedData(const std::string &bedfile, const std::string &bimfile, const std::string &famfile, int &numLoci, int &numInd,
+                 std::vector<HapData *> **hapDataByChr, std::vector<MapData *> **mapDataByChr,
+                 std::vector<FreqData *> **freqDataByChr, int nresample = 0, unsigned long long resampleSeed = 0,
+                 int device = 0);
 void scanIndData3(const std::string &filename, int &numInd, std::string &popName);  // :1893
 IndData *readIndData3(const std::string &filename, int numInd);                     // :1963
 std::vector<GenoLikeData *> *readTGLSData(const std::string &filename, int expectedLoci, int expectedInd,

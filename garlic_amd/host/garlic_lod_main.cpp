@@ -8,6 +8,9 @@
 //   <out>.<W>SNPs.lod.sorted.f64           instead, with --sorted-feed: the same doubles ascending -- the array
 //                                          computeKDE's nrd0 makes of the feed first (gsl_sort, src/garlic-kde.cpp:132),
 //                                          sorted on the device
+// Input besides the reference's tped/tfam: a PLINK .bed/.bim/.fam (--bfile PREFIX, or --bed F --bim F --fam F).  The rows go
+// to the device as they are; the counted allele of every SNP and its frequency come from a census there, and the genotypes
+// never exist on the host as anything but the mapped file.
 // KDE / ROH assembly / GMM themselves stay in GARLIC (out of scope here).
 #include "garlic_host.hpp"
 
@@ -25,7 +28,7 @@ using namespace garlic_host;
 namespace {
 struct Args {
     std::string tped, tfam, out = "outfile", build = "none", centromere = "none", tgls = "none",
-                gl_type = "none", freq_file = "none", map = "none", cache = "none";
+                gl_type = "none", freq_file = "none", map = "none", cache = "none", bed, bim, fam, bfile;
     char tped_missing = '0';       // src/garlic-cli.cpp:114
     double error = -1;             // :34 (must be in (0,1) unless TGLS)
     int winsize = 0;               // :38
@@ -50,7 +53,8 @@ struct Args {
 [[noreturn]] void usage(const char *msg)
 {
     std::cerr << "ERROR: " << msg << "\n"
-              << "usage: garlic-lod --tped F --tfam F --out P (--build hg18|hg19|hg38 | --centromere F)\n"
+              << "usage: garlic-lod (--tped F --tfam F | --bfile PREFIX | --bed F --bim F --fam F) --out P\n"
+                 "         (--build hg18|hg19|hg38 | --centromere F)\n"
                  "         (--error E | --tgls F --gl-type GQ|GL|PL) (--winsize W | --winsize-multi W1 W2 ...)\n"
                  "         [--auto-winsize] [--auto-winsize-step N] [--winsize-stream] [--max-gap N] [--overlap-frac X]\n"
                  "         [--freq-file F] [--tped-missing C] [--raw-lod] [--kde-subsample N] [--kde-seed S] [--no-kde-thinning]\n"
@@ -58,7 +62,9 @@ struct Args {
                  "         [--resample N --resample-seed S] [--gpus N | --devices 0,1,...] [--genotype-cache F] [--tgls-term-gb X]\n"
                  "         (--tgls-term-gb X: at most X GB of TGLS terms per device, built and read in slabs; binds --weighted --tgls too)\n"
                  "         [--sorted-feed]   (the KDE feeds ascending, as nrd0's gsl_sort leaves them: <out>.<W>SNPs.lod.sorted.f64)\n"
-                 "         [--lod-cutoff X --size-bounds B1 B2 ... [--cm]]   (ROH calls: <out>.roh.bed)\n";
+                 "         [--lod-cutoff X --size-bounds B1 B2 ... [--cm]]   (ROH calls: <out>.roh.bed)\n"
+                 "         (--bfile / --bed --bim --fam: PLINK SNP-major .bed input, read on the device; not with --tped / --tfam /\n"
+                 "          --phased; --genotype-cache F is then written from the .bed, never read)\n";
     exit(1);
 }
 
@@ -70,6 +76,10 @@ Args parse(int argc, char **argv)
         auto val = [&]() -> std::string { if (i + 1 >= argc) usage(("missing value for " + f).c_str()); return argv[++i]; };
         if (f == "--tped") a.tped = val();
         else if (f == "--tfam") a.tfam = val();
+        else if (f == "--bfile") a.bfile = val();
+        else if (f == "--bed") a.bed = val();
+        else if (f == "--bim") a.bim = val();
+        else if (f == "--fam") a.fam = val();
         else if (f == "--out") a.out = val();
         else if (f == "--build") a.build = val();
         else if (f == "--centromere") a.centromere = val();
@@ -118,7 +128,16 @@ Args parse(int argc, char **argv)
         else usage(("unknown flag " + f).c_str());
     }
     // validators of src/garlic-cli.cpp:240-462 that concern Phase I
-    if (a.tped.empty() || a.tfam.empty()) usage("--tped and --tfam are required");
+    if (!a.bfile.empty()) {
+        if (!a.bed.empty() || !a.bim.empty() || !a.fam.empty()) usage("--bfile and --bed / --bim / --fam exclude each other");
+        a.bed = a.bfile + ".bed"; a.bim = a.bfile + ".bim"; a.fam = a.bfile + ".fam";
+    }
+    if (!a.bed.empty() || !a.bim.empty() || !a.fam.empty()) {
+        if (a.bed.empty() || a.bim.empty() || a.fam.empty()) usage("--bed, --bim and --fam go together");
+        if (!a.tped.empty() || !a.tfam.empty()) usage("--bfile / --bed and --tped / --tfam exclude each other");
+        if (a.phased) usage("--phased with --bfile: a .bed carries no phase");
+        a.tfam = a.fam;      // the .fam is the TFAM format
+    } else if (a.tped.empty() || a.tfam.empty()) usage("--tped and --tfam (or --bfile) are required");
     if (a.build == "none" && a.centromere == "none") usage("must provide --build or --centromere (garlic-cli.cpp:285-291)");
     if ((a.error <= 0 || a.error >= 1) && a.tgls == "none")
         usage("Genotype error rate must be > 0 and < 1, or a TGLS file must be provided.");
@@ -169,8 +188,18 @@ int main(int argc, char **argv)
                 if (gls) releaseGLData(gls);
             }
         } owner{haps, maps, freqs, gls, ind};
-        FILE *probe = a.cache == "none" ? nullptr : fopen(a.cache.c_str(), "rb");
-        if (probe) {   // parsed before: load the 2-bit sidecar instead of the text
+        std::vector<int> devices = a.devices;
+        if (devices.empty())
+            for (int d = 0; d < a.gpus; d++) devices.push_back(d);
+        FILE *probe = a.cache == "none" || !a.bed.empty() ? nullptr : fopen(a.cache.c_str(), "rb");
+        if (!a.bed.empty()) {   // PLINK input: census on the first device; the cache, if asked for, is written from it
+            loadBedData(a.bed, a.bim, a.fam, numLoci, numInd, &haps, &maps, &freqs, a.resample, a.resample_seed, devices[0]);
+            if (a.resample > 0) std::cerr << "Allele frequencies resampled: " << a.resample << "\n";
+            if (a.cache != "none") {
+                writeGenotypeCache(a.cache, haps, maps, freqs);
+                std::cerr << "Wrote genotype cache " << a.cache << "\n";
+            }
+        } else if (probe) {   // parsed before: load the 2-bit sidecar instead of the text
             fclose(probe);
             loadGenotypeCache(a.cache, numLoci, numInd, &haps, &maps, &freqs, /*keepPacked=*/true);
             std::cerr << "Loaded genotype cache " << a.cache << "\n";
@@ -223,10 +252,6 @@ int main(int argc, char **argv)
             kept = filterMonomorphicSites(&maps, &haps, &freqs, &gls, USE_GL);
         }
         std::cerr << "Filtered monomorphic" << (a.weighted ? " or out of bounds" : "") << " sites: " << kept << " loci kept\n";
-
-        std::vector<int> devices = a.devices;
-        if (devices.empty())
-            for (int d = 0; d < a.gpus; d++) devices.push_back(d);
 
         std::vector<int> sizes = a.winsize_multi.empty() ? std::vector<int>{a.winsize} : a.winsize_multi;
         if (a.tgls_term_gb != 0 || a.sorted_feed) {

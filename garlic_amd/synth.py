@@ -93,3 +93,44 @@ def genotype_chunks(spec, nind, device, chunk=65536, ind_offset=0, miss=0.01, tr
         m = torch.rand((l1 - l0, nind), generator=g, device=device, dtype=torch.float32) < miss
         geno = torch.where(m, torch.full_like(geno, -9), geno)
         yield l0, geno.contiguous()
+
+
+def bed_rows(codes, pad_bits=0):
+    """PLINK codes (uint8 [nrows][nind]: 0 hom A1, 1 missing, 2 het, 3 hom A2) -> .bed rows, uint8 [nrows][(nind + 3) // 4],
+    individual j at bits 2 * (j % 4) of byte j // 4; the unused bits of the last byte take those of pad_bits."""
+    codes = np.asarray(codes, dtype=np.uint8)
+    nrows, nind = codes.shape
+    rb = (nind + 3) // 4
+    padded = np.empty((nrows, 4 * rb), dtype=np.uint8)
+    padded[:, :nind] = codes
+    for k in range(nind, 4 * rb):
+        padded[:, k] = (pad_bits >> (2 * (k % 4))) & 3
+    q = padded.reshape(nrows, rb, 4)
+    return (q[:, :, 0] | (q[:, :, 1] << 2) | (q[:, :, 2] << 4) | (q[:, :, 3] << 6)).astype(np.uint8)
+
+
+def write_bed_and_tped(prefix, codes, chrs, pos, a1="A", a2="G", gpos=None, names=None, pop="POP", pad_bits=0):
+    """One genotype matrix as PLINK .bed/.bim/.fam and as the twin .tped/.tfam.  codes: PLINK codes [nrows][nind] (see
+    bed_rows); chrs / pos: chromosome string and physical position per row; a1 / a2: one character each, or a list per row.
+    The TPED line of a row reads "A1 A1" for hom A1, "A1 A2" for a het, "A2 A2" for hom A2 and "0 0" for missing -- the
+    convention under which the bed reader's counted allele is GARLIC's first non-missing allele of the line."""
+    codes = np.asarray(codes, dtype=np.uint8)
+    nrows, nind = codes.shape
+    a1 = [a1] * nrows if isinstance(a1, str) else list(a1)
+    a2 = [a2] * nrows if isinstance(a2, str) else list(a2)
+    gpos = np.zeros(nrows) if gpos is None else np.asarray(gpos, dtype=np.float64)
+    names = ["rs%d" % r for r in range(nrows)] if names is None else list(names)
+    with open(prefix + ".bed", "wb") as f:
+        f.write(bytes([0x6C, 0x1B, 0x01]))
+        f.write(bed_rows(codes, pad_bits).tobytes())
+    with open(prefix + ".bim", "w") as f:
+        for r in range(nrows):
+            f.write("%s\t%s\t%.10g\t%d\t%s\t%s\n" % (chrs[r], names[r], gpos[r], pos[r], a1[r], a2[r]))
+    fam = "".join("%s ind%d 0 0 0 -9\n" % (pop, i) for i in range(nind))
+    for ext in (".fam", ".tfam"):
+        with open(prefix + ext, "w") as f:
+            f.write(fam)
+    with open(prefix + ".tped", "w") as f:
+        for r in range(nrows):
+            pair = ["%s %s" % (a1[r], a1[r]), "0 0", "%s %s" % (a1[r], a2[r]), "%s %s" % (a2[r], a2[r])]
+            f.write("%s %s %.10g %d %s\n" % (chrs[r], names[r], gpos[r], pos[r], " ".join(pair[c] for c in codes[r])))

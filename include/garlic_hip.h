@@ -51,7 +51,8 @@ extern "C" {
  *    garlic_lod_feed_multi_info, GARLIC_FEED_TGLS_CHAIN_SHARED (likewise); garlic_panel_compute_ld_multi,
  *    garlic_ld_finish_multi, garlic_panel_ld_info (likewise); garlic_panel_set_feed_order, garlic_feed_sort,
  *    garlic_feed_sort_info, GARLIC_FEED_ORDER_* (likewise); garlic_panel_set_phase_bits, garlic_panel_ld_form_info,
- *    GARLIC_LD_PAIR_* / GARLIC_LD_SUM_* (likewise); garlic_panel_set_gl_codes16, GARLIC_TGLS_DICTIONARY16 (likewise) */
+ *    GARLIC_LD_PAIR_* / GARLIC_LD_SUM_* (likewise); garlic_panel_set_gl_codes16, GARLIC_TGLS_DICTIONARY16 (likewise);
+ *    garlic_bed_create, garlic_bed_set_rows, garlic_bed_census, garlic_bed_destroy, garlic_panel_set_genotypes_bed (likewise) */
 #define GARLIC_HIP_ABI_VERSION 8
 
 #define GARLIC_OK 0
@@ -129,6 +130,41 @@ int garlic_panel_set_genotypes(garlic_panel *panel, const int16_t *geno, int64_t
 int garlic_panel_set_genotypes_2bit(garlic_panel *panel, const uint8_t *rows, int64_t row_bytes,
                                     int64_t ind_offset, int64_t locus_begin, int64_t locus_count,
                                     int32_t where);
+
+/* PLINK .bed input.  A garlic_bed is the SNP-major .bed image of a data set on the context's device: nrows rows of
+ * (nind_total + 3) / 4 bytes, individual j of a row at bits 2 * (j % 4) of byte j / 4, in PLINK's codes 00 hom A1,
+ * 01 missing, 10 het, 11 hom A2; the bits past individual nind_total - 1 are ignored, whatever they hold.  (The three magic
+ * bytes 6c 1b 01 of the file are the caller's to check and skip.)  1 <= nrows < 2^31, 1 <= nind_total < 2^30 (the counts are
+ * int32).  Calls on one image, like calls on one context, must not overlap in time; panels of several contexts on the image's
+ * device may fill from it one after the other.
+ *   garlic_bed_set_rows  rows [row_begin, row_begin + row_count) from `rows`, row_bytes apart (>= (nind_total + 3) / 4:
+ *                        padded sources are fine; no alignment is asked for); host or device memory; in as many calls as
+ *                        the caller likes, a row may be set again.
+ *   garlic_bed_census    per row, GARLIC's counted allele -- "the first non-missing allele on the line"
+ *                        (src/garlic-data.cpp:107-113) of the TPED line the row stands for, on which a hom A1 genotype reads
+ *                        "A1 A1", a het "A1 A2" and a hom A2 "A2 A2": A2 when the first non-missing genotype in file order is
+ *                        hom A2, A1 otherwise, none when every genotype is missing -- as counted[r] = 0 (A1), 1 (A2), 2
+ *                        (none), and counts[r] = {nalleles, total} = {2 * #hom(counted) + #het, 2 * #non-missing} ({0, 0}
+ *                        for none), the two integers of the reference's frequency double(nalleles) / double(total) (:141).
+ *                        GARLIC_ERR_STATE until every row has been set.  Computed once per image content and kept with it;
+ *                        either output may be NULL.
+ *   garlic_panel_set_genotypes_bed   recodes rows of the image into the panel (copies of the row's counted allele 0 / 1 / 2,
+ *                        missing 3; a row whose counted allele is none: all 3): dest_locus[r] (host array, nrows entries) is
+ *                        the panel's global locus for file row r, or -1 for a row the caller's site filters dropped.  The
+ *                        destinations of the kept rows must be strictly ascending (GARLIC_ERR_INVALID otherwise) and need not
+ *                        be consecutive; loci no row maps to keep their previous bits.  The panel's individual i is individual
+ *                        ind_offset + i of the row (a shard's column block).  The panel's context must be on the image's
+ *                        device.  Runs the census first when it has not been run.  Otherwise the effect of
+ *                        garlic_panel_set_genotypes_2bit. */
+typedef struct garlic_bed garlic_bed;
+int garlic_bed_create(garlic_ctx *ctx, int64_t nrows, int32_t nind_total, garlic_bed **bed);
+int garlic_bed_set_rows(garlic_bed *bed, const uint8_t *rows, int64_t row_bytes, int64_t row_begin, int64_t row_count,
+                        int32_t where);
+int garlic_bed_census(garlic_bed *bed, int32_t *counts /* [nrows][2]: nalleles, total */, uint8_t *counted /* [nrows] */,
+                      int32_t where);
+int garlic_panel_set_genotypes_bed(garlic_panel *panel, garlic_bed *bed, int64_t ind_offset,
+                                   const int64_t *dest_locus /* [nrows] */);
+int garlic_bed_destroy(garlic_bed *bed);
 
 /* GenoLikeData::data (src/garlic-data.h:91): per-genotype error probabilities, already converted
  * as readTGLSData does (src/garlic-data.cpp:1557-1576); same addressing as genotypes.  Any doubles.

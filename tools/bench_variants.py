@@ -27,6 +27,9 @@ resident panel: the unweighted feed (step = winsize) of --kde-inds individuals (
 everyone -- the device sort alone by HIP events, its bytes per second at 24 B x keys x passes run, the whole feed call in
 both orders, and on the same data one thread of std::sort and numpy's sort on the host, as stand-ins for gsl_sort
 (profiles/feed_sort_ab.txt).
+--modes bed_ingest: PLINK .bed input -- the census and the pack of a panel cut from a --file-inds file by HIP events with the bytes
+each moves, and with --bed-prefix the whole garlic-lod run from .bed, TPED and genotype cache (--tree: the latter two with the
+parent's tool); shapes 2M x 1280 and 10M x 1250 of a 10k-individual file; the table goes to profiles/bed_ingest_ab.txt.
 --modes ld_phased: the warm garlic_panel_compute_ld(phased = 1) call (weights only) for every size of --winsizes on one resident
 panel -- host clock around the synchronous call and the ordered-sum kernel by the library's HIP events, median and spread
 of --steps calls -- with the form the call took where the library reports it; and the phase upload from host memory both
@@ -202,6 +205,95 @@ def tgls_dict16_leg(args):
             "checksum": float(out[base[0]: base[0] + nloci].nan_to_num(0.0, 0.0, 0.0).sum().item())}
     if hasattr(panel, "tgls_terms_info"):
         line["terms_info"] = panel.tgls_terms_info()
+    print(json.dumps(line), flush=True)
+
+
+def bed_ingest_leg(args):
+    """PLINK .bed input on one device.  The image's rows are random bytes made on the device (a file of --file-inds
+    individuals, --snps rows); the context runs on a torch stream, so torch's events (HIP events) bracket the census call (the
+    kernel and the read-back of 9 bytes per row) and the pack call (the upload of the per-word row list, 4 bytes per locus, and
+    the kernel) of a panel of --inds individuals cut at --ind-offset.  With --bed-prefix P (P.bed / P.bim / P.fam, and the twins
+    P.tped / P.tfam if present: garlic_amd.synth.write_bed_and_tped writes them) also the whole garlic-lod run -- load, census,
+    upload, one feed -- from the .bed, from the TPED and from a genotype cache written by the first of them; --tree DIR runs
+    the TPED and cache legs with another checkout's tool (the parent commit)."""
+    import subprocess
+    import tempfile
+    import time
+    import torch
+    from garlic_amd import abi, synth
+
+    torch.cuda.set_device(0)
+    dev = torch.device("cuda", 0)
+    nloci, nind, nfile = args.snps, args.inds, max(args.file_inds, args.inds + args.ind_offset)
+    rb = (nfile + 3) // 4
+    spec = synth.PanelSpec(nloci, seed=20260105)
+    stream = torch.cuda.Stream()
+    ctx = abi.Context(0, stream=stream.cuda_stream)
+    bed = abi.Bed(ctx, nloci, nfile)
+    g = torch.Generator(device=dev)
+    g.manual_seed(5)
+    chunk = max(1, (256 << 20) // rb)
+    for r in range(0, nloci, chunk):
+        rows = torch.randint(0, 256, (min(chunk, nloci - r), rb), generator=g, device=dev, dtype=torch.uint8)
+        torch.cuda.synchronize()
+        bed.set_rows_device(rows.data_ptr(), rb, r, rows.shape[0])
+    first = rows[:1].clone()
+    del rows
+    panel = abi.Panel(ctx, spec.chr_nloci, nind)
+    dest = np.arange(nloci, dtype=np.int64)
+
+    def timed(fn):
+        ms = []
+        for k in range(1 + args.steps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            fn()
+            e1.record(stream)
+            torch.cuda.synchronize()
+            if k:
+                ms.append(e0.elapsed_time(e1))
+        return float(np.median(ms))
+
+    def census():
+        bed.set_rows_device(first.data_ptr(), rb, nloci - 1, 1)      # the same bytes again: the cached census is dropped
+        bed.census()
+
+    census_ms = timed(census)
+    pack_ms = timed(lambda: panel.set_genotypes_bed(bed, dest, args.ind_offset))
+    nblk = (nind + 126) // 64          # the panel's 64-individual blocks, its pad block included (nind_pad / 64): all are written
+    line = {"mode": "bed_ingest", "snps": nloci, "inds": nind, "file_inds": nfile, "ind_offset": args.ind_offset,
+            "repeats": args.steps, "census_call_ms_median_kernel_plus_9B_per_row_readback": census_ms, "census_image_bytes": nloci * rb,
+            "census_GBps": nloci * rb / (census_ms * 1e-3) / 1e9, "pack_call_ms_median_row_list_upload_plus_kernel": pack_ms,
+            "pack_genotype_bytes_of_the_column_block": nloci * ((nind + 3) // 4),
+            "pack_bytes_fetched_upper_bound_with_16B_piece_overhead": nloci * ((nind + 3) // 4 + 31 * ((nblk + 63) // 64)),
+            "pack_bytes_written_all_blocks": ((nloci + 15) // 16) * nblk * 256,
+            "pack_row_list_bytes": 4 * nloci}
+    panel.close()
+    bed.destroy()
+    if args.bed_prefix:
+        P = args.bed_prefix
+        tmp = tempfile.mkdtemp()
+        cen = os.path.join(tmp, "centromeres.txt")
+        with open(P + ".bim") as f, open(cen, "w") as c:
+            for name in dict.fromkeys(l.split(None, 1)[0] for l in f):
+                c.write("%s 0 0\n" % name)
+        mine = os.path.join(ROOT, "garlic_amd", "host", "garlic-lod")
+        other = os.path.join(args.tree, "garlic_amd", "host", "garlic-lod") if args.tree else mine
+        common = ["--centromere", cen, "--error", "0.001", "--winsize", str(args.winsize), "--kde-subsample", "0"]
+
+        def wall(tool, inputs, tag):
+            t0 = time.perf_counter()
+            subprocess.check_call([tool, *inputs, "--out", os.path.join(tmp, tag), *common], stderr=subprocess.DEVNULL)
+            return time.perf_counter() - t0
+
+        line["tool_bfile_load_census_upload_one_feed_s"] = wall(mine, ["--bfile", P], "bed")
+        if os.path.exists(P + ".tped"):
+            cache = os.path.join(tmp, "twin.g2b")
+            twin = ["--tped", P + ".tped", "--tfam", P + ".tfam"]
+            line["tool_tped_load_upload_one_feed_s"] = wall(other, twin, "tped")
+            line["tool_tped_load_cache_write_upload_one_feed_s"] = wall(other, twin + ["--genotype-cache", cache], "tpedc")
+            line["tool_cache_load_upload_one_feed_s"] = wall(other, twin + ["--genotype-cache", cache], "cache")
+            line["tped_and_cache_tool"] = other
     print(json.dumps(line), flush=True)
 
 
@@ -590,9 +682,12 @@ def main():
     ap.add_argument("--term-budget-gb", type=float, default=0.0, help="tgls_dict16: garlic_panel_set_tgls_term_budget (GB; < 0: -1)")
     ap.add_argument("--cutoff", type=float, default=2.5, help="tgls_slabs: the LOD cutoff of the segments call")
     ap.add_argument("--kde-inds", type=int, default=20, help="feed_sort: individuals of the subsampled feed (--kde-subsample)")
+    ap.add_argument("--file-inds", type=int, default=10000, help="bed_ingest: individuals of the .bed file the panel is cut from")
+    ap.add_argument("--ind-offset", type=int, default=0, help="bed_ingest: the panel's first individual in the file")
+    ap.add_argument("--bed-prefix", default="", help="bed_ingest: P.bed / P.bim / P.fam (and P.tped / P.tfam) for the whole-tool legs")
     ap.add_argument("--tree", default="", help="take garlic_amd from this checkout instead of the one the tool is in")
     args = ap.parse_args()
-    if args.tree:
+    if args.tree and args.modes != "bed_ingest":      # (bed_ingest: --tree names the tool of its TPED and cache legs only)
         sys.path.insert(0, os.path.abspath(args.tree))
     if args.modes == "tgls_slabs":
         return tgls_slabs_leg(args)
@@ -602,6 +697,8 @@ def main():
         return ld_multi_leg(args)
     if args.modes == "feed_sort":
         return feed_sort_leg(args)
+    if args.modes == "bed_ingest":
+        return bed_ingest_leg(args)
     if args.modes == "ld_phased":
         return ld_phased_leg(args)
     if args.modes == "tgls_dict16":
