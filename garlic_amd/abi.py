@@ -45,7 +45,9 @@ SYMBOLS = [
     "garlic_panel_set_phase_bits", "garlic_panel_ld_form_info",
     "garlic_panel_set_gl_codes16",
     "garlic_bed_create", "garlic_bed_set_rows", "garlic_bed_census", "garlic_bed_destroy", "garlic_panel_set_genotypes_bed",
+    "garlic_feed_kde", "garlic_lod_kde", "garlic_feed_kde_info", "garlic_feed_kde_times",
 ]
+KDE_POINTS = 512   # GARLIC_KDE_POINTS
 
 
 class CallStats(C.Structure):
@@ -53,6 +55,19 @@ class CallStats(C.Structure):
                 ("n_valid_windows", C.c_int64), ("n_missing", C.c_int64),
                 ("chain_kernel_ms", C.c_float), ("total_ms", C.c_float),
                 ("n_stall_reruns", C.c_int64), ("n_count_timeouts", C.c_int64)]
+
+
+class Kde(C.Structure):
+    """garlic_kde"""
+    _fields_ = [("n", C.c_int64), ("h", C.c_double), ("sd", C.c_double), ("q25", C.c_double), ("q75", C.c_double),
+                ("lo", C.c_double), ("hi", C.c_double), ("x", C.c_double * KDE_POINTS), ("y", C.c_double * KDE_POINTS),
+                ("raw", C.c_double * KDE_POINTS)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k in ("n", "h", "sd", "q25", "q75", "lo", "hi")}
+        for k in ("x", "y", "raw"):
+            d[k] = np.array(getattr(self, k), dtype=np.float64)
+        return d
 
 
 class GarlicError(RuntimeError):
@@ -147,6 +162,11 @@ def lib():
     L.garlic_panel_ld_form_info.argtypes = [_vp, _i32p, _i32p, _i32p, _i32p]
     L.garlic_feed_sort.argtypes = [_vp, _vp, C.c_int64, C.c_int32]
     L.garlic_feed_sort_info.argtypes = [_vp, _i32p, _i32p, _i64p]
+    L.garlic_feed_kde.argtypes = [_vp, _vp, C.c_int64, C.c_int32, C.POINTER(Kde)]
+    L.garlic_lod_kde.argtypes = [_vp, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32,
+                                 _i32p, C.c_int32, C.POINTER(Kde), _i64p]
+    L.garlic_feed_kde_info.argtypes = [_vp, _i64p, _i64p, _i64p]
+    L.garlic_feed_kde_times.argtypes = [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.garlic_bed_create.argtypes = [_vp, C.c_int64, C.c_int32, C.POINTER(_vp)]
     L.garlic_bed_set_rows.argtypes = [_vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32]
     L.garlic_bed_census.argtypes = [_vp, _vp, _vp, C.c_int32]
@@ -222,6 +242,32 @@ class Context:
         run, skipped, nbytes = C.c_int32(), C.c_int32(), C.c_int64()
         check(lib().garlic_feed_sort_info(self.handle, C.byref(run), C.byref(skipped), C.byref(nbytes)))
         return {"passes_run": run.value, "passes_skipped": skipped.value, "scratch_bytes": nbytes.value}
+
+    def feed_kde(self, values, n=None, out=None):
+        """garlic_feed_kde: computeKDE's bandwidth, targets and density of an ascending feed, as a dict: n, h, sd, q25,
+        q75, lo, hi and the float64 arrays x, y, raw [512].  values: a contiguous float64 numpy array (host; n defaults to
+        its length) or a device address (int) of n doubles.  out: an abi.Kde to fill instead (returned as it is)."""
+        k = Kde() if out is None else out
+        if isinstance(values, np.ndarray):
+            assert values.dtype == np.float64 and values.flags["C_CONTIGUOUS"] and values.ndim == 1
+            n = values.shape[0] if n is None else int(n)
+            assert n <= values.shape[0]
+            check(lib().garlic_feed_kde(self.handle, _vp(values.ctypes.data), n, HOST, C.byref(k)))
+        else:
+            check(lib().garlic_feed_kde(self.handle, _vp(values) if values else None, int(n), DEVICE, C.byref(k)))
+        return k.as_dict() if out is None else out
+
+    def feed_kde_info(self):
+        """garlic_feed_kde_info: {chunks, pairs_skipped, scratch_bytes} of the last KDE on this context"""
+        a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+        check(lib().garlic_feed_kde_info(self.handle, C.byref(a), C.byref(b), C.byref(c)))
+        return {"chunks": a.value, "pairs_skipped": b.value, "scratch_bytes": c.value}
+
+    def feed_kde_times(self):
+        """garlic_feed_kde_times: {moments_ms, sums_ms}, HIP-event times of the last KDE's kernels on this context"""
+        a, b = C.c_float(), C.c_float()
+        check(lib().garlic_feed_kde_times(self.handle, C.byref(a), C.byref(b)))
+        return {"moments_ms": a.value, "sums_ms": b.value}
 
     def close(self):
         if self.handle:
@@ -411,10 +457,13 @@ class Panel:
         check(lib().garlic_panel_set_gl_codes16(self.handle, _vp(codes.ctypes.data), codes.shape[1], locus_begin,
                                                 codes.shape[0], _vp(values.ctypes.data), values.shape[0], HOST))
 
+    feed_order = FEED_ORDER_REFERENCE   # what set_feed_order set last (the library has no getter)
+
     def set_feed_order(self, order):
         """garlic_panel_set_feed_order: FEED_ORDER_REFERENCE (chromosome -> individual -> locus, the default) or
         FEED_ORDER_SORTED (every feed call returns its values ascending, sorted on the device)"""
         check(lib().garlic_panel_set_feed_order(self.handle, int(order)))
+        self.feed_order = int(order)
 
     def release_scratch(self):
         """free the device scratch the panel keeps between calls (LD buffers, score / feed scratch)"""
@@ -639,6 +688,16 @@ class Panel:
                                            step, _ptr(idx, _i32p), 0 if idx is None else n_rows,
                                            _vp(feed.ctypes.data), cap, C.byref(n), _ptr(per_chr, _i64p)))
         return (feed[: n.value].copy() if copy else feed[: n.value]), per_chr
+
+    def lod_kde(self, winsize, error, max_gap, step, use_gl=False, weighted=False, M=7, mu=1e-9, ind_idx=None):
+        """garlic_lod_kde: lod_feed's arguments; the feed is sorted and reduced to its KDE on the device.  Returns
+        (the dict of Context.feed_kde, per-chromosome counts)."""
+        idx = None if ind_idx is None else np.ascontiguousarray(ind_idx, dtype=np.int32)
+        k = Kde()
+        per_chr = np.zeros(self.nchr, dtype=np.int64)
+        check(lib().garlic_lod_kde(self.handle, winsize, error, max_gap, int(use_gl), int(weighted), M, mu, step,
+                                   _ptr(idx, _i32p), 0 if idx is None else int(idx.shape[0]), C.byref(k), _ptr(per_chr, _i64p)))
+        return k.as_dict(), per_chr
 
     def lod_feed_multi(self, winsizes, error, max_gap, steps=None, ind_idx=None, copy=True):
         """garlic_lod_feed_multi: the feeds of several window sizes in one call (unweighted --error scores; steps

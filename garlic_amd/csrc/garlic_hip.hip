@@ -21,6 +21,8 @@
 #include "feed_kernel.hpp"
 #include "wlod_feed_kernel.hpp"
 #include "feed_sort_kernel.hpp"
+#include "kde_kernels.hpp"
+#include "../host/kde_select.hpp"
 #include "bed_kernels.hpp"
 
 #include <algorithm>
@@ -125,6 +127,31 @@ struct FeedSortScratch {
     void release() { keys.release(); stage.release(); tiles.release(); table.release(); }
 };
 
+// what garlic_feed_kde keeps between calls (kde_kernels.hpp): per-chunk partials and flags, per-slice sums, the targets
+struct KdeScratch {
+    DevBuf<double> stage;                          // the values of a host-buffer call
+    DevBuf<double> partial, slices, targets, raw;
+    DevBuf<int32_t> flags;
+    DevBuf<KdeMoments> mom;
+    DevBuf<unsigned long long> skipped;
+    hipEvent_t ev[4] = {};                         // around the moments kernels and around the sums kernels (garlic_feed_kde_times)
+    size_t bytes() const
+    {
+        return (stage.cap + partial.cap + slices.cap + targets.cap + raw.cap) * sizeof(double) + flags.cap * sizeof(int32_t) +
+               mom.cap * sizeof(KdeMoments) + skipped.cap * sizeof(unsigned long long);
+    }
+    void release()
+    {
+        stage.release(); partial.release(); slices.release(); targets.release(); raw.release(); flags.release();
+        mom.release(); skipped.release();
+        for (auto &e : ev) {
+            if (e) (void)hipEventDestroy(e);
+            e = nullptr;
+        }
+    }
+    ~KdeScratch() { release(); }
+};
+
 // lod(), src/garlic-roh.cpp:355-386.  Host arithmetic, host libm: identical to the reference.
 double host_lod(int genotype, double freq, double error)
 {
@@ -185,6 +212,10 @@ struct garlic_ctx {
     FeedSortScratch fs;
     int32_t fs_run = 0, fs_skipped = 0;
     int64_t fs_scratch_bytes = 0;
+    // garlic_feed_kde: its scratch, and what garlic_feed_kde_info reports
+    KdeScratch kde;
+    int64_t kde_chunks = 0, kde_skipped = 0;
+    float kde_moments_ms = 0.f, kde_sums_ms = 0.f;
 };
 
 static int score_alloc(garlic_ctx *ctx, size_t bytes, void **out);   // pooled score memory (below)
@@ -378,6 +409,8 @@ struct garlic_panel {
     DevBuf<double> d_feed;
     int32_t feed_order = GARLIC_FEED_ORDER_REFERENCE;   // garlic_panel_set_feed_order
     FeedSortScratch fs;                            // ... SORTED: the sorter's scratch of the single-size feed calls
+    // garlic_lod_kde: set around its feed call -- the feed is sorted and stays on the device, where and how many is noted here
+    struct FeedSink { const double *data = nullptr; int64_t n = 0; } *feed_sink = nullptr;
     // garlic_lod_feed_multi: one set of scratch and one stream per window size of the call, kept for the next call
     struct FeedSlot {
         hipStream_t stream = nullptr;
@@ -4055,7 +4088,7 @@ int garlic_panel_release_scratch(garlic_panel *p)
     p->lds.release();
     p->d_out.release(); p->d_feed.release();
     p->d_stage16.release(); p->d_stage64.release(); p->d_bed_word_rows.release();
-    p->fs.release(); p->ctx->fs.release();
+    p->fs.release(); p->ctx->fs.release(); p->ctx->kde.release();
     for (auto *sl : p->feed_slots) {
         HIP_TRY(hipStreamSynchronize(sl->stream));
         sl->fs.release();
@@ -4292,11 +4325,16 @@ static int feed_single(garlic_panel *p, int32_t winsize, double error, int32_t m
                            ind_idx ? d_list.p : nullptr, n_idx)))
         return rc;
     if (*count > feed_capacity || *count == 0) return GARLIC_OK;
-    if (!feed) return fail(GARLIC_ERR_INVALID, "feed is NULL");
+    if (!feed && !p->feed_sink) return fail(GARLIC_ERR_INVALID, "feed is NULL");
     const double *from = d_feed.p;
-    if (p->feed_order == GARLIC_FEED_ORDER_SORTED && *count > 1) {
+    if ((p->feed_order == GARLIC_FEED_ORDER_SORTED || p->feed_sink) && *count > 1) {
         if ((rc = sort_feed(p->ctx, p->ctx->stream, d_feed.p, *count, p->fs, false))) return rc;
         if ((rc = sort_result(p->ctx, p->ctx->stream, d_feed.p, p->fs, &from))) return rc;
+    }
+    if (p->feed_sink) {                            // garlic_lod_kde reads it where it lies
+        p->feed_sink->data = from;
+        p->feed_sink->n = *count;
+        return GARLIC_OK;
     }
     hipError_t e = hipMemcpy(feed, from, sizeof(double) * (size_t)*count, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(GARLIC_ERR_HIP, "feed copy-out: %s", hipGetErrorString(e));
@@ -4407,7 +4445,7 @@ int garlic_lod_feed_multi(garlic_panel *p, const int32_t *winsizes, const int32_
         hipError_t e_ = (expr);                                                                     \
         if (e_ != hipSuccess) return done(fail(GARLIC_ERR_HIP, "feed: %s: %s", #expr, hipGetErrorString(e_))); \
     } while (0)
-    const bool sorted = p->feed_order == GARLIC_FEED_ORDER_SORTED;
+    const bool sorted = p->feed_order == GARLIC_FEED_ORDER_SORTED || p->feed_sink;
     if (ind_idx) {
         blocks.assign((size_t)nblk, 0);
         row_map.assign((size_t)p->nind, -1);
@@ -4461,7 +4499,7 @@ int garlic_lod_feed_multi(garlic_panel *p, const int32_t *winsizes, const int32_
         n_items[(size_t)i] = items.size();
         if (off > feed_capacity[i] || off == 0) { n_items[(size_t)i] = 0; continue; }
         if (!items.empty() && (rc = feed_grid(ctx, items, &grids[(size_t)i], nullptr))) return done(rc);
-        if (!feeds[i]) return done(fail(GARLIC_ERR_INVALID, "feed %d is NULL", i));
+        if (!feeds[i] && !p->feed_sink) return done(fail(GARLIC_ERR_INVALID, "feed %d is NULL", i));
         if ((rc = sl.items.reserve(std::max<size_t>(items.size(), 1)))) return done(rc);
         if ((rc = sl.chrs.reserve((size_t)p->nchr))) return done(rc);
         if ((rc = sl.counter.reserve(4))) return done(rc);
@@ -4495,6 +4533,11 @@ int garlic_lod_feed_multi(garlic_panel *p, const int32_t *winsizes, const int32_
         if (!n_items[(size_t)i]) continue;
         const double *from = sl.feed.p;
         if (sorted && total[(size_t)i] > 1 && (rc = sort_result(ctx, sl.stream, sl.feed.p, sl.fs, &from))) return done(rc);
+        if (p->feed_sink) {                        // garlic_lod_kde (one size): the feed stays in the slot's buffer
+            p->feed_sink->data = from;
+            p->feed_sink->n = total[(size_t)i];
+            continue;
+        }
         FEED_TRY(hipMemcpyAsync(feeds[i], from, sizeof(double) * (size_t)total[(size_t)i], hipMemcpyDeviceToHost, sl.stream));
     }
     float ms_sum = 0.f;
@@ -5519,6 +5562,135 @@ int garlic_feed_sort_info(garlic_ctx *ctx, int32_t *passes_run, int32_t *passes_
     if (passes_skipped) *passes_skipped = ctx->fs_skipped;
     if (scratch_bytes) *scratch_bytes = ctx->fs_scratch_bytes;
     return GARLIC_OK;
+}
+
+// ---- computeKDE on the device (kde_kernels.hpp; host arithmetic: host/kde_select.hpp).  d_x: n >= 2 device doubles.
+static int kde_reserve(garlic_ctx *ctx, int64_t n, bool stage)
+{
+    const int64_t n_chunks = (n + KDE_CHUNK - 1) / KDE_CHUNK;
+    if (n_chunks > 0x7fffffff) return fail(GARLIC_ERR_INVALID, "feed KDE: %lld values are more chunks than one launch holds", (long long)n);
+    const int64_t cps = kde_chunks_per_slice(n_chunks), n_slices = (n_chunks + cps - 1) / cps;
+    KdeScratch &k = ctx->kde;
+    int rc;
+    if ((stage && (rc = k.stage.reserve((size_t)n))) || (rc = k.partial.reserve((size_t)n_chunks)) ||
+        (rc = k.flags.reserve((size_t)n_chunks)) || (rc = k.slices.reserve((size_t)n_slices * KDE_POINTS)) ||
+        (rc = k.targets.reserve(KDE_POINTS)) || (rc = k.raw.reserve(KDE_POINTS)) || (rc = k.mom.reserve(1)) ||
+        (rc = k.skipped.reserve(1)))
+        return rc;
+    for (auto &e : k.ev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    return GARLIC_OK;
+}
+
+static int kde_device(garlic_ctx *ctx, const double *d_x, int64_t n, garlic_kde *out)
+{
+    namespace gh = garlic_host;
+    static_assert(KDE_POINTS == GARLIC_KDE_POINTS && gh::KDE_POINTS == GARLIC_KDE_POINTS, "one M");
+    int rc;
+    if ((rc = kde_reserve(ctx, n, false))) return rc;
+    hipStream_t s = ctx->stream;
+    KdeScratch &k = ctx->kde;
+    const int64_t n_chunks = (n + KDE_CHUNK - 1) / KDE_CHUNK;
+    const int64_t cps = kde_chunks_per_slice(n_chunks), n_slices = (n_chunks + cps - 1) / cps;
+    KdeIdx idx;
+    double delta25, delta75;
+    idx.at[0] = 0;
+    idx.at[1] = n - 1;
+    gh::kdeQuantileIndex(n, 0.25, &idx.at[2], &delta25);
+    gh::kdeQuantileIndex(n, 0.75, &idx.at[4], &delta75);
+    idx.at[3] = idx.at[2] + 1;
+    idx.at[5] = idx.at[4] + 1;
+    HIP_TRY(hipEventRecord(k.ev[0], s));
+    for (int pass = 0; pass < 2; pass++) {
+        hipLaunchKernelGGL(kde_moment_kernel, dim3((unsigned)n_chunks), dim3(KDE_THREADS), 0, s, d_x, n, pass, k.mom.p, k.partial.p, k.flags.p);
+        hipLaunchKernelGGL(kde_tree_kernel, dim3(1), dim3(KDE_THREADS), 0, s, d_x, n, n_chunks, pass, k.partial.p, k.flags.p, idx, k.mom.p);
+    }
+    HIP_TRY(hipEventRecord(k.ev[1], s));
+    HIP_TRY(hipGetLastError());
+    KdeMoments mom;
+    HIP_TRY(hipMemcpyAsync(&mom, k.mom.p, sizeof mom, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (mom.flags & KDE_FLAG_NOT_FINITE) return fail(GARLIC_ERR_INVALID, "feed KDE: the values hold a NaN or an infinity");
+    if (mom.flags & KDE_FLAG_NOT_ASCENDING) return fail(GARLIC_ERR_INVALID, "feed KDE: the values are not in ascending order (garlic_feed_sort)");
+    garlic_kde r;
+    r.n = n;
+    r.lo = mom.stat[0];
+    r.hi = mom.stat[1];
+    r.sd = sqrt(mom.ssq / (double)(n - 1));
+    r.q25 = idx.at[2] >= n - 1 ? mom.stat[2] : gh::kdeQuantileMix(mom.stat[2], mom.stat[3], delta25);
+    r.q75 = idx.at[4] >= n - 1 ? mom.stat[4] : gh::kdeQuantileMix(mom.stat[4], mom.stat[5], delta75);
+    r.h = gh::kdeBandwidth(r.sd, r.q25, r.q75, n);
+    if (!(r.h > 0) || !std::isfinite(r.h))
+        return fail(GARLIC_ERR_INVALID, "feed KDE: bandwidth %g (sd %g, quartiles %g and %g): all values equal, or no spread between the quartiles",
+                    r.h, r.sd, r.q25, r.q75);
+    gh::kdeTargets(r.lo, r.hi, r.h, r.x);
+    const double inv_h2 = 1.0 / (r.h * r.h);
+    if (!std::isfinite(inv_h2)) return fail(GARLIC_ERR_INVALID, "feed KDE: bandwidth %g is too small to square", r.h);
+    HIP_TRY(hipMemcpyAsync(k.targets.p, r.x, sizeof r.x, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(k.skipped.p, 0, sizeof(unsigned long long), s));
+    HIP_TRY(hipEventRecord(k.ev[2], s));
+    hipLaunchKernelGGL(kde_sum_kernel, dim3((unsigned)n_slices), dim3(KDE_THREADS), 0, s, d_x, n, n_chunks, cps, k.targets.p, inv_h2,
+                       k.slices.p, k.skipped.p);
+    hipLaunchKernelGGL(kde_slice_kernel, dim3(KDE_POINTS), dim3(KDE_THREADS), 0, s, k.slices.p, n_slices, n, k.raw.p);
+    HIP_TRY(hipEventRecord(k.ev[3], s));
+    HIP_TRY(hipGetLastError());
+    unsigned long long skipped = 0;
+    HIP_TRY(hipMemcpyAsync(r.raw, k.raw.p, sizeof r.raw, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&skipped, k.skipped.p, sizeof skipped, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    gh::kdeNormalise(r.raw, r.x, r.y);
+    ctx->kde_chunks = n_chunks;
+    ctx->kde_skipped = (int64_t)skipped;
+    if (hipEventElapsedTime(&ctx->kde_moments_ms, k.ev[0], k.ev[1]) != hipSuccess) ctx->kde_moments_ms = 0.f;
+    if (hipEventElapsedTime(&ctx->kde_sums_ms, k.ev[2], k.ev[3]) != hipSuccess) ctx->kde_sums_ms = 0.f;
+    *out = r;
+    return GARLIC_OK;
+}
+
+int garlic_feed_kde(garlic_ctx *ctx, const double *sorted, int64_t n, int32_t where, garlic_kde *out)
+{
+    if (!ctx || !out) return fail(GARLIC_ERR_INVALID, "feed KDE: context and out are required");
+    if (where != GARLIC_HOST && where != GARLIC_DEVICE) return fail(GARLIC_ERR_INVALID, "feed KDE: where must be GARLIC_HOST or GARLIC_DEVICE");
+    if (n < 2) return fail(GARLIC_ERR_INVALID, "feed KDE: needs at least 2 values (got %lld)", (long long)n);
+    if (!sorted) return fail(GARLIC_ERR_INVALID, "feed KDE: values is NULL");
+    int rc;
+    if ((rc = set_device(ctx))) return rc;
+    if (where == GARLIC_DEVICE) return kde_device(ctx, sorted, n, out);
+    if ((rc = kde_reserve(ctx, n, true))) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->kde.stage.p, sorted, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    return kde_device(ctx, ctx->kde.stage.p, n, out);
+}
+
+int garlic_feed_kde_info(garlic_ctx *ctx, int64_t *chunks, int64_t *pairs_skipped, int64_t *scratch_bytes)
+{
+    if (!ctx) return fail(GARLIC_ERR_INVALID, "context is NULL");
+    if (chunks) *chunks = ctx->kde_chunks;
+    if (pairs_skipped) *pairs_skipped = ctx->kde_skipped;
+    if (scratch_bytes) *scratch_bytes = (int64_t)ctx->kde.bytes();
+    return GARLIC_OK;
+}
+
+int garlic_feed_kde_times(garlic_ctx *ctx, float *moments_ms, float *sums_ms)
+{
+    if (!ctx) return fail(GARLIC_ERR_INVALID, "context is NULL");
+    if (moments_ms) *moments_ms = ctx->kde_moments_ms;
+    if (sums_ms) *sums_ms = ctx->kde_sums_ms;
+    return GARLIC_OK;
+}
+
+int garlic_lod_kde(garlic_panel *p, int32_t winsize, double error, int32_t max_gap, int32_t use_gl, int32_t weighted, int32_t M,
+                   double mu, int32_t step, const int32_t *ind_idx, int32_t n_idx, garlic_kde *out, int64_t *chr_counts)
+{
+    if (!p || !out) return fail(GARLIC_ERR_INVALID, "panel and out are required");
+    garlic_panel::FeedSink sink;
+    int64_t count = 0;
+    p->feed_sink = &sink;                  // the feed call sorts and leaves the values on the device; the order setting is not touched
+    const int rc = garlic_lod_feed_subset(p, winsize, error, max_gap, use_gl, weighted, M, mu, step, ind_idx, n_idx, nullptr,
+                                          INT64_MAX, &count, chr_counts);
+    p->feed_sink = nullptr;
+    if (rc) return rc;
+    if (count < 2 || sink.n != count) return fail(GARLIC_ERR_INVALID, "feed KDE: needs at least 2 values (the feed holds %lld)", (long long)count);
+    return kde_device(p->ctx, sink.data, sink.n, out);
 }
 
 int garlic_lod_feed_info(garlic_panel *p, int32_t *form, int64_t *score_doubles)

@@ -1502,6 +1502,46 @@ DoubleData *LodEngine::lodFeed(int winsize, double error, int MAX_GAP, int step,
     return d;
 }
 
+// computeKDE of the feed lodFeed would return, sorted (garlic_hip.h: garlic_lod_kde).  One shard: the feed never leaves the
+// device.  Several: the shards' sorted feeds merged on the host as for LodOptions::feed_sorted, then garlic_feed_kde on
+// the first context -- correct, but the transfer is not saved (a sharded device path needs distributed order statistics).
+KdeData LodEngine::lodKde(int winsize, double error, int MAX_GAP, int step, bool weighted, int M, double mu,
+                             const std::vector<int> *kdeSubsample)
+{
+    static_assert(sizeof(KdeData) == sizeof(garlic_kde) && KDE_POINTS == GARLIC_KDE_POINTS, "KdeData mirrors garlic_kde");
+    garlic_kde gk;
+    auto result = [&] { KdeData k; memcpy(&k, &gk, sizeof k); return k; };
+    const bool subset = kdeSubsample && !kdeSubsample->empty();
+    if (impl->shards.size() == 1) {
+        auto &s = impl->shards[0];
+        std::cerr << "Calculating LOD scores with winsize " << winsize << " (thinned on the device, step " << step << ", KDE on the device).\n";
+        std::vector<int32_t> mine;
+        if (subset)
+            for (size_t i = 0; i < kdeSubsample->size(); i++) {
+                if (i && (*kdeSubsample)[i] <= (*kdeSubsample)[i - 1]) fail("KDE subsample must be in increasing order");
+                mine.push_back((*kdeSubsample)[i] - s.ind_begin);
+            }
+        if (garlic_lod_kde(s.panel, winsize, error, MAX_GAP, impl->use_gl, weighted, M, mu, step, subset ? mine.data() : nullptr,
+                           (int32_t)mine.size(), &gk, nullptr) != GARLIC_OK)
+            fail(std::string("garlic_lod_kde: ") + garlic_hip_last_error());
+        return result();
+    }
+    const bool was = g_options.feed_sorted;
+    g_options.feed_sorted = true;
+    DoubleData *feed = nullptr;
+    try {
+        feed = lodFeed(winsize, error, MAX_GAP, step, weighted, M, mu, kdeSubsample);
+    } catch (...) {
+        g_options.feed_sorted = was;
+        throw;
+    }
+    g_options.feed_sorted = was;
+    const int rc = garlic_feed_kde(impl->shards[0].ctx, feed->data, feed->size, GARLIC_HOST, &gk);
+    releaseDoubleData(feed);
+    if (rc != GARLIC_OK) fail(std::string("garlic_feed_kde: ") + garlic_hip_last_error());
+    return result();
+}
+
 // ---- ROH calls
 std::vector<ROHData *> *initROHData(IndData *indData)
 {

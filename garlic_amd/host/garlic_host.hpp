@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "feed_merge.hpp"
+#include "kde_select.hpp"
 
 namespace garlic_host {
 
@@ -309,6 +310,13 @@ std::vector<int> drawLdSubsample(int nind, int ldSubsample, unsigned long long s
 // there): empty = everyone (kdeSubsample <= 0 or >= nind), else kdeSubsample distinct indices, increasing
 std::vector<int> drawKdeSubsample(int nind, int kdeSubsample, unsigned long long seed);
 
+// garlic_kde of include/garlic_hip.h on this side (the same layout): LodEngine::lodKde's result
+struct KdeData {
+    int64_t n;
+    double h, sd, q25, q75, lo, hi;
+    double x[KDE_POINTS], y[KDE_POINTS], raw[KDE_POINTS];
+};
+
 // A panel kept on the device(s) across window sizes (exploreWinsizes / selectWinsize call the
 // path once per candidate winsize on the same data, garlic-roh.cpp:726-751,798-837,881-920).
 class LodEngine {
@@ -340,6 +348,11 @@ public:
     // gsl_ran_choose draws); NULL or empty = everyone.  Only their 64-individual blocks are scored.
     DoubleData *lodFeed(int winsize, double error, int MAX_GAP, int step, bool weighted = false, int M = 0,
                         double mu = 0.0, const std::vector<int> *kdeSubsample = nullptr);
+    // computeKDE (garlic-kde.cpp:14-140) of the ascending feed of lodFeed's arguments, on the device (garlic_lod_kde: exact
+    // Gaussian sums, not FIGTree's approximation).  One shard: no feed value crosses PCIe; several shards or devices: the
+    // sorted feeds merged on the host, then garlic_feed_kde.  kde_select.hpp turns the result into a cutoff.
+    KdeData lodKde(int winsize, double error, int MAX_GAP, int step, bool weighted = false, int M = 0, double mu = 0.0,
+                      const std::vector<int> *kdeSubsample = nullptr);
     // several window sizes in one call (unweighted --error scores): the feeds of exploreWinsizes / selectWinsize /
     // selectWinsizeFromList (garlic-roh.cpp:726-751, 798-837, 881-920), one DoubleData per size; steps NULL: the sizes
     std::vector<DoubleData *> lodFeedMulti(const std::vector<int> &winsizes, double error, int MAX_GAP,

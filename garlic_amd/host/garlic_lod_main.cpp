@@ -11,7 +11,12 @@
 // Input besides the reference's tped/tfam: a PLINK .bed/.bim/.fam (--bfile PREFIX, or --bed F --bim F --fam F).  The rows go
 // to the device as they are; the counted allele of every SNP and its frequency come from a census there, and the genotypes
 // never exist on the host as anything but the mapped file.
-// KDE / ROH assembly / GMM themselves stay in GARLIC (out of scope here).
+//   <out>.<W>SNPs.kde                      with --kde: computeKDE's density of the feed (src/garlic-kde.cpp:14-140; the exact
+//                                          Gaussian sums on the device, not FIGTree's approximation), the feed itself is
+//                                          not written; "Selected LOD score cutoff: X" on stderr (get_min_btw_modes), and
+//                                          with --size-bounds and no --lod-cutoff the ROH calls at that cutoff.  With
+//                                          --auto-winsize the tool runs selectWinsize / selectWinsizeFromList itself.
+// The GMM size classes stay in GARLIC (--size-bounds is required for ROH calls).
 #include "garlic_host.hpp"
 
 #include <algorithm>
@@ -35,6 +40,7 @@ struct Args {
     std::vector<int> winsize_multi;
     bool auto_winsize = false, weighted = false, raw_lod = false, kde_thinning = true, phased = false;
     bool sorted_feed = false;      // extension: the feeds ascending, <out>.<W>SNPs.lod.sorted.f64 (the device sorts them)
+    bool kde = false;              // extension: the KDE, the LOD cutoff and (--auto-winsize) the window size in this tool
     bool winsize_stream = false;   // extension: further window sizes from stdin (the loop of selectWinsize, driven by the KDE's owner)
     int auto_winsize_step = 10, max_gap = 200000, M = 7, threads = 1, kde_subsample = 20, gpus = 1;
     std::vector<int> devices;      // --devices; empty = 0 .. gpus-1
@@ -63,6 +69,8 @@ struct Args {
                  "         (--tgls-term-gb X: at most X GB of TGLS terms per device, built and read in slabs; binds --weighted --tgls too)\n"
                  "         [--sorted-feed]   (the KDE feeds ascending, as nrd0's gsl_sort leaves them: <out>.<W>SNPs.lod.sorted.f64)\n"
                  "         [--lod-cutoff X --size-bounds B1 B2 ... [--cm]]   (ROH calls: <out>.roh.bed)\n"
+                 "         [--kde]   (<out>.<W>SNPs.kde and the LOD cutoff from the KDE on the device instead of the feed files; with\n"
+                 "                    --size-bounds and no --lod-cutoff the ROH calls use it; with --auto-winsize the window size too)\n"
                  "         (--bfile / --bed --bim --fam: PLINK SNP-major .bed input, read on the device; not with --tped / --tfam /\n"
                  "          --phased; --genotype-cache F is then written from the .bed, never read)\n";
     exit(1);
@@ -98,6 +106,7 @@ Args parse(int argc, char **argv)
         else if (f == "--auto-winsize-step") a.auto_winsize_step = atoi(val().c_str());
         else if (f == "--winsize-stream") a.winsize_stream = !a.winsize_stream;
         else if (f == "--sorted-feed") a.sorted_feed = !a.sorted_feed;
+        else if (f == "--kde") a.kde = !a.kde;
         else if (f == "--max-gap") a.max_gap = atoi(val().c_str());
         else if (f == "--overlap-frac") a.overlap_frac = atof(val().c_str());
         else if (f == "--weighted") a.weighted = !a.weighted;
@@ -152,6 +161,9 @@ Args parse(int argc, char **argv)
     if (a.have_cutoff && a.size_bounds.empty())
         usage("--lod-cutoff writes the ROH calls and needs --size-bounds (the size classes otherwise come from GARLIC's GMM stage, "
               "Phase II, not part of this tool)");
+    if (a.kde && a.raw_lod) usage("--kde and --raw-lod exclude each other (the KDE path keeps the scores on the device)");
+    if (a.kde && a.sorted_feed) usage("--kde and --sorted-feed exclude each other (with --kde no feed file is written)");
+    if (a.kde && a.winsize_stream) usage("--kde and --winsize-stream exclude each other (with --kde the tool owns the KDE and runs --auto-winsize itself)");
     for (size_t k = 1; k < a.size_bounds.size(); k++)
         if (!(a.size_bounds[k] > a.size_bounds[k - 1])) usage("--size-bounds must increase");
     return a;
@@ -273,7 +285,7 @@ int main(int argc, char **argv)
             for (int i : kdesub) std::cerr << " " << ind->indID[i];
             std::cerr << "\n";
         }
-        if (!a.raw_lod && !a.weighted && sizes.size() > 1) {
+        if (!a.kde && !a.raw_lod && !a.weighted && sizes.size() > 1) {
             // --winsize-multi, feeds only, unweighted: all sizes in one call (their kernels and downloads overlap; with --tgls
             // the sizes share passes over the term matrix: garlic_lod_feed_multi_tgls)
             std::vector<int> steps;
@@ -287,10 +299,16 @@ int main(int argc, char **argv)
         }
         // --lod-cutoff: the ROH calls (garlic-main.cpp:346-420 with a user cutoff and user size classes): assembleROHWindows
         // on the device(s), straight from the genotypes -- no window scores, no per-SNP counts -- then the .roh.bed
-        auto roh_calls = [&](int W, bool single) {
-            if (!a.have_cutoff) return;
+        auto term_report = [&] {
+            if (!USE_GL || a.tgls_term_gb == 0) return;
+            int slab_blocks = 0, n_slabs = 0;
+            engine.tglsTermSlabs(&slab_blocks, &n_slabs);
+            std::cerr << "TGLS terms (--tgls-term-gb " << a.tgls_term_gb << "): last call in " << n_slabs << " slabs of " << slab_blocks
+                      << " blocks on the first device (0: the whole matrix, or terms looked up)\n";
+        };
+        auto roh_calls_at = [&](int W, bool single, double cutoff) {
             ROHLength *len = nullptr;
-            std::vector<ROHData *> *roh = engine.assembleROHWindows(ind, a.lod_cutoff, &len, W, a.error, a.max_gap, a.overlap_frac,
+            std::vector<ROHData *> *roh = engine.assembleROHWindows(ind, cutoff, &len, W, a.error, a.max_gap, a.overlap_frac,
                                                                     a.cm, a.weighted, a.M, a.mu);
             std::cerr << "ROH segments: " << (long long)len->size << " (garlic-lod, MI355X; .roh.bed in the format of garlic 1.1.6a)\n";
             writeROHData((single ? a.out : a.out + "." + std::to_string(W) + "SNPs") + ".roh.bed", roh, maps, a.size_bounds, ind->pop,
@@ -298,6 +316,54 @@ int main(int argc, char **argv)
             releaseROHData(roh);
             releaseROHLength(len);
         };
+        auto roh_calls = [&](int W, bool single) {
+            if (a.have_cutoff) roh_calls_at(W, single, a.lod_cutoff);
+        };
+        if (a.kde) {
+            // selectLODCutoff / selectWinsize / selectWinsizeFromList (garlic-roh.cpp:660-700, 766-930) with the KDE of every
+            // size made on the device (LodEngine::lodKde); kde_select.hpp holds what the reference does with the density
+            const bool single = a.winsize_multi.empty();
+            auto kde_of = [&](int W) {
+                if (a.weighted) engine.ldWeights(W, ldsub, false, a.phased);
+                return engine.lodKde(W, a.error, a.max_gap, a.kde_thinning ? W : 1, a.weighted, a.M, a.mu, &kdesub);
+            };
+            auto finish = [&](int W, const KdeData &k, double scale, bool single_out) {
+                const std::string path = a.out + "." + std::to_string(W) + "SNPs.kde";
+                std::vector<double> y(k.y, k.y + KDE_POINTS);
+                for (double &v : y) v = scale == 1.0 ? v : v * scale;
+                if (!writeKde(path, k.x, y.data(), KDE_POINTS)) { std::cerr << "ERROR: Failed to open " << path << "\n"; throw 0; }
+                std::cerr << "Wrote KDE results to " << path << " (" << (long long)k.n << " window scores, bandwidth " << k.h << ")\n";
+                double cutoff = 0;
+                std::string why;
+                if (!kdeMinBetweenModes(k.x, y.data(), KDE_POINTS, W, &cutoff, nullptr, &why)) {
+                    std::cerr << "ERROR: no LOD score cutoff from the KDE of winsize " << W << ": " << why << "\n";
+                    throw 0;
+                }
+                std::cerr << "Selected LOD score cutoff: " << cutoff << "\n";
+                if (!a.size_bounds.empty()) roh_calls_at(W, single_out, a.have_cutoff ? a.lod_cutoff : cutoff);
+            };
+            if (!a.auto_winsize) {
+                for (int W : sizes) finish(W, kde_of(W), 1.0, single);
+                term_report();
+                return 0;
+            }
+            if (a.weighted) { std::cerr << "Not currently supported.\n"; return 1; }    // as the reference's selectWinsize says
+            const double threshold = 0.50;
+            std::cerr << "Searching for acceptable window size, smoothness threshold: " << threshold << "\nwinsize\tsmoothness\n";
+            for (size_t i = 0;; i++) {      // selectWinsize: from --winsize in steps; selectWinsizeFromList: the list, the last size if none passes
+                const int W = single ? a.winsize + (int)i * a.auto_winsize_step : sizes[i];
+                const KdeData k = kde_of(W);
+                const double mse = kdeWiggle(k.x, k.y, KDE_POINTS);
+                std::cerr << W << "\t" << mse << "\n";
+                if (mse <= threshold || (!single && i + 1 == sizes.size())) {
+                    // calculateWiggle scales y by 100 in place before the reference writes and reads the density again
+                    std::cerr << "Selected window size: " << W << "\n";
+                    finish(W, k, 100.0, true);
+                    term_report();
+                    return 0;
+                }
+            }
+        }
         const bool single_size = a.winsize_multi.empty();
         if (a.have_cutoff && !a.weighted)
             for (int W : a.winsize_multi.empty() ? std::vector<int>{a.winsize} : a.winsize_multi) roh_calls(W, single_size);
@@ -351,12 +417,7 @@ int main(int argc, char **argv)
         } else if (a.auto_winsize)
             std::cerr << "NOTE: --auto-winsize picks among the feeds above in GARLIC's KDE stage (Phase II, not part of this tool); "
                          "--winsize-stream lets that stage ask for further window sizes on the resident panel\n";
-        if (USE_GL && a.tgls_term_gb != 0) {
-            int slab_blocks = 0, n_slabs = 0;
-            engine.tglsTermSlabs(&slab_blocks, &n_slabs);
-            std::cerr << "TGLS terms (--tgls-term-gb " << a.tgls_term_gb << "): last call in " << n_slabs << " slabs of " << slab_blocks
-                      << " blocks on the first device (0: the whole matrix, or terms looked up)\n";
-        }
+        term_report();
     } catch (...) {
         return 1;
     }

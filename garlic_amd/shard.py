@@ -129,3 +129,27 @@ def merge_sorted_feeds(feeds):
         merged[mask] = out
         out = merged
     return out
+
+
+def lod_kde(ctx, panels, winsize, error, max_gap, step, ind_idx=None, **kw):
+    """computeKDE's density of the panel-wide feed by LodEngine::lodKde's rule.  panels: the shards' abi.Panel objects in
+    rank order (one process holding them all), each with its own individuals; ind_idx: per shard, the shard-local part
+    of the KDE subsample (split_subsample) or None.  One shard: Panel.lod_kde, no feed value leaves the device.  Several:
+    the shards' sorted feeds merged on the host (merge_sorted_feeds), then Context.feed_kde on `ctx` -- correct, but the
+    transfer is not saved; a sharded device path needs distributed order statistics.  The panels' feed order setting is
+    left as found (Panel.feed_order) on both paths.  Returns the dict of Context.feed_kde."""
+    from . import abi
+    idx = list(ind_idx) if ind_idx is not None else [None] * len(panels)
+    if len(panels) == 1:
+        return panels[0].lod_kde(winsize, error, max_gap, step, ind_idx=idx[0], **kw)[0]
+    feeds = []
+    for p, sub in zip(panels, idx):
+        if sub is not None and len(sub) == 0:
+            continue                                  # no listed individual lives on this shard
+        was = p.feed_order
+        p.set_feed_order(abi.FEED_ORDER_SORTED)
+        try:
+            feeds.append(p.lod_feed(winsize, error, max_gap, step, ind_idx=sub, **kw)[0])
+        finally:
+            p.set_feed_order(was)
+    return ctx.feed_kde(merge_sorted_feeds(feeds))

@@ -52,7 +52,8 @@ extern "C" {
  *    garlic_ld_finish_multi, garlic_panel_ld_info (likewise); garlic_panel_set_feed_order, garlic_feed_sort,
  *    garlic_feed_sort_info, GARLIC_FEED_ORDER_* (likewise); garlic_panel_set_phase_bits, garlic_panel_ld_form_info,
  *    GARLIC_LD_PAIR_* / GARLIC_LD_SUM_* (likewise); garlic_panel_set_gl_codes16, GARLIC_TGLS_DICTIONARY16 (likewise);
- *    garlic_bed_create, garlic_bed_set_rows, garlic_bed_census, garlic_bed_destroy, garlic_panel_set_genotypes_bed (likewise) */
+ *    garlic_bed_create, garlic_bed_set_rows, garlic_bed_census, garlic_bed_destroy, garlic_panel_set_genotypes_bed (likewise);
+ *    garlic_kde, GARLIC_KDE_POINTS, garlic_feed_kde, garlic_lod_kde, garlic_feed_kde_info, garlic_feed_kde_times (likewise) */
 #define GARLIC_HIP_ABI_VERSION 8
 
 #define GARLIC_OK 0
@@ -542,6 +543,46 @@ int garlic_lod_feed_multi_info(garlic_panel *panel, int32_t n, int32_t *forms, i
 int garlic_panel_set_feed_order(garlic_panel *panel, int32_t order);
 int garlic_feed_sort(garlic_ctx *ctx, double *values, int64_t n, int32_t where);
 int garlic_feed_sort_info(garlic_ctx *ctx, int32_t *passes_run, int32_t *passes_skipped, int64_t *scratch_bytes);
+
+/* computeKDE (src/garlic-kde.cpp:14-140) on the device: nrd0's bandwidth, the 512 targets, the Gaussian sums and their
+ * normalisation, from a feed in ascending order (garlic_feed_sort, GARLIC_FEED_ORDER_SORTED) that never has to leave the
+ * device (csrc/kde_kernels.hpp; the host arithmetic: host/kde_select.hpp).
+ *     sd  = sqrt(sum (x_i - mean)^2 / (n - 1))                       (its mathematical value: two tree-summed passes, not
+ *                                                                     gsl_stats_sd's long-double recurrence bit for bit)
+ *     q(f) = (1 - d) x[k] + d x[k + 1],  k = (int)(f (n - 1)), d = f (n - 1) - k      (gsl_stats_quantile_from_sorted_data)
+ *     h   = 0.9 * min(sd, (q(0.75) - q(0.25)) / 1.34) * pow(n, -0.2)
+ *     x[i] = (double(i + 1) / 512) * (max' - min') + min',  min' = lo - 3 h,  max' = hi + 3 h
+ *     raw[j] = (1 / n) sum_i exp(-(x_i - x[j])^2 / h^2)              (FIGTree's kernel: no factor 2, no 1 / (h sqrt(pi)))
+ *     y[j] = raw[j] / ((raw[0] + raw[1] + ... in order) * (x[1] - x[0]))
+ * NOT FIGTree's output: figtree() (:81) approximates raw with |figtree - raw| <= 1e-2 before the normalisation; this is
+ * raw itself, FP64 exp of the device library on every (source, target) pair except those whose every term is exactly
+ * +0.0 (argument below -746).  The result is a pure function of (values, n): two calls, or a host and a device buffer,
+ * give identical bits.
+ * garlic_feed_kde: `sorted` holds n doubles, ascending; `where` GARLIC_DEVICE or GARLIC_HOST (uploaded, never modified).
+ * It does not sort.  GARLIC_ERR_INVALID, with a message that names the cause and *out untouched: n < 2; a NaN or an
+ * infinity; x[i] < x[i - 1] somewhere; h equal to 0 or not finite (all values equal, or more than half of them).  Scratch
+ * (8 B per 2048 values, up to 8 MB of slice sums; a host buffer: n doubles more) is kept with the context until
+ * garlic_panel_release_scratch; GARLIC_ERR_NOMEM leaves everything untouched.
+ * garlic_lod_kde: garlic_lod_feed_subset up to, not including, the copy to the host -- same arguments, same kernel forms,
+ * same garlic_lod_feed_info and chr_counts -- always in ascending order whatever garlic_panel_set_feed_order says (the
+ * setting is left as found), then garlic_feed_kde on the device buffer: no feed value crosses PCIe.  An empty feed is the
+ * n < 2 error.  The multi-size feed calls have no KDE twin: a sweep calls this once per size.
+ * garlic_feed_kde_info: of the last KDE on the context: chunks of 2048 sources, (chunk, target) pairs skipped as exactly
+ * zero, bytes of scratch held.  Any pointer may be NULL.
+ * garlic_feed_kde_times: HIP-event times of the last successful KDE on the context: the two moment passes with their
+ * tree kernels, and the sums with the slice reduction (tools/bench_variants.py --modes feed_kde).  Any pointer may be NULL. */
+#define GARLIC_KDE_POINTS 512
+typedef struct garlic_kde {
+    int64_t n;            /* sources */
+    double h, sd, q25, q75, lo, hi;   /* lo = x[0], hi = x[n-1] of the feed */
+    double x[GARLIC_KDE_POINTS], y[GARLIC_KDE_POINTS], raw[GARLIC_KDE_POINTS];
+} garlic_kde;
+int garlic_feed_kde(garlic_ctx *ctx, const double *sorted, int64_t n, int32_t where, garlic_kde *out);
+int garlic_lod_kde(garlic_panel *panel, int32_t winsize, double error, int32_t max_gap, int32_t use_gl,
+                   int32_t weighted, int32_t M, double mu, int32_t step, const int32_t *ind_idx, int32_t n_idx,
+                   garlic_kde *out, int64_t *chr_counts);
+int garlic_feed_kde_info(garlic_ctx *ctx, int64_t *chunks, int64_t *pairs_skipped, int64_t *scratch_bytes);
+int garlic_feed_kde_times(garlic_ctx *ctx, float *moments_ms, float *sums_ms);
 
 /* First half of assembleROHWindows (src/garlic-roh.cpp:446-454) on the device: for every individual
  * and SNP the number of windows with score >= cutoff that cover the SNP,

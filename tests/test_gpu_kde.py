@@ -1,0 +1,271 @@
+"""GPU: computeKDE's numbers on the device (csrc/kde_kernels.hpp, garlic_feed_kde / garlic_lod_kde) against the long-double
+numpy reference of tests/kde_cases.py -- never against a second run of the kernels, except where the claim is that two
+runs agree.
+
+Tolerances (none of them from what the kernels give):
+  h         relative 1e-13 against the long-double reference: summation trees of depth <= 40 with three roundings per
+            term, the mean's error entering squared, give <~ 5e-15 on sd; an order of margin.  Every content keeps
+            |mean| <= 1e3 sd for that reason.
+  q25, q75, lo, hi   bit for bit.
+  x         bit for bit against the formula evaluated from the returned h, lo, hi.
+  raw       |got - want| <= 1e-12 want + 1e-300 against the reference evaluated AT THE RETURNED h and x (so that the
+            bandwidth's error is not amplified by arguments of up to 746): the argument carries <= 4 roundings, the sum
+            at most (4 * 746 + 64) * 2^-53 ~ 3.4e-13, rounded up; 1e-300 covers subnormal terms.
+  y         bit for bit from the returned raw and x by the sequential rule."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import feed_sort_cases as fcases
+import kde_cases as cases
+import oracle_lib as ol
+import wlod_feed_cases as wcases
+from garlic_amd import abi
+
+pytestmark = pytest.mark.gpu
+MG, ERROR, M, MU = fcases.MG, fcases.ERROR, fcases.M, fcases.MU
+FIELDS = ("n", "h", "sd", "q25", "q75", "lo", "hi")
+
+
+def run_kde(ctx, x, device):
+    if not device:
+        return ctx.feed_kde(x)
+    import torch
+    t = torch.from_numpy(np.array(x)).cuda()
+    got = ctx.feed_kde(t.data_ptr(), n=x.shape[0])
+    torch.cuda.synchronize()
+    assert ol.bits_equal(t.cpu().numpy(), x), "the caller's device buffer was modified"
+    return got
+
+
+def same_struct(a, b):
+    return all(np.float64(a[k]).tobytes() == np.float64(b[k]).tobytes() for k in FIELDS) and \
+        all(ol.bits_equal(a[k], b[k]) for k in ("x", "y", "raw"))
+
+
+_raw_at_returned = {}
+
+
+def raw_reference(x, got):
+    """the long-double sums at the returned h and targets, once per distinct (feed, h, x)"""
+    at = cases.raw_targets(x.shape[0])
+    key = (x.shape[0], x[:64].tobytes(), np.float64(got["h"]).tobytes(), got["x"].tobytes())
+    if key not in _raw_at_returned:
+        _raw_at_returned[key] = cases.raw_longdouble(x, got["x"][at], got["h"])
+    return at, _raw_at_returned[key]
+
+
+def check_kde(got, x, what):
+    n = x.shape[0]
+    ref = cases.reference(x, with_raw=False)
+    assert got["n"] == n, what
+    print(what, "h rel err %.3g" % abs(float((np.longdouble(got["h"]) - np.longdouble(ref["h"])) / np.longdouble(ref["h"]))))
+    # the reference's h from the long-double sd, in long double up to the last product
+    want_h = np.longdouble(0.9) * min(ref["sd"], np.longdouble((ref["q75"] - ref["q25"]) / 1.34)) * np.longdouble(float(n)) ** np.longdouble(-0.2)
+    assert abs(np.longdouble(got["h"]) - want_h) <= np.longdouble(1e-13) * want_h, (what, got["h"], want_h)
+    assert abs(np.longdouble(got["sd"]) - ref["sd"]) <= np.longdouble(1e-13) * ref["sd"], (what, got["sd"], ref["sd"])
+    for k in ("q25", "q75", "lo", "hi"):
+        assert np.float64(got[k]).tobytes() == np.float64(ref[k]).tobytes(), (what, k, got[k], ref[k])
+    assert ol.bits_equal(got["x"], cases.targets(got["lo"], got["hi"], got["h"])), (what, "x")
+    at, want = raw_reference(x, got)
+    err = np.abs(got["raw"][at].astype(np.longdouble) - want)
+    bound = np.longdouble(1e-12) * want + np.longdouble(1e-300)
+    worst = float(np.max(err / bound))
+    print(what, "raw: worst error / bound %.3g" % worst)
+    assert (err <= bound).all(), (what, "raw", worst, int(np.argmax(err / bound)))
+    assert ol.bits_equal(got["y"], cases.normalise(got["raw"], got["x"])), (what, "y")
+
+
+# ------------------------------------------------------------------------------------------------ 1. garlic_feed_kde alone
+
+@pytest.mark.parametrize("device", [False, True], ids=["host", "device"])
+@pytest.mark.parametrize("name", cases.CONTENTS)
+def test_kde_sizes_and_contents(gpu_ctx, name, device):
+    chunk = cases.kde_chunk()
+    for n in cases.sizes():
+        x = cases.content(name, n)
+        got = run_kde(gpu_ctx, x, device)
+        info = gpu_ctx.feed_kde_info()
+        print(name, n, info)
+        check_kde(got, x, (name, n, "device" if device else "host"))
+        n_chunks = (n + chunk - 1) // chunk
+        assert info["chunks"] == n_chunks and 0 <= info["pairs_skipped"] <= n_chunks * 512 and info["scratch_bytes"] > 0
+        # the same tolerances above for both; what differs is how much may be left out exactly
+        if name == "wide" and n_chunks > 1:       # (one chunk spans the whole range: every target lies within 3 h of it)
+            assert info["pairs_skipped"] > 0, (n, info)
+        if name == "narrow":
+            assert info["pairs_skipped"] == 0, (n, info)
+
+
+@pytest.mark.parametrize("name", ["bimodal", "wide"])
+def test_kde_is_a_pure_function_of_the_values(gpu_ctx, name):
+    for n in (3 * cases.kde_chunk() + 17, cases.BIG):
+        x = cases.content(name, n)
+        first = run_kde(gpu_ctx, x, False)
+        for _ in range(2):
+            assert same_struct(run_kde(gpu_ctx, x, False), first), (name, n, "host buffer again")
+        gpu_ctx.feed_kde(cases.content("uniform", 65))           # another feed through the same scratch in between
+        assert same_struct(run_kde(gpu_ctx, x, True), first), (name, n, "device buffer")
+        assert same_struct(run_kde(gpu_ctx, x, True), first), (name, n, "device buffer again")
+
+
+@pytest.mark.parametrize("name", ["uniform", "wide"])
+def test_kde_with_several_chunks_per_slice(gpu_ctx, name):
+    """more chunks than the 2048 slices: the sums kernel's loop over a slice's chunks runs twice, the last slice once (the
+    shape of every feed above 4.2M values, the everyone scale included).  Same tolerances; raw at kde_cases.raw_targets"""
+    n, chunk = cases.HUGE, cases.kde_chunk()
+    assert (n + chunk - 1) // chunk > 2048 and (n + chunk - 1) // chunk % 2 == 1
+    x = cases.content(name, n)
+    got = run_kde(gpu_ctx, x, False)
+    info = gpu_ctx.feed_kde_info()
+    print(name, n, info, gpu_ctx.feed_kde_times())
+    check_kde(got, x, (name, n))
+    assert info["chunks"] == (n + chunk - 1) // chunk
+    if name == "wide":
+        assert info["pairs_skipped"] > 0
+    assert same_struct(run_kde(gpu_ctx, x, True), got), (name, "device buffer")
+    t = gpu_ctx.feed_kde_times()
+    assert t["moments_ms"] > 0 and t["sums_ms"] > 0
+
+
+def bad_feeds():
+    c = cases.kde_chunk()
+    base = np.array(cases.content("bimodal", 3 * c + 17))
+    nan = base.copy(); nan[len(nan) // 2] = np.nan
+    inf = base.copy(); inf[-1] = np.inf
+    inside = base.copy(); inside[[c + 100, c + 101]] = inside[[c + 101, c + 100]]
+    border = base.copy(); border[[2 * c - 1, 2 * c]] = border[[2 * c, 2 * c - 1]]
+    assert inside[c + 100] > inside[c + 101] and border[2 * c - 1] > border[2 * c]
+    return [("n = 0", base[:0], "at least 2"), ("n = 1", base[:1], "at least 2"), ("all equal", np.full(c + 5, -3.25), "bandwidth"),
+            ("two equal", np.full(2, 1.0), "bandwidth"), ("NaN in the middle", nan, "NaN"), ("+inf at the end", inf, "infinity"),
+            ("swapped inside a chunk", inside, "ascending"), ("swapped across a chunk border", border, "ascending")]
+
+
+@pytest.mark.parametrize("device", [False, True], ids=["host", "device"])
+def test_kde_errors_leave_the_output_untouched(gpu_ctx, device):
+    import torch
+    for what, x, word in bad_feeds():
+        out = abi.Kde()
+        C.memset(C.byref(out), 0x5A, C.sizeof(out))
+        before = bytes(out)
+        with pytest.raises(abi.GarlicError) as e:
+            if device:
+                t = torch.from_numpy(np.concatenate([x, [0.0]])).cuda()        # (never empty: a real address for n = 0 too)
+                gpu_ctx.feed_kde(t.data_ptr(), n=x.shape[0], out=out)
+            else:
+                gpu_ctx.feed_kde(np.ascontiguousarray(x), out=out)
+        assert e.value.code == abi.ERR_INVALID and word in str(e.value), (what, str(e.value))
+        assert bytes(out) == before, what
+    good = run_kde(gpu_ctx, cases.content("uniform", 65), device)             # and the context still works
+    check_kde(good, cases.content("uniform", 65), "after the errors")
+    L = abi.lib()
+    assert L.garlic_feed_kde_info(gpu_ctx.handle, None, None, None) == abi.OK
+    x = np.array([1.0, 2.0, 4.0])
+    assert L.garlic_feed_kde(gpu_ctx.handle, C.c_void_p(x.ctypes.data), 3, 7, C.byref(abi.Kde())) == abi.ERR_INVALID
+    assert L.garlic_feed_kde(gpu_ctx.handle, None, 3, abi.HOST, C.byref(abi.Kde())) == abi.ERR_INVALID
+    assert L.garlic_feed_kde(gpu_ctx.handle, C.c_void_p(x.ctypes.data), 3, abi.HOST, None) == abi.ERR_INVALID
+
+
+# ------------------------------------------------------------------------------------------------ 2. garlic_lod_kde
+
+NIND = 200
+KINDS = {"unweighted": "lod", "tgls": "tgls", "weighted": "wlod"}
+
+
+def open_panel(ctx, kind, W):
+    chroms, gpos, _, codes, values, _ = fcases.panel(NIND)
+    lds = [np.random.default_rng(9950 + W + k).uniform(1.0, 5.0, size=(c[0].shape[0], W)) for k, c in enumerate(chroms)]
+    panel = abi.Panel(ctx, [c[0].shape[0] for c in chroms], NIND)
+    panel.set_map(np.concatenate([c[2] for c in chroms]), [c[3] for c in chroms], [c[4] for c in chroms], gpos=np.concatenate(gpos))
+    panel.set_freq(np.concatenate([c[1] for c in chroms]))
+    panel.set_genotypes(np.concatenate([c[0] for c in chroms], axis=0))
+    if kind == "tgls":
+        panel.set_gl_codes(np.concatenate(codes, axis=0), values)
+    if kind == "weighted":
+        panel.set_ld(W, np.concatenate(lds, axis=0))
+    return panel, lds
+
+
+def oracle_feed(kind, W, lds, idx):
+    chroms, gpos, _, _, _, gl = fcases.panel(NIND)
+    if kind == "weighted":
+        scores = wcases.wlod_scores(chroms, gpos, lds, W)
+    else:
+        scores = fcases.oracle_scores(NIND, KINDS[kind], W)
+    return np.concatenate(wcases.flat(scores, W, idx))
+
+
+@pytest.mark.parametrize("subset", [False, True], ids=["everyone", "subset"])
+@pytest.mark.parametrize("W", [10, 100])
+@pytest.mark.parametrize("kind", list(KINDS))
+def test_lod_kde_is_feed_kde_of_the_sorted_feed(gpu_ctx, kind, W, subset):
+    idx = fcases.SUBSET if subset else None
+    args = dict(use_gl=kind == "tgls", weighted=kind == "weighted", M=M, mu=MU, ind_idx=idx)
+    panel, lds = open_panel(gpu_ctx, kind, W)
+    with panel:
+        ref_feed, ref_chr = panel.lod_feed(W, ERROR, MG, W, **args)
+        ref_info = panel.feed_info()
+        want_feed = oracle_feed(kind, W, lds, idx)
+        assert ol.bits_equal(ref_feed, want_feed), "the feed itself"
+        assert len(ref_feed) >= 2, "the panel gives this window size a feed"
+        for order in (abi.FEED_ORDER_REFERENCE, abi.FEED_ORDER_SORTED):
+            panel.set_feed_order(order)
+            before, _ = panel.lod_feed(W, ERROR, MG, W, **args)
+            got, per_chr = panel.lod_kde(W, ERROR, MG, W, **args)
+            assert panel.feed_info() == ref_info and list(per_chr) == list(ref_chr), (kind, W, order)
+            after, _ = panel.lod_feed(W, ERROR, MG, W, **args)       # the order setting is as it was
+            assert ol.bits_equal(after, before), (kind, W, order)
+            assert ol.bits_equal(before, np.sort(ref_feed) if order == abi.FEED_ORDER_SORTED else ref_feed)
+            want = gpu_ctx.feed_kde(np.sort(ref_feed) if order == abi.FEED_ORDER_REFERENCE else before)
+            assert same_struct(got, want), (kind, W, order)
+            s = np.sort(want_feed)
+            assert got["n"] == len(s) and got["lo"] == s[0] and got["hi"] == s[-1]
+        check_kde(got, np.sort(ref_feed), (kind, W, subset))
+
+
+def test_lod_kde_arguments(gpu_ctx):
+    panel, _ = open_panel(gpu_ctx, "unweighted", 10)
+    with panel:
+        L = abi.lib()
+        out = abi.Kde()
+        C.memset(C.byref(out), 0x5A, C.sizeof(out))
+        before = bytes(out)
+        assert L.garlic_lod_kde(panel.handle, 10, ERROR, MG, 0, 0, M, MU, 10, None, 0, None, None) == abi.ERR_INVALID
+        assert L.garlic_lod_kde(None, 10, ERROR, MG, 0, 0, M, MU, 10, None, 0, C.byref(out), None) == abi.ERR_INVALID
+        assert L.garlic_lod_kde(panel.handle, 1, ERROR, MG, 0, 0, M, MU, 10, None, 0, C.byref(out), None) == abi.ERR_INVALID
+        # a window wider than every chromosome: an empty feed is the "fewer than 2 values" error
+        assert L.garlic_lod_kde(panel.handle, 5000, ERROR, MG, 0, 0, M, MU, 5000, None, 0, C.byref(out), None) == abi.ERR_INVALID
+        assert bytes(out) == before
+        got, _ = panel.lod_kde(10, ERROR, MG, 10)
+        assert got["n"] >= 2
+
+
+def test_shard_lod_kde_is_the_unsplit_panels(gpu_ctx):
+    """garlic_amd.shard.lod_kde: one shard is Panel.lod_kde; two shards on the one device (sorted feeds merged on the host)
+    give the unsplit panel's struct bit for bit, with and without a subsample, and leave the order settings as found"""
+    from garlic_amd import shard
+    W = 10
+    chroms, _, _, _, _, _ = fcases.panel(NIND)
+    whole, _ = open_panel(gpu_ctx, "unweighted", W)
+    cut = 128
+    parts = []
+    for b, e in ((0, cut), (cut, NIND)):
+        p = abi.Panel(gpu_ctx, [c[0].shape[0] for c in chroms], e - b)
+        p.set_map(np.concatenate([c[2] for c in chroms]), [c[3] for c in chroms], [c[4] for c in chroms])
+        p.set_freq(np.concatenate([c[1] for c in chroms]))
+        p.set_genotypes(np.ascontiguousarray(np.concatenate([c[0] for c in chroms], axis=0)[:, b:e]))
+        parts.append(p)
+    with whole, parts[0], parts[1]:
+        for idx in (None, sorted(fcases.SUBSET)):
+            want, _ = whole.lod_kde(W, ERROR, MG, W, ind_idx=idx)
+            assert same_struct(shard.lod_kde(gpu_ctx, [whole], W, ERROR, MG, W, ind_idx=None if idx is None else [idx]), want)
+            split = None if idx is None else [[i for i in idx if i < cut], [i - cut for i in idx if i >= cut]]
+            parts[1].set_feed_order(abi.FEED_ORDER_SORTED)
+            got = shard.lod_kde(gpu_ctx, parts, W, ERROR, MG, W, ind_idx=split)
+            assert same_struct(got, want), idx
+            assert parts[0].feed_order == abi.FEED_ORDER_REFERENCE and parts[1].feed_order == abi.FEED_ORDER_SORTED
+            ref0, _ = parts[0].lod_feed(W, ERROR, MG, W)
+            ref1, _ = parts[1].lod_feed(W, ERROR, MG, W)
+            assert not ol.bits_equal(ref0, np.sort(ref0)) and ol.bits_equal(ref1, np.sort(ref1)), "the settings are as they were"
+            parts[1].set_feed_order(abi.FEED_ORDER_REFERENCE)

@@ -22,6 +22,9 @@ GARLIC_TGLS_FEED_MULTI_SOLO=1 for the groups-of-one leg).
 --modes ld_multi: the LD weights (no matrix output) of every size of --winsizes on one resident panel: a loop of single
 garlic_panel_compute_ld calls and, where the library has it, one garlic_panel_compute_ld_multi call (--tree for the parent
 commit, which times the loop only; several lists separated by ";" share one panel; profiles/ld_multi_ab.txt).
+--modes feed_kde: the device KDE (garlic_lod_kde: moment and sums kernels by HIP events, the whole call) beside the sorted
+garlic_lod_feed_subset call it replaces, at the --kde-inds and the everyone scale (--tree for the parent commit;
+profiles/feed_kde_ab.txt).
 --modes feed_sort: the sorted KDE feed (garlic_panel_set_feed_order / garlic_feed_sort) on real thinned feeds of one
 resident panel: the unweighted feed (step = winsize) of --kde-inds individuals (the --kde-subsample scale) and of
 everyone -- the device sort alone by HIP events, its bytes per second at 24 B x keys x passes run, the whole feed call in
@@ -381,6 +384,78 @@ def feed_sort_leg(args):
         panel.release_scratch()
 
 
+def feed_kde_leg(args):
+    """The device KDE (garlic_lod_kde) beside the call it replaces, the sorted garlic_lod_feed_subset whose feed crosses to
+    the host, on one resident panel, at the --kde-inds (--kde-subsample) and the everyone scale.  Per scale one JSON line:
+    the host clock around the sorted feed call; where the library has garlic_lod_kde (--tree DIR for the parent commit,
+    which has not: its line holds the feed call alone), the host clock and HIP events (the context runs on a torch stream)
+    around the whole garlic_lod_kde call, and the library's own HIP-event times of the moment kernels (kde_moment_kernel
+    + kde_tree_kernel, two passes) and the sums kernels (kde_sum_kernel + kde_slice_kernel): garlic_feed_kde_times."""
+    import time
+    import torch
+    from garlic_amd import abi, synth
+
+    torch.cuda.set_device(0)
+    dev = torch.device("cuda", 0)
+    nloci, nind, W = args.snps, args.inds, args.winsize
+    error, max_gap = 0.001, 200000
+    spec = synth.PanelSpec(nloci, seed=20260105, max_gap=max_gap)
+    stream = torch.cuda.Stream()
+    ctx = abi.Context(0, stream=stream.cuda_stream)
+    panel = abi.Panel(ctx, spec.chr_nloci, nind)
+    panel.set_map(spec.pos, spec.centro_start, spec.centro_end)
+    panel.set_freq(spec.freq)
+    for l0, g in synth.genotype_chunks(spec, nind, dev):
+        torch.cuda.synchronize()
+        panel.set_genotypes_device(g.data_ptr(), g.shape[1], l0, g.shape[0])
+    del g
+    have_kde = hasattr(panel, "lod_kde")
+    rng = np.random.default_rng(11)
+    subsets = [np.sort(rng.choice(nind, size=min(args.kde_inds, nind), replace=False)).astype(np.int32), None]
+    for idx in subsets:
+        panel.set_feed_order(abi.FEED_ORDER_SORTED)
+        wall = []
+        for k in range(1 + args.steps):
+            t0 = time.perf_counter()
+            feed, _ = panel.lod_feed(W, error, max_gap, W, copy=False, ind_idx=idx)
+            if k:
+                wall.append((time.perf_counter() - t0) * 1e3)
+        n = int(feed.shape[0])
+        line = {"mode": "feed_kde", "tree": os.path.abspath(args.tree) if args.tree else ROOT, "snps": nloci, "inds": nind,
+                "winsize": W, "step": W, "feed_individuals": nind if idx is None else int(idx.shape[0]), "values": n,
+                "feed_bytes_to_host": 8 * n, "repeats": args.steps, "sorted_feed_call_ms_median": float(np.median(wall)),
+                "sorted_feed_call_ms_min": min(wall), "has_lod_kde": have_kde}
+        panel.set_feed_order(abi.FEED_ORDER_REFERENCE)
+        if have_kde:
+            wall, ev, mom, sums = [], [], [], []
+            for k in range(1 + args.steps):
+                torch.cuda.synchronize()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0 = time.perf_counter()
+                e0.record(stream)
+                kde, _ = panel.lod_kde(W, error, max_gap, W, ind_idx=idx)
+                e1.record(stream)
+                torch.cuda.synchronize()
+                if k:
+                    wall.append((time.perf_counter() - t0) * 1e3)
+                    ev.append(e0.elapsed_time(e1))
+                    t = ctx.feed_kde_times() if hasattr(ctx, "feed_kde_times") else {"moments_ms": float("nan"), "sums_ms": float("nan")}
+                    mom.append(t["moments_ms"])
+                    sums.append(t["sums_ms"])
+            info = ctx.feed_kde_info()
+            assert kde["n"] == n and kde["lo"] == feed[0] and kde["hi"] == feed[-1]
+            line.update({"lod_kde_call_ms_median": float(np.median(wall)), "lod_kde_call_ms_min": min(wall),
+                         "lod_kde_call_hip_events_ms_median": float(np.median(ev)),
+                         "kde_moment_and_tree_kernels_ms_median": float(np.median(mom)),
+                         "kde_sum_and_slice_kernels_ms_median": float(np.median(sums)),
+                         "chunks": info["chunks"], "pairs_skipped": info["pairs_skipped"], "pairs": info["chunks"] * 512,
+                         "kde_scratch_bytes": info["scratch_bytes"], "bandwidth": kde["h"],
+                         "exp_per_s_of_pairs_not_skipped": (info["chunks"] * 512 - info["pairs_skipped"]) * 2048.0 / (float(np.median(sums)) * 1e-3)})
+        print(json.dumps(line), flush=True)
+        del feed
+        panel.release_scratch()
+
+
 def tgls_slabs_leg(args):
     """Host clock around the synchronous calls (the term pass, where there is one, is part of the call).  One panel; legs in
     this order so that the code table (host work of the first use_gl call) is built before anything is timed as a first
@@ -681,7 +756,7 @@ def main():
     ap.add_argument("--term-budgets-gb", default="8,12,32", help="tgls_slabs: garlic_panel_set_tgls_term_budget values to time")
     ap.add_argument("--term-budget-gb", type=float, default=0.0, help="tgls_dict16: garlic_panel_set_tgls_term_budget (GB; < 0: -1)")
     ap.add_argument("--cutoff", type=float, default=2.5, help="tgls_slabs: the LOD cutoff of the segments call")
-    ap.add_argument("--kde-inds", type=int, default=20, help="feed_sort: individuals of the subsampled feed (--kde-subsample)")
+    ap.add_argument("--kde-inds", type=int, default=20, help="feed_sort / feed_kde: individuals of the subsampled feed (--kde-subsample)")
     ap.add_argument("--file-inds", type=int, default=10000, help="bed_ingest: individuals of the .bed file the panel is cut from")
     ap.add_argument("--ind-offset", type=int, default=0, help="bed_ingest: the panel's first individual in the file")
     ap.add_argument("--bed-prefix", default="", help="bed_ingest: P.bed / P.bim / P.fam (and P.tped / P.tfam) for the whole-tool legs")
@@ -697,6 +772,8 @@ def main():
         return ld_multi_leg(args)
     if args.modes == "feed_sort":
         return feed_sort_leg(args)
+    if args.modes == "feed_kde":
+        return feed_kde_leg(args)
     if args.modes == "bed_ingest":
         return bed_ingest_leg(args)
     if args.modes == "ld_phased":
