@@ -78,24 +78,33 @@ def tiny_panels():
 
 
 def test_freq_and_raw_lod_match_reference_binary(tmp_path):
-    out = run_tool(tmp_path, "--winsize", "30", "--raw-lod")
-    # allele frequencies: same text
-    assert gzip.open(out + ".freq.gz", "rt").read() == gzip.open(os.path.join(E2E, "ref.freq.gz"), "rt").read()
-    n_tok = n_same = 0
-    for ref in sorted(glob.glob(os.path.join(E2E, "ref.POP.*.raw.lod.windows.gz"))):
-        mine = out + os.path.basename(ref)[3:]
-        a, b = read_rows(ref), read_rows(mine)
-        assert len(a) == len(b) == 24
-        for ra, rb in zip(a, b):
-            assert len(ra) == len(rb)
-            assert [x == "NA" for x in ra] == [x == "NA" for x in rb]       # identical MISSING mask
-            va = np.array([float(x) for x in ra if x != "NA"])
-            vb = np.array([float(x) for x in rb if x != "NA"])
-            # the prebuilt binary carries its own (older) libm; everything is printed with 6 digits
-            assert np.allclose(va, vb, rtol=2e-5, atol=2e-6)
-            n_tok += len(ra)
-            n_same += sum(x == y for x, y in zip(ra, rb))
-    assert n_same / n_tok > 0.999, (n_same, n_tok)
+    """--winsize 30 at the default --max-gap (one hole per chromosome), and --winsize 10 --max-gap 3900, which cuts the
+    chromosomes into 40 and more runs each (refg.*: chr7's raw windows)"""
+    for tag, flags, min_tok in (("ref", ["--winsize", "30"], 100000), ("refg", ["--winsize", "10", "--max-gap", "3900"], 30000)):
+        out = run_tool(tmp_path, *flags, "--raw-lod")
+        # allele frequencies: same text
+        assert gzip.open(out + ".freq.gz", "rt").read() == gzip.open(os.path.join(E2E, "ref.freq.gz"), "rt").read()
+        n_tok = n_same = n_na = 0
+        for ref in sorted(glob.glob(os.path.join(E2E, tag + ".POP.*.raw.lod.windows.gz"))):
+            mine = out + os.path.basename(ref)[len(tag):]
+            a, b = read_rows(ref), read_rows(mine)
+            assert len(a) == len(b) == 24
+            for ra, rb in zip(a, b):
+                assert len(ra) == len(rb)
+                assert [x == "NA" for x in ra] == [x == "NA" for x in rb]       # identical MISSING mask
+                va = np.array([float(x) for x in ra if x != "NA"])
+                vb = np.array([float(x) for x in rb if x != "NA"])
+                # the prebuilt binary carries its own (older) libm; everything is printed with 6 digits
+                assert np.allclose(va, vb, rtol=2e-5, atol=2e-6)
+                n_tok += len(ra)
+                n_same += sum(x == y for x, y in zip(ra, rb))
+                n_na += ra.count("NA")
+        assert n_tok > min_tok and n_same / n_tok > 0.999, (tag, n_same, n_tok)
+        if tag == "refg":       # chr7 in 40 runs and more: the MISSING windows of the oracle's mask over an independent re-parse
+            g, f, p, (cs, ce) = tiny_panels()[2]
+            mask = ol.oracle_mask(p, cs, ce, 10, 3900).astype(bool)
+            breaks = int(np.count_nonzero(np.diff(p.astype(np.int64)) > 3900))
+            assert breaks >= 40 and n_na == 24 * int(np.count_nonzero(~mask)) and n_tok == 24 * p.shape[0]
 
 
 @pytest.mark.parametrize("tag,flags", [("refw", []), ("refp", ["--phased"])])
@@ -305,14 +314,17 @@ def _bed(text):
     ("ref", ["--lod-cutoff", "-12", "--size-bounds", "50000", "200000"]),
     ("refw", ["--weighted", "--map", os.path.join(E2E, "tiny.map"), "--ld-subsample", "0", "--cm", "--lod-cutoff", "-4",
               "--size-bounds", "0.05", "0.2"]),
-    ("reft", ["--tgls", os.path.join(E2E, "tiny.tgls.gz"), "--gl-type", "GQ", "--lod-cutoff", "-11", "--size-bounds", "50000", "200000"])])
+    ("reft", ["--tgls", os.path.join(E2E, "tiny.tgls.gz"), "--gl-type", "GQ", "--lod-cutoff", "-11", "--size-bounds", "50000", "200000"]),
+    ("refg", ["--winsize", "10", "--max-gap", "3900", "--lod-cutoff", "-4", "--size-bounds", "20000", "50000"])])
 def test_roh_calls_match_reference_binary(tmp_path, tag, flags):
     """--lod-cutoff / --size-bounds: calcLODWindows + assembleROHWindows + writeROHData of the prebuilt binary (the
     .roh.bed in tests/golden/e2e) against the tool, whose device goes from the genotypes to the segments without scores
     or counts: every individual's chromosome / start / stop / size class / size / colour lines, in bp and in cM, and from
-    per-genotype likelihoods"""
+    per-genotype likelihoods; refg: --winsize 10 with a --max-gap that cuts every chromosome into 40 and more runs"""
     if tag == "reft":
         out = run_tool_tgls(tmp_path, "--winsize", "30", *flags)
+    elif tag == "refg":
+        out = run_tool(tmp_path, *flags)
     else:
         out = run_tool(tmp_path, "--winsize", "30", *flags)
     ref_text = gzip.open(os.path.join(E2E, tag + ".roh.bed.gz"), "rt").read()

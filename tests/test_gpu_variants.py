@@ -7,6 +7,7 @@ import pytest
 
 import oracle_lib as ol
 from garlic_amd import abi
+from run_cases import oracle_segments as _oracle_segments
 
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -491,17 +492,6 @@ def test_tgls_from_dictionary_codes(gpu_ctx):
             assert ol.bits_equal(np.ascontiguousarray(out[c]), want), c
         with pytest.raises(abi.GarlicError):      # a caller's table holds at most 256 values (one-byte codes)
             panel.set_gl_codes(codes[0], np.linspace(0.1, 0.9, 257))
-
-
-def _oracle_segments(chroms, scores, W, cutoff, mg, frac):
-    """the oracle's scores through the oracle's inWin[] loop and its restatement of the segment walk (pinned against the
-    real assembleROHWindows in tests/test_oracle_vs_ref.py) -> [(individual, chromosome, first SNP, last SNP)] in the
-    reference's order"""
-    out = []
-    for c, (g, f, p, cs, ce) in enumerate(chroms):
-        cov = ol.oracle_roh_coverage(np.ascontiguousarray(scores[c]), W, cutoff)
-        out += [(i, c, a, b) for i, a, b in ol.oracle_roh_segments(cov, p, cs, ce, W, mg, frac)]
-    return sorted(out)
 
 
 @pytest.mark.parametrize("W", [2, 30, 100, 250])
