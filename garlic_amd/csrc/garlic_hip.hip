@@ -23,6 +23,7 @@
 #include "feed_sort_kernel.hpp"
 #include "kde_kernels.hpp"
 #include "../host/kde_select.hpp"
+#include "../host/chain_order.hpp"
 #include "bed_kernels.hpp"
 
 #include <algorithm>
@@ -432,7 +433,10 @@ struct garlic_panel {
     int32_t multi_chain_launches = 0, multi_term_builds = 0;
     garlic_call_stats stats{};
     bool stats_pending = false;                    // event times of the last call not read yet
+    bool stats_one_kernel = false;                 // ... and that call was one kernel between the pair of stats_slot, nothing else recorded
     int stats_slot = 0;                            // the context's event pair that brackets its dominant kernel
+    int64_t n_stall_reruns = 0;                    // garlic_call_stats::n_stall_reruns as last read from the device
+    bool reruns_stale = false;                     // a strip launch since (launch_wlod): the device's count may have moved
     int64_t n_count_timeouts = 0;                  // garlic_call_stats::n_count_timeouts
     struct Placement { int32_t drawn = 0, rounds = 0; float best_ms = 0, median_ms = 0, worst_ms = 0, target_ms = 0; int32_t reached = 0; };
     Placement placement;                           // the last garlic_panel_alloc_scores on this panel
@@ -1934,6 +1938,14 @@ struct LodWork {
     std::vector<int32_t> feed_blocks;              // wlod_feed_kernel: the blocks in play (its column groups: tiles)
 };
 
+// persistent workgroups of lod_chain_kernel: one per CU (GARLIC_WORKERS: another count), no more than there are items
+int chain_workers(const garlic_ctx *ctx, size_t n_items)
+{
+    int workers = ctx->n_cu;
+    if (const char *e = getenv("GARLIC_WORKERS")) workers = std::max(1, atoi(e));
+    return std::min<int>(workers, (int)n_items);
+}
+
 // Runs, chain / feed items, the wLOD kernels' tiles, segments and strips, the ChrDev table; room for them on the device.
 int plan_lod(garlic_panel *p, const LodCall &c, const LodForm &form, const Layout &L, const garlic_panel::PlanKey &key, LodWork &w, Plan &plan)
 {
@@ -1963,6 +1975,16 @@ int plan_lod(garlic_panel *p, const LodCall &c, const LodForm &form, const Layou
         }
         if (form.slab_blocks) plan.slabs.push_back(Plan::Slab{c.ind_begin / WAVE + k0, c.ind_begin / WAVE + k1, item0, w.items.size() - item0});
         k0 = k1;
+    }
+    if (form.family == Family::chain && !form.slab_blocks) {
+        // lod_chain_kernel's list: the order a simulated pass ends soonest in (host/chain_order.hpp; longest first unless
+        // packing the items is simulated more than 1 % shorter) -- a function of the plan alone
+        std::vector<int32_t> len(w.items.size());
+        for (size_t i = 0; i < len.size(); i++) len[i] = w.items[i].b - w.items[i].a + 1;
+        const std::vector<int> at = garlic_host::chainOrder(len, chain_workers(p->ctx, len.size()));
+        std::vector<ChainItem> sorted(w.items.size());
+        for (size_t i = 0; i < at.size(); i++) sorted[i] = w.items[(size_t)at[i]];
+        w.items.swap(sorted);
     }
     if (form.family == Family::feed) {
         // the thinned score matrix: row = individual, column = locus / step
@@ -2192,12 +2214,20 @@ int launch_wlod(garlic_panel *p, const LodCall &c, const LodForm &form, const Pl
         if (form.strip_force_rerun) HIP_TRY(hipMemsetAsync(p->d_counter.p + 3, 1, sizeof(int32_t), s));
         a.run_if = p->d_counter.p + 3;
         a.rerun_count = p->d_counter.p + 4;
+        p->reruns_stale = true;
     }
     const void *fn = wlod_tile_fn(form.family, form.wlod_gl, form.aligned16);
     if (form.tile_lds > LDS_DEFAULT_MAX) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)form.tile_lds));
     void *kargs[] = {(void *)&a_packed, (void *)&a_wtab, (void *)&a_skew, (void *)&d_out, (void *)&a};
     HIP_TRY(hipLaunchKernel(fn, dim3((a.n_work + 7u) / 8u * 8u), wl_block, kargs, form.tile_lds, s));
     return GARLIC_OK;
+}
+
+// the launch of lod_chain_kernel writes the plan's MISSING stretches itself: full scores of the unweighted chain with a run to
+// score.  Every other family, and a plan with nothing to score (no chain launch), leaves them to fill_missing_kernel.
+bool chain_takes_fill(const LodForm &form, const Plan &plan, Family family)
+{
+    return family == Family::chain && plan.n_items && plan.n_fill && !form.wlod_tuned && !form.cov_bits;
 }
 
 // unweighted --error scores: the persistent chain kernel, or for thinned output the feed kernel (its grid is chosen from a fresh plan)
@@ -2215,7 +2245,12 @@ int launch_chain(garlic_panel *p, const LodCall &c, const LodForm &form, Plan &p
         HIP_TRY(hipLaunchKernel((const void *)lod_feed_kernel, dim3((unsigned)grid), dim3(FEED_G * WAVE), kargs, 0, ctx->stream));
     } else {
         ChainArgs a{p->d_packed.p, p->d_tab.p, p->d_items.p,     p->d_chrs.p,          d_out, p->nind_pad, p->nwordrows,
-                    c.ind_begin,   c.ind_count, c.W,             (int32_t)plan.n_items, p->d_counter.p, nullptr};
+                    c.ind_begin,   c.ind_count, c.W,             (int32_t)plan.n_items, p->d_counter.p, nullptr,
+                    nullptr,       0};
+        if (chain_takes_fill(form, plan, form.family)) {
+            a.fill = p->d_fill.p;
+            a.n_fill = (int32_t)plan.n_fill;
+        }
         a.trace = trace.begin(4, plan.n_items, " 0\n", ctx->stream);      // (a fifth column of zeros: the readers of the chain trace expect it)
         if (form.aligned16)
             hipLaunchKernelGGL((lod_chain_kernel<true>), dim3((unsigned)workers), dim3(CHAIN_THREADS), 0, ctx->stream, a);
@@ -2410,13 +2445,14 @@ int launch_wlod_slabs(garlic_panel *p, const LodCall &c, const LodForm &form, co
 // Everything a call puts on the stream (a second time, as Family::exact, when the rescan found a -9999.0).  (Replaying a repeated
 // asynchronous pass as one HIP graph -- counter reset, MISSING fill, chain kernel, events -- was measured: no difference, the
 // 1.6 ms kernel hides the launch gaps of the small operations once passes are enqueued back to back.)
+// one_kernel: the pass is the chain kernel and nothing else (launch_lod); the event pair around it times the call too
 int enqueue_lod(garlic_panel *p, const LodCall &c, const LodForm &form, const Layout &L, Plan &plan, const LodWork *fresh,
-                double *d_out, Family family)
+                double *d_out, Family family, bool one_kernel = false)
 {
     garlic_ctx *ctx = p->ctx;
     hipStream_t s = ctx->stream;
     int rc = GARLIC_OK;
-    HIP_TRY(hipEventRecord(ctx->ev_begin, s));
+    if (!one_kernel) HIP_TRY(hipEventRecord(ctx->ev_begin, s));
     if (fresh && ((rc = p->d_chrs.put(fresh->chrs, s)) || (rc = p->d_items.put(fresh->items, s)) || (rc = p->d_fill.put(fresh->fill, s)) ||
                   (rc = p->d_feed_items.put(fresh->feed_items, s)) || (rc = p->d_valid.put(fresh->valid, s)) ||
                   (rc = p->d_tiles.put(fresh->tiles, s)) || (rc = p->d_segs.put(fresh->segs, s)) || (rc = p->d_strips.put(fresh->strips, s)) ||
@@ -2424,7 +2460,8 @@ int enqueue_lod(garlic_panel *p, const LodCall &c, const LodForm &form, const La
         return rc;
     if (family == Family::feed || family == Family::tgls_feed) {          // small matrix: MISSING everywhere, the chain kernel overwrites the scored samples
         hipLaunchKernelGGL(fill_value_kernel, dim3(1024), dim3(256), 0, s, d_out, L.total, MISSING_D);
-    } else if (plan.n_fill && !form.wlod_tuned && family != Family::wlod_feed && !form.cov_bits) {   // the tuned and the sampled wLOD kernels write MISSING themselves
+    } else if (plan.n_fill && !form.wlod_tuned && family != Family::wlod_feed && !form.cov_bits &&
+               !chain_takes_fill(form, plan, family)) {   // the tuned and the sampled wLOD kernels and the chain kernel write MISSING themselves
         dim3 grid((unsigned)plan.n_fill, (unsigned)((c.ind_count + FILL_ROWS - 1) / FILL_ROWS));
         hipLaunchKernelGGL(fill_missing_kernel, grid, dim3(256), 0, s, p->d_fill.p, p->d_chrs.p, c.ind_count, d_out);
     }
@@ -2436,9 +2473,7 @@ int enqueue_lod(garlic_panel *p, const LodCall &c, const LodForm &form, const La
     // Persistent workgroups (4 waves each: CHAIN, POST, PRE, COMB), one per CU; items are pulled longest
     // first, so the short runs pack behind the long ones instead of competing with them for HBM
     // bandwidth.
-    int workers = ctx->n_cu;
-    if (const char *e = getenv("GARLIC_WORKERS")) workers = std::max(1, atoi(e));
-    workers = std::min<int>(workers, (int)plan.n_items);
+    const int workers = chain_workers(ctx, plan.n_items);
     if (form.wlod_tuned || plan.n_items || family == Family::wlod_feed)
         switch (family) {
         case Family::chain:
@@ -2505,7 +2540,12 @@ int launch_lod(garlic_panel *p, Mode mode, int32_t W, double error, int32_t max_
     LodWork work;
     if (!reuse && (rc = plan_lod(p, c, form, L, key, work, plan))) return rc;
 
-    if ((rc = enqueue_lod(p, c, form, L, plan, reuse ? nullptr : &work, d_out, form.family))) return rc;
+    // A repeated asynchronous pass of the unweighted chain is one kernel between one pair of events: no fill launch (the chain
+    // kernel writes the MISSING stretches), no counter reset, no rescan -- and the call's own pair of events, which would
+    // bracket the same kernel, is not recorded (garlic_last_call_stats reads both times from the one pair)
+    const bool one_kernel = ctx->async_device && where == GARLIC_DEVICE && reuse && mode == MODE_LOD && form.family == Family::chain &&
+                            plan.n_items && (!plan.n_fill || chain_takes_fill(form, plan, form.family)) && !form.exact_possible;
+    if ((rc = enqueue_lod(p, c, form, L, plan, reuse ? nullptr : &work, d_out, form.family, one_kernel))) return rc;
     p->last_chain_kind = form.family == Family::exact ? 2 : 0;
     if (form.exact_possible && form.family != Family::exact && plan.n_items) {
         // the reference tests "no score" by value: did a scored window of the tuned chain come out as exactly -9999.0?
@@ -2526,13 +2566,14 @@ int launch_lod(garlic_panel *p, Mode mode, int32_t W, double error, int32_t max_
             HIP_TRY(hipMemcpy2DAsync(out + Lhost.base[k], sizeof(double) * Lhost.pitch[k], d_out + L.base[k],
                                      sizeof(double) * L.pitch[k], sizeof(double) * p->chr_nloci[k],
                                      (size_t)ind_count, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev_end, ctx->stream));
+    if (!one_kernel) HIP_TRY(hipEventRecord(ctx->ev_end, ctx->stream));
     // The work list lives in host vectors and per-panel device scratch: finish before returning --
     // unless the context is asynchronous, the output stays on the device and the plan (already
     // resident) is being reused: then nothing on the host is needed again and the call only enqueues.
     const bool enqueue_only = ctx->async_device && where == GARLIC_DEVICE && reuse;
     if (!enqueue_only) HIP_TRY(hipStreamSynchronize(ctx->stream));
     p->stats_pending = true;
+    p->stats_one_kernel = one_kernel;
     plan.valid = true;
     p->plan = plan;
 
@@ -5334,19 +5375,25 @@ int garlic_last_call_stats(garlic_panel *p, garlic_call_stats *stats)
     if (p->stats_pending) {   // the event times of the last call (waits for it if it is still running)
         int rc;
         if ((rc = set_device(p->ctx))) return rc;
-        HIP_TRY(hipEventSynchronize(p->ctx->ev_end));
+        // (a one-kernel pass recorded only the pair around its kernel: the call's time is the kernel's)
+        HIP_TRY(hipEventSynchronize(p->stats_one_kernel ? p->ctx->hist1[p->stats_slot] : p->ctx->ev_end));
         (void)hipEventElapsedTime(&p->stats.chain_kernel_ms, p->ctx->hist0[p->stats_slot], p->ctx->hist1[p->stats_slot]);
-        (void)hipEventElapsedTime(&p->stats.total_ms, p->ctx->ev_begin, p->ctx->ev_end);
+        if (p->stats_one_kernel) p->stats.total_ms = p->stats.chain_kernel_ms;
+        else (void)hipEventElapsedTime(&p->stats.total_ms, p->ctx->ev_begin, p->ctx->ev_end);
         p->stats_pending = false;
     }
-    if (p->d_counter.p) {      // strip launches the tile form had to repair (counted on the device; waits for the stream)
+    // Strip launches the tile form had to repair, counted on the device: read once after a call that launched the strip
+    // kernel (that call has been waited for by now), not on every poll -- the copy waits for whatever the stream holds.
+    if (p->reruns_stale && p->d_counter.p) {
         int32_t n = 0;
         int rc;
         if ((rc = set_device(p->ctx))) return rc;
         HIP_TRY(hipMemcpyAsync(&n, p->d_counter.p + 4, sizeof(int32_t), hipMemcpyDeviceToHost, p->ctx->stream));
         HIP_TRY(hipStreamSynchronize(p->ctx->stream));
-        p->stats.n_stall_reruns = n;
+        p->n_stall_reruns = n;
+        p->reruns_stale = false;
     }
+    p->stats.n_stall_reruns = p->n_stall_reruns;
     p->stats.n_count_timeouts = p->n_count_timeouts;
     *stats = p->stats;
     return GARLIC_OK;

@@ -251,17 +251,22 @@ seg_compact_kernel(const int32_t *pos, const int64_t *chr_off, const int32_t *cs
 // every output element is written exactly once, so no memset pass over the whole output).
 // grid.x = fill item, grid.y = group of rows; lanes run along the SNP axis (contiguous bytes).
 constexpr int FILL_ROWS = 16;
+// one (fill item, group of FILL_ROWS rows) by `nwaves` wavefronts, this one the wave-th of them
+__device__ __forceinline__ void fill_rows(const FillItem &it, const ChrDev &c, int row0, int32_t nind, double *out,
+                                          int wave, int nwaves, int lane)
+{
+    for (int r = row0 + wave; r < row0 + FILL_ROWS && r < nind; r += nwaves) {
+        double *row = out + c.out_base + (int64_t)r * c.out_pitch;
+        for (int l = it.lo + lane; l < it.hi; l += WAVE) row[l] = MISSING_D;
+    }
+}
+
 __global__ void __launch_bounds__(256)
 fill_missing_kernel(const FillItem *items, const ChrDev *chrs, int32_t nind, double *out)
 {
     FillItem it = items[blockIdx.x];
     ChrDev c = chrs[it.chr];
-    int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    int row0 = blockIdx.y * FILL_ROWS;
-    for (int r = row0 + wave; r < row0 + FILL_ROWS && r < nind; r += 4) {
-        double *row = out + c.out_base + (int64_t)r * c.out_pitch;
-        for (int l = it.lo + lane; l < it.hi; l += WAVE) row[l] = MISSING_D;
-    }
+    fill_rows(it, c, blockIdx.y * FILL_ROWS, nind, out, threadIdx.x >> 6, 4, threadIdx.x & 63);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -281,7 +286,23 @@ struct ChainArgs {
     int32_t *next_item;       // [0] the persistent workgroups' queue head, [1] workgroups that have left; both zero
                               // at launch (the last workgroup to leave resets them)
     int64_t *trace;           // optional (GARLIC_TRACE): per item {worker, t_begin, t_asm, t_end} in 100 MHz ticks
+    const FillItem *fill;     // the plan's MISSING stretches, written by this launch (n_fill == 0: by fill_missing_kernel, or none)
+    int32_t n_fill;
 };
+
+// The MISSING stretches inside the chain launch: the (fill item, group of FILL_ROWS rows) units go round the workgroups,
+// waves first .. 3 of a workgroup share a unit's rows (fill_missing_kernel's stores).  No order against the scores is needed: a
+// fill stretch is never a scored window of the same plan, every cell is written once.
+__device__ __forceinline__ void chain_fill_share(const ChainArgs &p, int wave, int first, int lane)
+{
+    const int groups = (p.ind_count + FILL_ROWS - 1) / FILL_ROWS;
+    const int64_t units = (int64_t)p.n_fill * groups;
+    for (int64_t u = blockIdx.x; u < units; u += gridDim.x) {
+        const FillItem it = p.fill[u / groups];
+        const ChrDev c = p.chrs[it.chr];
+        fill_rows(it, c, (int)(u % groups) * FILL_ROWS, p.ind_count, p.out, wave - first, 4 - first, lane);
+    }
+}
 
 // LDS map (bytes).  One workgroup = 4 waves (CHAIN, POST, PRE, COMB roles) working on one item; the hand-scheduled loop
 // (chain_loop_gfx950.inc, see tools/gen_chain_asm.py for the full map) owns everything from 4096
@@ -435,6 +456,11 @@ lod_chain_kernel(ChainArgs p)
     // first, from one device-wide counter.  Wave 0 owns the accumulator: it sums the run's first
     // window and runs the first / last (partial) tiles through the compiler-generated path; all
     // full tiles go through the 4-role hand-scheduled loop.
+    // This workgroup's share of the MISSING stretches goes out behind its first pull, from the three waves that have
+    // nothing to do while wave 0 sums the first window of the item: stores where the launch otherwise only loads (every
+    // CU is in its first prologue at once), drained by the time the waves meet at the loop's first barrier.  A workgroup
+    // that finds the queue empty at its first pull (others were faster) writes its share with all four waves.
+    bool fill_pending = p.n_fill > 0;
     for (;;) {
     if (threadIdx.x == 0)
         *reinterpret_cast<int *>(smem + LDS_ITEM) = atomicAdd(p.next_item, 1);
@@ -443,6 +469,7 @@ lod_chain_kernel(ChainArgs p)
         __builtin_amdgcn_readfirstlane(*reinterpret_cast<const int *>(smem + LDS_ITEM));   // (barriers on both sides)
     __syncthreads();
     if (item_idx >= p.n_items) {
+        if (fill_pending) chain_fill_share(p, wave, 0, lane);
         // the last workgroup to leave puts the queue head (and this exit count) back to zero for
         // the next launch: one operation less between two passes
         if (threadIdx.x == 0) {
@@ -457,6 +484,10 @@ lod_chain_kernel(ChainArgs p)
     if (p.trace && threadIdx.x == 0) {
         p.trace[4 * item_idx + 0] = blockIdx.x;
         p.trace[4 * item_idx + 1] = wall_clock64();
+    }
+    if (fill_pending) {
+        if (wave != 0) chain_fill_share(p, wave, 1, lane);
+        fill_pending = false;
     }
     const ChainItem it = p.items[item_idx];
     const ChrDev c = p.chrs[it.chr];
