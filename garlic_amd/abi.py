@@ -46,8 +46,10 @@ SYMBOLS = [
     "garlic_panel_set_gl_codes16",
     "garlic_bed_create", "garlic_bed_set_rows", "garlic_bed_census", "garlic_bed_destroy", "garlic_panel_set_genotypes_bed",
     "garlic_feed_kde", "garlic_lod_kde", "garlic_feed_kde_info", "garlic_feed_kde_times",
+    "garlic_gmm_fit", "garlic_gmm_fit_info",
 ]
 KDE_POINTS = 512   # GARLIC_KDE_POINTS
+GMM_MAX_K = 8      # GARLIC_GMM_MAX_K
 
 
 class CallStats(C.Structure):
@@ -67,6 +69,19 @@ class Kde(C.Structure):
         d = {k: getattr(self, k) for k in ("n", "h", "sd", "q25", "q75", "lo", "hi")}
         for k in ("x", "y", "raw"):
             d[k] = np.array(getattr(self, k), dtype=np.float64)
+        return d
+
+
+class Gmm(C.Structure):
+    """garlic_gmm"""
+    _fields_ = [("k", C.c_int32), ("iterations", C.c_int32), ("converged", C.c_int32),
+                ("a", C.c_double * GMM_MAX_K), ("mean", C.c_double * GMM_MAX_K), ("var", C.c_double * GMM_MAX_K),
+                ("loglik", C.c_double), ("bic", C.c_double)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k in ("k", "iterations", "converged", "loglik", "bic")}
+        for k in ("a", "mean", "var"):
+            d[k] = np.array(getattr(self, k), dtype=np.float64)[:self.k]
         return d
 
 
@@ -167,6 +182,8 @@ def lib():
                                  _i32p, C.c_int32, C.POINTER(Kde), _i64p]
     L.garlic_feed_kde_info.argtypes = [_vp, _i64p, _i64p, _i64p]
     L.garlic_feed_kde_times.argtypes = [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.garlic_gmm_fit.argtypes = [_vp, _vp, C.c_int64, C.c_int32, C.c_int32, _f64p, _f64p, _f64p, C.c_int32, C.c_double, C.POINTER(Gmm)]
+    L.garlic_gmm_fit_info.argtypes = [_vp, _i64p, _i64p, C.POINTER(C.c_float)]
     L.garlic_bed_create.argtypes = [_vp, C.c_int64, C.c_int32, C.POINTER(_vp)]
     L.garlic_bed_set_rows.argtypes = [_vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32]
     L.garlic_bed_census.argtypes = [_vp, _vp, _vp, C.c_int32]
@@ -268,6 +285,31 @@ class Context:
         a, b = C.c_float(), C.c_float()
         check(lib().garlic_feed_kde_times(self.handle, C.byref(a), C.byref(b)))
         return {"moments_ms": a.value, "sums_ms": b.value}
+
+    def gmm_fit(self, values, a0, mean0, var0, n=None, max_iter=1000, precision=1e-5, out=None):
+        """garlic_gmm_fit: GMM::estimate's EM fit of len(a0) Gaussians, as a dict: k, iterations, converged, loglik, bic and
+        the float64 arrays a, mean, var [k].  values: a contiguous float64 numpy array (host; n defaults to its length) or
+        a device address (int) of n doubles.  out: an abi.Gmm to fill instead (returned as it is)."""
+        g = Gmm() if out is None else out
+        init = [np.ascontiguousarray(v, dtype=np.float64) for v in (a0, mean0, var0)]
+        k = init[0].shape[0]
+        assert all(v.shape == (k,) for v in init)
+        ptrs = [_ptr(v, _f64p) for v in init]
+        if isinstance(values, np.ndarray):
+            assert values.dtype == np.float64 and values.flags["C_CONTIGUOUS"] and values.ndim == 1
+            n = values.shape[0] if n is None else int(n)
+            assert n <= values.shape[0]
+            check(lib().garlic_gmm_fit(self.handle, _vp(values.ctypes.data), n, HOST, k, *ptrs, int(max_iter), float(precision), C.byref(g)))
+        else:
+            check(lib().garlic_gmm_fit(self.handle, _vp(values) if values else None, int(n), DEVICE, k, *ptrs, int(max_iter),
+                                       float(precision), C.byref(g)))
+        return g.as_dict() if out is None else out
+
+    def gmm_fit_info(self):
+        """garlic_gmm_fit_info: {blocks, scratch_bytes, em_ms} of the last GMM fit on this context"""
+        a, b, c = C.c_int64(), C.c_int64(), C.c_float()
+        check(lib().garlic_gmm_fit_info(self.handle, C.byref(a), C.byref(b), C.byref(c)))
+        return {"blocks": a.value, "scratch_bytes": b.value, "em_ms": c.value}
 
     def close(self):
         if self.handle:

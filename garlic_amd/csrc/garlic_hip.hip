@@ -22,6 +22,7 @@
 #include "wlod_feed_kernel.hpp"
 #include "feed_sort_kernel.hpp"
 #include "kde_kernels.hpp"
+#include "gmm_kernels.hpp"
 #include "../host/kde_select.hpp"
 #include "../host/chain_order.hpp"
 #include "bed_kernels.hpp"
@@ -153,6 +154,24 @@ struct KdeScratch {
     ~KdeScratch() { release(); }
 };
 
+// what garlic_gmm_fit keeps between calls (gmm_kernels.hpp): the blocks' partial sums, the state of the fit
+struct GmmScratch {
+    DevBuf<double> stage;                          // the values of a host-buffer call
+    DevBuf<double> partial;
+    DevBuf<GmmState> state;
+    hipEvent_t ev[2] = {};                         // around the EM loop (garlic_gmm_fit_info)
+    size_t bytes() const { return (stage.cap + partial.cap) * sizeof(double) + state.cap * sizeof(GmmState); }
+    void release()
+    {
+        stage.release(); partial.release(); state.release();
+        for (auto &e : ev) {
+            if (e) (void)hipEventDestroy(e);
+            e = nullptr;
+        }
+    }
+    ~GmmScratch() { release(); }
+};
+
 // lod(), src/garlic-roh.cpp:355-386.  Host arithmetic, host libm: identical to the reference.
 double host_lod(int genotype, double freq, double error)
 {
@@ -217,6 +236,10 @@ struct garlic_ctx {
     KdeScratch kde;
     int64_t kde_chunks = 0, kde_skipped = 0;
     float kde_moments_ms = 0.f, kde_sums_ms = 0.f;
+    // garlic_gmm_fit: its scratch, and what garlic_gmm_fit_info reports
+    GmmScratch gmm;
+    int64_t gmm_blocks = 0;
+    float gmm_em_ms = 0.f;
 };
 
 static int score_alloc(garlic_ctx *ctx, size_t bytes, void **out);   // pooled score memory (below)
@@ -4129,7 +4152,7 @@ int garlic_panel_release_scratch(garlic_panel *p)
     p->lds.release();
     p->d_out.release(); p->d_feed.release();
     p->d_stage16.release(); p->d_stage64.release(); p->d_bed_word_rows.release();
-    p->fs.release(); p->ctx->fs.release(); p->ctx->kde.release();
+    p->fs.release(); p->ctx->fs.release(); p->ctx->kde.release(); p->ctx->gmm.release();
     for (auto *sl : p->feed_slots) {
         HIP_TRY(hipStreamSynchronize(sl->stream));
         sl->fs.release();
@@ -5738,6 +5761,94 @@ int garlic_lod_kde(garlic_panel *p, int32_t winsize, double error, int32_t max_g
     if (rc) return rc;
     if (count < 2 || sink.n != count) return fail(GARLIC_ERR_INVALID, "feed KDE: needs at least 2 values (the feed holds %lld)", (long long)count);
     return kde_device(p->ctx, sink.data, sink.n, out);
+}
+
+// ---- GMM::estimate on the device (gmm_kernels.hpp).  One update is a pass over the points and the finish that turns the
+// blocks' partial sums into the next parameters (one launch when the pass is a single workgroup).  The host enqueues
+// GMM_BATCH updates at a time and reads the state once per batch: every kernel behind the update that met the stop rule
+// returns at once, so a batch costs no blocking round trip per iteration and at most GMM_BATCH - 1 empty updates.
+int garlic_gmm_fit(garlic_ctx *ctx, const double *x, int64_t n, int32_t where, int32_t k, const double *a0, const double *mean0,
+                   const double *var0, int32_t max_iter, double precision, garlic_gmm *out)
+{
+    static_assert(GMM_MAX_K == GARLIC_GMM_MAX_K, "one K limit");
+    if (!ctx || !out || !x || !a0 || !mean0 || !var0) return fail(GARLIC_ERR_INVALID, "GMM fit: context, values, initial parameters and out are required");
+    if (where != GARLIC_HOST && where != GARLIC_DEVICE) return fail(GARLIC_ERR_INVALID, "GMM fit: where must be GARLIC_HOST or GARLIC_DEVICE");
+    if (n < 1) return fail(GARLIC_ERR_INVALID, "GMM fit: needs at least 1 value (got %lld)", (long long)n);
+    if (k < 1 || k > GARLIC_GMM_MAX_K) return fail(GARLIC_ERR_INVALID, "GMM fit: %d Gaussians (1 to %d)", (int)k, GARLIC_GMM_MAX_K);
+    if (max_iter < 1) return fail(GARLIC_ERR_INVALID, "GMM fit: max_iter must be at least 1 (got %d)", (int)max_iter);
+    const int64_t n_blocks = (n + GMM_BLOCK_POINTS - 1) / GMM_BLOCK_POINTS;
+    if (n_blocks > 0x7fffffff) return fail(GARLIC_ERR_INVALID, "GMM fit: %lld values are more blocks than one launch holds", (long long)n);
+    int rc;
+    if ((rc = set_device(ctx))) return rc;
+    GmmScratch &g = ctx->gmm;
+    if ((where == GARLIC_HOST && (rc = g.stage.reserve((size_t)n))) || (rc = g.partial.reserve((size_t)n_blocks * 2 * (3 * (size_t)k + 1))) ||
+        (rc = g.state.reserve(1)))
+        return rc;
+    for (auto &e : g.ev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    hipStream_t s = ctx->stream;
+    const double *d_x = x;
+    if (where == GARLIC_HOST) {
+        HIP_TRY(hipMemcpyAsync(g.stage.p, x, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
+        d_x = g.stage.p;
+    }
+    GmmState st;
+    memset(&st, 0, sizeof st);
+    for (int i = 0; i < k; i++) {
+        st.a[i] = a0[i];
+        st.mean[i] = mean0[i];
+        st.var[i] = var0[i];
+    }
+    st.loglik = st.prev = -std::numeric_limits<double>::max();   // GMM::GMM, src/gmm.cpp:201-202
+    st.bic = std::numeric_limits<double>::max();
+    HIP_TRY(hipMemcpyAsync(g.state.p, &st, sizeof st, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));              // st is written below
+    const double log_n = log((double)n);
+    HIP_TRY(hipEventRecord(g.ev[0], s));
+    for (int done = 0; done < max_iter && !st.converged;) {
+        const int updates = std::min<int>(GMM_BATCH, max_iter - done);
+        switch (k) {
+        case 1: gmm_enqueue<1>(s, d_x, n, n_blocks, log_n, precision, g.state.p, g.partial.p, updates); break;
+        case 2: gmm_enqueue<2>(s, d_x, n, n_blocks, log_n, precision, g.state.p, g.partial.p, updates); break;
+        case 3: gmm_enqueue<3>(s, d_x, n, n_blocks, log_n, precision, g.state.p, g.partial.p, updates); break;
+        case 4: gmm_enqueue<4>(s, d_x, n, n_blocks, log_n, precision, g.state.p, g.partial.p, updates); break;
+        case 5: gmm_enqueue<5>(s, d_x, n, n_blocks, log_n, precision, g.state.p, g.partial.p, updates); break;
+        case 6: gmm_enqueue<6>(s, d_x, n, n_blocks, log_n, precision, g.state.p, g.partial.p, updates); break;
+        case 7: gmm_enqueue<7>(s, d_x, n, n_blocks, log_n, precision, g.state.p, g.partial.p, updates); break;
+        default: gmm_enqueue<8>(s, d_x, n, n_blocks, log_n, precision, g.state.p, g.partial.p, updates); break;
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&st, g.state.p, sizeof st, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        done += updates;
+    }
+    HIP_TRY(hipEventRecord(g.ev[1], s));
+    HIP_TRY(hipEventSynchronize(g.ev[1]));
+    garlic_gmm r;
+    memset(&r, 0, sizeof r);
+    r.k = k;
+    r.iterations = st.iterations;
+    r.converged = st.converged;
+    for (int i = 0; i < k; i++) {
+        r.a[i] = st.a[i];
+        r.mean[i] = st.mean[i];
+        r.var[i] = st.var[i];
+    }
+    r.loglik = st.loglik;
+    r.bic = st.bic;
+    ctx->gmm_blocks = n_blocks;
+    if (hipEventElapsedTime(&ctx->gmm_em_ms, g.ev[0], g.ev[1]) != hipSuccess) ctx->gmm_em_ms = 0.f;
+    *out = r;
+    return GARLIC_OK;
+}
+
+int garlic_gmm_fit_info(garlic_ctx *ctx, int64_t *blocks, int64_t *scratch_bytes, float *em_ms)
+{
+    if (!ctx) return fail(GARLIC_ERR_INVALID, "context is NULL");
+    if (blocks) *blocks = ctx->gmm_blocks;
+    if (scratch_bytes) *scratch_bytes = (int64_t)ctx->gmm.bytes();
+    if (em_ms) *em_ms = ctx->gmm_em_ms;
+    return GARLIC_OK;
 }
 
 int garlic_lod_feed_info(garlic_panel *p, int32_t *form, int64_t *score_doubles)

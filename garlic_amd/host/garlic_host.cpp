@@ -1662,6 +1662,28 @@ std::vector<ROHData *> *LodEngine::assembleROHWindows(IndData *indData, double l
     return rohDataByInd;
 }
 
+// selectSizeClasses, garlic-roh.cpp:935-1003: the initial guess on the host (one pass over doubles it already holds), the
+// EM fit on the first device, ordering, log lines and boundaries on the host (size_classes.hpp)
+std::vector<double> LodEngine::selectSizeClasses(const ROHLength *rohLength, int nclust)
+{
+    static_assert(GMM_MAX_K == GARLIC_GMM_MAX_K, "one K limit");
+    if (!rohLength || rohLength->size < 1) fail("selectSizeClasses: no ROH segments to fit size classes to");
+    if (nclust < 1 || nclust > GMM_MAX_K) fail("selectSizeClasses: " + std::to_string(nclust) + " size classes (1 to " + std::to_string(GMM_MAX_K) + ")");
+    const int64_t n = (int64_t)rohLength->size;
+    double a[GMM_MAX_K], mean[GMM_MAX_K], var[GMM_MAX_K];
+    sizeClassInit(rohLength->length, n, nclust, a, mean, var);
+    garlic_gmm g;
+    if (garlic_gmm_fit(impl->shards[0].ctx, rohLength->length, n, GARLIC_HOST, nclust, a, mean, var, GMM_MAX_ITER, GMM_PRECISION, &g) != GARLIC_OK)
+        fail(std::string("garlic_gmm_fit: ") + garlic_hip_last_error());
+    std::cerr << "GMM with " << nclust << " Gaussians on the device: " << g.iterations << " EM iterations"
+              << (g.converged ? "" : " (not converged)") << ", log likelihood " << g.loglik << "\n";
+    std::cerr << sizeClassLines(g.a, g.mean, g.var, nclust);
+    std::vector<double> bounds;
+    std::string why;
+    if (!sizeClassBounds(g.a, g.mean, g.var, nclust, &bounds, &why)) fail(why);
+    return bounds;
+}
+
 // The callers that sweep window sizes on one data set -- exploreWinsizes (garlic-roh.cpp:726-751), selectWinsize
 // (:798-837), selectWinsizeFromList (:881-920) -- through garlic_lod_feed_multi (unweighted --error scores) or, when the
 // engine holds per-genotype likelihoods (USE_GL; the sweeps run with --tgls as with --error), garlic_lod_feed_multi_tgls.  The

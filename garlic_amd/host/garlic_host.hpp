@@ -16,6 +16,7 @@
 
 #include "feed_merge.hpp"
 #include "kde_select.hpp"
+#include "size_classes.hpp"
 
 namespace garlic_host {
 
@@ -365,6 +366,12 @@ public:
     std::vector<ROHData *> *assembleROHWindows(IndData *indData, double lodScoreCutoff, ROHLength **rohLength, int winSize,
                                                double error, int MAX_GAP, double OVERLAP_FRAC, bool CM, bool weighted = false,
                                                int M = 0, double mu = 0.0);
+    // selectSizeClasses (garlic-roh.cpp:935-1003): the nclust-component Gaussian mixture of the pooled lengths that
+    // assembleROHWindows returns (individual order, bp or cM), fitted by EM on the engine's first device (garlic_gmm_fit),
+    // and the nclust - 1 boundaries between the classes ordered by mean (size_classes.hpp).  The fit is a function of the
+    // lengths alone, so one shard or several give the same bits.  Prints the reference's "Gaussian class" lines to stderr;
+    // `throw 0` where the reference aborts (no sign change between two means, no convergence of the root search).
+    std::vector<double> selectSizeClasses(const ROHLength *rohLength, int nclust);
     // garlic_panel_tgls_terms_info of the first shard: the slabs of its last call with likelihoods, weighted or not (n_slabs 0: none)
     void tglsTermSlabs(int *slab_blocks, int *n_slabs);
     LodEngine(const LodEngine &) = delete;

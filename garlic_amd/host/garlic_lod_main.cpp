@@ -16,7 +16,10 @@
 //                                          not written; "Selected LOD score cutoff: X" on stderr (get_min_btw_modes), and
 //                                          with --size-bounds and no --lod-cutoff the ROH calls at that cutoff.  With
 //                                          --auto-winsize the tool runs selectWinsize / selectWinsizeFromList itself.
-// The GMM size classes stay in GARLIC (--size-bounds is required for ROH calls).
+// --nclust K (GARLIC's flag) instead of --size-bounds: selectSizeClasses (src/garlic-roh.cpp:935-1003) -- a K-component
+// Gaussian mixture fitted to the ROH lengths by EM on the device, the class boundaries from a root search on the host;
+// the "Gaussian class" and "Selected ROH size boundaries" lines go to stderr.  Without --nclust nothing changes:
+// --size-bounds is then required for ROH calls.
 #include "garlic_host.hpp"
 
 #include <algorithm>
@@ -54,6 +57,7 @@ struct Args {
     bool have_cutoff = false, cm = false;   // --lod-cutoff (src/garlic-cli.cpp:101), --cm (:167)
     double lod_cutoff = 0.0;
     std::vector<double> size_bounds;        // --size-bounds (:107)
+    int nclust = 0;                         // --nclust (:163): the size classes from the GMM of the ROH lengths; 0 = not given
 };
 
 [[noreturn]] void usage(const char *msg)
@@ -69,6 +73,8 @@ struct Args {
                  "         (--tgls-term-gb X: at most X GB of TGLS terms per device, built and read in slabs; binds --weighted --tgls too)\n"
                  "         [--sorted-feed]   (the KDE feeds ascending, as nrd0's gsl_sort leaves them: <out>.<W>SNPs.lod.sorted.f64)\n"
                  "         [--lod-cutoff X --size-bounds B1 B2 ... [--cm]]   (ROH calls: <out>.roh.bed)\n"
+                 "         [--nclust K]   (instead of --size-bounds: K size classes, 1 to 8, from a Gaussian mixture fitted to the ROH\n"
+                 "                         lengths on the device; with --lod-cutoff or --kde)\n"
                  "         [--kde]   (<out>.<W>SNPs.kde and the LOD cutoff from the KDE on the device instead of the feed files; with\n"
                  "                    --size-bounds and no --lod-cutoff the ROH calls use it; with --auto-winsize the window size too)\n"
                  "         (--bfile / --bed --bim --fam: PLINK SNP-major .bed input, read on the device; not with --tped / --tfam /\n"
@@ -115,6 +121,11 @@ Args parse(int argc, char **argv)
         else if (f == "--size-bounds") {
             while (i + 1 < argc && (isdigit((unsigned char)argv[i + 1][0]) || argv[i + 1][0] == '.')) a.size_bounds.push_back(atof(argv[++i]));
         }
+        else if (f == "--nclust") {
+            a.nclust = atoi(val().c_str());
+            if (a.nclust <= 0) usage("Must choose positive number for number of GMM clusters.");   // checkNCLUST
+            if (a.nclust > GMM_MAX_K) usage("--nclust: at most 8 GMM clusters");
+        }
         else if (f == "--M") a.M = atoi(val().c_str());
         else if (f == "--mu") a.mu = atof(val().c_str());
         else if (f == "--threads") a.threads = atoi(val().c_str());
@@ -158,7 +169,9 @@ Args parse(int argc, char **argv)
     if (a.overlap_frac < 0 || a.overlap_frac > 1) usage("Overlap fraction must be >= 0 and <= 1.");
     if (a.weighted && a.map == "none") usage("--weighted needs --map");
     if (a.cm && a.map == "none") usage("--cm needs --map");
-    if (a.have_cutoff && a.size_bounds.empty())
+    if (a.nclust && !a.size_bounds.empty()) usage("--nclust and --size-bounds exclude each other (the size classes are fitted, or given)");
+    if (a.nclust && !a.have_cutoff && !a.kde) usage("--nclust classifies ROH calls and needs --lod-cutoff or --kde");
+    if (a.have_cutoff && a.size_bounds.empty() && !a.nclust)
         usage("--lod-cutoff writes the ROH calls and needs --size-bounds (the size classes otherwise come from GARLIC's GMM stage, "
               "Phase II, not part of this tool)");
     if (a.kde && a.raw_lod) usage("--kde and --raw-lod exclude each other (the KDE path keeps the scores on the device)");
@@ -311,7 +324,18 @@ int main(int argc, char **argv)
             std::vector<ROHData *> *roh = engine.assembleROHWindows(ind, cutoff, &len, W, a.error, a.max_gap, a.overlap_frac,
                                                                     a.cm, a.weighted, a.M, a.mu);
             std::cerr << "ROH segments: " << (long long)len->size << " (garlic-lod, MI355X; .roh.bed in the format of garlic 1.1.6a)\n";
-            writeROHData((single ? a.out : a.out + "." + std::to_string(W) + "SNPs") + ".roh.bed", roh, maps, a.size_bounds, ind->pop,
+            std::vector<double> bounds = a.size_bounds;
+            if (a.nclust) {      // garlic-main.cpp:393-398
+                try {
+                    bounds = engine.selectSizeClasses(len, a.nclust);
+                } catch (...) {
+                    releaseROHData(roh);
+                    releaseROHLength(len);
+                    throw;
+                }
+                std::cerr << sizeBoundsLine(bounds);
+            }
+            writeROHData((single ? a.out : a.out + "." + std::to_string(W) + "SNPs") + ".roh.bed", roh, maps, bounds, ind->pop,
                          "1.1.6a", a.cm);      // the track lines name the format's version (garlic VERSION); this tool says who it is on stderr
             releaseROHData(roh);
             releaseROHLength(len);
@@ -340,7 +364,7 @@ int main(int argc, char **argv)
                     throw 0;
                 }
                 std::cerr << "Selected LOD score cutoff: " << cutoff << "\n";
-                if (!a.size_bounds.empty()) roh_calls_at(W, single_out, a.have_cutoff ? a.lod_cutoff : cutoff);
+                if (!a.size_bounds.empty() || a.nclust) roh_calls_at(W, single_out, a.have_cutoff ? a.lod_cutoff : cutoff);
             };
             if (!a.auto_winsize) {
                 for (int W : sizes) finish(W, kde_of(W), 1.0, single);

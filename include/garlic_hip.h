@@ -53,7 +53,8 @@ extern "C" {
  *    garlic_feed_sort_info, GARLIC_FEED_ORDER_* (likewise); garlic_panel_set_phase_bits, garlic_panel_ld_form_info,
  *    GARLIC_LD_PAIR_* / GARLIC_LD_SUM_* (likewise); garlic_panel_set_gl_codes16, GARLIC_TGLS_DICTIONARY16 (likewise);
  *    garlic_bed_create, garlic_bed_set_rows, garlic_bed_census, garlic_bed_destroy, garlic_panel_set_genotypes_bed (likewise);
- *    garlic_kde, GARLIC_KDE_POINTS, garlic_feed_kde, garlic_lod_kde, garlic_feed_kde_info, garlic_feed_kde_times (likewise) */
+ *    garlic_kde, GARLIC_KDE_POINTS, garlic_feed_kde, garlic_lod_kde, garlic_feed_kde_info, garlic_feed_kde_times (likewise);
+ *    garlic_gmm, GARLIC_GMM_MAX_K, garlic_gmm_fit, garlic_gmm_fit_info (likewise) */
 #define GARLIC_HIP_ABI_VERSION 8
 
 #define GARLIC_OK 0
@@ -583,6 +584,39 @@ int garlic_lod_kde(garlic_panel *panel, int32_t winsize, double error, int32_t m
                    garlic_kde *out, int64_t *chr_counts);
 int garlic_feed_kde_info(garlic_ctx *ctx, int64_t *chunks, int64_t *pairs_skipped, int64_t *scratch_bytes);
 int garlic_feed_kde_times(garlic_ctx *ctx, float *moments_ms, float *sums_ms);
+
+/* GMM::estimate (src/gmm.cpp:385-442) on the device: the EM fit of a 1-D mixture of k Gaussians that selectSizeClasses
+ * (src/garlic-roh.cpp:935-1003) runs on the ROH lengths (csrc/gmm_kernels.hpp; the initial guess, the ordering of the
+ * classes and the boundaries between them: host/size_classes.hpp).  One update (GMM::update, :276-331), per point x_j:
+ *     r_i  = log(a_i) + (C - 0.5 log(var_i) - (x_j - mean_i)^2 / (2.0 var_i)),   C = -0.5 log(2 pi)
+ *     tmp  = l_max + log(sum_i exp(r_i - l_max)),  l_max = max_i r_i;   L += tmp
+ *     r_i <- exp(r_i - tmp),  den = sum_i r_i
+ *     S0_k += r_k / den,  S1_k += x_j * r_k / den,  S2_k += x_j * x_j * r_k / den
+ * then a_k = S0_k / n, mean_k = S1_k / S0_k, var_k = S2_k / S0_k - mean_k * mean_k, loglik = L,
+ * bic = -2 L + (3 k - 1) log(n) -- the reference's operations in its association, the n-term sums in a fixed tree that
+ * depends on n and k alone, each with the rounding errors of its adds carried in a second double and added at the end (a sum
+ * that is not finite: the plain sum), exp and log of the device library.  The fit stops after the first update with
+ * |L - L_prev| <= precision (L_prev starts at -DBL_MAX; a NaN never stops it, nor does precision < 0: then exactly
+ * max_iter updates run) or after max_iter updates.  The result is a pure function of the arguments: two calls, a host or a
+ * device buffer, any device, give identical bits.
+ * garlic_gmm_fit: x holds n doubles, `where` GARLIC_DEVICE or GARLIC_HOST (uploaded, never modified); a0 / mean0 / var0
+ * hold the k initial mixture weights, means and variances (host).  out->iterations: the updates run; out->converged: 1
+ * when the stop rule ended the fit.  NaN or infinite parameters are no error: they are returned as computed, with
+ * converged 0.  GARLIC_ERR_INVALID: a NULL pointer, n < 1, k < 1, k > GARLIC_GMM_MAX_K, max_iter < 1, another `where`.
+ * Scratch (2 (3 k + 1) doubles per 2048 points; a host buffer: n doubles more) is kept with the context until
+ * garlic_panel_release_scratch; GARLIC_ERR_NOMEM leaves everything untouched.
+ * garlic_gmm_fit_info: of the last fit on the context: workgroups of a pass (ceil(n / 2048)), bytes of scratch held, the
+ * HIP-event time of the EM loop (the waits for the state between batches of updates included).  Any pointer may be NULL. */
+#define GARLIC_GMM_MAX_K 8
+typedef struct garlic_gmm {
+    int32_t k, iterations, converged;
+    double a[GARLIC_GMM_MAX_K], mean[GARLIC_GMM_MAX_K], var[GARLIC_GMM_MAX_K];
+    double loglik, bic;
+} garlic_gmm;
+int garlic_gmm_fit(garlic_ctx *ctx, const double *x, int64_t n, int32_t where, int32_t k,
+                   const double *a0, const double *mean0, const double *var0,
+                   int32_t max_iter, double precision, garlic_gmm *out);
+int garlic_gmm_fit_info(garlic_ctx *ctx, int64_t *blocks, int64_t *scratch_bytes, float *em_ms);
 
 /* First half of assembleROHWindows (src/garlic-roh.cpp:446-454) on the device: for every individual
  * and SNP the number of windows with score >= cutoff that cover the SNP,
