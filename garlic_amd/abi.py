@@ -207,7 +207,10 @@ def _ptr(a, t):
 
 
 class Context:
-    """One device + one HIP stream (garlic_ctx)."""
+    """One device + one HIP stream (garlic_ctx).  stream: a hipStream_t handle (int) the caller owns, e.g.
+    torch.cuda.Stream().cuda_stream; the calls then keep that stream's order.  None or 0: the context creates a private
+    non-blocking stream.  Torch's DEFAULT stream has handle 0, so stream=torch.cuda.current_stream().cuda_stream on the
+    default stream silently gets the private stream, unordered with torch's work: create a torch.cuda.Stream() instead."""
 
     def __init__(self, device=0, stream=None):
         self.handle = _vp()

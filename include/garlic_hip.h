@@ -80,7 +80,13 @@ const char *garlic_hip_last_error(void);
 int garlic_hip_device_count(int32_t *count);
 
 /* Context: device ordinal + stream.  hip_stream == NULL: the context creates its own stream;
- * otherwise a hipStream_t owned by the caller (e.g. torch's current stream). */
+ * otherwise a hipStream_t owned by the caller (e.g. torch's current stream).  On a caller's stream the calls keep plain
+ * stream order: a device buffer that stream is still writing when a `where = GARLIC_DEVICE` call starts is read with its
+ * final contents, and a device output is complete for whatever the caller enqueues next on it
+ * (tests/test_gpu_caller_stream.py).
+ * The DEFAULT (null) stream cannot be handed over: its handle is 0, which is the NULL that means "create my own", so
+ * e.g. torch.cuda.current_stream().cuda_stream on torch's default stream silently gives a private non-blocking stream
+ * that is not ordered with the caller's work.  Pass a stream created for the purpose (torch.cuda.Stream()). */
 int garlic_ctx_create(int32_t device, void *hip_stream, garlic_ctx **ctx);
 int garlic_ctx_destroy(garlic_ctx *ctx);
 int garlic_ctx_synchronize(garlic_ctx *ctx);
