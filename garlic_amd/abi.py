@@ -47,8 +47,12 @@ SYMBOLS = [
     "garlic_bed_create", "garlic_bed_set_rows", "garlic_bed_census", "garlic_bed_destroy", "garlic_panel_set_genotypes_bed",
     "garlic_feed_kde", "garlic_lod_kde", "garlic_feed_kde_info", "garlic_feed_kde_times",
     "garlic_gmm_fit", "garlic_gmm_fit_info",
+    "garlic_kde_part_create", "garlic_lod_kde_part", "garlic_kde_part_destroy", "garlic_kde_part_count",
+    "garlic_kde_part_moment", "garlic_kde_part_rank", "garlic_kde_part_sums", "garlic_kde_parts", "garlic_kde_parts_info",
 ]
 KDE_POINTS = 512   # GARLIC_KDE_POINTS
+KDE_MAX_PARTS = 64   # GARLIC_KDE_MAX_PARTS
+KDE_RANK_MAX = 1024  # probe keys of one garlic_kde_part_rank
 GMM_MAX_K = 8      # GARLIC_GMM_MAX_K
 
 
@@ -182,6 +186,16 @@ def lib():
                                  _i32p, C.c_int32, C.POINTER(Kde), _i64p]
     L.garlic_feed_kde_info.argtypes = [_vp, _i64p, _i64p, _i64p]
     L.garlic_feed_kde_times.argtypes = [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.garlic_kde_part_create.argtypes = [_vp, _vp, C.c_int64, C.c_int32, C.POINTER(_vp)]
+    L.garlic_lod_kde_part.argtypes = [_vp, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32,
+                                      _i32p, C.c_int32, C.POINTER(_vp), _i64p]
+    L.garlic_kde_part_destroy.argtypes = [_vp]
+    L.garlic_kde_part_count.argtypes = [_vp, _i64p]
+    L.garlic_kde_part_moment.argtypes = [_vp, C.c_int32, C.c_double, _f64p, _f64p, _f64p]
+    L.garlic_kde_part_rank.argtypes = [_vp, C.POINTER(C.c_uint64), C.c_int32, _i64p]
+    L.garlic_kde_part_sums.argtypes = [_vp, _f64p, C.c_double, _f64p]
+    L.garlic_kde_parts.argtypes = [C.POINTER(_vp), C.c_int32, C.POINTER(Kde)]
+    L.garlic_kde_parts_info.argtypes = [C.POINTER(_vp), C.c_int32, _i64p, _i64p, _i32p, C.POINTER(C.c_float)]
     L.garlic_gmm_fit.argtypes = [_vp, _vp, C.c_int64, C.c_int32, C.c_int32, _f64p, _f64p, _f64p, C.c_int32, C.c_double, C.POINTER(Gmm)]
     L.garlic_gmm_fit_info.argtypes = [_vp, _i64p, _i64p, C.POINTER(C.c_float)]
     L.garlic_bed_create.argtypes = [_vp, C.c_int64, C.c_int32, C.POINTER(_vp)]
@@ -289,6 +303,20 @@ class Context:
         check(lib().garlic_feed_kde_times(self.handle, C.byref(a), C.byref(b)))
         return {"moments_ms": a.value, "sums_ms": b.value}
 
+    def kde_part(self, values, n=None):
+        """garlic_kde_part_create: an ascending feed (garlic_feed_sort's key order) as one part of a split feed, an
+        abi.KdePart.  values: a contiguous float64 numpy array (host, uploaded; n defaults to its length) or a device address
+        (int) of n doubles, borrowed until the part is closed."""
+        h = _vp()
+        if isinstance(values, np.ndarray):
+            assert values.dtype == np.float64 and values.flags["C_CONTIGUOUS"] and values.ndim == 1
+            n = values.shape[0] if n is None else int(n)
+            assert n <= values.shape[0]
+            check(lib().garlic_kde_part_create(self.handle, _vp(values.ctypes.data), n, HOST, C.byref(h)))
+        else:
+            check(lib().garlic_kde_part_create(self.handle, _vp(values) if values else None, int(n), DEVICE, C.byref(h)))
+        return KdePart(h)
+
     def gmm_fit(self, values, a0, mean0, var0, n=None, max_iter=1000, precision=1e-5, out=None):
         """garlic_gmm_fit: GMM::estimate's EM fit of len(a0) Gaussians, as a dict: k, iterations, converged, loglik, bic and
         the float64 arrays a, mean, var [k].  values: a contiguous float64 numpy array (host; n defaults to its length) or
@@ -324,6 +352,78 @@ class Context:
 
     def __exit__(self, *exc):
         self.close()
+
+
+class KdePart:
+    """garlic_kde_part: one sorted part of a split feed (Context.kde_part, Panel.lod_kde_part).  The step calls are what a
+    caller with one process per GPU all-reduces between; kde_parts(parts) runs them all.  Close it before its context."""
+
+    def __init__(self, handle):
+        self.handle = handle
+
+    def count(self):
+        n = C.c_int64()
+        check(lib().garlic_kde_part_count(self.handle, C.byref(n)))
+        return n.value
+
+    def moment(self, pass_, mean=0.0):
+        """pass 0: (sum, x[0], x[n - 1]) -- (0.0, None, None) for an empty part; pass 1: the sum of (x - mean)^2"""
+        v, lo, hi = C.c_double(), C.c_double(), C.c_double()
+        check(lib().garlic_kde_part_moment(self.handle, int(pass_), float(mean), C.byref(v), C.byref(lo), C.byref(hi)))
+        if pass_:
+            return v.value
+        return (v.value, lo.value, hi.value) if self.count() else (v.value, None, None)
+
+    def rank(self, keys):
+        """how many of the part's values have a key below each of keys (uint64, at most 1024): int64 array"""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        below = np.zeros(keys.shape[0], dtype=np.int64)
+        check(lib().garlic_kde_part_rank(self.handle, keys.ctypes.data_as(C.POINTER(C.c_uint64)), int(keys.shape[0]),
+                                         _ptr(below, _i64p)))
+        return below
+
+    def sums(self, targets, h):
+        """the part's 512 undivided Gaussian sums at targets for the bandwidth h"""
+        targets = np.ascontiguousarray(targets, dtype=np.float64)
+        assert targets.shape == (KDE_POINTS,)
+        out = np.zeros(KDE_POINTS, dtype=np.float64)
+        check(lib().garlic_kde_part_sums(self.handle, _ptr(targets, _f64p), float(h), _ptr(out, _f64p)))
+        return out
+
+    def close(self):
+        if self.handle:
+            lib().garlic_kde_part_destroy(self.handle)
+            self.handle = _vp()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def _part_handles(parts):
+    return (_vp * max(len(parts), 1))(*[None if p is None else p.handle for p in parts])
+
+
+def kde_parts(parts, out=None):
+    """garlic_kde_parts: the KDE of the union of the parts (KdePart objects, in this order), as Context.feed_kde's dict.
+    out: an abi.Kde to fill instead (returned as it is)."""
+    k = Kde() if out is None else out
+    check(lib().garlic_kde_parts(_part_handles(parts), len(parts), C.byref(k)))
+    return k.as_dict() if out is None else out
+
+
+def kde_parts_info(parts):
+    """garlic_kde_parts_info: {chunks [P], pairs_skipped [P], rank_rounds, sums_ms [P]} of the last KDE over these parts"""
+    n = max(len(parts), 1)
+    chunks, skipped = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+    ms = np.zeros(n, dtype=np.float32)
+    rounds = C.c_int32()
+    check(lib().garlic_kde_parts_info(_part_handles(parts), len(parts), _ptr(chunks, _i64p), _ptr(skipped, _i64p), C.byref(rounds),
+                                      ms.ctypes.data_as(C.POINTER(C.c_float))))
+    return {"chunks": chunks[:len(parts)], "pairs_skipped": skipped[:len(parts)], "rank_rounds": rounds.value,
+            "sums_ms": ms[:len(parts)]}
 
 
 class DeviceBuffer:
@@ -743,6 +843,16 @@ class Panel:
         check(lib().garlic_lod_kde(self.handle, winsize, error, max_gap, int(use_gl), int(weighted), M, mu, step,
                                    _ptr(idx, _i32p), 0 if idx is None else int(idx.shape[0]), C.byref(k), _ptr(per_chr, _i64p)))
         return k.as_dict(), per_chr
+
+    def lod_kde_part(self, winsize, error, max_gap, step, use_gl=False, weighted=False, M=7, mu=1e-9, ind_idx=None):
+        """garlic_lod_kde_part: lod_kde's arguments; the sorted device feed becomes an abi.KdePart that borrows the panel's
+        scratch (stale after the panel's next score or feed call).  Returns (the part, per-chromosome counts)."""
+        idx = None if ind_idx is None else np.ascontiguousarray(ind_idx, dtype=np.int32)
+        h = _vp()
+        per_chr = np.zeros(self.nchr, dtype=np.int64)
+        check(lib().garlic_lod_kde_part(self.handle, winsize, error, max_gap, int(use_gl), int(weighted), M, mu, step,
+                                        _ptr(idx, _i32p), 0 if idx is None else int(idx.shape[0]), C.byref(h), _ptr(per_chr, _i64p)))
+        return KdePart(h), per_chr
 
     def lod_feed_multi(self, winsizes, error, max_gap, steps=None, ind_idx=None, copy=True):
         """garlic_lod_feed_multi: the feeds of several window sizes in one call (unweighted --error scores; steps

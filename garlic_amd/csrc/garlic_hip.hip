@@ -24,6 +24,7 @@
 #include "kde_kernels.hpp"
 #include "gmm_kernels.hpp"
 #include "../host/kde_select.hpp"
+#include "../host/kde_parts.hpp"
 #include "../host/chain_order.hpp"
 #include "bed_kernels.hpp"
 
@@ -435,6 +436,9 @@ struct garlic_panel {
     FeedSortScratch fs;                            // ... SORTED: the sorter's scratch of the single-size feed calls
     // garlic_lod_kde: set around its feed call -- the feed is sorted and stays on the device, where and how many is noted here
     struct FeedSink { const double *data = nullptr; int64_t n = 0; } *feed_sink = nullptr;
+    // garlic_lod_kde_part: a part borrows the feed from the scratch above.  Every call that may write that scratch (scores,
+    // a feed, garlic_panel_release_scratch, the panel's end) moves the count on; a part whose count is behind is stale.
+    std::shared_ptr<uint64_t> scratch_gen = std::make_shared<uint64_t>(0);
     // garlic_lod_feed_multi: one set of scratch and one stream per window size of the call, kept for the next call
     struct FeedSlot {
         hipStream_t stream = nullptr;
@@ -2535,6 +2539,7 @@ int launch_lod(garlic_panel *p, Mode mode, int32_t W, double error, int32_t max_
 {
     garlic_ctx *ctx = p->ctx;
     int rc;
+    ++*p->scratch_gen;
     if ((rc = set_device(ctx))) return rc;
     // Host output: the device always computes into the padded layout the tuned kernels need; the
     // rows are copied out into the caller's (possibly dense) layout by strided D2H copies.
@@ -2763,6 +2768,7 @@ int garlic_panel_destroy(garlic_panel *p)
     if (!p) return GARLIC_OK;
     (void)hipSetDevice(p->ctx->device);
     (void)hipStreamSynchronize(p->ctx->stream);
+    ++*p->scratch_gen;
     p->d_out.release();
     release_feed_slots(p);
     if (p->slab_stream) {
@@ -4149,6 +4155,7 @@ int garlic_panel_release_scratch(garlic_panel *p)
     int rc;
     if ((rc = set_device(p->ctx))) return rc;
     HIP_TRY(hipStreamSynchronize(p->ctx->stream));
+    ++*p->scratch_gen;
     p->lds.release();
     p->d_out.release(); p->d_feed.release();
     p->d_stage16.release(); p->d_stage64.release(); p->d_bed_word_rows.release();
@@ -4327,6 +4334,7 @@ static int feed_single(garlic_panel *p, int32_t winsize, double error, int32_t m
     if (step < 1) return fail(GARLIC_ERR_INVALID, "step must be >= 1");
     if (ind_idx && n_idx < 1) return fail(GARLIC_ERR_INVALID, "an individual list needs at least one entry");
     int rc;
+    ++*p->scratch_gen;
     if ((rc = set_device(p->ctx))) return rc;
     // the listed individuals (convertSubsetWinData2DoubleData's randInd[]) and the blocks that hold them
     const int nblk = (p->nind + WAVE - 1) / WAVE;
@@ -4470,6 +4478,7 @@ int garlic_lod_feed_multi(garlic_panel *p, const int32_t *winsizes, const int32_
     }
     garlic_ctx *ctx = p->ctx;
     int rc;
+    ++*p->scratch_gen;
     if ((rc = set_device(ctx))) return rc;
     if (!p->have_map || !p->have_freq || !p->have_geno)
         return fail(GARLIC_ERR_STATE, "panel needs map, freq and genotypes before computing LOD");
@@ -4659,6 +4668,7 @@ int garlic_lod_feed_multi_tgls(garlic_panel *p, const int32_t *winsizes, const i
     garlic_ctx *ctx = p->ctx;
     hipStream_t s = ctx->stream;
     int rc;
+    ++*p->scratch_gen;
     if ((rc = set_device(ctx))) return rc;
     const int nblk = (p->nind + WAVE - 1) / WAVE;
     const int nrows = ind_idx ? n_idx : p->nind;
@@ -5761,6 +5771,389 @@ int garlic_lod_kde(garlic_panel *p, int32_t winsize, double error, int32_t max_g
     if (rc) return rc;
     if (count < 2 || sink.n != count) return fail(GARLIC_ERR_INVALID, "feed KDE: needs at least 2 values (the feed holds %lld)", (long long)count);
     return kde_device(p->ctx, sink.data, sink.n, out);
+}
+
+// ---- The KDE of a feed that is split into sorted parts (a sharded panel: one part per shard, on the shard's device).
+// n, the sums and the 512 Gaussian sums add over the parts, lo / hi are a min and a max, and the four order statistics
+// come from rank queries (host/kde_parts.hpp).  A part owns its scratch and a pinned block for what comes back, so every
+// step is enqueued on every part's stream before any is waited for.
+struct KdePartHost {
+    KdeMoments mom;
+    double ends[2];
+    unsigned long long skipped;
+    unsigned long long keys[KDE_RANK_MAX];
+    long long below[KDE_RANK_MAX];
+    double sums[KDE_POINTS];
+};
+
+struct garlic_kde_part {
+    garlic_ctx *ctx = nullptr;
+    const double *x = nullptr;                     // n ascending doubles on ctx's device (own.p, or borrowed)
+    int64_t n = 0;
+    DevBuf<double> own;                            // a host buffer's upload
+    std::shared_ptr<uint64_t> gen;                 // garlic_lod_kde_part: the panel's scratch count, and its value at creation
+    uint64_t gen_at = 0;
+    DevBuf<double> partial, slices, targets, sums;
+    DevBuf<int32_t> flags;
+    DevBuf<KdeMoments> mom;
+    DevBuf<unsigned long long> skipped, keys;
+    DevBuf<long long> below;
+    KdePartHost *h = nullptr;
+    hipEvent_t ev[2] = {};                         // around the sums kernels
+    int32_t rank_m = 0;
+    int64_t chunks = 0, pairs_skipped = 0;         // garlic_kde_parts_info
+    int32_t rank_rounds = 0;
+    float sums_ms = 0.f;
+    int64_t n_chunks() const { return (n + KDE_CHUNK - 1) / KDE_CHUNK; }
+    int64_t n_slices() const { const int64_t c = n_chunks(), cps = kde_chunks_per_slice(c); return cps ? (c + cps - 1) / cps : 0; }
+};
+
+static int kde_part_usable(const garlic_kde_part *part)
+{
+    if (!part) return fail(GARLIC_ERR_INVALID, "KDE part is NULL");
+    if (part->gen && *part->gen != part->gen_at)
+        return fail(GARLIC_ERR_STATE, "KDE part is stale: its panel has computed scores or a feed, or released its scratch, since the part was made");
+    return GARLIC_OK;
+}
+
+static void kde_part_free(garlic_kde_part *part)
+{
+    for (auto &e : part->ev)
+        if (e) (void)hipEventDestroy(e);
+    if (part->h) (void)hipHostFree(part->h);
+    delete part;
+}
+
+// everything a part's steps need, before anything is enqueued (out of memory: nothing was touched)
+static int kde_part_new(garlic_ctx *ctx, int64_t n, garlic_kde_part **out)
+{
+    if (n > (int64_t)0x7fffffff * KDE_CHUNK) return fail(GARLIC_ERR_INVALID, "feed KDE: %lld values are more chunks than one launch holds", (long long)n);
+    int rc;
+    if ((rc = set_device(ctx))) return rc;
+    std::unique_ptr<garlic_kde_part, void (*)(garlic_kde_part *)> part(new garlic_kde_part, kde_part_free);
+    part->ctx = ctx;
+    part->n = n;
+    if ((rc = part->partial.reserve((size_t)std::max<int64_t>(part->n_chunks(), 1))) ||
+        (rc = part->flags.reserve((size_t)std::max<int64_t>(part->n_chunks(), 1))) ||
+        (rc = part->slices.reserve((size_t)std::max<int64_t>(part->n_slices(), 1) * KDE_POINTS)) ||
+        (rc = part->targets.reserve(KDE_POINTS)) || (rc = part->sums.reserve(KDE_POINTS)) || (rc = part->mom.reserve(1)) ||
+        (rc = part->skipped.reserve(1)) || (rc = part->keys.reserve(KDE_RANK_MAX)) || (rc = part->below.reserve(KDE_RANK_MAX)))
+        return rc;
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&part->h), sizeof(KdePartHost), hipHostMallocDefault));
+    memset(part->h, 0, sizeof(KdePartHost));
+    for (auto &e : part->ev) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipMemsetAsync(part->mom.p, 0, sizeof(KdeMoments), ctx->stream));
+    *out = part.release();
+    return GARLIC_OK;
+}
+
+int garlic_kde_part_create(garlic_ctx *ctx, const double *sorted, int64_t n, int32_t where, garlic_kde_part **out)
+{
+    if (!ctx || !out) return fail(GARLIC_ERR_INVALID, "KDE part: context and part are required");
+    if (where != GARLIC_HOST && where != GARLIC_DEVICE) return fail(GARLIC_ERR_INVALID, "KDE part: where must be GARLIC_HOST or GARLIC_DEVICE");
+    if (n < 0) return fail(GARLIC_ERR_INVALID, "KDE part: n must be >= 0 (got %lld)", (long long)n);
+    if (n > 0 && !sorted) return fail(GARLIC_ERR_INVALID, "KDE part: values is NULL");
+    garlic_kde_part *part = nullptr;
+    int rc;
+    if ((rc = kde_part_new(ctx, n, &part))) return rc;
+    part->x = sorted;
+    if (where == GARLIC_HOST && n > 0) {
+        hipError_t e = hipSuccess;
+        if ((rc = part->own.reserve((size_t)n)) ||
+            (e = hipMemcpyAsync(part->own.p, sorted, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess ||
+            (e = hipStreamSynchronize(ctx->stream)) != hipSuccess) {
+            kde_part_free(part);
+            return rc ? rc : fail(GARLIC_ERR_HIP, "KDE part upload: %s", hipGetErrorString(e));
+        }
+        part->x = part->own.p;
+    }
+    if (n == 0) part->x = nullptr;
+    *out = part;
+    return GARLIC_OK;
+}
+
+int garlic_lod_kde_part(garlic_panel *p, int32_t winsize, double error, int32_t max_gap, int32_t use_gl, int32_t weighted, int32_t M,
+                        double mu, int32_t step, const int32_t *ind_idx, int32_t n_idx, garlic_kde_part **out, int64_t *chr_counts)
+{
+    if (!p || !out) return fail(GARLIC_ERR_INVALID, "panel and part are required");
+    garlic_panel::FeedSink sink;
+    int64_t count = 0;
+    p->feed_sink = &sink;                  // as garlic_lod_kde: sorted, left on the device
+    int rc = garlic_lod_feed_subset(p, winsize, error, max_gap, use_gl, weighted, M, mu, step, ind_idx, n_idx, nullptr,
+                                    INT64_MAX, &count, chr_counts);
+    p->feed_sink = nullptr;
+    if (rc) return rc;
+    if (count > 0 && sink.n != count) return fail(GARLIC_ERR_STATE, "KDE part: the feed of %lld values was not left on the device", (long long)count);
+    garlic_kde_part *part = nullptr;
+    if ((rc = kde_part_new(p->ctx, count, &part))) return rc;
+    part->x = count > 0 ? sink.data : nullptr;
+    part->gen = p->scratch_gen;
+    part->gen_at = *p->scratch_gen;
+    *out = part;
+    return GARLIC_OK;
+}
+
+int garlic_kde_part_destroy(garlic_kde_part *part)
+{
+    if (!part) return GARLIC_OK;
+    (void)hipSetDevice(part->ctx->device);
+    (void)hipStreamSynchronize(part->ctx->stream);
+    kde_part_free(part);
+    return GARLIC_OK;
+}
+
+int garlic_kde_part_count(garlic_kde_part *part, int64_t *n)
+{
+    int rc;
+    if ((rc = kde_part_usable(part))) return rc;
+    if (n) *n = part->n;
+    return GARLIC_OK;
+}
+
+// The steps in two halves: *_enqueue puts the work and the copies back on the part's stream, *_wait waits for that stream
+// and reads the pinned block.  An empty part enqueues nothing (the rank kernel excepted: it reads no value).
+static int kde_part_moment_enqueue(garlic_kde_part *part, int pass, double mean)
+{
+    int rc;
+    if ((rc = set_device(part->ctx))) return rc;
+    if (part->n == 0) return GARLIC_OK;
+    hipStream_t s = part->ctx->stream;
+    const int64_t n = part->n, n_chunks = part->n_chunks();
+    KdeIdx idx{};                                  // (pass 1 of the tree fetches x[0] six times: not used)
+    if (pass == 0)
+        hipLaunchKernelGGL(kde_moment_kernel, dim3((unsigned)n_chunks), dim3(KDE_THREADS), 0, s, part->x, n, 0, part->mom.p, part->partial.p, part->flags.p);
+    else
+        hipLaunchKernelGGL(kde_moment_about_kernel, dim3((unsigned)n_chunks), dim3(KDE_THREADS), 0, s, part->x, n, mean, part->partial.p, part->flags.p);
+    hipLaunchKernelGGL(kde_tree_kernel, dim3(1), dim3(KDE_THREADS), 0, s, part->x, n, n_chunks, pass, part->partial.p, part->flags.p, idx, part->mom.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&part->h->mom, part->mom.p, sizeof(KdeMoments), hipMemcpyDeviceToHost, s));
+    if (pass == 0) {
+        HIP_TRY(hipMemcpyAsync(&part->h->ends[0], part->x, sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(&part->h->ends[1], part->x + (n - 1), sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    return GARLIC_OK;
+}
+
+static int kde_part_moment_wait(garlic_kde_part *part, int pass, double *value, double *lo, double *hi)
+{
+    if (part->n == 0) {
+        *value = 0.0;
+        return GARLIC_OK;
+    }
+    int rc;
+    if ((rc = set_device(part->ctx))) return rc;
+    HIP_TRY(hipStreamSynchronize(part->ctx->stream));
+    const KdeMoments &mom = part->h->mom;
+    if (pass == 0) {
+        if (mom.flags & KDE_FLAG_NOT_FINITE) return fail(GARLIC_ERR_INVALID, "feed KDE: the values hold a NaN or an infinity");
+        if (mom.flags & KDE_FLAG_NOT_ASCENDING) return fail(GARLIC_ERR_INVALID, "feed KDE: the values are not in ascending order (garlic_feed_sort)");
+        if (lo) *lo = part->h->ends[0];
+        if (hi) *hi = part->h->ends[1];
+    }
+    *value = pass == 0 ? mom.sum : mom.ssq;
+    return GARLIC_OK;
+}
+
+static int kde_part_rank_enqueue(garlic_kde_part *part, const uint64_t *keys, int32_t m)
+{
+    int rc;
+    if ((rc = set_device(part->ctx))) return rc;
+    hipStream_t s = part->ctx->stream;
+    for (int i = 0; i < m; i++) part->h->keys[i] = keys[i];
+    part->rank_m = m;
+    HIP_TRY(hipMemcpyAsync(part->keys.p, part->h->keys, sizeof(unsigned long long) * (size_t)m, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(kde_rank_kernel, dim3((unsigned)((m + KDE_THREADS - 1) / KDE_THREADS)), dim3(KDE_THREADS), 0, s, part->x, part->n,
+                       part->keys.p, (int)m, part->below.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(part->h->below, part->below.p, sizeof(long long) * (size_t)m, hipMemcpyDeviceToHost, s));
+    return GARLIC_OK;
+}
+
+static int kde_part_rank_wait(garlic_kde_part *part)      // the counts are in part->h->below[0 .. rank_m)
+{
+    int rc;
+    if ((rc = set_device(part->ctx))) return rc;
+    HIP_TRY(hipStreamSynchronize(part->ctx->stream));
+    return GARLIC_OK;
+}
+
+static int kde_part_sums_enqueue(garlic_kde_part *part, const double *targets, double inv_h2)
+{
+    int rc;
+    if ((rc = set_device(part->ctx))) return rc;
+    if (part->n == 0) return GARLIC_OK;
+    hipStream_t s = part->ctx->stream;
+    const int64_t n_chunks = part->n_chunks(), cps = kde_chunks_per_slice(n_chunks), n_slices = part->n_slices();
+    HIP_TRY(hipMemcpyAsync(part->targets.p, targets, sizeof(double) * KDE_POINTS, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(part->skipped.p, 0, sizeof(unsigned long long), s));
+    HIP_TRY(hipEventRecord(part->ev[0], s));
+    hipLaunchKernelGGL(kde_sum_kernel, dim3((unsigned)n_slices), dim3(KDE_THREADS), 0, s, part->x, part->n, n_chunks, cps, part->targets.p, inv_h2,
+                       part->slices.p, part->skipped.p);
+    hipLaunchKernelGGL(kde_slice_sum_kernel, dim3(KDE_POINTS), dim3(KDE_THREADS), 0, s, part->slices.p, n_slices, part->sums.p);
+    HIP_TRY(hipEventRecord(part->ev[1], s));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(part->h->sums, part->sums.p, sizeof(double) * KDE_POINTS, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&part->h->skipped, part->skipped.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    return GARLIC_OK;
+}
+
+static int kde_part_sums_wait(garlic_kde_part *part)      // the sums are in part->h->sums
+{
+    part->chunks = part->n_chunks();
+    if (part->n == 0) {
+        for (double &v : part->h->sums) v = 0.0;
+        part->pairs_skipped = 0;
+        part->sums_ms = 0.f;
+        return GARLIC_OK;
+    }
+    int rc;
+    if ((rc = set_device(part->ctx))) return rc;
+    HIP_TRY(hipStreamSynchronize(part->ctx->stream));
+    part->pairs_skipped = (int64_t)part->h->skipped;
+    if (hipEventElapsedTime(&part->sums_ms, part->ev[0], part->ev[1]) != hipSuccess) part->sums_ms = 0.f;
+    return GARLIC_OK;
+}
+
+int garlic_kde_part_moment(garlic_kde_part *part, int32_t pass, double mean, double *value, double *lo, double *hi)
+{
+    int rc;
+    if ((rc = kde_part_usable(part))) return rc;
+    if (pass != 0 && pass != 1) return fail(GARLIC_ERR_INVALID, "KDE part: pass must be 0 (sum) or 1 (squared deviations), got %d", (int)pass);
+    if (!value) return fail(GARLIC_ERR_INVALID, "KDE part: value is NULL");
+    if ((rc = kde_part_moment_enqueue(part, pass, mean))) return rc;
+    return kde_part_moment_wait(part, pass, value, lo, hi);
+}
+
+int garlic_kde_part_rank(garlic_kde_part *part, const uint64_t *keys, int32_t m, int64_t *below)
+{
+    int rc;
+    if ((rc = kde_part_usable(part))) return rc;
+    if (m < 1 || m > KDE_RANK_MAX) return fail(GARLIC_ERR_INVALID, "KDE part: %d probe keys (1 to %d)", (int)m, KDE_RANK_MAX);
+    if (!keys || !below) return fail(GARLIC_ERR_INVALID, "KDE part: keys and below are required");
+    if ((rc = kde_part_rank_enqueue(part, keys, m)) || (rc = kde_part_rank_wait(part))) return rc;
+    for (int i = 0; i < m; i++) below[i] = part->h->below[i];
+    return GARLIC_OK;
+}
+
+int garlic_kde_part_sums(garlic_kde_part *part, const double *targets, double h, double *sums)
+{
+    int rc;
+    if ((rc = kde_part_usable(part))) return rc;
+    if (!targets || !sums) return fail(GARLIC_ERR_INVALID, "KDE part: targets and sums are required");
+    const double inv_h2 = 1.0 / (h * h);
+    if (!(h > 0) || !std::isfinite(inv_h2)) return fail(GARLIC_ERR_INVALID, "feed KDE: bandwidth %g cannot be used (zero, negative, not finite or too small to square)", h);
+    if ((rc = kde_part_sums_enqueue(part, targets, inv_h2)) || (rc = kde_part_sums_wait(part))) return rc;
+    memcpy(sums, part->h->sums, sizeof(double) * KDE_POINTS);
+    return GARLIC_OK;
+}
+
+int garlic_kde_parts(garlic_kde_part *const *parts, int32_t n_parts, garlic_kde *out)
+{
+    namespace gh = garlic_host;
+    static_assert(GARLIC_KDE_MAX_PARTS <= KDE_THREADS && gh::KDE_DESCENT_PROBES == KDE_RANK_MAX, "one descent round is one rank launch");
+    if (!parts || !out) return fail(GARLIC_ERR_INVALID, "KDE parts: parts and out are required");
+    if (n_parts < 1 || n_parts > GARLIC_KDE_MAX_PARTS) return fail(GARLIC_ERR_INVALID, "KDE parts: %d parts (1 to %d)", (int)n_parts, GARLIC_KDE_MAX_PARTS);
+    int rc;
+    int64_t n = 0;
+    for (int p = 0; p < n_parts; p++) {
+        if (!parts[p]) return fail(GARLIC_ERR_INVALID, "KDE parts: part %d is NULL", p);
+        for (int q = 0; q < p; q++)
+            if (parts[q] == parts[p]) return fail(GARLIC_ERR_INVALID, "KDE parts: part %d is part %d again", p, q);
+        if ((rc = kde_part_usable(parts[p]))) return rc;
+        n += parts[p]->n;
+    }
+    if (n < 2) return fail(GARLIC_ERR_INVALID, "feed KDE: needs at least 2 values (the parts hold %lld)", (long long)n);
+    // a step on every part: all enqueued, then all waited for (the first error is the one returned)
+    auto each = [&](auto enqueue, auto wait) {
+        int first = GARLIC_OK;
+        int enqueued = 0;
+        for (; enqueued < n_parts && !first; enqueued++) first = enqueue(parts[enqueued], enqueued);
+        for (int p = 0; p < (first ? enqueued - 1 : enqueued); p++) {
+            const int r = wait(parts[p], p);
+            if (r && !first) first = r;
+        }
+        return first;
+    };
+    garlic_kde r;
+    r.n = n;
+    double part_value[GARLIC_KDE_MAX_PARTS];
+    uint64_t lo_key = 0, hi_key = 0;
+    bool have_ends = false;
+    if ((rc = each([&](garlic_kde_part *part, int) { return kde_part_moment_enqueue(part, 0, 0.0); },
+                   [&](garlic_kde_part *part, int p) {
+                       double lo = 0, hi = 0;
+                       const int r2 = kde_part_moment_wait(part, 0, &part_value[p], &lo, &hi);
+                       if (r2 || part->n == 0) return r2;
+                       const uint64_t kl = gh::kdeKey(lo), kh = gh::kdeKey(hi);
+                       if (!have_ends || kl < lo_key) lo_key = kl;
+                       if (!have_ends || kh > hi_key) hi_key = kh;
+                       have_ends = true;
+                       return r2;
+                   })))
+        return rc;
+    r.lo = gh::kdeKeyValue(lo_key);
+    r.hi = gh::kdeKeyValue(hi_key);
+    const double mean = gh::kdeCombine(part_value, n_parts) / (double)n;
+    if ((rc = each([&](garlic_kde_part *part, int) { return kde_part_moment_enqueue(part, 1, mean); },
+                   [&](garlic_kde_part *part, int p) { return kde_part_moment_wait(part, 1, &part_value[p], nullptr, nullptr); })))
+        return rc;
+    r.sd = sqrt(gh::kdeCombine(part_value, n_parts) / (double)(n - 1));
+    // the four order statistics of the union
+    int64_t k25, k75, rank[4];
+    double delta25, delta75, stat[4];
+    gh::kdeQuantileIndex(n, 0.25, &k25, &delta25);
+    gh::kdeQuantileIndex(n, 0.75, &k75, &delta75);
+    const int64_t at[4] = {k25, k25 + 1, k75, k75 + 1};
+    for (int q = 0; q < 4; q++) rank[q] = at[q] < 0 ? 0 : (at[q] >= n ? n - 1 : at[q]);
+    int rounds = 0;
+    rc = gh::kdeSelectRanks(rank, [&](const uint64_t *probes, int m, int64_t *below) {
+        for (int i = 0; i < m; i++) below[i] = 0;
+        return each([&](garlic_kde_part *part, int) { return kde_part_rank_enqueue(part, probes, m); },
+                    [&](garlic_kde_part *part, int) {
+                        const int r2 = kde_part_rank_wait(part);
+                        for (int i = 0; i < m && !r2; i++) below[i] += part->h->below[i];
+                        return r2;
+                    });
+    }, stat, &rounds);
+    if (rc) return rc;
+    r.q25 = k25 >= n - 1 ? stat[0] : gh::kdeQuantileMix(stat[0], stat[1], delta25);
+    r.q75 = k75 >= n - 1 ? stat[2] : gh::kdeQuantileMix(stat[2], stat[3], delta75);
+    r.h = gh::kdeBandwidth(r.sd, r.q25, r.q75, n);
+    if (!(r.h > 0) || !std::isfinite(r.h))
+        return fail(GARLIC_ERR_INVALID, "feed KDE: bandwidth %g (sd %g, quartiles %g and %g): all values equal, or no spread between the quartiles",
+                    r.h, r.sd, r.q25, r.q75);
+    gh::kdeTargets(r.lo, r.hi, r.h, r.x);
+    const double inv_h2 = 1.0 / (r.h * r.h);
+    if (!std::isfinite(inv_h2)) return fail(GARLIC_ERR_INVALID, "feed KDE: bandwidth %g is too small to square", r.h);
+    if ((rc = each([&](garlic_kde_part *part, int) { return kde_part_sums_enqueue(part, r.x, inv_h2); },
+                   [&](garlic_kde_part *part, int) { return kde_part_sums_wait(part); })))
+        return rc;
+    const double *sums[GARLIC_KDE_MAX_PARTS];
+    for (int p = 0; p < n_parts; p++) {
+        sums[p] = parts[p]->h->sums;
+        parts[p]->rank_rounds = rounds;
+    }
+    gh::kdeCombineSums(sums, n_parts, KDE_POINTS, n, r.raw);
+    gh::kdeNormalise(r.raw, r.x, r.y);
+    *out = r;
+    return GARLIC_OK;
+}
+
+int garlic_kde_parts_info(garlic_kde_part *const *parts, int32_t n_parts, int64_t *chunks, int64_t *pairs_skipped, int32_t *rank_rounds,
+                          float *sums_ms)
+{
+    if (!parts) return fail(GARLIC_ERR_INVALID, "KDE parts: parts is NULL");
+    if (n_parts < 1 || n_parts > GARLIC_KDE_MAX_PARTS) return fail(GARLIC_ERR_INVALID, "KDE parts: %d parts (1 to %d)", (int)n_parts, GARLIC_KDE_MAX_PARTS);
+    for (int p = 0; p < n_parts; p++) {
+        if (!parts[p]) return fail(GARLIC_ERR_INVALID, "KDE parts: part %d is NULL", p);
+        const int rc = kde_part_usable(parts[p]);
+        if (rc) return rc;
+        if (chunks) chunks[p] = parts[p]->chunks;
+        if (pairs_skipped) pairs_skipped[p] = parts[p]->pairs_skipped;
+        if (sums_ms) sums_ms[p] = parts[p]->sums_ms;
+    }
+    if (rank_rounds) *rank_rounds = parts[0]->rank_rounds;
+    return GARLIC_OK;
 }
 
 // ---- GMM::estimate on the device (gmm_kernels.hpp).  One update is a pass over the points and the finish that turns the

@@ -24,6 +24,9 @@
 //     target walks the chunk for the other alone; a wave whose 64 lanes skip both enters no loop.  The count of
 //     skipped pairs (integer adds) is what garlic_feed_kde_info reports.
 //   * 64-bit element indices and counts; a chunk count fits 32 bits (checked by the caller).
+//   * a feed split into parts (garlic_kde_parts): kde_moment_about_kernel is pass 1 about the caller's mean,
+//     kde_slice_sum_kernel leaves a part's sums undivided, kde_rank_kernel counts the values below each of up to 1024
+//     probe keys.  The first two run the lines of their single-feed twins, so one part gives the single feed's bits.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -63,15 +66,13 @@ __device__ __forceinline__ double kde_block_tree(double v, double *red)
     return red[0];
 }
 
-// pass 0: partial[chunk] = sum of the chunk; pass 1: sum of (x - mean)^2 with mom->mean
-__global__ void __launch_bounds__(KDE_THREADS)
-kde_moment_kernel(const double *x, int64_t n, int pass, const KdeMoments *mom, double *partial, int32_t *flags)
+// one chunk's partial and flags: pass 0 the sum, pass 1 the sum of (x - mean)^2 (both moment kernels run these lines)
+__device__ __forceinline__ void kde_moment_chunk(const double *x, int64_t n, int pass, double mean, double *partial, int32_t *flags)
 {
     __shared__ double red[KDE_THREADS];
     __shared__ int32_t flag;
     if (threadIdx.x == 0) flag = 0;
     __syncthreads();
-    const double mean = pass ? mom->mean : 0.0;
     const int64_t i0 = (int64_t)blockIdx.x * KDE_CHUNK;
     double acc = 0.0;
     int32_t f = 0;
@@ -94,6 +95,20 @@ kde_moment_kernel(const double *x, int64_t n, int pass, const KdeMoments *mom, d
         partial[blockIdx.x] = total;
         flags[blockIdx.x] = flag;
     }
+}
+
+// pass 0: partial[chunk] = sum of the chunk; pass 1: sum of (x - mean)^2 with mom->mean
+__global__ void __launch_bounds__(KDE_THREADS)
+kde_moment_kernel(const double *x, int64_t n, int pass, const KdeMoments *mom, double *partial, int32_t *flags)
+{
+    kde_moment_chunk(x, n, pass, pass ? mom->mean : 0.0, partial, flags);
+}
+
+// pass 1 about the caller's mean (a part of a split feed: the mean of the union, garlic_kde_part_moment)
+__global__ void __launch_bounds__(KDE_THREADS)
+kde_moment_about_kernel(const double *x, int64_t n, double mean, double *partial, int32_t *flags)
+{
+    kde_moment_chunk(x, n, 1, mean, partial, flags);
 }
 
 // one workgroup: the chunks' partials and flags; pass 0 -> sum and mean, pass 1 -> ssq and the order statistics at idx[6]
@@ -189,15 +204,55 @@ kde_sum_kernel(const double *x, int64_t n, int64_t n_chunks, int64_t chunks_per_
     partial[(int64_t)blockIdx.x * KDE_POINTS + 2 * threadIdx.x + 1] = sum1;
 }
 
-// workgroup j: raw[j] = (sum over the slices, in the fixed order) / n
-__global__ void __launch_bounds__(KDE_THREADS)
-kde_slice_kernel(const double *partial, int64_t n_slices, int64_t n, double *raw)
+// the slices' sums of target blockIdx.x in the fixed order: thread t slices t, t + 256, ..., then the tree
+__device__ __forceinline__ double kde_slice_total(const double *partial, int64_t n_slices)
 {
     __shared__ double red[KDE_THREADS];
     double acc = 0.0;
     for (int64_t s = threadIdx.x; s < n_slices; s += KDE_THREADS) acc += partial[s * KDE_POINTS + blockIdx.x];
-    const double total = kde_block_tree(acc, red);
+    return kde_block_tree(acc, red);
+}
+
+// workgroup j: raw[j] = (sum over the slices, in the fixed order) / n
+__global__ void __launch_bounds__(KDE_THREADS)
+kde_slice_kernel(const double *partial, int64_t n_slices, int64_t n, double *raw)
+{
+    const double total = kde_slice_total(partial, n_slices);
     if (threadIdx.x == 0) raw[blockIdx.x] = total / (double)n;
+}
+
+// workgroup j: sums[j] = the same total, undivided (a part of a split feed: the host adds the parts and divides by the union's n)
+__global__ void __launch_bounds__(KDE_THREADS)
+kde_slice_sum_kernel(const double *partial, int64_t n_slices, double *sums)
+{
+    const double total = kde_slice_total(partial, n_slices);
+    if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+
+// garlic_feed_sort's key (garlic_hip.h): unsigned order of the keys is ascending order of the doubles, -0.0 before +0.0
+__device__ __forceinline__ unsigned long long kde_key(double v)
+{
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    return b ^ (b >> 63 ? 0xFFFFFFFFFFFFFFFFull : 0x8000000000000000ull);
+}
+
+// thread t: below[t] = how many of x[0 .. n) have a key below keys[t] (x ascending in key order: a lower bound).  One
+// binary search per thread, about log2(n) dependent loads: latency-bound, a launch holds at most KDE_RANK_MAX probes.
+// mid < hi <= n, so no read leaves the array; n = 0 reads nothing.
+constexpr int KDE_RANK_MAX = 1024;
+
+__global__ void __launch_bounds__(KDE_THREADS)
+kde_rank_kernel(const double *x, int64_t n, const unsigned long long *keys, int m, long long *below)
+{
+    const int t = blockIdx.x * KDE_THREADS + threadIdx.x;
+    if (t >= m) return;
+    const unsigned long long key = keys[t];
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        if (kde_key(x[mid]) < key) lo = mid + 1; else hi = mid;
+    }
+    below[t] = lo;
 }
 
 } // namespace garlic

@@ -1504,7 +1504,11 @@ DoubleData *LodEngine::lodFeed(int winsize, double error, int MAX_GAP, int step,
 
 // computeKDE of the feed lodFeed would return, sorted (garlic_hip.h: garlic_lod_kde).  One shard: the feed never leaves the
 // device.  Several: the shards' sorted feeds merged on the host as for LodOptions::feed_sorted, then garlic_feed_kde on
-// the first context -- correct, but the transfer is not saved (a sharded device path needs distributed order statistics).
+// the first context -- every feed value crosses PCIe twice and one device computes all the sums.
+// LodOptions::kde_on_shards: every shard with KDE individuals leaves its sorted feed on its device as one garlic_kde_part
+// (on the shards' threads, as assembleROHWindows runs them) and garlic_kde_parts reduces them where they lie: the moments
+// and the Gaussian sums add over the shards, the quartiles come from rank queries (kde_parts.hpp).  One shard: one part,
+// garlic_lod_kde's bits.
 KdeData LodEngine::lodKde(int winsize, double error, int MAX_GAP, int step, bool weighted, int M, double mu,
                              const std::vector<int> *kdeSubsample)
 {
@@ -1512,6 +1516,44 @@ KdeData LodEngine::lodKde(int winsize, double error, int MAX_GAP, int step, bool
     garlic_kde gk;
     auto result = [&] { KdeData k; memcpy(&k, &gk, sizeof k); return k; };
     const bool subset = kdeSubsample && !kdeSubsample->empty();
+    if (g_options.kde_on_shards) {
+        if (subset)
+            for (size_t i = 1; i < kdeSubsample->size(); i++)
+                if ((*kdeSubsample)[i] <= (*kdeSubsample)[i - 1]) fail("KDE subsample must be in increasing order");
+        const size_t ns = impl->shards.size();
+        std::vector<garlic_kde_part *> made(ns, nullptr);
+        std::vector<std::string> errors(ns);
+        std::vector<std::thread> th;
+        for (size_t k = 0; k < ns; k++)
+            th.emplace_back([&, k] {
+                auto &s = impl->shards[k];
+                std::vector<int32_t> mine;
+                if (subset) {
+                    for (int g : *kdeSubsample)
+                        if (g >= s.ind_begin && g < s.ind_begin + s.nind) mine.push_back(g - s.ind_begin);
+                    if (mine.empty()) return;          // no listed individual lives here: no part
+                }
+                if (garlic_lod_kde_part(s.panel, winsize, error, MAX_GAP, impl->use_gl, weighted, M, mu, step, subset ? mine.data() : nullptr,
+                                        (int32_t)mine.size(), &made[k], nullptr) != GARLIC_OK)
+                    errors[k] = garlic_hip_last_error();
+            });
+        for (auto &t : th) t.join();
+        std::vector<garlic_kde_part *> parts;
+        for (garlic_kde_part *p : made)
+            if (p) parts.push_back(p);
+        std::string error_text;
+        for (auto &e : errors)
+            if (!e.empty() && error_text.empty()) error_text = "garlic_lod_kde_part: " + e;
+        if (error_text.empty()) {
+            std::cerr << "KDE on " << parts.size() << " shards\n";
+            if (parts.empty()) error_text = "garlic_kde_parts: no shard holds a KDE individual";
+            else if (garlic_kde_parts(parts.data(), (int32_t)parts.size(), &gk) != GARLIC_OK)
+                error_text = std::string("garlic_kde_parts: ") + garlic_hip_last_error();
+        }
+        for (garlic_kde_part *p : parts) garlic_kde_part_destroy(p);
+        if (!error_text.empty()) fail(error_text);
+        return result();
+    }
     if (impl->shards.size() == 1) {
         auto &s = impl->shards[0];
         std::cerr << "Calculating LOD scores with winsize " << winsize << " (thinned on the device, step " << step << ", KDE on the device).\n";

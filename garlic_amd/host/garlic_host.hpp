@@ -279,6 +279,9 @@ struct LodOptions {
     // -> locus order: the array nrd0's gsl_sort (garlic-kde.cpp:132) would make of it.  Sorted on the devices
     // (garlic_panel_set_feed_order on every shard's panel), the shards' arrays merged on the host (feed_merge.hpp).
     bool feed_sorted = false;
+    // LodEngine::lodKde: the KDE of a sharded panel from one garlic_kde_part per shard (garlic_kde_parts) instead of the
+    // shards' feeds merged on the host and one device's garlic_feed_kde.  Off by default until a node has measured it.
+    bool kde_on_shards = false;
 };
 void setLodOptions(const LodOptions &o);
 

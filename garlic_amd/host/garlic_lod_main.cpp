@@ -43,6 +43,7 @@ struct Args {
     std::vector<int> winsize_multi;
     bool auto_winsize = false, weighted = false, raw_lod = false, kde_thinning = true, phased = false;
     bool sorted_feed = false;      // extension: the feeds ascending, <out>.<W>SNPs.lod.sorted.f64 (the device sorts them)
+    bool kde_sharded = false;      // extension: with --kde, the KDE of a sharded panel on the shards' devices (garlic_kde_parts)
     bool kde = false;              // extension: the KDE, the LOD cutoff and (--auto-winsize) the window size in this tool
     bool winsize_stream = false;   // extension: further window sizes from stdin (the loop of selectWinsize, driven by the KDE's owner)
     int auto_winsize_step = 10, max_gap = 200000, M = 7, threads = 1, kde_subsample = 20, gpus = 1;
@@ -77,6 +78,7 @@ struct Args {
                  "                         lengths on the device; with --lod-cutoff or --kde)\n"
                  "         [--kde]   (<out>.<W>SNPs.kde and the LOD cutoff from the KDE on the device instead of the feed files; with\n"
                  "                    --size-bounds and no --lod-cutoff the ROH calls use it; with --auto-winsize the window size too)\n"
+                 "         [--kde-sharded]   (with --kde: every shard's feed stays on its device, the KDE is reduced over the shards)\n"
                  "         (--bfile / --bed --bim --fam: PLINK SNP-major .bed input, read on the device; not with --tped / --tfam /\n"
                  "          --phased; --genotype-cache F is then written from the .bed, never read)\n";
     exit(1);
@@ -113,6 +115,7 @@ Args parse(int argc, char **argv)
         else if (f == "--winsize-stream") a.winsize_stream = !a.winsize_stream;
         else if (f == "--sorted-feed") a.sorted_feed = !a.sorted_feed;
         else if (f == "--kde") a.kde = !a.kde;
+        else if (f == "--kde-sharded") a.kde_sharded = !a.kde_sharded;
         else if (f == "--max-gap") a.max_gap = atoi(val().c_str());
         else if (f == "--overlap-frac") a.overlap_frac = atof(val().c_str());
         else if (f == "--weighted") a.weighted = !a.weighted;
@@ -174,6 +177,7 @@ Args parse(int argc, char **argv)
     if (a.have_cutoff && a.size_bounds.empty() && !a.nclust)
         usage("--lod-cutoff writes the ROH calls and needs --size-bounds (the size classes otherwise come from GARLIC's GMM stage, "
               "Phase II, not part of this tool)");
+    if (a.kde_sharded && !a.kde) usage("--kde-sharded needs --kde (it says where the KDE of --kde is computed)");
     if (a.kde && a.raw_lod) usage("--kde and --raw-lod exclude each other (the KDE path keeps the scores on the device)");
     if (a.kde && a.sorted_feed) usage("--kde and --sorted-feed exclude each other (with --kde no feed file is written)");
     if (a.kde && a.winsize_stream) usage("--kde and --winsize-stream exclude each other (with --kde the tool owns the KDE and runs --auto-winsize itself)");
@@ -279,12 +283,13 @@ int main(int argc, char **argv)
         std::cerr << "Filtered monomorphic" << (a.weighted ? " or out of bounds" : "") << " sites: " << kept << " loci kept\n";
 
         std::vector<int> sizes = a.winsize_multi.empty() ? std::vector<int>{a.winsize} : a.winsize_multi;
-        if (a.tgls_term_gb != 0 || a.sorted_feed) {
+        if (a.tgls_term_gb != 0 || a.sorted_feed || a.kde_sharded) {
             LodOptions lo;
             lo.devices = devices;
             // per device: the TGLS term matrix in slabs when it is larger than this
             if (a.tgls_term_gb != 0) lo.tgls_term_bytes = a.tgls_term_gb < 0 ? -1 : (long long)(a.tgls_term_gb * 1e9);
             lo.feed_sorted = a.sorted_feed;      // every feed of the engine arrives ascending
+            lo.kde_on_shards = a.kde_sharded;    // LodEngine::lodKde prints "KDE on <P> shards"
             setLodOptions(lo);
         }
         auto feed_file = [&](int W) { return a.out + "." + std::to_string(W) + (a.sorted_feed ? "SNPs.lod.sorted.f64" : "SNPs.lod.f64"); };

@@ -54,7 +54,9 @@ extern "C" {
  *    GARLIC_LD_PAIR_* / GARLIC_LD_SUM_* (likewise); garlic_panel_set_gl_codes16, GARLIC_TGLS_DICTIONARY16 (likewise);
  *    garlic_bed_create, garlic_bed_set_rows, garlic_bed_census, garlic_bed_destroy, garlic_panel_set_genotypes_bed (likewise);
  *    garlic_kde, GARLIC_KDE_POINTS, garlic_feed_kde, garlic_lod_kde, garlic_feed_kde_info, garlic_feed_kde_times (likewise);
- *    garlic_gmm, GARLIC_GMM_MAX_K, garlic_gmm_fit, garlic_gmm_fit_info (likewise) */
+ *    garlic_gmm, GARLIC_GMM_MAX_K, garlic_gmm_fit, garlic_gmm_fit_info (likewise); garlic_kde_part,
+ *    GARLIC_KDE_MAX_PARTS, garlic_kde_part_create, garlic_lod_kde_part, garlic_kde_part_destroy, garlic_kde_part_count,
+ *    garlic_kde_part_moment, garlic_kde_part_rank, garlic_kde_part_sums, garlic_kde_parts, garlic_kde_parts_info (likewise) */
 #define GARLIC_HIP_ABI_VERSION 8
 
 #define GARLIC_OK 0
@@ -590,6 +592,65 @@ int garlic_lod_kde(garlic_panel *panel, int32_t winsize, double error, int32_t m
                    garlic_kde *out, int64_t *chr_counts);
 int garlic_feed_kde_info(garlic_ctx *ctx, int64_t *chunks, int64_t *pairs_skipped, int64_t *scratch_bytes);
 int garlic_feed_kde_times(garlic_ctx *ctx, float *moments_ms, float *sums_ms);
+
+/* The KDE of a feed that is split into sorted parts: a sharded panel makes one part per shard, each on its shard's device,
+ * and no feed value leaves its device.  n, the sum, the sum of squared deviations and the 512 Gaussian sums add over the
+ * parts; lo / hi are a min and a max; the four order statistics x[k25], x[k25 + 1], x[k75], x[k75 + 1] of the union are
+ * found exactly with rank queries (csrc/kde_kernels.hpp: kde_rank_kernel; the descent and the combination rules:
+ * host/kde_parts.hpp).
+ *
+ * garlic_kde_part_create: `sorted` holds n >= 0 doubles in the key order of garlic_feed_sort (the library's own feeds are).
+ * GARLIC_DEVICE: borrowed, it must stay valid and unchanged until garlic_kde_part_destroy; GARLIC_HOST: uploaded into
+ * memory the part owns (the caller's buffer is free again on return).  A part's scratch (8 B per 2048 values, up to 8 MB
+ * of slice sums, 20 KB of probes and counts, a pinned block of the same size on the host) lives and ends with the part;
+ * destroy the parts before their context.  GARLIC_ERR_NOMEM leaves everything untouched.
+ * garlic_lod_kde_part: garlic_lod_kde up to, not including, the KDE: the panel's sorted device feed becomes the part.  It
+ * is borrowed from the panel's scratch: the next call on that panel that computes scores or a feed, or
+ * garlic_panel_release_scratch, or garlic_panel_destroy, makes the part stale, and any use of a stale part (destroy
+ * excepted) is GARLIC_ERR_STATE.  An empty feed is a valid part.
+ *
+ * The steps -- what a caller with one process per GPU all-reduces between:
+ * garlic_kde_part_moment: pass 0: *value = the part's sum (the tree of garlic_feed_kde), *lo = x[0], *hi = x[n - 1]; an
+ * empty part: 0.0, lo / hi untouched; GARLIC_ERR_INVALID with a message that names the cause for a NaN or an infinity,
+ * or x[i] < x[i - 1] somewhere.  Pass 1: *value = the sum of (x - mean)^2 for the mean given.  lo / hi may be NULL.
+ * garlic_kde_part_rank: below[t] = the number of the part's values whose key (garlic_feed_sort's) is below keys[t],
+ * 1 <= m <= 1024; an empty part: 0 everywhere.
+ * garlic_kde_part_sums: sums[j] = sum_i exp(-(x_i - targets[j])^2 * (1 / h^2)), 512 targets, NOT divided by anything; the
+ * chunk / slice partition (a function of the part's n alone), the exact skipping and the skipped-pair count of
+ * garlic_feed_kde.  An empty part: 0.0 everywhere.
+ *
+ * garlic_kde_parts: the whole KDE of the union of parts[0 .. n_parts), 1 <= n_parts <= GARLIC_KDE_MAX_PARTS, on any mix
+ * of contexts and devices; each step is enqueued on every part's stream before any is waited for.
+ *     n = sum n_p                                    (n < 2: the "at least 2 values" error)
+ *     mean = (((0.0 + s_0) + s_1) + ...) / (double)n,  ssq by the same rule,  sd = sqrt(ssq / (n - 1))
+ *     lo / hi: the min / max over the non-empty parts
+ *     the order statistics: a radix descent over the key, most significant byte first, exactly 8 rounds.  In a round the
+ *       four ranks probe their 256 candidate digits with one garlic_kde_part_rank (m = 1024) per part, the host adds the
+ *       parts' counts and keeps, per rank r, the largest digit whose count is <= r.  After round 8 the key is the value.
+ *     q25, q75, h, x: as garlic_feed_kde from these (same bandwidth errors)
+ *     raw[j] = ((((0.0 + S_0[j]) + S_1[j]) + ...) / (double)n,  y from raw as garlic_feed_kde
+ * The result is a pure function of (the parts' values, their order).  n, q25, q75, lo and hi do not depend on how the
+ * union is split.  With ONE part every field equals garlic_feed_kde's bit for bit.  Parts must be in garlic_feed_sort's
+ * key order; for a caller's buffer that puts +0.0 in front of -0.0 the sign of a zero order statistic is unspecified.
+ * GARLIC_ERR_INVALID with *out untouched: a NULL part or out, n_parts out of range, the same part twice, and what
+ * garlic_feed_kde refuses (it names the cause).
+ * garlic_kde_parts_info: of the last garlic_kde_parts (or step call) on these parts: chunks[p] = ceil(n_p / 2048),
+ * pairs_skipped[p], *rank_rounds (8 after garlic_kde_parts), sums_ms[p] the HIP-event time of part p's sums.  Any
+ * pointer but parts may be NULL. */
+#define GARLIC_KDE_MAX_PARTS 64
+typedef struct garlic_kde_part garlic_kde_part;
+int garlic_kde_part_create(garlic_ctx *ctx, const double *sorted, int64_t n, int32_t where, garlic_kde_part **part);
+int garlic_lod_kde_part(garlic_panel *panel, int32_t winsize, double error, int32_t max_gap, int32_t use_gl,
+                        int32_t weighted, int32_t M, double mu, int32_t step, const int32_t *ind_idx, int32_t n_idx,
+                        garlic_kde_part **part, int64_t *chr_counts);
+int garlic_kde_part_destroy(garlic_kde_part *part);
+int garlic_kde_part_count(garlic_kde_part *part, int64_t *n);
+int garlic_kde_part_moment(garlic_kde_part *part, int32_t pass, double mean, double *value, double *lo, double *hi);
+int garlic_kde_part_rank(garlic_kde_part *part, const uint64_t *keys, int32_t m, int64_t *below);
+int garlic_kde_part_sums(garlic_kde_part *part, const double *targets, double h, double *sums);
+int garlic_kde_parts(garlic_kde_part *const *parts, int32_t n_parts, garlic_kde *out);
+int garlic_kde_parts_info(garlic_kde_part *const *parts, int32_t n_parts, int64_t *chunks, int64_t *pairs_skipped,
+                          int32_t *rank_rounds, float *sums_ms);
 
 /* GMM::estimate (src/gmm.cpp:385-442) on the device: the EM fit of a 1-D mixture of k Gaussians that selectSizeClasses
  * (src/garlic-roh.cpp:935-1003) runs on the ROH lengths (csrc/gmm_kernels.hpp; the initial guess, the ordering of the

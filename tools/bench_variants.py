@@ -25,6 +25,8 @@ commit, which times the loop only; several lists separated by ";" share one pane
 --modes feed_kde: the device KDE (garlic_lod_kde: moment and sums kernels by HIP events, the whole call) beside the sorted
 garlic_lod_feed_subset call it replaces, at the --kde-inds and the everyone scale (--tree for the parent commit;
 profiles/feed_kde_ab.txt).
+--modes feed_kde_parts: the KDE of a panel sharded over two panels on the one device: the present path (sorted feeds to the
+host, merged, uploaded, garlic_feed_kde) beside garlic_lod_kde_part + garlic_kde_parts (profiles/kde_parts_ab.txt).
 --modes feed_sort: the sorted KDE feed (garlic_panel_set_feed_order / garlic_feed_sort) on real thinned feeds of one
 resident panel: the unweighted feed (step = winsize) of --kde-inds individuals (the --kde-subsample scale) and of
 everyone -- the device sort alone by HIP events, its bytes per second at 24 B x keys x passes run, the whole feed call in
@@ -456,6 +458,84 @@ def feed_kde_leg(args):
         panel.release_scratch()
 
 
+def feed_kde_parts_leg(args):
+    """The KDE of a panel sharded over two panels that split its individuals -- both on device 0, so this shows the saved
+    transfer and host merge, NOT the scaling of the sums over devices.  Per scale (--kde-inds, everyone) one JSON line with
+    two legs on real thinned feeds: "merged", the present several-shard path (every shard's sorted feed to the host, merged
+    there -- numpy's sort of the concatenation stands in for the tool's merge --, uploaded, garlic_feed_kde), and "parts"
+    (garlic_lod_kde_part per shard, garlic_kde_parts).  Host clock around each leg, warm-up call dropped, median and min;
+    the library's HIP-event times of the sums kernels of either path."""
+    import time
+    import torch
+    from garlic_amd import abi, synth
+
+    torch.cuda.set_device(0)
+    dev = torch.device("cuda", 0)
+    nloci, nind, W = args.snps, args.inds, args.winsize
+    error, max_gap = 0.001, 200000
+    spec = synth.PanelSpec(nloci, seed=20260105, max_gap=max_gap)
+    cut = nind // 2
+    bounds = [(0, cut), (cut, nind)]
+    ctxs = [abi.Context(0) for _ in bounds]
+    panels = []
+    for ctx, (b, e) in zip(ctxs, bounds):
+        panel = abi.Panel(ctx, spec.chr_nloci, e - b)
+        panel.set_map(spec.pos, spec.centro_start, spec.centro_end)
+        panel.set_freq(spec.freq)
+        panels.append(panel)
+    for l0, g in synth.genotype_chunks(spec, nind, dev):
+        for panel, (b, e) in zip(panels, bounds):
+            half = g[:, b:e].contiguous()
+            torch.cuda.synchronize()
+            panel.set_genotypes_device(half.data_ptr(), half.shape[1], l0, half.shape[0])
+            torch.cuda.synchronize()
+    del g, half
+    rng = np.random.default_rng(11)
+    subsets = [np.sort(rng.choice(nind, size=min(args.kde_inds, nind), replace=False)).astype(np.int32), None]
+    for idx in subsets:
+        split = [None, None] if idx is None else [idx[idx < cut], idx[idx >= cut] - cut]
+        legs = {}
+        for leg in ("merged", "parts"):
+            wall, sums_ms = [], []
+            for k in range(1 + args.steps):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                if leg == "merged":
+                    feeds = []
+                    for panel, mine in zip(panels, split):
+                        panel.set_feed_order(abi.FEED_ORDER_SORTED)
+                        feeds.append(panel.lod_feed(W, error, max_gap, W, ind_idx=mine)[0])
+                        panel.set_feed_order(abi.FEED_ORDER_REFERENCE)
+                    t1 = time.perf_counter()
+                    merged = np.sort(np.concatenate(feeds), kind="stable")
+                    t2 = time.perf_counter()
+                    kde = ctxs[0].feed_kde(merged)
+                    dt = time.perf_counter() - t0
+                    ms = [ctxs[0].feed_kde_times()["sums_ms"]]
+                    extra = {"host_merge_ms": (t2 - t1) * 1e3, "feed_bytes_each_way": 8 * int(merged.shape[0])}
+                else:
+                    parts = [panel.lod_kde_part(W, error, max_gap, W, ind_idx=mine)[0] for panel, mine in zip(panels, split)]
+                    kde = abi.kde_parts(parts)
+                    dt = time.perf_counter() - t0
+                    info = abi.kde_parts_info(parts)
+                    ms = [float(v) for v in info["sums_ms"]]
+                    extra = {"rank_rounds": info["rank_rounds"], "part_values": [p.count() for p in parts]}
+                    for p in parts:
+                        p.close()
+                if k:
+                    wall.append(dt * 1e3)
+                    sums_ms.append(ms)
+            legs[leg] = dict(extra, call_ms_median=float(np.median(wall)), call_ms_min=min(wall),
+                             sums_kernels_ms_median=[float(v) for v in np.median(np.array(sums_ms), axis=0)],
+                             n=int(kde["n"]), h=kde["h"], q25=kde["q25"], q75=kde["q75"])
+        assert all(legs["merged"][k] == legs["parts"][k] for k in ("n", "q25", "q75")), legs
+        print(json.dumps({"mode": "feed_kde_parts", "snps": nloci, "inds": nind, "winsize": W, "step": W, "shards": 2,
+                          "devices": [0, 0], "feed_individuals": nind if idx is None else int(idx.shape[0]),
+                          "repeats": args.steps, "merged": legs["merged"], "parts": legs["parts"]}), flush=True)
+        for panel in panels:
+            panel.release_scratch()
+
+
 def tgls_slabs_leg(args):
     """Host clock around the synchronous calls (the term pass, where there is one, is part of the call).  One panel; legs in
     this order so that the code table (host work of the first use_gl call) is built before anything is timed as a first
@@ -774,6 +854,8 @@ def main():
         return feed_sort_leg(args)
     if args.modes == "feed_kde":
         return feed_kde_leg(args)
+    if args.modes == "feed_kde_parts":
+        return feed_kde_parts_leg(args)
     if args.modes == "bed_ingest":
         return bed_ingest_leg(args)
     if args.modes == "ld_phased":
