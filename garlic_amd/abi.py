@@ -49,7 +49,13 @@ SYMBOLS = [
     "garlic_gmm_fit", "garlic_gmm_fit_info",
     "garlic_kde_part_create", "garlic_lod_kde_part", "garlic_kde_part_destroy", "garlic_kde_part_count",
     "garlic_kde_part_moment", "garlic_kde_part_rank", "garlic_kde_part_sums", "garlic_kde_parts", "garlic_kde_parts_info",
+    "garlic_feature_set_create", "garlic_feature_set_destroy", "garlic_feature_set_rows", "garlic_feature_set_sites",
+    "garlic_feature_counts", "garlic_feature_counts_info",
 ]
+FEATURE_MAX_EFFECTS = 256   # GARLIC_FEATURE_MAX_EFFECTS
+FEATURE_GROUP_EFFECTS = 32  # effects per launch
+FEATURE_CHUNK_ROWS = 4096   # rows per wavefront
+ROH_INTERVAL = np.dtype([("ind", "<i4"), ("chr", "<i4"), ("start", "<i4"), ("stop", "<i4"), ("cls", "<i4")])   # garlic_roh_interval
 KDE_POINTS = 512   # GARLIC_KDE_POINTS
 KDE_MAX_PARTS = 64   # GARLIC_KDE_MAX_PARTS
 KDE_RANK_MAX = 1024  # probe keys of one garlic_kde_part_rank
@@ -196,6 +202,12 @@ def lib():
     L.garlic_kde_part_sums.argtypes = [_vp, _f64p, C.c_double, _f64p]
     L.garlic_kde_parts.argtypes = [C.POINTER(_vp), C.c_int32, C.POINTER(Kde)]
     L.garlic_kde_parts_info.argtypes = [C.POINTER(_vp), C.c_int32, _i64p, _i64p, _i32p, C.POINTER(C.c_float)]
+    L.garlic_feature_set_create.argtypes = [_vp, C.c_int64, C.c_int32, C.POINTER(_vp)]
+    L.garlic_feature_set_destroy.argtypes = [_vp]
+    L.garlic_feature_set_rows.argtypes = [_vp, _vp, C.c_int64, C.c_int64, C.c_int64]
+    L.garlic_feature_set_sites.argtypes = [_vp, _i32p, _i32p, _i32p]
+    L.garlic_feature_counts.argtypes = [_vp, _vp, C.c_int64, C.c_int32, C.c_int32, _vp, C.c_int32]
+    L.garlic_feature_counts_info.argtypes = [_vp, _i64p, _i64p, _i64p, C.POINTER(C.c_float)]
     L.garlic_gmm_fit.argtypes = [_vp, _vp, C.c_int64, C.c_int32, C.c_int32, _f64p, _f64p, _f64p, C.c_int32, C.c_double, C.POINTER(Gmm)]
     L.garlic_gmm_fit_info.argtypes = [_vp, _i64p, _i64p, C.POINTER(C.c_float)]
     L.garlic_bed_create.argtypes = [_vp, C.c_int64, C.c_int32, C.POINTER(_vp)]
@@ -345,6 +357,77 @@ class Context:
     def close(self):
         if self.handle:
             lib().garlic_ctx_destroy(self.handle)
+            self.handle = _vp()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class FeatureSet:
+    """garlic_feature_set: the hom rows of annotated alleles over nind individuals (garlic_hip.h).  rows: uint8 [nrows,
+    row_bytes], bit i & 7 of byte i >> 3 is individual i; chr / pos / effect: int32 [nrows], sorted by (chr, pos).  Close it
+    before its context."""
+
+    def __init__(self, ctx, nrows, nind, rows=None, chr=None, pos=None, effect=None):
+        self.nrows, self.nind = int(nrows), int(nind)
+        self.handle = _vp()
+        check(lib().garlic_feature_set_create(ctx.handle, self.nrows, self.nind, C.byref(self.handle)))
+        try:
+            if rows is not None and self.nrows:
+                self.set_rows(rows)
+            if chr is not None:
+                self.set_sites(chr, pos, effect)
+        except Exception:
+            self.close()
+            raise
+
+    def set_rows(self, rows, row_begin=0):
+        rows = np.ascontiguousarray(rows, dtype=np.uint8)
+        assert rows.ndim == 2
+        check(lib().garlic_feature_set_rows(self.handle, _vp(rows.ctypes.data), rows.shape[1], int(row_begin), rows.shape[0]))
+
+    def set_sites(self, chr, pos, effect):
+        a = [np.ascontiguousarray(v, dtype=np.int32) for v in (chr, pos, effect)]
+        assert all(v.shape == (self.nrows,) for v in a)
+        check(lib().garlic_feature_set_sites(self.handle, *[_ptr(v, _i32p) for v in a]))
+
+    @staticmethod
+    def _intervals(intervals):
+        iv = np.ascontiguousarray(intervals, dtype=ROH_INTERVAL)
+        assert iv.ndim == 1
+        return iv
+
+    def counts(self, intervals, n_classes, n_effects):
+        """garlic_feature_counts to the host: int64 [nind, n_classes + 1, n_effects]; intervals: an array of ROH_INTERVAL"""
+        iv = self._intervals(intervals)
+        out = np.full((self.nind, n_classes + 1, n_effects), -1, dtype=np.int64)
+        check(lib().garlic_feature_counts(self.handle, _vp(iv.ctypes.data) if iv.shape[0] else None, iv.shape[0], int(n_classes),
+                                          int(n_effects), _vp(out.ctypes.data), HOST))
+        return out
+
+    def counts_device(self, intervals, n_classes, n_effects, out):
+        """the same into device memory (out: a torch int64 tensor of nind * (n_classes + 1) * n_effects elements, or its
+        address): enqueued on the context's stream, no wait"""
+        iv = self._intervals(intervals)
+        ptr = out if isinstance(out, int) else out.data_ptr()
+        if not isinstance(out, int):
+            assert out.numel() >= self.nind * (n_classes + 1) * n_effects and out.element_size() == 8 and out.is_contiguous()
+        check(lib().garlic_feature_counts(self.handle, _vp(iv.ctypes.data) if iv.shape[0] else None, iv.shape[0], int(n_classes),
+                                          int(n_effects), _vp(ptr), DEVICE))
+
+    def info(self):
+        """garlic_feature_counts_info: {blocks, chunks, words_skipped, kernel_ms} of the last count (waits for it)"""
+        b, c, w = C.c_int64(), C.c_int64(), C.c_int64()
+        ms = C.c_float()
+        check(lib().garlic_feature_counts_info(self.handle, C.byref(b), C.byref(c), C.byref(w), C.byref(ms)))
+        return {"blocks": b.value, "chunks": c.value, "words_skipped": w.value, "kernel_ms": ms.value}
+
+    def close(self):
+        if self.handle:
+            lib().garlic_feature_set_destroy(self.handle)
             self.handle = _vp()
 
     def __enter__(self):

@@ -23,6 +23,7 @@
 #include "feed_sort_kernel.hpp"
 #include "kde_kernels.hpp"
 #include "gmm_kernels.hpp"
+#include "feature_kernels.hpp"
 #include "../host/kde_select.hpp"
 #include "../host/kde_parts.hpp"
 #include "../host/chain_order.hpp"
@@ -6241,6 +6242,220 @@ int garlic_gmm_fit_info(garlic_ctx *ctx, int64_t *blocks, int64_t *scratch_bytes
     if (blocks) *blocks = ctx->gmm_blocks;
     if (scratch_bytes) *scratch_bytes = (int64_t)ctx->gmm.bytes();
     if (em_ms) *em_ms = ctx->gmm_em_ms;
+    return GARLIC_OK;
+}
+
+// ---- count_features_in_roh.pl on the device (feature_kernels.hpp).  A feature set holds the hom rows of the annotated
+// alleles block-major, with the rows' chromosome, position and effect; a call brings one list of classified intervals and
+// counts.  The intervals and their per-individual offsets travel through a pinned block of the set's, so the call enqueues
+// and returns: the only wait is for the previous call's upload out of that block (an event), never for the stream.
+struct garlic_feature_set {
+    garlic_ctx *ctx = nullptr;
+    int64_t nrows = 0;
+    int32_t nind = 0, nblk = 0;
+    bool have_sites = false;
+    int32_t max_effect = -1;
+    DevBuf<uint64_t> bits;                         // [blk][row]
+    DevBuf<int32_t> chr, pos, eff;
+    DevBuf<FeatInterval> iv;
+    DevBuf<int32_t> off;
+    DevBuf<unsigned long long> counts, skipped;
+    void *pinned = nullptr;                        // intervals, then offsets
+    size_t pinned_bytes = 0;
+    hipEvent_t uploaded = nullptr, ev[2] = {};
+    bool upload_pending = false, timed = false;
+    int64_t blocks = 0, chunks = 0, launches = 0;
+};
+
+static void feature_set_free(garlic_feature_set *fs)
+{
+    if (fs->uploaded) (void)hipEventDestroy(fs->uploaded);
+    for (auto &e : fs->ev)
+        if (e) (void)hipEventDestroy(e);
+    if (fs->pinned) (void)hipHostFree(fs->pinned);
+    delete fs;
+}
+
+int garlic_feature_set_create(garlic_ctx *ctx, int64_t nrows, int32_t nind, garlic_feature_set **out)
+{
+    static_assert(sizeof(FeatInterval) == sizeof(garlic_roh_interval) && FEAT_MAX_EFFECTS == GARLIC_FEATURE_MAX_EFFECTS &&
+                  FEAT_MAX_CLASSES == GARLIC_GMM_MAX_K, "one interval, one set of limits");
+    if (!ctx || !out) return fail(GARLIC_ERR_INVALID, "feature set: context and set are required");
+    if (nrows < 0 || nind < 1) return fail(GARLIC_ERR_INVALID, "feature set: %lld rows, %d individuals (>= 0 and >= 1)", (long long)nrows, (int)nind);
+    const int64_t nblk = ((int64_t)nind + WAVE - 1) / WAVE, n_chunks = (nrows + FEAT_CHUNK_ROWS - 1) / FEAT_CHUNK_ROWS;
+    if (nblk * n_chunks > 0x7fffffff) return fail(GARLIC_ERR_INVALID, "feature set: %lld rows x %d individuals are more wavefronts than one launch holds", (long long)nrows, (int)nind);
+    int rc;
+    if ((rc = set_device(ctx))) return rc;
+    std::unique_ptr<garlic_feature_set, void (*)(garlic_feature_set *)> fs(new garlic_feature_set, feature_set_free);
+    fs->ctx = ctx;
+    fs->nrows = nrows;
+    fs->nind = nind;
+    fs->nblk = (int32_t)nblk;
+    const size_t rows = (size_t)std::max<int64_t>(nrows, 1);
+    if ((rc = fs->bits.reserve(rows * (size_t)nblk)) || (rc = fs->chr.reserve(rows)) || (rc = fs->pos.reserve(rows)) || (rc = fs->eff.reserve(rows)) ||
+        (rc = fs->off.reserve((size_t)nind + 1)) || (rc = fs->skipped.reserve(1)))
+        return rc;
+    HIP_TRY(hipEventCreateWithFlags(&fs->uploaded, hipEventDisableTiming));
+    for (auto &e : fs->ev) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipMemsetAsync(fs->bits.p, 0, sizeof(uint64_t) * rows * (size_t)nblk, ctx->stream));    // rows never set hold no homozygote
+    *out = fs.release();
+    return GARLIC_OK;
+}
+
+int garlic_feature_set_destroy(garlic_feature_set *fs)
+{
+    if (!fs) return GARLIC_OK;
+    (void)hipSetDevice(fs->ctx->device);
+    (void)hipStreamSynchronize(fs->ctx->stream);
+    feature_set_free(fs);
+    return GARLIC_OK;
+}
+
+int garlic_feature_set_rows(garlic_feature_set *fs, const uint8_t *bits, int64_t row_bytes, int64_t row_begin, int64_t row_count)
+{
+    if (!fs || !bits) return fail(GARLIC_ERR_INVALID, "feature set and rows are required");
+    if (row_bytes < ((int64_t)fs->nind + 7) / 8) return fail(GARLIC_ERR_INVALID, "row_bytes %lld < %d bits", (long long)row_bytes, fs->nind);
+    if (row_begin < 0 || row_count < 1 || row_begin + row_count > fs->nrows)
+        return fail(GARLIC_ERR_INVALID, "row range [%lld,+%lld) outside feature set of %lld rows", (long long)row_begin, (long long)row_count, (long long)fs->nrows);
+    int rc;
+    if ((rc = set_device(fs->ctx))) return rc;
+    hipStream_t s = fs->ctx->stream;
+    DevBuf<uint8_t> stage;
+    return for_each_upload_slab(s, "feature_set_rows", bits, row_bytes, row_count, GARLIC_HOST, stage, [&](const void *src, int64_t at, int64_t n) {
+        hipLaunchKernelGGL(phase_bits_planes_kernel, dim3((unsigned)((n + WAVE - 1) / WAVE)), dim3(256), 0, s, (const uint8_t *)src, row_bytes,
+                           row_begin + at, n, fs->nind, fs->nblk, fs->nrows, fs->bits.p);
+        return GARLIC_OK;
+    });
+}
+
+int garlic_feature_set_sites(garlic_feature_set *fs, const int32_t *chr, const int32_t *pos, const int32_t *effect)
+{
+    if (!fs) return fail(GARLIC_ERR_INVALID, "feature set is NULL");
+    if (fs->nrows > 0 && (!chr || !pos || !effect)) return fail(GARLIC_ERR_INVALID, "feature set: chr, pos and effect are required");
+    int32_t max_effect = -1;
+    for (int64_t r = 0; r < fs->nrows; r++) {
+        if (chr[r] < 0 || effect[r] < 0 || effect[r] >= GARLIC_FEATURE_MAX_EFFECTS)
+            return fail(GARLIC_ERR_INVALID, "feature set: row %lld has chromosome %d, effect %d (chromosome >= 0, effect in [0, %d))", (long long)r,
+                        (int)chr[r], (int)effect[r], GARLIC_FEATURE_MAX_EFFECTS);
+        if (r && (chr[r] < chr[r - 1] || (chr[r] == chr[r - 1] && pos[r] < pos[r - 1])))
+            return fail(GARLIC_ERR_INVALID, "feature set: rows are not sorted by (chromosome, position) at row %lld", (long long)r);
+        max_effect = std::max(max_effect, effect[r]);
+    }
+    int rc;
+    if ((rc = set_device(fs->ctx))) return rc;
+    hipStream_t s = fs->ctx->stream;
+    if (fs->nrows > 0) {
+        const size_t bytes = sizeof(int32_t) * (size_t)fs->nrows;
+        HIP_TRY(hipMemcpyAsync(fs->chr.p, chr, bytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(fs->pos.p, pos, bytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(fs->eff.p, effect, bytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));          // the caller's arrays are free on return
+    }
+    fs->max_effect = max_effect;
+    fs->have_sites = true;
+    return GARLIC_OK;
+}
+
+int garlic_feature_counts(garlic_feature_set *fs, const garlic_roh_interval *intervals, int64_t n_intervals, int32_t n_classes,
+                          int32_t n_effects, int64_t *counts, int32_t where)
+{
+    if (!fs || !counts) return fail(GARLIC_ERR_INVALID, "feature counts: set and counts are required");
+    if (where != GARLIC_HOST && where != GARLIC_DEVICE) return fail(GARLIC_ERR_INVALID, "feature counts: where must be GARLIC_HOST or GARLIC_DEVICE");
+    if (n_intervals < 0 || n_intervals > 0x7fffffff || (n_intervals > 0 && !intervals))
+        return fail(GARLIC_ERR_INVALID, "feature counts: %lld intervals (0 to 2^31 - 1, with a list)", (long long)n_intervals);
+    if (n_classes < 1 || n_classes > GARLIC_GMM_MAX_K) return fail(GARLIC_ERR_INVALID, "feature counts: %d classes (1 to %d)", (int)n_classes, GARLIC_GMM_MAX_K);
+    if (n_effects < 1 || n_effects > GARLIC_FEATURE_MAX_EFFECTS)
+        return fail(GARLIC_ERR_INVALID, "feature counts: %d effects (1 to %d)", (int)n_effects, GARLIC_FEATURE_MAX_EFFECTS);
+    if (!fs->have_sites) return fail(GARLIC_ERR_STATE, "feature counts: the set needs garlic_feature_set_sites first");
+    if (fs->max_effect >= n_effects) return fail(GARLIC_ERR_INVALID, "feature counts: a row has effect %d, n_effects is %d", (int)fs->max_effect, (int)n_effects);
+    for (int64_t i = 0; i < n_intervals; i++) {
+        const garlic_roh_interval &v = intervals[i];
+        if (v.ind < 0 || v.ind >= fs->nind) return fail(GARLIC_ERR_INVALID, "feature counts: interval %lld has individual %d (0 to %d)", (long long)i, (int)v.ind, fs->nind - 1);
+        if (v.cls < 0 || v.cls >= n_classes) return fail(GARLIC_ERR_INVALID, "feature counts: interval %lld has class %d (0 to %d)", (long long)i, (int)v.cls, n_classes - 1);
+        if (v.chr < 0 || v.stop < v.start) return fail(GARLIC_ERR_INVALID, "feature counts: interval %lld has chromosome %d, [%d, %d)", (long long)i, (int)v.chr, (int)v.start, (int)v.stop);
+        if (!i) continue;
+        const garlic_roh_interval &u = intervals[i - 1];
+        if (v.ind < u.ind || (v.ind == u.ind && (v.chr < u.chr || (v.chr == u.chr && v.start < u.start))))
+            return fail(GARLIC_ERR_INVALID, "feature counts: intervals are not ordered by (individual, chromosome, start) at interval %lld", (long long)i);
+        if (v.ind == u.ind && v.chr == u.chr && v.start < u.stop)
+            return fail(GARLIC_ERR_INVALID, "feature counts: interval %lld overlaps the one before it", (long long)i);
+    }
+    int rc;
+    if ((rc = set_device(fs->ctx))) return rc;
+    hipStream_t s = fs->ctx->stream;
+    // the pinned block: free again once the previous call's copies out of it have run
+    if (fs->upload_pending) HIP_TRY(hipEventSynchronize(fs->uploaded));
+    fs->upload_pending = false;
+    const size_t iv_bytes = sizeof(FeatInterval) * (size_t)n_intervals, off_bytes = sizeof(int32_t) * ((size_t)fs->nind + 1);
+    const size_t off_at = (iv_bytes + 15) & ~(size_t)15, need = off_at + off_bytes;
+    if (need > fs->pinned_bytes) {
+        if (fs->pinned) HIP_TRY(hipHostFree(fs->pinned));
+        fs->pinned = nullptr;
+        fs->pinned_bytes = 0;
+        HIP_TRY(hipHostMalloc(&fs->pinned, need + need / 2, hipHostMallocDefault));
+        fs->pinned_bytes = need + need / 2;
+    }
+    const size_t n_counts = (size_t)fs->nind * (size_t)(n_classes + 1) * (size_t)n_effects;
+    if ((rc = fs->iv.reserve(std::max<size_t>((size_t)n_intervals, 1))) || (where == GARLIC_HOST && (rc = fs->counts.reserve(n_counts)))) return rc;
+    uint8_t *pin = (uint8_t *)fs->pinned;
+    if (n_intervals) memcpy(pin, intervals, iv_bytes);
+    int32_t *off = (int32_t *)(pin + off_at);
+    {
+        int64_t i = 0;
+        for (int32_t ind = 0; ind <= fs->nind; ind++) {
+            while (i < n_intervals && intervals[i].ind < ind) i++;
+            off[ind] = (int32_t)i;
+        }
+    }
+    if (n_intervals) HIP_TRY(hipMemcpyAsync(fs->iv.p, pin, iv_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(fs->off.p, off, off_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(fs->uploaded, s));
+    fs->upload_pending = true;
+    unsigned long long *d_counts = where == GARLIC_HOST ? fs->counts.p : (unsigned long long *)counts;
+    HIP_TRY(hipMemsetAsync(d_counts, 0, sizeof(unsigned long long) * n_counts, s));
+    HIP_TRY(hipMemsetAsync(fs->skipped.p, 0, sizeof(unsigned long long), s));
+    const int64_t n_chunks = (fs->nrows + FEAT_CHUNK_ROWS - 1) / FEAT_CHUNK_ROWS;
+    int64_t launches = 0;
+    HIP_TRY(hipEventRecord(fs->ev[0], s));
+    if (n_chunks > 0)
+        for (int e0 = 0; e0 <= fs->max_effect; e0 += FEAT_GROUP_EFFECTS, launches++) {
+            const int ge = std::min<int>(FEAT_GROUP_EFFECTS, n_effects - e0);
+            const size_t lds = feature_counts_lds(n_classes, ge);
+            if (lds > LDS_DEFAULT_MAX) HIP_TRY(hipFuncSetAttribute((const void *)feature_counts_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL(feature_counts_kernel, dim3((unsigned)(n_chunks * fs->nblk)), dim3(WAVE), lds, s, fs->bits.p, fs->chr.p, fs->pos.p,
+                               fs->eff.p, fs->nrows, fs->nind, n_chunks, fs->iv.p, fs->off.p, (int)n_classes, (int)n_effects, e0, ge, d_counts,
+                               e0 == 0 ? fs->skipped.p : nullptr);        // zero words are counted once, not once per launch
+            HIP_TRY(hipGetLastError());
+        }
+    HIP_TRY(hipEventRecord(fs->ev[1], s));
+    fs->timed = true;
+    fs->blocks = fs->nblk;
+    fs->chunks = n_chunks;
+    fs->launches = launches;
+    if (where == GARLIC_HOST) {
+        HIP_TRY(hipMemcpyAsync(counts, fs->counts.p, sizeof(int64_t) * n_counts, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    return GARLIC_OK;
+}
+
+int garlic_feature_counts_info(garlic_feature_set *fs, int64_t *blocks, int64_t *chunks, int64_t *words_skipped, float *kernel_ms)
+{
+    if (!fs) return fail(GARLIC_ERR_INVALID, "feature set is NULL");
+    if (blocks) *blocks = fs->blocks;
+    if (chunks) *chunks = fs->chunks;
+    if (!words_skipped && !kernel_ms) return GARLIC_OK;
+    int rc;
+    if ((rc = set_device(fs->ctx))) return rc;
+    unsigned long long skipped = 0;
+    float ms = 0.f;
+    if (fs->timed) {                               // waits for the last call's kernels
+        HIP_TRY(hipMemcpyAsync(&skipped, fs->skipped.p, sizeof skipped, hipMemcpyDeviceToHost, fs->ctx->stream));
+        HIP_TRY(hipStreamSynchronize(fs->ctx->stream));
+        if (hipEventElapsedTime(&ms, fs->ev[0], fs->ev[1]) != hipSuccess) ms = 0.f;
+    }
+    if (words_skipped) *words_skipped = (int64_t)skipped;
+    if (kernel_ms) *kernel_ms = ms;
     return GARLIC_OK;
 }
 

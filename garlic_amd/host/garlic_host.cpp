@@ -1392,6 +1392,96 @@ void LodEngine::upload(std::vector<HapData *> *haps, std::vector<FreqData *> *fr
 
 LodEngine::~LodEngine() { release(); }
 
+// ---- feature counts per ROH class (feature_counts.hpp)
+FeatureData *loadFeatureCounts(const std::string &features, const std::string &tpedCounting, const std::string &tfamCounting)
+{
+    try {
+        FeatureData *d = new FeatureData(loadFeatureData(features, tpedCounting, tfamCounting));
+        std::cerr << "Feature counts: " << d->ann.allele.size() << " annotated alleles, " << d->ann.effects.size() << " effects; "
+                  << d->rows.lines_annotated << " of " << d->rows.lines << " counting loci annotated, " << d->iid.size() << " individuals\n";
+        return d;
+    } catch (const std::exception &e) {
+        fail(e.what());
+    }
+}
+
+void releaseFeatureCounts(FeatureData *data) { delete data; }
+
+namespace {
+// the hom rows onto the device, the count, the table
+void featureCountsOn(garlic_ctx *ctx, const FeatureData &d, const std::vector<FeatureInterval> &iv, int n_classes, const std::string &outfile)
+{
+    static_assert(sizeof(FeatureInterval) == sizeof(garlic_roh_interval), "one interval");
+    const size_t nind = d.iid.size(), ne = d.ann.effects.size();
+    std::vector<int64_t> counts(nind * (size_t)(n_classes + 1) * std::max<size_t>(ne, 1), 0);
+    if (ne > 0) {
+        garlic_feature_set *fs = nullptr;
+        check(garlic_feature_set_create(ctx, d.rows.nrows(), (int32_t)nind, &fs), "garlic_feature_set_create");
+        int rc = GARLIC_OK;
+        const char *what = "";
+        if (d.rows.nrows() > 0) {
+            what = "garlic_feature_set_rows";
+            rc = garlic_feature_set_rows(fs, d.rows.bits.data(), d.rows.row_bytes, 0, d.rows.nrows());
+        }
+        if (rc == GARLIC_OK) {
+            what = "garlic_feature_set_sites";
+            rc = garlic_feature_set_sites(fs, d.rows.chr.data(), d.rows.pos.data(), d.rows.effect.data());
+        }
+        if (rc == GARLIC_OK) {
+            what = "garlic_feature_counts";
+            rc = garlic_feature_counts(fs, (const garlic_roh_interval *)iv.data(), (int64_t)iv.size(), n_classes, (int32_t)ne, counts.data(), GARLIC_HOST);
+        }
+        const std::string error = rc == GARLIC_OK ? "" : std::string(what) + ": " + garlic_hip_last_error();
+        garlic_feature_set_destroy(fs);
+        if (!error.empty()) fail(error);
+    }
+    std::ofstream out(outfile.c_str());
+    if (out.fail()) fail("Failed to open " + outfile);
+    writeFeatureTable(out, d.ann.effects, d.iid, counts.data(), n_classes);
+    out.close();
+    std::cerr << "Feature counts: " << outfile << " (" << d.rows.nrows() << " hom rows, " << iv.size() << " ROH, " << n_classes << " classes)\n";
+}
+} // namespace
+
+void featureCountsFromBed(FeatureData *data, const std::string &rohBed, const std::string &outfile, int device)
+{
+    if (!data) fail("featureCountsFromBed: no feature data");
+    int n_classes = 0;
+    std::vector<FeatureInterval> iv;
+    try {
+        iv = readRohBed(rohBed, data->iid, data->chrs, &n_classes);
+    } catch (const std::exception &e) {
+        fail(e.what());
+    }
+    garlic_ctx *ctx = nullptr;
+    check(garlic_ctx_create(device, nullptr, &ctx), "garlic_ctx_create");
+    try {
+        featureCountsOn(ctx, *data, iv, n_classes, outfile);
+    } catch (...) {
+        garlic_ctx_destroy(ctx);
+        throw;
+    }
+    garlic_ctx_destroy(ctx);
+}
+
+void LodEngine::featureCounts(FeatureData *data, std::vector<ROHData *> *rohDataByInd, std::vector<MapData *> *mapDataByChr,
+                              const std::vector<double> &bounds, const std::string &outfile)
+{
+    if (!data || !rohDataByInd || !mapDataByChr) fail("featureCounts: feature data, ROH calls and maps are required");
+    if ((int)bounds.size() + 1 > FEATURE_MAX_CLASSES) fail("featureCounts: at most " + std::to_string(FEATURE_MAX_CLASSES) + " size classes");
+    std::vector<std::string> panel_iid;
+    std::vector<std::vector<FeatureCall>> calls;
+    for (const ROHData *r : *rohDataByInd) {
+        panel_iid.push_back(r->indID);
+        calls.emplace_back();
+        for (size_t k = 0; k < r->chr.size(); k++)       // start / stop as writeROHData prints them
+            calls.back().push_back(FeatureCall{mapDataByChr->at((size_t)r->chr[k])->chr, int(r->start[k]), int(r->stop[k]), r->length[k]});
+    }
+    int n_classes = 0;
+    const std::vector<FeatureInterval> iv = buildFeatureIntervals(panel_iid, calls, bounds, data->iid, data->chrs, &n_classes);
+    featureCountsOn(impl->shards[0].ctx, *data, iv, n_classes, outfile);
+}
+
 void LodEngine::tglsTermSlabs(int *slab_blocks, int *n_slabs)
 {
     int32_t sb = 0, ns = 0;

@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 
+#include "feature_counts.hpp"
 #include "feed_merge.hpp"
 #include "kde_select.hpp"
 #include "size_classes.hpp"
@@ -266,6 +267,15 @@ void releaseROHLength(ROHLength *rohLength);                           // :556-5
 void writeROHData(const std::string &outfile, std::vector<ROHData *> *rohDataByInd, std::vector<MapData *> *mapDataByChr,
                   const std::vector<double> &bounds, const std::string &popName, const std::string &version, bool CM);
 
+// ---- feature counts per ROH class (the reference's src/count_features_in_roh.pl; feature_counts.hpp holds the readers and
+// the writer, csrc/feature_kernels.hpp the counting).  loadFeatureCounts reads the feature file and the counting TPED /
+// TFAM once; `throw 0` with a message that names file and line for what feature_counts.hpp refuses.
+// featureCountsFromBed: the table of an existing .roh.bed on `device`, no panel needed.  The table has the script's
+// columns A B C NONE per effect; with more than three classes A .. <last letter> NONE.
+FeatureData *loadFeatureCounts(const std::string &features, const std::string &tpedCounting, const std::string &tfamCounting);
+void releaseFeatureCounts(FeatureData *data);
+void featureCountsFromBed(FeatureData *data, const std::string &rohBed, const std::string &outfile, int device);
+
 // ---- the path (drop-in signatures)
 struct LodOptions {
     std::vector<int> devices;   // HIP device ordinals; empty = {0}.  Individuals shard contiguously.
@@ -375,6 +385,11 @@ public:
     // lengths alone, so one shard or several give the same bits.  Prints the reference's "Gaussian class" lines to stderr;
     // `throw 0` where the reference aborts (no sign change between two means, no convergence of the root search).
     std::vector<double> selectSizeClasses(const ROHLength *rohLength, int nclust);
+    // The feature counts of calls that are still in memory (what writeROHData was given): the intervals get writeROHData's
+    // classes from `bounds`, panel individuals map to the counting TFAM's by id, and the table is written to outfile.  Runs
+    // on the engine's first device: the counts are per individual of the COUNTING file, which no shard splits.
+    void featureCounts(FeatureData *data, std::vector<ROHData *> *rohDataByInd, std::vector<MapData *> *mapDataByChr,
+                       const std::vector<double> &bounds, const std::string &outfile);
     // garlic_panel_tgls_terms_info of the first shard: the slabs of its last call with likelihoods, weighted or not (n_slabs 0: none)
     void tglsTermSlabs(int *slab_blocks, int *n_slabs);
     LodEngine(const LodEngine &) = delete;

@@ -59,6 +59,9 @@ struct Args {
     double lod_cutoff = 0.0;
     std::vector<double> size_bounds;        // --size-bounds (:107)
     int nclust = 0;                         // --nclust (:163): the size classes from the GMM of the ROH lengths; 0 = not given
+    // --features / --tped-counting / --tfam-counting (:177-189, declared there and never wired in: the reference leaves the
+    // stage to src/count_features_in_roh.pl); --roh-bed: extension, count on an existing calls file and exit
+    std::string features, tped_counting, tfam_counting, roh_bed;
 };
 
 [[noreturn]] void usage(const char *msg)
@@ -79,6 +82,13 @@ struct Args {
                  "         [--kde]   (<out>.<W>SNPs.kde and the LOD cutoff from the KDE on the device instead of the feed files; with\n"
                  "                    --size-bounds and no --lod-cutoff the ROH calls use it; with --auto-winsize the window size too)\n"
                  "         [--kde-sharded]   (with --kde: every shard's feed stays on its device, the KDE is reduced over the shards)\n"
+                 "         [--features F --tped-counting T [--tfam-counting M]]   (with a run that writes ROH calls: per individual of T / M\n"
+                 "                    the homozygous genotypes of F's annotated alleles (lines `chrN:pos ref allele effect`) inside ROH of\n"
+                 "                    each size class and outside any, <out>[.<W>SNPs].feature.counts, counted on the device; M defaults\n"
+                 "                    to T with .tped replaced by .tfam.  The columns are count_features_in_roh.pl's <effect>A B C NONE;\n"
+                 "                    with more than three size classes they run A .. <last letter> NONE, so nothing is dropped)\n"
+                 "         [--roh-bed F --features F --tped-counting T [--tfam-counting M] --out P]   (no genotype input: the same table\n"
+                 "                    for the calls of an existing .roh.bed, <out>.feature.counts, then exit)\n"
                  "         (--bfile / --bed --bim --fam: PLINK SNP-major .bed input, read on the device; not with --tped / --tfam /\n"
                  "          --phased; --genotype-cache F is then written from the .bed, never read)\n";
     exit(1);
@@ -129,6 +139,10 @@ Args parse(int argc, char **argv)
             if (a.nclust <= 0) usage("Must choose positive number for number of GMM clusters.");   // checkNCLUST
             if (a.nclust > GMM_MAX_K) usage("--nclust: at most 8 GMM clusters");
         }
+        else if (f == "--features") a.features = val();
+        else if (f == "--tped-counting") a.tped_counting = val();
+        else if (f == "--tfam-counting") a.tfam_counting = val();
+        else if (f == "--roh-bed") a.roh_bed = val();
         else if (f == "--M") a.M = atoi(val().c_str());
         else if (f == "--mu") a.mu = atof(val().c_str());
         else if (f == "--threads") a.threads = atoi(val().c_str());
@@ -149,6 +163,15 @@ Args parse(int argc, char **argv)
             while (std::getline(ss, tok, ',')) a.devices.push_back(atoi(tok.c_str()));
         }
         else usage(("unknown flag " + f).c_str());
+    }
+    if (!a.features.empty() || !a.tped_counting.empty() || !a.tfam_counting.empty() || !a.roh_bed.empty()) {
+        if (a.features.empty() || a.tped_counting.empty()) usage("feature counts need --features and --tped-counting");
+        if (a.tfam_counting.empty()) a.tfam_counting = featureTfamOf(a.tped_counting);
+    }
+    if (!a.roh_bed.empty()) {      // counts on an existing calls file: nothing else is read
+        if (!a.tped.empty() || !a.tfam.empty() || !a.bfile.empty() || !a.bed.empty()) usage("--roh-bed counts on existing calls and takes no genotype input");
+        if (a.devices.empty()) a.devices.push_back(0);
+        return a;
     }
     // validators of src/garlic-cli.cpp:240-462 that concern Phase I
     if (!a.bfile.empty()) {
@@ -177,6 +200,8 @@ Args parse(int argc, char **argv)
     if (a.have_cutoff && a.size_bounds.empty() && !a.nclust)
         usage("--lod-cutoff writes the ROH calls and needs --size-bounds (the size classes otherwise come from GARLIC's GMM stage, "
               "Phase II, not part of this tool)");
+    if (!a.features.empty() && !((a.have_cutoff || a.kde) && (!a.size_bounds.empty() || a.nclust)))
+        usage("--features counts inside ROH calls: give --roh-bed, or a run that writes them (--lod-cutoff or --kde, with --size-bounds or --nclust)");
     if (a.kde_sharded && !a.kde) usage("--kde-sharded needs --kde (it says where the KDE of --kde is computed)");
     if (a.kde && a.raw_lod) usage("--kde and --raw-lod exclude each other (the KDE path keeps the scores on the device)");
     if (a.kde && a.sorted_feed) usage("--kde and --sorted-feed exclude each other (with --kde no feed file is written)");
@@ -200,6 +225,15 @@ int main(int argc, char **argv)
 {
     const Args a = parse(argc, argv);
     try {
+        struct FeatureOwner {
+            FeatureData *d = nullptr;
+            ~FeatureOwner() { releaseFeatureCounts(d); }
+        } fdata;
+        if (!a.features.empty()) fdata.d = loadFeatureCounts(a.features, a.tped_counting, a.tfam_counting);
+        if (!a.roh_bed.empty()) {
+            featureCountsFromBed(fdata.d, a.roh_bed, a.out + ".feature.counts", a.devices[0]);
+            return 0;
+        }
         centromere centro(a.build, a.centromere, "none");
         int numLoci = 0, numInd = 0;
         std::vector<HapData *> *haps = nullptr; std::vector<MapData *> *maps = nullptr;
@@ -340,8 +374,18 @@ int main(int argc, char **argv)
                 }
                 std::cerr << sizeBoundsLine(bounds);
             }
-            writeROHData((single ? a.out : a.out + "." + std::to_string(W) + "SNPs") + ".roh.bed", roh, maps, bounds, ind->pop,
+            const std::string stem = single ? a.out : a.out + "." + std::to_string(W) + "SNPs";
+            writeROHData(stem + ".roh.bed", roh, maps, bounds, ind->pop,
                          "1.1.6a", a.cm);      // the track lines name the format's version (garlic VERSION); this tool says who it is on stderr
+            if (fdata.d) {
+                try {
+                    engine.featureCounts(fdata.d, roh, maps, bounds, stem + ".feature.counts");
+                } catch (...) {
+                    releaseROHData(roh);
+                    releaseROHLength(len);
+                    throw;
+                }
+            }
             releaseROHData(roh);
             releaseROHLength(len);
         };

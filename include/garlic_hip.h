@@ -56,7 +56,10 @@ extern "C" {
  *    garlic_kde, GARLIC_KDE_POINTS, garlic_feed_kde, garlic_lod_kde, garlic_feed_kde_info, garlic_feed_kde_times (likewise);
  *    garlic_gmm, GARLIC_GMM_MAX_K, garlic_gmm_fit, garlic_gmm_fit_info (likewise); garlic_kde_part,
  *    GARLIC_KDE_MAX_PARTS, garlic_kde_part_create, garlic_lod_kde_part, garlic_kde_part_destroy, garlic_kde_part_count,
- *    garlic_kde_part_moment, garlic_kde_part_rank, garlic_kde_part_sums, garlic_kde_parts, garlic_kde_parts_info (likewise) */
+ *    garlic_kde_part_moment, garlic_kde_part_rank, garlic_kde_part_sums, garlic_kde_parts, garlic_kde_parts_info (likewise);
+ *    garlic_feature_set, garlic_roh_interval, GARLIC_FEATURE_MAX_EFFECTS, garlic_feature_set_create,
+ *    garlic_feature_set_destroy, garlic_feature_set_rows, garlic_feature_set_sites, garlic_feature_counts,
+ *    garlic_feature_counts_info (likewise) */
 #define GARLIC_HIP_ABI_VERSION 8
 
 #define GARLIC_OK 0
@@ -734,6 +737,49 @@ typedef struct garlic_roh_segment {
 int garlic_roh_segments(garlic_panel *panel, int32_t winsize, double error, int32_t max_gap, int32_t use_gl, int32_t weighted,
                         int32_t M, double mu, double cutoff, double overlap_frac, garlic_roh_segment *segments,
                         int64_t capacity, int64_t *n_segments);
+
+/* count_features_in_roh.pl (the reference's src/) on the device: for every individual, the homozygous genotypes of
+ * annotated alleles that fall inside ROH of each size class and outside any ROH (csrc/feature_kernels.hpp; the file
+ * readers, the interval builder and the table writer: host/feature_counts.hpp).
+ *
+ * A feature set holds `nrows` hom rows over `nind` individuals: one row per annotated (site, allele) that occurs in the
+ * counting genotypes, bit i set when individual i is homozygous for that allele (a missing genotype and a heterozygote
+ * set nothing).  Destroy the sets before their context.
+ * garlic_feature_set_rows: host bit rows, `row_bytes` apart, bit i & 7 of byte i >> 3 is individual i (LSB first, as
+ * garlic_panel_set_phase_bits), uploaded in slabs; bits past nind are ignored.  Rows never set hold no homozygote.  The
+ * caller's rows are free on return.
+ * garlic_feature_set_sites: per row the chromosome (any id >= 0 the caller also uses in the intervals), the physical
+ * position and the effect id in [0, GARLIC_FEATURE_MAX_EFFECTS).  GARLIC_ERR_INVALID for rows that are not sorted by
+ * (chromosome, position); two rows may share a position (two alleles of one site, with different effects).
+ * garlic_feature_counts: counts[ind][cls][effect], int64, n_classes + 1 classes of n_effects each: the rows whose bit
+ * `ind` is set, by the class of the interval of `ind` that holds the row's position and by the row's effect; class
+ * n_classes is NONE, the rows inside no interval.  A position p is inside an interval iff chr is the row's and
+ *     start <= p < stop
+ * where stop is the `end` column of a .roh.bed line: GARLIC's writer puts the LAST SNP's position there and the script
+ * tests p <= end - 1, so a variant exactly at a segment's last SNP counts as outside.  That is reproduced, not mended.
+ * An interval with start == stop holds nothing.  The intervals are a host array in the order garlic_roh_segments returns
+ * segments in -- individual, chromosome, start -- and must not overlap within an individual (start >= the previous
+ * stop); GARLIC_ERR_INVALID names the first interval that is out of order, overlaps, has cls outside [0, n_classes) or
+ * ind outside [0, nind).  1 <= n_classes <= GARLIC_GMM_MAX_K; 1 <= n_effects <= GARLIC_FEATURE_MAX_EFFECTS and above
+ * every row's effect, else GARLIC_ERR_INVALID; a launch counts 32 effects, more are further launches over the same rows.
+ * counts are overwritten, not accumulated: `where` = GARLIC_HOST copies them out and returns when they are there;
+ * GARLIC_DEVICE: counts is device memory, the call enqueues on the context's stream and returns (the list of intervals
+ * is copied before it returns).  Integer sums: the same bytes from run to run.
+ * garlic_feature_counts_info: of the last garlic_feature_counts: the 64-individual blocks, the chunks of rows per block
+ * (ceil(nrows / 4096): one wavefront per block and chunk), the 64-bit words that were zero and skipped, the HIP-event
+ * time of the kernels.  The last two wait for that call's kernels.  Any pointer but the set may be NULL. */
+#define GARLIC_FEATURE_MAX_EFFECTS 256
+typedef struct garlic_feature_set garlic_feature_set;
+typedef struct garlic_roh_interval {
+    int32_t ind, chr, start, stop, cls;
+} garlic_roh_interval;
+int garlic_feature_set_create(garlic_ctx *ctx, int64_t nrows, int32_t nind, garlic_feature_set **set);
+int garlic_feature_set_destroy(garlic_feature_set *set);
+int garlic_feature_set_rows(garlic_feature_set *set, const uint8_t *bits, int64_t row_bytes, int64_t row_begin, int64_t row_count);
+int garlic_feature_set_sites(garlic_feature_set *set, const int32_t *chr, const int32_t *pos, const int32_t *effect);
+int garlic_feature_counts(garlic_feature_set *set, const garlic_roh_interval *intervals, int64_t n_intervals, int32_t n_classes,
+                          int32_t n_effects, int64_t *counts, int32_t where);
+int garlic_feature_counts_info(garlic_feature_set *set, int64_t *blocks, int64_t *chunks, int64_t *words_skipped, float *kernel_ms);
 
 /* Introspection used by tests and the bench (device work of the last garlic_*_windows call). */
 typedef struct garlic_call_stats {

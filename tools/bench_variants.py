@@ -27,6 +27,9 @@ garlic_lod_feed_subset call it replaces, at the --kde-inds and the everyone scal
 profiles/feed_kde_ab.txt).
 --modes feed_kde_parts: the KDE of a panel sharded over two panels on the one device: the present path (sorted feeds to the
 host, merged, uploaded, garlic_feed_kde) beside garlic_lod_kde_part + garlic_kde_parts (profiles/kde_parts_ab.txt).
+--modes feature_counts: garlic_feature_counts at --snps hom rows x --inds individuals (the issue's shapes: 1000000 x 1250 and x
+10000), 3 classes, 3 effects, hom-bit density 1e-3, 40 ROH per individual: the kernels by HIP events, the whole host-output
+call, the bytes of row words and row fields one pass reads (profiles/feature_counts_ab.txt).
 --modes feed_sort: the sorted KDE feed (garlic_panel_set_feed_order / garlic_feed_sort) on real thinned feeds of one
 resident panel: the unweighted feed (step = winsize) of --kde-inds individuals (the --kde-subsample scale) and of
 everyone -- the device sort alone by HIP events, its bytes per second at 24 B x keys x passes run, the whole feed call in
@@ -536,6 +539,79 @@ def feed_kde_parts_leg(args):
             panel.release_scratch()
 
 
+def feature_counts_leg(args):
+    """One JSON line.  The hom bits are drawn sparse (density x rows x individuals set bits at random places) and uploaded in
+    slabs of rows; intervals: 40 per individual over 22 chromosomes, classes at random.  The count is checked against numpy on
+    the first 64 individuals.  Host clock around the host-output call, warm-up call dropped; kernel_ms from the library."""
+    import time
+    from garlic_amd import abi
+
+    nrows, nind, n_classes, n_effects, density, per_ind = args.snps, args.inds, 3, 3, 1e-3, 40
+    rng = np.random.default_rng(20260301)
+    chr_ = np.sort(rng.integers(0, 22, nrows)).astype(np.int32)
+    pos = np.zeros(nrows, dtype=np.int32)
+    for c in range(22):
+        m = chr_ == c
+        pos[m] = np.sort(rng.integers(1, 250000000, int(m.sum())))
+    effect = rng.integers(0, n_effects, nrows).astype(np.int32)
+    iv = np.zeros(nind * per_ind, dtype=abi.ROH_INTERVAL)
+    iv["ind"] = np.repeat(np.arange(nind), per_ind)
+    iv["chr"] = np.sort(rng.integers(0, 22, (nind, per_ind)), axis=1).reshape(-1)
+    iv["start"] = rng.integers(1, 240000000, nind * per_ind)
+    iv["stop"] = iv["start"] + rng.integers(100000, 5000000, nind * per_ind)
+    iv["cls"] = rng.integers(0, n_classes, nind * per_ind)
+    iv = iv[np.lexsort((iv["start"], iv["chr"], iv["ind"]))]
+    same = (iv["ind"][1:] == iv["ind"][:-1]) & (iv["chr"][1:] == iv["chr"][:-1])      # an interval ends where the next begins, at the latest
+    iv["stop"][:-1] = np.where(same, np.minimum(iv["stop"][:-1], iv["start"][1:]), iv["stop"][:-1])
+    iv = np.ascontiguousarray(iv)
+    row_bytes = (nind + 7) // 8
+    first64 = np.zeros((nrows, 8), dtype=np.uint8)
+    with abi.Context(0) as ctx, abi.FeatureSet(ctx, nrows, nind, chr=chr_, pos=pos, effect=effect) as fs:
+        slab = max(1, (256 << 20) // row_bytes)
+        for r0 in range(0, nrows, slab):
+            n = min(slab, nrows - r0)
+            bits = np.zeros((n, row_bytes), dtype=np.uint8)
+            k = rng.binomial(n * nind, density)
+            at_r, at_i = rng.integers(0, n, k), rng.integers(0, nind, k)
+            np.bitwise_or.at(bits, (at_r, at_i >> 3), (1 << (at_i & 7)).astype(np.uint8))
+            first64[r0:r0 + n, :min(8, row_bytes)] = bits[:, :8]
+            fs.set_rows(bits, r0)
+        wall, kern = [], []
+        for k in range(1 + args.steps):
+            t0 = time.perf_counter()
+            counts = fs.counts(iv, n_classes, n_effects)
+            dt = time.perf_counter() - t0
+            info = fs.info()
+            if k:
+                wall.append(dt * 1e3)
+                kern.append(info["kernel_ms"])
+    # numpy on the first 64 individuals
+    m = min(64, nind)
+    hom = np.unpackbits(first64, axis=1, bitorder="little")[:, :m].astype(bool)
+    key = chr_.astype(np.int64) * (1 << 32) + pos
+    for i in range(m):
+        rows = np.nonzero(hom[:, i])[0]
+        mine = iv[iv["ind"] == i]
+        starts = mine["chr"].astype(np.int64) * (1 << 32) + mine["start"]
+        stops = mine["chr"].astype(np.int64) * (1 << 32) + mine["stop"]
+        at = np.searchsorted(starts, key[rows], side="right") - 1
+        inside = (at >= 0) & (key[rows] < stops[np.maximum(at, 0)])
+        cls = np.where(inside, mine["cls"][np.maximum(at, 0)], n_classes)
+        want = np.zeros((n_classes + 1, n_effects), dtype=np.int64)
+        np.add.at(want, (cls, effect[rows]), 1)
+        assert np.array_equal(counts[i], want), ("individual", i)
+    nblk = (nind + 63) // 64
+    words = nblk * nrows
+    print(json.dumps({"mode": "feature_counts", "rows": nrows, "inds": nind, "classes": n_classes, "effects": n_effects, "density": density,
+                      "intervals": int(iv.shape[0]), "blocks": info["blocks"], "chunks": info["chunks"], "words": words,
+                      "words_skipped": info["words_skipped"], "row_word_bytes": 8 * words,
+                      "row_field_bytes_at_most": 12 * (words - info["words_skipped"]),
+                      "kernel_ms_median": float(np.median(kern)), "kernel_ms_min": float(min(kern)),
+                      "call_ms_median": float(np.median(wall)), "call_ms_min": float(min(wall)),
+                      "row_words_GBps_at_median": 8 * words / (float(np.median(kern)) * 1e6) if np.median(kern) > 0 else None,
+                      "counted": int(counts.sum()), "repeats": args.steps}), flush=True)
+
+
 def tgls_slabs_leg(args):
     """Host clock around the synchronous calls (the term pass, where there is one, is part of the call).  One panel; legs in
     this order so that the code table (host work of the first use_gl call) is built before anything is timed as a first
@@ -854,6 +930,8 @@ def main():
         return feed_sort_leg(args)
     if args.modes == "feed_kde":
         return feed_kde_leg(args)
+    if args.modes == "feature_counts":
+        return feature_counts_leg(args)
     if args.modes == "feed_kde_parts":
         return feed_kde_parts_leg(args)
     if args.modes == "bed_ingest":
