@@ -51,6 +51,7 @@ SYMBOLS = [
     "garlic_kde_part_moment", "garlic_kde_part_rank", "garlic_kde_part_sums", "garlic_kde_parts", "garlic_kde_parts_info",
     "garlic_feature_set_create", "garlic_feature_set_destroy", "garlic_feature_set_rows", "garlic_feature_set_sites",
     "garlic_feature_counts", "garlic_feature_counts_info",
+    "garlic_feed_kde_multi", "garlic_lod_kde_multi", "garlic_feed_kde_multi_info",
 ]
 FEATURE_MAX_EFFECTS = 256   # GARLIC_FEATURE_MAX_EFFECTS
 FEATURE_GROUP_EFFECTS = 32  # effects per launch
@@ -58,6 +59,7 @@ FEATURE_CHUNK_ROWS = 4096   # rows per wavefront
 ROH_INTERVAL = np.dtype([("ind", "<i4"), ("chr", "<i4"), ("start", "<i4"), ("stop", "<i4"), ("cls", "<i4")])   # garlic_roh_interval
 KDE_POINTS = 512   # GARLIC_KDE_POINTS
 KDE_MAX_PARTS = 64   # GARLIC_KDE_MAX_PARTS
+KDE_MAX_FEEDS = 32   # GARLIC_KDE_MAX_FEEDS
 KDE_RANK_MAX = 1024  # probe keys of one garlic_kde_part_rank
 GMM_MAX_K = 8      # GARLIC_GMM_MAX_K
 
@@ -192,6 +194,11 @@ def lib():
                                  _i32p, C.c_int32, C.POINTER(Kde), _i64p]
     L.garlic_feed_kde_info.argtypes = [_vp, _i64p, _i64p, _i64p]
     L.garlic_feed_kde_times.argtypes = [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.garlic_feed_kde_multi.argtypes = [_vp, C.POINTER(_vp), _i64p, C.c_int32, C.c_int32, C.POINTER(Kde), _i32p]
+    L.garlic_lod_kde_multi.argtypes = [_vp, _i32p, _i32p, C.c_int32, C.c_double, C.c_int32, C.c_int32, _i32p, C.c_int32,
+                                       C.POINTER(Kde), _i32p, _i64p]
+    L.garlic_feed_kde_multi_info.argtypes = [_vp, C.c_int32, _i64p, _i64p, _i32p, _i32p, _i64p, C.POINTER(C.c_float),
+                                             C.POINTER(C.c_float)]
     L.garlic_kde_part_create.argtypes = [_vp, _vp, C.c_int64, C.c_int32, C.POINTER(_vp)]
     L.garlic_lod_kde_part.argtypes = [_vp, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32,
                                       _i32p, C.c_int32, C.POINTER(_vp), _i64p]
@@ -315,6 +322,36 @@ class Context:
         check(lib().garlic_feed_kde_times(self.handle, C.byref(a), C.byref(b)))
         return {"moments_ms": a.value, "sums_ms": b.value}
 
+    def feed_kde_multi(self, feeds, ns=None, strict=False, outs=None):
+        """garlic_feed_kde_multi: the KDEs of up to KDE_MAX_FEEDS ascending feeds from one set of launches.  feeds: a list
+        of contiguous float64 numpy arrays (host; ns defaults to their lengths), or of device addresses (int) with ns their
+        lengths.  Returns ([feed_kde's dict, or None for a refused feed], [status per feed], None).  strict: no per-feed
+        status -- any refused feed raises.  outs: an (abi.Kde * len(feeds)) array to fill instead of a fresh one."""
+        m = len(feeds)
+        host = all(isinstance(f, np.ndarray) for f in feeds)
+        assert host or not any(isinstance(f, np.ndarray) for f in feeds), "host arrays or device addresses, not both"
+        if host:
+            for f in feeds:
+                assert f.dtype == np.float64 and f.flags["C_CONTIGUOUS"] and f.ndim == 1
+            ns = [f.shape[0] for f in feeds] if ns is None else [int(v) for v in ns]
+            ptrs = (_vp * max(m, 1))(*[f.ctypes.data for f in feeds])
+        else:
+            ptrs = (_vp * max(m, 1))(*[int(f) if f else None for f in feeds])
+        lens = np.ascontiguousarray(ns, dtype=np.int64)
+        assert lens.shape == (m,)
+        return _kde_multi_result(lambda ks, st: lib().garlic_feed_kde_multi(self.handle, ptrs, _ptr(lens, _i64p), m, HOST if host else DEVICE,
+                                                                           ks, st), m, strict, outs) + (None,)
+
+    def feed_kde_multi_info(self, n):
+        """garlic_feed_kde_multi_info for the first n feeds of the last multi-feed KDE on this context: {chunks [n],
+        pairs_skipped [n], kernel_launches, host_waits, scratch_bytes, moments_ms, sums_ms}"""
+        chunks, skipped = np.zeros(max(n, 1), dtype=np.int64), np.zeros(max(n, 1), dtype=np.int64)
+        launches, waits, nbytes, a, b = C.c_int32(), C.c_int32(), C.c_int64(), C.c_float(), C.c_float()
+        check(lib().garlic_feed_kde_multi_info(self.handle, n, _ptr(chunks, _i64p), _ptr(skipped, _i64p), C.byref(launches), C.byref(waits),
+                                               C.byref(nbytes), C.byref(a), C.byref(b)))
+        return {"chunks": [int(v) for v in chunks[:n]], "pairs_skipped": [int(v) for v in skipped[:n]], "kernel_launches": launches.value,
+                "host_waits": waits.value, "scratch_bytes": nbytes.value, "moments_ms": a.value, "sums_ms": b.value}
+
     def kde_part(self, values, n=None):
         """garlic_kde_part_create: an ascending feed (garlic_feed_sort's key order) as one part of a split feed, an
         abi.KdePart.  values: a contiguous float64 numpy array (host, uploaded; n defaults to its length) or a device address
@@ -435,6 +472,15 @@ class FeatureSet:
 
     def __exit__(self, *exc):
         self.close()
+
+
+def _kde_multi_result(call, m, strict, outs):
+    """runs call(outs, status) of a multi-feed KDE; -> ([dict or None], [status])"""
+    ks = (Kde * max(m, 1))() if outs is None else outs
+    status = None if strict else np.full(max(m, 1), -1, dtype=np.int32)
+    check(call(ks, _ptr(status, _i32p)))
+    codes = [OK] * m if strict else [int(v) for v in status[:m]]
+    return [ks[i].as_dict() if codes[i] == OK else None for i in range(m)], codes
 
 
 class KdePart:
@@ -926,6 +972,20 @@ class Panel:
         check(lib().garlic_lod_kde(self.handle, winsize, error, max_gap, int(use_gl), int(weighted), M, mu, step,
                                    _ptr(idx, _i32p), 0 if idx is None else int(idx.shape[0]), C.byref(k), _ptr(per_chr, _i64p)))
         return k.as_dict(), per_chr
+
+    def lod_kde_multi(self, winsizes, error, max_gap, steps=None, use_gl=False, ind_idx=None, strict=False, outs=None):
+        """garlic_lod_kde_multi: the KDEs of several window sizes' feeds in one call (unweighted scores; steps default to the
+        window sizes).  Returns ([lod_kde's dict, or None for a refused size], [status per size], per-chromosome counts
+        [n_sizes, nchr]).  strict and outs as Context.feed_kde_multi."""
+        sizes = np.ascontiguousarray(winsizes, dtype=np.int32)
+        st = sizes.copy() if steps is None else np.ascontiguousarray(steps, dtype=np.int32)
+        idx = None if ind_idx is None else np.ascontiguousarray(ind_idx, dtype=np.int32)
+        m = int(sizes.shape[0])
+        per_chr = np.zeros((max(m, 1), self.nchr), dtype=np.int64)
+        got = _kde_multi_result(lambda ks, status: lib().garlic_lod_kde_multi(
+            self.handle, _ptr(sizes, _i32p), _ptr(st, _i32p), m, error, max_gap, int(use_gl), _ptr(idx, _i32p),
+            0 if idx is None else int(idx.shape[0]), ks, status, _ptr(per_chr, _i64p)), m, strict, outs)
+        return got + (per_chr[:m],)
 
     def lod_kde_part(self, winsize, error, max_gap, step, use_gl=False, weighted=False, M=7, mu=1e-9, ind_idx=None):
         """garlic_lod_kde_part: lod_kde's arguments; the sorted device feed becomes an abi.KdePart that borrows the panel's

@@ -22,6 +22,7 @@
 #include "wlod_feed_kernel.hpp"
 #include "feed_sort_kernel.hpp"
 #include "kde_kernels.hpp"
+#include "kde_multi_kernels.hpp"
 #include "gmm_kernels.hpp"
 #include "feature_kernels.hpp"
 #include "../host/kde_select.hpp"
@@ -156,6 +157,28 @@ struct KdeScratch {
     ~KdeScratch() { release(); }
 };
 
+// what garlic_feed_kde_multi keeps between calls (kde_multi_kernels.hpp): the feeds of a host-buffer call one after the
+// other, the per-chunk partials and flags and the per-slice sums of all feeds, the table of descriptors
+struct KdeMultiScratch {
+    DevBuf<double> stage, partial, slices;
+    DevBuf<int32_t> flags;
+    DevBuf<KdeFeedDesc> table;
+    hipEvent_t ev[4] = {};                         // around the moments kernels and around the sums kernels
+    size_t bytes() const
+    {
+        return (stage.cap + partial.cap + slices.cap) * sizeof(double) + flags.cap * sizeof(int32_t) + table.cap * sizeof(KdeFeedDesc);
+    }
+    void release()
+    {
+        stage.release(); partial.release(); slices.release(); flags.release(); table.release();
+        for (auto &e : ev) {
+            if (e) (void)hipEventDestroy(e);
+            e = nullptr;
+        }
+    }
+    ~KdeMultiScratch() { release(); }
+};
+
 // what garlic_gmm_fit keeps between calls (gmm_kernels.hpp): the blocks' partial sums, the state of the fit
 struct GmmScratch {
     DevBuf<double> stage;                          // the values of a host-buffer call
@@ -238,6 +261,11 @@ struct garlic_ctx {
     KdeScratch kde;
     int64_t kde_chunks = 0, kde_skipped = 0;
     float kde_moments_ms = 0.f, kde_sums_ms = 0.f;
+    // garlic_feed_kde_multi: its scratch, and what garlic_feed_kde_multi_info reports
+    KdeMultiScratch kdem;
+    std::vector<int64_t> kdem_chunks, kdem_skipped;
+    int32_t kdem_launches = 0, kdem_waits = 0;
+    float kdem_moments_ms = 0.f, kdem_sums_ms = 0.f;
     // garlic_gmm_fit: its scratch, and what garlic_gmm_fit_info reports
     GmmScratch gmm;
     int64_t gmm_blocks = 0;
@@ -435,8 +463,17 @@ struct garlic_panel {
     DevBuf<double> d_feed;
     int32_t feed_order = GARLIC_FEED_ORDER_REFERENCE;   // garlic_panel_set_feed_order
     FeedSortScratch fs;                            // ... SORTED: the sorter's scratch of the single-size feed calls
-    // garlic_lod_kde: set around its feed call -- the feed is sorted and stays on the device, where and how many is noted here
-    struct FeedSink { const double *data = nullptr; int64_t n = 0; } *feed_sink = nullptr;
+    // garlic_lod_kde, garlic_lod_kde_multi: set around their feed call -- every size's feed is sorted and stays on the device,
+    // where and how many is noted here, one entry per window size of the call.  A size that goes through feed_single leaves
+    // its feed in the panel's scratch (d_feed / fs), which the next size overwrites: `at` says which entry it is, and with
+    // to_slot the feed is moved into that size's FeedSlot buffer before feed_single returns.
+    struct FeedSink {
+        struct Entry { const double *data = nullptr; int64_t n = 0; };
+        std::vector<Entry> size;
+        int32_t at = 0;
+        bool to_slot = false;
+        explicit FeedSink(int32_t n_sizes = 1) : size((size_t)n_sizes) {}
+    } *feed_sink = nullptr;
     // garlic_lod_kde_part: a part borrows the feed from the scratch above.  Every call that may write that scratch (scores,
     // a feed, garlic_panel_release_scratch, the panel's end) moves the count on; a part whose count is behind is stale.
     std::shared_ptr<uint64_t> scratch_gen = std::make_shared<uint64_t>(0);
@@ -4160,7 +4197,7 @@ int garlic_panel_release_scratch(garlic_panel *p)
     p->lds.release();
     p->d_out.release(); p->d_feed.release();
     p->d_stage16.release(); p->d_stage64.release(); p->d_bed_word_rows.release();
-    p->fs.release(); p->ctx->fs.release(); p->ctx->kde.release(); p->ctx->gmm.release();
+    p->fs.release(); p->ctx->fs.release(); p->ctx->kde.release(); p->ctx->kdem.release(); p->ctx->gmm.release();
     for (auto *sl : p->feed_slots) {
         HIP_TRY(hipStreamSynchronize(sl->stream));
         sl->fs.release();
@@ -4405,8 +4442,14 @@ static int feed_single(garlic_panel *p, int32_t winsize, double error, int32_t m
         if ((rc = sort_result(p->ctx, p->ctx->stream, d_feed.p, p->fs, &from))) return rc;
     }
     if (p->feed_sink) {                            // garlic_lod_kde reads it where it lies
-        p->feed_sink->data = from;
-        p->feed_sink->n = *count;
+        garlic_panel::FeedSink &sink = *p->feed_sink;
+        if (sink.to_slot) {                        // one size of several: out of the panel's scratch before the next size runs
+            garlic_panel::FeedSlot &sl = *p->feed_slots[(size_t)sink.at];
+            if ((rc = sl.feed.reserve((size_t)*count))) return rc;
+            HIP_TRY(hipMemcpyAsync(sl.feed.p, from, sizeof(double) * (size_t)*count, hipMemcpyDeviceToDevice, p->ctx->stream));
+            from = sl.feed.p;
+        }
+        sink.size[(size_t)sink.at] = garlic_panel::FeedSink::Entry{from, *count};
         return GARLIC_OK;
     }
     hipError_t e = hipMemcpy(feed, from, sizeof(double) * (size_t)*count, hipMemcpyDeviceToHost);
@@ -4492,10 +4535,12 @@ int garlic_lod_feed_multi(garlic_panel *p, const int32_t *winsizes, const int32_
         for (int i = 0; i < n_sizes && direct; i++) direct = !lod_exact_needed(p, MODE_LOD, winsizes[i]);
     }
     if (!direct) {
-        for (int i = 0; i < n_sizes; i++)
+        for (int i = 0; i < n_sizes; i++) {
+            if (p->feed_sink) p->feed_sink->at = i;
             if ((rc = feed_single(p, winsizes[i], error, max_gap, 0, 0, 0, 0.0, steps[i], ind_idx, n_idx, feeds[i],
                                   feed_capacity[i], &counts[i], chr_counts ? chr_counts + (size_t)i * p->nchr : nullptr)))
                 return rc;
+        }
         return GARLIC_OK;
     }
     p->last_feed_form = GARLIC_FEED_CHAIN;      // the samples go straight into the feeds: no score matrix of any kind
@@ -4607,9 +4652,8 @@ int garlic_lod_feed_multi(garlic_panel *p, const int32_t *winsizes, const int32_
         if (!n_items[(size_t)i]) continue;
         const double *from = sl.feed.p;
         if (sorted && total[(size_t)i] > 1 && (rc = sort_result(ctx, sl.stream, sl.feed.p, sl.fs, &from))) return done(rc);
-        if (p->feed_sink) {                        // garlic_lod_kde (one size): the feed stays in the slot's buffer
-            p->feed_sink->data = from;
-            p->feed_sink->n = total[(size_t)i];
+        if (p->feed_sink) {                        // garlic_lod_kde, garlic_lod_kde_multi: the feed stays in the slot's buffers
+            p->feed_sink->size[(size_t)i] = garlic_panel::FeedSink::Entry{from, total[(size_t)i]};
             continue;
         }
         FEED_TRY(hipMemcpyAsync(feeds[i], from, sizeof(double) * (size_t)total[(size_t)i], hipMemcpyDeviceToHost, sl.stream));
@@ -4891,15 +4935,19 @@ int garlic_lod_feed_multi_tgls(garlic_panel *p, const int32_t *winsizes, const i
                 for (auto &c : rcnt) { const int64_t n = c; c = total; total += n; }
                 counts[i] = total;
                 if (total > feed_capacity[i] || total == 0) continue;
-                if (!feeds[i]) return done(fail(GARLIC_ERR_INVALID, "feed %d is NULL", i));
+                if (!feeds[i] && !p->feed_sink) return done(fail(GARLIC_ERR_INVALID, "feed %d is NULL", i));
                 if ((rc = sl.feed.reserve((size_t)total))) return done(rc);
                 FEED_TRY(hipMemcpyAsync(sl.row_counts.p, rcnt.data(), sizeof(int64_t) * n_flat, hipMemcpyHostToDevice, sl.stream));
                 hipLaunchKernelGGL(feed_write_kernel, dim3((unsigned)n_flat), dim3(WAVE), 0, sl.stream, sl.out.p,
                                    p->d_multi_chrs.p + (size_t)i * p->nchr, p->nchr, nrows, ind_idx ? d_list.p : nullptr, 1, sl.row_counts.p,
                                    sl.feed.p);
-                if (p->feed_order == GARLIC_FEED_ORDER_SORTED && total > 1) {      // fetched below, once every size's sort is enqueued
+                if ((p->feed_order == GARLIC_FEED_ORDER_SORTED || p->feed_sink) && total > 1) {      // fetched below, once every size's sort is enqueued
                     if ((rc = sort_feed(ctx, sl.stream, sl.feed.p, total, sl.fs, false))) return done(rc);
                     sort_n[(size_t)i] = total;
+                    continue;
+                }
+                if (p->feed_sink) {                    // garlic_lod_kde_multi: (one value) stays in the slot's buffer
+                    p->feed_sink->size[(size_t)i] = garlic_panel::FeedSink::Entry{sl.feed.p, total};
                     continue;
                 }
                 FEED_TRY(hipMemcpyAsync(feeds[i], sl.feed.p, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, sl.stream));
@@ -4910,6 +4958,10 @@ int garlic_lod_feed_multi_tgls(garlic_panel *p, const int32_t *winsizes, const i
                 garlic_panel::FeedSlot &sl = *p->feed_slots[(size_t)i];
                 const double *from = sl.feed.p;
                 if ((rc = sort_result(ctx, sl.stream, sl.feed.p, sl.fs, &from))) return done(rc);
+                if (p->feed_sink) {                    // garlic_lod_kde_multi: stays in the slot's buffers
+                    p->feed_sink->size[(size_t)i] = garlic_panel::FeedSink::Entry{from, sort_n[(size_t)i]};
+                    continue;
+                }
                 FEED_TRY(hipMemcpyAsync(feeds[i], from, sizeof(double) * (size_t)sort_n[(size_t)i], hipMemcpyDeviceToHost, sl.stream));
             }
         for (const Group &g : G)
@@ -4931,6 +4983,7 @@ int garlic_lod_feed_multi_tgls(garlic_panel *p, const int32_t *winsizes, const i
         std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return group[(size_t)x] < group[(size_t)y]; });
         for (int i : order) {
             if (ring_ok[(size_t)i]) continue;
+            if (p->feed_sink) p->feed_sink->at = i;
             if ((rc = feed_single(p, winsizes[i], 0.0, max_gap, 1, 0, 0, 0.0, steps[i], ind_idx, n_idx, feeds[i], feed_capacity[i],
                                   &counts[i], chr_counts ? chr_counts + (size_t)i * p->nchr : nullptr)))
                 return rc;
@@ -5663,6 +5716,42 @@ static int kde_reserve(garlic_ctx *ctx, int64_t n, bool stage)
     return GARLIC_OK;
 }
 
+// where the six order statistics of n values lie, and the weights of the two quartile mixes
+static void kde_stat_index(int64_t n, KdeIdx &idx, double &delta25, double &delta75)
+{
+    namespace gh = garlic_host;
+    idx.at[0] = 0;
+    idx.at[1] = n - 1;
+    gh::kdeQuantileIndex(n, 0.25, &idx.at[2], &delta25);
+    gh::kdeQuantileIndex(n, 0.75, &idx.at[4], &delta75);
+    idx.at[3] = idx.at[2] + 1;
+    idx.at[5] = idx.at[4] + 1;
+}
+
+// what the moments say of a feed: refused (the cause in the error text), or n, lo, hi, sd, the quartiles, h and the targets
+// in r, with 1 / h^2 for the sums (garlic_feed_kde and garlic_feed_kde_multi run these lines)
+static int kde_from_moments(const KdeMoments &mom, int64_t n, const KdeIdx &idx, double delta25, double delta75, garlic_kde &r,
+                            double &inv_h2)
+{
+    namespace gh = garlic_host;
+    if (mom.flags & KDE_FLAG_NOT_FINITE) return fail(GARLIC_ERR_INVALID, "feed KDE: the values hold a NaN or an infinity");
+    if (mom.flags & KDE_FLAG_NOT_ASCENDING) return fail(GARLIC_ERR_INVALID, "feed KDE: the values are not in ascending order (garlic_feed_sort)");
+    r.n = n;
+    r.lo = mom.stat[0];
+    r.hi = mom.stat[1];
+    r.sd = sqrt(mom.ssq / (double)(n - 1));
+    r.q25 = idx.at[2] >= n - 1 ? mom.stat[2] : gh::kdeQuantileMix(mom.stat[2], mom.stat[3], delta25);
+    r.q75 = idx.at[4] >= n - 1 ? mom.stat[4] : gh::kdeQuantileMix(mom.stat[4], mom.stat[5], delta75);
+    r.h = gh::kdeBandwidth(r.sd, r.q25, r.q75, n);
+    if (!(r.h > 0) || !std::isfinite(r.h))
+        return fail(GARLIC_ERR_INVALID, "feed KDE: bandwidth %g (sd %g, quartiles %g and %g): all values equal, or no spread between the quartiles",
+                    r.h, r.sd, r.q25, r.q75);
+    gh::kdeTargets(r.lo, r.hi, r.h, r.x);
+    inv_h2 = 1.0 / (r.h * r.h);
+    if (!std::isfinite(inv_h2)) return fail(GARLIC_ERR_INVALID, "feed KDE: bandwidth %g is too small to square", r.h);
+    return GARLIC_OK;
+}
+
 static int kde_device(garlic_ctx *ctx, const double *d_x, int64_t n, garlic_kde *out)
 {
     namespace gh = garlic_host;
@@ -5675,12 +5764,7 @@ static int kde_device(garlic_ctx *ctx, const double *d_x, int64_t n, garlic_kde 
     const int64_t cps = kde_chunks_per_slice(n_chunks), n_slices = (n_chunks + cps - 1) / cps;
     KdeIdx idx;
     double delta25, delta75;
-    idx.at[0] = 0;
-    idx.at[1] = n - 1;
-    gh::kdeQuantileIndex(n, 0.25, &idx.at[2], &delta25);
-    gh::kdeQuantileIndex(n, 0.75, &idx.at[4], &delta75);
-    idx.at[3] = idx.at[2] + 1;
-    idx.at[5] = idx.at[4] + 1;
+    kde_stat_index(n, idx, delta25, delta75);
     HIP_TRY(hipEventRecord(k.ev[0], s));
     for (int pass = 0; pass < 2; pass++) {
         hipLaunchKernelGGL(kde_moment_kernel, dim3((unsigned)n_chunks), dim3(KDE_THREADS), 0, s, d_x, n, pass, k.mom.p, k.partial.p, k.flags.p);
@@ -5691,22 +5775,9 @@ static int kde_device(garlic_ctx *ctx, const double *d_x, int64_t n, garlic_kde 
     KdeMoments mom;
     HIP_TRY(hipMemcpyAsync(&mom, k.mom.p, sizeof mom, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    if (mom.flags & KDE_FLAG_NOT_FINITE) return fail(GARLIC_ERR_INVALID, "feed KDE: the values hold a NaN or an infinity");
-    if (mom.flags & KDE_FLAG_NOT_ASCENDING) return fail(GARLIC_ERR_INVALID, "feed KDE: the values are not in ascending order (garlic_feed_sort)");
     garlic_kde r;
-    r.n = n;
-    r.lo = mom.stat[0];
-    r.hi = mom.stat[1];
-    r.sd = sqrt(mom.ssq / (double)(n - 1));
-    r.q25 = idx.at[2] >= n - 1 ? mom.stat[2] : gh::kdeQuantileMix(mom.stat[2], mom.stat[3], delta25);
-    r.q75 = idx.at[4] >= n - 1 ? mom.stat[4] : gh::kdeQuantileMix(mom.stat[4], mom.stat[5], delta75);
-    r.h = gh::kdeBandwidth(r.sd, r.q25, r.q75, n);
-    if (!(r.h > 0) || !std::isfinite(r.h))
-        return fail(GARLIC_ERR_INVALID, "feed KDE: bandwidth %g (sd %g, quartiles %g and %g): all values equal, or no spread between the quartiles",
-                    r.h, r.sd, r.q25, r.q75);
-    gh::kdeTargets(r.lo, r.hi, r.h, r.x);
-    const double inv_h2 = 1.0 / (r.h * r.h);
-    if (!std::isfinite(inv_h2)) return fail(GARLIC_ERR_INVALID, "feed KDE: bandwidth %g is too small to square", r.h);
+    double inv_h2;
+    if ((rc = kde_from_moments(mom, n, idx, delta25, delta75, r, inv_h2))) return rc;
     HIP_TRY(hipMemcpyAsync(k.targets.p, r.x, sizeof r.x, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemsetAsync(k.skipped.p, 0, sizeof(unsigned long long), s));
     HIP_TRY(hipEventRecord(k.ev[2], s));
@@ -5770,8 +5841,215 @@ int garlic_lod_kde(garlic_panel *p, int32_t winsize, double error, int32_t max_g
                                           INT64_MAX, &count, chr_counts);
     p->feed_sink = nullptr;
     if (rc) return rc;
-    if (count < 2 || sink.n != count) return fail(GARLIC_ERR_INVALID, "feed KDE: needs at least 2 values (the feed holds %lld)", (long long)count);
-    return kde_device(p->ctx, sink.data, sink.n, out);
+    if (count < 2 || sink.size[0].n != count) return fail(GARLIC_ERR_INVALID, "feed KDE: needs at least 2 values (the feed holds %lld)", (long long)count);
+    return kde_device(p->ctx, sink.size[0].data, sink.size[0].n, out);
+}
+
+// ---- The KDE of several feeds in one set of launches (kde_multi_kernels.hpp; the plan: host/kde_multi_plan.hpp).
+// d_x[i]: n[i] device doubles, ascending (anything, NULL included, where n[i] < 2).  Six launches and two waits on the
+// context's stream whatever n_feeds is; four and one when no feed is left after the moments.  few_fmt: the wording of
+// the "at least 2 values" refusal of the caller (one %lld).  status NULL: any refused feed fails the call.  Nothing of
+// outs or status is written before everything has succeeded.
+static int kde_multi_device(garlic_ctx *ctx, const double *const *d_x, const int64_t *n, int32_t n_feeds, const char *few_fmt,
+                            garlic_kde *outs, int32_t *status)
+{
+    namespace gh = garlic_host;
+    static_assert(GARLIC_KDE_MAX_FEEDS == gh::KDE_MULTI_MAX_FEEDS, "one limit");
+    gh::KdeMultiPlan plan;
+    if (!gh::kdeMultiPlan(n, n_feeds, &plan))
+        return fail(GARLIC_ERR_INVALID, "feed KDE: the %d feeds are more chunks than one launch holds", (int)n_feeds);
+    KdeMultiScratch &k = ctx->kdem;
+    hipStream_t s = ctx->stream;
+    int rc;
+    if ((rc = k.partial.reserve((size_t)std::max<int64_t>(plan.total_chunks, 1))) ||
+        (rc = k.flags.reserve((size_t)std::max<int64_t>(plan.total_chunks, 1))) ||
+        (rc = k.slices.reserve((size_t)std::max<int64_t>(plan.total_slices, 1) * KDE_POINTS)) ||
+        (rc = k.table.reserve(GARLIC_KDE_MAX_FEEDS)))
+        return rc;
+    for (auto &e : k.ev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    // per feed: the code and the words of its refusal (garlic_feed_kde's), what the moments gave
+    std::vector<int32_t> code((size_t)n_feeds, GARLIC_OK);
+    std::vector<std::string> why((size_t)n_feeds);
+    std::vector<garlic_kde> res((size_t)n_feeds);
+    std::vector<KdeFeedDesc> table((size_t)n_feeds);
+    std::vector<double> delta25((size_t)n_feeds, 0.0), delta75((size_t)n_feeds, 0.0);
+    auto refuse = [&](int i, int c) { code[(size_t)i] = c; why[(size_t)i] = g_last_error; };
+    memset(table.data(), 0, sizeof(KdeFeedDesc) * table.size());
+    for (int i = 0; i < n_feeds; i++) {
+        const gh::KdeMultiFeedPlan &f = plan.feed[i];
+        KdeFeedDesc &d = table[(size_t)i];
+        if (n[i] < 2) { refuse(i, fail(GARLIC_ERR_INVALID, few_fmt, (long long)n[i])); continue; }
+        d.x = d_x[i];
+        d.n = f.n;
+        d.n_chunks = f.n_chunks;
+        d.chunks_per_slice = f.chunks_per_slice;
+        d.n_slices = f.n_slices;
+        d.chunk_off = plan.chunk_first.at[i];
+        d.slice_off = plan.slice_first.at[i];
+        kde_stat_index(f.n, d.idx, delta25[(size_t)i], delta75[(size_t)i]);
+    }
+    auto first_refused = [&]() {
+        for (int i = 0; i < n_feeds; i++)
+            if (code[(size_t)i]) return i;
+        return -1;
+    };
+    // the refusal of the lowest index as the call's error text; strict: as the call's code too
+    auto report = [&]() {
+        const int i = first_refused();
+        return i < 0 ? (int)GARLIC_OK : fail(code[(size_t)i], "feed %d: %s", i, why[(size_t)i].c_str());
+    };
+    int32_t launches = 0, waits = 0;
+    const size_t table_bytes = sizeof(KdeFeedDesc) * (size_t)n_feeds;
+    if (plan.total_chunks > 0 && !(status == nullptr && first_refused() >= 0)) {
+        HIP_TRY(hipMemcpyAsync(k.table.p, table.data(), table_bytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipEventRecord(k.ev[0], s));
+        for (int pass = 0; pass < 2; pass++) {
+            hipLaunchKernelGGL(kde_moment_multi_kernel, dim3((unsigned)plan.total_chunks), dim3(KDE_THREADS), 0, s, k.table.p, (int)n_feeds,
+                               plan.chunk_first, pass, k.partial.p, k.flags.p);
+            hipLaunchKernelGGL(kde_tree_multi_kernel, dim3((unsigned)n_feeds), dim3(KDE_THREADS), 0, s, k.table.p, pass, k.partial.p, k.flags.p);
+            launches += 2;
+        }
+        HIP_TRY(hipEventRecord(k.ev[1], s));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(table.data(), k.table.p, table_bytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        waits++;
+    }
+    // every h and every target set, then one upload
+    int n_active = 0;
+    for (int i = 0; i < n_feeds && waits; i++) {
+        KdeFeedDesc &d = table[(size_t)i];
+        if (code[(size_t)i]) continue;
+        if ((rc = kde_from_moments(d.mom, d.n, d.idx, delta25[(size_t)i], delta75[(size_t)i], res[(size_t)i], d.inv_h2))) {
+            refuse(i, rc);
+            continue;
+        }
+        memcpy(d.targets, res[(size_t)i].x, sizeof d.targets);
+        d.skipped = 0;
+        d.active = 1;
+        n_active++;
+    }
+    if (status == nullptr && (rc = report())) return rc;
+    if (n_active) {
+        HIP_TRY(hipMemcpyAsync(k.table.p, table.data(), table_bytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipEventRecord(k.ev[2], s));
+        hipLaunchKernelGGL(kde_sum_multi_kernel, dim3((unsigned)plan.total_slices), dim3(KDE_THREADS), 0, s, k.table.p, (int)n_feeds,
+                           plan.slice_first, k.slices.p);
+        hipLaunchKernelGGL(kde_slice_multi_kernel, dim3((unsigned)n_feeds * KDE_POINTS), dim3(KDE_THREADS), 0, s, k.table.p, k.slices.p);
+        launches += 2;
+        HIP_TRY(hipEventRecord(k.ev[3], s));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(table.data(), k.table.p, table_bytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        waits++;
+    }
+    ctx->kdem_chunks.assign((size_t)n_feeds, 0);
+    ctx->kdem_skipped.assign((size_t)n_feeds, 0);
+    for (int i = 0; i < n_feeds; i++) {
+        const KdeFeedDesc &d = table[(size_t)i];
+        ctx->kdem_chunks[(size_t)i] = d.n_chunks;
+        if (status) status[i] = code[(size_t)i];
+        if (code[(size_t)i]) continue;
+        garlic_kde &r = res[(size_t)i];
+        memcpy(r.raw, d.raw, sizeof r.raw);
+        gh::kdeNormalise(r.raw, r.x, r.y);
+        ctx->kdem_skipped[(size_t)i] = (int64_t)d.skipped;
+        outs[i] = r;
+    }
+    ctx->kdem_launches = launches;
+    ctx->kdem_waits = waits;
+    ctx->kdem_moments_ms = ctx->kdem_sums_ms = 0.f;
+    if (waits && hipEventElapsedTime(&ctx->kdem_moments_ms, k.ev[0], k.ev[1]) != hipSuccess) ctx->kdem_moments_ms = 0.f;
+    if (n_active && hipEventElapsedTime(&ctx->kdem_sums_ms, k.ev[2], k.ev[3]) != hipSuccess) ctx->kdem_sums_ms = 0.f;
+    (void)report();                        // (status given: the call ran; the text names the lowest refused feed)
+    return GARLIC_OK;
+}
+
+int garlic_feed_kde_multi(garlic_ctx *ctx, const double *const *sorted, const int64_t *n, int32_t n_feeds, int32_t where,
+                          garlic_kde *outs, int32_t *status)
+{
+    if (!ctx || !sorted || !n || !outs) return fail(GARLIC_ERR_INVALID, "feed KDE: context, feeds, lengths and outs are required");
+    if (n_feeds < 1 || n_feeds > GARLIC_KDE_MAX_FEEDS)
+        return fail(GARLIC_ERR_INVALID, "feed KDE: %d feeds (1 to %d)", (int)n_feeds, GARLIC_KDE_MAX_FEEDS);
+    if (where != GARLIC_HOST && where != GARLIC_DEVICE) return fail(GARLIC_ERR_INVALID, "feed KDE: where must be GARLIC_HOST or GARLIC_DEVICE");
+    for (int i = 0; i < n_feeds; i++)
+        if (n[i] > 0 && !sorted[i]) return fail(GARLIC_ERR_INVALID, "feed KDE: values of feed %d is NULL", i);
+    int rc;
+    if ((rc = set_device(ctx))) return rc;
+    const char *few = "feed KDE: needs at least 2 values (got %lld)";
+    if (where == GARLIC_DEVICE) return kde_multi_device(ctx, sorted, n, n_feeds, few, outs, status);
+    // host buffers: the feeds that can take part, one after the other in the context's scratch
+    const double *d_x[GARLIC_KDE_MAX_FEEDS] = {};
+    int64_t total = 0;
+    for (int i = 0; i < n_feeds; i++)
+        if (n[i] >= 2) {
+            if (n[i] > INT64_MAX / 16 - total) return fail(GARLIC_ERR_INVALID, "feed KDE: the %d feeds are more chunks than one launch holds", (int)n_feeds);
+            total += n[i];
+        }
+    if ((rc = ctx->kdem.stage.reserve((size_t)std::max<int64_t>(total, 1)))) return rc;
+    int64_t at = 0;
+    for (int i = 0; i < n_feeds; i++) {
+        if (n[i] < 2) continue;
+        HIP_TRY(hipMemcpyAsync(ctx->kdem.stage.p + at, sorted[i], sizeof(double) * (size_t)n[i], hipMemcpyHostToDevice, ctx->stream));
+        d_x[i] = ctx->kdem.stage.p + at;
+        at += n[i];
+    }
+    return kde_multi_device(ctx, d_x, n, n_feeds, few, outs, status);
+}
+
+int garlic_feed_kde_multi_info(garlic_ctx *ctx, int32_t n, int64_t *chunks, int64_t *pairs_skipped, int32_t *kernel_launches,
+                               int32_t *host_waits, int64_t *scratch_bytes, float *moments_ms, float *sums_ms)
+{
+    if (!ctx) return fail(GARLIC_ERR_INVALID, "context is NULL");
+    if (n < 0 || (size_t)n > ctx->kdem_chunks.size())
+        return fail(GARLIC_ERR_INVALID, "the last multi-feed KDE on the context had %d feeds (asked for %d)", (int)ctx->kdem_chunks.size(), (int)n);
+    for (int i = 0; i < n; i++) {
+        if (chunks) chunks[i] = ctx->kdem_chunks[(size_t)i];
+        if (pairs_skipped) pairs_skipped[i] = ctx->kdem_skipped[(size_t)i];
+    }
+    if (kernel_launches) *kernel_launches = ctx->kdem_launches;
+    if (host_waits) *host_waits = ctx->kdem_waits;
+    if (scratch_bytes) *scratch_bytes = (int64_t)ctx->kdem.bytes();
+    if (moments_ms) *moments_ms = ctx->kdem_moments_ms;
+    if (sums_ms) *sums_ms = ctx->kdem_sums_ms;
+    return GARLIC_OK;
+}
+
+int garlic_lod_kde_multi(garlic_panel *p, const int32_t *winsizes, const int32_t *steps, int32_t n_sizes, double error,
+                         int32_t max_gap, int32_t use_gl, const int32_t *ind_idx, int32_t n_idx, garlic_kde *outs, int32_t *status,
+                         int64_t *chr_counts)
+{
+    if (!p || !outs) return fail(GARLIC_ERR_INVALID, "panel and outs are required");
+    if (!winsizes || !steps) return fail(GARLIC_ERR_INVALID, "panel, winsizes, steps, feeds, feed_capacity and counts are required");
+    if (n_sizes < 1) return fail(GARLIC_ERR_INVALID, "n_sizes must be >= 1");
+    if (n_sizes > GARLIC_KDE_MAX_FEEDS) return fail(GARLIC_ERR_INVALID, "feed KDE: %d window sizes (1 to %d)", (int)n_sizes, GARLIC_KDE_MAX_FEEDS);
+    garlic_ctx *ctx = p->ctx;
+    int rc;
+    if ((rc = set_device(ctx)) || (rc = ensure_feed_slots(p, n_sizes))) return rc;
+    // the feed call sorts every size and leaves it in that size's slot; the order setting is not touched
+    garlic_panel::FeedSink sink(n_sizes);
+    sink.to_slot = true;
+    std::vector<double *> feeds((size_t)n_sizes, nullptr);
+    std::vector<int64_t> cap((size_t)n_sizes, INT64_MAX), counts((size_t)n_sizes, 0);
+    p->feed_sink = &sink;
+    rc = use_gl ? garlic_lod_feed_multi_tgls(p, winsizes, steps, n_sizes, max_gap, ind_idx, n_idx, feeds.data(), cap.data(), counts.data(), chr_counts)
+                : garlic_lod_feed_multi(p, winsizes, steps, n_sizes, error, max_gap, ind_idx, n_idx, feeds.data(), cap.data(), counts.data(),
+                                        chr_counts);
+    p->feed_sink = nullptr;
+    if (rc) return rc;
+    // the KDE on the context's stream, behind whatever the sizes' streams still hold
+    const double *d_x[GARLIC_KDE_MAX_FEEDS] = {};
+    int64_t n[GARLIC_KDE_MAX_FEEDS] = {};
+    for (int i = 0; i < n_sizes; i++) {
+        garlic_panel::FeedSlot &sl = *p->feed_slots[(size_t)i];
+        HIP_TRY(hipEventRecord(sl.ev1, sl.stream));
+        HIP_TRY(hipStreamWaitEvent(ctx->stream, sl.ev1, 0));
+        const bool held = counts[(size_t)i] >= 2 && sink.size[(size_t)i].n == counts[(size_t)i];
+        d_x[i] = held ? sink.size[(size_t)i].data : nullptr;
+        n[i] = held ? counts[(size_t)i] : std::min<int64_t>(counts[(size_t)i], 1);
+    }
+    return kde_multi_device(ctx, d_x, n, n_sizes, "feed KDE: needs at least 2 values (the feed holds %lld)", outs, status);
 }
 
 // ---- The KDE of a feed that is split into sorted parts (a sharded panel: one part per shard, on the shard's device).
@@ -5884,10 +6162,10 @@ int garlic_lod_kde_part(garlic_panel *p, int32_t winsize, double error, int32_t 
                                     INT64_MAX, &count, chr_counts);
     p->feed_sink = nullptr;
     if (rc) return rc;
-    if (count > 0 && sink.n != count) return fail(GARLIC_ERR_STATE, "KDE part: the feed of %lld values was not left on the device", (long long)count);
+    if (count > 0 && sink.size[0].n != count) return fail(GARLIC_ERR_STATE, "KDE part: the feed of %lld values was not left on the device", (long long)count);
     garlic_kde_part *part = nullptr;
     if ((rc = kde_part_new(p->ctx, count, &part))) return rc;
-    part->x = count > 0 ? sink.data : nullptr;
+    part->x = count > 0 ? sink.size[0].data : nullptr;
     part->gen = p->scratch_gen;
     part->gen_at = *p->scratch_gen;
     *out = part;

@@ -24,6 +24,8 @@
 //     target walks the chunk for the other alone; a wave whose 64 lanes skip both enters no loop.  The count of
 //     skipped pairs (integer adds) is what garlic_feed_kde_info reports.
 //   * 64-bit element indices and counts; a chunk count fits 32 bits (checked by the caller).
+//   * the bodies are __device__ functions of (feed, chunk / slice / target): the kernels here pass blockIdx.x, the batched
+//     kernels of kde_multi_kernels.hpp the place of the workgroup in its feed -- one source, one result.
 //   * a feed split into parts (garlic_kde_parts): kde_moment_about_kernel is pass 1 about the caller's mean,
 //     kde_slice_sum_kernel leaves a part's sums undivided, kde_rank_kernel counts the values below each of up to 1024
 //     probe keys.  The first two run the lines of their single-feed twins, so one part gives the single feed's bits.
@@ -66,14 +68,16 @@ __device__ __forceinline__ double kde_block_tree(double v, double *red)
     return red[0];
 }
 
-// one chunk's partial and flags: pass 0 the sum, pass 1 the sum of (x - mean)^2 (both moment kernels run these lines)
-__device__ __forceinline__ void kde_moment_chunk(const double *x, int64_t n, int pass, double mean, double *partial, int32_t *flags)
+// chunk `chunk`'s partial and flags: pass 0 the sum, pass 1 the sum of (x - mean)^2 (every moment kernel runs these lines,
+// the single-feed ones with blockIdx.x for the chunk, kde_multi_kernels.hpp with the chunk of the workgroup's feed)
+__device__ __forceinline__ void kde_moment_chunk(const double *x, int64_t n, int64_t chunk, int pass, double mean, double *partial,
+                                                 int32_t *flags)
 {
     __shared__ double red[KDE_THREADS];
     __shared__ int32_t flag;
     if (threadIdx.x == 0) flag = 0;
     __syncthreads();
-    const int64_t i0 = (int64_t)blockIdx.x * KDE_CHUNK;
+    const int64_t i0 = chunk * KDE_CHUNK;
     double acc = 0.0;
     int32_t f = 0;
     for (int j = 0; j < KDE_CHUNK / KDE_THREADS; j++) {
@@ -92,8 +96,8 @@ __device__ __forceinline__ void kde_moment_chunk(const double *x, int64_t n, int
     if (f) atomicOr(&flag, f);             // (LDS, integer)
     const double total = kde_block_tree(acc, red);
     if (threadIdx.x == 0) {
-        partial[blockIdx.x] = total;
-        flags[blockIdx.x] = flag;
+        partial[chunk] = total;
+        flags[chunk] = flag;
     }
 }
 
@@ -101,22 +105,22 @@ __device__ __forceinline__ void kde_moment_chunk(const double *x, int64_t n, int
 __global__ void __launch_bounds__(KDE_THREADS)
 kde_moment_kernel(const double *x, int64_t n, int pass, const KdeMoments *mom, double *partial, int32_t *flags)
 {
-    kde_moment_chunk(x, n, pass, pass ? mom->mean : 0.0, partial, flags);
+    kde_moment_chunk(x, n, blockIdx.x, pass, pass ? mom->mean : 0.0, partial, flags);
 }
 
 // pass 1 about the caller's mean (a part of a split feed: the mean of the union, garlic_kde_part_moment)
 __global__ void __launch_bounds__(KDE_THREADS)
 kde_moment_about_kernel(const double *x, int64_t n, double mean, double *partial, int32_t *flags)
 {
-    kde_moment_chunk(x, n, 1, mean, partial, flags);
+    kde_moment_chunk(x, n, blockIdx.x, 1, mean, partial, flags);
 }
 
 // one workgroup: the chunks' partials and flags; pass 0 -> sum and mean, pass 1 -> ssq and the order statistics at idx[6]
 struct KdeIdx { int64_t at[6]; };
 
-__global__ void __launch_bounds__(KDE_THREADS)
-kde_tree_kernel(const double *x, int64_t n, int64_t n_chunks, int pass, const double *partial, const int32_t *flags,
-                KdeIdx idx, KdeMoments *mom)
+// one feed's tree, by one workgroup (kde_tree_kernel; kde_tree_multi_kernel, one workgroup per feed)
+__device__ __forceinline__ void kde_tree_feed(const double *x, int64_t n, int64_t n_chunks, int pass, const double *partial,
+                                              const int32_t *flags, const KdeIdx &idx, KdeMoments *mom)
 {
     __shared__ double red[KDE_THREADS];
     __shared__ int32_t flag;
@@ -147,8 +151,16 @@ kde_tree_kernel(const double *x, int64_t n, int64_t n_chunks, int pass, const do
 }
 
 __global__ void __launch_bounds__(KDE_THREADS)
-kde_sum_kernel(const double *x, int64_t n, int64_t n_chunks, int64_t chunks_per_slice, const double *targets, double inv_h2,
-               double *partial, unsigned long long *skipped)
+kde_tree_kernel(const double *x, int64_t n, int64_t n_chunks, int pass, const double *partial, const int32_t *flags,
+                KdeIdx idx, KdeMoments *mom)
+{
+    kde_tree_feed(x, n, n_chunks, pass, partial, flags, idx, mom);
+}
+
+// slice `slice` of one feed, by one workgroup: its chunks' sums at the 512 targets into partial[slice][512] (kde_sum_kernel;
+// kde_sum_multi_kernel with the slice, the targets and 1 / h^2 of the workgroup's feed)
+__device__ __forceinline__ void kde_sum_slice(const double *x, int64_t n, int64_t n_chunks, int64_t chunks_per_slice, int64_t slice,
+                                              const double *targets, double inv_h2, double *partial, unsigned long long *skipped)
 {
     __shared__ double src[KDE_CHUNK];
     __shared__ unsigned int n_skipped;
@@ -157,7 +169,7 @@ kde_sum_kernel(const double *x, int64_t n, int64_t n_chunks, int64_t chunks_per_
     // thread t owns the neighbours 2t and 2t + 1: what one of them may skip the other mostly may too
     const double t0 = targets[2 * threadIdx.x], t1 = targets[2 * threadIdx.x + 1];
     double sum0 = 0.0, sum1 = 0.0;
-    const int64_t c0 = (int64_t)blockIdx.x * chunks_per_slice;
+    const int64_t c0 = slice * chunks_per_slice;
     const int64_t c1 = c0 + chunks_per_slice < n_chunks ? c0 + chunks_per_slice : n_chunks;
     unsigned int mine = 0;
     for (int64_t c = c0; c < c1; c++) {
@@ -200,16 +212,23 @@ kde_sum_kernel(const double *x, int64_t n, int64_t n_chunks, int64_t chunks_per_
     if (mine) atomicAdd(&n_skipped, mine);
     __syncthreads();
     if (threadIdx.x == 0 && n_skipped) atomicAdd(skipped, (unsigned long long)n_skipped);
-    partial[(int64_t)blockIdx.x * KDE_POINTS + 2 * threadIdx.x] = sum0;
-    partial[(int64_t)blockIdx.x * KDE_POINTS + 2 * threadIdx.x + 1] = sum1;
+    partial[slice * KDE_POINTS + 2 * threadIdx.x] = sum0;
+    partial[slice * KDE_POINTS + 2 * threadIdx.x + 1] = sum1;
 }
 
-// the slices' sums of target blockIdx.x in the fixed order: thread t slices t, t + 256, ..., then the tree
-__device__ __forceinline__ double kde_slice_total(const double *partial, int64_t n_slices)
+__global__ void __launch_bounds__(KDE_THREADS)
+kde_sum_kernel(const double *x, int64_t n, int64_t n_chunks, int64_t chunks_per_slice, const double *targets, double inv_h2,
+               double *partial, unsigned long long *skipped)
+{
+    kde_sum_slice(x, n, n_chunks, chunks_per_slice, blockIdx.x, targets, inv_h2, partial, skipped);
+}
+
+// the slices' sums of target `target` in the fixed order: thread t slices t, t + 256, ..., then the tree
+__device__ __forceinline__ double kde_slice_total(const double *partial, int64_t n_slices, int target)
 {
     __shared__ double red[KDE_THREADS];
     double acc = 0.0;
-    for (int64_t s = threadIdx.x; s < n_slices; s += KDE_THREADS) acc += partial[s * KDE_POINTS + blockIdx.x];
+    for (int64_t s = threadIdx.x; s < n_slices; s += KDE_THREADS) acc += partial[s * KDE_POINTS + target];
     return kde_block_tree(acc, red);
 }
 
@@ -217,7 +236,7 @@ __device__ __forceinline__ double kde_slice_total(const double *partial, int64_t
 __global__ void __launch_bounds__(KDE_THREADS)
 kde_slice_kernel(const double *partial, int64_t n_slices, int64_t n, double *raw)
 {
-    const double total = kde_slice_total(partial, n_slices);
+    const double total = kde_slice_total(partial, n_slices, blockIdx.x);
     if (threadIdx.x == 0) raw[blockIdx.x] = total / (double)n;
 }
 
@@ -225,7 +244,7 @@ kde_slice_kernel(const double *partial, int64_t n_slices, int64_t n, double *raw
 __global__ void __launch_bounds__(KDE_THREADS)
 kde_slice_sum_kernel(const double *partial, int64_t n_slices, double *sums)
 {
-    const double total = kde_slice_total(partial, n_slices);
+    const double total = kde_slice_total(partial, n_slices, blockIdx.x);
     if (threadIdx.x == 0) sums[blockIdx.x] = total;
 }
 

@@ -1674,6 +1674,45 @@ KdeData LodEngine::lodKde(int winsize, double error, int MAX_GAP, int step, bool
     return result();
 }
 
+bool LodEngine::kdeMultiInOneCall() const { return impl->shards.size() == 1 && !g_options.kde_on_shards; }
+
+std::vector<KdeData> LodEngine::lodKdeMulti(const std::vector<int> &winsizes, double error, int MAX_GAP, const std::vector<int> *steps,
+                                            const std::vector<int> *kdeSubsample, std::vector<int> *status)
+{
+    const size_t m = winsizes.size();
+    std::vector<KdeData> out(m);
+    std::vector<int32_t> st(m);
+    for (size_t i = 0; i < m; i++) st[i] = steps ? (*steps)[i] : winsizes[i];
+    if (status) status->assign(m, 0);
+    static_assert(KDE_MAX_FEEDS == GARLIC_KDE_MAX_FEEDS, "one limit");
+    if (!kdeMultiInOneCall() || m > (size_t)GARLIC_KDE_MAX_FEEDS) {
+        for (size_t i = 0; i < m; i++) out[i] = lodKde(winsizes[i], error, MAX_GAP, st[i], false, 0, 0.0, kdeSubsample);
+        return out;
+    }
+    if (m == 0) return out;
+    auto &s = impl->shards[0];
+    const bool subset = kdeSubsample && !kdeSubsample->empty();
+    std::cerr << "Calculating LOD scores with winsizes";
+    for (size_t i = 0; i < m; i++) std::cerr << (i ? ", " : " ") << winsizes[i];
+    std::cerr << " (thinned on the device, KDE of all sizes on the device in one call).\n";
+    std::vector<int32_t> mine;
+    if (subset)
+        for (size_t i = 0; i < kdeSubsample->size(); i++) {
+            if (i && (*kdeSubsample)[i] <= (*kdeSubsample)[i - 1]) fail("KDE subsample must be in increasing order");
+            mine.push_back((*kdeSubsample)[i] - s.ind_begin);
+        }
+    std::vector<garlic_kde> gk(m);
+    std::vector<int32_t> sizes(winsizes.begin(), winsizes.end()), code(m, 0);
+    if (garlic_lod_kde_multi(s.panel, sizes.data(), st.data(), (int32_t)m, error, MAX_GAP, impl->use_gl, subset ? mine.data() : nullptr,
+                             (int32_t)mine.size(), gk.data(), status ? code.data() : nullptr, nullptr) != GARLIC_OK)
+        fail(std::string("garlic_lod_kde_multi: ") + garlic_hip_last_error());
+    for (size_t i = 0; i < m; i++) {
+        if (status) (*status)[i] = code[i];
+        if (!code[i]) memcpy(&out[i], &gk[i], sizeof out[i]);
+    }
+    return out;
+}
+
 // ---- ROH calls
 std::vector<ROHData *> *initROHData(IndData *indData)
 {

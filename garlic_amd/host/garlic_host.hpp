@@ -324,6 +324,7 @@ std::vector<int> drawLdSubsample(int nind, int ldSubsample, unsigned long long s
 // there): empty = everyone (kdeSubsample <= 0 or >= nind), else kdeSubsample distinct indices, increasing
 std::vector<int> drawKdeSubsample(int nind, int kdeSubsample, unsigned long long seed);
 
+constexpr int KDE_MAX_FEEDS = 32;    // GARLIC_KDE_MAX_FEEDS: the most window sizes one LodEngine::lodKdeMulti call hands the library
 // garlic_kde of include/garlic_hip.h on this side (the same layout): LodEngine::lodKde's result
 struct KdeData {
     int64_t n;
@@ -367,6 +368,14 @@ public:
     // sorted feeds merged on the host, then garlic_feed_kde.  kde_select.hpp turns the result into a cutoff.
     KdeData lodKde(int winsize, double error, int MAX_GAP, int step, bool weighted = false, int M = 0, double mu = 0.0,
                       const std::vector<int> *kdeSubsample = nullptr);
+    // lodKde of several window sizes of a sweep (unweighted scores; steps NULL: the sizes).  One shard on one device: one
+    // garlic_lod_kde_multi -- one pass over the panel for all feeds, six KDE launches and two waits for all sizes -- and
+    // every result equals lodKde's bit for bit.  status given: status->at(i) != 0 marks a size the library refused (its
+    // result is not set; lodKde of that size says why), the others stand; NULL: any refused size fails the call.  Several
+    // shards or devices (kdeMultiInOneCall() false): a loop over lodKde, which fails at the first refused size.
+    std::vector<KdeData> lodKdeMulti(const std::vector<int> &winsizes, double error, int MAX_GAP, const std::vector<int> *steps = nullptr,
+                                     const std::vector<int> *kdeSubsample = nullptr, std::vector<int> *status = nullptr);
+    bool kdeMultiInOneCall() const;
     // several window sizes in one call (unweighted --error scores): the feeds of exploreWinsizes / selectWinsize /
     // selectWinsizeFromList (garlic-roh.cpp:726-751, 798-837, 881-920), one DoubleData per size; steps NULL: the sizes
     std::vector<DoubleData *> lodFeedMulti(const std::vector<int> &winsizes, double error, int MAX_GAP,

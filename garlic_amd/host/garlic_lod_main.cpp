@@ -415,17 +415,50 @@ int main(int argc, char **argv)
                 std::cerr << "Selected LOD score cutoff: " << cutoff << "\n";
                 if (!a.size_bounds.empty() || a.nclust) roh_calls_at(W, single_out, a.have_cutoff ? a.lod_cutoff : cutoff);
             };
+            // Unweighted sweeps on one device: the KDEs of several sizes from one call (LodEngine::lodKdeMulti) -- a whole
+            // --winsize-multi list, or the next SWEEP_BATCH sizes of the stepping search, where the sizes past the selected
+            // one are computed ahead of need: one that the library refuses fails the run only when the loop reaches it, with
+            // the per-size call's message.  GARLIC_KDE_MULTI_OFF: the per-size loop (same files, same selection lines).
+            const bool batched = !a.weighted && !getenv("GARLIC_KDE_MULTI_OFF") && engine.kdeMultiInOneCall() && (!single || a.auto_winsize);
+            constexpr int SWEEP_BATCH = 4;
+            std::vector<int> batch_sizes, batch_status;
+            std::vector<KdeData> batch;
+            auto kde_batch = [&](const std::vector<int> &ws) {
+                std::vector<int> steps;
+                for (int W : ws) steps.push_back(a.kde_thinning ? W : 1);
+                batch_sizes = ws;
+                batch = engine.lodKdeMulti(ws, a.error, a.max_gap, &steps, &kdesub, &batch_status);
+            };
+            auto from_batch = [&](size_t j) -> KdeData {
+                if (batch_status[j]) return kde_of(batch_sizes[j]);      // refused: the per-size call says why, and fails
+                return batch[j];
+            };
             if (!a.auto_winsize) {
-                for (int W : sizes) finish(W, kde_of(W), 1.0, single);
+                if (batched) {
+                    for (size_t i0 = 0; i0 < sizes.size(); i0 += KDE_MAX_FEEDS) {
+                        kde_batch(std::vector<int>(sizes.begin() + (long)i0, sizes.begin() + (long)std::min(sizes.size(), i0 + KDE_MAX_FEEDS)));
+                        for (size_t j = 0; j < batch_sizes.size(); j++) finish(batch_sizes[j], from_batch(j), 1.0, single);
+                    }
+                } else {
+                    for (int W : sizes) finish(W, kde_of(W), 1.0, single);
+                }
                 term_report();
                 return 0;
             }
             if (a.weighted) { std::cerr << "Not currently supported.\n"; return 1; }    // as the reference's selectWinsize says
             const double threshold = 0.50;
             std::cerr << "Searching for acceptable window size, smoothness threshold: " << threshold << "\nwinsize\tsmoothness\n";
+            size_t batch0 = 0;                  // the loop index of the batch's first size
             for (size_t i = 0;; i++) {      // selectWinsize: from --winsize in steps; selectWinsizeFromList: the list, the last size if none passes
                 const int W = single ? a.winsize + (int)i * a.auto_winsize_step : sizes[i];
-                const KdeData k = kde_of(W);
+                if (batched && (i == 0 || i - batch0 >= batch_sizes.size())) {
+                    std::vector<int> ws;
+                    const size_t want = single ? (size_t)SWEEP_BATCH : std::min<size_t>(sizes.size() - i, KDE_MAX_FEEDS);
+                    for (size_t j = 0; j < want; j++) ws.push_back(single ? a.winsize + (int)(i + j) * a.auto_winsize_step : sizes[i + j]);
+                    batch0 = i;
+                    kde_batch(ws);
+                }
+                const KdeData k = batched ? from_batch(i - batch0) : kde_of(W);
                 const double mse = kdeWiggle(k.x, k.y, KDE_POINTS);
                 std::cerr << W << "\t" << mse << "\n";
                 if (mse <= threshold || (!single && i + 1 == sizes.size())) {

@@ -59,7 +59,8 @@ extern "C" {
  *    garlic_kde_part_moment, garlic_kde_part_rank, garlic_kde_part_sums, garlic_kde_parts, garlic_kde_parts_info (likewise);
  *    garlic_feature_set, garlic_roh_interval, GARLIC_FEATURE_MAX_EFFECTS, garlic_feature_set_create,
  *    garlic_feature_set_destroy, garlic_feature_set_rows, garlic_feature_set_sites, garlic_feature_counts,
- *    garlic_feature_counts_info (likewise) */
+ *    garlic_feature_counts_info (likewise); GARLIC_KDE_MAX_FEEDS, garlic_feed_kde_multi, garlic_lod_kde_multi,
+ *    garlic_feed_kde_multi_info (likewise) */
 #define GARLIC_HIP_ABI_VERSION 8
 
 #define GARLIC_OK 0
@@ -578,7 +579,7 @@ int garlic_feed_sort_info(garlic_ctx *ctx, int32_t *passes_run, int32_t *passes_
  * garlic_lod_kde: garlic_lod_feed_subset up to, not including, the copy to the host -- same arguments, same kernel forms,
  * same garlic_lod_feed_info and chr_counts -- always in ascending order whatever garlic_panel_set_feed_order says (the
  * setting is left as found), then garlic_feed_kde on the device buffer: no feed value crosses PCIe.  An empty feed is the
- * n < 2 error.  The multi-size feed calls have no KDE twin: a sweep calls this once per size.
+ * n < 2 error.  A sweep over several window sizes: garlic_lod_kde_multi, below.
  * garlic_feed_kde_info: of the last KDE on the context: chunks of 2048 sources, (chunk, target) pairs skipped as exactly
  * zero, bytes of scratch held.  Any pointer may be NULL.
  * garlic_feed_kde_times: HIP-event times of the last successful KDE on the context: the two moment passes with their
@@ -595,6 +596,48 @@ int garlic_lod_kde(garlic_panel *panel, int32_t winsize, double error, int32_t m
                    garlic_kde *out, int64_t *chr_counts);
 int garlic_feed_kde_info(garlic_ctx *ctx, int64_t *chunks, int64_t *pairs_skipped, int64_t *scratch_bytes);
 int garlic_feed_kde_times(garlic_ctx *ctx, float *moments_ms, float *sums_ms);
+
+/* The KDE of several feeds in one call (csrc/kde_multi_kernels.hpp; which workgroup does what: host/kde_multi_plan.hpp):
+ * the window sizes of a sweep (exploreWinsizes, selectWinsize, selectWinsizeFromList) without a pass, two waits and six
+ * small launches per size.  The four steps of garlic_feed_kde run once each for all feeds -- two moment passes, two tree
+ * passes, one sums launch, one slice launch: SIX kernel launches whatever n_feeds is -- and the host waits on the
+ * context's stream TWICE in the call: for all feeds' moments (it then computes every h and every target set and uploads
+ * them in one copy), and for all feeds' sums and skip counts.  When no feed is left after the moments the sums part is
+ * skipped: four launches, one wait.  A feed's partition, element order and summation trees are those of garlic_feed_kde
+ * (the same source lines), so every successful outs[i] equals garlic_feed_kde's struct for feed i alone, in every field,
+ * bit for bit, whatever else is in the batch.
+ * garlic_feed_kde_multi: sorted[i] holds n[i] doubles, ascending, 1 <= n_feeds <= GARLIC_KDE_MAX_FEEDS.  GARLIC_DEVICE:
+ * borrowed, never modified; GARLIC_HOST: uploaded one after the other into context scratch.  Per feed:
+ *     status != NULL: the call returns GARLIC_OK when it ran; status[i] is GARLIC_OK or GARLIC_ERR_INVALID for what
+ *       garlic_feed_kde refuses (n < 2; a NaN or an infinity; not ascending; a bad bandwidth).  outs[i] of a refused feed
+ *       is untouched, and garlic_hip_last_error names the lowest refused index and its cause ("feed 3: " and
+ *       garlic_feed_kde's words).  A feed refused after the moments takes no part in the sums launches.
+ *     status == NULL: any refused feed makes the call return its code, with ALL outs untouched.
+ * Argument errors -- a NULL ctx, sorted, n or outs; n_feeds out of range; a bad `where`; sorted[i] NULL with n[i] > 0; more
+ * than 2^31 - 1 chunks in all -- and GARLIC_ERR_NOMEM leave everything untouched.  Scratch (8 B + 4 B per 2048 values, the
+ * slice sums, 8.5 KB per feed of table; host buffers: the values) is kept with the context until
+ * garlic_panel_release_scratch.
+ * garlic_lod_kde_multi: unweighted scores (no weighted multi-size feed exists).  garlic_lod_feed_multi (use_gl == 0) or
+ * garlic_lod_feed_multi_tgls (use_gl != 0) up to, not including, the copy to the host -- the same validation of winsizes,
+ * steps and ind_idx, the same planning, kernel forms and grouping, the same garlic_lod_feed_info /
+ * garlic_lod_feed_multi_info answers and chr_counts ([n_sizes][nchr], or NULL) -- always in ascending order (the order
+ * setting is left as found); a size that those calls run through the single-size path has its feed moved, device to
+ * device, out of the panel's scratch before the next size runs.  Then the batched KDE on the sizes' device buffers, on the
+ * context's stream behind an event from every size's stream: no feed value crosses PCIe.  n_sizes <=
+ * GARLIC_KDE_MAX_FEEDS.  outs[i] equals garlic_lod_kde(winsizes[i], .., steps[i], ..)'s struct bit for bit; status and the
+ * untouched-output rules as above; a size whose feed holds fewer than 2 values (a window wider than every chromosome) is
+ * refused in garlic_lod_kde's words.  Like every feed call it makes KDE parts borrowed from the panel earlier stale.
+ * garlic_feed_kde_multi_info: of the last multi-feed KDE on the context, for its first n feeds: chunks[i] = ceil(n_i / 2048)
+ * (0 for a feed refused before the moments), pairs_skipped[i], *kernel_launches (6, or 4), *host_waits (2, or 1), bytes of
+ * scratch held, HIP-event times of the moment part and the sums part.  Any pointer may be NULL. */
+#define GARLIC_KDE_MAX_FEEDS 32
+int garlic_feed_kde_multi(garlic_ctx *ctx, const double *const *sorted, const int64_t *n, int32_t n_feeds, int32_t where,
+                          garlic_kde *outs, int32_t *status);
+int garlic_lod_kde_multi(garlic_panel *panel, const int32_t *winsizes, const int32_t *steps, int32_t n_sizes, double error,
+                         int32_t max_gap, int32_t use_gl, const int32_t *ind_idx, int32_t n_idx, garlic_kde *outs,
+                         int32_t *status, int64_t *chr_counts);
+int garlic_feed_kde_multi_info(garlic_ctx *ctx, int32_t n, int64_t *chunks, int64_t *pairs_skipped, int32_t *kernel_launches,
+                               int32_t *host_waits, int64_t *scratch_bytes, float *moments_ms, float *sums_ms);
 
 /* The KDE of a feed that is split into sorted parts: a sharded panel makes one part per shard, each on its shard's device,
  * and no feed value leaves its device.  n, the sum, the sum of squared deviations and the 512 Gaussian sums add over the

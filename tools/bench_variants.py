@@ -25,6 +25,9 @@ commit, which times the loop only; several lists separated by ";" share one pane
 --modes feed_kde: the device KDE (garlic_lod_kde: moment and sums kernels by HIP events, the whole call) beside the sorted
 garlic_lod_feed_subset call it replaces, at the --kde-inds and the everyone scale (--tree for the parent commit;
 profiles/feed_kde_ab.txt).
+--modes kde_multi: the KDEs of every size of --winsizes (step = size; a sweep: 50,100,200,300) on one resident panel, as a loop
+of garlic_lod_kde per size (the path of the commits before garlic_lod_kde_multi, unchanged) beside one garlic_lod_kde_multi
+call, at the --kde-inds and the everyone scale, with the moment and sums event times of both (profiles/kde_multi_ab.txt).
 --modes feed_kde_parts: the KDE of a panel sharded over two panels on the one device: the present path (sorted feeds to the
 host, merged, uploaded, garlic_feed_kde) beside garlic_lod_kde_part + garlic_kde_parts (profiles/kde_parts_ab.txt).
 --modes feature_counts: garlic_feature_counts at --snps hom rows x --inds individuals (the issue's shapes: 1000000 x 1250 and x
@@ -458,6 +461,68 @@ def feed_kde_leg(args):
                          "exp_per_s_of_pairs_not_skipped": (info["chunks"] * 512 - info["pairs_skipped"]) * 2048.0 / (float(np.median(sums)) * 1e-3)})
         print(json.dumps(line), flush=True)
         del feed
+        panel.release_scratch()
+
+
+def kde_multi_leg(args):
+    """A window-size sweep's KDEs on one resident panel (unweighted --error scores, step = size): "loop" is one garlic_lod_kde
+    per size, "multi" one garlic_lod_kde_multi over all sizes.  Per scale (--kde-inds individuals, everyone) one JSON line:
+    the host clock around either (1 + --steps repeats, the first dropped; every repeat listed, so the spread shows), the
+    sums of the loop's per-size moment and sums event times (garlic_feed_kde_times) and the multi call's own
+    (garlic_feed_kde_multi_info), and whether the structs agree bit for bit."""
+    import time
+    import torch
+    from garlic_amd import abi, synth
+
+    torch.cuda.set_device(0)
+    dev = torch.device("cuda", 0)
+    nloci, nind = args.snps, args.inds
+    sizes = [int(w) for w in args.winsizes.split(",")]
+    error, max_gap = 0.001, 200000
+    spec = synth.PanelSpec(nloci, seed=20260105, max_gap=max_gap)
+    ctx = abi.Context(0)
+    panel = abi.Panel(ctx, spec.chr_nloci, nind)
+    panel.set_map(spec.pos, spec.centro_start, spec.centro_end)
+    panel.set_freq(spec.freq)
+    for l0, g in synth.genotype_chunks(spec, nind, dev):
+        torch.cuda.synchronize()
+        panel.set_genotypes_device(g.data_ptr(), g.shape[1], l0, g.shape[0])
+    del g
+    rng = np.random.default_rng(11)
+    subsets = [np.sort(rng.choice(nind, size=min(args.kde_inds, nind), replace=False)).astype(np.int32), None]
+    for idx in subsets:
+        loop_ms, loop_mom, loop_sums, multi_ms, multi_mom, multi_sums = [], [], [], [], [], []
+        for k in range(1 + args.steps):          # the two paths in turn, so that a drift of the clocks meets both
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            one, mom, sums = [], 0.0, 0.0
+            for W in sizes:
+                one.append(panel.lod_kde(W, error, max_gap, W, ind_idx=idx)[0])
+                t = ctx.feed_kde_times()
+                mom += t["moments_ms"]
+                sums += t["sums_ms"]
+            t1 = time.perf_counter()
+            many, status, _ = panel.lod_kde_multi(sizes, error, max_gap, ind_idx=idx, strict=True)
+            t2 = time.perf_counter()
+            info = ctx.feed_kde_multi_info(len(sizes))
+            if k:
+                loop_ms.append((t1 - t0) * 1e3)
+                multi_ms.append((t2 - t1) * 1e3)
+                loop_mom.append(mom)
+                loop_sums.append(sums)
+                multi_mom.append(info["moments_ms"])
+                multi_sums.append(info["sums_ms"])
+        same = all(a["n"] == b["n"] and all(np.float64(a[f]).tobytes() == np.float64(b[f]).tobytes() for f in ("h", "sd", "q25", "q75", "lo", "hi"))
+                   and all(a[f].tobytes() == b[f].tobytes() for f in ("x", "y", "raw")) for a, b in zip(one, many))
+        print(json.dumps({"mode": "kde_multi", "snps": nloci, "inds": nind, "winsizes": sizes, "repeats": args.steps,
+                          "feed_individuals": nind if idx is None else int(idx.shape[0]), "values": [int(k["n"]) for k in many],
+                          "chunks": info["chunks"], "pairs_skipped": info["pairs_skipped"],
+                          "loop_of_lod_kde_ms": loop_ms, "loop_of_lod_kde_ms_median": float(np.median(loop_ms)),
+                          "lod_kde_multi_ms": multi_ms, "lod_kde_multi_ms_median": float(np.median(multi_ms)),
+                          "loop_moment_kernels_ms_median": float(np.median(loop_mom)), "loop_sums_kernels_ms_median": float(np.median(loop_sums)),
+                          "multi_moment_kernels_ms_median": float(np.median(multi_mom)), "multi_sums_kernels_ms_median": float(np.median(multi_sums)),
+                          "multi_kernel_launches": info["kernel_launches"], "multi_host_waits": info["host_waits"],
+                          "multi_scratch_bytes": info["scratch_bytes"], "structs_identical": bool(same)}), flush=True)
         panel.release_scratch()
 
 
@@ -934,6 +999,8 @@ def main():
         return feature_counts_leg(args)
     if args.modes == "feed_kde_parts":
         return feed_kde_parts_leg(args)
+    if args.modes == "kde_multi":
+        return kde_multi_leg(args)
     if args.modes == "bed_ingest":
         return bed_ingest_leg(args)
     if args.modes == "ld_phased":
