@@ -52,6 +52,9 @@ SYMBOLS = [
     "garlic_feature_set_create", "garlic_feature_set_destroy", "garlic_feature_set_rows", "garlic_feature_set_sites",
     "garlic_feature_counts", "garlic_feature_counts_info",
     "garlic_feed_kde_multi", "garlic_lod_kde_multi", "garlic_feed_kde_multi_info",
+    "garlic_kde_part_set_create", "garlic_lod_kde_part_set", "garlic_kde_part_set_destroy", "garlic_kde_part_set_counts",
+    "garlic_kde_part_set_moment", "garlic_kde_part_set_rank", "garlic_kde_part_set_sums", "garlic_kde_parts_multi",
+    "garlic_kde_parts_multi_info",
 ]
 FEATURE_MAX_EFFECTS = 256   # GARLIC_FEATURE_MAX_EFFECTS
 FEATURE_GROUP_EFFECTS = 32  # effects per launch
@@ -209,6 +212,17 @@ def lib():
     L.garlic_kde_part_sums.argtypes = [_vp, _f64p, C.c_double, _f64p]
     L.garlic_kde_parts.argtypes = [C.POINTER(_vp), C.c_int32, C.POINTER(Kde)]
     L.garlic_kde_parts_info.argtypes = [C.POINTER(_vp), C.c_int32, _i64p, _i64p, _i32p, C.POINTER(C.c_float)]
+    L.garlic_kde_part_set_create.argtypes = [_vp, C.POINTER(_vp), _i64p, C.c_int32, C.c_int32, C.POINTER(_vp)]
+    L.garlic_lod_kde_part_set.argtypes = [_vp, _i32p, _i32p, C.c_int32, C.c_double, C.c_int32, C.c_int32, _i32p, C.c_int32,
+                                          C.POINTER(_vp), _i64p]
+    L.garlic_kde_part_set_destroy.argtypes = [_vp]
+    L.garlic_kde_part_set_counts.argtypes = [_vp, _i64p]
+    L.garlic_kde_part_set_moment.argtypes = [_vp, C.c_int32, _f64p, _f64p, _f64p, _f64p, _i32p]
+    L.garlic_kde_part_set_rank.argtypes = [_vp, C.POINTER(C.c_uint64), C.c_int32, _i64p]
+    L.garlic_kde_part_set_sums.argtypes = [_vp, _f64p, _f64p, _i32p, _f64p, _i64p]
+    L.garlic_kde_parts_multi.argtypes = [C.POINTER(_vp), C.c_int32, C.POINTER(Kde), _i32p]
+    L.garlic_kde_parts_multi_info.argtypes = [C.POINTER(_vp), C.c_int32, _i64p, _i64p, _i32p, _i32p, _i32p, C.POINTER(C.c_float),
+                                              C.POINTER(C.c_float)]
     L.garlic_feature_set_create.argtypes = [_vp, C.c_int64, C.c_int32, C.POINTER(_vp)]
     L.garlic_feature_set_destroy.argtypes = [_vp]
     L.garlic_feature_set_rows.argtypes = [_vp, _vp, C.c_int64, C.c_int64, C.c_int64]
@@ -365,6 +379,26 @@ class Context:
         else:
             check(lib().garlic_kde_part_create(self.handle, _vp(values) if values else None, int(n), DEVICE, C.byref(h)))
         return KdePart(h)
+
+    def kde_part_set(self, feeds, ns=None):
+        """garlic_kde_part_set_create: one shard's parts of several split feeds, an abi.KdePartSet.  feeds: a list of
+        contiguous float64 numpy arrays (host, uploaded; ns defaults to their lengths), or of device addresses (int, 0 for an
+        empty feed) with ns their lengths, borrowed until the set is closed."""
+        m = len(feeds)
+        host = all(isinstance(f, np.ndarray) for f in feeds)
+        assert host or not any(isinstance(f, np.ndarray) for f in feeds), "host arrays or device addresses, not both"
+        if host:
+            for f in feeds:
+                assert f.dtype == np.float64 and f.flags["C_CONTIGUOUS"] and f.ndim == 1
+            ns = [f.shape[0] for f in feeds] if ns is None else [int(v) for v in ns]
+            ptrs = (_vp * max(m, 1))(*[f.ctypes.data for f in feeds])
+        else:
+            ptrs = (_vp * max(m, 1))(*[int(f) if f else None for f in feeds])
+        lens = np.ascontiguousarray(ns, dtype=np.int64)
+        assert lens.shape == (m,)
+        h = _vp()
+        check(lib().garlic_kde_part_set_create(self.handle, ptrs, _ptr(lens, _i64p), m, HOST if host else DEVICE, C.byref(h)))
+        return KdePartSet(h, m)
 
     def gmm_fit(self, values, a0, mean0, var0, n=None, max_iter=1000, precision=1e-5, out=None):
         """garlic_gmm_fit: GMM::estimate's EM fit of len(a0) Gaussians, as a dict: k, iterations, converged, loglik, bic and
@@ -553,6 +587,85 @@ def kde_parts_info(parts):
                                       ms.ctypes.data_as(C.POINTER(C.c_float))))
     return {"chunks": chunks[:len(parts)], "pairs_skipped": skipped[:len(parts)], "rank_rounds": rounds.value,
             "sums_ms": ms[:len(parts)]}
+
+
+class KdePartSet:
+    """garlic_kde_part_set: one shard's sorted parts of F split feeds (Context.kde_part_set, Panel.lod_kde_part_set).  The
+    step calls work on all F feeds at once and are what a caller with one process per GPU all-reduces between;
+    kde_parts_multi(sets) runs them all.  Close it before its context."""
+
+    def __init__(self, handle, n_feeds):
+        self.handle, self.n_feeds = handle, n_feeds
+
+    def counts(self):
+        n = np.zeros(self.n_feeds, dtype=np.int64)
+        check(lib().garlic_kde_part_set_counts(self.handle, _ptr(n, _i64p)))
+        return n
+
+    def moment(self, pass_, means=None, status=None):
+        """pass 0: (sums [F], lo [F], hi [F], status [F]) -- NaN in lo / hi of an empty or switched-off feed; pass 1: (the
+        sums of (x - means[i])^2 [F], status).  status: int32 [F], nonzero switches a feed off (default: none)."""
+        F = self.n_feeds
+        st = np.zeros(F, dtype=np.int32) if status is None else np.ascontiguousarray(status, dtype=np.int32).copy()
+        m = None if means is None else np.ascontiguousarray(means, dtype=np.float64)
+        assert st.shape == (F,) and (m is None or m.shape == (F,))
+        v, lo, hi = np.zeros(F), np.full(F, np.nan), np.full(F, np.nan)
+        check(lib().garlic_kde_part_set_moment(self.handle, int(pass_), _ptr(m, _f64p), _ptr(v, _f64p), _ptr(lo, _f64p), _ptr(hi, _f64p),
+                                               _ptr(st, _i32p)))
+        return (v, st) if pass_ else (v, lo, hi, st)
+
+    def rank(self, keys):
+        """keys: uint64 [F, m], m <= 1024; how many values of feed i have a key below keys[i, t]: int64 [F, m]"""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        assert keys.ndim == 2 and keys.shape[0] == self.n_feeds
+        below = np.zeros(keys.shape, dtype=np.int64)
+        check(lib().garlic_kde_part_set_rank(self.handle, keys.ctypes.data_as(C.POINTER(C.c_uint64)), int(keys.shape[1]),
+                                             _ptr(below, _i64p)))
+        return below
+
+    def sums(self, targets, h, active=None):
+        """targets [F, 512], h [F], active int32 [F] or None -> (the undivided Gaussian sums [F, 512], pairs_skipped [F])"""
+        F = self.n_feeds
+        targets = np.ascontiguousarray(targets, dtype=np.float64)
+        h = np.ascontiguousarray(h, dtype=np.float64)
+        act = None if active is None else np.ascontiguousarray(active, dtype=np.int32)
+        assert targets.shape == (F, KDE_POINTS) and h.shape == (F,) and (act is None or act.shape == (F,))
+        out, skipped = np.zeros((F, KDE_POINTS)), np.zeros(F, dtype=np.int64)
+        check(lib().garlic_kde_part_set_sums(self.handle, _ptr(targets, _f64p), _ptr(h, _f64p), _ptr(act, _i32p), _ptr(out, _f64p),
+                                             _ptr(skipped, _i64p)))
+        return out, skipped
+
+    def close(self):
+        if self.handle:
+            lib().garlic_kde_part_set_destroy(self.handle)
+            self.handle = _vp()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def kde_parts_multi(sets, strict=False, outs=None):
+    """garlic_kde_parts_multi: the KDEs of the unions {feed i of every set, in this order}.  Returns ([feed_kde's dict, or
+    None for a refused feed], [status per feed]); strict and outs as Context.feed_kde_multi."""
+    m = sets[0].n_feeds if sets and sets[0] is not None else 0
+    return _kde_multi_result(lambda ks, st: lib().garlic_kde_parts_multi(_part_handles(sets), len(sets), ks, st), m, strict, outs)
+
+
+def kde_parts_multi_info(sets):
+    """garlic_kde_parts_multi_info: {chunks [P, F], pairs_skipped [P, F], kernel_launches [P], host_waits [P], rank_rounds [P],
+    moments_ms [P], sums_ms [P]} of the last KDE over these sets"""
+    P, F = len(sets), sets[0].n_feeds
+    chunks, skipped = np.zeros((P, F), dtype=np.int64), np.zeros((P, F), dtype=np.int64)
+    launches, waits, rounds = (np.zeros(P, dtype=np.int32) for _ in range(3))
+    mom, sums = np.zeros(P, dtype=np.float32), np.zeros(P, dtype=np.float32)
+    fp = C.POINTER(C.c_float)
+    check(lib().garlic_kde_parts_multi_info(_part_handles(sets), P, _ptr(chunks, _i64p), _ptr(skipped, _i64p), _ptr(launches, _i32p),
+                                            _ptr(waits, _i32p), _ptr(rounds, _i32p), mom.ctypes.data_as(fp), sums.ctypes.data_as(fp)))
+    return {"chunks": chunks, "pairs_skipped": skipped, "kernel_launches": launches, "host_waits": waits, "rank_rounds": rounds,
+            "moments_ms": mom, "sums_ms": sums}
 
 
 class DeviceBuffer:
@@ -996,6 +1109,20 @@ class Panel:
         check(lib().garlic_lod_kde_part(self.handle, winsize, error, max_gap, int(use_gl), int(weighted), M, mu, step,
                                         _ptr(idx, _i32p), 0 if idx is None else int(idx.shape[0]), C.byref(h), _ptr(per_chr, _i64p)))
         return KdePart(h), per_chr
+
+    def lod_kde_part_set(self, winsizes, error, max_gap, steps=None, use_gl=False, ind_idx=None):
+        """garlic_lod_kde_part_set: lod_kde_multi's arguments; the sizes' sorted device feeds become an abi.KdePartSet that
+        borrows the panel's feed slots (stale after the panel's next score or feed call).  Returns (the set, per-chromosome
+        counts [n_sizes, nchr])."""
+        sizes = np.ascontiguousarray(winsizes, dtype=np.int32)
+        st = sizes.copy() if steps is None else np.ascontiguousarray(steps, dtype=np.int32)
+        idx = None if ind_idx is None else np.ascontiguousarray(ind_idx, dtype=np.int32)
+        m = int(sizes.shape[0])
+        h = _vp()
+        per_chr = np.zeros((max(m, 1), self.nchr), dtype=np.int64)
+        check(lib().garlic_lod_kde_part_set(self.handle, _ptr(sizes, _i32p), _ptr(st, _i32p), m, error, max_gap, int(use_gl),
+                                            _ptr(idx, _i32p), 0 if idx is None else int(idx.shape[0]), C.byref(h), _ptr(per_chr, _i64p)))
+        return KdePartSet(h, m), per_chr[:m]
 
     def lod_feed_multi(self, winsizes, error, max_gap, steps=None, ind_idx=None, copy=True):
         """garlic_lod_feed_multi: the feeds of several window sizes in one call (unweighted --error scores; steps

@@ -23,6 +23,7 @@
 #include "feed_sort_kernel.hpp"
 #include "kde_kernels.hpp"
 #include "kde_multi_kernels.hpp"
+#include "kde_part_set_kernels.hpp"
 #include "gmm_kernels.hpp"
 #include "feature_kernels.hpp"
 #include "../host/kde_select.hpp"
@@ -6432,6 +6433,597 @@ int garlic_kde_parts_info(garlic_kde_part *const *parts, int32_t n_parts, int64_
         if (sums_ms) sums_ms[p] = parts[p]->sums_ms;
     }
     if (rank_rounds) *rank_rounds = parts[0]->rank_rounds;
+    return GARLIC_OK;
+}
+
+// ---- The KDEs of several split feeds at once (a window-size sweep on a sharded panel): a set holds one shard's part of
+// every feed, and every step of garlic_kde_parts runs once per set for all its feeds (kde_part_set_kernels.hpp).  The set's table of KdeFeedDesc lives in pinned memory and is mirrored on the device: the host writes
+// what a step needs (who is active, the unions' means, the targets), the step uploads it, runs, and copies it back.
+struct garlic_kde_part_set {
+    garlic_ctx *ctx = nullptr;
+    int32_t n_feeds = 0;
+    garlic_host::KdeMultiPlan plan;
+    int64_t n[GARLIC_KDE_MAX_FEEDS] = {};
+    DevBuf<double> own;                            // host buffers' uploads, one after the other
+    std::shared_ptr<uint64_t> gen;                 // garlic_lod_kde_part_set: as garlic_kde_part
+    uint64_t gen_at = 0;
+    DevBuf<double> partial, slices;
+    DevBuf<int32_t> flags;
+    DevBuf<KdeFeedDesc> table;
+    DevBuf<unsigned long long> keys;
+    DevBuf<long long> below;
+    void *pinned = nullptr;                        // h_table[n_feeds], h_keys and h_below [n_feeds][KDE_RANK_MAX]
+    KdeFeedDesc *h_table = nullptr;
+    unsigned long long *h_keys = nullptr;
+    long long *h_below = nullptr;
+    hipEvent_t ev[4] = {};                         // around the moment part and around the sums part
+    int32_t rank_m = 0;
+    int32_t launches = 0, waits = 0, rank_rounds = 0;   // garlic_kde_parts_multi_info
+    float moments_ms = 0.f, sums_ms = 0.f;
+    bool moments_timed = false;
+    size_t table_bytes() const { return sizeof(KdeFeedDesc) * (size_t)n_feeds; }
+    bool has_values() const { return plan.total_chunks > 0; }
+};
+
+static int kde_set_usable(const garlic_kde_part_set *set)
+{
+    if (!set) return fail(GARLIC_ERR_INVALID, "KDE part set is NULL");
+    if (set->gen && *set->gen != set->gen_at)
+        return fail(GARLIC_ERR_STATE, "KDE part set is stale: its panel has computed scores or a feed, or released its scratch, since the set was made");
+    return GARLIC_OK;
+}
+
+static void kde_set_free(garlic_kde_part_set *set)
+{
+    for (auto &e : set->ev)
+        if (e) (void)hipEventDestroy(e);
+    if (set->pinned) (void)hipHostFree(set->pinned);
+    delete set;
+}
+
+// everything a set's steps need, before anything is enqueued; d_x[i] may be filled in by the caller afterwards (h_table[i].x)
+static int kde_set_new(garlic_ctx *ctx, const int64_t *n, int32_t n_feeds, garlic_kde_part_set **out)
+{
+    namespace gh = garlic_host;
+    int rc;
+    if ((rc = set_device(ctx))) return rc;
+    std::unique_ptr<garlic_kde_part_set, void (*)(garlic_kde_part_set *)> set(new garlic_kde_part_set, kde_set_free);
+    set->ctx = ctx;
+    set->n_feeds = n_feeds;
+    if (!gh::kdePartSetPlan(n, n_feeds, &set->plan))
+        return fail(GARLIC_ERR_INVALID, "KDE part set: the %d feeds are more chunks than one launch holds", (int)n_feeds);
+    const size_t probes = (size_t)n_feeds * KDE_RANK_MAX;
+    if ((rc = set->partial.reserve((size_t)std::max<int64_t>(set->plan.total_chunks, 1))) ||
+        (rc = set->flags.reserve((size_t)std::max<int64_t>(set->plan.total_chunks, 1))) ||
+        (rc = set->slices.reserve((size_t)std::max<int64_t>(set->plan.total_slices, 1) * KDE_POINTS)) ||
+        (rc = set->table.reserve((size_t)n_feeds)) || (rc = set->keys.reserve(probes)) || (rc = set->below.reserve(probes)))
+        return rc;
+    const size_t bytes = set->table_bytes() + probes * (sizeof(unsigned long long) + sizeof(long long));
+    HIP_TRY(hipHostMalloc(&set->pinned, bytes, hipHostMallocDefault));
+    memset(set->pinned, 0, bytes);
+    set->h_table = static_cast<KdeFeedDesc *>(set->pinned);
+    set->h_keys = reinterpret_cast<unsigned long long *>(set->h_table + n_feeds);
+    set->h_below = reinterpret_cast<long long *>(set->h_keys + probes);
+    for (auto &e : set->ev) HIP_TRY(hipEventCreate(&e));
+    for (int i = 0; i < n_feeds; i++) {
+        const gh::KdeMultiFeedPlan &f = set->plan.feed[i];
+        KdeFeedDesc &d = set->h_table[i];
+        set->n[i] = n[i];
+        d.n = f.n;
+        d.n_chunks = f.n_chunks;
+        d.chunks_per_slice = f.chunks_per_slice;
+        d.n_slices = f.n_slices;
+        d.chunk_off = set->plan.chunk_first.at[i];
+        d.slice_off = set->plan.slice_first.at[i];
+        d.active = 1;
+    }
+    *out = set.release();
+    return GARLIC_OK;
+}
+
+int garlic_kde_part_set_create(garlic_ctx *ctx, const double *const *sorted, const int64_t *n, int32_t n_feeds, int32_t where,
+                               garlic_kde_part_set **out)
+{
+    if (!ctx || !sorted || !n || !out) return fail(GARLIC_ERR_INVALID, "KDE part set: context, feeds, lengths and set are required");
+    if (n_feeds < 1 || n_feeds > GARLIC_KDE_MAX_FEEDS)
+        return fail(GARLIC_ERR_INVALID, "KDE part set: %d feeds (1 to %d)", (int)n_feeds, GARLIC_KDE_MAX_FEEDS);
+    if (where != GARLIC_HOST && where != GARLIC_DEVICE) return fail(GARLIC_ERR_INVALID, "KDE part set: where must be GARLIC_HOST or GARLIC_DEVICE");
+    int64_t total = 0;
+    for (int i = 0; i < n_feeds; i++) {
+        if (n[i] < 0) return fail(GARLIC_ERR_INVALID, "KDE part set: n of feed %d must be >= 0 (got %lld)", i, (long long)n[i]);
+        if (n[i] > 0 && !sorted[i]) return fail(GARLIC_ERR_INVALID, "KDE part set: values of feed %d is NULL", i);
+        if (n[i] > INT64_MAX / 16 - total) return fail(GARLIC_ERR_INVALID, "KDE part set: the %d feeds are more chunks than one launch holds", (int)n_feeds);
+        total += n[i];
+    }
+    garlic_kde_part_set *set = nullptr;
+    int rc;
+    if ((rc = kde_set_new(ctx, n, n_feeds, &set))) return rc;
+    if (where == GARLIC_HOST && total > 0) {
+        hipError_t e = hipSuccess;
+        rc = set->own.reserve((size_t)total);
+        int64_t at = 0;
+        for (int i = 0; i < n_feeds && !rc && e == hipSuccess; i++) {
+            if (n[i] == 0) continue;
+            e = hipMemcpyAsync(set->own.p + at, sorted[i], sizeof(double) * (size_t)n[i], hipMemcpyHostToDevice, ctx->stream);
+            set->h_table[i].x = set->own.p + at;
+            at += n[i];
+        }
+        if (!rc && e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (rc || e != hipSuccess) {
+            kde_set_free(set);
+            return rc ? rc : fail(GARLIC_ERR_HIP, "KDE part set upload: %s", hipGetErrorString(e));
+        }
+    } else {
+        for (int i = 0; i < n_feeds; i++) set->h_table[i].x = n[i] > 0 ? sorted[i] : nullptr;
+    }
+    *out = set;
+    return GARLIC_OK;
+}
+
+int garlic_lod_kde_part_set(garlic_panel *p, const int32_t *winsizes, const int32_t *steps, int32_t n_sizes, double error,
+                            int32_t max_gap, int32_t use_gl, const int32_t *ind_idx, int32_t n_idx, garlic_kde_part_set **out,
+                            int64_t *chr_counts)
+{
+    if (!p || !out) return fail(GARLIC_ERR_INVALID, "panel and set are required");
+    if (!winsizes || !steps) return fail(GARLIC_ERR_INVALID, "panel, winsizes, steps, feeds, feed_capacity and counts are required");
+    if (n_sizes < 1) return fail(GARLIC_ERR_INVALID, "n_sizes must be >= 1");
+    if (n_sizes > GARLIC_KDE_MAX_FEEDS) return fail(GARLIC_ERR_INVALID, "feed KDE: %d window sizes (1 to %d)", (int)n_sizes, GARLIC_KDE_MAX_FEEDS);
+    garlic_ctx *ctx = p->ctx;
+    int rc;
+    if ((rc = set_device(ctx)) || (rc = ensure_feed_slots(p, n_sizes))) return rc;
+    // as garlic_lod_kde_multi: every size sorted and left in its slot
+    garlic_panel::FeedSink sink(n_sizes);
+    sink.to_slot = true;
+    std::vector<double *> feeds((size_t)n_sizes, nullptr);
+    std::vector<int64_t> cap((size_t)n_sizes, INT64_MAX), counts((size_t)n_sizes, 0);
+    p->feed_sink = &sink;
+    rc = use_gl ? garlic_lod_feed_multi_tgls(p, winsizes, steps, n_sizes, max_gap, ind_idx, n_idx, feeds.data(), cap.data(), counts.data(), chr_counts)
+                : garlic_lod_feed_multi(p, winsizes, steps, n_sizes, error, max_gap, ind_idx, n_idx, feeds.data(), cap.data(), counts.data(),
+                                        chr_counts);
+    p->feed_sink = nullptr;
+    if (rc) return rc;
+    for (int i = 0; i < n_sizes; i++)
+        if (counts[(size_t)i] > 0 && sink.size[(size_t)i].n != counts[(size_t)i])
+            return fail(GARLIC_ERR_STATE, "KDE part set: the feed of size %d (%lld values) was not left on the device", i, (long long)counts[(size_t)i]);
+    garlic_kde_part_set *set = nullptr;
+    if ((rc = kde_set_new(ctx, counts.data(), n_sizes, &set))) return rc;
+    // the set's steps run on the context's stream, behind whatever the sizes' streams still hold
+    for (int i = 0; i < n_sizes; i++) {
+        garlic_panel::FeedSlot &sl = *p->feed_slots[(size_t)i];
+        hipError_t e = hipEventRecord(sl.ev1, sl.stream);
+        if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, sl.ev1, 0);
+        if (e != hipSuccess) {
+            kde_set_free(set);
+            return fail(GARLIC_ERR_HIP, "KDE part set: %s", hipGetErrorString(e));
+        }
+        set->h_table[i].x = counts[(size_t)i] > 0 ? sink.size[(size_t)i].data : nullptr;
+    }
+    set->gen = p->scratch_gen;
+    set->gen_at = *p->scratch_gen;
+    *out = set;
+    return GARLIC_OK;
+}
+
+int garlic_kde_part_set_destroy(garlic_kde_part_set *set)
+{
+    if (!set) return GARLIC_OK;
+    (void)hipSetDevice(set->ctx->device);
+    (void)hipStreamSynchronize(set->ctx->stream);
+    kde_set_free(set);
+    return GARLIC_OK;
+}
+
+int garlic_kde_part_set_counts(garlic_kde_part_set *set, int64_t *n)
+{
+    int rc;
+    if ((rc = kde_set_usable(set))) return rc;
+    if (!n) return fail(GARLIC_ERR_INVALID, "KDE part set: n is NULL");
+    for (int i = 0; i < set->n_feeds; i++) n[i] = set->n[i];
+    return GARLIC_OK;
+}
+
+// The steps in two halves, as a single part's.  active[i] == 0 switches feed i off for this and every later step of the
+// set, up to the next pass 0 (NULL: as it stands).  A set without a value enqueues nothing, the ranks excepted (they read
+// no value, and upload the table themselves: a rank call may be a set's first).
+static void kde_set_activate(garlic_kde_part_set *set, const int32_t *active)
+{
+    for (int i = 0; i < set->n_feeds && active; i++)
+        if (!active[i]) set->h_table[i].active = 0;
+}
+
+static int kde_set_moment_enqueue(garlic_kde_part_set *set, int pass, const double *means, const int32_t *active)
+{
+    int rc;
+    if ((rc = set_device(set->ctx))) return rc;
+    if (pass == 0) {                               // a new KDE: every feed takes part again, the counts of _info start over
+        for (int i = 0; i < set->n_feeds; i++) set->h_table[i].active = 1;
+        set->launches = set->waits = set->rank_rounds = 0;
+    }
+    kde_set_activate(set, active);
+    if (!set->has_values()) return GARLIC_OK;
+    hipStream_t s = set->ctx->stream;
+    for (int i = 0; i < set->n_feeds && pass; i++) set->h_table[i].mom.mean = means[i];
+    HIP_TRY(hipMemcpyAsync(set->table.p, set->h_table, set->table_bytes(), hipMemcpyHostToDevice, s));
+    if (pass == 0) HIP_TRY(hipEventRecord(set->ev[0], s));
+    hipLaunchKernelGGL(kde_moment_set_kernel, dim3((unsigned)set->plan.total_chunks), dim3(KDE_THREADS), 0, s, set->table.p, (int)set->n_feeds,
+                       set->plan.chunk_first, pass, set->partial.p, set->flags.p);
+    hipLaunchKernelGGL(kde_tree_set_kernel, dim3((unsigned)set->n_feeds), dim3(KDE_THREADS), 0, s, set->table.p, pass, set->partial.p, set->flags.p);
+    set->launches += 2;
+    if (pass == 1) HIP_TRY(hipEventRecord(set->ev[1], s));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(set->h_table, set->table.p, set->table_bytes(), hipMemcpyDeviceToHost, s));
+    return GARLIC_OK;
+}
+
+// values[i]: the sum (pass 0) or the squared deviations of feed i's part, 0.0 for an empty part; pass 0: lo / hi its ends and
+// code[i], why[i] what its flags refuse (such a feed is switched off).  A feed that is not active is passed over.
+static int kde_set_moment_wait(garlic_kde_part_set *set, int pass, double *values, double *lo, double *hi, int32_t *code, std::string *why)
+{
+    int rc;
+    if ((rc = set_device(set->ctx))) return rc;
+    if (set->has_values()) {
+        HIP_TRY(hipStreamSynchronize(set->ctx->stream));
+        set->waits++;
+        set->moments_timed = pass == 1;
+    }
+    for (int i = 0; i < set->n_feeds; i++) {
+        KdeFeedDesc &d = set->h_table[i];
+        if (!d.active) continue;
+        if (d.n == 0) {
+            values[i] = 0.0;
+            continue;
+        }
+        if (pass == 0 && (d.mom.flags & (KDE_FLAG_NOT_FINITE | KDE_FLAG_NOT_ASCENDING))) {
+            const int c = d.mom.flags & KDE_FLAG_NOT_FINITE ? fail(GARLIC_ERR_INVALID, "feed KDE: the values hold a NaN or an infinity")
+                                                            : fail(GARLIC_ERR_INVALID, "feed KDE: the values are not in ascending order (garlic_feed_sort)");
+            d.active = 0;
+            if (code) code[i] = c;
+            if (why) why[i] = g_last_error;
+            continue;
+        }
+        values[i] = pass == 0 ? d.mom.sum : d.mom.ssq;
+        if (pass == 0 && lo) lo[i] = d.mom.stat[0];
+        if (pass == 0 && hi) hi[i] = d.mom.stat[1];
+    }
+    return GARLIC_OK;
+}
+
+// keys: [n_feeds][m]
+static int kde_set_rank_enqueue(garlic_kde_part_set *set, const uint64_t *keys, int32_t m)
+{
+    int rc;
+    if ((rc = set_device(set->ctx))) return rc;
+    hipStream_t s = set->ctx->stream;
+    const size_t total = (size_t)set->n_feeds * (size_t)m;
+    for (size_t i = 0; i < total; i++) set->h_keys[i] = keys[i];
+    set->rank_m = m;
+    HIP_TRY(hipMemcpyAsync(set->table.p, set->h_table, set->table_bytes(), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(set->keys.p, set->h_keys, sizeof(unsigned long long) * total, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(kde_rank_multi_kernel, dim3((unsigned)((total + KDE_RANK_SET_THREADS - 1) / KDE_RANK_SET_THREADS)), dim3(KDE_RANK_SET_THREADS),
+                       0, s, set->table.p, (int)set->n_feeds, set->keys.p, (int)m, set->below.p);
+    set->launches++;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(set->h_below, set->below.p, sizeof(long long) * total, hipMemcpyDeviceToHost, s));
+    return GARLIC_OK;
+}
+
+static int kde_set_rank_wait(garlic_kde_part_set *set)      // the counts of the active feeds are in h_below[i * rank_m ..]
+{
+    int rc;
+    if ((rc = set_device(set->ctx))) return rc;
+    HIP_TRY(hipStreamSynchronize(set->ctx->stream));
+    set->waits++;
+    set->rank_rounds++;
+    return GARLIC_OK;
+}
+
+// targets: [n_feeds][512]; inv_h2: [n_feeds] (what an inactive feed's entries hold is not read)
+static int kde_set_sums_enqueue(garlic_kde_part_set *set, const double *targets, const double *inv_h2, const int32_t *active)
+{
+    int rc;
+    if ((rc = set_device(set->ctx))) return rc;
+    kde_set_activate(set, active);
+    if (!set->has_values()) return GARLIC_OK;
+    hipStream_t s = set->ctx->stream;
+    for (int i = 0; i < set->n_feeds; i++) {
+        KdeFeedDesc &d = set->h_table[i];
+        d.skipped = 0;
+        if (!d.active) continue;
+        memcpy(d.targets, targets + (size_t)i * KDE_POINTS, sizeof d.targets);
+        d.inv_h2 = inv_h2[i];
+    }
+    HIP_TRY(hipMemcpyAsync(set->table.p, set->h_table, set->table_bytes(), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(set->ev[2], s));
+    hipLaunchKernelGGL(kde_sum_multi_kernel, dim3((unsigned)set->plan.total_slices), dim3(KDE_THREADS), 0, s, set->table.p, (int)set->n_feeds,
+                       set->plan.slice_first, set->slices.p);
+    hipLaunchKernelGGL(kde_slice_sum_multi_kernel, dim3((unsigned)set->n_feeds * KDE_POINTS), dim3(KDE_THREADS), 0, s, set->table.p, set->slices.p);
+    set->launches += 2;
+    HIP_TRY(hipEventRecord(set->ev[3], s));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(set->h_table, set->table.p, set->table_bytes(), hipMemcpyDeviceToHost, s));
+    return GARLIC_OK;
+}
+
+static int kde_set_sums_wait(garlic_kde_part_set *set)      // feed i's undivided sums are in h_table[i].raw (zeros for an empty part)
+{
+    int rc;
+    if ((rc = set_device(set->ctx))) return rc;
+    set->moments_ms = set->sums_ms = 0.f;
+    if (set->has_values()) {
+        HIP_TRY(hipStreamSynchronize(set->ctx->stream));
+        set->waits++;
+        if (set->moments_timed && hipEventElapsedTime(&set->moments_ms, set->ev[0], set->ev[1]) != hipSuccess) set->moments_ms = 0.f;
+        if (hipEventElapsedTime(&set->sums_ms, set->ev[2], set->ev[3]) != hipSuccess) set->sums_ms = 0.f;
+    }
+    for (int i = 0; i < set->n_feeds; i++) {
+        KdeFeedDesc &d = set->h_table[i];
+        if (d.active && d.n == 0) memset(d.raw, 0, sizeof d.raw);
+    }
+    return GARLIC_OK;
+}
+
+// status of a step call: on entry a nonzero status[i] switches feed i off, on return it holds what this set refuses of it
+static void kde_set_status_in(const garlic_kde_part_set *set, const int32_t *status, int32_t *active)
+{
+    for (int i = 0; i < set->n_feeds; i++) active[i] = !(status && status[i]);
+}
+
+int garlic_kde_part_set_moment(garlic_kde_part_set *set, int32_t pass, const double *means, double *values, double *lo, double *hi,
+                               int32_t *status)
+{
+    int rc;
+    if ((rc = kde_set_usable(set))) return rc;
+    if (pass != 0 && pass != 1) return fail(GARLIC_ERR_INVALID, "KDE part set: pass must be 0 (sums) or 1 (squared deviations), got %d", (int)pass);
+    if (!values || (pass == 1 && !means)) return fail(GARLIC_ERR_INVALID, "KDE part set: values and, for pass 1, means are required");
+    int32_t active[GARLIC_KDE_MAX_FEEDS], code[GARLIC_KDE_MAX_FEEDS] = {};
+    std::string why[GARLIC_KDE_MAX_FEEDS];
+    kde_set_status_in(set, status, active);
+    if ((rc = kde_set_moment_enqueue(set, pass, means, active)) || (rc = kde_set_moment_wait(set, pass, values, lo, hi, code, why))) return rc;
+    for (int i = 0; i < set->n_feeds; i++) {
+        if (!code[i]) continue;
+        if (!status) return fail(code[i], "feed %d: %s", i, why[i].c_str());
+        status[i] = code[i];
+    }
+    for (int i = set->n_feeds - 1; i >= 0; i--)
+        if (code[i]) (void)fail(code[i], "feed %d: %s", i, why[i].c_str());      // (the text names the lowest refused feed)
+    return GARLIC_OK;
+}
+
+int garlic_kde_part_set_rank(garlic_kde_part_set *set, const uint64_t *keys, int32_t m, int64_t *below)
+{
+    int rc;
+    if ((rc = kde_set_usable(set))) return rc;
+    if (m < 1 || m > KDE_RANK_MAX) return fail(GARLIC_ERR_INVALID, "KDE part set: %d probe keys per feed (1 to %d)", (int)m, KDE_RANK_MAX);
+    if (!keys || !below) return fail(GARLIC_ERR_INVALID, "KDE part set: keys and below are required");
+    if ((rc = kde_set_rank_enqueue(set, keys, m)) || (rc = kde_set_rank_wait(set))) return rc;
+    for (int i = 0; i < set->n_feeds; i++) {
+        if (!set->h_table[i].active) continue;
+        for (int j = 0; j < m; j++) below[(size_t)i * m + j] = set->h_below[(size_t)i * m + j];
+    }
+    return GARLIC_OK;
+}
+
+int garlic_kde_part_set_sums(garlic_kde_part_set *set, const double *targets, const double *h, const int32_t *active, double *sums,
+                             int64_t *pairs_skipped)
+{
+    int rc;
+    if ((rc = kde_set_usable(set))) return rc;
+    if (!targets || !h || !sums) return fail(GARLIC_ERR_INVALID, "KDE part set: targets, h and sums are required");
+    kde_set_activate(set, active);
+    double inv_h2[GARLIC_KDE_MAX_FEEDS] = {};
+    for (int i = 0; i < set->n_feeds; i++) {
+        if (!set->h_table[i].active) continue;
+        inv_h2[i] = 1.0 / (h[i] * h[i]);
+        if (!(h[i] > 0) || !std::isfinite(inv_h2[i]))
+            return fail(GARLIC_ERR_INVALID, "feed %d: feed KDE: bandwidth %g cannot be used (zero, negative, not finite or too small to square)", i, h[i]);
+    }
+    if ((rc = kde_set_sums_enqueue(set, targets, inv_h2, nullptr)) || (rc = kde_set_sums_wait(set))) return rc;
+    for (int i = 0; i < set->n_feeds; i++) {
+        const KdeFeedDesc &d = set->h_table[i];
+        if (!d.active) continue;
+        memcpy(sums + (size_t)i * KDE_POINTS, d.raw, sizeof d.raw);
+        if (pairs_skipped) pairs_skipped[i] = (int64_t)d.skipped;
+    }
+    return GARLIC_OK;
+}
+
+int garlic_kde_parts_multi(garlic_kde_part_set *const *sets, int32_t n_sets, garlic_kde *outs, int32_t *status)
+{
+    namespace gh = garlic_host;
+    if (!sets || !outs) return fail(GARLIC_ERR_INVALID, "KDE parts: sets and outs are required");
+    if (n_sets < 1 || n_sets > GARLIC_KDE_MAX_PARTS) return fail(GARLIC_ERR_INVALID, "KDE parts: %d sets (1 to %d)", (int)n_sets, GARLIC_KDE_MAX_PARTS);
+    int rc;
+    for (int p = 0; p < n_sets; p++) {
+        if (!sets[p]) return fail(GARLIC_ERR_INVALID, "KDE parts: set %d is NULL", p);
+        for (int q = 0; q < p; q++)
+            if (sets[q] == sets[p]) return fail(GARLIC_ERR_INVALID, "KDE parts: set %d is set %d again", p, q);
+        if ((rc = kde_set_usable(sets[p]))) return rc;
+        if (sets[p]->n_feeds != sets[0]->n_feeds)
+            return fail(GARLIC_ERR_INVALID, "KDE parts: set %d holds %d feeds, set 0 holds %d", p, (int)sets[p]->n_feeds, (int)sets[0]->n_feeds);
+    }
+    const int F = sets[0]->n_feeds;
+    const size_t nF = (size_t)F, nP = (size_t)n_sets;
+    // per feed: the code and the words of its refusal, what the steps gave
+    std::vector<int32_t> code(nF, GARLIC_OK), active(nF, 1);
+    std::vector<std::string> why(nF);
+    std::vector<garlic_kde> res(nF);
+    std::vector<int64_t> n(nF, 0);
+    auto first_refused = [&]() {
+        for (int i = 0; i < F; i++)
+            if (code[(size_t)i]) return i;
+        return -1;
+    };
+    auto report = [&]() {
+        const int i = first_refused();
+        return i < 0 ? (int)GARLIC_OK : fail(code[(size_t)i], "feed %d: %s", i, why[(size_t)i].c_str());
+    };
+    auto refuse = [&](int i, int c, const std::string &words) {
+        code[(size_t)i] = c;
+        why[(size_t)i] = words;
+        active[(size_t)i] = 0;
+    };
+    for (int i = 0; i < F; i++) {
+        for (int p = 0; p < n_sets; p++) n[(size_t)i] += sets[p]->n[i];
+        if (n[(size_t)i] < 2) {
+            const int c = fail(GARLIC_ERR_INVALID, "feed KDE: needs at least 2 values (the parts hold %lld)", (long long)n[(size_t)i]);
+            refuse(i, c, g_last_error);
+        }
+    }
+    if (status == nullptr && (rc = report())) return rc;
+    // a step on every set: all enqueued, then all waited for (the first error is the one returned)
+    auto each = [&](auto enqueue, auto wait) {
+        int first = GARLIC_OK;
+        int enqueued = 0;
+        for (; enqueued < n_sets && !first; enqueued++) first = enqueue(sets[enqueued], enqueued);
+        for (int p = 0; p < (first ? enqueued - 1 : enqueued); p++) {
+            const int r = wait(sets[p], p);
+            if (r && !first) first = r;
+        }
+        return first;
+    };
+    // pass 0: the parts' sums, ends and flags
+    std::vector<double> value(nP * nF, 0.0), lo(nF, 0.0), hi(nF, 0.0), mean(nF, 0.0);
+    std::vector<uint64_t> lo_key(nF, 0), hi_key(nF, 0);
+    std::vector<char> have_ends(nF, 0);
+    if ((rc = each([&](garlic_kde_part_set *set, int) { return kde_set_moment_enqueue(set, 0, nullptr, active.data()); },
+                   [&](garlic_kde_part_set *set, int p) {
+                       std::vector<int32_t> c(nF, GARLIC_OK);
+                       std::vector<std::string> w(nF);
+                       const int r2 = kde_set_moment_wait(set, 0, &value[(size_t)p * nF], lo.data(), hi.data(), c.data(), w.data());
+                       for (int i = 0; i < F && !r2; i++) {
+                           if (c[(size_t)i] && !code[(size_t)i]) {
+                               code[(size_t)i] = c[(size_t)i];
+                               why[(size_t)i] = "set " + std::to_string(p) + ": " + w[(size_t)i];
+                           }
+                           if (c[(size_t)i] || !set->h_table[i].active || set->n[i] == 0) continue;
+                           const uint64_t kl = gh::kdeKey(lo[(size_t)i]), kh = gh::kdeKey(hi[(size_t)i]);
+                           if (!have_ends[(size_t)i] || kl < lo_key[(size_t)i]) lo_key[(size_t)i] = kl;
+                           if (!have_ends[(size_t)i] || kh > hi_key[(size_t)i]) hi_key[(size_t)i] = kh;
+                           have_ends[(size_t)i] = 1;
+                       }
+                       return r2;
+                   })))
+        return rc;
+    for (int i = 0; i < F; i++)
+        if (code[(size_t)i]) active[(size_t)i] = 0;
+    if (status == nullptr && (rc = report())) return rc;
+    std::vector<double> of_feed(nP);
+    auto combine = [&](int i) {
+        for (int p = 0; p < n_sets; p++) of_feed[(size_t)p] = value[(size_t)p * nF + (size_t)i];
+        return gh::kdeCombine(of_feed.data(), n_sets);
+    };
+    for (int i = 0; i < F; i++) {
+        if (!active[(size_t)i]) continue;
+        garlic_kde &r = res[(size_t)i];
+        r.n = n[(size_t)i];
+        r.lo = gh::kdeKeyValue(lo_key[(size_t)i]);
+        r.hi = gh::kdeKeyValue(hi_key[(size_t)i]);
+        mean[(size_t)i] = combine(i) / (double)r.n;
+    }
+    // pass 1 about the unions' means
+    if ((rc = each([&](garlic_kde_part_set *set, int) { return kde_set_moment_enqueue(set, 1, mean.data(), active.data()); },
+                   [&](garlic_kde_part_set *set, int p) {
+                       return kde_set_moment_wait(set, 1, &value[(size_t)p * nF], nullptr, nullptr, nullptr, nullptr);
+                   })))
+        return rc;
+    // the four order statistics of every union: one descent, eight rounds
+    std::vector<int64_t> rank(nF * 4, 0), k25(nF, 0), k75(nF, 0);
+    std::vector<double> delta25(nF, 0.0), delta75(nF, 0.0), stat(nF * 4, 0.0);
+    std::vector<uint8_t> descend(nF, 0);
+    for (int i = 0; i < F; i++) {
+        if (!active[(size_t)i]) continue;
+        garlic_kde &r = res[(size_t)i];
+        r.sd = sqrt(combine(i) / (double)(r.n - 1));
+        gh::kdeQuantileIndex(r.n, 0.25, &k25[(size_t)i], &delta25[(size_t)i]);
+        gh::kdeQuantileIndex(r.n, 0.75, &k75[(size_t)i], &delta75[(size_t)i]);
+        const int64_t at[4] = {k25[(size_t)i], k25[(size_t)i] + 1, k75[(size_t)i], k75[(size_t)i] + 1};
+        for (int q = 0; q < 4; q++) rank[(size_t)i * 4 + q] = at[q] < 0 ? 0 : (at[q] >= r.n ? r.n - 1 : at[q]);
+        descend[(size_t)i] = 1;
+    }
+    int rounds = 0;
+    const bool any_active = std::find(active.begin(), active.end(), 1) != active.end();
+    if (any_active) {
+        rc = gh::kdeSelectRanksMulti(F, rank.data(), descend.data(), [&](const uint64_t *probes, int m, int64_t *below) {
+            for (size_t i = 0; i < nF * (size_t)m; i++) below[i] = 0;
+            return each([&](garlic_kde_part_set *set, int) { return kde_set_rank_enqueue(set, probes, m); },
+                        [&](garlic_kde_part_set *set, int) {
+                            const int r2 = kde_set_rank_wait(set);
+                            for (int i = 0; i < F && !r2; i++) {
+                                if (!active[(size_t)i]) continue;
+                                for (int j = 0; j < m; j++) below[(size_t)i * m + j] += set->h_below[(size_t)i * m + j];
+                            }
+                            return r2;
+                        });
+        }, stat.data(), &rounds);
+        if (rc) return rc;
+    }
+    // every h and every target set
+    std::vector<double> targets(nF * KDE_POINTS, 0.0), inv_h2(nF, 0.0);
+    for (int i = 0; i < F; i++) {
+        if (!active[(size_t)i]) continue;
+        garlic_kde &r = res[(size_t)i];
+        const double *st = &stat[(size_t)i * 4];
+        r.q25 = k25[(size_t)i] >= r.n - 1 ? st[0] : gh::kdeQuantileMix(st[0], st[1], delta25[(size_t)i]);
+        r.q75 = k75[(size_t)i] >= r.n - 1 ? st[2] : gh::kdeQuantileMix(st[2], st[3], delta75[(size_t)i]);
+        r.h = gh::kdeBandwidth(r.sd, r.q25, r.q75, r.n);
+        if (!(r.h > 0) || !std::isfinite(r.h)) {
+            const int c = fail(GARLIC_ERR_INVALID, "feed KDE: bandwidth %g (sd %g, quartiles %g and %g): all values equal, or no spread between the quartiles",
+                               r.h, r.sd, r.q25, r.q75);
+            refuse(i, c, g_last_error);
+            continue;
+        }
+        gh::kdeTargets(r.lo, r.hi, r.h, r.x);
+        inv_h2[(size_t)i] = 1.0 / (r.h * r.h);
+        if (!std::isfinite(inv_h2[(size_t)i])) {
+            const int c = fail(GARLIC_ERR_INVALID, "feed KDE: bandwidth %g is too small to square", r.h);
+            refuse(i, c, g_last_error);
+            continue;
+        }
+        memcpy(&targets[(size_t)i * KDE_POINTS], r.x, sizeof r.x);
+    }
+    if (status == nullptr && (rc = report())) return rc;
+    if (std::find(active.begin(), active.end(), 1) != active.end()) {
+        if ((rc = each([&](garlic_kde_part_set *set, int) { return kde_set_sums_enqueue(set, targets.data(), inv_h2.data(), active.data()); },
+                       [&](garlic_kde_part_set *set, int) { return kde_set_sums_wait(set); })))
+            return rc;
+    }
+    std::vector<const double *> sums(nP);
+    for (int i = 0; i < F; i++) {
+        if (status) status[i] = code[(size_t)i];
+        if (code[(size_t)i]) continue;
+        garlic_kde &r = res[(size_t)i];
+        for (int p = 0; p < n_sets; p++) sums[(size_t)p] = sets[p]->h_table[i].raw;
+        gh::kdeCombineSums(sums.data(), n_sets, KDE_POINTS, r.n, r.raw);
+        gh::kdeNormalise(r.raw, r.x, r.y);
+        outs[i] = r;
+    }
+    (void)report();                                // (status given: the call ran; the text names the lowest refused feed)
+    return GARLIC_OK;
+}
+
+int garlic_kde_parts_multi_info(garlic_kde_part_set *const *sets, int32_t n_sets, int64_t *chunks, int64_t *pairs_skipped,
+                                int32_t *kernel_launches, int32_t *host_waits, int32_t *rank_rounds, float *moments_ms, float *sums_ms)
+{
+    if (!sets) return fail(GARLIC_ERR_INVALID, "KDE parts: sets is NULL");
+    if (n_sets < 1 || n_sets > GARLIC_KDE_MAX_PARTS) return fail(GARLIC_ERR_INVALID, "KDE parts: %d sets (1 to %d)", (int)n_sets, GARLIC_KDE_MAX_PARTS);
+    for (int p = 0; p < n_sets; p++) {
+        if (!sets[p]) return fail(GARLIC_ERR_INVALID, "KDE parts: set %d is NULL", p);
+        const int rc = kde_set_usable(sets[p]);
+        if (rc) return rc;
+        if (sets[p]->n_feeds != sets[0]->n_feeds)
+            return fail(GARLIC_ERR_INVALID, "KDE parts: set %d holds %d feeds, set 0 holds %d", p, (int)sets[p]->n_feeds, (int)sets[0]->n_feeds);
+        const size_t row = (size_t)p * (size_t)sets[0]->n_feeds;
+        for (int i = 0; i < sets[p]->n_feeds; i++) {
+            const KdeFeedDesc &d = sets[p]->h_table[i];
+            if (chunks) chunks[row + (size_t)i] = d.n_chunks;
+            if (pairs_skipped) pairs_skipped[row + (size_t)i] = d.active ? (int64_t)d.skipped : 0;
+        }
+        if (kernel_launches) kernel_launches[p] = sets[p]->launches;
+        if (host_waits) host_waits[p] = sets[p]->waits;
+        if (rank_rounds) rank_rounds[p] = sets[p]->rank_rounds;
+        if (moments_ms) moments_ms[p] = sets[p]->moments_ms;
+        if (sums_ms) sums_ms[p] = sets[p]->sums_ms;
+    }
     return GARLIC_OK;
 }
 

@@ -255,9 +255,20 @@ __device__ __forceinline__ unsigned long long kde_key(double v)
     return b ^ (b >> 63 ? 0xFFFFFFFFFFFFFFFFull : 0x8000000000000000ull);
 }
 
-// thread t: below[t] = how many of x[0 .. n) have a key below keys[t] (x ascending in key order: a lower bound).  One
-// binary search per thread, about log2(n) dependent loads: latency-bound, a launch holds at most KDE_RANK_MAX probes.
-// mid < hi <= n, so no read leaves the array; n = 0 reads nothing.
+// how many of x[0 .. n) have a key below `key` (x ascending in key order: a lower bound).  About log2(n) dependent loads.
+// mid < hi <= n, so no read leaves the array; n = 0 reads nothing.  (kde_rank_kernel; kde_rank_multi_kernel on a feed of a set)
+__device__ __forceinline__ int64_t kde_rank_below(const double *x, int64_t n, unsigned long long key)
+{
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        if (kde_key(x[mid]) < key) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// thread t: below[t] = kde_rank_below of keys[t].  One binary search per thread: latency-bound, a launch holds at most
+// KDE_RANK_MAX probes.
 constexpr int KDE_RANK_MAX = 1024;
 
 __global__ void __launch_bounds__(KDE_THREADS)
@@ -265,13 +276,7 @@ kde_rank_kernel(const double *x, int64_t n, const unsigned long long *keys, int 
 {
     const int t = blockIdx.x * KDE_THREADS + threadIdx.x;
     if (t >= m) return;
-    const unsigned long long key = keys[t];
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = lo + (hi - lo) / 2;
-        if (kde_key(x[mid]) < key) lo = mid + 1; else hi = mid;
-    }
-    below[t] = lo;
+    below[t] = kde_rank_below(x, n, keys[t]);
 }
 
 } // namespace garlic

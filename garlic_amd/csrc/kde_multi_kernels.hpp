@@ -13,6 +13,8 @@
 //     feed's pointers and the workgroup's place in the feed.  A feed's result does not depend on what else is in the batch.
 //   * a feed that is not active (fewer than 2 values; refused after the moments) takes no part in the sums launches: its
 //     workgroups leave before the first barrier.  No floating-point atomics.
+//   * kde_rank_multi_kernel: the rank queries of F feeds in one launch, for the feeds of a part set (kde_part_set_kernels.hpp,
+//     which also runs kde_sum_multi_kernel as it stands).
 #pragma once
 #include "kde_kernels.hpp"
 #include "../host/kde_multi_plan.hpp"
@@ -78,6 +80,26 @@ kde_slice_multi_kernel(KdeFeedDesc *feeds, const double *slices)
     if (!d.active) return;
     const double total = kde_slice_total(slices + d.slice_off * KDE_POINTS, d.n_slices, target);
     if (threadIdx.x == 0) d.raw[target] = total / (double)d.n;
+}
+
+// ---- The ranks of a part set's descent (garlic_kde_part_set_rank; the other kernels of a set: kde_part_set_kernels.hpp).
+// thread t: probe t % m of feed t / m: below[t] = kde_rank_below on that feed's x, n (n = 0 reads nothing; a feed that is
+// not active is not searched and its counts are left as they were).  Every thread is a chain of about log2(n) dependent
+// loads with next to no arithmetic between them, so what a launch takes is one chain's latency as long as every wave
+// has a SIMD to itself: workgroups of one wave, which the dispatcher spreads over the CUs -- 16 waves for one feed, 512
+// for 32 feeds, on 1024 SIMDs.  Blocks of 256 threads would put four chains' waves on one CU and leave the CUs beside it
+// idle for the same latency, no faster; registers and LDS do not limit anything here.  Neighbouring lanes hold
+// neighbouring digits of one rank's probe, so the first steps of their searches load the same lines.
+constexpr int KDE_RANK_SET_THREADS = 64;
+
+__global__ void __launch_bounds__(KDE_RANK_SET_THREADS)
+kde_rank_multi_kernel(const KdeFeedDesc *feeds, int n_feeds, const unsigned long long *keys, int m, long long *below)
+{
+    const int t = blockIdx.x * KDE_RANK_SET_THREADS + threadIdx.x;
+    if (t >= n_feeds * m) return;
+    const KdeFeedDesc &d = feeds[t / m];
+    if (!d.active) return;
+    below[t] = kde_rank_below(d.x, d.n, keys[t]);
 }
 
 } // namespace garlic

@@ -1216,6 +1216,7 @@ struct LodEngine::Impl {
     int nind = 0;
     bool use_gl = false;
     bool have_phase = false;   // every HapData carries firstCopy: the panels hold the phase planes
+    int kde_multi_shards = 0;  // LodEngine::kdeMultiShards
 };
 
 LodEngine::LodEngine(std::vector<HapData *> *haps, std::vector<FreqData *> *freqs, std::vector<MapData *> *maps,
@@ -1674,7 +1675,11 @@ KdeData LodEngine::lodKde(int winsize, double error, int MAX_GAP, int step, bool
     return result();
 }
 
-bool LodEngine::kdeMultiInOneCall() const { return impl->shards.size() == 1 && !g_options.kde_on_shards; }
+// one shard on one device (garlic_lod_kde_multi), or LodOptions::kde_on_shards on any number of shards (one
+// garlic_kde_part_set per shard, garlic_kde_parts_multi)
+bool LodEngine::kdeMultiInOneCall() const { return impl->shards.size() == 1 || g_options.kde_on_shards; }
+
+int LodEngine::kdeMultiShards() const { return impl->kde_multi_shards; }
 
 std::vector<KdeData> LodEngine::lodKdeMulti(const std::vector<int> &winsizes, double error, int MAX_GAP, const std::vector<int> *steps,
                                             const std::vector<int> *kdeSubsample, std::vector<int> *status)
@@ -1685,8 +1690,60 @@ std::vector<KdeData> LodEngine::lodKdeMulti(const std::vector<int> &winsizes, do
     for (size_t i = 0; i < m; i++) st[i] = steps ? (*steps)[i] : winsizes[i];
     if (status) status->assign(m, 0);
     static_assert(KDE_MAX_FEEDS == GARLIC_KDE_MAX_FEEDS, "one limit");
+    impl->kde_multi_shards = 0;
     if (!kdeMultiInOneCall() || m > (size_t)GARLIC_KDE_MAX_FEEDS) {
         for (size_t i = 0; i < m; i++) out[i] = lodKde(winsizes[i], error, MAX_GAP, st[i], false, 0, 0.0, kdeSubsample);
+        return out;
+    }
+    if (m == 0) return out;
+    if (g_options.kde_on_shards) {
+        // lodKde's sharded path for all sizes at once: every shard with KDE individuals leaves the sorted feeds of all sizes
+        // on its device as one garlic_kde_part_set (on the shards' threads), garlic_kde_parts_multi reduces them where they lie
+        const bool subset = kdeSubsample && !kdeSubsample->empty();
+        if (subset)
+            for (size_t i = 1; i < kdeSubsample->size(); i++)
+                if ((*kdeSubsample)[i] <= (*kdeSubsample)[i - 1]) fail("KDE subsample must be in increasing order");
+        const size_t ns = impl->shards.size();
+        std::cerr << "Calculating LOD scores with winsizes";
+        for (size_t i = 0; i < m; i++) std::cerr << (i ? ", " : " ") << winsizes[i];
+        std::cerr << " (thinned on the devices, KDE of all sizes on the shards in one call).\n";
+        std::vector<int32_t> sizes(winsizes.begin(), winsizes.end()), code(m, 0);
+        std::vector<garlic_kde_part_set *> made(ns, nullptr);
+        std::vector<std::string> errors(ns);
+        std::vector<std::thread> th;
+        for (size_t k = 0; k < ns; k++)
+            th.emplace_back([&, k] {
+                auto &s = impl->shards[k];
+                std::vector<int32_t> mine;
+                if (subset) {
+                    for (int g : *kdeSubsample)
+                        if (g >= s.ind_begin && g < s.ind_begin + s.nind) mine.push_back(g - s.ind_begin);
+                    if (mine.empty()) return;          // no listed individual lives here: no set
+                }
+                if (garlic_lod_kde_part_set(s.panel, sizes.data(), st.data(), (int32_t)m, error, MAX_GAP, impl->use_gl, subset ? mine.data() : nullptr,
+                                            (int32_t)mine.size(), &made[k], nullptr) != GARLIC_OK)
+                    errors[k] = garlic_hip_last_error();
+            });
+        for (auto &t : th) t.join();
+        std::vector<garlic_kde_part_set *> sets;
+        for (garlic_kde_part_set *p : made)
+            if (p) sets.push_back(p);
+        std::string error_text;
+        for (auto &e : errors)
+            if (!e.empty() && error_text.empty()) error_text = "garlic_lod_kde_part_set: " + e;
+        std::vector<garlic_kde> gk(m);
+        if (error_text.empty()) {
+            if (sets.empty()) error_text = "garlic_kde_parts_multi: no shard holds a KDE individual";
+            else if (garlic_kde_parts_multi(sets.data(), (int32_t)sets.size(), gk.data(), status ? code.data() : nullptr) != GARLIC_OK)
+                error_text = std::string("garlic_kde_parts_multi: ") + garlic_hip_last_error();
+        }
+        impl->kde_multi_shards = (int)sets.size();
+        for (garlic_kde_part_set *p : sets) garlic_kde_part_set_destroy(p);
+        if (!error_text.empty()) fail(error_text);
+        for (size_t i = 0; i < m; i++) {
+            if (status) (*status)[i] = code[i];
+            if (!code[i]) memcpy(&out[i], &gk[i], sizeof out[i]);
+        }
         return out;
     }
     if (m == 0) return out;

@@ -371,11 +371,15 @@ public:
     // lodKde of several window sizes of a sweep (unweighted scores; steps NULL: the sizes).  One shard on one device: one
     // garlic_lod_kde_multi -- one pass over the panel for all feeds, six KDE launches and two waits for all sizes -- and
     // every result equals lodKde's bit for bit.  status given: status->at(i) != 0 marks a size the library refused (its
-    // result is not set; lodKde of that size says why), the others stand; NULL: any refused size fails the call.  Several
-    // shards or devices (kdeMultiInOneCall() false): a loop over lodKde, which fails at the first refused size.
+    // result is not set; lodKde of that size says why), the others stand; NULL: any refused size fails the call.
+    // LodOptions::kde_on_shards, any number of shards: one garlic_lod_kde_part_set per shard that holds KDE individuals and
+    // one garlic_kde_parts_multi -- every result equals the sharded lodKde's bit for bit, status as above; the caller prints
+    // lodKde's "KDE on <P> shards" per size it uses, <P> = kdeMultiShards().  Several shards without kde_on_shards, or more sizes
+    // than KDE_MAX_FEEDS (kdeMultiInOneCall() false): a loop over lodKde, which fails at the first refused size.
     std::vector<KdeData> lodKdeMulti(const std::vector<int> &winsizes, double error, int MAX_GAP, const std::vector<int> *steps = nullptr,
                                      const std::vector<int> *kdeSubsample = nullptr, std::vector<int> *status = nullptr);
     bool kdeMultiInOneCall() const;
+    int kdeMultiShards() const;      // the shards the last lodKdeMulti reduced on their devices (0: it took another path)
     // several window sizes in one call (unweighted --error scores): the feeds of exploreWinsizes / selectWinsize /
     // selectWinsizeFromList (garlic-roh.cpp:726-751, 798-837, 881-920), one DoubleData per size; steps NULL: the sizes
     std::vector<DoubleData *> lodFeedMulti(const std::vector<int> &winsizes, double error, int MAX_GAP,

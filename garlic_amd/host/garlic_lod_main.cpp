@@ -415,7 +415,8 @@ int main(int argc, char **argv)
                 std::cerr << "Selected LOD score cutoff: " << cutoff << "\n";
                 if (!a.size_bounds.empty() || a.nclust) roh_calls_at(W, single_out, a.have_cutoff ? a.lod_cutoff : cutoff);
             };
-            // Unweighted sweeps on one device: the KDEs of several sizes from one call (LodEngine::lodKdeMulti) -- a whole
+            // Unweighted sweeps on one device, or under --kde-sharded on any number of shards: the KDEs of several sizes from
+            // one call (LodEngine::lodKdeMulti) -- a whole
             // --winsize-multi list, or the next SWEEP_BATCH sizes of the stepping search, where the sizes past the selected
             // one are computed ahead of need: one that the library refuses fails the run only when the loop reaches it, with
             // the per-size call's message.  GARLIC_KDE_MULTI_OFF: the per-size loop (same files, same selection lines).
@@ -431,6 +432,7 @@ int main(int argc, char **argv)
             };
             auto from_batch = [&](size_t j) -> KdeData {
                 if (batch_status[j]) return kde_of(batch_sizes[j]);      // refused: the per-size call says why, and fails
+                if (engine.kdeMultiShards()) std::cerr << "KDE on " << engine.kdeMultiShards() << " shards\n";      // as lodKde, per size used
                 return batch[j];
             };
             if (!a.auto_winsize) {

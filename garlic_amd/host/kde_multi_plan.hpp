@@ -4,7 +4,8 @@
 //
 //   * a feed of n >= 2 values has ceil(n / 2048) chunks, kde_chunks_per_slice(chunks) chunks per slice and
 //     ceil(chunks / chunks_per_slice) <= 2048 slices: exactly the partition of the single-feed call, so a feed's sums are
-//     added in the single call's order.  A feed of fewer than 2 values (refused before anything runs) has none.
+//     added in the single call's order.  A feed of fewer than 2 values (refused before anything runs) has none.  The
+//     feeds of a part set (kdePartSetPlan) are parts of unions: there one value is a chunk, and only an empty part has none.
 //   * the launches are flat: workgroup b of the moment launch is chunk (b - chunk_first[f]) of the feed f with
 //     chunk_first[f] <= b < chunk_first[f + 1]; the sums launch likewise over slice_first.  The tables are exclusive
 //     prefix sums with the total at [n_feeds], padded with the total up to [KDE_MULTI_MAX_FEEDS]; kdeMultiFind is the
@@ -54,15 +55,16 @@ GARLIC_KDE_PLAN_FN int kdeMultiFind(const KdeMultiFirst &first, int n_feeds, int
     return f;
 }
 
-// false: n_feeds out of range, or more chunks than one launch holds (nothing usable in *plan then)
-inline bool kdeMultiPlan(const int64_t *n, int n_feeds, KdeMultiPlan *plan)
+// false: n_feeds out of range, or more chunks than one launch holds (nothing usable in *plan then).  min_n: the fewest
+// values with which a feed takes part
+inline bool kdeMultiPlanFrom(const int64_t *n, int n_feeds, int64_t min_n, KdeMultiPlan *plan)
 {
     if (n_feeds < 1 || n_feeds > KDE_MULTI_MAX_FEEDS) return false;
     plan->n_feeds = n_feeds;
     int64_t chunks = 0, slices = 0;
     for (int f = 0; f < n_feeds; f++) {
         KdeMultiFeedPlan &p = plan->feed[f];
-        p.n = n[f] >= 2 ? n[f] : 0;
+        p.n = n[f] >= min_n ? n[f] : 0;
         p.n_chunks = p.n / KDE_MULTI_CHUNK + (p.n % KDE_MULTI_CHUNK != 0);
         p.chunks_per_slice = (p.n_chunks + KDE_MULTI_MAX_SLICES - 1) / KDE_MULTI_MAX_SLICES;
         p.n_slices = p.chunks_per_slice ? (p.n_chunks + p.chunks_per_slice - 1) / p.chunks_per_slice : 0;
@@ -80,5 +82,11 @@ inline bool kdeMultiPlan(const int64_t *n, int n_feeds, KdeMultiPlan *plan)
     plan->total_slices = slices;
     return true;
 }
+
+// whole feeds (garlic_feed_kde_multi): a KDE needs 2 values
+inline bool kdeMultiPlan(const int64_t *n, int n_feeds, KdeMultiPlan *plan) { return kdeMultiPlanFrom(n, n_feeds, 2, plan); }
+
+// the feeds of one shard (garlic_kde_part_set): a part of one value takes part, the union has the others
+inline bool kdePartSetPlan(const int64_t *n, int n_feeds, KdeMultiPlan *plan) { return kdeMultiPlanFrom(n, n_feeds, 1, plan); }
 
 } // namespace garlic_host

@@ -8,6 +8,7 @@
 
 #include <cstdint>
 #include <cstring>
+#include <vector>
 
 namespace garlic_host {
 
@@ -72,6 +73,34 @@ inline int kdeSelectRanks(const int64_t *rank, RankBelow rank_below, double *val
         kdeDescentChoose(prefix, round, rank, below);
     }
     for (int q = 0; q < KDE_DESCENT_RANKS; q++) value[q] = kdeKeyValue(prefix[q]);
+    return 0;
+}
+
+// The same descent for n_feeds unions at once (garlic_kde_parts_multi): feed f has the ranks rank[4 f .. 4 f + 4) and gets
+// value[4 f .. 4 f + 4).  One rank query per round carries every feed's probes, feed f's at probes[1024 f ..], and
+// fills below likewise: eight queries in all, not eight per feed.  A feed with active[f] == 0 is carried along: its
+// probes are zeros, its counts are not read, its values are not written.  Every feed's probes and choices are
+// kdeDescentProbes and kdeDescentChoose on its own prefixes, so its values are kdeSelectRanks's whatever else is in the batch.
+template <class RankBelow>
+inline int kdeSelectRanksMulti(int n_feeds, const int64_t *rank, const uint8_t *active, RankBelow rank_below, double *value, int *rounds)
+{
+    std::vector<uint64_t> prefix((size_t)n_feeds * KDE_DESCENT_RANKS, 0), probes((size_t)n_feeds * KDE_DESCENT_PROBES, 0);
+    std::vector<int64_t> below((size_t)n_feeds * KDE_DESCENT_PROBES, 0);
+    if (rounds) *rounds = 0;
+    for (int round = 0; round < KDE_DESCENT_ROUNDS; round++) {
+        for (int f = 0; f < n_feeds; f++)
+            if (active[f]) kdeDescentProbes(&prefix[(size_t)f * KDE_DESCENT_RANKS], round, &probes[(size_t)f * KDE_DESCENT_PROBES]);
+        const int rc = rank_below(probes.data(), KDE_DESCENT_PROBES, below.data());
+        if (rc) return rc;
+        if (rounds) ++*rounds;
+        for (int f = 0; f < n_feeds; f++)
+            if (active[f])
+                kdeDescentChoose(&prefix[(size_t)f * KDE_DESCENT_RANKS], round, rank + (size_t)f * KDE_DESCENT_RANKS,
+                                 &below[(size_t)f * KDE_DESCENT_PROBES]);
+    }
+    for (int f = 0; f < n_feeds; f++)
+        for (int q = 0; q < KDE_DESCENT_RANKS && active[f]; q++)
+            value[(size_t)f * KDE_DESCENT_RANKS + q] = kdeKeyValue(prefix[(size_t)f * KDE_DESCENT_RANKS + q]);
     return 0;
 }
 

@@ -131,15 +131,28 @@ def merge_sorted_feeds(feeds):
     return out
 
 
-def lod_kde(ctx, panels, winsize, error, max_gap, step, ind_idx=None, **kw):
+def lod_kde(ctx, panels, winsize, error, max_gap, step, ind_idx=None, on_shards=False, **kw):
     """computeKDE's density of the panel-wide feed by LodEngine::lodKde's rule.  panels: the shards' abi.Panel objects in
     rank order (one process holding them all), each with its own individuals; ind_idx: per shard, the shard-local part
     of the KDE subsample (split_subsample) or None.  One shard: Panel.lod_kde, no feed value leaves the device.  Several:
     the shards' sorted feeds merged on the host (merge_sorted_feeds), then Context.feed_kde on `ctx` -- correct, but the
-    transfer is not saved; a sharded device path needs distributed order statistics.  The panels' feed order setting is
-    left as found (Panel.feed_order) on both paths.  Returns the dict of Context.feed_kde."""
+    transfer is not saved.  on_shards=True (LodOptions::kde_on_shards): every shard that holds listed individuals leaves
+    its sorted feed on its device as an abi.KdePart and abi.kde_parts reduces them where they lie, for any shard count.
+    The panels' feed order setting is left as found (Panel.feed_order) on every path.  Returns the dict of
+    Context.feed_kde."""
     from . import abi
     idx = list(ind_idx) if ind_idx is not None else [None] * len(panels)
+    if on_shards:
+        parts = []
+        try:
+            for p, sub in zip(panels, idx):
+                if sub is not None and len(sub) == 0:
+                    continue                              # no listed individual lives on this shard: no part
+                parts.append(p.lod_kde_part(winsize, error, max_gap, step, ind_idx=sub, **kw)[0])
+            return abi.kde_parts(parts)
+        finally:
+            for part in parts:
+                part.close()
     if len(panels) == 1:
         return panels[0].lod_kde(winsize, error, max_gap, step, ind_idx=idx[0], **kw)[0]
     feeds = []
@@ -153,3 +166,26 @@ def lod_kde(ctx, panels, winsize, error, max_gap, step, ind_idx=None, **kw):
         finally:
             p.set_feed_order(was)
     return ctx.feed_kde(merge_sorted_feeds(feeds))
+
+
+def lod_kde_multi(ctx, panels, winsizes, error, max_gap, steps=None, ind_idx=None, use_gl=False, strict=False):
+    """lod_kde for every window size of a sweep by LodEngine::lodKdeMulti's rule (unweighted scores; steps default to the
+    sizes).  One shard: Panel.lod_kde_multi.  Several: every shard that holds listed individuals leaves the sorted feeds
+    of all sizes on its device as one abi.KdePartSet (Panel.lod_kde_part_set) and abi.kde_parts_multi reduces them where
+    they lie -- no feed value leaves its device, and each result equals lod_kde(..., on_shards=True)'s bit for bit.
+    `ctx` is not used on that path.  Returns ([the dict of Context.feed_kde, or None for a refused size], [status per
+    size]); strict: any refused size raises."""
+    from . import abi
+    idx = list(ind_idx) if ind_idx is not None else [None] * len(panels)
+    if len(panels) == 1:
+        return panels[0].lod_kde_multi(winsizes, error, max_gap, steps=steps, use_gl=use_gl, ind_idx=idx[0], strict=strict)[:2]
+    sets = []
+    try:
+        for p, sub in zip(panels, idx):
+            if sub is not None and len(sub) == 0:
+                continue                                  # no listed individual lives on this shard: no set
+            sets.append(p.lod_kde_part_set(winsizes, error, max_gap, steps=steps, use_gl=use_gl, ind_idx=sub)[0])
+        return abi.kde_parts_multi(sets, strict=strict)
+    finally:
+        for s in sets:
+            s.close()

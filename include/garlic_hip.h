@@ -60,7 +60,9 @@ extern "C" {
  *    garlic_feature_set, garlic_roh_interval, GARLIC_FEATURE_MAX_EFFECTS, garlic_feature_set_create,
  *    garlic_feature_set_destroy, garlic_feature_set_rows, garlic_feature_set_sites, garlic_feature_counts,
  *    garlic_feature_counts_info (likewise); GARLIC_KDE_MAX_FEEDS, garlic_feed_kde_multi, garlic_lod_kde_multi,
- *    garlic_feed_kde_multi_info (likewise) */
+ *    garlic_feed_kde_multi_info (likewise); garlic_kde_part_set, garlic_kde_part_set_create, garlic_lod_kde_part_set,
+ *    garlic_kde_part_set_destroy, garlic_kde_part_set_counts, garlic_kde_part_set_moment, garlic_kde_part_set_rank,
+ *    garlic_kde_part_set_sums, garlic_kde_parts_multi, garlic_kde_parts_multi_info (likewise) */
 #define GARLIC_HIP_ABI_VERSION 8
 
 #define GARLIC_OK 0
@@ -697,6 +699,70 @@ int garlic_kde_part_sums(garlic_kde_part *part, const double *targets, double h,
 int garlic_kde_parts(garlic_kde_part *const *parts, int32_t n_parts, garlic_kde *out);
 int garlic_kde_parts_info(garlic_kde_part *const *parts, int32_t n_parts, int64_t *chunks, int64_t *pairs_skipped,
                           int32_t *rank_rounds, float *sums_ms);
+
+/* The KDEs of several split feeds at once -- every window size of a sweep on a sharded panel (csrc/kde_part_set_kernels.hpp,
+ * kde_rank_multi_kernel of csrc/kde_multi_kernels.hpp; the descent for F feeds: host/kde_parts.hpp, kdeSelectRanksMulti).  A garlic_kde_part_set is
+ * the F feeds (1 <= F <= GARLIC_KDE_MAX_FEEDS) of ONE shard on one context: feed i of the set is that shard's part of
+ * union i.  Every step of garlic_kde_parts runs once per set for all its feeds: per set 4 moment launches, 8 rank launches
+ * of F x 1024 probes, 2 sums launches and 11 host waits, whatever F is.
+ *
+ * garlic_kde_part_set_create: sorted[i] holds n[i] >= 0 doubles in garlic_feed_sort's key order; feed i may be empty
+ * (sorted[i] is not read then).  GARLIC_DEVICE: borrowed until garlic_kde_part_set_destroy; GARLIC_HOST: uploaded, one
+ * after the other, into memory the set owns.  The set's scratch (8 B per 2048 values, the slice sums, 8.3 KB of table
+ * and 16 KB of probes and counts per feed, and a pinned block of the table's and the probes' size on the host) lives and
+ * ends with the set; destroy the sets before their context.  GARLIC_ERR_NOMEM leaves everything untouched.
+ * garlic_lod_kde_part_set: garlic_lod_kde_multi up to, not including, the KDE -- the same validation, planning, kernel
+ * forms and grouping, the same garlic_lod_feed_info, garlic_lod_feed_multi_info and chr_counts; unweighted scores and
+ * use_gl only.  The sizes' sorted device feeds become the set's feeds, borrowed from the panel's feed slots: the set is
+ * stale by garlic_lod_kde_part's rule, and any use of a stale set (destroy excepted) is GARLIC_ERR_STATE.
+ * garlic_kde_part_set_counts: n[i] = the length of feed i, F values.
+ *
+ * The steps, each for all F feeds in one pass -- what a caller with one process per GPU all-reduces between
+ * (INTEGRATION.md).  A feed that is switched off takes no part in a step: no kernel reads it, and its entries of the
+ * output arrays are left as they were.  Every feed is switched on by a pass 0; it is switched off by a nonzero status[i]
+ * on entry to a moment step, by what a moment step refuses of it, and by active[i] == 0 in the sums step, and stays off
+ * up to the set's next pass 0.
+ * garlic_kde_part_set_moment: pass 0: values[i] = the sum of feed i (the tree of garlic_feed_kde), lo[i] / hi[i] its ends;
+ * an empty feed: 0.0, lo / hi untouched; `means` is not read.  Pass 1: values[i] = the sum of (x - means[i])^2.
+ * status: on return of pass 0, status[i] = GARLIC_ERR_INVALID for a feed with a NaN or an infinity or x[j] < x[j - 1]
+ * (garlic_hip_last_error names the lowest such feed and the cause), entries that came in nonzero are kept, the others are
+ * 0.  status == NULL: every feed takes part and such a feed fails the call.  lo / hi may be NULL.
+ * garlic_kde_part_set_rank: keys[i * m + t], below[i * m + t]: garlic_kde_part_rank on feed i, 1 <= m <= 1024, one launch.
+ * garlic_kde_part_set_sums: targets[i * 512 + j], h[i], sums[i * 512 + j], pairs_skipped[i]: garlic_kde_part_sums on feed i
+ * (undivided).  active and pairs_skipped may be NULL.
+ *
+ * garlic_kde_parts_multi: the KDEs of the F unions {feed i of sets[0], feed i of sets[1], ...}, 1 <= n_sets <=
+ * GARLIC_KDE_MAX_PARTS, all sets with the same F, on any mix of contexts and devices; every step is enqueued on every
+ * set's stream before any is waited for.  outs[i] equals, in every field bit for bit, what garlic_kde_parts returns for
+ * those parts in that order, whatever else is in the batch: so with ONE set outs[i] is garlic_feed_kde_multi's struct, and
+ * n, q25, q75, lo and hi do not depend on the split.  status and the untouched outputs are garlic_feed_kde_multi's:
+ * status[i] = GARLIC_OK or the code garlic_kde_parts would fail with (fewer than 2 values in the union; a NaN; not
+ * ascending; no bandwidth), outs[i] is written only where status[i] is GARLIC_OK, the call returns GARLIC_OK and
+ * garlic_hip_last_error reads "feed <i>: ..." for the lowest refused i ("feed <i>: set <p>: ..." where the values of one
+ * part are at fault); status == NULL: a refused feed fails the call at the step that refuses it (the lengths, the first
+ * moment pass, the bandwidths) with the code and text of the lowest feed refused by then, all outs untouched.  A feed
+ * refused at the moments or at the bandwidth takes no part in the later steps.
+ * garlic_kde_parts_multi_info: of the last garlic_kde_parts_multi (or step calls) on these sets: chunks[p * F + i] and
+ * pairs_skipped[p * F + i] per set and feed; per set kernel_launches[p], host_waits[p] (a set without any value: 8 and
+ * 8, the ranks alone), rank_rounds[p], moments_ms[p] (HIP events from the first moment launch to the last: the host's
+ * turn between the two passes is inside) and sums_ms[p].  Any pointer but sets may be NULL. */
+typedef struct garlic_kde_part_set garlic_kde_part_set;
+int garlic_kde_part_set_create(garlic_ctx *ctx, const double *const *sorted, const int64_t *n, int32_t n_feeds, int32_t where,
+                               garlic_kde_part_set **set);
+int garlic_lod_kde_part_set(garlic_panel *panel, const int32_t *winsizes, const int32_t *steps, int32_t n_sizes, double error,
+                            int32_t max_gap, int32_t use_gl, const int32_t *ind_idx, int32_t n_idx, garlic_kde_part_set **set,
+                            int64_t *chr_counts);
+int garlic_kde_part_set_destroy(garlic_kde_part_set *set);
+int garlic_kde_part_set_counts(garlic_kde_part_set *set, int64_t *n);
+int garlic_kde_part_set_moment(garlic_kde_part_set *set, int32_t pass, const double *means, double *values, double *lo, double *hi,
+                               int32_t *status);
+int garlic_kde_part_set_rank(garlic_kde_part_set *set, const uint64_t *keys, int32_t m, int64_t *below);
+int garlic_kde_part_set_sums(garlic_kde_part_set *set, const double *targets, const double *h, const int32_t *active, double *sums,
+                             int64_t *pairs_skipped);
+int garlic_kde_parts_multi(garlic_kde_part_set *const *sets, int32_t n_sets, garlic_kde *outs, int32_t *status);
+int garlic_kde_parts_multi_info(garlic_kde_part_set *const *sets, int32_t n_sets, int64_t *chunks, int64_t *pairs_skipped,
+                                int32_t *kernel_launches, int32_t *host_waits, int32_t *rank_rounds, float *moments_ms,
+                                float *sums_ms);
 
 /* GMM::estimate (src/gmm.cpp:385-442) on the device: the EM fit of a 1-D mixture of k Gaussians that selectSizeClasses
  * (src/garlic-roh.cpp:935-1003) runs on the ROH lengths (csrc/gmm_kernels.hpp; the initial guess, the ordering of the

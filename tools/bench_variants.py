@@ -30,6 +30,9 @@ of garlic_lod_kde per size (the path of the commits before garlic_lod_kde_multi,
 call, at the --kde-inds and the everyone scale, with the moment and sums event times of both (profiles/kde_multi_ab.txt).
 --modes feed_kde_parts: the KDE of a panel sharded over two panels on the one device: the present path (sorted feeds to the
 host, merged, uploaded, garlic_feed_kde) beside garlic_lod_kde_part + garlic_kde_parts (profiles/kde_parts_ab.txt).
+--modes kde_parts_multi: the KDEs of every size of --winsizes on a panel sharded over two panels on the one device: the loop of
+garlic_lod_kde_part + garlic_kde_parts per size beside one garlic_lod_kde_part_set per shard + garlic_kde_parts_multi, at the
+--kde-inds and the everyone scale; asserts that the structs agree bit for bit (profiles/kde_parts_multi_ab.txt).
 --modes feature_counts: garlic_feature_counts at --snps hom rows x --inds individuals (the issue's shapes: 1000000 x 1250 and x
 10000), 3 classes, 3 effects, hom-bit density 1e-3, 40 ROH per individual: the kernels by HIP events, the whole host-output
 call, the bytes of row words and row fields one pass reads (profiles/feature_counts_ab.txt).
@@ -604,6 +607,83 @@ def feed_kde_parts_leg(args):
             panel.release_scratch()
 
 
+def kde_parts_multi_leg(args):
+    """A window-size sweep's KDEs on a panel sharded over two panels that split its individuals, both on device 0 (so this
+    shows launches, host waits and feed passes saved, NOT the scaling over devices; unweighted --error scores, step = size).
+    "loop": per size garlic_lod_kde_part on either shard + garlic_kde_parts -- the path before garlic_kde_parts_multi,
+    unchanged.  "sets": one garlic_lod_kde_part_set per shard + one garlic_kde_parts_multi.  Per scale (--kde-inds
+    individuals, everyone) one JSON line: the host clock around either leg in turn (1 + --steps repeats, the first dropped;
+    every repeat listed), the sets' launches, waits and event times (garlic_kde_parts_multi_info), and the assertion that
+    the structs agree bit for bit."""
+    import time
+    import torch
+    from garlic_amd import abi, synth
+
+    torch.cuda.set_device(0)
+    dev = torch.device("cuda", 0)
+    nloci, nind = args.snps, args.inds
+    sizes = [int(w) for w in args.winsizes.split(",")]
+    error, max_gap = 0.001, 200000
+    spec = synth.PanelSpec(nloci, seed=20260105, max_gap=max_gap)
+    cut = nind // 2
+    bounds = [(0, cut), (cut, nind)]
+    ctxs = [abi.Context(0) for _ in bounds]
+    panels = []
+    for ctx, (b, e) in zip(ctxs, bounds):
+        panel = abi.Panel(ctx, spec.chr_nloci, e - b)
+        panel.set_map(spec.pos, spec.centro_start, spec.centro_end)
+        panel.set_freq(spec.freq)
+        panels.append(panel)
+    for l0, g in synth.genotype_chunks(spec, nind, dev):
+        for panel, (b, e) in zip(panels, bounds):
+            half = g[:, b:e].contiguous()
+            torch.cuda.synchronize()
+            panel.set_genotypes_device(half.data_ptr(), half.shape[1], l0, half.shape[0])
+            torch.cuda.synchronize()
+    del g, half
+    rng = np.random.default_rng(11)
+    subsets = [np.sort(rng.choice(nind, size=min(args.kde_inds, nind), replace=False)).astype(np.int32), None]
+    for idx in subsets:
+        split = [None, None] if idx is None else [idx[idx < cut], idx[idx >= cut] - cut]
+        loop_ms, sets_ms, mom_ms, sums_ms = [], [], [], []
+        for k in range(1 + args.steps):          # the two paths in turn, so that a drift of the clocks meets both
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            one = []
+            for W in sizes:
+                parts = [panel.lod_kde_part(W, error, max_gap, W, ind_idx=mine)[0] for panel, mine in zip(panels, split)]
+                one.append(abi.kde_parts(parts))
+                for p in parts:
+                    p.close()
+            t1 = time.perf_counter()
+            sets = [panel.lod_kde_part_set(sizes, error, max_gap, ind_idx=mine)[0] for panel, mine in zip(panels, split)]
+            many, status = abi.kde_parts_multi(sets, strict=True)
+            t2 = time.perf_counter()
+            info = abi.kde_parts_multi_info(sets)
+            part_values = [[int(v) for v in s.counts()] for s in sets]
+            for s in sets:
+                s.close()
+            if k:
+                loop_ms.append((t1 - t0) * 1e3)
+                sets_ms.append((t2 - t1) * 1e3)
+                mom_ms.append([float(v) for v in info["moments_ms"]])
+                sums_ms.append([float(v) for v in info["sums_ms"]])
+        same = all(a["n"] == b["n"] and all(np.float64(a[f]).tobytes() == np.float64(b[f]).tobytes() for f in ("h", "sd", "q25", "q75", "lo", "hi"))
+                   and all(a[f].tobytes() == b[f].tobytes() for f in ("x", "y", "raw")) for a, b in zip(one, many))
+        assert same, "garlic_kde_parts_multi differs from the loop of garlic_kde_parts"
+        print(json.dumps({"mode": "kde_parts_multi", "snps": nloci, "inds": nind, "winsizes": sizes, "shards": 2, "devices": [0, 0],
+                          "repeats": args.steps, "feed_individuals": nind if idx is None else int(idx.shape[0]),
+                          "values": [int(k["n"]) for k in many], "part_values": part_values,
+                          "loop_of_kde_parts_ms": loop_ms, "loop_of_kde_parts_ms_median": float(np.median(loop_ms)), "loop_of_kde_parts_ms_min": min(loop_ms),
+                          "kde_parts_multi_ms": sets_ms, "kde_parts_multi_ms_median": float(np.median(sets_ms)), "kde_parts_multi_ms_min": min(sets_ms),
+                          "set_moment_span_ms_median": [float(v) for v in np.median(np.array(mom_ms), axis=0)],
+                          "set_sums_kernels_ms_median": [float(v) for v in np.median(np.array(sums_ms), axis=0)],
+                          "set_kernel_launches": [int(v) for v in info["kernel_launches"]], "set_host_waits": [int(v) for v in info["host_waits"]],
+                          "loop_host_waits_per_shard": 11 * len(sizes), "structs_identical": bool(same)}), flush=True)
+        for panel in panels:
+            panel.release_scratch()
+
+
 def feature_counts_leg(args):
     """One JSON line.  The hom bits are drawn sparse (density x rows x individuals set bits at random places) and uploaded in
     slabs of rows; intervals: 40 per individual over 22 chromosomes, classes at random.  The count is checked against numpy on
@@ -1001,6 +1081,8 @@ def main():
         return feed_kde_parts_leg(args)
     if args.modes == "kde_multi":
         return kde_multi_leg(args)
+    if args.modes == "kde_parts_multi":
+        return kde_parts_multi_leg(args)
     if args.modes == "bed_ingest":
         return bed_ingest_leg(args)
     if args.modes == "ld_phased":
