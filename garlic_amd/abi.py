@@ -45,6 +45,7 @@ SYMBOLS = [
     "garlic_panel_set_phase_bits", "garlic_panel_ld_form_info",
     "garlic_panel_set_gl_codes16",
     "garlic_bed_create", "garlic_bed_set_rows", "garlic_bed_census", "garlic_bed_destroy", "garlic_panel_set_genotypes_bed",
+    "garlic_bed_extract", "garlic_bed_get_rows",
     "garlic_feed_kde", "garlic_lod_kde", "garlic_feed_kde_info", "garlic_feed_kde_times",
     "garlic_gmm_fit", "garlic_gmm_fit_info",
     "garlic_kde_part_create", "garlic_lod_kde_part", "garlic_kde_part_destroy", "garlic_kde_part_count",
@@ -235,6 +236,8 @@ def lib():
     L.garlic_bed_set_rows.argtypes = [_vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32]
     L.garlic_bed_census.argtypes = [_vp, _vp, _vp, C.c_int32]
     L.garlic_bed_destroy.argtypes = [_vp]
+    L.garlic_bed_extract.argtypes = [_vp, _vp, C.c_int32, C.POINTER(_vp)]
+    L.garlic_bed_get_rows.argtypes = [_vp, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_int32]
     L.garlic_panel_set_genotypes_bed.argtypes = [_vp, _vp, C.c_int64, _i64p]
     for name in SYMBOLS:
         f = getattr(L, name)
@@ -738,6 +741,28 @@ class Bed:
 
     def census_device(self, counts_ptr, counted_ptr):
         check(lib().garlic_bed_census(self.handle, _vp(counts_ptr), _vp(counted_ptr), DEVICE))
+
+    def extract(self, idx):
+        """A new Bed on the same context whose individual i is this image's individual idx[i] (any order, repeats allowed):
+        one population of a multi-population file.  Independent of this image once made; it needs the context."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        assert idx.ndim == 1
+        handle = _vp()
+        check(lib().garlic_bed_extract(self.handle, _vp(idx.ctypes.data), idx.shape[0], C.byref(handle)))
+        sub = object.__new__(Bed)
+        sub.ctx = self.ctx
+        sub.nrows = self.nrows
+        sub.nind_total = int(idx.shape[0])
+        sub.row_bytes = (sub.nind_total + 3) // 4
+        sub.handle = handle
+        return sub
+
+    def get_rows(self, row_begin=0, row_count=None):
+        """uint8 [row_count][(nind_total + 3) // 4]: the image's rows as they stand on the device."""
+        row_count = self.nrows - row_begin if row_count is None else row_count
+        rows = np.empty((max(row_count, 0), self.row_bytes), dtype=np.uint8)
+        check(lib().garlic_bed_get_rows(self.handle, row_begin, row_count, _vp(rows.ctypes.data), self.row_bytes, HOST))
+        return rows
 
     def destroy(self):
         if self.handle:

@@ -180,4 +180,110 @@ bed_pack_kernel(const uint8_t *__restrict__ image, int64_t image_bytes /* padded
     }
 }
 
+// A column subset of an image as a new image: individual i of every new row is individual idx[i] of the same source row, in
+// PLINK's codes, unchanged; the pad bits of a new row's last byte are zero.  Exact: bytes are moved, nothing is computed.
+//
+// A thread owns one 8-byte word of the new row (32 subset individuals) and keeps where each of them sits in the source row
+// -- (byte, shift) relative to the first source byte its span needs -- in 32 registers across all the rows it walks.  A
+// workgroup covers a span of 256 words (8192 subset individuals); blockIdx.x is the span, blockIdx.y walks steps of rows with
+// the grid's stride.  A span of fewer than 129 words is laid over the workgroup several times (`words` lanes a copy, a power
+// of two), each copy taking other rows of the step, so that a narrow subset leaves no lane idle.
+//
+// Per step the workgroup stages, for each of the step's rows, the source bytes [lo, hi] the span needs (lo / hi: the bytes of
+// the span's smallest / largest index, found by the host) into LDS, in the aligned 16-byte pieces and under the image_bytes
+// guard of bed_pack_kernel; a source row starts at any byte, so (begin + lo) & 15 is a per-row scalar on the lane's LDS
+// offset.  Then every lane assembles its word from 32 LDS byte reads.  LDS budget: BED_EXTRACT_LDS bytes per workgroup (32
+// KiB; 4 workgroups of it fit a CU's 160 KB); a row's range takes `pieces` = ((hi - lo + 15) >> 4) + 1 pieces whatever its
+// alignment, and min(BED_EXTRACT_ROWS, budget / range) rows go into a step.  A span whose range does not fit once (hi - lo
+// + 1 > 32,753 bytes: more than 131,012 file individuals between its smallest and largest index) has pieces = 0 and takes
+// the global form: the same 32 byte reads per lane, from the image itself.
+//
+// New rows start at any byte as well: a full word is stored with two 4-byte stores when its address is 4-byte aligned and
+// with byte stores otherwise, a row's ragged last word always with byte stores of its own bytes only -- no store touches a
+// byte of a neighbouring row, so nothing depends on the order of the stores.
+constexpr int BED_EXTRACT_SPAN_WORDS = 256;
+constexpr int BED_EXTRACT_LDS = 32 * 1024;
+constexpr int BED_EXTRACT_ROWS = 16;                   // rows of a step at the most
+constexpr int BED_EXTRACT_MAX_RANGE = BED_EXTRACT_LDS - 15;    // hi - lo + 1 above this: global form
+
+struct BedSpan {
+    int32_t lo;          // first source byte of a row that the span needs
+    int32_t pieces;      // 16-byte pieces per row in LDS; 0 = global form
+};
+
+__global__ void __launch_bounds__(256)
+bed_extract_kernel(const uint8_t *__restrict__ image, int64_t image_bytes, int64_t nrows, int64_t src_row_bytes,
+                   const int32_t *__restrict__ idx, int32_t n_idx, const BedSpan *__restrict__ spans, uint8_t *__restrict__ out,
+                   int64_t out_row_bytes)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t tile[BED_EXTRACT_LDS];
+    const int tid = threadIdx.x;
+    const BedSpan span = spans[blockIdx.x];
+    const int64_t nwords = ((int64_t)n_idx + 31) >> 5;
+    const int64_t word0 = (int64_t)blockIdx.x * BED_EXTRACT_SPAN_WORDS;
+    const int span_words = (int)(nwords - word0 < BED_EXTRACT_SPAN_WORDS ? nwords - word0 : BED_EXTRACT_SPAN_WORDS);
+    int words = 1;                                      // lanes per copy of the span
+    while (words < span_words) words <<= 1;
+    const int copies = 256 / words;
+    const int my_copy = tid / words, my_word = tid & (words - 1);
+    const bool owner = my_word < span_words;
+    const int64_t w = word0 + my_word;                  // the word of the new row
+    // where the 32 individuals of the word sit, relative to 4 * lo; `valid`: the low bit of every field that has an individual
+    uint32_t rel[32];
+    uint64_t valid = 0;
+#pragma unroll
+    for (int k = 0; k < 32; k++) {
+        const int64_t i = 32 * w + k;
+        const bool have = owner && i < n_idx;
+        rel[k] = have ? (uint32_t)(idx[i] - 4 * span.lo) : 0u;
+        valid |= have ? 1ull << (2 * k) : 0ull;
+    }
+    valid |= valid << 1;
+    const int word_bytes = owner ? (int)(out_row_bytes - 8 * w < 8 ? out_row_bytes - 8 * w : 8) : 0;
+    const int range = span.pieces * 16;                 // LDS bytes per row of a step
+    const int step_rows = span.pieces ? (BED_EXTRACT_LDS / range < BED_EXTRACT_ROWS ? BED_EXTRACT_LDS / range : BED_EXTRACT_ROWS)
+                                      : BED_EXTRACT_ROWS;
+    const int64_t nsteps = (nrows + step_rows - 1) / step_rows;
+    for (int64_t step = blockIdx.y; step < nsteps; step += gridDim.y) {
+        const int64_t r0 = step * step_rows;
+        const int nr = (int)(nrows - r0 < step_rows ? nrows - r0 : step_rows);
+        if (span.pieces) {
+            __syncthreads();                            // the previous step's reads are done
+            for (int p = tid; p < nr * span.pieces; p += 256) {
+                const int q = p / span.pieces, pc = p - q * span.pieces;
+                const int64_t first = (r0 + q) * src_row_bytes + span.lo;       // first byte the span needs of this row
+                const int64_t at = (first & ~(int64_t)15) + 16 * (int64_t)pc;
+                const int64_t end = (r0 + q + 1) * src_row_bytes - 1;            // the row's last byte
+                if (at > end || at + 16 > image_bytes) continue;
+                *reinterpret_cast<uint4 *>(&tile[q * range + 16 * pc]) = *reinterpret_cast<const uint4 *>(image + at);
+            }
+            __syncthreads();
+        }
+        for (int q = my_copy; q < nr; q += copies) {
+            if (!owner) break;
+            const int64_t first = (r0 + q) * src_row_bytes + span.lo;
+            uint64_t word = 0;
+            if (span.pieces) {
+                const uint8_t *src = tile + q * range + (int)(first & 15);
+#pragma unroll
+                for (int k = 0; k < 32; k++)
+                    word |= (uint64_t)(((uint32_t)src[rel[k] >> 2] >> (2 * (rel[k] & 3u))) & 3u) << (2 * k);
+            } else {
+                const uint8_t *src = image + first;
+#pragma unroll
+                for (int k = 0; k < 32; k++)
+                    word |= (uint64_t)(((uint32_t)src[rel[k] >> 2] >> (2 * (rel[k] & 3u))) & 3u) << (2 * k);
+            }
+            word &= valid;
+            uint8_t *dst = out + (r0 + q) * out_row_bytes + 8 * w;
+            if (word_bytes == 8 && ((uintptr_t)dst & 3) == 0) {
+                reinterpret_cast<uint32_t *>(dst)[0] = (uint32_t)word;
+                reinterpret_cast<uint32_t *>(dst)[1] = (uint32_t)(word >> 32);
+            } else {
+                for (int t = 0; t < word_bytes; t++) dst[t] = (uint8_t)(word >> (8 * t));
+            }
+        }
+    }
+}
+
 } // namespace garlic

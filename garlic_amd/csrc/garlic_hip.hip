@@ -3083,6 +3083,77 @@ int garlic_panel_set_genotypes_bed(garlic_panel *p, garlic_bed *b, int64_t ind_o
     return GARLIC_OK;
 }
 
+int garlic_bed_extract(garlic_bed *src, const int32_t *ind_idx, int32_t n_idx, garlic_bed **out)
+{
+    if (!src || !ind_idx || !out) return fail(GARLIC_ERR_INVALID, "bed extract: src, ind_idx and out are required");
+    if (n_idx < 1 || n_idx >= (1 << 30)) return fail(GARLIC_ERR_INVALID, "bed extract: need 1 <= n_idx < 2^30, got %d", n_idx);
+    if (src->n_set != src->nrows)
+        return fail(GARLIC_ERR_STATE, "bed extract needs every row of the source: %lld of %lld set", (long long)src->n_set, (long long)src->nrows);
+    for (int32_t i = 0; i < n_idx; i++)
+        if (ind_idx[i] < 0 || ind_idx[i] >= src->nind)
+            return fail(GARLIC_ERR_INVALID, "bed extract: ind_idx[%d] = %d outside the source's %d individuals", i, ind_idx[i], src->nind);
+    int rc;
+    if ((rc = set_device(src->ctx))) return rc;
+    hipStream_t s = src->ctx->stream;
+    // per span of 8192 subset individuals: the first source byte it needs and the pieces of a row in LDS (0: global form)
+    const int64_t nwords = ((int64_t)n_idx + 31) / 32;
+    const int64_t nspans = (nwords + BED_EXTRACT_SPAN_WORDS - 1) / BED_EXTRACT_SPAN_WORDS;
+    std::vector<BedSpan> spans((size_t)nspans);
+    for (int64_t sp = 0; sp < nspans; sp++) {
+        const int64_t i0 = sp * BED_EXTRACT_SPAN_WORDS * 32, i1 = std::min<int64_t>(n_idx, i0 + BED_EXTRACT_SPAN_WORDS * 32);
+        int32_t lo = ind_idx[i0], hi = ind_idx[i0];
+        for (int64_t i = i0; i < i1; i++) { lo = std::min(lo, ind_idx[i]); hi = std::max(hi, ind_idx[i]); }
+        const int32_t range = (hi >> 2) - (lo >> 2) + 1;
+        spans[(size_t)sp] = {lo >> 2, range > BED_EXTRACT_MAX_RANGE ? 0 : ((range + 14) >> 4) + 1};
+    }
+    std::unique_ptr<garlic_bed> b(new garlic_bed);      // (a failure below frees what it holds; *out is written last)
+    b->ctx = src->ctx;
+    b->nrows = src->nrows;
+    b->nind = n_idx;
+    b->row_bytes = ((int64_t)n_idx + 3) / 4;
+    b->image_bytes = ((b->nrows * b->row_bytes + 15) & ~(int64_t)15) + BED_IMAGE_PAD;
+    DevBuf<int32_t> d_idx;
+    DevBuf<BedSpan> d_spans;
+    if ((rc = b->d_image.reserve((size_t)b->image_bytes)) || (rc = b->d_counts.reserve((size_t)(2 * b->nrows))) ||
+        (rc = b->d_counted.reserve((size_t)b->nrows)) || (rc = d_idx.reserve((size_t)n_idx)) || (rc = d_spans.put(spans, s)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(d_idx.p, ind_idx, sizeof(int32_t) * (size_t)n_idx, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(b->d_image.p + b->image_bytes - BED_IMAGE_PAD - 16, 0, BED_IMAGE_PAD + 16, s));
+    const int64_t want = std::max<int64_t>(1, (8 * (int64_t)src->ctx->n_cu + nspans - 1) / nspans);
+    const dim3 grid((unsigned)nspans, (unsigned)std::min<int64_t>(std::min<int64_t>(b->nrows, 65535), want));
+    hipLaunchKernelGGL(bed_extract_kernel, grid, dim3(256), 0, s, src->d_image.p, src->image_bytes, src->nrows, src->row_bytes,
+                       d_idx.p, n_idx, d_spans.p, b->d_image.p, b->row_bytes);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));                   // the index lists are free again; `src` may go
+    b->row_set.assign((size_t)((b->nrows + 63) / 64), ~0ull);
+    b->n_set = b->nrows;
+    *out = b.release();
+    return GARLIC_OK;
+}
+
+int garlic_bed_get_rows(garlic_bed *b, int64_t row_begin, int64_t row_count, uint8_t *rows, int64_t row_bytes, int32_t where)
+{
+    if (!b || !rows) return fail(GARLIC_ERR_INVALID, "bed and rows are required");
+    if (where != GARLIC_HOST && where != GARLIC_DEVICE) return fail(GARLIC_ERR_INVALID, "where must be GARLIC_HOST or GARLIC_DEVICE");
+    if (row_bytes < b->row_bytes)
+        return fail(GARLIC_ERR_INVALID, "row_bytes %lld too small for %d individuals (%lld)", (long long)row_bytes, b->nind,
+                    (long long)b->row_bytes);
+    if (row_begin < 0 || row_count < 1 || row_begin + row_count > b->nrows)
+        return fail(GARLIC_ERR_INVALID, "row range [%lld,+%lld) outside image of %lld rows", (long long)row_begin,
+                    (long long)row_count, (long long)b->nrows);
+    int rc;
+    if ((rc = set_device(b->ctx))) return rc;
+    hipStream_t s = b->ctx->stream;
+    const uint8_t *from = b->d_image.p + row_begin * b->row_bytes;
+    const hipMemcpyKind kind = where == GARLIC_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    if (row_bytes == b->row_bytes)
+        HIP_TRY(hipMemcpyAsync(rows, from, (size_t)(row_count * row_bytes), kind, s));
+    else
+        HIP_TRY(hipMemcpy2DAsync(rows, (size_t)row_bytes, from, (size_t)b->row_bytes, (size_t)b->row_bytes, (size_t)row_count, kind, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return GARLIC_OK;
+}
+
 // ---- uploads into a panel of 16-bit codes.
 // The caller's table joins the panel's (by bit pattern, first seen first): remap[caller code] = panel code.  When the merged
 // table would pass 65,536 values the panel goes on with the values themselves (gl_wide unset on return; remap is void then).

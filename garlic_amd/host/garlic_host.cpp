@@ -518,15 +518,30 @@ void closeBedFile(BedFile *b)
         if (im.ctx) garlic_ctx_destroy((garlic_ctx *)im.ctx);
     }
     if (b->map) munmap(b->map, b->map_bytes);
+    BedFile *parent = b->parent;      // (its contexts carried this file's extracts: it goes after them)
     delete b;
+    if (parent) releaseBedFile(parent);
 }
 
-BedFile *openBedFile(const std::string &bedfile, const std::string &bimfile, const std::string &famfile)
+void releaseBedFile(BedFile *b)
+{
+    if (b && --b->refs <= 0) closeBedFile(b);
+}
+
+BedFile *openBedFile(const std::string &bedfile, const std::string &bimfile, const std::string &famfile, bool anyPopulations)
 {
     std::unique_ptr<BedFile, void (*)(BedFile *)> b(new BedFile, closeBedFile);
     b->path = bedfile;
     std::string pop;
-    scanIndData3(famfile, b->nind, pop);
+    if (anyPopulations) {
+        try {
+            b->nind = (int)readFam(famfile).size();
+        } catch (const std::exception &e) {
+            fail(e.what());
+        }
+    } else {
+        scanIndData3(famfile, b->nind, pop);
+    }
     if (b->nind < 1) fail("no individuals in " + famfile);
     b->row_bytes = ((size_t)b->nind + 3) / 4;
     {
@@ -577,18 +592,28 @@ BedFile *openBedFile(const std::string &bedfile, const std::string &bimfile, con
 }
 
 namespace {
-// the image of the file on `device` (made, filled chunk by chunk and censused at the first request)
-garlic_bed *bedImageOn(BedFile *b, int device)
+// the slot of `device` in the file's image list, with its context
+size_t bedSlotOn(BedFile *b, int device)
 {
-    for (auto &im : b->images)
-        if (im.device == device) return (garlic_bed *)im.bed;
+    for (size_t k = 0; k < b->images.size(); k++)
+        if (b->images[k].device == device) return k;
     b->images.push_back({device, nullptr, nullptr});
-    garlic_ctx *ctx = nullptr;
-    check(garlic_ctx_create(device, nullptr, &ctx), "garlic_ctx_create");
-    b->images.back().ctx = ctx;
+    if (!b->parent) {      // (an extract lives on its parent's context)
+        garlic_ctx *ctx = nullptr;
+        check(garlic_ctx_create(device, nullptr, &ctx), "garlic_ctx_create");
+        b->images.back().ctx = ctx;
+    }
+    return b->images.size() - 1;
+}
+
+// the image of the whole mapped file on `device` (made and filled chunk by chunk at the first request)
+garlic_bed *bedFullImageOn(BedFile *b, int device)
+{
+    const size_t slot = bedSlotOn(b, device);
+    if (b->images[slot].bed) return (garlic_bed *)b->images[slot].bed;
     garlic_bed *bed = nullptr;
-    check(garlic_bed_create(ctx, b->nrows, b->nind, &bed), "garlic_bed_create");
-    b->images.back().bed = bed;
+    check(garlic_bed_create((garlic_ctx *)b->images[slot].ctx, b->nrows, b->nind, &bed), "garlic_bed_create");
+    b->images[slot].bed = bed;
     // chunks of 64 MB through an ordinary buffer (not the read-only file mapping itself: what the runtime does to pin or stage
     // the source of a large copy is then no concern of the mapping)
     const long long chunk = std::max<long long>(1, ((long long)64 << 20) / (long long)b->row_bytes);
@@ -597,6 +622,35 @@ garlic_bed *bedImageOn(BedFile *b, int device)
         const long long n = std::min(chunk, b->nrows - r);
         memcpy(buf.data(), b->rows + (size_t)r * b->row_bytes, (size_t)n * b->row_bytes);
         check(garlic_bed_set_rows(bed, buf.data(), (int64_t)b->row_bytes, r, n, GARLIC_HOST), "garlic_bed_set_rows");
+    }
+    return bed;
+}
+
+// the image of the file set on `device`, censused at the first request: the whole file's, or -- for a subset -- the extract
+// cut from the parent's image there (which then goes, unless the parent holds it for further populations)
+garlic_bed *bedImageOn(BedFile *b, int device)
+{
+    garlic_bed *bed = nullptr;
+    if (b->parent) {
+        const size_t slot = bedSlotOn(b, device);
+        if (!b->images[slot].bed) {
+            garlic_bed *full = bedFullImageOn(b->parent, device);
+            check(garlic_bed_extract(full, b->keep.data(), (int32_t)b->keep.size(), &bed), "garlic_bed_extract");
+            b->images[slot].bed = bed;
+            if (!b->parent->hold_images) {
+                const size_t ps = bedSlotOn(b->parent, device);
+                garlic_bed_destroy((garlic_bed *)b->parent->images[ps].bed);
+                b->parent->images[ps].bed = nullptr;
+            }
+        }
+        bed = (garlic_bed *)b->images[slot].bed;
+        if (!b->rows) {      // the host's view of the genotypes (genotypeAt, the genotype cache): the subset's own rows
+            b->own_rows.resize((size_t)b->nrows * b->row_bytes);
+            check(garlic_bed_get_rows(bed, 0, b->nrows, b->own_rows.data(), (int64_t)b->row_bytes, GARLIC_HOST), "garlic_bed_get_rows");
+            b->rows = b->own_rows.data();
+        }
+    } else {
+        bed = bedFullImageOn(b, device);
     }
     if (b->counted.empty()) {
         b->counts.resize(2 * (size_t)b->nrows);
@@ -607,12 +661,45 @@ garlic_bed *bedImageOn(BedFile *b, int device)
 }
 } // namespace
 
+// the triple of an open file set `b` (the caller's reference on it passes to the HapData, or is dropped on failure)
+static void loadBedFile(BedFile *b, int &numLoci, int &numInd, std::vector<HapData *> **hapDataByChr,
+                        std::vector<MapData *> **mapDataByChr, std::vector<FreqData *> **freqDataByChr, int nresample,
+                        unsigned long long resampleSeed, int device);
+
 void loadBedData(const std::string &bedfile, const std::string &bimfile, const std::string &famfile, int &numLoci, int &numInd,
                  std::vector<HapData *> **hapDataByChr, std::vector<MapData *> **mapDataByChr,
                  std::vector<FreqData *> **freqDataByChr, int nresample, unsigned long long resampleSeed, int device)
 {
     BedFile *b = openBedFile(bedfile, bimfile, famfile);
     b->refs = 1;                 // this function's, until the HapData hold theirs
+    loadBedFile(b, numLoci, numInd, hapDataByChr, mapDataByChr, freqDataByChr, nresample, resampleSeed, device);
+}
+
+void loadBedSubset(BedFile *full, const std::vector<int> &keep, int &numLoci, int &numInd, std::vector<HapData *> **hapDataByChr,
+                   std::vector<MapData *> **mapDataByChr, std::vector<FreqData *> **freqDataByChr, int nresample,
+                   unsigned long long resampleSeed, int device)
+{
+    if (keep.empty()) fail("no individuals kept of " + full->path);
+    for (size_t i = 0; i < keep.size(); i++)
+        if (keep[i] < 0 || keep[i] >= full->nind || (i && keep[i] <= keep[i - 1]))
+            fail("kept individuals must be ascending indices into the .fam of " + full->path);
+    BedFile *b = new BedFile;
+    b->path = full->path;
+    b->parent = full;
+    full->refs++;
+    b->keep = keep;
+    b->nind = (int)keep.size();
+    b->nrows = full->nrows;
+    b->row_bytes = ((size_t)b->nind + 3) / 4;
+    b->refs = 1;
+    loadBedFile(b, numLoci, numInd, hapDataByChr, mapDataByChr, freqDataByChr, nresample, resampleSeed, device);
+}
+
+static void loadBedFile(BedFile *b, int &numLoci, int &numInd, std::vector<HapData *> **hapDataByChr,
+                        std::vector<MapData *> **mapDataByChr, std::vector<FreqData *> **freqDataByChr, int nresample,
+                        unsigned long long resampleSeed, int device)
+{
+    const BedFile *bim = b->bim();      // the .bim columns: the parent's for a subset
     *hapDataByChr = new std::vector<HapData *>;
     *mapDataByChr = new std::vector<MapData *>;
     *freqDataByChr = new std::vector<FreqData *>;
@@ -622,11 +709,11 @@ void loadBedData(const std::string &bedfile, const std::string &bimfile, const s
         std::mt19937 resampler((uint32_t)(seed0 & 0xffffffffull) ? (uint32_t)(seed0 & 0xffffffffull) : 4357u);
         for (long long r0 = 0; r0 < b->nrows;) {
             long long r1 = r0;
-            while (r1 < b->nrows && b->chr[(size_t)r1] == b->chr[(size_t)r0]) r1++;   // a new chromosome where the chr string changes
+            while (r1 < b->nrows && bim->chr[(size_t)r1] == bim->chr[(size_t)r0]) r1++;   // a new chromosome where the chr string changes
             const int n = (int)(r1 - r0);
             MapData *m = initMapData(n);
             (*mapDataByChr)->push_back(m);
-            m->chr = checkChrName(b->chr[(size_t)r0]);
+            m->chr = checkChrName(bim->chr[(size_t)r0]);
             FreqData *f = initFreqData(n);
             (*freqDataByChr)->push_back(f);
             HapData *h = new HapData{nullptr, b->nind, n, nullptr, nullptr, nullptr, b, new long long[n]};
@@ -635,11 +722,11 @@ void loadBedData(const std::string &bedfile, const std::string &bimfile, const s
             for (int l = 0; l < n; l++) {
                 const size_t r = (size_t)(r0 + l);
                 h->bedRow[l] = (long long)r;
-                m->physicalPos[l] = (int)b->ppos[r];
-                m->geneticPos[l] = b->gpos[r];
-                m->locusName[l] = b->name[r];
+                m->physicalPos[l] = (int)bim->ppos[r];
+                m->geneticPos[l] = bim->gpos[r];
+                m->locusName[l] = bim->name[r];
                 // what loadTPEDData stores as oneAllele: the counted allele's character, the missing character '0' for none
-                m->allele[l] = b->counted[r] == 0 ? b->a1[r] : b->counted[r] == 1 ? b->a2[r] : '0';
+                m->allele[l] = b->counted[r] == 0 ? bim->a1[r] : b->counted[r] == 1 ? bim->a2[r] : '0';
                 const int nalleles = b->counts[2 * r], total = b->counts[2 * r + 1];
                 double freq = total == 0 ? 0.0 : double(nalleles) / double(total);   // garlic-data.cpp:141
                 if (nresample > 0 && total != 0) {
@@ -682,6 +769,25 @@ void scanIndData3(const std::string &filename, int &numInd, std::string &popName
     numInd = n;
 }
 
+IndData *indDataOfKept(const std::vector<FamEntry> &fam, const std::vector<int> &keep, const std::string &famfile)
+{
+    if (keep.empty()) fail("Number of individuals must be positive");
+    std::map<std::string, int> seen;
+    const std::string pop = fam[(size_t)keep[0]].fid;
+    for (int i : keep) {
+        const FamEntry &e = fam[(size_t)i];
+        if (seen.count(e.iid)) fail("Found duplicate individual ID (" + e.iid + ") in " + famfile);
+        seen[e.iid] = 1;
+        if (e.fid != pop) fail("Found multiple population IDs (" + e.fid + ", " + pop + ") in " + famfile + " among the kept individuals");
+    }
+    IndData *d = new IndData;
+    d->nind = (int)keep.size();
+    d->indID = new std::string[keep.size()];
+    for (size_t k = 0; k < keep.size(); k++) d->indID[k] = fam[(size_t)keep[k]].iid;
+    d->pop = pop;
+    return d;
+}
+
 IndData *readIndData3(const std::string &filename, int numInd)
 {
     if (numInd < 1) fail("Number of individuals must be positive");
@@ -700,8 +806,11 @@ IndData *readIndData3(const std::string &filename, int numInd)
 }
 
 std::vector<GenoLikeData *> *readTGLSData(const std::string &filename, int /*expectedLoci*/, int expectedInd,
-                                          std::vector<MapData *> *maps, const std::string &GL_TYPE, bool compact)
+                                          std::vector<MapData *> *maps, const std::string &GL_TYPE, bool compact,
+                                          const std::vector<int> *cols, int fileInd)
 {
+    if (cols && (int)cols->size() != expectedInd) fail("readTGLSData: one column per kept individual is needed");
+    std::vector<double> raw(cols ? (size_t)fileInd : 0);
     if (GL_TYPE != "GQ" && GL_TYPE != "GL" && GL_TYPE != "PL") fail("Must choose GQ/GL/PL for genotype likelihood format");
     LineReader in(filename);
     auto *out = new std::vector<GenoLikeData *>;
@@ -722,9 +831,10 @@ std::vector<GenoLikeData *> *readTGLSData(const std::string &filename, int /*exp
         for (int l = 0; l < m->nloci; l++) {
             if (!in.next(line)) fail("too few lines in " + filename);
             const int num = countFields(line);
-            if (num != expectedInd + 4) fail("Incorrect number of columns in tgls file: " + std::to_string(num));
+            if (num != (cols ? fileInd : expectedInd) + 4) fail("Incorrect number of columns in tgls file: " + std::to_string(num));
             std::stringstream ss(line);
             ss >> junk >> junk >> junk >> junk;
+            for (double &v : raw) ss >> v;      // --keep: the whole line, then the kept columns
             if (compact && width == 1) d->codes[l] = new unsigned char[expectedInd];
             else if (compact && width == 2) d->codes16[l] = new unsigned short[expectedInd];
             else if (compact) d->data[l] = new double[expectedInd];
@@ -732,7 +842,8 @@ std::vector<GenoLikeData *> *readTGLSData(const std::string &filename, int /*exp
             int last_code = -1;
             for (int i = 0; i < expectedInd; i++) {
                 double gl;
-                ss >> gl;
+                if (cols) gl = raw[(size_t)(*cols)[(size_t)i]];
+                else ss >> gl;
                 // garlic-data.cpp:1557-1576, operation for operation
                 if (GL_TYPE == "GQ") { gl /= (-10.0); gl = (gl > -10) ? gl : -10; gl = pow(10, gl); }
                 else if (GL_TYPE == "GL") { gl = (gl > -10) ? gl : -10; gl = 1 - pow(10, gl); }

@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 
+#include "bed_keep.hpp"
 #include "feature_counts.hpp"
 #include "feed_merge.hpp"
 #include "kde_select.hpp"
@@ -43,6 +44,17 @@ struct BedFile {
     struct Image { int device; void *ctx; void *bed; };
     std::vector<Image> images;            // the image on each device that has asked for it (bedImageOn)
     int refs = 0;                         // HapData that point here; the last one released closes the file
+    // --keep / --pops (subsetBedFile): this is the file set that holds only the individuals `keep` of `parent` (indices into
+    // its .fam, ascending).  nind / row_bytes / counted / counts are the subset's; `rows` points into own_rows, the subset
+    // image fetched back from the first device (garlic_bed_get_rows); `images` holds the extracts (garlic_bed_extract, made on
+    // the parent's contexts: ctx NULL here); the .bim columns are read through bim().  A subset holds one reference on its
+    // parent.  On a parent, hold_images keeps the full image of a device after an extract was cut from it (--pops: one
+    // upload serves every population); without it the full image of a device goes as soon as the extract exists.
+    BedFile *parent = nullptr;
+    std::vector<int> keep;
+    std::vector<unsigned char> own_rows;
+    bool hold_images = false;
+    const BedFile *bim() const { return parent ? parent : this; }
 };
 // copies of the counted allele by counted[row] and PLINK code; -9 = missing
 inline short bedGenotype(unsigned counted, unsigned code)
@@ -195,8 +207,20 @@ void loadTPEDData(const std::string &tpedfile, int &numLoci, int &numInd,
 // (chr snpid gpos ppos a1 a2; ppos is read as a double like the TPED's), maps the .bed and checks it: the magic bytes
 // 6c 1b 01 (anything else, the individual-major 6c 1b 00 included, is refused), its size against rows x individuals, alleles
 // of one character (GARLIC's alleles are single characters: a longer one is an error that names the line).  No GPU needed.
-BedFile *openBedFile(const std::string &bedfile, const std::string &bimfile, const std::string &famfile);
+// anyPopulations (--keep / --pops): the .fam may carry several family IDs; the single-population check is then the caller's,
+// over the individuals it keeps.
+BedFile *openBedFile(const std::string &bedfile, const std::string &bimfile, const std::string &famfile, bool anyPopulations = false);
 void closeBedFile(BedFile *b);
+void releaseBedFile(BedFile *b);          // one reference less; the last one closes the file
+// The (hap, map, freq) triple of the file set that holds only the individuals `keep` of `full` (ascending indices into its
+// .fam): the full image goes to `device` (once per device and parent), garlic_bed_extract cuts the subset out of it, and
+// census, frequencies, row map, shards and the host's view of the genotypes are the subset image's from there on.
+void loadBedSubset(BedFile *full, const std::vector<int> &keep, int &numLoci, int &numInd, std::vector<HapData *> **hapDataByChr,
+                   std::vector<MapData *> **mapDataByChr, std::vector<FreqData *> **freqDataByChr, int nresample,
+                   unsigned long long resampleSeed, int device);
+// IndData of the kept individuals of a .fam (readFam order): their single family ID is the population name; several among
+// them fail like scanIndData3 ("Found multiple population IDs"), as does an individual ID twice
+IndData *indDataOfKept(const std::vector<FamEntry> &fam, const std::vector<int> &keep, const std::string &famfile);
 // The same (hap, map, freq) triple as loadTPEDData from a .bed/.bim/.fam: the rows go to `device` in chunks, the census there
 // (garlic_bed_census) finds every row's counted allele -- the first non-missing allele of the TPED line the row stands for,
 // on which a het reads "A1 A2" -- and the two integers of its frequency; the division is the host's, :141.  HapData::bed /
@@ -210,7 +234,9 @@ IndData *readIndData3(const std::string &filename, int numInd);                 
 std::vector<GenoLikeData *> *readTGLSData(const std::string &filename, int expectedLoci, int expectedInd,
                                           std::vector<MapData *> *mapDataByChr,
                                           const std::string &GL_TYPE,
-                                          bool compact = false);   // compact: ::codes / ::codes16 where the values allow, else ::data   // :1516
+                                          bool compact = false,    // compact: ::codes / ::codes16 where the values allow, else ::data   // :1516
+                                          // --keep: the file has fileInd + 4 fields per line and individual i is its column cols[i]
+                                          const std::vector<int> *cols = nullptr, int fileInd = 0);
 std::vector<FreqData *> *readFreqData(const std::string &freqfile,
                                       std::vector<MapData *> *mapDataByChr);        // :1345
 void writeFreqData(const std::string &freqOutfile, std::vector<FreqData *> *freqDataByChr,

@@ -28,6 +28,7 @@
 #include <cstring>
 #include <iostream>
 #include <sstream>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -62,6 +63,11 @@ struct Args {
     // --features / --tped-counting / --tfam-counting (:177-189, declared there and never wired in: the reference leaves the
     // stage to src/count_features_in_roh.pl); --roh-bed: extension, count on an existing calls file and exit
     std::string features, tped_counting, tfam_counting, roh_bed;
+    // extensions, PLINK input only: --keep F runs the individuals listed in F (a PLINK keep file) as if the file set held
+    // only them; --pops all | NAME ... runs every listed family ID of the .fam in turn, each as --keep of its members with
+    // --out <out>.<NAME>
+    std::string keep;
+    std::vector<std::string> pops;
 };
 
 [[noreturn]] void usage(const char *msg)
@@ -90,7 +96,14 @@ struct Args {
                  "         [--roh-bed F --features F --tped-counting T [--tfam-counting M] --out P]   (no genotype input: the same table\n"
                  "                    for the calls of an existing .roh.bed, <out>.feature.counts, then exit)\n"
                  "         (--bfile / --bed --bim --fam: PLINK SNP-major .bed input, read on the device; not with --tped / --tfam /\n"
-                 "          --phased; --genotype-cache F is then written from the .bed, never read)\n";
+                 "          --phased; --genotype-cache F is then written from the .bed, never read)\n"
+                 "         [--keep F]   (with PLINK input: the run is that of a file set holding only the individuals of F, a PLINK keep\n"
+                 "                       file of `FID IID` lines, in the .fam's order; they must share one family ID, the population's\n"
+                 "                       name; the subset is cut out of the image on the device)\n"
+                 "         [--pops all | NAME [NAME ...]]   (with PLINK input: every listed family ID of the .fam in turn -- all: every\n"
+                 "                       distinct one, first seen first -- each as --keep of its members with --out <out>.<NAME>; one\n"
+                 "                       upload of the file per device serves all; stops at the first population that fails; not with\n"
+                 "                       --keep, --freq-file, --genotype-cache or --roh-bed)\n";
     exit(1);
 }
 
@@ -143,6 +156,11 @@ Args parse(int argc, char **argv)
         else if (f == "--tped-counting") a.tped_counting = val();
         else if (f == "--tfam-counting") a.tfam_counting = val();
         else if (f == "--roh-bed") a.roh_bed = val();
+        else if (f == "--keep") a.keep = val();
+        else if (f == "--pops") {
+            while (i + 1 < argc && !(argv[i + 1][0] == '-' && argv[i + 1][1] == '-')) a.pops.push_back(argv[++i]);
+            if (a.pops.empty()) usage("--pops needs all, or family IDs of the .fam");
+        }
         else if (f == "--M") a.M = atoi(val().c_str());
         else if (f == "--mu") a.mu = atof(val().c_str());
         else if (f == "--threads") a.threads = atoi(val().c_str());
@@ -168,6 +186,8 @@ Args parse(int argc, char **argv)
         if (a.features.empty() || a.tped_counting.empty()) usage("feature counts need --features and --tped-counting");
         if (a.tfam_counting.empty()) a.tfam_counting = featureTfamOf(a.tped_counting);
     }
+    if (!a.keep.empty() && !a.pops.empty()) usage("--keep and --pops exclude each other (--pops is --keep of every listed population in turn)");
+    if (!a.pops.empty() && !a.roh_bed.empty()) usage("--pops with --roh-bed: --roh-bed counts on existing calls and reads no populations");
     if (!a.roh_bed.empty()) {      // counts on an existing calls file: nothing else is read
         if (!a.tped.empty() || !a.tfam.empty() || !a.bfile.empty() || !a.bed.empty()) usage("--roh-bed counts on existing calls and takes no genotype input");
         if (a.devices.empty()) a.devices.push_back(0);
@@ -183,7 +203,11 @@ Args parse(int argc, char **argv)
         if (!a.tped.empty() || !a.tfam.empty()) usage("--bfile / --bed and --tped / --tfam exclude each other");
         if (a.phased) usage("--phased with --bfile: a .bed carries no phase");
         a.tfam = a.fam;      // the .fam is the TFAM format
+    } else if (!a.keep.empty() || !a.pops.empty()) {
+        usage("--keep / --pops select individuals of a PLINK .fam and need --bfile (or --bed --bim --fam), not --tped");
     } else if (a.tped.empty() || a.tfam.empty()) usage("--tped and --tfam (or --bfile) are required");
+    if (!a.pops.empty() && a.freq_file != "none") usage("--pops with --freq-file: one frequency file cannot serve several populations");
+    if (!a.pops.empty() && a.cache != "none") usage("--pops with --genotype-cache: one cache file cannot hold several populations");
     if (a.build == "none" && a.centromere == "none") usage("must provide --build or --centromere (garlic-cli.cpp:285-291)");
     if ((a.error <= 0 || a.error >= 1) && a.tgls == "none")
         usage("Genotype error rate must be > 0 and < 1, or a TGLS file must be provided.");
@@ -219,21 +243,13 @@ void writeFeed(const std::string &path, const DoubleData *d)
     fclose(f);
     std::cerr << "Wrote " << path << " (" << d->size << " window scores)\n";
 }
-} // namespace
 
-int main(int argc, char **argv)
+// One run of the tool on one population: everything from the ingest to the last output of `a`.  `features`: the loaded
+// --features table or NULL.  With `keep` (--keep / --pops) the population is the individuals `keep` (ascending indices into
+// `fam`, the .fam's lines) of the open PLINK file set `full`; otherwise the inputs are read as `a` names them.
+int run(const Args &a, FeatureData *features, BedFile *full, const std::vector<FamEntry> *fam, const std::vector<int> *keep)
 {
-    const Args a = parse(argc, argv);
     try {
-        struct FeatureOwner {
-            FeatureData *d = nullptr;
-            ~FeatureOwner() { releaseFeatureCounts(d); }
-        } fdata;
-        if (!a.features.empty()) fdata.d = loadFeatureCounts(a.features, a.tped_counting, a.tfam_counting);
-        if (!a.roh_bed.empty()) {
-            featureCountsFromBed(fdata.d, a.roh_bed, a.out + ".feature.counts", a.devices[0]);
-            return 0;
-        }
         centromere centro(a.build, a.centromere, "none");
         int numLoci = 0, numInd = 0;
         std::vector<HapData *> *haps = nullptr; std::vector<MapData *> *maps = nullptr;
@@ -255,8 +271,10 @@ int main(int argc, char **argv)
         if (devices.empty())
             for (int d = 0; d < a.gpus; d++) devices.push_back(d);
         FILE *probe = a.cache == "none" || !a.bed.empty() ? nullptr : fopen(a.cache.c_str(), "rb");
+        if (keep) ind = indDataOfKept(*fam, *keep, a.fam);      // the single-population check, over the kept individuals
         if (!a.bed.empty()) {   // PLINK input: census on the first device; the cache, if asked for, is written from it
-            loadBedData(a.bed, a.bim, a.fam, numLoci, numInd, &haps, &maps, &freqs, a.resample, a.resample_seed, devices[0]);
+            if (keep) loadBedSubset(full, *keep, numLoci, numInd, &haps, &maps, &freqs, a.resample, a.resample_seed, devices[0]);
+            else loadBedData(a.bed, a.bim, a.fam, numLoci, numInd, &haps, &maps, &freqs, a.resample, a.resample_seed, devices[0]);
             if (a.resample > 0) std::cerr << "Allele frequencies resampled: " << a.resample << "\n";
             if (a.cache != "none") {
                 writeGenotypeCache(a.cache, haps, maps, freqs);
@@ -279,16 +297,19 @@ int main(int argc, char **argv)
                 std::cerr << "Wrote genotype cache " << a.cache << "\n";
             }
         }
-        std::string pop;
-        int nindFam = 0;
-        scanIndData3(a.tfam, nindFam, pop);
-        if (nindFam != numInd) { std::cerr << "ERROR: tfam lists " << nindFam << " individuals, tped has " << numInd << "\n"; return 1; }
-        ind = readIndData3(a.tfam, numInd);
+        if (!keep) {
+            std::string pop;
+            int nindFam = 0;
+            scanIndData3(a.tfam, nindFam, pop);
+            if (nindFam != numInd) { std::cerr << "ERROR: tfam lists " << nindFam << " individuals, tped has " << numInd << "\n"; return 1; }
+            ind = readIndData3(a.tfam, numInd);
+        }
         std::cerr << "Loaded " << numLoci << " loci x " << numInd << " individuals (" << maps->size() << " chromosomes)\n";
 
         const bool USE_GL = a.tgls != "none";
         if (USE_GL) {
-            gls = readTGLSData(a.tgls, numLoci, numInd, maps, a.gl_type, /*compact=*/true); // rows in pre-filter TPED order
+            // rows in pre-filter TPED order; under --keep the kept individuals' columns of the whole .fam's
+            gls = readTGLSData(a.tgls, numLoci, numInd, maps, a.gl_type, /*compact=*/true, keep, keep ? (int)fam->size() : 0);
             // the form each chromosome took: one byte per genotype up to 256 distinct values, two up to 65,536, else doubles
             std::cerr << "Genotype likelihoods (" << a.gl_type << "):";
             for (size_t c = 0; c < gls->size(); c++) {
@@ -377,9 +398,9 @@ int main(int argc, char **argv)
             const std::string stem = single ? a.out : a.out + "." + std::to_string(W) + "SNPs";
             writeROHData(stem + ".roh.bed", roh, maps, bounds, ind->pop,
                          "1.1.6a", a.cm);      // the track lines name the format's version (garlic VERSION); this tool says who it is on stderr
-            if (fdata.d) {
+            if (features) {
                 try {
-                    engine.featureCounts(fdata.d, roh, maps, bounds, stem + ".feature.counts");
+                    engine.featureCounts(features, roh, maps, bounds, stem + ".feature.counts");
                 } catch (...) {
                     releaseROHData(roh);
                     releaseROHLength(len);
@@ -526,6 +547,68 @@ int main(int argc, char **argv)
             std::cerr << "NOTE: --auto-winsize picks among the feeds above in GARLIC's KDE stage (Phase II, not part of this tool); "
                          "--winsize-stream lets that stage ask for further window sizes on the resident panel\n";
         term_report();
+    } catch (...) {
+        return 1;
+    }
+    return 0;
+}
+} // namespace
+
+int main(int argc, char **argv)
+{
+    const Args a = parse(argc, argv);
+    try {
+        struct FeatureOwner {
+            FeatureData *d = nullptr;
+            ~FeatureOwner() { releaseFeatureCounts(d); }
+        } fdata;
+        if (!a.features.empty()) fdata.d = loadFeatureCounts(a.features, a.tped_counting, a.tfam_counting);
+        if (!a.roh_bed.empty()) {
+            featureCountsFromBed(fdata.d, a.roh_bed, a.out + ".feature.counts", a.devices[0]);
+            return 0;
+        }
+        if (a.keep.empty() && a.pops.empty()) return run(a, fdata.d, nullptr, nullptr, nullptr);
+        // --keep / --pops: the whole file set is opened once; every run extracts its individuals from the image on the device
+        std::vector<FamEntry> fam;
+        std::vector<int> kept;
+        std::vector<FamFamily> todo;
+        try {
+            fam = readFam(a.fam);
+            if (!a.keep.empty()) kept = readKeepFile(a.keep, fam);
+            else {
+                const std::vector<FamFamily> all = famFamilies(fam);
+                if (a.pops.size() == 1 && a.pops[0] == "all") todo = all;
+                else
+                    for (const std::string &name : a.pops) {
+                        size_t k = 0;
+                        while (k < all.size() && all[k].fid != name) k++;
+                        if (k == all.size()) throw std::runtime_error("--pops: no family ID " + name + " in " + a.fam);
+                        todo.push_back(all[k]);
+                    }
+                if (todo.empty()) throw std::runtime_error("no individuals in " + a.fam);
+            }
+        } catch (const std::exception &e) {
+            std::cerr << "ERROR: " << e.what() << "\n";
+            return 1;
+        }
+        struct FileOwner {
+            BedFile *b = nullptr;
+            ~FileOwner() { releaseBedFile(b); }
+        } file;
+        file.b = openBedFile(a.bed, a.bim, a.fam, /*anyPopulations=*/true);
+        file.b->refs = 1;
+        if (!a.keep.empty()) return run(a, fdata.d, file.b, &fam, &kept);
+        file.b->hold_images = true;      // one upload per device serves every population
+        for (const FamFamily &f : todo) {
+            Args one = a;
+            one.out = a.out + "." + f.fid;
+            std::cerr << "Population " << f.fid << ": " << f.members.size() << " individuals, --out " << one.out << "\n";
+            const int rc = run(one, fdata.d, file.b, &fam, &f.members);
+            if (rc) {
+                std::cerr << "ERROR: population " << f.fid << " failed; stopping\n";
+                return rc;
+            }
+        }
     } catch (...) {
         return 1;
     }

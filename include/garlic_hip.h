@@ -62,7 +62,8 @@ extern "C" {
  *    garlic_feature_counts_info (likewise); GARLIC_KDE_MAX_FEEDS, garlic_feed_kde_multi, garlic_lod_kde_multi,
  *    garlic_feed_kde_multi_info (likewise); garlic_kde_part_set, garlic_kde_part_set_create, garlic_lod_kde_part_set,
  *    garlic_kde_part_set_destroy, garlic_kde_part_set_counts, garlic_kde_part_set_moment, garlic_kde_part_set_rank,
- *    garlic_kde_part_set_sums, garlic_kde_parts_multi, garlic_kde_parts_multi_info (likewise) */
+ *    garlic_kde_part_set_sums, garlic_kde_parts_multi, garlic_kde_parts_multi_info (likewise); garlic_bed_extract,
+ *    garlic_bed_get_rows (likewise) */
 #define GARLIC_HIP_ABI_VERSION 8
 
 #define GARLIC_OK 0
@@ -181,6 +182,22 @@ int garlic_bed_census(garlic_bed *bed, int32_t *counts /* [nrows][2]: nalleles, 
 int garlic_panel_set_genotypes_bed(garlic_panel *panel, garlic_bed *bed, int64_t ind_offset,
                                    const int64_t *dest_locus /* [nrows] */);
 int garlic_bed_destroy(garlic_bed *bed);
+/* A column subset of an image as a new image on the same context and device -- one population of a multi-population file:
+ * nrows = src's, nind_total = n_idx, and individual i of every new row is individual ind_idx[i] of the same row of src, in
+ * PLINK's codes, unchanged; rows of (n_idx + 3) / 4 bytes back to back, the pad bits behind individual n_idx - 1 zero.
+ * ind_idx is a host array in any order, repeats allowed, every entry in [0, src nind_total).  The result is complete (every
+ * row set), its census has not been run, and it is an ordinary garlic_bed: garlic_bed_census is the census of the subset
+ * alone in ind_idx order ("first non-missing genotype" = first in the new row), garlic_panel_set_genotypes_bed cuts shards
+ * out of it by ind_offset, garlic_bed_destroy frees it.  It does not depend on src once the call has returned (src may be
+ * destroyed); it shares src's context, which must outlive it.  The work runs on the context's stream.
+ * GARLIC_ERR_STATE: src is not fully set.  GARLIC_ERR_INVALID: NULL arguments, n_idx < 1, n_idx >= 2^30, an index out of
+ * range (the message names the first).  GARLIC_ERR_NOMEM: the new image does not fit; *out is untouched and nothing is left
+ * allocated. */
+int garlic_bed_extract(garlic_bed *src, const int32_t *ind_idx, int32_t n_idx, garlic_bed **out);
+/* Rows [row_begin, row_begin + row_count) of an image, row_bytes (>= (nind_total + 3) / 4) apart, to host or device memory;
+ * bytes past a row's own are untouched.  (What garlic_bed_set_rows put in, or what garlic_bed_extract made.) */
+int garlic_bed_get_rows(garlic_bed *bed, int64_t row_begin, int64_t row_count, uint8_t *rows, int64_t row_bytes,
+                        int32_t where);
 
 /* GenoLikeData::data (src/garlic-data.h:91): per-genotype error probabilities, already converted
  * as readTGLSData does (src/garlic-data.cpp:1557-1576); same addressing as genotypes.  Any doubles.

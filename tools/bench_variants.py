@@ -44,6 +44,9 @@ both orders, and on the same data one thread of std::sort and numpy's sort on th
 --modes bed_ingest: PLINK .bed input -- the census and the pack of a panel cut from a --file-inds file by HIP events with the bytes
 each moves, and with --bed-prefix the whole garlic-lod run from .bed, TPED and genotype cache (--tree: the latter two with the
 parent's tool); shapes 2M x 1280 and 10M x 1250 of a 10k-individual file; the table goes to profiles/bed_ingest_ab.txt.
+--modes bed_extract: garlic_bed_extract of --inds individuals (1250) out of an image of --snps rows (1000000) x --file-inds
+individuals (10000), scattered and contiguous, by HIP events: milliseconds and (source + written bytes) / time against the HBM
+rate (profiles/bed_extract_ab.txt).
 --modes ld_phased: the warm garlic_panel_compute_ld(phased = 1) call (weights only) for every size of --winsizes on one resident
 panel -- host clock around the synchronous call and the ordered-sum kernel by the library's HIP events, median and spread
 of --steps calls -- with the form the call took where the library reports it; and the phase upload from host memory both
@@ -220,6 +223,61 @@ def tgls_dict16_leg(args):
     if hasattr(panel, "tgls_terms_info"):
         line["terms_info"] = panel.tgls_terms_info()
     print(json.dumps(line), flush=True)
+
+
+def bed_extract_leg(args):
+    """garlic_bed_extract on one device: an image of --snps rows x --file-inds individuals (random bytes made on the device),
+    --inds of them extracted -- scattered over the whole file (random, ascending) and contiguous (a block in the middle).  The
+    context runs on a torch stream, so torch's events (HIP events) bracket the call: the upload of the index list, the
+    allocation of the new image, the kernel, the stream wait.  Per leg: milliseconds (median) and (source bytes + written
+    bytes) / time against the HBM rate, for the source bytes the form must touch (the 16-byte pieces of the span's byte range
+    per row, whole rows when the indices are spread over them) and for the whole source image."""
+    import torch
+    from garlic_amd import abi
+
+    HBM_GBPS = 8000.0      # MI355X peak
+    torch.cuda.set_device(0)
+    dev = torch.device("cuda", 0)
+    nrows, nfile, n_idx = args.snps, args.file_inds, args.inds
+    rb = (nfile + 3) // 4
+    stream = torch.cuda.Stream()
+    ctx = abi.Context(0, stream=stream.cuda_stream)
+    bed = abi.Bed(ctx, nrows, nfile)
+    g = torch.Generator(device=dev)
+    g.manual_seed(5)
+    chunk = max(1, (256 << 20) // rb)
+    for r in range(0, nrows, chunk):
+        rows = torch.randint(0, 256, (min(chunk, nrows - r), rb), generator=g, device=dev, dtype=torch.uint8)
+        torch.cuda.synchronize()
+        bed.set_rows_device(rows.data_ptr(), rb, r, rows.shape[0])
+    del rows
+    rng = np.random.default_rng(7)
+    start = (nfile - n_idx) // 2
+    legs = {"scattered": np.sort(rng.choice(nfile, size=n_idx, replace=False)).astype(np.int32),
+            "contiguous": np.arange(start, start + n_idx, dtype=np.int32)}
+    for name, idx in legs.items():
+        ms = []
+        for k in range(1 + args.steps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            sub = bed.extract(idx)
+            e1.record(stream)
+            torch.cuda.synchronize()
+            sub.destroy()
+            if k:
+                ms.append(e0.elapsed_time(e1))
+        t = float(np.median(ms))
+        span = 8192      # subset individuals per workgroup: every span reads its own byte range of a row
+        touched = sum(((int(idx[a:a + span].max()) >> 2) - (int(idx[a:a + span].min()) >> 2) + 16) for a in range(0, n_idx, span))
+        written = nrows * ((n_idx + 3) // 4)
+        line = {"mode": "bed_extract", "leg": name, "rows": nrows, "file_inds": nfile, "inds": n_idx, "repeats": args.steps,
+                "call_ms_median": t, "source_bytes_touched": nrows * touched, "source_image_bytes": nrows * rb, "written_bytes": written,
+                "touched_plus_written_GBps": (nrows * touched + written) / (t * 1e-3) / 1e9,
+                "image_plus_written_GBps": (nrows * rb + written) / (t * 1e-3) / 1e9}
+        line["fraction_of_HBM_peak_touched"] = line["touched_plus_written_GBps"] / HBM_GBPS
+        print(json.dumps(line), flush=True)
+    bed.destroy()
+    ctx.close()
 
 
 def bed_ingest_leg(args):
@@ -1083,6 +1141,8 @@ def main():
         return kde_multi_leg(args)
     if args.modes == "kde_parts_multi":
         return kde_parts_multi_leg(args)
+    if args.modes == "bed_extract":
+        return bed_extract_leg(args)
     if args.modes == "bed_ingest":
         return bed_ingest_leg(args)
     if args.modes == "ld_phased":
