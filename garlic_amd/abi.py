@@ -51,7 +51,7 @@ SYMBOLS = [
     "garlic_kde_part_create", "garlic_lod_kde_part", "garlic_kde_part_destroy", "garlic_kde_part_count",
     "garlic_kde_part_moment", "garlic_kde_part_rank", "garlic_kde_part_sums", "garlic_kde_parts", "garlic_kde_parts_info",
     "garlic_feature_set_create", "garlic_feature_set_destroy", "garlic_feature_set_rows", "garlic_feature_set_sites",
-    "garlic_feature_counts", "garlic_feature_counts_info",
+    "garlic_feature_counts", "garlic_feature_counts_info", "garlic_feature_set_rows_bed", "garlic_feature_set_get_rows",
     "garlic_feed_kde_multi", "garlic_lod_kde_multi", "garlic_feed_kde_multi_info",
     "garlic_kde_part_set_create", "garlic_lod_kde_part_set", "garlic_kde_part_set_destroy", "garlic_kde_part_set_counts",
     "garlic_kde_part_set_moment", "garlic_kde_part_set_rank", "garlic_kde_part_set_sums", "garlic_kde_parts_multi",
@@ -228,6 +228,8 @@ def lib():
     L.garlic_feature_set_destroy.argtypes = [_vp]
     L.garlic_feature_set_rows.argtypes = [_vp, _vp, C.c_int64, C.c_int64, C.c_int64]
     L.garlic_feature_set_sites.argtypes = [_vp, _i32p, _i32p, _i32p]
+    L.garlic_feature_set_rows_bed.argtypes = [_vp, _vp, _vp, _vp, C.c_int64, C.c_int64]
+    L.garlic_feature_set_get_rows.argtypes = [_vp, C.c_int64, C.c_int64, _vp, C.c_int64]
     L.garlic_feature_counts.argtypes = [_vp, _vp, C.c_int64, C.c_int32, C.c_int32, _vp, C.c_int32]
     L.garlic_feature_counts_info.argtypes = [_vp, _i64p, _i64p, _i64p, C.POINTER(C.c_float)]
     L.garlic_gmm_fit.argtypes = [_vp, _vp, C.c_int64, C.c_int32, C.c_int32, _f64p, _f64p, _f64p, C.c_int32, C.c_double, C.POINTER(Gmm)]
@@ -462,6 +464,24 @@ class FeatureSet:
         rows = np.ascontiguousarray(rows, dtype=np.uint8)
         assert rows.ndim == 2
         check(lib().garlic_feature_set_rows(self.handle, _vp(rows.ctypes.data), rows.shape[1], int(row_begin), rows.shape[0]))
+
+    def set_rows_bed(self, bed, file_row, allele, row_begin=0):
+        """rows row_begin .. from a Bed image on the same device: row row_begin + k is image row file_row[k], hom A1 (allele[k]
+        = 0), hom A2 (1) or empty (2)"""
+        file_row = np.ascontiguousarray(file_row, dtype=np.int64)
+        allele = np.ascontiguousarray(allele, dtype=np.uint8)
+        assert file_row.ndim == 1 and file_row.shape == allele.shape
+        n = file_row.shape[0]
+        check(lib().garlic_feature_set_rows_bed(self.handle, bed.handle, _vp(file_row.ctypes.data) if n else None,
+                                                _vp(allele.ctypes.data) if n else None, int(row_begin), n))
+
+    def get_rows(self, row_begin=0, row_count=None):
+        """uint8 [row_count, (nind + 7) // 8]: the rows as they stand on the device, in set_rows' format (waits for the set's work)"""
+        row_count = self.nrows - row_begin if row_count is None else row_count
+        rows = np.zeros((max(row_count, 0), (self.nind + 7) // 8), dtype=np.uint8)
+        check(lib().garlic_feature_set_get_rows(self.handle, int(row_begin), int(row_count), _vp(rows.ctypes.data) if rows.size else None,
+                                                rows.shape[1]))
+        return rows
 
     def set_sites(self, chr, pos, effect):
         a = [np.ascontiguousarray(v, dtype=np.int32) for v in (chr, pos, effect)]

@@ -1,4 +1,5 @@
-// PLINK .bed rows on the device (gfx950, wave64): the allele census and the recode into the packed panel.
+// PLINK .bed rows on the device (gfx950, wave64): the allele census, the recode into the packed panel, the column subset
+// and the hom rows of a feature set.
 //
 // A .bed row holds the N individuals of one SNP at 2 bits each, 4 per byte, individual j at bits 2 * (j % 4) of byte j / 4:
 // 00 hom A1, 01 missing, 10 het, 11 hom A2.  GARLIC counts "the first non-missing allele on the line"
@@ -283,6 +284,102 @@ bed_extract_kernel(const uint8_t *__restrict__ image, int64_t image_bytes, int64
                 for (int t = 0; t < word_bytes; t++) dst[t] = (uint8_t)(word >> (8 * t));
             }
         }
+    }
+}
+
+// .bed rows -> the hom rows of a feature set (feature_kernels.hpp): output row k is "homozygous for A1" (selector 0: code 00,
+// ~lo & ~hi), "homozygous for A2" (1: code 11, lo & hi) or empty (2) of image row file_row[k], one bit per individual, stored
+// block-major: the word of the 64 individuals of block blk at bits[blk * set_rows + row_begin + k].  file_row comes in any
+// order and may repeat (the two alleles of one site).  Integer work, exact; no atomics, no LDS.
+//
+// A thread owns one output row and BED_HOM_BLOCKS consecutive blocks: 64 contiguous bytes of its image row, which start at any
+// byte -- it reads the 5 aligned 16-byte pieces that hold them (those that begin inside the row, under the image_bytes guard of
+// bed_pack_kernel: nothing past the image is read, pieces that are not read stay zero), shifts the 80 bytes down by the row's
+// misalignment in registers and compacts every 2 x 64 code bits to 64 hom bits by mask and shift.  Adjacent lanes take adjacent
+// k, so each of a wave's four stores is 512 contiguous bytes; the waves of a workgroup take consecutive block groups of the
+// same 64 rows, so the 64-byte sectors a row's pieces share between two groups are fetched by one CU.  Bits of individuals
+// >= nind are cleared by the mask of the valid fields whatever the image holds there: the pad bits of a row's last byte, the
+// neighbouring row's bytes in a piece, and the zeros of a piece that was not read would otherwise read as genotypes (a zero pad
+// is code 00, "hom A1").
+constexpr int BED_HOM_BLOCKS = 4;      // (the kernel's body is written out for 4)
+
+// the low bits of the 32 two-bit fields of x, gathered into bits 0 .. 31
+__device__ __forceinline__ uint64_t bed_gather_fields(uint64_t x)
+{
+    x &= BED_LO;
+    x = (x | (x >> 1)) & 0x3333333333333333ull;
+    x = (x | (x >> 2)) & 0x0F0F0F0F0F0F0F0Full;
+    x = (x | (x >> 4)) & 0x00FF00FF00FF00FFull;
+    x = (x | (x >> 8)) & 0x0000FFFF0000FFFFull;
+    return (x | (x >> 16)) & 0x00000000FFFFFFFFull;
+}
+
+// one aligned 16-byte piece as two words, or zeros
+__device__ __forceinline__ void bed_piece(const uint8_t *__restrict__ image, int64_t at, bool read, uint64_t &lo, uint64_t &hi)
+{
+    uint4 v = make_uint4(0, 0, 0, 0);
+    if (read) v = *reinterpret_cast<const uint4 *>(image + at);
+    lo = (uint64_t)v.x | ((uint64_t)v.y << 32);
+    hi = (uint64_t)v.z | ((uint64_t)v.w << 32);
+}
+
+// the hom word of block blk from its 16 code bytes, which begin sh bits into the three words a, b, c
+__device__ __forceinline__ uint64_t bed_hom_word(uint64_t a, uint64_t b, uint64_t c, int sh, uint32_t sel, int32_t nind, int64_t blk)
+{
+    uint64_t word = 0;
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        const uint64_t u = h ? b : a, v = h ? c : b;
+        const uint64_t x = sh ? (u >> sh) | (v << (64 - sh)) : u;        // field t: individual 64 blk + 32 h + t
+        const int64_t left = (int64_t)nind - (64 * blk + 32 * h);
+        const uint64_t valid = bed_field_mask(0, left < 0 ? 0 : (left < 32 ? (int)left : 32));
+        const uint64_t hom = (sel == 0 ? ~(x | (x >> 1)) : sel == 1 ? (x & (x >> 1)) : 0ull) & valid;
+        word |= bed_gather_fields(hom) << (32 * h);
+    }
+    return word;
+}
+
+__global__ void __launch_bounds__(256)
+bed_hom_rows_kernel(const uint8_t *__restrict__ image, int64_t image_bytes, int64_t row_bytes, int32_t nind,
+                    const int64_t *__restrict__ file_row, const uint8_t *__restrict__ allele, int64_t row_begin, int64_t row_count,
+                    int64_t set_rows, int32_t nblk, uint64_t *__restrict__ bits)
+{
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    const int64_t ngroups = ((int64_t)nblk + BED_HOM_BLOCKS - 1) / BED_HOM_BLOCKS;
+    const int64_t nitems = ((row_count + WAVE - 1) / WAVE) * ngroups;      // (64 rows) x (block group), the group fastest
+    for (int64_t item = wave; item < nitems; item += nwaves) {
+        const int64_t tile = item / ngroups;
+        const int64_t blk0 = (item - tile * ngroups) * BED_HOM_BLOCKS;
+        const int64_t k = tile * WAVE + lane;
+        if (k >= row_count) continue;
+        const uint32_t sel = allele[k];
+        // (a selector 2 reads nothing: file row 0 stands in for its addresses)
+        const int64_t row = (sel < 2 ? file_row[k] : 0) * row_bytes;
+        const int64_t begin = row + 16 * blk0;                       // the byte of the group's first individual
+        const int64_t end = row + row_bytes;                         // one past the row's last byte
+        const int64_t a0 = begin & ~(int64_t)15;
+        const int64_t last = (end < image_bytes - 15 ? end : image_bytes - 15);      // a piece is read iff it begins below this
+        const bool live = sel < 2;
+        uint64_t w0, w1, w2, w3, w4, w5, w6, w7, w8, w9;
+        bed_piece(image, a0, live && a0 < last, w0, w1);
+        bed_piece(image, a0 + 16, live && a0 + 16 < last, w2, w3);
+        bed_piece(image, a0 + 32, live && a0 + 32 < last, w4, w5);
+        bed_piece(image, a0 + 48, live && a0 + 48 < last, w6, w7);
+        bed_piece(image, a0 + 64, live && a0 + 64 < last, w8, w9);
+        // down by the row's misalignment: first by a whole word, then by the bytes inside a word (selects: all in registers)
+        const int s = (int)(begin & 15);
+        const bool by_word = s >= 8;
+        const int sh = 8 * (s & 7);
+        const uint64_t c0 = by_word ? w1 : w0, c1 = by_word ? w2 : w1, c2 = by_word ? w3 : w2, c3 = by_word ? w4 : w3,
+                       c4 = by_word ? w5 : w4, c5 = by_word ? w6 : w5, c6 = by_word ? w7 : w6, c7 = by_word ? w8 : w7,
+                       c8 = by_word ? w9 : w8;
+        uint64_t *out = bits + row_begin + k;
+        if (blk0 < nblk) out[blk0 * set_rows] = bed_hom_word(c0, c1, c2, sh, sel, nind, blk0);
+        if (blk0 + 1 < nblk) out[(blk0 + 1) * set_rows] = bed_hom_word(c2, c3, c4, sh, sel, nind, blk0 + 1);
+        if (blk0 + 2 < nblk) out[(blk0 + 2) * set_rows] = bed_hom_word(c4, c5, c6, sh, sel, nind, blk0 + 2);
+        if (blk0 + 3 < nblk) out[(blk0 + 3) * set_rows] = bed_hom_word(c6, c7, c8, sh, sel, nind, blk0 + 3);
     }
 }
 

@@ -7269,6 +7269,73 @@ int garlic_feature_set_rows(garlic_feature_set *fs, const uint8_t *bits, int64_t
     });
 }
 
+// the same rows from a .bed image on the set's device (bed_hom_rows_kernel): the plan's two lists are the only host bytes
+int garlic_feature_set_rows_bed(garlic_feature_set *fs, garlic_bed *b, const int64_t *file_row, const uint8_t *allele, int64_t row_begin,
+                                int64_t row_count)
+{
+    if (!fs || !b) return fail(GARLIC_ERR_INVALID, "feature set rows from a bed image: set and image are required");
+    if (row_count > 0 && (!file_row || !allele)) return fail(GARLIC_ERR_INVALID, "feature set rows from a bed image: file_row and allele are required");
+    if (fs->nind != b->nind)
+        return fail(GARLIC_ERR_INVALID, "the feature set has %d individuals, the bed image %d", fs->nind, b->nind);
+    if (b->ctx->device != fs->ctx->device)
+        return fail(GARLIC_ERR_INVALID, "the bed image is on device %d, the feature set on device %d", b->ctx->device, fs->ctx->device);
+    if (row_begin < 0 || row_count < 0 || row_begin + row_count > fs->nrows)
+        return fail(GARLIC_ERR_INVALID, "row range [%lld,+%lld) outside feature set of %lld rows", (long long)row_begin, (long long)row_count, (long long)fs->nrows);
+    if (b->n_set != b->nrows)
+        return fail(GARLIC_ERR_STATE, "feature set rows need every row of the bed image: %lld of %lld set", (long long)b->n_set, (long long)b->nrows);
+    for (int64_t k = 0; k < row_count; k++) {
+        if (file_row[k] < 0 || file_row[k] >= b->nrows)
+            return fail(GARLIC_ERR_INVALID, "file_row[%lld] = %lld outside the image's %lld rows", (long long)k, (long long)file_row[k], (long long)b->nrows);
+        if (allele[k] > 2) return fail(GARLIC_ERR_INVALID, "allele[%lld] = %d (0 = hom A1, 1 = hom A2, 2 = none)", (long long)k, (int)allele[k]);
+    }
+    if (row_count == 0) return GARLIC_OK;
+    int rc;
+    if ((rc = set_device(fs->ctx))) return rc;
+    hipStream_t s = fs->ctx->stream;      // (every call that writes the image has waited for its own stream before it returned)
+    DevBuf<int64_t> d_row;
+    DevBuf<uint8_t> d_allele;
+    if ((rc = d_row.reserve((size_t)row_count)) || (rc = d_allele.reserve((size_t)row_count))) return rc;
+    HIP_TRY(hipMemcpyAsync(d_row.p, file_row, sizeof(int64_t) * (size_t)row_count, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_allele.p, allele, (size_t)row_count, hipMemcpyHostToDevice, s));
+    const int64_t ngroups = ((int64_t)fs->nblk + BED_HOM_BLOCKS - 1) / BED_HOM_BLOCKS;
+    const int64_t nitems = ((row_count + WAVE - 1) / WAVE) * ngroups;
+    const unsigned grid = (unsigned)std::min<int64_t>((nitems + 3) / 4, 8 * (int64_t)fs->ctx->n_cu);
+    hipLaunchKernelGGL(bed_hom_rows_kernel, dim3(grid), dim3(256), 0, s, b->d_image.p, b->image_bytes, b->row_bytes, b->nind, d_row.p,
+                       d_allele.p, row_begin, row_count, fs->nrows, fs->nblk, fs->bits.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));      // the two lists are free again; the image may go
+    return GARLIC_OK;
+}
+
+int garlic_feature_set_get_rows(garlic_feature_set *fs, int64_t row_begin, int64_t row_count, uint8_t *bits, int64_t row_bytes)
+{
+    if (!fs) return fail(GARLIC_ERR_INVALID, "feature set is NULL");
+    if (row_count > 0 && !bits) return fail(GARLIC_ERR_INVALID, "feature set get_rows: bits is NULL");
+    const int64_t own = ((int64_t)fs->nind + 7) / 8;
+    if (row_bytes < own) return fail(GARLIC_ERR_INVALID, "row_bytes %lld < %d bits", (long long)row_bytes, fs->nind);
+    if (row_begin < 0 || row_count < 0 || row_begin + row_count > fs->nrows)
+        return fail(GARLIC_ERR_INVALID, "row range [%lld,+%lld) outside feature set of %lld rows", (long long)row_begin, (long long)row_count, (long long)fs->nrows);
+    int rc;
+    if ((rc = set_device(fs->ctx))) return rc;
+    hipStream_t s = fs->ctx->stream;
+    if (row_count == 0) {
+        HIP_TRY(hipStreamSynchronize(s));
+        return GARLIC_OK;
+    }
+    // the words [blk][row] of the range, then the transpose into byte rows on the host (a door for checks, not a hot path)
+    std::vector<uint64_t> words((size_t)fs->nblk * (size_t)row_count);
+    HIP_TRY(hipMemcpy2DAsync(words.data(), sizeof(uint64_t) * (size_t)row_count, fs->bits.p + row_begin, sizeof(uint64_t) * (size_t)fs->nrows,
+                             sizeof(uint64_t) * (size_t)row_count, (size_t)fs->nblk, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int64_t r = 0; r < row_count; r++)
+        for (int64_t blk = 0; blk < fs->nblk; blk++) {
+            const uint64_t w = words[(size_t)(blk * row_count + r)];
+            const int64_t n = std::min<int64_t>(8, own - 8 * blk);
+            for (int64_t t = 0; t < n; t++) bits[r * row_bytes + 8 * blk + t] = (uint8_t)(w >> (8 * t));
+        }
+    return GARLIC_OK;
+}
+
 int garlic_feature_set_sites(garlic_feature_set *fs, const int32_t *chr, const int32_t *pos, const int32_t *effect)
 {
     if (!fs) return fail(GARLIC_ERR_INVALID, "feature set is NULL");

@@ -29,6 +29,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <ostream>
 #include <regex>
 #include <stdexcept>
@@ -253,12 +254,19 @@ inline FeatureRows readCountingTped(const std::string &path, const FeatureAnnota
     return rows;
 }
 
+struct FeatureBedPlan;     // feature_bed.hpp
+struct BedFile;            // garlic_host.hpp
+
 // everything a count needs of the three input files
 struct FeatureData {
     FeatureAnnotations ann;
-    std::vector<std::string> iid;      // the counting TFAM's individuals, in file order
+    std::vector<std::string> iid;      // the counting TFAM's (or .fam's) individuals, in file order
     FeatureChrIds chrs;
     FeatureRows rows;
+    // the .bed form (feature_bed.hpp): instead of `rows`, which image row and which homozygote every row is, and the open
+    // counting file set whose image the device turns into hom rows (one reference, dropped by releaseFeatureCounts)
+    std::shared_ptr<const FeatureBedPlan> plan;
+    BedFile *bed = nullptr;
 };
 
 inline FeatureData loadFeatureData(const std::string &features, const std::string &tped, const std::string &tfam)

@@ -1517,33 +1517,79 @@ FeatureData *loadFeatureCounts(const std::string &features, const std::string &t
     }
 }
 
-void releaseFeatureCounts(FeatureData *data) { delete data; }
+// the .bed form: the plan from the .bim and the .fam, and the counting file set opened (its image is made where the count runs)
+FeatureData *loadFeatureCountsBed(const std::string &features, const std::string &bedCounting, const std::string &bimCounting,
+                                  const std::string &famCounting)
+{
+    std::unique_ptr<FeatureData, void (*)(FeatureData *)> d(nullptr, releaseFeatureCounts);
+    try {
+        d.reset(new FeatureData(loadFeatureDataBed(features, bimCounting, famCounting)));
+    } catch (const std::exception &e) {
+        fail(e.what());
+    }
+    d->bed = openBedFile(bedCounting, bimCounting, famCounting, /*anyPopulations=*/true);
+    d->bed->refs = 1;
+    if (d->bed->nrows != d->plan->image_rows || (size_t)d->bed->nind != d->iid.size())
+        fail(bimCounting + " / " + famCounting + ": " + std::to_string(d->plan->image_rows) + " loci x " + std::to_string(d->iid.size()) +
+             " individuals in the row plan, " + std::to_string(d->bed->nrows) + " x " + std::to_string(d->bed->nind) + " in the file set");
+    std::cerr << "Feature counts: " << d->ann.allele.size() << " annotated alleles, " << d->ann.effects.size() << " effects; "
+              << d->plan->lines_annotated << " of " << d->plan->lines << " counting loci annotated, " << d->iid.size() << " individuals\n";
+    return d.release();
+}
+
+void releaseFeatureCounts(FeatureData *data)
+{
+    if (!data) return;
+    releaseBedFile(data->bed);
+    delete data;
+}
 
 namespace {
 // the hom rows onto the device, the count, the table
-void featureCountsOn(garlic_ctx *ctx, const FeatureData &d, const std::vector<FeatureInterval> &iv, int n_classes, const std::string &outfile)
+// (`device`: the one `ctx` is on.)  The .bed form uploads the counting file's image there, has the device build the hom rows
+// from it and lets the image go before the count.
+void featureCountsOn(garlic_ctx *ctx, int device, const FeatureData &d, const std::vector<FeatureInterval> &iv, int n_classes,
+                     const std::string &outfile)
 {
     static_assert(sizeof(FeatureInterval) == sizeof(garlic_roh_interval), "one interval");
     const size_t nind = d.iid.size(), ne = d.ann.effects.size();
+    const int64_t nrows = d.plan ? d.plan->nrows() : d.rows.nrows();
     std::vector<int64_t> counts(nind * (size_t)(n_classes + 1) * std::max<size_t>(ne, 1), 0);
     if (ne > 0) {
         garlic_feature_set *fs = nullptr;
-        check(garlic_feature_set_create(ctx, d.rows.nrows(), (int32_t)nind, &fs), "garlic_feature_set_create");
+        check(garlic_feature_set_create(ctx, nrows, (int32_t)nind, &fs), "garlic_feature_set_create");
         int rc = GARLIC_OK;
         const char *what = "";
-        if (d.rows.nrows() > 0) {
+        std::string error;
+        if (d.plan && nrows > 0) {
+            try {
+                what = "garlic_feature_set_rows_bed";
+                rc = garlic_feature_set_rows_bed(fs, bedFullImageOn(d.bed, device), d.plan->file_row.data(), d.plan->allele.data(), 0, nrows);
+            } catch (...) {      // (the upload's own failure: its message is out already)
+                error = "the counting .bed did not reach the device";
+            }
+            if (rc != GARLIC_OK) error = std::string(what) + ": " + garlic_hip_last_error();
+            const size_t slot = bedSlotOn(d.bed, device);
+            garlic_bed_destroy((garlic_bed *)d.bed->images[slot].bed);
+            d.bed->images[slot].bed = nullptr;
+            if (!error.empty()) {
+                garlic_feature_set_destroy(fs);
+                fail(error);
+            }
+        } else if (nrows > 0) {
             what = "garlic_feature_set_rows";
-            rc = garlic_feature_set_rows(fs, d.rows.bits.data(), d.rows.row_bytes, 0, d.rows.nrows());
+            rc = garlic_feature_set_rows(fs, d.rows.bits.data(), d.rows.row_bytes, 0, nrows);
         }
         if (rc == GARLIC_OK) {
             what = "garlic_feature_set_sites";
-            rc = garlic_feature_set_sites(fs, d.rows.chr.data(), d.rows.pos.data(), d.rows.effect.data());
+            rc = d.plan ? garlic_feature_set_sites(fs, d.plan->chr.data(), d.plan->pos.data(), d.plan->effect.data())
+                        : garlic_feature_set_sites(fs, d.rows.chr.data(), d.rows.pos.data(), d.rows.effect.data());
         }
         if (rc == GARLIC_OK) {
             what = "garlic_feature_counts";
             rc = garlic_feature_counts(fs, (const garlic_roh_interval *)iv.data(), (int64_t)iv.size(), n_classes, (int32_t)ne, counts.data(), GARLIC_HOST);
         }
-        const std::string error = rc == GARLIC_OK ? "" : std::string(what) + ": " + garlic_hip_last_error();
+        if (rc != GARLIC_OK) error = std::string(what) + ": " + garlic_hip_last_error();
         garlic_feature_set_destroy(fs);
         if (!error.empty()) fail(error);
     }
@@ -1551,7 +1597,7 @@ void featureCountsOn(garlic_ctx *ctx, const FeatureData &d, const std::vector<Fe
     if (out.fail()) fail("Failed to open " + outfile);
     writeFeatureTable(out, d.ann.effects, d.iid, counts.data(), n_classes);
     out.close();
-    std::cerr << "Feature counts: " << outfile << " (" << d.rows.nrows() << " hom rows, " << iv.size() << " ROH, " << n_classes << " classes)\n";
+    std::cerr << "Feature counts: " << outfile << " (" << nrows << " hom rows, " << iv.size() << " ROH, " << n_classes << " classes)\n";
 }
 } // namespace
 
@@ -1568,7 +1614,7 @@ void featureCountsFromBed(FeatureData *data, const std::string &rohBed, const st
     garlic_ctx *ctx = nullptr;
     check(garlic_ctx_create(device, nullptr, &ctx), "garlic_ctx_create");
     try {
-        featureCountsOn(ctx, *data, iv, n_classes, outfile);
+        featureCountsOn(ctx, device, *data, iv, n_classes, outfile);
     } catch (...) {
         garlic_ctx_destroy(ctx);
         throw;
@@ -1591,7 +1637,7 @@ void LodEngine::featureCounts(FeatureData *data, std::vector<ROHData *> *rohData
     }
     int n_classes = 0;
     const std::vector<FeatureInterval> iv = buildFeatureIntervals(panel_iid, calls, bounds, data->iid, data->chrs, &n_classes);
-    featureCountsOn(impl->shards[0].ctx, *data, iv, n_classes, outfile);
+    featureCountsOn(impl->shards[0].ctx, impl->shards[0].device, *data, iv, n_classes, outfile);
 }
 
 void LodEngine::tglsTermSlabs(int *slab_blocks, int *n_slabs)

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "bed_keep.hpp"
+#include "feature_bed.hpp"
 #include "feature_counts.hpp"
 #include "feed_merge.hpp"
 #include "kde_select.hpp"
@@ -298,7 +299,12 @@ void writeROHData(const std::string &outfile, std::vector<ROHData *> *rohDataByI
 // TFAM once; `throw 0` with a message that names file and line for what feature_counts.hpp refuses.
 // featureCountsFromBed: the table of an existing .roh.bed on `device`, no panel needed.  The table has the script's
 // columns A B C NONE per effect; with more than three classes A .. <last letter> NONE.
+// loadFeatureCountsBed: the counting genotypes as a PLINK .bed / .bim / .fam instead (feature_bed.hpp): only the .bim and the
+// .fam are read, into a row plan; the .bed is opened and its image becomes hom rows on the device where the count runs
+// (garlic_feature_set_rows_bed).  The counting individuals are the .fam's, whatever --keep / --pops select of the run's.
 FeatureData *loadFeatureCounts(const std::string &features, const std::string &tpedCounting, const std::string &tfamCounting);
+FeatureData *loadFeatureCountsBed(const std::string &features, const std::string &bedCounting, const std::string &bimCounting,
+                                  const std::string &famCounting);
 void releaseFeatureCounts(FeatureData *data);
 void featureCountsFromBed(FeatureData *data, const std::string &rohBed, const std::string &outfile, int device);
 

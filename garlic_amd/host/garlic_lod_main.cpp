@@ -62,7 +62,9 @@ struct Args {
     int nclust = 0;                         // --nclust (:163): the size classes from the GMM of the ROH lengths; 0 = not given
     // --features / --tped-counting / --tfam-counting (:177-189, declared there and never wired in: the reference leaves the
     // stage to src/count_features_in_roh.pl); --roh-bed: extension, count on an existing calls file and exit
+    // --bfile-counting / --bed-counting --bim-counting --fam-counting: extension, the counting genotypes as a PLINK file set
     std::string features, tped_counting, tfam_counting, roh_bed;
+    std::string bfile_counting, bed_counting, bim_counting, fam_counting;
     // extensions, PLINK input only: --keep F runs the individuals listed in F (a PLINK keep file) as if the file set held
     // only them; --pops all | NAME ... runs every listed family ID of the .fam in turn, each as --keep of its members with
     // --out <out>.<NAME>
@@ -95,6 +97,10 @@ struct Args {
                  "                    with more than three size classes they run A .. <last letter> NONE, so nothing is dropped)\n"
                  "         [--roh-bed F --features F --tped-counting T [--tfam-counting M] --out P]   (no genotype input: the same table\n"
                  "                    for the calls of an existing .roh.bed, <out>.feature.counts, then exit)\n"
+                 "         [--bfile-counting PREFIX | --bed-counting F --bim-counting F --fam-counting F]   (instead of --tped-counting /\n"
+                 "                    --tfam-counting, wherever those go: the counting genotypes as a PLINK SNP-major file set; only the\n"
+                 "                    .bim and the .fam are read on the host, the hom rows are built from the .bed image on the device; the\n"
+                 "                    counting individuals are the .fam's, also under --keep / --pops)\n"
                  "         (--bfile / --bed --bim --fam: PLINK SNP-major .bed input, read on the device; not with --tped / --tfam /\n"
                  "          --phased; --genotype-cache F is then written from the .bed, never read)\n"
                  "         [--keep F]   (with PLINK input: the run is that of a file set holding only the individuals of F, a PLINK keep\n"
@@ -156,6 +162,10 @@ Args parse(int argc, char **argv)
         else if (f == "--tped-counting") a.tped_counting = val();
         else if (f == "--tfam-counting") a.tfam_counting = val();
         else if (f == "--roh-bed") a.roh_bed = val();
+        else if (f == "--bfile-counting") a.bfile_counting = val();
+        else if (f == "--bed-counting") a.bed_counting = val();
+        else if (f == "--bim-counting") a.bim_counting = val();
+        else if (f == "--fam-counting") a.fam_counting = val();
         else if (f == "--keep") a.keep = val();
         else if (f == "--pops") {
             while (i + 1 < argc && !(argv[i + 1][0] == '-' && argv[i + 1][1] == '-')) a.pops.push_back(argv[++i]);
@@ -182,7 +192,17 @@ Args parse(int argc, char **argv)
         }
         else usage(("unknown flag " + f).c_str());
     }
-    if (!a.features.empty() || !a.tped_counting.empty() || !a.tfam_counting.empty() || !a.roh_bed.empty()) {
+    if (!a.bfile_counting.empty()) {
+        if (!a.bed_counting.empty() || !a.bim_counting.empty() || !a.fam_counting.empty())
+            usage("--bfile-counting and --bed-counting / --bim-counting / --fam-counting exclude each other");
+        a.bed_counting = a.bfile_counting + ".bed"; a.bim_counting = a.bfile_counting + ".bim"; a.fam_counting = a.bfile_counting + ".fam";
+    }
+    if (!a.bed_counting.empty() || !a.bim_counting.empty() || !a.fam_counting.empty()) {
+        if (!a.tped_counting.empty() || !a.tfam_counting.empty())
+            usage("--bfile-counting / --bed-counting and --tped-counting / --tfam-counting exclude each other");
+        if (a.bed_counting.empty() || a.bim_counting.empty() || a.fam_counting.empty()) usage("--bed-counting, --bim-counting and --fam-counting go together");
+        if (a.features.empty()) usage("feature counts need --features and --tped-counting");
+    } else if (!a.features.empty() || !a.tped_counting.empty() || !a.tfam_counting.empty() || !a.roh_bed.empty()) {
         if (a.features.empty() || a.tped_counting.empty()) usage("feature counts need --features and --tped-counting");
         if (a.tfam_counting.empty()) a.tfam_counting = featureTfamOf(a.tped_counting);
     }
@@ -562,7 +582,9 @@ int main(int argc, char **argv)
             FeatureData *d = nullptr;
             ~FeatureOwner() { releaseFeatureCounts(d); }
         } fdata;
-        if (!a.features.empty()) fdata.d = loadFeatureCounts(a.features, a.tped_counting, a.tfam_counting);
+        if (!a.features.empty())
+            fdata.d = a.bed_counting.empty() ? loadFeatureCounts(a.features, a.tped_counting, a.tfam_counting)
+                                             : loadFeatureCountsBed(a.features, a.bed_counting, a.bim_counting, a.fam_counting);
         if (!a.roh_bed.empty()) {
             featureCountsFromBed(fdata.d, a.roh_bed, a.out + ".feature.counts", a.devices[0]);
             return 0;

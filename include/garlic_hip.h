@@ -63,7 +63,7 @@ extern "C" {
  *    garlic_feed_kde_multi_info (likewise); garlic_kde_part_set, garlic_kde_part_set_create, garlic_lod_kde_part_set,
  *    garlic_kde_part_set_destroy, garlic_kde_part_set_counts, garlic_kde_part_set_moment, garlic_kde_part_set_rank,
  *    garlic_kde_part_set_sums, garlic_kde_parts_multi, garlic_kde_parts_multi_info (likewise); garlic_bed_extract,
- *    garlic_bed_get_rows (likewise) */
+ *    garlic_bed_get_rows (likewise); garlic_feature_set_rows_bed, garlic_feature_set_get_rows (likewise) */
 #define GARLIC_HIP_ABI_VERSION 8
 
 #define GARLIC_OK 0
@@ -874,6 +874,20 @@ int garlic_roh_segments(garlic_panel *panel, int32_t winsize, double error, int3
  * garlic_feature_set_rows: host bit rows, `row_bytes` apart, bit i & 7 of byte i >> 3 is individual i (LSB first, as
  * garlic_panel_set_phase_bits), uploaded in slabs; bits past nind are ignored.  Rows never set hold no homozygote.  The
  * caller's rows are free on return.
+ * garlic_feature_set_rows_bed: the rows [row_begin, row_begin + row_count) from a .bed image on the set's device, no
+ * genotype crosses the host: row row_begin + k is built from image row file_row[k] (any order, repeats allowed: the two
+ * alleles of one site) by allele[k]: 0 = homozygous for A1 (PLINK code 00), 1 = homozygous for A2 (code 11), 2 = no bit
+ * (an annotated allele that is neither, or the absent allele `0` of a monomorphic site).  Missing (01) and heterozygous
+ * (10) genotypes set nothing; the bits past nind are 0 whatever the pad bits of the image hold.  file_row and allele are
+ * host arrays of row_count entries, copied before the call returns; the work runs on the set's context's stream and the
+ * call returns when it is done (the image may then be destroyed).  The image may be an ordinary one or one made by
+ * garlic_bed_extract; rows set this way and by garlic_feature_set_rows may be mixed in one set; row_count = 0 does
+ * nothing.  GARLIC_ERR_INVALID, and the set unchanged: a NULL argument, the set's nind != the image's nind_total, the
+ * image on another device than the set's context, a row range outside the set, a file_row outside [0, nrows) or an
+ * allele > 2 (the message names the first such entry); GARLIC_ERR_STATE: an image that is not fully set.
+ * garlic_feature_set_get_rows: the rows [row_begin, row_begin + row_count) as they stand on the device, in the format
+ * garlic_feature_set_rows takes, `row_bytes` >= (nind + 7) / 8 apart; the bytes past a row's own are not touched.  Waits
+ * for the work queued on the set.  A door for checks: the rows are transposed on the host.
  * garlic_feature_set_sites: per row the chromosome (any id >= 0 the caller also uses in the intervals), the physical
  * position and the effect id in [0, GARLIC_FEATURE_MAX_EFFECTS).  GARLIC_ERR_INVALID for rows that are not sorted by
  * (chromosome, position); two rows may share a position (two alleles of one site, with different effects).
@@ -902,6 +916,9 @@ typedef struct garlic_roh_interval {
 int garlic_feature_set_create(garlic_ctx *ctx, int64_t nrows, int32_t nind, garlic_feature_set **set);
 int garlic_feature_set_destroy(garlic_feature_set *set);
 int garlic_feature_set_rows(garlic_feature_set *set, const uint8_t *bits, int64_t row_bytes, int64_t row_begin, int64_t row_count);
+int garlic_feature_set_rows_bed(garlic_feature_set *set, garlic_bed *bed, const int64_t *file_row, const uint8_t *allele,
+                                int64_t row_begin, int64_t row_count);
+int garlic_feature_set_get_rows(garlic_feature_set *set, int64_t row_begin, int64_t row_count, uint8_t *bits, int64_t row_bytes);
 int garlic_feature_set_sites(garlic_feature_set *set, const int32_t *chr, const int32_t *pos, const int32_t *effect);
 int garlic_feature_counts(garlic_feature_set *set, const garlic_roh_interval *intervals, int64_t n_intervals, int32_t n_classes,
                           int32_t n_effects, int64_t *counts, int32_t where);

@@ -47,6 +47,9 @@ parent's tool); shapes 2M x 1280 and 10M x 1250 of a 10k-individual file; the ta
 --modes bed_extract: garlic_bed_extract of --inds individuals (1250) out of an image of --snps rows (1000000) x --file-inds
 individuals (10000), scattered and contiguous, by HIP events: milliseconds and (source + written bytes) / time against the HBM
 rate (profiles/bed_extract_ab.txt).
+--modes feature_rows_bed: garlic_feature_set_rows_bed (hom rows from a .bed image of --snps rows x --file-inds individuals, every
+row annotated and a sparse tenth) beside host-packed bit rows through garlic_feature_set_rows, both by HIP events, with the bytes
+moved against the HBM peak (profiles/feature_rows_bed_ab.txt).
 --modes ld_phased: the warm garlic_panel_compute_ld(phased = 1) call (weights only) for every size of --winsizes on one resident
 panel -- host clock around the synchronous call and the ordered-sum kernel by the library's HIP events, median and spread
 of --steps calls -- with the form the call took where the library reports it; and the phase upload from host memory both
@@ -276,6 +279,69 @@ def bed_extract_leg(args):
                 "image_plus_written_GBps": (nrows * rb + written) / (t * 1e-3) / 1e9}
         line["fraction_of_HBM_peak_touched"] = line["touched_plus_written_GBps"] / HBM_GBPS
         print(json.dumps(line), flush=True)
+    bed.destroy()
+    ctx.close()
+
+
+def feature_rows_bed_leg(args):
+    """garlic_feature_set_rows_bed on one device beside the route it replaces, on the same data: an image of --snps rows x
+    --file-inds individuals (random bytes made on the device) and two plans -- every image row annotated, and a sparse one of a
+    tenth of the rows (sorted, random) -- selectors 0 / 1 at random.  The context runs on a torch stream, so torch's events (HIP
+    events) bracket each call: for the new call the upload of the plan (9 bytes per row) and the kernel; for the baseline
+    garlic_feature_set_rows of the same rows as host-packed bit rows (fetched once through garlic_feature_set_get_rows): the
+    staged upload and the transpose kernel.  Per shape one JSON line: both medians, and the new call's bytes moved,
+    rows x (ceil(nind / 4) + 8 ceil(nind / 64)), against the HBM peak."""
+    import torch
+    from garlic_amd import abi
+
+    HBM_GBPS = 8000.0      # MI355X peak
+    torch.cuda.set_device(0)
+    dev = torch.device("cuda", 0)
+    nimage, nind = args.snps, args.file_inds
+    rb = (nind + 3) // 4
+    stream = torch.cuda.Stream()
+    ctx = abi.Context(0, stream=stream.cuda_stream)
+    bed = abi.Bed(ctx, nimage, nind)
+    g = torch.Generator(device=dev)
+    g.manual_seed(5)
+    chunk = max(1, (256 << 20) // rb)
+    for r in range(0, nimage, chunk):
+        rows = torch.randint(0, 256, (min(chunk, nimage - r), rb), generator=g, device=dev, dtype=torch.uint8)
+        torch.cuda.synchronize()
+        bed.set_rows_device(rows.data_ptr(), rb, r, rows.shape[0])
+    del rows
+    rng = np.random.default_rng(7)
+    shapes = {"every_row": np.arange(nimage, dtype=np.int64),
+              "sparse_tenth": np.sort(rng.choice(nimage, size=max(1, nimage // 10), replace=False)).astype(np.int64)}
+
+    def timed(call, repeats):
+        ms = []
+        for k in range(1 + repeats):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            call()
+            e1.record(stream)
+            torch.cuda.synchronize()
+            if k:
+                ms.append(e0.elapsed_time(e1))
+        return float(np.median(ms))
+
+    for name, file_row in shapes.items():
+        n = int(file_row.shape[0])
+        allele = rng.integers(0, 2, size=n).astype(np.uint8)
+        with abi.FeatureSet(ctx, n, nind) as fs:
+            t_bed = timed(lambda: fs.set_rows_bed(bed, file_row, allele), args.steps)
+            host_rows = fs.get_rows()
+            t_rows = timed(lambda: fs.set_rows(host_rows), max(1, min(args.steps, 2)))
+            same = bool(np.array_equal(fs.get_rows(0, min(n, 4096)), host_rows[:4096]))
+        moved = n * (rb + 8 * ((nind + 63) // 64))
+        line = {"mode": "feature_rows_bed", "shape": name, "image_rows": nimage, "inds": nind, "rows": n, "repeats": args.steps,
+                "rows_bed_ms_median": t_bed, "host_rows_ms_median": t_rows, "speedup": t_rows / t_bed if t_bed > 0 else None,
+                "host_bytes_rows_bed": 9 * n, "host_bytes_host_rows": int(host_rows.nbytes), "bytes_moved": moved,
+                "moved_GBps": moved / (t_bed * 1e-3) / 1e9, "fraction_of_HBM_peak": moved / (t_bed * 1e-3) / 1e9 / HBM_GBPS,
+                "baseline_rows_read_back_equal": same}
+        print(json.dumps(line), flush=True)
+        del host_rows
     bed.destroy()
     ctx.close()
 
@@ -1145,6 +1211,8 @@ def main():
         return bed_extract_leg(args)
     if args.modes == "bed_ingest":
         return bed_ingest_leg(args)
+    if args.modes == "feature_rows_bed":
+        return feature_rows_bed_leg(args)
     if args.modes == "ld_phased":
         return ld_phased_leg(args)
     if args.modes == "tgls_dict16":
