@@ -133,33 +133,8 @@ struct FeedSortScratch {
     void release() { keys.release(); stage.release(); tiles.release(); table.release(); }
 };
 
-// what garlic_feed_kde keeps between calls (kde_kernels.hpp): per-chunk partials and flags, per-slice sums, the targets
-struct KdeScratch {
-    DevBuf<double> stage;                          // the values of a host-buffer call
-    DevBuf<double> partial, slices, targets, raw;
-    DevBuf<int32_t> flags;
-    DevBuf<KdeMoments> mom;
-    DevBuf<unsigned long long> skipped;
-    hipEvent_t ev[4] = {};                         // around the moments kernels and around the sums kernels (garlic_feed_kde_times)
-    size_t bytes() const
-    {
-        return (stage.cap + partial.cap + slices.cap + targets.cap + raw.cap) * sizeof(double) + flags.cap * sizeof(int32_t) +
-               mom.cap * sizeof(KdeMoments) + skipped.cap * sizeof(unsigned long long);
-    }
-    void release()
-    {
-        stage.release(); partial.release(); slices.release(); targets.release(); raw.release(); flags.release();
-        mom.release(); skipped.release();
-        for (auto &e : ev) {
-            if (e) (void)hipEventDestroy(e);
-            e = nullptr;
-        }
-    }
-    ~KdeScratch() { release(); }
-};
-
-// what garlic_feed_kde_multi keeps between calls (kde_multi_kernels.hpp): the feeds of a host-buffer call one after the
-// other, the per-chunk partials and flags and the per-slice sums of all feeds, the table of descriptors
+// what garlic_feed_kde and garlic_feed_kde_multi keep between calls (kde_multi_kernels.hpp): the feeds of a host-buffer
+// call one after the other, the per-chunk partials and flags and the per-slice sums of all feeds, the table of descriptors
 struct KdeMultiScratch {
     DevBuf<double> stage, partial, slices;
     DevBuf<int32_t> flags;
@@ -178,6 +153,13 @@ struct KdeMultiScratch {
         }
     }
     ~KdeMultiScratch() { release(); }
+};
+
+// what a whole-feed KDE leaves for the _info calls, per feed and per call
+struct KdeInfo {
+    std::vector<int64_t> chunks, skipped;
+    int32_t launches = 0, waits = 0;
+    float moments_ms = 0.f, sums_ms = 0.f;
 };
 
 // what garlic_gmm_fit keeps between calls (gmm_kernels.hpp): the blocks' partial sums, the state of the fit
@@ -258,15 +240,10 @@ struct garlic_ctx {
     FeedSortScratch fs;
     int32_t fs_run = 0, fs_skipped = 0;
     int64_t fs_scratch_bytes = 0;
-    // garlic_feed_kde: its scratch, and what garlic_feed_kde_info reports
-    KdeScratch kde;
-    int64_t kde_chunks = 0, kde_skipped = 0;
-    float kde_moments_ms = 0.f, kde_sums_ms = 0.f;
-    // garlic_feed_kde_multi: its scratch, and what garlic_feed_kde_multi_info reports
+    // garlic_feed_kde and garlic_feed_kde_multi: their scratch, and what garlic_feed_kde_info and garlic_feed_kde_multi_info
+    // report (the last single call and the last multi-feed call, each on its own)
     KdeMultiScratch kdem;
-    std::vector<int64_t> kdem_chunks, kdem_skipped;
-    int32_t kdem_launches = 0, kdem_waits = 0;
-    float kdem_moments_ms = 0.f, kdem_sums_ms = 0.f;
+    KdeInfo kde_info, kdem_info;
     // garlic_gmm_fit: its scratch, and what garlic_gmm_fit_info reports
     GmmScratch gmm;
     int64_t gmm_blocks = 0;
@@ -4269,7 +4246,7 @@ int garlic_panel_release_scratch(garlic_panel *p)
     p->lds.release();
     p->d_out.release(); p->d_feed.release();
     p->d_stage16.release(); p->d_stage64.release(); p->d_bed_word_rows.release();
-    p->fs.release(); p->ctx->fs.release(); p->ctx->kde.release(); p->ctx->kdem.release(); p->ctx->gmm.release();
+    p->fs.release(); p->ctx->fs.release(); p->ctx->kdem.release(); p->ctx->gmm.release();
     for (auto *sl : p->feed_slots) {
         HIP_TRY(hipStreamSynchronize(sl->stream));
         sl->fs.release();
@@ -5770,23 +5747,8 @@ int garlic_feed_sort_info(garlic_ctx *ctx, int32_t *passes_run, int32_t *passes_
     return GARLIC_OK;
 }
 
-// ---- computeKDE on the device (kde_kernels.hpp; host arithmetic: host/kde_select.hpp).  d_x: n >= 2 device doubles.
-static int kde_reserve(garlic_ctx *ctx, int64_t n, bool stage)
-{
-    const int64_t n_chunks = (n + KDE_CHUNK - 1) / KDE_CHUNK;
-    if (n_chunks > 0x7fffffff) return fail(GARLIC_ERR_INVALID, "feed KDE: %lld values are more chunks than one launch holds", (long long)n);
-    const int64_t cps = kde_chunks_per_slice(n_chunks), n_slices = (n_chunks + cps - 1) / cps;
-    KdeScratch &k = ctx->kde;
-    int rc;
-    if ((stage && (rc = k.stage.reserve((size_t)n))) || (rc = k.partial.reserve((size_t)n_chunks)) ||
-        (rc = k.flags.reserve((size_t)n_chunks)) || (rc = k.slices.reserve((size_t)n_slices * KDE_POINTS)) ||
-        (rc = k.targets.reserve(KDE_POINTS)) || (rc = k.raw.reserve(KDE_POINTS)) || (rc = k.mom.reserve(1)) ||
-        (rc = k.skipped.reserve(1)))
-        return rc;
-    for (auto &e : k.ev)
-        if (!e) HIP_TRY(hipEventCreate(&e));
-    return GARLIC_OK;
-}
+// ---- computeKDE on the device (kde_kernels.hpp, kde_multi_kernels.hpp; host arithmetic: host/kde_select.hpp; the plan:
+// host/kde_multi_plan.hpp).  One driver for one feed and for several: the single calls are its batch of one.
 
 // where the six order statistics of n values lie, and the weights of the two quartile mixes
 static void kde_stat_index(int64_t n, KdeIdx &idx, double &delta25, double &delta75)
@@ -5824,51 +5786,192 @@ static int kde_from_moments(const KdeMoments &mom, int64_t n, const KdeIdx &idx,
     return GARLIC_OK;
 }
 
-static int kde_device(garlic_ctx *ctx, const double *d_x, int64_t n, garlic_kde *out)
+// what a KDE driver refuses of one feed: the code and the bare words (garlic_feed_kde's), and on a split feed the set whose
+// part caused it (-1: the union as a whole).  Only the public calls add "feed i: " and "set p: ", or nothing.
+struct KdeRefusal {
+    int32_t code = GARLIC_OK;
+    int set = -1;
+    std::string why;
+    std::string last;                      // where several parts refuse one feed: the words of the last of them (else empty)
+};
+
+static bool kde_any_refused(const KdeRefusal *refused, int n_feeds)
+{
+    return std::any_of(refused, refused + n_feeds, [](const KdeRefusal &r) { return r.code != GARLIC_OK; });
+}
+
+// a single-feed call's refusal, in its own words.  Where several parts of the feed are refused, the code is the first
+// part's and the text the last part's: garlic_kde_parts waits for every part, and each refusal leaves its sentence.
+static int kde_report_one(const KdeRefusal &refused)
+{
+    if (!refused.code) return GARLIC_OK;
+    return fail(refused.code, "%s", (refused.last.empty() ? refused.why : refused.last).c_str());
+}
+
+// a multi-feed call's refusals: the one of the lowest index as the call's error text; status NULL: as the call's code too
+static int kde_report_feeds(const KdeRefusal *refused, int n_feeds, int32_t *status)
+{
+    int rc = GARLIC_OK;
+    for (int i = n_feeds - 1; i >= 0; i--) {
+        const KdeRefusal &r = refused[i];
+        if (status) status[i] = r.code;
+        if (!r.code) continue;
+        rc = r.set < 0 ? fail(r.code, "feed %d: %s", i, r.why.c_str()) : fail(r.code, "feed %d: set %d: %s", i, r.set, r.why.c_str());
+    }
+    return status ? (int)GARLIC_OK : rc;
+}
+
+// The two launches of a step over a table of n_feeds descriptors (h: the host's copy, d: the device's).  The batched
+// kernels serve any number of feeds.  Where the table holds ONE feed, the single-feed kernels of kde_kernels.hpp run
+// on that feed's fields of the table instead: the same __device__ bodies, so the same bits, but x, n and the partition
+// arrive as kernel arguments -- the batched kernels fetch them from the table, which costs every workgroup a dependent
+// scalar load and turns the reads of x into flat loads (measured: profiles/kde_one_driver_ab.txt).
+static void kde_launch_moments(hipStream_t s, const KdeFeedDesc *h, KdeFeedDesc *d, int n_feeds, const garlic_host::KdeMultiPlan &plan, int pass,
+                               double *partial, int32_t *flags)
+{
+    if (n_feeds == 1 && h[0].n_chunks > 0) {
+        hipLaunchKernelGGL(kde_moment_kernel, dim3((unsigned)h[0].n_chunks), dim3(KDE_THREADS), 0, s, h[0].x, h[0].n, pass, &d[0].mom, partial, flags);
+        hipLaunchKernelGGL(kde_tree_kernel, dim3(1), dim3(KDE_THREADS), 0, s, h[0].x, h[0].n, h[0].n_chunks, pass, partial, flags, h[0].idx, &d[0].mom);
+        return;
+    }
+    hipLaunchKernelGGL(kde_moment_multi_kernel, dim3((unsigned)plan.total_chunks), dim3(KDE_THREADS), 0, s, d, n_feeds, plan.chunk_first, pass,
+                       partial, flags);
+    hipLaunchKernelGGL(kde_tree_multi_kernel, dim3((unsigned)n_feeds), dim3(KDE_THREADS), 0, s, d, pass, partial, flags);
+}
+
+// divided: raw = the sums / n (a whole feed); not: the sums themselves (a part of a split feed)
+static void kde_launch_sums(hipStream_t s, const KdeFeedDesc *h, KdeFeedDesc *d, int n_feeds, const garlic_host::KdeMultiPlan &plan, bool divided,
+                            double *slices)
+{
+    if (n_feeds == 1 && h[0].active && h[0].n_slices > 0) {
+        hipLaunchKernelGGL(kde_sum_kernel, dim3((unsigned)h[0].n_slices), dim3(KDE_THREADS), 0, s, h[0].x, h[0].n, h[0].n_chunks,
+                           h[0].chunks_per_slice, d[0].targets, h[0].inv_h2, slices, &d[0].skipped);
+        if (divided)
+            hipLaunchKernelGGL(kde_slice_kernel, dim3(KDE_POINTS), dim3(KDE_THREADS), 0, s, slices, h[0].n_slices, h[0].n, d[0].raw);
+        else
+            hipLaunchKernelGGL(kde_slice_sum_kernel, dim3(KDE_POINTS), dim3(KDE_THREADS), 0, s, slices, h[0].n_slices, d[0].raw);
+        return;
+    }
+    hipLaunchKernelGGL(kde_sum_multi_kernel, dim3((unsigned)plan.total_slices), dim3(KDE_THREADS), 0, s, d, n_feeds, plan.slice_first, slices);
+    if (divided)
+        hipLaunchKernelGGL(kde_slice_multi_kernel, dim3((unsigned)n_feeds * KDE_POINTS), dim3(KDE_THREADS), 0, s, d, slices);
+    else
+        hipLaunchKernelGGL(kde_slice_sum_multi_kernel, dim3((unsigned)n_feeds * KDE_POINTS), dim3(KDE_THREADS), 0, s, d, slices);
+}
+
+// The KDE of n_feeds whole feeds in one set of launches.  d_x[i]: n[i] device doubles, ascending (anything, NULL included,
+// where n[i] < 2).  Six launches and two waits on the context's stream whatever n_feeds is; four and one when no feed is
+// left after the moments.  few_fmt: the wording of the "at least 2 values" refusal of the caller (one %lld).  A nonzero
+// return is a failure of the call; otherwise refused[i] says what became of feed i.  strict: the first refusal ends the
+// call.  outs[i] is written for the feeds that were not refused, and `info`, after everything else has succeeded.
+static int kde_multi_device(garlic_ctx *ctx, const double *const *d_x, const int64_t *n, int32_t n_feeds, const char *few_fmt,
+                            bool strict, garlic_kde *outs, KdeRefusal *refused, KdeInfo &info)
 {
     namespace gh = garlic_host;
+    static_assert(GARLIC_KDE_MAX_FEEDS == gh::KDE_MULTI_MAX_FEEDS, "one limit");
     static_assert(KDE_POINTS == GARLIC_KDE_POINTS && gh::KDE_POINTS == GARLIC_KDE_POINTS, "one M");
-    int rc;
-    if ((rc = kde_reserve(ctx, n, false))) return rc;
+    gh::KdeMultiPlan plan;
+    if (!gh::kdeMultiPlan(n, n_feeds, &plan))
+        return fail(GARLIC_ERR_INVALID, "feed KDE: the %d feeds are more chunks than one launch holds", (int)n_feeds);
+    KdeMultiScratch &k = ctx->kdem;
     hipStream_t s = ctx->stream;
-    KdeScratch &k = ctx->kde;
-    const int64_t n_chunks = (n + KDE_CHUNK - 1) / KDE_CHUNK;
-    const int64_t cps = kde_chunks_per_slice(n_chunks), n_slices = (n_chunks + cps - 1) / cps;
-    KdeIdx idx;
-    double delta25, delta75;
-    kde_stat_index(n, idx, delta25, delta75);
-    HIP_TRY(hipEventRecord(k.ev[0], s));
-    for (int pass = 0; pass < 2; pass++) {
-        hipLaunchKernelGGL(kde_moment_kernel, dim3((unsigned)n_chunks), dim3(KDE_THREADS), 0, s, d_x, n, pass, k.mom.p, k.partial.p, k.flags.p);
-        hipLaunchKernelGGL(kde_tree_kernel, dim3(1), dim3(KDE_THREADS), 0, s, d_x, n, n_chunks, pass, k.partial.p, k.flags.p, idx, k.mom.p);
+    int rc;
+    if ((rc = k.partial.reserve((size_t)std::max<int64_t>(plan.total_chunks, 1))) ||
+        (rc = k.flags.reserve((size_t)std::max<int64_t>(plan.total_chunks, 1))) ||
+        (rc = k.slices.reserve((size_t)std::max<int64_t>(plan.total_slices, 1) * KDE_POINTS)) ||
+        (rc = k.table.reserve(GARLIC_KDE_MAX_FEEDS)))
+        return rc;
+    for (auto &e : k.ev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    // per feed: what the moments gave
+    std::vector<garlic_kde> res((size_t)n_feeds);
+    std::vector<KdeFeedDesc> table((size_t)n_feeds);
+    std::vector<double> delta25((size_t)n_feeds, 0.0), delta75((size_t)n_feeds, 0.0);
+    auto refuse = [&](int i, int c) { refused[i].code = c; refused[i].why = g_last_error; };
+    auto stop = [&]() { return strict && kde_any_refused(refused, n_feeds); };
+    memset(table.data(), 0, sizeof(KdeFeedDesc) * table.size());
+    for (int i = 0; i < n_feeds; i++) {
+        const gh::KdeMultiFeedPlan &f = plan.feed[i];
+        KdeFeedDesc &d = table[(size_t)i];
+        if (n[i] < 2) { refuse(i, fail(GARLIC_ERR_INVALID, few_fmt, (long long)n[i])); continue; }
+        d.x = d_x[i];
+        d.n = f.n;
+        d.n_chunks = f.n_chunks;
+        d.chunks_per_slice = f.chunks_per_slice;
+        d.n_slices = f.n_slices;
+        d.chunk_off = plan.chunk_first.at[i];
+        d.slice_off = plan.slice_first.at[i];
+        kde_stat_index(f.n, d.idx, delta25[(size_t)i], delta75[(size_t)i]);
     }
-    HIP_TRY(hipEventRecord(k.ev[1], s));
-    HIP_TRY(hipGetLastError());
-    KdeMoments mom;
-    HIP_TRY(hipMemcpyAsync(&mom, k.mom.p, sizeof mom, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    garlic_kde r;
-    double inv_h2;
-    if ((rc = kde_from_moments(mom, n, idx, delta25, delta75, r, inv_h2))) return rc;
-    HIP_TRY(hipMemcpyAsync(k.targets.p, r.x, sizeof r.x, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(k.skipped.p, 0, sizeof(unsigned long long), s));
-    HIP_TRY(hipEventRecord(k.ev[2], s));
-    hipLaunchKernelGGL(kde_sum_kernel, dim3((unsigned)n_slices), dim3(KDE_THREADS), 0, s, d_x, n, n_chunks, cps, k.targets.p, inv_h2,
-                       k.slices.p, k.skipped.p);
-    hipLaunchKernelGGL(kde_slice_kernel, dim3(KDE_POINTS), dim3(KDE_THREADS), 0, s, k.slices.p, n_slices, n, k.raw.p);
-    HIP_TRY(hipEventRecord(k.ev[3], s));
-    HIP_TRY(hipGetLastError());
-    unsigned long long skipped = 0;
-    HIP_TRY(hipMemcpyAsync(r.raw, k.raw.p, sizeof r.raw, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(&skipped, k.skipped.p, sizeof skipped, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    gh::kdeNormalise(r.raw, r.x, r.y);
-    ctx->kde_chunks = n_chunks;
-    ctx->kde_skipped = (int64_t)skipped;
-    if (hipEventElapsedTime(&ctx->kde_moments_ms, k.ev[0], k.ev[1]) != hipSuccess) ctx->kde_moments_ms = 0.f;
-    if (hipEventElapsedTime(&ctx->kde_sums_ms, k.ev[2], k.ev[3]) != hipSuccess) ctx->kde_sums_ms = 0.f;
-    *out = r;
+    int32_t launches = 0, waits = 0;
+    const size_t table_bytes = sizeof(KdeFeedDesc) * (size_t)n_feeds;
+    if (plan.total_chunks > 0 && !stop()) {
+        HIP_TRY(hipMemcpyAsync(k.table.p, table.data(), table_bytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipEventRecord(k.ev[0], s));
+        for (int pass = 0; pass < 2; pass++) {
+            kde_launch_moments(s, table.data(), k.table.p, n_feeds, plan, pass, k.partial.p, k.flags.p);
+            launches += 2;
+        }
+        HIP_TRY(hipEventRecord(k.ev[1], s));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(table.data(), k.table.p, table_bytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        waits++;
+    }
+    // every h and every target set, then one upload
+    int n_active = 0;
+    for (int i = 0; i < n_feeds && waits; i++) {
+        KdeFeedDesc &d = table[(size_t)i];
+        if (refused[i].code) continue;
+        if ((rc = kde_from_moments(d.mom, d.n, d.idx, delta25[(size_t)i], delta75[(size_t)i], res[(size_t)i], d.inv_h2))) {
+            refuse(i, rc);
+            continue;
+        }
+        memcpy(d.targets, res[(size_t)i].x, sizeof d.targets);
+        d.skipped = 0;
+        d.active = 1;
+        n_active++;
+    }
+    if (stop()) return GARLIC_OK;
+    if (n_active) {
+        HIP_TRY(hipMemcpyAsync(k.table.p, table.data(), table_bytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipEventRecord(k.ev[2], s));
+        kde_launch_sums(s, table.data(), k.table.p, n_feeds, plan, true, k.slices.p);
+        launches += 2;
+        HIP_TRY(hipEventRecord(k.ev[3], s));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(table.data(), k.table.p, table_bytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        waits++;
+    }
+    info.chunks.assign((size_t)n_feeds, 0);
+    info.skipped.assign((size_t)n_feeds, 0);
+    for (int i = 0; i < n_feeds; i++) {
+        const KdeFeedDesc &d = table[(size_t)i];
+        info.chunks[(size_t)i] = d.n_chunks;
+        if (refused[i].code) continue;
+        garlic_kde &r = res[(size_t)i];
+        memcpy(r.raw, d.raw, sizeof r.raw);
+        gh::kdeNormalise(r.raw, r.x, r.y);
+        info.skipped[(size_t)i] = (int64_t)d.skipped;
+        outs[i] = r;
+    }
+    info.launches = launches;
+    info.waits = waits;
+    info.moments_ms = info.sums_ms = 0.f;
+    if (waits && hipEventElapsedTime(&info.moments_ms, k.ev[0], k.ev[1]) != hipSuccess) info.moments_ms = 0.f;
+    if (n_active && hipEventElapsedTime(&info.sums_ms, k.ev[2], k.ev[3]) != hipSuccess) info.sums_ms = 0.f;
     return GARLIC_OK;
+}
+
+// one feed: the batch of one, refused in garlic_feed_kde's words ("feed KDE: ..." and no more)
+static int kde_one_device(garlic_ctx *ctx, const double *d_x, int64_t n, garlic_kde *out)
+{
+    if ((n + KDE_CHUNK - 1) / KDE_CHUNK > 0x7fffffff)
+        return fail(GARLIC_ERR_INVALID, "feed KDE: %lld values are more chunks than one launch holds", (long long)n);
+    KdeRefusal refused;
+    const int rc = kde_multi_device(ctx, &d_x, &n, 1, "feed KDE: needs at least 2 values (got %lld)", true, out, &refused, ctx->kde_info);
+    return rc ? rc : kde_report_one(refused);
 }
 
 int garlic_feed_kde(garlic_ctx *ctx, const double *sorted, int64_t n, int32_t where, garlic_kde *out)
@@ -5879,26 +5982,27 @@ int garlic_feed_kde(garlic_ctx *ctx, const double *sorted, int64_t n, int32_t wh
     if (!sorted) return fail(GARLIC_ERR_INVALID, "feed KDE: values is NULL");
     int rc;
     if ((rc = set_device(ctx))) return rc;
-    if (where == GARLIC_DEVICE) return kde_device(ctx, sorted, n, out);
-    if ((rc = kde_reserve(ctx, n, true))) return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->kde.stage.p, sorted, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    return kde_device(ctx, ctx->kde.stage.p, n, out);
+    if (where == GARLIC_DEVICE) return kde_one_device(ctx, sorted, n, out);
+    if ((rc = ctx->kdem.stage.reserve((size_t)n))) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->kdem.stage.p, sorted, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    return kde_one_device(ctx, ctx->kdem.stage.p, n, out);
 }
 
 int garlic_feed_kde_info(garlic_ctx *ctx, int64_t *chunks, int64_t *pairs_skipped, int64_t *scratch_bytes)
 {
     if (!ctx) return fail(GARLIC_ERR_INVALID, "context is NULL");
-    if (chunks) *chunks = ctx->kde_chunks;
-    if (pairs_skipped) *pairs_skipped = ctx->kde_skipped;
-    if (scratch_bytes) *scratch_bytes = (int64_t)ctx->kde.bytes();
+    const KdeInfo &info = ctx->kde_info;
+    if (chunks) *chunks = info.chunks.empty() ? 0 : info.chunks[0];
+    if (pairs_skipped) *pairs_skipped = info.skipped.empty() ? 0 : info.skipped[0];
+    if (scratch_bytes) *scratch_bytes = (int64_t)ctx->kdem.bytes();
     return GARLIC_OK;
 }
 
 int garlic_feed_kde_times(garlic_ctx *ctx, float *moments_ms, float *sums_ms)
 {
     if (!ctx) return fail(GARLIC_ERR_INVALID, "context is NULL");
-    if (moments_ms) *moments_ms = ctx->kde_moments_ms;
-    if (sums_ms) *sums_ms = ctx->kde_sums_ms;
+    if (moments_ms) *moments_ms = ctx->kde_info.moments_ms;
+    if (sums_ms) *sums_ms = ctx->kde_info.sums_ms;
     return GARLIC_OK;
 }
 
@@ -5914,128 +6018,16 @@ int garlic_lod_kde(garlic_panel *p, int32_t winsize, double error, int32_t max_g
     p->feed_sink = nullptr;
     if (rc) return rc;
     if (count < 2 || sink.size[0].n != count) return fail(GARLIC_ERR_INVALID, "feed KDE: needs at least 2 values (the feed holds %lld)", (long long)count);
-    return kde_device(p->ctx, sink.size[0].data, sink.size[0].n, out);
+    return kde_one_device(p->ctx, sink.size[0].data, sink.size[0].n, out);
 }
 
-// ---- The KDE of several feeds in one set of launches (kde_multi_kernels.hpp; the plan: host/kde_multi_plan.hpp).
-// d_x[i]: n[i] device doubles, ascending (anything, NULL included, where n[i] < 2).  Six launches and two waits on the
-// context's stream whatever n_feeds is; four and one when no feed is left after the moments.  few_fmt: the wording of
-// the "at least 2 values" refusal of the caller (one %lld).  status NULL: any refused feed fails the call.  Nothing of
-// outs or status is written before everything has succeeded.
-static int kde_multi_device(garlic_ctx *ctx, const double *const *d_x, const int64_t *n, int32_t n_feeds, const char *few_fmt,
+// several feeds: "feed i: " in front of a refusal's words; status NULL: any refused feed fails the call
+static int kde_feeds_device(garlic_ctx *ctx, const double *const *d_x, const int64_t *n, int32_t n_feeds, const char *few_fmt,
                             garlic_kde *outs, int32_t *status)
 {
-    namespace gh = garlic_host;
-    static_assert(GARLIC_KDE_MAX_FEEDS == gh::KDE_MULTI_MAX_FEEDS, "one limit");
-    gh::KdeMultiPlan plan;
-    if (!gh::kdeMultiPlan(n, n_feeds, &plan))
-        return fail(GARLIC_ERR_INVALID, "feed KDE: the %d feeds are more chunks than one launch holds", (int)n_feeds);
-    KdeMultiScratch &k = ctx->kdem;
-    hipStream_t s = ctx->stream;
-    int rc;
-    if ((rc = k.partial.reserve((size_t)std::max<int64_t>(plan.total_chunks, 1))) ||
-        (rc = k.flags.reserve((size_t)std::max<int64_t>(plan.total_chunks, 1))) ||
-        (rc = k.slices.reserve((size_t)std::max<int64_t>(plan.total_slices, 1) * KDE_POINTS)) ||
-        (rc = k.table.reserve(GARLIC_KDE_MAX_FEEDS)))
-        return rc;
-    for (auto &e : k.ev)
-        if (!e) HIP_TRY(hipEventCreate(&e));
-    // per feed: the code and the words of its refusal (garlic_feed_kde's), what the moments gave
-    std::vector<int32_t> code((size_t)n_feeds, GARLIC_OK);
-    std::vector<std::string> why((size_t)n_feeds);
-    std::vector<garlic_kde> res((size_t)n_feeds);
-    std::vector<KdeFeedDesc> table((size_t)n_feeds);
-    std::vector<double> delta25((size_t)n_feeds, 0.0), delta75((size_t)n_feeds, 0.0);
-    auto refuse = [&](int i, int c) { code[(size_t)i] = c; why[(size_t)i] = g_last_error; };
-    memset(table.data(), 0, sizeof(KdeFeedDesc) * table.size());
-    for (int i = 0; i < n_feeds; i++) {
-        const gh::KdeMultiFeedPlan &f = plan.feed[i];
-        KdeFeedDesc &d = table[(size_t)i];
-        if (n[i] < 2) { refuse(i, fail(GARLIC_ERR_INVALID, few_fmt, (long long)n[i])); continue; }
-        d.x = d_x[i];
-        d.n = f.n;
-        d.n_chunks = f.n_chunks;
-        d.chunks_per_slice = f.chunks_per_slice;
-        d.n_slices = f.n_slices;
-        d.chunk_off = plan.chunk_first.at[i];
-        d.slice_off = plan.slice_first.at[i];
-        kde_stat_index(f.n, d.idx, delta25[(size_t)i], delta75[(size_t)i]);
-    }
-    auto first_refused = [&]() {
-        for (int i = 0; i < n_feeds; i++)
-            if (code[(size_t)i]) return i;
-        return -1;
-    };
-    // the refusal of the lowest index as the call's error text; strict: as the call's code too
-    auto report = [&]() {
-        const int i = first_refused();
-        return i < 0 ? (int)GARLIC_OK : fail(code[(size_t)i], "feed %d: %s", i, why[(size_t)i].c_str());
-    };
-    int32_t launches = 0, waits = 0;
-    const size_t table_bytes = sizeof(KdeFeedDesc) * (size_t)n_feeds;
-    if (plan.total_chunks > 0 && !(status == nullptr && first_refused() >= 0)) {
-        HIP_TRY(hipMemcpyAsync(k.table.p, table.data(), table_bytes, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipEventRecord(k.ev[0], s));
-        for (int pass = 0; pass < 2; pass++) {
-            hipLaunchKernelGGL(kde_moment_multi_kernel, dim3((unsigned)plan.total_chunks), dim3(KDE_THREADS), 0, s, k.table.p, (int)n_feeds,
-                               plan.chunk_first, pass, k.partial.p, k.flags.p);
-            hipLaunchKernelGGL(kde_tree_multi_kernel, dim3((unsigned)n_feeds), dim3(KDE_THREADS), 0, s, k.table.p, pass, k.partial.p, k.flags.p);
-            launches += 2;
-        }
-        HIP_TRY(hipEventRecord(k.ev[1], s));
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(table.data(), k.table.p, table_bytes, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        waits++;
-    }
-    // every h and every target set, then one upload
-    int n_active = 0;
-    for (int i = 0; i < n_feeds && waits; i++) {
-        KdeFeedDesc &d = table[(size_t)i];
-        if (code[(size_t)i]) continue;
-        if ((rc = kde_from_moments(d.mom, d.n, d.idx, delta25[(size_t)i], delta75[(size_t)i], res[(size_t)i], d.inv_h2))) {
-            refuse(i, rc);
-            continue;
-        }
-        memcpy(d.targets, res[(size_t)i].x, sizeof d.targets);
-        d.skipped = 0;
-        d.active = 1;
-        n_active++;
-    }
-    if (status == nullptr && (rc = report())) return rc;
-    if (n_active) {
-        HIP_TRY(hipMemcpyAsync(k.table.p, table.data(), table_bytes, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipEventRecord(k.ev[2], s));
-        hipLaunchKernelGGL(kde_sum_multi_kernel, dim3((unsigned)plan.total_slices), dim3(KDE_THREADS), 0, s, k.table.p, (int)n_feeds,
-                           plan.slice_first, k.slices.p);
-        hipLaunchKernelGGL(kde_slice_multi_kernel, dim3((unsigned)n_feeds * KDE_POINTS), dim3(KDE_THREADS), 0, s, k.table.p, k.slices.p);
-        launches += 2;
-        HIP_TRY(hipEventRecord(k.ev[3], s));
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(table.data(), k.table.p, table_bytes, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        waits++;
-    }
-    ctx->kdem_chunks.assign((size_t)n_feeds, 0);
-    ctx->kdem_skipped.assign((size_t)n_feeds, 0);
-    for (int i = 0; i < n_feeds; i++) {
-        const KdeFeedDesc &d = table[(size_t)i];
-        ctx->kdem_chunks[(size_t)i] = d.n_chunks;
-        if (status) status[i] = code[(size_t)i];
-        if (code[(size_t)i]) continue;
-        garlic_kde &r = res[(size_t)i];
-        memcpy(r.raw, d.raw, sizeof r.raw);
-        gh::kdeNormalise(r.raw, r.x, r.y);
-        ctx->kdem_skipped[(size_t)i] = (int64_t)d.skipped;
-        outs[i] = r;
-    }
-    ctx->kdem_launches = launches;
-    ctx->kdem_waits = waits;
-    ctx->kdem_moments_ms = ctx->kdem_sums_ms = 0.f;
-    if (waits && hipEventElapsedTime(&ctx->kdem_moments_ms, k.ev[0], k.ev[1]) != hipSuccess) ctx->kdem_moments_ms = 0.f;
-    if (n_active && hipEventElapsedTime(&ctx->kdem_sums_ms, k.ev[2], k.ev[3]) != hipSuccess) ctx->kdem_sums_ms = 0.f;
-    (void)report();                        // (status given: the call ran; the text names the lowest refused feed)
-    return GARLIC_OK;
+    KdeRefusal refused[GARLIC_KDE_MAX_FEEDS];
+    const int rc = kde_multi_device(ctx, d_x, n, n_feeds, few_fmt, status == nullptr, outs, refused, ctx->kdem_info);
+    return rc ? rc : kde_report_feeds(refused, n_feeds, status);
 }
 
 int garlic_feed_kde_multi(garlic_ctx *ctx, const double *const *sorted, const int64_t *n, int32_t n_feeds, int32_t where,
@@ -6050,7 +6042,7 @@ int garlic_feed_kde_multi(garlic_ctx *ctx, const double *const *sorted, const in
     int rc;
     if ((rc = set_device(ctx))) return rc;
     const char *few = "feed KDE: needs at least 2 values (got %lld)";
-    if (where == GARLIC_DEVICE) return kde_multi_device(ctx, sorted, n, n_feeds, few, outs, status);
+    if (where == GARLIC_DEVICE) return kde_feeds_device(ctx, sorted, n, n_feeds, few, outs, status);
     // host buffers: the feeds that can take part, one after the other in the context's scratch
     const double *d_x[GARLIC_KDE_MAX_FEEDS] = {};
     int64_t total = 0;
@@ -6067,24 +6059,24 @@ int garlic_feed_kde_multi(garlic_ctx *ctx, const double *const *sorted, const in
         d_x[i] = ctx->kdem.stage.p + at;
         at += n[i];
     }
-    return kde_multi_device(ctx, d_x, n, n_feeds, few, outs, status);
+    return kde_feeds_device(ctx, d_x, n, n_feeds, few, outs, status);
 }
 
 int garlic_feed_kde_multi_info(garlic_ctx *ctx, int32_t n, int64_t *chunks, int64_t *pairs_skipped, int32_t *kernel_launches,
                                int32_t *host_waits, int64_t *scratch_bytes, float *moments_ms, float *sums_ms)
 {
     if (!ctx) return fail(GARLIC_ERR_INVALID, "context is NULL");
-    if (n < 0 || (size_t)n > ctx->kdem_chunks.size())
-        return fail(GARLIC_ERR_INVALID, "the last multi-feed KDE on the context had %d feeds (asked for %d)", (int)ctx->kdem_chunks.size(), (int)n);
+    if (n < 0 || (size_t)n > ctx->kdem_info.chunks.size())
+        return fail(GARLIC_ERR_INVALID, "the last multi-feed KDE on the context had %d feeds (asked for %d)", (int)ctx->kdem_info.chunks.size(), (int)n);
     for (int i = 0; i < n; i++) {
-        if (chunks) chunks[i] = ctx->kdem_chunks[(size_t)i];
-        if (pairs_skipped) pairs_skipped[i] = ctx->kdem_skipped[(size_t)i];
+        if (chunks) chunks[i] = ctx->kdem_info.chunks[(size_t)i];
+        if (pairs_skipped) pairs_skipped[i] = ctx->kdem_info.skipped[(size_t)i];
     }
-    if (kernel_launches) *kernel_launches = ctx->kdem_launches;
-    if (host_waits) *host_waits = ctx->kdem_waits;
+    if (kernel_launches) *kernel_launches = ctx->kdem_info.launches;
+    if (host_waits) *host_waits = ctx->kdem_info.waits;
     if (scratch_bytes) *scratch_bytes = (int64_t)ctx->kdem.bytes();
-    if (moments_ms) *moments_ms = ctx->kdem_moments_ms;
-    if (sums_ms) *sums_ms = ctx->kdem_sums_ms;
+    if (moments_ms) *moments_ms = ctx->kdem_info.moments_ms;
+    if (sums_ms) *sums_ms = ctx->kdem_info.sums_ms;
     return GARLIC_OK;
 }
 
@@ -6121,394 +6113,15 @@ int garlic_lod_kde_multi(garlic_panel *p, const int32_t *winsizes, const int32_t
         d_x[i] = held ? sink.size[(size_t)i].data : nullptr;
         n[i] = held ? counts[(size_t)i] : std::min<int64_t>(counts[(size_t)i], 1);
     }
-    return kde_multi_device(ctx, d_x, n, n_sizes, "feed KDE: needs at least 2 values (the feed holds %lld)", outs, status);
+    return kde_feeds_device(ctx, d_x, n, n_sizes, "feed KDE: needs at least 2 values (the feed holds %lld)", outs, status);
 }
 
-// ---- The KDE of a feed that is split into sorted parts (a sharded panel: one part per shard, on the shard's device).
-// n, the sums and the 512 Gaussian sums add over the parts, lo / hi are a min and a max, and the four order statistics
-// come from rank queries (host/kde_parts.hpp).  A part owns its scratch and a pinned block for what comes back, so every
-// step is enqueued on every part's stream before any is waited for.
-struct KdePartHost {
-    KdeMoments mom;
-    double ends[2];
-    unsigned long long skipped;
-    unsigned long long keys[KDE_RANK_MAX];
-    long long below[KDE_RANK_MAX];
-    double sums[KDE_POINTS];
-};
-
-struct garlic_kde_part {
-    garlic_ctx *ctx = nullptr;
-    const double *x = nullptr;                     // n ascending doubles on ctx's device (own.p, or borrowed)
-    int64_t n = 0;
-    DevBuf<double> own;                            // a host buffer's upload
-    std::shared_ptr<uint64_t> gen;                 // garlic_lod_kde_part: the panel's scratch count, and its value at creation
-    uint64_t gen_at = 0;
-    DevBuf<double> partial, slices, targets, sums;
-    DevBuf<int32_t> flags;
-    DevBuf<KdeMoments> mom;
-    DevBuf<unsigned long long> skipped, keys;
-    DevBuf<long long> below;
-    KdePartHost *h = nullptr;
-    hipEvent_t ev[2] = {};                         // around the sums kernels
-    int32_t rank_m = 0;
-    int64_t chunks = 0, pairs_skipped = 0;         // garlic_kde_parts_info
-    int32_t rank_rounds = 0;
-    float sums_ms = 0.f;
-    int64_t n_chunks() const { return (n + KDE_CHUNK - 1) / KDE_CHUNK; }
-    int64_t n_slices() const { const int64_t c = n_chunks(), cps = kde_chunks_per_slice(c); return cps ? (c + cps - 1) / cps : 0; }
-};
-
-static int kde_part_usable(const garlic_kde_part *part)
-{
-    if (!part) return fail(GARLIC_ERR_INVALID, "KDE part is NULL");
-    if (part->gen && *part->gen != part->gen_at)
-        return fail(GARLIC_ERR_STATE, "KDE part is stale: its panel has computed scores or a feed, or released its scratch, since the part was made");
-    return GARLIC_OK;
-}
-
-static void kde_part_free(garlic_kde_part *part)
-{
-    for (auto &e : part->ev)
-        if (e) (void)hipEventDestroy(e);
-    if (part->h) (void)hipHostFree(part->h);
-    delete part;
-}
-
-// everything a part's steps need, before anything is enqueued (out of memory: nothing was touched)
-static int kde_part_new(garlic_ctx *ctx, int64_t n, garlic_kde_part **out)
-{
-    if (n > (int64_t)0x7fffffff * KDE_CHUNK) return fail(GARLIC_ERR_INVALID, "feed KDE: %lld values are more chunks than one launch holds", (long long)n);
-    int rc;
-    if ((rc = set_device(ctx))) return rc;
-    std::unique_ptr<garlic_kde_part, void (*)(garlic_kde_part *)> part(new garlic_kde_part, kde_part_free);
-    part->ctx = ctx;
-    part->n = n;
-    if ((rc = part->partial.reserve((size_t)std::max<int64_t>(part->n_chunks(), 1))) ||
-        (rc = part->flags.reserve((size_t)std::max<int64_t>(part->n_chunks(), 1))) ||
-        (rc = part->slices.reserve((size_t)std::max<int64_t>(part->n_slices(), 1) * KDE_POINTS)) ||
-        (rc = part->targets.reserve(KDE_POINTS)) || (rc = part->sums.reserve(KDE_POINTS)) || (rc = part->mom.reserve(1)) ||
-        (rc = part->skipped.reserve(1)) || (rc = part->keys.reserve(KDE_RANK_MAX)) || (rc = part->below.reserve(KDE_RANK_MAX)))
-        return rc;
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&part->h), sizeof(KdePartHost), hipHostMallocDefault));
-    memset(part->h, 0, sizeof(KdePartHost));
-    for (auto &e : part->ev) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipMemsetAsync(part->mom.p, 0, sizeof(KdeMoments), ctx->stream));
-    *out = part.release();
-    return GARLIC_OK;
-}
-
-int garlic_kde_part_create(garlic_ctx *ctx, const double *sorted, int64_t n, int32_t where, garlic_kde_part **out)
-{
-    if (!ctx || !out) return fail(GARLIC_ERR_INVALID, "KDE part: context and part are required");
-    if (where != GARLIC_HOST && where != GARLIC_DEVICE) return fail(GARLIC_ERR_INVALID, "KDE part: where must be GARLIC_HOST or GARLIC_DEVICE");
-    if (n < 0) return fail(GARLIC_ERR_INVALID, "KDE part: n must be >= 0 (got %lld)", (long long)n);
-    if (n > 0 && !sorted) return fail(GARLIC_ERR_INVALID, "KDE part: values is NULL");
-    garlic_kde_part *part = nullptr;
-    int rc;
-    if ((rc = kde_part_new(ctx, n, &part))) return rc;
-    part->x = sorted;
-    if (where == GARLIC_HOST && n > 0) {
-        hipError_t e = hipSuccess;
-        if ((rc = part->own.reserve((size_t)n)) ||
-            (e = hipMemcpyAsync(part->own.p, sorted, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess ||
-            (e = hipStreamSynchronize(ctx->stream)) != hipSuccess) {
-            kde_part_free(part);
-            return rc ? rc : fail(GARLIC_ERR_HIP, "KDE part upload: %s", hipGetErrorString(e));
-        }
-        part->x = part->own.p;
-    }
-    if (n == 0) part->x = nullptr;
-    *out = part;
-    return GARLIC_OK;
-}
-
-int garlic_lod_kde_part(garlic_panel *p, int32_t winsize, double error, int32_t max_gap, int32_t use_gl, int32_t weighted, int32_t M,
-                        double mu, int32_t step, const int32_t *ind_idx, int32_t n_idx, garlic_kde_part **out, int64_t *chr_counts)
-{
-    if (!p || !out) return fail(GARLIC_ERR_INVALID, "panel and part are required");
-    garlic_panel::FeedSink sink;
-    int64_t count = 0;
-    p->feed_sink = &sink;                  // as garlic_lod_kde: sorted, left on the device
-    int rc = garlic_lod_feed_subset(p, winsize, error, max_gap, use_gl, weighted, M, mu, step, ind_idx, n_idx, nullptr,
-                                    INT64_MAX, &count, chr_counts);
-    p->feed_sink = nullptr;
-    if (rc) return rc;
-    if (count > 0 && sink.size[0].n != count) return fail(GARLIC_ERR_STATE, "KDE part: the feed of %lld values was not left on the device", (long long)count);
-    garlic_kde_part *part = nullptr;
-    if ((rc = kde_part_new(p->ctx, count, &part))) return rc;
-    part->x = count > 0 ? sink.size[0].data : nullptr;
-    part->gen = p->scratch_gen;
-    part->gen_at = *p->scratch_gen;
-    *out = part;
-    return GARLIC_OK;
-}
-
-int garlic_kde_part_destroy(garlic_kde_part *part)
-{
-    if (!part) return GARLIC_OK;
-    (void)hipSetDevice(part->ctx->device);
-    (void)hipStreamSynchronize(part->ctx->stream);
-    kde_part_free(part);
-    return GARLIC_OK;
-}
-
-int garlic_kde_part_count(garlic_kde_part *part, int64_t *n)
-{
-    int rc;
-    if ((rc = kde_part_usable(part))) return rc;
-    if (n) *n = part->n;
-    return GARLIC_OK;
-}
-
-// The steps in two halves: *_enqueue puts the work and the copies back on the part's stream, *_wait waits for that stream
-// and reads the pinned block.  An empty part enqueues nothing (the rank kernel excepted: it reads no value).
-static int kde_part_moment_enqueue(garlic_kde_part *part, int pass, double mean)
-{
-    int rc;
-    if ((rc = set_device(part->ctx))) return rc;
-    if (part->n == 0) return GARLIC_OK;
-    hipStream_t s = part->ctx->stream;
-    const int64_t n = part->n, n_chunks = part->n_chunks();
-    KdeIdx idx{};                                  // (pass 1 of the tree fetches x[0] six times: not used)
-    if (pass == 0)
-        hipLaunchKernelGGL(kde_moment_kernel, dim3((unsigned)n_chunks), dim3(KDE_THREADS), 0, s, part->x, n, 0, part->mom.p, part->partial.p, part->flags.p);
-    else
-        hipLaunchKernelGGL(kde_moment_about_kernel, dim3((unsigned)n_chunks), dim3(KDE_THREADS), 0, s, part->x, n, mean, part->partial.p, part->flags.p);
-    hipLaunchKernelGGL(kde_tree_kernel, dim3(1), dim3(KDE_THREADS), 0, s, part->x, n, n_chunks, pass, part->partial.p, part->flags.p, idx, part->mom.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(&part->h->mom, part->mom.p, sizeof(KdeMoments), hipMemcpyDeviceToHost, s));
-    if (pass == 0) {
-        HIP_TRY(hipMemcpyAsync(&part->h->ends[0], part->x, sizeof(double), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(&part->h->ends[1], part->x + (n - 1), sizeof(double), hipMemcpyDeviceToHost, s));
-    }
-    return GARLIC_OK;
-}
-
-static int kde_part_moment_wait(garlic_kde_part *part, int pass, double *value, double *lo, double *hi)
-{
-    if (part->n == 0) {
-        *value = 0.0;
-        return GARLIC_OK;
-    }
-    int rc;
-    if ((rc = set_device(part->ctx))) return rc;
-    HIP_TRY(hipStreamSynchronize(part->ctx->stream));
-    const KdeMoments &mom = part->h->mom;
-    if (pass == 0) {
-        if (mom.flags & KDE_FLAG_NOT_FINITE) return fail(GARLIC_ERR_INVALID, "feed KDE: the values hold a NaN or an infinity");
-        if (mom.flags & KDE_FLAG_NOT_ASCENDING) return fail(GARLIC_ERR_INVALID, "feed KDE: the values are not in ascending order (garlic_feed_sort)");
-        if (lo) *lo = part->h->ends[0];
-        if (hi) *hi = part->h->ends[1];
-    }
-    *value = pass == 0 ? mom.sum : mom.ssq;
-    return GARLIC_OK;
-}
-
-static int kde_part_rank_enqueue(garlic_kde_part *part, const uint64_t *keys, int32_t m)
-{
-    int rc;
-    if ((rc = set_device(part->ctx))) return rc;
-    hipStream_t s = part->ctx->stream;
-    for (int i = 0; i < m; i++) part->h->keys[i] = keys[i];
-    part->rank_m = m;
-    HIP_TRY(hipMemcpyAsync(part->keys.p, part->h->keys, sizeof(unsigned long long) * (size_t)m, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(kde_rank_kernel, dim3((unsigned)((m + KDE_THREADS - 1) / KDE_THREADS)), dim3(KDE_THREADS), 0, s, part->x, part->n,
-                       part->keys.p, (int)m, part->below.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(part->h->below, part->below.p, sizeof(long long) * (size_t)m, hipMemcpyDeviceToHost, s));
-    return GARLIC_OK;
-}
-
-static int kde_part_rank_wait(garlic_kde_part *part)      // the counts are in part->h->below[0 .. rank_m)
-{
-    int rc;
-    if ((rc = set_device(part->ctx))) return rc;
-    HIP_TRY(hipStreamSynchronize(part->ctx->stream));
-    return GARLIC_OK;
-}
-
-static int kde_part_sums_enqueue(garlic_kde_part *part, const double *targets, double inv_h2)
-{
-    int rc;
-    if ((rc = set_device(part->ctx))) return rc;
-    if (part->n == 0) return GARLIC_OK;
-    hipStream_t s = part->ctx->stream;
-    const int64_t n_chunks = part->n_chunks(), cps = kde_chunks_per_slice(n_chunks), n_slices = part->n_slices();
-    HIP_TRY(hipMemcpyAsync(part->targets.p, targets, sizeof(double) * KDE_POINTS, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(part->skipped.p, 0, sizeof(unsigned long long), s));
-    HIP_TRY(hipEventRecord(part->ev[0], s));
-    hipLaunchKernelGGL(kde_sum_kernel, dim3((unsigned)n_slices), dim3(KDE_THREADS), 0, s, part->x, part->n, n_chunks, cps, part->targets.p, inv_h2,
-                       part->slices.p, part->skipped.p);
-    hipLaunchKernelGGL(kde_slice_sum_kernel, dim3(KDE_POINTS), dim3(KDE_THREADS), 0, s, part->slices.p, n_slices, part->sums.p);
-    HIP_TRY(hipEventRecord(part->ev[1], s));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(part->h->sums, part->sums.p, sizeof(double) * KDE_POINTS, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(&part->h->skipped, part->skipped.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    return GARLIC_OK;
-}
-
-static int kde_part_sums_wait(garlic_kde_part *part)      // the sums are in part->h->sums
-{
-    part->chunks = part->n_chunks();
-    if (part->n == 0) {
-        for (double &v : part->h->sums) v = 0.0;
-        part->pairs_skipped = 0;
-        part->sums_ms = 0.f;
-        return GARLIC_OK;
-    }
-    int rc;
-    if ((rc = set_device(part->ctx))) return rc;
-    HIP_TRY(hipStreamSynchronize(part->ctx->stream));
-    part->pairs_skipped = (int64_t)part->h->skipped;
-    if (hipEventElapsedTime(&part->sums_ms, part->ev[0], part->ev[1]) != hipSuccess) part->sums_ms = 0.f;
-    return GARLIC_OK;
-}
-
-int garlic_kde_part_moment(garlic_kde_part *part, int32_t pass, double mean, double *value, double *lo, double *hi)
-{
-    int rc;
-    if ((rc = kde_part_usable(part))) return rc;
-    if (pass != 0 && pass != 1) return fail(GARLIC_ERR_INVALID, "KDE part: pass must be 0 (sum) or 1 (squared deviations), got %d", (int)pass);
-    if (!value) return fail(GARLIC_ERR_INVALID, "KDE part: value is NULL");
-    if ((rc = kde_part_moment_enqueue(part, pass, mean))) return rc;
-    return kde_part_moment_wait(part, pass, value, lo, hi);
-}
-
-int garlic_kde_part_rank(garlic_kde_part *part, const uint64_t *keys, int32_t m, int64_t *below)
-{
-    int rc;
-    if ((rc = kde_part_usable(part))) return rc;
-    if (m < 1 || m > KDE_RANK_MAX) return fail(GARLIC_ERR_INVALID, "KDE part: %d probe keys (1 to %d)", (int)m, KDE_RANK_MAX);
-    if (!keys || !below) return fail(GARLIC_ERR_INVALID, "KDE part: keys and below are required");
-    if ((rc = kde_part_rank_enqueue(part, keys, m)) || (rc = kde_part_rank_wait(part))) return rc;
-    for (int i = 0; i < m; i++) below[i] = part->h->below[i];
-    return GARLIC_OK;
-}
-
-int garlic_kde_part_sums(garlic_kde_part *part, const double *targets, double h, double *sums)
-{
-    int rc;
-    if ((rc = kde_part_usable(part))) return rc;
-    if (!targets || !sums) return fail(GARLIC_ERR_INVALID, "KDE part: targets and sums are required");
-    const double inv_h2 = 1.0 / (h * h);
-    if (!(h > 0) || !std::isfinite(inv_h2)) return fail(GARLIC_ERR_INVALID, "feed KDE: bandwidth %g cannot be used (zero, negative, not finite or too small to square)", h);
-    if ((rc = kde_part_sums_enqueue(part, targets, inv_h2)) || (rc = kde_part_sums_wait(part))) return rc;
-    memcpy(sums, part->h->sums, sizeof(double) * KDE_POINTS);
-    return GARLIC_OK;
-}
-
-int garlic_kde_parts(garlic_kde_part *const *parts, int32_t n_parts, garlic_kde *out)
-{
-    namespace gh = garlic_host;
-    static_assert(GARLIC_KDE_MAX_PARTS <= KDE_THREADS && gh::KDE_DESCENT_PROBES == KDE_RANK_MAX, "one descent round is one rank launch");
-    if (!parts || !out) return fail(GARLIC_ERR_INVALID, "KDE parts: parts and out are required");
-    if (n_parts < 1 || n_parts > GARLIC_KDE_MAX_PARTS) return fail(GARLIC_ERR_INVALID, "KDE parts: %d parts (1 to %d)", (int)n_parts, GARLIC_KDE_MAX_PARTS);
-    int rc;
-    int64_t n = 0;
-    for (int p = 0; p < n_parts; p++) {
-        if (!parts[p]) return fail(GARLIC_ERR_INVALID, "KDE parts: part %d is NULL", p);
-        for (int q = 0; q < p; q++)
-            if (parts[q] == parts[p]) return fail(GARLIC_ERR_INVALID, "KDE parts: part %d is part %d again", p, q);
-        if ((rc = kde_part_usable(parts[p]))) return rc;
-        n += parts[p]->n;
-    }
-    if (n < 2) return fail(GARLIC_ERR_INVALID, "feed KDE: needs at least 2 values (the parts hold %lld)", (long long)n);
-    // a step on every part: all enqueued, then all waited for (the first error is the one returned)
-    auto each = [&](auto enqueue, auto wait) {
-        int first = GARLIC_OK;
-        int enqueued = 0;
-        for (; enqueued < n_parts && !first; enqueued++) first = enqueue(parts[enqueued], enqueued);
-        for (int p = 0; p < (first ? enqueued - 1 : enqueued); p++) {
-            const int r = wait(parts[p], p);
-            if (r && !first) first = r;
-        }
-        return first;
-    };
-    garlic_kde r;
-    r.n = n;
-    double part_value[GARLIC_KDE_MAX_PARTS];
-    uint64_t lo_key = 0, hi_key = 0;
-    bool have_ends = false;
-    if ((rc = each([&](garlic_kde_part *part, int) { return kde_part_moment_enqueue(part, 0, 0.0); },
-                   [&](garlic_kde_part *part, int p) {
-                       double lo = 0, hi = 0;
-                       const int r2 = kde_part_moment_wait(part, 0, &part_value[p], &lo, &hi);
-                       if (r2 || part->n == 0) return r2;
-                       const uint64_t kl = gh::kdeKey(lo), kh = gh::kdeKey(hi);
-                       if (!have_ends || kl < lo_key) lo_key = kl;
-                       if (!have_ends || kh > hi_key) hi_key = kh;
-                       have_ends = true;
-                       return r2;
-                   })))
-        return rc;
-    r.lo = gh::kdeKeyValue(lo_key);
-    r.hi = gh::kdeKeyValue(hi_key);
-    const double mean = gh::kdeCombine(part_value, n_parts) / (double)n;
-    if ((rc = each([&](garlic_kde_part *part, int) { return kde_part_moment_enqueue(part, 1, mean); },
-                   [&](garlic_kde_part *part, int p) { return kde_part_moment_wait(part, 1, &part_value[p], nullptr, nullptr); })))
-        return rc;
-    r.sd = sqrt(gh::kdeCombine(part_value, n_parts) / (double)(n - 1));
-    // the four order statistics of the union
-    int64_t k25, k75, rank[4];
-    double delta25, delta75, stat[4];
-    gh::kdeQuantileIndex(n, 0.25, &k25, &delta25);
-    gh::kdeQuantileIndex(n, 0.75, &k75, &delta75);
-    const int64_t at[4] = {k25, k25 + 1, k75, k75 + 1};
-    for (int q = 0; q < 4; q++) rank[q] = at[q] < 0 ? 0 : (at[q] >= n ? n - 1 : at[q]);
-    int rounds = 0;
-    rc = gh::kdeSelectRanks(rank, [&](const uint64_t *probes, int m, int64_t *below) {
-        for (int i = 0; i < m; i++) below[i] = 0;
-        return each([&](garlic_kde_part *part, int) { return kde_part_rank_enqueue(part, probes, m); },
-                    [&](garlic_kde_part *part, int) {
-                        const int r2 = kde_part_rank_wait(part);
-                        for (int i = 0; i < m && !r2; i++) below[i] += part->h->below[i];
-                        return r2;
-                    });
-    }, stat, &rounds);
-    if (rc) return rc;
-    r.q25 = k25 >= n - 1 ? stat[0] : gh::kdeQuantileMix(stat[0], stat[1], delta25);
-    r.q75 = k75 >= n - 1 ? stat[2] : gh::kdeQuantileMix(stat[2], stat[3], delta75);
-    r.h = gh::kdeBandwidth(r.sd, r.q25, r.q75, n);
-    if (!(r.h > 0) || !std::isfinite(r.h))
-        return fail(GARLIC_ERR_INVALID, "feed KDE: bandwidth %g (sd %g, quartiles %g and %g): all values equal, or no spread between the quartiles",
-                    r.h, r.sd, r.q25, r.q75);
-    gh::kdeTargets(r.lo, r.hi, r.h, r.x);
-    const double inv_h2 = 1.0 / (r.h * r.h);
-    if (!std::isfinite(inv_h2)) return fail(GARLIC_ERR_INVALID, "feed KDE: bandwidth %g is too small to square", r.h);
-    if ((rc = each([&](garlic_kde_part *part, int) { return kde_part_sums_enqueue(part, r.x, inv_h2); },
-                   [&](garlic_kde_part *part, int) { return kde_part_sums_wait(part); })))
-        return rc;
-    const double *sums[GARLIC_KDE_MAX_PARTS];
-    for (int p = 0; p < n_parts; p++) {
-        sums[p] = parts[p]->h->sums;
-        parts[p]->rank_rounds = rounds;
-    }
-    gh::kdeCombineSums(sums, n_parts, KDE_POINTS, n, r.raw);
-    gh::kdeNormalise(r.raw, r.x, r.y);
-    *out = r;
-    return GARLIC_OK;
-}
-
-int garlic_kde_parts_info(garlic_kde_part *const *parts, int32_t n_parts, int64_t *chunks, int64_t *pairs_skipped, int32_t *rank_rounds,
-                          float *sums_ms)
-{
-    if (!parts) return fail(GARLIC_ERR_INVALID, "KDE parts: parts is NULL");
-    if (n_parts < 1 || n_parts > GARLIC_KDE_MAX_PARTS) return fail(GARLIC_ERR_INVALID, "KDE parts: %d parts (1 to %d)", (int)n_parts, GARLIC_KDE_MAX_PARTS);
-    for (int p = 0; p < n_parts; p++) {
-        if (!parts[p]) return fail(GARLIC_ERR_INVALID, "KDE parts: part %d is NULL", p);
-        const int rc = kde_part_usable(parts[p]);
-        if (rc) return rc;
-        if (chunks) chunks[p] = parts[p]->chunks;
-        if (pairs_skipped) pairs_skipped[p] = parts[p]->pairs_skipped;
-        if (sums_ms) sums_ms[p] = parts[p]->sums_ms;
-    }
-    if (rank_rounds) *rank_rounds = parts[0]->rank_rounds;
-    return GARLIC_OK;
-}
-
-// ---- The KDEs of several split feeds at once (a window-size sweep on a sharded panel): a set holds one shard's part of
-// every feed, and every step of garlic_kde_parts runs once per set for all its feeds (kde_part_set_kernels.hpp).  The set's table of KdeFeedDesc lives in pinned memory and is mirrored on the device: the host writes
+// ---- The KDE of feeds that are split into sorted parts (a sharded panel: one part of every feed per shard, on the
+// shard's device).  n, the sums and the 512 Gaussian sums add over the parts, lo / hi are a min and a max, and the four
+// order statistics come from rank queries (host/kde_parts.hpp).  A set holds one shard's part of every feed of a
+// window-size sweep, and every step runs once per set for all its feeds (kde_part_set_kernels.hpp); a garlic_kde_part
+// (below) is a set of one feed.  A set owns its scratch, so every step is enqueued on every set's stream before any is
+// waited for.  The set's table of KdeFeedDesc lives in pinned memory and is mirrored on the device: the host writes
 // what a step needs (who is active, the unions' means, the targets), the step uploads it, runs, and copies it back.
 struct garlic_kde_part_set {
     garlic_ctx *ctx = nullptr;
@@ -6516,7 +6129,7 @@ struct garlic_kde_part_set {
     garlic_host::KdeMultiPlan plan;
     int64_t n[GARLIC_KDE_MAX_FEEDS] = {};
     DevBuf<double> own;                            // host buffers' uploads, one after the other
-    std::shared_ptr<uint64_t> gen;                 // garlic_lod_kde_part_set: as garlic_kde_part
+    std::shared_ptr<uint64_t> gen;                 // a set borrowed from a panel: the panel's scratch count, and its value at creation
     uint64_t gen_at = 0;
     DevBuf<double> partial, slices;
     DevBuf<int32_t> flags;
@@ -6693,13 +6306,20 @@ int garlic_kde_part_set_counts(garlic_kde_part_set *set, int64_t *n)
     return GARLIC_OK;
 }
 
-// The steps in two halves, as a single part's.  active[i] == 0 switches feed i off for this and every later step of the
+// The steps in two halves: *_enqueue puts the work and the copy back on the set's stream, *_wait waits for that stream
+// and reads the pinned table.  active[i] == 0 switches feed i off for this and every later step of the
 // set, up to the next pass 0 (NULL: as it stands).  A set without a value enqueues nothing, the ranks excepted (they read
 // no value, and upload the table themselves: a rank call may be a set's first).
 static void kde_set_activate(garlic_kde_part_set *set, const int32_t *active)
 {
     for (int i = 0; i < set->n_feeds && active; i++)
         if (!active[i]) set->h_table[i].active = 0;
+}
+
+// every feed on again without a pass 0 (a garlic_kde_part's step calls: each runs whatever an earlier step refused)
+static void kde_set_reactivate(garlic_kde_part_set *set)
+{
+    for (int i = 0; i < set->n_feeds; i++) set->h_table[i].active = 1;
 }
 
 static int kde_set_moment_enqueue(garlic_kde_part_set *set, int pass, const double *means, const int32_t *active)
@@ -6805,9 +6425,7 @@ static int kde_set_sums_enqueue(garlic_kde_part_set *set, const double *targets,
     }
     HIP_TRY(hipMemcpyAsync(set->table.p, set->h_table, set->table_bytes(), hipMemcpyHostToDevice, s));
     HIP_TRY(hipEventRecord(set->ev[2], s));
-    hipLaunchKernelGGL(kde_sum_multi_kernel, dim3((unsigned)set->plan.total_slices), dim3(KDE_THREADS), 0, s, set->table.p, (int)set->n_feeds,
-                       set->plan.slice_first, set->slices.p);
-    hipLaunchKernelGGL(kde_slice_sum_multi_kernel, dim3((unsigned)set->n_feeds * KDE_POINTS), dim3(KDE_THREADS), 0, s, set->table.p, set->slices.p);
+    kde_launch_sums(s, set->h_table, set->table.p, set->n_feeds, set->plan, false, set->slices.p);
     set->launches += 2;
     HIP_TRY(hipEventRecord(set->ev[3], s));
     HIP_TRY(hipGetLastError());
@@ -6898,49 +6516,35 @@ int garlic_kde_part_set_sums(garlic_kde_part_set *set, const double *targets, co
     return GARLIC_OK;
 }
 
-int garlic_kde_parts_multi(garlic_kde_part_set *const *sets, int32_t n_sets, garlic_kde *outs, int32_t *status)
+// The KDEs of the F unions whose parts lie in n_sets usable sets of F feeds each (garlic_kde_parts_multi; garlic_kde_parts
+// with F = 1).  A nonzero return is a failure of the call; otherwise refused[i] says what became of union i.  strict: the
+// first refusal ends the call.  outs[i] is written for the unions that were not refused, after everything has succeeded.
+static int kde_parts_reduce(garlic_kde_part_set *const *sets, int32_t n_sets, bool strict, garlic_kde *outs, KdeRefusal *refused)
 {
     namespace gh = garlic_host;
-    if (!sets || !outs) return fail(GARLIC_ERR_INVALID, "KDE parts: sets and outs are required");
-    if (n_sets < 1 || n_sets > GARLIC_KDE_MAX_PARTS) return fail(GARLIC_ERR_INVALID, "KDE parts: %d sets (1 to %d)", (int)n_sets, GARLIC_KDE_MAX_PARTS);
+    static_assert(GARLIC_KDE_MAX_PARTS <= KDE_THREADS && gh::KDE_DESCENT_PROBES == KDE_RANK_MAX, "one descent round is one rank launch");
     int rc;
-    for (int p = 0; p < n_sets; p++) {
-        if (!sets[p]) return fail(GARLIC_ERR_INVALID, "KDE parts: set %d is NULL", p);
-        for (int q = 0; q < p; q++)
-            if (sets[q] == sets[p]) return fail(GARLIC_ERR_INVALID, "KDE parts: set %d is set %d again", p, q);
-        if ((rc = kde_set_usable(sets[p]))) return rc;
-        if (sets[p]->n_feeds != sets[0]->n_feeds)
-            return fail(GARLIC_ERR_INVALID, "KDE parts: set %d holds %d feeds, set 0 holds %d", p, (int)sets[p]->n_feeds, (int)sets[0]->n_feeds);
-    }
     const int F = sets[0]->n_feeds;
     const size_t nF = (size_t)F, nP = (size_t)n_sets;
-    // per feed: the code and the words of its refusal, what the steps gave
-    std::vector<int32_t> code(nF, GARLIC_OK), active(nF, 1);
-    std::vector<std::string> why(nF);
+    // per feed: what the steps gave
+    std::vector<int32_t> active(nF, 1);
     std::vector<garlic_kde> res(nF);
     std::vector<int64_t> n(nF, 0);
-    auto first_refused = [&]() {
-        for (int i = 0; i < F; i++)
-            if (code[(size_t)i]) return i;
-        return -1;
-    };
-    auto report = [&]() {
-        const int i = first_refused();
-        return i < 0 ? (int)GARLIC_OK : fail(code[(size_t)i], "feed %d: %s", i, why[(size_t)i].c_str());
-    };
-    auto refuse = [&](int i, int c, const std::string &words) {
-        code[(size_t)i] = c;
-        why[(size_t)i] = words;
+    auto stop = [&]() { return strict && kde_any_refused(refused, F); };
+    auto refuse = [&](int i, int c, int set, const std::string &words) {
+        refused[i].code = c;
+        refused[i].set = set;
+        refused[i].why = words;
         active[(size_t)i] = 0;
     };
     for (int i = 0; i < F; i++) {
         for (int p = 0; p < n_sets; p++) n[(size_t)i] += sets[p]->n[i];
         if (n[(size_t)i] < 2) {
             const int c = fail(GARLIC_ERR_INVALID, "feed KDE: needs at least 2 values (the parts hold %lld)", (long long)n[(size_t)i]);
-            refuse(i, c, g_last_error);
+            refuse(i, c, -1, g_last_error);
         }
     }
-    if (status == nullptr && (rc = report())) return rc;
+    if (stop()) return GARLIC_OK;
     // a step on every set: all enqueued, then all waited for (the first error is the one returned)
     auto each = [&](auto enqueue, auto wait) {
         int first = GARLIC_OK;
@@ -6962,10 +6566,8 @@ int garlic_kde_parts_multi(garlic_kde_part_set *const *sets, int32_t n_sets, gar
                        std::vector<std::string> w(nF);
                        const int r2 = kde_set_moment_wait(set, 0, &value[(size_t)p * nF], lo.data(), hi.data(), c.data(), w.data());
                        for (int i = 0; i < F && !r2; i++) {
-                           if (c[(size_t)i] && !code[(size_t)i]) {
-                               code[(size_t)i] = c[(size_t)i];
-                               why[(size_t)i] = "set " + std::to_string(p) + ": " + w[(size_t)i];
-                           }
+                           if (c[(size_t)i] && !refused[i].code) refused[i] = KdeRefusal{c[(size_t)i], p, w[(size_t)i]};
+                           if (c[(size_t)i]) refused[i].last = w[(size_t)i];
                            if (c[(size_t)i] || !set->h_table[i].active || set->n[i] == 0) continue;
                            const uint64_t kl = gh::kdeKey(lo[(size_t)i]), kh = gh::kdeKey(hi[(size_t)i]);
                            if (!have_ends[(size_t)i] || kl < lo_key[(size_t)i]) lo_key[(size_t)i] = kl;
@@ -6976,8 +6578,8 @@ int garlic_kde_parts_multi(garlic_kde_part_set *const *sets, int32_t n_sets, gar
                    })))
         return rc;
     for (int i = 0; i < F; i++)
-        if (code[(size_t)i]) active[(size_t)i] = 0;
-    if (status == nullptr && (rc = report())) return rc;
+        if (refused[i].code) active[(size_t)i] = 0;
+    if (stop()) return GARLIC_OK;
     std::vector<double> of_feed(nP);
     auto combine = [&](int i) {
         for (int p = 0; p < n_sets; p++) of_feed[(size_t)p] = value[(size_t)p * nF + (size_t)i];
@@ -7040,19 +6642,19 @@ int garlic_kde_parts_multi(garlic_kde_part_set *const *sets, int32_t n_sets, gar
         if (!(r.h > 0) || !std::isfinite(r.h)) {
             const int c = fail(GARLIC_ERR_INVALID, "feed KDE: bandwidth %g (sd %g, quartiles %g and %g): all values equal, or no spread between the quartiles",
                                r.h, r.sd, r.q25, r.q75);
-            refuse(i, c, g_last_error);
+            refuse(i, c, -1, g_last_error);
             continue;
         }
         gh::kdeTargets(r.lo, r.hi, r.h, r.x);
         inv_h2[(size_t)i] = 1.0 / (r.h * r.h);
         if (!std::isfinite(inv_h2[(size_t)i])) {
             const int c = fail(GARLIC_ERR_INVALID, "feed KDE: bandwidth %g is too small to square", r.h);
-            refuse(i, c, g_last_error);
+            refuse(i, c, -1, g_last_error);
             continue;
         }
         memcpy(&targets[(size_t)i * KDE_POINTS], r.x, sizeof r.x);
     }
-    if (status == nullptr && (rc = report())) return rc;
+    if (stop()) return GARLIC_OK;
     if (std::find(active.begin(), active.end(), 1) != active.end()) {
         if ((rc = each([&](garlic_kde_part_set *set, int) { return kde_set_sums_enqueue(set, targets.data(), inv_h2.data(), active.data()); },
                        [&](garlic_kde_part_set *set, int) { return kde_set_sums_wait(set); })))
@@ -7060,16 +6662,32 @@ int garlic_kde_parts_multi(garlic_kde_part_set *const *sets, int32_t n_sets, gar
     }
     std::vector<const double *> sums(nP);
     for (int i = 0; i < F; i++) {
-        if (status) status[i] = code[(size_t)i];
-        if (code[(size_t)i]) continue;
+        if (refused[i].code) continue;
         garlic_kde &r = res[(size_t)i];
         for (int p = 0; p < n_sets; p++) sums[(size_t)p] = sets[p]->h_table[i].raw;
         gh::kdeCombineSums(sums.data(), n_sets, KDE_POINTS, r.n, r.raw);
         gh::kdeNormalise(r.raw, r.x, r.y);
         outs[i] = r;
     }
-    (void)report();                                // (status given: the call ran; the text names the lowest refused feed)
     return GARLIC_OK;
+}
+
+int garlic_kde_parts_multi(garlic_kde_part_set *const *sets, int32_t n_sets, garlic_kde *outs, int32_t *status)
+{
+    if (!sets || !outs) return fail(GARLIC_ERR_INVALID, "KDE parts: sets and outs are required");
+    if (n_sets < 1 || n_sets > GARLIC_KDE_MAX_PARTS) return fail(GARLIC_ERR_INVALID, "KDE parts: %d sets (1 to %d)", (int)n_sets, GARLIC_KDE_MAX_PARTS);
+    int rc;
+    for (int p = 0; p < n_sets; p++) {
+        if (!sets[p]) return fail(GARLIC_ERR_INVALID, "KDE parts: set %d is NULL", p);
+        for (int q = 0; q < p; q++)
+            if (sets[q] == sets[p]) return fail(GARLIC_ERR_INVALID, "KDE parts: set %d is set %d again", p, q);
+        if ((rc = kde_set_usable(sets[p]))) return rc;
+        if (sets[p]->n_feeds != sets[0]->n_feeds)
+            return fail(GARLIC_ERR_INVALID, "KDE parts: set %d holds %d feeds, set 0 holds %d", p, (int)sets[p]->n_feeds, (int)sets[0]->n_feeds);
+    }
+    KdeRefusal refused[GARLIC_KDE_MAX_FEEDS];
+    if ((rc = kde_parts_reduce(sets, n_sets, status == nullptr, outs, refused))) return rc;
+    return kde_report_feeds(refused, sets[0]->n_feeds, status);
 }
 
 int garlic_kde_parts_multi_info(garlic_kde_part_set *const *sets, int32_t n_sets, int64_t *chunks, int64_t *pairs_skipped,
@@ -7095,6 +6713,194 @@ int garlic_kde_parts_multi_info(garlic_kde_part_set *const *sets, int32_t n_sets
         if (moments_ms) moments_ms[p] = sets[p]->moments_ms;
         if (sums_ms) sums_ms[p] = sets[p]->sums_ms;
     }
+    return GARLIC_OK;
+}
+
+// ---- One feed split into parts: a garlic_kde_part is a part set of one feed behind a handle of its own, with its own
+// wording for what the handle refuses.  Its step calls run the set's halves on the one feed, and garlic_kde_parts is the
+// reduction of garlic_kde_parts_multi with F = 1, a refusal in garlic_feed_kde's bare words.
+struct garlic_kde_part {
+    garlic_kde_part_set *set = nullptr;
+    int64_t chunks = 0, pairs_skipped = 0;         // garlic_kde_parts_info: of the part's last sums ...
+    float sums_ms = 0.f;
+    int32_t rank_rounds = 0;                       // ... and of the last garlic_kde_parts it took part in
+};
+
+// what the sums that have just been waited for leave for garlic_kde_parts_info
+static void kde_part_note_sums(garlic_kde_part *part)
+{
+    part->chunks = part->set->h_table[0].n_chunks;
+    part->pairs_skipped = (int64_t)part->set->h_table[0].skipped;
+    part->sums_ms = part->set->sums_ms;
+}
+
+static int kde_part_usable(const garlic_kde_part *part)
+{
+    if (!part) return fail(GARLIC_ERR_INVALID, "KDE part is NULL");
+    if (part->set->gen && *part->set->gen != part->set->gen_at)
+        return fail(GARLIC_ERR_STATE, "KDE part is stale: its panel has computed scores or a feed, or released its scratch, since the part was made");
+    return GARLIC_OK;
+}
+
+static void kde_part_free(garlic_kde_part *part)
+{
+    kde_set_free(part->set);
+    delete part;
+}
+
+static int kde_part_new(garlic_ctx *ctx, int64_t n, garlic_kde_part **out)
+{
+    if (n > (int64_t)0x7fffffff * KDE_CHUNK) return fail(GARLIC_ERR_INVALID, "feed KDE: %lld values are more chunks than one launch holds", (long long)n);
+    garlic_kde_part_set *set = nullptr;
+    const int rc = kde_set_new(ctx, &n, 1, &set);
+    if (rc) return rc;
+    *out = new garlic_kde_part;
+    (*out)->set = set;
+    return GARLIC_OK;
+}
+
+int garlic_kde_part_create(garlic_ctx *ctx, const double *sorted, int64_t n, int32_t where, garlic_kde_part **out)
+{
+    if (!ctx || !out) return fail(GARLIC_ERR_INVALID, "KDE part: context and part are required");
+    if (where != GARLIC_HOST && where != GARLIC_DEVICE) return fail(GARLIC_ERR_INVALID, "KDE part: where must be GARLIC_HOST or GARLIC_DEVICE");
+    if (n < 0) return fail(GARLIC_ERR_INVALID, "KDE part: n must be >= 0 (got %lld)", (long long)n);
+    if (n > 0 && !sorted) return fail(GARLIC_ERR_INVALID, "KDE part: values is NULL");
+    garlic_kde_part *part = nullptr;
+    int rc;
+    if ((rc = kde_part_new(ctx, n, &part))) return rc;
+    garlic_kde_part_set *set = part->set;
+    set->h_table[0].x = n > 0 ? sorted : nullptr;
+    if (where == GARLIC_HOST && n > 0) {
+        hipError_t e = hipSuccess;
+        if ((rc = set->own.reserve((size_t)n)) ||
+            (e = hipMemcpyAsync(set->own.p, sorted, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess ||
+            (e = hipStreamSynchronize(ctx->stream)) != hipSuccess) {
+            kde_part_free(part);
+            return rc ? rc : fail(GARLIC_ERR_HIP, "KDE part upload: %s", hipGetErrorString(e));
+        }
+        set->h_table[0].x = set->own.p;
+    }
+    *out = part;
+    return GARLIC_OK;
+}
+
+int garlic_lod_kde_part(garlic_panel *p, int32_t winsize, double error, int32_t max_gap, int32_t use_gl, int32_t weighted, int32_t M,
+                        double mu, int32_t step, const int32_t *ind_idx, int32_t n_idx, garlic_kde_part **out, int64_t *chr_counts)
+{
+    if (!p || !out) return fail(GARLIC_ERR_INVALID, "panel and part are required");
+    garlic_panel::FeedSink sink;
+    int64_t count = 0;
+    p->feed_sink = &sink;                  // as garlic_lod_kde: sorted, left on the device
+    int rc = garlic_lod_feed_subset(p, winsize, error, max_gap, use_gl, weighted, M, mu, step, ind_idx, n_idx, nullptr,
+                                    INT64_MAX, &count, chr_counts);
+    p->feed_sink = nullptr;
+    if (rc) return rc;
+    if (count > 0 && sink.size[0].n != count) return fail(GARLIC_ERR_STATE, "KDE part: the feed of %lld values was not left on the device", (long long)count);
+    garlic_kde_part *part = nullptr;
+    if ((rc = kde_part_new(p->ctx, count, &part))) return rc;
+    part->set->h_table[0].x = count > 0 ? sink.size[0].data : nullptr;
+    part->set->gen = p->scratch_gen;
+    part->set->gen_at = *p->scratch_gen;
+    *out = part;
+    return GARLIC_OK;
+}
+
+int garlic_kde_part_destroy(garlic_kde_part *part)
+{
+    if (!part) return GARLIC_OK;
+    (void)hipSetDevice(part->set->ctx->device);
+    (void)hipStreamSynchronize(part->set->ctx->stream);
+    kde_part_free(part);
+    return GARLIC_OK;
+}
+
+int garlic_kde_part_count(garlic_kde_part *part, int64_t *n)
+{
+    int rc;
+    if ((rc = kde_part_usable(part))) return rc;
+    if (n) *n = part->set->n[0];
+    return GARLIC_OK;
+}
+
+int garlic_kde_part_moment(garlic_kde_part *part, int32_t pass, double mean, double *value, double *lo, double *hi)
+{
+    int rc;
+    if ((rc = kde_part_usable(part))) return rc;
+    if (pass != 0 && pass != 1) return fail(GARLIC_ERR_INVALID, "KDE part: pass must be 0 (sum) or 1 (squared deviations), got %d", (int)pass);
+    if (!value) return fail(GARLIC_ERR_INVALID, "KDE part: value is NULL");
+    garlic_kde_part_set *set = part->set;
+    kde_set_reactivate(set);
+    KdeRefusal refused;
+    if ((rc = kde_set_moment_enqueue(set, pass, &mean, nullptr)) || (rc = kde_set_moment_wait(set, pass, value, lo, hi, &refused.code, &refused.why)))
+        return rc;
+    return kde_report_one(refused);
+}
+
+int garlic_kde_part_rank(garlic_kde_part *part, const uint64_t *keys, int32_t m, int64_t *below)
+{
+    int rc;
+    if ((rc = kde_part_usable(part))) return rc;
+    if (m < 1 || m > KDE_RANK_MAX) return fail(GARLIC_ERR_INVALID, "KDE part: %d probe keys (1 to %d)", (int)m, KDE_RANK_MAX);
+    if (!keys || !below) return fail(GARLIC_ERR_INVALID, "KDE part: keys and below are required");
+    garlic_kde_part_set *set = part->set;
+    kde_set_reactivate(set);
+    if ((rc = kde_set_rank_enqueue(set, keys, m)) || (rc = kde_set_rank_wait(set))) return rc;
+    for (int i = 0; i < m; i++) below[i] = set->h_below[i];
+    return GARLIC_OK;
+}
+
+int garlic_kde_part_sums(garlic_kde_part *part, const double *targets, double h, double *sums)
+{
+    int rc;
+    if ((rc = kde_part_usable(part))) return rc;
+    if (!targets || !sums) return fail(GARLIC_ERR_INVALID, "KDE part: targets and sums are required");
+    const double inv_h2 = 1.0 / (h * h);
+    if (!(h > 0) || !std::isfinite(inv_h2)) return fail(GARLIC_ERR_INVALID, "feed KDE: bandwidth %g cannot be used (zero, negative, not finite or too small to square)", h);
+    garlic_kde_part_set *set = part->set;
+    kde_set_reactivate(set);
+    if ((rc = kde_set_sums_enqueue(set, targets, &inv_h2, nullptr)) || (rc = kde_set_sums_wait(set))) return rc;
+    kde_part_note_sums(part);
+    memcpy(sums, set->h_table[0].raw, sizeof(double) * KDE_POINTS);
+    return GARLIC_OK;
+}
+
+int garlic_kde_parts(garlic_kde_part *const *parts, int32_t n_parts, garlic_kde *out)
+{
+    if (!parts || !out) return fail(GARLIC_ERR_INVALID, "KDE parts: parts and out are required");
+    if (n_parts < 1 || n_parts > GARLIC_KDE_MAX_PARTS) return fail(GARLIC_ERR_INVALID, "KDE parts: %d parts (1 to %d)", (int)n_parts, GARLIC_KDE_MAX_PARTS);
+    int rc;
+    garlic_kde_part_set *sets[GARLIC_KDE_MAX_PARTS];
+    for (int p = 0; p < n_parts; p++) {
+        if (!parts[p]) return fail(GARLIC_ERR_INVALID, "KDE parts: part %d is NULL", p);
+        for (int q = 0; q < p; q++)
+            if (parts[q] == parts[p]) return fail(GARLIC_ERR_INVALID, "KDE parts: part %d is part %d again", p, q);
+        if ((rc = kde_part_usable(parts[p]))) return rc;
+        sets[p] = parts[p]->set;
+    }
+    KdeRefusal refused;
+    if ((rc = kde_parts_reduce(sets, n_parts, true, out, &refused))) return rc;
+    if (refused.code) return kde_report_one(refused);
+    for (int p = 0; p < n_parts; p++) {
+        kde_part_note_sums(parts[p]);
+        parts[p]->rank_rounds = sets[p]->rank_rounds;
+    }
+    return GARLIC_OK;
+}
+
+int garlic_kde_parts_info(garlic_kde_part *const *parts, int32_t n_parts, int64_t *chunks, int64_t *pairs_skipped, int32_t *rank_rounds,
+                          float *sums_ms)
+{
+    if (!parts) return fail(GARLIC_ERR_INVALID, "KDE parts: parts is NULL");
+    if (n_parts < 1 || n_parts > GARLIC_KDE_MAX_PARTS) return fail(GARLIC_ERR_INVALID, "KDE parts: %d parts (1 to %d)", (int)n_parts, GARLIC_KDE_MAX_PARTS);
+    for (int p = 0; p < n_parts; p++) {
+        if (!parts[p]) return fail(GARLIC_ERR_INVALID, "KDE parts: part %d is NULL", p);
+        const int rc = kde_part_usable(parts[p]);
+        if (rc) return rc;
+        if (chunks) chunks[p] = parts[p]->chunks;
+        if (pairs_skipped) pairs_skipped[p] = parts[p]->pairs_skipped;
+        if (sums_ms) sums_ms[p] = parts[p]->sums_ms;
+    }
+    if (rank_rounds) *rank_rounds = parts[0]->rank_rounds;
     return GARLIC_OK;
 }
 

@@ -25,10 +25,13 @@
 //     skipped pairs (integer adds) is what garlic_feed_kde_info reports.
 //   * 64-bit element indices and counts; a chunk count fits 32 bits (checked by the caller).
 //   * the bodies are __device__ functions of (feed, chunk / slice / target): the kernels here pass blockIdx.x, the batched
-//     kernels of kde_multi_kernels.hpp the place of the workgroup in its feed -- one source, one result.
-//   * a feed split into parts (garlic_kde_parts): kde_moment_about_kernel is pass 1 about the caller's mean,
-//     kde_slice_sum_kernel leaves a part's sums undivided, kde_rank_kernel counts the values below each of up to 1024
-//     probe keys.  The first two run the lines of their single-feed twins, so one part gives the single feed's bits.
+//     kernels of kde_multi_kernels.hpp the place of the workgroup in its feed -- one source, one result.  The host has
+//     one driver per path; it launches the kernels here where a call holds ONE feed, because they take x and n as kernel
+//     arguments: the batched kernels fetch them from the table, read x through flat loads and start every workgroup with
+//     one more dependent scalar load, which shows in the event times of one feed (profiles/kde_one_driver_ab.txt).
+//   * a feed split into parts (garlic_kde_parts): pass 1 is about the union's mean (the host writes it where pass 0
+//     left the part's own), kde_slice_sum_kernel leaves a part's sums undivided, kde_rank_below counts the values below
+//     a probe key (kde_rank_multi_kernel).  They run the lines of the whole feed, so one part gives its bits.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -106,13 +109,6 @@ __global__ void __launch_bounds__(KDE_THREADS)
 kde_moment_kernel(const double *x, int64_t n, int pass, const KdeMoments *mom, double *partial, int32_t *flags)
 {
     kde_moment_chunk(x, n, blockIdx.x, pass, pass ? mom->mean : 0.0, partial, flags);
-}
-
-// pass 1 about the caller's mean (a part of a split feed: the mean of the union, garlic_kde_part_moment)
-__global__ void __launch_bounds__(KDE_THREADS)
-kde_moment_about_kernel(const double *x, int64_t n, double mean, double *partial, int32_t *flags)
-{
-    kde_moment_chunk(x, n, blockIdx.x, 1, mean, partial, flags);
 }
 
 // one workgroup: the chunks' partials and flags; pass 0 -> sum and mean, pass 1 -> ssq and the order statistics at idx[6]
@@ -256,7 +252,7 @@ __device__ __forceinline__ unsigned long long kde_key(double v)
 }
 
 // how many of x[0 .. n) have a key below `key` (x ascending in key order: a lower bound).  About log2(n) dependent loads.
-// mid < hi <= n, so no read leaves the array; n = 0 reads nothing.  (kde_rank_kernel; kde_rank_multi_kernel on a feed of a set)
+// mid < hi <= n, so no read leaves the array; n = 0 reads nothing.  (kde_rank_multi_kernel on a feed of a set)
 __device__ __forceinline__ int64_t kde_rank_below(const double *x, int64_t n, unsigned long long key)
 {
     int64_t lo = 0, hi = n;
@@ -267,16 +263,7 @@ __device__ __forceinline__ int64_t kde_rank_below(const double *x, int64_t n, un
     return lo;
 }
 
-// thread t: below[t] = kde_rank_below of keys[t].  One binary search per thread: latency-bound, a launch holds at most
-// KDE_RANK_MAX probes.
+// a rank launch holds at most KDE_RANK_MAX probes per feed (one round of the descent of host/kde_parts.hpp)
 constexpr int KDE_RANK_MAX = 1024;
-
-__global__ void __launch_bounds__(KDE_THREADS)
-kde_rank_kernel(const double *x, int64_t n, const unsigned long long *keys, int m, long long *below)
-{
-    const int t = blockIdx.x * KDE_THREADS + threadIdx.x;
-    if (t >= m) return;
-    below[t] = kde_rank_below(x, n, keys[t]);
-}
 
 } // namespace garlic

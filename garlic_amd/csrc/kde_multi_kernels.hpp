@@ -1,6 +1,7 @@
-// The KDE of several feeds in one set of launches (garlic_feed_kde_multi, garlic_lod_kde_multi): the four steps of
+// The KDE of several whole feeds in one set of launches (garlic_feed_kde_multi, garlic_lod_kde_multi): the four steps of
 // kde_kernels.hpp, each once for all feeds -- a window-size sweep's feeds are a few hundred chunks each, and one workgroup
-// per slice of one feed leaves most of the device idle.
+// per slice of one feed leaves most of the device idle.  The host driver is also the single calls'; for one feed it
+// launches the kernels of kde_kernels.hpp, which take the feed as kernel arguments.
 //
 //   * a device table of KdeFeedDesc, one per feed, says where the feed lies, how it is partitioned, where its partials lie
 //     in the shared arrays, and holds what the steps hand to each other: the moments, the targets with 1 / h^2, the count
@@ -9,8 +10,8 @@
 //   * which workgroup does what is host/kde_multi_plan.hpp: flat grids over the feeds' chunks and slices, the prefix tables
 //     passed by value (a function of the feeds' lengths alone).  The tree and slice launches are one workgroup per feed and
 //     per (feed, target).
-//   * the arithmetic is kde_kernels.hpp's: every kernel here calls the __device__ body its single-feed twin calls, with the
-//     feed's pointers and the workgroup's place in the feed.  A feed's result does not depend on what else is in the batch.
+//   * the arithmetic is kde_kernels.hpp's: every kernel here calls a __device__ body of that header with the feed's
+//     pointers and the workgroup's place in the feed.  A feed's result does not depend on what else is in the batch.
 //   * a feed that is not active (fewer than 2 values; refused after the moments) takes no part in the sums launches: its
 //     workgroups leave before the first barrier.  No floating-point atomics.
 //   * kde_rank_multi_kernel: the rank queries of F feeds in one launch, for the feeds of a part set (kde_part_set_kernels.hpp,
@@ -40,7 +41,7 @@ struct KdeFeedDesc {
     double raw[KDE_POINTS];
 };
 
-// one workgroup per (feed, chunk): kde_moment_kernel's lines; pass 1 about the feed's own mean
+// one workgroup per (feed, chunk): kde_moment_chunk; pass 1 about the feed's own mean
 __global__ void __launch_bounds__(KDE_THREADS)
 kde_moment_multi_kernel(const KdeFeedDesc *feeds, int n_feeds, KdeMultiFirst first, int pass, double *partial, int32_t *flags)
 {
@@ -51,7 +52,7 @@ kde_moment_multi_kernel(const KdeFeedDesc *feeds, int n_feeds, KdeMultiFirst fir
     kde_moment_chunk(d.x, d.n, chunk, pass, pass ? d.mom.mean : 0.0, partial + d.chunk_off, flags + d.chunk_off);
 }
 
-// one workgroup per feed: kde_tree_kernel's lines into the feed's moments
+// one workgroup per feed: kde_tree_feed into the feed's moments
 __global__ void __launch_bounds__(KDE_THREADS)
 kde_tree_multi_kernel(KdeFeedDesc *feeds, int pass, const double *partial, const int32_t *flags)
 {
@@ -60,7 +61,7 @@ kde_tree_multi_kernel(KdeFeedDesc *feeds, int pass, const double *partial, const
     kde_tree_feed(d.x, d.n, d.n_chunks, pass, partial + d.chunk_off, flags + d.chunk_off, d.idx, &d.mom);
 }
 
-// one workgroup per (feed, slice): kde_sum_kernel's lines with the feed's targets and 1 / h^2, skipped pairs counted per feed
+// one workgroup per (feed, slice): kde_sum_slice with the feed's targets and 1 / h^2, skipped pairs counted per feed
 __global__ void __launch_bounds__(KDE_THREADS)
 kde_sum_multi_kernel(KdeFeedDesc *feeds, int n_feeds, KdeMultiFirst first, double *slices)
 {
@@ -71,7 +72,7 @@ kde_sum_multi_kernel(KdeFeedDesc *feeds, int n_feeds, KdeMultiFirst first, doubl
     kde_sum_slice(d.x, d.n, d.n_chunks, d.chunks_per_slice, slice, d.targets, d.inv_h2, slices + d.slice_off * KDE_POINTS, &d.skipped);
 }
 
-// one workgroup per (feed, target): kde_slice_kernel's lines
+// one workgroup per (feed, target): kde_slice_total, divided by the feed's n
 __global__ void __launch_bounds__(KDE_THREADS)
 kde_slice_multi_kernel(KdeFeedDesc *feeds, const double *slices)
 {

@@ -1,5 +1,6 @@
-// One shard's parts of several split feeds (garlic_kde_part_set, garlic_kde_parts_multi): the steps of a single part
-// (kde_kernels.hpp: kde_moment_about_kernel, kde_slice_sum_kernel, kde_rank_kernel), each once for all F feeds of the set.
+// One shard's parts of one or several split feeds (garlic_kde_part_set, garlic_kde_parts_multi; a garlic_kde_part of
+// garlic_kde_parts is a set of one feed, whose sums the host launches as kde_sum_kernel and kde_slice_sum_kernel of
+// kde_kernels.hpp): the steps of a part, each once for all F feeds of the set.
 // The table, the flat grids and the sums launch are kde_multi_kernels.hpp's (kde_sum_multi_kernel runs unchanged, and
 // kde_rank_multi_kernel lives there); the arithmetic is kde_kernels.hpp's __device__ bodies, so part i of a set gives the
 // bits of a garlic_kde_part made of the same values.  No floating-point atomics.
@@ -10,7 +11,7 @@
 //     upload of the table, as the targets are written); pass 0's tree has left the part's own mean there;
 //   * the tree also leaves the part's ends x[0], x[n - 1] in mom.stat[0 .. 2) after either pass (the union's lo and hi are
 //     the extremes over the parts); idx is not used;
-//   * the sums stay undivided (kde_slice_sum_kernel's line): the host adds the parts' and divides by the union's n.
+//   * the sums stay undivided: the host adds the parts' and divides by the union's n.
 // `active` is the host's: a feed whose union is refused (fewer than 2 values, a NaN, not ascending, no bandwidth) is
 // switched off in every set and takes no part in any later launch.  A part of one value has one chunk (the plan of a set
 // counts from 1 value, not 2).
@@ -30,7 +31,7 @@ kde_moment_set_kernel(const KdeFeedDesc *feeds, int n_feeds, KdeMultiFirst first
     kde_moment_chunk(d.x, d.n, chunk, pass, pass ? d.mom.mean : 0.0, partial + d.chunk_off, flags + d.chunk_off);
 }
 
-// one workgroup per feed: kde_tree_kernel's lines, and the part's ends
+// one workgroup per feed: kde_tree_feed, and the part's ends
 __global__ void __launch_bounds__(KDE_THREADS)
 kde_tree_set_kernel(KdeFeedDesc *feeds, int pass, const double *partial, const int32_t *flags)
 {
@@ -40,7 +41,7 @@ kde_tree_set_kernel(KdeFeedDesc *feeds, int pass, const double *partial, const i
     if (threadIdx.x < 2) d.mom.stat[threadIdx.x] = d.x[threadIdx.x ? d.n - 1 : 0];
 }
 
-// one workgroup per (feed, target): kde_slice_sum_kernel's line into raw
+// one workgroup per (feed, target): kde_slice_total, undivided, into raw
 __global__ void __launch_bounds__(KDE_THREADS)
 kde_slice_sum_multi_kernel(KdeFeedDesc *feeds, const double *slices)
 {

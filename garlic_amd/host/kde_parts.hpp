@@ -1,6 +1,6 @@
 // The host arithmetic of a KDE over a feed that is split into sorted parts (garlic_kde_parts): the exact order statistics
 // of the union by a radix descent over garlic_feed_sort's 64-bit key, and the rules that combine the parts' sums.
-// Header-only, no GPU: the rank query is a callback, so libgarlic_hip.so (kde_rank_kernel on every part) and
+// Header-only, no GPU: the rank query is a callback, so libgarlic_hip.so (kde_rank_multi_kernel on every set) and
 // tests/host_unit/kde_parts_unit.cpp (std::lower_bound, under the sanitizers) run the same lines.  Built with
 // -ffp-contract=off like kde_select.hpp: every operation rounds on its own, in the association written.
 #ifndef GARLIC_KDE_PARTS_HPP
@@ -53,34 +53,16 @@ inline void kdeDescentChoose(uint64_t *prefix, int round, const int64_t *rank, c
     }
 }
 
-// The values at the 0-based ranks rank[0 .. 4) of the union (0 <= rank[q] < n).  rank_below(probes, m, below) fills
-// below[i] with the number of values of the union whose key is below probes[i] and returns 0, or an error code that
-// ends the descent and is returned.  The count of keys below K never decreases with K, and the value at rank r is the
-// largest K with count(K) <= r, so choosing the largest qualifying digit byte by byte arrives at it: after the eighth
-// round the key is the value.  *rounds: the rank queries made.
-template <class RankBelow>
-inline int kdeSelectRanks(const int64_t *rank, RankBelow rank_below, double *value, int *rounds)
-{
-    uint64_t prefix[KDE_DESCENT_RANKS] = {0, 0, 0, 0};
-    uint64_t probes[KDE_DESCENT_PROBES];
-    int64_t below[KDE_DESCENT_PROBES];
-    if (rounds) *rounds = 0;
-    for (int round = 0; round < KDE_DESCENT_ROUNDS; round++) {
-        kdeDescentProbes(prefix, round, probes);
-        const int rc = rank_below(probes, KDE_DESCENT_PROBES, below);
-        if (rc) return rc;
-        if (rounds) ++*rounds;
-        kdeDescentChoose(prefix, round, rank, below);
-    }
-    for (int q = 0; q < KDE_DESCENT_RANKS; q++) value[q] = kdeKeyValue(prefix[q]);
-    return 0;
-}
-
-// The same descent for n_feeds unions at once (garlic_kde_parts_multi): feed f has the ranks rank[4 f .. 4 f + 4) and gets
-// value[4 f .. 4 f + 4).  One rank query per round carries every feed's probes, feed f's at probes[1024 f ..], and
-// fills below likewise: eight queries in all, not eight per feed.  A feed with active[f] == 0 is carried along: its
-// probes are zeros, its counts are not read, its values are not written.  Every feed's probes and choices are
-// kdeDescentProbes and kdeDescentChoose on its own prefixes, so its values are kdeSelectRanks's whatever else is in the batch.
+// The descent for n_feeds unions at once (garlic_kde_parts_multi; garlic_kde_parts with one): feed f has the ranks
+// rank[4 f .. 4 f + 4), 0 <= rank < n_f, and gets the values at those 0-based ranks of its union in value[4 f .. 4 f + 4).
+// rank_below(probes, m, below) fills below[1024 f + i] with the number of values of union f whose key is below
+// probes[1024 f + i] (m = 1024 probes per feed) and returns 0, or an error code that ends the descent and is returned.
+// The count of keys below K never decreases with K, and the value at rank r is the largest K with count(K) <= r, so
+// choosing the largest qualifying digit byte by byte arrives at it: after the eighth round the key is the value.  One
+// rank query per round carries every feed's probes: eight queries in all, not eight per feed (*rounds: the queries
+// made).  A feed with active[f] == 0 is carried along: its probes are zeros, its counts are not read, its values are
+// not written.  Every feed's probes and choices are kdeDescentProbes and kdeDescentChoose on its own prefixes, so its
+// values do not depend on what else is in the batch.
 template <class RankBelow>
 inline int kdeSelectRanksMulti(int n_feeds, const int64_t *rank, const uint8_t *active, RankBelow rank_below, double *value, int *rounds)
 {
@@ -102,6 +84,14 @@ inline int kdeSelectRanksMulti(int n_feeds, const int64_t *rank, const uint8_t *
         for (int q = 0; q < KDE_DESCENT_RANKS && active[f]; q++)
             value[(size_t)f * KDE_DESCENT_RANKS + q] = kdeKeyValue(prefix[(size_t)f * KDE_DESCENT_RANKS + q]);
     return 0;
+}
+
+// one union: the batch of one
+template <class RankBelow>
+inline int kdeSelectRanks(const int64_t *rank, RankBelow rank_below, double *value, int *rounds)
+{
+    const uint8_t active = 1;
+    return kdeSelectRanksMulti(1, rank, &active, rank_below, value, rounds);
 }
 
 // ((0.0 + s[0]) + s[1]) + ... in part order: the parts' sums, and their sums of squared deviations

@@ -600,7 +600,8 @@ int garlic_feed_sort_info(garlic_ctx *ctx, int32_t *passes_run, int32_t *passes_
  * setting is left as found), then garlic_feed_kde on the device buffer: no feed value crosses PCIe.  An empty feed is the
  * n < 2 error.  A sweep over several window sizes: garlic_lod_kde_multi, below.
  * garlic_feed_kde_info: of the last KDE on the context: chunks of 2048 sources, (chunk, target) pairs skipped as exactly
- * zero, bytes of scratch held.  Any pointer may be NULL.
+ * zero, bytes of scratch held (the scratch is shared with garlic_feed_kde_multi; the records of the two calls are not: a
+ * multi-feed KDE in between changes neither the chunks nor the pairs nor the times reported here).  Any pointer may be NULL.
  * garlic_feed_kde_times: HIP-event times of the last successful KDE on the context: the two moment passes with their
  * tree kernels, and the sums with the slice reduction (tools/bench_variants.py --modes feed_kde).  Any pointer may be NULL. */
 #define GARLIC_KDE_POINTS 512
@@ -661,7 +662,7 @@ int garlic_feed_kde_multi_info(garlic_ctx *ctx, int32_t n, int64_t *chunks, int6
 /* The KDE of a feed that is split into sorted parts: a sharded panel makes one part per shard, each on its shard's device,
  * and no feed value leaves its device.  n, the sum, the sum of squared deviations and the 512 Gaussian sums add over the
  * parts; lo / hi are a min and a max; the four order statistics x[k25], x[k25 + 1], x[k75], x[k75 + 1] of the union are
- * found exactly with rank queries (csrc/kde_kernels.hpp: kde_rank_kernel; the descent and the combination rules:
+ * found exactly with rank queries (csrc/kde_multi_kernels.hpp: kde_rank_multi_kernel; the descent and the combination rules:
  * host/kde_parts.hpp).
  *
  * garlic_kde_part_create: `sorted` holds n >= 0 doubles in the key order of garlic_feed_sort (the library's own feeds are).
@@ -683,6 +684,8 @@ int garlic_feed_kde_multi_info(garlic_ctx *ctx, int32_t n, int64_t *chunks, int6
  * garlic_kde_part_sums: sums[j] = sum_i exp(-(x_i - targets[j])^2 * (1 / h^2)), 512 targets, NOT divided by anything; the
  * chunk / slice partition (a function of the part's n alone), the exact skipping and the skipped-pair count of
  * garlic_feed_kde.  An empty part: 0.0 everywhere.
+ * Every step call of a part runs whatever an earlier one refused: pass 1, the ranks and the sums of a part whose pass 0
+ * met a NaN are still computed.  (A garlic_kde_part_set, below, leaves a refused feed out until its next pass 0.)
  *
  * garlic_kde_parts: the whole KDE of the union of parts[0 .. n_parts), 1 <= n_parts <= GARLIC_KDE_MAX_PARTS, on any mix
  * of contexts and devices; each step is enqueued on every part's stream before any is waited for.

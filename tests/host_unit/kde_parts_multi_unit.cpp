@@ -1,5 +1,6 @@
 // garlic_amd/host/kde_parts.hpp without a device: the descent for F feeds at once (kdeSelectRanksMulti) against the
-// single-feed kdeSelectRanks and against the sorted union, with std::lower_bound on keys as the rank query.
+// single-feed kdeSelectRanks (the same descent as a batch of one: what else is in the batch changes nothing) and against
+// the sorted union (the independent check), with std::lower_bound on keys as the rank query.
 // tests/test_kde_parts_multi_cpu.py builds this under -fsanitize=address,undefined and runs it.
 //
 //   kde_parts_multi_unit <file> ...      (every file is one batch, in order)

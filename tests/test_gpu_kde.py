@@ -167,6 +167,43 @@ def test_kde_errors_leave_the_output_untouched(gpu_ctx, device):
     assert L.garlic_feed_kde(gpu_ctx.handle, C.c_void_p(x.ctypes.data), 3, abi.HOST, None) == abi.ERR_INVALID
 
 
+FEW = "feed KDE: needs at least 2 values (%s %d)"
+NOT_FINITE = "feed KDE: the values hold a NaN or an infinity"
+NOT_ASCENDING = "feed KDE: the values are not in ascending order (garlic_feed_sort)"
+NO_BANDWIDTH = "feed KDE: bandwidth %g (sd %g, quartiles %g and %g): all values equal, or no spread between the quartiles"
+
+
+def refusal_text(x, few):
+    """the sentence garlic_feed_kde refuses the feed x of bad_feeds() with, to the letter: the literals of the library's
+    source with the reference's numbers (`few`: what the call says of the count, "got" or "the parts hold")"""
+    n = x.shape[0]
+    if n < 2:
+        return FEW % (few, n)
+    if not np.isfinite(x).all():
+        return NOT_FINITE
+    if (np.diff(x) < 0).any():
+        return NOT_ASCENDING
+    sd, q25, q75 = float(cases.sd_longdouble(x)), cases.quantile(x, 0.25), cases.quantile(x, 0.75)
+    assert sd == 0.0 and q25 == q75, "all values equal: every number of the sentence is exact"
+    return NO_BANDWIDTH % (cases.bandwidth(sd, q25, q75, n), sd, q25, q75)
+
+
+@pytest.mark.parametrize("device", [False, True], ids=["host", "device"])
+def test_kde_refusals_to_the_letter(gpu_ctx, device):
+    """the single call says what it said before it became the batch of one: no "feed 0: " in front, no other wording"""
+    import torch
+    for what, x, _ in bad_feeds():
+        out = abi.Kde()
+        if device:
+            t = torch.from_numpy(np.concatenate([x, [0.0]])).cuda()
+            code = abi.lib().garlic_feed_kde(gpu_ctx.handle, C.c_void_p(t.data_ptr()), x.shape[0], abi.DEVICE, C.byref(out))
+        else:
+            x = np.ascontiguousarray(x)
+            code = abi.lib().garlic_feed_kde(gpu_ctx.handle, C.c_void_p(x.ctypes.data), x.shape[0], abi.HOST, C.byref(out))
+        msg = abi.lib().garlic_hip_last_error().decode()
+        assert code == abi.ERR_INVALID and msg == refusal_text(x, "got"), (what, msg)
+
+
 # ------------------------------------------------------------------------------------------------ 2. garlic_lod_kde
 
 NIND = 200

@@ -119,6 +119,40 @@ def test_six_launches_and_two_waits_whatever_the_batch(gpu_ctx, n_feeds):
     assert abi.lib().garlic_feed_kde_multi_info(gpu_ctx.handle, n_feeds, None, None, None, None, None, None, None) == abi.OK
 
 
+@gpu
+def test_single_and_multi_info_records_do_not_mix(gpu_ctx):
+    """garlic_feed_kde runs the multi-feed driver with one feed, yet "the last KDE on the context" and "the last multi-feed
+    KDE" stay two records: neither call shows in the other's _info (scratch_bytes apart: the scratch is one)"""
+    c = cases.kde_chunk()
+    three = [cases.content("bimodal", n) for n in (c - 1, c, c + 1)]
+    fourth = cases.content("wide", 3 * c + 17)
+
+    def records():
+        multi = gpu_ctx.feed_kde_multi_info(3)
+        one = dict(gpu_ctx.feed_kde_info(), **gpu_ctx.feed_kde_times())
+        multi.pop("scratch_bytes"), one.pop("scratch_bytes")
+        return multi, one
+
+    for multi_first in (True, False):
+        if multi_first:
+            _, status, _ = run_multi(gpu_ctx, three, False)
+            multi_before, _ = records()
+            gpu_ctx.feed_kde(np.ascontiguousarray(fourth))
+            multi, one = records()
+            assert multi == multi_before, "the single call shows in the multi-feed record"
+        else:
+            gpu_ctx.feed_kde(np.ascontiguousarray(fourth))
+            _, one_before = records()
+            _, status, _ = run_multi(gpu_ctx, three, False)
+            multi, one = records()
+            assert one == one_before, "the multi-feed call shows in the single record"
+        assert status == [abi.OK] * 3
+        assert multi["chunks"] == [1, 1, 2] and multi["kernel_launches"] == 6 and multi["host_waits"] == 2, multi
+        assert one["chunks"] == 4 and one["pairs_skipped"] > 0 and one["moments_ms"] > 0 and one["sums_ms"] > 0, one
+        with pytest.raises(abi.GarlicError):
+            gpu_ctx.feed_kde_multi_info(4)
+
+
 # ------------------------------------------------------------------------------------------------ 4. refusals inside a batch
 
 def filled(n):

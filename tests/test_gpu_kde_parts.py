@@ -1,5 +1,5 @@
-"""GPU: the KDE of a feed split into sorted parts (garlic_kde_parts, csrc/kde_kernels.hpp: kde_rank_kernel,
-kde_moment_about_kernel, kde_slice_sum_kernel) against the long-double numpy reference of tests/kde_cases.py evaluated on
+"""GPU: the KDE of a feed split into sorted parts (garlic_kde_parts: every part a part set of one feed,
+csrc/kde_part_set_kernels.hpp, csrc/kde_kernels.hpp: kde_sum_kernel, kde_slice_sum_kernel) against the long-double numpy reference of tests/kde_cases.py evaluated on
 the UNION -- never against a second run of the kernels, except where the claim is that two runs agree (one part and
 garlic_feed_kde, the same call twice, two contexts, the step calls composed here).  All parts sit on the one device.
 
@@ -301,6 +301,48 @@ def refused(parts_or_handles, n_parts=None):
         msg = abi.lib().garlic_hip_last_error().decode()
     assert bytes(out) == before, msg
     return code, msg
+
+
+def test_parts_refusals_to_the_letter(gpu_ctx):
+    """garlic_kde_parts on the bad feeds of tests/test_gpu_kde.py split in two says garlic_feed_kde's sentences, with "the
+    parts hold" for the count: nothing of the sets behind the parts ("feed 0: ", "set 1: ") shows"""
+    from test_gpu_kde import bad_feeds, refusal_text
+    for what, x, _ in bad_feeds():
+        half = x.shape[0] // 2
+        with Parts(gpu_ctx, [x[:half], x[half:]]) as parts:
+            code, msg = refused((C.c_void_p * 2)(parts[0].handle, parts[1].handle), 2)
+        assert code == abi.ERR_INVALID and msg == refusal_text(x, "the parts hold"), (what, msg)
+    # two parts refused for different reasons: every part is waited for and each refusal leaves its sentence, so the text
+    # is the last refused part's (the code is the first's; both are GARLIC_ERR_INVALID)
+    feeds = {what: x for what, x, _ in bad_feeds()}
+    descending, nan = feeds["swapped inside a chunk"], feeds["NaN in the middle"]
+    for arrays, want in (([descending, nan], nan), ([nan, descending], descending)):
+        with Parts(gpu_ctx, arrays) as parts:
+            code, msg = refused((C.c_void_p * 2)(parts[0].handle, parts[1].handle), 2)
+        assert code == abi.ERR_INVALID and msg == refusal_text(want, "the parts hold"), msg
+
+
+def test_parts_info_is_of_the_last_sums_and_the_last_kde_parts(gpu_ctx):
+    """garlic_kde_parts_info answers zeros before anything ran; chunks, pairs_skipped and sums_ms are of a part's last sums
+    (garlic_kde_parts or the step call), rank_rounds of the last garlic_kde_parts alone: rank step calls do not count"""
+    chunk = cases.kde_chunk()
+    x = cases.content("wide", 3 * chunk + 17)
+    arrays = [np.ascontiguousarray(x[:chunk + 1]), np.ascontiguousarray(x[chunk + 1:])]
+    with Parts(gpu_ctx, arrays) as parts:
+        info = abi.kde_parts_info(parts)
+        assert list(info["chunks"]) == [0, 0] and not info["pairs_skipped"].any() and info["rank_rounds"] == 0, info
+        assert list(info["sums_ms"]) == [0, 0], info
+        parts[0].rank([0, 1])
+        assert abi.kde_parts_info(parts)["rank_rounds"] == 0
+        got = abi.kde_parts(parts)
+        parts[0].rank([0, 1])
+        info = abi.kde_parts_info(parts)
+        assert info["rank_rounds"] == 8 and list(info["chunks"]) == [(a.shape[0] + chunk - 1) // chunk for a in arrays] == [2, 3], info
+        assert all(s > 0 for s in info["pairs_skipped"]) and all(ms > 0 for ms in info["sums_ms"]), info
+        parts[1].sums(got["x"], 1e4)                       # the step call with a bandwidth at which no argument reaches -746
+        after = abi.kde_parts_info(parts)
+        assert after["pairs_skipped"][0] == info["pairs_skipped"][0] and after["pairs_skipped"][1] == 0, (info, after)
+        assert after["rank_rounds"] == 8
 
 
 def test_refusals_leave_the_output_untouched(gpu_ctx):

@@ -148,6 +148,27 @@ def test_one_set_is_feed_kde_multi_bit_for_bit(gpu_ctx):
     assert got[-1] is None and want[-1] is None
 
 
+def test_a_part_is_a_set_of_one_feed(gpu_ctx):
+    """garlic_kde_parts over [2 values, the rest, an empty part] and garlic_kde_parts_multi over three sets of one feed made
+    of the same values: one struct, and garlic_kde_parts_info still answers per part"""
+    chunk = cases.kde_chunk()
+    x = cases.content("bimodal", 3 * chunk + 17)
+    arrays = [np.ascontiguousarray(x[:2]), np.ascontiguousarray(x[2:]), mcases.EMPTY]
+    parts = [gpu_ctx.kde_part(a) for a in arrays]
+    try:
+        want = abi.kde_parts(parts)
+        info = abi.kde_parts_info(parts)
+    finally:
+        for p in parts:
+            p.close()
+    with Sets(gpu_ctx, [("2 + rest + 0", arrays)]) as sets:
+        got, status = abi.kde_parts_multi(sets)
+    assert status == [abi.OK] and same_struct(got[0], want)
+    assert info["rank_rounds"] == 8, info
+    assert list(info["chunks"]) == [1, 4, 0] == [(a.shape[0] + chunk - 1) // chunk for a in arrays], info
+    assert info["pairs_skipped"][2] == 0 and info["sums_ms"][0] > 0 and info["sums_ms"][1] > 0 and info["sums_ms"][2] == 0, info
+
+
 # --------------------------------------------------------------------------------------------- 2. per-feed refusal
 
 def refusal_feeds():
