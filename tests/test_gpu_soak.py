@@ -19,3 +19,13 @@ def test_soak_slice(gpu_ctx, seed, capsys):
     out = capsys.readouterr().out
     assert fails == 0, out[-3000:]
     assert checks > 300
+
+
+def test_soak_reused_panels(gpu_ctx, capsys):
+    """10 trials on panels that live for three trials each: genotypes, frequencies, map, likelihoods, phase and weights of the
+    second and third trial arrive through the setters of a panel that has computed everything before"""
+    import soak
+    checks, fails = soak.soak(gpu_ctx, 10, 20260303, verbose=False, reuse_panel=True)
+    out = capsys.readouterr().out
+    assert fails == 0, out[-3000:]
+    assert checks > 100

@@ -2,10 +2,11 @@
 """One-off soak on the GPU box: many random panels through every variant of the path, each result
 against the CPU oracle bit for bit.  Not part of the test suite (minutes, not seconds):
 
-    python tools/soak.py [--trials 150] [--seed 1]
+    python tools/soak.py [--trials 150] [--seed 1] [--reuse-panel]
 
 Prints one line per failure and a summary; exit code 1 if anything differed."""
 import argparse
+import contextlib
 import os
 import sys
 import time
@@ -17,37 +18,55 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
-def same(a, b):
-    a = np.ascontiguousarray(a, dtype=np.float64)
-    b = np.ascontiguousarray(b, dtype=np.float64)
-    if a.shape != b.shape or not np.array_equal(np.isnan(a), np.isnan(b)):
-        return False
-    ok = ~np.isnan(a)
-    return np.array_equal(a[ok].view(np.uint64), b[ok].view(np.uint64))
+class PanelKeeper:
+    """reuse_panel: one panel per (sizes, nind) for three consecutive trials -- the second and third trial change its map,
+    frequencies and genotypes (and everything after) through the setters instead of starting from a new panel"""
+
+    def __init__(self, reuse, trials):
+        self.reuse, self.trials, self.panel = reuse, trials, None
+
+    def new_shape(self, trial):
+        return not self.reuse or trial % 3 == 0
+
+    @contextlib.contextmanager
+    def hold(self, ctx, trial, sizes, nind):
+        from garlic_amd import abi
+        if self.panel is None:
+            self.panel = abi.Panel(ctx, sizes, nind)
+        ok = False
+        try:
+            yield self.panel
+            ok = True
+        finally:
+            if not ok or not self.reuse or trial % 3 == 2 or trial == self.trials - 1:
+                self.panel.close()
+                self.panel = None
 
 
-def soak(ctx, trials, seed, verbose=True):
+def soak(ctx, trials, seed, verbose=True, reuse_panel=False):
     """`trials` random panels through every variant on context `ctx`; returns (checks, failures).
-    tests/test_gpu_soak.py runs a 60-panel slice of this in the -m gpu suite."""
+    tests/test_gpu_soak.py runs a 60-panel slice of this in the -m gpu suite.  reuse_panel: see PanelKeeper."""
     import oracle_lib as ol
     from garlic_amd import abi
 
     rng = np.random.default_rng(seed)
     fails, checks, t0 = 0, 0, time.time()
     strip_env = os.environ.get("GARLIC_WLOD_STRIP_GROUPS")
+    keeper = PanelKeeper(reuse_panel, trials)
     for trial in range(trials):
-        nchr = int(rng.integers(1, 4))
-        W = int(rng.choice([2, 5, 10, 15, 16, 17, 31, 32, 33, 64, 100, 129, 130]))
-        sizes = [int(rng.choice([1, W - 1, W, W + 1, int(rng.integers(2 * W, 40 * W + 300))])) for _ in range(nchr)]
-        sizes = [max(1, n) for n in sizes]
-        nind = int(rng.choice([1, 63, 64, 65, int(rng.integers(2, 260))]))
+        if keeper.new_shape(trial):
+            nchr = int(rng.integers(1, 4))
+            W = int(rng.choice([2, 5, 10, 15, 16, 17, 31, 32, 33, 64, 100, 129, 130]))
+            sizes = [int(rng.choice([1, W - 1, W, W + 1, int(rng.integers(2 * W, 40 * W + 300))])) for _ in range(nchr)]
+            sizes = [max(1, n) for n in sizes]
+            nind = int(rng.choice([1, 63, 64, 65, int(rng.integers(2, 260))]))
         mg = int(rng.choice([3000, 50000, 200000]))
         chroms = [ol.random_panel(rng, n, nind, max_gap=mg, gaps=int(rng.integers(0, 5)) if n > 50 else 0,
                                   miss=float(rng.choice([0.0, 0.03, 0.3]))) for n in sizes]
         gpos = [np.cumsum(np.diff(c[2], prepend=0) * 1e-6 * rng.uniform(0.8, 1.2, size=c[2].shape[0])) for c in chroms]
         err = float(rng.choice([1e-6, 0.001, 0.05]))
         tag = (trial, sizes, W, nind, mg)
-        with abi.Panel(ctx, sizes, nind) as panel:
+        with keeper.hold(ctx, trial, sizes, nind) as panel:
             panel.set_map(np.concatenate([c[2] for c in chroms]), [c[3] for c in chroms], [c[4] for c in chroms],
                           gpos=np.concatenate(gpos))
             panel.set_freq(np.concatenate([c[1] for c in chroms]))
@@ -105,7 +124,7 @@ def soak(ctx, trials, seed, verbose=True):
                 ld = panel.compute_ld(W, sub_idx=sub)
                 want_ld = np.concatenate([ol.oracle_hr2_ld(c[0], W, idx=sub) for c in chroms], axis=0)
                 checks += 1
-                if not same(ld, want_ld):
+                if not ol.bits_equal(ld, want_ld):
                     fails += 1
                     print("FAIL hr2", tag)
                 phase = rng.integers(0, 2, size=(sum(sizes), nind)).astype(np.uint8)
@@ -116,7 +135,7 @@ def soak(ctx, trials, seed, verbose=True):
                     parts.append(ol.oracle_r2_ld(c[0], phase[o:o + c[0].shape[0]], c[1], W, idx=sub))
                     o += c[0].shape[0]
                 checks += 1
-                if not same(r2, np.concatenate(parts, axis=0)):
+                if not ol.bits_equal(r2, np.concatenate(parts, axis=0)):
                     fails += 1
                     print("FAIL r2", tag)
             # wLOD (synthetic weights) and TGLS
@@ -220,9 +239,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--trials", type=int, default=150)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--reuse-panel", action="store_true", help="keep one panel for three consecutive trials (PanelKeeper)")
     args = ap.parse_args()
     from garlic_amd import abi
-    checks, fails = soak(abi.Context(0), args.trials, args.seed)
+    checks, fails = soak(abi.Context(0), args.trials, args.seed, reuse_panel=args.reuse_panel)
     print(f"soak: {args.trials} panels, {checks} checks, {fails} failures")
     sys.exit(1 if fails else 0)
 
