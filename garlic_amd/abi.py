@@ -14,6 +14,8 @@ LIB_PATH = os.path.join(_HERE, "libgarlic_hip.so")
 
 OK, ERR_INVALID, ERR_HIP, ERR_STATE, ERR_NOMEM = 0, 1, 2, 3, 4
 HOST, DEVICE = 0, 1
+# GARLIC_VCF_*: what garlic_bed_set_rows_vcf answers per row
+VCF_BAD_BYTE, VCF_HALF_MISSING, VCF_HAPLOID, VCF_ALLELE_INDEX, VCF_FEW_COLUMNS, VCF_MANY_COLUMNS = 1, 2, 3, 4, 5, 6
 FEED_FROM_SCORES, FEED_CHAIN, FEED_SAMPLED_WLOD, FEED_TGLS_CHAIN = 0, 1, 2, 3   # garlic_lod_feed_info
 FEED_TGLS_CHAIN_SHARED = 4   # garlic_lod_feed_multi_info: the size shared its chain launch with another size
 FEED_ORDER_REFERENCE, FEED_ORDER_SORTED = 0, 1   # garlic_panel_set_feed_order
@@ -46,6 +48,7 @@ SYMBOLS = [
     "garlic_panel_set_gl_codes16",
     "garlic_bed_create", "garlic_bed_set_rows", "garlic_bed_census", "garlic_bed_destroy", "garlic_panel_set_genotypes_bed",
     "garlic_bed_extract", "garlic_bed_get_rows",
+    "garlic_bed_set_order_rows", "garlic_bed_get_order_rows", "garlic_bed_set_rows_vcf", "garlic_panel_set_phase_bed",
     "garlic_feed_kde", "garlic_lod_kde", "garlic_feed_kde_info", "garlic_feed_kde_times",
     "garlic_gmm_fit", "garlic_gmm_fit_info",
     "garlic_kde_part_create", "garlic_lod_kde_part", "garlic_kde_part_destroy", "garlic_kde_part_count",
@@ -241,6 +244,10 @@ def lib():
     L.garlic_bed_extract.argtypes = [_vp, _vp, C.c_int32, C.POINTER(_vp)]
     L.garlic_bed_get_rows.argtypes = [_vp, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_int32]
     L.garlic_panel_set_genotypes_bed.argtypes = [_vp, _vp, C.c_int64, _i64p]
+    L.garlic_bed_set_order_rows.argtypes = [_vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32]
+    L.garlic_bed_get_order_rows.argtypes = [_vp, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_int32]
+    L.garlic_bed_set_rows_vcf.argtypes = [_vp, _vp, C.c_int64, _i64p, C.c_int64, C.c_int64, _vp, C.c_int32]
+    L.garlic_panel_set_phase_bed.argtypes = [_vp, _vp, C.c_int64, _i64p]
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int and name not in ("garlic_hip_abi_version",):
@@ -784,6 +791,50 @@ class Bed:
         check(lib().garlic_bed_get_rows(self.handle, row_begin, row_count, _vp(rows.ctypes.data), self.row_bytes, HOST))
         return rows
 
+    @property
+    def order_row_bytes(self):
+        return (self.nind_total + 7) // 8
+
+    def set_order_rows(self, rows, row_begin=0):
+        """rows: uint8 [row_count][row_bytes >= (nind_total + 7) // 8] (host): the order plane, bit i & 7 of byte i >> 3 of a
+        row = "the first allele of individual i's genotype is A2"."""
+        rows = np.asarray(rows)
+        assert rows.dtype == np.uint8 and rows.ndim == 2 and (rows.shape[1] == 1 or rows.strides[1] == 1)
+        check(lib().garlic_bed_set_order_rows(self.handle, _vp(rows.ctypes.data), rows.strides[0], row_begin, rows.shape[0], HOST))
+
+    def set_order_rows_device(self, ptr, row_bytes, row_begin, row_count):
+        check(lib().garlic_bed_set_order_rows(self.handle, _vp(ptr), row_bytes, row_begin, row_count, DEVICE))
+
+    def get_order_rows(self, row_begin=0, row_count=None):
+        """uint8 [row_count][(nind_total + 7) // 8]: the order plane's rows as they stand on the device."""
+        row_count = self.nrows - row_begin if row_count is None else row_count
+        rows = np.empty((max(row_count, 0), self.order_row_bytes), dtype=np.uint8)
+        check(lib().garlic_bed_get_order_rows(self.handle, row_begin, row_count, _vp(rows.ctypes.data), self.order_row_bytes, HOST))
+        return rows
+
+    def set_rows_vcf(self, text, line_begin, row_begin=0, text_bytes=None, where=HOST):
+        """Image and order rows [row_begin, row_begin + len(line_begin) - 1) parsed from VCF text on the device
+        (garlic_bed_set_rows_vcf).  text: bytes / uint8 array (host), or a device address with text_bytes and where=DEVICE.
+        Returns (status int32 [rows][2] = code, sample column; error or None): an offence fills the status and comes back as
+        the GarlicError instead of being raised, so that a caller sees both."""
+        lb = np.ascontiguousarray(line_begin, dtype=np.int64)
+        assert lb.ndim == 1 and lb.shape[0] >= 2
+        if where == HOST:
+            buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else np.asarray(text)
+            assert buf.dtype == np.uint8 and buf.ndim == 1 and (buf.shape[0] <= 1 or buf.strides[0] == 1)
+            ptr, text_bytes = buf.ctypes.data, buf.shape[0] if text_bytes is None else text_bytes
+        else:
+            ptr = int(text)
+        status = np.zeros((lb.shape[0] - 1, 2), dtype=np.int32)
+        rc = lib().garlic_bed_set_rows_vcf(self.handle, _vp(ptr), int(text_bytes), _ptr(lb, _i64p), row_begin, lb.shape[0] - 1,
+                                           _vp(status.ctypes.data), where)
+        err = None
+        if rc != OK:
+            err = GarlicError(rc, lib().garlic_hip_last_error().decode())
+            if rc != ERR_INVALID or not status[:, 0].any():
+                raise err
+        return status, err
+
     def destroy(self):
         if self.handle:
             lib().garlic_bed_destroy(self.handle)
@@ -872,6 +923,12 @@ class Panel:
         dest = np.ascontiguousarray(dest_locus, dtype=np.int64)
         assert dest.shape == (bed.nrows,)
         check(lib().garlic_panel_set_genotypes_bed(self.handle, bed.handle, ind_offset, _ptr(dest, _i64p)))
+
+    def set_phase_bed(self, bed, dest_locus, ind_offset=0):
+        """HapData::firstCopy from a Bed image with an order plane, device to device; arguments as set_genotypes_bed."""
+        dest = np.ascontiguousarray(dest_locus, dtype=np.int64)
+        assert dest.shape == (bed.nrows,)
+        check(lib().garlic_panel_set_phase_bed(self.handle, bed.handle, ind_offset, _ptr(dest, _i64p)))
 
     def set_gl_codes(self, codes, values, locus_begin=0):
         """codes: uint8 [nloci_chunk][nind] indexing values (float64, <= 256 error probabilities)"""

@@ -35,9 +35,13 @@ __device__ __forceinline__ uint64_t bed_field_mask(int a, int b)
 // class counts of its pieces by popcount and the first non-missing genotype as the key  2 * individual + (hom A2);  per
 // group: sums and the minimum key over the lanes by cross-lane exchange -- no atomics, nothing depends on arrival order.
 // counts[r] = {nalleles, total}, counted[r] = 0 (A1), 1 (A2), 2 (none: every genotype missing).
+// An image with an order plane (`order` != NULL: one bit per genotype, rows of order_row_bytes, bit i & 7 of byte i >> 3 =
+// "the first allele of individual i's genotype is A2") takes the low bit of the winning key from the plane: a het that reads
+// "A2 A1" on its TPED line counts A2.
 __global__ void __launch_bounds__(256)
 bed_census_kernel(const uint8_t *__restrict__ image, int64_t nrows, int32_t nind, int64_t row_bytes, int32_t group,
-                  int32_t *__restrict__ counts, uint8_t *__restrict__ counted)
+                  int32_t *__restrict__ counts, uint8_t *__restrict__ counted, const uint8_t *__restrict__ order,
+                  int64_t order_row_bytes)
 {
     const int lane = threadIdx.x & (WAVE - 1);
     const int sub = lane & (group - 1);
@@ -86,6 +90,10 @@ bed_census_kernel(const uint8_t *__restrict__ image, int64_t nrows, int32_t nind
         }
         if (live && sub == 0) {
             const bool none = first == 0xFFFFFFFFu;
+            if (order && !none) {     // the genotype's own first allele instead of the implied "hom A2"
+                const uint32_t i = first >> 1;
+                first = (first & ~1u) | (((uint32_t)order[r * order_row_bytes + (i >> 3)] >> (i & 7u)) & 1u);
+            }
             const uint32_t c = none ? 2u : (first & 1u);
             counts[2 * r] = none ? 0 : (int32_t)(2 * (c ? n_a2 : n_a1) + n_het);
             counts[2 * r + 1] = none ? 0 : (int32_t)(2 * (n_a1 + n_het + n_a2));

@@ -30,6 +30,7 @@
 #include "../host/kde_parts.hpp"
 #include "../host/chain_order.hpp"
 #include "bed_kernels.hpp"
+#include "vcf_kernels.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -2907,6 +2908,13 @@ struct garlic_bed {
     bool census_valid = false;
     std::vector<int32_t> counts;                            // the census, cached with the image
     std::vector<uint8_t> counted;
+    // the order plane (vcf_kernels.hpp): one bit per genotype, "its first allele is A2"; absent until the first order or VCF call
+    int64_t order_row_bytes = 0;                            // (nind + 7) / 8
+    DevBuf<uint8_t> d_order;
+    bool have_order = false;
+    DevBuf<uint8_t> vcf_text;                               // garlic_bed_set_rows_vcf: a host slab on the device
+    DevBuf<int64_t> vcf_lines;
+    DevBuf<int32_t> vcf_status;
 };
 
 int garlic_bed_create(garlic_ctx *ctx, int64_t nrows, int32_t nind_total, garlic_bed **out)
@@ -2923,6 +2931,7 @@ int garlic_bed_create(garlic_ctx *ctx, int64_t nrows, int32_t nind_total, garlic
     b->nrows = nrows;
     b->nind = nind_total;
     b->row_bytes = ((int64_t)nind_total + 3) / 4;
+    b->order_row_bytes = ((int64_t)nind_total + 7) / 8;
     b->image_bytes = ((nrows * b->row_bytes + 15) & ~(int64_t)15) + BED_IMAGE_PAD;
     if ((rc = b->d_image.reserve((size_t)b->image_bytes)) || (rc = b->d_counts.reserve((size_t)(2 * nrows))) ||
         (rc = b->d_counted.reserve((size_t)nrows)))
@@ -2989,7 +2998,8 @@ static int bed_ensure_census(garlic_bed *b)
     const int64_t rows_per_block = 4 * (64 / group);
     const unsigned grid = (unsigned)std::min<int64_t>((b->nrows + rows_per_block - 1) / rows_per_block, 8 * (int64_t)b->ctx->n_cu);
     hipLaunchKernelGGL(bed_census_kernel, dim3(grid), dim3(256), 0, s, b->d_image.p, b->nrows, b->nind, b->row_bytes, group,
-                       b->d_counts.p, b->d_counted.p);
+                       b->d_counts.p, b->d_counted.p, b->have_order ? (const uint8_t *)b->d_order.p : (const uint8_t *)nullptr,
+                       b->order_row_bytes);
     HIP_TRY(hipGetLastError());
     b->counts.resize((size_t)(2 * b->nrows));
     b->counted.resize((size_t)b->nrows);
@@ -3018,14 +3028,16 @@ int garlic_bed_census(garlic_bed *b, int32_t *counts, uint8_t *counted, int32_t 
     return GARLIC_OK;
 }
 
-int garlic_panel_set_genotypes_bed(garlic_panel *p, garlic_bed *b, int64_t ind_offset, const int64_t *dest_locus)
+// what the doors from an image into a panel ask of their arguments; first / last: the smallest and largest destination
+static int bed_check_dest(const garlic_panel *p, const garlic_bed *b, int64_t ind_offset, const int64_t *dest_locus, int64_t &first,
+                          int64_t &last)
 {
-    if (!p || !b || !dest_locus) return fail(GARLIC_ERR_INVALID, "panel, bed and dest_locus are required");
     if (b->ctx->device != p->ctx->device)
         return fail(GARLIC_ERR_INVALID, "the bed image is on device %d, the panel on device %d", b->ctx->device, p->ctx->device);
     if (ind_offset < 0 || ind_offset + p->nind > b->nind)
         return fail(GARLIC_ERR_INVALID, "individuals [%lld,+%d) outside the image's %d", (long long)ind_offset, p->nind, b->nind);
-    int64_t prev = -1, first = -1;
+    int64_t prev = -1;
+    first = -1;
     for (int64_t r = 0; r < b->nrows; r++) {
         const int64_t l = dest_locus[r];
         if (l == -1) continue;
@@ -3038,6 +3050,15 @@ int garlic_panel_set_genotypes_bed(garlic_panel *p, garlic_bed *b, int64_t ind_o
         prev = l;
     }
     if (first < 0) return fail(GARLIC_ERR_INVALID, "dest_locus keeps no row");
+    last = prev;
+    return GARLIC_OK;
+}
+
+int garlic_panel_set_genotypes_bed(garlic_panel *p, garlic_bed *b, int64_t ind_offset, const int64_t *dest_locus)
+{
+    if (!p || !b || !dest_locus) return fail(GARLIC_ERR_INVALID, "panel, bed and dest_locus are required");
+    int64_t first, prev;
+    if (int rc = bed_check_dest(p, b, ind_offset, dest_locus, first, prev)) return rc;
     int rc;
     if ((rc = bed_ensure_census(b)) || (rc = set_device(p->ctx))) return rc;
     // the rows of every 16-locus word the call touches
@@ -3064,6 +3085,8 @@ int garlic_bed_extract(garlic_bed *src, const int32_t *ind_idx, int32_t n_idx, g
 {
     if (!src || !ind_idx || !out) return fail(GARLIC_ERR_INVALID, "bed extract: src, ind_idx and out are required");
     if (n_idx < 1 || n_idx >= (1 << 30)) return fail(GARLIC_ERR_INVALID, "bed extract: need 1 <= n_idx < 2^30, got %d", n_idx);
+    if (src->have_order)
+        return fail(GARLIC_ERR_INVALID, "bed extract: a column subset of an image with an order plane (VCF input) is not built");
     if (src->n_set != src->nrows)
         return fail(GARLIC_ERR_STATE, "bed extract needs every row of the source: %lld of %lld set", (long long)src->n_set, (long long)src->nrows);
     for (int32_t i = 0; i < n_idx; i++)
@@ -3088,6 +3111,7 @@ int garlic_bed_extract(garlic_bed *src, const int32_t *ind_idx, int32_t n_idx, g
     b->nrows = src->nrows;
     b->nind = n_idx;
     b->row_bytes = ((int64_t)n_idx + 3) / 4;
+    b->order_row_bytes = ((int64_t)n_idx + 7) / 8;
     b->image_bytes = ((b->nrows * b->row_bytes + 15) & ~(int64_t)15) + BED_IMAGE_PAD;
     DevBuf<int32_t> d_idx;
     DevBuf<BedSpan> d_spans;
@@ -3128,6 +3152,129 @@ int garlic_bed_get_rows(garlic_bed *b, int64_t row_begin, int64_t row_count, uin
     else
         HIP_TRY(hipMemcpy2DAsync(rows, (size_t)row_bytes, from, (size_t)b->row_bytes, (size_t)b->row_bytes, (size_t)row_count, kind, s));
     HIP_TRY(hipStreamSynchronize(s));
+    return GARLIC_OK;
+}
+
+// ---- the order plane of an image and the VCF door (vcf_kernels.hpp)
+// the plane of an image that gets its first order bits, all zero (padded as the image is)
+static int bed_ensure_order(garlic_bed *b)
+{
+    if (b->have_order) return GARLIC_OK;
+    const size_t bytes = (size_t)(((b->nrows * b->order_row_bytes + 15) & ~(int64_t)15) + BED_IMAGE_PAD);
+    if (int rc = b->d_order.reserve(bytes)) return rc;
+    HIP_TRY(hipMemsetAsync(b->d_order.p, 0, bytes, b->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(b->ctx->stream));
+    b->have_order = true;
+    b->census_valid = false;          // the counted allele now follows the plane
+    return GARLIC_OK;
+}
+
+static int bed_check_order_args(const garlic_bed *b, const void *rows, int64_t row_bytes, int64_t row_begin, int64_t row_count, int32_t where)
+{
+    if (!b || !rows) return fail(GARLIC_ERR_INVALID, "bed and rows are required");
+    if (where != GARLIC_HOST && where != GARLIC_DEVICE) return fail(GARLIC_ERR_INVALID, "where must be GARLIC_HOST or GARLIC_DEVICE");
+    if (row_bytes < b->order_row_bytes)
+        return fail(GARLIC_ERR_INVALID, "row_bytes %lld too small for the order bits of %d individuals (%lld)", (long long)row_bytes,
+                    b->nind, (long long)b->order_row_bytes);
+    if (row_begin < 0 || row_count < 1 || row_begin + row_count > b->nrows)
+        return fail(GARLIC_ERR_INVALID, "row range [%lld,+%lld) outside image of %lld rows", (long long)row_begin,
+                    (long long)row_count, (long long)b->nrows);
+    return GARLIC_OK;
+}
+
+int garlic_bed_set_order_rows(garlic_bed *b, const uint8_t *rows, int64_t row_bytes, int64_t row_begin, int64_t row_count, int32_t where)
+{
+    int rc;
+    if ((rc = bed_check_order_args(b, rows, row_bytes, row_begin, row_count, where)) || (rc = set_device(b->ctx)) ||
+        (rc = bed_ensure_order(b)))
+        return rc;
+    hipStream_t s = b->ctx->stream;
+    b->census_valid = false;
+    return for_each_upload_slab(s, "bed_set_order_rows", rows, row_bytes, row_count, where, b->stage, [&](const void *src, int64_t at, int64_t n) {
+        uint8_t *dst = b->d_order.p + (row_begin + at) * b->order_row_bytes;
+        const hipError_t e = row_bytes == b->order_row_bytes
+            ? hipMemcpyAsync(dst, src, (size_t)(n * row_bytes), hipMemcpyDeviceToDevice, s)
+            : hipMemcpy2DAsync(dst, (size_t)b->order_row_bytes, src, (size_t)row_bytes, (size_t)b->order_row_bytes, (size_t)n,
+                               hipMemcpyDeviceToDevice, s);
+        return e == hipSuccess ? GARLIC_OK : upload_fail("bed_set_order_rows", e);
+    });
+}
+
+int garlic_bed_get_order_rows(garlic_bed *b, int64_t row_begin, int64_t row_count, uint8_t *rows, int64_t row_bytes, int32_t where)
+{
+    int rc;
+    if ((rc = bed_check_order_args(b, rows, row_bytes, row_begin, row_count, where))) return rc;
+    if (!b->have_order) return fail(GARLIC_ERR_STATE, "the image has no order plane");
+    if ((rc = set_device(b->ctx))) return rc;
+    hipStream_t s = b->ctx->stream;
+    const uint8_t *from = b->d_order.p + row_begin * b->order_row_bytes;
+    const hipMemcpyKind kind = where == GARLIC_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    if (row_bytes == b->order_row_bytes)
+        HIP_TRY(hipMemcpyAsync(rows, from, (size_t)(row_count * row_bytes), kind, s));
+    else
+        HIP_TRY(hipMemcpy2DAsync(rows, (size_t)row_bytes, from, (size_t)b->order_row_bytes, (size_t)b->order_row_bytes, (size_t)row_count, kind, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return GARLIC_OK;
+}
+
+static const char *vcf_offence_name(int code)
+{
+    switch (code) {
+    case VCF_BAD_BYTE: return "a byte that is no part of a genotype `a sep b`";
+    case VCF_HALF_MISSING: return "a half-missing genotype";
+    case VCF_HAPLOID: return "a haploid genotype";
+    case VCF_ALLELE_INDEX: return "an allele index of 2 or more";
+    case VCF_FEW_COLUMNS: return "too few sample columns";
+    case VCF_MANY_COLUMNS: return "too many sample columns";
+    }
+    return "an unknown offence";
+}
+
+int garlic_bed_set_rows_vcf(garlic_bed *b, const char *text, int64_t text_bytes, const int64_t *line_begin, int64_t row_begin,
+                            int64_t row_count, int32_t *row_status, int32_t where)
+{
+    if (!b || !text || !line_begin) return fail(GARLIC_ERR_INVALID, "bed, text and line_begin are required");
+    if (where != GARLIC_HOST && where != GARLIC_DEVICE) return fail(GARLIC_ERR_INVALID, "where must be GARLIC_HOST or GARLIC_DEVICE");
+    if (text_bytes < 1) return fail(GARLIC_ERR_INVALID, "text_bytes %lld: the slab is empty", (long long)text_bytes);
+    if (row_begin < 0 || row_count < 1 || row_begin + row_count > b->nrows)
+        return fail(GARLIC_ERR_INVALID, "row range [%lld,+%lld) outside image of %lld rows", (long long)row_begin,
+                    (long long)row_count, (long long)b->nrows);
+    for (int64_t r = 0; r <= row_count; r++)
+        if (line_begin[r] < 0 || line_begin[r] > text_bytes || (r && line_begin[r] < line_begin[r - 1]))
+            return fail(GARLIC_ERR_INVALID, "line_begin[%lld] = %lld: the offsets must ascend inside the slab of %lld bytes", (long long)r,
+                        (long long)line_begin[r], (long long)text_bytes);
+    int rc;
+    if ((rc = set_device(b->ctx)) || (rc = bed_ensure_order(b))) return rc;
+    hipStream_t s = b->ctx->stream;
+    b->census_valid = false;
+    const uint8_t *d_text = reinterpret_cast<const uint8_t *>(text);
+    if (where == GARLIC_HOST) {
+        if ((rc = b->vcf_text.reserve((size_t)text_bytes + 16))) return rc;      // (its last piece lies inside the buffer)
+        HIP_TRY(hipMemcpyAsync(b->vcf_text.p, text, (size_t)text_bytes, hipMemcpyHostToDevice, s));
+        d_text = b->vcf_text.p;
+    }
+    if ((rc = b->vcf_lines.reserve((size_t)row_count + 1)) || (rc = b->vcf_status.reserve((size_t)(2 * row_count)))) return rc;
+    HIP_TRY(hipMemcpyAsync(b->vcf_lines.p, line_begin, sizeof(int64_t) * (size_t)(row_count + 1), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(vcf_parse_kernel, dim3((unsigned)row_count), dim3(256), 0, s, d_text, text_bytes, b->vcf_lines.p, row_begin,
+                       b->nind, b->d_image.p, b->row_bytes, b->d_order.p, b->order_row_bytes, b->vcf_status.p);
+    HIP_TRY(hipGetLastError());
+    std::vector<int32_t> status((size_t)(2 * row_count));
+    HIP_TRY(hipMemcpyAsync(status.data(), b->vcf_status.p, sizeof(int32_t) * status.size(), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (row_status) memcpy(row_status, status.data(), sizeof(int32_t) * status.size());
+    int64_t bad = -1;
+    for (int64_t r = 0; r < row_count; r++) {
+        if (status[(size_t)(2 * r)]) {
+            if (bad < 0) bad = r;
+            continue;                  // its bits are unspecified: the row does not count as set
+        }
+        uint64_t &word = b->row_set[(size_t)((row_begin + r) >> 6)];
+        const uint64_t bit = 1ull << ((row_begin + r) & 63);
+        if (!(word & bit)) { word |= bit; b->n_set++; }
+    }
+    if (bad >= 0)
+        return fail(GARLIC_ERR_INVALID, "VCF row %lld (line %lld of the call): %s at sample column %d", (long long)(row_begin + bad),
+                    (long long)bad, vcf_offence_name(status[(size_t)(2 * bad)]), status[(size_t)(2 * bad + 1)]);
     return GARLIC_OK;
 }
 
@@ -3340,6 +3487,31 @@ int garlic_panel_set_phase_bits(garlic_panel *p, const uint8_t *rows, int64_t ro
         return GARLIC_OK;
     });
     if (rc) return rc;
+    p->have_phase = true;
+    return GARLIC_OK;
+}
+
+int garlic_panel_set_phase_bed(garlic_panel *p, garlic_bed *b, int64_t ind_offset, const int64_t *dest_locus)
+{
+    if (!p || !b || !dest_locus) return fail(GARLIC_ERR_INVALID, "panel, bed and dest_locus are required");
+    if (!b->have_order) return fail(GARLIC_ERR_STATE, "set_phase_bed: the image has no order plane (it carries no phase)");
+    int64_t first, last;
+    const int nblk = (int)(p->nind_pad / WAVE);
+    int rc;
+    if ((rc = bed_check_dest(p, b, ind_offset, dest_locus, first, last)) || (rc = bed_ensure_census(b)) || (rc = set_device(p->ctx)) ||
+        (rc = ensure_phase_planes(p, nblk)))
+        return rc;
+    hipStream_t s = p->ctx->stream;
+    DevBuf<int64_t> d_dest;      // (freed behind the synchronise below)
+    if ((rc = d_dest.reserve((size_t)b->nrows))) return rc;
+    HIP_TRY(hipMemcpyAsync(d_dest.p, dest_locus, sizeof(int64_t) * (size_t)b->nrows, hipMemcpyHostToDevice, s));
+    const int64_t blocks = (b->nrows * nblk + 3) / 4;
+    hipLaunchKernelGGL(bed_phase_planes_kernel, dim3((unsigned)std::min<int64_t>(blocks, 64 * (int64_t)p->ctx->n_cu)), dim3(256), 0, s,
+                       b->d_image.p, b->row_bytes, b->d_order.p, b->order_row_bytes, b->d_counted.p, d_dest.p, b->nrows, ind_offset,
+                       p->nind, nblk, p->nloci, p->d_phase.p);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(s);       // also: dest_locus is free again
+    if (e != hipSuccess) return upload_fail("set_phase_bed", e);
     p->have_phase = true;
     return GARLIC_OK;
 }

@@ -1,5 +1,6 @@
 // Host adapter: the reference's Phase-I interface on top of libgarlic_hip.so (see garlic_host.hpp).
 #include "garlic_host.hpp"
+#include "vcf_lines.hpp"
 
 #include "../../include/garlic_hip.h"
 
@@ -623,6 +624,8 @@ garlic_bed *bedFullImageOn(BedFile *b, int device)
         memcpy(buf.data(), b->rows + (size_t)r * b->row_bytes, (size_t)n * b->row_bytes);
         check(garlic_bed_set_rows(bed, buf.data(), (int64_t)b->row_bytes, r, n, GARLIC_HOST), "garlic_bed_set_rows");
     }
+    if (b->order)      // a VCF image: its order plane from the host's copy
+        check(garlic_bed_set_order_rows(bed, b->order, (int64_t)b->order_row_bytes, 0, b->nrows, GARLIC_HOST), "garlic_bed_set_order_rows");
     return bed;
 }
 
@@ -673,6 +676,111 @@ void loadBedData(const std::string &bedfile, const std::string &bimfile, const s
     BedFile *b = openBedFile(bedfile, bimfile, famfile);
     b->refs = 1;                 // this function's, until the HapData hold theirs
     loadBedFile(b, numLoci, numInd, hapDataByChr, mapDataByChr, freqDataByChr, nresample, resampleSeed, device);
+}
+
+void loadVcfData(const std::string &vcffile, bool phased, bool snpsOnly, std::vector<std::string> &samples, int &numLoci, int &numInd,
+                 std::vector<HapData *> **hapDataByChr, std::vector<MapData *> **mapDataByChr, std::vector<FreqData *> **freqDataByChr,
+                 int nresample, unsigned long long resampleSeed, int device)
+{
+    std::unique_ptr<BedFile, void (*)(BedFile *)> b(new BedFile, closeBedFile);
+    b->path = vcffile;
+    b->phased = phased;
+    const size_t SLAB = (size_t)64 << 20;
+    // first pass: the header, the nine fixed columns of every data line, and which lines are kept -- the row count that
+    // garlic_bed_create needs
+    std::vector<char> kept;                // per data line
+    samples.clear();
+    {
+        vcf::Reader rd;
+        if (!rd.open(vcffile, SLAB)) fail(rd.error);
+        vcf::SlabLines cut;
+        size_t used = 0;
+        std::string err;
+        do {
+            if (!rd.next(used)) fail(vcffile + ": " + rd.error);
+            used = cut.take(rd.slab.data(), rd.have, rd.eof);
+            if (!rd.eof && used == 0 && rd.have == rd.slab.size()) fail(vcffile + ": a line longer than 64 MB");
+            for (size_t k = 0; k < cut.begin.size(); k++) {
+                const char *line = rd.slab.data() + cut.begin[k];
+                const size_t len = (size_t)(cut.end[k] - cut.begin[k]);
+                const std::string where = "line " + std::to_string(cut.number[k]) + " of " + vcffile + ": ";
+                if (line[0] == '#') {
+                    if (len >= 6 && memcmp(line, "#CHROM", 6) == 0 && !vcf::parseHeader(line, len, samples, err)) fail(where + err);
+                    continue;
+                }
+                if (samples.empty()) fail(where + "a data line before the #CHROM line");
+                vcf::Site site;
+                const vcf::LineKind kind = vcf::parseFixed(line, len, site, err);
+                if (kind == vcf::LINE_BAD || (kind == vcf::LINE_NOT_SNP && !snpsOnly))
+                    fail(where + err + (kind == vcf::LINE_NOT_SNP ? " (--vcf-biallelic-snps-only leaves such lines out)" : ""));
+                kept.push_back(kind == vcf::LINE_SNP);
+                if (kind != vcf::LINE_SNP) { b->skipped_non_snp++; continue; }
+                b->chr.push_back(site.chr); b->name.push_back(site.name); b->gpos.push_back(0.0); b->ppos.push_back((double)site.ppos);
+                b->a1.push_back(site.a1); b->a2.push_back(site.a2);
+            }
+        } while (!rd.eof || used < rd.have);
+    }
+    if (samples.empty()) fail("no #CHROM line in " + vcffile);
+    b->nind = (int)samples.size();
+    b->nrows = (long long)b->chr.size();
+    if (b->nrows < 1) fail("no loci in " + vcffile);
+    b->row_bytes = ((size_t)b->nind + 3) / 4;
+    b->order_row_bytes = ((size_t)b->nind + 7) / 8;
+    // second pass: the text to the device in slabs, one parse call per slab
+    const size_t slot = bedSlotOn(b.get(), device);
+    garlic_bed *bed = nullptr;
+    check(garlic_bed_create((garlic_ctx *)b->images[slot].ctx, b->nrows, b->nind, &bed), "garlic_bed_create");
+    b->images[slot].bed = bed;
+    {
+        vcf::Reader rd;
+        if (!rd.open(vcffile, SLAB)) fail(rd.error);
+        vcf::SlabLines cut;
+        size_t used = 0, data_line = 0;
+        long long row = 0;
+        std::vector<int64_t> lb, number;
+        std::vector<int32_t> status;
+        do {
+            if (!rd.next(used)) fail(vcffile + ": " + rd.error);
+            used = cut.take(rd.slab.data(), rd.have, rd.eof);
+            lb.clear();
+            number.clear();
+            int64_t last_end = 0;
+            for (size_t k = 0; k < cut.begin.size(); k++) {
+                if (rd.slab[(size_t)cut.begin[k]] == '#') continue;
+                if (data_line >= kept.size()) fail(vcffile + " changed while it was read");
+                if (!kept[data_line++]) continue;
+                lb.push_back(cut.begin[k]);
+                number.push_back(cut.number[k]);
+                last_end = cut.end[k];
+            }
+            if (lb.empty()) continue;
+            const int64_t n = (int64_t)lb.size();
+            if (row + n > b->nrows) fail(vcffile + " changed while it was read");
+            lb.push_back(last_end);
+            status.assign((size_t)(2 * n), 0);
+            const int rc = garlic_bed_set_rows_vcf(bed, rd.slab.data(), (int64_t)rd.have, lb.data(), row, n, status.data(), GARLIC_HOST);
+            if (rc == GARLIC_ERR_INVALID) {
+                for (int64_t r = 0; r < n; r++)
+                    if (status[(size_t)(2 * r)]) {
+                        const int col = status[(size_t)(2 * r + 1)];
+                        fail("line " + std::to_string(number[(size_t)r]) + " of " + vcffile + ", sample " + std::to_string(col + 1) +
+                             (col < b->nind ? " (" + samples[(size_t)col] + ")" : std::string()) + ": " + garlic_hip_last_error());
+                    }
+            }
+            check(rc, "garlic_bed_set_rows_vcf");
+            row += n;
+        } while (!rd.eof || used < rd.have);
+        if (row != b->nrows) fail(vcffile + " changed while it was read");
+    }
+    // the host's copies, fetched once: genotypeAt, the phase readers, the genotype cache, and the source of further devices' images
+    b->own_rows.resize((size_t)b->nrows * b->row_bytes);
+    b->own_order.resize((size_t)b->nrows * b->order_row_bytes);
+    check(garlic_bed_get_rows(bed, 0, b->nrows, b->own_rows.data(), (int64_t)b->row_bytes, GARLIC_HOST), "garlic_bed_get_rows");
+    check(garlic_bed_get_order_rows(bed, 0, b->nrows, b->own_order.data(), (int64_t)b->order_row_bytes, GARLIC_HOST), "garlic_bed_get_order_rows");
+    b->rows = b->own_rows.data();
+    b->order = b->own_order.data();
+    b->refs = 1;
+    loadBedFile(b.release(), numLoci, numInd, hapDataByChr, mapDataByChr, freqDataByChr, nresample, resampleSeed, device);
 }
 
 void loadBedSubset(BedFile *full, const std::vector<int> &keep, int &numLoci, int &numInd, std::vector<HapData *> **hapDataByChr,
@@ -1233,6 +1341,12 @@ void writeGenotypeCache(const std::string &path, std::vector<HapData *> *haps, s
             for (int l = 0; l < m->nloci; l++) {   // HapData::firstCopy, one bit per individual: bit i & 7 of byte i >> 3
                 if (h->phaseBits) { o.put(h->phaseBits[l], prow); continue; }
                 std::fill(pbits.begin(), pbits.end(), 0);
+                if (h->bed) {      // a VCF image: firstCopy from the order plane
+                    for (int i = 0; i < nind; i++)
+                        if (bedFirstCopy(h->bed, (size_t)h->bedRow[l], i)) pbits[i >> 3] |= (uint8_t)(1u << (i & 7));
+                    o.put(pbits.data(), prow);
+                    continue;
+                }
                 for (int i = 0; i < nind; i++)
                     if (h->firstCopy[l][i]) pbits[i >> 3] |= (uint8_t)(1u << (i & 7));
                 o.put(pbits.data(), prow);
@@ -1404,9 +1518,12 @@ void LodEngine::upload(std::vector<HapData *> *haps, std::vector<FreqData *> *fr
             if (h->bed != b) fail("the chromosomes come from different .bed files");
             for (int l = 0; l < h->nloci; l++) dest[(size_t)h->bedRow[l]] = at++;
         }
-        for (auto &s : impl->shards)
+        for (auto &s : impl->shards) {
             check(garlic_panel_set_genotypes_bed(s.panel, bedImageOn(b, s.device), s.ind_begin, dest.data()),
                   "garlic_panel_set_genotypes_bed");
+            if (hasPhase(haps->at(0)))      // a phased VCF: firstCopy from the image's order plane, device to device
+                check(garlic_panel_set_phase_bed(s.panel, bedImageOn(b, s.device), s.ind_begin, dest.data()), "garlic_panel_set_phase_bed");
+        }
     }
     // genotype rows are separate allocations in HapData: stage a slab of SNP rows at a time
     const int64_t slab = std::max<int64_t>(1, ((int64_t)64 << 20) / (2 * (int64_t)impl->nind));
@@ -1452,7 +1569,8 @@ void LodEngine::upload(std::vector<HapData *> *haps, std::vector<FreqData *> *fr
                     memcpy(&stage_gl[(size_t)r * impl->nind], gld->data[l0 + r], sizeof(double) * impl->nind);
             }
             const size_t prow_bytes = ((size_t)impl->nind + 7) / 8;
-            if (impl->have_phase && h->phaseBits) {   // one bit per genotype, as the cache holds them
+            if (h->bed) {   // (filled above)
+            } else if (impl->have_phase && h->phaseBits) {   // one bit per genotype, as the cache holds them
                 stage_fc.resize((size_t)rows * prow_bytes);
                 for (int r = 0; r < rows; r++) memcpy(&stage_fc[(size_t)r * prow_bytes], h->phaseBits[l0 + r], prow_bytes);
             } else if (impl->have_phase) {
@@ -1469,7 +1587,8 @@ void LodEngine::upload(std::vector<HapData *> *haps, std::vector<FreqData *> *fr
                 else
                     check(garlic_panel_set_genotypes(s.panel, stage.data() + s.ind_begin, impl->nind, o + l0, rows,
                                                      GARLIC_HOST), "garlic_panel_set_genotypes");
-                if (impl->have_phase && h->phaseBits && (s.ind_begin & 7) == 0) {
+                if (h->bed) {
+                } else if (impl->have_phase && h->phaseBits && (s.ind_begin & 7) == 0) {
                     check(garlic_panel_set_phase_bits(s.panel, stage_fc.data() + s.ind_begin / 8, (int64_t)prow_bytes, o + l0, rows,
                                                       GARLIC_HOST), "garlic_panel_set_phase_bits");
                 } else if (impl->have_phase && h->phaseBits) {   // a shard that begins inside a byte: its bits moved down

@@ -55,8 +55,27 @@ struct BedFile {
     std::vector<int> keep;
     std::vector<unsigned char> own_rows;
     bool hold_images = false;
+    // VCF input (loadVcfData): nothing is mapped; `rows` points into own_rows, the image fetched back once after the parse on
+    // the first device, and `order` into own_order, its order plane (one bit per genotype: the first allele is A2; row r at
+    // order + r * order_row_bytes).  Further devices get both through garlic_bed_set_rows / garlic_bed_set_order_rows.  With
+    // `phased` the plane is also the phase: HapData::firstCopy is firstCopyAt.
+    const unsigned char *order = nullptr;
+    size_t order_row_bytes = 0;           // (nind + 7) / 8
+    std::vector<unsigned char> own_order;
+    bool phased = false;
+    long long skipped_non_snp = 0;        // --vcf-biallelic-snps-only: lines left out
     const BedFile *bim() const { return parent ? parent : this; }
 };
+// HapData::firstCopy of file row r, individual i of a VCF image: non-missing && (order bit == (counted == A2)); all true on a
+// row without a counted allele
+inline bool bedFirstCopy(const BedFile *b, size_t r, int i)
+{
+    const unsigned c = b->counted[r];
+    if (c >= 2) return true;
+    const unsigned code = (b->rows[r * b->row_bytes + (i >> 2)] >> (2 * (i & 3))) & 3u;
+    const unsigned bit = (b->order[r * b->order_row_bytes + (i >> 3)] >> (i & 7)) & 1u;
+    return code != 1u && bit == c;
+}
 // copies of the counted allele by counted[row] and PLINK code; -9 = missing
 inline short bedGenotype(unsigned counted, unsigned code)
 {
@@ -84,7 +103,7 @@ struct HapData {           // src/garlic-data.h:32-38
     BedFile *bed;
     long long *bedRow;
 };
-inline bool hasPhase(const HapData *h) { return h->firstCopy || h->phaseBits; }
+inline bool hasPhase(const HapData *h) { return h->firstCopy || h->phaseBits || (h->bed && h->bed->order && h->bed->phased); }
 inline short genotypeAt(const HapData *h, int locus, int ind)
 {
     if (h->data) return h->data[locus][ind];
@@ -216,6 +235,13 @@ void releaseBedFile(BedFile *b);          // one reference less; the last one cl
 // The (hap, map, freq) triple of the file set that holds only the individuals `keep` of `full` (ascending indices into its
 // .fam): the full image goes to `device` (once per device and parent), garlic_bed_extract cuts the subset out of it, and
 // census, frequencies, row map, shards and the host's view of the genotypes are the subset image's from there on.
+// VCF input: the genotype text is parsed on `device` (garlic_bed_set_rows_vcf) into an image with an order plane; the host reads
+// the header and the nine fixed columns (vcf_lines.hpp).  tfam "": family 0 and the header's names; otherwise its count must
+// match.  samples: the header's names.  snpsOnly: lines whose REF / ALT is not one base are left out and counted
+// (BedFile::skipped_non_snp) instead of ending the run.
+void loadVcfData(const std::string &vcffile, bool phased, bool snpsOnly, std::vector<std::string> &samples, int &numLoci, int &numInd,
+                 std::vector<HapData *> **hapDataByChr, std::vector<MapData *> **mapDataByChr, std::vector<FreqData *> **freqDataByChr,
+                 int nresample, unsigned long long resampleSeed, int device);
 void loadBedSubset(BedFile *full, const std::vector<int> &keep, int &numLoci, int &numInd, std::vector<HapData *> **hapDataByChr,
                    std::vector<MapData *> **mapDataByChr, std::vector<FreqData *> **freqDataByChr, int nresample,
                    unsigned long long resampleSeed, int device);

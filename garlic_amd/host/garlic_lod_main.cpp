@@ -8,7 +8,8 @@
 //   <out>.<W>SNPs.lod.sorted.f64           instead, with --sorted-feed: the same doubles ascending -- the array
 //                                          computeKDE's nrd0 makes of the feed first (gsl_sort, src/garlic-kde.cpp:132),
 //                                          sorted on the device
-// Input besides the reference's tped/tfam: a PLINK .bed/.bim/.fam (--bfile PREFIX, or --bed F --bim F --fam F).  The rows go
+// Input besides the reference's tped/tfam: a VCF (--vcf F[.gz], parsed on the device, phase included) or
+// a PLINK .bed/.bim/.fam (--bfile PREFIX, or --bed F --bim F --fam F).  The rows go
 // to the device as they are; the counted allele of every SNP and its frequency come from a census there, and the genotypes
 // never exist on the host as anything but the mapped file.
 //   <out>.<W>SNPs.kde                      with --kde: computeKDE's density of the feed (src/garlic-kde.cpp:14-140; the exact
@@ -37,12 +38,12 @@ using namespace garlic_host;
 namespace {
 struct Args {
     std::string tped, tfam, out = "outfile", build = "none", centromere = "none", tgls = "none",
-                gl_type = "none", freq_file = "none", map = "none", cache = "none", bed, bim, fam, bfile;
+                gl_type = "none", freq_file = "none", map = "none", cache = "none", bed, bim, fam, bfile, vcf;
     char tped_missing = '0';       // src/garlic-cli.cpp:114
     double error = -1;             // :34 (must be in (0,1) unless TGLS)
     int winsize = 0;               // :38
     std::vector<int> winsize_multi;
-    bool auto_winsize = false, weighted = false, raw_lod = false, kde_thinning = true, phased = false;
+    bool auto_winsize = false, weighted = false, raw_lod = false, kde_thinning = true, phased = false, vcf_snps_only = false;
     bool sorted_feed = false;      // extension: the feeds ascending, <out>.<W>SNPs.lod.sorted.f64 (the device sorts them)
     bool kde_sharded = false;      // extension: with --kde, the KDE of a sharded panel on the shards' devices (garlic_kde_parts)
     bool kde = false;              // extension: the KDE, the LOD cutoff and (--auto-winsize) the window size in this tool
@@ -101,6 +102,10 @@ struct Args {
                  "                    --tfam-counting, wherever those go: the counting genotypes as a PLINK SNP-major file set; only the\n"
                  "                    .bim and the .fam are read on the host, the hom rows are built from the .bed image on the device; the\n"
                  "                    counting individuals are the .fam's, also under --keep / --pops)\n"
+                 "         [--vcf F[.gz] [--tfam T] [--vcf-biallelic-snps-only]]   (VCF input wherever --bfile goes: the genotypes and the phase\n"
+                 "          are parsed on the device, --phased is allowed; without --tfam the family is 0 and the IDs are the header's;\n"
+                 "          a REF / ALT that is not one base ends the run, or is left out and counted under --vcf-biallelic-snps-only;\n"
+                 "          not with --keep / --pops / --bfile / --bed / --bim / --fam / --tped)\n"
                  "         (--bfile / --bed --bim --fam: PLINK SNP-major .bed input, read on the device; not with --tped / --tfam /\n"
                  "          --phased; --genotype-cache F is then written from the .bed, never read)\n"
                  "         [--keep F]   (with PLINK input: the run is that of a file set holding only the individuals of F, a PLINK keep\n"
@@ -122,6 +127,8 @@ Args parse(int argc, char **argv)
         if (f == "--tped") a.tped = val();
         else if (f == "--tfam") a.tfam = val();
         else if (f == "--bfile") a.bfile = val();
+        else if (f == "--vcf") a.vcf = val();
+        else if (f == "--vcf-biallelic-snps-only") a.vcf_snps_only = true;
         else if (f == "--bed") a.bed = val();
         else if (f == "--bim") a.bim = val();
         else if (f == "--fam") a.fam = val();
@@ -209,16 +216,24 @@ Args parse(int argc, char **argv)
     if (!a.keep.empty() && !a.pops.empty()) usage("--keep and --pops exclude each other (--pops is --keep of every listed population in turn)");
     if (!a.pops.empty() && !a.roh_bed.empty()) usage("--pops with --roh-bed: --roh-bed counts on existing calls and reads no populations");
     if (!a.roh_bed.empty()) {      // counts on an existing calls file: nothing else is read
-        if (!a.tped.empty() || !a.tfam.empty() || !a.bfile.empty() || !a.bed.empty()) usage("--roh-bed counts on existing calls and takes no genotype input");
+        if (!a.tped.empty() || !a.tfam.empty() || !a.bfile.empty() || !a.bed.empty() || !a.vcf.empty()) usage("--roh-bed counts on existing calls and takes no genotype input");
         if (a.devices.empty()) a.devices.push_back(0);
         return a;
     }
     // validators of src/garlic-cli.cpp:240-462 that concern Phase I
-    if (!a.bfile.empty()) {
+    if (a.vcf_snps_only && a.vcf.empty()) usage("--vcf-biallelic-snps-only needs --vcf");
+    if (!a.vcf.empty()) {
+        if (!a.bfile.empty() || !a.bed.empty() || !a.bim.empty() || !a.fam.empty() || !a.tped.empty())
+            usage("--vcf and --bfile / --bed / --bim / --fam / --tped exclude each other");
+        if (!a.keep.empty() || !a.pops.empty()) usage("--vcf with --keep / --pops: a column subset of a VCF image is not built");
+    }
+    if (!a.vcf.empty()) {
+    } else if (!a.bfile.empty()) {
         if (!a.bed.empty() || !a.bim.empty() || !a.fam.empty()) usage("--bfile and --bed / --bim / --fam exclude each other");
         a.bed = a.bfile + ".bed"; a.bim = a.bfile + ".bim"; a.fam = a.bfile + ".fam";
     }
-    if (!a.bed.empty() || !a.bim.empty() || !a.fam.empty()) {
+    if (!a.vcf.empty()) {
+    } else if (!a.bed.empty() || !a.bim.empty() || !a.fam.empty()) {
         if (a.bed.empty() || a.bim.empty() || a.fam.empty()) usage("--bed, --bim and --fam go together");
         if (!a.tped.empty() || !a.tfam.empty()) usage("--bfile / --bed and --tped / --tfam exclude each other");
         if (a.phased) usage("--phased with --bfile: a .bed carries no phase");
@@ -290,9 +305,20 @@ int run(const Args &a, FeatureData *features, BedFile *full, const std::vector<F
         std::vector<int> devices = a.devices;
         if (devices.empty())
             for (int d = 0; d < a.gpus; d++) devices.push_back(d);
-        FILE *probe = a.cache == "none" || !a.bed.empty() ? nullptr : fopen(a.cache.c_str(), "rb");
+        FILE *probe = a.cache == "none" || !a.bed.empty() || !a.vcf.empty() ? nullptr : fopen(a.cache.c_str(), "rb");
+        std::vector<std::string> vcf_samples;
         if (keep) ind = indDataOfKept(*fam, *keep, a.fam);      // the single-population check, over the kept individuals
-        if (!a.bed.empty()) {   // PLINK input: census on the first device; the cache, if asked for, is written from it
+        if (!a.vcf.empty()) {   // VCF input: parsed on the first device; the cache, if asked for, is written from the image
+            loadVcfData(a.vcf, a.phased, a.vcf_snps_only, vcf_samples, numLoci, numInd, &haps, &maps, &freqs, a.resample, a.resample_seed,
+                        devices[0]);
+            if (a.vcf_snps_only)
+                std::cerr << "Left out " << haps->at(0)->bed->skipped_non_snp << " lines of " << a.vcf << " that are no biallelic SNPs\n";
+            if (a.resample > 0) std::cerr << "Allele frequencies resampled: " << a.resample << "\n";
+            if (a.cache != "none") {
+                writeGenotypeCache(a.cache, haps, maps, freqs);
+                std::cerr << "Wrote genotype cache " << a.cache << "\n";
+            }
+        } else if (!a.bed.empty()) {   // PLINK input: census on the first device; the cache, if asked for, is written from it
             if (keep) loadBedSubset(full, *keep, numLoci, numInd, &haps, &maps, &freqs, a.resample, a.resample_seed, devices[0]);
             else loadBedData(a.bed, a.bim, a.fam, numLoci, numInd, &haps, &maps, &freqs, a.resample, a.resample_seed, devices[0]);
             if (a.resample > 0) std::cerr << "Allele frequencies resampled: " << a.resample << "\n";
@@ -317,7 +343,13 @@ int run(const Args &a, FeatureData *features, BedFile *full, const std::vector<F
                 std::cerr << "Wrote genotype cache " << a.cache << "\n";
             }
         }
-        if (!keep) {
+        if (!a.vcf.empty() && a.tfam.empty()) {      // the .tfam vcf2tped.pl writes: family 0, the header's names
+            ind = new IndData;
+            ind->nind = numInd;
+            ind->pop = "0";
+            ind->indID = new std::string[numInd];
+            for (int i = 0; i < numInd; i++) ind->indID[i] = vcf_samples[(size_t)i];
+        } else if (!keep) {
             std::string pop;
             int nindFam = 0;
             scanIndData3(a.tfam, nindFam, pop);

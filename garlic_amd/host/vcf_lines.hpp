@@ -1,0 +1,181 @@
+// VCF text on the host: everything about a VCF that is not a genotype.  Header-only.
+//
+// The genotypes of a data line are parsed on the device (garlic_bed_set_rows_vcf); the host reads the file through zlib
+// (gzopen: plain text, .gz, and bgzf as multi-member gzip), skips the ## lines, takes the individuals from the #CHROM line,
+// and of every data line parses the nine fixed columns into the .bim fields
+//     chr = CHROM, name = ID, gpos = 0, ppos = POS, a1 = REF, a2 = ALT
+// checking that FORMAT begins with GT.  A line whose REF or ALT is not exactly one character (`,` lists, `.`, `*`, `<...>`
+// included) is no biallelic SNP: refused, or under skipNonSnp left out of line_begin and counted.
+//
+// The text goes to the device in slabs.  VcfSlabLines cuts a slab into lines with memchr: a slab ends wherever the read
+// ended, so the bytes behind its last '\n' are carried to the front of the next one; the file's last line needs no '\n', and
+// a '\r' before the '\n' belongs to the line (the device accepts it as the end of a genotype).
+#pragma once
+#include <zlib.h>
+
+#include <cstdint>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+namespace vcf {
+
+struct Site {
+    std::string chr, name;
+    double gpos = 0;
+    long long ppos = 0;
+    char a1 = 0, a2 = 0;
+};
+
+enum LineKind { LINE_SNP = 0, LINE_NOT_SNP = 1, LINE_BAD = 2 };
+
+// the samples of a "#CHROM POS ID REF ALT QUAL FILTER INFO FORMAT s0 s1 ..." line (tab-separated; a trailing \r is dropped)
+inline bool parseHeader(const char *line, size_t len, std::vector<std::string> &samples, std::string &err)
+{
+    while (len && (line[len - 1] == '\n' || line[len - 1] == '\r')) len--;
+    std::vector<std::string> cols;
+    size_t at = 0;
+    while (at <= len) {
+        const char *tab = (const char *)memchr(line + at, '\t', len - at);
+        const size_t end = tab ? (size_t)(tab - line) : len;
+        cols.emplace_back(line + at, end - at);
+        at = end + 1;
+    }
+    if (cols.size() < 10 || cols[0] != "#CHROM" || cols[8] != "FORMAT") {
+        err = "the #CHROM line needs the nine fixed columns up to FORMAT and at least one sample";
+        return false;
+    }
+    samples.assign(cols.begin() + 9, cols.end());
+    for (const std::string &s : samples)
+        if (s.empty()) { err = "the #CHROM line has an empty sample name"; return false; }
+    return true;
+}
+
+// the nine fixed columns of a data line [line, line + len) (len stops at or before the '\n')
+inline LineKind parseFixed(const char *line, size_t len, Site &site, std::string &err)
+{
+    const char *col[10];
+    size_t n = 0, at = 0;
+    col[0] = line;
+    while (n < 9 && len) {
+        const char *tab = (const char *)memchr(line + at, '\t', len - at);
+        if (!tab) break;
+        at = (size_t)(tab - line) + 1;
+        col[++n] = line + at;
+    }
+    if (n < 9) { err = "fewer than nine fixed columns and one sample"; return LINE_BAD; }
+    auto width = [&](int k) { return (size_t)(col[k + 1] - col[k]) - 1; };
+    if (width(0) == 0 || width(1) == 0 || width(2) == 0) { err = "empty CHROM, POS or ID"; return LINE_BAD; }
+    site.chr.assign(col[0], width(0));
+    site.name.assign(col[2], width(2));
+    site.gpos = 0;
+    const std::string pos(col[1], width(1));
+    char *stop = nullptr;
+    site.ppos = strtoll(pos.c_str(), &stop, 10);
+    if (*stop || site.ppos < 0) { err = "POS '" + pos + "' is no position"; return LINE_BAD; }
+    if (width(8) < 2 || col[8][0] != 'G' || col[8][1] != 'T' || (width(8) > 2 && col[8][2] != ':')) {
+        err = "FORMAT '" + std::string(col[8], width(8)) + "' does not begin with GT";
+        return LINE_BAD;
+    }
+    auto base = [](char c) { return c != '.' && c != '*' && c != ',' && c != '<' && c != '>'; };
+    if (width(3) != 1 || width(4) != 1 || !base(col[3][0]) || !base(col[4][0])) {
+        err = "REF '" + std::string(col[3], width(3)) + "' ALT '" + std::string(col[4], width(4)) + "' is no biallelic SNP";
+        return LINE_NOT_SNP;
+    }
+    site.a1 = col[3][0];
+    site.a2 = col[4][0];
+    return LINE_SNP;
+}
+
+// One slab of text cut into lines.  take(slab, n, last): the lines that are complete in [slab, slab + n) -- all of them when
+// `last` (the file has ended: a final line without '\n' counts) -- as begin[k] / end[k] (end: the '\n' or n); returns the
+// number of bytes consumed: the caller moves the rest, slab[consumed .. n), to the front of the next slab.  Empty lines
+// are passed over.
+struct SlabLines {
+    std::vector<int64_t> begin, end, number;      // number: the line's 1-based number in the file, empty lines counted
+    int64_t seen = 0;                             // lines of the file taken so far
+    size_t take(const char *slab, size_t n, bool last)
+    {
+        begin.clear();
+        end.clear();
+        number.clear();
+        size_t at = 0;
+        while (at < n) {
+            const char *nl = (const char *)memchr(slab + at, '\n', n - at);
+            if (!nl && !last) break;
+            const size_t e = nl ? (size_t)(nl - slab) : n;
+            const bool blank = e == at || (e == at + 1 && slab[at] == '\r');
+            seen++;
+            if (!blank) {
+                begin.push_back((int64_t)at);
+                end.push_back((int64_t)e);
+                number.push_back(seen);
+            }
+            at = nl ? e + 1 : n;
+        }
+        return at;
+    }
+};
+
+// A VCF read through zlib in slabs of at most `cap` bytes.  next() fills the slab behind what the previous one left over;
+// false when the file has ended and nothing is left.
+struct Reader {
+    gzFile f = nullptr;
+    std::vector<char> slab;
+    size_t have = 0;          // bytes of the slab in use
+    bool eof = false;
+    std::string error;
+    bool open(const std::string &path, size_t cap)
+    {
+        f = gzopen(path.c_str(), "rb");
+        if (!f) { error = "cannot open " + path; return false; }
+        gzbuffer(f, 1 << 20);
+        slab.resize(cap);
+        have = 0;
+        eof = false;
+        return true;
+    }
+    // drop the first `consumed` bytes and read on; returns false on a read error (error set) -- at the end of the file it
+    // returns true with eof set and have = what was left
+    bool next(size_t consumed)
+    {
+        memmove(slab.data(), slab.data() + consumed, have - consumed);
+        have -= consumed;
+        while (!eof && have < slab.size()) {
+            const size_t want = slab.size() - have;
+            const int got = gzread(f, slab.data() + have, (unsigned)(want < (1u << 30) ? want : (1u << 30)));
+            if (got < 0) { int e; error = gzerror(f, &e); return false; }
+            if (got == 0) {
+                // a truncated .gz hands out what it has and leaves Z_BUF_ERROR behind: no clean end of the file
+                int e = Z_OK;
+                const char *msg = gzerror(f, &e);
+                if (e != Z_OK && e != Z_STREAM_END) { error = std::string("read error (truncated file?): ") + msg; return false; }
+                eof = true;
+            }
+            have += (size_t)got;
+        }
+        return true;
+    }
+    void close() { if (f) gzclose(f); f = nullptr; }
+    ~Reader() { close(); }
+};
+
+// lines of a file that do not start with '#': the counting pass in front of garlic_bed_create
+inline bool countDataLines(const std::string &path, int64_t &nlines, std::string &err)
+{
+    Reader rd;
+    if (!rd.open(path, 1 << 22)) { err = rd.error; return false; }
+    SlabLines cut;
+    nlines = 0;
+    size_t consumed = 0;
+    do {
+        if (!rd.next(consumed)) { err = rd.error; return false; }
+        consumed = cut.take(rd.slab.data(), rd.have, rd.eof);
+        for (int64_t b : cut.begin) nlines += rd.slab[(size_t)b] != '#';
+        if (!rd.eof && consumed == 0 && rd.have == rd.slab.size()) { err = "a line longer than the slab"; return false; }
+    } while (!rd.eof || consumed < rd.have);
+    return true;
+}
+
+} // namespace vcf

@@ -134,3 +134,46 @@ def write_bed_and_tped(prefix, codes, chrs, pos, a1="A", a2="G", gpos=None, name
         for r in range(nrows):
             pair = ["%s %s" % (a1[r], a1[r]), "0 0", "%s %s" % (a1[r], a2[r]), "%s %s" % (a2[r], a2[r])]
             f.write("%s %s %.10g %d %s\n" % (chrs[r], names[r], gpos[r], pos[r], " ".join(pair[c] for c in codes[r])))
+
+
+def vcf_gt(code, order, sep="|"):
+    """the GT of one genotype: PLINK code (0 hom REF, 1 missing, 2 het, 3 hom ALT) and order bit (1: the first allele is ALT,
+    which tells `1|0` from `0|1`; it is what the code says for a homozygote and 0 for a missing genotype)"""
+    a, b = (("0", "0"), (".", "."), ("1", "0") if order else ("0", "1"), ("1", "1"))[int(code)]
+    return a + sep + b
+
+
+def write_vcf_and_tped(prefix, codes, order, chrs, pos, a1="A", a2="G", sep="|", extra_subfields=None, names=None, samples=None,
+                       meta=("##fileformat=VCFv4.2",), newline="\n", last_newline=True):
+    """One phased genotype matrix as prefix.vcf and as the twin prefix.tped / prefix.tfam that vcf2tped.pl writes from it.
+    codes: PLINK codes [nrows][nind] with A1 = REF, A2 = ALT; order: [nrows][nind], 1 where the genotype's first allele is
+    ALT (only a het's bit is free).  sep: "|" or "/", one string or an array [nrows][nind] of them.  extra_subfields: None, or
+    f(r, j) -> the text behind the GT of genotype (r, j) ("" = bare GT; otherwise FORMAT reads GT:X and the field GT:text).
+    The TPED line: CHROM ID 0 POS, then the two letters of every sample in the VCF's own allele order, tab-separated; the TFAM
+    line: 0 IID 0 0 0 0."""
+    codes = np.asarray(codes, dtype=np.uint8)
+    order = np.asarray(order, dtype=np.uint8)
+    nrows, nind = codes.shape
+    a1 = [a1] * nrows if isinstance(a1, str) else list(a1)
+    a2 = [a2] * nrows if isinstance(a2, str) else list(a2)
+    names = ["rs%d" % r for r in range(nrows)] if names is None else list(names)
+    samples = ["ind%d" % i for i in range(nind)] if samples is None else list(samples)
+    seps = np.full((nrows, nind), sep) if isinstance(sep, str) else np.asarray(sep)
+    lines = list(meta) + ["\t".join(["#CHROM", "POS", "ID", "REF", "ALT", "QUAL", "FILTER", "INFO", "FORMAT"] + samples)]
+    tped = []
+    for r in range(nrows):
+        fields, letters = [], []
+        for j in range(nind):
+            gt = vcf_gt(codes[r, j], order[r, j], str(seps[r, j]))
+            more = extra_subfields(r, j) if extra_subfields else ""
+            fields.append(gt + (":" + more if more else ""))
+            letters += [{"0": a1[r], "1": a2[r], ".": "0"}[gt[0]], {"0": a1[r], "1": a2[r], ".": "0"}[gt[2]]]
+        lines.append("\t".join([str(chrs[r]), "%d" % pos[r], names[r], a1[r], a2[r], ".", "PASS", ".",
+                                "GT:X" if extra_subfields else "GT"] + fields))
+        tped.append("\t".join([str(chrs[r]), names[r], "0", "%d" % pos[r]] + letters))
+    with open(prefix + ".vcf", "w", newline="") as f:
+        f.write(newline.join(lines) + (newline if last_newline else ""))
+    with open(prefix + ".tped", "w") as f:
+        f.write("".join(t + "\n" for t in tped))
+    with open(prefix + ".tfam", "w") as f:
+        f.write("".join("0\t%s\t0\t0\t0\t0\n" % s for s in samples))

@@ -63,7 +63,9 @@ extern "C" {
  *    garlic_feed_kde_multi_info (likewise); garlic_kde_part_set, garlic_kde_part_set_create, garlic_lod_kde_part_set,
  *    garlic_kde_part_set_destroy, garlic_kde_part_set_counts, garlic_kde_part_set_moment, garlic_kde_part_set_rank,
  *    garlic_kde_part_set_sums, garlic_kde_parts_multi, garlic_kde_parts_multi_info (likewise); garlic_bed_extract,
- *    garlic_bed_get_rows (likewise); garlic_feature_set_rows_bed, garlic_feature_set_get_rows (likewise) */
+ *    garlic_bed_get_rows (likewise); garlic_feature_set_rows_bed, garlic_feature_set_get_rows (likewise);
+ *    garlic_bed_set_order_rows, garlic_bed_get_order_rows, garlic_bed_set_rows_vcf, GARLIC_VCF_*, garlic_panel_set_phase_bed
+ *    (likewise) */
 #define GARLIC_HIP_ABI_VERSION 8
 
 #define GARLIC_OK 0
@@ -199,6 +201,44 @@ int garlic_bed_extract(garlic_bed *src, const int32_t *ind_idx, int32_t n_idx, g
 int garlic_bed_get_rows(garlic_bed *bed, int64_t row_begin, int64_t row_count, uint8_t *rows, int64_t row_bytes,
                         int32_t where);
 
+/* The order plane of an image: one bit per genotype, 1 = "the genotype's first allele is A2" (a VCF's `1|0`, `1|1`), 0 for a
+ * missing genotype; rows of (nind_total + 7) / 8 bytes back to back, bit i & 7 of byte i >> 3 of a row is individual i, the
+ * bits past the last individual are ignored (the VCF call writes them as zeros).  A .bed has no such thing: an image gets its
+ * plane, all zeros, with the first set_order_rows or set_rows_vcf call, and without one it behaves as before.  With a plane,
+ *   garlic_bed_census   counts A2 when the first non-missing genotype in file order has its order bit set, A1 otherwise --
+ *                       "the first non-missing allele on the line" of the TPED line on which every genotype reads in the
+ *                       VCF's own allele order; nalleles and total follow the counted allele as before;
+ *   garlic_bed_extract  is not built: GARLIC_ERR_INVALID.
+ * garlic_bed_set_order_rows / garlic_bed_get_order_rows take the arguments of garlic_bed_set_rows / garlic_bed_get_rows
+ * (row_bytes >= (nind_total + 7) / 8); get: GARLIC_ERR_STATE on an image without a plane. */
+int garlic_bed_set_order_rows(garlic_bed *bed, const uint8_t *rows, int64_t row_bytes, int64_t row_begin, int64_t row_count,
+                              int32_t where);
+int garlic_bed_get_order_rows(garlic_bed *bed, int64_t row_begin, int64_t row_count, uint8_t *rows, int64_t row_bytes,
+                              int32_t where);
+/* Image rows and order rows [row_begin, row_begin + row_count) parsed on the device from VCF text.  `text` is a slab of
+ * text_bytes bytes in host or device memory (no alignment asked for; the device reads the aligned 16-byte pieces that overlap
+ * the slab and nothing else).  line_begin (host, row_count + 1 ascending offsets) names the data lines: line_begin[r] is the
+ * first byte of the line that becomes row row_begin + r, and the line ends at its own '\n', at line_begin[r + 1] or at
+ * text_bytes, whichever comes first -- lines the caller leaves out simply lie between two kept ones.  Of a line, nine
+ * tab-separated columns are skipped; sample j is column 9 + j, of which the leading GT `a sep b` is read: a, b one of 0 1 . ,
+ * sep / or | , followed by : tab \r \n or the line's end.  0?0 -> 00, 1?1 -> 11, 0?1 and 1?0 -> 10, .?. -> 01 (PLINK's
+ * codes: A1 = REF, A2 = ALT), order bit = (a == '1'); pad bits of the row's last bytes zero.
+ * Everything else is an offence: row_status[r] = {code, sample column (0-based) of the line's first offence in file order},
+ * {0, 0} for a clean line (host array, may be NULL): GARLIC_VCF_BAD_BYTE, _HALF_MISSING (./1), _HAPLOID (one allele, no
+ * separator), _ALLELE_INDEX (an index >= 2), _FEW_COLUMNS (column = the number of sample columns found), _MANY_COLUMNS
+ * (column = nind_total).  The call then returns GARLIC_ERR_INVALID and garlic_hip_last_error names the lowest such row; the
+ * clean rows of the call are written and count as set, an offending row's bits are unspecified and it does not.
+ * Any line length, field width and nind_total work.  Device memory: the image keeps the staging buffer of its largest host
+ * slab (text_bytes + 16), the line offsets and the status words until garlic_bed_destroy, so that a file's slabs reuse them. */
+#define GARLIC_VCF_BAD_BYTE 1
+#define GARLIC_VCF_HALF_MISSING 2
+#define GARLIC_VCF_HAPLOID 3
+#define GARLIC_VCF_ALLELE_INDEX 4
+#define GARLIC_VCF_FEW_COLUMNS 5
+#define GARLIC_VCF_MANY_COLUMNS 6
+int garlic_bed_set_rows_vcf(garlic_bed *bed, const char *text, int64_t text_bytes, const int64_t *line_begin,
+                            int64_t row_begin, int64_t row_count, int32_t *row_status, int32_t where);
+
 /* GenoLikeData::data (src/garlic-data.h:91): per-genotype error probabilities, already converted
  * as readTGLSData does (src/garlic-data.cpp:1557-1576); same addressing as genotypes.  Any doubles.
  * A panel holds its likelihoods in one of three forms (garlic_panel_tgls_mode):
@@ -310,6 +350,14 @@ int garlic_panel_set_phase(garlic_panel *panel, const uint8_t *first_copy, int64
  * the panel as garlic_panel_set_phase over the same loci, at an eighth of the bytes. */
 int garlic_panel_set_phase_bits(garlic_panel *panel, const uint8_t *rows, int64_t row_bytes, int64_t locus_begin,
                                 int64_t locus_count, int32_t where);
+
+/* The same phase from an image with an order plane, device to device: HapData::firstCopy of the TPED line a row stands for,
+ *     firstCopy = non-missing && (order bit == (counted == A2)),   all ones on a row whose counted allele is none
+ * (alleleStr1 == oneAllele at src/garlic-data.cpp:129 when both are the missing character).  ind_offset (any integer in
+ * range) and dest_locus mean what they mean for garlic_panel_set_genotypes_bed; runs the census first when it has not been
+ * run.  Same effect on the panel as garlic_panel_set_phase_bits over the same loci.  GARLIC_ERR_STATE: the image has no
+ * plane. */
+int garlic_panel_set_phase_bed(garlic_panel *panel, garlic_bed *bed, int64_t ind_offset, const int64_t *dest_locus /* [nrows] */);
 
 /* LDData::LD (src/garlic-data.h:105) for winsize: ld[l * winsize + k], l global locus. */
 int garlic_panel_set_ld(garlic_panel *panel, int32_t winsize, const double *ld, int32_t where);
