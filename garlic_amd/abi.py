@@ -12,7 +12,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgarlic_hip.so")
 
-OK, ERR_INVALID, ERR_HIP, ERR_STATE, ERR_NOMEM = 0, 1, 2, 3, 4
+OK, ERR_INVALID, ERR_HIP, ERR_STATE, ERR_NOMEM, ERR_RANGE = 0, 1, 2, 3, 4, 5
 HOST, DEVICE = 0, 1
 # GARLIC_VCF_*: what garlic_bed_set_rows_vcf answers per row
 VCF_BAD_BYTE, VCF_HALF_MISSING, VCF_HAPLOID, VCF_ALLELE_INDEX, VCF_FEW_COLUMNS, VCF_MANY_COLUMNS = 1, 2, 3, 4, 5, 6
@@ -22,6 +22,9 @@ FEED_ORDER_REFERENCE, FEED_ORDER_SORTED = 0, 1   # garlic_panel_set_feed_order
 LD_PAIR_PLAIN, LD_PAIR_MFMA, LD_PAIR_LANE, LD_PAIR_TILED, LD_PAIR_FLAT = 0, 1, 2, 3, 4   # garlic_panel_ld_form_info
 LD_SUM_PLAIN, LD_SUM_FLAT, LD_SUM_COL, LD_SUM_TILED = 0, 1, 2, 3
 TGLS_DICTIONARY, TGLS_CONTINUOUS, TGLS_DICTIONARY16 = 1, 2, 3   # garlic_panel_tgls_mode
+# GARLIC_TGLS_*: what garlic_tgls_set_rows_text answers per row; TGLS_RAW: gl_type of garlic_tgls_get_rows without conversion
+TGLS_OK, TGLS_DEFERRED, TGLS_FEW_COLUMNS, TGLS_MANY_COLUMNS, TGLS_RAW = 0, 1, 2, 3, -1
+GL_GQ, GL_GL, GL_PL = 0, 1, 2
 MISSING = -9999.0
 
 # every symbol include/garlic_hip.h declares (tests check the library exports them all)
@@ -49,6 +52,9 @@ SYMBOLS = [
     "garlic_bed_create", "garlic_bed_set_rows", "garlic_bed_census", "garlic_bed_destroy", "garlic_panel_set_genotypes_bed",
     "garlic_bed_extract", "garlic_bed_get_rows",
     "garlic_bed_set_order_rows", "garlic_bed_get_order_rows", "garlic_bed_set_rows_vcf", "garlic_panel_set_phase_bed",
+    "garlic_tgls_create", "garlic_tgls_set_rows_text", "garlic_tgls_set_rows_values", "garlic_tgls_get_rows", "garlic_tgls_info",
+    "garlic_tgls_get_values", "garlic_tgls_count_values",
+    "garlic_tgls_destroy", "garlic_panel_set_gl_tgls",
     "garlic_feed_kde", "garlic_lod_kde", "garlic_feed_kde_info", "garlic_feed_kde_times",
     "garlic_gmm_fit", "garlic_gmm_fit_info",
     "garlic_kde_part_create", "garlic_lod_kde_part", "garlic_kde_part_destroy", "garlic_kde_part_count",
@@ -248,6 +254,15 @@ def lib():
     L.garlic_bed_get_order_rows.argtypes = [_vp, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_int32]
     L.garlic_bed_set_rows_vcf.argtypes = [_vp, _vp, C.c_int64, _i64p, C.c_int64, C.c_int64, _vp, C.c_int32]
     L.garlic_panel_set_phase_bed.argtypes = [_vp, _vp, C.c_int64, _i64p]
+    L.garlic_tgls_create.argtypes = [_vp, C.c_int64, C.c_int32, _i32p, C.c_int32, C.POINTER(_vp)]
+    L.garlic_tgls_set_rows_text.argtypes = [_vp, _vp, C.c_int64, _i64p, C.c_int64, C.c_int64, _vp, C.c_int32]
+    L.garlic_tgls_set_rows_values.argtypes = [_vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32]
+    L.garlic_tgls_get_rows.argtypes = [_vp, C.c_int32, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_int32]
+    L.garlic_tgls_info.argtypes = [_vp, _i32p, _i64p, _i64p]
+    L.garlic_tgls_get_values.argtypes = [_vp, C.c_int32, _f64p, C.c_int32]
+    L.garlic_tgls_count_values.argtypes = [_vp, C.c_int32, C.c_int64, C.c_int64, _i32p]
+    L.garlic_tgls_destroy.argtypes = [_vp]
+    L.garlic_panel_set_gl_tgls.argtypes = [_vp, _vp, C.c_int32, C.c_int64, _i64p]
     for name in SYMBOLS:
         f = getattr(L, name)
         if f.restype is C.c_int and name not in ("garlic_hip_abi_version",):
@@ -849,6 +864,89 @@ class Bed:
         self.destroy()
 
 
+class Tgls:
+    """The likelihoods of a --tgls file on a context's device (garlic_tgls): nrows rows of uint16 codes into one dictionary of
+    the raw values, parsed from the text on the device.  col_idx: the sample columns kept, in the order kept (None = all)."""
+
+    def __init__(self, ctx, nrows, ncols_total, col_idx=None):
+        self.ctx = ctx
+        self.nrows = int(nrows)
+        self.ncols_total = int(ncols_total)
+        idx = None if col_idx is None else np.ascontiguousarray(col_idx, dtype=np.int32)
+        self.n_kept = self.ncols_total if idx is None else int(idx.shape[0])
+        self.handle = _vp()
+        check(lib().garlic_tgls_create(ctx.handle, self.nrows, self.ncols_total, None if idx is None else _ptr(idx, _i32p),
+                                       0 if idx is None else idx.shape[0], C.byref(self.handle)))
+
+    def set_rows_text(self, text, line_begin, row_begin=0, text_bytes=None, where=HOST):
+        """Rows [row_begin, row_begin + len(line_begin) - 1) parsed from text on the device (garlic_tgls_set_rows_text).  text:
+        bytes / uint8 array (host), or a device address with text_bytes and where=DEVICE.  Returns (status int32 [rows][2] =
+        code, sample column; error or None): a column-count offence fills the status and comes back as the GarlicError
+        instead of being raised, so that a caller sees both.  A deferred row is no error."""
+        lb = np.ascontiguousarray(line_begin, dtype=np.int64)
+        assert lb.ndim == 1 and lb.shape[0] >= 2
+        if where == HOST:
+            buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else np.asarray(text)
+            assert buf.dtype == np.uint8 and buf.ndim == 1 and (buf.shape[0] <= 1 or buf.strides[0] == 1)
+            ptr, text_bytes = buf.ctypes.data, buf.shape[0] if text_bytes is None else text_bytes
+        else:
+            ptr = int(text)
+        status = np.zeros((lb.shape[0] - 1, 2), dtype=np.int32)
+        rc = lib().garlic_tgls_set_rows_text(self.handle, _vp(ptr), int(text_bytes), _ptr(lb, _i64p), row_begin, lb.shape[0] - 1,
+                                             _vp(status.ctypes.data), where)
+        err = None
+        if rc != OK:
+            err = GarlicError(rc, lib().garlic_hip_last_error().decode())
+            if rc != ERR_INVALID or not (status[:, 0] >= TGLS_FEW_COLUMNS).any():
+                raise err
+        return status, err
+
+    def set_rows_values(self, raw, row_begin=0):
+        """raw: float64 [row_count][n_kept] (host): the rows' raw values as the host parses them."""
+        raw = np.ascontiguousarray(raw, dtype=np.float64)
+        assert raw.ndim == 2 and raw.shape[1] == self.n_kept
+        check(lib().garlic_tgls_set_rows_values(self.handle, _vp(raw.ctypes.data), raw.shape[1], row_begin, raw.shape[0], HOST))
+
+    def get_rows(self, gl_type=TGLS_RAW, row_begin=0, row_count=None):
+        """float64 [row_count][n_kept]: the rows' values, raw (TGLS_RAW) or converted (GL_GQ / GL_GL / GL_PL)."""
+        row_count = self.nrows - row_begin if row_count is None else row_count
+        out = np.empty((max(row_count, 0), self.n_kept), dtype=np.float64)
+        check(lib().garlic_tgls_get_rows(self.handle, gl_type, row_begin, row_count, _vp(out.ctypes.data), self.n_kept, HOST))
+        return out
+
+    def info(self):
+        """(distinct raw values, rows set, rows deferred)"""
+        n, rs, rd = C.c_int32(0), C.c_int64(0), C.c_int64(0)
+        check(lib().garlic_tgls_info(self.handle, C.byref(n), C.byref(rs), C.byref(rd)))
+        return n.value, rs.value, rd.value
+
+    def count_values(self, gl_type=TGLS_RAW, row_begin=0, row_count=None):
+        """the number of distinct values, raw or converted, among the rows of the range"""
+        n = C.c_int32(0)
+        row_count = self.nrows - row_begin if row_count is None else row_count
+        check(lib().garlic_tgls_count_values(self.handle, gl_type, row_begin, row_count, C.byref(n)))
+        return n.value
+
+    def values(self, gl_type=TGLS_RAW):
+        """float64 [n_raw_values]: the dictionary in the order its codes were issued, raw or converted"""
+        out = np.empty(self.info()[0], dtype=np.float64)
+        check(lib().garlic_tgls_get_values(self.handle, gl_type, _ptr(out, _f64p), out.shape[0]))
+        return out
+
+    def destroy(self):
+        if self.handle:
+            lib().garlic_tgls_destroy(self.handle)
+            self.handle = _vp()
+
+    close = destroy
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.destroy()
+
+
 class Panel:
     """Device-resident genotype panel (garlic_panel) for the individuals one context owns."""
 
@@ -929,6 +1027,13 @@ class Panel:
         dest = np.ascontiguousarray(dest_locus, dtype=np.int64)
         assert dest.shape == (bed.nrows,)
         check(lib().garlic_panel_set_phase_bed(self.handle, bed.handle, ind_offset, _ptr(dest, _i64p)))
+
+    def set_gl_tgls(self, tgls, gl_type, dest_locus, ind_offset=0):
+        """The likelihoods from a Tgls object, device to device (garlic_panel_set_gl_tgls): row r of the object goes to locus
+        dest_locus[r] (-1 = dropped, the others strictly ascending); the panel's individual i is kept column ind_offset + i."""
+        dest = np.ascontiguousarray(dest_locus, dtype=np.int64)
+        assert dest.shape == (tgls.nrows,)
+        check(lib().garlic_panel_set_gl_tgls(self.handle, tgls.handle, gl_type, ind_offset, _ptr(dest, _i64p)))
 
     def set_gl_codes(self, codes, values, locus_begin=0):
         """codes: uint8 [nloci_chunk][nind] indexing values (float64, <= 256 error probabilities)"""

@@ -31,6 +31,7 @@
 #include "../host/chain_order.hpp"
 #include "bed_kernels.hpp"
 #include "vcf_kernels.hpp"
+#include "tgls_kernels.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -3440,6 +3441,410 @@ int garlic_panel_set_gl_codes16(garlic_panel *p, const uint16_t *codes, int64_t 
         return GARLIC_OK;
     });
     return rc ? rc : end_gl_upload(p, locus_begin, locus_count);
+}
+
+// ---- --tgls text (tgls_kernels.hpp): rows of 16-bit codes into a dictionary of the RAW values, and the door into a panel
+// leaves its scope with the stream idle: declared behind the host lists and device buffers whose copies and readers may be pending
+struct StreamDrain {
+    hipStream_t s;
+    ~StreamDrain() { (void)hipStreamSynchronize(s); }
+};
+
+struct garlic_tgls {
+    garlic_ctx *ctx = nullptr;
+    int64_t nrows = 0;
+    int32_t ncols = 0, n_kept = 0;
+    bool dead = false;                                      // a 65,537th raw value arrived: the file needs the host reader
+    DevBuf<uint16_t> d_codes;                               // [nrows][n_kept]
+    DevBuf<int32_t> d_col_dest, d_k_src;                    // column -> staged column or -1; kept column -> staged column
+    std::vector<uint64_t> raw_bits;                         // the dictionary: code -> bit pattern, in the order the codes were issued
+    std::vector<std::pair<uint64_t, uint16_t>> sorted;      // the same, sorted by bit pattern
+    DevBuf<uint64_t> d_bits;                                // `sorted` on the device, TGLS_DICT_MAX entries of room
+    DevBuf<uint16_t> d_code;
+    DevBuf<unsigned long long> d_set;                       // the unknown values of an encode round
+    DevBuf<int32_t> d_flags;                                // 3 words (tgls_encode_kernel)
+    std::vector<uint64_t> row_set, row_deferred;            // one bit per row
+    int64_t n_set = 0, n_deferred = 0;
+    DevBuf<uint8_t> text;                                   // staging, kept until destroy: a host slab,
+    DevBuf<int64_t> lines;                                  // its line offsets,
+    DevBuf<int32_t> status;                                 // the status pairs,
+    DevBuf<double> raw;                                     // the parsed doubles [row_count][n_kept] (and the rows of set_rows_values),
+    DevBuf<double> d_table, d_out;                          // and what get_rows decodes with and into
+};
+
+int garlic_tgls_create(garlic_ctx *ctx, int64_t nrows, int32_t ncols_total, const int32_t *col_idx, int32_t n_idx, garlic_tgls **out)
+{
+    if (!out) return fail(GARLIC_ERR_INVALID, "tgls out pointer is NULL");
+    *out = nullptr;
+    if (!ctx) return fail(GARLIC_ERR_INVALID, "ctx is NULL");
+    if (nrows < 1 || nrows > 0x7FFFFFFF || ncols_total < 1 || ncols_total >= (1 << 28))
+        return fail(GARLIC_ERR_INVALID, "need 1 <= nrows < 2^31 and 1 <= ncols_total < 2^28");
+    if (col_idx && (n_idx < 1 || n_idx >= (1 << 28))) return fail(GARLIC_ERR_INVALID, "need 1 <= n_idx < 2^28, got %d", n_idx);
+    const int32_t n_kept = col_idx ? n_idx : ncols_total;
+    for (int32_t k = 0; col_idx && k < n_idx; k++)
+        if (col_idx[k] < 0 || col_idx[k] >= ncols_total)
+            return fail(GARLIC_ERR_INVALID, "col_idx[%d] = %d outside the file's %d columns", k, col_idx[k], ncols_total);
+    int rc;
+    if ((rc = set_device(ctx))) return rc;
+    std::unique_ptr<garlic_tgls> t(new garlic_tgls);
+    t->ctx = ctx;
+    t->nrows = nrows;
+    t->ncols = ncols_total;
+    t->n_kept = n_kept;
+    // a column is staged where its first kept position is; a position that names it again reads it from there
+    std::vector<int32_t> dest((size_t)ncols_total, -1), src((size_t)n_kept);
+    for (int32_t k = 0; k < n_kept; k++) {
+        const int32_t c = col_idx ? col_idx[k] : k;
+        if (dest[(size_t)c] < 0) dest[(size_t)c] = k;
+        src[(size_t)k] = dest[(size_t)c];
+    }
+    hipStream_t s = ctx->stream;
+    if ((rc = t->d_codes.reserve((size_t)(nrows * n_kept))) || (rc = t->d_col_dest.put(dest, s)) || (rc = t->d_k_src.put(src, s)) ||
+        (rc = t->d_bits.reserve(TGLS_DICT_MAX)) || (rc = t->d_code.reserve(TGLS_DICT_MAX)) || (rc = t->d_set.reserve(TGLS_SET_SLOTS)) ||
+        (rc = t->d_flags.reserve(3)))
+        return rc;
+    HIP_TRY(hipStreamSynchronize(s));                   // dest / src may go
+    t->row_set.assign((size_t)((nrows + 63) / 64), 0);
+    t->row_deferred.assign((size_t)((nrows + 63) / 64), 0);
+    *out = t.release();
+    return GARLIC_OK;
+}
+
+int garlic_tgls_destroy(garlic_tgls *t)
+{
+    if (!t) return GARLIC_OK;
+    (void)hipSetDevice(t->ctx->device);
+    (void)hipStreamSynchronize(t->ctx->stream);
+    delete t;
+    return GARLIC_OK;
+}
+
+static int tgls_check_rows(const garlic_tgls *t, int64_t row_begin, int64_t row_count, int32_t where)
+{
+    if (where != GARLIC_HOST && where != GARLIC_DEVICE) return fail(GARLIC_ERR_INVALID, "where must be GARLIC_HOST or GARLIC_DEVICE");
+    if (row_begin < 0 || row_count < 1 || row_begin + row_count > t->nrows)
+        return fail(GARLIC_ERR_INVALID, "row range [%lld,+%lld) outside the object's %lld rows", (long long)row_begin, (long long)row_count,
+                    (long long)t->nrows);
+    if (t->dead)
+        return fail(GARLIC_ERR_STATE, "the object met more than %d distinct raw values and is unusable: the file needs the host reader", TGLS_DICT_MAX);
+    return GARLIC_OK;
+}
+
+static void tgls_mark(garlic_tgls *t, int64_t row, bool set)
+{
+    uint64_t &ws = t->row_set[(size_t)(row >> 6)], &wd = t->row_deferred[(size_t)(row >> 6)];
+    const uint64_t bit = 1ull << (row & 63);
+    if (set) {
+        if (!(ws & bit)) { ws |= bit; t->n_set++; }
+        if (wd & bit) { wd &= ~bit; t->n_deferred--; }
+    } else {                                                // deferred: not set until set_rows_values brings it
+        if (ws & bit) { ws &= ~bit; t->n_set--; }
+        if (!(wd & bit)) { wd |= bit; t->n_deferred++; }
+    }
+}
+
+// Staged rows -> codes, the dictionary growing by the SORTED set of the values it does not hold, until it holds all (two
+// rounds at most).  d_status: the rows' status pairs on the device, or NULL when every row is to be coded.
+static int tgls_encode_rows(garlic_tgls *t, const double *d_raw, int64_t ld, const int32_t *d_status, const int32_t *d_k_src,
+                            int64_t row_begin, int64_t row_count)
+{
+    hipStream_t s = t->ctx->stream;
+    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((row_count * t->n_kept + 255) / 256, 2048));
+    for (int round = 0;; round++) {
+        HIP_TRY(hipMemsetAsync(t->d_set.p, 0xFF, sizeof(unsigned long long) * TGLS_SET_SLOTS, s));
+        HIP_TRY(hipMemsetAsync(t->d_flags.p, 0, 3 * sizeof(int32_t), s));
+        hipLaunchKernelGGL(tgls_encode_kernel, dim3(grid), dim3(256), 0, s, d_raw, ld, d_status, row_count, t->n_kept, d_k_src,
+                           t->d_bits.p, t->d_code.p, (int)t->sorted.size(), t->d_codes.p + row_begin * t->n_kept, t->d_set.p,
+                           (int32_t)(TGLS_DICT_MAX - (int)t->sorted.size()), t->d_flags.p);
+        HIP_TRY(hipGetLastError());
+        int32_t flags[3] = {0, 0, 0};
+        HIP_TRY(hipMemcpyAsync(flags, t->d_flags.p, sizeof flags, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (!flags[0] && !flags[1] && !flags[2]) return GARLIC_OK;
+        if (round >= 2) return fail(GARLIC_ERR_HIP, "tgls encode: values still unknown after the dictionary was extended");
+        if ((int64_t)t->sorted.size() + flags[0] + (flags[1] ? 1 : 0) > TGLS_DICT_MAX) {
+            t->dead = true;
+            return fail(GARLIC_ERR_RANGE, "the likelihood file holds more than %d distinct raw values: it needs the host reader "
+                        "(the object is unusable from here on)", TGLS_DICT_MAX);
+        }
+        if (flags[2]) return fail(GARLIC_ERR_HIP, "tgls encode: a value found no slot in a set that is at most half full");
+        std::vector<uint64_t> set(TGLS_SET_SLOTS), fresh;
+        HIP_TRY(hipMemcpy(set.data(), t->d_set.p, sizeof(uint64_t) * set.size(), hipMemcpyDeviceToHost));
+        for (uint64_t b : set)
+            if (b != TGLS_SET_EMPTY) fresh.push_back(b);
+        if (flags[1]) fresh.push_back(TGLS_SET_EMPTY);
+        std::sort(fresh.begin(), fresh.end());
+        for (uint64_t b : fresh) {
+            t->sorted.emplace_back(b, (uint16_t)t->raw_bits.size());
+            t->raw_bits.push_back(b);
+        }
+        std::sort(t->sorted.begin(), t->sorted.end());
+        std::vector<uint64_t> hb(t->sorted.size());
+        std::vector<uint16_t> hc(t->sorted.size());
+        for (size_t k = 0; k < hb.size(); k++) { hb[k] = t->sorted[k].first; hc[k] = t->sorted[k].second; }
+        HIP_TRY(hipMemcpy(t->d_bits.p, hb.data(), sizeof(uint64_t) * hb.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(t->d_code.p, hc.data(), sizeof(uint16_t) * hc.size(), hipMemcpyHostToDevice));
+    }
+}
+
+static const char *tgls_offence_name(int code)
+{
+    return code == TGLS_FEW_COLUMNS ? "too few sample columns" : code == TGLS_MANY_COLUMNS ? "too many sample columns" : "a deferred token";
+}
+
+int garlic_tgls_set_rows_text(garlic_tgls *t, const char *text, int64_t text_bytes, const int64_t *line_begin, int64_t row_begin,
+                              int64_t row_count, int32_t *row_status, int32_t where)
+{
+    if (!t || !text || !line_begin) return fail(GARLIC_ERR_INVALID, "tgls, text and line_begin are required");
+    if (text_bytes < 1) return fail(GARLIC_ERR_INVALID, "text_bytes %lld: the slab is empty", (long long)text_bytes);
+    int rc;
+    if ((rc = tgls_check_rows(t, row_begin, row_count, where))) return rc;
+    for (int64_t r = 0; r <= row_count; r++)
+        if (line_begin[r] < 0 || line_begin[r] > text_bytes || (r && line_begin[r] < line_begin[r - 1]))
+            return fail(GARLIC_ERR_INVALID, "line_begin[%lld] = %lld: the offsets must ascend inside the slab of %lld bytes", (long long)r,
+                        (long long)line_begin[r], (long long)text_bytes);
+    if ((rc = set_device(t->ctx))) return rc;
+    hipStream_t s = t->ctx->stream;
+    const uint8_t *d_text = reinterpret_cast<const uint8_t *>(text);
+    if (where == GARLIC_HOST) {
+        if ((rc = t->text.reserve((size_t)text_bytes + 16))) return rc;          // (its last piece lies inside the buffer)
+        HIP_TRY(hipMemcpyAsync(t->text.p, text, (size_t)text_bytes, hipMemcpyHostToDevice, s));
+        d_text = t->text.p;
+    }
+    if ((rc = t->lines.reserve((size_t)row_count + 1)) || (rc = t->status.reserve((size_t)(2 * row_count))) ||
+        (rc = t->raw.reserve((size_t)(row_count * t->n_kept))))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(t->lines.p, line_begin, sizeof(int64_t) * (size_t)(row_count + 1), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(tgls_parse_kernel, dim3((unsigned)row_count), dim3(256), 0, s, d_text, text_bytes, t->lines.p, t->ncols,
+                       t->d_col_dest.p, t->raw.p, (int64_t)t->n_kept, t->status.p);
+    HIP_TRY(hipGetLastError());
+    std::vector<int32_t> status((size_t)(2 * row_count));
+    HIP_TRY(hipMemcpyAsync(status.data(), t->status.p, sizeof(int32_t) * status.size(), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (row_status) memcpy(row_status, status.data(), sizeof(int32_t) * status.size());
+    if ((rc = tgls_encode_rows(t, t->raw.p, t->n_kept, t->status.p, t->d_k_src.p, row_begin, row_count))) return rc;
+    int64_t bad = -1;
+    for (int64_t r = 0; r < row_count; r++) {
+        const int code = status[(size_t)(2 * r)];
+        if (code == TGLS_OK) tgls_mark(t, row_begin + r, true);
+        else if (code == TGLS_DEFERRED) tgls_mark(t, row_begin + r, false);
+        else if (bad < 0) bad = r;                          // its codes are unspecified: the row keeps the state it had
+    }
+    if (bad >= 0)
+        return fail(GARLIC_ERR_INVALID, "TGLS row %lld (line %lld of the call): %s (%d)", (long long)(row_begin + bad), (long long)bad,
+                    tgls_offence_name(status[(size_t)(2 * bad)]), status[(size_t)(2 * bad + 1)]);
+    return GARLIC_OK;
+}
+
+int garlic_tgls_set_rows_values(garlic_tgls *t, const double *raw, int64_t ld, int64_t row_begin, int64_t row_count, int32_t where)
+{
+    if (!t || !raw) return fail(GARLIC_ERR_INVALID, "tgls and raw are required");
+    int rc;
+    if ((rc = tgls_check_rows(t, row_begin, row_count, where))) return rc;
+    if (ld < t->n_kept) return fail(GARLIC_ERR_INVALID, "ld %lld < the object's %d kept columns", (long long)ld, t->n_kept);
+    if ((rc = set_device(t->ctx))) return rc;
+    hipStream_t s = t->ctx->stream;
+    int64_t at_row = row_begin;
+    rc = for_each_upload_slab(s, "tgls_set_rows_values", raw, 8 * ld, row_count, where, t->raw, [&](const void *rows, int64_t at, int64_t n) {
+        at_row = row_begin + at;
+        const int enc = tgls_encode_rows(t, (const double *)rows, ld, nullptr, nullptr, at_row, n);
+        return enc ? enc : SLAB_DRAINED;
+    });
+    if (rc) return rc;
+    for (int64_t r = 0; r < row_count; r++) tgls_mark(t, row_begin + r, true);
+    return GARLIC_OK;
+}
+
+// garlic-data.cpp:1557-1576, operation for operation, with the host libm
+static double tgls_convert(double gl, int32_t gl_type)
+{
+    if (gl_type == GARLIC_GL_GQ) { gl /= (-10.0); gl = (gl > -10) ? gl : -10; gl = pow(10, gl); }
+    else if (gl_type == GARLIC_GL_GL) { gl = (gl > -10) ? gl : -10; gl = 1 - pow(10, gl); }
+    else { gl /= (-10.0); gl = (gl > -10) ? gl : -10; gl = 1 - pow(10, gl); }
+    if (gl <= 0) gl = 0.0000000000000001;
+    if (gl > 1) gl = 1;
+    return gl;
+}
+
+static bool tgls_gl_type_ok(int32_t gl_type, bool raw_too)
+{
+    return gl_type == GARLIC_GL_GQ || gl_type == GARLIC_GL_GL || gl_type == GARLIC_GL_PL || (raw_too && gl_type == GARLIC_TGLS_RAW);
+}
+
+// the object's table, code -> value: raw (GARLIC_TGLS_RAW) or converted
+static std::vector<double> tgls_table(const garlic_tgls *t, int32_t gl_type)
+{
+    std::vector<double> table(t->raw_bits.size());
+    for (size_t c = 0; c < table.size(); c++) {
+        double v;
+        memcpy(&v, &t->raw_bits[c], sizeof v);
+        table[c] = gl_type == GARLIC_TGLS_RAW ? v : tgls_convert(v, gl_type);
+    }
+    return table;
+}
+
+int garlic_tgls_get_rows(garlic_tgls *t, int32_t gl_type, int64_t row_begin, int64_t row_count, double *out, int64_t ld, int32_t where)
+{
+    if (!t || !out) return fail(GARLIC_ERR_INVALID, "tgls and out are required");
+    if (!tgls_gl_type_ok(gl_type, true)) return fail(GARLIC_ERR_INVALID, "gl_type must be GARLIC_TGLS_RAW or GARLIC_GL_GQ / _GL / _PL (got %d)", gl_type);
+    int rc;
+    if ((rc = tgls_check_rows(t, row_begin, row_count, where))) return rc;
+    if (ld < t->n_kept) return fail(GARLIC_ERR_INVALID, "ld %lld < the object's %d kept columns", (long long)ld, t->n_kept);
+    for (int64_t r = row_begin; r < row_begin + row_count; r++)
+        if (!((t->row_set[(size_t)(r >> 6)] >> (r & 63)) & 1))
+            return fail(GARLIC_ERR_STATE, "tgls row %lld is not set%s", (long long)r,
+                        ((t->row_deferred[(size_t)(r >> 6)] >> (r & 63)) & 1) ? " (deferred: it waits for garlic_tgls_set_rows_values)" : "");
+    if ((rc = set_device(t->ctx))) return rc;
+    hipStream_t s = t->ctx->stream;
+    const std::vector<double> table = tgls_table(t, gl_type);
+    StreamDrain drain{s};                                   // (the table's copy may be pending at any return from here on)
+    if ((rc = t->d_table.put(table, s))) return rc;
+    // host rows go through a staging buffer a slab at a time, device rows are written where they are
+    const int64_t slab = where == GARLIC_HOST ? std::max<int64_t>(16, ((int64_t)64 << 20) / (8 * (int64_t)t->n_kept)) : row_count;
+    for (int64_t at = 0; at < row_count; at += slab) {
+        const int64_t n = std::min(slab, row_count - at);
+        double *dst = out + at * ld;
+        int64_t dst_ld = ld;
+        if (where == GARLIC_HOST) {
+            if ((rc = t->d_out.reserve((size_t)(n * t->n_kept)))) return rc;
+            dst = t->d_out.p;
+            dst_ld = t->n_kept;
+        }
+        const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n * t->n_kept + 255) / 256, 2048));
+        hipLaunchKernelGGL(tgls_decode_kernel, dim3(grid), dim3(256), 0, s, t->d_codes.p + (row_begin + at) * t->n_kept, n, t->n_kept,
+                           t->d_table.p, dst, dst_ld);
+        HIP_TRY(hipGetLastError());
+        if (where == GARLIC_HOST)
+            HIP_TRY(hipMemcpy2DAsync(out + at * ld, (size_t)(8 * ld), dst, (size_t)(8 * dst_ld), (size_t)(8 * t->n_kept), (size_t)n,
+                                     hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    return GARLIC_OK;
+}
+
+int garlic_tgls_info(garlic_tgls *t, int32_t *n_raw_values, int64_t *rows_set, int64_t *rows_deferred)
+{
+    if (!t) return fail(GARLIC_ERR_INVALID, "tgls is NULL");
+    if (n_raw_values) *n_raw_values = (int32_t)t->raw_bits.size();
+    if (rows_set) *rows_set = t->n_set;
+    if (rows_deferred) *rows_deferred = t->n_deferred;
+    return GARLIC_OK;
+}
+
+int garlic_tgls_count_values(garlic_tgls *t, int32_t gl_type, int64_t row_begin, int64_t row_count, int32_t *n_values)
+{
+    if (!t || !n_values) return fail(GARLIC_ERR_INVALID, "tgls and n_values are required");
+    if (!tgls_gl_type_ok(gl_type, true)) return fail(GARLIC_ERR_INVALID, "gl_type must be GARLIC_TGLS_RAW or GARLIC_GL_GQ / _GL / _PL (got %d)", gl_type);
+    int rc;
+    if ((rc = tgls_check_rows(t, row_begin, row_count, GARLIC_HOST))) return rc;
+    for (int64_t r = row_begin; r < row_begin + row_count; r++)
+        if (!((t->row_set[(size_t)(r >> 6)] >> (r & 63)) & 1)) return fail(GARLIC_ERR_STATE, "tgls row %lld is not set", (long long)r);
+    if ((rc = set_device(t->ctx))) return rc;
+    hipStream_t s = t->ctx->stream;
+    DevBuf<uint8_t> d_used;
+    if ((rc = d_used.reserve(TGLS_DICT_MAX))) return rc;
+    StreamDrain drain{s};
+    HIP_TRY(hipMemsetAsync(d_used.p, 0, TGLS_DICT_MAX, s));
+    const int64_t n = row_count * t->n_kept;
+    hipLaunchKernelGGL(tgls_mark_kernel, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 2048))), dim3(256), 0, s,
+                       t->d_codes.p + row_begin * t->n_kept, n, d_used.p);
+    HIP_TRY(hipGetLastError());
+    std::vector<uint8_t> used(TGLS_DICT_MAX);
+    HIP_TRY(hipMemcpyAsync(used.data(), d_used.p, used.size(), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const std::vector<double> table = tgls_table(t, gl_type);
+    std::unordered_map<uint64_t, int> seen;
+    for (size_t c = 0; c < table.size(); c++)
+        if (used[c]) seen.emplace(value_bits(table[c]), 0);
+    *n_values = (int32_t)seen.size();
+    return GARLIC_OK;
+}
+
+int garlic_tgls_get_values(garlic_tgls *t, int32_t gl_type, double *values, int32_t n)
+{
+    if (!t || !values) return fail(GARLIC_ERR_INVALID, "tgls and values are required");
+    if (!tgls_gl_type_ok(gl_type, true)) return fail(GARLIC_ERR_INVALID, "gl_type must be GARLIC_TGLS_RAW or GARLIC_GL_GQ / _GL / _PL (got %d)", gl_type);
+    if (n < 0 || (size_t)n > t->raw_bits.size()) return fail(GARLIC_ERR_INVALID, "n = %d outside the dictionary's %zu values", n, t->raw_bits.size());
+    const std::vector<double> table = tgls_table(t, gl_type);
+    std::copy(table.begin(), table.begin() + n, values);
+    return GARLIC_OK;
+}
+
+int garlic_panel_set_gl_tgls(garlic_panel *p, garlic_tgls *t, int32_t gl_type, int64_t ind_offset, const int64_t *dest_locus)
+{
+    if (!p || !t || !dest_locus) return fail(GARLIC_ERR_INVALID, "panel, tgls and dest_locus are required");
+    if (!tgls_gl_type_ok(gl_type, false)) return fail(GARLIC_ERR_INVALID, "gl_type must be GARLIC_GL_GQ / _GL / _PL (got %d)", gl_type);
+    if (t->ctx->device != p->ctx->device)
+        return fail(GARLIC_ERR_INVALID, "the tgls object is on device %d, the panel on device %d", t->ctx->device, p->ctx->device);
+    if (t->dead)
+        return fail(GARLIC_ERR_STATE, "the object met more than %d distinct raw values and is unusable: the file needs the host reader", TGLS_DICT_MAX);
+    if (t->n_set != t->nrows)
+        return fail(GARLIC_ERR_STATE, "set_gl_tgls needs every row of the object: %lld of %lld set, %lld deferred", (long long)t->n_set,
+                    (long long)t->nrows, (long long)t->n_deferred);
+    if (ind_offset < 0 || ind_offset + p->nind > t->n_kept)
+        return fail(GARLIC_ERR_INVALID, "individuals [%lld,+%d) outside the object's %d kept columns", (long long)ind_offset, p->nind, t->n_kept);
+    // the kept rows, and the runs of consecutive destinations they form
+    std::vector<int64_t> src_row;
+    struct Run { int64_t first_kept, locus, count; };
+    std::vector<Run> runs;
+    int64_t prev = -1;
+    for (int64_t r = 0; r < t->nrows; r++) {
+        const int64_t l = dest_locus[r];
+        if (l == -1) continue;
+        if (l < 0 || l >= p->nloci) return fail(GARLIC_ERR_INVALID, "dest_locus[%lld] = %lld outside the panel's %lld loci", (long long)r, (long long)l, (long long)p->nloci);
+        if (!src_row.empty() && l <= prev)
+            return fail(GARLIC_ERR_INVALID, "dest_locus[%lld] = %lld: the destinations of the kept rows must be strictly ascending", (long long)r, (long long)l);
+        if (!runs.empty() && l == prev + 1) runs.back().count++;
+        else runs.push_back(Run{(int64_t)src_row.size(), l, 1});
+        src_row.push_back(r);
+        prev = l;
+    }
+    if (src_row.empty()) return fail(GARLIC_ERR_INVALID, "dest_locus keeps no row");
+    // the dictionary converted on the host; the distinct converted values, first code first, are the table the panel gets
+    const std::vector<double> conv = tgls_table(t, gl_type);
+    std::vector<double> values;
+    std::vector<uint16_t> map(conv.size());
+    {
+        std::unordered_map<uint64_t, int> seen;
+        seen.reserve(2 * conv.size());
+        for (size_t c = 0; c < conv.size(); c++) {
+            auto ins = seen.emplace(value_bits(conv[c]), (int)values.size());
+            if (ins.second) values.push_back(conv[c]);
+            map[c] = (uint16_t)ins.first->second;
+        }
+    }
+    int rc;
+    if ((rc = set_device(p->ctx))) return rc;
+    hipStream_t s = p->ctx->stream;
+    const bool narrow = !p->gl_wide && !p->gl_cont && values.size() <= (size_t)GL_DICT_MAX;      // the one-byte door, as the host reader's codes take it
+    const size_t code_bytes = narrow ? 1 : 2;
+    DevBuf<int64_t> d_src;
+    DevBuf<uint16_t> d_map;
+    DevBuf<uint8_t> d_out;
+    StreamDrain drain{s};                                   // (the lists' copies and the kernels that read the buffers: idle before they go)
+    const int64_t slab = std::max<int64_t>(16, ((int64_t)64 << 20) / ((int64_t)code_bytes * p->nind));
+    if ((rc = d_src.put(src_row, s)) || (rc = d_map.put(map, s)) ||
+        (rc = d_out.reserve((size_t)(std::min<int64_t>(slab, (int64_t)src_row.size()) * p->nind) * code_bytes)))
+        return rc;
+    for (const Run &run : runs)
+        for (int64_t at = 0; at < run.count; at += slab) {
+            const int64_t n = std::min(slab, run.count - at);
+            const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n * p->nind + 255) / 256, 2048));
+            const int64_t *src = d_src.p + run.first_kept + at;
+            if (narrow)
+                hipLaunchKernelGGL(tgls_compact_kernel<uint8_t>, dim3(grid), dim3(256), 0, s, t->d_codes.p, t->n_kept, src, n, ind_offset,
+                                   p->nind, d_map.p, d_out.p);
+            else
+                hipLaunchKernelGGL(tgls_compact_kernel<uint16_t>, dim3(grid), dim3(256), 0, s, t->d_codes.p, t->n_kept, src, n, ind_offset,
+                                   p->nind, d_map.p, reinterpret_cast<uint16_t *>(d_out.p));
+            HIP_TRY(hipGetLastError());
+            rc = narrow ? garlic_panel_set_gl_codes(p, d_out.p, p->nind, run.locus + at, n, values.data(), (int32_t)values.size(), GARLIC_DEVICE)
+                        : garlic_panel_set_gl_codes16(p, reinterpret_cast<const uint16_t *>(d_out.p), p->nind, run.locus + at, n, values.data(),
+                                                      (int32_t)values.size(), GARLIC_DEVICE);
+            if (rc) return rc;                              // (the doors synchronise behind their slab: d_out is free again)
+        }
+    HIP_TRY(hipStreamSynchronize(s));
+    return GARLIC_OK;
 }
 
 // the phase planes of a panel that gets its first phase, all zero

@@ -227,6 +227,8 @@ FreqData *initFreqData(int nloci)
 void releaseFreqData(FreqData *d) { if (d) { delete[] d->freq; delete d; } }
 void releaseFreqData(std::vector<FreqData *> *v) { for (auto d : *v) releaseFreqData(d); delete v; }
 
+static void closeTglsFile(TglsFile *f);
+
 GenoLikeData *initGLData(unsigned int nind, unsigned int nloci)
 {
     if (nind < 1 || nloci < 1) fail("Can not allocate GenoLikeData object: counts must be positive.");
@@ -238,6 +240,8 @@ GenoLikeData *initGLData(unsigned int nind, unsigned int nloci)
     d->values = nullptr;
     d->nvalues = 0;
     d->codes16 = nullptr;
+    d->tgls = nullptr;
+    d->tglsRow = nullptr;
     for (unsigned l = 0; l < nloci; l++) {
         d->data[l] = new double[nind];
         std::fill(d->data[l], d->data[l] + nind, (double)MISSING);
@@ -256,6 +260,8 @@ void releaseGLData(GenoLikeData *d)
     delete[] d->codes;
     delete[] d->codes16;
     delete[] d->values;
+    delete[] d->tglsRow;
+    if (d->tgls && --d->tgls->refs == 0) closeTglsFile(d->tgls);
     delete d;
 }
 void releaseGLData(std::vector<GenoLikeData *> *v) { for (auto d : *v) releaseGLData(d); delete v; }
@@ -1018,6 +1024,134 @@ std::vector<GenoLikeData *> *readTGLSData(const std::string &filename, int /*exp
     return out;
 }
 
+// ---- the same file through the device (garlic_tgls): slabs of text up, rows of codes there, nothing per genotype here
+static void closeTglsFile(TglsFile *f)
+{
+    if (!f) return;
+    for (auto &o : f->objects) {
+        if (o.tgls) garlic_tgls_destroy((garlic_tgls *)o.tgls);
+        if (o.ctx) garlic_ctx_destroy((garlic_ctx *)o.ctx);
+    }
+    delete f;
+}
+
+// The file's first f->nrows lines into obj, whose kept columns are objCols: 64 MB slabs cut at line ends, one
+// garlic_tgls_set_rows_text per slab; a row the device defers is parsed here as readTGLSData parses it and handed over through
+// garlic_tgls_set_rows_values.  false: the 65,537th distinct raw value.
+static bool fillTglsObject(const TglsFile *f, garlic_tgls *obj, const std::vector<int> &objCols)
+{
+    vcf::Reader rd;
+    if (!rd.open(f->path, (size_t)64 << 20)) fail(rd.error);
+    vcf::SlabLines cut;
+    std::vector<int64_t> lb;
+    std::vector<int32_t> status;
+    std::vector<double> raw((size_t)f->fileInd), vals(objCols.size());
+    std::string junk;
+    long long done = 0;
+    size_t consumed = 0;
+    do {
+        if (!rd.next(consumed)) fail(f->path + ": " + rd.error);
+        consumed = cut.take(rd.slab.data(), rd.have, rd.eof);
+        if (!rd.eof && consumed == 0 && rd.have == rd.slab.size()) fail("a line of " + f->path + " is longer than a slab");
+        const long long n = std::min<long long>((long long)cut.begin.size(), f->nrows - done);
+        if (n > 0) {
+            lb.assign(cut.begin.begin(), cut.begin.begin() + n);
+            lb.push_back((size_t)n < cut.begin.size() ? cut.begin[(size_t)n] : (int64_t)consumed);
+            status.assign((size_t)(2 * n), 0);
+            int rc = garlic_tgls_set_rows_text(obj, rd.slab.data(), (int64_t)consumed, lb.data(), done, n, status.data(), GARLIC_HOST);
+            if (rc == GARLIC_ERR_RANGE) return false;
+            auto lineOf = [&](long long r) { return std::string(rd.slab.data() + cut.begin[(size_t)r], (size_t)(cut.end[(size_t)r] - cut.begin[(size_t)r])); };
+            for (long long r = 0; r < n; r++)
+                if (status[(size_t)(2 * r)] >= GARLIC_TGLS_FEW_COLUMNS)
+                    fail("Incorrect number of columns in tgls file: " + std::to_string(countFields(lineOf(r))));
+            check(rc, "garlic_tgls_set_rows_text");
+            for (long long r = 0; r < n; r++) {
+                if (status[(size_t)(2 * r)] != GARLIC_TGLS_DEFERRED) continue;
+                const std::string line = lineOf(r);
+                const int num = countFields(line);
+                if (num != f->fileInd + 4) fail("Incorrect number of columns in tgls file: " + std::to_string(num));
+                std::stringstream ss(line);
+                ss >> junk >> junk >> junk >> junk;
+                for (double &v : raw) ss >> v;
+                for (size_t k = 0; k < objCols.size(); k++) vals[k] = raw[(size_t)objCols[k]];
+                rc = garlic_tgls_set_rows_values(obj, vals.data(), (int64_t)vals.size(), done + r, 1, GARLIC_HOST);
+                if (rc == GARLIC_ERR_RANGE) return false;
+                check(rc, "garlic_tgls_set_rows_values");
+            }
+            done += n;
+        }
+    } while (done < f->nrows && (!rd.eof || consumed < rd.have));
+    if (done < f->nrows) fail("too few lines in " + f->path);
+    return true;
+}
+
+// the object that serves individuals [ind_begin, +nind) on `device`, and where its columns begin in it
+static garlic_tgls *tglsObjectOn(TglsFile *f, int device, int ind_begin, int nind, int64_t &ind_offset)
+{
+    for (auto &o : f->objects)
+        if (o.device == device && o.ind_begin <= ind_begin && ind_begin + nind <= o.ind_begin + o.nind) {
+            ind_offset = ind_begin - o.ind_begin;
+            return (garlic_tgls *)o.tgls;
+        }
+    f->objects.push_back({device, ind_begin, nind, nullptr, nullptr});
+    TglsFile::Object &o = f->objects.back();
+    garlic_ctx *ctx = nullptr;
+    check(garlic_ctx_create(device, nullptr, &ctx), "garlic_ctx_create");
+    o.ctx = ctx;
+    const std::vector<int> objCols(f->cols.begin() + ind_begin, f->cols.begin() + ind_begin + nind);
+    garlic_tgls *obj = nullptr;
+    check(garlic_tgls_create(ctx, f->nrows, f->fileInd, objCols.data(), nind, &obj), "garlic_tgls_create");
+    o.tgls = obj;
+    if (!fillTglsObject(f, obj, objCols)) fail(f->path + " holds more than 65,536 distinct raw values on a second reading");
+    ind_offset = 0;
+    return obj;
+}
+
+std::vector<GenoLikeData *> *loadTGLSFile(const std::string &filename, int expectedInd, std::vector<MapData *> *maps,
+                                          const std::string &GL_TYPE, const std::vector<int> *cols, int fileInd, int device)
+{
+    if (cols && (int)cols->size() != expectedInd) fail("loadTGLSFile: one column per kept individual is needed");
+    if (GL_TYPE != "GQ" && GL_TYPE != "GL" && GL_TYPE != "PL") fail("Must choose GQ/GL/PL for genotype likelihood format");
+    std::unique_ptr<TglsFile, void (*)(TglsFile *)> f(new TglsFile, closeTglsFile);
+    f->path = filename;
+    f->glType = GL_TYPE == "GQ" ? GARLIC_GL_GQ : GL_TYPE == "GL" ? GARLIC_GL_GL : GARLIC_GL_PL;
+    f->fileInd = cols ? fileInd : expectedInd;
+    if (cols) f->cols = *cols;
+    else for (int i = 0; i < expectedInd; i++) f->cols.push_back(i);
+    for (int c : f->cols)
+        if (c < 0 || c >= f->fileInd) fail("loadTGLSFile: a kept column outside the file's columns");
+    for (auto m : *maps) f->nrows += m->nloci;
+    f->objects.push_back({device, 0, expectedInd, nullptr, nullptr});
+    garlic_ctx *ctx = nullptr;
+    check(garlic_ctx_create(device, nullptr, &ctx), "garlic_ctx_create");
+    f->objects.back().ctx = ctx;
+    garlic_tgls *obj = nullptr;
+    check(garlic_tgls_create(ctx, f->nrows, f->fileInd, f->cols.data(), expectedInd, &obj), "garlic_tgls_create");
+    f->objects.back().tgls = obj;
+    if (!fillTglsObject(f.get(), obj, f->cols)) {
+        std::cerr << filename << " holds more than 65,536 distinct values: read by the host reader instead\n";
+        return nullptr;
+    }
+    auto *out = new std::vector<GenoLikeData *>;
+    long long row = 0;
+    try {
+        for (auto m : *maps) {
+            int32_t nvalues = 0;
+            check(garlic_tgls_count_values(obj, f->glType, row, m->nloci, &nvalues), "garlic_tgls_count_values");
+            GenoLikeData *d = new GenoLikeData{nullptr, expectedInd, m->nloci, nullptr, nullptr, nvalues, nullptr, f.get(), new long long[m->nloci]};
+            f->refs++;
+            out->push_back(d);
+            for (int l = 0; l < m->nloci; l++) d->tglsRow[l] = row++;
+        }
+    } catch (...) {
+        for (auto d : *out) { delete[] d->tglsRow; delete d; }
+        delete out;
+        throw;
+    }
+    f.release();
+    return out;
+}
+
 std::vector<FreqData *> *readFreqData(const std::string &freqfile, std::vector<MapData *> *maps)
 {
     LineReader in(freqfile);
@@ -1112,7 +1246,8 @@ void filterSites(size_t c, const std::vector<char> &keep, std::vector<MapData *>
     GenoLikeData *g2 = nullptr;
     if (g) {
         g2 = new GenoLikeData{g->data ? new double *[n] : nullptr, g->nind, n, g->codes ? new unsigned char *[n] : nullptr,
-                              g->values, g->nvalues, g->codes16 ? new unsigned short *[n] : nullptr};
+                              g->values, g->nvalues, g->codes16 ? new unsigned short *[n] : nullptr,
+                              g->tgls, g->tgls ? new long long[n] : nullptr};      // (a device-held file: only the row map is edited)
         if (g->values) g->values = nullptr;   // the table moves on with the kept rows
     }
     int j = 0;
@@ -1138,10 +1273,11 @@ void filterSites(size_t c, const std::vector<char> &keep, std::vector<MapData *>
         if (g && g->data) g2->data[j] = g->data[l];
         if (g && g->codes) g2->codes[j] = g->codes[l];
         if (g && g->codes16) g2->codes16[j] = g->codes16[l];
+        if (g && g->tgls) g2->tglsRow[j] = g->tglsRow[l];
         j++;
     }
     delete[] h->data; delete[] h->firstCopy; delete[] h->packed; delete[] h->phaseBits; delete[] h->bedRow; delete h;
-    if (g) { delete[] g->data; delete[] g->codes; delete[] g->codes16; delete g; (*gls)[c] = g2; }
+    if (g) { delete[] g->data; delete[] g->codes; delete[] g->codes16; delete[] g->tglsRow; delete g; (*gls)[c] = g2; }
     releaseMapData(m); releaseFreqData(f);
     (*maps)[c] = m2; (*haps)[c] = h2; (*freqs)[c] = f2;
 }
@@ -1525,6 +1661,24 @@ void LodEngine::upload(std::vector<HapData *> *haps, std::vector<FreqData *> *fr
                 check(garlic_panel_set_phase_bed(s.panel, bedImageOn(b, s.device), s.ind_begin, dest.data()), "garlic_panel_set_phase_bed");
         }
     }
+    // likelihoods held on the devices (loadTGLSFile): every shard's panel takes its columns from the object on its device,
+    // through the row map the site filters left
+    const bool gl_on_device = USE_GL && gls->at(0)->tgls;
+    if (gl_on_device) {
+        TglsFile *f = gls->at(0)->tgls;
+        std::vector<int64_t> dest((size_t)f->nrows, -1);
+        int64_t at = 0;
+        for (int c = 0; c < nchr; c++) {
+            const GenoLikeData *g = gls->at(c);
+            if (g->tgls != f) fail("the chromosomes' likelihoods come from different files");
+            for (int l = 0; l < g->nloci; l++) dest[(size_t)g->tglsRow[l]] = at++;
+        }
+        for (auto &s : impl->shards) {
+            int64_t ind_offset = 0;
+            garlic_tgls *obj = tglsObjectOn(f, s.device, s.ind_begin, s.nind, ind_offset);
+            check(garlic_panel_set_gl_tgls(s.panel, obj, f->glType, ind_offset, dest.data()), "garlic_panel_set_gl_tgls");
+        }
+    }
     // genotype rows are separate allocations in HapData: stage a slab of SNP rows at a time
     const int64_t slab = std::max<int64_t>(1, ((int64_t)64 << 20) / (2 * (int64_t)impl->nind));
     std::vector<int16_t> stage;
@@ -1553,7 +1707,7 @@ void LodEngine::upload(std::vector<HapData *> *haps, std::vector<FreqData *> *fr
                 for (int r = 0; r < rows; r++)
                     memcpy(&stage[(size_t)r * impl->nind], h->data[l0 + r], sizeof(short) * impl->nind);
             }
-            const GenoLikeData *gld = USE_GL ? gls->at(c) : nullptr;
+            const GenoLikeData *gld = USE_GL && !gl_on_device ? gls->at(c) : nullptr;   // (on the device: filled above)
             const bool gl16 = gld && (gld->codes16 || (gld->codes && wide_codes));
             if (gl16) {
                 stage_glc16.resize((size_t)rows * impl->nind);

@@ -131,6 +131,20 @@ struct FreqData {          // src/garlic-data.h:69-73
     double *freq;
     int nloci;
 };
+// A --tgls file whose likelihoods live on the devices only (loadTGLSFile): parsed from the text and dictionary-coded there
+// (garlic_tgls), one object per device.  The first device's object holds every kept column -- it also answers how many
+// distinct values a chromosome has -- a further device's object holds its shard's columns, read from the file when the engine
+// first asks for it.  No per-genotype likelihood exists on the host.
+struct TglsFile {
+    std::string path;
+    int glType = 0;               // GARLIC_GL_GQ / _GL / _PL
+    int fileInd = 0;              // sample columns of a line
+    std::vector<int> cols;        // the kept columns of a line, in the panel's order of individuals
+    long long nrows = 0;          // lines read: the loci before any site filter
+    int refs = 0;                 // GenoLikeData that point here
+    struct Object { int device, ind_begin, nind; void *ctx, *tgls; };
+    std::vector<Object> objects;
+};
 struct GenoLikeData {      // src/garlic-data.h:89-95
     double **data;         // [locus][ind]: per-genotype error probability
     int nind;
@@ -145,6 +159,12 @@ struct GenoLikeData {      // src/garlic-data.h:89-95
     double *values;
     int nvalues;
     unsigned short **codes16;
+    // Extension (loadTGLSFile): the likelihoods are rows of a file held on the devices: data, codes and codes16 are NULL,
+    // locus l is row tglsRow[l] of `tgls`, nvalues the number of distinct converted values the chromosome had when it was
+    // read.  The site filters only edit tglsRow; the engine fills its panels device to device (garlic_panel_set_gl_tgls).
+    // likelihoodAt has nothing to read here.
+    TglsFile *tgls;
+    long long *tglsRow;
 };
 inline double likelihoodAt(const GenoLikeData *g, int locus, int ind)
 {
@@ -152,7 +172,11 @@ inline double likelihoodAt(const GenoLikeData *g, int locus, int ind)
     return g->values[g->codes16 ? g->codes16[locus][ind] : g->codes[locus][ind]];
 }
 // "one-byte codes", "16-bit codes" or "doubles": how a chromosome's likelihoods are held
-inline const char *likelihoodForm(const GenoLikeData *g) { return g->data ? "doubles" : g->codes16 ? "16-bit codes" : "one-byte codes"; }
+inline const char *likelihoodForm(const GenoLikeData *g)
+{
+    if (g->tgls) return g->nvalues > 256 ? "16-bit codes" : "one-byte codes";      // what the host reader's counts decide
+    return g->data ? "doubles" : g->codes16 ? "16-bit codes" : "one-byte codes";
+}
 struct LDData {            // src/garlic-data.h:103-108
     double **LD;           // [locus][winsize]
     int nloci;
@@ -258,6 +282,10 @@ void loadBedData(const std::string &bedfile, const std::string &bimfile, const s
                  int device = 0);
 void scanIndData3(const std::string &filename, int &numInd, std::string &popName);  // :1893
 IndData *readIndData3(const std::string &filename, int numInd);                     // :1963
+// The same file read through the device (TglsFile): the GenoLikeData per chromosome carry rows, not values.  cols / fileInd as
+// for readTGLSData.  NULL when the file holds more than 65,536 distinct raw values: it needs readTGLSData (one line on stderr).
+std::vector<GenoLikeData *> *loadTGLSFile(const std::string &filename, int expectedInd, std::vector<MapData *> *maps,
+                                          const std::string &GL_TYPE, const std::vector<int> *cols, int fileInd, int device);
 std::vector<GenoLikeData *> *readTGLSData(const std::string &filename, int expectedLoci, int expectedInd,
                                           std::vector<MapData *> *mapDataByChr,
                                           const std::string &GL_TYPE,

@@ -361,7 +361,13 @@ int run(const Args &a, FeatureData *features, BedFile *full, const std::vector<F
         const bool USE_GL = a.tgls != "none";
         if (USE_GL) {
             // rows in pre-filter TPED order; under --keep the kept individuals' columns of the whole .fam's
-            gls = readTGLSData(a.tgls, numLoci, numInd, maps, a.gl_type, /*compact=*/true, keep, keep ? (int)fam->size() : 0);
+            // parsed and coded on the first device, no likelihood on the host; GARLIC_TGLS_HOST_READER=1, or a file of more
+            // than 65,536 distinct values, keeps the host reader
+            const char *host_reader = getenv("GARLIC_TGLS_HOST_READER");
+            if (!(host_reader && *host_reader && strcmp(host_reader, "0")))
+                gls = loadTGLSFile(a.tgls, numInd, maps, a.gl_type, keep, keep ? (int)fam->size() : 0, devices[0]);
+            if (!gls)
+                gls = readTGLSData(a.tgls, numLoci, numInd, maps, a.gl_type, /*compact=*/true, keep, keep ? (int)fam->size() : 0);
             // the form each chromosome took: one byte per genotype up to 256 distinct values, two up to 65,536, else doubles
             std::cerr << "Genotype likelihoods (" << a.gl_type << "):";
             for (size_t c = 0; c < gls->size(); c++) {

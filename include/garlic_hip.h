@@ -65,7 +65,9 @@ extern "C" {
  *    garlic_kde_part_set_sums, garlic_kde_parts_multi, garlic_kde_parts_multi_info (likewise); garlic_bed_extract,
  *    garlic_bed_get_rows (likewise); garlic_feature_set_rows_bed, garlic_feature_set_get_rows (likewise);
  *    garlic_bed_set_order_rows, garlic_bed_get_order_rows, garlic_bed_set_rows_vcf, GARLIC_VCF_*, garlic_panel_set_phase_bed
- *    (likewise) */
+ *    (likewise); garlic_tgls, garlic_tgls_create, garlic_tgls_set_rows_text, garlic_tgls_set_rows_values, garlic_tgls_get_rows,
+ *    garlic_tgls_info, garlic_tgls_count_values, garlic_tgls_get_values, garlic_tgls_destroy, garlic_panel_set_gl_tgls, GARLIC_TGLS_OK / _DEFERRED / _FEW_COLUMNS /
+ *    _MANY_COLUMNS / _RAW, GARLIC_ERR_RANGE (likewise) */
 #define GARLIC_HIP_ABI_VERSION 8
 
 #define GARLIC_OK 0
@@ -73,6 +75,7 @@ extern "C" {
 #define GARLIC_ERR_HIP 2      /* HIP runtime failure / no gfx950 device */
 #define GARLIC_ERR_STATE 3    /* inputs missing for the requested computation */
 #define GARLIC_ERR_NOMEM 4
+#define GARLIC_ERR_RANGE 5    /* the input is outside what the object can hold (garlic_tgls: a 65,537th distinct raw value) */
 
 #define GARLIC_HOST 0
 #define GARLIC_DEVICE 1
@@ -290,6 +293,73 @@ int garlic_panel_set_gl_codes16(garlic_panel *panel, const uint16_t *codes, int6
 #define GARLIC_TGLS_CONTINUOUS 2
 #define GARLIC_TGLS_DICTIONARY16 3
 int garlic_panel_tgls_mode(garlic_panel *panel, int32_t *mode, int32_t *terms_by);
+
+/* A --tgls file's likelihoods, parsed from the text and dictionary-coded on the device (csrc/tgls_kernels.hpp).
+ * The object holds nrows rows of n_kept = (col_idx ? n_idx : ncols_total) uint16 codes and ONE dictionary of the RAW values --
+ * the doubles as operator>> reads them, before readTGLSData's conversion -- of at most 65,536 entries.  col_idx (host, may be
+ * NULL = every column in file order) names the sample columns the object keeps, in the order it keeps them; any order, and an
+ * index may repeat.  Code numbers are issued slab by slab: the values a call meets for the first time get the next codes in
+ * ascending order of their bit patterns, so the numbers depend on the file and the slab boundaries alone, and a code, once
+ * issued, never changes.
+ *
+ * garlic_tgls_set_rows_text   rows [row_begin, row_begin + row_count) from a slab of text; text, text_bytes, line_begin and
+ *     where mean what they mean for garlic_bed_set_rows_vcf (host or device text, no alignment asked for; a line ends at its
+ *     '\n', at the next line_begin or at text_bytes).  Of a line, four tokens are skipped; token 4 + j is sample column j.
+ *     Tokens are separated as operator>> and countFields separate them: by runs of isspace() bytes, leading and trailing
+ *     runs and a '\r' before the '\n' included.  A kept column's token becomes a double only where that is provably what
+ *     strtod gives (csrc/tgls_number.hpp: [+-]? (digits [. digits*]? | . digits) ([eE] [+-]? digits)?, at most 32 bytes,
+ *     the digits an integer <= 2^53, the decimal exponent within +-22); columns that are not kept are not read.
+ *     row_status[r] = {code, sample column of the line's first offence in file order}, {0, 0} for a clean line (host, may be
+ *     NULL):
+ *       GARLIC_TGLS_DEFERRED       a kept token that gets no value here.  NOT an error: the call returns GARLIC_OK, the row
+ *                                  counts as not set (rows_deferred of garlic_tgls_info) until garlic_tgls_set_rows_values
+ *                                  brings its doubles as the host parses them.  (A line whose first offence is a deferred
+ *                                  token is not looked at further: the host that parses it counts its fields as well.)
+ *       GARLIC_TGLS_FEW_COLUMNS    column = the number of sample columns found;
+ *       GARLIC_TGLS_MANY_COLUMNS   column = ncols_total.  Either makes the call GARLIC_ERR_INVALID, with the lowest such row
+ *                                  in garlic_hip_last_error; the clean rows of the call are written and count as set.
+ *     GARLIC_ERR_RANGE: the call met the 65,537th distinct raw value; the file needs the host reader, and every later call
+ *     on the object but destroy and info answers GARLIC_ERR_STATE.  (A form of 8 bytes per genotype is deliberately not
+ *     built: it needs the conversion's pow on the device, and GQ / GL / PL columns do not print that many values.)
+ *     The object keeps its staging buffers (the largest host slab + 16 bytes, 8 bytes per kept genotype of the largest call,
+ *     the line offsets and status pairs) until garlic_tgls_destroy, so that a file's slabs reuse them.
+ * garlic_tgls_set_rows_values the same rows from raw doubles raw[(r - row_begin) * ld + k], k < n_kept in the object's own
+ *     column order, ld >= n_kept, host or device.
+ * garlic_tgls_get_rows        out[(r - row_begin) * ld + k] (host or device) = the row's values: GARLIC_TGLS_RAW as parsed, or
+ *     GARLIC_GL_GQ / _GL / _PL converted as readTGLSData converts them (src/garlic-data.cpp:1557-1576, host libm, applied
+ *     to the dictionary).  GARLIC_ERR_STATE when a row of the range is not set.
+ * garlic_tgls_info            the dictionary's size and the numbers of set and of deferred rows (any pointer may be NULL).
+ * garlic_tgls_count_values    *n_values = the number of distinct values, raw or converted as for get_rows, among the rows of the
+ *     range: what decides the form a host reader would have given them (256 / 65,536).  Only a 64 KB flag array leaves the device.
+ * garlic_tgls_get_values      values[c] (host, n <= n_raw_values entries) = the value of code c, raw or converted as for get_rows:
+ *     the dictionary in the order its codes were issued.
+ * garlic_panel_set_gl_tgls    the panel's likelihoods from the object, device to device: row r goes to locus dest_locus[r]
+ *     (host, nrows entries, -1 = dropped, the others strictly ascending), individual i of the panel is kept column
+ *     ind_offset + i.  The dictionary is converted on the host (at most 65,536 values) and the codes go through the panel's
+ *     own doors: a panel without 16-bit codes that faces at most 256 distinct CONVERTED values takes them narrowed to one
+ *     byte through garlic_panel_set_gl_codes, every other one through garlic_panel_set_gl_codes16 -- the panel a host
+ *     reader's codes would have filled.  GARLIC_ERR_STATE while a row of the object is unset or deferred. */
+#define GARLIC_TGLS_OK 0
+#define GARLIC_TGLS_DEFERRED 1
+#define GARLIC_TGLS_FEW_COLUMNS 2
+#define GARLIC_TGLS_MANY_COLUMNS 3
+#define GARLIC_TGLS_RAW (-1) /* gl_type of garlic_tgls_get_rows: no conversion (GARLIC_GL_GQ is 0) */
+typedef struct garlic_tgls garlic_tgls;
+int garlic_tgls_create(garlic_ctx *ctx, int64_t nrows, int32_t ncols_total, const int32_t *col_idx /* NULL = all */,
+                       int32_t n_idx, garlic_tgls **out);
+int garlic_tgls_set_rows_text(garlic_tgls *tgls, const char *text, int64_t text_bytes, const int64_t *line_begin /* row_count + 1 */,
+                              int64_t row_begin, int64_t row_count, int32_t *row_status /* [row_count][2], may be NULL */,
+                              int32_t where);
+int garlic_tgls_set_rows_values(garlic_tgls *tgls, const double *raw, int64_t ld, int64_t row_begin, int64_t row_count,
+                                int32_t where);
+int garlic_tgls_get_rows(garlic_tgls *tgls, int32_t gl_type, int64_t row_begin, int64_t row_count, double *out, int64_t ld,
+                         int32_t where);
+int garlic_tgls_info(garlic_tgls *tgls, int32_t *n_raw_values, int64_t *rows_set, int64_t *rows_deferred);
+int garlic_tgls_count_values(garlic_tgls *tgls, int32_t gl_type, int64_t row_begin, int64_t row_count, int32_t *n_values);
+int garlic_tgls_get_values(garlic_tgls *tgls, int32_t gl_type, double *values, int32_t n);
+int garlic_panel_set_gl_tgls(garlic_panel *panel, garlic_tgls *tgls, int32_t gl_type, int64_t ind_offset,
+                             const int64_t *dest_locus /* [nrows], -1 = dropped */);
+int garlic_tgls_destroy(garlic_tgls *tgls);
 
 /* Unweighted scores from dictionary-coded likelihoods run in two passes: the codes are expanded once into the TGLS term
  * matrix (8 bytes per genotype, 64-individual blocks of rows x 64 doubles, rows = 32 + nloci + 4160), which the chain then
