@@ -1,8 +1,9 @@
 """GPU: garlic-lod --tgls through the device reader (loadTGLSFile: the text parsed and dictionary-coded on the device, the
 panels filled device to device) against the same run under GARLIC_TGLS_HOST_READER=1 (readTGLSData, which
 tests/test_oracle_vs_ref.py pins to the reference's reader): every output file byte for byte, and the same "Genotype
-likelihoods" line.  600 loci x 24 individuals, W = 30; GQ integers (one-byte codes) and GL decimals (16-bit codes), one row
-of each file with a token the device defers to the host's stream parse."""
+likelihoods" line.  600 loci x 24 individuals, W = 30; GQ integers (one-byte codes), GL decimals (16-bit codes) and GL values
+in every spelling of the grammar (exponents, +, .5, 5., signed zeros), one row of each file with a token the device defers to
+the host's stream parse."""
 import filecmp
 import glob
 import gzip
@@ -13,6 +14,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import tgls_cases as tc
 from garlic_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -65,7 +67,26 @@ def make_set(d, n, seed):
         with open(path, "rb") as f, gzip.open(path + ".gz", "wb") as g:
             shutil.copyfileobj(f, g)
         files[name] = path
+    files["GLX"] = spellings_file(str(d / "GLX.tgls"), rng, chrs, pos)
     return {"vcf": prefix + ".vcf", "tped": ["--tped", prefix + ".tped", "--tfam", prefix + ".tfam"], "plink": plink, "tgls": files}
+
+
+def spellings_file(path, rng, chrs, pos):
+    """GL values -12 .. 0 to three decimals, each in a spelling spelled() draws, and in every row five valued members of
+    grammar_tokens(): an exponent, a +, a .5, a 5. and a signed zero; one token deferred for its exponent"""
+    valued = [t for t, _ in tc.grammar_tokens() if not tc.defers(t)]
+    picks = [[t for t in valued if b"e" in t.lower() and float(t) != 0], [b"+5", b"+5.e0", b"+0.000"], [b".5", b"-.5"], [b"5.", b"0."],
+             [b"0", b"-0", b"-0.0", b"+0.000", b"-.0", b"0e99999999999", b"-0e-99999999999"]]
+    assert all(len(p) >= 2 and set(p) <= set(valued) for p in picks)
+    with open(path, "wb") as f:
+        for l in range(len(chrs)):
+            row = [tc.spelled(rng, int(m), -3, sign=b"-") for m in rng.integers(1, 12000, size=NIND)]
+            for p, c in zip(picks, rng.permutation(NIND)):
+                row[c] = p[int(rng.integers(0, len(p)))]
+            if l == 7:
+                row[3] = b"1e-23"                      # deferred: the exponent is past the fast path
+            f.write(b"%s rs%d 0 %d " % (chrs[l].encode(), l, pos[l]) + (b" " if l % 2 else b"\t").join(row) + b"\n")
+    return path
 
 
 @pytest.fixture(scope="module")
@@ -104,6 +125,11 @@ def both(tmp_path, inputs, tgls, gl_type, want_form):
 @pytest.mark.parametrize("gl_type,form", [("GQ", "one-byte codes"), ("GL", "16-bit codes")])
 def test_tped_run_equals_the_host_readers(tmp_path, small, gl_type, form):
     err = both(tmp_path, small["tped"], small["tgls"][gl_type], gl_type, form)
+    assert "host reader" not in err
+
+
+def test_every_spelling_of_the_grammar_equals_the_host_readers(tmp_path, small):
+    err = both(tmp_path, small["tped"], small["tgls"]["GLX"], "GL", "16-bit codes")
     assert "host reader" not in err
 
 
