@@ -16,6 +16,8 @@ OK, ERR_INVALID, ERR_HIP, ERR_STATE, ERR_NOMEM, ERR_RANGE = 0, 1, 2, 3, 4, 5
 HOST, DEVICE = 0, 1
 # GARLIC_VCF_*: what garlic_bed_set_rows_vcf answers per row
 VCF_BAD_BYTE, VCF_HALF_MISSING, VCF_HAPLOID, VCF_ALLELE_INDEX, VCF_FEW_COLUMNS, VCF_MANY_COLUMNS = 1, 2, 3, 4, 5, 6
+# GARLIC_TPED_*: what garlic_bed_set_rows_tped answers per row
+TPED_LONG_ALLELE, TPED_BAD_BYTE, TPED_FEW_COLUMNS, TPED_MANY_COLUMNS = 1, 2, 3, 4
 FEED_FROM_SCORES, FEED_CHAIN, FEED_SAMPLED_WLOD, FEED_TGLS_CHAIN = 0, 1, 2, 3   # garlic_lod_feed_info
 FEED_TGLS_CHAIN_SHARED = 4   # garlic_lod_feed_multi_info: the size shared its chain launch with another size
 FEED_ORDER_REFERENCE, FEED_ORDER_SORTED = 0, 1   # garlic_panel_set_feed_order
@@ -52,6 +54,7 @@ SYMBOLS = [
     "garlic_bed_create", "garlic_bed_set_rows", "garlic_bed_census", "garlic_bed_destroy", "garlic_panel_set_genotypes_bed",
     "garlic_bed_extract", "garlic_bed_get_rows",
     "garlic_bed_set_order_rows", "garlic_bed_get_order_rows", "garlic_bed_set_rows_vcf", "garlic_panel_set_phase_bed",
+    "garlic_bed_set_rows_tped", "garlic_bed_set_census",
     "garlic_tgls_create", "garlic_tgls_set_rows_text", "garlic_tgls_set_rows_values", "garlic_tgls_get_rows", "garlic_tgls_info",
     "garlic_tgls_get_values", "garlic_tgls_count_values",
     "garlic_tgls_destroy", "garlic_panel_set_gl_tgls",
@@ -254,6 +257,8 @@ def lib():
     L.garlic_bed_get_order_rows.argtypes = [_vp, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_int32]
     L.garlic_bed_set_rows_vcf.argtypes = [_vp, _vp, C.c_int64, _i64p, C.c_int64, C.c_int64, _vp, C.c_int32]
     L.garlic_panel_set_phase_bed.argtypes = [_vp, _vp, C.c_int64, _i64p]
+    L.garlic_bed_set_rows_tped.argtypes = [_vp, _vp, C.c_int64, _i64p, C.c_int64, C.c_int64, C.c_uint8, _vp, _vp, C.c_int32]
+    L.garlic_bed_set_census.argtypes = [_vp, _vp, _vp, C.c_int32]
     L.garlic_tgls_create.argtypes = [_vp, C.c_int64, C.c_int32, _i32p, C.c_int32, C.POINTER(_vp)]
     L.garlic_tgls_set_rows_text.argtypes = [_vp, _vp, C.c_int64, _i64p, C.c_int64, C.c_int64, _vp, C.c_int32]
     L.garlic_tgls_set_rows_values.argtypes = [_vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32]
@@ -849,6 +854,38 @@ class Bed:
             if rc != ERR_INVALID or not status[:, 0].any():
                 raise err
         return status, err
+
+    def set_rows_tped(self, text, line_begin, row_begin=0, missing=b"0", text_bytes=None, where=HOST):
+        """Image rows, order rows and census of rows [row_begin, row_begin + len(line_begin) - 1) parsed from TPED text on the
+        device (garlic_bed_set_rows_tped).  text: bytes / uint8 array (host), or a device address with text_bytes and
+        where=DEVICE; missing: the --tped-missing character (one byte, or its value).
+        Returns (row_allele uint8 [rows], row_status int32 [rows][2] = code, individual).  An offending line raises the
+        GarlicError (ERR_INVALID) with both arrays as its row_allele / row_status attributes: the clean rows are written."""
+        lb = np.ascontiguousarray(line_begin, dtype=np.int64)
+        assert lb.ndim == 1 and lb.shape[0] >= 2
+        if where == HOST:
+            buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else np.asarray(text)
+            assert buf.dtype == np.uint8 and buf.ndim == 1 and (buf.shape[0] <= 1 or buf.strides[0] == 1)
+            ptr, text_bytes = buf.ctypes.data, buf.shape[0] if text_bytes is None else text_bytes
+        else:
+            ptr = int(text)
+        miss = missing[0] if isinstance(missing, (bytes, bytearray)) else ord(missing) if isinstance(missing, str) else int(missing)
+        status = np.zeros((lb.shape[0] - 1, 2), dtype=np.int32)
+        allele = np.zeros(lb.shape[0] - 1, dtype=np.uint8)
+        rc = lib().garlic_bed_set_rows_tped(self.handle, _vp(ptr), int(text_bytes), _ptr(lb, _i64p), row_begin, lb.shape[0] - 1, miss,
+                                            _vp(allele.ctypes.data), _vp(status.ctypes.data), where)
+        if rc != OK:
+            err = GarlicError(rc, lib().garlic_hip_last_error().decode())
+            err.row_allele, err.row_status = allele, status
+            raise err
+        return allele, status
+
+    def set_census(self, counts, counted):
+        """The census the image's source computed (garlic_bed_set_census): counts int32 [nrows][2], counted uint8 [nrows]."""
+        counts = np.ascontiguousarray(counts, dtype=np.int32)
+        counted = np.ascontiguousarray(counted, dtype=np.uint8)
+        assert counts.shape == (self.nrows, 2) and counted.shape == (self.nrows,)
+        check(lib().garlic_bed_set_census(self.handle, _vp(counts.ctypes.data), _vp(counted.ctypes.data), HOST))
 
     def destroy(self):
         if self.handle:

@@ -31,6 +31,7 @@
 #include "../host/chain_order.hpp"
 #include "bed_kernels.hpp"
 #include "vcf_kernels.hpp"
+#include "tped_kernels.hpp"
 #include "tgls_kernels.hpp"
 
 #include <algorithm>
@@ -2916,7 +2917,22 @@ struct garlic_bed {
     DevBuf<uint8_t> vcf_text;                               // garlic_bed_set_rows_vcf: a host slab on the device
     DevBuf<int64_t> vcf_lines;
     DevBuf<int32_t> vcf_status;
+    // where the rows came from: an image filled by garlic_bed_set_rows_tped carries the census its parse wrote (tped_kernels.hpp),
+    // which the image rule cannot recompute, so the two kinds of source do not mix on one image
+    enum Source { SOURCE_NONE = 0, SOURCE_ROWS = 1, SOURCE_TPED = 2 };
+    int source = SOURCE_NONE;
+    DevBuf<uint8_t> tped_allele;                            // garlic_bed_set_rows_tped: `one` per row of the call
 };
+
+// the first call that fills an image decides its kind
+static int bed_claim_source(garlic_bed *b, int source, const char *what)
+{
+    if (b->source != garlic_bed::SOURCE_NONE && b->source != source)
+        return fail(GARLIC_ERR_STATE, "%s: the image holds rows %s; the two sources do not mix on one image", what,
+                    b->source == garlic_bed::SOURCE_TPED ? "parsed from TPED text, with the census of that parse" : "set as image rows or parsed from a VCF");
+    b->source = source;
+    return GARLIC_OK;
+}
 
 int garlic_bed_create(garlic_ctx *ctx, int64_t nrows, int32_t nind_total, garlic_bed **out)
 {
@@ -2964,7 +2980,7 @@ int garlic_bed_set_rows(garlic_bed *b, const uint8_t *rows, int64_t row_bytes, i
         return fail(GARLIC_ERR_INVALID, "row range [%lld,+%lld) outside image of %lld rows", (long long)row_begin,
                     (long long)row_count, (long long)b->nrows);
     int rc;
-    if ((rc = set_device(b->ctx))) return rc;
+    if ((rc = bed_claim_source(b, garlic_bed::SOURCE_ROWS, "bed_set_rows")) || (rc = set_device(b->ctx))) return rc;
     hipStream_t s = b->ctx->stream;
     b->census_valid = false;
     rc = for_each_upload_slab(s, "bed_set_rows", rows, row_bytes, row_count, where, b->stage, [&](const void *src, int64_t at, int64_t n) {
@@ -2992,6 +3008,15 @@ static int bed_ensure_census(garlic_bed *b)
     int rc;
     if ((rc = set_device(b->ctx))) return rc;
     hipStream_t s = b->ctx->stream;
+    if (b->source == garlic_bed::SOURCE_TPED) {      // the parse wrote it, row by row: only the host's copy is missing
+        b->counts.resize((size_t)(2 * b->nrows));
+        b->counted.resize((size_t)b->nrows);
+        HIP_TRY(hipMemcpyAsync(b->counts.data(), b->d_counts.p, sizeof(int32_t) * 2 * b->nrows, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(b->counted.data(), b->d_counted.p, (size_t)b->nrows, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        b->census_valid = true;
+        return GARLIC_OK;
+    }
     // lanes per row: the pieces a row can touch (it starts at any byte), as a power of two; narrower rows share a wave
     const int64_t pieces = (b->row_bytes + 30) >> 4;
     int group = 1;
@@ -3129,6 +3154,7 @@ int garlic_bed_extract(garlic_bed *src, const int32_t *ind_idx, int32_t n_idx, g
     HIP_TRY(hipStreamSynchronize(s));                   // the index lists are free again; `src` may go
     b->row_set.assign((size_t)((b->nrows + 63) / 64), ~0ull);
     b->n_set = b->nrows;
+    b->source = garlic_bed::SOURCE_ROWS;
     *out = b.release();
     return GARLIC_OK;
 }
@@ -3186,8 +3212,8 @@ static int bed_check_order_args(const garlic_bed *b, const void *rows, int64_t r
 int garlic_bed_set_order_rows(garlic_bed *b, const uint8_t *rows, int64_t row_bytes, int64_t row_begin, int64_t row_count, int32_t where)
 {
     int rc;
-    if ((rc = bed_check_order_args(b, rows, row_bytes, row_begin, row_count, where)) || (rc = set_device(b->ctx)) ||
-        (rc = bed_ensure_order(b)))
+    if ((rc = bed_check_order_args(b, rows, row_bytes, row_begin, row_count, where)) ||
+        (rc = bed_claim_source(b, garlic_bed::SOURCE_ROWS, "bed_set_order_rows")) || (rc = set_device(b->ctx)) || (rc = bed_ensure_order(b)))
         return rc;
     hipStream_t s = b->ctx->stream;
     b->census_valid = false;
@@ -3245,7 +3271,7 @@ int garlic_bed_set_rows_vcf(garlic_bed *b, const char *text, int64_t text_bytes,
             return fail(GARLIC_ERR_INVALID, "line_begin[%lld] = %lld: the offsets must ascend inside the slab of %lld bytes", (long long)r,
                         (long long)line_begin[r], (long long)text_bytes);
     int rc;
-    if ((rc = set_device(b->ctx)) || (rc = bed_ensure_order(b))) return rc;
+    if ((rc = bed_claim_source(b, garlic_bed::SOURCE_ROWS, "bed_set_rows_vcf")) || (rc = set_device(b->ctx)) || (rc = bed_ensure_order(b))) return rc;
     hipStream_t s = b->ctx->stream;
     b->census_valid = false;
     const uint8_t *d_text = reinterpret_cast<const uint8_t *>(text);
@@ -3276,6 +3302,110 @@ int garlic_bed_set_rows_vcf(garlic_bed *b, const char *text, int64_t text_bytes,
     if (bad >= 0)
         return fail(GARLIC_ERR_INVALID, "VCF row %lld (line %lld of the call): %s at sample column %d", (long long)(row_begin + bad),
                     (long long)bad, vcf_offence_name(status[(size_t)(2 * bad)]), status[(size_t)(2 * bad + 1)]);
+    return GARLIC_OK;
+}
+
+// ---- the TPED door (tped_kernels.hpp) and the census a source hands over
+static const char *tped_offence_name(int code)
+{
+    switch (code) {
+    case TPED_LONG_ALLELE: return "an allele longer than one character";
+    case TPED_BAD_BYTE: return "a vertical tab, form feed or NUL byte";
+    case TPED_FEW_COLUMNS: return "too few allele columns";
+    case TPED_MANY_COLUMNS: return "too many allele columns";
+    }
+    return "an unknown offence";
+}
+
+int garlic_bed_set_rows_tped(garlic_bed *b, const char *text, int64_t text_bytes, const int64_t *line_begin, int64_t row_begin,
+                             int64_t row_count, uint8_t missing, uint8_t *row_allele, int32_t *row_status, int32_t where)
+{
+    if (!b || !text || !line_begin) return fail(GARLIC_ERR_INVALID, "bed, text and line_begin are required");
+    if (where != GARLIC_HOST && where != GARLIC_DEVICE) return fail(GARLIC_ERR_INVALID, "where must be GARLIC_HOST or GARLIC_DEVICE");
+    if (text_bytes < 1) return fail(GARLIC_ERR_INVALID, "text_bytes %lld: the slab is empty", (long long)text_bytes);
+    if (missing == ' ' || missing == '\t' || missing == '\r' || missing == '\n')
+        return fail(GARLIC_ERR_INVALID, "the missing character (byte %d) is a blank or a newline", (int)missing);
+    if (row_begin < 0 || row_count < 1 || row_begin + row_count > b->nrows)
+        return fail(GARLIC_ERR_INVALID, "row range [%lld,+%lld) outside image of %lld rows", (long long)row_begin,
+                    (long long)row_count, (long long)b->nrows);
+    for (int64_t r = 0; r <= row_count; r++)
+        if (line_begin[r] < 0 || line_begin[r] > text_bytes || (r && line_begin[r] < line_begin[r - 1]))
+            return fail(GARLIC_ERR_INVALID, "line_begin[%lld] = %lld: the offsets must ascend inside the slab of %lld bytes", (long long)r,
+                        (long long)line_begin[r], (long long)text_bytes);
+    int rc;
+    if ((rc = bed_claim_source(b, garlic_bed::SOURCE_TPED, "bed_set_rows_tped")) || (rc = set_device(b->ctx)) || (rc = bed_ensure_order(b)))
+        return rc;
+    hipStream_t s = b->ctx->stream;
+    b->census_valid = false;
+    const uint8_t *d_text = reinterpret_cast<const uint8_t *>(text);
+    if (where == GARLIC_HOST) {
+        if ((rc = b->vcf_text.reserve((size_t)text_bytes + 16))) return rc;      // (its last piece lies inside the buffer)
+        HIP_TRY(hipMemcpyAsync(b->vcf_text.p, text, (size_t)text_bytes, hipMemcpyHostToDevice, s));
+        d_text = b->vcf_text.p;
+    }
+    if ((rc = b->vcf_lines.reserve((size_t)row_count + 1)) || (rc = b->vcf_status.reserve((size_t)(2 * row_count))) ||
+        (rc = b->tped_allele.reserve((size_t)row_count)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(b->vcf_lines.p, line_begin, sizeof(int64_t) * (size_t)(row_count + 1), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(tped_parse_kernel, dim3((unsigned)row_count), dim3(256), 0, s, d_text, text_bytes, b->vcf_lines.p, row_begin, b->nind,
+                       (uint32_t)missing, b->d_image.p, b->row_bytes, b->d_order.p, b->order_row_bytes, b->d_counts.p, b->d_counted.p,
+                       b->tped_allele.p, b->vcf_status.p);
+    HIP_TRY(hipGetLastError());
+    std::vector<int32_t> status((size_t)(2 * row_count));
+    std::vector<uint8_t> one((size_t)row_count);
+    HIP_TRY(hipMemcpyAsync(status.data(), b->vcf_status.p, sizeof(int32_t) * status.size(), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(one.data(), b->tped_allele.p, one.size(), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (row_status) memcpy(row_status, status.data(), sizeof(int32_t) * status.size());
+    if (row_allele) memcpy(row_allele, one.data(), one.size());
+    int64_t bad = -1;
+    for (int64_t r = 0; r < row_count; r++) {
+        uint64_t &word = b->row_set[(size_t)((row_begin + r) >> 6)];
+        const uint64_t bit = 1ull << ((row_begin + r) & 63);
+        if (status[(size_t)(2 * r)]) {
+            if (bad < 0) bad = r;
+            if (word & bit) { word &= ~bit; b->n_set--; }      // its bits and its census are unspecified now
+            continue;
+        }
+        if (!(word & bit)) { word |= bit; b->n_set++; }
+    }
+    if (bad >= 0)
+        return fail(GARLIC_ERR_INVALID, "TPED row %lld (line %lld of the call): %s at individual %d", (long long)(row_begin + bad),
+                    (long long)bad, tped_offence_name(status[(size_t)(2 * bad)]), status[(size_t)(2 * bad + 1)]);
+    return GARLIC_OK;
+}
+
+int garlic_bed_set_census(garlic_bed *b, const int32_t *counts, const uint8_t *counted, int32_t where)
+{
+    if (!b || !counts || !counted) return fail(GARLIC_ERR_INVALID, "bed, counts and counted are required");
+    if (where != GARLIC_HOST && where != GARLIC_DEVICE) return fail(GARLIC_ERR_INVALID, "where must be GARLIC_HOST or GARLIC_DEVICE");
+    if (b->n_set != b->nrows)
+        return fail(GARLIC_ERR_STATE, "bed set_census needs every row: %lld of %lld set", (long long)b->n_set, (long long)b->nrows);
+    int rc;
+    if ((rc = set_device(b->ctx))) return rc;
+    hipStream_t s = b->ctx->stream;
+    std::vector<int32_t> c((size_t)(2 * b->nrows));
+    std::vector<uint8_t> k((size_t)b->nrows);
+    if (where == GARLIC_HOST) {
+        memcpy(c.data(), counts, sizeof(int32_t) * c.size());
+        memcpy(k.data(), counted, k.size());
+    } else {
+        HIP_TRY(hipMemcpyAsync(c.data(), counts, sizeof(int32_t) * c.size(), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(k.data(), counted, k.size(), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    for (int64_t r = 0; r < b->nrows; r++) {
+        if (k[(size_t)r] > 2) return fail(GARLIC_ERR_INVALID, "set_census: counted[%lld] = %d is none of 0 (A1), 1 (A2), 2 (none)", (long long)r, (int)k[(size_t)r]);
+        const int32_t na = c[(size_t)(2 * r)], tot = c[(size_t)(2 * r + 1)];
+        if (na < 0 || tot < 0 || na > tot)
+            return fail(GARLIC_ERR_INVALID, "set_census: counts[%lld] = {%d, %d} are no {nalleles, total}", (long long)r, na, tot);
+    }
+    HIP_TRY(hipMemcpyAsync(b->d_counts.p, c.data(), sizeof(int32_t) * c.size(), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(b->d_counted.p, k.data(), k.size(), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    b->counts.swap(c);
+    b->counted.swap(k);
+    b->census_valid = true;
     return GARLIC_OK;
 }
 

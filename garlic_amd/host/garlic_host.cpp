@@ -1,6 +1,7 @@
 // Host adapter: the reference's Phase-I interface on top of libgarlic_hip.so (see garlic_host.hpp).
 #include "garlic_host.hpp"
 #include "vcf_lines.hpp"
+#include "tped_lines.hpp"
 
 #include "../../include/garlic_hip.h"
 
@@ -630,8 +631,10 @@ garlic_bed *bedFullImageOn(BedFile *b, int device)
         memcpy(buf.data(), b->rows + (size_t)r * b->row_bytes, (size_t)n * b->row_bytes);
         check(garlic_bed_set_rows(bed, buf.data(), (int64_t)b->row_bytes, r, n, GARLIC_HOST), "garlic_bed_set_rows");
     }
-    if (b->order)      // a VCF image: its order plane from the host's copy
+    if (b->order)      // a VCF or TPED image: its order plane from the host's copy
         check(garlic_bed_set_order_rows(bed, b->order, (int64_t)b->order_row_bytes, 0, b->nrows, GARLIC_HOST), "garlic_bed_set_order_rows");
+    if (b->own_census)  // a TPED image: the census its parse wrote on the first device (the image rule cannot recompute it)
+        check(garlic_bed_set_census(bed, b->counts.data(), b->counted.data(), GARLIC_HOST), "garlic_bed_set_census");
     return bed;
 }
 
@@ -789,6 +792,102 @@ void loadVcfData(const std::string &vcffile, bool phased, bool snpsOnly, std::ve
     loadBedFile(b.release(), numLoci, numInd, hapDataByChr, mapDataByChr, freqDataByChr, nresample, resampleSeed, device);
 }
 
+bool loadTPEDDataOnDevice(const std::string &tpedfile, int &numLoci, int &numInd, std::vector<HapData *> **hapDataByChr,
+                          std::vector<MapData *> **mapDataByChr, std::vector<FreqData *> **freqDataByChr, char TPED_MISSING, bool PHASED,
+                          int nresample, unsigned long long resampleSeed, int device, std::string &refusal)
+{
+    refusal.clear();
+    if (TPED_MISSING == ' ' || TPED_MISSING == '\t' || TPED_MISSING == '\r' || TPED_MISSING == '\n') {
+        refusal = tpedfile + ": the missing character is a blank";
+        return false;
+    }
+    std::unique_ptr<BedFile, void (*)(BedFile *)> b(new BedFile, closeBedFile);
+    b->path = tpedfile;
+    b->phased = PHASED;
+    b->own_census = true;
+    b->none_allele = TPED_MISSING;
+    const size_t SLAB = (size_t)64 << 20;
+    // first pass: the four leading tokens of every line and the number of individuals -- what garlic_bed_create needs
+    {
+        tped::Reader rd;
+        if (!rd.open(tpedfile, SLAB)) { refusal = rd.error; return false; }      // (the host reader says what it says about that)
+        tped::SlabLines cut;
+        size_t used = 0;
+        do {
+            if (!rd.next(used)) fail(tpedfile + ": " + rd.error);
+            used = cut.take(rd.slab.data(), rd.have, rd.eof);
+            if (!rd.eof && used == 0 && rd.have == rd.slab.size()) fail(tpedfile + ": a line longer than 64 MB");
+            for (size_t k = 0; k < cut.begin.size(); k++) {
+                const char *line = rd.slab.data() + cut.begin[k];
+                const size_t len = (size_t)(cut.end[k] - cut.begin[k]);
+                if (b->chr.empty()) {
+                    b->nind = tped::individualsOf(line, len);
+                    if (b->nind < 1) {
+                        refusal = "line " + std::to_string(cut.number[k]) + " of " + tpedfile + ": no genotype columns";
+                        return false;
+                    }
+                }
+                tped::Lead lead;
+                tped::parseLead(line, len, lead);
+                b->chr.push_back(lead.chr); b->name.push_back(lead.name); b->gpos.push_back(lead.gpos); b->ppos.push_back(lead.ppos);
+            }
+        } while (!rd.eof || used < rd.have);
+    }
+    b->nrows = (long long)b->chr.size();
+    if (b->nrows < 1) fail("no loci in " + tpedfile);
+    b->row_bytes = ((size_t)b->nind + 3) / 4;
+    b->order_row_bytes = ((size_t)b->nind + 7) / 8;
+    b->a1.assign((size_t)b->nrows, TPED_MISSING);
+    b->a2.assign((size_t)b->nrows, TPED_MISSING);
+    // second pass: the text to the device in slabs, one parse call per slab
+    const size_t slot = bedSlotOn(b.get(), device);
+    garlic_bed *bed = nullptr;
+    check(garlic_bed_create((garlic_ctx *)b->images[slot].ctx, b->nrows, b->nind, &bed), "garlic_bed_create");
+    b->images[slot].bed = bed;
+    {
+        tped::Reader rd;
+        if (!rd.open(tpedfile, SLAB)) fail(rd.error);
+        tped::SlabLines cut;
+        size_t used = 0;
+        long long row = 0;
+        std::vector<int64_t> lb;
+        std::vector<int32_t> status;
+        do {
+            if (!rd.next(used)) fail(tpedfile + ": " + rd.error);
+            used = cut.take(rd.slab.data(), rd.have, rd.eof);
+            if (cut.begin.empty()) continue;
+            const int64_t n = (int64_t)cut.begin.size();
+            if (row + n > b->nrows) fail(tpedfile + " changed while it was read");
+            lb.assign(cut.begin.begin(), cut.begin.end());
+            lb.push_back(cut.end.back());
+            status.assign((size_t)(2 * n), 0);
+            const int rc = garlic_bed_set_rows_tped(bed, rd.slab.data(), (int64_t)rd.have, lb.data(), row, n, (uint8_t)TPED_MISSING,
+                                                    (uint8_t *)b->a1.data() + row, status.data(), GARLIC_HOST);
+            if (rc == GARLIC_ERR_INVALID) {
+                for (int64_t r = 0; r < n; r++)
+                    if (status[(size_t)(2 * r)]) {
+                        refusal = "line " + std::to_string(cut.number[(size_t)r]) + " of " + tpedfile + " is refused by the device reader (code " +
+                                  std::to_string(status[(size_t)(2 * r)]) + ": " + garlic_hip_last_error() + ")";
+                        return false;
+                    }
+            }
+            check(rc, "garlic_bed_set_rows_tped");
+            row += n;
+        } while (!rd.eof || used < rd.have);
+        if (row != b->nrows) fail(tpedfile + " changed while it was read");
+    }
+    // the host's copies, fetched once: genotypeAt, the phase readers, the genotype cache, and the source of further devices' images
+    b->own_rows.resize((size_t)b->nrows * b->row_bytes);
+    b->own_order.resize((size_t)b->nrows * b->order_row_bytes);
+    check(garlic_bed_get_rows(bed, 0, b->nrows, b->own_rows.data(), (int64_t)b->row_bytes, GARLIC_HOST), "garlic_bed_get_rows");
+    check(garlic_bed_get_order_rows(bed, 0, b->nrows, b->own_order.data(), (int64_t)b->order_row_bytes, GARLIC_HOST), "garlic_bed_get_order_rows");
+    b->rows = b->own_rows.data();
+    b->order = b->own_order.data();
+    b->refs = 1;
+    loadBedFile(b.release(), numLoci, numInd, hapDataByChr, mapDataByChr, freqDataByChr, nresample, resampleSeed, device);
+    return true;
+}
+
 void loadBedSubset(BedFile *full, const std::vector<int> &keep, int &numLoci, int &numInd, std::vector<HapData *> **hapDataByChr,
                    std::vector<MapData *> **mapDataByChr, std::vector<FreqData *> **freqDataByChr, int nresample,
                    unsigned long long resampleSeed, int device)
@@ -839,8 +938,8 @@ static void loadBedFile(BedFile *b, int &numLoci, int &numInd, std::vector<HapDa
                 m->physicalPos[l] = (int)bim->ppos[r];
                 m->geneticPos[l] = bim->gpos[r];
                 m->locusName[l] = bim->name[r];
-                // what loadTPEDData stores as oneAllele: the counted allele's character, the missing character '0' for none
-                m->allele[l] = b->counted[r] == 0 ? bim->a1[r] : b->counted[r] == 1 ? bim->a2[r] : '0';
+                // what loadTPEDData stores as oneAllele: the counted allele's character, the missing character for none
+                m->allele[l] = b->counted[r] == 0 ? bim->a1[r] : b->counted[r] == 1 ? bim->a2[r] : b->none_allele;
                 const int nalleles = b->counts[2 * r], total = b->counts[2 * r + 1];
                 double freq = total == 0 ? 0.0 : double(nalleles) / double(total);   // garlic-data.cpp:141
                 if (nresample > 0 && total != 0) {

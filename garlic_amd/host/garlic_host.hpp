@@ -64,6 +64,11 @@ struct BedFile {
     std::vector<unsigned char> own_order;
     bool phased = false;
     long long skipped_non_snp = 0;        // --vcf-biallelic-snps-only: lines left out
+    // TPED input (loadTPEDDataOnDevice): as VCF input, and a1 holds each line's counted allele (garlic_bed_set_rows_tped's
+    // row_allele).  own_census: counts / counted are what the parse on the first device wrote (half-missing genotypes count
+    // in total, which no rule recounts from the image); further devices get them through garlic_bed_set_census.
+    bool own_census = false;
+    char none_allele = '0';               // MapData::allele of a row without a counted allele: the missing character
     const BedFile *bim() const { return parent ? parent : this; }
 };
 // HapData::firstCopy of file row r, individual i of a VCF image: non-missing && (order bit == (counted == A2)); all true on a
@@ -269,6 +274,15 @@ void loadVcfData(const std::string &vcffile, bool phased, bool snpsOnly, std::ve
 void loadBedSubset(BedFile *full, const std::vector<int> &keep, int &numLoci, int &numInd, std::vector<HapData *> **hapDataByChr,
                    std::vector<MapData *> **mapDataByChr, std::vector<FreqData *> **freqDataByChr, int nresample,
                    unsigned long long resampleSeed, int device);
+// TPED input on the device: the same triple as loadTPEDData, the alleles parsed, coded and counted on `device`
+// (garlic_bed_set_rows_tped, 64 MB slabs, .gz included) into an image with an order plane and the census of the parse; the host
+// parses the four leading tokens of every line (tped_lines.hpp) and runs the --resample draws in file order from the census
+// counts.  HapData::bed / ::bedRow instead of ::data; with PHASED the plane is the phase.  false: the device refused a line
+// (an allele longer than one character, a column count that differs from the first line's, \v \f NUL) -- `refusal` names the
+// first such line and its code, nothing is loaded, and the caller reads the file with loadTPEDData, whose leniency is unchanged.
+bool loadTPEDDataOnDevice(const std::string &tpedfile, int &numLoci, int &numInd, std::vector<HapData *> **hapDataByChr,
+                          std::vector<MapData *> **mapDataByChr, std::vector<FreqData *> **freqDataByChr, char TPED_MISSING, bool PHASED,
+                          int nresample, unsigned long long resampleSeed, int device, std::string &refusal);
 // IndData of the kept individuals of a .fam (readFam order): their single family ID is the population name; several among
 // them fail like scanIndData3 ("Found multiple population IDs"), as does an individual ID twice
 IndData *indDataOfKept(const std::vector<FamEntry> &fam, const std::vector<int> &keep, const std::string &famfile);

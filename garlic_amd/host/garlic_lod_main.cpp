@@ -335,8 +335,21 @@ int run(const Args &a, FeatureData *features, BedFile *full, const std::vector<F
                 return 1;
             }
         } else {
-            loadTPEDData(a.tped, numLoci, numInd, &haps, &maps, &freqs, a.tped_missing, a.phased, a.resample,
-                         a.resample_seed);
+            // GARLIC_TPED_DEVICE_READER=1: parsed, coded and counted on the first device.  The host reader is the default: on the
+            // one shape measured (profiles/tped_parse_ab.txt) the load phase through the device reader was the slower one.
+            // GARLIC_TPED_HOST_READER=1, or a file with a line the device refuses, keeps the host reader in any case
+            const char *host_reader = getenv("GARLIC_TPED_HOST_READER"), *device_reader = getenv("GARLIC_TPED_DEVICE_READER");
+            bool on_device = device_reader && *device_reader && strcmp(device_reader, "0") && !(host_reader && *host_reader && strcmp(host_reader, "0"));
+            if (on_device) {
+                std::string refusal;
+                on_device = loadTPEDDataOnDevice(a.tped, numLoci, numInd, &haps, &maps, &freqs, a.tped_missing, a.phased, a.resample,
+                                                 a.resample_seed, devices[0], refusal);
+                if (!on_device) std::cerr << "TPED device reader: " << refusal << "; reading the file again with the host reader\n";
+                else std::cerr << "TPED parsed on device " << devices[0] << "\n";
+            }
+            if (!on_device)
+                loadTPEDData(a.tped, numLoci, numInd, &haps, &maps, &freqs, a.tped_missing, a.phased, a.resample,
+                             a.resample_seed);
             if (a.resample > 0) std::cerr << "Allele frequencies resampled: " << a.resample << "\n";   // garlic-main.cpp:91
             if (a.cache != "none") {
                 writeGenotypeCache(a.cache, haps, maps, freqs);

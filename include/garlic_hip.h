@@ -67,7 +67,7 @@ extern "C" {
  *    garlic_bed_set_order_rows, garlic_bed_get_order_rows, garlic_bed_set_rows_vcf, GARLIC_VCF_*, garlic_panel_set_phase_bed
  *    (likewise); garlic_tgls, garlic_tgls_create, garlic_tgls_set_rows_text, garlic_tgls_set_rows_values, garlic_tgls_get_rows,
  *    garlic_tgls_info, garlic_tgls_count_values, garlic_tgls_get_values, garlic_tgls_destroy, garlic_panel_set_gl_tgls, GARLIC_TGLS_OK / _DEFERRED / _FEW_COLUMNS /
- *    _MANY_COLUMNS / _RAW, GARLIC_ERR_RANGE (likewise) */
+ *    _MANY_COLUMNS / _RAW, GARLIC_ERR_RANGE (likewise); garlic_bed_set_rows_tped, GARLIC_TPED_*, garlic_bed_set_census (likewise) */
 #define GARLIC_HIP_ABI_VERSION 8
 
 #define GARLIC_OK 0
@@ -241,6 +241,46 @@ int garlic_bed_get_order_rows(garlic_bed *bed, int64_t row_begin, int64_t row_co
 #define GARLIC_VCF_MANY_COLUMNS 6
 int garlic_bed_set_rows_vcf(garlic_bed *bed, const char *text, int64_t text_bytes, const int64_t *line_begin,
                             int64_t row_begin, int64_t row_count, int32_t *row_status, int32_t where);
+
+/* Image rows, order rows and the census of rows [row_begin, row_begin + row_count) parsed on the device from TPED text.
+ * text, text_bytes, line_begin and where mean what they mean for garlic_bed_set_rows_vcf.  A line is tokens separated by runs
+ * of blanks (' ', '\t', '\r'; leading and trailing runs, a '\r' before the '\n' and a last line without '\n' are fine): four
+ * leading tokens of any width, which are not read, then 2 * nind_total allele tokens of exactly one byte; any byte value is
+ * an allele (compared as unsigned bytes) except the blanks, '\n', and '\v', '\f', NUL, which are offences anywhere in the
+ * line.  `missing` is the --tped-missing character (a blank or '\n': GARLIC_ERR_INVALID).  The rule is the reference's
+ * (src/garlic-data.cpp:103-141): `one` is the line's first allele that is not `missing`; with A1 := one a genotype becomes
+ * 00 (one one), 10 (exactly one allele is one), 11 (neither is), 01 (either allele missing), order bit = (first allele !=
+ * one) on a non-missing genotype, 0 on a missing one; pad bits zero.  row_allele[r] (host, may be NULL) is `one`, or `missing`
+ * when every allele of the line is missing.  Every letter that is not `one` folds into A2, so such an image cannot tell
+ * `C C` from `C G` when one = A: feature counting (--tped-counting) does not read through it.
+ * The census travels with the image: the parse writes {nalleles, total} per row -- the alleles equal to `one` and the
+ * non-missing alleles, those of half-missing genotypes (`0 G`) included, which no rule could recount from the image -- and
+ * garlic_bed_census returns them with counted[r] = 0 (A1 = one), or 2 when every allele is missing (GARLIC_ERR_STATE until
+ * every row is set); garlic_panel_set_genotypes_bed and garlic_panel_set_phase_bed use it unchanged.
+ * row_status[r] = {code, individual (0-based) of the line's first offence in file order}, {0, 0} for a clean line (host, may
+ * be NULL): GARLIC_TPED_LONG_ALLELE (an allele token longer than one byte), _BAD_BYTE ('\v', '\f', NUL; individual 0 inside the
+ * leading tokens), _FEW_COLUMNS (fewer than 4 + 2 * nind_total tokens; individual = allele tokens found / 2), _MANY_COLUMNS
+ * (more; individual = nind_total).  The call then returns GARLIC_ERR_INVALID and garlic_hip_last_error names the lowest such
+ * row; the clean rows of the call are written and count as set, an offending row's bits are unspecified and it does not.
+ * The sources do not mix on one image: GARLIC_ERR_STATE for this call on an image that has rows from garlic_bed_set_rows,
+ * garlic_bed_set_order_rows, garlic_bed_set_rows_vcf or garlic_bed_extract, and for those calls on an image filled by this
+ * one.  garlic_bed_extract stays refused, as on every image with an order plane.  The staging buffers (slab, line offsets,
+ * status words, row alleles) are kept with the image and reused across a file's slabs. */
+#define GARLIC_TPED_LONG_ALLELE 1
+#define GARLIC_TPED_BAD_BYTE 2
+#define GARLIC_TPED_FEW_COLUMNS 3
+#define GARLIC_TPED_MANY_COLUMNS 4
+int garlic_bed_set_rows_tped(garlic_bed *bed, const char *text, int64_t text_bytes, const int64_t *line_begin,
+                             int64_t row_begin, int64_t row_count, uint8_t missing,
+                             uint8_t *row_allele /* host [row_count], may be NULL */,
+                             int32_t *row_status /* host [row_count][2], may be NULL */, int32_t where);
+/* Gives a fully set image the census its source computed, in place of the one the image rule would compute: counts[r] =
+ * {nalleles, total}, counted[r] = 0 (A1), 1 (A2), 2 (none); host or device arrays.  This is how a TPED image reaches a second
+ * device: rows through garlic_bed_set_rows, plane through garlic_bed_set_order_rows, census through this call.
+ * GARLIC_ERR_STATE when a row is not set; GARLIC_ERR_INVALID for a counted outside 0..2, negative counts or nalleles > total.
+ * Setting rows or order rows afterwards discards the supplied census, exactly as it discards a computed one. */
+int garlic_bed_set_census(garlic_bed *bed, const int32_t *counts /* [nrows][2] */, const uint8_t *counted /* [nrows] */,
+                          int32_t where);
 
 /* GenoLikeData::data (src/garlic-data.h:91): per-genotype error probabilities, already converted
  * as readTGLSData does (src/garlic-data.cpp:1557-1576); same addressing as genotypes.  Any doubles.
