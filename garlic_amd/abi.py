@@ -26,6 +26,7 @@ LD_SUM_PLAIN, LD_SUM_FLAT, LD_SUM_COL, LD_SUM_TILED = 0, 1, 2, 3
 TGLS_DICTIONARY, TGLS_CONTINUOUS, TGLS_DICTIONARY16 = 1, 2, 3   # garlic_panel_tgls_mode
 # GARLIC_TGLS_*: what garlic_tgls_set_rows_text answers per row; TGLS_RAW: gl_type of garlic_tgls_get_rows without conversion
 TGLS_OK, TGLS_DEFERRED, TGLS_FEW_COLUMNS, TGLS_MANY_COLUMNS, TGLS_RAW = 0, 1, 2, 3, -1
+TGLS_VCF_NO_KEY, TGLS_VCF_NO_VALUE = 4, 5   # garlic_tgls_set_rows_vcf's own
 GL_GQ, GL_GL, GL_PL = 0, 1, 2
 MISSING = -9999.0
 
@@ -56,7 +57,7 @@ SYMBOLS = [
     "garlic_bed_set_order_rows", "garlic_bed_get_order_rows", "garlic_bed_set_rows_vcf", "garlic_panel_set_phase_bed",
     "garlic_bed_set_rows_tped", "garlic_bed_set_census",
     "garlic_tgls_create", "garlic_tgls_set_rows_text", "garlic_tgls_set_rows_values", "garlic_tgls_get_rows", "garlic_tgls_info",
-    "garlic_tgls_get_values", "garlic_tgls_count_values",
+    "garlic_tgls_get_values", "garlic_tgls_count_values", "garlic_tgls_set_rows_vcf", "garlic_device_upload",
     "garlic_tgls_destroy", "garlic_panel_set_gl_tgls",
     "garlic_feed_kde", "garlic_lod_kde", "garlic_feed_kde_info", "garlic_feed_kde_times",
     "garlic_gmm_fit", "garlic_gmm_fit_info",
@@ -261,6 +262,8 @@ def lib():
     L.garlic_bed_set_census.argtypes = [_vp, _vp, _vp, C.c_int32]
     L.garlic_tgls_create.argtypes = [_vp, C.c_int64, C.c_int32, _i32p, C.c_int32, C.POINTER(_vp)]
     L.garlic_tgls_set_rows_text.argtypes = [_vp, _vp, C.c_int64, _i64p, C.c_int64, C.c_int64, _vp, C.c_int32]
+    L.garlic_tgls_set_rows_vcf.argtypes = [_vp, _vp, C.c_int64, _i64p, C.c_int64, C.c_int64, C.c_char_p, _f64p, _vp, C.c_int32]
+    L.garlic_device_upload.argtypes = [_vp, _vp, _vp, C.c_int64]
     L.garlic_tgls_set_rows_values.argtypes = [_vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32]
     L.garlic_tgls_get_rows.argtypes = [_vp, C.c_int32, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_int32]
     L.garlic_tgls_info.argtypes = [_vp, _i32p, _i64p, _i64p]
@@ -931,6 +934,30 @@ class Tgls:
         status = np.zeros((lb.shape[0] - 1, 2), dtype=np.int32)
         rc = lib().garlic_tgls_set_rows_text(self.handle, _vp(ptr), int(text_bytes), _ptr(lb, _i64p), row_begin, lb.shape[0] - 1,
                                              _vp(status.ctypes.data), where)
+        err = None
+        if rc != OK:
+            err = GarlicError(rc, lib().garlic_hip_last_error().decode())
+            if rc != ERR_INVALID or not (status[:, 0] >= TGLS_FEW_COLUMNS).any():
+                raise err
+        return status, err
+
+    def set_rows_vcf(self, text, line_begin, key, missing_raw=None, row_begin=0, text_bytes=None, where=HOST):
+        """The same rows from the data lines of a VCF (garlic_tgls_set_rows_vcf): the FORMAT subfield `key` (str or bytes) of
+        every sample column.  missing_raw: the raw value a called genotype without a value takes (None: such a line is
+        refused).  text, line_begin, the return value and the errors as for set_rows_text."""
+        lb = np.ascontiguousarray(line_begin, dtype=np.int64)
+        assert lb.ndim == 1 and lb.shape[0] >= 2
+        if where == HOST:
+            buf = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else np.asarray(text)
+            assert buf.dtype == np.uint8 and buf.ndim == 1 and (buf.shape[0] <= 1 or buf.strides[0] == 1)
+            ptr, text_bytes = buf.ctypes.data, buf.shape[0] if text_bytes is None else text_bytes
+        else:
+            ptr = int(text)
+        status = np.zeros((lb.shape[0] - 1, 2), dtype=np.int32)
+        miss = None if missing_raw is None else C.byref(C.c_double(float(missing_raw)))
+        rc = lib().garlic_tgls_set_rows_vcf(self.handle, _vp(ptr), int(text_bytes), _ptr(lb, _i64p), row_begin, lb.shape[0] - 1,
+                                            key.encode() if isinstance(key, str) else bytes(key),
+                                            None if miss is None else C.cast(miss, _f64p), _vp(status.ctypes.data), where)
         err = None
         if rc != OK:
             err = GarlicError(rc, lib().garlic_hip_last_error().decode())

@@ -33,6 +33,7 @@
 #include "vcf_kernels.hpp"
 #include "tped_kernels.hpp"
 #include "tgls_kernels.hpp"
+#include "vcf_gl_kernels.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -3719,13 +3720,21 @@ static int tgls_encode_rows(garlic_tgls *t, const double *d_raw, int64_t ld, con
 
 static const char *tgls_offence_name(int code)
 {
-    return code == TGLS_FEW_COLUMNS ? "too few sample columns" : code == TGLS_MANY_COLUMNS ? "too many sample columns" : "a deferred token";
+    switch (code) {
+    case TGLS_FEW_COLUMNS: return "too few sample columns";
+    case TGLS_MANY_COLUMNS: return "too many sample columns";
+    case TGLS_VCF_NO_KEY: return "FORMAT does not name the key";
+    case TGLS_VCF_NO_VALUE: return "a called genotype without a value and no missing value given, at sample column";
+    }
+    return "a deferred token";
 }
 
-int garlic_tgls_set_rows_text(garlic_tgls *t, const char *text, int64_t text_bytes, const int64_t *line_begin, int64_t row_begin,
-                              int64_t row_count, int32_t *row_status, int32_t where)
+// What garlic_tgls_set_rows_text and garlic_tgls_set_rows_vcf share: the slab and its offsets onto the device, `parse` (the
+// launch of the door's kernel: device text -> t->raw and t->status), the encode, the rows' bookkeeping and the refusal.
+static int tgls_set_rows_parsed(garlic_tgls *t, const char *what, const char *text, int64_t text_bytes, const int64_t *line_begin,
+                                int64_t row_begin, int64_t row_count, int32_t *row_status, int32_t where,
+                                const std::function<void(const uint8_t *, hipStream_t)> &parse)
 {
-    if (!t || !text || !line_begin) return fail(GARLIC_ERR_INVALID, "tgls, text and line_begin are required");
     if (text_bytes < 1) return fail(GARLIC_ERR_INVALID, "text_bytes %lld: the slab is empty", (long long)text_bytes);
     int rc;
     if ((rc = tgls_check_rows(t, row_begin, row_count, where))) return rc;
@@ -3745,8 +3754,7 @@ int garlic_tgls_set_rows_text(garlic_tgls *t, const char *text, int64_t text_byt
         (rc = t->raw.reserve((size_t)(row_count * t->n_kept))))
         return rc;
     HIP_TRY(hipMemcpyAsync(t->lines.p, line_begin, sizeof(int64_t) * (size_t)(row_count + 1), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(tgls_parse_kernel, dim3((unsigned)row_count), dim3(256), 0, s, d_text, text_bytes, t->lines.p, t->ncols,
-                       t->d_col_dest.p, t->raw.p, (int64_t)t->n_kept, t->status.p);
+    parse(d_text, s);
     HIP_TRY(hipGetLastError());
     std::vector<int32_t> status((size_t)(2 * row_count));
     HIP_TRY(hipMemcpyAsync(status.data(), t->status.p, sizeof(int32_t) * status.size(), hipMemcpyDeviceToHost, s));
@@ -3761,9 +3769,41 @@ int garlic_tgls_set_rows_text(garlic_tgls *t, const char *text, int64_t text_byt
         else if (bad < 0) bad = r;                          // its codes are unspecified: the row keeps the state it had
     }
     if (bad >= 0)
-        return fail(GARLIC_ERR_INVALID, "TGLS row %lld (line %lld of the call): %s (%d)", (long long)(row_begin + bad), (long long)bad,
+        return fail(GARLIC_ERR_INVALID, "%s row %lld (line %lld of the call): %s (%d)", what, (long long)(row_begin + bad), (long long)bad,
                     tgls_offence_name(status[(size_t)(2 * bad)]), status[(size_t)(2 * bad + 1)]);
     return GARLIC_OK;
+}
+
+int garlic_tgls_set_rows_text(garlic_tgls *t, const char *text, int64_t text_bytes, const int64_t *line_begin, int64_t row_begin,
+                              int64_t row_count, int32_t *row_status, int32_t where)
+{
+    if (!t || !text || !line_begin) return fail(GARLIC_ERR_INVALID, "tgls, text and line_begin are required");
+    return tgls_set_rows_parsed(t, "TGLS", text, text_bytes, line_begin, row_begin, row_count, row_status, where,
+                                [&](const uint8_t *d_text, hipStream_t s) {
+        hipLaunchKernelGGL(tgls_parse_kernel, dim3((unsigned)row_count), dim3(256), 0, s, d_text, text_bytes, t->lines.p, t->ncols,
+                           t->d_col_dest.p, t->raw.p, (int64_t)t->n_kept, t->status.p);
+    });
+}
+
+int garlic_tgls_set_rows_vcf(garlic_tgls *t, const char *text, int64_t text_bytes, const int64_t *line_begin, int64_t row_begin,
+                             int64_t row_count, const char *key, const double *missing_raw, int32_t *row_status, int32_t where)
+{
+    if (!t || !text || !line_begin || !key) return fail(GARLIC_ERR_INVALID, "tgls, text, line_begin and key are required");
+    const size_t key_len = strnlen(key, VGL_KEY_MAX + 1);
+    bool key_ok = key_len >= 1 && key_len <= (size_t)VGL_KEY_MAX && strcmp(key, "GT") != 0;
+    for (size_t i = 0; key_ok && i < key_len; i++) {
+        const char c = key[i];
+        key_ok = (c >= 'A' && c <= 'Z') || (c >= 'a' && c <= 'z') || (c >= '0' && c <= '9') || c == '_' || c == '.';
+    }
+    if (!key_ok) return fail(GARLIC_ERR_INVALID, "key must be 1 to %d bytes of [A-Za-z0-9_.] and not GT", VGL_KEY_MAX);
+    uint64_t kw[2] = {0, 0};
+    memcpy(kw, key, key_len);
+    return tgls_set_rows_parsed(t, "VCF likelihood", text, text_bytes, line_begin, row_begin, row_count, row_status, where,
+                                [&](const uint8_t *d_text, hipStream_t s) {
+        hipLaunchKernelGGL(tgls_vcf_parse_kernel, dim3((unsigned)row_count), dim3(256), 0, s, d_text, text_bytes, t->lines.p, t->ncols,
+                           t->d_col_dest.p, kw[0], kw[1], (int32_t)key_len, missing_raw ? *missing_raw : 0.0, missing_raw ? 1 : 0,
+                           t->raw.p, (int64_t)t->n_kept, t->status.p);
+    });
 }
 
 int garlic_tgls_set_rows_values(garlic_tgls *t, const double *raw, int64_t ld, int64_t row_begin, int64_t row_count, int32_t where)
@@ -6272,6 +6312,18 @@ int garlic_device_free(garlic_ctx *ctx, void *ptr)
     int rc;
     if ((rc = set_device(ctx))) return rc;
     return score_free(ctx, ptr);
+}
+
+int garlic_device_upload(garlic_ctx *ctx, void *dst, const void *src, int64_t bytes)
+{
+    if (!ctx || !dst || !src) return fail(GARLIC_ERR_INVALID, "context, dst and src are required");
+    if (bytes < 0) return fail(GARLIC_ERR_INVALID, "bytes %lld is negative", (long long)bytes);
+    int rc;
+    if ((rc = set_device(ctx))) return rc;
+    if (!bytes) return GARLIC_OK;
+    HIP_TRY(hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return GARLIC_OK;
 }
 
 int garlic_device_trim(garlic_ctx *ctx)

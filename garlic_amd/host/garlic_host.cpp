@@ -17,6 +17,7 @@
 #include <cstdio>
 #include <cstring>
 #include <fstream>
+#include <functional>
 #include <iostream>
 #include <sstream>
 #include <random>
@@ -687,9 +688,25 @@ void loadBedData(const std::string &bedfile, const std::string &bimfile, const s
     loadBedFile(b, numLoci, numInd, hapDataByChr, mapDataByChr, freqDataByChr, nresample, resampleSeed, device);
 }
 
+static void closeTglsFile(TglsFile *f);
+static bool vcfGlSlab(const TglsFile *f, garlic_tgls *obj, const void *d_text, const char *h_text, int64_t text_bytes,
+                      const std::vector<int64_t> &lb, const std::vector<int64_t> &ends, const std::vector<int64_t> &number, long long row);
+
+// the loader's slab of text on the devices that parse it: one buffer per likelihood object, freed with the scope
+struct VcfDeviceSlabs {
+    struct One { garlic_ctx *ctx; garlic_tgls *obj; void *text; };
+    std::vector<One> on;
+    void release()
+    {
+        for (One &o : on) garlic_device_free(o.ctx, o.text);
+        on.clear();
+    }
+    ~VcfDeviceSlabs() { release(); }
+};
+
 void loadVcfData(const std::string &vcffile, bool phased, bool snpsOnly, std::vector<std::string> &samples, int &numLoci, int &numInd,
                  std::vector<HapData *> **hapDataByChr, std::vector<MapData *> **mapDataByChr, std::vector<FreqData *> **freqDataByChr,
-                 int nresample, unsigned long long resampleSeed, int device)
+                 int nresample, unsigned long long resampleSeed, int device, VcfGlRequest *gl)
 {
     std::unique_ptr<BedFile, void (*)(BedFile *)> b(new BedFile, closeBedFile);
     b->path = vcffile;
@@ -740,19 +757,55 @@ void loadVcfData(const std::string &vcffile, bool phased, bool snpsOnly, std::ve
     garlic_bed *bed = nullptr;
     check(garlic_bed_create((garlic_ctx *)b->images[slot].ctx, b->nrows, b->nind, &bed), "garlic_bed_create");
     b->images[slot].bed = bed;
+    // the likelihoods from the same slabs: one object of every sample's column per distinct device, and a buffer there that
+    // the slab is uploaded to once; on the loader's own device the genotype parse reads that buffer too
+    std::unique_ptr<TglsFile, void (*)(TglsFile *)> glFile(nullptr, closeTglsFile);
+    VcfDeviceSlabs slabs;          // (behind glFile: its buffers go before the contexts they came from)
+    if (gl) {
+        gl->file = nullptr;
+        gl->overflow = false;
+        if (gl->glType != "GQ" && gl->glType != "GL" && gl->glType != "PL") fail("Must choose GQ/GL/PL for genotype likelihood format");
+        glFile.reset(new TglsFile);
+        glFile->path = vcffile;
+        glFile->glType = gl->glType == "GQ" ? GARLIC_GL_GQ : gl->glType == "GL" ? GARLIC_GL_GL : GARLIC_GL_PL;
+        glFile->fileInd = b->nind;
+        for (int i = 0; i < b->nind; i++) glFile->cols.push_back(i);
+        glFile->nrows = b->nrows;
+        glFile->vcfKey = gl->key;
+        glFile->vcfHasMissing = gl->hasMissing;
+        glFile->vcfMissing = gl->missing;
+        glFile->vcfSnpsOnly = snpsOnly;
+        glFile->vcfSamples = samples;
+        std::vector<int> devs{device};
+        for (int d : gl->devices)
+            if (std::find(devs.begin(), devs.end(), d) == devs.end()) devs.push_back(d);
+        for (int d : devs) {
+            glFile->objects.push_back({d, 0, b->nind, nullptr, nullptr});
+            garlic_ctx *ctx = nullptr;
+            check(garlic_ctx_create(d, nullptr, &ctx), "garlic_ctx_create");
+            glFile->objects.back().ctx = ctx;
+            garlic_tgls *obj = nullptr;
+            check(garlic_tgls_create(ctx, b->nrows, b->nind, glFile->cols.data(), b->nind, &obj), "garlic_tgls_create");
+            glFile->objects.back().tgls = obj;
+            void *text = nullptr;
+            check(garlic_device_alloc(ctx, (int64_t)SLAB + 16, &text), "garlic_device_alloc");      // (the last piece lies inside)
+            slabs.on.push_back({ctx, obj, text});
+        }
+    }
     {
         vcf::Reader rd;
         if (!rd.open(vcffile, SLAB)) fail(rd.error);
         vcf::SlabLines cut;
         size_t used = 0, data_line = 0;
         long long row = 0;
-        std::vector<int64_t> lb, number;
+        std::vector<int64_t> lb, number, ends;
         std::vector<int32_t> status;
         do {
             if (!rd.next(used)) fail(vcffile + ": " + rd.error);
             used = cut.take(rd.slab.data(), rd.have, rd.eof);
             lb.clear();
             number.clear();
+            ends.clear();
             int64_t last_end = 0;
             for (size_t k = 0; k < cut.begin.size(); k++) {
                 if (rd.slab[(size_t)cut.begin[k]] == '#') continue;
@@ -760,6 +813,7 @@ void loadVcfData(const std::string &vcffile, bool phased, bool snpsOnly, std::ve
                 if (!kept[data_line++]) continue;
                 lb.push_back(cut.begin[k]);
                 number.push_back(cut.number[k]);
+                ends.push_back(cut.end[k]);
                 last_end = cut.end[k];
             }
             if (lb.empty()) continue;
@@ -767,7 +821,12 @@ void loadVcfData(const std::string &vcffile, bool phased, bool snpsOnly, std::ve
             if (row + n > b->nrows) fail(vcffile + " changed while it was read");
             lb.push_back(last_end);
             status.assign((size_t)(2 * n), 0);
-            const int rc = garlic_bed_set_rows_vcf(bed, rd.slab.data(), (int64_t)rd.have, lb.data(), row, n, status.data(), GARLIC_HOST);
+            // one upload per device; the first buffer stands on the image's device and serves both parses
+            for (auto &o : slabs.on) check(garlic_device_upload(o.ctx, o.text, rd.slab.data(), (int64_t)rd.have), "garlic_device_upload");
+            const int rc = slabs.on.empty()
+                               ? garlic_bed_set_rows_vcf(bed, rd.slab.data(), (int64_t)rd.have, lb.data(), row, n, status.data(), GARLIC_HOST)
+                               : garlic_bed_set_rows_vcf(bed, (const char *)slabs.on[0].text, (int64_t)rd.have, lb.data(), row, n, status.data(),
+                                                         GARLIC_DEVICE);
             if (rc == GARLIC_ERR_INVALID) {
                 for (int64_t r = 0; r < n; r++)
                     if (status[(size_t)(2 * r)]) {
@@ -777,10 +836,20 @@ void loadVcfData(const std::string &vcffile, bool phased, bool snpsOnly, std::ve
                     }
             }
             check(rc, "garlic_bed_set_rows_vcf");
+            for (size_t k = 0; k < slabs.on.size(); k++)
+                if (!vcfGlSlab(glFile.get(), slabs.on[k].obj, slabs.on[k].text, rd.slab.data(), (int64_t)rd.have, lb, ends, number, row)) {
+                    // the 65,537th distinct raw value: the objects are of no use; the genotypes go on from host text
+                    slabs.release();
+                    glFile.reset();
+                    gl->overflow = true;
+                    break;
+                }
             row += n;
         } while (!rd.eof || used < rd.have);
         if (row != b->nrows) fail(vcffile + " changed while it was read");
     }
+    slabs.release();
+    if (gl && !gl->overflow) gl->file = glFile.release();
     // the host's copies, fetched once: genotypeAt, the phase readers, the genotype cache, and the source of further devices' images
     b->own_rows.resize((size_t)b->nrows * b->row_bytes);
     b->own_order.resize((size_t)b->nrows * b->order_row_bytes);
@@ -1018,16 +1087,14 @@ IndData *readIndData3(const std::string &filename, int numInd)
     return d;
 }
 
-std::vector<GenoLikeData *> *readTGLSData(const std::string &filename, int /*expectedLoci*/, int expectedInd,
-                                          std::vector<MapData *> *maps, const std::string &GL_TYPE, bool compact,
-                                          const std::vector<int> *cols, int fileInd)
+// readTGLSData behind the text: nextRow(vals) brings the next locus' raw values, one per kept individual; the conversion and
+// the forms (compact: codes that widen at the 257th and the 65,537th value) are what every host reader of likelihoods shares
+static std::vector<GenoLikeData *> *readGLRows(int expectedInd, std::vector<MapData *> *maps, const std::string &GL_TYPE, bool compact,
+                                               const std::function<void(double *)> &nextRow)
 {
-    if (cols && (int)cols->size() != expectedInd) fail("readTGLSData: one column per kept individual is needed");
-    std::vector<double> raw(cols ? (size_t)fileInd : 0);
     if (GL_TYPE != "GQ" && GL_TYPE != "GL" && GL_TYPE != "PL") fail("Must choose GQ/GL/PL for genotype likelihood format");
-    LineReader in(filename);
     auto *out = new std::vector<GenoLikeData *>;
-    std::string line, junk;
+    std::vector<double> vals((size_t)expectedInd);
     for (auto m : *maps) {
         GenoLikeData *d;
         // compact: one byte per genotype and a table of the distinct converted values, in the order they are first seen;
@@ -1042,21 +1109,14 @@ std::vector<GenoLikeData *> *readTGLSData(const std::string &filename, int /*exp
         }
         out->push_back(d);
         for (int l = 0; l < m->nloci; l++) {
-            if (!in.next(line)) fail("too few lines in " + filename);
-            const int num = countFields(line);
-            if (num != (cols ? fileInd : expectedInd) + 4) fail("Incorrect number of columns in tgls file: " + std::to_string(num));
-            std::stringstream ss(line);
-            ss >> junk >> junk >> junk >> junk;
-            for (double &v : raw) ss >> v;      // --keep: the whole line, then the kept columns
+            nextRow(vals.data());
             if (compact && width == 1) d->codes[l] = new unsigned char[expectedInd];
             else if (compact && width == 2) d->codes16[l] = new unsigned short[expectedInd];
             else if (compact) d->data[l] = new double[expectedInd];
             uint64_t last_bits = 0;
             int last_code = -1;
             for (int i = 0; i < expectedInd; i++) {
-                double gl;
-                if (cols) gl = raw[(size_t)(*cols)[(size_t)i]];
-                else ss >> gl;
+                double gl = vals[(size_t)i];
                 // garlic-data.cpp:1557-1576, operation for operation
                 if (GL_TYPE == "GQ") { gl /= (-10.0); gl = (gl > -10) ? gl : -10; gl = pow(10, gl); }
                 else if (GL_TYPE == "GL") { gl = (gl > -10) ? gl : -10; gl = 1 - pow(10, gl); }
@@ -1123,6 +1183,28 @@ std::vector<GenoLikeData *> *readTGLSData(const std::string &filename, int /*exp
     return out;
 }
 
+std::vector<GenoLikeData *> *readTGLSData(const std::string &filename, int /*expectedLoci*/, int expectedInd,
+                                          std::vector<MapData *> *maps, const std::string &GL_TYPE, bool compact,
+                                          const std::vector<int> *cols, int fileInd)
+{
+    if (cols && (int)cols->size() != expectedInd) fail("readTGLSData: one column per kept individual is needed");
+    std::vector<double> raw(cols ? (size_t)fileInd : 0);
+    LineReader in(filename);
+    std::string line, junk;
+    return readGLRows(expectedInd, maps, GL_TYPE, compact, [&](double *vals) {
+        if (!in.next(line)) fail("too few lines in " + filename);
+        const int num = countFields(line);
+        if (num != (cols ? fileInd : expectedInd) + 4) fail("Incorrect number of columns in tgls file: " + std::to_string(num));
+        std::stringstream ss(line);
+        ss >> junk >> junk >> junk >> junk;
+        for (double &v : raw) ss >> v;      // --keep: the whole line, then the kept columns
+        for (int i = 0; i < expectedInd; i++) {
+            if (cols) vals[i] = raw[(size_t)(*cols)[(size_t)i]];
+            else ss >> vals[i];
+        }
+    });
+}
+
 // ---- the same file through the device (garlic_tgls): slabs of text up, rows of codes there, nothing per genotype here
 static void closeTglsFile(TglsFile *f)
 {
@@ -1139,6 +1221,7 @@ static void closeTglsFile(TglsFile *f)
 // garlic_tgls_set_rows_values.  false: the 65,537th distinct raw value.
 static bool fillTglsObject(const TglsFile *f, garlic_tgls *obj, const std::vector<int> &objCols)
 {
+    if (!f->vcfKey.empty()) fail(f->path + ": no likelihood object on this device (loadVcfData fills one per device it is told of)");
     vcf::Reader rd;
     if (!rd.open(f->path, (size_t)64 << 20)) fail(rd.error);
     vcf::SlabLines cut;
@@ -1184,6 +1267,50 @@ static bool fillTglsObject(const TglsFile *f, garlic_tgls *obj, const std::vecto
     return true;
 }
 
+[[noreturn]] static void refuseVcfLine(const TglsFile *f, int64_t line, int col, const std::string &why)
+{
+    fail("line " + std::to_string(line) + " of " + f->path +
+         (col >= 0 ? ", sample " + std::to_string(col + 1) + (col < (int)f->vcfSamples.size() ? " (" + f->vcfSamples[(size_t)col] + ")" : std::string()) : std::string()) +
+         ": " + why);
+}
+
+// One slab of loadVcfData into obj: rows [row, row + n) from the lines lb (n + 1 offsets; ends: where each stops; number: its
+// line in the file) of the text that stands on obj's device at d_text and in host memory at h_text.  A row the device defers
+// is parsed by vcf::parseGlValues; a refused line ends the run.  false: the 65,537th distinct raw value.
+static bool vcfGlSlab(const TglsFile *f, garlic_tgls *obj, const void *d_text, const char *h_text, int64_t text_bytes,
+                      const std::vector<int64_t> &lb, const std::vector<int64_t> &ends, const std::vector<int64_t> &number, long long row)
+{
+    const int64_t n = (int64_t)lb.size() - 1;
+    const double *missing = f->vcfHasMissing ? &f->vcfMissing : nullptr;
+    std::vector<int32_t> status((size_t)(2 * n), 0);
+    int rc = garlic_tgls_set_rows_vcf(obj, (const char *)d_text, text_bytes, lb.data(), row, n, f->vcfKey.c_str(), missing, status.data(),
+                                      GARLIC_DEVICE);
+    if (rc == GARLIC_ERR_RANGE) return false;
+    if (rc == GARLIC_ERR_INVALID)
+        for (int64_t r = 0; r < n; r++) {
+            const int code = status[(size_t)(2 * r)], col = status[(size_t)(2 * r + 1)];
+            if (code == GARLIC_TGLS_VCF_NO_KEY) refuseVcfLine(f, number[(size_t)r], -1, "FORMAT does not name " + f->vcfKey);
+            else if (code == GARLIC_TGLS_VCF_NO_VALUE)
+                refuseVcfLine(f, number[(size_t)r], col, "a called genotype without " + f->vcfKey + " (--vcf-gl-missing X gives such genotypes the raw value X)");
+            else if (code >= GARLIC_TGLS_FEW_COLUMNS)
+                refuseVcfLine(f, number[(size_t)r], -1, code == GARLIC_TGLS_FEW_COLUMNS ? "too few sample columns" : "too many sample columns");
+        }
+    check(rc, "garlic_tgls_set_rows_vcf");
+    std::vector<double> vals((size_t)f->fileInd);
+    std::string err;
+    for (int64_t r = 0; r < n; r++) {
+        if (status[(size_t)(2 * r)] != GARLIC_TGLS_DEFERRED) continue;
+        int sample = -1;
+        if (!vcf::parseGlValues(h_text + lb[(size_t)r], (size_t)(ends[(size_t)r] - lb[(size_t)r]), f->vcfKey, f->fileInd, nullptr, vals.size(), missing,
+                                vals.data(), sample, err))
+            refuseVcfLine(f, number[(size_t)r], sample, err);
+        rc = garlic_tgls_set_rows_values(obj, vals.data(), (int64_t)vals.size(), row + r, 1, GARLIC_HOST);
+        if (rc == GARLIC_ERR_RANGE) return false;
+        check(rc, "garlic_tgls_set_rows_values");
+    }
+    return true;
+}
+
 // the object that serves individuals [ind_begin, +nind) on `device`, and where its columns begin in it
 static garlic_tgls *tglsObjectOn(TglsFile *f, int device, int ind_begin, int nind, int64_t &ind_offset)
 {
@@ -1206,6 +1333,9 @@ static garlic_tgls *tglsObjectOn(TglsFile *f, int device, int ind_begin, int nin
     return obj;
 }
 
+static std::vector<GenoLikeData *> *tglsFileOnDevice(std::unique_ptr<TglsFile, void (*)(TglsFile *)> &f, int expectedInd,
+                                                     std::vector<MapData *> *maps, int device);
+
 std::vector<GenoLikeData *> *loadTGLSFile(const std::string &filename, int expectedInd, std::vector<MapData *> *maps,
                                           const std::string &GL_TYPE, const std::vector<int> *cols, int fileInd, int device)
 {
@@ -1219,6 +1349,71 @@ std::vector<GenoLikeData *> *loadTGLSFile(const std::string &filename, int expec
     else for (int i = 0; i < expectedInd; i++) f->cols.push_back(i);
     for (int c : f->cols)
         if (c < 0 || c >= f->fileInd) fail("loadTGLSFile: a kept column outside the file's columns");
+    auto *out = tglsFileOnDevice(f, expectedInd, maps, device);
+    if (!out) std::cerr << filename << " holds more than 65,536 distinct values: read by the host reader instead\n";
+    return out;
+}
+
+static std::vector<GenoLikeData *> *glDataOfTglsFile(std::unique_ptr<TglsFile, void (*)(TglsFile *)> &f, int expectedInd,
+                                                     std::vector<MapData *> *maps);
+
+// The likelihoods loadVcfData left in `gl`: the GenoLikeData of its device objects, or -- a field of more than 65,536 distinct
+// raw values -- the file read once more on the host, line by line through vcf::parseGlValues, into readTGLSData's compact forms
+std::vector<GenoLikeData *> *vcfGlData(VcfGlRequest &gl, const std::string &vcffile, bool snpsOnly, const std::vector<std::string> &samples,
+                                       std::vector<MapData *> *maps)
+{
+    const int nind = (int)samples.size();
+    if (!gl.overflow) {
+        if (!gl.file) fail("vcfGlData: loadVcfData has not run with this request");
+        std::unique_ptr<TglsFile, void (*)(TglsFile *)> f(gl.file, closeTglsFile);
+        gl.file = nullptr;
+        long long rows = 0;
+        for (auto m : *maps) rows += m->nloci;
+        if (rows != f->nrows) fail("vcfGlData: the maps do not hold the loci that were read");
+        return glDataOfTglsFile(f, nind, maps);
+    }
+    std::cerr << vcffile << ": " << gl.key << " holds more than 65,536 distinct values: read by the host reader instead\n";
+    TglsFile names;
+    names.path = vcffile;
+    names.vcfSamples = samples;
+    vcf::Reader rd;
+    if (!rd.open(vcffile, (size_t)64 << 20)) fail(rd.error);
+    vcf::SlabLines cut;
+    size_t used = 0, at = 0;
+    bool first = true;
+    std::string err;
+    const double *missing = gl.hasMissing ? &gl.missing : nullptr;
+    return readGLRows(nind, maps, gl.glType, /*compact=*/true, [&](double *vals) {
+        for (;;) {
+            if (first || at >= cut.begin.size()) {
+                if (!first && rd.eof && used >= rd.have) fail(vcffile + " changed while it was read");
+                if (!rd.next(first ? 0 : used)) fail(vcffile + ": " + rd.error);
+                used = cut.take(rd.slab.data(), rd.have, rd.eof);
+                if (!rd.eof && used == 0 && rd.have == rd.slab.size()) fail(vcffile + ": a line longer than 64 MB");
+                first = false;
+                at = 0;
+                continue;
+            }
+            const size_t k = at++;
+            const char *line = rd.slab.data() + cut.begin[k];
+            const size_t len = (size_t)(cut.end[k] - cut.begin[k]);
+            if (line[0] == '#') continue;
+            vcf::Site site;
+            const vcf::LineKind kind = vcf::parseFixed(line, len, site, err);
+            if (kind == vcf::LINE_BAD || (kind == vcf::LINE_NOT_SNP && !snpsOnly)) refuseVcfLine(&names, cut.number[k], -1, err);
+            if (kind != vcf::LINE_SNP) continue;
+            int sample = -1;
+            if (!vcf::parseGlValues(line, len, gl.key, nind, nullptr, (size_t)nind, missing, vals, sample, err))
+                refuseVcfLine(&names, cut.number[k], sample, err);
+            return;
+        }
+    });
+}
+
+// f filled on `device` and one GenoLikeData per chromosome that points into it; NULL (f closed): a 65,537th distinct raw value
+static std::vector<GenoLikeData *> *tglsFileOnDevice(std::unique_ptr<TglsFile, void (*)(TglsFile *)> &f, int expectedInd,
+                                                     std::vector<MapData *> *maps, int device)
+{
     for (auto m : *maps) f->nrows += m->nloci;
     f->objects.push_back({device, 0, expectedInd, nullptr, nullptr});
     garlic_ctx *ctx = nullptr;
@@ -1227,10 +1422,15 @@ std::vector<GenoLikeData *> *loadTGLSFile(const std::string &filename, int expec
     garlic_tgls *obj = nullptr;
     check(garlic_tgls_create(ctx, f->nrows, f->fileInd, f->cols.data(), expectedInd, &obj), "garlic_tgls_create");
     f->objects.back().tgls = obj;
-    if (!fillTglsObject(f.get(), obj, f->cols)) {
-        std::cerr << filename << " holds more than 65,536 distinct values: read by the host reader instead\n";
-        return nullptr;
-    }
+    if (!fillTglsObject(f.get(), obj, f->cols)) return nullptr;
+    return glDataOfTglsFile(f, expectedInd, maps);
+}
+
+// one GenoLikeData per chromosome that points into f, whose first object is filled; f is theirs from here on
+static std::vector<GenoLikeData *> *glDataOfTglsFile(std::unique_ptr<TglsFile, void (*)(TglsFile *)> &f, int expectedInd,
+                                                     std::vector<MapData *> *maps)
+{
+    garlic_tgls *obj = (garlic_tgls *)f->objects.front().tgls;
     auto *out = new std::vector<GenoLikeData *>;
     long long row = 0;
     try {

@@ -149,6 +149,20 @@ struct TglsFile {
     int refs = 0;                 // GenoLikeData that point here
     struct Object { int device, ind_begin, nind; void *ctx, *tgls; };
     std::vector<Object> objects;
+    // a VCF as the source (loadVcfData with a VcfGlRequest): the FORMAT key read, the raw value of a called genotype without one (if any),
+    // whether lines that are no biallelic SNPs are left out, and the header's sample names for messages
+    std::string vcfKey;
+    bool vcfHasMissing = false, vcfSnpsOnly = false;
+    double vcfMissing = 0;
+    std::vector<std::string> vcfSamples;
+};
+struct VcfGlRequest {
+    std::string key, glType;      // the FORMAT key; GQ / GL / PL
+    bool hasMissing = false;      // `missing` is the raw value of a called genotype without one (else such a line ends the run)
+    double missing = 0;
+    std::vector<int> devices;     // every device that will hold a shard (loadVcfData's own is added if it is not among them)
+    TglsFile *file = nullptr;     // out: the filled objects, one per distinct device; vcfGlData takes it over
+    bool overflow = false;        // out: a 65,537th distinct raw value was met; no objects, vcfGlData reads on the host
 };
 struct GenoLikeData {      // src/garlic-data.h:89-95
     double **data;         // [locus][ind]: per-genotype error probability
@@ -268,9 +282,12 @@ void releaseBedFile(BedFile *b);          // one reference less; the last one cl
 // the header and the nine fixed columns (vcf_lines.hpp).  tfam "": family 0 and the header's names; otherwise its count must
 // match.  samples: the header's names.  snpsOnly: lines whose REF / ALT is not one base are left out and counted
 // (BedFile::skipped_non_snp) instead of ending the run.
+// gl: the scalar FORMAT field gl->key of every sample column as likelihoods, from the same slabs (garlic_tgls_set_rows_vcf):
+// the file is read once, and each slab goes once to every device of gl->devices -- into a device buffer of the loader's that
+// both parse calls read with where = GARLIC_DEVICE -- where an object of all the samples' columns is filled.
 void loadVcfData(const std::string &vcffile, bool phased, bool snpsOnly, std::vector<std::string> &samples, int &numLoci, int &numInd,
                  std::vector<HapData *> **hapDataByChr, std::vector<MapData *> **mapDataByChr, std::vector<FreqData *> **freqDataByChr,
-                 int nresample, unsigned long long resampleSeed, int device);
+                 int nresample, unsigned long long resampleSeed, int device, VcfGlRequest *gl = nullptr);
 void loadBedSubset(BedFile *full, const std::vector<int> &keep, int &numLoci, int &numInd, std::vector<HapData *> **hapDataByChr,
                    std::vector<MapData *> **mapDataByChr, std::vector<FreqData *> **freqDataByChr, int nresample,
                    unsigned long long resampleSeed, int device);
@@ -300,6 +317,12 @@ IndData *readIndData3(const std::string &filename, int numInd);                 
 // for readTGLSData.  NULL when the file holds more than 65,536 distinct raw values: it needs readTGLSData (one line on stderr).
 std::vector<GenoLikeData *> *loadTGLSFile(const std::string &filename, int expectedInd, std::vector<MapData *> *maps,
                                           const std::string &GL_TYPE, const std::vector<int> *cols, int fileInd, int device);
+// The likelihoods of a VCF's own lines, asked of loadVcfData through its last argument (VcfGlRequest, above): vcfGlData
+// turns what the load left in the request into the GenoLikeData per chromosome -- rows of the device objects, or, past 65,536
+// distinct raw values, the file read once more on the host (vcf::parseGlValues per line; one line on stderr) into the forms of
+// readTGLSData(compact = true).  A refused line ends the run naming file, line, sample and reason.
+std::vector<GenoLikeData *> *vcfGlData(VcfGlRequest &gl, const std::string &vcffile, bool snpsOnly, const std::vector<std::string> &samples,
+                                       std::vector<MapData *> *maps);
 std::vector<GenoLikeData *> *readTGLSData(const std::string &filename, int expectedLoci, int expectedInd,
                                           std::vector<MapData *> *mapDataByChr,
                                           const std::string &GL_TYPE,

@@ -24,6 +24,7 @@
 #include "garlic_host.hpp"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -54,6 +55,9 @@ struct Args {
     int resample = 0;              // src/garlic-cli.cpp:62-64: resamples for the allele frequencies
     unsigned long long resample_seed = 0;   // extension: 0 = time-seeded like the reference
     unsigned long long ld_seed = 0; // extension: 0 = time-seeded like the reference
+    std::string vcf_gl_field;      // extension: with --vcf, the likelihoods are this scalar FORMAT field of the VCF's own lines
+    bool have_vcf_gl_missing = false;
+    double vcf_gl_missing = 0;     // --vcf-gl-missing: the raw value of a called genotype without the field
     double tgls_term_gb = 0;       // extension: garlic_panel_set_tgls_term_budget in GB (0 whole matrix or none, -1 automatic)
     unsigned long long kde_seed = 0; // extension: the --kde-subsample draw, 0 = time-seeded like the reference
     double mu = 1e-9, overlap_frac = 0.25;
@@ -106,6 +110,10 @@ struct Args {
                  "          are parsed on the device, --phased is allowed; without --tfam the family is 0 and the IDs are the header's;\n"
                  "          a REF / ALT that is not one base ends the run, or is left out and counted under --vcf-biallelic-snps-only;\n"
                  "          not with --keep / --pops / --bfile / --bed / --bim / --fam / --tped)\n"
+                 "         [--vcf F[.gz] --vcf-gl-field KEY --gl-type GQ|GL|PL [--vcf-gl-missing X]]   (instead of --tgls: the likelihoods\n"
+                 "          are the scalar FORMAT field KEY of the VCF's own sample columns, parsed and coded on the device; a missing\n"
+                 "          genotype needs no value; a called genotype without one ends the run, or takes the raw value X; under\n"
+                 "          --gl-type GQ a raw 0 makes every LOD term of the genotype 0, the neutral X; lists (GL / PL triples) are refused)\n"
                  "         (--bfile / --bed --bim --fam: PLINK SNP-major .bed input, read on the device; not with --tped / --tfam /\n"
                  "          --phased; --genotype-cache F is then written from the .bed, never read)\n"
                  "         [--keep F]   (with PLINK input: the run is that of a file set holding only the individuals of F, a PLINK keep\n"
@@ -129,6 +137,14 @@ Args parse(int argc, char **argv)
         else if (f == "--bfile") a.bfile = val();
         else if (f == "--vcf") a.vcf = val();
         else if (f == "--vcf-biallelic-snps-only") a.vcf_snps_only = true;
+        else if (f == "--vcf-gl-field") a.vcf_gl_field = val();
+        else if (f == "--vcf-gl-missing") {
+            const std::string v = val();
+            char *stop = nullptr;
+            a.vcf_gl_missing = strtod(v.c_str(), &stop);
+            if (v.empty() || *stop || !std::isfinite(a.vcf_gl_missing)) usage("--vcf-gl-missing takes one finite number");
+            a.have_vcf_gl_missing = true;
+        }
         else if (f == "--bed") a.bed = val();
         else if (f == "--bim") a.bim = val();
         else if (f == "--fam") a.fam = val();
@@ -222,6 +238,14 @@ Args parse(int argc, char **argv)
     }
     // validators of src/garlic-cli.cpp:240-462 that concern Phase I
     if (a.vcf_snps_only && a.vcf.empty()) usage("--vcf-biallelic-snps-only needs --vcf");
+    if (!a.vcf_gl_field.empty() && a.vcf.empty()) usage("--vcf-gl-field reads a FORMAT field of the --vcf file and needs --vcf");
+    if (!a.vcf_gl_field.empty() && a.tgls != "none") usage("--vcf-gl-field and --tgls exclude each other (the likelihoods come from one of them)");
+    if (a.have_vcf_gl_missing && a.vcf_gl_field.empty()) usage("--vcf-gl-missing needs --vcf-gl-field");
+    if (!a.vcf_gl_field.empty()) {
+        bool ok = a.vcf_gl_field.size() <= 16 && a.vcf_gl_field != "GT";
+        for (char c : a.vcf_gl_field) ok = ok && (isalnum((unsigned char)c) || c == '_' || c == '.');
+        if (!ok) usage("--vcf-gl-field takes a FORMAT key of 1 to 16 characters of [A-Za-z0-9_.] other than GT");
+    }
     if (!a.vcf.empty()) {
         if (!a.bfile.empty() || !a.bed.empty() || !a.bim.empty() || !a.fam.empty() || !a.tped.empty())
             usage("--vcf and --bfile / --bed / --bim / --fam / --tped exclude each other");
@@ -244,9 +268,9 @@ Args parse(int argc, char **argv)
     if (!a.pops.empty() && a.freq_file != "none") usage("--pops with --freq-file: one frequency file cannot serve several populations");
     if (!a.pops.empty() && a.cache != "none") usage("--pops with --genotype-cache: one cache file cannot hold several populations");
     if (a.build == "none" && a.centromere == "none") usage("must provide --build or --centromere (garlic-cli.cpp:285-291)");
-    if ((a.error <= 0 || a.error >= 1) && a.tgls == "none")
+    if ((a.error <= 0 || a.error >= 1) && a.tgls == "none" && a.vcf_gl_field.empty())
         usage("Genotype error rate must be > 0 and < 1, or a TGLS file must be provided.");
-    if (a.tgls != "none" && a.gl_type != "GQ" && a.gl_type != "GL" && a.gl_type != "PL")
+    if ((a.tgls != "none" || !a.vcf_gl_field.empty()) && a.gl_type != "GQ" && a.gl_type != "GL" && a.gl_type != "PL")
         usage("Must choose GQ/GL/PL for genotype likelihood format.");
     if (a.winsize <= 1 && a.winsize_multi.empty()) usage("SNP window size must be > 1.");
     for (int w : a.winsize_multi) if (w <= 1) usage("SNP window sizes must be > 1.");
@@ -307,10 +331,17 @@ int run(const Args &a, FeatureData *features, BedFile *full, const std::vector<F
             for (int d = 0; d < a.gpus; d++) devices.push_back(d);
         FILE *probe = a.cache == "none" || !a.bed.empty() || !a.vcf.empty() ? nullptr : fopen(a.cache.c_str(), "rb");
         std::vector<std::string> vcf_samples;
+        VcfGlRequest vcf_gl;
         if (keep) ind = indDataOfKept(*fam, *keep, a.fam);      // the single-population check, over the kept individuals
         if (!a.vcf.empty()) {   // VCF input: parsed on the first device; the cache, if asked for, is written from the image
+            // --vcf-gl-field: the likelihoods from the same slabs, on every device that will hold a shard
+            vcf_gl.key = a.vcf_gl_field;
+            vcf_gl.glType = a.gl_type;
+            vcf_gl.hasMissing = a.have_vcf_gl_missing;
+            vcf_gl.missing = a.vcf_gl_missing;
+            vcf_gl.devices = devices;
             loadVcfData(a.vcf, a.phased, a.vcf_snps_only, vcf_samples, numLoci, numInd, &haps, &maps, &freqs, a.resample, a.resample_seed,
-                        devices[0]);
+                        devices[0], a.vcf_gl_field.empty() ? nullptr : &vcf_gl);
             if (a.vcf_snps_only)
                 std::cerr << "Left out " << haps->at(0)->bed->skipped_non_snp << " lines of " << a.vcf << " that are no biallelic SNPs\n";
             if (a.resample > 0) std::cerr << "Allele frequencies resampled: " << a.resample << "\n";
@@ -371,8 +402,18 @@ int run(const Args &a, FeatureData *features, BedFile *full, const std::vector<F
         }
         std::cerr << "Loaded " << numLoci << " loci x " << numInd << " individuals (" << maps->size() << " chromosomes)\n";
 
-        const bool USE_GL = a.tgls != "none";
-        if (USE_GL) {
+        const bool USE_GL = a.tgls != "none" || !a.vcf_gl_field.empty();
+        if (USE_GL && !a.vcf_gl_field.empty()) {
+            // the VCF's own FORMAT field, parsed and coded by loadVcfData from the slabs of the genotype parse
+            gls = vcfGlData(vcf_gl, a.vcf, a.vcf_snps_only, vcf_samples, maps);
+            std::cerr << "Genotype likelihoods (" << a.gl_type << ", FORMAT field " << a.vcf_gl_field << " of " << a.vcf << "):";
+            for (size_t c = 0; c < gls->size(); c++)
+            {
+                std::cerr << (c ? ", " : " ") << maps->at(c)->chr << " as " << likelihoodForm(gls->at(c));
+                if (!gls->at(c)->data) std::cerr << " (" << gls->at(c)->nvalues << " values)";
+            }
+            std::cerr << "\n";
+        } else if (USE_GL) {
             // rows in pre-filter TPED order; under --keep the kept individuals' columns of the whole .fam's
             // parsed and coded on the first device, no likelihood on the host; GARLIC_TGLS_HOST_READER=1, or a file of more
             // than 65,536 distinct values, keeps the host reader

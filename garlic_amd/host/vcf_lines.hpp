@@ -13,6 +13,7 @@
 #pragma once
 #include <zlib.h>
 
+#include <cmath>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
@@ -86,6 +87,77 @@ inline LineKind parseFixed(const char *line, size_t len, Site &site, std::string
     site.a1 = col[3][0];
     site.a2 = col[4][0];
     return LINE_SNP;
+}
+
+// The scalar FORMAT subfield `key` of a data line's sample columns, as the device defines it (csrc/vcf_gl_kernels.hpp): the
+// line ends at its first \r or \n; k = the index of the first key of FORMAT (column 8) that equals `key`; sample j is column
+// 9 + j and its value is subfield k of the column.  A column without subfield k, an empty one and "." are missing: on a column
+// that starts with '.' the value is *missing, or 0 without one; on any other column *missing, or the line is refused.  Every
+// other subfield goes through strtod, which must consume all of it and give a finite value: a list (0,12,40), trailing junk, nan
+// and inf are refused (hex floats pass, as strtod reads them).
+// out[i] = the value of sample cols[i], i < ncols (cols == NULL: sample i).  false: err says why and `sample` names the
+// sample column (-1: the line as a whole).
+inline bool parseGlValues(const char *line, size_t len, const std::string &key, int nsamples, const int *cols, size_t ncols,
+                          const double *missing, double *out, int &sample, std::string &err)
+{
+    sample = -1;
+    for (size_t i = 0; i < len; i++)
+        if (line[i] == '\r' || line[i] == '\n') { len = i; break; }
+    std::vector<size_t> begin;           // of every column; begin[c + 1] - 1 is where column c ends
+    begin.push_back(0);
+    for (size_t i = 0; i < len; i++)
+        if (line[i] == '\t') begin.push_back(i + 1);
+    begin.push_back(len + 1);
+    const size_t ncolumns = begin.size() - 1;
+    const size_t found = ncolumns > 9 ? ncolumns - 9 : 0;
+    if (found < (size_t)nsamples || ncolumns < 10) { err = "too few sample columns (" + std::to_string(found) + ")"; return false; }
+    if (found > (size_t)nsamples) { err = "too many sample columns (" + std::to_string(found) + ")"; return false; }
+    // subfield `want` of [b, e): false when the column has fewer colons
+    auto subfield = [&](size_t b, size_t e, long want, size_t &sb, size_t &se) {
+        long at = 0;
+        sb = b;
+        for (size_t i = b; i <= e; i++) {
+            if (i < e && line[i] != ':') continue;
+            if (at == want) { se = i; return true; }
+            at++;
+            sb = i + 1;
+        }
+        return false;
+    };
+    long k = -1;
+    {
+        const size_t b = begin[8], e = begin[9] - 1;
+        size_t sb, se;
+        for (long at = 0; subfield(b, e, at, sb, se); at++)
+            if (se - sb == key.size() && memcmp(line + sb, key.data(), key.size()) == 0) { k = at; break; }
+    }
+    if (k < 0) { err = "FORMAT '" + std::string(line + begin[8], begin[9] - 1 - begin[8]) + "' does not name " + key; return false; }
+    for (size_t i = 0; i < ncols; i++) {
+        const int j = cols ? cols[i] : (int)i;
+        const size_t b = begin[(size_t)(9 + j)], e = begin[(size_t)(10 + j)] - 1;
+        size_t sb = b, se = b;
+        const bool have = subfield(b, e, k, sb, se);
+        if (!have || se == sb || (se - sb == 1 && line[sb] == '.')) {
+            if (missing) out[i] = *missing;
+            else if (e > b && line[b] == '.') out[i] = 0.0;
+            else { sample = j; err = "a called genotype without " + key + " (--vcf-gl-missing X gives such genotypes the raw value X)"; return false; }
+            continue;
+        }
+        const std::string tok(line + sb, se - sb);
+        char *stop = nullptr;
+        out[i] = strtod(tok.c_str(), &stop);
+        if (stop == tok.c_str() || *stop || tok.size() != strlen(tok.c_str())) {
+            sample = j;
+            err = key + " '" + tok + "' is no single number" + (tok.find(',') != std::string::npos ? " (a list: only scalar FORMAT fields are read)" : "");
+            return false;
+        }
+        if (!std::isfinite(out[i])) {      // nan, inf, 1e999: strtod reads them, no likelihood is one
+            sample = j;
+            err = key + " '" + tok + "' is no finite number";
+            return false;
+        }
+    }
+    return true;
 }
 
 // One slab of text cut into lines.  take(slab, n, last): the lines that are complete in [slab, slab + n) -- all of them when

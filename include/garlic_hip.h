@@ -67,7 +67,8 @@ extern "C" {
  *    garlic_bed_set_order_rows, garlic_bed_get_order_rows, garlic_bed_set_rows_vcf, GARLIC_VCF_*, garlic_panel_set_phase_bed
  *    (likewise); garlic_tgls, garlic_tgls_create, garlic_tgls_set_rows_text, garlic_tgls_set_rows_values, garlic_tgls_get_rows,
  *    garlic_tgls_info, garlic_tgls_count_values, garlic_tgls_get_values, garlic_tgls_destroy, garlic_panel_set_gl_tgls, GARLIC_TGLS_OK / _DEFERRED / _FEW_COLUMNS /
- *    _MANY_COLUMNS / _RAW, GARLIC_ERR_RANGE (likewise); garlic_bed_set_rows_tped, GARLIC_TPED_*, garlic_bed_set_census (likewise) */
+ *    _MANY_COLUMNS / _RAW, GARLIC_ERR_RANGE (likewise); garlic_bed_set_rows_tped, GARLIC_TPED_*, garlic_bed_set_census (likewise);
+ *    garlic_tgls_set_rows_vcf, GARLIC_TGLS_VCF_NO_KEY / _NO_VALUE, garlic_device_upload (likewise) */
 #define GARLIC_HIP_ABI_VERSION 8
 
 #define GARLIC_OK 0
@@ -363,6 +364,21 @@ int garlic_panel_tgls_mode(garlic_panel *panel, int32_t *mode, int32_t *terms_by
  *     built: it needs the conversion's pow on the device, and GQ / GL / PL columns do not print that many values.)
  *     The object keeps its staging buffers (the largest host slab + 16 bytes, 8 bytes per kept genotype of the largest call,
  *     the line offsets and status pairs) until garlic_tgls_destroy, so that a file's slabs reuse them.
+ * garlic_tgls_set_rows_vcf    the same rows from the data lines of a VCF (csrc/vcf_gl_kernels.hpp): one scalar FORMAT subfield
+ *     per sample.  A line ends at its first '\r' or '\n' (or as above).  Eight tab-separated columns are skipped; column 8
+ *     is FORMAT, keys joined by ':', and k is the index of the first of them that equals `key` bytewise -- per line, FORMAT
+ *     may change.  key: 1 to 16 bytes of [A-Za-z0-9_.], not "GT" (GARLIC_ERR_INVALID).  Sample j is column 9 + j; its value
+ *     is the bytes between the column's k-th ':' and the next ':' or the column's end, and goes through the same number
+ *     grammar with the same limits.  The value is MISSING when the column has fewer than k colons (trailing subfields may be
+ *     dropped), when the subfield is empty and when it is exactly ".".  A missing value of a column that starts with '.' (a
+ *     missing genotype, whose score never reads the value) becomes *missing_raw, or 0.0 when missing_raw is NULL; on any
+ *     other column it becomes *missing_raw, or is an offence when missing_raw is NULL.  Columns that are not kept are counted
+ *     and nothing else.  Status codes: _DEFERRED, _FEW_COLUMNS and _MANY_COLUMNS as above (a list such as 0,12,40, nan, a
+ *     token of more than 32 bytes and an integer above 2^53 are deferred), and
+ *       GARLIC_TGLS_VCF_NO_KEY     FORMAT does not name the key; column = 0;
+ *       GARLIC_TGLS_VCF_NO_VALUE   a called genotype without a value and no missing_raw; column = the sample column.
+ *     Either makes the call GARLIC_ERR_INVALID as the column counts do.  Behind the parse the call is set_rows_text's --
+ *     staging, encode, dictionary, GARLIC_ERR_RANGE -- and the rows of one object may come from either call.
  * garlic_tgls_set_rows_values the same rows from raw doubles raw[(r - row_begin) * ld + k], k < n_kept in the object's own
  *     column order, ld >= n_kept, host or device.
  * garlic_tgls_get_rows        out[(r - row_begin) * ld + k] (host or device) = the row's values: GARLIC_TGLS_RAW as parsed, or
@@ -383,6 +399,8 @@ int garlic_panel_tgls_mode(garlic_panel *panel, int32_t *mode, int32_t *terms_by
 #define GARLIC_TGLS_DEFERRED 1
 #define GARLIC_TGLS_FEW_COLUMNS 2
 #define GARLIC_TGLS_MANY_COLUMNS 3
+#define GARLIC_TGLS_VCF_NO_KEY 4
+#define GARLIC_TGLS_VCF_NO_VALUE 5
 #define GARLIC_TGLS_RAW (-1) /* gl_type of garlic_tgls_get_rows: no conversion (GARLIC_GL_GQ is 0) */
 typedef struct garlic_tgls garlic_tgls;
 int garlic_tgls_create(garlic_ctx *ctx, int64_t nrows, int32_t ncols_total, const int32_t *col_idx /* NULL = all */,
@@ -390,6 +408,9 @@ int garlic_tgls_create(garlic_ctx *ctx, int64_t nrows, int32_t ncols_total, cons
 int garlic_tgls_set_rows_text(garlic_tgls *tgls, const char *text, int64_t text_bytes, const int64_t *line_begin /* row_count + 1 */,
                               int64_t row_begin, int64_t row_count, int32_t *row_status /* [row_count][2], may be NULL */,
                               int32_t where);
+int garlic_tgls_set_rows_vcf(garlic_tgls *tgls, const char *text, int64_t text_bytes, const int64_t *line_begin /* row_count + 1 */,
+                             int64_t row_begin, int64_t row_count, const char *key, const double *missing_raw /* NULL: refuse */,
+                             int32_t *row_status /* [row_count][2], may be NULL */, int32_t where);
 int garlic_tgls_set_rows_values(garlic_tgls *tgls, const double *raw, int64_t ld, int64_t row_begin, int64_t row_count,
                                 int32_t where);
 int garlic_tgls_get_rows(garlic_tgls *tgls, int32_t gl_type, int64_t row_begin, int64_t row_count, double *out, int64_t ld,
@@ -1130,6 +1151,11 @@ int garlic_panel_chain_kind(garlic_panel *panel, int32_t *kind);
  * use. */
 int garlic_device_alloc(garlic_ctx *ctx, int64_t bytes, void **out);
 int garlic_device_free(garlic_ctx *ctx, void *ptr);
+/* bytes from host memory into device memory of the context's device (a buffer of garlic_device_alloc, or any device pointer),
+ * on the context's stream; returns when the copy is done.  For a caller without a HIP runtime of its own that keeps a slab of
+ * text on the device and hands it to several where = GARLIC_DEVICE calls (garlic_bed_set_rows_vcf and
+ * garlic_tgls_set_rows_vcf on one upload). */
+int garlic_device_upload(garlic_ctx *ctx, void *dst, const void *src, int64_t bytes);
 int garlic_device_alloc_stats(garlic_ctx *ctx, int64_t *live_bytes, int64_t *pooled_bytes, int64_t *reserved_bytes);
 int garlic_device_trim(garlic_ctx *ctx);   /* idle pooled buffers give their memory back now (the library does this itself
                                               when one of its own allocations runs out of memory) */

@@ -59,6 +59,9 @@ resident panel: through garlic_panel_set_gl_codes16 where the library has it (2 
 (continuous, 8 B per genotype: --tree for the parent commit).  The first TGLS score call (term pass + chain), warm calls (chain
 alone), their difference as the term pass, the same after a change of frequencies (no re-upload with codes), and the device
 memory in use (profiles/tgls_dict16_ab.txt).
+--modes vcf_gl_parse: garlic_tgls_set_rows_vcf on device-resident VCF text of --snps lines x --inds samples beside
+garlic_tgls_set_rows_text on the twin .tgls text of the same values, each call between stream events, GB/s of text
+(profiles/vcf_gl_parse_ab.txt).
 --tree for the parent commit; GARLIC_LD_PAIR_NO_MFMA=1 for this tree's AND + popcount form (profiles/ld_phased_mfma_ab.txt).
 """
 import argparse
@@ -1168,6 +1171,87 @@ def ld_phased_leg(args):
         panel.release_scratch()
 
 
+def vcf_gl_parse_leg(args):
+    """--modes vcf_gl_parse: garlic_tgls_set_rows_vcf on device-resident VCF text of --snps lines x --inds samples (e.g. 20000
+    x 10000) beside garlic_tgls_set_rows_text on the twin .tgls text of the same GQ values, each call (parse,
+    encode, status) between two events on the context's stream, in slabs of at most 256 MB of VCF text; GB/s of the text
+    each reads.  Columns are `g|g:DP:GQ` with two-digit DP and GQ (10 bytes with the tab; the twin: 3 bytes)."""
+    import torch
+    from garlic_amd import abi
+
+    torch.cuda.set_device(0)
+    dev = torch.device("cuda", 0)
+    nrows, nind = args.snps, args.inds
+    stream = torch.cuda.Stream()
+    ctx = abi.Context(0, stream=stream.cuda_stream)
+    head_v = np.frombuffer(b"1\t1000000\trs0000000\tA\tG\t.\tPASS\t.\tGT:DP:GQ", dtype=np.uint8)
+    head_t = np.frombuffer(b"1 rs0000000 0 1000000", dtype=np.uint8)
+    slab_rows = max(1, min(nrows, (256 << 20) // (len(head_v) + 10 * nind + 1)))
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(11)
+
+    def digits(v):      # two ASCII digits of every value
+        return torch.stack([v // 10 + 48, v % 10 + 48], dim=-1).to(torch.uint8)
+
+    def slab(n):
+        gq = torch.randint(10, 100, (n, nind), generator=gen, device=dev)
+        dp = torch.randint(10, 100, (n, nind), generator=gen, device=dev)
+        gt = torch.randint(0, 2, (n, nind, 2), generator=gen, device=dev)
+        v = torch.empty((n, len(head_v) + 10 * nind + 1), dtype=torch.uint8, device=dev)
+        v[:, :len(head_v)] = torch.from_numpy(head_v.copy()).to(dev)
+        cols = v[:, len(head_v):-1].view(n, nind, 10)
+        cols[:, :, 0] = 9
+        cols[:, :, 1] = (gt[:, :, 0] + 48).to(torch.uint8)
+        cols[:, :, 2] = ord("|")
+        cols[:, :, 3] = (gt[:, :, 1] + 48).to(torch.uint8)
+        cols[:, :, 4] = ord(":")
+        cols[:, :, 5:7] = digits(dp)
+        cols[:, :, 7] = ord(":")
+        cols[:, :, 8:10] = digits(gq)
+        v[:, -1] = 10
+        t = torch.empty((n, len(head_t) + 3 * nind + 1), dtype=torch.uint8, device=dev)
+        t[:, :len(head_t)] = torch.from_numpy(head_t.copy()).to(dev)
+        tc = t[:, len(head_t):-1].view(n, nind, 3)
+        tc[:, :, 0] = 32
+        tc[:, :, 1:3] = digits(gq)
+        t[:, -1] = 10
+        torch.cuda.synchronize()
+        return v, t
+
+    def timed(call):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(stream)
+        call()
+        b.record(stream)
+        b.synchronize()
+        return a.elapsed_time(b)
+
+    ms = {"vcf": 0.0, "tgls": 0.0}
+    nbytes = {"vcf": 0, "tgls": 0}
+    with abi.Tgls(ctx, nrows, nind) as from_vcf, abi.Tgls(ctx, nrows, nind) as from_text:
+        for step in range(args.steps + 1):          # the first round warms both kernels up and is not counted
+            for r0 in range(0, nrows, slab_rows):
+                n = min(slab_rows, nrows - r0)
+                v, t = slab(n)
+                lb_v = np.arange(n + 1, dtype=np.int64) * v.shape[1]
+                lb_t = np.arange(n + 1, dtype=np.int64) * t.shape[1]
+                dv = timed(lambda: from_vcf.set_rows_vcf(v.data_ptr(), lb_v, "GQ", row_begin=r0, text_bytes=v.numel(), where=abi.DEVICE))
+                dt = timed(lambda: from_text.set_rows_text(t.data_ptr(), lb_t, row_begin=r0, text_bytes=t.numel(), where=abi.DEVICE))
+                if step:
+                    ms["vcf"] += dv
+                    ms["tgls"] += dt
+                    nbytes["vcf"] += v.numel()
+                    nbytes["tgls"] += t.numel()
+                if step == 0 and r0 == 0:
+                    assert np.array_equal(from_vcf.get_rows(row_count=2), from_text.get_rows(row_count=2))
+                del v, t
+    print(json.dumps({"mode": "vcf_gl_parse", "lines": nrows, "samples": nind, "rounds": args.steps, "slab_lines": slab_rows,
+                      "vcf_call_ms": ms["vcf"] / args.steps, "vcf_text_gb": nbytes["vcf"] / args.steps / 1e9,
+                      "vcf_gb_per_s": nbytes["vcf"] / 1e6 / ms["vcf"],
+                      "tgls_call_ms": ms["tgls"] / args.steps, "tgls_text_gb": nbytes["tgls"] / args.steps / 1e9,
+                      "tgls_gb_per_s": nbytes["tgls"] / 1e6 / ms["tgls"]}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--snps", type=int, default=200000)
@@ -1217,6 +1301,8 @@ def main():
         return ld_phased_leg(args)
     if args.modes == "tgls_dict16":
         return tgls_dict16_leg(args)
+    if args.modes == "vcf_gl_parse":
+        return vcf_gl_parse_leg(args)
     if args.modes in ("wlod_feed", "tgls_feed"):
         return wlod_feed_leg(args, tgls=args.modes == "tgls_feed")
 
