@@ -29,7 +29,10 @@
 //      slot and the three behind it, so a value of TGLS_TOKEN_MAX bytes that starts behind the slot's last byte is seen whole
 //      (16 + 32 < 64): that is why the walk runs three slots behind the load and why no byte is loaded twice.  Every FORMAT
 //      subfield lies in front of every sample, so k is known wherever a sample needs it;
-//   5. a kept column's double is stored with a plain 8-byte vector store at raw[row][col_dest[j]].
+//   5. a kept column's double is stored with a plain 8-byte vector store at raw[row][col_dest[j]];
+//   6. behind the last pass lane 0 closes the line's last column.  A tab that is the line's last byte starts an empty column
+//      behind it, as for every tab; where that tab is also the last byte of the pass and the line ends by its limit, the
+//      column's first byte lies in a slot that no lane holds, and lane 0 opens and counts it before it closes the line.
 // The first offence of the line is a 64-bit minimum in LDS over (sample column << 3 | code): independent of arrival order.  No
 // global atomics; a staging row is written by one workgroup only.  No switch point: any line length, subfield width and
 // sample count take this one path.
@@ -309,6 +312,16 @@ tgls_vcf_parse_kernel(const uint8_t *__restrict__ text, int64_t text_bytes, cons
         __syncthreads();
         if (last) {
             if (tid == 0) {
+                if (end == INT64_MAX && (s_tab[VGL_PASS_PIECES + VGL_CARRY - 1] >> 15)) {
+                    // the line ends by `limit` behind a tab that is the pass's last byte: the empty column it starts lies in
+                    // a slot no lane holds.  It closes the column in front and is counted here.
+                    const int64_t jf = col - 9;
+                    if (jf >= 0 && jf < ncols && k != VGL_NO_KEY && ccarry < k) missing(jf, dcarry);
+                    col++;
+                    ccarry = dcarry = 0;
+                    if (col - 9 >= ncols) offend(ncols, TGLS_MANY_COLUMNS);
+                    else if (col >= 9 && k == 0) missing(col - 9, 0);
+                }
                 const int64_t jc = col - 9;                   // the line's end closes its last column
                 if (jc >= 0 && jc < ncols && k != VGL_NO_KEY && ccarry < k) missing(jc, dcarry);
                 const int64_t found = col >= 8 ? col - 8 : 0;

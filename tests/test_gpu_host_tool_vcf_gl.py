@@ -94,6 +94,31 @@ def test_field_equals_the_tgls_twin_and_the_tped_twin(tmp_path, twin, gl_twin, m
     hv.same_files(a, c)
 
 
+def test_long_info_in_front_of_format(tmp_path, gl_twin):
+    """INFO of a third of the data lines grown to 1 to 9 KB (colons and the key's letters in it): FORMAT then stands in the
+    first, the second and the third 4 KB pass of the likelihood parse, and the genotype parse reads the same lines.  The same
+    files as from the unpadded file"""
+    rng = np.random.default_rng(31)
+    lines = open(gl_twin + ".vcf").read().split("\n")
+    k, passes = 0, set()
+    for i, ln in enumerate(lines):
+        if not ln or ln.startswith("#"):
+            continue
+        if k % 3 == 0:
+            t = ln.split("\t")
+            n = int(rng.integers(1024, 9 * 1024 + 1))
+            t[7] = ("DP=14;GQ:AF=0.5,GQ;Q=:GQ:;" * (n // 26 + 1))[:n]
+            lines[i] = "\t".join(t)
+            passes.add(lines[i].index("\tGT:") // 4096)
+        k += 1
+    assert passes == {0, 1, 2}
+    path = str(tmp_path / "I.vcf")
+    open(path, "w").write("\n".join(lines))
+    a = hv.run(tmp_path / "padded", ["--vcf", path], *MODES["unweighted"], *field("GQ", "GQ"))
+    b = hv.run(tmp_path / "plain", ["--vcf", gl_twin + ".vcf"], *MODES["unweighted"], *field("GQ", "GQ"))
+    hv.same_files(a, b)
+
+
 def test_gz_phased_and_two_shards(tmp_path, twin, gl_twin):
     with open(gl_twin + ".vcf", "rb") as f, gzip.open(str(tmp_path / "G.vcf.gz"), "wb") as g:
         shutil.copyfileobj(f, g)

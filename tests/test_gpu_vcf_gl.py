@@ -13,33 +13,12 @@ import tgls_cases as tc
 import vcf_cases as vc
 import vcf_gl_cases as vg
 from garlic_amd import abi
+from vcf_gl_cases import feed
 
 pytestmark = pytest.mark.gpu
 
 ROWS = 40
 KEY = b"GQ"
-
-
-class DeviceSlab:
-    """the text at `offset` bytes past a 16-byte aligned device address, with 64 bytes of `poison` on each side"""
-
-    def __init__(self, text, offset, poison):
-        import torch
-        self.buf = torch.full((len(text) + 160,), poison, dtype=torch.uint8, device="cuda")
-        base = self.buf.data_ptr()
-        self.at = (-base) % 16 + 64 + offset
-        self.buf[self.at:self.at + len(text)] = torch.frombuffer(bytearray(text), dtype=torch.uint8).cuda()
-        torch.cuda.synchronize()
-        self.ptr = base + self.at
-        assert self.ptr % 16 == offset
-
-
-def feed(obj, text, lb, where="host", row_begin=0, key=KEY, missing_raw=None):
-    """-> (status, err); where: "host", or "devN" = device text N bytes past an aligned address, poisoned with ':' around"""
-    if where == "host":
-        return obj.set_rows_vcf(text, lb, key, missing_raw=missing_raw, row_begin=row_begin)
-    slab = DeviceSlab(text, int(where[3:]), 0x3A)
-    return obj.set_rows_vcf(slab.ptr, lb, key, missing_raw=missing_raw, row_begin=row_begin, text_bytes=len(text), where=abi.DEVICE)
 
 
 def random_tokens(rng, rows, nind):

@@ -5,6 +5,7 @@ import subprocess
 
 import numpy as np
 
+import vcf_gl_border_cases as bc
 import vcf_gl_cases as vg
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -27,6 +28,16 @@ HAND = [
     (F + b"GT:DP:GQ\t0/0:1:5\n", 2, None, None, (vg.FEW, 1)),
     (F + b"GT:DP:GQ\t0/0:1:5\t0/0:1:5\t0/0:1:5\n", 2, None, None, (vg.MANY, 2)),
     (b"1\t5\n", 2, None, None, (vg.FEW, 0)),
+    # the key first in FORMAT: the value stands on the column's own first byte
+    (F + b"GQ:GT\t5:0/1\t:0/1\n", 2, 3.0, [5.0, 3.0], (0, 0)),
+    (F + b"GQ:GT:DP\t.\t.:3\t8\t.:./.:4\n", 4, None, [0.0, 0.0, 8.0, 0.0], (0, 0)),
+    (F + b"GQ:GT\t\t5:0/1\n", 2, None, None, (vg.NO_VALUE, 0)),
+    (F + b"GQ:GT\t5:0/1\t:0/1\n", 2, None, None, (vg.NO_VALUE, 1)),
+    # a tab as the line's last byte: an empty column behind it
+    (F + b"GT:DP:GQ\t0/0:1:5\t0/0:1:6\t\n", 2, None, None, (vg.MANY, 2)),
+    (F + b"GT:DP:GQ\t0/0:1:5\t0/0:1:6\t", 2, 42.0, None, (vg.MANY, 2)),
+    (F + b"GT:DP:GQ\t0/0:1:5\t", 2, 42.0, [5.0, 42.0], (0, 0)),
+    (F + b"GT:DP:GQ\t0/0:1:5\t\r\n", 2, None, None, (vg.NO_VALUE, 1)),
 ]
 # what the device defers and the host completes, or refuses
 DEFERRED = [
@@ -100,3 +111,23 @@ def test_vcf_gl_lines_unit_under_sanitizers(tmp_path):
     lines = [h[0] for h in HAND[:4]]
     out = run(lines, 2, None, cols=(1, 0, 1))
     assert [o.split()[1:] for o in out] == [["7", "35", "7"], ["7.5", "35", "7.5"], ["10", "35", "10"], ["5", "2", "5"]]
+    # the lines of tests/vcf_gl_border_cases.py, the key first and trailing tabs among them: the host gives the rule's values
+    # wherever the rule gives values (and completes what the device defers), and refuses what the rule refuses
+    # (in late_slab every deferred value stands in a line with a second offence, which the host names instead)
+    for slab, missing, completes in ((bc.key_first_slab(0), None, True), (bc.key_first_slab(3), 99.0, True),
+                                     (bc.carried_slab(2, 0), None, True), (bc.line_end_slab(0), None, True),
+                                     (bc.line_end_slab(1), 99.0, True), (bc.late_slab(0), None, False)):
+        text, lb, marks, nind = slab
+        rows = [text[int(lb[r]):int(lb[r + 1])] for r in range(len(marks))]
+        want, status = vg.parse_slab(text, lb, nind, b"GQ", missing)
+        out = run(rows, nind, missing)
+        assert len(out) == len(rows)
+        for r, o in enumerate(out):
+            o = o.split(" ", 2)
+            if status[r, 0] == vg.OK or (status[r, 0] == vg.DEFERRED and completes):
+                got = np.array([float(v) for v in " ".join(o[1:]).split()])
+                full = np.where(np.isnan(want[r]), 12.5, want[r])           # the one deferred value of these lines
+                assert o[0] == "ok" and np.array_equal(got.view(np.uint64), full.view(np.uint64)), (marks[r], o)
+            else:
+                assert o[0] == "bad", (marks[r], o)
+                assert status[r, 0] == vg.DEFERRED or int(o[1]) == (status[r, 1] if status[r, 0] == vg.NO_VALUE else -1), (marks[r], o)

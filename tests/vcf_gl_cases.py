@@ -161,3 +161,27 @@ def random_lines(rng, rows, nind, tokens, key=b"GQ", eols=(b"\n",), drop=0.1, la
         eol = last_eol if r == rows - 1 else eols[r % len(eols)]
         lines.append(data_line(r, keys, cols, eol))
     return lines
+
+
+# ---- device text (the GPU tests only: torch and the binding are imported where they are used)
+class DeviceSlab:
+    """the text at `offset` bytes past a 16-byte aligned device address, with 64 bytes of `poison` on each side"""
+
+    def __init__(self, text, offset, poison):
+        import torch
+        self.buf = torch.full((len(text) + 160,), poison, dtype=torch.uint8, device="cuda")
+        base = self.buf.data_ptr()
+        self.at = (-base) % 16 + 64 + offset
+        self.buf[self.at:self.at + len(text)] = torch.frombuffer(bytearray(text), dtype=torch.uint8).cuda()
+        torch.cuda.synchronize()
+        self.ptr = base + self.at
+        assert self.ptr % 16 == offset
+
+
+def feed(obj, text, lb, where="host", row_begin=0, key=b"GQ", missing_raw=None, poison=0x3A):
+    """-> (status, err); where: "host", or "devN" = device text N bytes past an aligned address, with `poison` (':') around"""
+    from garlic_amd import abi
+    if where == "host":
+        return obj.set_rows_vcf(text, lb, key, missing_raw=missing_raw, row_begin=row_begin)
+    slab = DeviceSlab(text, int(where[3:]), poison)
+    return obj.set_rows_vcf(slab.ptr, lb, key, missing_raw=missing_raw, row_begin=row_begin, text_bytes=len(text), where=abi.DEVICE)
