@@ -2899,6 +2899,55 @@ int garlic_panel_set_genotypes_2bit(garlic_panel *p, const uint8_t *rows, int64_
     return GARLIC_OK;
 }
 
+// ---- What the text doors share (text_line.hpp): garlic_bed_set_rows_vcf, garlic_bed_set_rows_tped, garlic_tgls_set_rows_text
+// and garlic_tgls_set_rows_vcf take a slab of text and line_begin[row_count + 1] and answer with a status pair per line.
+struct TextStage {
+    DevBuf<uint8_t> text;                                   // staging, kept until the object's destroy: a host slab,
+    DevBuf<int64_t> lines;                                  // its line offsets,
+    DevBuf<int32_t> status;                                 // the status pairs
+};
+
+static int text_rows_check(int64_t text_bytes, const int64_t *line_begin, int64_t row_count)
+{
+    for (int64_t r = 0; r <= row_count; r++)
+        if (line_begin[r] < 0 || line_begin[r] > text_bytes || (r && line_begin[r] < line_begin[r - 1]))
+            return fail(GARLIC_ERR_INVALID, "line_begin[%lld] = %lld: the offsets must ascend inside the slab of %lld bytes", (long long)r,
+                        (long long)line_begin[r], (long long)text_bytes);
+    return GARLIC_OK;
+}
+
+// the slab (uploaded when it is the host's) and its offsets onto the device, room for the status pairs; *d_text: the slab there
+static int text_rows_stage(TextStage &st, const char *text, int64_t text_bytes, const int64_t *line_begin, int64_t row_count,
+                           int32_t where, hipStream_t s, const uint8_t **d_text)
+{
+    int rc;
+    *d_text = reinterpret_cast<const uint8_t *>(text);
+    if (where == GARLIC_HOST) {
+        if ((rc = st.text.reserve((size_t)text_bytes + 16))) return rc;          // (its last piece lies inside the buffer)
+        HIP_TRY(hipMemcpyAsync(st.text.p, text, (size_t)text_bytes, hipMemcpyHostToDevice, s));
+        *d_text = st.text.p;
+    }
+    if ((rc = st.lines.reserve((size_t)row_count + 1)) || (rc = st.status.reserve((size_t)(2 * row_count)))) return rc;
+    HIP_TRY(hipMemcpyAsync(st.lines.p, line_begin, sizeof(int64_t) * (size_t)(row_count + 1), hipMemcpyHostToDevice, s));
+    return GARLIC_OK;
+}
+
+// Behind the door's launch: the status pairs to the host (the stream is idle when this returns) and into row_status.
+// *bad = the first row whose code is above `benign` (0, or the highest code that is no refusal), -1 for none.
+static int text_rows_status(TextStage &st, int64_t row_count, int32_t *row_status, int benign, hipStream_t s,
+                            std::vector<int32_t> &status, int64_t *bad)
+{
+    HIP_TRY(hipGetLastError());
+    status.resize((size_t)(2 * row_count));
+    HIP_TRY(hipMemcpyAsync(status.data(), st.status.p, sizeof(int32_t) * status.size(), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (row_status) memcpy(row_status, status.data(), sizeof(int32_t) * status.size());
+    *bad = -1;
+    for (int64_t r = 0; r < row_count && *bad < 0; r++)
+        if (status[(size_t)(2 * r)] > benign) *bad = r;
+    return GARLIC_OK;
+}
+
 // ---- PLINK .bed rows (bed_kernels.hpp): the image, its census, and the door into a panel
 struct garlic_bed {
     garlic_ctx *ctx = nullptr;
@@ -2915,9 +2964,7 @@ struct garlic_bed {
     int64_t order_row_bytes = 0;                            // (nind + 7) / 8
     DevBuf<uint8_t> d_order;
     bool have_order = false;
-    DevBuf<uint8_t> vcf_text;                               // garlic_bed_set_rows_vcf: a host slab on the device
-    DevBuf<int64_t> vcf_lines;
-    DevBuf<int32_t> vcf_status;
+    TextStage text;                                         // garlic_bed_set_rows_vcf, garlic_bed_set_rows_tped
     // where the rows came from: an image filled by garlic_bed_set_rows_tped carries the census its parse wrote (tped_kernels.hpp),
     // which the image rule cannot recompute, so the two kinds of source do not mix on one image
     enum Source { SOURCE_NONE = 0, SOURCE_ROWS = 1, SOURCE_TPED = 2 };
@@ -3267,35 +3314,20 @@ int garlic_bed_set_rows_vcf(garlic_bed *b, const char *text, int64_t text_bytes,
     if (row_begin < 0 || row_count < 1 || row_begin + row_count > b->nrows)
         return fail(GARLIC_ERR_INVALID, "row range [%lld,+%lld) outside image of %lld rows", (long long)row_begin,
                     (long long)row_count, (long long)b->nrows);
-    for (int64_t r = 0; r <= row_count; r++)
-        if (line_begin[r] < 0 || line_begin[r] > text_bytes || (r && line_begin[r] < line_begin[r - 1]))
-            return fail(GARLIC_ERR_INVALID, "line_begin[%lld] = %lld: the offsets must ascend inside the slab of %lld bytes", (long long)r,
-                        (long long)line_begin[r], (long long)text_bytes);
     int rc;
+    if ((rc = text_rows_check(text_bytes, line_begin, row_count))) return rc;
     if ((rc = bed_claim_source(b, garlic_bed::SOURCE_ROWS, "bed_set_rows_vcf")) || (rc = set_device(b->ctx)) || (rc = bed_ensure_order(b))) return rc;
     hipStream_t s = b->ctx->stream;
     b->census_valid = false;
-    const uint8_t *d_text = reinterpret_cast<const uint8_t *>(text);
-    if (where == GARLIC_HOST) {
-        if ((rc = b->vcf_text.reserve((size_t)text_bytes + 16))) return rc;      // (its last piece lies inside the buffer)
-        HIP_TRY(hipMemcpyAsync(b->vcf_text.p, text, (size_t)text_bytes, hipMemcpyHostToDevice, s));
-        d_text = b->vcf_text.p;
-    }
-    if ((rc = b->vcf_lines.reserve((size_t)row_count + 1)) || (rc = b->vcf_status.reserve((size_t)(2 * row_count)))) return rc;
-    HIP_TRY(hipMemcpyAsync(b->vcf_lines.p, line_begin, sizeof(int64_t) * (size_t)(row_count + 1), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(vcf_parse_kernel, dim3((unsigned)row_count), dim3(256), 0, s, d_text, text_bytes, b->vcf_lines.p, row_begin,
-                       b->nind, b->d_image.p, b->row_bytes, b->d_order.p, b->order_row_bytes, b->vcf_status.p);
-    HIP_TRY(hipGetLastError());
-    std::vector<int32_t> status((size_t)(2 * row_count));
-    HIP_TRY(hipMemcpyAsync(status.data(), b->vcf_status.p, sizeof(int32_t) * status.size(), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (row_status) memcpy(row_status, status.data(), sizeof(int32_t) * status.size());
-    int64_t bad = -1;
+    const uint8_t *d_text;
+    if ((rc = text_rows_stage(b->text, text, text_bytes, line_begin, row_count, where, s, &d_text))) return rc;
+    hipLaunchKernelGGL(vcf_parse_kernel, dim3((unsigned)row_count), dim3(256), 0, s, d_text, text_bytes, b->text.lines.p, row_begin,
+                       b->nind, b->d_image.p, b->row_bytes, b->d_order.p, b->order_row_bytes, b->text.status.p);
+    std::vector<int32_t> status;
+    int64_t bad;
+    if ((rc = text_rows_status(b->text, row_count, row_status, VCF_OK, s, status, &bad))) return rc;
     for (int64_t r = 0; r < row_count; r++) {
-        if (status[(size_t)(2 * r)]) {
-            if (bad < 0) bad = r;
-            continue;                  // its bits are unspecified: the row does not count as set
-        }
+        if (status[(size_t)(2 * r)]) continue;                 // its bits are unspecified: the row does not count as set
         uint64_t &word = b->row_set[(size_t)((row_begin + r) >> 6)];
         const uint64_t bit = 1ull << ((row_begin + r) & 63);
         if (!(word & bit)) { word |= bit; b->n_set++; }
@@ -3329,42 +3361,29 @@ int garlic_bed_set_rows_tped(garlic_bed *b, const char *text, int64_t text_bytes
     if (row_begin < 0 || row_count < 1 || row_begin + row_count > b->nrows)
         return fail(GARLIC_ERR_INVALID, "row range [%lld,+%lld) outside image of %lld rows", (long long)row_begin,
                     (long long)row_count, (long long)b->nrows);
-    for (int64_t r = 0; r <= row_count; r++)
-        if (line_begin[r] < 0 || line_begin[r] > text_bytes || (r && line_begin[r] < line_begin[r - 1]))
-            return fail(GARLIC_ERR_INVALID, "line_begin[%lld] = %lld: the offsets must ascend inside the slab of %lld bytes", (long long)r,
-                        (long long)line_begin[r], (long long)text_bytes);
     int rc;
+    if ((rc = text_rows_check(text_bytes, line_begin, row_count))) return rc;
     if ((rc = bed_claim_source(b, garlic_bed::SOURCE_TPED, "bed_set_rows_tped")) || (rc = set_device(b->ctx)) || (rc = bed_ensure_order(b)))
         return rc;
     hipStream_t s = b->ctx->stream;
     b->census_valid = false;
-    const uint8_t *d_text = reinterpret_cast<const uint8_t *>(text);
-    if (where == GARLIC_HOST) {
-        if ((rc = b->vcf_text.reserve((size_t)text_bytes + 16))) return rc;      // (its last piece lies inside the buffer)
-        HIP_TRY(hipMemcpyAsync(b->vcf_text.p, text, (size_t)text_bytes, hipMemcpyHostToDevice, s));
-        d_text = b->vcf_text.p;
-    }
-    if ((rc = b->vcf_lines.reserve((size_t)row_count + 1)) || (rc = b->vcf_status.reserve((size_t)(2 * row_count))) ||
+    const uint8_t *d_text;
+    if ((rc = text_rows_stage(b->text, text, text_bytes, line_begin, row_count, where, s, &d_text)) ||
         (rc = b->tped_allele.reserve((size_t)row_count)))
         return rc;
-    HIP_TRY(hipMemcpyAsync(b->vcf_lines.p, line_begin, sizeof(int64_t) * (size_t)(row_count + 1), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(tped_parse_kernel, dim3((unsigned)row_count), dim3(256), 0, s, d_text, text_bytes, b->vcf_lines.p, row_begin, b->nind,
+    hipLaunchKernelGGL(tped_parse_kernel, dim3((unsigned)row_count), dim3(256), 0, s, d_text, text_bytes, b->text.lines.p, row_begin, b->nind,
                        (uint32_t)missing, b->d_image.p, b->row_bytes, b->d_order.p, b->order_row_bytes, b->d_counts.p, b->d_counted.p,
-                       b->tped_allele.p, b->vcf_status.p);
-    HIP_TRY(hipGetLastError());
-    std::vector<int32_t> status((size_t)(2 * row_count));
+                       b->tped_allele.p, b->text.status.p);
+    std::vector<int32_t> status;
     std::vector<uint8_t> one((size_t)row_count);
-    HIP_TRY(hipMemcpyAsync(status.data(), b->vcf_status.p, sizeof(int32_t) * status.size(), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(one.data(), b->tped_allele.p, one.size(), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (row_status) memcpy(row_status, status.data(), sizeof(int32_t) * status.size());
+    HIP_TRY(hipMemcpyAsync(one.data(), b->tped_allele.p, one.size(), hipMemcpyDeviceToHost, s));      // (waited for with the status)
+    int64_t bad;
+    if ((rc = text_rows_status(b->text, row_count, row_status, TPED_OK, s, status, &bad))) return rc;
     if (row_allele) memcpy(row_allele, one.data(), one.size());
-    int64_t bad = -1;
     for (int64_t r = 0; r < row_count; r++) {
         uint64_t &word = b->row_set[(size_t)((row_begin + r) >> 6)];
         const uint64_t bit = 1ull << ((row_begin + r) & 63);
         if (status[(size_t)(2 * r)]) {
-            if (bad < 0) bad = r;
             if (word & bit) { word &= ~bit; b->n_set--; }      // its bits and its census are unspecified now
             continue;
         }
@@ -3596,9 +3615,7 @@ struct garlic_tgls {
     DevBuf<int32_t> d_flags;                                // 3 words (tgls_encode_kernel)
     std::vector<uint64_t> row_set, row_deferred;            // one bit per row
     int64_t n_set = 0, n_deferred = 0;
-    DevBuf<uint8_t> text;                                   // staging, kept until destroy: a host slab,
-    DevBuf<int64_t> lines;                                  // its line offsets,
-    DevBuf<int32_t> status;                                 // the status pairs,
+    TextStage text;                                         // garlic_tgls_set_rows_text, garlic_tgls_set_rows_vcf
     DevBuf<double> raw;                                     // the parsed doubles [row_count][n_kept] (and the rows of set_rows_values),
     DevBuf<double> d_table, d_out;                          // and what get_rows decodes with and into
 };
@@ -3730,7 +3747,7 @@ static const char *tgls_offence_name(int code)
 }
 
 // What garlic_tgls_set_rows_text and garlic_tgls_set_rows_vcf share: the slab and its offsets onto the device, `parse` (the
-// launch of the door's kernel: device text -> t->raw and t->status), the encode, the rows' bookkeeping and the refusal.
+// launch of the door's kernel: device text -> t->raw and t->text.status), the encode, the rows' bookkeeping and the refusal.
 static int tgls_set_rows_parsed(garlic_tgls *t, const char *what, const char *text, int64_t text_bytes, const int64_t *line_begin,
                                 int64_t row_begin, int64_t row_count, int32_t *row_status, int32_t where,
                                 const std::function<void(const uint8_t *, hipStream_t)> &parse)
@@ -3738,35 +3755,21 @@ static int tgls_set_rows_parsed(garlic_tgls *t, const char *what, const char *te
     if (text_bytes < 1) return fail(GARLIC_ERR_INVALID, "text_bytes %lld: the slab is empty", (long long)text_bytes);
     int rc;
     if ((rc = tgls_check_rows(t, row_begin, row_count, where))) return rc;
-    for (int64_t r = 0; r <= row_count; r++)
-        if (line_begin[r] < 0 || line_begin[r] > text_bytes || (r && line_begin[r] < line_begin[r - 1]))
-            return fail(GARLIC_ERR_INVALID, "line_begin[%lld] = %lld: the offsets must ascend inside the slab of %lld bytes", (long long)r,
-                        (long long)line_begin[r], (long long)text_bytes);
-    if ((rc = set_device(t->ctx))) return rc;
+    if ((rc = text_rows_check(text_bytes, line_begin, row_count)) || (rc = set_device(t->ctx))) return rc;
     hipStream_t s = t->ctx->stream;
-    const uint8_t *d_text = reinterpret_cast<const uint8_t *>(text);
-    if (where == GARLIC_HOST) {
-        if ((rc = t->text.reserve((size_t)text_bytes + 16))) return rc;          // (its last piece lies inside the buffer)
-        HIP_TRY(hipMemcpyAsync(t->text.p, text, (size_t)text_bytes, hipMemcpyHostToDevice, s));
-        d_text = t->text.p;
-    }
-    if ((rc = t->lines.reserve((size_t)row_count + 1)) || (rc = t->status.reserve((size_t)(2 * row_count))) ||
+    const uint8_t *d_text;
+    if ((rc = text_rows_stage(t->text, text, text_bytes, line_begin, row_count, where, s, &d_text)) ||
         (rc = t->raw.reserve((size_t)(row_count * t->n_kept))))
         return rc;
-    HIP_TRY(hipMemcpyAsync(t->lines.p, line_begin, sizeof(int64_t) * (size_t)(row_count + 1), hipMemcpyHostToDevice, s));
     parse(d_text, s);
-    HIP_TRY(hipGetLastError());
-    std::vector<int32_t> status((size_t)(2 * row_count));
-    HIP_TRY(hipMemcpyAsync(status.data(), t->status.p, sizeof(int32_t) * status.size(), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (row_status) memcpy(row_status, status.data(), sizeof(int32_t) * status.size());
-    if ((rc = tgls_encode_rows(t, t->raw.p, t->n_kept, t->status.p, t->d_k_src.p, row_begin, row_count))) return rc;
-    int64_t bad = -1;
+    std::vector<int32_t> status;
+    int64_t bad;
+    if ((rc = text_rows_status(t->text, row_count, row_status, TGLS_DEFERRED, s, status, &bad))) return rc;
+    if ((rc = tgls_encode_rows(t, t->raw.p, t->n_kept, t->text.status.p, t->d_k_src.p, row_begin, row_count))) return rc;
     for (int64_t r = 0; r < row_count; r++) {
         const int code = status[(size_t)(2 * r)];
         if (code == TGLS_OK) tgls_mark(t, row_begin + r, true);
-        else if (code == TGLS_DEFERRED) tgls_mark(t, row_begin + r, false);
-        else if (bad < 0) bad = r;                          // its codes are unspecified: the row keeps the state it had
+        else if (code == TGLS_DEFERRED) tgls_mark(t, row_begin + r, false);      // (any other: its codes are unspecified, the row keeps the state it had)
     }
     if (bad >= 0)
         return fail(GARLIC_ERR_INVALID, "%s row %lld (line %lld of the call): %s (%d)", what, (long long)(row_begin + bad), (long long)bad,
@@ -3780,8 +3783,8 @@ int garlic_tgls_set_rows_text(garlic_tgls *t, const char *text, int64_t text_byt
     if (!t || !text || !line_begin) return fail(GARLIC_ERR_INVALID, "tgls, text and line_begin are required");
     return tgls_set_rows_parsed(t, "TGLS", text, text_bytes, line_begin, row_begin, row_count, row_status, where,
                                 [&](const uint8_t *d_text, hipStream_t s) {
-        hipLaunchKernelGGL(tgls_parse_kernel, dim3((unsigned)row_count), dim3(256), 0, s, d_text, text_bytes, t->lines.p, t->ncols,
-                           t->d_col_dest.p, t->raw.p, (int64_t)t->n_kept, t->status.p);
+        hipLaunchKernelGGL(tgls_parse_kernel, dim3((unsigned)row_count), dim3(256), 0, s, d_text, text_bytes, t->text.lines.p, t->ncols,
+                           t->d_col_dest.p, t->raw.p, (int64_t)t->n_kept, t->text.status.p);
     });
 }
 
@@ -3800,9 +3803,9 @@ int garlic_tgls_set_rows_vcf(garlic_tgls *t, const char *text, int64_t text_byte
     memcpy(kw, key, key_len);
     return tgls_set_rows_parsed(t, "VCF likelihood", text, text_bytes, line_begin, row_begin, row_count, row_status, where,
                                 [&](const uint8_t *d_text, hipStream_t s) {
-        hipLaunchKernelGGL(tgls_vcf_parse_kernel, dim3((unsigned)row_count), dim3(256), 0, s, d_text, text_bytes, t->lines.p, t->ncols,
+        hipLaunchKernelGGL(tgls_vcf_parse_kernel, dim3((unsigned)row_count), dim3(256), 0, s, d_text, text_bytes, t->text.lines.p, t->ncols,
                            t->d_col_dest.p, kw[0], kw[1], (int32_t)key_len, missing_raw ? *missing_raw : 0.0, missing_raw ? 1 : 0,
-                           t->raw.p, (int64_t)t->n_kept, t->status.p);
+                           t->raw.p, (int64_t)t->n_kept, t->text.status.p);
     });
 }
 

@@ -5,15 +5,12 @@
 // \f, \r; the '\n' ends the line), with leading and trailing runs allowed.  A token starts at a non-blank byte whose predecessor
 // is blank or the line's begin; token 4 + j is sample column j.
 //
-// tgls_parse_kernel: one workgroup of 256 lanes per line, after vcf_parse_kernel; the line goes through it in passes of 256
-// aligned 16-byte pieces (4 KB), every piece read from HBM once:
-//   1. a lane loads its piece, replaces the bytes outside the line's [begin, limit) by '\n', and compares: a 16-bit mask of the
-//      non-blank bytes and one of the newlines;
-//   2. the first newline of the pass (ballot per wave, minimum over the four waves through LDS) ends the line: what lies behind
-//      it is blank;
+// tgls_parse_kernel: one workgroup of 256 lanes per line; the line goes through it in passes of 256 aligned 16-byte pieces
+// (4 KB), every piece read from HBM once:
+//   1, 2. the line walk of text_line.hpp with the masks of the non-blank bytes and the newlines; the first newline ends the line
+//      and what lies behind it is blank;
 //   3. start mask = non-blank and predecessor blank (the predecessor of a piece's first byte is the last byte of the slot in
-//      front, read from LDS); popcount, inclusive scan by __shfl_up inside a wave and over the four wave totals through LDS: the
-//      token index of each piece's first start;
+//      front, read from LDS); popcount through text_block_scan: the token index of each piece's first start;
 //   4. the pieces and their masks stand in LDS as slots 2 .. 257; slots 0 and 1 are the previous pass's last two pieces and slots
 //      258, 259 are blank.  A lane decodes the tokens that START in its slot.  A token's length is the distance to the next
 //      blank in the non-blank masks of the slot and the two behind it, so a token of up to TGLS_TOKEN_MAX = 32 bytes that starts
@@ -36,8 +33,8 @@
 #include <stdint.h>
 
 #include "lod_kernels.hpp"
+#include "text_line.hpp"
 #include "tgls_number.hpp"
-#include "vcf_kernels.hpp"
 
 namespace garlic {
 
@@ -46,9 +43,8 @@ constexpr int TGLS_DEFERRED = 1;        // a token tgls_number leaves to the hos
 constexpr int TGLS_FEW_COLUMNS = 2;     // column = the number of sample columns the line has
 constexpr int TGLS_MANY_COLUMNS = 3;    // column = ncols_total
 
-constexpr int TGLS_PASS_PIECES = 256;
 constexpr int TGLS_CARRY = 2;                                   // slots a token may reach behind the one it starts in
-constexpr int TGLS_SLOTS = TGLS_PASS_PIECES + 2 * TGLS_CARRY;
+constexpr int TGLS_SLOTS = TEXT_PASS_PIECES + 2 * TGLS_CARRY;
 static_assert(15 + TGLS_TOKEN_MAX < 16 * (TGLS_CARRY + 1), "a token that starts at a slot's last byte ends inside the look-ahead");
 
 constexpr int TGLS_DICT_MAX = 65536;
@@ -80,21 +76,13 @@ tgls_parse_kernel(const uint8_t *__restrict__ text, int64_t text_bytes, const in
     __shared__ uint32_t s_cnt[4];
     __shared__ unsigned long long s_offence;
 
-    const int tid = threadIdx.x, wv = tid >> 6, lane = tid & (WAVE - 1);
+    const int tid = threadIdx.x;
     const int64_t r = blockIdx.x;
-    int64_t begin = line_begin[r], limit = line_begin[r + 1];
-    limit = limit < text_bytes ? limit : text_bytes;
-    begin = begin < limit ? begin : limit;
-    // pieces are aligned in memory, not in the slab: byte `o` of the slab sits at piece (o + shift) >> 4
-    const int64_t shift = (int64_t)((uintptr_t)text & 15);
-    const uint8_t *base = text - shift;                       // 16-byte aligned
-    const int64_t p_first = (begin + shift) >> 4;
-    const int64_t p_end = (limit + shift + 15) >> 4;          // one past the last piece that holds a byte of the line
-    const int64_t lo = begin + shift, hi = limit + shift;     // the line's bytes as offsets from `base`
+    const TextLine ln = text_line_of(text, text_bytes, line_begin, r);
 
     if (tid == 0) s_offence = ~0ull;
     if (tid < 2 * TGLS_CARRY) {                               // the carry slots in front and the blank slots behind
-        const int slot = tid < TGLS_CARRY ? tid : TGLS_PASS_PIECES + tid;
+        const int slot = tid < TGLS_CARRY ? tid : TEXT_PASS_PIECES + tid;
         *reinterpret_cast<uint4 *>(s_text + 16 * slot) = make_uint4(0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au);
         s_nb[slot] = 0;
         s_start[slot] = 0;
@@ -104,68 +92,27 @@ tgls_parse_kernel(const uint8_t *__restrict__ text, int64_t text_bytes, const in
     unsigned long long offence = ~0ull;
     int64_t tok = 0;              // tokens of the line that start in front of this pass
     bool ended = false;
-    for (int64_t p0 = p_first; !ended; p0 += TGLS_PASS_PIECES) {
+    for (int64_t p0 = ln.p_first; !ended; p0 += TEXT_PASS_PIECES) {
         __syncthreads();          // the previous pass has let go of the slots and the scan cells
-        const int64_t pc = p0 + tid;
-        const int64_t at = 16 * pc;
-        uint32_t w[4] = {0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au};
-        uint32_t live = 0xFFFFu;  // bytes of the piece at or behind the line's first
-        if (pc < p_end) {
-            const uint4 v = *reinterpret_cast<const uint4 *>(base + at);
-            w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-            if (at < lo || at + 16 > hi) {                    // a piece at an end of the line
-                live = 0;
-#pragma unroll
-                for (int k = 0; k < 16; k++) {
-                    const int64_t o = at + k;
-                    if (o < lo || o >= hi) w[k >> 2] = (w[k >> 2] & ~(0xFFu << (8 * (k & 3)))) | (0x0Au << (8 * (k & 3)));
-                    if (o >= lo) live |= 1u << k;
-                }
-            }
-        }
+        uint32_t w[4], live;
+        text_load_piece(ln, p0 + tid, w, live);
         *reinterpret_cast<uint4 *>(s_text + 16 * (tid + TGLS_CARRY)) = make_uint4(w[0], w[1], w[2], w[3]);
-        uint32_t nb = ~tgls_blank_mask(w) & 0xFFFFu;
-        const uint32_t nls = vcf_eq_mask(w, '\n') & live;
-        // the first newline of the pass, as a byte offset from the pass's first piece
-        const uint64_t has = __ballot(nls != 0);
-        const int my_nl = nls ? __ffs(nls) - 1 : 0;
-        const int first_lane = has ? __ffsll((unsigned long long)has) - 1 : 0;
-        const int nl_byte = __shfl(my_nl, first_lane, WAVE);
-        if (lane == 0) s_end[wv] = has ? (int64_t)(16 * (64 * wv + first_lane) + nl_byte) : INT64_MAX;
-        __syncthreads();
-        int64_t end = s_end[0];
-#pragma unroll
-        for (int k = 1; k < 4; k++) end = s_end[k] < end ? s_end[k] : end;
-        const bool last = end != INT64_MAX || p0 + TGLS_PASS_PIECES >= p_end;
+        const int64_t end = text_first_end(text_eq_mask(w, '\n') & live, s_end, tid);
+        const bool last = text_last_pass(ln, p0, end);
         // what lies behind the line's end is blank
-        const int64_t mine = 16 * (int64_t)tid;
-        if (end <= mine) nb = 0;
-        else if (end < mine + 16) nb &= (1u << (int)(end - mine)) - 1u;
+        const uint32_t nb = ~tgls_blank_mask(w) & text_keep_mask(end, tid);
         s_nb[tid + TGLS_CARRY] = nb;
         __syncthreads();
         const uint32_t prev = s_nb[tid + TGLS_CARRY - 1] >> 15;       // the byte in front of the piece is part of a token
         const uint32_t start = nb & ~((nb << 1) | prev) & 0xFFFFu;
-        uint32_t incl = __popc(start);
-#pragma unroll
-        for (int d = 1; d < WAVE; d <<= 1) {
-            const uint32_t o = __shfl_up(incl, d, WAVE);
-            if (lane >= d) incl += o;
-        }
-        if (lane == WAVE - 1) s_cnt[wv] = incl;
-        __syncthreads();
-        int64_t before = tok;
-        uint32_t pass_starts = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            if (k < wv) before += s_cnt[k];
-            pass_starts += s_cnt[k];
-        }
+        uint32_t before, pass_starts;
+        text_block_scan(__popc(start), s_cnt, tid, before, pass_starts);
         s_start[tid + TGLS_CARRY] = start;
-        s_tok[tid + TGLS_CARRY] = before + incl - __popc(start);
+        s_tok[tid + TGLS_CARRY] = tok + before;
         tok += pass_starts;
         __syncthreads();
         // decode the tokens that start in slots 0 .. 255 (and in slots 256, 257 when no pass follows)
-        const int nslots = last ? TGLS_PASS_PIECES + TGLS_CARRY : TGLS_PASS_PIECES;
+        const int nslots = last ? TEXT_PASS_PIECES + TGLS_CARRY : TEXT_PASS_PIECES;
         for (int slot = tid; slot < nslots; slot += 256) {
             uint32_t m = s_start[slot];
             if (!m) continue;
@@ -178,8 +125,7 @@ tgls_parse_kernel(const uint8_t *__restrict__ text, int64_t text_bytes, const in
                 t++;
                 if (j < 0) continue;
                 if (j >= ncols) {
-                    const unsigned long long key = ((unsigned long long)ncols << 3) | TGLS_MANY_COLUMNS;
-                    offence = key < offence ? key : offence;
+                    text_offend(offence, ncols, TGLS_MANY_COLUMNS);
                     continue;
                 }
                 const int32_t d = col_dest[j];
@@ -189,20 +135,16 @@ tgls_parse_kernel(const uint8_t *__restrict__ text, int64_t text_bytes, const in
                 if (len <= TGLS_TOKEN_MAX && tgls_number(s_text + 16 * slot + q, len, &v)) {
                     raw_row[d] = v;
                 } else {
-                    const unsigned long long key = ((unsigned long long)j << 3) | TGLS_DEFERRED;
-                    offence = key < offence ? key : offence;
+                    text_offend(offence, j, TGLS_DEFERRED);
                 }
             }
         }
         __syncthreads();
         if (last) {
             const int64_t found = tok > 4 ? tok - 4 : 0;
-            if (found < ncols) {
-                const unsigned long long key = ((unsigned long long)found << 3) | TGLS_FEW_COLUMNS;
-                offence = key < offence ? key : offence;
-            }
+            if (found < ncols) text_offend(offence, found, TGLS_FEW_COLUMNS);
         } else if (tid < TGLS_CARRY) {
-            const int from = TGLS_PASS_PIECES + tid;
+            const int from = TEXT_PASS_PIECES + tid;
             *reinterpret_cast<uint4 *>(s_text + 16 * tid) = *reinterpret_cast<const uint4 *>(s_text + 16 * from);
             s_nb[tid] = s_nb[from];
             s_start[tid] = s_start[from];
@@ -210,14 +152,7 @@ tgls_parse_kernel(const uint8_t *__restrict__ text, int64_t text_bytes, const in
         }
         ended = last;
     }
-    if (offence != ~0ull) atomicMin(&s_offence, offence);
-    __syncthreads();
-    if (tid == 0) {
-        const unsigned long long o = s_offence;
-        const bool clean = o == ~0ull;
-        status[2 * r] = clean ? 0 : (int32_t)(o & 7u);
-        status[2 * r + 1] = clean ? 0 : (int32_t)((o >> 3) < 0x7FFFFFFFull ? (o >> 3) : 0x7FFFFFFFull);
-    }
+    text_write_status(&s_offence, offence, status, r, tid);
 }
 
 __device__ __forceinline__ uint32_t tgls_hash(uint64_t b)

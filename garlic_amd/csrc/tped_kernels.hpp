@@ -14,15 +14,13 @@
 //
 // tped_parse_kernel: one workgroup of 256 lanes per line; the line goes through it in passes of 256 aligned 16-byte pieces
 // (4 KB), every piece read from HBM once and decoded from the registers that hold it.  Per pass:
-//   1. a lane loads its piece, replaces the bytes outside the line's [begin, limit) by '\n', and builds 16-bit masks by
-//      byte-parallel compares: blank, newline, offending byte (\v \f NUL), missing character;
-//   2. the first newline of the pass (ballot per wave, minimum over the four waves through LDS) ends the line: the bytes at
-//      and behind it are blanks.  A token START is a non-blank byte behind a blank (the byte in front of a piece comes from
-//      the neighbour lane, the wave in front, or the previous pass); a non-blank byte behind a non-blank one CONTINUES a
-//      token -- inside an allele token that is the offence "longer than one byte", seen from its second byte, so no lane
-//      looks into the piece behind its own;
-//   3. popcount of the start mask, inclusive scan by __shfl_up inside a wave and over the four wave totals through LDS: the
-//      index of each piece's first token; token 4 + a is allele a, individual a >> 1;
+//   1, 2. the line walk of text_line.hpp with the masks of the blanks, the newlines, the offending bytes (\v \f NUL) and the
+//      missing character; the first newline ends the line and the bytes at and behind it are blanks.  A token START is a
+//      non-blank byte behind a blank (the byte in front of a piece comes from the neighbour lane, the wave in front, or the
+//      previous pass); a non-blank byte behind a non-blank one CONTINUES a token -- inside an allele token that is the
+//      offence "longer than one byte", seen from its second byte, so no lane looks into the piece behind its own;
+//   3. popcount of the start mask through text_block_scan: the index of each piece's first token; token 4 + a is allele a,
+//      individual a >> 1;
 //   4. while `one` is unknown: the pass's first non-missing allele (ballot per wave, first wave through LDS).  The alleles in
 //      front of it are all missing, so nothing coded before depends on it;
 //   5. every allele goes to an LDS byte (0 = one, 1 = other, 2 = missing) in a window that starts at a multiple of 16 alleles;
@@ -39,6 +37,7 @@
 #include <stdint.h>
 
 #include "lod_kernels.hpp"
+#include "text_line.hpp"
 
 namespace garlic {
 
@@ -48,24 +47,7 @@ constexpr int TPED_BAD_BYTE = 2;       // \v, \f or NUL in the line
 constexpr int TPED_FEW_COLUMNS = 3;    // column = the allele tokens found / 2
 constexpr int TPED_MANY_COLUMNS = 4;   // column = nind_total
 
-constexpr int TPED_PASS_PIECES = 256;
-constexpr int TPED_STAGE = 8 * TPED_PASS_PIECES + 32;      // the alleles that can start in a pass + the 15 left over
-
-// 0x80 in every byte of x that equals c (exact: no borrow crosses a byte)
-__device__ __forceinline__ uint32_t tped_eq_flags(uint32_t x, uint32_t c)
-{
-    const uint32_t t = x ^ (c * 0x01010101u);
-    return ~(((t & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | t | 0x7F7F7F7Fu);
-}
-
-// the four 0x80 flags of a word as bits 0 .. 3
-__device__ __forceinline__ uint32_t tped_flag_bits(uint32_t f) { return (((f >> 7) * 0x00204081u) >> 21) & 0xFu; }
-
-__device__ __forceinline__ uint32_t tped_eq_mask(const uint32_t w[4], uint32_t c)
-{
-    return tped_flag_bits(tped_eq_flags(w[0], c)) | tped_flag_bits(tped_eq_flags(w[1], c)) << 4 |
-           tped_flag_bits(tped_eq_flags(w[2], c)) << 8 | tped_flag_bits(tped_eq_flags(w[3], c)) << 12;
-}
+constexpr int TPED_STAGE = 8 * TEXT_PASS_PIECES + 32;      // the alleles that can start in a pass + the 15 left over
 
 __global__ void __launch_bounds__(256)
 tped_parse_kernel(const uint8_t *__restrict__ text, int64_t text_bytes, const int64_t *__restrict__ line_begin, int64_t row_begin,
@@ -83,15 +65,7 @@ tped_parse_kernel(const uint8_t *__restrict__ text, int64_t text_bytes, const in
 
     const int tid = threadIdx.x, wv = tid >> 6, lane = tid & (WAVE - 1);
     const int64_t r = blockIdx.x;
-    int64_t begin = line_begin[r], limit = line_begin[r + 1];
-    limit = limit < text_bytes ? limit : text_bytes;
-    begin = begin < limit ? begin : limit;
-    // pieces are aligned in memory, not in the slab: byte `o` of the slab sits at piece (o + shift) >> 4
-    const int64_t shift = (int64_t)((uintptr_t)text & 15);
-    const uint8_t *base = text - shift;                       // 16-byte aligned
-    const int64_t p_first = (begin + shift) >> 4;
-    const int64_t p_end = (limit + shift + 15) >> 4;          // one past the last piece that holds a byte of the line
-    const int64_t lo = begin + shift, hi = limit + shift;     // the line's bytes as offsets from `base`
+    const TextLine ln = text_line_of(text, text_bytes, line_begin, r);
     const int64_t nall_tokens = 2 * (int64_t)nind;
 
     if (tid == 0) s_offence = ~0ull;
@@ -103,51 +77,25 @@ tped_parse_kernel(const uint8_t *__restrict__ text, int64_t text_bytes, const in
     bool have_one = false;
     int32_t n_one = 0, n_total = 0;
     bool ended = false;
-    for (int64_t p0 = p_first; !ended; p0 += TPED_PASS_PIECES) {
+    for (int64_t p0 = ln.p_first; !ended; p0 += TEXT_PASS_PIECES) {
         __syncthreads();          // the previous pass has let go of the scan cells and of the window's front
-        const int64_t pc = p0 + tid;
-        const int64_t at = 16 * pc;
-        uint32_t w[4] = {0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au};
-        uint32_t live = 0xFFFFu;  // bytes of the piece at or behind the line's first
-        if (pc < p_end) {
-            const uint4 v = *reinterpret_cast<const uint4 *>(base + at);
-            w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-            if (at < lo || at + 16 > hi) {                    // a piece at an end of the line
-                live = 0;
-#pragma unroll
-                for (int k = 0; k < 16; k++) {
-                    const int64_t o = at + k;
-                    if (o < lo || o >= hi) w[k >> 2] = (w[k >> 2] & ~(0xFFu << (8 * (k & 3)))) | (0x0Au << (8 * (k & 3)));
-                    if (o >= lo) live |= 1u << k;
-                }
-            }
-        }
+        uint32_t w[4], live;
+        text_load_piece(ln, p0 + tid, w, live);
         uint32_t nlf[4], blf[4], badf[4];
 #pragma unroll
         for (int k = 0; k < 4; k++) {
-            nlf[k] = tped_eq_flags(w[k], '\n');
-            blf[k] = nlf[k] | tped_eq_flags(w[k], ' ') | tped_eq_flags(w[k], '\t') | tped_eq_flags(w[k], '\r');
-            badf[k] = tped_eq_flags(w[k], '\v') | tped_eq_flags(w[k], '\f') | tped_eq_flags(w[k], 0);
+            nlf[k] = text_eq_flags(w[k], '\n');
+            blf[k] = nlf[k] | text_eq_flags(w[k], ' ') | text_eq_flags(w[k], '\t') | text_eq_flags(w[k], '\r');
+            badf[k] = text_eq_flags(w[k], '\v') | text_eq_flags(w[k], '\f') | text_eq_flags(w[k], 0);
         }
-        const uint32_t nls = (tped_flag_bits(nlf[0]) | tped_flag_bits(nlf[1]) << 4 | tped_flag_bits(nlf[2]) << 8 | tped_flag_bits(nlf[3]) << 12) & live;
-        const uint32_t bl = tped_flag_bits(blf[0]) | tped_flag_bits(blf[1]) << 4 | tped_flag_bits(blf[2]) << 8 | tped_flag_bits(blf[3]) << 12;
-        uint32_t bad = tped_flag_bits(badf[0]) | tped_flag_bits(badf[1]) << 4 | tped_flag_bits(badf[2]) << 8 | tped_flag_bits(badf[3]) << 12;
-        const uint32_t ms = tped_eq_mask(w, missing);
-        // the first newline of the pass, as a byte offset from the pass's first piece
-        const uint64_t has = __ballot(nls != 0);
-        const int my_nl = nls ? __ffs(nls) - 1 : 0;
-        const int first_lane = has ? __ffsll((unsigned long long)has) - 1 : 0;
-        const int nl_byte = __shfl(my_nl, first_lane, WAVE);
-        if (lane == 0) s_end[wv] = has ? (int64_t)(16 * (64 * wv + first_lane) + nl_byte) : INT64_MAX;
+        const uint32_t bl = text_flag_mask(blf);
+        uint32_t bad = text_flag_mask(badf);
+        const uint32_t ms = text_eq_mask(w, missing);
         // a byte in front of the line's end has its neighbour in front of it too: the raw mask serves
-        if (lane == WAVE - 1) s_tail[wv] = bl >> 15;
-        __syncthreads();
-        int64_t end = s_end[0];
-#pragma unroll
-        for (int k = 1; k < 4; k++) end = s_end[k] < end ? s_end[k] : end;
-        const bool last = end != INT64_MAX || p0 + TPED_PASS_PIECES >= p_end;
-        const int64_t mine = 16 * (int64_t)tid;
-        const uint32_t keep = end <= mine ? 0u : end < mine + 16 ? (1u << (int)(end - mine)) - 1u : 0xFFFFu;
+        if (lane == WAVE - 1) s_tail[wv] = bl >> 15;         // (read behind the barrier of text_first_end)
+        const int64_t end = text_first_end(text_flag_mask(nlf) & live, s_end, tid);
+        const bool last = text_last_pass(ln, p0, end);
+        const uint32_t keep = text_keep_mask(end, tid);
         uint32_t prevb = __shfl_up(bl >> 15, 1, WAVE);
         if (lane == 0) prevb = wv ? s_tail[wv - 1] : prev_tail;
         prev_tail = s_tail[3];
@@ -155,30 +103,16 @@ tped_parse_kernel(const uint8_t *__restrict__ text, int64_t text_bytes, const in
         const uint32_t start = ~bl & behind_blank & keep;
         const uint32_t cont = ~bl & ~behind_blank & keep;
         bad &= keep;
-        uint32_t incl = __popc(start);
-#pragma unroll
-        for (int d = 1; d < WAVE; d <<= 1) {
-            const uint32_t o = __shfl_up(incl, d, WAVE);
-            if (lane >= d) incl += o;
-        }
-        if (lane == WAVE - 1) s_starts[wv] = incl;
-        __syncthreads();
-        int64_t before = tok;
-        uint32_t pass_starts = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            if (k < wv) before += s_starts[k];
-            pass_starts += s_starts[k];
-        }
-        const int64_t first_tok = before + incl - __popc(start);      // tokens that start before this piece
+        uint32_t before, pass_starts;
+        text_block_scan(__popc(start), s_starts, tid, before, pass_starts);
+        const int64_t first_tok = tok + before;                       // tokens that start before this piece
         tok += pass_starts;
         // the allele tokens among the piece's starts
         uint32_t am = start;
         int64_t a0 = first_tok - 4;                                   // the allele of am's lowest bit
         while (a0 < 0 && am) { am &= am - 1; a0++; }
         if (a0 + __popc(am) > nall_tokens) {
-            const unsigned long long key = ((unsigned long long)nind << 3) | TPED_MANY_COLUMNS;
-            offence = key < offence ? key : offence;
+            text_offend(offence, nind, TPED_MANY_COLUMNS);
             uint32_t t = am;
             am = 0;
             for (int64_t a = a0; a < nall_tokens && t; a++) { am |= t & (0u - t); t &= t - 1; }
@@ -188,14 +122,8 @@ tped_parse_kernel(const uint8_t *__restrict__ text, int64_t text_bytes, const in
             odd &= odd - 1;
             const int64_t t = first_tok + __popc(start & ((2u << q) - 1u)) - 1;      // the token that holds byte q
             const int64_t j = t < 4 ? 0 : ((t - 4) >> 1) < nind ? (t - 4) >> 1 : nind;
-            if ((bad >> q) & 1u) {
-                const unsigned long long key = ((unsigned long long)j << 3) | TPED_BAD_BYTE;
-                offence = key < offence ? key : offence;
-            }
-            if (((cont >> q) & 1u) && t >= 4) {
-                const unsigned long long key = ((unsigned long long)j << 3) | TPED_LONG_ALLELE;
-                offence = key < offence ? key : offence;
-            }
+            if ((bad >> q) & 1u) text_offend(offence, j, TPED_BAD_BYTE);
+            if (((cont >> q) & 1u) && t >= 4) text_offend(offence, j, TPED_LONG_ALLELE);
         }
         const uint32_t nonmiss = am & ~ms;
         if (!have_one) {          // (uniform over the workgroup)
@@ -210,7 +138,7 @@ tped_parse_kernel(const uint8_t *__restrict__ text, int64_t text_bytes, const in
             for (int k = 3; k >= 0; k--)
                 if (s_one[k] < 0x100u) { one = s_one[k]; have_one = true; }
         }
-        const uint32_t oneeq = have_one ? tped_eq_mask(w, one) : 0u;
+        const uint32_t oneeq = have_one ? text_eq_mask(w, one) : 0u;
         n_total += __popc(nonmiss);
         n_one += __popc(nonmiss & oneeq);
         {
@@ -223,10 +151,7 @@ tped_parse_kernel(const uint8_t *__restrict__ text, int64_t text_bytes, const in
         __syncthreads();
         // alleles coded so far
         int64_t adone = tok - 4 > 0 ? tok - 4 : 0;
-        if (last && adone < nall_tokens) {
-            const unsigned long long key = ((unsigned long long)(adone >> 1) << 3) | TPED_FEW_COLUMNS;
-            offence = key < offence ? key : offence;
-        }
+        if (last && adone < nall_tokens) text_offend(offence, adone >> 1, TPED_FEW_COLUMNS);
         adone = adone < nall_tokens ? adone : nall_tokens;
         const int64_t done = adone >> 1;                              // individuals with both alleles coded
         const int64_t g_lo = abase >> 4;
@@ -263,19 +188,14 @@ tped_parse_kernel(const uint8_t *__restrict__ text, int64_t text_bytes, const in
         abase = 16 * g_hi;
         ended = last;
     }
-    if (offence != ~0ull) atomicMin(&s_offence, offence);
 #pragma unroll
     for (int d = WAVE / 2; d; d >>= 1) {
         n_one += __shfl_down(n_one, d, WAVE);
         n_total += __shfl_down(n_total, d, WAVE);
     }
     if (lane == 0) { s_sum[2 * wv] = n_one; s_sum[2 * wv + 1] = n_total; }
-    __syncthreads();
+    text_write_status(&s_offence, offence, status, r, tid);      // (its barrier stands behind the store of s_sum too)
     if (tid == 0) {
-        const unsigned long long o = s_offence;
-        const bool clean = o == ~0ull;
-        status[2 * r] = clean ? 0 : (int32_t)(o & 7u);
-        status[2 * r + 1] = clean ? 0 : (int32_t)((o >> 3) < 0x7FFFFFFFull ? (o >> 3) : 0x7FFFFFFFull);
         counts[2 * (row_begin + r)] = s_sum[0] + s_sum[2] + s_sum[4] + s_sum[6];
         counts[2 * (row_begin + r) + 1] = s_sum[1] + s_sum[3] + s_sum[5] + s_sum[7];
         counted[row_begin + r] = have_one ? 0 : 2;

@@ -10,12 +10,10 @@
 // with '.' (a missing genotype: no score reads the value); on any other column it becomes the caller's missing value or,
 // when the caller gave none, the offence TGLS_VCF_NO_VALUE.  Columns that are not kept are counted and nothing else.
 //
-// tgls_vcf_parse_kernel: one workgroup of 256 lanes per line, after tgls_parse_kernel; the line goes through it in passes of
-// 256 aligned 16-byte pieces (4 KB), every piece read from HBM once:
-//   1. a lane loads its piece, replaces the bytes outside the line's [begin, limit) by '\n', and compares: 16-bit masks of the
-//      tabs, the colons and the stops (tab : \r \n);
-//   2. the first \r or \n of the pass (ballot per wave, minimum over the four waves through LDS) ends the line: tabs and
-//      colons at or behind it are dropped;
+// tgls_vcf_parse_kernel: one workgroup of 256 lanes per line; the line goes through it in passes of 256 aligned 16-byte
+// pieces (4 KB), every piece read from HBM once:
+//   1, 2. the line walk of text_line.hpp with the masks of the tabs, the colons and the stops (tab : \r \n); the first \r or
+//      \n ends the line, and tabs and colons at or behind it are dropped;
 //   3. column starts = the bytes behind a tab (the tab of a piece's last byte starts a column in the next slot: read from LDS).
 //      A segmented scan over the pieces with the element (column starts, colons at or behind the last start, has a start,
 //      the last start's byte is '.') -- __shfl_up inside a wave, the four wave totals through LDS, the state of the passes
@@ -41,8 +39,8 @@
 #include <stdint.h>
 
 #include "lod_kernels.hpp"
+#include "text_line.hpp"
 #include "tgls_kernels.hpp"
-#include "vcf_kernels.hpp"
 
 namespace garlic {
 
@@ -50,9 +48,8 @@ constexpr int TGLS_VCF_NO_KEY = 4;      // FORMAT does not name the key; column 
 constexpr int TGLS_VCF_NO_VALUE = 5;    // a called genotype without a value and no missing value to take; column = the sample
 
 constexpr int VGL_KEY_MAX = 16;
-constexpr int VGL_PASS_PIECES = 256;
 constexpr int VGL_CARRY = 3;                                    // slots a value may reach behind the one its colon stands in
-constexpr int VGL_SLOTS = VGL_PASS_PIECES + 2 * VGL_CARRY;
+constexpr int VGL_SLOTS = TEXT_PASS_PIECES + 2 * VGL_CARRY;
 constexpr uint32_t VGL_NO_KEY = 0xFFFFFFFFu;
 static_assert(16 + TGLS_TOKEN_MAX < 16 * (VGL_CARRY + 1), "a value behind a slot's last byte ends inside the look-ahead");
 static_assert(16 + VGL_KEY_MAX < 16 * (VGL_CARRY + 1), "and so does a FORMAT subfield as long as the longest key");
@@ -91,22 +88,14 @@ tgls_vcf_parse_kernel(const uint8_t *__restrict__ text, int64_t text_bytes, cons
 
     const int tid = threadIdx.x, wv = tid >> 6, lane = tid & (WAVE - 1);
     const int64_t r = blockIdx.x;
-    int64_t begin = line_begin[r], limit = line_begin[r + 1];
-    limit = limit < text_bytes ? limit : text_bytes;
-    begin = begin < limit ? begin : limit;
-    // pieces are aligned in memory, not in the slab: byte `o` of the slab sits at piece (o + shift) >> 4
-    const int64_t shift = (int64_t)((uintptr_t)text & 15);
-    const uint8_t *base = text - shift;                       // 16-byte aligned
-    const int64_t p_first = (begin + shift) >> 4;
-    const int64_t p_end = (limit + shift + 15) >> 4;          // one past the last piece that holds a byte of the line
-    const int64_t lo = begin + shift, hi = limit + shift;     // the line's bytes as offsets from `base`
+    const TextLine ln = text_line_of(text, text_bytes, line_begin, r);
 
     if (tid == 0) {
         s_offence = ~0ull;
         s_k = VGL_NO_KEY;
     }
     if (tid < 2 * VGL_CARRY) {                                // the carry slots in front and the stop slots behind
-        const int slot = tid < VGL_CARRY ? tid : VGL_PASS_PIECES + tid;
+        const int slot = tid < VGL_CARRY ? tid : TEXT_PASS_PIECES + tid;
         *reinterpret_cast<uint4 *>(s_text + 16 * slot) = make_uint4(0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au);
         s_stop[slot] = 0xFFFFu;
         s_tab[slot] = 0;
@@ -117,10 +106,7 @@ tgls_vcf_parse_kernel(const uint8_t *__restrict__ text, int64_t text_bytes, cons
     }
     double *raw_row = raw + r * raw_ld;
     unsigned long long offence = ~0ull;
-    const auto offend = [&](int64_t column, int code) {
-        const unsigned long long key = ((unsigned long long)column << 3) | (unsigned)code;
-        offence = key < offence ? key : offence;
-    };
+    const auto offend = [&](int64_t column, int code) { text_offend(offence, column, code); };
     // a missing value of sample j, whose column began with '.' (dot) or did not
     const auto missing = [&](int64_t j, uint32_t dot) {
         const int32_t d = col_dest[j];
@@ -132,47 +118,19 @@ tgls_vcf_parse_kernel(const uint8_t *__restrict__ text, int64_t text_bytes, cons
     int64_t col = 0;              // the state at the pass's first byte, as in s_col / s_cc / s_dot
     uint32_t ccarry = 0, dcarry = 0;
     bool ended = false;
-    for (int64_t p0 = p_first; !ended; p0 += VGL_PASS_PIECES) {
+    for (int64_t p0 = ln.p_first; !ended; p0 += TEXT_PASS_PIECES) {
         __syncthreads();          // the previous pass has let go of the slots and the scan cells
-        const int64_t pc = p0 + tid;
-        const int64_t at = 16 * pc;
-        uint32_t w[4] = {0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au};
-        uint32_t live = 0xFFFFu;  // bytes of the piece at or behind the line's first
-        if (pc < p_end) {
-            const uint4 v = *reinterpret_cast<const uint4 *>(base + at);
-            w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-            if (at < lo || at + 16 > hi) {                    // a piece at an end of the line
-                live = 0;
-#pragma unroll
-                for (int k = 0; k < 16; k++) {
-                    const int64_t o = at + k;
-                    if (o < lo || o >= hi) w[k >> 2] = (w[k >> 2] & ~(0xFFu << (8 * (k & 3)))) | (0x0Au << (8 * (k & 3)));
-                    if (o >= lo) live |= 1u << k;
-                }
-            }
-        }
+        uint32_t w[4], live;
+        text_load_piece(ln, p0 + tid, w, live);
         const int me = tid + VGL_CARRY;
         *reinterpret_cast<uint4 *>(s_text + 16 * me) = make_uint4(w[0], w[1], w[2], w[3]);
-        uint32_t tabs = vcf_eq_mask(w, '\t'), colons = vcf_eq_mask(w, ':');
-        const uint32_t ends = vcf_eq_mask(w, '\n') | vcf_eq_mask(w, '\r');
+        uint32_t tabs = text_eq_mask(w, '\t'), colons = text_eq_mask(w, ':');
+        const uint32_t ends = text_eq_mask(w, '\n') | text_eq_mask(w, '\r');
         s_stop[me] = tabs | colons | ends;
-        const uint32_t nls = ends & live;
-        // the first line end of the pass, as a byte offset from the pass's first piece
-        const uint64_t has = __ballot(nls != 0);
-        const int my_nl = nls ? __ffs(nls) - 1 : 0;
-        const int first_lane = has ? __ffsll((unsigned long long)has) - 1 : 0;
-        const int nl_byte = __shfl(my_nl, first_lane, WAVE);
-        if (lane == 0) s_end[wv] = has ? (int64_t)(16 * (64 * wv + first_lane) + nl_byte) : INT64_MAX;
-        __syncthreads();
-        int64_t end = s_end[0];
-#pragma unroll
-        for (int k = 1; k < 4; k++) end = s_end[k] < end ? s_end[k] : end;
-        const bool last = end != INT64_MAX || p0 + VGL_PASS_PIECES >= p_end;
+        const int64_t end = text_first_end(ends & live, s_end, tid);
+        const bool last = text_last_pass(ln, p0, end);
         // tabs and colons at or behind the line's end are none
-        const int64_t mine = 16 * (int64_t)tid;
-        uint32_t keep = 0xFFFFu;
-        if (end <= mine) keep = 0;
-        else if (end < mine + 16) keep = (1u << (int)(end - mine)) - 1u;
+        const uint32_t keep = text_keep_mask(end, tid);
         tabs &= keep;
         colons &= keep;
         s_tab[me] = tabs;
@@ -228,7 +186,7 @@ tgls_vcf_parse_kernel(const uint8_t *__restrict__ text, int64_t text_bytes, cons
         dcarry = total.n ? total.dot : dcarry;
         __syncthreads();
         // walk slots 0 .. 255 (and slots 256 .. 258 when no pass follows)
-        const int nslots = last ? VGL_PASS_PIECES + VGL_CARRY : VGL_PASS_PIECES;
+        const int nslots = last ? TEXT_PASS_PIECES + VGL_CARRY : TEXT_PASS_PIECES;
         // FORMAT: the subfield starts of column 8 against the key
         for (int slot = tid; slot < nslots; slot += 256) {
             uint32_t ev = s_ev[slot];
@@ -312,7 +270,7 @@ tgls_vcf_parse_kernel(const uint8_t *__restrict__ text, int64_t text_bytes, cons
         __syncthreads();
         if (last) {
             if (tid == 0) {
-                if (end == INT64_MAX && (s_tab[VGL_PASS_PIECES + VGL_CARRY - 1] >> 15)) {
+                if (end == INT64_MAX && (s_tab[TEXT_PASS_PIECES + VGL_CARRY - 1] >> 15)) {
                     // the line ends by `limit` behind a tab that is the pass's last byte: the empty column it starts lies in
                     // a slot no lane holds.  It closes the column in front and is counted here.
                     const int64_t jf = col - 9;
@@ -329,7 +287,7 @@ tgls_vcf_parse_kernel(const uint8_t *__restrict__ text, int64_t text_bytes, cons
                 if (k == VGL_NO_KEY) offend(0, TGLS_VCF_NO_KEY);
             }
         } else if (tid < VGL_CARRY) {
-            const int from = VGL_PASS_PIECES + tid;
+            const int from = TEXT_PASS_PIECES + tid;
             *reinterpret_cast<uint4 *>(s_text + 16 * tid) = *reinterpret_cast<const uint4 *>(s_text + 16 * from);
             s_stop[tid] = s_stop[from];
             s_tab[tid] = s_tab[from];
@@ -340,14 +298,7 @@ tgls_vcf_parse_kernel(const uint8_t *__restrict__ text, int64_t text_bytes, cons
         }
         ended = last;
     }
-    if (offence != ~0ull) atomicMin(&s_offence, offence);
-    __syncthreads();
-    if (tid == 0) {
-        const unsigned long long o = s_offence;
-        const bool clean = o == ~0ull;
-        status[2 * r] = clean ? 0 : (int32_t)(o & 7u);
-        status[2 * r + 1] = clean ? 0 : (int32_t)((o >> 3) < 0x7FFFFFFFull ? (o >> 3) : 0x7FFFFFFFull);
-    }
+    text_write_status(&s_offence, offence, status, r, tid);
 }
 
 } // namespace garlic

@@ -8,12 +8,9 @@
 //
 // vcf_parse_kernel: one workgroup of 256 lanes per line; the line goes through it in passes of 256 aligned 16-byte pieces
 // (4 KB), every piece read from HBM once.  Fields have any width, so a lane finds the sample of a byte by counting tabs:
-//   1. a lane loads its piece, replaces the bytes outside the line's [begin, limit) by '\n' (what a poisoned neighbour holds
-//      never reaches a decision), and compares for tab and newline: two 16-bit masks;
-//   2. the first newline of the pass (ballot per wave, minimum over the four waves through LDS) ends the line: tabs behind it
-//      are dropped from the masks;
-//   3. popcount of the tab mask, inclusive scan by __shfl_up inside a wave and over the four wave totals through LDS: the
-//      column of each piece's first byte;
+//   1, 2. the line walk of text_line.hpp with the masks of the tabs and the newlines; the first newline ends the line and the
+//      tabs behind it are dropped;
+//   3. popcount of the tab mask through text_block_scan: the column of each piece's first byte;
 //   4. the pieces, their masks and columns stand in LDS as slots 1 .. 256; slot 0 is the previous pass's last piece and slot
 //      257 is all '\n'.  A lane decodes the fields that START in slot `lane` (the byte after each of its tabs) from four LDS
 //      bytes, which may reach into the next slot -- that is why the decode runs one slot behind the load (slot 256 is decoded
@@ -29,6 +26,7 @@
 #include <stdint.h>
 
 #include "lod_kernels.hpp"
+#include "text_line.hpp"
 
 namespace garlic {
 
@@ -40,18 +38,8 @@ constexpr int VCF_ALLELE_INDEX = 4;    // an allele index >= 2
 constexpr int VCF_FEW_COLUMNS = 5;     // column = the number of sample columns the line has
 constexpr int VCF_MANY_COLUMNS = 6;    // column = nind_total
 
-constexpr int VCF_PASS_PIECES = 256;
-constexpr int VCF_SLOTS = VCF_PASS_PIECES + 2;
-constexpr int VCF_STAGE = 16 * (VCF_PASS_PIECES + 1) + 16;     // samples that can start in the 257 slots of a last pass + the 7 left over
-
-// the 16-bit mask of the bytes of a piece that equal c
-__device__ __forceinline__ uint32_t vcf_eq_mask(const uint32_t w[4], uint32_t c)
-{
-    uint32_t m = 0;
-#pragma unroll
-    for (int k = 0; k < 16; k++) m |= (((w[k >> 2] >> (8 * (k & 3))) & 0xFFu) == c ? 1u : 0u) << k;
-    return m;
-}
+constexpr int VCF_SLOTS = TEXT_PASS_PIECES + 2;
+constexpr int VCF_STAGE = 16 * (TEXT_PASS_PIECES + 1) + 16;    // samples that can start in the 257 slots of a last pass + the 7 left over
 
 __device__ __forceinline__ bool vcf_is_digit(uint32_t c) { return c >= '0' && c <= '9'; }
 __device__ __forceinline__ bool vcf_is_end(uint32_t c) { return c == ':' || c == '\t' || c == '\r' || c == '\n'; }
@@ -82,17 +70,9 @@ vcf_parse_kernel(const uint8_t *__restrict__ text, int64_t text_bytes, const int
     __shared__ uint32_t s_tabs[4];
     __shared__ unsigned long long s_offence;
 
-    const int tid = threadIdx.x, wv = tid >> 6, lane = tid & (WAVE - 1);
+    const int tid = threadIdx.x;
     const int64_t r = blockIdx.x;
-    int64_t begin = line_begin[r], limit = line_begin[r + 1];
-    limit = limit < text_bytes ? limit : text_bytes;
-    begin = begin < limit ? begin : limit;
-    // pieces are aligned in memory, not in the slab: byte `o` of the slab sits at piece (o + shift) >> 4
-    const int64_t shift = (int64_t)((uintptr_t)text & 15);
-    const uint8_t *base = text - shift;                       // 16-byte aligned
-    const int64_t p_first = (begin + shift) >> 4;
-    const int64_t p_end = (limit + shift + 15) >> 4;          // one past the last piece that holds a byte of the line
-    const int64_t lo = begin + shift, hi = limit + shift;     // the line's bytes as offsets from `base`
+    const TextLine ln = text_line_of(text, text_bytes, line_begin, r);
 
     if (tid == 0) {
         s_offence = ~0ull;
@@ -108,67 +88,23 @@ vcf_parse_kernel(const uint8_t *__restrict__ text, int64_t text_bytes, const int
     int64_t col = 0;              // tabs of the line before this pass = column of the pass's first byte
     int64_t jbase = 0;            // sample of s_stage[0], a multiple of 8
     bool ended = false;
-    for (int64_t p0 = p_first; !ended; p0 += VCF_PASS_PIECES) {
+    for (int64_t p0 = ln.p_first; !ended; p0 += TEXT_PASS_PIECES) {
         __syncthreads();          // the previous pass has let go of the slots and the scan cells
-        const int64_t pc = p0 + tid;
-        const int64_t at = 16 * pc;
-        uint32_t w[4] = {0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au};
-        uint32_t live = 0;        // bytes of the piece at or behind the line's first
-        if (pc < p_end) {
-            const uint4 v = *reinterpret_cast<const uint4 *>(base + at);
-            w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-            live = 0xFFFFu;
-            if (at < lo || at + 16 > hi) {                    // a piece at an end of the line
-                live = 0;
-#pragma unroll
-                for (int k = 0; k < 16; k++) {
-                    const int64_t o = at + k;
-                    if (o < lo || o >= hi) w[k >> 2] = (w[k >> 2] & ~(0xFFu << (8 * (k & 3)))) | (0x0Au << (8 * (k & 3)));
-                    if (o >= lo) live |= 1u << k;
-                }
-            }
-        } else {
-            live = 0xFFFFu;
-        }
+        uint32_t w[4], live;
+        text_load_piece(ln, p0 + tid, w, live);
         *reinterpret_cast<uint4 *>(s_text + 16 * (tid + 1)) = make_uint4(w[0], w[1], w[2], w[3]);
-        uint32_t tabs = vcf_eq_mask(w, '\t');
-        const uint32_t nls = vcf_eq_mask(w, '\n') & live;
-        // the first newline of the pass, as a byte offset from the pass's first piece
-        const uint64_t has = __ballot(nls != 0);
-        const int my_nl = nls ? __ffs(nls) - 1 : 0;
-        const int first_lane = has ? __ffsll((unsigned long long)has) - 1 : 0;
-        const int nl_byte = __shfl(my_nl, first_lane, WAVE);
-        if (lane == 0) s_end[wv] = has ? (int64_t)(16 * (64 * wv + first_lane) + nl_byte) : INT64_MAX;
-        __syncthreads();
-        int64_t end = s_end[0];
-#pragma unroll
-        for (int k = 1; k < 4; k++) end = s_end[k] < end ? s_end[k] : end;
-        const bool last = end != INT64_MAX || p0 + VCF_PASS_PIECES >= p_end;
+        const int64_t end = text_first_end(text_eq_mask(w, '\n') & live, s_end, tid);
+        const bool last = text_last_pass(ln, p0, end);
         // tabs behind the line's end are no columns
-        const int64_t mine = 16 * (int64_t)tid;
-        if (end <= mine) tabs = 0;
-        else if (end < mine + 16) tabs &= (1u << (int)(end - mine)) - 1u;
-        uint32_t incl = __popc(tabs);
-#pragma unroll
-        for (int d = 1; d < WAVE; d <<= 1) {
-            const uint32_t o = __shfl_up(incl, d, WAVE);
-            if (lane >= d) incl += o;
-        }
-        if (lane == WAVE - 1) s_tabs[wv] = incl;
-        __syncthreads();
-        int64_t before = col;
-        uint32_t pass_tabs = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            if (k < wv) before += s_tabs[k];
-            pass_tabs += s_tabs[k];
-        }
+        const uint32_t tabs = text_eq_mask(w, '\t') & text_keep_mask(end, tid);
+        uint32_t before, pass_tabs;
+        text_block_scan(__popc(tabs), s_tabs, tid, before, pass_tabs);
         s_mask[tid + 1] = tabs;
-        s_col[tid + 1] = before + incl - __popc(tabs);
+        s_col[tid + 1] = col + before;
         col += pass_tabs;
         __syncthreads();
         // decode the fields that start behind the tabs of slots 0 .. 255 (and of slot 256 when no pass follows)
-        const int nslots = last ? VCF_PASS_PIECES + 1 : VCF_PASS_PIECES;
+        const int nslots = last ? TEXT_PASS_PIECES + 1 : TEXT_PASS_PIECES;
         for (int slot = tid; slot < nslots; slot += 256) {
             uint32_t m = s_mask[slot];
             int64_t c = s_col[slot];
@@ -179,28 +115,21 @@ vcf_parse_kernel(const uint8_t *__restrict__ text, int64_t text_bytes, const int
                 const int64_t j = c - 9;
                 if (j < 0) continue;
                 if (j >= nind) {
-                    const unsigned long long key = ((unsigned long long)nind << 3) | VCF_MANY_COLUMNS;
-                    offence = key < offence ? key : offence;
+                    text_offend(offence, nind, VCF_MANY_COLUMNS);
                     continue;
                 }
                 const uint8_t *f = s_text + 16 * slot + q + 1;
                 uint32_t out = 0;
                 const int code = vcf_decode_gt(f[0], f[1], f[2], f[3], out);
-                if (code != VCF_OK) {
-                    const unsigned long long key = ((unsigned long long)j << 3) | (unsigned)code;
-                    offence = key < offence ? key : offence;
-                }
+                if (code != VCF_OK) text_offend(offence, j, code);
                 s_stage[j - jbase] = (uint8_t)out;
             }
         }
         __syncthreads();
         // samples decoded so far: those whose tab lies in a decoded slot
-        const int64_t cols_done = last ? col : s_col[VCF_PASS_PIECES];
+        const int64_t cols_done = last ? col : s_col[TEXT_PASS_PIECES];
         int64_t done = cols_done - 8 > 0 ? cols_done - 8 : 0;
-        if (last && done < nind) {
-            const unsigned long long key = ((unsigned long long)done << 3) | VCF_FEW_COLUMNS;
-            offence = key < offence ? key : offence;
-        }
+        if (last && done < nind) text_offend(offence, done, VCF_FEW_COLUMNS);
         done = done < nind ? done : nind;
         const int64_t g_lo = jbase >> 3;
         const int64_t g_hi = last ? (done + 7) >> 3 : done >> 3;      // groups of 8 samples to store now
@@ -225,21 +154,14 @@ vcf_parse_kernel(const uint8_t *__restrict__ text, int64_t text_bytes, const int
             const int left = (int)(done - 8 * g_hi);                  // 0 .. 7
             const int from = (int)(8 * (g_hi - g_lo));
             for (int k = 0; k < left; k++) s_stage[k] = s_stage[from + k];
-            *reinterpret_cast<uint4 *>(s_text) = *reinterpret_cast<const uint4 *>(s_text + 16 * VCF_PASS_PIECES);
-            s_mask[0] = s_mask[VCF_PASS_PIECES];
-            s_col[0] = s_col[VCF_PASS_PIECES];
+            *reinterpret_cast<uint4 *>(s_text) = *reinterpret_cast<const uint4 *>(s_text + 16 * TEXT_PASS_PIECES);
+            s_mask[0] = s_mask[TEXT_PASS_PIECES];
+            s_col[0] = s_col[TEXT_PASS_PIECES];
         }
         jbase = 8 * g_hi;
         ended = last;
     }
-    if (offence != ~0ull) atomicMin(&s_offence, offence);
-    __syncthreads();
-    if (tid == 0) {
-        const unsigned long long o = s_offence;
-        const bool clean = o == ~0ull;
-        status[2 * r] = clean ? 0 : (int32_t)(o & 7u);
-        status[2 * r + 1] = clean ? 0 : (int32_t)((o >> 3) < 0x7FFFFFFFull ? (o >> 3) : 0x7FFFFFFFull);
-    }
+    text_write_status(&s_offence, offence, status, r, tid);
 }
 
 // HapData::firstCopy of the TPED line an image row stands for, as the panel's phase planes [blk][nloci]:

@@ -229,7 +229,15 @@ FreqData *initFreqData(int nloci)
 void releaseFreqData(FreqData *d) { if (d) { delete[] d->freq; delete d; } }
 void releaseFreqData(std::vector<FreqData *> *v) { for (auto d : *v) releaseFreqData(d); delete v; }
 
-static void closeTglsFile(TglsFile *f);
+static void closeTglsFile(TglsFile *f)
+{
+    if (!f) return;
+    for (auto &o : f->objects) {
+        if (o.tgls) garlic_tgls_destroy((garlic_tgls *)o.tgls);
+        if (o.ctx) garlic_ctx_destroy((garlic_ctx *)o.ctx);
+    }
+    delete f;
+}
 
 GenoLikeData *initGLData(unsigned int nind, unsigned int nloci)
 {
@@ -677,308 +685,6 @@ garlic_bed *bedImageOn(BedFile *b, int device)
 // the triple of an open file set `b` (the caller's reference on it passes to the HapData, or is dropped on failure)
 static void loadBedFile(BedFile *b, int &numLoci, int &numInd, std::vector<HapData *> **hapDataByChr,
                         std::vector<MapData *> **mapDataByChr, std::vector<FreqData *> **freqDataByChr, int nresample,
-                        unsigned long long resampleSeed, int device);
-
-void loadBedData(const std::string &bedfile, const std::string &bimfile, const std::string &famfile, int &numLoci, int &numInd,
-                 std::vector<HapData *> **hapDataByChr, std::vector<MapData *> **mapDataByChr,
-                 std::vector<FreqData *> **freqDataByChr, int nresample, unsigned long long resampleSeed, int device)
-{
-    BedFile *b = openBedFile(bedfile, bimfile, famfile);
-    b->refs = 1;                 // this function's, until the HapData hold theirs
-    loadBedFile(b, numLoci, numInd, hapDataByChr, mapDataByChr, freqDataByChr, nresample, resampleSeed, device);
-}
-
-static void closeTglsFile(TglsFile *f);
-static bool vcfGlSlab(const TglsFile *f, garlic_tgls *obj, const void *d_text, const char *h_text, int64_t text_bytes,
-                      const std::vector<int64_t> &lb, const std::vector<int64_t> &ends, const std::vector<int64_t> &number, long long row);
-
-// the loader's slab of text on the devices that parse it: one buffer per likelihood object, freed with the scope
-struct VcfDeviceSlabs {
-    struct One { garlic_ctx *ctx; garlic_tgls *obj; void *text; };
-    std::vector<One> on;
-    void release()
-    {
-        for (One &o : on) garlic_device_free(o.ctx, o.text);
-        on.clear();
-    }
-    ~VcfDeviceSlabs() { release(); }
-};
-
-void loadVcfData(const std::string &vcffile, bool phased, bool snpsOnly, std::vector<std::string> &samples, int &numLoci, int &numInd,
-                 std::vector<HapData *> **hapDataByChr, std::vector<MapData *> **mapDataByChr, std::vector<FreqData *> **freqDataByChr,
-                 int nresample, unsigned long long resampleSeed, int device, VcfGlRequest *gl)
-{
-    std::unique_ptr<BedFile, void (*)(BedFile *)> b(new BedFile, closeBedFile);
-    b->path = vcffile;
-    b->phased = phased;
-    const size_t SLAB = (size_t)64 << 20;
-    // first pass: the header, the nine fixed columns of every data line, and which lines are kept -- the row count that
-    // garlic_bed_create needs
-    std::vector<char> kept;                // per data line
-    samples.clear();
-    {
-        vcf::Reader rd;
-        if (!rd.open(vcffile, SLAB)) fail(rd.error);
-        vcf::SlabLines cut;
-        size_t used = 0;
-        std::string err;
-        do {
-            if (!rd.next(used)) fail(vcffile + ": " + rd.error);
-            used = cut.take(rd.slab.data(), rd.have, rd.eof);
-            if (!rd.eof && used == 0 && rd.have == rd.slab.size()) fail(vcffile + ": a line longer than 64 MB");
-            for (size_t k = 0; k < cut.begin.size(); k++) {
-                const char *line = rd.slab.data() + cut.begin[k];
-                const size_t len = (size_t)(cut.end[k] - cut.begin[k]);
-                const std::string where = "line " + std::to_string(cut.number[k]) + " of " + vcffile + ": ";
-                if (line[0] == '#') {
-                    if (len >= 6 && memcmp(line, "#CHROM", 6) == 0 && !vcf::parseHeader(line, len, samples, err)) fail(where + err);
-                    continue;
-                }
-                if (samples.empty()) fail(where + "a data line before the #CHROM line");
-                vcf::Site site;
-                const vcf::LineKind kind = vcf::parseFixed(line, len, site, err);
-                if (kind == vcf::LINE_BAD || (kind == vcf::LINE_NOT_SNP && !snpsOnly))
-                    fail(where + err + (kind == vcf::LINE_NOT_SNP ? " (--vcf-biallelic-snps-only leaves such lines out)" : ""));
-                kept.push_back(kind == vcf::LINE_SNP);
-                if (kind != vcf::LINE_SNP) { b->skipped_non_snp++; continue; }
-                b->chr.push_back(site.chr); b->name.push_back(site.name); b->gpos.push_back(0.0); b->ppos.push_back((double)site.ppos);
-                b->a1.push_back(site.a1); b->a2.push_back(site.a2);
-            }
-        } while (!rd.eof || used < rd.have);
-    }
-    if (samples.empty()) fail("no #CHROM line in " + vcffile);
-    b->nind = (int)samples.size();
-    b->nrows = (long long)b->chr.size();
-    if (b->nrows < 1) fail("no loci in " + vcffile);
-    b->row_bytes = ((size_t)b->nind + 3) / 4;
-    b->order_row_bytes = ((size_t)b->nind + 7) / 8;
-    // second pass: the text to the device in slabs, one parse call per slab
-    const size_t slot = bedSlotOn(b.get(), device);
-    garlic_bed *bed = nullptr;
-    check(garlic_bed_create((garlic_ctx *)b->images[slot].ctx, b->nrows, b->nind, &bed), "garlic_bed_create");
-    b->images[slot].bed = bed;
-    // the likelihoods from the same slabs: one object of every sample's column per distinct device, and a buffer there that
-    // the slab is uploaded to once; on the loader's own device the genotype parse reads that buffer too
-    std::unique_ptr<TglsFile, void (*)(TglsFile *)> glFile(nullptr, closeTglsFile);
-    VcfDeviceSlabs slabs;          // (behind glFile: its buffers go before the contexts they came from)
-    if (gl) {
-        gl->file = nullptr;
-        gl->overflow = false;
-        if (gl->glType != "GQ" && gl->glType != "GL" && gl->glType != "PL") fail("Must choose GQ/GL/PL for genotype likelihood format");
-        glFile.reset(new TglsFile);
-        glFile->path = vcffile;
-        glFile->glType = gl->glType == "GQ" ? GARLIC_GL_GQ : gl->glType == "GL" ? GARLIC_GL_GL : GARLIC_GL_PL;
-        glFile->fileInd = b->nind;
-        for (int i = 0; i < b->nind; i++) glFile->cols.push_back(i);
-        glFile->nrows = b->nrows;
-        glFile->vcfKey = gl->key;
-        glFile->vcfHasMissing = gl->hasMissing;
-        glFile->vcfMissing = gl->missing;
-        glFile->vcfSnpsOnly = snpsOnly;
-        glFile->vcfSamples = samples;
-        std::vector<int> devs{device};
-        for (int d : gl->devices)
-            if (std::find(devs.begin(), devs.end(), d) == devs.end()) devs.push_back(d);
-        for (int d : devs) {
-            glFile->objects.push_back({d, 0, b->nind, nullptr, nullptr});
-            garlic_ctx *ctx = nullptr;
-            check(garlic_ctx_create(d, nullptr, &ctx), "garlic_ctx_create");
-            glFile->objects.back().ctx = ctx;
-            garlic_tgls *obj = nullptr;
-            check(garlic_tgls_create(ctx, b->nrows, b->nind, glFile->cols.data(), b->nind, &obj), "garlic_tgls_create");
-            glFile->objects.back().tgls = obj;
-            void *text = nullptr;
-            check(garlic_device_alloc(ctx, (int64_t)SLAB + 16, &text), "garlic_device_alloc");      // (the last piece lies inside)
-            slabs.on.push_back({ctx, obj, text});
-        }
-    }
-    {
-        vcf::Reader rd;
-        if (!rd.open(vcffile, SLAB)) fail(rd.error);
-        vcf::SlabLines cut;
-        size_t used = 0, data_line = 0;
-        long long row = 0;
-        std::vector<int64_t> lb, number, ends;
-        std::vector<int32_t> status;
-        do {
-            if (!rd.next(used)) fail(vcffile + ": " + rd.error);
-            used = cut.take(rd.slab.data(), rd.have, rd.eof);
-            lb.clear();
-            number.clear();
-            ends.clear();
-            int64_t last_end = 0;
-            for (size_t k = 0; k < cut.begin.size(); k++) {
-                if (rd.slab[(size_t)cut.begin[k]] == '#') continue;
-                if (data_line >= kept.size()) fail(vcffile + " changed while it was read");
-                if (!kept[data_line++]) continue;
-                lb.push_back(cut.begin[k]);
-                number.push_back(cut.number[k]);
-                ends.push_back(cut.end[k]);
-                last_end = cut.end[k];
-            }
-            if (lb.empty()) continue;
-            const int64_t n = (int64_t)lb.size();
-            if (row + n > b->nrows) fail(vcffile + " changed while it was read");
-            lb.push_back(last_end);
-            status.assign((size_t)(2 * n), 0);
-            // one upload per device; the first buffer stands on the image's device and serves both parses
-            for (auto &o : slabs.on) check(garlic_device_upload(o.ctx, o.text, rd.slab.data(), (int64_t)rd.have), "garlic_device_upload");
-            const int rc = slabs.on.empty()
-                               ? garlic_bed_set_rows_vcf(bed, rd.slab.data(), (int64_t)rd.have, lb.data(), row, n, status.data(), GARLIC_HOST)
-                               : garlic_bed_set_rows_vcf(bed, (const char *)slabs.on[0].text, (int64_t)rd.have, lb.data(), row, n, status.data(),
-                                                         GARLIC_DEVICE);
-            if (rc == GARLIC_ERR_INVALID) {
-                for (int64_t r = 0; r < n; r++)
-                    if (status[(size_t)(2 * r)]) {
-                        const int col = status[(size_t)(2 * r + 1)];
-                        fail("line " + std::to_string(number[(size_t)r]) + " of " + vcffile + ", sample " + std::to_string(col + 1) +
-                             (col < b->nind ? " (" + samples[(size_t)col] + ")" : std::string()) + ": " + garlic_hip_last_error());
-                    }
-            }
-            check(rc, "garlic_bed_set_rows_vcf");
-            for (size_t k = 0; k < slabs.on.size(); k++)
-                if (!vcfGlSlab(glFile.get(), slabs.on[k].obj, slabs.on[k].text, rd.slab.data(), (int64_t)rd.have, lb, ends, number, row)) {
-                    // the 65,537th distinct raw value: the objects are of no use; the genotypes go on from host text
-                    slabs.release();
-                    glFile.reset();
-                    gl->overflow = true;
-                    break;
-                }
-            row += n;
-        } while (!rd.eof || used < rd.have);
-        if (row != b->nrows) fail(vcffile + " changed while it was read");
-    }
-    slabs.release();
-    if (gl && !gl->overflow) gl->file = glFile.release();
-    // the host's copies, fetched once: genotypeAt, the phase readers, the genotype cache, and the source of further devices' images
-    b->own_rows.resize((size_t)b->nrows * b->row_bytes);
-    b->own_order.resize((size_t)b->nrows * b->order_row_bytes);
-    check(garlic_bed_get_rows(bed, 0, b->nrows, b->own_rows.data(), (int64_t)b->row_bytes, GARLIC_HOST), "garlic_bed_get_rows");
-    check(garlic_bed_get_order_rows(bed, 0, b->nrows, b->own_order.data(), (int64_t)b->order_row_bytes, GARLIC_HOST), "garlic_bed_get_order_rows");
-    b->rows = b->own_rows.data();
-    b->order = b->own_order.data();
-    b->refs = 1;
-    loadBedFile(b.release(), numLoci, numInd, hapDataByChr, mapDataByChr, freqDataByChr, nresample, resampleSeed, device);
-}
-
-bool loadTPEDDataOnDevice(const std::string &tpedfile, int &numLoci, int &numInd, std::vector<HapData *> **hapDataByChr,
-                          std::vector<MapData *> **mapDataByChr, std::vector<FreqData *> **freqDataByChr, char TPED_MISSING, bool PHASED,
-                          int nresample, unsigned long long resampleSeed, int device, std::string &refusal)
-{
-    refusal.clear();
-    if (TPED_MISSING == ' ' || TPED_MISSING == '\t' || TPED_MISSING == '\r' || TPED_MISSING == '\n') {
-        refusal = tpedfile + ": the missing character is a blank";
-        return false;
-    }
-    std::unique_ptr<BedFile, void (*)(BedFile *)> b(new BedFile, closeBedFile);
-    b->path = tpedfile;
-    b->phased = PHASED;
-    b->own_census = true;
-    b->none_allele = TPED_MISSING;
-    const size_t SLAB = (size_t)64 << 20;
-    // first pass: the four leading tokens of every line and the number of individuals -- what garlic_bed_create needs
-    {
-        tped::Reader rd;
-        if (!rd.open(tpedfile, SLAB)) { refusal = rd.error; return false; }      // (the host reader says what it says about that)
-        tped::SlabLines cut;
-        size_t used = 0;
-        do {
-            if (!rd.next(used)) fail(tpedfile + ": " + rd.error);
-            used = cut.take(rd.slab.data(), rd.have, rd.eof);
-            if (!rd.eof && used == 0 && rd.have == rd.slab.size()) fail(tpedfile + ": a line longer than 64 MB");
-            for (size_t k = 0; k < cut.begin.size(); k++) {
-                const char *line = rd.slab.data() + cut.begin[k];
-                const size_t len = (size_t)(cut.end[k] - cut.begin[k]);
-                if (b->chr.empty()) {
-                    b->nind = tped::individualsOf(line, len);
-                    if (b->nind < 1) {
-                        refusal = "line " + std::to_string(cut.number[k]) + " of " + tpedfile + ": no genotype columns";
-                        return false;
-                    }
-                }
-                tped::Lead lead;
-                tped::parseLead(line, len, lead);
-                b->chr.push_back(lead.chr); b->name.push_back(lead.name); b->gpos.push_back(lead.gpos); b->ppos.push_back(lead.ppos);
-            }
-        } while (!rd.eof || used < rd.have);
-    }
-    b->nrows = (long long)b->chr.size();
-    if (b->nrows < 1) fail("no loci in " + tpedfile);
-    b->row_bytes = ((size_t)b->nind + 3) / 4;
-    b->order_row_bytes = ((size_t)b->nind + 7) / 8;
-    b->a1.assign((size_t)b->nrows, TPED_MISSING);
-    b->a2.assign((size_t)b->nrows, TPED_MISSING);
-    // second pass: the text to the device in slabs, one parse call per slab
-    const size_t slot = bedSlotOn(b.get(), device);
-    garlic_bed *bed = nullptr;
-    check(garlic_bed_create((garlic_ctx *)b->images[slot].ctx, b->nrows, b->nind, &bed), "garlic_bed_create");
-    b->images[slot].bed = bed;
-    {
-        tped::Reader rd;
-        if (!rd.open(tpedfile, SLAB)) fail(rd.error);
-        tped::SlabLines cut;
-        size_t used = 0;
-        long long row = 0;
-        std::vector<int64_t> lb;
-        std::vector<int32_t> status;
-        do {
-            if (!rd.next(used)) fail(tpedfile + ": " + rd.error);
-            used = cut.take(rd.slab.data(), rd.have, rd.eof);
-            if (cut.begin.empty()) continue;
-            const int64_t n = (int64_t)cut.begin.size();
-            if (row + n > b->nrows) fail(tpedfile + " changed while it was read");
-            lb.assign(cut.begin.begin(), cut.begin.end());
-            lb.push_back(cut.end.back());
-            status.assign((size_t)(2 * n), 0);
-            const int rc = garlic_bed_set_rows_tped(bed, rd.slab.data(), (int64_t)rd.have, lb.data(), row, n, (uint8_t)TPED_MISSING,
-                                                    (uint8_t *)b->a1.data() + row, status.data(), GARLIC_HOST);
-            if (rc == GARLIC_ERR_INVALID) {
-                for (int64_t r = 0; r < n; r++)
-                    if (status[(size_t)(2 * r)]) {
-                        refusal = "line " + std::to_string(cut.number[(size_t)r]) + " of " + tpedfile + " is refused by the device reader (code " +
-                                  std::to_string(status[(size_t)(2 * r)]) + ": " + garlic_hip_last_error() + ")";
-                        return false;
-                    }
-            }
-            check(rc, "garlic_bed_set_rows_tped");
-            row += n;
-        } while (!rd.eof || used < rd.have);
-        if (row != b->nrows) fail(tpedfile + " changed while it was read");
-    }
-    // the host's copies, fetched once: genotypeAt, the phase readers, the genotype cache, and the source of further devices' images
-    b->own_rows.resize((size_t)b->nrows * b->row_bytes);
-    b->own_order.resize((size_t)b->nrows * b->order_row_bytes);
-    check(garlic_bed_get_rows(bed, 0, b->nrows, b->own_rows.data(), (int64_t)b->row_bytes, GARLIC_HOST), "garlic_bed_get_rows");
-    check(garlic_bed_get_order_rows(bed, 0, b->nrows, b->own_order.data(), (int64_t)b->order_row_bytes, GARLIC_HOST), "garlic_bed_get_order_rows");
-    b->rows = b->own_rows.data();
-    b->order = b->own_order.data();
-    b->refs = 1;
-    loadBedFile(b.release(), numLoci, numInd, hapDataByChr, mapDataByChr, freqDataByChr, nresample, resampleSeed, device);
-    return true;
-}
-
-void loadBedSubset(BedFile *full, const std::vector<int> &keep, int &numLoci, int &numInd, std::vector<HapData *> **hapDataByChr,
-                   std::vector<MapData *> **mapDataByChr, std::vector<FreqData *> **freqDataByChr, int nresample,
-                   unsigned long long resampleSeed, int device)
-{
-    if (keep.empty()) fail("no individuals kept of " + full->path);
-    for (size_t i = 0; i < keep.size(); i++)
-        if (keep[i] < 0 || keep[i] >= full->nind || (i && keep[i] <= keep[i - 1]))
-            fail("kept individuals must be ascending indices into the .fam of " + full->path);
-    BedFile *b = new BedFile;
-    b->path = full->path;
-    b->parent = full;
-    full->refs++;
-    b->keep = keep;
-    b->nind = (int)keep.size();
-    b->nrows = full->nrows;
-    b->row_bytes = ((size_t)b->nind + 3) / 4;
-    b->refs = 1;
-    loadBedFile(b, numLoci, numInd, hapDataByChr, mapDataByChr, freqDataByChr, nresample, resampleSeed, device);
-}
-
-static void loadBedFile(BedFile *b, int &numLoci, int &numInd, std::vector<HapData *> **hapDataByChr,
-                        std::vector<MapData *> **mapDataByChr, std::vector<FreqData *> **freqDataByChr, int nresample,
                         unsigned long long resampleSeed, int device)
 {
     const BedFile *bim = b->bim();      // the .bim columns: the parent's for a subset
@@ -1030,6 +736,347 @@ static void loadBedFile(BedFile *b, int &numLoci, int &numInd, std::vector<HapDa
     numLoci = (int)b->nrows;
     numInd = b->nind;
     b->refs--;                   // at least one HapData holds the file now
+}
+
+void loadBedData(const std::string &bedfile, const std::string &bimfile, const std::string &famfile, int &numLoci, int &numInd,
+                 std::vector<HapData *> **hapDataByChr, std::vector<MapData *> **mapDataByChr,
+                 std::vector<FreqData *> **freqDataByChr, int nresample, unsigned long long resampleSeed, int device)
+{
+    BedFile *b = openBedFile(bedfile, bimfile, famfile);
+    b->refs = 1;                 // this function's, until the HapData hold theirs
+    loadBedFile(b, numLoci, numInd, hapDataByChr, mapDataByChr, freqDataByChr, nresample, resampleSeed, device);
+}
+
+[[noreturn]] static void refuseVcfLine(const TglsFile *f, int64_t line, int col, const std::string &why)
+{
+    fail("line " + std::to_string(line) + " of " + f->path +
+         (col >= 0 ? ", sample " + std::to_string(col + 1) + (col < (int)f->vcfSamples.size() ? " (" + f->vcfSamples[(size_t)col] + ")" : std::string()) : std::string()) +
+         ": " + why);
+}
+
+// One slab of loadVcfData into obj: rows [row, row + n) from the lines lb (n + 1 offsets; ends: where each stops; number: its
+// line in the file) of the text that stands on obj's device at d_text and in host memory at h_text.  A row the device defers
+// is parsed by vcf::parseGlValues; a refused line ends the run.  false: the 65,537th distinct raw value.
+static bool vcfGlSlab(const TglsFile *f, garlic_tgls *obj, const void *d_text, const char *h_text, int64_t text_bytes,
+                      const std::vector<int64_t> &lb, const std::vector<int64_t> &ends, const std::vector<int64_t> &number, long long row)
+{
+    const int64_t n = (int64_t)lb.size() - 1;
+    const double *missing = f->vcfHasMissing ? &f->vcfMissing : nullptr;
+    std::vector<int32_t> status((size_t)(2 * n), 0);
+    int rc = garlic_tgls_set_rows_vcf(obj, (const char *)d_text, text_bytes, lb.data(), row, n, f->vcfKey.c_str(), missing, status.data(),
+                                      GARLIC_DEVICE);
+    if (rc == GARLIC_ERR_RANGE) return false;
+    if (rc == GARLIC_ERR_INVALID)
+        for (int64_t r = 0; r < n; r++) {
+            const int code = status[(size_t)(2 * r)], col = status[(size_t)(2 * r + 1)];
+            if (code == GARLIC_TGLS_VCF_NO_KEY) refuseVcfLine(f, number[(size_t)r], -1, "FORMAT does not name " + f->vcfKey);
+            else if (code == GARLIC_TGLS_VCF_NO_VALUE)
+                refuseVcfLine(f, number[(size_t)r], col, "a called genotype without " + f->vcfKey + " (--vcf-gl-missing X gives such genotypes the raw value X)");
+            else if (code >= GARLIC_TGLS_FEW_COLUMNS)
+                refuseVcfLine(f, number[(size_t)r], -1, code == GARLIC_TGLS_FEW_COLUMNS ? "too few sample columns" : "too many sample columns");
+        }
+    check(rc, "garlic_tgls_set_rows_vcf");
+    std::vector<double> vals((size_t)f->fileInd);
+    std::string err;
+    for (int64_t r = 0; r < n; r++) {
+        if (status[(size_t)(2 * r)] != GARLIC_TGLS_DEFERRED) continue;
+        int sample = -1;
+        if (!vcf::parseGlValues(h_text + lb[(size_t)r], (size_t)(ends[(size_t)r] - lb[(size_t)r]), f->vcfKey, f->fileInd, nullptr, vals.size(), missing,
+                                vals.data(), sample, err))
+            refuseVcfLine(f, number[(size_t)r], sample, err);
+        rc = garlic_tgls_set_rows_values(obj, vals.data(), (int64_t)vals.size(), row + r, 1, GARLIC_HOST);
+        if (rc == GARLIC_ERR_RANGE) return false;
+        check(rc, "garlic_tgls_set_rows_values");
+    }
+    return true;
+}
+
+// the empty image of a text file's rows on the loader's device, and -- when the parse has filled it -- the host's copies of
+// its rows, fetched once: genotypeAt, the phase readers, the genotype cache, and the source of further devices' images
+static garlic_bed *createParsedImage(BedFile *b, int device)
+{
+    const size_t slot = bedSlotOn(b, device);
+    garlic_bed *bed = nullptr;
+    check(garlic_bed_create((garlic_ctx *)b->images[slot].ctx, b->nrows, b->nind, &bed), "garlic_bed_create");
+    b->images[slot].bed = bed;
+    return bed;
+}
+
+static void fetchParsedRows(BedFile *b, garlic_bed *bed)
+{
+    b->own_rows.resize((size_t)b->nrows * b->row_bytes);
+    b->own_order.resize((size_t)b->nrows * b->order_row_bytes);
+    check(garlic_bed_get_rows(bed, 0, b->nrows, b->own_rows.data(), (int64_t)b->row_bytes, GARLIC_HOST), "garlic_bed_get_rows");
+    check(garlic_bed_get_order_rows(bed, 0, b->nrows, b->own_order.data(), (int64_t)b->order_row_bytes, GARLIC_HOST), "garlic_bed_get_order_rows");
+    b->rows = b->own_rows.data();
+    b->order = b->own_order.data();
+}
+
+// text::forEachSlab for a loader that gives up on a file it cannot read; longLine: what it says about a line that fills a
+// slab.  false: onSlab stopped the walk.
+template <class OnSlab>
+static bool slabsOrFail(const std::string &path, size_t slabBytes, const std::string &longLine, OnSlab onSlab)
+{
+    std::string error;
+    const text::SlabsEnd end = text::forEachSlab(path, slabBytes, error, onSlab);
+    if (end == text::SLABS_NO_FILE) fail(error);
+    if (end == text::SLABS_READ_ERROR) fail(path + ": " + error);
+    if (end == text::SLABS_LONG_LINE) fail(longLine);
+    return end == text::SLABS_DONE;
+}
+
+// the loader's slab of text on the devices that parse it: one buffer per likelihood object, freed with the scope
+struct VcfDeviceSlabs {
+    struct One { garlic_ctx *ctx; garlic_tgls *obj; void *text; };
+    std::vector<One> on;
+    void release()
+    {
+        for (One &o : on) garlic_device_free(o.ctx, o.text);
+        on.clear();
+    }
+    ~VcfDeviceSlabs() { release(); }
+};
+
+void loadVcfData(const std::string &vcffile, bool phased, bool snpsOnly, std::vector<std::string> &samples, int &numLoci, int &numInd,
+                 std::vector<HapData *> **hapDataByChr, std::vector<MapData *> **mapDataByChr, std::vector<FreqData *> **freqDataByChr,
+                 int nresample, unsigned long long resampleSeed, int device, VcfGlRequest *gl)
+{
+    std::unique_ptr<BedFile, void (*)(BedFile *)> b(new BedFile, closeBedFile);
+    b->path = vcffile;
+    b->phased = phased;
+    const size_t SLAB = (size_t)64 << 20;
+    // first pass: the header, the nine fixed columns of every data line, and which lines are kept -- the row count that
+    // garlic_bed_create needs
+    std::vector<char> kept;                // per data line
+    samples.clear();
+    {
+        std::string err;
+        slabsOrFail(vcffile, SLAB, vcffile + ": a line longer than 64 MB", [&](const text::Reader &rd, const text::SlabLines &cut, size_t) {
+            for (size_t k = 0; k < cut.begin.size(); k++) {
+                const char *line = rd.slab.data() + cut.begin[k];
+                const size_t len = (size_t)(cut.end[k] - cut.begin[k]);
+                const std::string where = "line " + std::to_string(cut.number[k]) + " of " + vcffile + ": ";
+                if (line[0] == '#') {
+                    if (len >= 6 && memcmp(line, "#CHROM", 6) == 0 && !vcf::parseHeader(line, len, samples, err)) fail(where + err);
+                    continue;
+                }
+                if (samples.empty()) fail(where + "a data line before the #CHROM line");
+                vcf::Site site;
+                const vcf::LineKind kind = vcf::parseFixed(line, len, site, err);
+                if (kind == vcf::LINE_BAD || (kind == vcf::LINE_NOT_SNP && !snpsOnly))
+                    fail(where + err + (kind == vcf::LINE_NOT_SNP ? " (--vcf-biallelic-snps-only leaves such lines out)" : ""));
+                kept.push_back(kind == vcf::LINE_SNP);
+                if (kind != vcf::LINE_SNP) { b->skipped_non_snp++; continue; }
+                b->chr.push_back(site.chr); b->name.push_back(site.name); b->gpos.push_back(0.0); b->ppos.push_back((double)site.ppos);
+                b->a1.push_back(site.a1); b->a2.push_back(site.a2);
+            }
+            return true;
+        });
+    }
+    if (samples.empty()) fail("no #CHROM line in " + vcffile);
+    b->nind = (int)samples.size();
+    b->nrows = (long long)b->chr.size();
+    if (b->nrows < 1) fail("no loci in " + vcffile);
+    b->row_bytes = ((size_t)b->nind + 3) / 4;
+    b->order_row_bytes = ((size_t)b->nind + 7) / 8;
+    // second pass: the text to the device in slabs, one parse call per slab
+    garlic_bed *bed = createParsedImage(b.get(), device);
+    // the likelihoods from the same slabs: one object of every sample's column per distinct device, and a buffer there that
+    // the slab is uploaded to once; on the loader's own device the genotype parse reads that buffer too
+    std::unique_ptr<TglsFile, void (*)(TglsFile *)> glFile(nullptr, closeTglsFile);
+    VcfDeviceSlabs slabs;          // (behind glFile: its buffers go before the contexts they came from)
+    if (gl) {
+        gl->file = nullptr;
+        gl->overflow = false;
+        if (gl->glType != "GQ" && gl->glType != "GL" && gl->glType != "PL") fail("Must choose GQ/GL/PL for genotype likelihood format");
+        glFile.reset(new TglsFile);
+        glFile->path = vcffile;
+        glFile->glType = gl->glType == "GQ" ? GARLIC_GL_GQ : gl->glType == "GL" ? GARLIC_GL_GL : GARLIC_GL_PL;
+        glFile->fileInd = b->nind;
+        for (int i = 0; i < b->nind; i++) glFile->cols.push_back(i);
+        glFile->nrows = b->nrows;
+        glFile->vcfKey = gl->key;
+        glFile->vcfHasMissing = gl->hasMissing;
+        glFile->vcfMissing = gl->missing;
+        glFile->vcfSnpsOnly = snpsOnly;
+        glFile->vcfSamples = samples;
+        std::vector<int> devs{device};
+        for (int d : gl->devices)
+            if (std::find(devs.begin(), devs.end(), d) == devs.end()) devs.push_back(d);
+        for (int d : devs) {
+            glFile->objects.push_back({d, 0, b->nind, nullptr, nullptr});
+            garlic_ctx *ctx = nullptr;
+            check(garlic_ctx_create(d, nullptr, &ctx), "garlic_ctx_create");
+            glFile->objects.back().ctx = ctx;
+            garlic_tgls *obj = nullptr;
+            check(garlic_tgls_create(ctx, b->nrows, b->nind, glFile->cols.data(), b->nind, &obj), "garlic_tgls_create");
+            glFile->objects.back().tgls = obj;
+            void *text = nullptr;
+            check(garlic_device_alloc(ctx, (int64_t)SLAB + 16, &text), "garlic_device_alloc");      // (the last piece lies inside)
+            slabs.on.push_back({ctx, obj, text});
+        }
+    }
+    {
+        size_t data_line = 0;
+        long long row = 0;
+        std::vector<int64_t> lb, number, ends;
+        std::vector<int32_t> status;
+        // (a line longer than the slab: the first pass met none)
+        slabsOrFail(vcffile, SLAB, vcffile + " changed while it was read", [&](const text::Reader &rd, const text::SlabLines &cut, size_t) {
+            lb.clear();
+            number.clear();
+            ends.clear();
+            int64_t last_end = 0;
+            for (size_t k = 0; k < cut.begin.size(); k++) {
+                if (rd.slab[(size_t)cut.begin[k]] == '#') continue;
+                if (data_line >= kept.size()) fail(vcffile + " changed while it was read");
+                if (!kept[data_line++]) continue;
+                lb.push_back(cut.begin[k]);
+                number.push_back(cut.number[k]);
+                ends.push_back(cut.end[k]);
+                last_end = cut.end[k];
+            }
+            if (lb.empty()) return true;
+            const int64_t n = (int64_t)lb.size();
+            if (row + n > b->nrows) fail(vcffile + " changed while it was read");
+            lb.push_back(last_end);
+            status.assign((size_t)(2 * n), 0);
+            // one upload per device; the first buffer stands on the image's device and serves both parses
+            for (auto &o : slabs.on) check(garlic_device_upload(o.ctx, o.text, rd.slab.data(), (int64_t)rd.have), "garlic_device_upload");
+            const int rc = slabs.on.empty()
+                               ? garlic_bed_set_rows_vcf(bed, rd.slab.data(), (int64_t)rd.have, lb.data(), row, n, status.data(), GARLIC_HOST)
+                               : garlic_bed_set_rows_vcf(bed, (const char *)slabs.on[0].text, (int64_t)rd.have, lb.data(), row, n, status.data(),
+                                                         GARLIC_DEVICE);
+            if (rc == GARLIC_ERR_INVALID) {
+                for (int64_t r = 0; r < n; r++)
+                    if (status[(size_t)(2 * r)]) {
+                        const int col = status[(size_t)(2 * r + 1)];
+                        fail("line " + std::to_string(number[(size_t)r]) + " of " + vcffile + ", sample " + std::to_string(col + 1) +
+                             (col < b->nind ? " (" + samples[(size_t)col] + ")" : std::string()) + ": " + garlic_hip_last_error());
+                    }
+            }
+            check(rc, "garlic_bed_set_rows_vcf");
+            for (size_t k = 0; k < slabs.on.size(); k++)
+                if (!vcfGlSlab(glFile.get(), slabs.on[k].obj, slabs.on[k].text, rd.slab.data(), (int64_t)rd.have, lb, ends, number, row)) {
+                    // the 65,537th distinct raw value: the objects are of no use; the genotypes go on from host text
+                    slabs.release();
+                    glFile.reset();
+                    gl->overflow = true;
+                    break;
+                }
+            row += n;
+            return true;
+        });
+        if (row != b->nrows) fail(vcffile + " changed while it was read");
+    }
+    slabs.release();
+    if (gl && !gl->overflow) gl->file = glFile.release();
+    b->refs = 1;
+    fetchParsedRows(b.get(), bed);
+    loadBedFile(b.release(), numLoci, numInd, hapDataByChr, mapDataByChr, freqDataByChr, nresample, resampleSeed, device);
+}
+
+bool loadTPEDDataOnDevice(const std::string &tpedfile, int &numLoci, int &numInd, std::vector<HapData *> **hapDataByChr,
+                          std::vector<MapData *> **mapDataByChr, std::vector<FreqData *> **freqDataByChr, char TPED_MISSING, bool PHASED,
+                          int nresample, unsigned long long resampleSeed, int device, std::string &refusal)
+{
+    refusal.clear();
+    if (TPED_MISSING == ' ' || TPED_MISSING == '\t' || TPED_MISSING == '\r' || TPED_MISSING == '\n') {
+        refusal = tpedfile + ": the missing character is a blank";
+        return false;
+    }
+    std::unique_ptr<BedFile, void (*)(BedFile *)> b(new BedFile, closeBedFile);
+    b->path = tpedfile;
+    b->phased = PHASED;
+    b->own_census = true;
+    b->none_allele = TPED_MISSING;
+    const size_t SLAB = (size_t)64 << 20;
+    // first pass: the four leading tokens of every line and the number of individuals -- what garlic_bed_create needs
+    {
+        std::string error;
+        const text::SlabsEnd end = text::forEachSlab(tpedfile, SLAB, error, [&](const text::Reader &rd, const text::SlabLines &cut, size_t) {
+            for (size_t k = 0; k < cut.begin.size(); k++) {
+                const char *line = rd.slab.data() + cut.begin[k];
+                const size_t len = (size_t)(cut.end[k] - cut.begin[k]);
+                if (b->chr.empty()) {
+                    b->nind = tped::individualsOf(line, len);
+                    if (b->nind < 1) {
+                        refusal = "line " + std::to_string(cut.number[k]) + " of " + tpedfile + ": no genotype columns";
+                        return false;
+                    }
+                }
+                tped::Lead lead;
+                tped::parseLead(line, len, lead);
+                b->chr.push_back(lead.chr); b->name.push_back(lead.name); b->gpos.push_back(lead.gpos); b->ppos.push_back(lead.ppos);
+            }
+            return true;
+        });
+        if (end == text::SLABS_NO_FILE) refusal = error;      // (the host reader says what it says about that)
+        if (end == text::SLABS_NO_FILE || end == text::SLABS_STOPPED) return false;
+        if (end == text::SLABS_READ_ERROR) fail(tpedfile + ": " + error);
+        if (end == text::SLABS_LONG_LINE) fail(tpedfile + ": a line longer than 64 MB");
+    }
+    b->nrows = (long long)b->chr.size();
+    if (b->nrows < 1) fail("no loci in " + tpedfile);
+    b->row_bytes = ((size_t)b->nind + 3) / 4;
+    b->order_row_bytes = ((size_t)b->nind + 7) / 8;
+    b->a1.assign((size_t)b->nrows, TPED_MISSING);
+    b->a2.assign((size_t)b->nrows, TPED_MISSING);
+    // second pass: the text to the device in slabs, one parse call per slab
+    garlic_bed *bed = createParsedImage(b.get(), device);
+    {
+        long long row = 0;
+        std::vector<int64_t> lb;
+        std::vector<int32_t> status;
+        // (a line longer than the slab: the first pass met none)
+        const bool read = slabsOrFail(tpedfile, SLAB, tpedfile + " changed while it was read", [&](const text::Reader &rd, const text::SlabLines &cut, size_t) {
+            if (cut.begin.empty()) return true;
+            const int64_t n = (int64_t)cut.begin.size();
+            if (row + n > b->nrows) fail(tpedfile + " changed while it was read");
+            lb.assign(cut.begin.begin(), cut.begin.end());
+            lb.push_back(cut.end.back());
+            status.assign((size_t)(2 * n), 0);
+            const int rc = garlic_bed_set_rows_tped(bed, rd.slab.data(), (int64_t)rd.have, lb.data(), row, n, (uint8_t)TPED_MISSING,
+                                                    (uint8_t *)b->a1.data() + row, status.data(), GARLIC_HOST);
+            if (rc == GARLIC_ERR_INVALID) {
+                for (int64_t r = 0; r < n; r++)
+                    if (status[(size_t)(2 * r)]) {
+                        refusal = "line " + std::to_string(cut.number[(size_t)r]) + " of " + tpedfile + " is refused by the device reader (code " +
+                                  std::to_string(status[(size_t)(2 * r)]) + ": " + garlic_hip_last_error() + ")";
+                        return false;
+                    }
+            }
+            check(rc, "garlic_bed_set_rows_tped");
+            row += n;
+            return true;
+        });
+        if (!read) return false;       // (refusal says why)
+        if (row != b->nrows) fail(tpedfile + " changed while it was read");
+    }
+    b->refs = 1;
+    fetchParsedRows(b.get(), bed);
+    loadBedFile(b.release(), numLoci, numInd, hapDataByChr, mapDataByChr, freqDataByChr, nresample, resampleSeed, device);
+    return true;
+}
+
+void loadBedSubset(BedFile *full, const std::vector<int> &keep, int &numLoci, int &numInd, std::vector<HapData *> **hapDataByChr,
+                   std::vector<MapData *> **mapDataByChr, std::vector<FreqData *> **freqDataByChr, int nresample,
+                   unsigned long long resampleSeed, int device)
+{
+    if (keep.empty()) fail("no individuals kept of " + full->path);
+    for (size_t i = 0; i < keep.size(); i++)
+        if (keep[i] < 0 || keep[i] >= full->nind || (i && keep[i] <= keep[i - 1]))
+            fail("kept individuals must be ascending indices into the .fam of " + full->path);
+    BedFile *b = new BedFile;
+    b->path = full->path;
+    b->parent = full;
+    full->refs++;
+    b->keep = keep;
+    b->nind = (int)keep.size();
+    b->nrows = full->nrows;
+    b->row_bytes = ((size_t)b->nind + 3) / 4;
+    b->refs = 1;
+    loadBedFile(b, numLoci, numInd, hapDataByChr, mapDataByChr, freqDataByChr, nresample, resampleSeed, device);
 }
 
 void scanIndData3(const std::string &filename, int &numInd, std::string &popName)
@@ -1206,42 +1253,27 @@ std::vector<GenoLikeData *> *readTGLSData(const std::string &filename, int /*exp
 }
 
 // ---- the same file through the device (garlic_tgls): slabs of text up, rows of codes there, nothing per genotype here
-static void closeTglsFile(TglsFile *f)
-{
-    if (!f) return;
-    for (auto &o : f->objects) {
-        if (o.tgls) garlic_tgls_destroy((garlic_tgls *)o.tgls);
-        if (o.ctx) garlic_ctx_destroy((garlic_ctx *)o.ctx);
-    }
-    delete f;
-}
-
 // The file's first f->nrows lines into obj, whose kept columns are objCols: 64 MB slabs cut at line ends, one
 // garlic_tgls_set_rows_text per slab; a row the device defers is parsed here as readTGLSData parses it and handed over through
 // garlic_tgls_set_rows_values.  false: the 65,537th distinct raw value.
 static bool fillTglsObject(const TglsFile *f, garlic_tgls *obj, const std::vector<int> &objCols)
 {
     if (!f->vcfKey.empty()) fail(f->path + ": no likelihood object on this device (loadVcfData fills one per device it is told of)");
-    vcf::Reader rd;
-    if (!rd.open(f->path, (size_t)64 << 20)) fail(rd.error);
-    vcf::SlabLines cut;
     std::vector<int64_t> lb;
     std::vector<int32_t> status;
     std::vector<double> raw((size_t)f->fileInd), vals(objCols.size());
     std::string junk;
     long long done = 0;
-    size_t consumed = 0;
-    do {
-        if (!rd.next(consumed)) fail(f->path + ": " + rd.error);
-        consumed = cut.take(rd.slab.data(), rd.have, rd.eof);
-        if (!rd.eof && consumed == 0 && rd.have == rd.slab.size()) fail("a line of " + f->path + " is longer than a slab");
+    bool overflow = false;
+    slabsOrFail(f->path, (size_t)64 << 20, "a line of " + f->path + " is longer than a slab",
+                [&](const text::Reader &rd, const text::SlabLines &cut, size_t consumed) {
         const long long n = std::min<long long>((long long)cut.begin.size(), f->nrows - done);
         if (n > 0) {
             lb.assign(cut.begin.begin(), cut.begin.begin() + n);
             lb.push_back((size_t)n < cut.begin.size() ? cut.begin[(size_t)n] : (int64_t)consumed);
             status.assign((size_t)(2 * n), 0);
             int rc = garlic_tgls_set_rows_text(obj, rd.slab.data(), (int64_t)consumed, lb.data(), done, n, status.data(), GARLIC_HOST);
-            if (rc == GARLIC_ERR_RANGE) return false;
+            if (rc == GARLIC_ERR_RANGE) { overflow = true; return false; }
             auto lineOf = [&](long long r) { return std::string(rd.slab.data() + cut.begin[(size_t)r], (size_t)(cut.end[(size_t)r] - cut.begin[(size_t)r])); };
             for (long long r = 0; r < n; r++)
                 if (status[(size_t)(2 * r)] >= GARLIC_TGLS_FEW_COLUMNS)
@@ -1257,57 +1289,15 @@ static bool fillTglsObject(const TglsFile *f, garlic_tgls *obj, const std::vecto
                 for (double &v : raw) ss >> v;
                 for (size_t k = 0; k < objCols.size(); k++) vals[k] = raw[(size_t)objCols[k]];
                 rc = garlic_tgls_set_rows_values(obj, vals.data(), (int64_t)vals.size(), done + r, 1, GARLIC_HOST);
-                if (rc == GARLIC_ERR_RANGE) return false;
+                if (rc == GARLIC_ERR_RANGE) { overflow = true; return false; }
                 check(rc, "garlic_tgls_set_rows_values");
             }
             done += n;
         }
-    } while (done < f->nrows && (!rd.eof || consumed < rd.have));
+        return done < f->nrows;
+    });
+    if (overflow) return false;
     if (done < f->nrows) fail("too few lines in " + f->path);
-    return true;
-}
-
-[[noreturn]] static void refuseVcfLine(const TglsFile *f, int64_t line, int col, const std::string &why)
-{
-    fail("line " + std::to_string(line) + " of " + f->path +
-         (col >= 0 ? ", sample " + std::to_string(col + 1) + (col < (int)f->vcfSamples.size() ? " (" + f->vcfSamples[(size_t)col] + ")" : std::string()) : std::string()) +
-         ": " + why);
-}
-
-// One slab of loadVcfData into obj: rows [row, row + n) from the lines lb (n + 1 offsets; ends: where each stops; number: its
-// line in the file) of the text that stands on obj's device at d_text and in host memory at h_text.  A row the device defers
-// is parsed by vcf::parseGlValues; a refused line ends the run.  false: the 65,537th distinct raw value.
-static bool vcfGlSlab(const TglsFile *f, garlic_tgls *obj, const void *d_text, const char *h_text, int64_t text_bytes,
-                      const std::vector<int64_t> &lb, const std::vector<int64_t> &ends, const std::vector<int64_t> &number, long long row)
-{
-    const int64_t n = (int64_t)lb.size() - 1;
-    const double *missing = f->vcfHasMissing ? &f->vcfMissing : nullptr;
-    std::vector<int32_t> status((size_t)(2 * n), 0);
-    int rc = garlic_tgls_set_rows_vcf(obj, (const char *)d_text, text_bytes, lb.data(), row, n, f->vcfKey.c_str(), missing, status.data(),
-                                      GARLIC_DEVICE);
-    if (rc == GARLIC_ERR_RANGE) return false;
-    if (rc == GARLIC_ERR_INVALID)
-        for (int64_t r = 0; r < n; r++) {
-            const int code = status[(size_t)(2 * r)], col = status[(size_t)(2 * r + 1)];
-            if (code == GARLIC_TGLS_VCF_NO_KEY) refuseVcfLine(f, number[(size_t)r], -1, "FORMAT does not name " + f->vcfKey);
-            else if (code == GARLIC_TGLS_VCF_NO_VALUE)
-                refuseVcfLine(f, number[(size_t)r], col, "a called genotype without " + f->vcfKey + " (--vcf-gl-missing X gives such genotypes the raw value X)");
-            else if (code >= GARLIC_TGLS_FEW_COLUMNS)
-                refuseVcfLine(f, number[(size_t)r], -1, code == GARLIC_TGLS_FEW_COLUMNS ? "too few sample columns" : "too many sample columns");
-        }
-    check(rc, "garlic_tgls_set_rows_vcf");
-    std::vector<double> vals((size_t)f->fileInd);
-    std::string err;
-    for (int64_t r = 0; r < n; r++) {
-        if (status[(size_t)(2 * r)] != GARLIC_TGLS_DEFERRED) continue;
-        int sample = -1;
-        if (!vcf::parseGlValues(h_text + lb[(size_t)r], (size_t)(ends[(size_t)r] - lb[(size_t)r]), f->vcfKey, f->fileInd, nullptr, vals.size(), missing,
-                                vals.data(), sample, err))
-            refuseVcfLine(f, number[(size_t)r], sample, err);
-        rc = garlic_tgls_set_rows_values(obj, vals.data(), (int64_t)vals.size(), row + r, 1, GARLIC_HOST);
-        if (rc == GARLIC_ERR_RANGE) return false;
-        check(rc, "garlic_tgls_set_rows_values");
-    }
     return true;
 }
 
@@ -1333,99 +1323,6 @@ static garlic_tgls *tglsObjectOn(TglsFile *f, int device, int ind_begin, int nin
     return obj;
 }
 
-static std::vector<GenoLikeData *> *tglsFileOnDevice(std::unique_ptr<TglsFile, void (*)(TglsFile *)> &f, int expectedInd,
-                                                     std::vector<MapData *> *maps, int device);
-
-std::vector<GenoLikeData *> *loadTGLSFile(const std::string &filename, int expectedInd, std::vector<MapData *> *maps,
-                                          const std::string &GL_TYPE, const std::vector<int> *cols, int fileInd, int device)
-{
-    if (cols && (int)cols->size() != expectedInd) fail("loadTGLSFile: one column per kept individual is needed");
-    if (GL_TYPE != "GQ" && GL_TYPE != "GL" && GL_TYPE != "PL") fail("Must choose GQ/GL/PL for genotype likelihood format");
-    std::unique_ptr<TglsFile, void (*)(TglsFile *)> f(new TglsFile, closeTglsFile);
-    f->path = filename;
-    f->glType = GL_TYPE == "GQ" ? GARLIC_GL_GQ : GL_TYPE == "GL" ? GARLIC_GL_GL : GARLIC_GL_PL;
-    f->fileInd = cols ? fileInd : expectedInd;
-    if (cols) f->cols = *cols;
-    else for (int i = 0; i < expectedInd; i++) f->cols.push_back(i);
-    for (int c : f->cols)
-        if (c < 0 || c >= f->fileInd) fail("loadTGLSFile: a kept column outside the file's columns");
-    auto *out = tglsFileOnDevice(f, expectedInd, maps, device);
-    if (!out) std::cerr << filename << " holds more than 65,536 distinct values: read by the host reader instead\n";
-    return out;
-}
-
-static std::vector<GenoLikeData *> *glDataOfTglsFile(std::unique_ptr<TglsFile, void (*)(TglsFile *)> &f, int expectedInd,
-                                                     std::vector<MapData *> *maps);
-
-// The likelihoods loadVcfData left in `gl`: the GenoLikeData of its device objects, or -- a field of more than 65,536 distinct
-// raw values -- the file read once more on the host, line by line through vcf::parseGlValues, into readTGLSData's compact forms
-std::vector<GenoLikeData *> *vcfGlData(VcfGlRequest &gl, const std::string &vcffile, bool snpsOnly, const std::vector<std::string> &samples,
-                                       std::vector<MapData *> *maps)
-{
-    const int nind = (int)samples.size();
-    if (!gl.overflow) {
-        if (!gl.file) fail("vcfGlData: loadVcfData has not run with this request");
-        std::unique_ptr<TglsFile, void (*)(TglsFile *)> f(gl.file, closeTglsFile);
-        gl.file = nullptr;
-        long long rows = 0;
-        for (auto m : *maps) rows += m->nloci;
-        if (rows != f->nrows) fail("vcfGlData: the maps do not hold the loci that were read");
-        return glDataOfTglsFile(f, nind, maps);
-    }
-    std::cerr << vcffile << ": " << gl.key << " holds more than 65,536 distinct values: read by the host reader instead\n";
-    TglsFile names;
-    names.path = vcffile;
-    names.vcfSamples = samples;
-    vcf::Reader rd;
-    if (!rd.open(vcffile, (size_t)64 << 20)) fail(rd.error);
-    vcf::SlabLines cut;
-    size_t used = 0, at = 0;
-    bool first = true;
-    std::string err;
-    const double *missing = gl.hasMissing ? &gl.missing : nullptr;
-    return readGLRows(nind, maps, gl.glType, /*compact=*/true, [&](double *vals) {
-        for (;;) {
-            if (first || at >= cut.begin.size()) {
-                if (!first && rd.eof && used >= rd.have) fail(vcffile + " changed while it was read");
-                if (!rd.next(first ? 0 : used)) fail(vcffile + ": " + rd.error);
-                used = cut.take(rd.slab.data(), rd.have, rd.eof);
-                if (!rd.eof && used == 0 && rd.have == rd.slab.size()) fail(vcffile + ": a line longer than 64 MB");
-                first = false;
-                at = 0;
-                continue;
-            }
-            const size_t k = at++;
-            const char *line = rd.slab.data() + cut.begin[k];
-            const size_t len = (size_t)(cut.end[k] - cut.begin[k]);
-            if (line[0] == '#') continue;
-            vcf::Site site;
-            const vcf::LineKind kind = vcf::parseFixed(line, len, site, err);
-            if (kind == vcf::LINE_BAD || (kind == vcf::LINE_NOT_SNP && !snpsOnly)) refuseVcfLine(&names, cut.number[k], -1, err);
-            if (kind != vcf::LINE_SNP) continue;
-            int sample = -1;
-            if (!vcf::parseGlValues(line, len, gl.key, nind, nullptr, (size_t)nind, missing, vals, sample, err))
-                refuseVcfLine(&names, cut.number[k], sample, err);
-            return;
-        }
-    });
-}
-
-// f filled on `device` and one GenoLikeData per chromosome that points into it; NULL (f closed): a 65,537th distinct raw value
-static std::vector<GenoLikeData *> *tglsFileOnDevice(std::unique_ptr<TglsFile, void (*)(TglsFile *)> &f, int expectedInd,
-                                                     std::vector<MapData *> *maps, int device)
-{
-    for (auto m : *maps) f->nrows += m->nloci;
-    f->objects.push_back({device, 0, expectedInd, nullptr, nullptr});
-    garlic_ctx *ctx = nullptr;
-    check(garlic_ctx_create(device, nullptr, &ctx), "garlic_ctx_create");
-    f->objects.back().ctx = ctx;
-    garlic_tgls *obj = nullptr;
-    check(garlic_tgls_create(ctx, f->nrows, f->fileInd, f->cols.data(), expectedInd, &obj), "garlic_tgls_create");
-    f->objects.back().tgls = obj;
-    if (!fillTglsObject(f.get(), obj, f->cols)) return nullptr;
-    return glDataOfTglsFile(f, expectedInd, maps);
-}
-
 // one GenoLikeData per chromosome that points into f, whose first object is filled; f is theirs from here on
 static std::vector<GenoLikeData *> *glDataOfTglsFile(std::unique_ptr<TglsFile, void (*)(TglsFile *)> &f, int expectedInd,
                                                      std::vector<MapData *> *maps)
@@ -1449,6 +1346,85 @@ static std::vector<GenoLikeData *> *glDataOfTglsFile(std::unique_ptr<TglsFile, v
     }
     f.release();
     return out;
+}
+
+// f filled on `device` and one GenoLikeData per chromosome that points into it; NULL (f closed): a 65,537th distinct raw value
+static std::vector<GenoLikeData *> *tglsFileOnDevice(std::unique_ptr<TglsFile, void (*)(TglsFile *)> &f, int expectedInd,
+                                                     std::vector<MapData *> *maps, int device)
+{
+    for (auto m : *maps) f->nrows += m->nloci;
+    f->objects.push_back({device, 0, expectedInd, nullptr, nullptr});
+    garlic_ctx *ctx = nullptr;
+    check(garlic_ctx_create(device, nullptr, &ctx), "garlic_ctx_create");
+    f->objects.back().ctx = ctx;
+    garlic_tgls *obj = nullptr;
+    check(garlic_tgls_create(ctx, f->nrows, f->fileInd, f->cols.data(), expectedInd, &obj), "garlic_tgls_create");
+    f->objects.back().tgls = obj;
+    if (!fillTglsObject(f.get(), obj, f->cols)) return nullptr;
+    return glDataOfTglsFile(f, expectedInd, maps);
+}
+
+std::vector<GenoLikeData *> *loadTGLSFile(const std::string &filename, int expectedInd, std::vector<MapData *> *maps,
+                                          const std::string &GL_TYPE, const std::vector<int> *cols, int fileInd, int device)
+{
+    if (cols && (int)cols->size() != expectedInd) fail("loadTGLSFile: one column per kept individual is needed");
+    if (GL_TYPE != "GQ" && GL_TYPE != "GL" && GL_TYPE != "PL") fail("Must choose GQ/GL/PL for genotype likelihood format");
+    std::unique_ptr<TglsFile, void (*)(TglsFile *)> f(new TglsFile, closeTglsFile);
+    f->path = filename;
+    f->glType = GL_TYPE == "GQ" ? GARLIC_GL_GQ : GL_TYPE == "GL" ? GARLIC_GL_GL : GARLIC_GL_PL;
+    f->fileInd = cols ? fileInd : expectedInd;
+    if (cols) f->cols = *cols;
+    else for (int i = 0; i < expectedInd; i++) f->cols.push_back(i);
+    for (int c : f->cols)
+        if (c < 0 || c >= f->fileInd) fail("loadTGLSFile: a kept column outside the file's columns");
+    auto *out = tglsFileOnDevice(f, expectedInd, maps, device);
+    if (!out) std::cerr << filename << " holds more than 65,536 distinct values: read by the host reader instead\n";
+    return out;
+}
+
+// The likelihoods loadVcfData left in `gl`: the GenoLikeData of its device objects, or -- a field of more than 65,536 distinct
+// raw values -- the file read once more on the host, line by line through vcf::parseGlValues, into readTGLSData's compact forms
+std::vector<GenoLikeData *> *vcfGlData(VcfGlRequest &gl, const std::string &vcffile, bool snpsOnly, const std::vector<std::string> &samples,
+                                       std::vector<MapData *> *maps)
+{
+    const int nind = (int)samples.size();
+    if (!gl.overflow) {
+        if (!gl.file) fail("vcfGlData: loadVcfData has not run with this request");
+        std::unique_ptr<TglsFile, void (*)(TglsFile *)> f(gl.file, closeTglsFile);
+        gl.file = nullptr;
+        long long rows = 0;
+        for (auto m : *maps) rows += m->nloci;
+        if (rows != f->nrows) fail("vcfGlData: the maps do not hold the loci that were read");
+        return glDataOfTglsFile(f, nind, maps);
+    }
+    std::cerr << vcffile << ": " << gl.key << " holds more than 65,536 distinct values: read by the host reader instead\n";
+    TglsFile names;
+    names.path = vcffile;
+    names.vcfSamples = samples;
+    text::LineCursor in;
+    if (!in.rd.open(vcffile, (size_t)64 << 20)) fail(in.rd.error);
+    const text::SlabLines &cut = in.lines;
+    std::string err;
+    const double *missing = gl.hasMissing ? &gl.missing : nullptr;
+    return readGLRows(nind, maps, gl.glType, /*compact=*/true, [&](double *vals) {
+        for (;;) {
+            size_t k = 0;
+            if (!in.next(k))
+                fail(in.why == text::SLABS_DONE ? vcffile + " changed while it was read"
+                     : in.why == text::SLABS_READ_ERROR ? vcffile + ": " + in.rd.error : vcffile + ": a line longer than 64 MB");
+            const char *line = in.rd.slab.data() + cut.begin[k];
+            const size_t len = (size_t)(cut.end[k] - cut.begin[k]);
+            if (line[0] == '#') continue;
+            vcf::Site site;
+            const vcf::LineKind kind = vcf::parseFixed(line, len, site, err);
+            if (kind == vcf::LINE_BAD || (kind == vcf::LINE_NOT_SNP && !snpsOnly)) refuseVcfLine(&names, cut.number[k], -1, err);
+            if (kind != vcf::LINE_SNP) continue;
+            int sample = -1;
+            if (!vcf::parseGlValues(line, len, gl.key, nind, nullptr, (size_t)nind, missing, vals, sample, err))
+                refuseVcfLine(&names, cut.number[k], sample, err);
+            return;
+        }
+    });
 }
 
 std::vector<FreqData *> *readFreqData(const std::string &freqfile, std::vector<MapData *> *maps)

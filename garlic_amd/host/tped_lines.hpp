@@ -1,7 +1,7 @@
 // TPED text on the host: everything about a TPED line that is not an allele.  Header-only.
 //
 // The alleles of a line are parsed, coded and counted on the device (garlic_bed_set_rows_tped); the host reads the file
-// through the slab reader and line cutter of vcf_lines.hpp (zlib: plain text and .gz; a slab ends wherever the read ended, the
+// through the slab reader and line cutter of text_slabs.hpp (zlib: plain text and .gz; a slab ends wherever the read ended, the
 // file's last line needs no '\n', a '\r' before the '\n' belongs to the line and is a blank to the device; empty lines are
 // passed over) and of every line parses the four leading tokens
 //     chr  name  gpos  ppos
@@ -19,12 +19,12 @@
 #include <sstream>
 #include <string>
 
-#include "vcf_lines.hpp"
+#include "text_slabs.hpp"
 
 namespace tped {
 
-using vcf::Reader;
-using vcf::SlabLines;
+using text::Reader;
+using text::SlabLines;
 
 struct Lead {
     std::string chr, name;

@@ -7,12 +7,9 @@
 // checking that FORMAT begins with GT.  A line whose REF or ALT is not exactly one character (`,` lists, `.`, `*`, `<...>`
 // included) is no biallelic SNP: refused, or under skipNonSnp left out of line_begin and counted.
 //
-// The text goes to the device in slabs.  VcfSlabLines cuts a slab into lines with memchr: a slab ends wherever the read
-// ended, so the bytes behind its last '\n' are carried to the front of the next one; the file's last line needs no '\n', and
-// a '\r' before the '\n' belongs to the line (the device accepts it as the end of a genotype).
+// The text goes to the device in slabs of lines (text_slabs.hpp); a '\r' before the '\n' belongs to the line (the device
+// accepts it as the end of a genotype).
 #pragma once
-#include <zlib.h>
-
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
@@ -20,7 +17,12 @@
 #include <string>
 #include <vector>
 
+#include "text_slabs.hpp"
+
 namespace vcf {
+
+using text::Reader;          // the names the VCF readers have always used for them
+using text::SlabLines;
 
 struct Site {
     std::string chr, name;
@@ -160,94 +162,16 @@ inline bool parseGlValues(const char *line, size_t len, const std::string &key, 
     return true;
 }
 
-// One slab of text cut into lines.  take(slab, n, last): the lines that are complete in [slab, slab + n) -- all of them when
-// `last` (the file has ended: a final line without '\n' counts) -- as begin[k] / end[k] (end: the '\n' or n); returns the
-// number of bytes consumed: the caller moves the rest, slab[consumed .. n), to the front of the next slab.  Empty lines
-// are passed over.
-struct SlabLines {
-    std::vector<int64_t> begin, end, number;      // number: the line's 1-based number in the file, empty lines counted
-    int64_t seen = 0;                             // lines of the file taken so far
-    size_t take(const char *slab, size_t n, bool last)
-    {
-        begin.clear();
-        end.clear();
-        number.clear();
-        size_t at = 0;
-        while (at < n) {
-            const char *nl = (const char *)memchr(slab + at, '\n', n - at);
-            if (!nl && !last) break;
-            const size_t e = nl ? (size_t)(nl - slab) : n;
-            const bool blank = e == at || (e == at + 1 && slab[at] == '\r');
-            seen++;
-            if (!blank) {
-                begin.push_back((int64_t)at);
-                end.push_back((int64_t)e);
-                number.push_back(seen);
-            }
-            at = nl ? e + 1 : n;
-        }
-        return at;
-    }
-};
-
-// A VCF read through zlib in slabs of at most `cap` bytes.  next() fills the slab behind what the previous one left over;
-// false when the file has ended and nothing is left.
-struct Reader {
-    gzFile f = nullptr;
-    std::vector<char> slab;
-    size_t have = 0;          // bytes of the slab in use
-    bool eof = false;
-    std::string error;
-    bool open(const std::string &path, size_t cap)
-    {
-        f = gzopen(path.c_str(), "rb");
-        if (!f) { error = "cannot open " + path; return false; }
-        gzbuffer(f, 1 << 20);
-        slab.resize(cap);
-        have = 0;
-        eof = false;
-        return true;
-    }
-    // drop the first `consumed` bytes and read on; returns false on a read error (error set) -- at the end of the file it
-    // returns true with eof set and have = what was left
-    bool next(size_t consumed)
-    {
-        memmove(slab.data(), slab.data() + consumed, have - consumed);
-        have -= consumed;
-        while (!eof && have < slab.size()) {
-            const size_t want = slab.size() - have;
-            const int got = gzread(f, slab.data() + have, (unsigned)(want < (1u << 30) ? want : (1u << 30)));
-            if (got < 0) { int e; error = gzerror(f, &e); return false; }
-            if (got == 0) {
-                // a truncated .gz hands out what it has and leaves Z_BUF_ERROR behind: no clean end of the file
-                int e = Z_OK;
-                const char *msg = gzerror(f, &e);
-                if (e != Z_OK && e != Z_STREAM_END) { error = std::string("read error (truncated file?): ") + msg; return false; }
-                eof = true;
-            }
-            have += (size_t)got;
-        }
-        return true;
-    }
-    void close() { if (f) gzclose(f); f = nullptr; }
-    ~Reader() { close(); }
-};
-
 // lines of a file that do not start with '#': the counting pass in front of garlic_bed_create
 inline bool countDataLines(const std::string &path, int64_t &nlines, std::string &err)
 {
-    Reader rd;
-    if (!rd.open(path, 1 << 22)) { err = rd.error; return false; }
-    SlabLines cut;
     nlines = 0;
-    size_t consumed = 0;
-    do {
-        if (!rd.next(consumed)) { err = rd.error; return false; }
-        consumed = cut.take(rd.slab.data(), rd.have, rd.eof);
+    const text::SlabsEnd end = text::forEachSlab(path, 1 << 22, err, [&](const text::Reader &rd, const text::SlabLines &cut, size_t) {
         for (int64_t b : cut.begin) nlines += rd.slab[(size_t)b] != '#';
-        if (!rd.eof && consumed == 0 && rd.have == rd.slab.size()) { err = "a line longer than the slab"; return false; }
-    } while (!rd.eof || consumed < rd.have);
-    return true;
+        return true;
+    });
+    if (end == text::SLABS_LONG_LINE) err = "a line longer than the slab";
+    return end == text::SLABS_DONE;
 }
 
 } // namespace vcf
