@@ -27,6 +27,9 @@ TGLS_DICTIONARY, TGLS_CONTINUOUS, TGLS_DICTIONARY16 = 1, 2, 3   # garlic_panel_t
 # GARLIC_TGLS_*: what garlic_tgls_set_rows_text answers per row; TGLS_RAW: gl_type of garlic_tgls_get_rows without conversion
 TGLS_OK, TGLS_DEFERRED, TGLS_FEW_COLUMNS, TGLS_MANY_COLUMNS, TGLS_RAW = 0, 1, 2, 3, -1
 TGLS_VCF_NO_KEY, TGLS_VCF_NO_VALUE = 4, 5   # garlic_tgls_set_rows_vcf's own
+# GARLIC_BGZF_*: what garlic_bgzf_inflate answers per block
+(BGZF_OK, BGZF_BAD_BLOCK_TYPE, BGZF_BAD_CODE_LENGTHS, BGZF_BAD_SYMBOL, BGZF_BAD_DISTANCE, BGZF_INPUT_ENDED, BGZF_OUTPUT_FULL,
+ BGZF_OUTPUT_SHORT, BGZF_BAD_CRC) = range(9)
 GL_GQ, GL_GL, GL_PL = 0, 1, 2
 MISSING = -9999.0
 
@@ -69,6 +72,7 @@ SYMBOLS = [
     "garlic_kde_part_set_create", "garlic_lod_kde_part_set", "garlic_kde_part_set_destroy", "garlic_kde_part_set_counts",
     "garlic_kde_part_set_moment", "garlic_kde_part_set_rank", "garlic_kde_part_set_sums", "garlic_kde_parts_multi",
     "garlic_kde_parts_multi_info",
+    "garlic_bgzf_inflate", "garlic_text_lines", "garlic_device_download", "garlic_device_copy",
 ]
 FEATURE_MAX_EFFECTS = 256   # GARLIC_FEATURE_MAX_EFFECTS
 FEATURE_GROUP_EFFECTS = 32  # effects per launch
@@ -264,6 +268,11 @@ def lib():
     L.garlic_tgls_set_rows_text.argtypes = [_vp, _vp, C.c_int64, _i64p, C.c_int64, C.c_int64, _vp, C.c_int32]
     L.garlic_tgls_set_rows_vcf.argtypes = [_vp, _vp, C.c_int64, _i64p, C.c_int64, C.c_int64, C.c_char_p, _f64p, _vp, C.c_int32]
     L.garlic_device_upload.argtypes = [_vp, _vp, _vp, C.c_int64]
+    L.garlic_device_download.argtypes = [_vp, _vp, _vp, C.c_int64]
+    L.garlic_device_copy.argtypes = [_vp, _vp, _vp, C.c_int64]
+    L.garlic_bgzf_inflate.argtypes = [_vp, _vp, C.c_int64, _i64p, C.c_int64, _vp, _i64p, _i32p, C.c_int32]
+    L.garlic_text_lines.argtypes = [_vp, _vp, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _i64p, _i64p, _i64p, _vp, _i64p, _i64p,
+                                    _i64p]
     L.garlic_tgls_set_rows_values.argtypes = [_vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32]
     L.garlic_tgls_get_rows.argtypes = [_vp, C.c_int32, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_int32]
     L.garlic_tgls_info.argtypes = [_vp, _i32p, _i64p, _i64p]
@@ -754,6 +763,75 @@ class DeviceBuffer:
             self.free()
         except Exception:
             pass
+
+
+def device_upload(ctx, dst_ptr, data):
+    """garlic_device_upload: bytes / a contiguous numpy array to device address dst_ptr"""
+    buf = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data).view(np.uint8).ravel()
+    if buf.shape[0]:
+        check(lib().garlic_device_upload(ctx.handle, _vp(dst_ptr), _vp(buf.ctypes.data), buf.shape[0]))
+
+
+def device_download(ctx, src_ptr, nbytes):
+    """garlic_device_download: nbytes from device address src_ptr as a uint8 array"""
+    out = np.empty(int(nbytes), dtype=np.uint8)
+    if nbytes:
+        check(lib().garlic_device_download(ctx.handle, _vp(out.ctypes.data), _vp(src_ptr), int(nbytes)))
+    return out
+
+
+def device_copy(ctx, dst_ptr, src_ptr, nbytes):
+    """garlic_device_copy: nbytes between device ranges that do not overlap"""
+    check(lib().garlic_device_copy(ctx.handle, _vp(dst_ptr), _vp(src_ptr), int(nbytes)))
+
+
+def bgzf_inflate(ctx, comp, block_begin, out_ptr, out_begin, comp_bytes=None, where=HOST):
+    """garlic_bgzf_inflate: the BGZF blocks comp[block_begin[b], block_begin[b + 1]) to device memory out_ptr[out_begin[b],
+    out_begin[b + 1]).  comp: bytes / uint8 array (host), or a device address with comp_bytes and where=DEVICE.
+    Returns (status int32 [nblocks], error or None): a bad block fills its status and comes back as the GarlicError instead
+    of being raised, so that a caller sees both."""
+    bb = np.ascontiguousarray(block_begin, dtype=np.int64)
+    ob = np.ascontiguousarray(out_begin, dtype=np.int64)
+    assert bb.ndim == 1 and bb.shape == ob.shape and bb.shape[0] >= 1
+    if where == HOST:
+        buf = np.frombuffer(comp, dtype=np.uint8) if isinstance(comp, (bytes, bytearray)) else np.asarray(comp)
+        assert buf.dtype == np.uint8 and buf.ndim == 1
+        ptr, comp_bytes = buf.ctypes.data, buf.shape[0] if comp_bytes is None else comp_bytes
+    else:
+        ptr = int(comp)
+    status = np.zeros(bb.shape[0] - 1, dtype=np.int32)
+    rc = lib().garlic_bgzf_inflate(ctx.handle, _vp(ptr), int(comp_bytes), _ptr(bb, _i64p), bb.shape[0] - 1, _vp(out_ptr), _ptr(ob, _i64p),
+                                   _ptr(status, _i32p), where)
+    err = None
+    if rc != OK:
+        err = GarlicError(rc, lib().garlic_hip_last_error().decode())
+        if rc != ERR_INVALID or not status.any():
+            raise err
+    return status, err
+
+
+def text_lines(ctx, text_ptr, text_bytes, last, seen=0, head_bytes=0, capacity=None):
+    """garlic_text_lines: the line index of the device text text_ptr[0, text_bytes), as SlabLines::take gives it.  capacity
+    None: asked for with a first call without room (GARLIC_ERR_RANGE reports the count); a number: that much room, and
+    the GarlicError (ERR_RANGE) when the slab holds more.  Returns a dict: begin, end, number (int64 [n_lines]), heads
+    (uint8 [n_lines][head_bytes], None without head_bytes), consumed, seen."""
+    n, consumed, seen_out = C.c_int64(), C.c_int64(), C.c_int64()
+
+    def call(cap):
+        begin, end, number = (np.zeros(cap, dtype=np.int64) for _ in range(3))
+        heads = np.zeros((cap, head_bytes), dtype=np.uint8) if head_bytes else None
+        rc = lib().garlic_text_lines(ctx.handle, _vp(text_ptr), int(text_bytes), int(bool(last)), int(seen), int(head_bytes), cap,
+                                     _ptr(begin, _i64p), _ptr(end, _i64p), _ptr(number, _i64p),
+                                     _vp(heads.ctypes.data) if head_bytes and cap else None, C.byref(n), C.byref(consumed), C.byref(seen_out))
+        return rc, begin, end, number, heads
+
+    rc, begin, end, number, heads = call(0 if capacity is None else int(capacity))
+    if rc == ERR_RANGE and capacity is None:
+        rc, begin, end, number, heads = call(n.value)
+    check(rc)
+    k = n.value
+    return {"begin": begin[:k], "end": end[:k], "number": number[:k], "heads": None if heads is None else heads[:k],
+            "consumed": consumed.value, "seen": seen_out.value}
 
 
 class Bed:

@@ -34,6 +34,7 @@
 #include "tped_kernels.hpp"
 #include "tgls_kernels.hpp"
 #include "vcf_gl_kernels.hpp"
+#include "bgzf_kernels.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -184,6 +185,16 @@ struct GmmScratch {
     ~GmmScratch() { release(); }
 };
 
+// what garlic_bgzf_inflate and garlic_text_lines keep between calls (bgzf_kernels.hpp): the compressed bytes of a host-buffer
+// call, both offset lists and the statuses; the tile counts, the lines, their heads and the result
+struct BgzfScratch {
+    DevBuf<uint8_t> comp, heads;
+    DevBuf<int64_t> offsets, lines;
+    DevBuf<int32_t> status, tiles;
+    DevBuf<TextLinesResult> res;
+    void release() { comp.release(); heads.release(); offsets.release(); lines.release(); status.release(); tiles.release(); res.release(); }
+};
+
 // lod(), src/garlic-roh.cpp:355-386.  Host arithmetic, host libm: identical to the reference.
 double host_lod(int genotype, double freq, double error)
 {
@@ -252,6 +263,8 @@ struct garlic_ctx {
     GmmScratch gmm;
     int64_t gmm_blocks = 0;
     float gmm_em_ms = 0.f;
+    // garlic_bgzf_inflate and garlic_text_lines: their scratch
+    BgzfScratch bgzf;
 };
 
 static int score_alloc(garlic_ctx *ctx, size_t bytes, void **out);   // pooled score memory (below)
@@ -6326,6 +6339,141 @@ int garlic_device_upload(garlic_ctx *ctx, void *dst, const void *src, int64_t by
     if (!bytes) return GARLIC_OK;
     HIP_TRY(hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return GARLIC_OK;
+}
+
+int garlic_device_download(garlic_ctx *ctx, void *dst, const void *src, int64_t bytes)
+{
+    if (!ctx || !dst || !src) return fail(GARLIC_ERR_INVALID, "context, dst and src are required");
+    if (bytes < 0) return fail(GARLIC_ERR_INVALID, "bytes %lld is negative", (long long)bytes);
+    int rc;
+    if ((rc = set_device(ctx))) return rc;
+    if (!bytes) return GARLIC_OK;
+    HIP_TRY(hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return GARLIC_OK;
+}
+
+int garlic_device_copy(garlic_ctx *ctx, void *dst, const void *src, int64_t bytes)
+{
+    if (!ctx || !dst || !src) return fail(GARLIC_ERR_INVALID, "context, dst and src are required");
+    if (bytes < 0) return fail(GARLIC_ERR_INVALID, "bytes %lld is negative", (long long)bytes);
+    const uintptr_t d = (uintptr_t)dst, f = (uintptr_t)src;
+    if (d < f + (uintptr_t)bytes && f < d + (uintptr_t)bytes && bytes) return fail(GARLIC_ERR_INVALID, "the ranges overlap");
+    int rc;
+    if ((rc = set_device(ctx))) return rc;
+    if (!bytes) return GARLIC_OK;
+    HIP_TRY(hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return GARLIC_OK;
+}
+
+// ---- BGZF text on the device (bgzf_kernels.hpp)
+int garlic_bgzf_inflate(garlic_ctx *ctx, const void *comp, int64_t comp_bytes, const int64_t *block_begin, int64_t nblocks, void *out,
+                        const int64_t *out_begin, int32_t *block_status, int32_t where)
+{
+    if (!ctx || !block_begin || !out_begin) return fail(GARLIC_ERR_INVALID, "context, block_begin and out_begin are required");
+    if (where != GARLIC_HOST && where != GARLIC_DEVICE) return fail(GARLIC_ERR_INVALID, "where must be GARLIC_HOST or GARLIC_DEVICE");
+    if (nblocks < 0 || nblocks >= (1ll << 31) * BGZF_WAVES || comp_bytes < 0)
+        return fail(GARLIC_ERR_INVALID, "nblocks %lld, comp_bytes %lld", (long long)nblocks, (long long)comp_bytes);
+    if (!nblocks) return GARLIC_OK;
+    if (!comp || !out) return fail(GARLIC_ERR_INVALID, "comp and out are required");
+    if (block_begin[0] < 0 || block_begin[nblocks] > comp_bytes || out_begin[0] < 0)
+        return fail(GARLIC_ERR_INVALID, "the blocks must lie inside comp_bytes = %lld, the output ranges at or behind 0", (long long)comp_bytes);
+    for (int64_t b = 0; b < nblocks; b++) {
+        const int64_t m = block_begin[b + 1] - block_begin[b], o = out_begin[b + 1] - out_begin[b];
+        if (m < BGZF_MEMBER_MIN || m > BGZF_MEMBER_MAX || o < 0 || o > BGZF_MEMBER_MAX)
+            return fail(GARLIC_ERR_INVALID, "block %lld: %lld bytes to %lld: a BGZF block has %lld to %lld bytes and inflates to at most %lld",
+                        (long long)b, (long long)m, (long long)o, (long long)BGZF_MEMBER_MIN, (long long)BGZF_MEMBER_MAX, (long long)BGZF_MEMBER_MAX);
+    }
+    int rc;
+    if ((rc = set_device(ctx))) return rc;
+    BgzfScratch &sc = ctx->bgzf;
+    hipStream_t s = ctx->stream;
+    const uint8_t *d_comp = reinterpret_cast<const uint8_t *>(comp);
+    if (where == GARLIC_HOST) {
+        if ((rc = sc.comp.reserve((size_t)comp_bytes))) return rc;
+        HIP_TRY(hipMemcpyAsync(sc.comp.p, comp, (size_t)comp_bytes, hipMemcpyHostToDevice, s));
+        d_comp = sc.comp.p;
+    }
+    const size_t n1 = (size_t)nblocks + 1;
+    if ((rc = sc.offsets.reserve(2 * n1)) || (rc = sc.status.reserve((size_t)nblocks))) return rc;
+    HIP_TRY(hipMemcpyAsync(sc.offsets.p, block_begin, sizeof(int64_t) * n1, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(sc.offsets.p + n1, out_begin, sizeof(int64_t) * n1, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(bgzf_inflate_kernel, dim3((unsigned)((nblocks + BGZF_WAVES - 1) / BGZF_WAVES)), dim3(WAVE * BGZF_WAVES), 0, s, d_comp,
+                       sc.offsets.p, nblocks, reinterpret_cast<uint8_t *>(out), sc.offsets.p + n1, sc.status.p);
+    HIP_TRY(hipGetLastError());
+    std::vector<int32_t> own;                                 // only a caller without block_status needs it
+    if (!block_status) own.resize((size_t)nblocks);
+    int32_t *status = block_status ? block_status : own.data();
+    HIP_TRY(hipMemcpyAsync(status, sc.status.p, sizeof(int32_t) * (size_t)nblocks, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int64_t b = 0; b < nblocks; b++)
+        if (status[(size_t)b]) {
+            static const char *const what[] = {"", "bad block type or header", "bad code lengths", "bad symbol", "bad distance", "input ended",
+                                               "output full", "output short", "bad CRC32"};
+            const int32_t c = status[(size_t)b];
+            return fail(GARLIC_ERR_INVALID, "BGZF block %lld (at byte %lld): status %d (%s)", (long long)b, (long long)block_begin[b], (int)c,
+                        c > 0 && c < 9 ? what[c] : "?");
+        }
+    return GARLIC_OK;
+}
+
+int garlic_text_lines(garlic_ctx *ctx, const void *text, int64_t text_bytes, int32_t last, int64_t seen, int64_t head_bytes,
+                      int64_t capacity, int64_t *begin, int64_t *end, int64_t *number, void *heads, int64_t *n_lines,
+                      int64_t *consumed, int64_t *seen_out)
+{
+    if (!ctx || !n_lines || !consumed || !seen_out) return fail(GARLIC_ERR_INVALID, "context, n_lines, consumed and seen_out are required");
+    if (text_bytes < 0 || text_bytes >= (1ll << 31) || capacity < 0 || (capacity > 0 && (!begin || !end || !number)))
+        return fail(GARLIC_ERR_INVALID, "text_bytes %lld must be below 2^31; begin, end and number need room for capacity %lld",
+                    (long long)text_bytes, (long long)capacity);
+    if (heads && (head_bytes < 1 || head_bytes > (1 << 20))) return fail(GARLIC_ERR_INVALID, "head_bytes %lld: 1 to 2^20", (long long)head_bytes);
+    *n_lines = 0;
+    *consumed = 0;
+    *seen_out = seen;
+    if (!text_bytes) return GARLIC_OK;
+    if (!text) return fail(GARLIC_ERR_INVALID, "text is required");
+    int rc;
+    if ((rc = set_device(ctx))) return rc;
+    BgzfScratch &sc = ctx->bgzf;
+    hipStream_t s = ctx->stream;
+    const uint8_t *d_text = reinterpret_cast<const uint8_t *>(text);
+    const int64_t tiles = (text_bytes + (int64_t)((uintptr_t)text & 15) + TEXT_LINES_TILE - 1) / TEXT_LINES_TILE;
+    if ((rc = sc.tiles.reserve((size_t)(2 * tiles))) || (rc = sc.res.reserve(1))) return rc;
+    int32_t *t_newlines = sc.tiles.p, *t_full = sc.tiles.p + tiles;
+    hipLaunchKernelGGL(text_lines_count_kernel, dim3((unsigned)tiles), dim3(TEXT_PASS_PIECES), 0, s, d_text, text_bytes, t_newlines, t_full);
+    hipLaunchKernelGGL(text_lines_scan_kernel, dim3(1), dim3(TEXT_PASS_PIECES), 0, s, t_newlines, t_full, tiles, sc.res.p);
+    HIP_TRY(hipGetLastError());
+    TextLinesResult res = {};
+    HIP_TRY(hipMemcpyAsync(&res, sc.res.p, sizeof res, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const int64_t cap = res.lines + 1;                        // the lines that end at a '\n', and a last one that does not
+    if ((rc = sc.lines.reserve((size_t)(3 * cap)))) return rc;
+    int64_t *d_begin = sc.lines.p, *d_end = d_begin + cap, *d_number = d_end + cap;
+    hipLaunchKernelGGL(text_lines_write_kernel, dim3((unsigned)tiles), dim3(TEXT_PASS_PIECES), 0, s, d_text, text_bytes, (int)(last != 0), seen,
+                       t_newlines, t_full, res.newlines, cap, d_begin, d_end, d_number, sc.res.p);
+    const bool want_heads = heads && cap <= capacity + 1;
+    if (want_heads) {
+        if ((rc = sc.heads.reserve((size_t)(cap * head_bytes)))) return rc;
+        const int64_t blocks = std::min<int64_t>((cap * head_bytes + 255) / 256, 8 * (int64_t)ctx->n_cu);
+        hipLaunchKernelGGL(text_heads_kernel, dim3((unsigned)blocks), dim3(256), 0, s, d_text, d_begin, d_end, cap, sc.res.p, head_bytes,
+                           text_bytes, sc.heads.p);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&res, sc.res.p, sizeof res, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *n_lines = res.lines;
+    *consumed = res.consumed;
+    *seen_out = seen + res.taken;
+    if (res.lines > capacity) return fail(GARLIC_ERR_RANGE, "the slab holds %lld lines, the arrays %lld", (long long)res.lines, (long long)capacity);
+    if (res.lines) {
+        const size_t nb = sizeof(int64_t) * (size_t)res.lines;
+        HIP_TRY(hipMemcpyAsync(begin, d_begin, nb, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(end, d_end, nb, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(number, d_number, nb, hipMemcpyDeviceToHost, s));
+        if (heads) HIP_TRY(hipMemcpyAsync(heads, sc.heads.p, (size_t)(res.lines * head_bytes), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
     return GARLIC_OK;
 }
 

@@ -2,6 +2,7 @@
 #include "garlic_host.hpp"
 #include "vcf_lines.hpp"
 #include "tped_lines.hpp"
+#include "bgzf_slabs.hpp"
 
 #include "../../include/garlic_hip.h"
 
@@ -756,8 +757,9 @@ void loadBedData(const std::string &bedfile, const std::string &bimfile, const s
 
 // One slab of loadVcfData into obj: rows [row, row + n) from the lines lb (n + 1 offsets; ends: where each stops; number: its
 // line in the file) of the text that stands on obj's device at d_text and in host memory at h_text.  A row the device defers
-// is parsed by vcf::parseGlValues; a refused line ends the run.  false: the 65,537th distinct raw value.
-static bool vcfGlSlab(const TglsFile *f, garlic_tgls *obj, const void *d_text, const char *h_text, int64_t text_bytes,
+// is parsed by vcf::parseGlValues -- from h_text, or where that is NULL (the text stands on the devices only) from the line
+// fetched through ctx; a refused line ends the run.  false: the 65,537th distinct raw value.
+static bool vcfGlSlab(const TglsFile *f, garlic_ctx *ctx, garlic_tgls *obj, const void *d_text, const char *h_text, int64_t text_bytes,
                       const std::vector<int64_t> &lb, const std::vector<int64_t> &ends, const std::vector<int64_t> &number, long long row)
 {
     const int64_t n = (int64_t)lb.size() - 1;
@@ -777,11 +779,17 @@ static bool vcfGlSlab(const TglsFile *f, garlic_tgls *obj, const void *d_text, c
         }
     check(rc, "garlic_tgls_set_rows_vcf");
     std::vector<double> vals((size_t)f->fileInd);
+    std::vector<char> fetched;
     std::string err;
     for (int64_t r = 0; r < n; r++) {
         if (status[(size_t)(2 * r)] != GARLIC_TGLS_DEFERRED) continue;
         int sample = -1;
-        if (!vcf::parseGlValues(h_text + lb[(size_t)r], (size_t)(ends[(size_t)r] - lb[(size_t)r]), f->vcfKey, f->fileInd, nullptr, vals.size(), missing,
+        const size_t len = (size_t)(ends[(size_t)r] - lb[(size_t)r]);
+        if (!h_text) {
+            fetched.resize(len);
+            check(garlic_device_download(ctx, fetched.data(), (const char *)d_text + lb[(size_t)r], (int64_t)len), "garlic_device_download");
+        }
+        if (!vcf::parseGlValues(h_text ? h_text + lb[(size_t)r] : fetched.data(), len, f->vcfKey, f->fileInd, nullptr, vals.size(), missing,
                                 vals.data(), sample, err))
             refuseVcfLine(f, number[(size_t)r], sample, err);
         rc = garlic_tgls_set_rows_values(obj, vals.data(), (int64_t)vals.size(), row + r, 1, GARLIC_HOST);
@@ -829,33 +837,84 @@ static bool slabsOrFail(const std::string &path, size_t slabBytes, const std::st
 struct VcfDeviceSlabs {
     struct One { garlic_ctx *ctx; garlic_tgls *obj; void *text; };
     std::vector<One> on;
+    bool borrowed = false;         // the buffers are a bgzf::DeviceSlabs': named per slab, not freed here
     void release()
     {
-        for (One &o : on) garlic_device_free(o.ctx, o.text);
+        for (One &o : on)
+            if (!borrowed) garlic_device_free(o.ctx, o.text);
         on.clear();
     }
     ~VcfDeviceSlabs() { release(); }
 };
 
-void loadVcfData(const std::string &vcffile, bool phased, bool snpsOnly, std::vector<std::string> &samples, int &numLoci, int &numInd,
-                 std::vector<HapData *> **hapDataByChr, std::vector<MapData *> **mapDataByChr, std::vector<FreqData *> **freqDataByChr,
-                 int nresample, unsigned long long resampleSeed, int device, VcfGlRequest *gl)
+// One slab of either source, as the two walks of loadVcfData see it: the lines, and their text in host memory (host) or on the
+// devices with the lines' heads on the host (dev).
+struct VcfSlab {
+    const std::vector<int64_t> &begin, &end, &number;
+    int64_t have;
+    const char *host;
+    const bgzf::DeviceSlab *dev;
+};
+
+// loadVcfData through the host reader (onDevice false: any file) or through bgzf::DeviceSlabs (a BGZF file inflated on the
+// devices).  false, on the device path alone: the file is no BGZF file throughout or holds a bad block; refusal says which,
+// nothing has been handed out, and the host reader can take the file.
+static bool loadVcfDataThrough(bool onDevice, const std::string &vcffile, bool phased, bool snpsOnly, std::vector<std::string> &samples,
+                               int &numLoci, int &numInd, std::vector<HapData *> **hapDataByChr, std::vector<MapData *> **mapDataByChr,
+                               std::vector<FreqData *> **freqDataByChr, int nresample, unsigned long long resampleSeed, int device,
+                               VcfGlRequest *gl, std::string &refusal)
 {
     std::unique_ptr<BedFile, void (*)(BedFile *)> b(new BedFile, closeBedFile);
     b->path = vcffile;
     b->phased = phased;
-    const size_t SLAB = (size_t)64 << 20;
+    size_t SLAB = (size_t)64 << 20;
+    const int64_t HEAD = 512;              // bytes of every line that reach the host on the device path
+    if (onDevice)
+        if (const char *e = getenv("GARLIC_BGZF_SLAB_BYTES")) SLAB = (size_t)std::max<long long>(atoll(e), 65536);   // (tests: many slabs of a small file)
+    int64_t blocksInflated = 0;
+    // the walk over the file's slabs by either source; false: the device source refused the file
+    auto slabsOf = [&](const std::vector<int> &devices, const std::string &longLine, auto onSlab) -> bool {
+        if (!onDevice) {
+            slabsOrFail(vcffile, SLAB, longLine, [&](const text::Reader &rd, const text::SlabLines &cut, size_t) {
+                onSlab(VcfSlab{cut.begin, cut.end, cut.number, (int64_t)rd.have, rd.slab.data(), nullptr});
+                return true;
+            });
+            return true;
+        }
+        bgzf::DeviceSlabs src;
+        if (!src.open(devices, (int64_t)SLAB)) fail(vcffile + ": " + src.error);
+        const bgzf::DeviceSlabsEnd end = src.forEach(vcffile, HEAD, [&](const bgzf::DeviceSlab &s) {
+            onSlab(VcfSlab{s.begin, s.end, s.number, s.have, nullptr, &s});
+            return true;
+        });
+        blocksInflated = src.blocks / (int64_t)devices.size();
+        if (end == bgzf::DEV_NOT_BGZF || end == bgzf::DEV_BAD_BLOCK) { refusal = src.error; return false; }
+        if (end == bgzf::DEV_LONG_LINE) fail(longLine);
+        if (end != bgzf::DEV_DONE) fail(vcffile + ": " + src.error);
+        return true;
+    };
     // first pass: the header, the nine fixed columns of every data line, and which lines are kept -- the row count that
-    // garlic_bed_create needs
+    // garlic_bed_create needs.  On the device path a line's head serves where it holds the nine columns; '#CHROM' and a line
+    // whose ninth tab lies behind the head are fetched whole.
     std::vector<char> kept;                // per data line
     samples.clear();
     {
         std::string err;
-        slabsOrFail(vcffile, SLAB, vcffile + ": a line longer than 64 MB", [&](const text::Reader &rd, const text::SlabLines &cut, size_t) {
-            for (size_t k = 0; k < cut.begin.size(); k++) {
-                const char *line = rd.slab.data() + cut.begin[k];
-                const size_t len = (size_t)(cut.end[k] - cut.begin[k]);
-                const std::string where = "line " + std::to_string(cut.number[k]) + " of " + vcffile + ": ";
+        std::vector<char> fetched;
+        const bool read = slabsOf({device}, vcffile + ": a line longer than 64 MB", [&](const VcfSlab &s) {
+            for (size_t k = 0; k < s.begin.size(); k++) {
+                const char *line = s.host ? s.host + s.begin[k] : s.dev->head(k);
+                size_t len = s.host ? (size_t)(s.end[k] - s.begin[k]) : s.dev->headLen(k);
+                const std::string where = "line " + std::to_string(s.number[k]) + " of " + vcffile + ": ";
+                if (s.dev && !s.dev->whole(k)) {
+                    size_t tabs = 0;
+                    for (size_t i = 0; i < len && tabs < 9; i++) tabs += line[i] == '\t';
+                    if (line[0] == '#' ? (len >= 6 && memcmp(line, "#CHROM", 6) == 0) : tabs < 9) {
+                        if (!s.dev->fetch(k, fetched)) fail(where + garlic_hip_last_error());
+                        line = fetched.data();
+                        len = fetched.size();
+                    }
+                }
                 if (line[0] == '#') {
                     if (len >= 6 && memcmp(line, "#CHROM", 6) == 0 && !vcf::parseHeader(line, len, samples, err)) fail(where + err);
                     continue;
@@ -870,8 +929,8 @@ void loadVcfData(const std::string &vcffile, bool phased, bool snpsOnly, std::ve
                 b->chr.push_back(site.chr); b->name.push_back(site.name); b->gpos.push_back(0.0); b->ppos.push_back((double)site.ppos);
                 b->a1.push_back(site.a1); b->a2.push_back(site.a2);
             }
-            return true;
         });
+        if (!read) return false;
     }
     if (samples.empty()) fail("no #CHROM line in " + vcffile);
     b->nind = (int)samples.size();
@@ -882,9 +941,12 @@ void loadVcfData(const std::string &vcffile, bool phased, bool snpsOnly, std::ve
     // second pass: the text to the device in slabs, one parse call per slab
     garlic_bed *bed = createParsedImage(b.get(), device);
     // the likelihoods from the same slabs: one object of every sample's column per distinct device, and a buffer there that
-    // the slab is uploaded to once; on the loader's own device the genotype parse reads that buffer too
+    // the slab is uploaded to once (on the device path: the source's own buffer, where the slab was inflated); on the loader's
+    // own device the genotype parse reads that buffer too
     std::unique_ptr<TglsFile, void (*)(TglsFile *)> glFile(nullptr, closeTglsFile);
     VcfDeviceSlabs slabs;          // (behind glFile: its buffers go before the contexts they came from)
+    slabs.borrowed = onDevice;
+    std::vector<int> devs{device};
     if (gl) {
         gl->file = nullptr;
         gl->overflow = false;
@@ -900,7 +962,6 @@ void loadVcfData(const std::string &vcffile, bool phased, bool snpsOnly, std::ve
         glFile->vcfMissing = gl->missing;
         glFile->vcfSnpsOnly = snpsOnly;
         glFile->vcfSamples = samples;
-        std::vector<int> devs{device};
         for (int d : gl->devices)
             if (std::find(devs.begin(), devs.end(), d) == devs.end()) devs.push_back(d);
         for (int d : devs) {
@@ -912,7 +973,7 @@ void loadVcfData(const std::string &vcffile, bool phased, bool snpsOnly, std::ve
             check(garlic_tgls_create(ctx, b->nrows, b->nind, glFile->cols.data(), b->nind, &obj), "garlic_tgls_create");
             glFile->objects.back().tgls = obj;
             void *text = nullptr;
-            check(garlic_device_alloc(ctx, (int64_t)SLAB + 16, &text), "garlic_device_alloc");      // (the last piece lies inside)
+            if (!onDevice) check(garlic_device_alloc(ctx, (int64_t)SLAB + 16, &text), "garlic_device_alloc");      // (the last piece lies inside)
             slabs.on.push_back({ctx, obj, text});
         }
     }
@@ -922,30 +983,34 @@ void loadVcfData(const std::string &vcffile, bool phased, bool snpsOnly, std::ve
         std::vector<int64_t> lb, number, ends;
         std::vector<int32_t> status;
         // (a line longer than the slab: the first pass met none)
-        slabsOrFail(vcffile, SLAB, vcffile + " changed while it was read", [&](const text::Reader &rd, const text::SlabLines &cut, size_t) {
+        const bool read = slabsOf(devs, vcffile + " changed while it was read", [&](const VcfSlab &s) {
             lb.clear();
             number.clear();
             ends.clear();
             int64_t last_end = 0;
-            for (size_t k = 0; k < cut.begin.size(); k++) {
-                if (rd.slab[(size_t)cut.begin[k]] == '#') continue;
+            for (size_t k = 0; k < s.begin.size(); k++) {
+                if ((s.host ? s.host[(size_t)s.begin[k]] : s.dev->head(k)[0]) == '#') continue;
                 if (data_line >= kept.size()) fail(vcffile + " changed while it was read");
                 if (!kept[data_line++]) continue;
-                lb.push_back(cut.begin[k]);
-                number.push_back(cut.number[k]);
-                ends.push_back(cut.end[k]);
-                last_end = cut.end[k];
+                lb.push_back(s.begin[k]);
+                number.push_back(s.number[k]);
+                ends.push_back(s.end[k]);
+                last_end = s.end[k];
             }
-            if (lb.empty()) return true;
+            if (lb.empty()) return;
             const int64_t n = (int64_t)lb.size();
             if (row + n > b->nrows) fail(vcffile + " changed while it was read");
             lb.push_back(last_end);
             status.assign((size_t)(2 * n), 0);
             // one upload per device; the first buffer stands on the image's device and serves both parses
-            for (auto &o : slabs.on) check(garlic_device_upload(o.ctx, o.text, rd.slab.data(), (int64_t)rd.have), "garlic_device_upload");
-            const int rc = slabs.on.empty()
-                               ? garlic_bed_set_rows_vcf(bed, rd.slab.data(), (int64_t)rd.have, lb.data(), row, n, status.data(), GARLIC_HOST)
-                               : garlic_bed_set_rows_vcf(bed, (const char *)slabs.on[0].text, (int64_t)rd.have, lb.data(), row, n, status.data(),
+            for (size_t k = 0; k < slabs.on.size(); k++) {
+                if (s.dev) slabs.on[k].text = s.dev->text[k];
+                else check(garlic_device_upload(slabs.on[k].ctx, slabs.on[k].text, s.host, s.have), "garlic_device_upload");
+            }
+            const int rc = s.dev ? garlic_bed_set_rows_vcf(bed, s.dev->text[0], s.have, lb.data(), row, n, status.data(), GARLIC_DEVICE)
+                           : slabs.on.empty()
+                               ? garlic_bed_set_rows_vcf(bed, s.host, s.have, lb.data(), row, n, status.data(), GARLIC_HOST)
+                               : garlic_bed_set_rows_vcf(bed, (const char *)slabs.on[0].text, s.have, lb.data(), row, n, status.data(),
                                                          GARLIC_DEVICE);
             if (rc == GARLIC_ERR_INVALID) {
                 for (int64_t r = 0; r < n; r++)
@@ -957,23 +1022,44 @@ void loadVcfData(const std::string &vcffile, bool phased, bool snpsOnly, std::ve
             }
             check(rc, "garlic_bed_set_rows_vcf");
             for (size_t k = 0; k < slabs.on.size(); k++)
-                if (!vcfGlSlab(glFile.get(), slabs.on[k].obj, slabs.on[k].text, rd.slab.data(), (int64_t)rd.have, lb, ends, number, row)) {
-                    // the 65,537th distinct raw value: the objects are of no use; the genotypes go on from host text
+                if (!vcfGlSlab(glFile.get(), slabs.on[k].ctx, slabs.on[k].obj, slabs.on[k].text, s.host, s.have, lb, ends, number, row)) {
+                    // the 65,537th distinct raw value: the objects are of no use; the genotypes go on from the same text
                     slabs.release();
                     glFile.reset();
                     gl->overflow = true;
                     break;
                 }
             row += n;
-            return true;
         });
+        if (!read) return false;
         if (row != b->nrows) fail(vcffile + " changed while it was read");
     }
     slabs.release();
     if (gl && !gl->overflow) gl->file = glFile.release();
+    if (onDevice) fprintf(stderr, "%s: BGZF, %lld blocks inflated on the device\n", vcffile.c_str(), (long long)blocksInflated);
     b->refs = 1;
     fetchParsedRows(b.get(), bed);
     loadBedFile(b.release(), numLoci, numInd, hapDataByChr, mapDataByChr, freqDataByChr, nresample, resampleSeed, device);
+    return true;
+}
+
+// A BGZF file is inflated and cut into lines on the devices when GARLIC_BGZF_DEVICE_INFLATE=1 asks for it (opt-in: the load
+// phase has not been timed against the host reader); GARLIC_BGZF_HOST_INFLATE=1 keeps the host reader whatever else is set.
+// A file that stops being BGZF part-way or holds a block with a bad status is read again by the host reader, with one note.
+void loadVcfData(const std::string &vcffile, bool phased, bool snpsOnly, std::vector<std::string> &samples, int &numLoci, int &numInd,
+                 std::vector<HapData *> **hapDataByChr, std::vector<MapData *> **mapDataByChr, std::vector<FreqData *> **freqDataByChr,
+                 int nresample, unsigned long long resampleSeed, int device, VcfGlRequest *gl)
+{
+    auto set = [](const char *name) { const char *e = getenv(name); return e && *e && strcmp(e, "0") != 0; };
+    std::string refusal;
+    if (set("GARLIC_BGZF_DEVICE_INFLATE") && !set("GARLIC_BGZF_HOST_INFLATE") && bgzf::isBgzf(vcffile)) {
+        if (loadVcfDataThrough(true, vcffile, phased, snpsOnly, samples, numLoci, numInd, hapDataByChr, mapDataByChr, freqDataByChr, nresample,
+                               resampleSeed, device, gl, refusal))
+            return;
+        fprintf(stderr, "%s: %s; the file is read again by the host reader\n", vcffile.c_str(), refusal.c_str());
+    }
+    loadVcfDataThrough(false, vcffile, phased, snpsOnly, samples, numLoci, numInd, hapDataByChr, mapDataByChr, freqDataByChr, nresample,
+                       resampleSeed, device, gl, refusal);
 }
 
 bool loadTPEDDataOnDevice(const std::string &tpedfile, int &numLoci, int &numInd, std::vector<HapData *> **hapDataByChr,

@@ -68,7 +68,8 @@ extern "C" {
  *    (likewise); garlic_tgls, garlic_tgls_create, garlic_tgls_set_rows_text, garlic_tgls_set_rows_values, garlic_tgls_get_rows,
  *    garlic_tgls_info, garlic_tgls_count_values, garlic_tgls_get_values, garlic_tgls_destroy, garlic_panel_set_gl_tgls, GARLIC_TGLS_OK / _DEFERRED / _FEW_COLUMNS /
  *    _MANY_COLUMNS / _RAW, GARLIC_ERR_RANGE (likewise); garlic_bed_set_rows_tped, GARLIC_TPED_*, garlic_bed_set_census (likewise);
- *    garlic_tgls_set_rows_vcf, GARLIC_TGLS_VCF_NO_KEY / _NO_VALUE, garlic_device_upload (likewise) */
+ *    garlic_tgls_set_rows_vcf, GARLIC_TGLS_VCF_NO_KEY / _NO_VALUE, garlic_device_upload (likewise); garlic_bgzf_inflate,
+ *    GARLIC_BGZF_*, garlic_text_lines, garlic_device_download, garlic_device_copy (likewise) */
 #define GARLIC_HIP_ABI_VERSION 8
 
 #define GARLIC_OK 0
@@ -1156,6 +1157,61 @@ int garlic_device_free(garlic_ctx *ctx, void *ptr);
  * text on the device and hands it to several where = GARLIC_DEVICE calls (garlic_bed_set_rows_vcf and
  * garlic_tgls_set_rows_vcf on one upload). */
 int garlic_device_upload(garlic_ctx *ctx, void *dst, const void *src, int64_t bytes);
+/* the twin: bytes from device memory of the context's device into host memory; returns when they are there */
+int garlic_device_download(garlic_ctx *ctx, void *dst, const void *src, int64_t bytes);
+/* bytes from device memory to device memory of the context's device, ranges that do not overlap (GARLIC_ERR_INVALID if they
+ * do); returns when they are there.  The tail of a slab of text moves to the front of the next one with it. */
+int garlic_device_copy(garlic_ctx *ctx, void *dst, const void *src, int64_t bytes);
+
+/* BGZF text on the device (csrc/inflate.hpp, csrc/bgzf_kernels.hpp).
+ *
+ * garlic_bgzf_inflate: nblocks BGZF blocks (gzip members with a BC subfield, at most 65,536 bytes each and at most 65,536
+ * inflated) to device memory, one wave per block.  Block b is comp[block_begin[b], block_begin[b + 1]), header and footer
+ * included, and inflates to out[out_begin[b], out_begin[b + 1]): out_begin holds the prefix sums of the footers' ISIZEs.
+ * comp is host memory (GARLIC_HOST: uploaded into context scratch) or device memory; block_begin, out_begin and
+ * block_status (nblocks entries, may be NULL) are host arrays; out is device memory of out_begin[nblocks] bytes.
+ * GARLIC_ERR_INVALID without a launch: a NULL argument, nblocks < 0, lists that do not ascend, a member of fewer than 28 or
+ * more than 65,536 bytes, an output range of more than 65,536.  Every block gets a status:
+ *     GARLIC_BGZF_OK
+ *     GARLIC_BGZF_BAD_BLOCK_TYPE    block type 3, stored lengths that do not complement; a header that is not 1F 8B 08 04.  The
+ *                                   device takes the deflate data from 12 + XLEN and does NOT look for the BC subfield or compare
+ *                                   BSIZE: the caller's lists say where a member ends (bgzf::walk of host/bgzf_blocks.hpp checks both)
+ *     GARLIC_BGZF_BAD_CODE_LENGTHS  an over-subscribed or incomplete set of code lengths, where zlib refuses it
+ *     GARLIC_BGZF_BAD_SYMBOL        a code that no symbol has, or a symbol outside the alphabet
+ *     GARLIC_BGZF_BAD_DISTANCE      a distance that reaches in front of the block's own output
+ *     GARLIC_BGZF_INPUT_ENDED       the deflate data ends inside a code
+ *     GARLIC_BGZF_OUTPUT_FULL       more bytes than the output range (than ISIZE)
+ *     GARLIC_BGZF_OUTPUT_SHORT      fewer
+ *     GARLIC_BGZF_BAD_CRC           the CRC32 of the bytes is not the footer's; deflate data left over behind the final block
+ * If any is non-zero the call returns GARLIC_ERR_INVALID and garlic_hip_last_error names the lowest such block; the bytes of
+ * the clean blocks are written, those of a bad block are unspecified inside its own range, and nothing outside the ranges
+ * is touched.  The call returns when the statuses are on the host. */
+#define GARLIC_BGZF_OK 0
+#define GARLIC_BGZF_BAD_BLOCK_TYPE 1
+#define GARLIC_BGZF_BAD_CODE_LENGTHS 2
+#define GARLIC_BGZF_BAD_SYMBOL 3
+#define GARLIC_BGZF_BAD_DISTANCE 4
+#define GARLIC_BGZF_INPUT_ENDED 5
+#define GARLIC_BGZF_OUTPUT_FULL 6
+#define GARLIC_BGZF_OUTPUT_SHORT 7
+#define GARLIC_BGZF_BAD_CRC 8
+int garlic_bgzf_inflate(garlic_ctx *ctx, const void *comp, int64_t comp_bytes, const int64_t *block_begin, int64_t nblocks, void *out,
+                        const int64_t *out_begin, int32_t *block_status, int32_t where);
+
+/* garlic_text_lines: the line index of a slab of device text, text[0, text_bytes), text_bytes < 2^31: what the host's
+ * SlabLines::take(slab, n, last) gives on the same bytes.  Line k of the lines that are not blank (empty, or a lone '\r')
+ * and complete in the slab -- the final one needs no '\n' when `last` -- is text[begin[k], end[k]), end[k] its '\n' or
+ * text_bytes; number[k] = seen + its 1-based number in the slab, blank lines counted.  heads (may be NULL; head_bytes >= 1
+ * then): [capacity][head_bytes] bytes, row k = the first head_bytes bytes of line k, zeros behind a shorter line.
+ * begin, end, number and heads are host arrays with room for `capacity` lines.  The caller cannot know the count: the call
+ * always sets *n_lines, *consumed (the bytes those lines and the blank ones between them take; the caller carries the rest to
+ * the next slab) and *seen_out (seen + the lines taken, blank ones included); when *n_lines > capacity it returns
+ * GARLIC_ERR_RANGE with the arrays untouched, and the same call with that much room succeeds.  Scratch (8 bytes per 4 KB of
+ * text, 24 bytes + head_bytes per line) stays with the context. */
+int garlic_text_lines(garlic_ctx *ctx, const void *text, int64_t text_bytes, int32_t last, int64_t seen, int64_t head_bytes,
+                      int64_t capacity, int64_t *begin, int64_t *end, int64_t *number, void *heads, int64_t *n_lines,
+                      int64_t *consumed, int64_t *seen_out);
+
 int garlic_device_alloc_stats(garlic_ctx *ctx, int64_t *live_bytes, int64_t *pooled_bytes, int64_t *reserved_bytes);
 int garlic_device_trim(garlic_ctx *ctx);   /* idle pooled buffers give their memory back now (the library does this itself
                                               when one of its own allocations runs out of memory) */
